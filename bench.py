@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: fused bundle-entropy inference of the Bibsonomy-shaped PICNN.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
     N > 1 from a plain shell: bench.py starts its own N ranks (self_launch: one child process per GPU, rank 0 prints);
     under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` (WORLD_SIZE set)
     it is one of the ranks.
@@ -20,6 +20,8 @@ times configs[2] (completion conv PICNN, batch 256) at nIter = 5 and 30 and `ext
 Inputs (context, weights, y0) are resident in HBM before the timed region.
 
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the definitions of `roofline` and `cpu_baseline`.
+--dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy (write_outputs); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 The control flow (sharding, timing, max over ranks, JSON) is `run()`; the HIP workload is injected into it so
 that tests/test_bench_flow.py can drive the same code on CPU with gloo and a stub solver.
 """
@@ -133,6 +135,28 @@ class HipWorkload:
 
     def sync(self):
         torch.cuda.synchronize()
+
+    @staticmethod
+    def outputs(res, y_all):
+        """--dump-outputs: what a caller of the timed path receives from a step, one row per sample, in order of priority:
+        y* (the gathered global batch when N > 1), then for this rank's shard the outer iterations, the number of active
+        cuts and the active bundle in its order -- the reference tuple's lam, b, A, xs (BundleResult.as_reference_tuple)
+        as [B, slots(, n)] arrays, zero beyond each sample's count."""
+        B = res.state.B
+        cnt = res.count[:B].long()
+        T = res.active.shape[1]
+        live = torch.arange(T, device=cnt.device)[None, :] < cnt[:, None]
+        slot = torch.where(live, res.active[:B].long(), torch.zeros_like(cnt)[:, None]).clamp_(0, T - 1)
+
+        def in_bundle_order(a):
+            if a.dim() == 2:
+                return torch.where(live, a[:B].gather(1, slot), torch.zeros((), dtype=a.dtype, device=a.device))
+            rows = a[:B].gather(1, slot[:, :, None].expand(-1, -1, a.shape[2]))
+            return torch.where(live[:, :, None], rows, torch.zeros((), dtype=a.dtype, device=a.device))
+
+        out = {"y": y_all, "n_iters": res.n_iters[:B], "count": cnt, "lam": in_bundle_order(res.lam),
+               "b": in_bundle_order(res.h), "A": in_bundle_order(res.G), "xs": in_bundle_order(res.ys)}
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def kernel_for(self, n_iter):
         """Name of the kernel icnn_be_solve_fc dispatches for this rank's shard (be_api.hip)."""
@@ -496,6 +520,42 @@ def timed_steps(wl, n_iter, steps, warmup, rank, world, gather_dst, with_events)
 
 
 TIMING_DETAIL = {}      # per-rank solve / gather milliseconds of the last timed_steps call (events on the launch stream)
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> array with one row per sample, in order of priority) as
+    out_dir/<name>.npy, float32 kept, everything else as float64.  An array that does not fit in what is left of `limit`
+    bytes (.npy headers included) is written for a fixed, seeded subset of its rows, whose indices go to
+    out_dir/<name>_rows.npy; once no row fits, the remaining arrays are left out.  The same arrays give the same files.
+    Returns the names written."""
+    header = 1024                                                          # bound on one .npy header
+    os.makedirs(out_dir, exist_ok=True)
+    left = limit
+    written = []
+
+    def save(name, a):
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written.append(name)
+        return os.path.getsize(path)
+
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        rows_path = os.path.join(out_dir, name + "_rows.npy")
+        if a.nbytes + header > left:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8                  # + the row's float64 index
+            keep = min(a.shape[0], max(0, left - 2 * header) // row_bytes)
+            if keep == 0:                                                   # no room left: the rest is not written
+                break
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            left -= save(name + "_rows", rows.astype(np.float64))
+            a = a[rows]
+        elif os.path.exists(rows_path):                                     # from an earlier, larger run into the same DIR
+            os.remove(rows_path)
+        left -= save(name, a)
+    return written
 
 
 def run(args, workload_factory=None, backend=None):
@@ -531,6 +591,9 @@ def run(args, workload_factory=None, backend=None):
         res.raise_on_error()
     if rank == 0 and world > 1:
         assert y_all is not None and y_all.shape[0] == wl.global_batch
+    # the last timed step's result, before the extras below reuse the solver's buffers
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        write_outputs(args.dump_outputs, wl.outputs(res, y_all) if hasattr(wl, "outputs") else {"y": y_all})
 
     out = {
         "metric": "inner-solves/sec (batch x iters), n=159 K=10", "value": value, "unit": "inner-solves/s",
@@ -653,6 +716,10 @@ def parse_args(argv=None):
     ap.add_argument("--one-device", action="store_true",
                     help="every rank uses device 0 (two ranks on a one-GPU box, with --backend gloo: RCCL refuses that)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds before self-launched ranks are killed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all; a seeded subset of rows where that would be exceeded): y*, and for rank 0's "
+                         "shard nIters, the active-cut counts and the active bundle (lam, b, A, xs)")
     return ap.parse_args(argv)
 
 

@@ -8,6 +8,7 @@ import os
 import sys
 import subprocess
 
+import numpy as np
 import pytest
 
 import spawn_util
@@ -136,3 +137,69 @@ def test_self_launch_refuses_more_ranks_than_gpus():
         pytest.skip("this box has the GPUs")
     p = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--c4-steps", "0", "--cpu-sample", "0"], timeout=120)
     assert p.returncode == 2 and "GPU(s) visible" in p.stderr and not p.stdout.strip()
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, one .npy per array, the same files for the same arguments."""
+    p = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--c4-steps", "0", "--cpu-sample", "0",
+                    "--workload", "tests/bench_stub.py:StubWorkload", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len([ln for ln in p.stdout.splitlines() if ln.startswith("{")]) == 1
+    assert sorted(os.listdir(tmp_path / "out")) == ["y.npy"]
+    y = np.load(tmp_path / "out" / "y.npy")
+    assert y.dtype == np.float64 and np.array_equal(y, np.arange(8.0)[:, None].repeat(3, axis=1))
+
+
+def test_write_outputs_keeps_a_seeded_subset_within_the_limit(tmp_path):
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.RandomState(3)
+    arrays = {"y": rng.rand(100, 4), "count": np.arange(100, dtype=np.int32), "A": rng.rand(100, 5, 6).astype(np.float32)}
+    limit = 8000
+    for d in ("a", "b"):
+        names = bench.write_outputs(str(tmp_path / d), arrays, limit=limit)
+        assert names == ["y", "count", "A_rows", "A"]
+        assert sum(os.path.getsize(tmp_path / d / (n + ".npy")) for n in names) <= limit
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), arrays["y"])
+    assert np.load(tmp_path / "a" / "count.npy").dtype == np.float64
+    rows = np.load(tmp_path / "a" / "A_rows.npy").astype(np.int64)
+    assert 0 < rows.size < 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "A.npy"), arrays["A"][rows])
+    # a later run that fits writes the whole array and drops the stale row index
+    assert bench.write_outputs(str(tmp_path / "a"), arrays) == ["y", "count", "A"]
+    assert not os.path.exists(tmp_path / "a" / "A_rows.npy")
+
+
+def test_hip_outputs_put_the_active_bundle_in_its_order():
+    """HipWorkload.outputs on a host-side stand-in of a BundleResult: active[u, :count[u]] picks the slots, in that
+    order; everything past a sample's count is zero."""
+    import types
+
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    B, T, n = 3, 4, 2
+    G = torch.arange(B * T * n, dtype=torch.float32).reshape(B, T, n) + 1
+    ys = G.double() * 10
+    lam = torch.arange(B * T, dtype=torch.float64).reshape(B, T) + 1
+    h = -lam
+    active = torch.tensor([[2, 0, 7, 7], [0, 1, 2, 3], [9, 9, 9, 9]], dtype=torch.int32)
+    count = torch.tensor([2, 4, 0], dtype=torch.int32)
+    res = types.SimpleNamespace(state=types.SimpleNamespace(B=B), count=count, active=active, n_iters=count + 5,
+                                lam=lam, h=h, G=G, ys=ys)
+    y = torch.rand(B, n, dtype=torch.float64)
+    out = bench.HipWorkload.outputs(res, y)
+    assert list(out) == ["y", "n_iters", "count", "lam", "b", "A", "xs"]
+    assert np.array_equal(out["y"], y.numpy()) and np.array_equal(out["count"], [2, 4, 0])
+    assert out["A"].dtype == np.float32 and out["A"].shape == (B, T, n) and out["xs"].dtype == np.float64
+    for u in range(B):
+        for k in range(T):
+            live = k < int(count[u])
+            s = int(active[u, k]) if live else None
+            assert out["lam"][u, k] == (lam[u, s].item() if live else 0.0)
+            assert out["b"][u, k] == (h[u, s].item() if live else 0.0)
+            assert np.array_equal(out["A"][u, k], G[u, s].numpy() if live else np.zeros(n, np.float32))
+            assert np.array_equal(out["xs"][u, k], ys[u, s].numpy() if live else np.zeros(n))

@@ -77,8 +77,16 @@ def test_adam_obs_entry_refuses_mismatched_model_and_context_descriptions():
     for i in range(3):
         cx.w_stage[i] = C.cast(dummy, C.c_void_p)
         cx.b_stage[i] = C.cast(dummy, C.c_void_p)
-    args = (C.byref(m), C.byref(cx), dummy, 0, 10, dummy, dummy, dummy, dummy, None)
-    assert lib.icnn_be_adam_fc_obs(*args) in (0, -3)                 # consistent description: past validation (empty batch;
+    # past validation an empty batch only zeroes `iters` on the device: with a GPU that must be device memory (a host
+    # array makes the memset fail, and the runtime keeps that error for the next launch in the process)
+    gpu = torch.cuda.is_available()
+    iters = torch.full((1,), 7, dtype=torch.int32, device="cuda") if gpu else None
+    args = (C.byref(m), C.byref(cx), dummy, 0, 10, dummy, dummy, C.c_void_p(iters.data_ptr()) if gpu else dummy, dummy, None)
+    if gpu:
+        assert lib.icnn_be_adam_fc_obs(*args) == 0                   # consistent description: past validation
+        assert int(iters.item()) == 0
+    else:
+        assert lib.icnn_be_adam_fc_obs(*args) in (0, -3)             # consistent description: past validation (empty batch;
                                                                      # -3 = the memset of `iters` found no device on this box)
     cx.width[1] = 100                                                # another hidden width: refused
     assert lib.icnn_be_adam_fc_obs(*args) == -1
