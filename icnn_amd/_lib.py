@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libicnn_be.so")
 if os.environ.get("ICNN_BE_LIB"):          # diagnostic: another build of the same ABI (tools/lib_ab.py: same-box A/B of two builds)
     LIB_PATH = os.path.abspath(os.environ["ICNN_BE_LIB"])
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_LAYERS = 8
 MAX_SLOTS = 31
 MAX_ITERS = 64
@@ -35,6 +35,8 @@ FLAG_GLOBAL_BUNDLE = 64
 FLAG_WAVE_PER_SAMPLE = 128
 FLAG_MFMA_CONTRACTION = 256
 LOSS = {"xent": 0, "mse": 1}
+# ICNN_BE_PATH_*: how icnn_be_solve_fc runs a solve (icnn_be_debug_solve_plan)
+PATHS = ["ROWS", "TILE", "TILE_BUDGETED_THEN_ROWS", "ROUNDS_LOCKSTEP", "ROUNDS_SLICED_THEN_ROWS", "ROUNDS_SLICED_EXTRA"]
 ERRORS = {-1: "ICNN_BE_EINVAL (bad argument)", -2: "ICNN_BE_ELIMIT (size beyond a compiled-in limit)",
           -3: "ICNN_BE_ELAUNCH (HIP launch failed)"}
 
@@ -47,7 +49,7 @@ EXPORTS = [
     "icnn_be_fc_context_work_floats", "icnn_be_fc_context", "icnn_be_fc_context_stage", "icnn_be_fc_context_norm", "icnn_be_fc_clamp",
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
-    "icnn_be_debug_fast_math", "icnn_be_debug_trace",
+    "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 
@@ -169,6 +171,8 @@ def load():
     lib.icnn_be_export_active.restype = C.c_int
     lib.icnn_be_debug_fast_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.icnn_be_debug_fast_math.restype = C.c_int
+    lib.icnn_be_debug_solve_plan.argtypes = [C.POINTER(FcModel), C.POINTER(State), C.c_int, C.POINTER(C.c_int * 3)]
+    lib.icnn_be_debug_solve_plan.restype = C.c_int
     lib.icnn_be_debug_profile_phases.restype = C.c_int
     lib.icnn_be_adam_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
@@ -213,3 +217,13 @@ def check(rc, what):
     if rc == -3:
         msg += ": " + load().icnn_be_last_hip_error().decode()
     raise RuntimeError("%s failed: %s" % (what, msg))
+
+
+def solve_plan(model, state, cus=0):
+    """(path name, samples per workgroup, Newton budget per round, value icnn_be_solve_fc returns) for an FcModel and a State
+    (icnn_be_debug_solve_plan; cus < 1: the current device's CU count).  Host arithmetic: no GPU, no buffers needed."""
+    out = (C.c_int * 3)()
+    rc = load().icnn_be_debug_solve_plan(C.byref(model), C.byref(state), cus, C.byref(out))
+    if rc < 0:
+        check(rc, "icnn_be_debug_solve_plan")
+    return (PATHS[rc],) + tuple(out)

@@ -364,11 +364,8 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
                 for (int i = 0; i < m.n_layers; ++i) { r.cr.w_stage[i] = cx->w_stage[i]; r.cr.b_stage[i] = cx->b_stage[i]; }
             }
             r.a.tiles = (batch + per_wg - 1) / per_wg;
+            if (r.a.tiles == 1) return launch_kernel(adam_rows_kernel, dim3(1), dim3(RTHREADS), rows_lds, stream, r);
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
-            if (r.a.tiles == 1) {
-                hipLaunchKernelGGL(adam_rows_kernel, dim3(1), dim3(RTHREADS), rows_lds, stream, r);
-                return hipGetLastError();
-            }
             hipError_t e = hipMemsetAsync(r.a.arrive, 0, sizeof(unsigned) * r.a.tiles, stream);
             if (e != hipSuccess) return e;
             void *params[] = {&r};
@@ -380,11 +377,8 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
     a.red_off = (a.fa.lds_floats + 3) & ~3;
     lds = a.red_off * 4 + (NWAVE + 1) * 8;
     if (lds > 160 * 1024) return hipErrorNotSupported;
+    if (a.tiles == 1) return launch_kernel(adam_fc_kernel, dim3(1), dim3(NTHREADS), lds, stream, a);
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_fc_kernel), lds); e != hipSuccess) return e;
-    if (a.tiles == 1) {
-        hipLaunchKernelGGL(adam_fc_kernel, dim3(1), dim3(NTHREADS), lds, stream, a);
-        return hipGetLastError();
-    }
     int per_cu = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_fc_kernel),
                                                                 NTHREADS, lds);

@@ -18,7 +18,8 @@ int fail(hipError_t e) {
     return e == hipErrorInvalidValue ? ICNN_BE_EINVAL : ICNN_BE_ELAUNCH;
 }
 
-int check_state(const icnn_be_state *st) {
+// everything about a state but its buffers
+int check_shape(const icnn_be_state *st) {
     if (!st) return ICNN_BE_EINVAL;
     if (st->batch < 0 || st->n < 1) return ICNN_BE_EINVAL;
     if (st->slots < 1) return ICNN_BE_EINVAL;
@@ -27,14 +28,27 @@ int check_state(const icnn_be_state *st) {
     if (st->cut_dtype != ICNN_BE_CUT_F32 && st->cut_dtype != ICNN_BE_CUT_F64) return ICNN_BE_EINVAL;
     if (st->variant != ICNN_BE_VARIANT_DUAL && st->variant != ICNN_BE_VARIANT_RL && st->variant != ICNN_BE_VARIANT_PDIPM)
         return ICNN_BE_EINVAL;
-    if (!st->y || !st->G || !st->h || !st->ys || !st->lam || !st->active || !st->count ||
-        !st->n_iters || !st->finished || !st->status || !st->newton_iters || !st->t_next || !st->phase ||
-        !st->skip_fg || !st->pending || !st->park)
-        return ICNN_BE_EINVAL;
     /* a bundle of at least two cuts (one, for a single iteration) must fit the LDS of a workgroup */
     const int fit = icnn_be::dual_rows_fit(st->n, st->slots, st->cut_dtype, st->variant);
     if (fit < (st->slots < 2 ? st->slots : 2)) return ICNN_BE_ELIMIT;
     return 0;
+}
+
+int check_state(const icnn_be_state *st) {
+    if (int rc = check_shape(st)) return rc;
+    if (!st->y || !st->G || !st->h || !st->ys || !st->lam || !st->active || !st->count ||
+        !st->n_iters || !st->finished || !st->status || !st->newton_iters || !st->t_next || !st->phase ||
+        !st->skip_fg || !st->pending || !st->park)
+        return ICNN_BE_EINVAL;
+    return 0;
+}
+
+// what icnn_be_solve_fc requires of a model and a state beyond their buffers
+int check_fc_solve(const icnn_be_fc_model *model, const icnn_be_state *st) {
+    if (int rc = check_shape(st)) return rc;
+    if (!model || st->cut_dtype != ICNN_BE_CUT_F32 || st->n != model->n) return ICNN_BE_EINVAL;
+    if (st->flags & ICNN_BE_FLAG_F64_ENERGY) return ICNN_BE_EINVAL;        /* the fused energies are float32 */
+    return icnn_be::fc_check_model(*model);
 }
 }  // namespace
 
@@ -74,58 +88,84 @@ int device_cus() {
 }  // namespace icnn_be
 
 namespace {
-// rounds of { energy/gradient ; dual step } -- shared by the FC and the conv entry points
-struct NoFinish { hipError_t operator()() const { return hipErrorNotSupported; } };
-// finish_fn: one launch that brings every sample still behind after the T time-sliced rounds to the end at its own pace
-// (hipErrorNotSupported: none available, the stragglers get whole rounds)
-template <typename LaunchFg, typename FinishFn = NoFinish>
-int solve_rounds(const icnn_be_state *st, float *f_work, float *g_work, hipStream_t s, LaunchFg launch_fg,
-                 int lockstep_up_to = 15, FinishFn finish_fn = FinishFn()) {
-    const int T = st->iters > 0 ? st->iters : st->slots;          /* outer iterations */
-    /* the interior-point solve has a fixed cap of 20 iterations per round: nothing to slice */
-    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || st->variant == ICNN_BE_VARIANT_PDIPM ? true
-                          : (st->flags & ICNN_BE_FLAG_TIME_SLICE) ? false : T <= lockstep_up_to;
-    const int slice = 8;   /* Newton updates per round before a sample is parked: covers ~99 % of the solves; measured with the
-                              finishing launch below (4096 samples, nIter 30): budget 4 19.1 ms, 6 12.8, 8 12.1, 12 13.8, 16 14.3 */
-    int rounds = 0;
-    auto one_round = [&](int budget) -> hipError_t {
+constexpr int SLICE_BUDGET = 8;   /* Newton updates per sliced round before a sample is parked ("Solve dispatch") */
+static_assert(ICNN_BE_MAX_ROUNDS >= 2 * ICNN_BE_MAX_ITERS, "a sliced solve's straggler rounds fit st.pending");
+
+int outer_iters(const icnn_be_state &st) { return st.iters > 0 ? st.iters : st.slots; }
+
+/* Sliced rounds without a finishing launch: nIter more unbudgeted rounds for the samples that are behind.  How many are
+   needed -- the largest lag -- is only known on the device, and the host does NOT ask (no synchronisation anywhere in this
+   library; the call stays capturable in a HIP graph); a sample cannot be behind by more than the nIter iterations it has and
+   an unbudgeted round completes one of them, so nIter rounds always suffice ("Solve dispatch"). */
+int sliced_extra_rounds(int T) { return T + (T < ICNN_BE_MAX_ROUNDS - T ? T : ICNN_BE_MAX_ROUNDS - T); }
+
+// `total` rounds of { energy/gradient ; dual step }, shared by the FC and the conv entry points.  The first nIter give each
+// sample `budget` Newton updates (0: lockstep, every round completes an outer iteration of every sample); the rounds beyond
+// them are unbudgeted straggler rounds, closed by a launch that marks anything still behind with ICNN_BE_ST_UNFINISHED
+// (a safety net: unreachable by the argument of sliced_extra_rounds).
+template <typename LaunchFg>
+hipError_t solve_rounds(const icnn_be_state &st, int budget, int total, float *f_work, float *g_work, hipStream_t s,
+                        LaunchFg launch_fg) {
+    const int T = outer_iters(st);
+    for (int r = 0; r < total; ++r) {
         hipError_t e = launch_fg();
+        if (e == hipSuccess) e = icnn_be::launch_dual_step(st, r, r < T ? budget : 0, f_work, g_work, s);
         if (e != hipSuccess) return e;
-        e = icnn_be::launch_dual_step(*st, rounds, budget, f_work, g_work, s);
-        ++rounds;
-        return e;
-    };
-    for (int r = 0; r < T; ++r) {
-        hipError_t e = one_round(lockstep ? 0 : slice);
-        if (e != hipSuccess) return fail(e);
     }
-    if (lockstep) return rounds;
-    /* stragglers -- samples parked in a Newton loop, or behind by the rounds they were parked in.  Whole rounds for them
-       cost a launch pair each and last as long as the longest Newton chain of the round (nIter = 30, 4096 samples: twelve
-       rounds, 6.8 ms of a 14.2 ms solve); the persistent per-sample kernel instead lets each of them run its remaining
-       rounds back to back on a CU of its own (workgroups of finished samples leave at once), without asking the host */
-    if (!(st->flags & ICNN_BE_FLAG_TWO_KERNELS)) {
-        hipError_t e = finish_fn();
-        if (e == hipSuccess) return rounds + 1;
-        if (e != hipErrorNotSupported) return fail(e);
+    return total > T ? icnn_be::launch_mark_unfinished(st, s) : hipSuccess;
+}
+
+struct SolvePlan {
+    int path;      // ICNN_BE_PATH_*, or a negative ICNN_BE_E* code
+    int per_wg;    // samples per workgroup of the persistent kernel (0: launch pairs)
+    int budget;    // Newton updates per sample and round (0: unlimited)
+    int rounds;    // what icnn_be_solve_fc returns
+};
+
+int env_tile_budget() {
+    static const int budget = [] {         /* tuning knob (tools/tile_budget_sweep.py); default measured there */
+        const char *v = std::getenv("ICNN_BE_TILE_BUDGET");
+        return v ? std::atoi(v) : 0;
+    }();
+    return budget;
+}
+
+// The dispatch table of icnn_be_solve_fc: the first row that applies decides.  Pure host arithmetic (no HIP call, no device
+// memory); every fit decision is the layout function's that the launcher uses.  The measurements behind each row are in
+// DESIGN.md, "Solve dispatch".  Results are bit-identical whichever row runs.
+SolvePlan plan_fc_solve(const icnn_be_fc_model &m, const icnn_be_state &st, int cus, int env_budget) {
+    const int T = outer_iters(st), F = st.flags;
+    const bool dual = st.variant == ICNN_BE_VARIANT_DUAL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
+    const bool two = F & ICNN_BE_FLAG_TWO_KERNELS, persistent = F & ICNN_BE_FLAG_PERSISTENT, slice = F & ICNN_BE_FLAG_TIME_SLICE;
+    const bool forced = F & (ICNN_BE_FLAG_TWO_KERNELS | ICNN_BE_FLAG_PERSISTENT | ICNN_BE_FLAG_TIME_SLICE | ICNN_BE_FLAG_LOCKSTEP);
+    /* lockstep rounds by default up to nIter 15; the interior-point solve (fixed cap of 20 iterations per round) at any nIter */
+    const bool lockstep = (F & ICNN_BE_FLAG_LOCKSTEP) || (!slice && T <= 15);
+    const int per_wg = (st.batch + cus - 1) / cus, tiles = (st.batch + 15) / 16;
+    const int tile_rows = per_wg <= 4 ? 4 : per_wg <= 8 ? 8 : 16;
+    icnn_be::FusedRowsLayout rows;
+    icnn_be::FusedTileLayout tile;
+    // up to four samples per CU: a persistent workgroup per 1-4 samples, any nIter
+    if (!forced && per_wg <= 4 && icnn_be::fused_rows_layout(m, st, per_wg, false, rows))
+        return {ICNN_BE_PATH_ROWS, per_wg, 0, T};
+    // nIter > 15 (or forced): persistent tiles, the dual phase in groups; a per-round update budget (TIME_SLICE, or the
+    // ICNN_BE_TILE_BUDGET knob) parks samples, and one launch of the per-sample kernel finishes them
+    if (!lockstep && !ipm && !two && ((dual && 4 * tiles >= cus && !slice) || persistent)) {
+        const int budget = slice ? SLICE_BUDGET : env_budget;
+        if (icnn_be::fused_tile_layout(m, st, tile_rows, budget, tile)) {
+            if (budget <= 0) return {ICNN_BE_PATH_TILE, tile_rows, budget, T};
+            if (!icnn_be::fused_rows_layout(m, st, 1, true, rows)) return {ICNN_BE_ELIMIT, 0, 0, 0};
+            return {ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS, tile_rows, budget, T + 1};
+        }
     }
-    /* No such kernel for this model (the conv PICNN: its evaluation couples sixteen samples in the 2048 x 512 layer), or
-       the caller insists on launch pairs.  Nobody else is waiting any more, so no budget: every further round completes one
-       outer iteration of every sample that is behind.  How many are needed -- the largest lag -- is only known on the
-       device, and the host does NOT ask (no synchronisation anywhere in this library; the call stays capturable in a HIP
-       graph): T more rounds are enqueued -- a sample cannot be behind by more than the T iterations it has, and an unbudgeted
-       round completes one of them whatever its Newton solve takes, so T rounds always suffice --, in which the kernels of a
-       sample that has nothing left to do leave at their first instruction (an empty round costs its launches, ~10 us).
-       The closing launch marks anything still behind with ICNN_BE_ST_UNFINISHED (a safety net: unreachable by the argument
-       above). */
-    const int extra = T;
-    for (int r = 0; r < extra && rounds < ICNN_BE_MAX_ROUNDS; ++r) {
-        hipError_t e = one_round(0);
-        if (e != hipSuccess) return fail(e);
-    }
-    hipError_t e = icnn_be::launch_mark_unfinished(*st, s);
-    if (e != hipSuccess) return fail(e);
-    return rounds;
+    // lockstep tiles where every CU has between a quarter of a tile and two tiles (variants dual, pdipm), any batch if forced
+    const bool tile_shape = (dual || ipm) && 4 * tiles >= cus && tiles <= 2 * cus;
+    if (!two && (lockstep || ipm) && (persistent || tile_shape) && icnn_be::fused_tile_layout(m, st, tile_rows, 0, tile))
+        return {ICNN_BE_PATH_TILE, tile_rows, 0, T};
+    // launch pairs: lockstep, or time-sliced with the stragglers finished by the per-sample kernel or by nIter more rounds
+    if (lockstep || ipm) return {ICNN_BE_PATH_ROUNDS_LOCKSTEP, 0, 0, T};
+    if (!two && icnn_be::fused_rows_layout(m, st, 1, true, rows))
+        return {ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS, 0, SLICE_BUDGET, T + 1};
+    return {ICNN_BE_PATH_ROUNDS_SLICED_EXTRA, 0, SLICE_BUDGET, sliced_extra_rounds(T)};
 }
 }  // namespace
 
@@ -217,84 +257,42 @@ int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn
                      float *f_work, float *g_work, void *stream) {
     if (int rc = check_state(st)) return rc;
     if (!model || !ctx || !f_work || !g_work || !model->wpack) return ICNN_BE_EINVAL;
-    if (st->cut_dtype != ICNN_BE_CUT_F32 || st->n != model->n) return ICNN_BE_EINVAL;
-    if (st->flags & ICNN_BE_FLAG_F64_ENERGY) return ICNN_BE_EINVAL;        /* the fused energies are float32 */
-    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (int rc = check_fc_solve(model, st)) return rc;
     if (st->batch == 0) return 0;
+    const SolvePlan p = plan_fc_solve(*model, *st, icnn_be::device_cus(), env_tile_budget());
+    if (p.path < 0) return p.path;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    /* lockstep rounds (the default for nIter <= 15): the persistent per-tile kernel where the shape fits it */
-    const int iters = st->iters > 0 ? st->iters : st->slots;
-    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || (!(st->flags & ICNN_BE_FLAG_TIME_SLICE) && iters <= 15);
-    bool persistent = lockstep && !(st->flags & ICNN_BE_FLAG_TWO_KERNELS);
-    const int cus = icnn_be::device_cus();
-    /* at most two samples per CU: a persistent workgroup per sample or pair of samples (be_fused.hip).  Every sample
-       runs at its own pace there, so no time slicing is needed however many outer iterations there are. */
-    const int forced = ICNN_BE_FLAG_TWO_KERNELS | ICNN_BE_FLAG_PERSISTENT | ICNN_BE_FLAG_TIME_SLICE | ICNN_BE_FLAG_LOCKSTEP;
-    const int per_wg = (st->batch + cus - 1) / cus;
-    const bool ipm = st->variant == ICNN_BE_VARIANT_PDIPM;   /* (round 4: the interior-point variant runs through the persistent
-                                                                kernels too; its solve has a fixed cap of 20 iterations per
-                                                                round, so there is nothing to time-slice: lockstep at any nIter) */
-    if (ipm) persistent = !(st->flags & ICNN_BE_FLAG_TWO_KERNELS);
-    if (!(st->flags & forced) && per_wg <= 4) {
-        hipError_t e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, per_wg,
-                                                        icnn_be::dual_profile_buffer(), s);
-        if (e == hipSuccess) return iters;
-        if (e != hipErrorNotSupported) return fail(e);
+    long long *prof = icnn_be::dual_profile_buffer();
+    auto finish = [&] { return icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, 1, prof, s, true); };
+    auto fg = [&] { return icnn_be::launch_fc_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s); };
+    hipError_t e = hipSuccess;
+    switch (p.path) {
+    case ICNN_BE_PATH_ROWS:
+        e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, p.per_wg, prof, s, false);
+        break;
+    case ICNN_BE_PATH_TILE:
+    case ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS:
+        e = icnn_be::launch_fused_fc_solve(*model, ctx, *st, f_work, g_work, prof, s, p.per_wg, p.budget);
+        if (e == hipSuccess && p.path == ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS) e = finish();
+        break;
+    case ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS:
+        e = solve_rounds(*st, p.budget, outer_iters(*st), f_work, g_work, s, fg);
+        if (e == hipSuccess) e = finish();
+        break;
+    default:            // ICNN_BE_PATH_ROUNDS_LOCKSTEP, ICNN_BE_PATH_ROUNDS_SLICED_EXTRA
+        e = solve_rounds(*st, p.budget, p.rounds, f_work, g_work, s, fg);
     }
-    /* a tile of 16 samples per workgroup: worth it when the CUs are neither mostly idle nor several tiles deep
-       (the RL variant runs through the same kernel bit-identically but measured 8-40 % slower at every batch
-       size -- its dual step is long and evenly long --, so it only takes this path when forced) */
-    const int tiles = (st->batch + 15) / 16;
-    const bool tile_shape = (st->variant == ICNN_BE_VARIANT_DUAL || ipm) && 4 * tiles >= cus && tiles <= 2 * cus;
-    if (persistent && !(st->flags & ICNN_BE_FLAG_PERSISTENT)) persistent = tile_shape;
-    /* more outer iterations than that (nIter > 15, where launch pairs are time-sliced): the SAME persistent tile kernel with the
-       dual phase in groups (the bundles of sixteen samples at 15+ cuts each do not fit the LDS together, be_fused.hip).  One
-       launch instead of 2 x nIter.  A tile only waits for the slowest of ITS sixteen samples, and since limit cycles at their
-       rounding floor are recognised (be_dual_dev.h, NOISE_TOL) a sample's longest Newton solve is a few dozen updates, so the
-       tiles run in lockstep WITHOUT the per-round update budget of the launch pairs (measured, 4096 samples, nIter 30:
-       unlimited 6.8-7.0 ms, budget 8 7.4-7.6, 12 7.3-7.5; with a budget a parked sample skips phase A, resumes in its tile's
-       next dual phase, and ONE finishing launch of the per-sample kernel brings the samples that are behind to the end). */
-    /* (no upper limit on the tiles per CU here: 16384 samples at nIter 30 take 28.0 ms as persistent tiles, four per CU one
-       after the other, against 35.8 ms as launch pairs -- tools/big_batch_long_experiment.py) */
-    const bool long_tile_shape = st->variant == ICNN_BE_VARIANT_DUAL && 4 * tiles >= cus;
-    if (!lockstep && !ipm && !(st->flags & ICNN_BE_FLAG_TWO_KERNELS) &&
-        ((long_tile_shape && !(st->flags & ICNN_BE_FLAG_TIME_SLICE)) || (st->flags & ICNN_BE_FLAG_PERSISTENT))) {
-        int tile_rows = 16;
-        if (per_wg <= 8) tile_rows = per_wg <= 4 ? 4 : 8;
-        static const int env_budget = [] {         /* tuning knob (tools/tile_budget_sweep.py); default measured there */
-            const char *v = std::getenv("ICNN_BE_TILE_BUDGET");
-            return v ? std::atoi(v) : 0;
-        }();
-        /* ICNN_BE_FLAG_PERSISTENT | ICNN_BE_FLAG_TIME_SLICE: the budgeted form (eight updates per round + finishing launch) */
-        const int tile_budget = (st->flags & ICNN_BE_FLAG_TIME_SLICE) ? 8 : env_budget;
-        hipError_t e = icnn_be::launch_fused_fc_solve(*model, ctx, *st, f_work, g_work, icnn_be::dual_profile_buffer(), s,
-                                                      tile_rows, tile_budget);
-        if (e == hipSuccess) {
-            if (tile_budget <= 0) return iters;     /* nobody was parked: every sample is at its end */
-            e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, 1, icnn_be::dual_profile_buffer(), s, true);
-            if (e == hipSuccess) return iters + 1;
-            return fail(e);        /* (the same shapes fit both kernels: nothing to fall back to half-way) */
-        }
-        if (e != hipErrorNotSupported) return fail(e);
-    }
-    if (persistent) {
-        /* five to eight samples per CU (MI355X: 1025..2048 samples, e.g. the shard of the 4096 batch on two GPUs): partial
-           tiles -- 8 samples in the 16-row MFMA tile -- so that every CU has a tile and a tile's dual phase runs two waves
-           per SIMD and waits for the slowest of 8 (2048 samples: 1.00 ms against 1.17 with full tiles on half the CUs,
-           bit-identical; tools/partial_tiles_experiment.py).  Up to four per CU the per-sample kernel above is faster
-           (0.68 / 0.85 ms at 512 / 1024 against 0.91 with 4-sample tiles, which ICNN_BE_FLAG_PERSISTENT still selects). */
-        int tile_rows = 16;
-        if (per_wg <= 8) tile_rows = per_wg <= 4 ? 4 : 8;
-        hipError_t e = icnn_be::launch_fused_fc_solve(*model, ctx, *st, f_work, g_work, icnn_be::dual_profile_buffer(), s,
-                                                      tile_rows);
-        if (e == hipSuccess) return iters;
-        if (e != hipErrorNotSupported) return fail(e);
-    }
-    return solve_rounds(st, f_work, g_work, s, [&]() {
-        return icnn_be::launch_fc_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
-    }, 15, [&]() {
-        return icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, 1, icnn_be::dual_profile_buffer(), s, true);
-    });
+    return e == hipSuccess ? p.rounds : fail(e);
+}
+
+int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state *st, int cus, int out[3]) {
+    if (!out) return ICNN_BE_EINVAL;
+    if (int rc = check_fc_solve(model, st)) return rc;
+    if (st->batch == 0) return ICNN_BE_EINVAL;
+    const SolvePlan p = plan_fc_solve(*model, *st, cus > 0 ? cus : icnn_be::device_cus(), env_tile_budget());
+    if (p.path < 0) return p.path;
+    out[0] = p.per_wg; out[1] = p.budget; out[2] = p.rounds;
+    return p.path;
 }
 
 size_t icnn_be_fc_context_work_floats(const icnn_be_fc_ctx *c, int batch) {
@@ -472,15 +470,20 @@ int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const 
     if (st->batch > 0 && (!model->work || model->work_batch < st->batch)) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (st->batch == 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     /* Lockstep rounds at EVERY nIter (round 3; time slicing on request, ICNN_BE_FLAG_TIME_SLICE).  Slicing pays when a round
        is held up by a Newton solve that runs its 100-update cap; since limit cycles at their rounding floor are recognised
        (be_dual_dev.h, NOISE_TOL) those are one solve in a thousand, while every sliced solve pays nIter finishing rounds of
        five launches for its few laggards.  Measured at 256 samples (tools/conv_slice_experiment.py): nIter 30 lockstep
-       12.0 / 11.0 ms against 16.4 / 15.0 sliced on two instances, nIter 5 2.24 / 1.73 against 2.22 / 2.04. */
-    return solve_rounds(st, f_work, g_work, s, [&]() {
+       12.0 / 11.0 ms against 16.4 / 15.0 sliced on two instances, nIter 5 2.24 / 1.73 against 2.22 / 2.04.  No finishing
+       launch: its evaluation couples sixteen samples in the 2048 x 512 layer, so the stragglers get nIter whole rounds. */
+    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || st->variant == ICNN_BE_VARIANT_PDIPM ||
+                          !(st->flags & ICNN_BE_FLAG_TIME_SLICE);
+    const int T = outer_iters(*st), total = lockstep ? T : sliced_extra_rounds(T);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = solve_rounds(*st, lockstep ? 0 : SLICE_BUDGET, total, f_work, g_work, s, [&] {
         return icnn_be::launch_conv_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
-    }, ICNN_BE_MAX_ITERS);
+    });
+    return e == hipSuccess ? total : fail(e);
 }
 
 }  // extern "C"

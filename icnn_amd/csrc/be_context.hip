@@ -367,8 +367,7 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
         col += c.width[i - 1]; ctx_off += c.width[i - 1];
     }
     a.nseg = s;
-    hipLaunchKernelGGL(ctx_gemm_kernel, dim3((batch + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
-    return hipGetLastError();
+    return launch_kernel(ctx_gemm_kernel, dim3((batch + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
 }
 
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
@@ -380,9 +379,8 @@ hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch,
         if (i < L && stage_bn(c, i)) {
             int u_ld = 0;
             float *u_out = stage_u(c, i, batch, work, u_ld);
-            hipLaunchKernelGGL(ctx_bn_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u_out, u_ld, batch,
-                               c.width[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
-            e = hipGetLastError();
+            e = launch_kernel(ctx_bn_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u_out, u_ld, batch,
+                              c.width[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
             if (e != hipSuccess) return e;
         }
     }
@@ -396,9 +394,8 @@ int launch_fc_context_sums(const icnn_be_fc_ctx &c, int i, int batch, float *wor
     if (i < 0 || i >= c.n_layers - 1 || !stage_bn(c, i)) return 1;
     int u_ld = 0;
     const float *u = stage_u(c, i, batch, work, u_ld);
-    hipLaunchKernelGGL(ctx_bn_sums_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
-                       stats);
-    err = hipGetLastError();
+    err = launch_kernel(ctx_bn_sums_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
+                        stats);
     return 0;
 }
 hipError_t launch_fc_context_norm(const icnn_be_fc_ctx &c, int i, int batch, double batch_total, const double *stats,
@@ -406,9 +403,8 @@ hipError_t launch_fc_context_norm(const icnn_be_fc_ctx &c, int i, int batch, dou
     if (i < 0 || i >= c.n_layers - 1 || !stage_bn(c, i)) return hipErrorInvalidValue;
     int u_ld = 0;
     float *u = stage_u(c, i, batch, work, u_ld);
-    hipLaunchKernelGGL(ctx_bn_apply_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
-                       stats, batch_total, c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
-    return hipGetLastError();
+    return launch_kernel(ctx_bn_apply_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
+                         stats, batch_total, c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
 }
 
 // ---- conv PICNN (completion/icnn_ebundle.py:346-367 u-path, :376-452 heads) --------------------------------------
@@ -435,19 +431,18 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
         for (const CtxSeg &sg : segs) { a.seg[a.nseg++] = sg; n = sg.c1; }
         a.N = n; a.ldw = (n + 3) & ~3;
         a.a_vec = conv ? (IC % 4 == 0) : (lda % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0);
-        hipLaunchKernelGGL(ctx_gemm_kernel, dim3((a.M + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
-        return hipGetLastError();
+        return launch_kernel(ctx_gemm_kernel, dim3((a.M + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
     };
     auto bn = [&](float *u, int ld, int rows, int cols, int i) -> hipError_t {
         if (rows >= 16 * BNB && cols % 4 == 0 && cols <= 256 && ld == cols) {          // tall: row-parallel passes
-            for (int pass = 0; pass < 3; ++pass)
-                hipLaunchKernelGGL(ctx_bn_tall_kernel, dim3(BNB), dim3(TBT), 0, stream, u, ld, rows, cols, part, c.bn_gamma[i],
-                                   c.bn_beta[i], c.bn_eps, pass);
-            return hipGetLastError();
+            hipError_t e = hipSuccess;
+            for (int pass = 0; pass < 3 && e == hipSuccess; ++pass)
+                e = launch_kernel(ctx_bn_tall_kernel, dim3(BNB), dim3(TBT), 0, stream, u, ld, rows, cols, part, c.bn_gamma[i],
+                                  c.bn_beta[i], c.bn_eps, pass);
+            return e;
         }
-        hipLaunchKernelGGL(ctx_bn_kernel, dim3((cols + BNC - 1) / BNC), dim3(BNT), 0, stream, u, ld, rows, cols, c.bn_gamma[i],
-                           c.bn_beta[i], c.bn_eps);
-        return hipGetLastError();
+        return launch_kernel(ctx_bn_kernel, dim3((cols + BNC - 1) / BNC), dim3(BNT), 0, stream, u, ld, rows, cols, c.bn_gamma[i],
+                             c.bn_beta[i], c.bn_eps);
     };
     const int H = g.H, W = g.W, F0 = g.F[0], F1 = g.F[1], F2 = g.F[2];
     const int *oh = g.oh, *ow = g.ow, *K = g.K, *S = g.S, *Pd = g.pad, *P = g.P;
@@ -487,8 +482,7 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
 hipError_t launch_clamp(float *w, size_t count, int mode, hipStream_t stream) {
     if (count == 0) return hipSuccess;
     const int blocks = (int)((count + 255) / 256 < 2048 ? (count + 255) / 256 : 2048);
-    hipLaunchKernelGGL(clamp_kernel, dim3(blocks), dim3(256), 0, stream, w, count, mode);
-    return hipGetLastError();
+    return launch_kernel(clamp_kernel, dim3(blocks), dim3(256), 0, stream, w, count, mode);
 }
 
 }  // namespace icnn_be

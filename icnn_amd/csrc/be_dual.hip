@@ -196,19 +196,16 @@ __global__ void mark_unfinished_kernel(icnn_be_state st) {
 hipError_t launch_export_active(const icnn_be_state &st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
                                 double *lam_rows, hipStream_t stream) {
     ExportArgs a{st, row_offset, G_rows, ys_rows, h_rows, lam_rows};
-    if (st.cut_dtype == ICNN_BE_CUT_F64) hipLaunchKernelGGL(export_active_kernel<double>, dim3(st.batch), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(export_active_kernel<float>, dim3(st.batch), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    auto kern = st.cut_dtype == ICNN_BE_CUT_F64 ? export_active_kernel<double> : export_active_kernel<float>;
+    return launch_kernel(kern, dim3(st.batch), dim3(256), 0, stream, a);
 }
 
 hipError_t launch_fast_math(int which, const double *x, double *out, int count, hipStream_t stream) {
-    hipLaunchKernelGGL(fast_math_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, which, x, out, count);
-    return hipGetLastError();
+    return launch_kernel(fast_math_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, which, x, out, count);
 }
 
 hipError_t launch_mark_unfinished(const icnn_be_state &st, hipStream_t stream) {
-    hipLaunchKernelGGL(mark_unfinished_kernel, dim3((st.batch + 255) / 256), dim3(256), 0, stream, st);
-    return hipGetLastError();
+    return launch_kernel(mark_unfinished_kernel, dim3((st.batch + 255) / 256), dim3(256), 0, stream, st);
 }
 
 static long long *g_prof = nullptr;
@@ -257,100 +254,86 @@ int dual_rows_fit(int n, int slots, int cut_dtype, int variant) {
 
 hipError_t launch_state_init(const icnn_be_state &st, hipStream_t stream) {
     const int threads = st.batch > ICNN_BE_MAX_ROUNDS ? st.batch : ICNN_BE_MAX_ROUNDS;
-    hipLaunchKernelGGL(state_init_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, st);
-    return hipGetLastError();
+    return launch_kernel(state_init_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, st);
 }
 
-template <typename CutT, int KT, int NW, bool RL, bool IPM = false>
-static hipError_t launch_rl(const DualArgs &a, int lds, hipStream_t stream) {
-    auto kern = dual_step_kernel<CutT, KT, NW, RL, IPM>;
-    if (lds > 48 * 1024)
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.st.batch), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
-}
+namespace {
+typedef void (*DualKernel)(DualArgs);
+struct DualStepLaunch {
+    DualKernel kern;
+    int waves, lds, rows;
+};
+
+// the bundle in LDS: CutT, KT, NW fixed by the caller, the variant picks the body
 template <typename CutT, int KT, int NW>
-static hipError_t launch_one(const DualArgs &a, int lds, hipStream_t stream) {
-    if (a.st.variant == ICNN_BE_VARIANT_RL) {
-        if (NW != 1) return hipErrorInvalidValue;          // dual_waves() never widens the RL variant
-        return launch_rl<CutT, KT, 1, true>(a, lds, stream);
-    }
-    if (a.st.variant == ICNN_BE_VARIANT_PDIPM) return launch_rl<CutT, KT, NW, false, true>(a, lds, stream);
-    return launch_rl<CutT, KT, NW, false>(a, lds, stream);
+DualKernel dual_kernel_for(int variant) {
+    if (variant == ICNN_BE_VARIANT_RL) return dual_step_kernel<CutT, KT, 1, true>;     // dual_waves() never widens variant RL
+    if (variant == ICNN_BE_VARIANT_PDIPM) return dual_step_kernel<CutT, KT, NW, false, true>;
+    return dual_step_kernel<CutT, KT, NW, false>;
 }
+
+// Which dual_step_kernel instance the launch `a` runs, on how many waves, with how much LDS and how many staged rows.
+// false: no instance fits.
+bool choose_dual_step(const DualArgs &a, DualStepLaunch &c) {
+    const icnn_be_state &st = a.st;
+    const bool ipm = st.variant == ICNN_BE_VARIANT_PDIPM, f64 = st.cut_dtype == ICNN_BE_CUT_F64, big = st.slots > 15;
+    const bool global = st.flags & ICNN_BE_FLAG_GLOBAL_BUNDLE;
+    const int fit = dual_rows_fit(st.n, st.slots, st.cut_dtype, st.variant);
+    c.rows = a.rows;
+    c.waves = dual_waves(st.n, st.cut_dtype, st.variant);
+    if ((c.rows > fit || global) && st.scratch && scratch_bytes(st) > 0) {
+        // wide rows: the LDS holds fewer cuts than there are iterations.  From the round on in which a bundle could outgrow
+        // it, the bundle is staged in st.scratch instead (same kernel, the sweeps at L2 latency); without a scratch area the
+        // capacity stays and a sample that exceeds it stops with ICNN_BE_ST_OVERFLOW
+        auto staged_lds = [&](int rows, int waves) {
+            return carve(32, rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, waves, true, ipm, true).total;
+        };
+        c.lds = staged_lds(c.rows, c.waves);
+        if (c.lds > 160 * 1024 && c.waves > 1) {
+            // the per-wave systems of an eight-wave sample do not fit next to the column buffers (interior point: five of
+            // them; n_pad = 3072 from 23 rows on): the one-wave instance of the same body, whose carve-up has none
+            c.waves = 1;
+            c.lds = staged_lds(c.rows, 1);
+        }
+        if (c.lds > 160 * 1024) return false;
+        if (f64) {
+            c.kern = ipm ? dual_step_kernel<double, 32, 1, false, true, true> : dual_step_kernel<double, 32, 1, false, false, true>;
+        } else if (ipm) {
+            c.kern = c.waves > 1 ? dual_step_kernel<float, 32, 8, false, true, true> : dual_step_kernel<float, 32, 1, false, true, true>;
+        } else {
+            c.kern = c.waves > 1 ? dual_step_kernel<float, 32, 8, false, false, true> : dual_step_kernel<float, 32, 1, false, false, true>;
+            if (c.waves > 1 && !global) {
+                // split staging (dual_step_wide_kernel): LDS for the carve-up of a bundle of up to HV_KMAX cuts + the mirror
+                // of its WIDE_LR oldest rows, or for the plain device-memory body of a larger one
+                const int lds_b = ((staged_lds(c.rows < HV_KMAX ? c.rows : HV_KMAX, c.waves) + 15) & ~15) + WIDE_LR * a.ldA * 4;
+                const int lds_w = lds_b > c.lds ? lds_b : c.lds;
+                if (lds_w <= 160 * 1024) {
+                    c.kern = dual_step_wide_kernel;
+                    c.lds = lds_w;
+                }
+            }
+        }
+        return true;
+    }
+    if (c.rows > fit) c.rows = fit;
+    c.lds = dual_lds_bytes(st.n, st.slots, st.cut_dtype, st.variant, c.rows);
+    if (st.variant == ICNN_BE_VARIANT_RL) c.waves = 1;
+    c.kern = f64 ? (big ? dual_kernel_for<double, 32, 1>(st.variant) : dual_kernel_for<double, 16, 1>(st.variant))
+           : c.waves > 1 ? (big ? dual_kernel_for<float, 32, 8>(st.variant) : dual_kernel_for<float, 16, 8>(st.variant))
+                         : (big ? dual_kernel_for<float, 32, 1>(st.variant) : dual_kernel_for<float, 16, 1>(st.variant));
+    return true;
+}
+}  // namespace
 
 hipError_t launch_dual_step(const icnn_be_state &st, int round, int budget, const void *f, const void *g,
                             hipStream_t stream) {
     if (dual_step_small_fits(st, budget)) return launch_dual_step_small(st, round, f, g, stream);
     DualArgs a;
-    a.st = st;
-    a.f = f;
-    a.g = g;
-    a.round = round;
-    a.budget = budget;
-    a.n_pad = (st.n + 15) & ~15;
-    a.ldA = dual_row_pitch(a.n_pad);
-    a.prof = g_prof;
-    if (!pw_build(a.plan, st.n)) return hipErrorInvalidValue;
-    a.rows = round + 1 < st.slots ? round + 1 : st.slots;
-    // wide rows: the LDS holds fewer cuts than there are iterations.  From the round on in which a bundle could outgrow
-    // it, the bundle is staged in st.scratch instead (same kernel, the sweeps at L2 latency); without a scratch area the
-    // capacity stays and a sample that exceeds it stops with ICNN_BE_ST_OVERFLOW
-    const int fit = dual_rows_fit(st.n, st.slots, st.cut_dtype, st.variant);
-    if ((a.rows > fit || (st.flags & ICNN_BE_FLAG_GLOBAL_BUNDLE)) && st.scratch && scratch_bytes(st) > 0) {
-        const bool ipm = st.variant == ICNN_BE_VARIANT_PDIPM, f64 = st.cut_dtype == ICNN_BE_CUT_F64;
-        int nw = dual_waves(st.n, st.cut_dtype, st.variant);
-        int lds_g = carve(32, a.rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, nw, true, ipm, true).total;
-        if (lds_g > 160 * 1024 && nw > 1) {
-            // the per-wave systems of an eight-wave sample do not fit next to the column buffers (interior point: five of
-            // them; n_pad = 3072 from 23 rows on): the one-wave instance of the same body, whose carve-up has none
-            nw = 1;
-            lds_g = carve(32, a.rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, 1, true, ipm, true).total;
-        }
-        if (lds_g > 160 * 1024) return hipErrorInvalidValue;
-        auto go = [&](auto kern, int waves) -> hipError_t {
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_g); e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(st.batch), dim3(64 * waves), lds_g, stream, a);
-            return hipGetLastError();
-        };
-        if (f64) return ipm ? go(dual_step_kernel<double, 32, 1, false, true, true>, 1)
-                            : go(dual_step_kernel<double, 32, 1, false, false, true>, 1);
-        if (ipm) return nw > 1 ? go(dual_step_kernel<float, 32, 8, false, true, true>, 8)
-                               : go(dual_step_kernel<float, 32, 1, false, true, true>, 1);
-        if (nw > 1 && !(st.flags & ICNN_BE_FLAG_GLOBAL_BUNDLE)) {
-            // split staging (dual_step_wide_kernel): LDS for the carve-up of a bundle of up to HV_KMAX cuts + the mirror of
-            // its WIDE_LR oldest rows, or for the plain device-memory body of a larger one
-            const int mid = a.rows < HV_KMAX ? a.rows : HV_KMAX;
-            const int lds_b = ((carve(32, mid, a.ldA, a.n_pad, 4, a.plan.n_leaves, false, nw, true, false, true).total + 15) & ~15) +
-                              WIDE_LR * a.ldA * 4;
-            const int lds_w = lds_b > lds_g ? lds_b : lds_g;
-            if (lds_w <= 160 * 1024) {
-                if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(dual_step_wide_kernel), lds_w); e != hipSuccess)
-                    return e;
-                hipLaunchKernelGGL(dual_step_wide_kernel, dim3(st.batch), dim3(512), lds_w, stream, a);
-                return hipGetLastError();
-            }
-        }
-        return nw > 1 ? go(dual_step_kernel<float, 32, 8, false, false, true>, 8)
-                      : go(dual_step_kernel<float, 32, 1, false, false, true>, 1);
-    }
-    if (a.rows > fit) a.rows = fit;
-    const int lds = dual_lds_bytes(st.n, st.slots, st.cut_dtype, st.variant, a.rows);
-    const bool big = st.slots > 15;
-    if (st.cut_dtype == ICNN_BE_CUT_F64)
-        return big ? launch_one<double, 32, 1>(a, lds, stream) : launch_one<double, 16, 1>(a, lds, stream);
-    if (dual_waves(st.n, st.cut_dtype, st.variant) > 1)
-        return big ? launch_one<float, 32, 8>(a, lds, stream) : launch_one<float, 16, 8>(a, lds, stream);
-    return big ? launch_one<float, 32, 1>(a, lds, stream) : launch_one<float, 16, 1>(a, lds, stream);
-}
-
-template <typename CutT, int KT, bool GLB = false>
-static hipError_t launch_feed_one(const FeedArgs &a, int lds, hipStream_t stream) {
-    auto kern = implicit_feed_kernel<CutT, KT, GLB>;
-    if (lds > 48 * 1024)
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.st.batch), dim3(64), lds, stream, a);
-    return hipGetLastError();
+    DualStepLaunch c;
+    if (!make_dual_args(a, st, f, g, round, budget, round + 1 < st.slots ? round + 1 : st.slots, g_prof) || !choose_dual_step(a, c))
+        return hipErrorInvalidValue;
+    a.rows = c.rows;
+    return launch_kernel(c.kern, dim3(st.batch), dim3(64 * c.waves), c.lds, stream, a);
 }
 
 hipError_t launch_implicit_feed(const icnn_be_state &st, const double *y_true, int loss, const int *row_offset,
@@ -363,19 +346,20 @@ hipError_t launch_implicit_feed(const icnn_be_state &st, const double *y_true, i
     a.n_pad = (st.n + 15) & ~15;
     a.ldA = dual_row_pitch(a.n_pad);
     if (!pw_build(a.plan, st.n)) return hipErrorInvalidValue;
-    const bool big = st.slots > 15;
-    const int KT = big ? 32 : 16, cb = st.cut_dtype == ICNN_BE_CUT_F64 ? 8 : 4;     // (one wave per sample here)
-    const int lds = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false).total;
+    const bool big = st.slots > 15, f64 = st.cut_dtype == ICNN_BE_CUT_F64;
+    const int KT = big ? 32 : 16, cb = f64 ? 8 : 4;     // (one wave per sample here)
+    int lds = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false).total;
+    void (*kern)(FeedArgs);
     if (lds > 160 * 1024) {              // wide rows with more slots than LDS rows: the staging area in device memory
         if (!st.scratch || scratch_bytes(st) == 0) return hipErrorInvalidValue;
-        const int lds_g = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false, 1, true, false, true).total;
-        if (st.cut_dtype == ICNN_BE_CUT_F64)
-            return big ? launch_feed_one<double, 32, true>(a, lds_g, stream) : launch_feed_one<double, 16, true>(a, lds_g, stream);
-        return big ? launch_feed_one<float, 32, true>(a, lds_g, stream) : launch_feed_one<float, 16, true>(a, lds_g, stream);
+        lds = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false, 1, true, false, true).total;
+        kern = f64 ? (big ? implicit_feed_kernel<double, 32, true> : implicit_feed_kernel<double, 16, true>)
+                   : (big ? implicit_feed_kernel<float, 32, true> : implicit_feed_kernel<float, 16, true>);
+    } else {
+        kern = f64 ? (big ? implicit_feed_kernel<double, 32> : implicit_feed_kernel<double, 16>)
+                   : (big ? implicit_feed_kernel<float, 32> : implicit_feed_kernel<float, 16>);
     }
-    if (st.cut_dtype == ICNN_BE_CUT_F64)
-        return big ? launch_feed_one<double, 32>(a, lds, stream) : launch_feed_one<double, 16>(a, lds, stream);
-    return big ? launch_feed_one<float, 32>(a, lds, stream) : launch_feed_one<float, 16>(a, lds, stream);
+    return launch_kernel(kern, dim3(st.batch), dim3(64), lds, stream, a);
 }
 
 }  // namespace icnn_be

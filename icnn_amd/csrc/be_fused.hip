@@ -270,104 +270,99 @@ __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArg
 
 }  // namespace
 
-// Returns hipErrorNotSupported when the shape does not fit this path (the caller falls back to one launch per phase).
+bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int per_wg, bool resume, FusedRowsLayout &out) {
+    const bool rl = st.variant == ICNN_BE_VARIANT_RL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
+    if (st.cut_dtype != ICNN_BE_CUT_F32 || per_wg < 1 || per_wg > ROWS_MAX) return false;
+    if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || (ipm && resume)) return false;
+    PairwisePlan plan;
+    if (!pw_build(plan, st.n)) return false;
+    const int n_pad = (st.n + 15) & ~15, ldA = dual_row_pitch(n_pad);
+    RowsLayout lay;
+    out.dual_off = (rows_layout(m, per_wg, lay) + 15) & ~15;
+    out.sample_bytes = (carve(st.slots > 15 ? 32 : 16, st.slots, ldA, n_pad, 4, plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+    out.crow_off = out.dual_off + per_wg * out.sample_bytes;
+    out.lds = out.crow_off + ((2 * ldA * 4 + 15) & ~15);
+    return out.lds <= 160 * 1024;
+}
+
+bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget, FusedTileLayout &out) {
+    const bool rl = st.variant == ICNN_BE_VARIANT_RL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
+    if (st.cut_dtype != ICNN_BE_CUT_F32 || (tile_rows != 4 && tile_rows != 8 && tile_rows != TM)) return false;
+    if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || ((ipm || rl) && budget > 0)) return false;
+    FcArgs fa{};
+    int fg_bytes = 0;
+    PairwisePlan plan;
+    if (fill_args(m, fa, fg_bytes) != 0 || !pw_build(plan, st.n)) return false;
+    const bool big = st.slots > 15;
+    const int n_pad = (st.n + 15) & ~15, ldA = dual_row_pitch(n_pad);
+    out.sample_bytes = (carve(big ? 32 : 16, st.slots, ldA, n_pad, 4, plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+    // phase B: sixteen bundles from offset 0 (they overlay phase A's buffers); the shared constant rows live behind
+    // whichever region is larger, where neither phase overwrites them
+    const int crow_bytes = (2 * ldA * 4 + 15) & ~15, dual_bytes = TM * out.sample_bytes;
+    out.crow_off = ((fg_bytes > dual_bytes ? fg_bytes : dual_bytes) + 15) & ~15;
+    out.lds = out.crow_off + crow_bytes;
+    out.grouped = out.group_cap = out.need_off = 0;
+    if (out.lds > 160 * 1024 || big) {
+        // the sixteen full-size bundles do not fit together: groups sized by what the samples hold (FusedArgs::grouped).
+        // The staging region takes everything the workgroup can have; one sample's largest bundle must fit it.
+        const int need_bytes = 2 * TM * 4;            // per sample: bytes needed this round, and its done flag
+        out.crow_off = (160 * 1024 - 1024 - crow_bytes - need_bytes) & ~15;      // (1 KB: the kernel's static LDS, 256 B today)
+        if (out.crow_off < fg_bytes || out.crow_off < out.sample_bytes) return false;
+        out.grouped = 1; out.group_cap = out.crow_off; out.need_off = out.crow_off + crow_bytes;
+        out.lds = out.need_off + need_bytes;
+    }
+    return true;
+}
+
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                    float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume) {
-    const bool rl = st.variant == ICNN_BE_VARIANT_RL;
-    const bool ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
-    if (st.cut_dtype != ICNN_BE_CUT_F32 || per_wg < 1 || per_wg > ROWS_MAX) return hipErrorNotSupported;
-    if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || (ipm && resume)) return hipErrorNotSupported;
+    FusedRowsLayout lay;
+    if (!fused_rows_layout(m, st, per_wg, resume, lay)) return hipErrorInvalidValue;
     FusedRowsArgs args{};
     int unused = 0;
     if (fill_args(m, args.fa, unused) != 0) return hipErrorInvalidValue;
     args.fa.ctx = ctx; args.fa.y = st.y; args.fa.f = f_work; args.fa.g = g_work; args.fa.finished = nullptr;
     args.fa.batch = st.batch; args.fa.prof = fc_profile_buffer();
-    DualArgs &da = args.da;
-    da.st = st;
-    da.f = f_work;
-    da.g = g_work;
-    da.round = 0;
-    da.budget = 0;
-    da.n_pad = (st.n + 15) & ~15;
-    da.ldA = dual_row_pitch(da.n_pad);
-    da.rows = st.slots;
-    da.prof = dual_prof;
-    if (!pw_build(da.plan, st.n)) return hipErrorInvalidValue;
-    const bool big = st.slots > 15;
-    const int rows_bytes = (rows_layout(m, per_wg, args.lay) + 15) & ~15;
-    args.sample_bytes = (carve(big ? 32 : 16, st.slots, da.ldA, da.n_pad, 4, da.plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+    if (!make_dual_args(args.da, st, f_work, g_work, 0, 0, st.slots, dual_prof)) return hipErrorInvalidValue;
+    rows_layout(m, per_wg, args.lay);
+    args.sample_bytes = lay.sample_bytes;
     args.per_wg = per_wg;
-    args.dual_off = rows_bytes;
-    args.crow_off = rows_bytes + per_wg * args.sample_bytes;
-    const int lds = args.crow_off + ((2 * da.ldA * 4 + 15) & ~15);
-    if (lds > 160 * 1024) return hipErrorNotSupported;
+    args.dual_off = lay.dual_off;
+    args.crow_off = lay.crow_off;
     args.rounds = args.iters = st.iters > 0 ? st.iters : st.slots;
     args.resume = resume ? 1 : 0;
-    const int which = (rl ? 1 : 0) + (big ? 2 : 0);
+    const bool big = st.slots > 15;
+    const int which = (st.variant == ICNN_BE_VARIANT_RL ? 1 : 0) + (big ? 2 : 0);
     auto kern = which == 0 ? fused_rows_solve_kernel<false, 16> : which == 1 ? fused_rows_solve_kernel<true, 16>
               : which == 2 ? fused_rows_solve_kernel<false, 32> : fused_rows_solve_kernel<true, 32>;
-    if (ipm) kern = big ? fused_rows_solve_kernel<false, 32, 0, true> : fused_rows_solve_kernel<false, 16, 0, true>;
+    if (st.variant == ICNN_BE_VARIANT_PDIPM)
+        kern = big ? fused_rows_solve_kernel<false, 32, 0, true> : fused_rows_solve_kernel<false, 16, 0, true>;
     if (!resume && dual_step_small_fits(st, 0))         // narrow rows, variant RL: all dual steps of the workgroup on wave 0
         kern = st.slots <= 5 ? fused_rows_solve_kernel<true, 16, 5> : st.slots <= 7 ? fused_rows_solve_kernel<true, 16, 8>
                                                                                   : fused_rows_solve_kernel<true, 16, 16>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((st.batch + per_wg - 1) / per_wg), dim3(RTHREADS), lds, stream, args);
-    return hipGetLastError();
+    return launch_kernel(kern, dim3((st.batch + per_wg - 1) / per_wg), dim3(RTHREADS), lay.lds, stream, args);
 }
 
-// Returns hipErrorNotSupported when the shape does not fit this path (the caller falls back to one launch per phase).
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                  float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget) {
-    const bool rl = st.variant == ICNN_BE_VARIANT_RL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
-    if (st.cut_dtype != ICNN_BE_CUT_F32) return hipErrorNotSupported;
-    if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || ((ipm || rl) && budget > 0)) return hipErrorNotSupported;
-    const bool big = st.slots > 15;
-    FcArgs fa{};
+    FusedTileLayout lay;
+    if (!fused_tile_layout(m, st, tile_rows, budget, lay)) return hipErrorInvalidValue;
+    FusedArgs args{};
     int fg_bytes = 0;
-    if (fill_args(m, fa, fg_bytes) != 0) return hipErrorInvalidValue;
-    fa.ctx = ctx; fa.y = st.y; fa.f = f_work; fa.g = g_work; fa.finished = st.skip_fg; fa.batch = st.batch;
-    fa.prof = nullptr;
-    if (tile_rows != 4 && tile_rows != 8 && tile_rows != TM) return hipErrorInvalidValue;
-    fa.tile_rows = tile_rows;
-    DualArgs da;
-    da.st = st;
-    da.f = f_work;
-    da.g = g_work;
-    da.round = 0;
-    da.budget = budget;
-    da.n_pad = (st.n + 15) & ~15;
-    da.ldA = dual_row_pitch(da.n_pad);
-    da.rows = st.slots;
-    da.prof = dual_prof;
-    if (!pw_build(da.plan, st.n)) return hipErrorInvalidValue;
-    const int KT = big ? 32 : 16;
-    const int sample_bytes = (carve(KT, st.slots, da.ldA, da.n_pad, 4, da.plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
-    // phase B: sixteen bundles from offset 0 (they overlay phase A's buffers); the shared constant rows live behind
-    // whichever region is larger, where neither phase overwrites them
-    const int samples_off = 0, crow_bytes = (2 * da.ldA * 4 + 15) & ~15;
-    const int dual_bytes = samples_off + TM * sample_bytes;
-    int crow_off = ((fg_bytes > dual_bytes ? fg_bytes : dual_bytes) + 15) & ~15;
-    int lds = crow_off + crow_bytes;
-    FusedArgs args;
-    args.grouped = 0; args.group_cap = 0; args.need_off = 0;
-    if (lds > 160 * 1024 || big) {
-        // the sixteen full-size bundles do not fit together: groups sized by what the samples hold (FusedArgs::grouped).
-        // The staging region takes everything the workgroup can have; one sample's largest bundle must fit it.
-        const int need_bytes = 2 * TM * 4;            // per sample: bytes needed this round, and its done flag
-        crow_off = (160 * 1024 - 1024 - crow_bytes - need_bytes) & ~15;      // (1 KB: the kernel's static LDS, 256 B today)
-        if (crow_off < fg_bytes || crow_off < sample_bytes) return hipErrorNotSupported;
-        args.grouped = 1; args.group_cap = crow_off; args.need_off = crow_off + crow_bytes;
-        lds = args.need_off + need_bytes;
-    }
+    if (fill_args(m, args.fa, fg_bytes) != 0) return hipErrorInvalidValue;
+    args.fa.ctx = ctx; args.fa.y = st.y; args.fa.f = f_work; args.fa.g = g_work; args.fa.finished = st.skip_fg;
+    args.fa.batch = st.batch; args.fa.prof = nullptr; args.fa.tile_rows = tile_rows;
+    if (!make_dual_args(args.da, st, f_work, g_work, 0, budget, st.slots, dual_prof)) return hipErrorInvalidValue;
+    args.rounds = st.iters > 0 ? st.iters : st.slots;
+    args.crow_off = lay.crow_off; args.samples_off = 0; args.sample_bytes = lay.sample_bytes;
+    args.grouped = lay.grouped; args.group_cap = lay.group_cap; args.need_off = lay.need_off;
+    args.trace = dual_trace_buffer();
+    const bool rl = st.variant == ICNN_BE_VARIANT_RL, big = st.slots > 15;
     auto kern = big ? (rl ? fused_fc_solve_kernel<true, 32> : fused_fc_solve_kernel<false, 32>)
                     : (rl ? fused_fc_solve_kernel<true, 16> : fused_fc_solve_kernel<false, 16>);
-    if (ipm) kern = big ? fused_fc_solve_kernel<false, 32, true> : fused_fc_solve_kernel<false, 16, true>;
+    if (st.variant == ICNN_BE_VARIANT_PDIPM) kern = big ? fused_fc_solve_kernel<false, 32, true> : fused_fc_solve_kernel<false, 16, true>;
     if (budget > 0) kern = big ? fused_fc_solve_kernel<false, 32, false, true> : fused_fc_solve_kernel<false, 16, false, true>;
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-    args.da = da; args.fa = fa; args.trace = dual_trace_buffer();
-    args.rounds = st.iters > 0 ? st.iters : st.slots; args.crow_off = crow_off; args.samples_off = samples_off; args.sample_bytes = sample_bytes;
-    hipLaunchKernelGGL(kern, dim3((st.batch + tile_rows - 1) / tile_rows), dim3(NTHREADS), lds, stream, args);
-    return hipGetLastError();
+    return launch_kernel(kern, dim3((st.batch + tile_rows - 1) / tile_rows), dim3(NTHREADS), lay.lds, stream, args);
 }
 
 }  // namespace icnn_be

@@ -38,6 +38,31 @@ inline int dual_row_pitch(int n_pad) {
 hipError_t ensure_dynamic_lds(const void *kernel, int bytes);
 int device_cus();
 
+// Every launch of the library: raise the dynamic-LDS limit beyond the default 48 KB where needed, launch, report.
+template <typename... KArgs, typename... Args>
+hipError_t launch_kernel(void (*kern)(KArgs...), dim3 grid, dim3 block, int lds, hipStream_t stream, Args... args) {
+    if (lds > 48 * 1024)
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+// The dual-step arguments of every launcher (dual step, persistent kernels); false: n beyond the pairwise-sum plan
+inline bool make_dual_args(DualArgs &a, const icnn_be_state &st, const void *f, const void *g, int round, int budget, int rows,
+                           long long *prof) {
+    a = DualArgs{};
+    a.st = st;
+    a.f = f;
+    a.g = g;
+    a.round = round;
+    a.budget = budget;
+    a.n_pad = (st.n + 15) & ~15;
+    a.ldA = dual_row_pitch(a.n_pad);
+    a.rows = rows;
+    a.prof = prof;
+    return pw_build(a.plan, st.n);
+}
+
 int dual_lds_bytes(int n, int slots, int cut_dtype, int variant, int rows = 0);
 // most bundle rows (<= slots) whose staging fits the 160 KB of LDS; 0: not even one
 int dual_rows_fit(int n, int slots, int cut_dtype, int variant);
@@ -88,13 +113,25 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
                                float *work, hipStream_t stream);
 hipError_t launch_conv_clamp(const icnn_be_conv_model &m, int mode, hipStream_t stream);
 
-// Persistent per-tile solve (be_fused.hip); hipErrorNotSupported = shape outside this path, use the two-kernel rounds
-// budget: Newton updates a sample may spend per round before it is parked (0 = unlimited, lockstep inside the tile)
+// LDS layouts of the persistent kernels (be_fused.hip), host arithmetic only.  false: the shape does not fit that kernel.
+// The solve plan (be_api.hip) and the launchers below take their fit decisions from these two functions alone.
+struct FusedTileLayout {
+    int lds, crow_off, sample_bytes;
+    int grouped, group_cap, need_off;   // the dual phase in groups of samples whose bundles fit together (FusedArgs)
+};
+// per-tile solve, tile_rows samples per workgroup (4, 8 or 16); budget: Newton updates a sample may spend per round before
+// it is parked (<= 0: unlimited, lockstep inside the tile)
+bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget, FusedTileLayout &out);
+struct FusedRowsLayout {
+    int lds, dual_off, sample_bytes, crow_off;
+};
+// per-sample solve, per_wg (1..4) samples per workgroup; resume: the finishing launch after budgeted rounds
+bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int per_wg, bool resume, FusedRowsLayout &out);
+// hipErrorInvalidValue: a shape the layout functions refuse (the plan never sends one)
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows = 16, int budget = 0);
-// persistent workgroup per sample or pair of samples (batches of at most two samples per CU)
+                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget);
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume = false);
+                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume);
 int dual_waves(int n, int cut_dtype, int variant);
 long long *dual_profile_buffer();
 void set_dual_trace_buffer(long long *buf);

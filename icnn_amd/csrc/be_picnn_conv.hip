@@ -760,16 +760,12 @@ hipError_t launch_conv_fg(const icnn_be_conv_model &m, const float *ctx, const d
     a.a4 = w; w += (size_t)batch * a.fch;
     a.d3 = w; w += (size_t)batch * a.fch;
     a.d2 = w;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(conv_fwd_kernel), L.lds_fwd);
-    if (e == hipSuccess) e = ensure_dynamic_lds(reinterpret_cast<const void *>(conv_bwd_kernel), L.lds_bwd);
-    if (e == hipSuccess) e = ensure_dynamic_lds(reinterpret_cast<const void *>(conv_fc_bwd_kernel), L.lds_fcb);
-    if (e != hipSuccess) return e;
     const int tiles = (batch + 15) / 16, per = FT / 64;
-    hipLaunchKernelGGL(conv_fwd_kernel, dim3(batch), dim3(CT), L.lds_fwd, stream, a);
-    hipLaunchKernelGGL(conv_fc_fwd_kernel, dim3(a.fch / 16, tiles), dim3(FT), 0, stream, a);
-    hipLaunchKernelGGL(conv_fc_bwd_kernel, dim3((a.flat / 16 + per - 1) / per, tiles), dim3(FT), L.lds_fcb, stream, a);
-    hipLaunchKernelGGL(conv_bwd_kernel, dim3(batch), dim3(CT), L.lds_bwd, stream, a);
-    return hipGetLastError();
+    hipError_t e = launch_kernel(conv_fwd_kernel, dim3(batch), dim3(CT), L.lds_fwd, stream, a);
+    if (e == hipSuccess) e = launch_kernel(conv_fc_fwd_kernel, dim3(a.fch / 16, tiles), dim3(FT), 0, stream, a);
+    if (e == hipSuccess) e = launch_kernel(conv_fc_bwd_kernel, dim3((a.flat / 16 + per - 1) / per, tiles), dim3(FT), L.lds_fcb, stream, a);
+    if (e == hipSuccess) e = launch_kernel(conv_bwd_kernel, dim3(batch), dim3(CT), L.lds_bwd, stream, a);
+    return e;
 }
 
 }  // namespace icnn_be

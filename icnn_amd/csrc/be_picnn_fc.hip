@@ -93,14 +93,10 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
         if (per_wg <= 2 && rows_lds <= 160 * 1024) {        // at most two samples per CU
             r.fa = a;
             r.per_wg = per_wg;
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fc_fg_rows_kernel), rows_lds); e != hipSuccess) return e;
-            hipLaunchKernelGGL(fc_fg_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_lds, stream, r);
-            return hipGetLastError();
+            return launch_kernel(fc_fg_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_lds, stream, r);
         }
     }
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(fc_fg_kernel), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(fc_fg_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(fc_fg_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
 }
 
 hipError_t launch_fc_clamp(const icnn_be_fc_model &m, int mode, hipStream_t stream) {

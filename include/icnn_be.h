@@ -38,7 +38,7 @@ extern "C" {
 #define ICNN_BE_API
 #endif
 
-#define ICNN_BE_ABI_VERSION 10
+#define ICNN_BE_ABI_VERSION 11
 #define ICNN_BE_MAX_LAYERS 8   /* z-layers of a PICNN including the final scalar one */
 #define ICNN_BE_MAX_SLOTS 31   /* bundle slots (= outer iterations) per solve */
 #define ICNN_BE_MAX_ITERS 64   /* outer iterations per solve (icnn_be_state.iters; beyond MAX_SLOTS the slots are recycled) */
@@ -74,6 +74,14 @@ extern "C" {
                                   enough: a sample has nIter iterations and a finishing round completes one --; a sample
                                   still behind after them would say so here (safety net of icnn_be_solve_conv) */
 
+/* how icnn_be_solve_fc runs a solve (icnn_be_debug_solve_plan) */
+#define ICNN_BE_PATH_ROWS 0                     /* one launch of the persistent per-sample kernel (1-4 samples per workgroup) */
+#define ICNN_BE_PATH_TILE 1                     /* one launch of the persistent per-tile kernel (4, 8 or 16 samples) */
+#define ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS 2  /* per-tile kernel with an update budget + one finishing per-sample launch */
+#define ICNN_BE_PATH_ROUNDS_LOCKSTEP 3          /* nIter rounds of { icnn_be_fc_fg ; dual step } launches */
+#define ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS 4  /* nIter time-sliced rounds + one finishing per-sample launch */
+#define ICNN_BE_PATH_ROUNDS_SLICED_EXTRA 5      /* nIter time-sliced rounds + nIter unbudgeted rounds for the stragglers */
+
 /* return codes */
 #define ICNN_BE_EINVAL (-1)    /* bad argument */
 #define ICNN_BE_ELIMIT (-2)    /* size beyond a compiled-in limit */
@@ -94,15 +102,10 @@ extern "C" {
 #define ICNN_BE_FLAG_LOCKSTEP 4          /* fused solve: never do that; exactly nIter rounds, no sync.
                                             Neither flag: time slicing when nIter > 15 (measured) */
 #define ICNN_BE_FLAG_TWO_KERNELS 8       /* icnn_be_solve_fc: one launch per phase and round, never a persistent kernel */
-#define ICNN_BE_FLAG_PERSISTENT 16       /* icnn_be_solve_fc: the persistent per-tile kernel (a workgroup per 16 samples)
-                                          * whenever the shape fits it (float32 cuts, nIter <= 15, narrow rows, lockstep),
-                                          * whatever the batch size (with 4- or 8-sample partial tiles below one full tile per CU).
-                                          * Default (no flag): a persistent workgroup per 1-4
-                                          * samples for batches of at most four samples per CU (MI355X: <= 1024; any nIter,
-                                          * no time slicing needed), the per-tile kernel for batches that
-                                          * give every CU between a quarter of a tile and two tiles (1024..8192, variants dual and -- round 4 --
-                                          * pdipm, which always runs in lockstep rounds: its solve has a fixed iteration cap),
-                                          * two kernels otherwise.  Results are bit-identical whichever path runs. */
+#define ICNN_BE_FLAG_PERSISTENT 16       /* icnn_be_solve_fc: the persistent per-tile kernel (a workgroup per 4, 8 or 16
+                                          * samples) wherever the shape fits it, whatever the batch size.  Without a flag
+                                          * the batch size, nIter and the variant choose the path; icnn_be_debug_solve_plan
+                                          * reports which.  Results are bit-identical whichever path runs. */
 
 #define ICNN_BE_FLAG_WAVE_PER_SAMPLE 128  /* narrow rows (n <= 16, variant RL) run four samples per wave by default (one per
                                           * 16-lane DPP row, be_dual_small.hip); this flag keeps the wave-per-sample kernel.
@@ -513,6 +516,13 @@ ICNN_BE_API int icnn_be_debug_profile_phases(void);
 ICNN_BE_API int icnn_be_debug_fast_math(int which, const double *x, double *out, int count, void *stream);
 ICNN_BE_API void icnn_be_debug_profile_fc(long long *device_buf);
 ICNN_BE_API void icnn_be_debug_profile_conv(long long *device_buf);
+/*
+ * The plan icnn_be_solve_fc follows for this model and state on a device with `cus` CUs (cus < 1: the current device's):
+ * returns an ICNN_BE_PATH_* code and fills out = { samples per workgroup of the persistent kernel (0: launch pairs), Newton
+ * updates per sample and round (0: unlimited), the value icnn_be_solve_fc returns }, or a negative error code (batch 0:
+ * ICNN_BE_EINVAL, nothing is planned).  Host arithmetic only: needs neither a GPU nor any buffer of the model or the state.
+ */
+ICNN_BE_API int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state *st, int cus, int out[3]);
 
 #ifdef __cplusplus
 }

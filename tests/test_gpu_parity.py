@@ -31,6 +31,15 @@ def _solve(prob, n_iter, variant, **kw):
     return y0, res
 
 
+def _planned(model, res):
+    """The plan icnn_be_solve_fc followed for this FC solve (icnn_be_debug_solve_plan on the solve's own descriptors): asserts
+    that the solve issued the rounds the plan says and returns (path, samples per workgroup, budget, rounds)."""
+    from icnn_amd import _lib
+    plan = _lib.solve_plan(model.c_model, res.state.c_state)
+    assert res.state.rounds == plan[3], (plan, res.state.rounds)
+    return plan
+
+
 @pytest.mark.parametrize("case", DUAL_CASES)
 def test_dual_variant_matches_reference_golden(case):
     factory, n_iter = problems.GOLDEN_CASES[case]
@@ -233,15 +242,17 @@ def test_pdipm_persistent_kernels_equal_two_kernel_rounds(B, n_iter):
     params, x = _picnn_problem(spec, max(B, 64), 5, "spread")
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))[:B].contiguous()
-    outs, rounds = [], []
+    outs, rounds, plans = [], [], []
     for flags in (0, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "pdipm", flags=flags).solve(ctx, 0.5)
         outs.append(_all_outputs(res, B))
         rounds.append(res.state.rounds)
+        plans.append(_planned(model, res))
     for i, (a, b) in enumerate(zip(*outs)):
         assert np.array_equal(a, b), "output %d differs between the persistent kernel and launch pairs" % i
     assert (outs[0][10] == 0).all() and outs[0][3].max() > 1
     assert rounds == [n_iter, n_iter], rounds
+    assert plans[0][0] != plans[1][0], plans
 
 
 @pytest.mark.parametrize("n,variant,n_iter", [(300, "dual", 8), (700, "dual", 8), (300, "rl", 8), (300, "pdipm", 8),
@@ -449,12 +460,14 @@ def test_persistent_tile_kernel_equals_two_kernel_rounds(B, n_iter):
     x = (np.random.RandomState(77).rand(B, spec.n_features) < 0.04).astype(np.float32)
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))
-    outs = []
+    outs, plans = [], []
     for flags in (_lib.FLAG_PERSISTENT, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=flags).solve(ctx, 0.5)
+        plans.append(_planned(model, res))
         outs.append([t.cpu().numpy().copy() for t in (res.y, res.lam, res.active, res.count[:B], res.n_iters[:B],
                                                        res.newton_iters[:B], res.state.G, res.state.h, res.state.ys,
                                                        res.finished[:B], res.status[:B])])
+    assert plans[0][0] != plans[1][0], plans
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
@@ -478,12 +491,14 @@ def test_persistent_per_sample_kernel_equals_two_kernel_rounds(which, B, n_iter)
         x = np.random.RandomState(80).randn(max(B, 64), spec.n_features).astype(np.float32)
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))[:B].contiguous()
-    outs = []
+    outs, plans = [], []
     for flags in (0, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, variant, flags=flags).solve(ctx, 0.5)
+        plans.append(_planned(model, res))
         outs.append([t.cpu().numpy().copy() for t in (res.y, res.lam, res.active, res.count[:B], res.n_iters[:B],
                                                        res.newton_iters[:B], res.state.G, res.state.h, res.state.ys,
                                                        res.finished[:B], res.status[:B])])
+    assert plans[0][0] != plans[1][0], plans
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
@@ -500,12 +515,14 @@ def test_stragglers_of_time_sliced_rounds_finish_in_one_persistent_launch():
     x = (np.random.RandomState(81).rand(B, spec.n_features) < 0.04).astype(np.float32)
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))
-    outs = []
+    outs, plans = [], []
     for flags in (0, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=flags).solve(ctx, 0.5)
+        plans.append(_planned(model, res))
         outs.append([t.cpu().numpy().copy() for t in (res.y, res.lam, res.active, res.count[:B], res.n_iters[:B],
                                                        res.newton_iters[:B], res.state.G, res.state.h, res.state.ys,
                                                        res.finished[:B], res.status[:B])])
+    assert plans[0][0] != plans[1][0], plans
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
     assert outs[0][5].max() > 8 * n_iter / 2          # a sample with that many updates was parked along the way
@@ -522,14 +539,16 @@ def test_budgeted_tile_kernel_with_finishing_launch_equals_lockstep_tiles(B, n_i
     params, x = _picnn_problem(spec, B, 9, "spread")
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))
-    outs, rounds = [], []
+    outs, rounds, plans = [], [], []
     for flags in (_lib.FLAG_PERSISTENT, _lib.FLAG_PERSISTENT | _lib.FLAG_TIME_SLICE):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=flags).solve(ctx, 0.5)
         outs.append(_all_outputs(res, B))
         rounds.append(res.state.rounds)
+        plans.append(_planned(model, res))
     for i, (a, b) in enumerate(zip(*outs)):
         assert np.array_equal(a, b), "output %d differs" % i
     assert rounds == [n_iter, n_iter + 1], rounds
+    assert plans[0][0] != plans[1][0], plans
 
 
 def test_wide_rows_more_iterations_than_lds_rows():
@@ -615,11 +634,13 @@ def test_one_wave_valu_contraction_agrees_with_mfma_sweep(B, n_iter):
     params, x = _picnn_problem(spec, max(B, 64), 4, "spread")
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))[:B].contiguous()
-    outs = {}
+    outs, plans = {}, {}
     for mode in (0, _lib.FLAG_MFMA_CONTRACTION):
         for path in (0, _lib.FLAG_TWO_KERNELS):
             res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=mode | path).solve(ctx, 0.5)
             outs[(mode, path)] = _all_outputs(res, B)
+            plans[path] = _planned(model, res)
+        assert plans[0][0] != plans[_lib.FLAG_TWO_KERNELS][0], plans
         for i, (a, b) in enumerate(zip(outs[(mode, 0)], outs[(mode, _lib.FLAG_TWO_KERNELS)])):
             assert np.array_equal(a, b), "mode %d: output %d differs between the dispatch paths" % (mode, i)
     v, m = outs[(0, 0)], outs[(_lib.FLAG_MFMA_CONTRACTION, 0)]
@@ -715,11 +736,13 @@ def test_persistent_tile_kernel_rl_variant_equals_two_kernel_rounds():
     x = np.random.RandomState(78).randn(B, spec.n_features).astype(np.float32)
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))
-    outs = []
+    outs, plans = [], []
     for flags in (_lib.FLAG_PERSISTENT, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "rl", flags=flags).solve(ctx, 0.5)
+        plans.append(_planned(model, res))
         outs.append([t.cpu().numpy().copy() for t in (res.y, res.lam, res.active, res.count[:B], res.n_iters[:B],
                                                        res.finished[:B], res.status[:B])])
+    assert plans[0][0] != plans[1][0], plans
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
 
@@ -1655,16 +1678,18 @@ def test_more_iterations_than_slots_recycle_the_slots_of_pruned_cuts(B, n_iter):
     fg = picnn_oracle.make_fg_chain(params, ctx_rows, list(spec.szs))
     with np.errstate(all="ignore"):
         ora = oracle.solve_batch(fg, np.full((S, spec.n_labels), 0.5), n_iter)
-    outs = []
+    outs, plans = [], []
     for flags in (0, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=flags).solve(ctx, 0.5)
         outs.append(_all_outputs(res, B))
+        plans.append(_planned(model, res))
         host = result_to_host(res)
         assert (host["status"] == 0).all() and res.state.T == 31
         _assert_slice_parity(_slice_host(host, np.arange(S)), ora,
                              lambda rows: picnn_oracle.make_fg_chain(params, ctx_rows[rows], list(spec.szs)),
                              np.full((S, spec.n_labels), 0.5), n_iter, 1e-7, "nIter=%d flags=%d" % (n_iter, flags),
                              max_hard_frac=0.1, same_slots=False)
+    assert plans[0][0] != plans[1][0], plans
     for i, (a, b) in enumerate(zip(*outs)):
         assert np.array_equal(a, b), "output %d differs between the dispatch paths" % i
     ran_out = outs[0][9] == 0                               # samples that never left the loop ran all nIter iterations
@@ -1685,11 +1710,13 @@ def test_full_bundle_reports_overflow_on_every_dispatch_path(B, slots, n_iter):
     params, x = _picnn_problem(spec, max(B, 64), 8, "spread")
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))[:B].contiguous()
-    outs = []
+    outs, plans = [], []
     for flags in (0, _lib.FLAG_TWO_KERNELS):
         res = bundle_entropy.FusedSolver(model, B, n_iter, "dual", flags=flags, slots=slots).solve(ctx, 0.5)
         assert res.state.T == slots
         outs.append(_all_outputs(res, B))
+        plans.append(_planned(model, res))
+    assert plans[0][0] != plans[1][0], plans
     status = outs[0][10]
     over = (status & _lib.ST_OVERFLOW) != 0
     assert over.any(), "no sample filled its %d slots: the test does not exercise the bound" % slots
@@ -1711,12 +1738,14 @@ def test_time_sliced_rounds_equal_lockstep_rounds():
     params, x = _picnn_problem(spec, B, 0, "spread")
     model = picnn.FCModel(spec, params)
     ctx = model.context(torch.from_numpy(x))
-    out = []
+    out, plans = [], []
     for flags in (_lib.FLAG_TIME_SLICE, _lib.FLAG_LOCKSTEP):
         y0 = torch.full((B, spec.n_labels), 0.5, dtype=torch.float64, device="cuda")
         res = bundle_entropy.solveBatch(f=model, ctx=ctx, y0=y0, nIter=n_iter, native=True, flags=flags)
         out.append((result_to_host(res), res.state.rounds))
+        plans.append(_planned(model, res))
     (a, ra), (b, rb) = out
+    assert plans[0][0] != plans[1][0], plans
     assert rb == n_iter and ra >= n_iter
     assert a["newton"].max() > 8, "workload should contain solves longer than one slice"
     assert np.array_equal(a["y"], b["y"]) and a["active"] == b["active"] and a["n_iters"] == b["n_iters"]
