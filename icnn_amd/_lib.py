@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libicnn_be.so")
 if os.environ.get("ICNN_BE_LIB"):          # diagnostic: another build of the same ABI (tools/lib_ab.py: same-box A/B of two builds)
     LIB_PATH = os.path.abspath(os.environ["ICNN_BE_LIB"])
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_LAYERS = 8
 MAX_SLOTS = 31
 MAX_ITERS = 64
@@ -50,6 +50,7 @@ EXPORTS = [
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan",
+    "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 
@@ -198,6 +199,14 @@ def load():
     lib.icnn_be_conv_context.restype = C.c_int
     lib.icnn_be_conv_clamp.argtypes = [C.POINTER(ConvModel), C.c_int, C.c_void_p]
     lib.icnn_be_conv_clamp.restype = C.c_int
+    lib.icnn_be_fc_grad_floats.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx)]
+    lib.icnn_be_fc_grad_floats.restype = C.c_size_t
+    lib.icnn_be_fc_surrogate_grad_work_floats.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx), C.c_int, C.c_int]
+    lib.icnn_be_fc_surrogate_grad_work_floats.restype = C.c_size_t
+    lib.icnn_be_fc_surrogate_grad.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    lib.icnn_be_fc_surrogate_grad.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
     if tuple(lib.icnn_be_struct_size(i) for i in range(5)) != (

@@ -309,6 +309,27 @@ int icnn_be_fc_context(const icnn_be_fc_ctx *c, const float *x, int batch, float
     return e == hipSuccess ? 0 : fail(e);
 }
 
+size_t icnn_be_fc_grad_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c) {
+    if (!model || !c) return 0;
+    return icnn_be::fc_grad_floats(*model, *c);
+}
+
+size_t icnn_be_fc_surrogate_grad_work_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, int batch, int rows) {
+    if (!model || !c) return 0;
+    return icnn_be::fc_surrogate_work_floats(*model, *c, batch, rows);
+}
+
+int icnn_be_fc_surrogate_grad(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                              const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                              float *grad, float *F_rows, float *work, void *stream) {
+    if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ctx_check(*c)) return rc;
+    if (int rc = icnn_be::fc_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
+    hipError_t e = icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                     static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_fc_context_stage(const icnn_be_fc_ctx *c, int stage, const float *x, int batch, float *ctx, int ctx_width,
                              float *work, double *stats, void *stream) {
     /* an empty shard (a rank of a data-parallel group whose batch is smaller than the group) has no rows: its zero-element

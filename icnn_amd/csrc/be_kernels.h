@@ -113,6 +113,14 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
                                float *work, hipStream_t stream);
 hipError_t launch_conv_clamp(const icnn_be_conv_model &m, int mode, hipStream_t stream);
 
+// training gradient of the FC PICNN (be_train_fc.hip): sizes (0 = shape rejected), shape check, launcher
+size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c);
+size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows);
+int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool with_v);
+hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
+                                    const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                    float *grad, float *F_rows, float *work, hipStream_t stream);
+
 // LDS layouts of the persistent kernels (be_fused.hip), host arithmetic only.  false: the shape does not fit that kernel.
 // The solve plan (be_api.hip) and the launchers below take their fit decisions from these two functions alone.
 struct FusedTileLayout {

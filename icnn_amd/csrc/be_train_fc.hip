@@ -1,0 +1,660 @@
+// Training step of the fully-connected PICNN on the device: the parameter gradient of the reference's surrogate
+//   F = sum_r c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r>          multi-label-cls/icnn_ebundle.py:148-156
+// (v absent: the RL critic's c-weighted energy, RL/src/icnn.py:90-109) over every trainable variable.
+//
+// Structure (DESIGN.md "Training gradient"):
+//   1. x-only forward on the B unique samples, not on the R feed rows: the stage GEMMs are the context producer's
+//      (launch_fc_context_stage, be_context.hip); BatchNorm is weighted by the multiplicity m_j of each sample, which
+//      equals BatchNorm over the R repeated rows the reference feeds.  The context rows, the ReLU'd u-path values and
+//      x-hat / inv-std are kept for the backward pass.
+//   2. y-path on the R rows, layer by layer: the primal rows and the tangent rows (direction v) are stacked into one
+//      [2R][n + width_{i-1}] operand [ y*yu_i | z_{i-1}*gate_i ; v*yu_i | zdot_{i-1}*gate_i ] so that one GEMM with the
+//      stacked weights [Wyu_i ; Wzu_i] gives both pre-activations.  The reverse pass runs the two adjoint columns
+//      (abar seeded with c_r, adot seeded with 1) through the same masks: per layer one GEMM for the weight gradient
+//      of each operand (K = 2R) and one for the adjoints / context gradient.
+//   3. fixed-order segment sum of the per-row context gradient over the rows of each sample.
+//   4. x-only backward on B rows: head ReLUs, dW_stage = prev^T dpre, bias sums, dprev = dpre W_stage^T, ReLU and the
+//      weighted BatchNorm backward with its batch-statistics terms, down to u0.
+// Every product runs through ONE f32-MFMA GEMM kernel on strided operands with split-K and a fixed-order second pass:
+// no atomics anywhere, so the gradient is the same bits on every run and the whole entry can be captured in a graph.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+
+#include "be_picnn_fc_dev.h"   // the packed y-path layout (pack_offsets, kblocks, pad16)
+
+namespace icnn_be {
+
+namespace {
+
+constexpr int GBM = 64, GBN = 64, GBK = 16, GT_ = 256, GPITCH = GBK + 4;
+
+// C_part[split][M][N] = sum over k in split's chunk of A(m, k) B(k, n); A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn]
+struct TrGemmArgs {
+    const float *A, *B;
+    long long sam, sak, sbk, sbn;
+    int M, N, K, kchunk;
+    float *part;
+};
+
+__global__ __launch_bounds__(GT_) void tr_gemm_kernel(TrGemmArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[GBM][GPITCH];
+    __shared__ __attribute__((aligned(16))) float Bt[GBN][GPITCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
+    const int m0 = blockIdx.x * GBM, n0 = blockIdx.y * GBN;
+    const int k_beg = blockIdx.z * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
+    const bool a_kfast = a.sak == 1, b_nfast = a.sbn == 1;    // walk the unit-stride index across neighbouring lanes
+    f4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = k_beg; k0 < k_end; k0 += GBK) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int e = tid + GT_ * p;
+            const int ar = a_kfast ? e >> 4 : e & 63, ak = a_kfast ? e & 15 : e >> 6;
+            const int m = m0 + ar, k = k0 + ak;
+            As[ar][ak] = (m < a.M && k < k_end) ? a.A[(size_t)m * a.sam + (size_t)k * a.sak] : 0.f;
+            const int bc = b_nfast ? e & 63 : e >> 4, bk = b_nfast ? e >> 6 : e & 15;
+            const int n = n0 + bc, kb = k0 + bk;
+            Bt[bc][bk] = (n < a.N && kb < k_end) ? a.B[(size_t)kb * a.sbk + (size_t)n * a.sbn] : 0.f;
+        }
+        __syncthreads();
+        const f4 af = *reinterpret_cast<const f4 *>(&As[16 * wave + r16][4 * q]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const f4 bf = *reinterpret_cast<const f4 *>(&Bt[16 * t + r16][4 * q]);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.x, bf.x, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.y, bf.y, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, bf.z, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.w, bf.w, acc[t], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // acc[t][r] = C[m0 + 16 wave + 4 q + r][n0 + 16 t + r16]
+    float *out = a.part + (size_t)blockIdx.z * a.M * a.N;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int col = n0 + 16 * t + r16;
+        if (col >= a.N) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = m0 + 16 * wave + 4 * q + r;
+            if (row < a.M) out[(size_t)row * a.N + col] = acc[t][r];
+        }
+    }
+}
+
+// second pass: C[m][n] (pitch ldc) = sum_s part[s][m][n], splits in order
+__global__ void tr_gemm_reduce_kernel(const float *part, int splits, int M, int N, float *C, long long ldc) {
+    const size_t total = (size_t)M * N;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        float s = part[i];
+        for (int sp = 1; sp < splits; ++sp) s += part[(size_t)sp * total + i];
+        const size_t m = i / N, n = i - m * N;
+        C[m * ldc + n] = s;
+    }
+}
+
+// Row bookkeeping: samp[r] = the sample whose segment [row_offset[j], row_offset[j+1]) holds r (binary search, clamped to
+// 0..B-1 whatever row_offset holds), mult[j] = its row count as a float (the BatchNorm weight)
+__global__ void tr_rows_kernel(const int *row_offset, int B, int R, int *samp, float *mult) {
+    const int total = R > B ? R : B;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        if (i < R) {
+            int lo = 0, hi = B - 1;             // last j with row_offset[j] <= i
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (row_offset[mid] <= i) lo = mid; else hi = mid - 1;
+            }
+            samp[i] = lo;
+        }
+        if (i < B) {
+            const int a = min(max(row_offset[i], 0), R), b = min(max(row_offset[i + 1], 0), R);
+            mult[i] = b > a ? (float)(b - a) : 0.f;
+        }
+    }
+}
+
+// The y-path weights of every layer out of the packed fragments (both orientations are there; the forward one is read):
+// Wst_i[(n + w_{i-1})][w_i] = [ Wyu_i ; Wzu_i ] row-major
+struct UnpackArgs {
+    const float *wpack;
+    long long yu_f, zu_f;
+    int n, wprev, w, last;
+    float *dst;
+};
+__device__ __forceinline__ float packed_at(const float *p, int N, int k, int col) {
+    const int NT = pad16(N) / 16, kb = k >> 4, kk = k & 15, lane = (kk >> 2) * 16 + (col & 15), nt = col >> 4;
+    return p[((size_t)(kb * NT + nt) * 64 + lane) * 4 + (kk & 3)];
+}
+__global__ void tr_unpack_kernel(UnpackArgs a) {
+    const int rows = a.n + a.wprev, total = rows * a.w;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int k = i / a.w, col = i - k * a.w;
+        float v;
+        if (a.last) v = k < a.n ? a.wpack[a.yu_f + k] : a.wpack[a.zu_f + (k - a.n)];
+        else v = k < a.n ? packed_at(a.wpack + a.yu_f, a.w, k, col) : packed_at(a.wpack + a.zu_f, a.w, k - a.n, col);
+        a.dst[i] = v;
+    }
+}
+
+// network input of row r, column j: y rounded to float32 like a TensorFlow feed, 2y-1 for the RL wrapper; its tangent
+// direction v (times 2 for the wrapper, RL/src/icnn.py:148-158) -- as icnn_be_fc_fg reads y
+__device__ __forceinline__ float net_y(const double *y, size_t i, int box) { return box ? (float)(2.0 * y[i] - 1.0) : (float)y[i]; }
+__device__ __forceinline__ float net_v(const double *v, size_t i, int box) { return box ? 2.f * (float)v[i] : (float)v[i]; }
+
+struct RowArgs {
+    const double *y, *v, *c;
+    const int *samp;
+    const float *ctx;
+    int R, n, C, box;
+};
+
+// PQ_i[:, 0:n) = [ y*yu_i ; v*yu_i ]  (pitch ld)
+__global__ void tr_build_p_kernel(RowArgs a, int yu_off, float *pq, int ld) {
+    const int total = a.R * a.n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int r = i / a.n, j = i - r * a.n;
+        const float yu = a.ctx[(size_t)a.samp[r] * a.C + yu_off + j];
+        pq[(size_t)r * ld + j] = net_y(a.y, i, a.box) * yu;
+        if (a.v) pq[(size_t)(a.R + r) * ld + j] = net_v(a.v, i, a.box) * yu;
+    }
+}
+
+// hidden layer i: a = pre + zu_i;  z = act(a), d = act'(a), zdot = d * pre_dot;  PQ_{i+1}[:, n + k] = [z ; zdot] * gate_{i+1}
+__global__ void tr_hidden_fwd_kernel(RowArgs a, const float *pre, int w, int zu_off, int gate_next_off, float alpha, float *Z,
+                                     float *D, float *pq_next, int ld_next) {
+    const int total = a.R * w;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int r = i / w, k = i - r * w;
+        const float *crow = a.ctx + (size_t)a.samp[r] * a.C;
+        const float p = pre[i] + crow[zu_off + k];
+        const float d = p > 0.f ? 1.f : alpha;
+        const float z = p > 0.f ? p : alpha * p, g = crow[gate_next_off + k];
+        Z[i] = z;
+        D[i] = d;
+        pq_next[(size_t)r * ld_next + a.n + k] = z * g;
+        if (a.v) {
+            const float zd = d * pre[(size_t)a.R * w + i];
+            Z[(size_t)a.R * w + i] = zd;
+            pq_next[(size_t)(a.R + r) * ld_next + a.n + k] = zd * g;
+        }
+    }
+}
+
+// last layer: F_r = c_r (pre_r + zu_L) + pre_dot_r; adjoint seeds abar = c_r, adot = 1
+__global__ void tr_final_kernel(RowArgs a, const float *pre, int zu_off, float *F, float *adj) {
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += gridDim.x * blockDim.x) {
+        const float c = (float)a.c[r];
+        if (F) {
+            const float e = pre[r] + a.ctx[(size_t)a.samp[r] * a.C + zu_off];
+            F[r] = c * e + (a.v ? pre[a.R + r] : 0.f);
+        }
+        adj[r] = c;
+        if (a.v) adj[a.R + r] = 1.f;
+    }
+}
+
+// reverse step of layer i from BD = [abar_i ; adot_i] [Wyu_i ; Wzu_i]^T ([2R][n + wprev]):
+//   dyu_i = y * BD[r][0:n) + v * BD[R+r][0:n),   dzu_i = abar_i,
+//   dgate_i = z_{i-1} * BD[r][n:) + zdot_{i-1} * BD[R+r][n:),   [abar ; adot]_{i-1} = act'(a_{i-1}) * gate_i * BD[.][n:)
+struct BackArgs {
+    const float *BD, *adj, *Zp, *Dp;
+    float *adj_prev, *dctx;          // dctx: per-row context gradient [R][C]
+    int w, wprev, yu_off, zu_off, gate_off;
+};
+__global__ void tr_back_rows_kernel(RowArgs a, BackArgs b) {
+    const int cols = a.n + b.wprev + b.w, ldb = a.n + b.wprev, total = a.R * cols;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int r = i / cols, j = i - r * cols;
+        float *drow = b.dctx + (size_t)r * a.C;
+        if (j < a.n) {
+            const size_t yi = (size_t)r * a.n + j;
+            float g = net_y(a.y, yi, a.box) * b.BD[(size_t)r * ldb + j];
+            if (a.v) g += net_v(a.v, yi, a.box) * b.BD[(size_t)(a.R + r) * ldb + j];
+            drow[b.yu_off + j] = g;
+        } else if (j < ldb) {
+            const int k = j - a.n;
+            const size_t zi = (size_t)r * b.wprev + k, zr = (size_t)a.R * b.wprev;
+            const float bd = b.BD[(size_t)r * ldb + j];
+            const float gt = a.ctx[(size_t)a.samp[r] * a.C + b.gate_off + k], dg = b.Dp[zi] * gt;
+            float g = b.Zp[zi] * bd;
+            b.adj_prev[zi] = dg * bd;
+            if (a.v) {
+                const float bdd = b.BD[(size_t)(a.R + r) * ldb + j];
+                g += b.Zp[zr + zi] * bdd;
+                b.adj_prev[zr + zi] = dg * bdd;
+            }
+            drow[b.gate_off + k] = g;
+        } else {
+            const int k = j - ldb;
+            drow[b.zu_off + k] = b.adj[(size_t)r * b.w + k];
+        }
+    }
+}
+
+// dctx[j][col] = sum of the rows of sample j, in row order
+__global__ void tr_segment_sum_kernel(const float *rows, const int *row_offset, int B, int R, int C, float *out) {
+    const size_t total = (size_t)B * C;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i / C), col = (int)(i - (size_t)j * C);
+        const int r0 = min(max(row_offset[j], 0), R), r1 = min(max(row_offset[j + 1], 0), R);
+        float s = 0.f;
+        for (int r = r0; r < r1; ++r) s += rows[(size_t)r * C + col];
+        out[i] = s;
+    }
+}
+
+// Weighted batch statistics (BatchNorm in training mode over the R feed rows = over the B samples with weights m_j):
+// one workgroup per 32 columns, fixed-order tree.  h (the ReLU'd stage output, pitch ld) is copied to hsave, u = gamma
+// xhat + beta replaces it in place (the next stage reads it there), xhat and inv-std are kept for the backward pass.
+constexpr int WBT = 256, WBC = 32, WBG = WBT / WBC;
+__global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B, int N, const float *mult, float M,
+                                                         const float *gamma, const float *beta, float eps, float *hsave,
+                                                         float *xhat, float *inv_out) {
+    __shared__ float red[WBG][WBC];
+    __shared__ float stat[2][WBC];
+    const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.x * WBC + c;
+    const bool ok = col < N;
+    auto total = [&](float mine, float *out) {
+        red[g][c] = mine;
+        __syncthreads();
+        if (g == 0) {
+            float t = 0.f;
+            for (int i = 0; i < WBG; ++i) t += red[i][c];
+            *out = t / M;
+        }
+        __syncthreads();
+    };
+    float s = 0.f;
+    if (ok) for (int j = g; j < B; j += WBG) s += mult[j] * u[(size_t)j * ld + col];
+    total(s, &stat[0][c]);
+    const float mean = stat[0][c];
+    s = 0.f;
+    if (ok) for (int j = g; j < B; j += WBG) {
+        const float d = u[(size_t)j * ld + col] - mean;
+        s += mult[j] * d * d;
+    }
+    total(s, &stat[1][c]);
+    if (!ok) return;
+    const float inv = 1.f / sqrtf(stat[1][c] + eps), ga = gamma[col], be = beta[col];
+    if (g == 0) inv_out[col] = inv;
+    for (int j = g; j < B; j += WBG) {
+        const float h = u[(size_t)j * ld + col], xh = (h - mean) * inv;
+        hsave[(size_t)j * N + col] = h;
+        xhat[(size_t)j * N + col] = xh;
+        u[(size_t)j * ld + col] = ga * xh + be;
+    }
+}
+
+// du (gradient at u_i, [B][N]) -> the u columns of dpre_i (pitch ld_dpre).  mode 0: linear (last u layer); 1: ReLU only,
+// mask from u itself; 2: weighted BatchNorm backward then ReLU:
+//   S1 = sum_j du_j, S2 = sum_j du_j xhat_j,  dh_j = gamma inv (du_j - m_j / M (S1 + xhat_j S2)),  dgamma = S2, dbeta = S1
+__global__ __launch_bounds__(WBT) void tr_u_back_kernel(const float *du, int B, int N, int mode, const float *u, int ld_u,
+                                                        const float *hsave, const float *xhat, const float *inv,
+                                                        const float *gamma, const float *mult, float M, float *dpre,
+                                                        int ld_dpre, float *dgamma, float *dbeta) {
+    __shared__ float red[WBG][WBC];
+    __shared__ float stat[2][WBC];
+    const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.x * WBC + c;
+    const bool ok = col < N;
+    float s1 = 0.f, s2 = 0.f;
+    if (mode == 2) {
+        if (ok) for (int j = g; j < B; j += WBG) {
+            const float d = du[(size_t)j * N + col];
+            s1 += d;
+            s2 += d * xhat[(size_t)j * N + col];
+        }
+        for (int which = 0; which < 2; ++which) {
+            red[g][c] = which ? s2 : s1;
+            __syncthreads();
+            if (g == 0) {
+                float t = 0.f;
+                for (int i = 0; i < WBG; ++i) t += red[i][c];
+                stat[which][c] = t;
+            }
+            __syncthreads();
+        }
+        s1 = stat[0][c];
+        s2 = stat[1][c];
+        if (ok && g == 0) { dgamma[col] = s2; dbeta[col] = s1; }
+    }
+    if (!ok) return;
+    for (int j = g; j < B; j += WBG) {
+        const float d = du[(size_t)j * N + col];
+        float o;
+        if (mode == 0) o = d;
+        else if (mode == 1) o = u[(size_t)j * ld_u + col] > 0.f ? d : 0.f;
+        else {
+            const float xh = xhat[(size_t)j * N + col];
+            const float dh = gamma[col] * inv[col] * (d - mult[j] / M * (s1 + xh * s2));
+            o = hsave[(size_t)j * N + col] > 0.f ? dh : 0.f;
+        }
+        dpre[(size_t)j * ld_dpre + col] = o;
+    }
+}
+
+// head columns of dpre_i (pitch ld) from the per-sample context gradient: yu_i, zu_i as they are, gate_i through its ReLU
+// (mask from the gate value in the context row); the pad columns [cols, ld) are zero
+__global__ void tr_dpre_heads_kernel(const float *dctx, const float *ctx, int B, int C, int col0, int n, int w, int wprev,
+                                     int yu_off, int zu_off, int gate_off, float *dpre, int ld) {
+    const int span = ld - col0, total = B * span;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int j = i / span, k = i - j * span;
+        const float *d = dctx + (size_t)j * C, *cr = ctx + (size_t)j * C;
+        float v = 0.f;
+        if (k < n) v = d[yu_off + k];
+        else if (k < n + w) v = d[zu_off + k - n];
+        else if (k < n + w + wprev) v = cr[gate_off + k - n - w] > 0.f ? d[gate_off + k - n - w] : 0.f;
+        dpre[(size_t)j * ld + col0 + k] = v;
+    }
+}
+
+// out[col] = sum_j dpre[j][c0 + col], rows in order
+__global__ void tr_colsum_kernel(const float *dpre, int ld, int B, int c0, int N, float *out) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= N) return;
+    float s = 0.f;
+    for (int j = 0; j < B; ++j) s += dpre[(size_t)j * ld + c0 + col];
+    out[col] = s;
+}
+
+int grid_for(size_t total, int threads = 256) {
+    const size_t b = (total + threads - 1) / threads;
+    return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
+}
+
+// Workspace carving: the same walk sizes the buffer (dry run, base == nullptr) and launches (base != nullptr)
+struct Carver {
+    float *base;
+    size_t at = 0;
+    float *take(size_t floats) {
+        float *p = base ? base + at : nullptr;
+        at += (floats + 63) & ~size_t(63);       // 256-byte alignment of every piece
+        return p;
+    }
+};
+
+struct TrainShape {
+    int L, n, nf, C, B, R, R2, bn;
+    int w[ICNN_BE_MAX_LAYERS];
+    int yu_off[ICNN_BE_MAX_LAYERS], zu_off[ICNN_BE_MAX_LAYERS], gate_off[ICNN_BE_MAX_LAYERS];
+    int K(int i) const { return i == 0 ? nf : w[i - 1]; }                                   // stage input width
+    int stage_cols(int i) const { return (i < L ? w[i] : 0) + n + w[i] + (i > 0 ? w[i - 1] : 0); }
+    int stage_ld(int i) const { return (stage_cols(i) + 3) & ~3; }
+    int u_ld(int i) const { return (w[i] + 3) & ~3; }
+    int pq_ld(int i) const { return n + (i > 0 ? w[i - 1] : 0); }
+};
+
+// offsets of the variables inside the packed gradient, in the order of include/icnn_be.h (icnn_amd.picnn.init_params)
+struct GradLayout {
+    size_t uW[ICNN_BE_MAX_LAYERS], ub[ICNN_BE_MAX_LAYERS], gam[ICNN_BE_MAX_LAYERS], bet[ICNN_BE_MAX_LAYERS];
+    size_t zuuW[ICNN_BE_MAX_LAYERS], zuub[ICNN_BE_MAX_LAYERS], zproj[ICNN_BE_MAX_LAYERS];
+    size_t yuuW[ICNN_BE_MAX_LAYERS], yuub[ICNN_BE_MAX_LAYERS], yuW[ICNN_BE_MAX_LAYERS];
+    size_t zW[ICNN_BE_MAX_LAYERS], zb[ICNN_BE_MAX_LAYERS];
+    size_t total;
+};
+GradLayout grad_layout(const TrainShape &s) {
+    GradLayout g{};
+    size_t at = 0;
+    for (int i = 0; i < s.L; ++i) {
+        g.uW[i] = at; at += (size_t)s.K(i) * s.w[i];
+        g.ub[i] = at; at += s.w[i];
+        if (s.bn && i < s.L - 1) {
+            g.gam[i] = at; at += s.w[i];
+            g.bet[i] = at; at += s.w[i];
+        }
+    }
+    for (int i = 0; i <= s.L; ++i) {
+        if (i > 0) {
+            g.zuuW[i] = at; at += (size_t)s.K(i) * s.w[i - 1];
+            g.zuub[i] = at; at += s.w[i - 1];
+            g.zproj[i] = at; at += (size_t)s.w[i - 1] * s.w[i];
+        }
+        g.yuuW[i] = at; at += (size_t)s.K(i) * s.n;
+        g.yuub[i] = at; at += s.n;
+        g.yuW[i] = at; at += (size_t)s.n * s.w[i];
+        g.zW[i] = at; at += (size_t)s.K(i) * s.w[i];
+        g.zb[i] = at; at += s.w[i];
+    }
+    g.total = at;
+    return g;
+}
+
+int make_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool with_v, TrainShape &s) {
+    if (int rc = fc_check_model(m)) return rc;
+    if (c.n != m.n || c.n_layers != m.n_layers || c.n_features < 1) return ICNN_BE_EINVAL;
+    s = TrainShape{};
+    s.L = m.n_layers - 1;
+    s.n = m.n;
+    s.nf = c.n_features;
+    s.bn = c.batchnorm ? 1 : 0;
+    int o = 0;
+    for (int i = 0; i <= s.L; ++i) {
+        if (c.width[i] != m.width[i]) return ICNN_BE_EINVAL;
+        s.w[i] = m.width[i];
+        s.yu_off[i] = o; o += m.n;
+        s.zu_off[i] = o; o += m.width[i];
+        s.gate_off[i] = i > 0 ? o : -1;
+        if (i > 0) o += m.width[i - 1];
+    }
+    s.C = o;
+    if (batch < 1 || rows < 1) return ICNN_BE_EINVAL;
+    // every index of the row kernels is an int: R2 x ctx_width (which covers n + 2 widths), B x the widest stage row
+    int widest = o;
+    for (int i = 0; i <= s.L; ++i) {
+        const int cols = (i < s.L ? m.width[i] : 0) + m.n + m.width[i] + (i > 0 ? m.width[i - 1] : 0);
+        if (cols + 4 > widest) widest = cols + 4;
+    }
+    const size_t r2 = (with_v ? 2 : 1) * (size_t)rows;
+    if (r2 * (size_t)o > INT_MAX || (size_t)batch * widest > INT_MAX || (size_t)c.n_features * widest > INT_MAX)
+        return ICNN_BE_ELIMIT;
+    s.B = batch;
+    s.R = rows;
+    s.R2 = with_v ? 2 * rows : rows;
+    return 0;
+}
+
+struct Runner {
+    const TrainShape &s;
+    hipStream_t stream;
+    float *part;            // split-K partials (dry run: nullptr)
+    size_t part_need = 0;   // most partial floats any product needs
+    hipError_t err = hipSuccess;
+    bool dry() const { return part == nullptr; }
+
+    // C[M][N] (pitch ldc) = A B, strided operands; split-K over K so that a small output still fills the device
+    void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
+              float *C, long long ldc) {
+        if (err != hipSuccess || M <= 0 || N <= 0) return;
+        const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+        int splits = 1;
+        if (tiles < 256 && K > 64) {
+            splits = (256 + tiles - 1) / tiles;
+            const int most = (K + 63) / 64;
+            if (splits > most) splits = most;
+            if (splits > 32) splits = 32;
+        }
+        int kchunk = (K + splits - 1) / splits;
+        kchunk = (kchunk + GBK - 1) / GBK * GBK;
+        if (kchunk < GBK) kchunk = GBK;
+        splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
+        const size_t need = (size_t)splits * M * N;
+        if (need > part_need) part_need = need;
+        if (dry()) return;
+        TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part};
+        err = launch_kernel(tr_gemm_kernel, dim3((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits), dim3(GT_), 0, stream, a);
+        if (err == hipSuccess)
+            err = launch_kernel(tr_gemm_reduce_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream,
+                                (const float *)part, splits, M, N, C, ldc);
+    }
+    template <typename... KArgs, typename... Args>
+    void launch(void (*k)(KArgs...), int grid, int block, Args... args) {
+        if (err != hipSuccess || dry()) return;
+        err = launch_kernel(k, dim3(grid), dim3(block), 0, stream, args...);
+    }
+};
+
+// The whole step; with work == nullptr only sizes the workspace (returned through *work_floats)
+hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, const TrainShape &s, const float *x, const int *row_offset,
+                  const double *y, const double *v, const double *cvec, float *grad, float *F_rows, float *work,
+                  size_t *work_floats, hipStream_t stream) {
+    const int L = s.L, B = s.B, R = s.R, R2 = s.R2, n = s.n, C = s.C;
+    Carver cv{work};
+    int *samp = reinterpret_cast<int *>(cv.take(R));
+    float *mult = cv.take(B);
+    float *uwork = cv.take(ctx_work_floats(cx, B));
+    float *ctxb = cv.take((size_t)B * C);
+    float *hsave[ICNN_BE_MAX_LAYERS] = {}, *xhat[ICNN_BE_MAX_LAYERS] = {}, *inv[ICNN_BE_MAX_LAYERS] = {};
+    for (int i = 0; i + 1 < L; ++i)
+        if (s.bn) {
+            hsave[i] = cv.take((size_t)B * s.w[i]);
+            xhat[i] = cv.take((size_t)B * s.w[i]);
+            inv[i] = cv.take(s.w[i]);
+        }
+    float *wst[ICNN_BE_MAX_LAYERS], *pq[ICNN_BE_MAX_LAYERS], *adj[ICNN_BE_MAX_LAYERS], *Z[ICNN_BE_MAX_LAYERS] = {},
+          *D[ICNN_BE_MAX_LAYERS] = {}, *dpre[ICNN_BE_MAX_LAYERS];
+    int max_pq = 0, max_k = 0;
+    for (int i = 0; i <= L; ++i) {
+        wst[i] = cv.take((size_t)s.pq_ld(i) * s.w[i]);
+        pq[i] = cv.take((size_t)R2 * s.pq_ld(i));
+        adj[i] = cv.take((size_t)R2 * s.w[i]);
+        if (i < L) {
+            Z[i] = cv.take((size_t)R2 * s.w[i]);
+            D[i] = cv.take((size_t)R * s.w[i]);
+        }
+        dpre[i] = cv.take((size_t)B * s.stage_ld(i));
+        if (s.pq_ld(i) > max_pq) max_pq = s.pq_ld(i);
+        if (s.K(i) > max_k) max_k = s.K(i);
+    }
+    int max_w = 1;
+    for (int i = 0; i <= L; ++i) max_w = s.w[i] > max_w ? s.w[i] : max_w;
+    float *pre = cv.take((size_t)R2 * max_w);
+    float *bd = cv.take((size_t)R2 * max_pq);
+    float *drows = cv.take((size_t)R * C);
+    float *dctx = cv.take((size_t)B * C);
+    float *du = cv.take((size_t)B * max_k);
+    const size_t fixed = cv.at;
+
+    // the partials go last: their size is what the products below ask for (measured by the dry run)
+    Runner run{s, stream, work ? work + fixed : nullptr};
+    const PackOffsets po = pack_offsets(m);
+    const GradLayout gl = grad_layout(s);
+    RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, m.action_box ? 1 : 0};
+
+    // 1. rows and multiplicities, y-path weights
+    run.launch(tr_rows_kernel, grid_for(R > B ? R : B), 256, row_offset, B, R, samp, mult);
+    for (int i = 0; i <= L; ++i) {
+        UnpackArgs ua{m.wpack, po.yu_f[i], po.zu_f[i], n, i > 0 ? s.w[i - 1] : 0, s.w[i], i == L ? 1 : 0, wst[i]};
+        run.launch(tr_unpack_kernel, grid_for((size_t)s.pq_ld(i) * s.w[i]), 256, ua);
+    }
+    // 2. x-only forward on the B samples (context producer's stage GEMMs), weighted BatchNorm
+    for (int i = 0; i <= L; ++i) {
+        if (!run.dry() && run.err == hipSuccess) run.err = launch_fc_context_stage(cx, i, x, B, ctxb, C, uwork, stream);
+        if (i + 1 < L && s.bn) {
+            float *u = uwork;
+            for (int l = 0; l < i; ++l) u += (size_t)B * s.u_ld(l);
+            run.launch(tr_wbn_fwd_kernel, (s.w[i] + WBC - 1) / WBC, WBT, u, s.u_ld(i), B, s.w[i], (const float *)mult, (float)R,
+                       cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i]);
+        }
+    }
+    // 3. y-path forward: primal and tangent rows stacked, one GEMM per layer
+    for (int i = 0; i <= L; ++i) {
+        const int ld = s.pq_ld(i), w = s.w[i];
+        run.launch(tr_build_p_kernel, grid_for((size_t)R * n), 256, ra, s.yu_off[i], pq[i], ld);
+        run.gemm(pq[i], ld, 1, wst[i], w, 1, R2, w, ld, pre, w);
+        if (i < L)
+            run.launch(tr_hidden_fwd_kernel, grid_for((size_t)R * w), 256, ra, (const float *)pre, w, s.zu_off[i],
+                       s.gate_off[i + 1], m.alpha, Z[i], D[i], pq[i + 1], s.pq_ld(i + 1));
+        else
+            run.launch(tr_final_kernel, grid_for(R), 256, ra, (const float *)pre, s.zu_off[i], F_rows, adj[L]);
+    }
+    // 4. y-path reverse: weight gradients (K = 2R) and the per-row context gradient
+    for (int i = L; i >= 0; --i) {
+        const int ld = s.pq_ld(i), w = s.w[i], wp = i > 0 ? s.w[i - 1] : 0;
+        run.gemm(pq[i], 1, ld, adj[i], w, 1, n, w, R2, grad + gl.yuW[i], w);                     // (y*yu)^T abar
+        if (i > 0) run.gemm(pq[i] + n, 1, ld, adj[i], w, 1, wp, w, R2, grad + gl.zproj[i], w);  // (z*gate)^T abar
+        run.gemm(adj[i], w, 1, wst[i], 1, w, R2, ld, w, bd, ld);                                 // abar [Wyu ; Wzu]^T
+        BackArgs ba{bd, adj[i], i > 0 ? Z[i - 1] : nullptr, i > 0 ? D[i - 1] : nullptr, i > 0 ? adj[i - 1] : nullptr, drows,
+                    w, wp, s.yu_off[i], s.zu_off[i], s.gate_off[i]};
+        run.launch(tr_back_rows_kernel, grid_for((size_t)R * (ld + w)), 256, ra, ba);
+    }
+    // 5. per-sample context gradient
+    run.launch(tr_segment_sum_kernel, grid_for((size_t)B * C), 256, (const float *)drows, row_offset, B, R, C, dctx);
+    // 6. x-only backward on the B samples
+    for (int i = L; i >= 0; --i) {
+        const int K = s.K(i), ld = s.stage_ld(i), wp = i > 0 ? s.w[i - 1] : 0, ucols = i < L ? s.w[i] : 0;
+        run.launch(tr_dpre_heads_kernel, grid_for((size_t)B * (ld - ucols)), 256, (const float *)dctx, (const float *)ctxb, B, C,
+                   ucols, n, s.w[i], wp, s.yu_off[i], s.zu_off[i], s.gate_off[i], dpre[i], ld);
+        if (i < L) {        // u_i columns from du = dprev_{i+1} (computed in the previous iteration)
+            const int mode = i == L - 1 ? 0 : (s.bn ? 2 : 1);
+            const float *u = uwork;
+            for (int l = 0; l < i; ++l) u += (size_t)B * s.u_ld(l);
+            run.launch(tr_u_back_kernel, (s.w[i] + WBC - 1) / WBC, WBT, (const float *)du, B, s.w[i], mode, u, s.u_ld(i),
+                       (const float *)hsave[i], (const float *)xhat[i], (const float *)inv[i], cx.bn_gamma[i],
+                       (const float *)mult, (float)R, dpre[i], ld, mode == 2 ? grad + gl.gam[i] : nullptr,
+                       mode == 2 ? grad + gl.bet[i] : nullptr);
+        }
+        // stage input: x, or u_{i-1} as the next stage read it (after its BatchNorm)
+        const float *prev = x;
+        int prev_ld = s.nf;
+        if (i > 0) {
+            const float *u = uwork;
+            for (int l = 0; l < i - 1; ++l) u += (size_t)B * s.u_ld(l);
+            prev = u;
+            prev_ld = s.u_ld(i - 1);
+        }
+        // column segments of the stage: [ u_i | yu_u | u | zu_u ] -> their gradient variables
+        struct Seg { int c0, cols; size_t wo, bo; } segs[4];
+        int ns = 0, c0 = 0;
+        if (i < L) { segs[ns++] = Seg{c0, s.w[i], gl.uW[i], gl.ub[i]}; c0 += s.w[i]; }
+        segs[ns++] = Seg{c0, n, gl.yuuW[i], gl.yuub[i]}; c0 += n;
+        segs[ns++] = Seg{c0, s.w[i], gl.zW[i], gl.zb[i]}; c0 += s.w[i];
+        if (i > 0) { segs[ns++] = Seg{c0, wp, gl.zuuW[i], gl.zuub[i]}; c0 += wp; }
+        for (int q = 0; q < ns; ++q) {
+            run.gemm(prev, 1, prev_ld, dpre[i] + segs[q].c0, ld, 1, K, segs[q].cols, B, grad + segs[q].wo, segs[q].cols);
+            run.launch(tr_colsum_kernel, (segs[q].cols + 255) / 256, 256, (const float *)dpre[i], ld, B, segs[q].c0, segs[q].cols,
+                       grad + segs[q].bo);
+        }
+        if (i > 0)          // du_{i-1} = dpre_i W_stage_i^T  [B][w_{i-1}]
+            run.gemm(dpre[i], ld, 1, cx.w_stage[i], 1, ld, B, K, s.stage_cols(i), du, K);
+    }
+    if (work_floats) *work_floats = fixed + run.part_need;
+    return run.err;
+}
+
+}  // namespace
+
+size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c) {
+    TrainShape s;
+    if (make_shape(m, c, 1, 1, true, s) != 0) return 0;
+    return grad_layout(s).total;
+}
+
+size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows) {
+    // with and without v (2R or R stacked rows): the split-K partials need not grow with the row count, so take the larger
+    size_t most = 0;
+    for (int with_v = 0; with_v < 2; ++with_v) {
+        TrainShape s;
+        if (make_shape(m, c, batch, rows, with_v != 0, s) != 0) return 0;
+        size_t need = 0;
+        (void)surrogate_run(m, c, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need, nullptr);
+        if (need > most) most = need;
+    }
+    return most;
+}
+
+int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool with_v) {
+    TrainShape s;
+    return make_shape(m, c, batch, rows, with_v, s);
+}
+
+hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
+                                    const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                    float *grad, float *F_rows, float *work, hipStream_t stream) {
+    TrainShape s;
+    if (make_shape(m, c, batch, rows, v != nullptr, s) != 0) return hipErrorInvalidValue;
+    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream);
+}
+
+}  // namespace icnn_be

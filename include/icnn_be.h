@@ -38,7 +38,7 @@ extern "C" {
 #define ICNN_BE_API
 #endif
 
-#define ICNN_BE_ABI_VERSION 11
+#define ICNN_BE_ABI_VERSION 12
 #define ICNN_BE_MAX_LAYERS 8   /* z-layers of a PICNN including the final scalar one */
 #define ICNN_BE_MAX_SLOTS 31   /* bundle slots (= outer iterations) per solve */
 #define ICNN_BE_MAX_ITERS 64   /* outer iterations per solve (icnn_be_state.iters; beyond MAX_SLOTS the slots are recycled) */
@@ -401,6 +401,50 @@ ICNN_BE_API int icnn_be_conv_clamp(const icnn_be_conv_model *model, int mode, vo
 ICNN_BE_API int icnn_be_implicit_feed(const icnn_be_state *st, const double *y_true, int loss,
                                       const int *row_offset, double *fd_y, double *fd_v, double *fd_c,
                                       int *fd_sample, void *stream);
+
+/* ---- training step of the FC PICNN: gradient of the surrogate (ABI 12) ------------------------ */
+
+/*
+ * Floats of the packed parameter gradient of a model (0: shape rejected; host arithmetic, no GPU needed).  The variables
+ * follow one another in this order, each row-major with the reference's [in][out] W shapes (K_0 = n_features,
+ * K_i = width[i-1], L = n_layers - 1; the u-path has L layers of widths width[0..L-1]):
+ *   for i = 0 .. L-1:  'u{i}/W' [K_i][width[i]], 'u{i}/b' [width[i]],
+ *                      'u{i}/bn/gamma', 'u{i}/bn/beta' [width[i]]   (batchnorm and i < L-1 only)
+ *   for i = 0 .. L:    'z{i}_zu_u/W' [K_i][width[i-1]], 'z{i}_zu_u/b' [width[i-1]], 'z{i}_zu_proj/W' [width[i-1]][width[i]]
+ *                                                                                                   (i > 0 only)
+ *                      'z{i}_yu_u/W' [K_i][n], 'z{i}_yu_u/b' [n], 'z{i}_yu/W' [n][width[i]],
+ *                      'z{i}_u/W' [K_i][width[i]], 'z{i}_u/b' [width[i]]
+ * (the order of tf.trainable_variables() in multi-label-cls/icnn_ebundle.py:316-388, RL/src/icnn.py:325-404;
+ * icnn_amd.picnn.init_params returns its keys in the same order).  `c` supplies the x-only weights (stage
+ * concatenations, BatchNorm parameters) and must describe the same shape as `model`.
+ */
+ICNN_BE_API size_t icnn_be_fc_grad_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c);
+
+/* floats of device scratch icnn_be_fc_surrogate_grad needs for `batch` samples and `rows` feed rows (0: rejected) */
+ICNN_BE_API size_t icnn_be_fc_surrogate_grad_work_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, int batch,
+                                                         int rows);
+
+/*
+ * grad = d/dtheta  sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ]  over every trainable variable theta,
+ * float32, packed as icnn_be_fc_grad_floats describes -- what
+ *   F_ = c_ * E_ + reduce_sum(dE_dy_ * v_, 1);  AdamOptimizer.compute_gradients(F_, theta_)
+ * evaluates in multi-label-cls/icnn_ebundle.py:148-156 with the feed of train_step_fd (icnn_be_implicit_feed), and, with
+ * v = NULL, the gradient of sum_r c_r E_r that the RL critic update needs (RL/src/icnn.py:90-109, c_r = dloss/dQ_r).
+ *   x[batch][n_features] float32   the minibatch; the rows of sample j are row_offset[j] .. row_offset[j+1]-1 (int
+ *                                  [batch+1], row_offset[0] = 0, row_offset[batch] = rows, non-decreasing: what
+ *                                  icnn_be_implicit_feed emits); a sample may have no rows
+ *   y, v[rows][n] float64, c[rows] float64   the feed (y rounded to float32 like a TensorFlow feed; action_box models
+ *                                  see 2y-1, as icnn_be_fc_fg); v may be NULL
+ *   F_rows[rows] float32 or NULL   F_r = c_r E_r + <dE/dy_r, v_r>
+ *   work                           icnn_be_fc_surrogate_grad_work_floats(model, c, batch, rows) floats
+ * Semantics of icnn_be_fc_fg (ReLU / leaky ReLU alpha, action_box); the u-path BatchNorm runs in training mode over
+ * the feed rows (each sample counted once per row, as the reference's x_ = fd_xs), computed on the batch samples with
+ * their multiplicities.  Deterministic (no atomics: the same bits on every call), no host synchronisation (capturable in a
+ * HIP graph).  ICNN_BE_EINVAL / ICNN_BE_ELIMIT for a bad shape before anything is launched.
+ */
+ICNN_BE_API int icnn_be_fc_surrogate_grad(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                                          const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                          float *grad, float *F_rows, float *work, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
