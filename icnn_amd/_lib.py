@@ -51,6 +51,7 @@ EXPORTS = [
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
+    "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 
@@ -207,6 +208,14 @@ def load():
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
     lib.icnn_be_fc_surrogate_grad.restype = C.c_int
+    lib.icnn_be_conv_grad_floats.argtypes = [C.POINTER(ConvModel), C.POINTER(ConvCtx)]
+    lib.icnn_be_conv_grad_floats.restype = C.c_size_t
+    lib.icnn_be_conv_surrogate_grad_work_floats.argtypes = [C.POINTER(ConvModel), C.POINTER(ConvCtx), C.c_int, C.c_int]
+    lib.icnn_be_conv_surrogate_grad_work_floats.restype = C.c_size_t
+    lib.icnn_be_conv_surrogate_grad.argtypes = [C.POINTER(ConvModel), C.POINTER(ConvCtx), C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+    lib.icnn_be_conv_surrogate_grad.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
     if tuple(lib.icnn_be_struct_size(i) for i in range(5)) != (

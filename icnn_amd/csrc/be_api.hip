@@ -330,6 +330,30 @@ int icnn_be_fc_surrogate_grad(const icnn_be_fc_model *model, const icnn_be_fc_ct
     return e == hipSuccess ? 0 : fail(e);
 }
 
+size_t icnn_be_conv_grad_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c) {
+    if (!model || !c) return 0;
+    return icnn_be::conv_grad_floats(*model, *c);
+}
+
+size_t icnn_be_conv_surrogate_grad_work_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, int batch, int rows) {
+    if (!model || !c) return 0;
+    return icnn_be::conv_surrogate_work_floats(*model, *c, batch, rows);
+}
+
+int icnn_be_conv_surrogate_grad(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
+                                const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                float *grad, float *F_rows, float *work, void *stream) {
+    if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
+    for (int s = 0; s < 7; ++s)
+        if (!c->w_stage[s] || !c->b_stage[s]) return ICNN_BE_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (!c->bn_gamma[i] || !c->bn_beta[i]) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::conv_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
+    hipError_t e = icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                       static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_fc_context_stage(const icnn_be_fc_ctx *c, int stage, const float *x, int batch, float *ctx, int ctx_width,
                              float *work, double *stats, void *stream) {
     /* an empty shard (a rank of a data-parallel group whose batch is smaller than the group) has no rows: its zero-element

@@ -415,12 +415,20 @@ size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch) {
            2 * (size_t)BNB * 256;                    // + the BatchNorm partials
 }
 
-hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
-                               float *work, hipStream_t stream) {
-    float *u0 = work, *u1 = u0 + (size_t)batch * g.P[0] * g.F[0], *u2 = u1 + (size_t)batch * g.P[1] * g.F[1],
-          *u3 = u2 + (size_t)batch * g.P[2] * g.F[2], *part = u3 + (size_t)batch * ((g.fch + 3) & ~3);
+float *conv_ctx_u(const ConvCtxShape &g, int batch, float *work, int l) {
+    float *u = work;
+    for (int i = 0; i < l; ++i) u += (size_t)batch * (i < 3 ? (size_t)g.P[i] * g.F[i] : (size_t)((g.fch + 3) & ~3));
+    return u;
+}
+
+// The GEMM of one stage (include/icnn_be.h, icnn_be_conv_ctx): u-maps into `work` (ReLU'd, not yet normalised), heads
+// into the context rows
+hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_ctx &c, int stage, const float *x, int batch,
+                                     float *ctx, float *work, hipStream_t stream) {
+    float *u0 = conv_ctx_u(g, batch, work, 0), *u1 = conv_ctx_u(g, batch, work, 1), *u2 = conv_ctx_u(g, batch, work, 2),
+          *u3 = conv_ctx_u(g, batch, work, 3);
     const int C = g.ctx_width, u3_ld = (g.fch + 3) & ~3;
-    auto gemm = [&](int stage, const float *A, int conv, int IH, int IW, int IC, int KS, int ST, int PD, int OH, int OW,
+    auto gemm = [&](const float *A, int conv, int IH, int IW, int IC, int KS, int ST, int PD, int OH, int OW,
                     int lda, int K, std::initializer_list<CtxSeg> segs) -> hipError_t {
         CtxGemmArgs a{};
         a.A = A; a.W = c.w_stage[stage]; a.bias = c.b_stage[stage];
@@ -433,6 +441,39 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
         a.a_vec = conv ? (IC % 4 == 0) : (lda % 4 == 0 && reinterpret_cast<uintptr_t>(A) % 16 == 0);
         return launch_kernel(ctx_gemm_kernel, dim3((a.M + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
     };
+    const int H = g.H, W = g.W, F0 = g.F[0], F1 = g.F[1], F2 = g.F[2];
+    const int *oh = g.oh, *ow = g.ow, *K = g.K, *S = g.S, *Pd = g.pad, *P = g.P;
+    switch (stage) {
+    case 0:     // input x: 8x8/4 -> u0 (ReLU, then BN) | zu0
+        return gemm(x, 1, H, W, 1, K[0], S[0], Pd[0], oh[0], ow[0], 0, K[0] * K[0],
+                    {CtxSeg{0, F0, F0, 0, 1, 0, u0}, CtxSeg{F0, 2 * F0, C, g.c_zu[0], 0, P[0], ctx}});
+    case 1:     // input x: 3x3/1 -> yu0
+        return gemm(x, 1, H, W, 1, 3, 1, 1, H, W, 0, 9, {CtxSeg{0, 1, C, g.c_yu[0], 0, H * W, ctx}});
+    case 2:     // input u0: 4x4/2 -> u1 | zu1
+        return gemm(u0, 1, oh[0], ow[0], F0, K[1], S[1], Pd[1], oh[1], ow[1], 0, K[1] * K[1] * F0,
+                    {CtxSeg{0, F1, F1, 0, 1, 0, u1}, CtxSeg{F1, 2 * F1, C, g.c_zu[1], 0, P[1], ctx}});
+    case 3:     // input u0: 3x3/1 -> gate1 (ReLU) | yu1
+        return gemm(u0, 1, oh[0], ow[0], F0, 3, 1, 1, oh[0], ow[0], 0, 9 * F0,
+                    {CtxSeg{0, F0, C, g.c_gate[1], 1, P[0], ctx}, CtxSeg{F0, F0 + 1, C, g.c_yu[1], 0, P[0], ctx}});
+    case 4:     // input u1: 3x3/1 -> u2 | gate2 (ReLU) | yu2 | zu2
+        return gemm(u1, 1, oh[1], ow[1], F1, K[2], S[2], Pd[2], oh[2], ow[2], 0, K[2] * K[2] * F1,
+                    {CtxSeg{0, F2, F2, 0, 1, 0, u2}, CtxSeg{F2, F2 + F1, C, g.c_gate[2], 1, P[1], ctx},
+                     CtxSeg{F2 + F1, F2 + F1 + 1, C, g.c_yu[2], 0, P[1], ctx},
+                     CtxSeg{F2 + F1 + 1, 2 * F2 + F1 + 1, C, g.c_zu[2], 0, P[2], ctx}});
+    case 5:     // flat u2 [B][flat]: -> u3 (ReLU, BN) | gate3 (ReLU) | zu3
+        return gemm(u2, 0, 0, 0, 0, 0, 0, 0, 1, 1, g.flat, g.flat,
+                    {CtxSeg{0, g.fch, u3_ld, 0, 1, 0, u3}, CtxSeg{g.fch, g.fch + g.flat, C, g.c_gate[3], 1, 0, ctx},
+                     CtxSeg{g.fch + g.flat, 2 * g.fch + g.flat, C, g.c_zu3, 0, 0, ctx}});
+    case 6:     // u3 -> gate4 (ReLU) | zu4
+        return gemm(u3, 0, 0, 0, 0, 0, 0, 0, 1, 1, u3_ld, g.fch,
+                    {CtxSeg{0, g.fch, C, g.c_gate[4], 1, 0, ctx}, CtxSeg{g.fch, g.fch + 1, C, g.c_zu4, 0, 0, ctx}});
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
+                               float *work, hipStream_t stream) {
+    float *part = conv_ctx_u(g, batch, work, 4);
     auto bn = [&](float *u, int ld, int rows, int cols, int i) -> hipError_t {
         if (rows >= 16 * BNB && cols % 4 == 0 && cols <= 256 && ld == cols) {          // tall: row-parallel passes
             hipError_t e = hipSuccess;
@@ -444,39 +485,17 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
         return launch_kernel(ctx_bn_kernel, dim3((cols + BNC - 1) / BNC), dim3(BNT), 0, stream, u, ld, rows, cols, c.bn_gamma[i],
                              c.bn_beta[i], c.bn_eps);
     };
-    const int H = g.H, W = g.W, F0 = g.F[0], F1 = g.F[1], F2 = g.F[2];
-    const int *oh = g.oh, *ow = g.ow, *K = g.K, *S = g.S, *Pd = g.pad, *P = g.P;
-    hipError_t e;
-    // input x: 8x8/4 -> u0 (ReLU, then BN) | zu0;   3x3/1 -> yu0
-    e = gemm(0, x, 1, H, W, 1, K[0], S[0], Pd[0], oh[0], ow[0], 0, K[0] * K[0],
-             {CtxSeg{0, F0, F0, 0, 1, 0, u0}, CtxSeg{F0, 2 * F0, C, g.c_zu[0], 0, P[0], ctx}});
-    if (e != hipSuccess) return e;
-    e = gemm(1, x, 1, H, W, 1, 3, 1, 1, H, W, 0, 9, {CtxSeg{0, 1, C, g.c_yu[0], 0, H * W, ctx}});
-    if (e != hipSuccess) return e;
-    if ((e = bn(u0, F0, batch * P[0], F0, 0)) != hipSuccess) return e;
-    // input u0: 4x4/2 -> u1 | zu1;   3x3/1 -> gate1 (ReLU) | yu1
-    e = gemm(2, u0, 1, oh[0], ow[0], F0, K[1], S[1], Pd[1], oh[1], ow[1], 0, K[1] * K[1] * F0,
-             {CtxSeg{0, F1, F1, 0, 1, 0, u1}, CtxSeg{F1, 2 * F1, C, g.c_zu[1], 0, P[1], ctx}});
-    if (e != hipSuccess) return e;
-    e = gemm(3, u0, 1, oh[0], ow[0], F0, 3, 1, 1, oh[0], ow[0], 0, 9 * F0,
-             {CtxSeg{0, F0, C, g.c_gate[1], 1, P[0], ctx}, CtxSeg{F0, F0 + 1, C, g.c_yu[1], 0, P[0], ctx}});
-    if (e != hipSuccess) return e;
-    if ((e = bn(u1, F1, batch * P[1], F1, 1)) != hipSuccess) return e;
-    // input u1: 3x3/1 -> u2 | gate2 (ReLU) | yu2 | zu2
-    e = gemm(4, u1, 1, oh[1], ow[1], F1, K[2], S[2], Pd[2], oh[2], ow[2], 0, K[2] * K[2] * F1,
-             {CtxSeg{0, F2, F2, 0, 1, 0, u2}, CtxSeg{F2, F2 + F1, C, g.c_gate[2], 1, P[1], ctx},
-              CtxSeg{F2 + F1, F2 + F1 + 1, C, g.c_yu[2], 0, P[1], ctx},
-              CtxSeg{F2 + F1 + 1, 2 * F2 + F1 + 1, C, g.c_zu[2], 0, P[2], ctx}});
-    if (e != hipSuccess) return e;
-    if ((e = bn(u2, F2, batch * P[2], F2, 2)) != hipSuccess) return e;
-    // flat u2 [B][flat]: -> u3 (ReLU, BN) | gate3 (ReLU) | zu3;   u3 -> gate4 (ReLU) | zu4
-    e = gemm(5, u2, 0, 0, 0, 0, 0, 0, 0, 1, 1, g.flat, g.flat,
-             {CtxSeg{0, g.fch, u3_ld, 0, 1, 0, u3}, CtxSeg{g.fch, g.fch + g.flat, C, g.c_gate[3], 1, 0, ctx},
-              CtxSeg{g.fch + g.flat, 2 * g.fch + g.flat, C, g.c_zu3, 0, 0, ctx}});
-    if (e != hipSuccess) return e;
-    if ((e = bn(u3, u3_ld, batch, g.fch, 3)) != hipSuccess) return e;
-    return gemm(6, u3, 0, 0, 0, 0, 0, 0, 0, 1, 1, u3_ld, g.fch,
-                {CtxSeg{0, g.fch, C, g.c_gate[4], 1, 0, ctx}, CtxSeg{g.fch, g.fch + 1, C, g.c_zu4, 0, 0, ctx}});
+    // stage order of the launches; each u-map is normalised before the first stage that reads it
+    hipError_t e = hipSuccess;
+    for (int stage = 0; stage < 7 && e == hipSuccess; ++stage) {
+        e = launch_conv_context_stage(g, c, stage, x, batch, ctx, work, stream);
+        if (e != hipSuccess) break;
+        if (stage == 1) e = bn(conv_ctx_u(g, batch, work, 0), g.F[0], batch * g.P[0], g.F[0], 0);
+        else if (stage == 3) e = bn(conv_ctx_u(g, batch, work, 1), g.F[1], batch * g.P[1], g.F[1], 1);
+        else if (stage == 4) e = bn(conv_ctx_u(g, batch, work, 2), g.F[2], batch * g.P[2], g.F[2], 2);
+        else if (stage == 5) e = bn(conv_ctx_u(g, batch, work, 3), (g.fch + 3) & ~3, batch, g.fch, 3);
+    }
+    return e;
 }
 
 hipError_t launch_clamp(float *w, size_t count, int mode, hipStream_t stream) {

@@ -111,6 +111,10 @@ int conv_ctx_shape(const icnn_be_conv_model &m, ConvCtxShape &g);
 size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch);
 hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
                                float *work, hipStream_t stream);
+// one stage's GEMM of launch_conv_context (u-maps ReLU'd but not normalised); conv_ctx_u: u_l (l = 0..3) inside `work`
+hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_ctx &c, int stage, const float *x, int batch,
+                                     float *ctx, float *work, hipStream_t stream);
+float *conv_ctx_u(const ConvCtxShape &g, int batch, float *work, int l);
 hipError_t launch_conv_clamp(const icnn_be_conv_model &m, int mode, hipStream_t stream);
 
 // training gradient of the FC PICNN (be_train_fc.hip): sizes (0 = shape rejected), shape check, launcher
@@ -120,6 +124,19 @@ int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int b
 hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                     float *grad, float *F_rows, float *work, hipStream_t stream);
+// the strided f32-MFMA GEMM of be_train_fc.hip: C[M][N] (pitch ldc) = A B, A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn],
+// split-K into `part` (tr_gemm_part_floats(M, N, K) floats) and summed in split order -- no atomics
+size_t tr_gemm_part_floats(int M, int N, int K);
+hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
+                          int K, float *C, long long ldc, float *part, hipStream_t stream);
+
+// training gradient of the conv PICNN (be_train_conv.hip), as the FC one above
+size_t conv_grad_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c);
+size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows);
+int conv_surrogate_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows, bool with_v);
+hipError_t launch_conv_surrogate_grad(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, const float *x, int batch,
+                                      const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                      float *grad, float *F_rows, float *work, hipStream_t stream);
 
 // LDS layouts of the persistent kernels (be_fused.hip), host arithmetic only.  false: the shape does not fit that kernel.
 // The solve plan (be_api.hip) and the launchers below take their fit decisions from these two functions alone.
@@ -156,6 +173,11 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
 
 // ---- conv PICNN energy / gradient -------------------------------------------------
 int conv_check_model(const icnn_be_conv_model &m);
+// where the raw single-channel pieces and the forward MFMA operands of the convex weights sit inside wpack (floats)
+struct ConvPackOffsets {
+    long long w_yu[3], w_yr[2], b_yr[2], w_fc4, p_l2, p_l3, p_fc3;
+};
+int conv_pack_offsets(const icnn_be_conv_model &m, ConvPackOffsets &o);
 size_t conv_pack_floats(const icnn_be_conv_model &m);
 size_t conv_work_floats(const icnn_be_conv_model &m, int batch);
 int conv_pack(const icnn_be_conv_model &m, const float *const *w_yu, const float *const *w_yr,

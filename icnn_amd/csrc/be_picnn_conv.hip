@@ -714,6 +714,16 @@ int conv_check_model(const icnn_be_conv_model &m) {
     return conv_layout(m, L);
 }
 
+int conv_pack_offsets(const icnn_be_conv_model &m, ConvPackOffsets &o) {
+    ConvLayout L{};
+    if (int rc = conv_layout(m, L)) return rc;
+    const ConvArgs &a = L.a;
+    for (int l = 0; l < 3; ++l) o.w_yu[l] = a.w_yu[l];
+    for (int l = 0; l < 2; ++l) { o.w_yr[l] = a.w_yr[l]; o.b_yr[l] = a.b_yr[l]; }
+    o.w_fc4 = a.w_fc4; o.p_l2 = a.p_l2; o.p_l3 = a.p_l3; o.p_fc3 = a.p_fc3;
+    return 0;
+}
+
 int conv_ctx_shape(const icnn_be_conv_model &m, ConvCtxShape &g) {
     ConvLayout L{};
     if (int rc = conv_layout(m, L)) return rc;

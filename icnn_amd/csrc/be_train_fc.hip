@@ -455,6 +455,22 @@ int make_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, in
     return 0;
 }
 
+// split-K plan: enough splits that a small output still fills the device
+void gemm_splits(int M, int N, int K, int &splits, int &kchunk) {
+    const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+    splits = 1;
+    if (tiles < 256 && K > 64) {
+        splits = (256 + tiles - 1) / tiles;
+        const int most = (K + 63) / 64;
+        if (splits > most) splits = most;
+        if (splits > 32) splits = 32;
+    }
+    kchunk = (K + splits - 1) / splits;
+    kchunk = (kchunk + GBK - 1) / GBK * GBK;
+    if (kchunk < GBK) kchunk = GBK;
+    splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
+}
+
 struct Runner {
     const TrainShape &s;
     hipStream_t stream;
@@ -467,18 +483,8 @@ struct Runner {
     void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
               float *C, long long ldc) {
         if (err != hipSuccess || M <= 0 || N <= 0) return;
-        const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-        int splits = 1;
-        if (tiles < 256 && K > 64) {
-            splits = (256 + tiles - 1) / tiles;
-            const int most = (K + 63) / 64;
-            if (splits > most) splits = most;
-            if (splits > 32) splits = 32;
-        }
-        int kchunk = (K + splits - 1) / splits;
-        kchunk = (kchunk + GBK - 1) / GBK * GBK;
-        if (kchunk < GBK) kchunk = GBK;
-        splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
+        int splits, kchunk;
+        gemm_splits(M, N, K, splits, kchunk);
         const size_t need = (size_t)splits * M * N;
         if (need > part_need) part_need = need;
         if (dry()) return;
@@ -624,6 +630,26 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
 }
 
 }  // namespace
+
+size_t tr_gemm_part_floats(int M, int N, int K) {
+    if (M <= 0 || N <= 0) return 0;
+    int splits, kchunk;
+    gemm_splits(M, N, K, splits, kchunk);
+    return (size_t)splits * M * N;
+}
+
+hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
+                          int K, float *C, long long ldc, float *part, hipStream_t stream) {
+    if (M <= 0 || N <= 0) return hipSuccess;
+    int splits, kchunk;
+    gemm_splits(M, N, K, splits, kchunk);
+    TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part};
+    hipError_t e = launch_kernel(tr_gemm_kernel, dim3((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits), dim3(GT_), 0, stream, a);
+    if (e == hipSuccess)
+        e = launch_kernel(tr_gemm_reduce_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream, (const float *)part, splits,
+                          M, N, C, ldc);
+    return e;
+}
 
 size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c) {
     TrainShape s;

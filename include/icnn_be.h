@@ -446,6 +446,53 @@ ICNN_BE_API int icnn_be_fc_surrogate_grad(const icnn_be_fc_model *model, const i
                                           const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                           float *grad, float *F_rows, float *work, void *stream);
 
+/* ---- training step of the conv PICNN: gradient of the surrogate (additive to ABI 12) ----------- */
+
+/*
+ * Floats of the packed parameter gradient of the completion model (0: shape rejected; host arithmetic, no GPU needed).
+ * The variables follow one another in the order of icnn_amd.picnn.init_conv_params (tf.trainable_variables() of
+ * completion/icnn_ebundle.py:337-452), each row-major in tflearn's shapes -- [k][k][Cin][F] for a convolution, [in][out]
+ * for a dense layer; (k, s, F) = (ksize, stride, filters)[l], Cin_0 = 1, Cin_l = F_{l-1}, flat = the size of flatten(u2),
+ * fch = fc_hidden:
+ *   for l = 0 .. 2:  'u{l}/W' [k][k][Cin][F], 'u{l}/b' [F], 'u{l}/bn/gamma' [F], 'u{l}/bn/beta' [F],
+ *                    'z{l}_zu_u/W' [3][3][Cin][Cin], 'z{l}_zu_u/b' [Cin], 'z{l}_zu_proj/W' [k][k][Cin][F]   (l > 0 only)
+ *                    'z{l}_yu_u/W' [3][3][Cin][1], 'z{l}_yu_u/b' [1], 'z{l}_yu/W' [k][k][1][F],
+ *                    'z{l}_y_red/W' [k][k][1][1], 'z{l}_y_red/b' [1], 'z{l}_u/W' [k][k][Cin][F], 'z{l}_u/b' [F]
+ *   'u3/W' [flat][fch], 'u3/b', 'u3/bn/gamma', 'u3/bn/beta' [fch], 'u4/W' [fch][1], 'u4/b' [1]
+ *   'z3_zu_u/W' [flat][flat], 'z3_zu_u/b' [flat], 'z3_zu_proj/W' [flat][fch], 'z3_u/W' [flat][fch], 'z3_u/b' [fch]
+ *   'z4_zu_u/W' [fch][fch], 'z4_zu_u/b' [fch], 'z4_zu_proj/W' [fch][1], 'z4_u/W' [fch][1], 'z4_u/b' [1]
+ * 'u4/*' (us[4] is never read) and 'z2_y_red/*' (y_red after the last conv layer feeds only the commented-out fc
+ * passthrough, :425-434) do not reach E: TensorFlow's compute_gradients returns None for them, their gradient here is 0.
+ * `c` supplies the x-only weights (stage concatenations, BatchNorm parameters) of the same model.
+ */
+ICNN_BE_API size_t icnn_be_conv_grad_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c);
+
+/* floats of device scratch icnn_be_conv_surrogate_grad needs for `batch` samples and `rows` feed rows (0: rejected) */
+ICNN_BE_API size_t icnn_be_conv_surrogate_grad_work_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, int batch,
+                                                           int rows);
+
+/*
+ * grad = d/dtheta  sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ]  over every trainable variable theta,
+ * float32, packed as icnn_be_conv_grad_floats describes -- what
+ *   F_ = c_ * E_ + reduce_sum(dE_dyFlat_ * v_, 1);  AdamOptimizer.compute_gradients(F_, theta_)
+ * evaluates in completion/icnn_ebundle.py:129-140 with the feed of train_step_fd (:315-335, icnn_be_implicit_feed with
+ * ICNN_BE_LOSS_MSE).
+ *   x[batch][H][W][1] float32      the minibatch, already h-flipped (:215); the rows of sample j are row_offset[j] ..
+ *                                  row_offset[j+1]-1 (int [batch+1], row_offset[0] = 0, row_offset[batch] = rows,
+ *                                  non-decreasing: what icnn_be_implicit_feed emits); a sample may have no rows
+ *   y, v[rows][H*W] float64, c[rows] float64   the feed (y rounded to float32 like a TensorFlow feed); v may be NULL
+ *   F_rows[rows] float32 or NULL   F_r = c_r E_r + <dE/dy_r, v_r>
+ *   work                           icnn_be_conv_surrogate_grad_work_floats(model, c, batch, rows) floats
+ * model->work is not used.  The u-path BatchNorm runs in training mode over the feed rows (each sample counted once per
+ * row, as the reference's x_ = fd_xs), computed on the batch samples with their multiplicities; icnn_be_conv_context
+ * keeps its plain batch statistics.  Deterministic (no atomics: the same bits on every call), no host synchronisation
+ * (capturable in a HIP graph).  ICNN_BE_EINVAL / ICNN_BE_ELIMIT for a bad shape (the rule of icnn_be_conv_fg) or a NULL
+ * required pointer before anything is launched.
+ */
+ICNN_BE_API int icnn_be_conv_surrogate_grad(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
+                                            const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                            float *grad, float *F_rows, float *work, void *stream);
+
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
 /*
