@@ -52,8 +52,11 @@ EXPORTS = [
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
+    "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
+    "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
+BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
 
 
 class State(C.Structure):
@@ -104,6 +107,11 @@ class ConvCtx(C.Structure):
         ("w_stage", C.c_void_p * 7), ("b_stage", C.c_void_p * 7), ("bn_gamma", C.c_void_p * 4), ("bn_beta", C.c_void_p * 4),
         ("bn_eps", C.c_float),
     ]
+
+
+class BnMoving(C.Structure):
+    """struct icnn_be_bn_moving"""
+    _fields_ = [("mean", C.c_void_p * MAX_LAYERS), ("var", C.c_void_p * MAX_LAYERS), ("decay", C.c_float)]
 
 
 _lib = None
@@ -216,10 +224,26 @@ def load():
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
     lib.icnn_be_conv_surrogate_grad.restype = C.c_int
+    lib.icnn_be_fc_context_bn_work_floats.argtypes = [C.POINTER(FcCtx), C.c_int]
+    lib.icnn_be_fc_context_bn_work_floats.restype = C.c_size_t
+    lib.icnn_be_fc_context_bn.argtypes = [C.POINTER(FcCtx), C.POINTER(BnMoving), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_fc_context_bn.restype = C.c_int
+    lib.icnn_be_conv_context_bn_work_floats.argtypes = [C.POINTER(ConvModel), C.c_int]
+    lib.icnn_be_conv_context_bn_work_floats.restype = C.c_size_t
+    lib.icnn_be_conv_context_bn.argtypes = [C.POINTER(ConvModel), C.POINTER(ConvCtx), C.POINTER(BnMoving), C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.icnn_be_conv_context_bn.restype = C.c_int
+    lib.icnn_be_fc_surrogate_grad_bn.argtypes = (lib.icnn_be_fc_surrogate_grad.argtypes[:-1]
+                                                 + [C.POINTER(BnMoving), C.c_int, C.c_void_p])
+    lib.icnn_be_fc_surrogate_grad_bn.restype = C.c_int
+    lib.icnn_be_conv_surrogate_grad_bn.argtypes = (lib.icnn_be_conv_surrogate_grad.argtypes[:-1]
+                                                   + [C.POINTER(BnMoving), C.c_int, C.c_void_p])
+    lib.icnn_be_conv_surrogate_grad_bn.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
-    if tuple(lib.icnn_be_struct_size(i) for i in range(5)) != (
-            C.sizeof(State), C.sizeof(FcModel), C.sizeof(FcCtx), C.sizeof(ConvModel), C.sizeof(ConvCtx)):
+    if tuple(lib.icnn_be_struct_size(i) for i in range(6)) != (
+            C.sizeof(State), C.sizeof(FcModel), C.sizeof(FcCtx), C.sizeof(ConvModel), C.sizeof(ConvCtx), C.sizeof(BnMoving)):
         raise ImportError("ctypes struct layout differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"

@@ -92,6 +92,23 @@ class BundleState:
                                               self.stream()), "icnn_be_dual_step")
 
 
+def fg_evaluations(n_iters, nIter, finished=None):
+    """How many times the reference's solveBatch evaluated `fg` on the minibatch -- the number of BatchNorm folds of
+    training mode a solve makes.  lib/bundle_entropy.py:203-240 / lib/bundle_entropy_dual.py:129-179
+    call fg once per outer iteration t and return after the iteration in which the last sample finished; a sample
+    that finishes at t records nIters = t - 1.  So: nIter while any sample is unfinished, else max(nIters) + 2 (at most
+    nIter).  `finished` (per sample, optional) marks the finished samples; without it a sample is unfinished when its
+    nIters equals nIter.  Variants 'dual' and 'pdipm' (the 'rl' variant's stall test finishes samples without recording
+    it in nIters)."""
+    n_iters = np.asarray(n_iters, dtype=np.int64).reshape(-1)
+    if n_iters.size == 0:
+        return 0
+    done = (n_iters < nIter) if finished is None else np.asarray(finished).reshape(-1).astype(bool)
+    if not done.all():
+        return int(nIter)
+    return int(min(nIter, int(n_iters.max()) + 2))
+
+
 class BundleResult:
     """Slot-addressed result on the device (see include/icnn_be.h): cut taken at outer
     iteration t lives in slot t; `active[u, :count[u]]` are the slots still in sample u's
@@ -104,6 +121,14 @@ class BundleResult:
         self.n_iters, self.finished, self.status = state.n_iters, state.finished, state.status
         self.newton_iters = state.newton_iters
         self._host_y = host_y
+
+    def fg_evaluations(self):
+        """fg_evaluations of this solve (one wait for the device): the BatchNorm folds the reference's solveBatch makes on
+        the minibatch, e.g. model.context(x, bn_updates=res.fg_evaluations()) for the statistics of a training
+        iteration."""
+        B = self.state.B
+        head = torch.stack([self.n_iters[:B], self.finished[:B].to(self.n_iters.dtype)]).cpu().numpy()
+        return fg_evaluations(head[0], self.state.n_iter, head[1])
 
     def raise_on_error(self):
         """Map per-sample status to the reference's exceptions (SURVEY.md 8(b) 'Errors')."""

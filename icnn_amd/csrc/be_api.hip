@@ -43,6 +43,24 @@ int check_state(const icnn_be_state *st) {
     return 0;
 }
 
+// BatchNorm mode arguments of the *_context_bn / *_surrogate_grad_bn entries (include/icnn_be.h); n[l] > 0 for the
+// batch-normalised layers.  mv is only needed (and only checked) when the model normalises and the call reads or folds it.
+int check_bn_mode(const icnn_be_bn_moving *mv, int mode, int updates, const int *n, int nl) {
+    if (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING) return ICNN_BE_EINVAL;
+    if (updates < 0 || (mode == ICNN_BE_BN_MOVING && updates > 0)) return ICNN_BE_EINVAL;
+    bool any = false;
+    for (int l = 0; l < nl; ++l) any = any || n[l] > 0;
+    if (!any || (mode == ICNN_BE_BN_BATCH && updates == 0)) return 0;
+    if (!mv || !(mv->decay >= 0.f && mv->decay <= 1.f)) return ICNN_BE_EINVAL;
+    for (int l = 0; l < nl; ++l)
+        if (n[l] > 0 && (!mv->mean[l] || !mv->var[l])) return ICNN_BE_EINVAL;
+    return 0;
+}
+void fc_bn_layers(const icnn_be_fc_ctx &c, int *n) {
+    for (int l = 0; l < ICNN_BE_MAX_LAYERS; ++l) n[l] = c.batchnorm && l < c.n_layers - 2 ? c.width[l] : 0;
+}
+const int CONV_BN_LAYERS[4] = {1, 1, 1, 1};      // every u-map of the conv model is batch-normalised
+
 // what icnn_be_solve_fc requires of a model and a state beyond their buffers
 int check_fc_solve(const icnn_be_fc_model *model, const icnn_be_state *st) {
     if (int rc = check_shape(st)) return rc;
@@ -178,7 +196,7 @@ const char *icnn_be_last_hip_error(void) { return hipGetErrorString(g_last); }
 size_t icnn_be_struct_size(int which) {
     return which == 0 ? sizeof(icnn_be_state) : which == 1 ? sizeof(icnn_be_fc_model)
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
-         : which == 4 ? sizeof(icnn_be_conv_ctx) : 0;
+         : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -302,10 +320,24 @@ size_t icnn_be_fc_context_work_floats(const icnn_be_fc_ctx *c, int batch) {
 
 int icnn_be_fc_context(const icnn_be_fc_ctx *c, const float *x, int batch, float *ctx, int ctx_width, float *work,
                        void *stream) {
+    return icnn_be_fc_context_bn(c, nullptr, ICNN_BE_BN_BATCH, 0, x, batch, ctx, ctx_width, work, stream);
+}
+
+size_t icnn_be_fc_context_bn_work_floats(const icnn_be_fc_ctx *c, int batch) {
+    if (!c || batch < 0 || icnn_be::ctx_check(*c) != 0) return 0;
+    return icnn_be::ctx_bn_work_floats(*c, batch);
+}
+
+int icnn_be_fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode, int updates, const float *x,
+                          int batch, float *ctx, int ctx_width, float *work, void *stream) {
     if (!c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
+    int n[ICNN_BE_MAX_LAYERS];
+    fc_bn_layers(*c, n);
+    if (int rc = check_bn_mode(mv, mode, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream));
+    hipError_t e = icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream), mv, mode,
+                                              updates);
     return e == hipSuccess ? 0 : fail(e);
 }
 
@@ -322,11 +354,21 @@ size_t icnn_be_fc_surrogate_grad_work_floats(const icnn_be_fc_model *model, cons
 int icnn_be_fc_surrogate_grad(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
                               const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                               float *grad, float *F_rows, float *work, void *stream) {
+    return icnn_be_fc_surrogate_grad_bn(model, c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work, nullptr, 0, stream);
+}
+
+int icnn_be_fc_surrogate_grad_bn(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                                 const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                 float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
+                                 void *stream) {
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
+    int n[ICNN_BE_MAX_LAYERS];
+    fc_bn_layers(*c, n);
+    if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (int rc = icnn_be::fc_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                     static_cast<hipStream_t>(stream));
+                                                     static_cast<hipStream_t>(stream), mv, updates);
     return e == hipSuccess ? 0 : fail(e);
 }
 
@@ -343,14 +385,23 @@ size_t icnn_be_conv_surrogate_grad_work_floats(const icnn_be_conv_model *model, 
 int icnn_be_conv_surrogate_grad(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
                                 const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                 float *grad, float *F_rows, float *work, void *stream) {
+    return icnn_be_conv_surrogate_grad_bn(model, c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work, nullptr, 0,
+                                          stream);
+}
+
+int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
+                                   const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                   float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
+                                   void *stream) {
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     for (int s = 0; s < 7; ++s)
         if (!c->w_stage[s] || !c->b_stage[s]) return ICNN_BE_EINVAL;
     for (int i = 0; i < 4; ++i)
         if (!c->bn_gamma[i] || !c->bn_beta[i]) return ICNN_BE_EINVAL;
+    if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, CONV_BN_LAYERS, 4)) return rc;
     if (int rc = icnn_be::conv_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                       static_cast<hipStream_t>(stream));
+                                                       static_cast<hipStream_t>(stream), mv, updates);
     return e == hipSuccess ? 0 : fail(e);
 }
 
@@ -487,6 +538,17 @@ size_t icnn_be_conv_context_work_floats(const icnn_be_conv_model *shape, int bat
 
 int icnn_be_conv_context(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const float *x, int batch, float *ctx,
                          float *work, void *stream) {
+    return icnn_be_conv_context_bn(shape, c, nullptr, ICNN_BE_BN_BATCH, 0, x, batch, ctx, work, stream);
+}
+
+size_t icnn_be_conv_context_bn_work_floats(const icnn_be_conv_model *shape, int batch) {
+    icnn_be::ConvCtxShape g{};
+    if (!shape || batch < 0 || icnn_be::conv_ctx_shape(*shape, g) != 0) return 0;
+    return icnn_be::conv_ctx_bn_work_floats(g, batch);
+}
+
+int icnn_be_conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv, int mode,
+                            int updates, const float *x, int batch, float *ctx, float *work, void *stream) {
     if (!shape || !c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
     for (int s = 0; s < 7; ++s)
         if (!c->w_stage[s] || !c->b_stage[s]) return ICNN_BE_EINVAL;
@@ -494,8 +556,9 @@ int icnn_be_conv_context(const icnn_be_conv_model *shape, const icnn_be_conv_ctx
         if (!c->bn_gamma[i] || !c->bn_beta[i]) return ICNN_BE_EINVAL;
     icnn_be::ConvCtxShape g{};
     if (int rc = icnn_be::conv_ctx_shape(*shape, g)) return rc;
+    if (int rc = check_bn_mode(mv, mode, updates, CONV_BN_LAYERS, 4)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream));
+    hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates);
     return e == hipSuccess ? 0 : fail(e);
 }
 

@@ -11,7 +11,9 @@
 // output tile per workgroup of four waves, both operands staged through LDS (A as is, W transposed so that a lane's
 // four k-values are one ds_read_b128), register prefetch of the next k-block.  BatchNorm uses the statistics of the
 // batch it is given, like the reference (tflearn.is_training(True), :209,:259): one workgroup per 64 columns, three
-// passes over its column block (mean, variance of the centred values, normalise in place).
+// passes over its column block (mean, variance of the centred values, normalise in place); the statistics it normalised
+// with can be handed out and folded into the moving statistics.  Inference mode (tflearn.is_training(False)) normalises
+// with the moving statistics instead: one element-wise pass.
 #include <hip/hip_runtime.h>
 
 #include <initializer_list>
@@ -149,8 +151,9 @@ __global__ __launch_bounds__(GT) void ctx_gemm_kernel(CtxGemmArgs a) {
 // mode = tf.nn.moments + tf.nn.batch_normalization (epsilon 1e-5), multi-label-cls/icnn_ebundle.py:345.
 // One workgroup per 32 columns (ld is a multiple of 4: float4 accesses, 128 contiguous bytes per row), 128 row groups.
 constexpr int BNT = 1024, BNC = 32, BNQ = BNC / 4, BNG = BNT / BNQ;
+// stat_out (may be NULL): the mean [N] and the biased variance [N] it normalised with, one after the other.
 __global__ __launch_bounds__(BNT) void ctx_bn_kernel(float *u, int ld, int M, int N, const float *gamma, const float *beta,
-                                                     float eps) {
+                                                     float eps, float *stat_out) {
     __shared__ f4 red[BNG][BNQ];
     __shared__ f4 stat[2][BNQ];
     const int cq = threadIdx.x % BNQ, g = threadIdx.x / BNQ, col = blockIdx.x * BNC + 4 * cq;
@@ -184,6 +187,10 @@ __global__ __launch_bounds__(BNT) void ctx_bn_kernel(float *u, int ld, int M, in
         ga[i] = col + i < N ? gamma[col + i] : 0.f;
         be[i] = col + i < N ? beta[col + i] : 0.f;
     }
+    if (stat_out && g == 0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (col + i < N) { stat_out[col + i] = mean[i]; stat_out[N + col + i] = var[i]; }
     for (int r = g; r < M; r += BNG) {
         f4 *p = reinterpret_cast<f4 *>(u + (size_t)r * ld + col);
         *p = (*p - mean) * inv * ga + be;
@@ -243,8 +250,9 @@ __global__ __launch_bounds__(BNT) void ctx_bn_apply_kernel(float *u, int ld, int
 // forms from the pass-0 partials in the same fixed order), pass 2 normalises.  No atomics: the statistics are the same
 // bits whatever the schedule.
 constexpr int BNB = 128, TBT = 256;
+// Pass 2 of workgroup 0 hands the statistics out to stat_out (may be NULL) like ctx_bn_kernel.
 __global__ __launch_bounds__(TBT) void ctx_bn_tall_kernel(float *u, int ld, int M, int N, float *part, const float *gamma,
-                                                          const float *beta, float eps, int pass) {
+                                                          const float *beta, float eps, int pass, float *stat_out) {
     __shared__ f4 red[TBT];
     const int nq = N / 4, cq = threadIdx.x % nq, g = threadIdx.x / nq, ng = TBT / nq;    // N a multiple of 4, N <= 256
     const bool live = g < ng;
@@ -286,11 +294,52 @@ __global__ __launch_bounds__(TBT) void ctx_bn_tall_kernel(float *u, int ld, int 
             ga[i] = gamma[4 * cq + i];
             be[i] = beta[4 * cq + i];
         }
+        if (stat_out && blockIdx.x == 0 && g == 0)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { stat_out[4 * cq + i] = mean[i]; stat_out[N + 4 * cq + i] = var[i]; }
         for (int r = r0 + g; r < r1; r += ng) {
             f4 *p = reinterpret_cast<f4 *>(u + (size_t)r * ld + 4 * cq);
             *p = (*p - mean) * inv * ga + be;
         }
     }
+}
+
+// Inference-mode BatchNorm in place on u[M][ld], columns [0, N): u = (u - mean) gamma / sqrt(var + eps) + beta with the
+// moving statistics -- the arithmetic of ctx_bn_kernel's normalisation, element by element, so a row's result does not
+// depend on the other rows.  One thread per element, grid-stride.
+__global__ void ctx_bn_affine_kernel(float *u, int ld, int M, int N, const float *mean, const float *var, const float *gamma,
+                                     const float *beta, float eps) {
+    const size_t total = (size_t)M * N;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / N), col = (int)(i - (size_t)r * N);
+        const float inv = 1.f / sqrtf(var[col] + eps);
+        float *p = u + (size_t)r * ld + col;
+        *p = (*p - mean[col]) * inv * gamma[col] + beta[col];
+    }
+}
+
+// `updates` folds of the exported batch statistics into the moving ones, every batch-normalised layer in one launch
+// (blockIdx.y = layer): assign_moving_average without zero-debias, in float32, rounded after every operation like
+// TensorFlow's sub / mul / assign_sub.
+struct BnFoldArgs {
+    float *mean[ICNN_BE_MAX_LAYERS], *var[ICNN_BE_MAX_LAYERS];
+    const float *stat[ICNN_BE_MAX_LAYERS];      // mu [N] then sigma^2 [N]
+    int N[ICNN_BE_MAX_LAYERS];
+    float d;                                     // 1 - decay
+    int updates;
+};
+__global__ void bn_fold_kernel(BnFoldArgs a) {
+#pragma clang fp contract(off)
+    const int l = blockIdx.y, col = blockIdx.x * blockDim.x + threadIdx.x, N = a.N[l];
+    if (col >= N) return;
+    const float mu = a.stat[l][col], s2 = a.stat[l][N + col];
+    float m = a.mean[l][col], v = a.var[l][col];
+    for (int k = 0; k < a.updates; ++k) {
+        m = m - (m - mu) * a.d;
+        v = v - (v - s2) * a.d;
+    }
+    a.mean[l][col] = m;
+    a.var[l][col] = v;
 }
 
 // makeCvx (|W|) / proj (max(W, 0)) on the packed 'zu_proj' operands of a model, both orientations, in place
@@ -322,6 +371,48 @@ size_t ctx_work_floats(const icnn_be_fc_ctx &c, int batch) {
     size_t tot = 0;
     for (int i = 0; i + 1 < c.n_layers; ++i) tot += (size_t)batch * ((c.width[i] + 3) & ~3);
     return tot;
+}
+
+// The exported batch statistics of layer l sit behind the u-maps: mean [N_l] then variance [N_l], layers in order, each pair
+// rounded up to a multiple of four floats.  Widths of the normalised layers: n[l] (0: none).
+static size_t bn_stat_floats(const int *n, int nl) {
+    size_t tot = 0;
+    for (int l = 0; l < nl; ++l) tot += (size_t)((2 * n[l] + 3) & ~3);
+    return tot;
+}
+static float *bn_stat_at(float *stats, const int *n, int l) {
+    for (int i = 0; i < l; ++i) stats += (2 * n[i] + 3) & ~3;
+    return stats;
+}
+static void fc_bn_widths(const icnn_be_fc_ctx &c, int *n) {
+    for (int l = 0; l < ICNN_BE_MAX_LAYERS; ++l) n[l] = c.batchnorm && l < c.n_layers - 2 ? c.width[l] : 0;
+}
+size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch) {
+    int n[ICNN_BE_MAX_LAYERS];
+    fc_bn_widths(c, n);
+    return ctx_work_floats(c, batch) + bn_stat_floats(n, ICNN_BE_MAX_LAYERS);
+}
+
+hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const int *n, int nl, int updates,
+                          hipStream_t stream) {
+    BnFoldArgs a{};
+    int most = 0;
+    for (int l = 0; l < nl; ++l) {
+        a.mean[l] = mv.mean[l]; a.var[l] = mv.var[l]; a.stat[l] = stat[l]; a.N[l] = n[l];
+        most = n[l] > most ? n[l] : most;
+    }
+    a.d = 1.f - mv.decay;                  // float32(1 - decay), as tf.convert_to_tensor(1 - decay) in assign_moving_average
+    a.updates = updates;
+    if (updates == 0 || most == 0) return hipSuccess;
+    return launch_kernel(bn_fold_kernel, dim3((most + 255) / 256, nl), dim3(256), 0, stream, a);
+}
+
+hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
+                            const float *beta, float eps, hipStream_t stream) {
+    const size_t total = (size_t)rows * cols;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    return launch_kernel(ctx_bn_affine_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, u, ld, rows, cols, mean, var,
+                         gamma, beta, eps);
 }
 
 // Stage i of the context producer: ONE GEMM over everything that reads prev_i (x for i = 0, else u_{i-1} in `work`), epilogue
@@ -370,21 +461,32 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
     return launch_kernel(ctx_gemm_kernel, dim3((batch + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
 }
 
+// mode ICNN_BE_BN_BATCH: batch statistics, folded `updates` times into *mv (work: ctx_bn_work_floats when updates > 0);
+// ICNN_BE_BN_MOVING: the moving statistics of *mv (arguments checked by the caller)
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
-                             hipStream_t stream) {
+                             hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates) {
     const int L = c.n_layers - 1;
+    int n[ICNN_BE_MAX_LAYERS];
+    fc_bn_widths(c, n);
+    float *stats = c.batchnorm && updates > 0 ? work + ctx_work_floats(c, batch) : nullptr, *stat[ICNN_BE_MAX_LAYERS] = {};
     for (int i = 0; i <= L; ++i) {
         hipError_t e = launch_fc_context_stage(c, i, x, batch, ctx, ctx_width, work, stream);
         if (e != hipSuccess) return e;
         if (i < L && stage_bn(c, i)) {
             int u_ld = 0;
             float *u_out = stage_u(c, i, batch, work, u_ld);
-            e = launch_kernel(ctx_bn_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u_out, u_ld, batch,
-                              c.width[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
+            if (mode == ICNN_BE_BN_MOVING) {
+                e = launch_bn_affine(u_out, u_ld, batch, c.width[i], mv->mean[i], mv->var[i], c.bn_gamma[i], c.bn_beta[i],
+                                     c.bn_eps, stream);
+            } else {
+                if (stats) stat[i] = bn_stat_at(stats, n, i);
+                e = launch_kernel(ctx_bn_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u_out, u_ld, batch,
+                                  c.width[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps, stat[i]);
+            }
             if (e != hipSuccess) return e;
         }
     }
-    return hipSuccess;
+    return stats ? launch_bn_fold(*mv, stat, n, L > 1 ? L - 1 : 0, updates, stream) : hipSuccess;
 }
 
 // statistics of stage i's u (this rank's rows) -> stats[2][width_i] float64; 1 = the stage has no BatchNorm (nothing written)
@@ -413,6 +515,14 @@ hipError_t launch_fc_context_norm(const icnn_be_fc_ctx &c, int i, int batch, dou
 size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch) {
     return (size_t)batch * ((size_t)g.P[0] * g.F[0] + (size_t)g.P[1] * g.F[1] + (size_t)g.P[2] * g.F[2] + (size_t)((g.fch + 3) & ~3)) +
            2 * (size_t)BNB * 256;                    // + the BatchNorm partials
+}
+static void conv_bn_widths(const ConvCtxShape &g, int *n) {
+    n[0] = g.F[0]; n[1] = g.F[1]; n[2] = g.F[2]; n[3] = g.fch;
+}
+size_t conv_ctx_bn_work_floats(const ConvCtxShape &g, int batch) {
+    int n[4];
+    conv_bn_widths(g, n);
+    return conv_ctx_work_floats(g, batch) + bn_stat_floats(n, 4);
 }
 
 float *conv_ctx_u(const ConvCtxShape &g, int batch, float *work, int l) {
@@ -472,18 +582,24 @@ hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_c
 }
 
 hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
-                               float *work, hipStream_t stream) {
+                               float *work, hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates) {
     float *part = conv_ctx_u(g, batch, work, 4);
+    int n[4];
+    conv_bn_widths(g, n);
+    float *stats = updates > 0 ? work + conv_ctx_work_floats(g, batch) : nullptr, *stat[4] = {};
     auto bn = [&](float *u, int ld, int rows, int cols, int i) -> hipError_t {
+        if (mode == ICNN_BE_BN_MOVING)
+            return launch_bn_affine(u, ld, rows, cols, mv->mean[i], mv->var[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps, stream);
+        if (stats) stat[i] = bn_stat_at(stats, n, i);
         if (rows >= 16 * BNB && cols % 4 == 0 && cols <= 256 && ld == cols) {          // tall: row-parallel passes
             hipError_t e = hipSuccess;
             for (int pass = 0; pass < 3 && e == hipSuccess; ++pass)
                 e = launch_kernel(ctx_bn_tall_kernel, dim3(BNB), dim3(TBT), 0, stream, u, ld, rows, cols, part, c.bn_gamma[i],
-                                  c.bn_beta[i], c.bn_eps, pass);
+                                  c.bn_beta[i], c.bn_eps, pass, stat[i]);
             return e;
         }
         return launch_kernel(ctx_bn_kernel, dim3((cols + BNC - 1) / BNC), dim3(BNT), 0, stream, u, ld, rows, cols, c.bn_gamma[i],
-                             c.bn_beta[i], c.bn_eps);
+                             c.bn_beta[i], c.bn_eps, stat[i]);
     };
     // stage order of the launches; each u-map is normalised before the first stage that reads it
     hipError_t e = hipSuccess;
@@ -495,6 +611,7 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
         else if (stage == 4) e = bn(conv_ctx_u(g, batch, work, 2), g.F[2], batch * g.P[2], g.F[2], 2);
         else if (stage == 5) e = bn(conv_ctx_u(g, batch, work, 3), (g.fch + 3) & ~3, batch, g.fch, 3);
     }
+    if (e == hipSuccess && stats) e = launch_bn_fold(*mv, stat, n, 4, updates, stream);
     return e;
 }
 

@@ -91,8 +91,18 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
 // x-only context producer and clamps (be_context.hip)
 int ctx_check(const icnn_be_fc_ctx &c);
 size_t ctx_work_floats(const icnn_be_fc_ctx &c, int batch);
+// mv / mode / updates: BatchNorm mode (include/icnn_be.h icnn_be_fc_context_bn, arguments checked by the caller); the
+// defaults are icnn_be_fc_context
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
-                             hipStream_t stream);
+                             hipStream_t stream, const icnn_be_bn_moving *mv = nullptr, int mode = ICNN_BE_BN_BATCH,
+                             int updates = 0);
+size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch);
+// `updates` folds of stat[l] (mean [n[l]] then biased variance [n[l]], device) into mv's layers 0 .. nl-1 (n[l] = 0: none),
+// one launch; and inference-mode BatchNorm in place on u[rows][ld], columns [0, cols)
+hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const int *n, int nl, int updates,
+                          hipStream_t stream);
+hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
+                            const float *beta, float eps, hipStream_t stream);
 hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *x, int batch, float *ctx, int ctx_width,
                                    float *work, hipStream_t stream);
 int launch_fc_context_sums(const icnn_be_fc_ctx &c, int i, int batch, float *work, double *stats, hipStream_t stream,
@@ -110,7 +120,9 @@ struct ConvCtxShape {
 int conv_ctx_shape(const icnn_be_conv_model &m, ConvCtxShape &g);
 size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch);
 hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
-                               float *work, hipStream_t stream);
+                               float *work, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr,
+                               int mode = ICNN_BE_BN_BATCH, int updates = 0);
+size_t conv_ctx_bn_work_floats(const ConvCtxShape &g, int batch);
 // one stage's GEMM of launch_conv_context (u-maps ReLU'd but not normalised); conv_ctx_u: u_l (l = 0..3) inside `work`
 hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_ctx &c, int stage, const float *x, int batch,
                                      float *ctx, float *work, hipStream_t stream);
@@ -123,7 +135,8 @@ size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx 
 int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool with_v);
 hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
-                                    float *grad, float *F_rows, float *work, hipStream_t stream);
+                                    float *grad, float *F_rows, float *work, hipStream_t stream,
+                                    const icnn_be_bn_moving *mv = nullptr, int updates = 0);
 // the strided f32-MFMA GEMM of be_train_fc.hip: C[M][N] (pitch ldc) = A B, A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn],
 // split-K into `part` (tr_gemm_part_floats(M, N, K) floats) and summed in split order -- no atomics
 size_t tr_gemm_part_floats(int M, int N, int K);
@@ -136,7 +149,8 @@ size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_con
 int conv_surrogate_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows, bool with_v);
 hipError_t launch_conv_surrogate_grad(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, const float *x, int batch,
                                       const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
-                                      float *grad, float *F_rows, float *work, hipStream_t stream);
+                                      float *grad, float *F_rows, float *work, hipStream_t stream,
+                                      const icnn_be_bn_moving *mv = nullptr, int updates = 0);
 
 // LDS layouts of the persistent kernels (be_fused.hip), host arithmetic only.  false: the shape does not fit that kernel.
 // The solve plan (be_api.hip) and the launchers below take their fit decisions from these two functions alone.

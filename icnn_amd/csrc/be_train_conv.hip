@@ -353,7 +353,8 @@ __global__ void tc_segment_sum_kernel(const float *rows, const int *row_offset, 
 // Weighted BatchNorm of a u-map [rows][N] (pitch ld; row = (sample, position), P positions per sample), BatchNorm over the R
 // feed rows = over the samples with weights m_j (Mtot = R P): grid (NCH row chunks, column blocks of 32), fixed-order sums.
 //   pass 0: per-chunk weighted sums;  pass 1: per-chunk weighted squared deviations from the mean (every workgroup forms it
-//   from the pass-0 partials in the same order);  pass 2: hsave = h, xhat, u = gamma xhat + beta in place, inv.
+//   from the pass-0 partials in the same order);  pass 2: hsave = h, xhat, u = gamma xhat + beta in place, inv, and the
+//   mean [N] and variance [N] it normalised with to stat (may be NULL) for the moving statistics.
 constexpr int NCH = 64, WBT = 256, WBC = 32, WBG = WBT / WBC;
 struct WbnArgs {
     float *u;
@@ -362,7 +363,7 @@ struct WbnArgs {
     float Mtot;
     const float *gamma, *beta;
     float eps;
-    float *part, *hsave, *xhat, *inv;
+    float *part, *hsave, *xhat, *inv, *stat;
 };
 __device__ __forceinline__ float wg_colsum(float (*red)[WBC], int g, int c, float mine) {
     red[g][c] = mine;
@@ -394,9 +395,12 @@ __global__ __launch_bounds__(WBT) void tc_wbn_fwd_kernel(WbnArgs a, int pass) {
         return;
     }
     if (!ok) return;
-    const float inv = 1.f / sqrtf(chunk_total(a.part + (size_t)NCH * a.N, a.N, col) / a.Mtot + a.eps);
+    const float var = chunk_total(a.part + (size_t)NCH * a.N, a.N, col) / a.Mtot, inv = 1.f / sqrtf(var + a.eps);
     const float ga = a.gamma[col], be = a.beta[col];
-    if (ch == 0 && g == 0) a.inv[col] = inv;
+    if (ch == 0 && g == 0) {
+        a.inv[col] = inv;
+        if (a.stat) { a.stat[col] = mean; a.stat[a.N + col] = var; }
+    }
     for (int r = r0 + g; r < r1; r += WBG) {
         const float h = a.u[(size_t)r * a.ld + col], xh = (h - mean) * inv;
         a.hsave[(size_t)r * a.N + col] = h;
@@ -589,7 +593,8 @@ struct Runner {
 
 hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx, const TrainShape &s, const float *x,
                          const int *row_offset, const double *y, const double *v, const double *cvec, float *grad, float *F_rows,
-                         float *work, size_t *work_floats, hipStream_t stream) {
+                         float *work, size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr,
+                         int updates = 0) {
     const ConvCtxShape &g = s.g;
     const int B = s.B, R = s.R, R2 = s.R2, n = s.n, C = s.C, fch = g.fch, flat = g.flat;
     const int tan = v != nullptr;
@@ -606,11 +611,12 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
         uN[l] = l < 3 ? g.F[l] : fch;
         uld[l] = l < 3 ? g.F[l] : (fch + 3) & ~3;
     }
-    float *hsave[4], *xhat[4], *inv[4];
+    float *hsave[4], *xhat[4], *inv[4], *stat[4];
     for (int l = 0; l < 4; ++l) {
         hsave[l] = cv.take((size_t)urows[l] * uN[l]);
         xhat[l] = cv.take((size_t)urows[l] * uN[l]);
         inv[l] = cv.take(uN[l]);
+        stat[l] = cv.take(2 * (size_t)uN[l]);        // the weighted statistics, for the moving ones
     }
     float *bnpart = cv.take(2 * (size_t)NCH * (fch > 64 ? fch : 64));      // widest u-map: u3 (fch) or 64 channels
     // y-path state
@@ -696,7 +702,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     // 2. x-only forward on the B samples: stage GEMMs of the context producer, weighted BatchNorm behind the u-maps
     auto wbn_fwd = [&](int l) {
         WbnArgs a{u_[l], uld[l], urows[l], uP[l], uN[l], mult, (float)R * uP[l], cx.bn_gamma[l], cx.bn_beta[l], cx.bn_eps,
-                  bnpart, hsave[l], xhat[l], inv[l]};
+                  bnpart, hsave[l], xhat[l], inv[l], updates > 0 ? stat[l] : nullptr};
         for (int pass = 0; pass < 3; ++pass)
             run.launch(tc_wbn_fwd_kernel, dim3(NCH, (uN[l] + WBC - 1) / WBC), WBT, a, pass);
     };
@@ -707,6 +713,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
         else if (q == 4) wbn_fwd(2);
         else if (q == 5) wbn_fwd(3);
     }
+    if (updates > 0 && !run.dry() && run.err == hipSuccess) run.err = launch_bn_fold(*mv, stat, uN, 4, updates, stream);
 
     // 3. y-path forward, primal and tangent rows stacked
     auto colargs = [&](const float *in, int rows, int IH, int IW, int IC, int KS, int ST, int PD, int OH, int OW, int ld,
@@ -832,10 +839,11 @@ int conv_surrogate_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c,
 
 hipError_t launch_conv_surrogate_grad(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, const float *x, int batch,
                                       const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
-                                      float *grad, float *F_rows, float *work, hipStream_t stream) {
+                                      float *grad, float *F_rows, float *work, hipStream_t stream,
+                                      const icnn_be_bn_moving *mv, int updates) {
     TrainShape s;
     if (make_shape(m, c, batch, rows, v != nullptr, s) != 0) return hipErrorInvalidValue;
-    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream);
+    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates);
 }
 
 }  // namespace icnn_be

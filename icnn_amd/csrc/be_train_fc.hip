@@ -247,11 +247,12 @@ __global__ void tr_segment_sum_kernel(const float *rows, const int *row_offset, 
 
 // Weighted batch statistics (BatchNorm in training mode over the R feed rows = over the B samples with weights m_j):
 // one workgroup per 32 columns, fixed-order tree.  h (the ReLU'd stage output, pitch ld) is copied to hsave, u = gamma
-// xhat + beta replaces it in place (the next stage reads it there), xhat and inv-std are kept for the backward pass.
+// xhat + beta replaces it in place (the next stage reads it there), xhat and inv-std are kept for the backward pass, the
+// mean [N] and variance [N] it normalised with go to stat_out (may be NULL) for the moving statistics.
 constexpr int WBT = 256, WBC = 32, WBG = WBT / WBC;
 __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B, int N, const float *mult, float M,
                                                          const float *gamma, const float *beta, float eps, float *hsave,
-                                                         float *xhat, float *inv_out) {
+                                                         float *xhat, float *inv_out, float *stat_out) {
     __shared__ float red[WBG][WBC];
     __shared__ float stat[2][WBC];
     const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.x * WBC + c;
@@ -278,7 +279,10 @@ __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B
     total(s, &stat[1][c]);
     if (!ok) return;
     const float inv = 1.f / sqrtf(stat[1][c] + eps), ga = gamma[col], be = beta[col];
-    if (g == 0) inv_out[col] = inv;
+    if (g == 0) {
+        inv_out[col] = inv;
+        if (stat_out) { stat_out[col] = mean; stat_out[N + col] = stat[1][c]; }
+    }
     for (int j = g; j < B; j += WBG) {
         const float h = u[(size_t)j * ld + col], xh = (h - mean) * inv;
         hsave[(size_t)j * N + col] = h;
@@ -504,7 +508,7 @@ struct Runner {
 // The whole step; with work == nullptr only sizes the workspace (returned through *work_floats)
 hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, const TrainShape &s, const float *x, const int *row_offset,
                   const double *y, const double *v, const double *cvec, float *grad, float *F_rows, float *work,
-                  size_t *work_floats, hipStream_t stream) {
+                  size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr, int updates = 0) {
     const int L = s.L, B = s.B, R = s.R, R2 = s.R2, n = s.n, C = s.C;
     Carver cv{work};
     int *samp = reinterpret_cast<int *>(cv.take(R));
@@ -512,11 +516,15 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
     float *uwork = cv.take(ctx_work_floats(cx, B));
     float *ctxb = cv.take((size_t)B * C);
     float *hsave[ICNN_BE_MAX_LAYERS] = {}, *xhat[ICNN_BE_MAX_LAYERS] = {}, *inv[ICNN_BE_MAX_LAYERS] = {};
+    float *stat[ICNN_BE_MAX_LAYERS] = {};       // the weighted statistics, for the moving ones
+    int bn_n[ICNN_BE_MAX_LAYERS] = {};
     for (int i = 0; i + 1 < L; ++i)
         if (s.bn) {
             hsave[i] = cv.take((size_t)B * s.w[i]);
             xhat[i] = cv.take((size_t)B * s.w[i]);
             inv[i] = cv.take(s.w[i]);
+            stat[i] = cv.take(2 * (size_t)s.w[i]);
+            bn_n[i] = s.w[i];
         }
     float *wst[ICNN_BE_MAX_LAYERS], *pq[ICNN_BE_MAX_LAYERS], *adj[ICNN_BE_MAX_LAYERS], *Z[ICNN_BE_MAX_LAYERS] = {},
           *D[ICNN_BE_MAX_LAYERS] = {}, *dpre[ICNN_BE_MAX_LAYERS];
@@ -561,9 +569,11 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
             float *u = uwork;
             for (int l = 0; l < i; ++l) u += (size_t)B * s.u_ld(l);
             run.launch(tr_wbn_fwd_kernel, (s.w[i] + WBC - 1) / WBC, WBT, u, s.u_ld(i), B, s.w[i], (const float *)mult, (float)R,
-                       cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i]);
+                       cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i], updates > 0 ? stat[i] : nullptr);
         }
     }
+    if (s.bn && updates > 0 && !run.dry() && run.err == hipSuccess)
+        run.err = launch_bn_fold(*mv, stat, bn_n, L - 1, updates, stream);
     // 3. y-path forward: primal and tangent rows stacked, one GEMM per layer
     for (int i = 0; i <= L; ++i) {
         const int ld = s.pq_ld(i), w = s.w[i];
@@ -677,10 +687,11 @@ int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int b
 
 hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
-                                    float *grad, float *F_rows, float *work, hipStream_t stream) {
+                                    float *grad, float *F_rows, float *work, hipStream_t stream, const icnn_be_bn_moving *mv,
+                                    int updates) {
     TrainShape s;
     if (make_shape(m, c, batch, rows, v != nullptr, s) != 0) return hipErrorInvalidValue;
-    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream);
+    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates);
 }
 
 }  // namespace icnn_be

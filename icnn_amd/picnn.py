@@ -156,6 +156,32 @@ def project(params):
     return params
 
 
+def bn_layers(spec):
+    """(index, width) of every batch-normalised u-layer: FC u_i for i < L-1 when `batchnorm`; conv u0..u2 (per channel)
+    and u3 (per column)."""
+    if isinstance(spec, ConvSpec):
+        return [(l, nf) for l, (nf, k, s) in enumerate(CONV_LAYERS)] + [(3, CONV_FCS[0])]
+    return [(i, spec.szs[i]) for i in range(len(spec.szs) - 1)] if spec.batchnorm else []
+
+
+def init_bn_stats(spec) -> Dict[str, np.ndarray]:
+    """The BatchNorm moving statistics of a fresh model, as tflearn.batch_normalization creates them: 'u{i}/bn/moving_mean'
+    zeros and 'u{i}/bn/moving_variance' ones (float32) for every batch-normalised layer of an FCSpec or a ConvSpec.  Not
+    trainable: a dict of its own, beside init_params / init_conv_params."""
+    out = {}
+    for i, w in bn_layers(spec):
+        out["u%d/bn/moving_mean" % i] = np.zeros(w, np.float32)
+        out["u%d/bn/moving_variance" % i] = np.ones(w, np.float32)
+    return out
+
+
+def _moving_bn(u, t, bn_stats, i):
+    """inference-mode BatchNorm of layer i (tflearn.is_training(False)): the moving statistics instead of the batch's"""
+    m = torch.as_tensor(bn_stats["u%d/bn/moving_mean" % i], device=u.device).to(u.dtype)
+    v = torch.as_tensor(bn_stats["u%d/bn/moving_variance" % i], device=u.device).to(u.dtype)
+    return (u - m) / torch.sqrt(v + 1e-5) * t["u%d/bn/gamma" % i].to(u.dtype) + t["u%d/bn/beta" % i].to(u.dtype)
+
+
 def stage_weights(spec: FCSpec, params):
     """Per stage i = 0..L the column-wise concatenation icnn_be_fc_context multiplies prev_i with (include/icnn_be.h):
     [ u{i}/W (i < L) | z{i}_yu_u/W | z{i}_u/W | z{i}_zu_u/W (i > 0) ], padded with zero columns to a multiple of four,
@@ -173,12 +199,13 @@ def stage_weights(spec: FCSpec, params):
     return out
 
 
-def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=None) -> torch.Tensor:
+def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=None, bn_stats=None) -> torch.Tensor:
     """Host-side (torch) statement of the x-only context [B, C] float32, laid out per layer as
     yu_i | zu_i | gate_i (include/icnn_be.h); what the CPU tests and the gloo sharding tests use.  On the GPU
     `FCModel.context` runs the hand-written kernels of be_context.hip instead.  BatchNorm uses the statistics of
     the batch it is given (the reference runs with tflearn.is_training(True)), so
-    when a minibatch is sharded across GPUs call this on the whole batch first."""
+    when a minibatch is sharded across GPUs call this on the whole batch first.  With `bn_stats` (init_bn_stats' keys)
+    it runs in inference mode instead and normalises with those moving statistics."""
     dev = x.device
     t = {k: torch.as_tensor(v, device=dev) for k, v in params.items()}
     L = len(spec.szs)
@@ -193,7 +220,9 @@ def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=
         u = torch.addmm(t["u%d/b" % i], prev, t["u%d/W" % i])
         if i < L - 1:
             u = torch.relu(u)
-            if spec.batchnorm and all_reduce is not None:
+            if spec.batchnorm and bn_stats is not None:
+                u = _moving_bn(u, t, bn_stats, i)
+            elif spec.batchnorm and all_reduce is not None:
                 # data-parallel ranks: x is this rank's shard, the statistics are the global batch's -- one all-reduce of
                 # (sum u, sum u^2) in float64, as icnn_be_fc_context_stage / _norm do on the device
                 st = torch.stack([u.double().sum(dim=0), (u.double() ** 2).sum(dim=0)])
@@ -219,7 +248,49 @@ def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=
     return ctx
 
 
-class FCModel:
+class _BnMovingStats:
+    """The BatchNorm moving statistics a device model owns (struct icnn_be_bn_moving): float32 device tensors keyed like
+    init_bn_stats, updated in place (their addresses never change, so captured graphs keep finding them) and kept across
+    `repack`.  bn_decay: tflearn's `decay` (0.9)."""
+    bn_decay = 0.9
+
+    def _init_bn_stats(self):
+        self.bn_stats = {k: torch.from_numpy(v).to(self.device) for k, v in init_bn_stats(self.spec).items()}
+
+    def set_bn_stats(self, stats):
+        """Copy moving statistics (a dict keyed like init_bn_stats: arrays or tensors) into the model's tensors."""
+        if set(stats) != set(self.bn_stats):
+            raise KeyError("BatchNorm statistics keys %s, the model has %s" % (sorted(stats), sorted(self.bn_stats)))
+        for k, t in self.bn_stats.items():
+            v = torch.as_tensor(np.asarray(stats[k], np.float32) if not torch.is_tensor(stats[k]) else stats[k])
+            if tuple(v.shape) != tuple(t.shape):
+                raise ValueError("%s has shape %s, the model's %s" % (k, tuple(v.shape), tuple(t.shape)))
+            t.copy_(v.to(t.device, torch.float32))
+
+    def get_bn_stats(self):
+        """The moving statistics as host float32 arrays (waits for the work enqueued on the device)."""
+        return {k: t.cpu().numpy().copy() for k, t in self.bn_stats.items()}
+
+    def _c_bn(self):
+        from . import _lib
+        mv = _lib.BnMoving()
+        for i, _ in bn_layers(self.spec):
+            mv.mean[i] = self.bn_stats["u%d/bn/moving_mean" % i].data_ptr()
+            mv.var[i] = self.bn_stats["u%d/bn/moving_variance" % i].data_ptr()
+        mv.decay = float(self.bn_decay)
+        return mv
+
+    @staticmethod
+    def _bn_mode(bn, bn_updates):
+        from . import _lib
+        if bn not in _lib.BN_MODE:
+            raise ValueError("bn must be 'batch' or 'moving', got %r" % (bn,))
+        if int(bn_updates) < 0 or (bn == "moving" and bn_updates):
+            raise ValueError("bn_updates must be >= 0, and 0 in moving mode (got %r with bn=%r)" % (bn_updates, bn))
+        return _lib.BN_MODE[bn]
+
+
+class FCModel(_BnMovingStats):
     solve_entry = "icnn_be_solve_fc"
     """Device-resident y-path of one FC-PICNN: the packed 'z{i}_yu/W' / 'z{i}_zu_proj/W'
     weights (MFMA B-fragment order, both orientations) plus the C descriptor the
@@ -250,6 +321,7 @@ class FCModel:
         self.wpack = None
         self._ctx_keep = None
         self.c_ctx = None
+        self._init_bn_stats()
         self.repack(params)                     # y-path pack + x-only stage weights
 
     def repack_context(self, params):
@@ -297,16 +369,28 @@ class FCModel:
         # the x-only stage weights follow the same parameter set
         self.repack_context(params)
 
-    def context(self, x: torch.Tensor) -> torch.Tensor:
+    def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
         """x-only context rows [B, ctx_width] of the minibatch x [B, n_features] by the HIP kernels of be_context.hip
-        (one MFMA GEMM per stage with routed epilogue, batch-statistics BatchNorm in place); current stream."""
+        (one MFMA GEMM per stage with routed epilogue, batch-statistics BatchNorm in place); current stream.
+        bn="moving": inference mode, BatchNorm with self.bn_stats (valid at batch 1); bn="batch" with bn_updates = k > 0:
+        the same context, and the batch statistics folded k times into self.bn_stats (icnn_be_fc_context_bn)."""
         import ctypes as C
 
         from . import _lib
+        mode = self._bn_mode(bn, bn_updates)
         x = x.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         assert x.shape[1] == self.spec.n_features
         ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device)
+        if mode != _lib.BN_MODE["batch"] or bn_updates:
+            work = torch.empty(max(int(self._lib.icnn_be_fc_context_bn_work_floats(C.byref(self.c_ctx), B)), 1),
+                               dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mv = self._c_bn()
+            _lib.check(self._lib.icnn_be_fc_context_bn(C.byref(self.c_ctx), C.byref(mv), mode, int(bn_updates), x.data_ptr(), B,
+                                                       ctx.data_ptr(), self.spec.ctx_width, work.data_ptr(),
+                                                       C.c_void_p(stream)), "icnn_be_fc_context_bn")
+            return ctx
         work = torch.empty(max(int(self._lib.icnn_be_fc_context_work_floats(C.byref(self.c_ctx), B)), 1),
                            dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -483,9 +567,10 @@ def init_conv_params(spec: ConvSpec, seed=0, regime="init"):
     return p
 
 
-def conv_context(spec: ConvSpec, params, x: torch.Tensor) -> torch.Tensor:
+def conv_context(spec: ConvSpec, params, x: torch.Tensor, bn_stats=None) -> torch.Tensor:
     """x-only context [B, ctx_width] float32 on x's device (x: [B, H, W, 1], already h-flipped by the
-    caller as completion/icnn_ebundle.py:215 does).  Plain torch ops: plumbing, not the hot path."""
+    caller as completion/icnn_ebundle.py:215 does).  Plain torch ops: plumbing, not the hot path.  BatchNorm in training
+    mode (batch statistics over samples x positions), or with `bn_stats` (init_bn_stats' keys) in inference mode."""
     import torch.nn.functional as F
     dev = x.device
     t = {k: torch.as_tensor(v, device=dev) for k, v in params.items()}
@@ -495,7 +580,9 @@ def conv_context(spec: ConvSpec, params, x: torch.Tensor) -> torch.Tensor:
         out = F.conv2d(inp.permute(0, 3, 1, 2), W.permute(3, 2, 0, 1), b, stride=stride, padding=pad_of[W.shape[0]])
         return out.permute(0, 2, 3, 1)
 
-    def bn(v, g, b, dims):
+    def bn(v, g, b, dims, i):
+        if bn_stats is not None:
+            return _moving_bn(v, t, bn_stats, i)
         mean = v.mean(dim=dims, keepdim=True)
         var = ((v - mean) ** 2).mean(dim=dims, keepdim=True)
         return (v - mean) / torch.sqrt(var + 1e-5) * g + b
@@ -504,11 +591,11 @@ def conv_context(spec: ConvSpec, params, x: torch.Tensor) -> torch.Tensor:
     us, prev = [], x
     for l, (nf, k, s) in enumerate(CONV_LAYERS):
         u = bn(torch.relu(conv(prev, t["u%d/W" % l], t["u%d/b" % l], s)), t["u%d/bn/gamma" % l],
-               t["u%d/bn/beta" % l], (0, 1, 2))
+               t["u%d/bn/beta" % l], (0, 1, 2), l)
         us.append(u)
         prev = u
     flat = prev.reshape(prev.shape[0], -1)
-    u3 = bn(torch.relu(flat @ t["u3/W"] + t["u3/b"]), t["u3/bn/gamma"], t["u3/bn/beta"], (0,))
+    u3 = bn(torch.relu(flat @ t["u3/W"] + t["u3/b"]), t["u3/bn/gamma"], t["u3/bn/beta"], (0,), 3)
     us.append(u3)
     B = x.shape[0]
     parts, prevU = [], x
@@ -553,7 +640,7 @@ def stage_conv_weights(params):
             for ws, bs in CONV_CTX_STAGES]
 
 
-class ConvModel:
+class ConvModel(_BnMovingStats):
     """Device-resident y-path of the conv PICNN (struct icnn_be_conv_model + packed weights)."""
     solve_entry = "icnn_be_solve_conv"
 
@@ -576,6 +663,7 @@ class ConvModel:
         if self.n_pack_floats == 0:
             raise ValueError("conv model shape rejected by libicnn_be")
         self.work = None
+        self._init_bn_stats()
         self.repack(params)
 
     def reserve(self, batch):
@@ -638,19 +726,30 @@ class ConvModel:
             c.bn_gamma[i], c.bn_beta[i] = gd.data_ptr(), bd.data_ptr()
         self.c_ctx = c
 
-    def context(self, x: torch.Tensor) -> torch.Tensor:
+    def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
         """x-only context [B, ctx_width] of x [B, H, W, 1] (already h-flipped by the caller as
         completion/icnn_ebundle.py:215 does), on the device: be_context.hip through `icnn_be_conv_context`
-        (`conv_context` above is the torch restatement the tests compare it with)."""
+        (`conv_context` above is the torch restatement the tests compare it with).  bn / bn_updates as FCModel.context:
+        bn="moving" is the inference mode of the completion test phase (icnn_be_conv_context_bn)."""
         import ctypes as C
 
         from . import _lib
+        mode = self._bn_mode(bn, bn_updates)
         x = x.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         assert tuple(x.shape[1:]) == (self.spec.H, self.spec.W, 1)
         if getattr(self, "c_ctx", None) is None:
             self.repack_context(self.params)
         ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device)
+        if mode != _lib.BN_MODE["batch"] or bn_updates:
+            n = int(self._lib.icnn_be_conv_context_bn_work_floats(C.byref(self.c_model), B))
+            work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mv = self._c_bn()
+            _lib.check(self._lib.icnn_be_conv_context_bn(C.byref(self.c_model), C.byref(self.c_ctx), C.byref(mv), mode,
+                                                         int(bn_updates), x.data_ptr(), B, ctx.data_ptr(), work.data_ptr(),
+                                                         C.c_void_p(stream)), "icnn_be_conv_context_bn")
+            return ctx
         n = int(self._lib.icnn_be_conv_context_work_floats(C.byref(self.c_model), B))
         work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream

@@ -85,7 +85,7 @@ def grad_floats(model) -> int:
     return int(model._lib.icnn_be_fc_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
 
 
-def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None) -> Dict[str, torch.Tensor]:
+def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0) -> Dict[str, torch.Tensor]:
     """Gradient of sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ] over every trainable variable of `model`,
     keyed like picnn.init_params(spec) -- for a ConvModel like picnn.init_conv_params(spec), x [B, H, W, 1] already
     h-flipped (completion/icnn_ebundle.py:215).
@@ -93,8 +93,9 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     feed_or_rows: an ImplicitFeed (bundle_entropy.implicit_feed: rows grouped by sample, in sample order), or (y, c) --
     the RL critic, one row per sample and no v -- or (y, v, c) with `row_offset` (int32 [B+1]: rows of sample j are
     row_offset[j] .. row_offset[j+1]-1).  BatchNorm runs over the feed rows, each sample counted once per row, as the
-    reference's x_ = fd_xs.  F_rows: optional float32 [R] tensor that receives F_r.  Enqueued on the current stream
-    without any host synchronisation (capturable in a CUDA graph)."""
+    reference's x_ = fd_xs.  F_rows: optional float32 [R] tensor that receives F_r.  bn_updates = k > 0 also folds those
+    BatchNorm statistics k times into model.bn_stats (1: what the reference's train_step does); the gradient is the same.
+    Enqueued on the current stream without any host synchronisation (capturable in a CUDA graph)."""
     spec, dev = model.spec, model.device
     conv = isinstance(model, ConvModel)
     x = x.to(dev, torch.float32).contiguous()
@@ -131,6 +132,9 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     row_offset = torch.as_tensor(row_offset).to(dev, torch.int32).contiguous()
     if row_offset.shape != (B + 1,):
         raise ValueError("row_offset has shape %s, the batch needs (%d,)" % (tuple(row_offset.shape), B + 1))
+    bn_updates = int(bn_updates)
+    if bn_updates < 0:
+        raise ValueError("bn_updates must be >= 0, got %d" % bn_updates)
     entry = "icnn_be_conv_surrogate_grad" if conv else "icnn_be_fc_surrogate_grad"
     grad = torch.empty(grad_floats(model), dtype=torch.float32, device=dev)
     if R == 0:
@@ -142,10 +146,11 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     if F_rows is not None:
         assert F_rows.dtype == torch.float32 and F_rows.shape == (R,) and F_rows.is_contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(getattr(model._lib, entry)(
+    mv = model._c_bn()
+    _lib.check(getattr(model._lib, entry + "_bn")(
         C.byref(model.c_model), C.byref(model.c_ctx), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
         None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
-        None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.c_void_p(stream)), entry)
+        None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates, C.c_void_p(stream)), entry)
     return unpack_grad(spec, grad)
 
 

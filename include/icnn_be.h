@@ -217,7 +217,7 @@ ICNN_BE_API int icnn_be_abi_version(void);
 ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
- * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4: lets a
+ * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5: lets a
  * foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
@@ -387,6 +387,47 @@ ICNN_BE_API int icnn_be_conv_context(const icnn_be_conv_model *shape, const icnn
  * on the 'z{1..4}_zu_proj/W' operands inside model->wpack (every packed orientation), in place on the device. */
 ICNN_BE_API int icnn_be_conv_clamp(const icnn_be_conv_model *model, int mode, void *stream);
 
+/* ---- BatchNorm moving statistics: inference mode and the folds of training mode (additive to ABI 12) ---- */
+
+/*
+ * tflearn.batch_normalization keeps, per batch-normalised u-layer, a moving mean (initialised to 0) and a moving variance
+ * (initialised to 1).  In inference mode (tflearn.is_training(False): the completion test phase,
+ * completion/icnn_ebundle.py:264-292; the RL agent's act() and target solve, RL/src/icnn.py:277,:316) the layer normalises
+ * with them:  u <- (u - mean) gamma / sqrt(var + bn_eps) + beta.  In training mode every evaluation of the op folds the
+ * batch mean mu and the biased batch variance sigma^2 it normalised with into them (assign_moving_average without
+ * zero-debias, float32, d = 1 - decay):  mean <- mean - (mean - mu) d,  var <- var - (var - sigma^2) d.
+ * mean[i] / var[i] are device float32 vectors, one pair per batch-normalised layer: FC u_i for i < n_layers-2 (width[i]
+ * floats, NULL elsewhere); conv u0..u2 (filters[l], per channel) and u3 (fc_hidden, per column), indices 0..3.
+ */
+#define ICNN_BE_BN_BATCH 0     /* normalise with the statistics of the batch (training mode); `updates` folds them */
+#define ICNN_BE_BN_MOVING 1    /* normalise with mv (inference mode); nothing is written to mv, valid at batch 1 */
+typedef struct icnn_be_bn_moving {
+    float *mean[ICNN_BE_MAX_LAYERS];
+    float *var[ICNN_BE_MAX_LAYERS];
+    float decay;               /* tflearn's default 0.9; in [0, 1] */
+} icnn_be_bn_moving;
+
+/* floats of device scratch the *_context_bn entries need (the *_context_work_floats plus the exported batch statistics) */
+ICNN_BE_API size_t icnn_be_fc_context_bn_work_floats(const icnn_be_fc_ctx *c, int batch);
+ICNN_BE_API size_t icnn_be_conv_context_bn_work_floats(const icnn_be_conv_model *shape, int batch);
+
+/*
+ * icnn_be_fc_context / icnn_be_conv_context with the BatchNorm mode chosen:
+ *   mode ICNN_BE_BN_BATCH,  updates = 0   the plain call (the same bits; mv is not read)
+ *   mode ICNN_BE_BN_BATCH,  updates > 0   the same context, and the batch statistics folded `updates` times into mv (the
+ *                                         number of times the reference evaluates the op on this batch)
+ *   mode ICNN_BE_BN_MOVING, updates = 0   inference mode: normalise with mv, read only.  Every row is independent of the
+ *                                         others (the same bits at any batch size)
+ * ICNN_BE_EINVAL before anything is launched for an unknown mode, updates < 0, updates > 0 with ICNN_BE_BN_MOVING, and --
+ * when mv is needed (a BatchNorm model with ICNN_BE_BN_MOVING or updates > 0) -- mv == NULL, a NULL vector of a
+ * batch-normalised layer or a decay outside [0, 1].  A model without BatchNorm ignores mv.  `work` holds
+ * icnn_be_fc_context_bn_work_floats / icnn_be_conv_context_bn_work_floats floats.  No host synchronisation, no atomics.
+ */
+ICNN_BE_API int icnn_be_fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode, int updates, const float *x,
+                                      int batch, float *ctx, int ctx_width, float *work, void *stream);
+ICNN_BE_API int icnn_be_conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv,
+                                        int mode, int updates, const float *x, int batch, float *ctx, float *work, void *stream);
+
 /* ---- implicit-differentiation feed of a training step ----------------- */
 #define ICNN_BE_LOSS_XENT 0   /* crossEntrGrad, multi-label-cls/icnn_ebundle.py:390-417 */
 #define ICNN_BE_LOSS_MSE 1    /* mseGrad,       completion/icnn_ebundle.py:493-522     */
@@ -492,6 +533,22 @@ ICNN_BE_API size_t icnn_be_conv_surrogate_grad_work_floats(const icnn_be_conv_mo
 ICNN_BE_API int icnn_be_conv_surrogate_grad(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
                                             const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                             float *grad, float *F_rows, float *work, void *stream);
+
+/*
+ * icnn_be_fc_surrogate_grad / icnn_be_conv_surrogate_grad (mv = NULL, updates = 0) that also fold the BatchNorm statistics
+ * of the feed rows -- the multiplicity-weighted statistics the training-mode normalisation used, BatchNorm over the R
+ * gathered rows -- `updates` times into mv (icnn_be_bn_moving; 1 for the reference's train_step).  grad and F_rows are the
+ * same bits as without the fold.  ICNN_BE_EINVAL for updates < 0 and, on a BatchNorm model with updates > 0, for
+ * mv == NULL, a NULL vector or a decay outside [0, 1].  The work sizes are the *_surrogate_grad_work_floats.
+ */
+ICNN_BE_API int icnn_be_fc_surrogate_grad_bn(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                                             const int *row_offset, int rows, const double *y, const double *v,
+                                             const double *cvec, float *grad, float *F_rows, float *work,
+                                             const icnn_be_bn_moving *mv, int updates, void *stream);
+ICNN_BE_API int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x,
+                                               int batch, const int *row_offset, int rows, const double *y, const double *v,
+                                               const double *cvec, float *grad, float *F_rows, float *work,
+                                               const icnn_be_bn_moving *mv, int updates, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
