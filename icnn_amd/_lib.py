@@ -53,10 +53,11 @@ EXPORTS = [
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
-    "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn",
+    "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn", "icnn_be_param_update",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
+MAX_PROJ_RANGES = 8
 
 
 class State(C.Structure):
@@ -112,6 +113,16 @@ class ConvCtx(C.Structure):
 class BnMoving(C.Structure):
     """struct icnn_be_bn_moving"""
     _fields_ = [("mean", C.c_void_p * MAX_LAYERS), ("var", C.c_void_p * MAX_LAYERS), ("decay", C.c_float)]
+
+
+class ParamUpdateArgs(C.Structure):
+    """struct icnn_be_param_update_args"""
+    _fields_ = [
+        ("n", C.c_longlong), ("theta", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p),
+        ("dest_off", C.c_void_p), ("dest", C.c_void_p), ("arena", C.c_void_p), ("arena_floats", C.c_longlong),
+        ("step", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float),
+        ("n_proj", C.c_int), ("proj_begin", C.c_longlong * MAX_PROJ_RANGES), ("proj_end", C.c_longlong * MAX_PROJ_RANGES),
+    ]
 
 
 _lib = None
@@ -240,10 +251,13 @@ def load():
     lib.icnn_be_conv_surrogate_grad_bn.argtypes = (lib.icnn_be_conv_surrogate_grad.argtypes[:-1]
                                                    + [C.POINTER(BnMoving), C.c_int, C.c_void_p])
     lib.icnn_be_conv_surrogate_grad_bn.restype = C.c_int
+    lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
+    lib.icnn_be_param_update.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
-    if tuple(lib.icnn_be_struct_size(i) for i in range(6)) != (
-            C.sizeof(State), C.sizeof(FcModel), C.sizeof(FcCtx), C.sizeof(ConvModel), C.sizeof(ConvCtx), C.sizeof(BnMoving)):
+    if tuple(lib.icnn_be_struct_size(i) for i in range(7)) != (
+            C.sizeof(State), C.sizeof(FcModel), C.sizeof(FcCtx), C.sizeof(ConvModel), C.sizeof(ConvCtx), C.sizeof(BnMoving),
+            C.sizeof(ParamUpdateArgs)):
         raise ImportError("ctypes struct layout differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"

@@ -1,6 +1,7 @@
 // C ABI of libicnn_be.so (see include/icnn_be.h for the contract and the reference lines
 // each entry point replaces).  Everything here only validates arguments and enqueues work.
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <cstdlib>
 
 #include <map>
@@ -196,7 +197,8 @@ const char *icnn_be_last_hip_error(void) { return hipGetErrorString(g_last); }
 size_t icnn_be_struct_size(int which) {
     return which == 0 ? sizeof(icnn_be_state) : which == 1 ? sizeof(icnn_be_fc_model)
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
-         : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving) : 0;
+         : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving)
+         : which == 6 ? sizeof(icnn_be_param_update_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -592,6 +594,23 @@ int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const 
         return icnn_be::launch_conv_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
     });
     return e == hipSuccess ? total : fail(e);
+}
+
+int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {
+    if (!a || a->n < 1 || !a->theta || !a->m || !a->v || !a->grad || !a->dest_off || !a->dest || !a->arena || !a->step)
+        return ICNN_BE_EINVAL;
+    if (a->arena_floats < 0 || a->arena_floats > 0x7fffffffLL || icnn_be::param_update_blocks(a->n) > 0x7fffffffLL)
+        return ICNN_BE_EINVAL;
+    const void *aligned[] = {a->theta, a->m, a->v, a->grad, a->dest_off};
+    for (const void *p : aligned)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return ICNN_BE_EINVAL;
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f && a->lr == a->lr))
+        return ICNN_BE_EINVAL;
+    if (a->n_proj < 0 || a->n_proj > ICNN_BE_MAX_PROJ_RANGES) return ICNN_BE_EINVAL;
+    for (int r = 0; r < a->n_proj; ++r)
+        if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_param_update(*a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
 }
 
 }  // extern "C"

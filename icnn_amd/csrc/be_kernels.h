@@ -200,4 +200,8 @@ int conv_pack(const icnn_be_conv_model &m, const float *const *w_yu, const float
 hipError_t launch_conv_fg(const icnn_be_conv_model &m, const float *ctx, const double *y, int batch, float *f,
                           float *g, const int *skip, hipStream_t stream);
 
+// ---- parameter update (be_train_update.hip) -----------------------------------------
+long long param_update_blocks(long long n);
+hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream);
+
 }  // namespace icnn_be

@@ -1,0 +1,123 @@
+// Parameter update of a PICNN on the device: tf.train.AdamOptimizer's step over the flat theta, the reference's proj clamp
+// and the scatter of every new weight into each copy the kernels read (the weight arena), in one launch
+// (include/icnn_be.h, icnn_be_param_update).
+//
+// One thread per four consecutive parameters: 16-byte loads and stores on the theta / m / v / grad streams, four CSR
+// offsets of the map with one more 16-byte load, then the scattered stores of the copies.  The arithmetic of one element,
+// float32, correctly rounded at every operation, no contraction (the NumPy restatement of tests/test_device_update.py
+// reproduces it bit for bit; sqrt as the float of the double root, which is the correctly rounded float root):
+//   m = b1 * m + c1 * g                 b1 = (float)beta1, c1 = (float)(1 - beta1)
+//   v = b2 * v + c2 * (g * g)           b2 = (float)beta2, c2 = (float)(1 - beta2)
+//   theta = theta - (lr_t * m) / (sqrt(v) + eps)
+//   theta = 0 if theta < 0 and the element is a proj weight (np.maximum(theta, 0): -0 and NaN stay)
+// lr_t = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t)) in double from the step count t, as train.TFAdam computes it.
+#include "be_kernels.h"
+
+namespace icnn_be {
+
+namespace {
+
+constexpr int UPD_THREADS = 256;
+constexpr int UPD_PER_THREAD = 4;
+
+struct UpdArgs {
+    icnn_be_param_update_args a;
+    float b1, c1, b2, c2;
+};
+
+__device__ __forceinline__ bool in_proj(const icnn_be_param_update_args &a, long long j) {
+    bool p = false;
+    for (int r = 0; r < a.n_proj; ++r) p |= j >= a.proj_begin[r] && j < a.proj_end[r];
+    return p;
+}
+
+__global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
+#pragma clang fp contract(off)
+    const icnn_be_param_update_args &a = u.a;
+    __shared__ float s_lr_t;
+    __shared__ int s_t;
+    if (threadIdx.x == 0) {
+        // updates done so far; the last workgroup of this launch writes t back only after every workgroup has taken its
+        // ticket, and every workgroup reads the count before it takes one
+        const int t = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+        s_t = t;
+        s_lr_t = (float)(a.lr * sqrt(1.0 - pow(a.beta2, (double)t)) / (1.0 - pow(a.beta1, (double)t)));
+    }
+    __syncthreads();
+    const float lr_t = s_lr_t, eps = a.eps;
+    const long long j0 = ((long long)blockIdx.x * UPD_THREADS + threadIdx.x) * UPD_PER_THREAD;
+    if (j0 < a.n) {
+        const int cnt = a.n - j0 < UPD_PER_THREAD ? (int)(a.n - j0) : UPD_PER_THREAD;
+        float th[UPD_PER_THREAD] = {}, m[UPD_PER_THREAD] = {}, v[UPD_PER_THREAD] = {}, g[UPD_PER_THREAD] = {};
+        int off[UPD_PER_THREAD + 1] = {};
+        if (cnt == UPD_PER_THREAD) {
+            const float4 t4 = *reinterpret_cast<const float4 *>(a.theta + j0);
+            const float4 m4 = *reinterpret_cast<const float4 *>(a.m + j0);
+            const float4 v4 = *reinterpret_cast<const float4 *>(a.v + j0);
+            const float4 g4 = *reinterpret_cast<const float4 *>(a.grad + j0);
+            const int4 o4 = *reinterpret_cast<const int4 *>(a.dest_off + j0);
+            th[0] = t4.x; th[1] = t4.y; th[2] = t4.z; th[3] = t4.w;
+            m[0] = m4.x; m[1] = m4.y; m[2] = m4.z; m[3] = m4.w;
+            v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
+            g[0] = g4.x; g[1] = g4.y; g[2] = g4.z; g[3] = g4.w;
+            off[0] = o4.x; off[1] = o4.y; off[2] = o4.z; off[3] = o4.w;
+        } else {
+            for (int k = 0; k < cnt; ++k) {
+                th[k] = a.theta[j0 + k]; m[k] = a.m[j0 + k]; v[k] = a.v[j0 + k]; g[k] = a.grad[j0 + k];
+                off[k] = a.dest_off[j0 + k];
+            }
+        }
+        off[cnt] = a.dest_off[j0 + cnt];
+#pragma unroll
+        for (int k = 0; k < UPD_PER_THREAD; ++k) {
+            // plain operators under the pragma above: the __f*_rn helpers are header functions outside its scope, and
+            // the compiler fused their products into the sums.  sqrt: the float of the double root (correctly rounded
+            // both times, and 53 >= 2 * 24 + 2 bits make the double rounding innocuous); v_sqrt_f32 alone is 1 ulp
+            m[k] = u.b1 * m[k] + u.c1 * g[k];
+            v[k] = u.b2 * v[k] + u.c2 * (g[k] * g[k]);
+            const float root = (float)__builtin_sqrt((double)v[k]);
+            th[k] = th[k] - (lr_t * m[k]) / (root + eps);
+            if (th[k] < 0.f && in_proj(a, j0 + k)) th[k] = 0.f;
+        }
+        if (cnt == UPD_PER_THREAD) {
+            *reinterpret_cast<float4 *>(a.theta + j0) = make_float4(th[0], th[1], th[2], th[3]);
+            *reinterpret_cast<float4 *>(a.m + j0) = make_float4(m[0], m[1], m[2], m[3]);
+            *reinterpret_cast<float4 *>(a.v + j0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            for (int k = 0; k < cnt; ++k) { a.theta[j0 + k] = th[k]; a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k]; }
+        }
+        for (int k = 0; k < cnt; ++k)
+            for (int d = off[k]; d < off[k + 1]; ++d) {
+                const int at = a.dest[d];
+                if (at >= 0 && at < a.arena_floats) a.arena[at] = th[k];
+            }
+    }
+    // the step count: the last workgroup to arrive stores t and re-arms the ticket for the next launch
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int ticket = __hip_atomic_fetch_add(a.step + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == (int)gridDim.x - 1) {
+            __hip_atomic_store(a.step, s_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.step + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+}  // namespace
+
+long long param_update_blocks(long long n) {
+    const long long per_block = (long long)UPD_THREADS * UPD_PER_THREAD;
+    return (n + per_block - 1) / per_block;
+}
+
+hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream) {
+    UpdArgs u{};
+    u.a = a;
+    u.b1 = (float)a.beta1;
+    u.c1 = (float)(1.0 - a.beta1);
+    u.b2 = (float)a.beta2;
+    u.c2 = (float)(1.0 - a.beta2);
+    return launch_kernel(param_update_kernel, dim3((unsigned)param_update_blocks(a.n)), dim3(UPD_THREADS), 0, stream, u);
+}
+
+}  // namespace icnn_be

@@ -290,7 +290,35 @@ class _BnMovingStats:
         return _lib.BN_MODE[bn]
 
 
-class FCModel(_BnMovingStats):
+class _DeviceWeights:
+    """The weight arena hooks of a device model (train.DeviceAdam).  arena_parts(params) lists every buffer the kernels
+    read -- ("wpack", 0, packed y-path), then ("w_stage" | "b_stage" | "bn_gamma" | "bn_beta", index, array) in the order
+    repack_context uploads them -- as host float32 arrays built by the host packers.  Once a DeviceAdam owns the weights,
+    c_model.wpack and every c_ctx pointer point into its arena for good, `params` are live device views of its theta, and
+    repack / repack_context / clamp raise instead of letting the packed copies drift from theta."""
+    _optimizer = None
+
+    def _refuse_if_attached(self, what):
+        if self._optimizer is not None:
+            raise RuntimeError("%s: the weights of this model belong to a train.DeviceAdam; use its load(params)" % what)
+
+    def arena_parts(self, params):
+        return [("wpack", 0, self._pack_host(params))] + self._ctx_host(params)
+
+    def _use_arena(self, optimizer, arena, parts, offsets):
+        c = self._ctx_struct()
+        for (field, i, a), off in zip(parts, offsets):
+            if field == "wpack":
+                self.wpack = arena[off:off + a.size]
+                self.c_model.wpack = self.wpack.data_ptr()
+            else:
+                getattr(c, field)[i] = arena.data_ptr() + 4 * off
+        self._ctx_keep, self.c_ctx = [arena], c
+        self._optimizer = optimizer
+        self.params = optimizer.params()
+
+
+class FCModel(_BnMovingStats, _DeviceWeights):
     solve_entry = "icnn_be_solve_fc"
     """Device-resident y-path of one FC-PICNN: the packed 'z{i}_yu/W' / 'z{i}_zu_proj/W'
     weights (MFMA B-fragment order, both orientations) plus the C descriptor the
@@ -324,29 +352,47 @@ class FCModel(_BnMovingStats):
         self._init_bn_stats()
         self.repack(params)                     # y-path pack + x-only stage weights
 
-    def repack_context(self, params):
-        """Upload the x-only weights (stage concatenations, BN parameters) for icnn_be_fc_context."""
+    def _ctx_struct(self):
         from . import _lib
-        spec, dev = self.spec, self.device
+        spec = self.spec
         c = _lib.FcCtx()
         c.n_features, c.n, c.n_layers = spec.n_features, spec.n_labels, spec.n_layers
         for i, w in enumerate(spec.widths):
             c.width[i] = w
         c.batchnorm = int(spec.batchnorm)
         c.bn_eps = 1e-5
-        keep = []
+        return c
+
+    def _ctx_host(self, params):
+        spec, out = self.spec, []
         for i, (W, b) in enumerate(stage_weights(spec, params)):
-            Wd, bd = torch.from_numpy(W).to(dev), torch.from_numpy(b).to(dev)
-            keep += [Wd, bd]
-            c.w_stage[i], c.b_stage[i] = Wd.data_ptr(), bd.data_ptr()
+            out += [("w_stage", i, W), ("b_stage", i, b)]
             if spec.batchnorm and i < len(spec.szs) - 1:
-                ga = torch.from_numpy(np.ascontiguousarray(params["u%d/bn/gamma" % i], dtype=np.float32)).to(dev)
-                be = torch.from_numpy(np.ascontiguousarray(params["u%d/bn/beta" % i], dtype=np.float32)).to(dev)
-                keep += [ga, be]
-                c.bn_gamma[i], c.bn_beta[i] = ga.data_ptr(), be.data_ptr()
+                out += [("bn_gamma", i, np.ascontiguousarray(params["u%d/bn/gamma" % i], dtype=np.float32)),
+                        ("bn_beta", i, np.ascontiguousarray(params["u%d/bn/beta" % i], dtype=np.float32))]
+        return out
+
+    def repack_context(self, params):
+        """Upload the x-only weights (stage concatenations, BN parameters) for icnn_be_fc_context."""
+        self._refuse_if_attached("repack_context")
+        c, keep = self._ctx_struct(), []
+        for field, i, a in self._ctx_host(params):
+            t = torch.from_numpy(a).to(self.device)
+            keep.append(t)
+            getattr(c, field)[i] = t.data_ptr()
         self._ctx_keep, self.c_ctx = keep, c
 
     def repack(self, params):
+        self._refuse_if_attached("repack")
+        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
+        self.c_model.wpack = self.wpack.data_ptr()
+        self.params = params
+        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
+        # the x-only stage weights follow the same parameter set
+        self.repack_context(params)
+
+    def _pack_host(self, params):
+        """icnn_be_fc_pack of params' y-path weights: the host image of wpack"""
         import ctypes as C
         L1 = self.spec.n_layers
         keep = []
@@ -362,12 +408,7 @@ class FCModel(_BnMovingStats):
         from . import _lib
         _lib.check(self._lib.icnn_be_fc_pack(C.byref(self.c_model), yu, zu, host.ctypes.data),
                    "icnn_be_fc_pack")
-        self.wpack = torch.from_numpy(host).to(self.device)
-        self.c_model.wpack = self.wpack.data_ptr()
-        self.params = params
-        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
-        # the x-only stage weights follow the same parameter set
-        self.repack_context(params)
+        return host
 
     def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
         """x-only context rows [B, ctx_width] of the minibatch x [B, n_features] by the HIP kernels of be_context.hip
@@ -448,6 +489,7 @@ class FCModel(_BnMovingStats):
         import ctypes as C
 
         from . import _lib
+        self._refuse_if_attached("clamp")
         code = {"makeCvx": _lib.CLAMP_ABS, "proj": _lib.CLAMP_RELU}[mode]
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._lib.icnn_be_fc_clamp(C.byref(self.c_model), code, C.c_void_p(stream)), "icnn_be_fc_clamp")
@@ -640,7 +682,7 @@ def stage_conv_weights(params):
             for ws, bs in CONV_CTX_STAGES]
 
 
-class ConvModel(_BnMovingStats):
+class ConvModel(_BnMovingStats, _DeviceWeights):
     """Device-resident y-path of the conv PICNN (struct icnn_be_conv_model + packed weights)."""
     solve_entry = "icnn_be_solve_conv"
 
@@ -681,6 +723,16 @@ class ConvModel(_BnMovingStats):
         self.c_model.work, self.c_model.work_batch = self.work.data_ptr(), batch
 
     def repack(self, params):
+        self._refuse_if_attached("repack")
+        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
+        self.c_model.wpack = self.wpack.data_ptr()
+        self.params = params
+        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
+        # the x-only stage weights follow the same parameter set
+        self.repack_context(params)
+
+    def _pack_host(self, params):
+        """icnn_be_conv_pack of params' y-path weights: the host image of wpack"""
         import ctypes as C
 
         from . import _lib
@@ -698,33 +750,35 @@ class ConvModel(_BnMovingStats):
         host = np.empty(self.n_pack_floats, dtype=np.float32)
         _lib.check(self._lib.icnn_be_conv_pack(C.byref(self.c_model), w_yu, w_yr, b_yr, w_zu, ptr("z3_zu_proj/W"),
                                                ptr("z4_zu_proj/W"), host.ctypes.data), "icnn_be_conv_pack")
-        self.wpack = torch.from_numpy(host).to(self.device)
-        self.c_model.wpack = self.wpack.data_ptr()
-        self.params = params
-        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
-        # the x-only stage weights follow the same parameter set
-        self.repack_context(params)
+        return host
 
-    def repack_context(self, params):
-        """Upload the stage operands of the x-only context producer (struct icnn_be_conv_ctx, include/icnn_be.h)."""
+    def _ctx_struct(self):
         from . import _lib
-        stages = stage_conv_weights(params)
         c = _lib.ConvCtx()
         c.bn_eps = 1e-5
-        self._ctx_keep = []
-        for s, (w, b) in enumerate(stages):
+        return c
+
+    def _ctx_host(self, params):
+        out = []
+        for s, (w, b) in enumerate(stage_conv_weights(params)):
             ld = (w.shape[1] + 3) & ~3
             wp = np.zeros((w.shape[0], ld), np.float32)
             wp[:, :w.shape[1]] = w
-            wd, bd = torch.from_numpy(wp).to(self.device), torch.from_numpy(b).to(self.device)
-            self._ctx_keep += [wd, bd]
-            c.w_stage[s], c.b_stage[s] = wd.data_ptr(), bd.data_ptr()
+            out += [("w_stage", s, wp), ("b_stage", s, b)]
         for i in range(4):
-            gd = torch.from_numpy(np.asarray(params["u%d/bn/gamma" % i], np.float32)).to(self.device)
-            bd = torch.from_numpy(np.asarray(params["u%d/bn/beta" % i], np.float32)).to(self.device)
-            self._ctx_keep += [gd, bd]
-            c.bn_gamma[i], c.bn_beta[i] = gd.data_ptr(), bd.data_ptr()
-        self.c_ctx = c
+            out += [("bn_gamma", i, np.ascontiguousarray(params["u%d/bn/gamma" % i], np.float32)),
+                    ("bn_beta", i, np.ascontiguousarray(params["u%d/bn/beta" % i], np.float32))]
+        return out
+
+    def repack_context(self, params):
+        """Upload the stage operands of the x-only context producer (struct icnn_be_conv_ctx, include/icnn_be.h)."""
+        self._refuse_if_attached("repack_context")
+        c, keep = self._ctx_struct(), []
+        for field, i, a in self._ctx_host(params):
+            t = torch.from_numpy(a).to(self.device)
+            keep.append(t)
+            getattr(c, field)[i] = t.data_ptr()
+        self._ctx_keep, self.c_ctx = keep, c
 
     def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
         """x-only context [B, ctx_width] of x [B, H, W, 1] (already h-flipped by the caller as
@@ -763,6 +817,7 @@ class ConvModel(_BnMovingStats):
         import ctypes as C
 
         from . import _lib
+        self._refuse_if_attached("clamp")
         code = {"makeCvx": _lib.CLAMP_ABS_HALF, "proj": _lib.CLAMP_RELU}[mode]
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._lib.icnn_be_conv_clamp(C.byref(self.c_model), code, C.c_void_p(stream)), "icnn_be_conv_clamp")

@@ -6,8 +6,13 @@
                     conv PICNN of the completion experiment (completion/icnn_ebundle.py:129-140) be_train_conv.hip
                     through icnn_be_conv_surrogate_grad.
     TFAdam          tf.train.AdamOptimizer's update rule on device tensors (torch plumbing, not a kernel).
+    DeviceAdam      the same update, the reference's proj and the repack of every copy the kernels read, in one launch of
+                    be_train_update.hip (icnn_be_param_update) over a flat theta; the model's packed weights live in one
+                    device buffer (the arena) that the update writes in place.
 
 One training step of the multi-label experiment:
+    solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
+or, for a caller that updates the weights itself,
     solve -> bundle_entropy.implicit_feed -> surrogate_grad -> TFAdam.step -> picnn.project -> model.repack
 and of the completion experiment the same with ConvModel.context, a conv solve and implicit_feed(..., "mse").
 """
@@ -85,7 +90,7 @@ def grad_floats(model) -> int:
     return int(model._lib.icnn_be_fc_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
 
 
-def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0) -> Dict[str, torch.Tensor]:
+def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0, flat=False):
     """Gradient of sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ] over every trainable variable of `model`,
     keyed like picnn.init_params(spec) -- for a ConvModel like picnn.init_conv_params(spec), x [B, H, W, 1] already
     h-flipped (completion/icnn_ebundle.py:215).
@@ -95,7 +100,8 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     row_offset[j] .. row_offset[j+1]-1).  BatchNorm runs over the feed rows, each sample counted once per row, as the
     reference's x_ = fd_xs.  F_rows: optional float32 [R] tensor that receives F_r.  bn_updates = k > 0 also folds those
     BatchNorm statistics k times into model.bn_stats (1: what the reference's train_step does); the gradient is the same.
-    Enqueued on the current stream without any host synchronisation (capturable in a CUDA graph)."""
+    flat=True: the packed float32 [grad_floats] tensor itself (grad_layout order, what DeviceAdam.step takes) instead of the
+    dict of views.  Enqueued on the current stream without any host synchronisation (capturable in a CUDA graph)."""
     spec, dev = model.spec, model.device
     conv = isinstance(model, ConvModel)
     x = x.to(dev, torch.float32).contiguous()
@@ -138,7 +144,7 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     entry = "icnn_be_conv_surrogate_grad" if conv else "icnn_be_fc_surrogate_grad"
     grad = torch.empty(grad_floats(model), dtype=torch.float32, device=dev)
     if R == 0:
-        return unpack_grad(spec, grad.zero_())
+        return grad.zero_() if flat else unpack_grad(spec, grad.zero_())
     n_work = int(getattr(model._lib, entry + "_work_floats")(C.byref(model.c_model), C.byref(model.c_ctx), B, R))
     if n_work == 0:
         raise ValueError("%s: shape rejected (batch %d, rows %d)" % (entry, B, R))
@@ -151,7 +157,7 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
         C.byref(model.c_model), C.byref(model.c_ctx), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
         None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
         None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates, C.c_void_p(stream)), entry)
-    return unpack_grad(spec, grad)
+    return grad if flat else unpack_grad(spec, grad)
 
 
 class TFAdam:
@@ -177,3 +183,179 @@ class TFAdam:
             m.mul_(self.beta1).add_(g, alpha=1.0 - self.beta1)
             v.mul_(self.beta2).addcmul_(g, g, value=1.0 - self.beta2)
             p.sub_(lr_t * m / (v.sqrt() + self.eps))
+
+
+# --------------------------------------------------------------------------------------------- #
+# Device-side update: the weight arena, the map from theta into it, and DeviceAdam
+# --------------------------------------------------------------------------------------------- #
+ARENA_ALIGN = 64            # floats: every sub-buffer of the arena starts on a 256-byte boundary
+INDEX_LIMIT = 1 << 24       # float(j + 1) is exact for j + 1 <= 2^24
+
+
+def index_params(layout) -> Dict[str, np.ndarray]:
+    """The index image of a parameter layout ((name, shape) list, grad_layout order): entry j of the flat theta holds
+    float(j + 1), so that what the host packers make of it says which theta index landed where (0: padding)."""
+    total = sum(int(np.prod(shape)) for _, shape in layout)
+    if total > INDEX_LIMIT:
+        raise ValueError("%d parameters: the index image float(j + 1) is exact only up to 2^24 = %d" % (total, INDEX_LIMIT))
+    idx = np.arange(1, total + 1, dtype=np.int64).astype(np.float32)
+    out, at = {}, 0
+    for name, shape in layout:
+        size = int(np.prod(shape))
+        out[name] = idx[at:at + size].reshape(shape)
+        at += size
+    return out
+
+
+def arena_offsets(parts) -> Tuple[List[int], int]:
+    """Float offset of every part of model.arena_parts in the arena (each 256-byte aligned) and the arena's size."""
+    offs, at = [], 0
+    for _, _, a in parts:
+        offs.append(at)
+        at += -(-a.size // ARENA_ALIGN) * ARENA_ALIGN
+    return offs, at
+
+
+def arena_image(model, params) -> Tuple[np.ndarray, list, List[int]]:
+    """Host image of the arena for `params`: the host packers' output (icnn_be_*_pack, the stage concatenations, gamma /
+    beta) at arena_offsets, zeros elsewhere.  Returns (image, parts, offsets)."""
+    parts = model.arena_parts(params)
+    offs, total = arena_offsets(parts)
+    img = np.zeros(total, np.float32)
+    for (_, _, a), off in zip(parts, offs):
+        img[off:off + a.size] = np.asarray(a, np.float32).reshape(-1)
+    return img, parts, offs
+
+
+class ParamMap:
+    """Where every entry of the flat theta sits in the arena, built once per model shape through the host packers fed
+    the index image: dest[dest_off[j]:dest_off[j + 1]] are the arena float offsets holding a copy of theta[j] (CSR,
+    int32).  proj: the [begin, end) ranges of theta that picnn.project clamps."""
+
+    def __init__(self, model):
+        layout = grad_layout(model.spec)
+        self.n = sum(int(np.prod(shape)) for _, shape in layout)
+        img, parts, self.offsets = arena_image(model, index_params(layout))
+        self.arena_floats = img.size
+        if self.arena_floats >= 1 << 31:
+            raise ValueError("arena of %d floats: int32 offsets do not reach" % self.arena_floats)
+        src = img.astype(np.int64)
+        if not (np.array_equal(src.astype(np.float32), img) and src.min() >= 0 and src.max() <= self.n):
+            raise AssertionError("the host packers changed an index value: the arena is not a copy of theta")
+        src -= 1                                       # -1: padding
+        pos = np.nonzero(src >= 0)[0]
+        order = np.argsort(src[pos], kind="stable")
+        self.dest = pos[order].astype(np.int32)
+        counts = np.bincount(src[pos], minlength=self.n)
+        self.dest_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        self.max_fanout = int(counts.max())
+        self.proj, at = [], 0
+        for name, shape in layout:
+            size = int(np.prod(shape))
+            if "proj" in name and name.endswith("/W"):
+                self.proj.append((at, at + size))
+            at += size
+
+    def scatter(self, theta) -> np.ndarray:
+        """The arena of a flat float32 theta as the kernel writes it (NumPy; padding zero)."""
+        out = np.zeros(self.arena_floats, np.float32)
+        src = np.repeat(np.arange(self.n), np.diff(self.dest_off))
+        out[self.dest] = np.asarray(theta, np.float32)[src]
+        return out
+
+
+def adam_lr_t(lr, beta1, beta2, t) -> float:
+    """TFAdam's bias-corrected step size, float64 from the step count (DeviceAdam rounds it once to float32)"""
+    return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+
+
+def _host(params) -> Dict[str, np.ndarray]:
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float32)) for k, v in params.items()}
+
+
+class DeviceAdam:
+    """tf.train.AdamOptimizer (TFAdam's rule) + the reference's proj + the repack of the model, on the device, one launch
+    per step (icnn_be_param_update).  theta, m, v are flat float32 device tensors in grad_layout order; the step count
+    lives on the device and every launch advances it, so a captured step replayed k times is k steps.
+
+    Constructing one ATTACHES the model: its packed weights move into one persistent device buffer (the arena) that
+    c_model.wpack and every c_ctx pointer reference from then on, so solves, contexts and gradients captured in a graph keep
+    reading the current weights.  An attached model's `params` are live device views of theta; its repack, repack_context
+    and clamp raise (use load)."""
+
+    def __init__(self, model, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        if getattr(model, "_optimizer", None) is not None:
+            raise RuntimeError("the model is already attached to a DeviceAdam")
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
+        self.layout = grad_layout(self.spec)
+        self.map = ParamMap(model)
+        self.n = self.map.n
+        if self.n != grad_floats(model):
+            raise AssertionError("grad_layout has %d floats, the library's gradient %d" % (self.n, grad_floats(model)))
+        if len(self.map.proj) > _lib.MAX_PROJ_RANGES:
+            raise ValueError("%d proj weights, the kernel takes %d ranges" % (len(self.map.proj), _lib.MAX_PROJ_RANGES))
+        dev = self.device
+        self.theta = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.m = torch.zeros_like(self.theta)
+        self.v = torch.zeros_like(self.theta)
+        self.step_count = torch.zeros(2, dtype=torch.int32, device=dev)     # updates done, ticket
+        self.dest_off = torch.from_numpy(self.map.dest_off).to(dev)
+        self.dest = torch.from_numpy(self.map.dest).to(dev)
+        buf = torch.zeros(self.map.arena_floats + ARENA_ALIGN, dtype=torch.float32, device=dev)
+        lead = (-buf.data_ptr() % 256) // 4           # device allocations are aligned already; host ones to 64 bytes
+        self.arena = buf[lead:lead + self.map.arena_floats]
+        assert self.arena.data_ptr() % 256 == 0
+        params = _host(model.params)
+        self.load(params)
+        model._use_arena(self, self.arena, model.arena_parts(params), self.map.offsets)
+        a = _lib.ParamUpdateArgs()
+        a.n, a.theta, a.m, a.v = self.n, self.theta.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
+        a.dest_off, a.dest, a.arena = self.dest_off.data_ptr(), self.dest.data_ptr(), self.arena.data_ptr()
+        a.arena_floats, a.step = self.arena.numel(), self.step_count.data_ptr()
+        a.lr, a.beta1, a.beta2, a.eps = self.lr, self.beta1, self.beta2, self.eps
+        a.n_proj = len(self.map.proj)
+        for i, (b, e) in enumerate(self.map.proj):
+            a.proj_begin[i], a.proj_end[i] = b, e
+        self._args = a
+
+    @property
+    def t(self) -> int:
+        """updates done (reads the device counter: synchronises)"""
+        return int(self.step_count[0].item())
+
+    def step(self, grad):
+        """One update with `grad`: the flat float32 [n] tensor surrogate_grad(..., flat=True) returns, or its dict form.
+        Enqueued on the current stream, no host synchronisation (capturable)."""
+        if isinstance(grad, dict):
+            grad = torch.cat([grad[name].reshape(-1) for name, _ in self.layout])
+        grad = grad.to(self.device, torch.float32)
+        if grad.shape != (self.n,):
+            raise ValueError("gradient of shape %s, the model has %d parameters" % (tuple(grad.shape), self.n))
+        if not grad.is_contiguous() or grad.data_ptr() % 16:
+            grad = grad.clone()
+        self._args.grad = grad.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.model._lib.icnn_be_param_update(C.byref(self._args), C.c_void_p(stream)), "icnn_be_param_update")
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        """device views of theta under the reference's names and shapes"""
+        return unpack_grad(self.spec, self.theta)
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        """theta as a NumPy dict (one copy; synchronises): checkpoints, or a fresh FCModel / ConvModel"""
+        flat = self.theta.cpu().numpy()
+        return {name: t.numpy().copy() for name, t in unpack_grad(self.spec, torch.from_numpy(flat)).items()}
+
+    def load(self, params):
+        """Replace theta by `params` (host arrays or device tensors keyed like grad_layout) and rewrite the arena from
+        them through the host packers.  m, v and the step count are kept."""
+        host = _host(params)
+        missing = [name for name, _ in self.layout if name not in host]
+        if missing:
+            raise KeyError("parameters missing: %s" % missing)
+        flat = np.concatenate([np.asarray(host[name], np.float32).reshape(-1) for name, _ in self.layout])
+        if flat.size != self.n:
+            raise ValueError("parameters hold %d floats, the model %d" % (flat.size, self.n))
+        self.theta.copy_(torch.from_numpy(flat))
+        self.arena.copy_(torch.from_numpy(arena_image(self.model, host)[0]))

@@ -217,8 +217,8 @@ ICNN_BE_API int icnn_be_abi_version(void);
 ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
- * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5: lets a
- * foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
+ * sizeof(icnn_be_param_update_args) for 6: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -549,6 +549,41 @@ ICNN_BE_API int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, 
                                                int batch, const int *row_offset, int rows, const double *y, const double *v,
                                                const double *cvec, float *grad, float *F_rows, float *work,
                                                const icnn_be_bn_moving *mv, int updates, void *stream);
+
+/* ---- parameter update on the device (be_train_update.hip, additive to ABI 12) ------------------ */
+
+/*
+ * One tf.train.AdamOptimizer step over the flat parameter vector theta (the order of the *_surrogate_grad gradient), the
+ * reference's proj clamp, and the scatter of every new theta[j] into each copy the kernels read (the weight arena: wpack,
+ * the x-only stage operands, BatchNorm gamma / beta).  Per element j, float32, in this order and without contraction:
+ *   m = beta1 * m + (1 - beta1) * g;  v = beta2 * v + (1 - beta2) * (g * g);
+ *   theta = theta - (lr_t * m) / (sqrt(v) + eps);  theta = 0 if theta < 0 and j lies in a proj range;
+ *   arena[dest[k]] = theta  for dest_off[j] <= k < dest_off[j + 1]
+ * with beta1, 1 - beta1, beta2, 1 - beta2 (computed in double) and eps rounded to float, and
+ *   lr_t = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t))   in double, t = step[0] + 1
+ * step[0] (updates done) lives in device memory and the launch advances it: the last workgroup to finish (ticket step[1],
+ * zero between launches) writes t back.  A captured launch replayed k times is therefore k updates.
+ * theta, m, v, grad: 16-byte aligned.  dest[] entries >= arena_floats are skipped.  EINVAL for a NULL pointer, n < 1,
+ * a misaligned stream, n_proj outside [0, ICNN_BE_MAX_PROJ_RANGES], a bad range, beta outside [0, 1) or eps <= 0,
+ * before anything is launched.  No host synchronisation (capturable in a HIP graph).
+ */
+#define ICNN_BE_MAX_PROJ_RANGES 8
+typedef struct icnn_be_param_update_args {
+    long long n;                   /* floats of theta */
+    float *theta, *m, *v;          /* [n] float32, updated in place */
+    const float *grad;             /* [n] float32 */
+    const int *dest_off;           /* [n + 1] CSR offsets into dest */
+    const int *dest;               /* arena float offsets */
+    float *arena;
+    long long arena_floats;
+    int *step;                     /* [2] int32: updates done, ticket */
+    double lr, beta1, beta2;
+    float eps;
+    int n_proj;                    /* [proj_begin[i], proj_end[i]) of theta are clamped at 0 */
+    long long proj_begin[ICNN_BE_MAX_PROJ_RANGES], proj_end[ICNN_BE_MAX_PROJ_RANGES];
+} icnn_be_param_update_args;
+
+ICNN_BE_API int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
