@@ -20,6 +20,9 @@ def _problem(which, seed=0):
     if which == "rl":
         spec = picnn.halfcheetah_spec()
         return spec, picnn.init_params(spec, seed, "init", yu_bias=1.0, gate_bias=1.0), picnn.FCModel
+    if which == "deep":        # 8 z-layers, six batch-normalised u-layers (tests/test_architectures.py)
+        from test_architectures import DEEP
+        return DEEP, picnn.init_params(DEEP, seed, "spread"), picnn.FCModel
     spec = picnn.ConvSpec()
     return spec, picnn.init_conv_params(spec, seed, "spread"), picnn.ConvModel
 
@@ -35,7 +38,7 @@ def _bits(a):
 # ------------------------------------------------------------------------------------------------ CPU: the map
 
 
-@pytest.mark.parametrize("which", ["bibtex", "rl", "conv"])
+@pytest.mark.parametrize("which", ["bibtex", "rl", "deep", "conv"])
 def test_map_scatter_equals_host_packers(which):
     """The map applied as a NumPy scatter to random parameters = icnn_be_*_pack + the stage / gamma / beta buffers that
     repack / repack_context upload, bit for bit, at the arena's offsets; padding stays zero."""
@@ -59,7 +62,7 @@ def test_map_scatter_equals_host_packers(which):
           % (which, pm.n, pm.arena_floats, pm.dest.size, pm.max_fanout))
 
 
-@pytest.mark.parametrize("which", ["bibtex", "rl", "conv"])
+@pytest.mark.parametrize("which", ["bibtex", "rl", "deep", "conv"])
 def test_every_arena_float_has_one_source(which):
     spec, params, Model = _problem(which)
     model = Model(spec, params, "cpu")
@@ -71,11 +74,11 @@ def test_every_arena_float_has_one_source(which):
     src = np.repeat(np.arange(pm.n), np.diff(pm.dest_off))
     assert np.array_equal(idx[pm.dest].astype(np.int64) - 1, src)
     assert pm.dest_off[0] == 0 and pm.dest_off[-1] == pm.dest.size and (np.diff(pm.dest_off) >= 0).all()
-    expect = {"bibtex": 2, "rl": 2, "conv": 3}[which]
+    expect = {"bibtex": 2, "rl": 2, "deep": 2, "conv": 3}[which]
     assert pm.max_fanout == expect
 
 
-@pytest.mark.parametrize("which", ["bibtex", "rl", "conv"])
+@pytest.mark.parametrize("which", ["bibtex", "rl", "deep", "conv"])
 def test_arena_offsets_are_256_byte_aligned(which):
     spec, params, Model = _problem(which)
     model = Model(spec, params, "cpu")
@@ -157,7 +160,7 @@ def _random_grad(n, rng, scale=1e-2):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", ["bibtex", "conv"])
+@pytest.mark.parametrize("which", ["bibtex", "rl", "deep", "conv"])
 @pytest.mark.parametrize("t", [1, 7])
 def test_one_step_matches_numpy_restatement(which, t):
     spec, params, Model = _problem(which, 3)
@@ -187,7 +190,7 @@ def test_one_step_matches_numpy_restatement(which, t):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", ["bibtex", "conv"])
+@pytest.mark.parametrize("which", ["bibtex", "rl", "deep", "conv"])
 def test_five_steps_against_tfadam_and_project(which):
     spec, params, Model = _problem(which, 4)
     model = Model(spec, params, "cuda")
