@@ -57,10 +57,6 @@ int check_bn_mode(const icnn_be_bn_moving *mv, int mode, int updates, const int 
         if (n[l] > 0 && (!mv->mean[l] || !mv->var[l])) return ICNN_BE_EINVAL;
     return 0;
 }
-void fc_bn_layers(const icnn_be_fc_ctx &c, int *n) {
-    for (int l = 0; l < ICNN_BE_MAX_LAYERS; ++l) n[l] = c.batchnorm && l < c.n_layers - 2 ? c.width[l] : 0;
-}
-const int CONV_BN_LAYERS[4] = {1, 1, 1, 1};      // every u-map of the conv model is batch-normalised
 
 // what icnn_be_solve_fc requires of a model and a state beyond their buffers
 int check_fc_solve(const icnn_be_fc_model *model, const icnn_be_state *st) {
@@ -335,7 +331,7 @@ int icnn_be_fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, 
     if (!c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
     int n[ICNN_BE_MAX_LAYERS];
-    fc_bn_layers(*c, n);
+    icnn_be::fc_bn_widths(*c, n);
     if (int rc = check_bn_mode(mv, mode, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (batch == 0) return 0;
     hipError_t e = icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream), mv, mode,
@@ -366,7 +362,7 @@ int icnn_be_fc_surrogate_grad_bn(const icnn_be_fc_model *model, const icnn_be_fc
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
     int n[ICNN_BE_MAX_LAYERS];
-    fc_bn_layers(*c, n);
+    icnn_be::fc_bn_widths(*c, n);
     if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (int rc = icnn_be::fc_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
@@ -396,11 +392,12 @@ int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, const icnn_b
                                    float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
                                    void *stream) {
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
-    for (int s = 0; s < 7; ++s)
-        if (!c->w_stage[s] || !c->b_stage[s]) return ICNN_BE_EINVAL;
-    for (int i = 0; i < 4; ++i)
-        if (!c->bn_gamma[i] || !c->bn_beta[i]) return ICNN_BE_EINVAL;
-    if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, CONV_BN_LAYERS, 4)) return rc;
+    if (int rc = icnn_be::conv_ctx_check(*c)) return rc;
+    icnn_be::ConvCtxShape g{};
+    if (int rc = icnn_be::conv_ctx_shape(*model, g)) return rc;
+    int n[4];
+    icnn_be::conv_bn_widths(g, n);
+    if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, 4)) return rc;
     if (int rc = icnn_be::conv_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
                                                        static_cast<hipStream_t>(stream), mv, updates);
@@ -552,13 +549,12 @@ size_t icnn_be_conv_context_bn_work_floats(const icnn_be_conv_model *shape, int 
 int icnn_be_conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv, int mode,
                             int updates, const float *x, int batch, float *ctx, float *work, void *stream) {
     if (!shape || !c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
-    for (int s = 0; s < 7; ++s)
-        if (!c->w_stage[s] || !c->b_stage[s]) return ICNN_BE_EINVAL;
-    for (int i = 0; i < 4; ++i)
-        if (!c->bn_gamma[i] || !c->bn_beta[i]) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::conv_ctx_check(*c)) return rc;
     icnn_be::ConvCtxShape g{};
     if (int rc = icnn_be::conv_ctx_shape(*shape, g)) return rc;
-    if (int rc = check_bn_mode(mv, mode, updates, CONV_BN_LAYERS, 4)) return rc;
+    int n[4];
+    icnn_be::conv_bn_widths(g, n);
+    if (int rc = check_bn_mode(mv, mode, updates, n, 4)) return rc;
     if (batch == 0) return 0;
     hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates);
     return e == hipSuccess ? 0 : fail(e);

@@ -360,6 +360,14 @@ int ctx_check(const icnn_be_fc_ctx &c) {
     return 0;
 }
 
+int conv_ctx_check(const icnn_be_conv_ctx &c) {
+    for (int s = 0; s < 7; ++s)
+        if (!c.w_stage[s] || !c.b_stage[s]) return ICNN_BE_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (!c.bn_gamma[i] || !c.bn_beta[i]) return ICNN_BE_EINVAL;
+    return 0;
+}
+
 // columns of stage i: [ u_i (width[i], i < L) | yu_i (n) | zu_i (width[i]) | gate_i (width[i-1], i > 0) ]
 int ctx_stage_cols(const icnn_be_fc_ctx &c, int i) {
     const int L = c.n_layers - 1;
@@ -384,7 +392,7 @@ static float *bn_stat_at(float *stats, const int *n, int l) {
     for (int i = 0; i < l; ++i) stats += (2 * n[i] + 3) & ~3;
     return stats;
 }
-static void fc_bn_widths(const icnn_be_fc_ctx &c, int *n) {
+void fc_bn_widths(const icnn_be_fc_ctx &c, int *n) {
     for (int l = 0; l < ICNN_BE_MAX_LAYERS; ++l) n[l] = c.batchnorm && l < c.n_layers - 2 ? c.width[l] : 0;
 }
 size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch) {
@@ -420,10 +428,10 @@ hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *m
 // ld_l, so the stages can be issued one by one (icnn_be_fc_context_stage: data-parallel ranks all-reduce the BatchNorm
 // statistics between them) or back to back (icnn_be_fc_context).
 static int stage_bn(const icnn_be_fc_ctx &c, int i) { return c.batchnorm && i < c.n_layers - 2; }
-static float *stage_u(const icnn_be_fc_ctx &c, int i, int batch, float *work, int &u_ld) {
+float *fc_ctx_u(const icnn_be_fc_ctx &c, int batch, float *work, int i, int *ld) {
     float *wk = work;
     for (int l = 0; l < i; ++l) wk += (size_t)batch * ((c.width[l] + 3) & ~3);
-    u_ld = (c.width[i] + 3) & ~3;
+    *ld = (c.width[i] + 3) & ~3;
     return wk;
 }
 hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *x, int batch, float *ctx, int ctx_width,
@@ -437,7 +445,7 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
     if (expect != ctx_width || i < 0 || i > L) return hipErrorInvalidValue;       // before anything is written
     const float *prev = x;
     int prev_ld = c.n_features, prev_k = c.n_features;
-    if (i > 0) { prev = stage_u(c, i - 1, batch, work, prev_ld); prev_k = c.width[i - 1]; }
+    if (i > 0) { prev = fc_ctx_u(c, batch, work, i - 1, &prev_ld); prev_k = c.width[i - 1]; }
     CtxGemmArgs a{};
     a.A = prev; a.lda = prev_ld; a.M = batch; a.K = prev_k;
     a.W = c.w_stage[i]; a.ldw = ctx_stage_ld(c, i); a.N = ctx_stage_cols(c, i); a.bias = c.b_stage[i];
@@ -445,7 +453,7 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
     int col = 0, s = 0;
     if (i < L) {            // u_i: input of the next stage; hidden layers are ReLU'd (:343), the last one is linear
         int u_ld = 0;
-        float *u_out = stage_u(c, i, batch, work, u_ld);
+        float *u_out = fc_ctx_u(c, batch, work, i, &u_ld);
         a.seg[s++] = CtxSeg{col, col + c.width[i], u_ld, 0, i < L - 1 ? 1 : 0, 0, u_out};
         col += c.width[i];
     }
@@ -474,7 +482,7 @@ hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch,
         if (e != hipSuccess) return e;
         if (i < L && stage_bn(c, i)) {
             int u_ld = 0;
-            float *u_out = stage_u(c, i, batch, work, u_ld);
+            float *u_out = fc_ctx_u(c, batch, work, i, &u_ld);
             if (mode == ICNN_BE_BN_MOVING) {
                 e = launch_bn_affine(u_out, u_ld, batch, c.width[i], mv->mean[i], mv->var[i], c.bn_gamma[i], c.bn_beta[i],
                                      c.bn_eps, stream);
@@ -495,7 +503,7 @@ int launch_fc_context_sums(const icnn_be_fc_ctx &c, int i, int batch, float *wor
     err = hipSuccess;
     if (i < 0 || i >= c.n_layers - 1 || !stage_bn(c, i)) return 1;
     int u_ld = 0;
-    const float *u = stage_u(c, i, batch, work, u_ld);
+    const float *u = fc_ctx_u(c, batch, work, i, &u_ld);
     err = launch_kernel(ctx_bn_sums_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
                         stats);
     return 0;
@@ -504,7 +512,7 @@ hipError_t launch_fc_context_norm(const icnn_be_fc_ctx &c, int i, int batch, dou
                                   float *work, hipStream_t stream) {
     if (i < 0 || i >= c.n_layers - 1 || !stage_bn(c, i)) return hipErrorInvalidValue;
     int u_ld = 0;
-    float *u = stage_u(c, i, batch, work, u_ld);
+    float *u = fc_ctx_u(c, batch, work, i, &u_ld);
     return launch_kernel(ctx_bn_apply_kernel, dim3((c.width[i] + BNC - 1) / BNC), dim3(BNT), 0, stream, u, u_ld, batch, c.width[i],
                          stats, batch_total, c.bn_gamma[i], c.bn_beta[i], c.bn_eps);
 }
@@ -516,7 +524,7 @@ size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch) {
     return (size_t)batch * ((size_t)g.P[0] * g.F[0] + (size_t)g.P[1] * g.F[1] + (size_t)g.P[2] * g.F[2] + (size_t)((g.fch + 3) & ~3)) +
            2 * (size_t)BNB * 256;                    // + the BatchNorm partials
 }
-static void conv_bn_widths(const ConvCtxShape &g, int *n) {
+void conv_bn_widths(const ConvCtxShape &g, int *n) {
     n[0] = g.F[0]; n[1] = g.F[1]; n[2] = g.F[2]; n[3] = g.fch;
 }
 size_t conv_ctx_bn_work_floats(const ConvCtxShape &g, int batch) {

@@ -90,7 +90,14 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
 
 // x-only context producer and clamps (be_context.hip)
 int ctx_check(const icnn_be_fc_ctx &c);
+int conv_ctx_check(const icnn_be_conv_ctx &c);      // the stage and BatchNorm pointers of every conv entry
 size_t ctx_work_floats(const icnn_be_fc_ctx &c, int batch);
+// columns of stage i's GEMM and their pitch in w_stage[i]; fc_ctx_u: u_i (i < n_layers - 1) inside `work`, pitch *ld
+int ctx_stage_cols(const icnn_be_fc_ctx &c, int i);
+int ctx_stage_ld(const icnn_be_fc_ctx &c, int i);
+float *fc_ctx_u(const icnn_be_fc_ctx &c, int batch, float *work, int i, int *ld);
+// widths of the batch-normalised layers (n[l] = 0: not normalised), ICNN_BE_MAX_LAYERS of them for the FC model, 4 for the conv
+void fc_bn_widths(const icnn_be_fc_ctx &c, int *n);
 // mv / mode / updates: BatchNorm mode (include/icnn_be.h icnn_be_fc_context_bn, arguments checked by the caller); the
 // defaults are icnn_be_fc_context
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
@@ -127,6 +134,7 @@ size_t conv_ctx_bn_work_floats(const ConvCtxShape &g, int batch);
 hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_ctx &c, int stage, const float *x, int batch,
                                      float *ctx, float *work, hipStream_t stream);
 float *conv_ctx_u(const ConvCtxShape &g, int batch, float *work, int l);
+void conv_bn_widths(const ConvCtxShape &g, int *n);
 hipError_t launch_conv_clamp(const icnn_be_conv_model &m, int mode, hipStream_t stream);
 
 // training gradient of the FC PICNN (be_train_fc.hip): sizes (0 = shape rejected), shape check, launcher
@@ -137,11 +145,16 @@ hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                     float *grad, float *F_rows, float *work, hipStream_t stream,
                                     const icnn_be_bn_moving *mv = nullptr, int updates = 0);
-// the strided f32-MFMA GEMM of be_train_fc.hip: C[M][N] (pitch ldc) = A B, A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn],
-// split-K into `part` (tr_gemm_part_floats(M, N, K) floats) and summed in split order -- no atomics
+// shared by both training units (be_train_common.hip).  The strided f32-MFMA GEMM: C[M][N] (pitch ldc) = A B,
+// A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn], split-K into `part` (tr_gemm_part_floats(M, N, K) floats) and summed
+// in split order -- no atomics
 size_t tr_gemm_part_floats(int M, int N, int K);
 hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
                           int K, float *C, long long ldc, float *part, hipStream_t stream);
+// the feed's rows: samp[r] = the sample of row r, mult[j] = the row count of sample j (a float); out [B][C] = the rows
+// [R][C] of each sample summed in row order
+hipError_t launch_tr_rows(const int *row_offset, int B, int R, int *samp, float *mult, hipStream_t stream);
+hipError_t launch_tr_segment_sum(const float *rows, const int *row_offset, int B, int R, int C, float *out, hipStream_t stream);
 
 // training gradient of the conv PICNN (be_train_conv.hip), as the FC one above
 size_t conv_grad_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c);

@@ -16,45 +16,20 @@
 //   4. x-only backward on the B samples: head ReLUs, the weighted BatchNorm backward with its batch-statistics terms,
 //      stage weight and bias gradients (im2col^T dpre with a ones column: the bias row lands behind the weight, where the
 //      packed gradient keeps the bias), stage input gradients by col2im, down to u0.
-// Every contraction runs through be_train_fc.hip's strided f32-MFMA GEMM (launch_tr_gemm): split-K partials summed in a
-// fixed order, no atomics anywhere -- the same bits on every run, and no host synchronisation.
+// Every contraction runs through be_train_common.hip's strided f32-MFMA GEMM (launch_tr_gemm): split-K partials summed in
+// a fixed order, no atomics anywhere -- the same bits on every run, and no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
-#include "be_common.h"
-#include "be_kernels.h"
+#include "be_train_common.h"
 #include "icnn_be.h"
 
 namespace icnn_be {
 
 namespace {
 
-int grid_for(size_t total, int threads = 256) {
-    const size_t b = (total + threads - 1) / threads;
-    return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
 #define TC_LOOP(i, total) for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (total); i += (size_t)gridDim.x * blockDim.x)
-
-// samp[r] = the sample whose segment [row_offset[j], row_offset[j+1]) holds r (clamped to 0..B-1 whatever row_offset
-// holds), mult[j] = its row count (the BatchNorm weight)
-__global__ void tc_rows_kernel(const int *row_offset, int B, int R, int *samp, float *mult) {
-    TC_LOOP(i, (size_t)(R > B ? R : B)) {
-        if ((int)i < R) {
-            int lo = 0, hi = B - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (row_offset[mid] <= (int)i) lo = mid; else hi = mid - 1;
-            }
-            samp[i] = lo;
-        }
-        if ((int)i < B) {
-            const int a = min(max(row_offset[i], 0), R), b = min(max(row_offset[i + 1], 0), R);
-            mult[i] = b > a ? (float)(b - a) : 0.f;
-        }
-    }
-}
 
 // W[kk][col] of a forward MFMA operand packed by pack_frag (be_picnn_conv.hip), N output columns
 __device__ __forceinline__ float frag_at(const float *p, int N, int kk, int col) {
@@ -339,17 +314,6 @@ __global__ void tc_zero_kernel(float *p, size_t count) {
     TC_LOOP(i, count) p[i] = 0.f;
 }
 
-// out[j][col] = sum of the rows of sample j, in row order
-__global__ void tc_segment_sum_kernel(const float *rows, const int *row_offset, int B, int R, int C, float *out) {
-    TC_LOOP(i, (size_t)B * C) {
-        const int j = (int)(i / C), col = (int)(i - (size_t)j * C);
-        const int r0 = min(max(row_offset[j], 0), R), r1 = min(max(row_offset[j + 1], 0), R);
-        float s = 0.f;
-        for (int r = r0; r < r1; ++r) s += rows[(size_t)r * C + col];
-        out[i] = s;
-    }
-}
-
 // Weighted BatchNorm of a u-map [rows][N] (pitch ld; row = (sample, position), P positions per sample), BatchNorm over the R
 // feed rows = over the samples with weights m_j (Mtot = R P): grid (NCH row chunks, column blocks of 32), fixed-order sums.
 //   pass 0: per-chunk weighted sums;  pass 1: per-chunk weighted squared deviations from the mean (every workgroup forms it
@@ -560,37 +524,6 @@ int make_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch
     return 0;
 }
 
-// Workspace carving: the same walk sizes the buffer (dry run, base == nullptr) and launches (base != nullptr)
-struct Carver {
-    float *base;
-    size_t at = 0;
-    float *take(size_t floats) {
-        float *p = base ? base + at : nullptr;
-        at += (floats + 63) & ~size_t(63);       // 256-byte alignment of every piece
-        return p;
-    }
-};
-
-struct Runner {
-    hipStream_t stream;
-    float *part;            // split-K partials (dry run: nullptr)
-    size_t part_need = 0;
-    hipError_t err = hipSuccess;
-    bool dry() const { return part == nullptr; }
-    void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
-              float *C, long long ldc) {
-        const size_t need = tr_gemm_part_floats(M, N, K);
-        if (need > part_need) part_need = need;
-        if (err != hipSuccess || dry()) return;
-        err = launch_tr_gemm(A, sam, sak, B, sbk, sbn, M, N, K, C, ldc, part, stream);
-    }
-    template <typename... KArgs, typename... Args>
-    void launch(void (*k)(KArgs...), dim3 grid, int block, Args... args) {
-        if (err != hipSuccess || dry()) return;
-        err = launch_kernel(k, grid, dim3(block), 0, stream, args...);
-    }
-};
-
 hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx, const TrainShape &s, const float *x,
                          const int *row_offset, const double *y, const double *v, const double *cvec, float *grad, float *F_rows,
                          float *work, size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr,
@@ -691,7 +624,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     conv_pack_offsets(m, po);
 
     // 1. rows, multiplicities, y-path weights
-    run.launch(tc_rows_kernel, dim3(grid_for(R > B ? R : B)), 256, row_offset, B, R, samp, mult);
+    run.call([&] { return launch_tr_rows(row_offset, B, R, samp, mult, stream); });
     for (int l = 0; l < 3; ++l) {
         WyArgs wa{m.wpack, l == 1 ? po.p_l2 : po.p_l3, po.w_yu[l], l < 2 ? po.w_yr[l] : 0, l < 2 ? po.b_yr[l] : 0,
                   g.K[l] * g.K[l], s.cin[l], s.ch[l], g.F[l], l < 2 ? 1 : 0, Wy[l]};
@@ -707,13 +640,13 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
             run.launch(tc_wbn_fwd_kernel, dim3(NCH, (uN[l] + WBC - 1) / WBC), WBT, a, pass);
     };
     for (int q = 0; q < 7; ++q) {
-        if (!run.dry() && run.err == hipSuccess) run.err = launch_conv_context_stage(g, cx, q, x, B, ctxb, uwork, stream);
+        run.call([&] { return launch_conv_context_stage(g, cx, q, x, B, ctxb, uwork, stream); });
         if (q == 1) wbn_fwd(0);
         else if (q == 3) wbn_fwd(1);
         else if (q == 4) wbn_fwd(2);
         else if (q == 5) wbn_fwd(3);
     }
-    if (updates > 0 && !run.dry() && run.err == hipSuccess) run.err = launch_bn_fold(*mv, stat, uN, 4, updates, stream);
+    if (updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, uN, 4, updates, stream); });
 
     // 3. y-path forward, primal and tangent rows stacked
     auto colargs = [&](const float *in, int rows, int IH, int IW, int IC, int KS, int ST, int PD, int OH, int OW, int ld,
@@ -775,7 +708,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     run.launch(tc_zero_kernel, dim3(1), 256, grad + gl.u4W, (size_t)fch + 1);                     // u4: never read
 
     // 5. per-sample context gradient
-    run.launch(tc_segment_sum_kernel, dim3(grid_for((size_t)B * C)), 256, (const float *)drows, row_offset, B, R, C, dctx);
+    run.call([&] { return launch_tr_segment_sum(drows, row_offset, B, R, C, dctx, stream); });
 
     // 6. x-only backward on the B samples, stages in reverse order
     auto wbn_back = [&](int l, int q) {

@@ -15,105 +15,18 @@
 //   3. fixed-order segment sum of the per-row context gradient over the rows of each sample.
 //   4. x-only backward on B rows: head ReLUs, dW_stage = prev^T dpre, bias sums, dprev = dpre W_stage^T, ReLU and the
 //      weighted BatchNorm backward with its batch-statistics terms, down to u0.
-// Every product runs through ONE f32-MFMA GEMM kernel on strided operands with split-K and a fixed-order second pass:
-// no atomics anywhere, so the gradient is the same bits on every run and the whole entry can be captured in a graph.
+// Every product runs through be_train_common.hip's f32-MFMA GEMM (launch_tr_gemm): split-K partials summed in a fixed
+// order, no atomics anywhere -- the same bits on every run, and the whole entry can be captured in a graph.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
 #include "be_picnn_fc_dev.h"   // the packed y-path layout (pack_offsets, kblocks, pad16)
+#include "be_train_common.h"
 
 namespace icnn_be {
 
 namespace {
-
-constexpr int GBM = 64, GBN = 64, GBK = 16, GT_ = 256, GPITCH = GBK + 4;
-
-// C_part[split][M][N] = sum over k in split's chunk of A(m, k) B(k, n); A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn]
-struct TrGemmArgs {
-    const float *A, *B;
-    long long sam, sak, sbk, sbn;
-    int M, N, K, kchunk;
-    float *part;
-};
-
-__global__ __launch_bounds__(GT_) void tr_gemm_kernel(TrGemmArgs a) {
-    __shared__ __attribute__((aligned(16))) float As[GBM][GPITCH];
-    __shared__ __attribute__((aligned(16))) float Bt[GBN][GPITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
-    const int m0 = blockIdx.x * GBM, n0 = blockIdx.y * GBN;
-    const int k_beg = blockIdx.z * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
-    const bool a_kfast = a.sak == 1, b_nfast = a.sbn == 1;    // walk the unit-stride index across neighbouring lanes
-    f4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = k_beg; k0 < k_end; k0 += GBK) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int e = tid + GT_ * p;
-            const int ar = a_kfast ? e >> 4 : e & 63, ak = a_kfast ? e & 15 : e >> 6;
-            const int m = m0 + ar, k = k0 + ak;
-            As[ar][ak] = (m < a.M && k < k_end) ? a.A[(size_t)m * a.sam + (size_t)k * a.sak] : 0.f;
-            const int bc = b_nfast ? e & 63 : e >> 4, bk = b_nfast ? e >> 6 : e & 15;
-            const int n = n0 + bc, kb = k0 + bk;
-            Bt[bc][bk] = (n < a.N && kb < k_end) ? a.B[(size_t)kb * a.sbk + (size_t)n * a.sbn] : 0.f;
-        }
-        __syncthreads();
-        const f4 af = *reinterpret_cast<const f4 *>(&As[16 * wave + r16][4 * q]);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const f4 bf = *reinterpret_cast<const f4 *>(&Bt[16 * t + r16][4 * q]);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.x, bf.x, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.y, bf.y, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, bf.z, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.w, bf.w, acc[t], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // acc[t][r] = C[m0 + 16 wave + 4 q + r][n0 + 16 t + r16]
-    float *out = a.part + (size_t)blockIdx.z * a.M * a.N;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int col = n0 + 16 * t + r16;
-        if (col >= a.N) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + 16 * wave + 4 * q + r;
-            if (row < a.M) out[(size_t)row * a.N + col] = acc[t][r];
-        }
-    }
-}
-
-// second pass: C[m][n] (pitch ldc) = sum_s part[s][m][n], splits in order
-__global__ void tr_gemm_reduce_kernel(const float *part, int splits, int M, int N, float *C, long long ldc) {
-    const size_t total = (size_t)M * N;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        float s = part[i];
-        for (int sp = 1; sp < splits; ++sp) s += part[(size_t)sp * total + i];
-        const size_t m = i / N, n = i - m * N;
-        C[m * ldc + n] = s;
-    }
-}
-
-// Row bookkeeping: samp[r] = the sample whose segment [row_offset[j], row_offset[j+1]) holds r (binary search, clamped to
-// 0..B-1 whatever row_offset holds), mult[j] = its row count as a float (the BatchNorm weight)
-__global__ void tr_rows_kernel(const int *row_offset, int B, int R, int *samp, float *mult) {
-    const int total = R > B ? R : B;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        if (i < R) {
-            int lo = 0, hi = B - 1;             // last j with row_offset[j] <= i
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (row_offset[mid] <= i) lo = mid; else hi = mid - 1;
-            }
-            samp[i] = lo;
-        }
-        if (i < B) {
-            const int a = min(max(row_offset[i], 0), R), b = min(max(row_offset[i + 1], 0), R);
-            mult[i] = b > a ? (float)(b - a) : 0.f;
-        }
-    }
-}
 
 // The y-path weights of every layer out of the packed fragments (both orientations are there; the forward one is read):
 // Wst_i[(n + w_{i-1})][w_i] = [ Wyu_i ; Wzu_i ] row-major
@@ -230,18 +143,6 @@ __global__ void tr_back_rows_kernel(RowArgs a, BackArgs b) {
             const int k = j - ldb;
             drow[b.zu_off + k] = b.adj[(size_t)r * b.w + k];
         }
-    }
-}
-
-// dctx[j][col] = sum of the rows of sample j, in row order
-__global__ void tr_segment_sum_kernel(const float *rows, const int *row_offset, int B, int R, int C, float *out) {
-    const size_t total = (size_t)B * C;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(i / C), col = (int)(i - (size_t)j * C);
-        const int r0 = min(max(row_offset[j], 0), R), r1 = min(max(row_offset[j + 1], 0), R);
-        float s = 0.f;
-        for (int r = r0; r < r1; ++r) s += rows[(size_t)r * C + col];
-        out[i] = s;
     }
 }
 
@@ -363,30 +264,11 @@ __global__ void tr_colsum_kernel(const float *dpre, int ld, int B, int c0, int N
     out[col] = s;
 }
 
-int grid_for(size_t total, int threads = 256) {
-    const size_t b = (total + threads - 1) / threads;
-    return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
-// Workspace carving: the same walk sizes the buffer (dry run, base == nullptr) and launches (base != nullptr)
-struct Carver {
-    float *base;
-    size_t at = 0;
-    float *take(size_t floats) {
-        float *p = base ? base + at : nullptr;
-        at += (floats + 63) & ~size_t(63);       // 256-byte alignment of every piece
-        return p;
-    }
-};
-
 struct TrainShape {
     int L, n, nf, C, B, R, R2, bn;
     int w[ICNN_BE_MAX_LAYERS];
     int yu_off[ICNN_BE_MAX_LAYERS], zu_off[ICNN_BE_MAX_LAYERS], gate_off[ICNN_BE_MAX_LAYERS];
     int K(int i) const { return i == 0 ? nf : w[i - 1]; }                                   // stage input width
-    int stage_cols(int i) const { return (i < L ? w[i] : 0) + n + w[i] + (i > 0 ? w[i - 1] : 0); }
-    int stage_ld(int i) const { return (stage_cols(i) + 3) & ~3; }
-    int u_ld(int i) const { return (w[i] + 3) & ~3; }
     int pq_ld(int i) const { return n + (i > 0 ? w[i - 1] : 0); }
 };
 
@@ -447,7 +329,7 @@ int make_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, in
     // every index of the row kernels is an int: R2 x ctx_width (which covers n + 2 widths), B x the widest stage row
     int widest = o;
     for (int i = 0; i <= s.L; ++i) {
-        const int cols = (i < s.L ? m.width[i] : 0) + m.n + m.width[i] + (i > 0 ? m.width[i - 1] : 0);
+        const int cols = ctx_stage_cols(c, i);
         if (cols + 4 > widest) widest = cols + 4;
     }
     const size_t r2 = (with_v ? 2 : 1) * (size_t)rows;
@@ -458,52 +340,6 @@ int make_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, in
     s.R2 = with_v ? 2 * rows : rows;
     return 0;
 }
-
-// split-K plan: enough splits that a small output still fills the device
-void gemm_splits(int M, int N, int K, int &splits, int &kchunk) {
-    const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-    splits = 1;
-    if (tiles < 256 && K > 64) {
-        splits = (256 + tiles - 1) / tiles;
-        const int most = (K + 63) / 64;
-        if (splits > most) splits = most;
-        if (splits > 32) splits = 32;
-    }
-    kchunk = (K + splits - 1) / splits;
-    kchunk = (kchunk + GBK - 1) / GBK * GBK;
-    if (kchunk < GBK) kchunk = GBK;
-    splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
-}
-
-struct Runner {
-    const TrainShape &s;
-    hipStream_t stream;
-    float *part;            // split-K partials (dry run: nullptr)
-    size_t part_need = 0;   // most partial floats any product needs
-    hipError_t err = hipSuccess;
-    bool dry() const { return part == nullptr; }
-
-    // C[M][N] (pitch ldc) = A B, strided operands; split-K over K so that a small output still fills the device
-    void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
-              float *C, long long ldc) {
-        if (err != hipSuccess || M <= 0 || N <= 0) return;
-        int splits, kchunk;
-        gemm_splits(M, N, K, splits, kchunk);
-        const size_t need = (size_t)splits * M * N;
-        if (need > part_need) part_need = need;
-        if (dry()) return;
-        TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part};
-        err = launch_kernel(tr_gemm_kernel, dim3((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits), dim3(GT_), 0, stream, a);
-        if (err == hipSuccess)
-            err = launch_kernel(tr_gemm_reduce_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream,
-                                (const float *)part, splits, M, N, C, ldc);
-    }
-    template <typename... KArgs, typename... Args>
-    void launch(void (*k)(KArgs...), int grid, int block, Args... args) {
-        if (err != hipSuccess || dry()) return;
-        err = launch_kernel(k, dim3(grid), dim3(block), 0, stream, args...);
-    }
-};
 
 // The whole step; with work == nullptr only sizes the workspace (returned through *work_floats)
 hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, const TrainShape &s, const float *x, const int *row_offset,
@@ -517,14 +353,14 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
     float *ctxb = cv.take((size_t)B * C);
     float *hsave[ICNN_BE_MAX_LAYERS] = {}, *xhat[ICNN_BE_MAX_LAYERS] = {}, *inv[ICNN_BE_MAX_LAYERS] = {};
     float *stat[ICNN_BE_MAX_LAYERS] = {};       // the weighted statistics, for the moving ones
-    int bn_n[ICNN_BE_MAX_LAYERS] = {};
+    int bn_n[ICNN_BE_MAX_LAYERS];
+    fc_bn_widths(cx, bn_n);
     for (int i = 0; i + 1 < L; ++i)
-        if (s.bn) {
-            hsave[i] = cv.take((size_t)B * s.w[i]);
-            xhat[i] = cv.take((size_t)B * s.w[i]);
-            inv[i] = cv.take(s.w[i]);
-            stat[i] = cv.take(2 * (size_t)s.w[i]);
-            bn_n[i] = s.w[i];
+        if (bn_n[i]) {
+            hsave[i] = cv.take((size_t)B * bn_n[i]);
+            xhat[i] = cv.take((size_t)B * bn_n[i]);
+            inv[i] = cv.take(bn_n[i]);
+            stat[i] = cv.take(2 * (size_t)bn_n[i]);
         }
     float *wst[ICNN_BE_MAX_LAYERS], *pq[ICNN_BE_MAX_LAYERS], *adj[ICNN_BE_MAX_LAYERS], *Z[ICNN_BE_MAX_LAYERS] = {},
           *D[ICNN_BE_MAX_LAYERS] = {}, *dpre[ICNN_BE_MAX_LAYERS];
@@ -537,7 +373,7 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
             Z[i] = cv.take((size_t)R2 * s.w[i]);
             D[i] = cv.take((size_t)R * s.w[i]);
         }
-        dpre[i] = cv.take((size_t)B * s.stage_ld(i));
+        dpre[i] = cv.take((size_t)B * ctx_stage_ld(cx, i));
         if (s.pq_ld(i) > max_pq) max_pq = s.pq_ld(i);
         if (s.K(i) > max_k) max_k = s.K(i);
     }
@@ -549,31 +385,31 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
     float *dctx = cv.take((size_t)B * C);
     float *du = cv.take((size_t)B * max_k);
     const size_t fixed = cv.at;
+    // u_i (i < L) as the context producer leaves it in uwork: the input of stage i + 1, after its BatchNorm
+    float *u[ICNN_BE_MAX_LAYERS] = {};
+    int u_ld[ICNN_BE_MAX_LAYERS] = {};
+    for (int i = 0; i < L; ++i) u[i] = uwork ? fc_ctx_u(cx, B, uwork, i, &u_ld[i]) : nullptr;
 
     // the partials go last: their size is what the products below ask for (measured by the dry run)
-    Runner run{s, stream, work ? work + fixed : nullptr};
+    Runner run{stream, work ? work + fixed : nullptr};
     const PackOffsets po = pack_offsets(m);
     const GradLayout gl = grad_layout(s);
     RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, m.action_box ? 1 : 0};
 
     // 1. rows and multiplicities, y-path weights
-    run.launch(tr_rows_kernel, grid_for(R > B ? R : B), 256, row_offset, B, R, samp, mult);
+    run.call([&] { return launch_tr_rows(row_offset, B, R, samp, mult, stream); });
     for (int i = 0; i <= L; ++i) {
         UnpackArgs ua{m.wpack, po.yu_f[i], po.zu_f[i], n, i > 0 ? s.w[i - 1] : 0, s.w[i], i == L ? 1 : 0, wst[i]};
         run.launch(tr_unpack_kernel, grid_for((size_t)s.pq_ld(i) * s.w[i]), 256, ua);
     }
     // 2. x-only forward on the B samples (context producer's stage GEMMs), weighted BatchNorm
     for (int i = 0; i <= L; ++i) {
-        if (!run.dry() && run.err == hipSuccess) run.err = launch_fc_context_stage(cx, i, x, B, ctxb, C, uwork, stream);
-        if (i + 1 < L && s.bn) {
-            float *u = uwork;
-            for (int l = 0; l < i; ++l) u += (size_t)B * s.u_ld(l);
-            run.launch(tr_wbn_fwd_kernel, (s.w[i] + WBC - 1) / WBC, WBT, u, s.u_ld(i), B, s.w[i], (const float *)mult, (float)R,
+        run.call([&] { return launch_fc_context_stage(cx, i, x, B, ctxb, C, uwork, stream); });
+        if (bn_n[i])
+            run.launch(tr_wbn_fwd_kernel, (s.w[i] + WBC - 1) / WBC, WBT, u[i], u_ld[i], B, s.w[i], (const float *)mult, (float)R,
                        cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i], updates > 0 ? stat[i] : nullptr);
-        }
     }
-    if (s.bn && updates > 0 && !run.dry() && run.err == hipSuccess)
-        run.err = launch_bn_fold(*mv, stat, bn_n, L - 1, updates, stream);
+    if (s.bn && updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, bn_n, L - 1, updates, stream); });
     // 3. y-path forward: primal and tangent rows stacked, one GEMM per layer
     for (int i = 0; i <= L; ++i) {
         const int ld = s.pq_ld(i), w = s.w[i];
@@ -596,30 +432,22 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
         run.launch(tr_back_rows_kernel, grid_for((size_t)R * (ld + w)), 256, ra, ba);
     }
     // 5. per-sample context gradient
-    run.launch(tr_segment_sum_kernel, grid_for((size_t)B * C), 256, (const float *)drows, row_offset, B, R, C, dctx);
+    run.call([&] { return launch_tr_segment_sum(drows, row_offset, B, R, C, dctx, stream); });
     // 6. x-only backward on the B samples
     for (int i = L; i >= 0; --i) {
-        const int K = s.K(i), ld = s.stage_ld(i), wp = i > 0 ? s.w[i - 1] : 0, ucols = i < L ? s.w[i] : 0;
+        const int K = s.K(i), ld = ctx_stage_ld(cx, i), wp = i > 0 ? s.w[i - 1] : 0, ucols = i < L ? s.w[i] : 0;
         run.launch(tr_dpre_heads_kernel, grid_for((size_t)B * (ld - ucols)), 256, (const float *)dctx, (const float *)ctxb, B, C,
                    ucols, n, s.w[i], wp, s.yu_off[i], s.zu_off[i], s.gate_off[i], dpre[i], ld);
         if (i < L) {        // u_i columns from du = dprev_{i+1} (computed in the previous iteration)
             const int mode = i == L - 1 ? 0 : (s.bn ? 2 : 1);
-            const float *u = uwork;
-            for (int l = 0; l < i; ++l) u += (size_t)B * s.u_ld(l);
-            run.launch(tr_u_back_kernel, (s.w[i] + WBC - 1) / WBC, WBT, (const float *)du, B, s.w[i], mode, u, s.u_ld(i),
+            run.launch(tr_u_back_kernel, (s.w[i] + WBC - 1) / WBC, WBT, (const float *)du, B, s.w[i], mode, u[i], u_ld[i],
                        (const float *)hsave[i], (const float *)xhat[i], (const float *)inv[i], cx.bn_gamma[i],
                        (const float *)mult, (float)R, dpre[i], ld, mode == 2 ? grad + gl.gam[i] : nullptr,
                        mode == 2 ? grad + gl.bet[i] : nullptr);
         }
         // stage input: x, or u_{i-1} as the next stage read it (after its BatchNorm)
-        const float *prev = x;
-        int prev_ld = s.nf;
-        if (i > 0) {
-            const float *u = uwork;
-            for (int l = 0; l < i - 1; ++l) u += (size_t)B * s.u_ld(l);
-            prev = u;
-            prev_ld = s.u_ld(i - 1);
-        }
+        const float *prev = i > 0 ? u[i - 1] : x;
+        const int prev_ld = i > 0 ? u_ld[i - 1] : s.nf;
         // column segments of the stage: [ u_i | yu_u | u | zu_u ] -> their gradient variables
         struct Seg { int c0, cols; size_t wo, bo; } segs[4];
         int ns = 0, c0 = 0;
@@ -633,33 +461,13 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
                        grad + segs[q].bo);
         }
         if (i > 0)          // du_{i-1} = dpre_i W_stage_i^T  [B][w_{i-1}]
-            run.gemm(dpre[i], ld, 1, cx.w_stage[i], 1, ld, B, K, s.stage_cols(i), du, K);
+            run.gemm(dpre[i], ld, 1, cx.w_stage[i], 1, ld, B, K, ctx_stage_cols(cx, i), du, K);
     }
     if (work_floats) *work_floats = fixed + run.part_need;
     return run.err;
 }
 
 }  // namespace
-
-size_t tr_gemm_part_floats(int M, int N, int K) {
-    if (M <= 0 || N <= 0) return 0;
-    int splits, kchunk;
-    gemm_splits(M, N, K, splits, kchunk);
-    return (size_t)splits * M * N;
-}
-
-hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
-                          int K, float *C, long long ldc, float *part, hipStream_t stream) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    int splits, kchunk;
-    gemm_splits(M, N, K, splits, kchunk);
-    TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part};
-    hipError_t e = launch_kernel(tr_gemm_kernel, dim3((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits), dim3(GT_), 0, stream, a);
-    if (e == hipSuccess)
-        e = launch_kernel(tr_gemm_reduce_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream, (const float *)part, splits,
-                          M, N, C, ldc);
-    return e;
-}
 
 size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c) {
     TrainShape s;

@@ -31,14 +31,14 @@ FC_CASES = {
     "box_depth4": FC(20, 12, (30, 20, 16), alpha=0.01, batchnorm=True, action_box=True),
     "box_L1": FC(17, 6, (24,), alpha=0.01, batchnorm=False, action_box=True),
 }
-# be_train_fc.hip: 64 x 64 output tiles, K in steps of 16, at most 32 splits
+# be_train_common.hip: 64 x 64 output tiles, K in steps of 16, at most 32 splits
 GBM = GBN = 64
 GBK = 16
 MAX_SPLITS = 32
 
 
 def gemm_splits(M, N, K):
-    """(splits, kchunk) of be_train_fc.hip's gemm_splits, restated"""
+    """(splits, kchunk) of be_train_common.hip's gemm_splits, restated"""
     tiles = -(-M // GBM) * -(-N // GBN)
     splits = 1
     if tiles < 256 and K > 64:
