@@ -54,6 +54,7 @@ EXPORTS = [
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
     "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn", "icnn_be_param_update",
+    "icnn_be_gd_workspace_bytes", "icnn_be_fc_gd", "icnn_be_conv_gd",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
@@ -253,6 +254,13 @@ def load():
     lib.icnn_be_conv_surrogate_grad_bn.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
+    lib.icnn_be_gd_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.icnn_be_gd_workspace_bytes.restype = C.c_size_t
+    lib.icnn_be_fc_gd.argtypes = ([C.POINTER(FcModel), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+                                  + [C.c_void_p] * 5)
+    lib.icnn_be_fc_gd.restype = C.c_int
+    lib.icnn_be_conv_gd.argtypes = [C.POINTER(ConvModel)] + lib.icnn_be_fc_gd.argtypes[1:]
+    lib.icnn_be_conv_gd.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
     if tuple(lib.icnn_be_struct_size(i) for i in range(7)) != (

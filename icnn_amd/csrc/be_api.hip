@@ -519,6 +519,34 @@ int icnn_be_conv_pack(const icnn_be_conv_model *shape, const float *const *w_yu_
     return icnn_be::conv_pack(*shape, w_yu_host, w_yr_host, b_yr_host, w_zu_host, w_fc3_host, w_fc4_host, out_host);
 }
 
+size_t icnn_be_gd_workspace_bytes(int batch, int n) {
+    return batch < 0 || n < 1 ? 0 : icnn_be::gd_workspace_bytes(batch, n);
+}
+
+int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                  double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
+    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack || model->action_box) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    hipError_t e = icnn_be::launch_fc_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
+                                         static_cast<hipStream_t>(stream));
+    if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                    double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
+    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::conv_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_conv_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
+                                           static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_conv_fg(const icnn_be_conv_model *model, const float *ctx, const double *y, int batch,
                     float *f, float *g, const int *finished, void *stream) {
     if (!model || !ctx || !y || !f || !g || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;

@@ -198,6 +198,14 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
                           float *f_best, int *iters, void *workspace, hipStream_t stream,
                           const icnn_be_fc_ctx *cx = nullptr, const float *obs = nullptr);
 
+// Unrolled momentum gradient descent on y (be_gd.hip): the FC form is one launch (persistent tiles or the per-sample rows
+// path), the conv form 1 + K (+1) rounds of launches.  hipErrorNotSupported: the model's tile does not fit the LDS.
+size_t gd_workspace_bytes(int batch, int n);
+bool gd_constants_ok(double lr, double momentum);     // lr, momentum and their float32 constants finite
+hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                        double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
+hipError_t launch_conv_gd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                          double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
 // ---- conv PICNN energy / gradient -------------------------------------------------
 int conv_check_model(const icnn_be_conv_model &m);
 // where the raw single-channel pieces and the forward MFMA operands of the convex weights sit inside wpack (floats)

@@ -10,6 +10,10 @@
                     be_train_update.hip (icnn_be_param_update) over a flat theta; the model's packed weights live in one
                     device buffer (the arena) that the update writes in place.
 
+    unrolled_grad   the parameter gradient of a loss of y_K through the unrolled momentum-GD inference of gd.solve (the
+                    back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
+                    over the trajectory's rows with c = 0 and v = coefficient x dL/dy_K.
+
 One training step of the multi-label experiment:
     solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
 or, for a caller that updates the weights itself,
@@ -158,6 +162,42 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
         None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
         None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates, C.c_void_p(stream)), entry)
     return grad if flat else unpack_grad(spec, grad)
+
+
+_COEF_CACHE: Dict[tuple, torch.Tensor] = {}
+
+
+def unrolled_grad(model, x: torch.Tensor, traj: torch.Tensor, ybar: torch.Tensor, lr: float, momentum: float, bn_updates=0,
+                  flat=False):
+    """Gradient of L(y_K) over every trainable variable of `model` when y_K = gd.solve(model, context(x), y0, K, lr, momentum)
+    -- the back-optimisation training step.  traj: float64 [B, K, n] (gd.solve(..., trajectory=True)), ybar = dL/dy_K
+    [B, n] (ConvModel: x, traj and ybar may carry the image shape).  E is piecewise linear in y, so the adjoint of y is the
+    same at every step and the gradient is sum_k grad_theta <dE/dy(x, y_k), coefficients[k] ybar>: one surrogate_grad over
+    the B K rows (sample-major, row_offset[j] = K j) with c = 0.  Each sample has the same multiplicity K, so BatchNorm over
+    those rows has the statistics of the reference's per-call batch, and the x-only backward runs once.
+
+    bn_updates is passed through.  Read as written, the reference's train_step executes K calls of f on its path to the
+    loss (E(y_0) .. E(y_{K-1}), each with its own BatchNorm of the batch) and would fold the statistics once per call, K
+    times; TensorFlow's graph optimiser may merge those identical x-only subgraphs, so that count is not pinned down.  flat: as surrogate_grad.  No host synchronisation once the step coefficients of (K, lr, momentum)
+    are on the device (the first call per triple uploads them: make it before capturing a CUDA graph)."""
+    dev = model.device
+    spec = model.spec
+    n = spec.n_labels
+    B = traj.shape[0]
+    traj = traj.to(dev, torch.float64).reshape(B, -1, n)
+    K = traj.shape[1]
+    ybar = ybar.to(dev, torch.float64).reshape(B, 1, n)
+    key = (K, float(lr), float(momentum), str(dev))
+    coef = _COEF_CACHE.get(key)
+    if coef is None:
+        from .gd import coefficients
+        coef = torch.from_numpy(coefficients(K, lr, momentum)).to(dev).view(1, K, 1)
+        _COEF_CACHE[key] = coef
+    y = traj.reshape(B * K, n)
+    v = (coef * ybar).reshape(B * K, n)
+    c = torch.zeros(B * K, dtype=torch.float64, device=dev)
+    row_offset = torch.arange(0, (B + 1) * K, K, dtype=torch.int32, device=dev)
+    return surrogate_grad(model, x, (y, v, c), row_offset=row_offset, bn_updates=bn_updates, flat=flat)
 
 
 class TFAdam:

@@ -630,6 +630,34 @@ ICNN_BE_API int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be
                                     int max_iter, double *act_best, float *f_best, int *iters, void *workspace,
                                     void *stream);
 
+/* ---- unrolled momentum gradient descent on y: back-optimisation inference (be_gd.hip, additive to ABI 12) ---- */
+
+/* bytes of device scratch icnn_be_fc_gd / icnn_be_conv_gd need for `batch` samples of dim(y) = n (0: bad arguments) */
+ICNN_BE_API size_t icnn_be_gd_workspace_bytes(int batch, int n);
+
+/*
+ * n_iter steps of momentum gradient descent on y inside the graph, as multi-label-cls/icnn-back.py:120-133 and
+ * completion/icnn.back.py:136-147 build them: from v_0 = 0, for k = 0 .. n_iter-1
+ *     g_k = dE/dy(x, y_k),  v_{k+1} = mu v_k - lr g_k,  y_{k+1} = (y_k - mu v_k) + (1+mu) v_{k+1}
+ * in float32 (every operation rounded, no contraction; constants float32(lr), float32(mu), float32(1.0 + mu) with the sum
+ * formed in double), no clipping to the box.  y0[B][n]: float64 holding float32 values, rounded on entry like a feed (may
+ * alias y_out).  Out (device): y_out[B][n] = y_K (float64 holding float32 values); traj (may be NULL) [B][n_iter][n] =
+ * y_0 .. y_{n_iter-1} -- the row layout of icnn_be_*_surrogate_grad with row_offset[j] = n_iter j; f_out (may be NULL)
+ * [B] float32 = E(y_K) from one more evaluation.  E and dE/dy are evaluated with the operations of icnn_be_fc_fg /
+ * icnn_be_conv_fg, so the result is bit-identical to a loop of those calls plus the float32 update.  Samples are
+ * independent: every batch size runs.  FC: one launch; conv: 1 + n_iter (+1) rounds of launches (the model's `work` must
+ * hold `batch`, SINGLE-STREAM as for icnn_be_conv_fg).  Enqueued on `stream`, no host synchronisation (capturable).
+ * ICNN_BE_EINVAL before any launch for n_iter < 1, batch < 0, a non-finite lr / momentum (or float32 constant), a NULL
+ * model, ctx, y0, y_out or workspace, an action_box model, or a shape the fg entries reject; ICNN_BE_ELIMIT for a model
+ * whose evaluation does not fit the LDS.
+ */
+ICNN_BE_API int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter,
+                              double lr, double momentum, double *y_out, double *traj, float *f_out, void *workspace,
+                              void *stream);
+ICNN_BE_API int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter,
+                                double lr, double momentum, double *y_out, double *traj, float *f_out, void *workspace,
+                                void *stream);
+
 /* ---- convolutional PICNN (completion/icnn_ebundle.py) ---------------------------------------- */
 
 /* Number of floats of the packed weight buffer (0 if the shape is rejected). */
