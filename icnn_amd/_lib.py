@@ -55,10 +55,13 @@ EXPORTS = [
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
     "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn", "icnn_be_param_update",
     "icnn_be_gd_workspace_bytes", "icnn_be_fc_gd", "icnn_be_conv_gd",
+    "icnn_be_rl_td", "icnn_be_rl_critic_update",
 ]
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
 MAX_PROJ_RANGES = 8
+RL_TD_MAX_BLOCKS = 256
+RL_TD_WORK_BYTES = 8 * RL_TD_MAX_BLOCKS + 16
 
 
 class State(C.Structure):
@@ -123,6 +126,14 @@ class ParamUpdateArgs(C.Structure):
         ("dest_off", C.c_void_p), ("dest", C.c_void_p), ("arena", C.c_void_p), ("arena_floats", C.c_longlong),
         ("step", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float),
         ("n_proj", C.c_int), ("proj_begin", C.c_longlong * MAX_PROJ_RANGES), ("proj_end", C.c_longlong * MAX_PROJ_RANGES),
+    ]
+
+
+class RlUpdateArgs(C.Structure):
+    """struct icnn_be_rl_update_args"""
+    _fields_ = [
+        ("adam", ParamUpdateArgs), ("target_theta", C.c_void_p), ("target_arena", C.c_void_p), ("decay", C.c_void_p),
+        ("tau", C.c_float), ("l2norm", C.c_float), ("wd", C.c_float),
     ]
 
 
@@ -261,12 +272,19 @@ def load():
     lib.icnn_be_fc_gd.restype = C.c_int
     lib.icnn_be_conv_gd.argtypes = [C.POINTER(ConvModel)] + lib.icnn_be_fc_gd.argtypes[1:]
     lib.icnn_be_conv_gd.restype = C.c_int
+    lib.icnn_be_rl_td.argtypes = ([C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                                         C.c_float, C.c_float] + [C.c_void_p] * 5)
+    lib.icnn_be_rl_td.restype = C.c_int
+    lib.icnn_be_rl_critic_update.argtypes = [C.POINTER(RlUpdateArgs), C.c_void_p]
+    lib.icnn_be_rl_critic_update.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
     if tuple(lib.icnn_be_struct_size(i) for i in range(7)) != (
             C.sizeof(State), C.sizeof(FcModel), C.sizeof(FcCtx), C.sizeof(ConvModel), C.sizeof(ConvCtx), C.sizeof(BnMoving),
             C.sizeof(ParamUpdateArgs)):
         raise ImportError("ctypes struct layout differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(7) != C.sizeof(RlUpdateArgs):
+        raise ImportError("ctypes struct layout of icnn_be_rl_update_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

@@ -15,6 +15,7 @@
 #include "be_dual_dev.h"
 #include "be_picnn_fc_dev.h"
 #include "be_picnn_fc_rows_dev.h"
+#include "be_rl_dev.h"
 
 namespace icnn_be {
 
@@ -117,14 +118,9 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
                 const int j = j0 + lane;
                 float pen = 0.f;
                 if (j < n) {
-                    const float af = (float)a.act[row + j];
-                    const float half = (af + 1.f) * 0.5f;
-                    const float p = fminf(fmaxf(half, 1e-4f), 0.9999f);          // tf.clip_by_value, :456
-                    const float q = 1.f - p;
-                    const float lp = (float)log((double)p), lq = (float)log((double)q);
-                    pen = p * lp + q * lq;
-                    const bool inside = half >= 1e-4f && half <= 0.9999f;
-                    const float ge = a.fa.g[row + j] + (inside ? 0.5f * (lp - lq) : 0.f);
+                    const EntropyTerm e = rl_entropy_term((float)a.act[row + j]);
+                    pen = e.pen;
+                    const float ge = a.fa.g[row + j] + e.dpen;
                     a.fa.g[row + j] = ge;                                        // read back by the same lane below
                 }
                 const int cnt = n - j0 < 64 ? n - j0 : 64;
@@ -239,14 +235,9 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
             const float *row = lds + wave * RF;
             float pen = 0.f;
             if (lane < n) {
-                const float af = (float)x;
-                const float half = (af + 1.f) * 0.5f;
-                const float p = fminf(fmaxf(half, 1e-4f), 0.9999f);
-                const float q = 1.f - p;
-                const float lp = (float)log((double)p), lq = (float)log((double)q);
-                pen = p * lp + q * lq;
-                const bool inside = half >= 1e-4f && half <= 0.9999f;
-                ge = row[lay.g_off + lane] + (inside ? 0.5f * (lp - lq) : 0.f);
+                const EntropyTerm e = rl_entropy_term((float)x);
+                pen = e.pen;
+                ge = row[lay.g_off + lane] + e.dpen;
             }
             float tot = 0.f;
             for (int l = 0; l < n; ++l) tot = tot + lane_value(pen, l);

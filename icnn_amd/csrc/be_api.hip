@@ -2,6 +2,7 @@
 // each entry point replaces).  Everything here only validates arguments and enqueues work.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cmath>
 #include <cstdlib>
 
 #include <map>
@@ -184,6 +185,25 @@ SolvePlan plan_fc_solve(const icnn_be_fc_model &m, const icnn_be_state &st, int 
 }
 }  // namespace
 
+namespace {
+// what icnn_be_param_update and icnn_be_rl_critic_update refuse before any launch
+int check_param_update(const icnn_be_param_update_args *a) {
+    if (!a || a->n < 1 || !a->theta || !a->m || !a->v || !a->grad || !a->dest_off || !a->dest || !a->arena || !a->step)
+        return ICNN_BE_EINVAL;
+    if (a->arena_floats < 0 || a->arena_floats > 0x7fffffffLL || icnn_be::param_update_blocks(a->n) > 0x7fffffffLL)
+        return ICNN_BE_EINVAL;
+    const void *aligned[] = {a->theta, a->m, a->v, a->grad, a->dest_off};
+    for (const void *p : aligned)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return ICNN_BE_EINVAL;
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f && a->lr == a->lr))
+        return ICNN_BE_EINVAL;
+    if (a->n_proj < 0 || a->n_proj > ICNN_BE_MAX_PROJ_RANGES) return ICNN_BE_EINVAL;
+    for (int r = 0; r < a->n_proj; ++r)
+        if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int icnn_be_abi_version(void) { return ICNN_BE_ABI_VERSION; }
@@ -194,7 +214,7 @@ size_t icnn_be_struct_size(int which) {
     return which == 0 ? sizeof(icnn_be_state) : which == 1 ? sizeof(icnn_be_fc_model)
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
          : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving)
-         : which == 6 ? sizeof(icnn_be_param_update_args) : 0;
+         : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -621,20 +641,49 @@ int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const 
 }
 
 int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {
-    if (!a || a->n < 1 || !a->theta || !a->m || !a->v || !a->grad || !a->dest_off || !a->dest || !a->arena || !a->step)
-        return ICNN_BE_EINVAL;
-    if (a->arena_floats < 0 || a->arena_floats > 0x7fffffffLL || icnn_be::param_update_blocks(a->n) > 0x7fffffffLL)
-        return ICNN_BE_EINVAL;
-    const void *aligned[] = {a->theta, a->m, a->v, a->grad, a->dest_off};
-    for (const void *p : aligned)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return ICNN_BE_EINVAL;
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f && a->lr == a->lr))
-        return ICNN_BE_EINVAL;
-    if (a->n_proj < 0 || a->n_proj > ICNN_BE_MAX_PROJ_RANGES) return ICNN_BE_EINVAL;
-    for (int r = 0; r < a->n_proj; ++r)
-        if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
+    if (int rc = check_param_update(a)) return rc;
     hipError_t e = icnn_be::launch_param_update(*a, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : fail(e);
 }
 
+int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, const float *rew, const unsigned char *term,
+                  const float *q2_src, const double *act2, float discount, const float *theta, long long n_theta,
+                  const unsigned char *decay, float l2norm, float wd, float *td, double *c, float *loss, void *work,
+                  void *stream) {
+    if (batch < 1 || n < 1 || n_theta < 1 || n_theta > 0x7fffffffLL) return ICNN_BE_EINVAL;
+    if (!e_critic || !act || !rew || !term || !q2_src || !theta || !decay || !td || !c || !loss || !work)
+        return ICNN_BE_EINVAL;
+    const uintptr_t a8[] = {reinterpret_cast<uintptr_t>(act), reinterpret_cast<uintptr_t>(act2),
+                            reinterpret_cast<uintptr_t>(c)};
+    for (uintptr_t p : a8)
+        if (p % 8) return ICNN_BE_EINVAL;
+    const uintptr_t a4[] = {reinterpret_cast<uintptr_t>(e_critic), reinterpret_cast<uintptr_t>(rew),
+                            reinterpret_cast<uintptr_t>(q2_src), reinterpret_cast<uintptr_t>(theta),
+                            reinterpret_cast<uintptr_t>(td), reinterpret_cast<uintptr_t>(loss)};
+    for (uintptr_t p : a4)
+        if (p % 4) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(work) % 16 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    if (!std::isfinite(discount) || !(l2norm >= 0.f) || !(wd >= 0.f) || !std::isfinite(l2norm) || !std::isfinite(wd))
+        return ICNN_BE_EINVAL;
+    const icnn_be::RlTdLaunch l{batch, n, e_critic, act, rew, term, q2_src, act2, discount, theta, n_theta, decay,
+                                l2norm, wd, td, c, loss, work};
+    hipError_t e = icnn_be::launch_rl_td(l, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
+    if (!a) return ICNN_BE_EINVAL;
+    if (int rc = check_param_update(&a->adam)) return rc;
+    if (!a->target_theta || !a->target_arena || !a->decay) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->target_theta) % 16 || reinterpret_cast<uintptr_t>(a->decay) % 4 ||
+        reinterpret_cast<uintptr_t>(a->target_arena) % 4 || reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    if (!(a->tau >= 0.f && a->tau <= 1.f) || !(a->l2norm >= 0.f) || !(a->wd >= 0.f) || !std::isfinite(a->l2norm) ||
+        !std::isfinite(a->wd))
+        return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_rl_critic_update(*a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 }  // extern "C"
+

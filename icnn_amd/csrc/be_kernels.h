@@ -225,4 +225,27 @@ hipError_t launch_conv_fg(const icnn_be_conv_model &m, const float *ctx, const d
 long long param_update_blocks(long long n);
 hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream);
 
+// ---- the RL critic's step (be_rl_train.hip) -----------------------------------------
+struct RlTdLaunch {
+    int batch, n;
+    const float *e_critic;
+    const double *act;
+    const float *rew;
+    const unsigned char *term;
+    const float *q2_src;
+    const double *act2;
+    float discount;
+    const float *theta;
+    long long n_theta;
+    const unsigned char *decay;
+    float l2norm, wd;
+    float *td;
+    double *c;
+    float *loss;
+    void *work;
+};
+int rl_td_blocks(long long n_theta);
+hipError_t launch_rl_td(const RlTdLaunch &l, hipStream_t stream);
+hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream);
+
 }  // namespace icnn_be

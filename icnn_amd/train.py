@@ -9,6 +9,8 @@
     DeviceAdam      the same update, the reference's proj and the repack of every copy the kernels read, in one launch of
                     be_train_update.hip (icnn_be_param_update) over a flat theta; the model's packed weights live in one
                     device buffer (the arena) that the update writes in place.
+    FollowerWeights the same theta and arena without optimiser state, for a model another launch writes (the RL agent's
+                    target network, rl_train.CriticTrainer).
 
     unrolled_grad   the parameter gradient of a loss of y_K through the unrolled momentum-GD inference of gd.solve (the
                     back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
@@ -313,7 +315,67 @@ def _host(params) -> Dict[str, np.ndarray]:
     return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float32)) for k, v in params.items()}
 
 
-class DeviceAdam:
+class _ArenaOwner:
+    """What a device-resident weight set is made of: the flat float32 theta in grad_layout order, the ParamMap of the model,
+    and the arena that the model's descriptors point into once attached."""
+
+    def _attach(self, model, max_proj=None):
+        if getattr(model, "_optimizer", None) is not None:
+            raise RuntimeError("the model is already attached to a DeviceAdam")
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.layout = grad_layout(self.spec)
+        self.map = ParamMap(model)
+        self.n = self.map.n
+        if self.n != grad_floats(model):
+            raise AssertionError("grad_layout has %d floats, the library's gradient %d" % (self.n, grad_floats(model)))
+        if max_proj is not None and len(self.map.proj) > max_proj:
+            raise ValueError("%d proj weights, the kernel takes %d ranges" % (len(self.map.proj), max_proj))
+        dev = self.device
+        self.theta = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self.dest_off = torch.from_numpy(self.map.dest_off).to(dev)
+        self.dest = torch.from_numpy(self.map.dest).to(dev)
+        buf = torch.zeros(self.map.arena_floats + ARENA_ALIGN, dtype=torch.float32, device=dev)
+        lead = (-buf.data_ptr() % 256) // 4           # device allocations are aligned already; host ones to 64 bytes
+        self.arena = buf[lead:lead + self.map.arena_floats]
+        assert self.arena.data_ptr() % 256 == 0
+        params = _host(model.params)
+        self.load(params)
+        model._use_arena(self, self.arena, model.arena_parts(params), self.map.offsets)
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        """device views of theta under the reference's names and shapes"""
+        return unpack_grad(self.spec, self.theta)
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        """theta as a NumPy dict (one copy; synchronises): checkpoints, or a fresh FCModel / ConvModel"""
+        flat = self.theta.cpu().numpy()
+        return {name: t.numpy().copy() for name, t in unpack_grad(self.spec, torch.from_numpy(flat)).items()}
+
+    def load(self, params):
+        """Replace theta by `params` (host arrays or device tensors keyed like grad_layout) and rewrite the arena from
+        them through the host packers."""
+        host = _host(params)
+        missing = [name for name, _ in self.layout if name not in host]
+        if missing:
+            raise KeyError("parameters missing: %s" % missing)
+        flat = np.concatenate([np.asarray(host[name], np.float32).reshape(-1) for name, _ in self.layout])
+        if flat.size != self.n:
+            raise ValueError("parameters hold %d floats, the model %d" % (flat.size, self.n))
+        self.theta.copy_(torch.from_numpy(flat))
+        self.arena.copy_(torch.from_numpy(arena_image(self.model, host)[0]))
+
+
+class FollowerWeights(_ArenaOwner):
+    """The weights of a model that another launch writes -- the RL agent's target network, which the critic's update
+    moves by a soft (Polyak) step (rl_train.CriticTrainer, icnn_be_rl_critic_update): theta and an arena of its own as
+    DeviceAdam keeps them, no optimiser state.  Constructing one ATTACHES the model the same way: its descriptors point
+    into the arena for good and its `params` are live device views of theta."""
+
+    def __init__(self, model):
+        self._attach(model)
+
+
+class DeviceAdam(_ArenaOwner):
     """tf.train.AdamOptimizer (TFAdam's rule) + the reference's proj + the repack of the model, on the device, one launch
     per step (icnn_be_param_update).  theta, m, v are flat float32 device tensors in grad_layout order; the step count
     lives on the device and every launch advances it, so a captured step replayed k times is k steps.
@@ -324,31 +386,11 @@ class DeviceAdam:
     and clamp raise (use load)."""
 
     def __init__(self, model, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
-        if getattr(model, "_optimizer", None) is not None:
-            raise RuntimeError("the model is already attached to a DeviceAdam")
-        self.model, self.spec, self.device = model, model.spec, model.device
         self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
-        self.layout = grad_layout(self.spec)
-        self.map = ParamMap(model)
-        self.n = self.map.n
-        if self.n != grad_floats(model):
-            raise AssertionError("grad_layout has %d floats, the library's gradient %d" % (self.n, grad_floats(model)))
-        if len(self.map.proj) > _lib.MAX_PROJ_RANGES:
-            raise ValueError("%d proj weights, the kernel takes %d ranges" % (len(self.map.proj), _lib.MAX_PROJ_RANGES))
-        dev = self.device
-        self.theta = torch.zeros(self.n, dtype=torch.float32, device=dev)
+        self._attach(model, max_proj=_lib.MAX_PROJ_RANGES)
         self.m = torch.zeros_like(self.theta)
         self.v = torch.zeros_like(self.theta)
-        self.step_count = torch.zeros(2, dtype=torch.int32, device=dev)     # updates done, ticket
-        self.dest_off = torch.from_numpy(self.map.dest_off).to(dev)
-        self.dest = torch.from_numpy(self.map.dest).to(dev)
-        buf = torch.zeros(self.map.arena_floats + ARENA_ALIGN, dtype=torch.float32, device=dev)
-        lead = (-buf.data_ptr() % 256) // 4           # device allocations are aligned already; host ones to 64 bytes
-        self.arena = buf[lead:lead + self.map.arena_floats]
-        assert self.arena.data_ptr() % 256 == 0
-        params = _host(model.params)
-        self.load(params)
-        model._use_arena(self, self.arena, model.arena_parts(params), self.map.offsets)
+        self.step_count = torch.zeros(2, dtype=torch.int32, device=self.device)     # updates done, ticket
         a = _lib.ParamUpdateArgs()
         a.n, a.theta, a.m, a.v = self.n, self.theta.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
         a.dest_off, a.dest, a.arena = self.dest_off.data_ptr(), self.dest.data_ptr(), self.arena.data_ptr()
@@ -378,24 +420,7 @@ class DeviceAdam:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.model._lib.icnn_be_param_update(C.byref(self._args), C.c_void_p(stream)), "icnn_be_param_update")
 
-    def params(self) -> Dict[str, torch.Tensor]:
-        """device views of theta under the reference's names and shapes"""
-        return unpack_grad(self.spec, self.theta)
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        """theta as a NumPy dict (one copy; synchronises): checkpoints, or a fresh FCModel / ConvModel"""
-        flat = self.theta.cpu().numpy()
-        return {name: t.numpy().copy() for name, t in unpack_grad(self.spec, torch.from_numpy(flat)).items()}
-
     def load(self, params):
         """Replace theta by `params` (host arrays or device tensors keyed like grad_layout) and rewrite the arena from
         them through the host packers.  m, v and the step count are kept."""
-        host = _host(params)
-        missing = [name for name, _ in self.layout if name not in host]
-        if missing:
-            raise KeyError("parameters missing: %s" % missing)
-        flat = np.concatenate([np.asarray(host[name], np.float32).reshape(-1) for name, _ in self.layout])
-        if flat.size != self.n:
-            raise ValueError("parameters hold %d floats, the model %d" % (flat.size, self.n))
-        self.theta.copy_(torch.from_numpy(flat))
-        self.arena.copy_(torch.from_numpy(arena_image(self.model, host)[0]))
+        _ArenaOwner.load(self, params)

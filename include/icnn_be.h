@@ -218,7 +218,8 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
- * sizeof(icnn_be_param_update_args) for 6: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7: lets a foreign-language binding verify
+ * its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -584,6 +585,57 @@ typedef struct icnn_be_param_update_args {
 } icnn_be_param_update_args;
 
 ICNN_BE_API int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream);
+
+/* ---- the RL agent's critic step: TD target, loss, decay, Adam, proj, soft target update (be_rl_train.hip, additive to ABI 12) */
+
+/*
+ * The TD part of the critic's training step (RL/src/icnn.py:56-93, FLAGS.icnn_opt == 'adam'), per sample j < batch,
+ * float32 in this order and without contraction, with tot(a) = sum_i pen(a_i) summed sequentially in float32 (the
+ * entropy term of be_adam.hip, pen from the float32 action):
+ *   q  = -(e_critic[j] + tot(act[j]))                                   q_entr at (obs, act)
+ *   q2 = -q2_src[j]  when act2 == NULL (q2_src already holds negQ_entr: the inner Adam's f_best),
+ *        -(q2_src[j] + tot(act2[j]))  otherwise (q2_src holds the target's negQ at act2)
+ *   y  = term[j] ? rew[j] : rew[j] + discount * q2;   y = max(q - 1, y);   y = min(q + 1, y)
+ *   td[j] = q - y;   c[j] = (double)(-((1 / batch) * (2 * td[j])))       the weight of E_j in the loss gradient
+ * and the loss, in double from float32 inputs, rounded once to float32:
+ *   loss = sum_j td_j^2 / batch + l2norm * (wd * sum_{i: decay[i]} theta[i]^2 / 2)
+ * decay[i] != 0 marks the elements of theta under the L2 regulariser (the W of every fully connected layer).  The sums
+ * have a fixed order for a given batch and n_theta (per-workgroup partials, then the last workgroup by ticket), so the
+ * result is bitwise repeatable.  work: ICNN_BE_RL_TD_WORK_BYTES bytes, zero before the first call (the call leaves it
+ * re-armed).  EINVAL for batch < 1, n < 1, n_theta < 1, a NULL or misaligned pointer (act, act2, c: 8 bytes; work: 16
+ * bytes), a non-finite discount, negative l2norm or wd, a misaligned stream, before anything is launched.  No host
+ * synchronisation (capturable in a HIP graph).
+ */
+#define ICNN_BE_RL_TD_MAX_BLOCKS 256
+#define ICNN_BE_RL_TD_WORK_BYTES (8 * ICNN_BE_RL_TD_MAX_BLOCKS + 16)
+ICNN_BE_API int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, const float *rew,
+                              const unsigned char *term, const float *q2_src, const double *act2, float discount,
+                              const float *theta, long long n_theta, const unsigned char *decay, float l2norm, float wd,
+                              float *td, double *c, float *loss, void *work, void *stream);
+
+/*
+ * The critic's weight update and the soft update of the target network in one launch.  Per element j of the flat theta
+ * (float32, in this order, without contraction; u = adam):
+ *   read theta_old = u.theta[j], theta_t = target_theta[j], m, v, g = u.grad[j]
+ *   target_theta[j] = theta_t - tau * (theta_t - theta_old)      (RL/src/icnn.py:104-105, from the critic's theta BEFORE
+ *                                                                  this step's Adam update)
+ *   g = g + k * theta_old  if decay[j],  k = (float)l2norm * (float)wd rounded to float32   (the L2 regulariser's gradient)
+ *   the TF-Adam step and proj of icnn_be_param_update with that g (same rules, same device step counter)
+ *   u.arena[dest[d]] = theta,  target_arena[dest[d]] = target_theta[j]   for u.dest_off[j] <= d < u.dest_off[j + 1]
+ * The critic and the target share one shape and therefore one map; the target is never projected.  target_theta: 16-byte
+ * aligned; decay: 4-byte aligned.  EINVAL for everything icnn_be_param_update refuses, a NULL target_theta /
+ * target_arena / decay, a misaligned pointer, tau outside [0, 1], negative l2norm or wd, before anything is launched.  No
+ * host synchronisation (capturable in a HIP graph).
+ */
+typedef struct icnn_be_rl_update_args {
+    icnn_be_param_update_args adam;   /* the critic: theta, m, v, grad, the map, its arena, the step counter, Adam */
+    float *target_theta;              /* [adam.n] float32, updated in place */
+    float *target_arena;              /* the target's arena: adam.arena_floats floats, the same map */
+    const unsigned char *decay;       /* [adam.n] nonzero: the element is under the L2 regulariser */
+    float tau, l2norm, wd;
+} icnn_be_rl_update_args;
+
+ICNN_BE_API int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
