@@ -1,0 +1,57 @@
+"""Train the FICNN of the synthetic classification experiment (synthetic-cls/icnn.py) on the device: moons, circles or
+linearly separable points generated with NumPy, 30 steps of momentum GD as inference, full-batch TF-Adam with proj.
+
+    python examples/synthetic_cls.py [--dataset moons|circles|linear] [--epochs 100] [--head sum|linear] [--n 100]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from icnn_amd import ficnn  # noqa: E402
+
+
+def make_data(name, n, seed):
+    rng = np.random.RandomState(seed)
+    h = n // 2
+    if name == "moons":
+        a, b = rng.rand(h) * np.pi, rng.rand(n - h) * np.pi
+        X = np.r_[np.c_[np.cos(a), np.sin(a)], np.c_[1 - np.cos(b), 0.5 - np.sin(b)]] + 0.1 * rng.randn(n, 2)
+        Y = np.r_[np.zeros(h), np.ones(n - h)]
+    elif name == "circles":
+        a = rng.rand(n) * 2 * np.pi
+        r = np.r_[np.ones(h), 0.5 * np.ones(n - h)]
+        X = np.c_[r * np.cos(a), r * np.sin(a)] + 0.05 * rng.randn(n, 2)
+        Y = np.r_[np.zeros(h), np.ones(n - h)]
+    elif name == "linear":
+        X = rng.uniform(-1, 1, (n, 2))
+        Y = (X[:, 0] + 0.5 * X[:, 1] + 0.2 * rng.randn(n) > 0).astype(np.float64)
+    else:
+        raise ValueError(name)
+    return X.astype(np.float32), Y.reshape(n, 1).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", default="moons", choices=["moons", "circles", "linear"])
+    ap.add_argument("--epochs", type=int, default=100)
+    ap.add_argument("--head", default="sum", choices=["sum", "linear"])
+    ap.add_argument("--n", type=int, default=100)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    X, Y = make_data(args.dataset, args.n, args.seed)
+    spec = ficnn.synthetic_spec(args.head)
+    params = ficnn.make_convex(ficnn.init_params(spec, args.seed))        # makeCvx after initialisation (icnn.py:172)
+    trainer = ficnn.GDTrainer(ficnn.FICNNModel(spec, params), args.n)
+    x, y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
+    for epoch in range(args.epochs):
+        loss = trainer.step(x if epoch == 0 else None, y if epoch == 0 else None)
+        print("=== Epoch %d ===\n + loss: %.5e" % (epoch, float(loss.item())))
+
+
+if __name__ == "__main__":
+    main()

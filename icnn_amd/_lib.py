@@ -56,7 +56,11 @@ EXPORTS = [
     "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn", "icnn_be_param_update",
     "icnn_be_gd_workspace_bytes", "icnn_be_fc_gd", "icnn_be_conv_gd",
     "icnn_be_rl_td", "icnn_be_rl_critic_update",
+    "icnn_be_ficnn_pack_floats", "icnn_be_ficnn_pack", "icnn_be_ficnn_context_work_floats", "icnn_be_ficnn_context",
+    "icnn_be_ficnn_fg", "icnn_be_ficnn_gd", "icnn_be_solve_ficnn", "icnn_be_ficnn_grad_floats",
+    "icnn_be_ficnn_surrogate_grad_work_floats", "icnn_be_ficnn_surrogate_grad",
 ]
+FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
 MAX_PROJ_RANGES = 8
@@ -94,6 +98,14 @@ class FcCtx(C.Structure):
         ("batchnorm", C.c_int), ("bn_eps", C.c_float),
         ("w_stage", C.c_void_p * MAX_LAYERS), ("b_stage", C.c_void_p * MAX_LAYERS),
         ("bn_gamma", C.c_void_p * MAX_LAYERS), ("bn_beta", C.c_void_p * MAX_LAYERS),
+    ]
+
+
+class FicnnModel(C.Structure):
+    """struct icnn_be_ficnn_model"""
+    _fields_ = [
+        ("n_features", C.c_int), ("n", C.c_int), ("n_layers", C.c_int), ("width", C.c_int * MAX_LAYERS),
+        ("head", C.c_int), ("ctx_width", C.c_int), ("wpack", C.c_void_p),
     ]
 
 
@@ -277,6 +289,27 @@ def load():
     lib.icnn_be_rl_td.restype = C.c_int
     lib.icnn_be_rl_critic_update.argtypes = [C.POINTER(RlUpdateArgs), C.c_void_p]
     lib.icnn_be_rl_critic_update.restype = C.c_int
+    FM = C.POINTER(FicnnModel)
+    lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
+    lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
+    lib.icnn_be_ficnn_pack.argtypes = [FM] + [C.POINTER(C.c_void_p)] * 3 + [C.c_void_p]
+    lib.icnn_be_ficnn_pack.restype = C.c_int
+    lib.icnn_be_ficnn_context_work_floats.argtypes = [FM, C.c_int]
+    lib.icnn_be_ficnn_context_work_floats.restype = C.c_size_t
+    lib.icnn_be_ficnn_context.argtypes = [FM, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.icnn_be_ficnn_context.restype = C.c_int
+    lib.icnn_be_ficnn_fg.argtypes = [FM] + lib.icnn_be_fc_fg.argtypes[1:]
+    lib.icnn_be_ficnn_fg.restype = C.c_int
+    lib.icnn_be_ficnn_gd.argtypes = [FM] + lib.icnn_be_fc_gd.argtypes[1:]
+    lib.icnn_be_ficnn_gd.restype = C.c_int
+    lib.icnn_be_solve_ficnn.argtypes = [FM] + lib.icnn_be_solve_fc.argtypes[1:]
+    lib.icnn_be_solve_ficnn.restype = C.c_int
+    lib.icnn_be_ficnn_grad_floats.argtypes = [FM]
+    lib.icnn_be_ficnn_grad_floats.restype = C.c_size_t
+    lib.icnn_be_ficnn_surrogate_grad_work_floats.argtypes = [FM, C.c_int, C.c_int]
+    lib.icnn_be_ficnn_surrogate_grad_work_floats.restype = C.c_size_t
+    lib.icnn_be_ficnn_surrogate_grad.argtypes = [FM, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.icnn_be_ficnn_surrogate_grad.restype = C.c_int
     lib.icnn_be_struct_size.argtypes = [C.c_int]
     lib.icnn_be_struct_size.restype = C.c_size_t
     if tuple(lib.icnn_be_struct_size(i) for i in range(7)) != (
@@ -285,6 +318,8 @@ def load():
         raise ImportError("ctypes struct layout differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(7) != C.sizeof(RlUpdateArgs):
         raise ImportError("ctypes struct layout of icnn_be_rl_update_args differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(8) != C.sizeof(FicnnModel):
+        raise ImportError("ctypes struct layout of icnn_be_ficnn_model differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

@@ -214,7 +214,8 @@ size_t icnn_be_struct_size(int which) {
     return which == 0 ? sizeof(icnn_be_state) : which == 1 ? sizeof(icnn_be_fc_model)
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
          : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving)
-         : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args) : 0;
+         : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args)
+         : which == 8 ? sizeof(icnn_be_ficnn_model) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -638,6 +639,94 @@ int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const 
         return icnn_be::launch_conv_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
     });
     return e == hipSuccess ? total : fail(e);
+}
+
+/* ---- FICNN (be_ficnn.hip, be_train_ficnn.hip) ---- */
+size_t icnn_be_ficnn_pack_floats(const icnn_be_ficnn_model *shape) {
+    if (!shape || icnn_be::ficnn_check_model(*shape) != 0) return 0;
+    return icnn_be::ficnn_pack_floats(*shape);
+}
+
+int icnn_be_ficnn_pack(const icnn_be_ficnn_model *shape, const float *const *w_x_host, const float *const *b_host,
+                       const float *const *w_z_host, float *out_host) {
+    if (!shape || !w_x_host || !b_host || !w_z_host || !out_host) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_check_model(*shape)) return rc;
+    const int L = shape->n_layers - 1, top = shape->head == ICNN_BE_FICNN_HEAD_LINEAR ? L : L - 1;
+    for (int i = 0; i <= top; ++i)
+        if (!w_x_host[i] || !b_host[i] || (i > 0 && !w_z_host[i])) return ICNN_BE_EINVAL;
+    return icnn_be::ficnn_pack(*shape, w_x_host, b_host, w_z_host, out_host);
+}
+
+size_t icnn_be_ficnn_context_work_floats(const icnn_be_ficnn_model *model, int batch) {
+    if (!model || batch < 0 || icnn_be::ficnn_check_model(*model) != 0) return 0;
+    return icnn_be::ficnn_context_work_floats(*model, batch);
+}
+
+int icnn_be_ficnn_context(const icnn_be_ficnn_model *model, const float *x, int batch, float *ctx, float *work, void *stream) {
+    if (!model || !x || !ctx || !work || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    hipError_t e = icnn_be::launch_ficnn_context(*model, x, batch, ctx, work, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_ficnn_fg(const icnn_be_ficnn_model *model, const float *ctx, const double *y, int batch, float *f, float *g,
+                     const int *finished, void *stream) {
+    if (!model || !ctx || !y || !f || !g || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    hipError_t e = icnn_be::launch_ficnn_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_ficnn_gd(const icnn_be_ficnn_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                     double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
+    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    hipError_t e = icnn_be::launch_ficnn_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
+                                            static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_solve_ficnn(const icnn_be_ficnn_model *model, const float *ctx, const icnn_be_state *st, float *f_work,
+                        float *g_work, void *stream) {
+    if (int rc = check_state(st)) return rc;
+    if (!model || !ctx || !f_work || !g_work || !model->wpack) return ICNN_BE_EINVAL;
+    if (st->cut_dtype != ICNN_BE_CUT_F32 || st->n != model->n) return ICNN_BE_EINVAL;
+    if (st->flags & ICNN_BE_FLAG_F64_ENERGY) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
+    if (st->batch == 0) return 0;
+    /* the scheduling of icnn_be_solve_conv: lockstep rounds unless time slicing is asked for */
+    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || st->variant == ICNN_BE_VARIANT_PDIPM ||
+                          !(st->flags & ICNN_BE_FLAG_TIME_SLICE);
+    const int T = outer_iters(*st), total = lockstep ? T : sliced_extra_rounds(T);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = solve_rounds(*st, lockstep ? 0 : SLICE_BUDGET, total, f_work, g_work, s, [&] {
+        return icnn_be::launch_ficnn_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
+    });
+    return e == hipSuccess ? total : fail(e);
+}
+
+size_t icnn_be_ficnn_grad_floats(const icnn_be_ficnn_model *model) {
+    if (!model) return 0;
+    return icnn_be::ficnn_grad_floats(*model);
+}
+
+size_t icnn_be_ficnn_surrogate_grad_work_floats(const icnn_be_ficnn_model *model, int batch, int rows) {
+    if (!model) return 0;
+    return icnn_be::ficnn_surrogate_work_floats(*model, batch, rows);
+}
+
+int icnn_be_ficnn_surrogate_grad(const icnn_be_ficnn_model *model, const float *x, int batch, const int *row_offset, int rows,
+                                 const double *y, const double *v, const double *cvec, float *grad, float *F_rows, float *work,
+                                 void *stream) {
+    if (!model || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::ficnn_surrogate_shape(*model, batch, rows, v != nullptr)) return rc;
+    hipError_t e = icnn_be::launch_ficnn_surrogate_grad(*model, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
 }
 
 int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {

@@ -206,6 +206,23 @@ hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const doubl
                         double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
 hipError_t launch_conv_gd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                           double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
+// ---- FICNN (be_ficnn.hip: context, energy / gradient, GD; be_train_ficnn.hip: training gradient) ----
+int ficnn_check_model(const icnn_be_ficnn_model &m);
+size_t ficnn_pack_floats(const icnn_be_ficnn_model &m);
+int ficnn_pack(const icnn_be_ficnn_model &m, const float *const *w_x, const float *const *b, const float *const *w_z, float *out);
+size_t ficnn_context_work_floats(const icnn_be_ficnn_model &m, int batch);
+hipError_t launch_ficnn_context(const icnn_be_ficnn_model &m, const float *x, int batch, float *ctx, float *work,
+                                hipStream_t stream);
+hipError_t launch_ficnn_fg(const icnn_be_ficnn_model &m, const float *ctx, const double *y, int batch, float *f, float *g,
+                           const int *finished, hipStream_t stream);
+hipError_t launch_ficnn_gd(const icnn_be_ficnn_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                           double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
+size_t ficnn_grad_floats(const icnn_be_ficnn_model &m);
+size_t ficnn_surrogate_work_floats(const icnn_be_ficnn_model &m, int batch, int rows);
+int ficnn_surrogate_shape(const icnn_be_ficnn_model &m, int batch, int rows, bool with_v);
+hipError_t launch_ficnn_surrogate_grad(const icnn_be_ficnn_model &m, const float *x, int batch, const int *row_offset, int rows,
+                                       const double *y, const double *v, const double *cvec, float *grad, float *F_rows,
+                                       float *work, hipStream_t stream);
 // ---- conv PICNN energy / gradient -------------------------------------------------
 int conv_check_model(const icnn_be_conv_model &m);
 // where the raw single-channel pieces and the forward MFMA operands of the convex weights sit inside wpack (floats)

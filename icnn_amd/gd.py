@@ -62,7 +62,7 @@ def solve(model, ctx: torch.Tensor, y0, n_iter: int, lr: float, momentum: float,
     stream = torch.cuda.current_stream(dev).cuda_stream
     if conv:
         model.reserve(B)
-    entry = "icnn_be_conv_gd" if conv else "icnn_be_fc_gd"
+    entry = "icnn_be_conv_gd" if conv else getattr(model, "gd_entry", "icnn_be_fc_gd")      # FICNNModel: icnn_be_ficnn_gd
     _lib.check(getattr(model._lib, entry)(
         C.byref(model.c_model), ctx.data_ptr(), y0.data_ptr(), B, K, float(lr), float(momentum), y.data_ptr(),
         None if traj is None else traj.data_ptr(), None if f is None else f.data_ptr(), ws.data_ptr(), C.c_void_p(stream)),

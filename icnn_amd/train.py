@@ -60,6 +60,10 @@ def grad_layout(spec) -> List[Tuple[str, tuple]]:
     picnn.init_params' keys for an FCSpec, of picnn.init_conv_params' for a ConvSpec)."""
     if isinstance(spec, ConvSpec):
         return _conv_grad_layout(spec)
+    from .ficnn import FICNNSpec
+    if isinstance(spec, FICNNSpec):
+        from .ficnn import grad_layout as ficnn_layout
+        return ficnn_layout(spec)
     L, n, w = len(spec.szs), spec.n_labels, spec.widths
     out = []
     prev = spec.n_features
@@ -91,6 +95,9 @@ def unpack_grad(spec, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
 
 
 def grad_floats(model) -> int:
+    from .ficnn import FICNNModel
+    if isinstance(model, FICNNModel):
+        return int(model._lib.icnn_be_ficnn_grad_floats(C.byref(model.c_model)))
     if isinstance(model, ConvModel):
         return int(model._lib.icnn_be_conv_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
     return int(model._lib.icnn_be_fc_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
@@ -147,6 +154,11 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     bn_updates = int(bn_updates)
     if bn_updates < 0:
         raise ValueError("bn_updates must be >= 0, got %d" % bn_updates)
+    from . import ficnn
+    if isinstance(model, ficnn.FICNNModel):            # no BatchNorm: icnn_be_ficnn_surrogate_grad
+        if bn_updates:
+            raise ValueError("a FICNN has no BatchNorm statistics to fold (bn_updates=%d)" % bn_updates)
+        return ficnn.surrogate_grad(model, x, row_offset, y, v, c, F_rows, flat)
     entry = "icnn_be_conv_surrogate_grad" if conv else "icnn_be_fc_surrogate_grad"
     grad = torch.empty(grad_floats(model), dtype=torch.float32, device=dev)
     if R == 0:
@@ -169,6 +181,19 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
 _COEF_CACHE: Dict[tuple, torch.Tensor] = {}
 
 
+def unrolled_coefficients(n_iter, lr, momentum, device) -> torch.Tensor:
+    """gd.coefficients(n_iter, lr, momentum) as a float64 [1, K, 1] device tensor, uploaded once per (K, lr, momentum,
+    device) -- call it before capturing a graph that runs unrolled_grad"""
+    K = int(n_iter)
+    key = (K, float(lr), float(momentum), str(device))
+    coef = _COEF_CACHE.get(key)
+    if coef is None:
+        from .gd import coefficients
+        coef = torch.from_numpy(coefficients(K, lr, momentum)).to(device).view(1, K, 1)
+        _COEF_CACHE[key] = coef
+    return coef
+
+
 def unrolled_grad(model, x: torch.Tensor, traj: torch.Tensor, ybar: torch.Tensor, lr: float, momentum: float, bn_updates=0,
                   flat=False):
     """Gradient of L(y_K) over every trainable variable of `model` when y_K = gd.solve(model, context(x), y0, K, lr, momentum)
@@ -189,12 +214,7 @@ def unrolled_grad(model, x: torch.Tensor, traj: torch.Tensor, ybar: torch.Tensor
     traj = traj.to(dev, torch.float64).reshape(B, -1, n)
     K = traj.shape[1]
     ybar = ybar.to(dev, torch.float64).reshape(B, 1, n)
-    key = (K, float(lr), float(momentum), str(dev))
-    coef = _COEF_CACHE.get(key)
-    if coef is None:
-        from .gd import coefficients
-        coef = torch.from_numpy(coefficients(K, lr, momentum)).to(dev).view(1, K, 1)
-        _COEF_CACHE[key] = coef
+    coef = unrolled_coefficients(K, lr, momentum, dev)
     y = traj.reshape(B * K, n)
     v = (coef * ybar).reshape(B * K, n)
     c = torch.zeros(B * K, dtype=torch.float64, device=dev)

@@ -218,8 +218,8 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
- * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7: lets a foreign-language binding verify
- * its struct layout at load time. */
+ * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8: lets a
+ * foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -709,6 +709,104 @@ ICNN_BE_API int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, c
 ICNN_BE_API int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter,
                                 double lr, double momentum, double *y_out, double *traj, float *f_out, void *workspace,
                                 void *stream);
+
+/* ---- fully input-convex network, FICNN (synthetic-cls/icnn.py; be_ficnn.hip, be_train_ficnn.hip, additive to ABI 12) --- */
+
+#define ICNN_BE_FICNN_HEAD_SUM 0     /* the reference's f_ficnn: E = sum_k z_{L-1,k} (its last layer never reassigns z) */
+#define ICNN_BE_FICNN_HEAD_LINEAR 1  /* the paper's FICNN: E = a_L, a linear scalar layer */
+
+/*
+ * Shape + packed weights of a FICNN (synthetic-cls/icnn.py:213-234, f_ficnn) with xy = concat(x, y):
+ *   a_i = xy W_x_i + b_i  (+ z_{i-1} W_z_i for i > 0, no bias),   z_i = relu(a_i)   for i = 0 .. L-1,
+ * E = sum_k z_{L-1,k} (head SUM) or E = a_L (head LINEAR), width[L] = 1.  W_x_i is 'z_x{i}/W' [n_features + n][width[i]]
+ * (x rows first), b_i 'z_x{i}/b', W_z_i 'z_z{i}_proj/W' [width[i-1]][width[i]].  The x-only context row of a sample is
+ *   c_0[width[0]] | c_1[width[1]] | ... ,  c_i = x W_x_i[:n_features] + b_i,
+ * over the layers the head evaluates: i < L (SUM) or i <= L (LINEAR); ctx_width is its length.
+ */
+typedef struct icnn_be_ficnn_model {
+    int n_features;                     /* dim(x) */
+    int n;                              /* dim(y) */
+    int n_layers;                       /* L+1: the hidden layers and the scalar head layer (2 .. ICNN_BE_MAX_LAYERS) */
+    int width[ICNN_BE_MAX_LAYERS];      /* s_0 .. s_L, s_L == 1 */
+    int head;                           /* ICNN_BE_FICNN_HEAD_* */
+    int ctx_width;                      /* floats per context row (checked against the shape) */
+    const float *wpack;                 /* packed weights, icnn_be_ficnn_pack_floats() floats */
+} icnn_be_ficnn_model;
+
+/* Number of floats of the packed weight buffer (0 if the shape is rejected: layer count, widths, head, ctx_width, or an
+ * evaluation tile that does not fit the LDS).  Host arithmetic. */
+ICNN_BE_API size_t icnn_be_ficnn_pack_floats(const icnn_be_ficnn_model *shape);
+
+/*
+ * Pack every weight the FICNN kernels read (host -> host; upload the result and store the device pointer in
+ * model->wpack): w_x_host[i] = 'z_x{i}/W' [n_features + n][width[i]], b_host[i] = 'z_x{i}/b' [width[i]], w_z_host[i]
+ * (i >= 1) = 'z_z{i}_proj/W' [width[i-1]][width[i]], row-major float32 as tflearn stores them.  The head layer's
+ * pointers (i = L) are read only for head LINEAR and may be NULL for head SUM.  Every packed float is a copy of one
+ * parameter element or zero (padding).
+ */
+ICNN_BE_API int icnn_be_ficnn_pack(const icnn_be_ficnn_model *shape, const float *const *w_x_host, const float *const *b_host,
+                                   const float *const *w_z_host, float *out_host);
+
+/* floats of device scratch icnn_be_ficnn_context needs for a batch (0: rejected) */
+ICNN_BE_API size_t icnn_be_ficnn_context_work_floats(const icnn_be_ficnn_model *model, int batch);
+
+/*
+ * ctx[batch][ctx_width] from x[batch][n_features] (float32): c_i = x W_x_i[:n_features] + b_i for every layer the head
+ * evaluates, one f32-MFMA GEMM against the concatenated x rows of those layers plus the bias row.  work:
+ * icnn_be_ficnn_context_work_floats(model, batch) floats.  No host synchronisation (capturable).
+ */
+ICNN_BE_API int icnn_be_ficnn_context(const icnn_be_ficnn_model *model, const float *x, int batch, float *ctx, float *work,
+                                      void *stream);
+
+/*
+ * E[B] and dE/dy[B][n] (float32) of the FICNN at y (float64, rounded to float32 on entry like a TensorFlow feed):
+ * what sess.run(tf.gradients(E_, y_)) evaluates in synthetic-cls/icnn.py:125 (tf.gradients sums over the [B, width[L-1]]
+ * outputs of head SUM).  ctx[B][ctx_width] is the x-only part.  Rows whose finished[u] != 0 are left untouched
+ * (finished may be NULL).  One workgroup per 16 samples, f32 MFMA.
+ */
+ICNN_BE_API int icnn_be_ficnn_fg(const icnn_be_ficnn_model *model, const float *ctx, const double *y, int batch, float *f,
+                                 float *g, const int *finished, void *stream);
+
+/*
+ * n_iter steps of momentum gradient descent on y for the FICNN: the recurrence, float32 arithmetic, arguments, outputs and
+ * errors of icnn_be_fc_gd (workspace: icnn_be_gd_workspace_bytes(batch, n)), synthetic-cls/icnn.py:117-131.  One
+ * persistent launch, a workgroup per 16 samples; bit-identical to a loop of icnn_be_ficnn_fg plus the float32 update.
+ */
+ICNN_BE_API int icnn_be_ficnn_gd(const icnn_be_ficnn_model *model, const float *ctx, const double *y0, int batch, int n_iter,
+                                 double lr, double momentum, double *y_out, double *traj, float *f_out, void *workspace,
+                                 void *stream);
+
+/*
+ * solveBatch on the device for a FICNN energy: the rounds of { icnn_be_ficnn_fg ; dual step } with the scheduling of
+ * icnn_be_solve_conv (lockstep unless ICNN_BE_FLAG_TIME_SLICE).  f_work[B], g_work[B][n] are scratch; the state must
+ * have been reset with icnn_be_state_init and st->cut_dtype must be F32.  Returns the number of rounds issued (> 0) or
+ * a negative error code.
+ */
+ICNN_BE_API int icnn_be_solve_ficnn(const icnn_be_ficnn_model *model, const float *ctx, const icnn_be_state *st,
+                                    float *f_work, float *g_work, void *stream);
+
+/*
+ * Floats of the packed parameter gradient of a FICNN (0: shape rejected; host arithmetic).  For i = 0 .. L, in the order
+ * of tf.trainable_variables() in synthetic-cls/icnn.py:213-234 (icnn_amd.ficnn.init_params):
+ *   'z_x{i}/W' [n_features + n][width[i]], 'z_x{i}/b' [width[i]], 'z_z{i}_proj/W' [width[i-1]][width[i]] (i > 0 only)
+ * With head SUM the head layer's variables do not reach E (compute_gradients returns None, :137-139): their gradient is 0.
+ */
+ICNN_BE_API size_t icnn_be_ficnn_grad_floats(const icnn_be_ficnn_model *model);
+
+/* floats of device scratch icnn_be_ficnn_surrogate_grad needs for `batch` samples and `rows` rows (0: rejected) */
+ICNN_BE_API size_t icnn_be_ficnn_surrogate_grad_work_floats(const icnn_be_ficnn_model *model, int batch, int rows);
+
+/*
+ * grad = d/dtheta  sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ]  over every variable, float32, packed as
+ * icnn_be_ficnn_grad_floats describes; the arguments are those of icnn_be_fc_surrogate_grad (row_offset, y, v, c, F_rows,
+ * v may be NULL).  With c = 0 and v_k = coefficient_k dL/dy_K over the trajectory of icnn_be_ficnn_gd it is the gradient
+ * of L(y_K) through the unrolled inference (synthetic-cls/icnn.py:133-139).  Deterministic (no atomics), no host
+ * synchronisation (capturable).  ICNN_BE_EINVAL / ICNN_BE_ELIMIT for a bad shape or a NULL required pointer before
+ * anything is launched.
+ */
+ICNN_BE_API int icnn_be_ficnn_surrogate_grad(const icnn_be_ficnn_model *model, const float *x, int batch, const int *row_offset,
+                                             int rows, const double *y, const double *v, const double *cvec, float *grad,
+                                             float *F_rows, float *work, void *stream);
 
 /* ---- convolutional PICNN (completion/icnn_ebundle.py) ---------------------------------------- */
 
