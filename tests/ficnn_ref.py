@@ -66,3 +66,20 @@ def wide_params(spec, seed, scale=1.0):
         else:
             p[name] = (rng.randn(*shape) * scale / np.sqrt(shape[0])).astype(np.float32)
     return p
+
+
+def surrogate_grad64(spec, params, x, counts, y, v, c):
+    """float64 autograd of F = sum_r c_r E_r + <dE/dy_r, v_r> over every variable, rows of sample j repeated counts[j]
+    times (v None: no tangent term).  Returns (gradient {name: ndarray}, F_r [R])."""
+    theta = {k: torch.tensor(np.asarray(p, np.float64), requires_grad=True) for k, p in params.items()}
+    X = torch.tensor(np.repeat(np.asarray(x, np.float64), counts, axis=0))
+    Y = torch.tensor(np.asarray(y, np.float64), requires_grad=True)
+    E, _ = energy(spec, theta, X, Y)
+    F = torch.tensor(np.asarray(c, np.float64)) * E
+    if v is not None:
+        g, = torch.autograd.grad(E.sum(), Y, create_graph=True)
+        F = F + (g * torch.tensor(np.asarray(v, np.float64))).sum(1)
+    names = list(theta)
+    gs = torch.autograd.grad(F.sum(), [theta[k] for k in names], allow_unused=True)
+    out = {k: (np.zeros(params[k].shape) if gg is None else gg.numpy()) for k, gg in zip(names, gs)}
+    return out, F.detach().numpy()

@@ -12,6 +12,7 @@ import torch
 import bn_ref
 import train_conv_ref
 import train_ref
+from gemm_ref import MAX_SPLITS, gemm_splits
 from gpu_util import compare_with_oracle, result_to_host
 from icnn_amd import picnn
 from test_train_grad_conv import BN_TOL, MARGIN, ZERO_VARS
@@ -31,23 +32,6 @@ FC_CASES = {
     "box_depth4": FC(20, 12, (30, 20, 16), alpha=0.01, batchnorm=True, action_box=True),
     "box_L1": FC(17, 6, (24,), alpha=0.01, batchnorm=False, action_box=True),
 }
-# be_train_common.hip: 64 x 64 output tiles, K in steps of 16, at most 32 splits
-GBM = GBN = 64
-GBK = 16
-MAX_SPLITS = 32
-
-
-def gemm_splits(M, N, K):
-    """(splits, kchunk) of be_train_common.hip's gemm_splits, restated"""
-    tiles = -(-M // GBM) * -(-N // GBN)
-    splits = 1
-    if tiles < 256 and K > 64:
-        splits = min(-(-256 // tiles), -(-K // 64), MAX_SPLITS)
-    kchunk = -(-K // splits)
-    kchunk = max(-(-kchunk // GBK) * GBK, GBK)
-    return (-(-K // kchunk) if K > 0 else 1), kchunk
-
-
 def _perturbed(params, rng):
     for k in params:                             # non-trivial BatchNorm parameters and biases
         if k.endswith("/bn/gamma") or k.endswith("/bn/beta") or k.endswith("/b"):

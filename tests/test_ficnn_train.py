@@ -49,22 +49,6 @@ def test_unrolled_gradient_is_one_surrogate_over_the_trajectory(head, K):
 F32 = 2.0 ** -24
 
 
-def _grad64(spec, params, x, counts, y, v, c):
-    theta = {k: torch.tensor(np.asarray(p, np.float64), requires_grad=True) for k, p in params.items()}
-    X = torch.tensor(np.repeat(x.astype(np.float64), counts, axis=0))
-    Y = torch.tensor(y, requires_grad=True)
-    E, _ = ficnn_ref.energy(spec, theta, X, Y)
-    F = (torch.tensor(c) * E).sum()
-    if v is not None:
-        g, = torch.autograd.grad(E.sum(), Y, create_graph=True)
-        F = F + (g * torch.tensor(v)).sum()
-    names = list(theta)
-    gs = torch.autograd.grad(F, [theta[k] for k in names], allow_unused=True)
-    out = {k: (np.zeros(params[k].shape) if gg is None else gg.numpy()) for k, gg in zip(names, gs)}
-    ta = {k: t.detach().abs() for k, t in theta.items()}
-    return out, ta
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("head", ["sum", "linear"])
 @pytest.mark.parametrize("with_v", [False, True])
@@ -78,7 +62,7 @@ def test_surrogate_grad_against_float64(head, with_v):
     y = rng.rand(R, 4).astype(np.float32).astype(np.float64)
     v = rng.randn(R, 4) if with_v else None
     c = rng.randn(R)
-    ref, _ = _grad64(spec, params, x, counts, y, v, c)
+    ref, _ = ficnn_ref.surrogate_grad64(spec, params, x, counts, y, v, c)
     model = ficnn.FICNNModel(spec, params)
     off = torch.tensor(np.r_[0, np.cumsum(counts)], dtype=torch.int32, device="cuda")
     rows = (torch.from_numpy(y).cuda(), None if v is None else torch.from_numpy(v).cuda(), torch.from_numpy(c).cuda())

@@ -35,6 +35,24 @@ def _flat(spec, params):
     return np.concatenate([np.asarray(params[k], np.float32).reshape(-1) for k, _ in train.grad_layout(spec)])
 
 
+TD_THREADS = 256                             # be_rl_train.hip
+
+
+def rl_td_blocks(n_theta):
+    """be_rl_train.hip rl_td_blocks: four grid strides per thread, 1 .. ICNN_BE_RL_TD_MAX_BLOCKS workgroups"""
+    return max(1, min(-(-n_theta // (TD_THREADS * 4)), _lib.RL_TD_MAX_BLOCKS))
+
+
+def _n_theta(spec):
+    return sum(int(np.prod(s)) for _, s in train.grad_layout(spec))
+
+
+# the critics of the TD cases: one workgroup, the default grid, and a grid capped at ICNN_BE_RL_TD_MAX_BLOCKS
+TD_CRITICS = {"one_block": (5,), "default": (200, 200), "capped": (200, 200, 200)}
+# critics whose n_theta % 4 is 0 and 2 (the halfcheetah ones give 1 and 3): a partial last group of four in the update
+UPDATE_SPECS = {"mod4_0": dict(n_labels=7), "mod4_2": dict(n_labels=5)}
+
+
 # ------------------------------------------------------------------------------------------------ CPU
 
 
@@ -146,6 +164,17 @@ def test_closed_form_gradient_equals_autograd_of_the_loss(batchnorm):
     assert np.allclose(c, c64, rtol=1e-6, atol=1e-9)
 
 
+def test_td_cases_reach_the_grids_they_claim():
+    grids = {k: rl_td_blocks(_n_theta(_critic_spec(szs=szs))) for k, szs in TD_CRITICS.items()}
+    assert _lib.RL_TD_MAX_BLOCKS == 256 and grids == {"one_block": 1, "default": 209, "capped": 256}
+    n = _n_theta(_critic_spec(szs=TD_CRITICS["one_block"]))
+    assert TD_THREADS < n <= TD_THREADS * 4                       # one workgroup, some of its threads take a second stride
+    n = _n_theta(_critic_spec(szs=TD_CRITICS["capped"]))
+    assert n > 4 * TD_THREADS * _lib.RL_TD_MAX_BLOCKS              # the capped grid: threads past four strides
+    assert _n_theta(_critic_spec()) % 4 in (1, 3)
+    assert sorted(_n_theta(dataclasses.replace(_critic_spec(), **kw)) % 4 for kw in UPDATE_SPECS.values()) == [0, 2]
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 
 
@@ -167,11 +196,9 @@ def _minibatch(spec, B, seed):
     return obs, act, rew, ob2, term
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("with_act2", [False, True])
-def test_rl_td_matches_numpy(with_act2):
-    spec, B = _critic_spec(), 256
+def _check_td(spec, B, with_act2):
     tr = _trainer(spec, B, 1)
+    assert tr.opt.n == _n_theta(spec)
     obs, act, rew, ob2, term = _minibatch(spec, B, 2)
     rng = np.random.RandomState(4)
     e = (rng.randn(B) * 3).astype(np.float32)
@@ -184,7 +211,8 @@ def test_rl_td_matches_numpy(with_act2):
     tr.td_loss(torch.from_numpy(e).cuda(), torch.from_numpy(q2).cuda(), a2)
     torch.cuda.synchronize()
     q, y, td, c = ref.td(e, act, rew, term, q2, act2, DISCOUNT, B)
-    assert (y == q + np.float32(1)).any() and (y == q - np.float32(1)).any() and term.any()
+    if B >= 255:
+        assert (y == q + np.float32(1)).any() and (y == q - np.float32(1)).any() and term.any()
     got_td = tr.td.cpu().numpy()
     ulp = np.spacing(np.maximum(np.abs(q), np.abs(td)).astype(np.float32))
     assert np.all(np.abs(got_td - td) <= 2 * ulp)          # entropy's log may differ by an ulp
@@ -195,6 +223,26 @@ def test_rl_td_matches_numpy(with_act2):
     first = tr.loss.clone()
     tr.td_loss(torch.from_numpy(e).cuda(), torch.from_numpy(q2).cuda(), a2)   # the ticket was re-armed; repeatable
     assert torch.equal(first, tr.loss)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_act2", [False, True])
+def test_rl_td_matches_numpy(with_act2):
+    spec = _critic_spec()
+    assert rl_td_blocks(_n_theta(spec)) == 209
+    _check_td(spec, 256, with_act2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_act2", [False, True], ids=["q2", "act2"])
+@pytest.mark.parametrize("B", [1, 255, 257, 1000])
+@pytest.mark.parametrize("critic", list(TD_CRITICS))
+def test_rl_td_at_every_grid_and_batch(critic, B, with_act2):
+    """a one-workgroup grid, the default one and the capped one (threads past four strides), each at batches of one, on
+    either side of a TD_THREADS multiple and past several of them"""
+    spec = _critic_spec(szs=TD_CRITICS[critic])
+    assert rl_td_blocks(_n_theta(spec)) == {"one_block": 1, "default": 209, "capped": 256}[critic]
+    _check_td(spec, B, with_act2)
 
 
 def _set_state(tr, rng, step):
@@ -212,10 +260,7 @@ def _set_state(tr, rng, step):
     return theta, theta_t, m, v, g
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("batchnorm", [False, True])
-def test_rl_critic_update_matches_numpy_bit_for_bit(batchnorm):
-    spec = _critic_spec(batchnorm, szs=(200, 200, 200) if batchnorm else (200, 200))
+def _check_critic_update(spec):
     tr = _trainer(spec, 8, 3)
     rng = np.random.RandomState(5)
     theta, theta_t, m, v, g = _set_state(tr, rng, 4)
@@ -230,6 +275,20 @@ def test_rl_critic_update_matches_numpy_bit_for_bit(batchnorm):
     assert tr.opt.step_count.cpu().tolist() == [4, 0]
     assert np.array_equal(_bits(tr.opt.arena.cpu().numpy()), _bits(tr.opt.map.scatter(th_r)))
     assert np.array_equal(_bits(tr.follower.arena.cpu().numpy()), _bits(tr.opt.map.scatter(tt_r)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batchnorm", [False, True])
+def test_rl_critic_update_matches_numpy_bit_for_bit(batchnorm):
+    _check_critic_update(_critic_spec(batchnorm, szs=(200, 200, 200) if batchnorm else (200, 200)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", list(UPDATE_SPECS))
+def test_rl_critic_update_bit_for_bit_at_other_remainders(which):
+    spec = dataclasses.replace(_critic_spec(), **UPDATE_SPECS[which])
+    assert _n_theta(spec) % 4 == {"mod4_0": 0, "mod4_2": 2}[which]
+    _check_critic_update(spec)
 
 
 @pytest.mark.gpu
