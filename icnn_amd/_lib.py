@@ -59,6 +59,9 @@ EXPORTS = [
     "icnn_be_ficnn_pack_floats", "icnn_be_ficnn_pack", "icnn_be_ficnn_context_work_floats", "icnn_be_ficnn_context",
     "icnn_be_ficnn_fg", "icnn_be_ficnn_gd", "icnn_be_solve_ficnn", "icnn_be_ficnn_grad_floats",
     "icnn_be_ficnn_surrogate_grad_work_floats", "icnn_be_ficnn_surrogate_grad",
+    "icnn_be_feed_plan_work_bytes", "icnn_be_feed_plan", "icnn_be_feed_pad", "icnn_be_fc_surrogate_grad_dev",
+    "icnn_be_conv_surrogate_grad_dev", "icnn_be_fc_context_bn_dev", "icnn_be_conv_context_bn_dev",
+    "icnn_be_fc_surrogate_grad_dev_work_floats", "icnn_be_conv_surrogate_grad_dev_work_floats",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -275,6 +278,28 @@ def load():
     lib.icnn_be_conv_surrogate_grad_bn.argtypes = (lib.icnn_be_conv_surrogate_grad.argtypes[:-1]
                                                    + [C.POINTER(BnMoving), C.c_int, C.c_void_p])
     lib.icnn_be_conv_surrogate_grad_bn.restype = C.c_int
+    lib.icnn_be_fc_surrogate_grad_dev.argtypes = (lib.icnn_be_fc_surrogate_grad.argtypes[:-1]
+                                                  + [C.POINTER(BnMoving), C.c_int, C.c_void_p, C.c_void_p])
+    lib.icnn_be_fc_surrogate_grad_dev.restype = C.c_int
+    lib.icnn_be_conv_surrogate_grad_dev.argtypes = (lib.icnn_be_conv_surrogate_grad.argtypes[:-1]
+                                                    + [C.POINTER(BnMoving), C.c_int, C.c_void_p, C.c_void_p])
+    lib.icnn_be_conv_surrogate_grad_dev.restype = C.c_int
+    lib.icnn_be_fc_context_bn_dev.argtypes = [C.POINTER(FcCtx), C.POINTER(BnMoving), C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_fc_context_bn_dev.restype = C.c_int
+    lib.icnn_be_conv_context_bn_dev.argtypes = [C.POINTER(ConvModel), C.POINTER(ConvCtx), C.POINTER(BnMoving), C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.icnn_be_conv_context_bn_dev.restype = C.c_int
+    lib.icnn_be_feed_plan_work_bytes.argtypes = [C.c_int]
+    lib.icnn_be_feed_plan_work_bytes.restype = C.c_size_t
+    lib.icnn_be_fc_surrogate_grad_dev_work_floats.argtypes = lib.icnn_be_fc_surrogate_grad_work_floats.argtypes
+    lib.icnn_be_fc_surrogate_grad_dev_work_floats.restype = C.c_size_t
+    lib.icnn_be_conv_surrogate_grad_dev_work_floats.argtypes = lib.icnn_be_conv_surrogate_grad_work_floats.argtypes
+    lib.icnn_be_conv_surrogate_grad_dev_work_floats.restype = C.c_size_t
+    lib.icnn_be_feed_plan.argtypes = [C.POINTER(State), C.c_void_p, C.c_int] + [C.c_void_p] * 6
+    lib.icnn_be_feed_plan.restype = C.c_int
+    lib.icnn_be_feed_pad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.icnn_be_feed_pad.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
     lib.icnn_be_gd_workspace_bytes.argtypes = [C.c_int, C.c_int]

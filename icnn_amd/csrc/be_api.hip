@@ -347,17 +347,31 @@ size_t icnn_be_fc_context_bn_work_floats(const icnn_be_fc_ctx *c, int batch) {
     return icnn_be::ctx_bn_work_floats(*c, batch);
 }
 
-int icnn_be_fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode, int updates, const float *x,
-                          int batch, float *ctx, int ctx_width, float *work, void *stream) {
+namespace {
+int fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode, int updates, const int *updates_dev,
+                  const float *x, int batch, float *ctx, int ctx_width, float *work, void *stream) {
     if (!c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
     int n[ICNN_BE_MAX_LAYERS];
     icnn_be::fc_bn_widths(*c, n);
-    if (int rc = check_bn_mode(mv, mode, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
+    /* a device count may be anything: the arguments a fold needs are checked as for one update */
+    if (int rc = check_bn_mode(mv, mode, updates_dev ? 1 : updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (batch == 0) return 0;
     hipError_t e = icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream), mv, mode,
-                                              updates);
+                                              updates, updates_dev);
     return e == hipSuccess ? 0 : fail(e);
+}
+}  // namespace
+
+int icnn_be_fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode, int updates, const float *x,
+                          int batch, float *ctx, int ctx_width, float *work, void *stream) {
+    return fc_context_bn(c, mv, mode, updates, nullptr, x, batch, ctx, ctx_width, work, stream);
+}
+
+int icnn_be_fc_context_bn_dev(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, const int *updates_dev, const float *x,
+                              int batch, float *ctx, int ctx_width, float *work, void *stream) {
+    if (!updates_dev) return ICNN_BE_EINVAL;
+    return fc_context_bn(c, mv, ICNN_BE_BN_BATCH, 0, updates_dev, x, batch, ctx, ctx_width, work, stream);
 }
 
 size_t icnn_be_fc_grad_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c) {
@@ -380,6 +394,14 @@ int icnn_be_fc_surrogate_grad_bn(const icnn_be_fc_model *model, const icnn_be_fc
                                  const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                  float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
                                  void *stream) {
+    return icnn_be_fc_surrogate_grad_dev(model, c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work, mv, updates,
+                                         nullptr, stream);
+}
+
+int icnn_be_fc_surrogate_grad_dev(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                                  const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                  float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
+                                  const int *rows_dev, void *stream) {
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ctx_check(*c)) return rc;
     int n[ICNN_BE_MAX_LAYERS];
@@ -387,8 +409,19 @@ int icnn_be_fc_surrogate_grad_bn(const icnn_be_fc_model *model, const icnn_be_fc
     if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (int rc = icnn_be::fc_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                     static_cast<hipStream_t>(stream), mv, updates);
+                                                     static_cast<hipStream_t>(stream), mv, updates, rows_dev);
     return e == hipSuccess ? 0 : fail(e);
+}
+
+size_t icnn_be_fc_surrogate_grad_dev_work_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, int batch, int rows) {
+    if (!model || !c) return 0;
+    return icnn_be::fc_surrogate_work_floats(*model, *c, batch, rows, true);
+}
+
+size_t icnn_be_conv_surrogate_grad_dev_work_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, int batch,
+                                                   int rows) {
+    if (!model || !c) return 0;
+    return icnn_be::conv_surrogate_work_floats(*model, *c, batch, rows, true);
 }
 
 size_t icnn_be_conv_grad_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c) {
@@ -412,6 +445,14 @@ int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, const icnn_b
                                    const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                    float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
                                    void *stream) {
+    return icnn_be_conv_surrogate_grad_dev(model, c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work, mv, updates,
+                                           nullptr, stream);
+}
+
+int icnn_be_conv_surrogate_grad_dev(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x, int batch,
+                                    const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
+                                    float *grad, float *F_rows, float *work, const icnn_be_bn_moving *mv, int updates,
+                                    const int *rows_dev, void *stream) {
     if (!model || !c || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::conv_ctx_check(*c)) return rc;
     icnn_be::ConvCtxShape g{};
@@ -421,7 +462,7 @@ int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, const icnn_b
     if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, 4)) return rc;
     if (int rc = icnn_be::conv_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
     hipError_t e = icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                       static_cast<hipStream_t>(stream), mv, updates);
+                                                       static_cast<hipStream_t>(stream), mv, updates, rows_dev);
     return e == hipSuccess ? 0 : fail(e);
 }
 
@@ -510,6 +551,27 @@ int icnn_be_implicit_feed(const icnn_be_state *st, const double *y_true, int los
     return e == hipSuccess ? 0 : fail(e);
 }
 
+size_t icnn_be_feed_plan_work_bytes(int batch) { return batch < 0 ? 0 : icnn_be::feed_plan_work_bytes(batch); }
+
+int icnn_be_feed_plan(const icnn_be_state *st, const double *y_true, int loss, int *row_offset, int *counts,
+                      double *loss_out, int *tallies, void *work, void *stream) {
+    if (int rc = check_state(st)) return rc;
+    if (!y_true || !row_offset || !counts || !loss_out || !work) return ICNN_BE_EINVAL;
+    if (loss != ICNN_BE_LOSS_XENT && loss != ICNN_BE_LOSS_MSE) return ICNN_BE_EINVAL;
+    if (st->batch == 0) return 0;
+    icnn_be::FeedPlanLaunch l{*st, y_true, loss, row_offset, counts, loss_out, tallies, work};
+    hipError_t e = icnn_be::launch_feed_plan(l, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c, int *fd_sample,
+                     void *stream) {
+    if (!rows || !fd_y || !fd_v || !fd_c || !fd_sample || batch < 1 || n < 1 || row_cap < 0) return ICNN_BE_EINVAL;
+    if (row_cap == 0) return 0;
+    hipError_t e = icnn_be::launch_feed_pad(rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
                           double *lam_rows, void *stream) {
     if (int rc = check_state(st)) return rc;
@@ -595,18 +657,32 @@ size_t icnn_be_conv_context_bn_work_floats(const icnn_be_conv_model *shape, int 
     return icnn_be::conv_ctx_bn_work_floats(g, batch);
 }
 
-int icnn_be_conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv, int mode,
-                            int updates, const float *x, int batch, float *ctx, float *work, void *stream) {
+namespace {
+int conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv, int mode,
+                    int updates, const int *updates_dev, const float *x, int batch, float *ctx, float *work, void *stream) {
     if (!shape || !c || !x || !ctx || !work || batch < 0) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::conv_ctx_check(*c)) return rc;
     icnn_be::ConvCtxShape g{};
     if (int rc = icnn_be::conv_ctx_shape(*shape, g)) return rc;
     int n[4];
     icnn_be::conv_bn_widths(g, n);
-    if (int rc = check_bn_mode(mv, mode, updates, n, 4)) return rc;
+    if (int rc = check_bn_mode(mv, mode, updates_dev ? 1 : updates, n, 4)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates);
+    hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates,
+                                                updates_dev);
     return e == hipSuccess ? 0 : fail(e);
+}
+}  // namespace
+
+int icnn_be_conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv, int mode,
+                            int updates, const float *x, int batch, float *ctx, float *work, void *stream) {
+    return conv_context_bn(shape, c, mv, mode, updates, nullptr, x, batch, ctx, work, stream);
+}
+
+int icnn_be_conv_context_bn_dev(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, const icnn_be_bn_moving *mv,
+                                const int *updates_dev, const float *x, int batch, float *ctx, float *work, void *stream) {
+    if (!updates_dev) return ICNN_BE_EINVAL;
+    return conv_context_bn(shape, c, mv, ICNN_BE_BN_BATCH, 0, updates_dev, x, batch, ctx, work, stream);
 }
 
 int icnn_be_conv_clamp(const icnn_be_conv_model *model, int mode, void *stream) {

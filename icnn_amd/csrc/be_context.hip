@@ -327,6 +327,8 @@ struct BnFoldArgs {
     int N[ICNN_BE_MAX_LAYERS];
     float d;                                     // 1 - decay
     int updates;
+    const int *updates_dev;                      // not NULL: the fold count is read from the device (0 .. ICNN_BE_MAX_ITERS)
+    const int *gate_dev;                         // not NULL: no fold at all when *gate_dev <= 0 (a feed without rows)
 };
 __global__ void bn_fold_kernel(BnFoldArgs a) {
 #pragma clang fp contract(off)
@@ -334,7 +336,9 @@ __global__ void bn_fold_kernel(BnFoldArgs a) {
     if (col >= N) return;
     const float mu = a.stat[l][col], s2 = a.stat[l][N + col];
     float m = a.mean[l][col], v = a.var[l][col];
-    for (int k = 0; k < a.updates; ++k) {
+    int updates = a.updates_dev ? min(max(*a.updates_dev, 0), ICNN_BE_MAX_ITERS) : a.updates;
+    if (a.gate_dev && *a.gate_dev <= 0) updates = 0;
+    for (int k = 0; k < updates; ++k) {
         m = m - (m - mu) * a.d;
         v = v - (v - s2) * a.d;
     }
@@ -402,7 +406,7 @@ size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch) {
 }
 
 hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const int *n, int nl, int updates,
-                          hipStream_t stream) {
+                          hipStream_t stream, const int *updates_dev, const int *gate_dev) {
     BnFoldArgs a{};
     int most = 0;
     for (int l = 0; l < nl; ++l) {
@@ -411,7 +415,9 @@ hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const
     }
     a.d = 1.f - mv.decay;                  // float32(1 - decay), as tf.convert_to_tensor(1 - decay) in assign_moving_average
     a.updates = updates;
-    if (updates == 0 || most == 0) return hipSuccess;
+    a.updates_dev = updates_dev;
+    a.gate_dev = gate_dev;
+    if ((updates == 0 && !updates_dev) || most == 0) return hipSuccess;
     return launch_kernel(bn_fold_kernel, dim3((most + 255) / 256, nl), dim3(256), 0, stream, a);
 }
 
@@ -469,14 +475,15 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
     return launch_kernel(ctx_gemm_kernel, dim3((batch + BM - 1) / BM, (a.N + BN - 1) / BN), dim3(GT), 0, stream, a);
 }
 
-// mode ICNN_BE_BN_BATCH: batch statistics, folded `updates` times into *mv (work: ctx_bn_work_floats when updates > 0);
+// mode ICNN_BE_BN_BATCH: batch statistics, folded `updates` times into *mv (work: ctx_bn_work_floats when updates > 0), or
+// *updates_dev times when that device pointer is given;
 // ICNN_BE_BN_MOVING: the moving statistics of *mv (arguments checked by the caller)
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
-                             hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates) {
+                             hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates, const int *updates_dev) {
     const int L = c.n_layers - 1;
     int n[ICNN_BE_MAX_LAYERS];
     fc_bn_widths(c, n);
-    float *stats = c.batchnorm && updates > 0 ? work + ctx_work_floats(c, batch) : nullptr, *stat[ICNN_BE_MAX_LAYERS] = {};
+    float *stats = c.batchnorm && (updates > 0 || updates_dev) ? work + ctx_work_floats(c, batch) : nullptr, *stat[ICNN_BE_MAX_LAYERS] = {};
     for (int i = 0; i <= L; ++i) {
         hipError_t e = launch_fc_context_stage(c, i, x, batch, ctx, ctx_width, work, stream);
         if (e != hipSuccess) return e;
@@ -494,7 +501,7 @@ hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch,
             if (e != hipSuccess) return e;
         }
     }
-    return stats ? launch_bn_fold(*mv, stat, n, L > 1 ? L - 1 : 0, updates, stream) : hipSuccess;
+    return stats ? launch_bn_fold(*mv, stat, n, L > 1 ? L - 1 : 0, updates, stream, updates_dev) : hipSuccess;
 }
 
 // statistics of stage i's u (this rank's rows) -> stats[2][width_i] float64; 1 = the stage has no BatchNorm (nothing written)
@@ -590,11 +597,12 @@ hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_c
 }
 
 hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
-                               float *work, hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates) {
+                               float *work, hipStream_t stream, const icnn_be_bn_moving *mv, int mode, int updates,
+                               const int *updates_dev) {
     float *part = conv_ctx_u(g, batch, work, 4);
     int n[4];
     conv_bn_widths(g, n);
-    float *stats = updates > 0 ? work + conv_ctx_work_floats(g, batch) : nullptr, *stat[4] = {};
+    float *stats = updates > 0 || updates_dev ? work + conv_ctx_work_floats(g, batch) : nullptr, *stat[4] = {};
     auto bn = [&](float *u, int ld, int rows, int cols, int i) -> hipError_t {
         if (mode == ICNN_BE_BN_MOVING)
             return launch_bn_affine(u, ld, rows, cols, mv->mean[i], mv->var[i], c.bn_gamma[i], c.bn_beta[i], c.bn_eps, stream);
@@ -619,7 +627,7 @@ hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c,
         else if (stage == 4) e = bn(conv_ctx_u(g, batch, work, 2), g.F[2], batch * g.P[2], g.F[2], 2);
         else if (stage == 5) e = bn(conv_ctx_u(g, batch, work, 3), (g.fch + 3) & ~3, batch, g.fch, 3);
     }
-    if (e == hipSuccess && stats) e = launch_bn_fold(*mv, stat, n, 4, updates, stream);
+    if (e == hipSuccess && stats) e = launch_bn_fold(*mv, stat, n, 4, updates, stream, updates_dev);
     return e;
 }
 

@@ -102,12 +102,13 @@ void fc_bn_widths(const icnn_be_fc_ctx &c, int *n);
 // defaults are icnn_be_fc_context
 hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch, float *ctx, int ctx_width, float *work,
                              hipStream_t stream, const icnn_be_bn_moving *mv = nullptr, int mode = ICNN_BE_BN_BATCH,
-                             int updates = 0);
+                             int updates = 0, const int *updates_dev = nullptr);
 size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch);
 // `updates` folds of stat[l] (mean [n[l]] then biased variance [n[l]], device) into mv's layers 0 .. nl-1 (n[l] = 0: none),
-// one launch; and inference-mode BatchNorm in place on u[rows][ld], columns [0, cols)
+// one launch; and inference-mode BatchNorm in place on u[rows][ld], columns [0, cols).  updates_dev (device int32, may be
+// NULL) replaces `updates` by a count read on the device; gate_dev (may be NULL): no fold when *gate_dev <= 0
 hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const int *n, int nl, int updates,
-                          hipStream_t stream);
+                          hipStream_t stream, const int *updates_dev = nullptr, const int *gate_dev = nullptr);
 hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
                             const float *beta, float eps, hipStream_t stream);
 hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *x, int batch, float *ctx, int ctx_width,
@@ -128,7 +129,7 @@ int conv_ctx_shape(const icnn_be_conv_model &m, ConvCtxShape &g);
 size_t conv_ctx_work_floats(const ConvCtxShape &g, int batch);
 hipError_t launch_conv_context(const ConvCtxShape &g, const icnn_be_conv_ctx &c, const float *x, int batch, float *ctx,
                                float *work, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr,
-                               int mode = ICNN_BE_BN_BATCH, int updates = 0);
+                               int mode = ICNN_BE_BN_BATCH, int updates = 0, const int *updates_dev = nullptr);
 size_t conv_ctx_bn_work_floats(const ConvCtxShape &g, int batch);
 // one stage's GEMM of launch_conv_context (u-maps ReLU'd but not normalised); conv_ctx_u: u_l (l = 0..3) inside `work`
 hipError_t launch_conv_context_stage(const ConvCtxShape &g, const icnn_be_conv_ctx &c, int stage, const float *x, int batch,
@@ -139,18 +140,22 @@ hipError_t launch_conv_clamp(const icnn_be_conv_model &m, int mode, hipStream_t 
 
 // training gradient of the FC PICNN (be_train_fc.hip): sizes (0 = shape rejected), shape check, launcher
 size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c);
-size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows);
+// dev: the size of the device-count variant (rows_dev != NULL), whose forward products keep partials for any plan
+size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool dev = false);
 int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool with_v);
 hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                     float *grad, float *F_rows, float *work, hipStream_t stream,
-                                    const icnn_be_bn_moving *mv = nullptr, int updates = 0);
+                                    const icnn_be_bn_moving *mv = nullptr, int updates = 0, const int *rows_dev = nullptr);
 // shared by both training units (be_train_common.hip).  The strided f32-MFMA GEMM: C[M][N] (pitch ldc) = A B,
 // A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn], split-K into `part` (tr_gemm_part_floats(M, N, K) floats) and summed
 // in split order -- no atomics
-size_t tr_gemm_part_floats(int M, int N, int K);
+// rows_dev (device int32, may be NULL) with m_per_row: the split-K plan of the product with m_per_row x *rows_dev rows is
+// formed on the device (the bits of the compact call on the rows both share); part then holds tr_gemm_part_floats(M, N, K, true)
+size_t tr_gemm_part_floats(int M, int N, int K, bool dev_plan = false);
 hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
-                          int K, float *C, long long ldc, float *part, hipStream_t stream);
+                          int K, float *C, long long ldc, float *part, hipStream_t stream, const int *rows_dev = nullptr,
+                          int m_per_row = 0);
 // the feed's rows: samp[r] = the sample of row r, mult[j] = the row count of sample j (a float); out [B][C] = the rows
 // [R][C] of each sample summed in row order
 hipError_t launch_tr_rows(const int *row_offset, int B, int R, int *samp, float *mult, hipStream_t stream);
@@ -158,12 +163,12 @@ hipError_t launch_tr_segment_sum(const float *rows, const int *row_offset, int B
 
 // training gradient of the conv PICNN (be_train_conv.hip), as the FC one above
 size_t conv_grad_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c);
-size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows);
+size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows, bool dev = false);
 int conv_surrogate_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows, bool with_v);
 hipError_t launch_conv_surrogate_grad(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, const float *x, int batch,
                                       const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                       float *grad, float *F_rows, float *work, hipStream_t stream,
-                                      const icnn_be_bn_moving *mv = nullptr, int updates = 0);
+                                      const icnn_be_bn_moving *mv = nullptr, int updates = 0, const int *rows_dev = nullptr);
 
 // LDS layouts of the persistent kernels (be_fused.hip), host arithmetic only.  false: the shape does not fit that kernel.
 // The solve plan (be_api.hip) and the launchers below take their fit decisions from these two functions alone.
@@ -237,6 +242,21 @@ int conv_pack(const icnn_be_conv_model &m, const float *const *w_yu, const float
               float *out);
 hipError_t launch_conv_fg(const icnn_be_conv_model &m, const float *ctx, const double *y, int batch, float *f,
                           float *g, const int *skip, hipStream_t stream);
+
+// ---- the bundle-entropy training step's feed plan (be_train_bundle.hip) ------------
+struct FeedPlanLaunch {
+    icnn_be_state st;
+    const double *y_true;
+    int loss;
+    int *row_offset, *counts;     // [B + 1]; counts[3] = rows, fg evaluations, OR of the status words
+    double *loss_out;
+    int *tallies;                 // [B][3] tp / fp / fn (cross entropy; may be NULL)
+    void *work;                   // feed_plan_work_bytes(B)
+};
+size_t feed_plan_work_bytes(int batch);
+hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream);
+hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
+                           int *fd_sample, hipStream_t stream);
 
 // ---- parameter update (be_train_update.hip) -----------------------------------------
 long long param_update_blocks(long long n);

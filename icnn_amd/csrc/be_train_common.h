@@ -36,11 +36,12 @@ struct Runner {
     bool dry() const { return part == nullptr; }
     // C[M][N] (pitch ldc) = A B through launch_tr_gemm
     void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
-              float *C, long long ldc) {
-        const size_t need = tr_gemm_part_floats(M, N, K);
+              float *C, long long ldc, const int *rows_dev = nullptr, int m_per_row = 0, bool dev_size = false) {
+        // dev_size: size the partials for a device plan (the dry run of the device-count variant has no rows_dev yet)
+        const size_t need = tr_gemm_part_floats(M, N, K, dev_size || rows_dev != nullptr);
         if (need > part_need) part_need = need;
         if (err != hipSuccess || dry()) return;
-        err = launch_tr_gemm(A, sam, sak, B, sbk, sbn, M, N, K, C, ldc, part, stream);
+        err = launch_tr_gemm(A, sam, sak, B, sbk, sbn, M, N, K, C, ldc, part, stream, rows_dev, m_per_row);
     }
     template <typename... KArgs, typename... Args>
     void launch(void (*k)(KArgs...), dim3 grid, int block, Args... args) {

@@ -12,12 +12,38 @@ namespace {
 
 constexpr int GBM = 64, GBN = 64, GBK = 16, GT_ = 256, GPITCH = GBK + 4;
 
+// split-K plan: enough splits that a small output still fills the device
+__host__ __device__ inline void gemm_splits(int M, int N, int K, int &splits, int &kchunk) {
+    const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+    splits = 1;
+    if (tiles < 256 && K > 64) {
+        splits = (256 + tiles - 1) / tiles;
+        const int most = (K + 63) / 64;
+        if (splits > most) splits = most;
+        if (splits > 32) splits = 32;
+    }
+    kchunk = (K + splits - 1) / splits;
+    kchunk = (kchunk + GBK - 1) / GBK * GBK;
+    if (kchunk < GBK) kchunk = GBK;
+    splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
+}
+// the most splits any plan of this K has
+inline int gemm_max_splits(int K) { return K > 64 ? ((K + 63) / 64 < 32 ? (K + 63) / 64 : 32) : 1; }
+// The plan of a product whose row count lives on the device (rows_dev != NULL): that of the compact call, which has
+// m_per_row x *rows_dev rows -- the same chunks of k summed in the same order, so the rows both calls share get the same bits
+__device__ __forceinline__ void gemm_dev_plan(const int *rows_dev, int m_per_row, int M, int N, int K, int &splits, int &kchunk) {
+    const long long m = (long long)m_per_row * max(*rows_dev, 0);
+    gemm_splits((int)(m < 1 ? 1 : (m < M ? m : M)), N, K, splits, kchunk);
+}
+
 // C_part[split][M][N] = sum over k in split's chunk of A(m, k) B(k, n); A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn]
 struct TrGemmArgs {
     const float *A, *B;
     long long sam, sak, sbk, sbn;
     int M, N, K, kchunk;
     float *part;
+    const int *rows_dev;     // not NULL: gemm_dev_plan; the grid has gemm_max_splits(K) slices, the surplus ones leave
+    int m_per_row;
 };
 
 __global__ __launch_bounds__(GT_) void tr_gemm_kernel(TrGemmArgs a) {
@@ -25,7 +51,13 @@ __global__ __launch_bounds__(GT_) void tr_gemm_kernel(TrGemmArgs a) {
     __shared__ __attribute__((aligned(16))) float Bt[GBN][GPITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
     const int m0 = blockIdx.x * GBM, n0 = blockIdx.y * GBN;
-    const int k_beg = blockIdx.z * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
+    int kchunk = a.kchunk;
+    if (a.rows_dev) {
+        int splits;
+        gemm_dev_plan(a.rows_dev, a.m_per_row, a.M, a.N, a.K, splits, kchunk);
+        if ((int)blockIdx.z >= splits) return;
+    }
+    const int k_beg = blockIdx.z * kchunk, k_end = min(a.K, k_beg + kchunk);
     const bool a_kfast = a.sak == 1, b_nfast = a.sbn == 1;    // walk the unit-stride index across neighbouring lanes
     f4 acc[4];
 #pragma unroll
@@ -68,8 +100,13 @@ __global__ __launch_bounds__(GT_) void tr_gemm_kernel(TrGemmArgs a) {
 }
 
 // second pass: C[m][n] (pitch ldc) = sum_s part[s][m][n], splits in order
-__global__ void tr_gemm_reduce_kernel(const float *part, int splits, int M, int N, float *C, long long ldc) {
+__global__ void tr_gemm_reduce_kernel(const float *part, int splits, int M, int N, float *C, long long ldc, int K,
+                                      const int *rows_dev, int m_per_row) {
     const size_t total = (size_t)M * N;
+    if (rows_dev) {
+        int kchunk;
+        gemm_dev_plan(rows_dev, m_per_row, M, N, K, splits, kchunk);
+    }
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         float s = part[i];
         for (int sp = 1; sp < splits; ++sp) s += part[(size_t)sp * total + i];
@@ -110,41 +147,27 @@ __global__ void tr_segment_sum_kernel(const float *rows, const int *row_offset, 
     }
 }
 
-// split-K plan: enough splits that a small output still fills the device
-void gemm_splits(int M, int N, int K, int &splits, int &kchunk) {
-    const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-    splits = 1;
-    if (tiles < 256 && K > 64) {
-        splits = (256 + tiles - 1) / tiles;
-        const int most = (K + 63) / 64;
-        if (splits > most) splits = most;
-        if (splits > 32) splits = 32;
-    }
-    kchunk = (K + splits - 1) / splits;
-    kchunk = (kchunk + GBK - 1) / GBK * GBK;
-    if (kchunk < GBK) kchunk = GBK;
-    splits = K > 0 ? (K + kchunk - 1) / kchunk : 1;
-}
-
 }  // namespace
 
-size_t tr_gemm_part_floats(int M, int N, int K) {
+size_t tr_gemm_part_floats(int M, int N, int K, bool dev_plan) {
     if (M <= 0 || N <= 0) return 0;
     int splits, kchunk;
     gemm_splits(M, N, K, splits, kchunk);
+    if (dev_plan) splits = gemm_max_splits(K);
     return (size_t)splits * M * N;
 }
 
 hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N,
-                          int K, float *C, long long ldc, float *part, hipStream_t stream) {
+                          int K, float *C, long long ldc, float *part, hipStream_t stream, const int *rows_dev, int m_per_row) {
     if (M <= 0 || N <= 0) return hipSuccess;
     int splits, kchunk;
     gemm_splits(M, N, K, splits, kchunk);
-    TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part};
+    if (rows_dev) splits = gemm_max_splits(K);
+    TrGemmArgs a{A, B, sam, sak, sbk, sbn, M, N, K, kchunk, part, rows_dev, m_per_row};
     hipError_t e = launch_kernel(tr_gemm_kernel, dim3((M + GBM - 1) / GBM, (N + GBN - 1) / GBN, splits), dim3(GT_), 0, stream, a);
     if (e == hipSuccess)
         e = launch_kernel(tr_gemm_reduce_kernel, dim3(grid_for((size_t)M * N)), dim3(256), 0, stream, (const float *)part, splits,
-                          M, N, C, ldc);
+                          M, N, C, ldc, K, rows_dev, m_per_row);
     return e;
 }
 

@@ -125,6 +125,7 @@ struct RowArgs {
     const int *samp;
     const float *ctx;      // context rows of the B samples (weighted BatchNorm)
     int R, n, C, tan;      // tan: the tangent rows R..2R-1 exist (v given)
+    const int *rows_dev;   // not NULL: the true row count (rows [*rows_dev, R) are padding: c = 0, v = 0)
 };
 
 // input map of z-layer 0: [y * yu0 | y] (tangent rows [v * yu0 | v]); y rounded to float32 like a TensorFlow feed
@@ -199,7 +200,8 @@ __global__ __launch_bounds__(FT_) void tc_final_kernel(RowArgs a, FinalArgs f) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const float *crow = a.ctx + (size_t)a.samp[r] * a.C;
     float *drow = f.drows + (size_t)r * a.C;
-    const float c = (float)a.c[r];
+    const bool live = !a.rows_dev || r < *a.rows_dev;          // padding: no energy, no adjoint
+    const float c = live ? (float)a.c[r] : 0.f;
     const size_t rt = (size_t)a.R + r;
     float e = 0.f, et = 0.f;
     for (int k = tid; k < f.fch; k += FT_) {
@@ -213,7 +215,7 @@ __global__ __launch_bounds__(FT_) void tc_final_kernel(RowArgs a, FinalArgs f) {
         f.adj3[(size_t)r * f.fch + k] = ap;
         f.X4[(size_t)r * f.fch + k] = z * g;
         if (a.tan) {
-            f.adj3[rt * f.fch + k] = on ? g * w : 0.f;
+            f.adj3[rt * f.fch + k] = (on && live) ? g * w : 0.f;
             f.X4[rt * f.fch + k] = zt * g;
         }
         drow[f.c_zu3 + k] = ap;
@@ -229,8 +231,8 @@ __global__ __launch_bounds__(FT_) void tc_final_kernel(RowArgs a, FinalArgs f) {
     if (tid == 0) {
         drow[f.c_zu4] = c;
         f.seed[r] = c;
-        if (a.tan) f.seed[rt] = 1.f;
-        if (f.F) f.F[r] = c * (red[0][0] + crow[f.c_zu4]) + red[1][0];
+        if (a.tan) f.seed[rt] = live ? 1.f : 0.f;
+        if (f.F) f.F[r] = live ? c * (red[0][0] + crow[f.c_zu4]) + red[1][0] : 0.f;
     }
 }
 
@@ -328,6 +330,7 @@ struct WbnArgs {
     const float *gamma, *beta;
     float eps;
     float *part, *hsave, *xhat, *inv, *stat;
+    const int *rows_dev;       // not NULL: Mtot = (float)*rows_dev * P, read on the device; 0 gives mean 0 and variance 0
 };
 __device__ __forceinline__ float wg_colsum(float (*red)[WBC], int g, int c, float mine) {
     red[g][c] = mine;
@@ -347,7 +350,8 @@ __global__ __launch_bounds__(WBT) void tc_wbn_fwd_kernel(WbnArgs a, int pass) {
     const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.y * WBC + c, ch = blockIdx.x;
     const bool ok = col < a.N;
     const int per = (a.rows + NCH - 1) / NCH, r0 = ch * per, r1 = min(a.rows, r0 + per);
-    const float mean = (pass > 0 && ok) ? chunk_total(a.part, a.N, col) / a.Mtot : 0.f;
+    const float Mtot = a.rows_dev ? (float)*a.rows_dev * a.P : a.Mtot;
+    const float mean = (pass > 0 && ok && Mtot > 0.f) ? chunk_total(a.part, a.N, col) / Mtot : 0.f;
     if (pass < 2) {
         float s = 0.f;
         if (ok) for (int r = r0 + g; r < r1; r += WBG) {
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(WBT) void tc_wbn_fwd_kernel(WbnArgs a, int pass) {
         return;
     }
     if (!ok) return;
-    const float var = chunk_total(a.part + (size_t)NCH * a.N, a.N, col) / a.Mtot, inv = 1.f / sqrtf(var + a.eps);
+    const float var = Mtot > 0.f ? chunk_total(a.part + (size_t)NCH * a.N, a.N, col) / Mtot : 0.f, inv = 1.f / sqrtf(var + a.eps);
     const float ga = a.gamma[col], be = a.beta[col];
     if (ch == 0 && g == 0) {
         a.inv[col] = inv;
@@ -384,6 +388,7 @@ struct WbnBackArgs {
     float *part, *dpre;
     int ld_dpre;
     float *dgamma, *dbeta;
+    const int *rows_dev;       // as WbnArgs
 };
 __global__ __launch_bounds__(WBT) void tc_wbn_back_kernel(WbnBackArgs a, int pass) {
     __shared__ float red[WBG][WBC];
@@ -408,9 +413,10 @@ __global__ __launch_bounds__(WBT) void tc_wbn_back_kernel(WbnBackArgs a, int pas
     const float S1 = chunk_total(a.part, a.N, col), S2 = chunk_total(a.part + (size_t)NCH * a.N, a.N, col);
     if (ch == 0 && g == 0) { a.dgamma[col] = S2; a.dbeta[col] = S1; }
     const float gi = a.gamma[col] * a.inv[col];
+    const float Mtot = a.rows_dev ? (float)*a.rows_dev * a.P : a.Mtot;
     for (int r = r0 + g; r < r1; r += WBG) {
         const float d = a.du[(size_t)r * a.N + col], xh = a.xhat[(size_t)r * a.N + col];
-        const float dh = gi * (d - a.mult[r / a.P] / a.Mtot * (S1 + xh * S2));
+        const float dh = gi * (d - (Mtot > 0.f ? a.mult[r / a.P] / Mtot : 0.f) * (S1 + xh * S2));
         a.dpre[(size_t)r * a.ld_dpre + col] = a.hsave[(size_t)r * a.N + col] > 0.f ? dh : 0.f;
     }
 }
@@ -527,7 +533,7 @@ int make_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch
 hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx, const TrainShape &s, const float *x,
                          const int *row_offset, const double *y, const double *v, const double *cvec, float *grad, float *F_rows,
                          float *work, size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr,
-                         int updates = 0) {
+                         int updates = 0, const int *rows_dev = nullptr, bool dev_sizes = false) {
     const ConvCtxShape &g = s.g;
     const int B = s.B, R = s.R, R2 = s.R2, n = s.n, C = s.C, fch = g.fch, flat = g.flat;
     const int tan = v != nullptr;
@@ -619,7 +625,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     const size_t fixed = cv.at;
 
     Runner run{stream, work ? work + fixed : nullptr};
-    RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, tan};
+    RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, tan, rows_dev};
     ConvPackOffsets po{};
     conv_pack_offsets(m, po);
 
@@ -635,7 +641,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     // 2. x-only forward on the B samples: stage GEMMs of the context producer, weighted BatchNorm behind the u-maps
     auto wbn_fwd = [&](int l) {
         WbnArgs a{u_[l], uld[l], urows[l], uP[l], uN[l], mult, (float)R * uP[l], cx.bn_gamma[l], cx.bn_beta[l], cx.bn_eps,
-                  bnpart, hsave[l], xhat[l], inv[l], updates > 0 ? stat[l] : nullptr};
+                  bnpart, hsave[l], xhat[l], inv[l], updates > 0 ? stat[l] : nullptr, rows_dev};
         for (int pass = 0; pass < 3; ++pass)
             run.launch(tc_wbn_fwd_kernel, dim3(NCH, (uN[l] + WBC - 1) / WBC), WBT, a, pass);
     };
@@ -646,7 +652,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
         else if (q == 4) wbn_fwd(2);
         else if (q == 5) wbn_fwd(3);
     }
-    if (updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, uN, 4, updates, stream); });
+    if (updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, uN, 4, updates, stream, nullptr, rows_dev); });
 
     // 3. y-path forward, primal and tangent rows stacked
     auto colargs = [&](const float *in, int rows, int IH, int IW, int IC, int KS, int ST, int PD, int OH, int OW, int ld,
@@ -663,7 +669,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
         const int M = R2 * g.P[l];
         run.launch(tc_im2col_kernel, dim3(grid_for((size_t)M * s.Kc[l])), 256, ca);
         float *pre = adj[l];          // the adjoint buffer holds the pre-activation until the reverse pass
-        run.gemm(col, s.Kc[l], 1, Wy[l], s.N[l], 1, M, s.N[l], s.Kc[l], pre, s.N[l]);
+        run.gemm(col, s.Kc[l], 1, Wy[l], s.N[l], 1, M, s.N[l], s.Kc[l], pre, s.N[l], rows_dev, (R2 / R) * g.P[l], dev_sizes);
         EpiArgs ea{pre, g.P[l], g.F[l], l < 2 ? 1 : 0, g.c_zu[l], g.c_gate[l + 1], l < 2 ? g.c_yu[l + 1] : 0,
                    l < 2 ? s.ch[l + 1] : flat, Z[l], l < 2 ? Yr[l + 1] : nullptr, l < 2 ? X[l + 1] : X3};
         if (l == 2) {           // X3 [R2][flat]: the map index (p, o) is the flat index with "channel pitch" F2
@@ -672,7 +678,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
         }
         run.launch(tc_conv_epi_kernel, dim3(grid_for((size_t)R * g.P[l] * s.N[l])), 256, ra, ea);
     }
-    run.gemm(X3, flat, 1, W3, fch, 1, R2, fch, flat, pre3, fch);
+    run.gemm(X3, flat, 1, W3, fch, 1, R2, fch, flat, pre3, fch, rows_dev, R2 / R, dev_sizes);
     FinalArgs fa{pre3, m.wpack + po.w_fc4, fch, g.c_zu3, g.c_gate[4], g.c_zu4, adj3, X4, seed, F_rows, drows};
     run.launch(tc_final_kernel, dim3(R), FT_, ra, fa);
 
@@ -713,7 +719,7 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
     // 6. x-only backward on the B samples, stages in reverse order
     auto wbn_back = [&](int l, int q) {
         WbnBackArgs a{du[l], xhat[l], hsave[l], inv[l], cx.bn_gamma[l], mult, urows[l], uP[l], uN[l], (float)R * uP[l], bnpart,
-                      dpre[q], st[q].N, grad + gl.gam[l], grad + gl.bet[l]};
+                      dpre[q], st[q].N, grad + gl.gam[l], grad + gl.bet[l], rows_dev};
         for (int pass = 0; pass < 2; ++pass)
             run.launch(tc_wbn_back_kernel, dim3(NCH, (uN[l] + WBC - 1) / WBC), WBT, a, pass);
     };
@@ -753,13 +759,14 @@ size_t conv_grad_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c) 
     return conv_grad_layout(s.g).total;
 }
 
-size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows) {
+size_t conv_surrogate_work_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, int batch, int rows, bool dev) {
     size_t most = 0;
     for (int with_v = 0; with_v < 2; ++with_v) {
         TrainShape s;
         if (make_shape(m, c, batch, rows, with_v != 0, s) != 0) return 0;
         size_t need = 0;
-        (void)surrogate_run(m, c, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need, nullptr);
+        (void)surrogate_run(m, c, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need, nullptr,
+                            nullptr, 0, nullptr, dev);
         if (need > most) most = need;
     }
     return most;
@@ -773,10 +780,10 @@ int conv_surrogate_shape(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c,
 hipError_t launch_conv_surrogate_grad(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c, const float *x, int batch,
                                       const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                       float *grad, float *F_rows, float *work, hipStream_t stream,
-                                      const icnn_be_bn_moving *mv, int updates) {
+                                      const icnn_be_bn_moving *mv, int updates, const int *rows_dev) {
     TrainShape s;
     if (make_shape(m, c, batch, rows, v != nullptr, s) != 0) return hipErrorInvalidValue;
-    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates);
+    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates, rows_dev);
 }
 
 }  // namespace icnn_be

@@ -61,6 +61,7 @@ struct RowArgs {
     const int *samp;
     const float *ctx;
     int R, n, C, box;
+    const int *rows_dev;        // not NULL: the true row count (rows [*rows_dev, R) are padding: c = 0, v = 0)
 };
 
 // PQ_i[:, 0:n) = [ y*yu_i ; v*yu_i ]  (pitch ld)
@@ -97,7 +98,14 @@ __global__ void tr_hidden_fwd_kernel(RowArgs a, const float *pre, int w, int zu_
 
 // last layer: F_r = c_r (pre_r + zu_L) + pre_dot_r; adjoint seeds abar = c_r, adot = 1
 __global__ void tr_final_kernel(RowArgs a, const float *pre, int zu_off, float *F, float *adj) {
+    const int live = a.rows_dev ? *a.rows_dev : a.R;
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < a.R; r += gridDim.x * blockDim.x) {
+        if (r >= live) {            // padding: no energy, no adjoint
+            if (F) F[r] = 0.f;
+            adj[r] = 0.f;
+            if (a.v) adj[a.R + r] = 0.f;
+            continue;
+        }
         const float c = (float)a.c[r];
         if (F) {
             const float e = pre[r] + a.ctx[(size_t)a.samp[r] * a.C + zu_off];
@@ -151,11 +159,13 @@ __global__ void tr_back_rows_kernel(RowArgs a, BackArgs b) {
 // xhat + beta replaces it in place (the next stage reads it there), xhat and inv-std are kept for the backward pass, the
 // mean [N] and variance [N] it normalised with go to stat_out (may be NULL) for the moving statistics.
 constexpr int WBT = 256, WBC = 32, WBG = WBT / WBC;
+// rows_dev (may be NULL): the normaliser M is the row count read from the device; a count of 0 gives mean 0 and variance 0
 __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B, int N, const float *mult, float M,
                                                          const float *gamma, const float *beta, float eps, float *hsave,
-                                                         float *xhat, float *inv_out, float *stat_out) {
+                                                         float *xhat, float *inv_out, float *stat_out, const int *rows_dev) {
     __shared__ float red[WBG][WBC];
     __shared__ float stat[2][WBC];
+    if (rows_dev) M = (float)*rows_dev;
     const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.x * WBC + c;
     const bool ok = col < N;
     auto total = [&](float mine, float *out) {
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B
         if (g == 0) {
             float t = 0.f;
             for (int i = 0; i < WBG; ++i) t += red[i][c];
-            *out = t / M;
+            *out = M > 0.f ? t / M : 0.f;
         }
         __syncthreads();
     };
@@ -198,9 +208,10 @@ __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B
 __global__ __launch_bounds__(WBT) void tr_u_back_kernel(const float *du, int B, int N, int mode, const float *u, int ld_u,
                                                         const float *hsave, const float *xhat, const float *inv,
                                                         const float *gamma, const float *mult, float M, float *dpre,
-                                                        int ld_dpre, float *dgamma, float *dbeta) {
+                                                        int ld_dpre, float *dgamma, float *dbeta, const int *rows_dev) {
     __shared__ float red[WBG][WBC];
     __shared__ float stat[2][WBC];
+    if (rows_dev) M = (float)*rows_dev;
     const int c = threadIdx.x % WBC, g = threadIdx.x / WBC, col = blockIdx.x * WBC + c;
     const bool ok = col < N;
     float s1 = 0.f, s2 = 0.f;
@@ -232,7 +243,7 @@ __global__ __launch_bounds__(WBT) void tr_u_back_kernel(const float *du, int B, 
         else if (mode == 1) o = u[(size_t)j * ld_u + col] > 0.f ? d : 0.f;
         else {
             const float xh = xhat[(size_t)j * N + col];
-            const float dh = gamma[col] * inv[col] * (d - mult[j] / M * (s1 + xh * s2));
+            const float dh = gamma[col] * inv[col] * (d - (M > 0.f ? mult[j] / M : 0.f) * (s1 + xh * s2));
             o = hsave[(size_t)j * N + col] > 0.f ? dh : 0.f;
         }
         dpre[(size_t)j * ld_dpre + col] = o;
@@ -344,7 +355,8 @@ int make_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, in
 // The whole step; with work == nullptr only sizes the workspace (returned through *work_floats)
 hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, const TrainShape &s, const float *x, const int *row_offset,
                   const double *y, const double *v, const double *cvec, float *grad, float *F_rows, float *work,
-                  size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr, int updates = 0) {
+                  size_t *work_floats, hipStream_t stream, const icnn_be_bn_moving *mv = nullptr, int updates = 0,
+                  const int *rows_dev = nullptr, bool dev_sizes = false) {
     const int L = s.L, B = s.B, R = s.R, R2 = s.R2, n = s.n, C = s.C;
     Carver cv{work};
     int *samp = reinterpret_cast<int *>(cv.take(R));
@@ -394,7 +406,7 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
     Runner run{stream, work ? work + fixed : nullptr};
     const PackOffsets po = pack_offsets(m);
     const GradLayout gl = grad_layout(s);
-    RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, m.action_box ? 1 : 0};
+    RowArgs ra{y, v, cvec, samp, ctxb, R, n, C, m.action_box ? 1 : 0, rows_dev};
 
     // 1. rows and multiplicities, y-path weights
     run.call([&] { return launch_tr_rows(row_offset, B, R, samp, mult, stream); });
@@ -407,14 +419,14 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
         run.call([&] { return launch_fc_context_stage(cx, i, x, B, ctxb, C, uwork, stream); });
         if (bn_n[i])
             run.launch(tr_wbn_fwd_kernel, (s.w[i] + WBC - 1) / WBC, WBT, u[i], u_ld[i], B, s.w[i], (const float *)mult, (float)R,
-                       cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i], updates > 0 ? stat[i] : nullptr);
+                       cx.bn_gamma[i], cx.bn_beta[i], cx.bn_eps, hsave[i], xhat[i], inv[i], updates > 0 ? stat[i] : nullptr, rows_dev);
     }
-    if (s.bn && updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, bn_n, L - 1, updates, stream); });
+    if (s.bn && updates > 0) run.call([&] { return launch_bn_fold(*mv, stat, bn_n, L - 1, updates, stream, nullptr, rows_dev); });
     // 3. y-path forward: primal and tangent rows stacked, one GEMM per layer
     for (int i = 0; i <= L; ++i) {
         const int ld = s.pq_ld(i), w = s.w[i];
         run.launch(tr_build_p_kernel, grid_for((size_t)R * n), 256, ra, s.yu_off[i], pq[i], ld);
-        run.gemm(pq[i], ld, 1, wst[i], w, 1, R2, w, ld, pre, w);
+        run.gemm(pq[i], ld, 1, wst[i], w, 1, R2, w, ld, pre, w, rows_dev, R2 / R, dev_sizes);
         if (i < L)
             run.launch(tr_hidden_fwd_kernel, grid_for((size_t)R * w), 256, ra, (const float *)pre, w, s.zu_off[i],
                        s.gate_off[i + 1], m.alpha, Z[i], D[i], pq[i + 1], s.pq_ld(i + 1));
@@ -443,7 +455,7 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
             run.launch(tr_u_back_kernel, (s.w[i] + WBC - 1) / WBC, WBT, (const float *)du, B, s.w[i], mode, u[i], u_ld[i],
                        (const float *)hsave[i], (const float *)xhat[i], (const float *)inv[i], cx.bn_gamma[i],
                        (const float *)mult, (float)R, dpre[i], ld, mode == 2 ? grad + gl.gam[i] : nullptr,
-                       mode == 2 ? grad + gl.bet[i] : nullptr);
+                       mode == 2 ? grad + gl.bet[i] : nullptr, rows_dev);
         }
         // stage input: x, or u_{i-1} as the next stage read it (after its BatchNorm)
         const float *prev = i > 0 ? u[i - 1] : x;
@@ -475,14 +487,15 @@ size_t fc_grad_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c) {
     return grad_layout(s).total;
 }
 
-size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows) {
+size_t fc_surrogate_work_floats(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int batch, int rows, bool dev) {
     // with and without v (2R or R stacked rows): the split-K partials need not grow with the row count, so take the larger
     size_t most = 0;
     for (int with_v = 0; with_v < 2; ++with_v) {
         TrainShape s;
         if (make_shape(m, c, batch, rows, with_v != 0, s) != 0) return 0;
         size_t need = 0;
-        (void)surrogate_run(m, c, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need, nullptr);
+        (void)surrogate_run(m, c, s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &need, nullptr,
+                            nullptr, 0, nullptr, dev);
         if (need > most) most = need;
     }
     return most;
@@ -496,10 +509,10 @@ int fc_surrogate_shape(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, int b
 hipError_t launch_fc_surrogate_grad(const icnn_be_fc_model &m, const icnn_be_fc_ctx &c, const float *x, int batch,
                                     const int *row_offset, int rows, const double *y, const double *v, const double *cvec,
                                     float *grad, float *F_rows, float *work, hipStream_t stream, const icnn_be_bn_moving *mv,
-                                    int updates) {
+                                    int updates, const int *rows_dev) {
     TrainShape s;
     if (make_shape(m, c, batch, rows, v != nullptr, s) != 0) return hipErrorInvalidValue;
-    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates);
+    return surrogate_run(m, c, s, x, row_offset, y, v, cvec, grad, F_rows, work, nullptr, stream, mv, updates, rows_dev);
 }
 
 }  // namespace icnn_be

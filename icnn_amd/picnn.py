@@ -280,6 +280,15 @@ class _BnMovingStats:
         mv.decay = float(self.bn_decay)
         return mv
 
+    def _device_updates(self, bn, bn_updates):
+        """bn_updates given as a device tensor (the fold count of a solve that never left the device): the int32 [1] tensor
+        the *_context_bn_dev entries read, without a host wait"""
+        if bn != "batch":
+            raise ValueError("a device bn_updates folds batch statistics: bn must be 'batch', got %r" % (bn,))
+        if bn_updates.dtype != torch.int32 or bn_updates.numel() != 1 or bn_updates.device.type != self.device.type:
+            raise ValueError("a device bn_updates is one int32 on %s" % (self.device,))
+        return bn_updates
+
     @staticmethod
     def _bn_mode(bn, bn_updates):
         from . import _lib
@@ -410,30 +419,52 @@ class FCModel(_BnMovingStats, _DeviceWeights):
                    "icnn_be_fc_pack")
         return host
 
-    def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
+    def context_work_floats(self, batch) -> int:
+        """floats of the `work` buffer context(..., work=) takes at this batch size (any bn / bn_updates)"""
+        import ctypes as C
+        return max(int(self._lib.icnn_be_fc_context_bn_work_floats(C.byref(self.c_ctx), batch)), 1)
+
+    def context(self, x: torch.Tensor, bn="batch", bn_updates=0, out=None, work=None) -> torch.Tensor:
         """x-only context rows [B, ctx_width] of the minibatch x [B, n_features] by the HIP kernels of be_context.hip
         (one MFMA GEMM per stage with routed epilogue, batch-statistics BatchNorm in place); current stream.
         bn="moving": inference mode, BatchNorm with self.bn_stats (valid at batch 1); bn="batch" with bn_updates = k > 0:
-        the same context, and the batch statistics folded k times into self.bn_stats (icnn_be_fc_context_bn)."""
+        the same context, and the batch statistics folded k times into self.bn_stats (icnn_be_fc_context_bn).  bn_updates
+        may be an int32 device tensor (one element): the count is read on the device, no host wait
+        (icnn_be_fc_context_bn_dev).  out / work: caller-owned buffers ([B, ctx_width] float32; context_work_floats(B)
+        floats) for a step that allocates nothing."""
         import ctypes as C
 
         from . import _lib
-        mode = self._bn_mode(bn, bn_updates)
+        k_dev = self._device_updates(bn, bn_updates) if torch.is_tensor(bn_updates) else None
+        mode = _lib.BN_MODE["batch"] if k_dev is not None else self._bn_mode(bn, bn_updates)
         x = x.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         assert x.shape[1] == self.spec.n_features
-        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device)
+        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device) if out is None else out
+        assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32 and ctx.is_contiguous()
+        if work is not None:
+            assert work.dtype == torch.float32 and work.numel() >= self.context_work_floats(B)
+        if k_dev is not None:
+            if work is None:
+                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mv = self._c_bn()
+            _lib.check(self._lib.icnn_be_fc_context_bn_dev(C.byref(self.c_ctx), C.byref(mv), k_dev.data_ptr(), x.data_ptr(), B,
+                                                           ctx.data_ptr(), self.spec.ctx_width, work.data_ptr(),
+                                                           C.c_void_p(stream)), "icnn_be_fc_context_bn_dev")
+            return ctx
         if mode != _lib.BN_MODE["batch"] or bn_updates:
-            work = torch.empty(max(int(self._lib.icnn_be_fc_context_bn_work_floats(C.byref(self.c_ctx), B)), 1),
-                               dtype=torch.float32, device=self.device)
+            if work is None:
+                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
             stream = torch.cuda.current_stream(self.device).cuda_stream
             mv = self._c_bn()
             _lib.check(self._lib.icnn_be_fc_context_bn(C.byref(self.c_ctx), C.byref(mv), mode, int(bn_updates), x.data_ptr(), B,
                                                        ctx.data_ptr(), self.spec.ctx_width, work.data_ptr(),
                                                        C.c_void_p(stream)), "icnn_be_fc_context_bn")
             return ctx
-        work = torch.empty(max(int(self._lib.icnn_be_fc_context_work_floats(C.byref(self.c_ctx), B)), 1),
-                           dtype=torch.float32, device=self.device)
+        if work is None:
+            work = torch.empty(max(int(self._lib.icnn_be_fc_context_work_floats(C.byref(self.c_ctx), B)), 1),
+                               dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._lib.icnn_be_fc_context(C.byref(self.c_ctx), x.data_ptr(), B, ctx.data_ptr(), self.spec.ctx_width,
                                                 work.data_ptr(), C.c_void_p(stream)), "icnn_be_fc_context")
@@ -780,32 +811,52 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
             getattr(c, field)[i] = t.data_ptr()
         self._ctx_keep, self.c_ctx = keep, c
 
-    def context(self, x: torch.Tensor, bn="batch", bn_updates=0) -> torch.Tensor:
+    def context_work_floats(self, batch) -> int:
+        """floats of the `work` buffer context(..., work=) takes at this batch size (any bn / bn_updates)"""
+        import ctypes as C
+        return max(int(self._lib.icnn_be_conv_context_bn_work_floats(C.byref(self.c_model), batch)), 1)
+
+    def context(self, x: torch.Tensor, bn="batch", bn_updates=0, out=None, work=None) -> torch.Tensor:
         """x-only context [B, ctx_width] of x [B, H, W, 1] (already h-flipped by the caller as
         completion/icnn_ebundle.py:215 does), on the device: be_context.hip through `icnn_be_conv_context`
-        (`conv_context` above is the torch restatement the tests compare it with).  bn / bn_updates as FCModel.context:
-        bn="moving" is the inference mode of the completion test phase (icnn_be_conv_context_bn)."""
+        (`conv_context` above is the torch restatement the tests compare it with).  bn / bn_updates / out / work as
+        FCModel.context: bn="moving" is the inference mode of the completion test phase (icnn_be_conv_context_bn); an int32
+        device tensor as bn_updates is read on the device (icnn_be_conv_context_bn_dev)."""
         import ctypes as C
 
         from . import _lib
-        mode = self._bn_mode(bn, bn_updates)
+        k_dev = self._device_updates(bn, bn_updates) if torch.is_tensor(bn_updates) else None
+        mode = _lib.BN_MODE["batch"] if k_dev is not None else self._bn_mode(bn, bn_updates)
         x = x.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         assert tuple(x.shape[1:]) == (self.spec.H, self.spec.W, 1)
         if getattr(self, "c_ctx", None) is None:
             self.repack_context(self.params)
-        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device)
+        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device) if out is None else out
+        assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32 and ctx.is_contiguous()
+        if work is not None:
+            assert work.dtype == torch.float32 and work.numel() >= self.context_work_floats(B)
+        if k_dev is not None:
+            if work is None:
+                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mv = self._c_bn()
+            _lib.check(self._lib.icnn_be_conv_context_bn_dev(C.byref(self.c_model), C.byref(self.c_ctx), C.byref(mv),
+                                                             k_dev.data_ptr(), x.data_ptr(), B, ctx.data_ptr(), work.data_ptr(),
+                                                             C.c_void_p(stream)), "icnn_be_conv_context_bn_dev")
+            return ctx
         if mode != _lib.BN_MODE["batch"] or bn_updates:
-            n = int(self._lib.icnn_be_conv_context_bn_work_floats(C.byref(self.c_model), B))
-            work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            if work is None:
+                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
             stream = torch.cuda.current_stream(self.device).cuda_stream
             mv = self._c_bn()
             _lib.check(self._lib.icnn_be_conv_context_bn(C.byref(self.c_model), C.byref(self.c_ctx), C.byref(mv), mode,
                                                          int(bn_updates), x.data_ptr(), B, ctx.data_ptr(), work.data_ptr(),
                                                          C.c_void_p(stream)), "icnn_be_conv_context_bn")
             return ctx
-        n = int(self._lib.icnn_be_conv_context_work_floats(C.byref(self.c_model), B))
-        work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+        if work is None:
+            n = int(self._lib.icnn_be_conv_context_work_floats(C.byref(self.c_model), B))
+            work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._lib.icnn_be_conv_context(C.byref(self.c_model), C.byref(self.c_ctx), x.data_ptr(), B,
                                                   ctx.data_ptr(), work.data_ptr(), C.c_void_p(stream)), "icnn_be_conv_context")

@@ -12,6 +12,11 @@
     FollowerWeights the same theta and arena without optimiser state, for a model another launch writes (the RL agent's
                     target network, rl_train.CriticTrainer).
 
+    BundleTrainer   one whole iteration of the bundle-entropy training loops without a host wait (capturable): context,
+                    fused solve, FeedPlan (be_train_bundle.hip: row offsets, row count, fg evaluations, status OR, loss, F1
+                    tallies), BatchNorm folds with a device count, PaddedFeed, surrogate_grad(rows_dev=), DeviceAdam.step
+                    (DESIGN.md §15).
+
     unrolled_grad   the parameter gradient of a loss of y_K through the unrolled momentum-GD inference of gd.solve (the
                     back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
                     over the trajectory's rows with c = 0 and v = coefficient x dL/dy_K.
@@ -103,7 +108,8 @@ def grad_floats(model) -> int:
     return int(model._lib.icnn_be_fc_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
 
 
-def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0, flat=False):
+def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0, flat=False,
+                   rows_dev=None, out=None, work=None):
     """Gradient of sum_r [ c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r> ] over every trainable variable of `model`,
     keyed like picnn.init_params(spec) -- for a ConvModel like picnn.init_conv_params(spec), x [B, H, W, 1] already
     h-flipped (completion/icnn_ebundle.py:215).
@@ -114,7 +120,13 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     reference's x_ = fd_xs.  F_rows: optional float32 [R] tensor that receives F_r.  bn_updates = k > 0 also folds those
     BatchNorm statistics k times into model.bn_stats (1: what the reference's train_step does); the gradient is the same.
     flat=True: the packed float32 [grad_floats] tensor itself (grad_layout order, what DeviceAdam.step takes) instead of the
-    dict of views.  Enqueued on the current stream without any host synchronisation (capturable in a CUDA graph)."""
+    dict of views.  Enqueued on the current stream without any host synchronisation (capturable in a CUDA graph).
+
+    rows_dev: an int32 device tensor (one element) holding the TRUE row count of a fixed-capacity feed -- y.shape[0] is then
+    the capacity R_cap, row_offset[B] equals the count, and the rows behind it are padding (finite y, v = 0, c = 0:
+    icnn_be_feed_pad) that contributes exactly nothing; BatchNorm normalises by the true count, so bn_stats and F_rows
+    [0, count) are the compact call's bits, and a count of 0 gives a zero gradient and leaves bn_stats alone.  out / work:
+    caller-owned float32 buffers (grad_floats(model); surrogate_work_floats(model, B, R)) for a step that allocates nothing."""
     spec, dev = model.spec, model.device
     conv = isinstance(model, ConvModel)
     x = x.to(dev, torch.float32).contiguous()
@@ -158,24 +170,59 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     if isinstance(model, ficnn.FICNNModel):            # no BatchNorm: icnn_be_ficnn_surrogate_grad
         if bn_updates:
             raise ValueError("a FICNN has no BatchNorm statistics to fold (bn_updates=%d)" % bn_updates)
+        if rows_dev is not None or out is not None or work is not None:
+            raise ValueError("rows_dev / out / work are for the PICNN entries: icnn_be_ficnn_surrogate_grad has no such form")
         return ficnn.surrogate_grad(model, x, row_offset, y, v, c, F_rows, flat)
     entry = "icnn_be_conv_surrogate_grad" if conv else "icnn_be_fc_surrogate_grad"
-    grad = torch.empty(grad_floats(model), dtype=torch.float32, device=dev)
+    if rows_dev is not None and (not torch.is_tensor(rows_dev) or rows_dev.dtype != torch.int32 or rows_dev.numel() != 1
+                                 or not rows_dev.is_cuda):
+        raise ValueError("rows_dev is one int32 on the device")
+    grad = torch.empty(grad_floats(model), dtype=torch.float32, device=dev) if out is None else out
+    assert grad.shape == (grad_floats(model),) and grad.dtype == torch.float32 and grad.is_contiguous()
     if R == 0:
         return grad.zero_() if flat else unpack_grad(spec, grad.zero_())
-    n_work = int(getattr(model._lib, entry + "_work_floats")(C.byref(model.c_model), C.byref(model.c_ctx), B, R))
-    if n_work == 0:
-        raise ValueError("%s: shape rejected (batch %d, rows %d)" % (entry, B, R))
-    work = torch.empty(n_work, dtype=torch.float32, device=dev)
+    n_work = surrogate_work_floats(model, B, R, dev=rows_dev is not None)
+    if work is None:
+        work = torch.empty(n_work, dtype=torch.float32, device=dev)
+    assert work.dtype == torch.float32 and work.numel() >= n_work
     if F_rows is not None:
         assert F_rows.dtype == torch.float32 and F_rows.shape == (R,) and F_rows.is_contiguous()
     stream = torch.cuda.current_stream(dev).cuda_stream
     mv = model._c_bn()
-    _lib.check(getattr(model._lib, entry + "_bn")(
-        C.byref(model.c_model), C.byref(model.c_ctx), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
-        None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
-        None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates, C.c_void_p(stream)), entry)
+    args = [C.byref(model.c_model), C.byref(model.c_ctx), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
+            None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
+            None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates]
+    if rows_dev is None:
+        _lib.check(getattr(model._lib, entry + "_bn")(*args, C.c_void_p(stream)), entry)
+    else:
+        _lib.check(getattr(model._lib, entry + "_dev")(*args, rows_dev.data_ptr(), C.c_void_p(stream)), entry + "_dev")
     return grad if flat else unpack_grad(spec, grad)
+
+
+def surrogate_work_floats(model, batch, rows, dev=False) -> int:
+    """floats of surrogate_grad's workspace for a PICNN at (batch, rows); dev: of the rows_dev form, which is larger (its
+    forward products keep split-K partials for any plan).  Raises on a shape the library rejects"""
+    entry = "icnn_be_conv_surrogate_grad" if isinstance(model, ConvModel) else "icnn_be_fc_surrogate_grad"
+    if dev:
+        entry += "_dev"
+    n_work = int(getattr(model._lib, entry + "_work_floats")(C.byref(model.c_model), C.byref(model.c_ctx), batch, rows))
+    if n_work == 0:
+        raise ValueError("%s: shape rejected (batch %d, rows %d)" % (entry, batch, rows))
+    return n_work
+
+
+def macro_f1(tallies) -> float:
+    """util.macroF1 of the reference from per-example tallies [B, 3] (tp, fp, fn over the labels of each example, prediction
+    y >= 0.5): that function transposes both arrays before sklearn's f1_score(average='macro'), so sklearn's classes are the
+    EXAMPLES and the macro average runs over them -- mean over examples of 2 tp / (2 tp + fp + fn), 0 where the denominator
+    is 0 (an example without a positive label or prediction).  Host arithmetic; a device tensor is copied (one wait)."""
+    t = tallies.detach().cpu().numpy() if torch.is_tensor(tallies) else np.asarray(tallies)
+    t = t.reshape(-1, 3).astype(np.float64)
+    if t.shape[0] == 0:
+        return 0.0
+    den = 2.0 * t[:, 0] + t[:, 1] + t[:, 2]
+    f1 = np.where(den > 0, 2.0 * t[:, 0] / np.where(den > 0, den, 1.0), 0.0)
+    return float(f1.mean())
 
 
 _COEF_CACHE: Dict[tuple, torch.Tensor] = {}
@@ -444,3 +491,160 @@ class DeviceAdam(_ArenaOwner):
         """Replace theta by `params` (host arrays or device tensors keyed like grad_layout) and rewrite the arena from
         them through the host packers.  m, v and the step count are kept."""
         _ArenaOwner.load(self, params)
+
+
+# --------------------------------------------------------------------------------------------- #
+# The bundle-entropy training step as one device step
+# --------------------------------------------------------------------------------------------- #
+class FeedPlan:
+    """The device-side plan of a training feed (icnn_be_feed_plan, be_train_bundle.hip) at one batch size and loss: from a
+    finished solve and the targets, row_offset [B+1], counts = (rows, fg evaluations, OR of the status words), the loss
+    (float64) and, for "xent", the per-example F1 tallies [B, 3] -- all device tensors, allocated here once."""
+
+    def __init__(self, state, loss):
+        if loss not in _lib.LOSS:
+            raise ValueError("loss must be 'xent' or 'mse', got %r" % (loss,))
+        self.state, self.loss_name = state, loss
+        B, dev = state.B, state.y.device
+        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.rows, self.fg_evals, self.status_or = self.counts[0:1], self.counts[1:2], self.counts[2:3]
+        self.loss = torch.zeros((), dtype=torch.float64, device=dev)
+        self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev) if loss == "xent" else None
+        n_work = int(state.lib.icnn_be_feed_plan_work_bytes(B))
+        self._work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)       # zeroed once: the ticket
+
+    def run(self, true_y):
+        """enqueue the plan for the state's current contents and true_y (float64 [B, n] device tensor); no host wait"""
+        st = self.state
+        assert true_y.dtype == torch.float64 and true_y.is_contiguous() and true_y.shape == (st.B, st.n) and true_y.is_cuda
+        _lib.check(st.lib.icnn_be_feed_plan(C.byref(st.c_state), true_y.data_ptr(), _lib.LOSS[self.loss_name],
+                                            self.row_offset.data_ptr(), self.counts.data_ptr(), self.loss.data_ptr(),
+                                            None if self.f1_tallies is None else self.f1_tallies.data_ptr(),
+                                            self._work.data_ptr(), st.stream()), "icnn_be_feed_plan")
+        return self
+
+
+class PaddedFeed:
+    """A training feed of fixed capacity R_cap = B x (the state's slot count): a sample keeps at most that many cuts active,
+    so every feed of the state fits.  fill() writes rows [0, R) exactly as bundle_entropy.implicit_feed does and the padding
+    [R, R_cap): y = 0.5, v = 0, c = 0.  `scale` (tests) multiplies the capacity."""
+
+    def __init__(self, state, scale=1):
+        B, n, dev = state.B, state.n, state.y.device
+        self.state, self.row_cap = state, int(scale) * B * state.T
+        R = self.row_cap
+        self.y = torch.full((R, n), 0.5, dtype=torch.float64, device=dev)
+        self.v = torch.zeros(R, n, dtype=torch.float64, device=dev)
+        self.c = torch.zeros(R, dtype=torch.float64, device=dev)
+        self.sample = torch.zeros(R, dtype=torch.int32, device=dev)
+
+    def fill(self, plan: FeedPlan, true_y):
+        st = self.state
+        if st.B == 0:
+            return self
+        _lib.check(st.lib.icnn_be_implicit_feed(C.byref(st.c_state), true_y.data_ptr(), _lib.LOSS[plan.loss_name],
+                                                plan.row_offset.data_ptr(), self.y.data_ptr(), self.v.data_ptr(),
+                                                self.c.data_ptr(), self.sample.data_ptr(), st.stream()), "icnn_be_implicit_feed")
+        _lib.check(st.lib.icnn_be_feed_pad(plan.rows.data_ptr(), st.B, st.n, self.row_cap, self.y.data_ptr(), self.v.data_ptr(),
+                                           self.c.data_ptr(), self.sample.data_ptr(), st.stream()), "icnn_be_feed_pad")
+        return self
+
+
+class BundleTrainer:
+    """One iteration of the bundle-entropy training loops (multi-label-cls/icnn_ebundle.py:208-250 with loss "xent" on a
+    picnn.FCModel; completion/icnn_ebundle.py with loss "mse" on a picnn.ConvModel) at one batch size, all of it enqueued
+    on the current stream without a host wait, so a step can be captured in a CUDA graph:
+
+        context (batch statistics) -> FusedSolver.solve from y0 = 0.5 -> FeedPlan -> BatchNorm folds for the solve's fg
+        evaluations (models with BatchNorm) -> PaddedFeed -> surrogate_grad(bn_updates=1, rows_dev=) -> DeviceAdam.step
+
+    Constructing one ATTACHES the model to its DeviceAdam and allocates every buffer; step allocates nothing.  After a step
+    the device tensors loss (float64, what the reference prints as l_yN / the squared error), f1_tallies ("xent": int32 [B,
+    3], see macro_f1), rows, fg_evals, status_or (int32 [1] each) and grad (the flat gradient) hold its results; read them
+    after a synchronisation of your choosing.  The update is NOT skipped on a solver error as the reference's completion loop
+    does on LinAlgError: call raise_on_error() and reload the weights if you need that."""
+
+    def __init__(self, model, batch, n_iter=10, loss="xent", variant="pdipm", lr=1e-3):
+        from .bundle_entropy import FusedSolver
+        if loss not in _lib.LOSS:
+            raise ValueError("loss must be 'xent' or 'mse', got %r" % (loss,))
+        if not isinstance(model, (FCModel, ConvModel)):
+            raise TypeError("BundleTrainer serves picnn.FCModel and picnn.ConvModel, got %s" % type(model).__name__)
+        want = "mse" if isinstance(model, ConvModel) else "xent"
+        if loss != want:
+            raise ValueError("a %s trains with loss %r, got %r" % (type(model).__name__, want, loss))
+        if variant not in ("dual", "pdipm"):
+            raise ValueError("variant must be 'dual' or 'pdipm' (the rl variant does not record n_iters), got %r" % (variant,))
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError("batch must be >= 1")
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.n_iter, self.loss_name, self.variant, self.lr = int(n_iter), loss, variant, float(lr)
+        self.conv = isinstance(model, ConvModel)
+        self.has_bn = self.conv or bool(getattr(self.spec, "batchnorm", False))
+        self.opt = DeviceAdam(model, lr=lr)
+        B, dev, n = self.batch, self.device, self.spec.n_labels
+        self.solver = FusedSolver(model, B, self.n_iter, variant)
+        st = self.solver.state
+        self.plan = FeedPlan(st, loss)
+        self.feed = PaddedFeed(st)
+        x_shape = (B, self.spec.H, self.spec.W, 1) if self.conv else (B, self.spec.n_features)
+        self.x = torch.zeros(x_shape, dtype=torch.float32, device=dev)
+        self.true_y = torch.zeros(B, n, dtype=torch.float64, device=dev)
+        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
+        self._ctx_fold = torch.empty_like(self.ctx) if self.has_bn else None
+        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
+        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
+        self._grad_work = torch.empty(surrogate_work_floats(model, B, self.feed.row_cap, dev=True), dtype=torch.float32, device=dev)
+        self.loss, self.f1_tallies = self.plan.loss, self.plan.f1_tallies
+        self.rows, self.fg_evals, self.status_or = self.plan.rows, self.plan.fg_evals, self.plan.status_or
+        self.row_offset = self.plan.row_offset
+
+    def step(self, x=None, true_y=None) -> torch.Tensor:
+        """One iteration on (x, true_y [B, n]); None keeps the batch of the previous call (graph replay).  Returns the loss at
+        y* (before the update), a float64 device scalar."""
+        if x is not None:
+            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
+        if true_y is not None:
+            self.true_y.copy_(torch.as_tensor(true_y).to(self.device, torch.float64).reshape(self.true_y.shape))
+        model = self.model
+        model.context(self.x, out=self.ctx, work=self._ctx_work)
+        self.solver.solve(self.ctx, 0.5)
+        self.plan.run(self.true_y)
+        if self.has_bn:
+            model.context(self.x, bn_updates=self.fg_evals, out=self._ctx_fold, work=self._ctx_work)
+        self.feed.fill(self.plan, self.true_y)
+        surrogate_grad(model, self.x, (self.feed.y, self.feed.v, self.feed.c), row_offset=self.row_offset, bn_updates=1,
+                       flat=True, rows_dev=self.rows, out=self.grad, work=self._grad_work)
+        self.opt.step(self.grad)
+        return self.loss
+
+    def raise_on_error(self):
+        """BundleResult.raise_on_error from status_or (reads it: one wait).  The OR names no sample."""
+        bits = int(self.status_or.item())
+        if bits & _lib.ST_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix (a sample of the last step)")
+        if bits & _lib.ST_NONFINITE:
+            raise FloatingPointError("non-finite value in the bundle of a sample of the last step")
+        if bits & _lib.ST_UNFINISHED:
+            raise RuntimeError("a sample is still behind after the finishing rounds of a time-sliced solve "
+                               "(ICNN_BE_ST_UNFINISHED)")
+        if bits & _lib.ST_OVERFLOW:
+            raise MemoryError("the active bundle of a sample outgrew the cuts one workgroup can stage")
+
+    def macro_f1(self) -> float:
+        """the train F1 of the last step (util.macroF1; "xent" only; one wait)"""
+        if self.f1_tallies is None:
+            raise ValueError("F1 tallies exist for loss 'xent' only")
+        return macro_f1(self.f1_tallies)
+
+    @property
+    def t_steps(self) -> int:
+        return self.opt.t
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        return self.opt.params()
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return self.opt.host_params()

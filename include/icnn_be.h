@@ -551,6 +551,69 @@ ICNN_BE_API int icnn_be_conv_surrogate_grad_bn(const icnn_be_conv_model *model, 
                                                const double *cvec, float *grad, float *F_rows, float *work,
                                                const icnn_be_bn_moving *mv, int updates, void *stream);
 
+/* ---- the bundle-entropy training step without the host (be_train_bundle.hip, additive to ABI 12) -- */
+
+/*
+ * What the host used to read back between a solve and its training gradient, in one launch of B
+ * workgroups from the state of a finished solve and the targets y_true [B][n]:
+ *   row_offset [B+1]  exclusive scan of st->count (each count clamped to 0 .. slots); row_offset[B] is the row count
+ *   counts [3]        the row count, the number of fg evaluations of the solve (what the reference's solveBatch called fg:
+ *                     the outer iteration count while any sample is unfinished, else min(that, max n_iters + 2); variants
+ *                     dual and pdipm), and the OR of the B status words
+ *   loss_out [1]      ICNN_BE_LOSS_XENT: - sum_{y>0} t log y - sum_{y<1} (1-t) log(1-y) (multi-label-cls/icnn_ebundle.py:
+ *                     419-421); ICNN_BE_LOSS_MSE: mean((255 (y - t))^2) (completion/icnn_ebundle.py:476-477).  float64,
+ *                     summed per sample and then over the samples in one fixed order: the same bits on every call
+ *   tallies [B][3]    cross entropy only, may be NULL: tp, fp, fn of example u over its labels with the prediction
+ *                     y >= 0.5 and the truth (int)t != 0 (util.macroF1 averages F1 over the EXAMPLES)
+ * work: icnn_be_feed_plan_work_bytes(batch) bytes, 8-byte aligned, ZEROED ONCE by the caller (the kernel re-arms it).
+ * batch = 0: nothing is launched.  No host synchronisation.
+ */
+ICNN_BE_API size_t icnn_be_feed_plan_work_bytes(int batch);
+ICNN_BE_API int icnn_be_feed_plan(const icnn_be_state *st, const double *y_true, int loss, int *row_offset, int *counts,
+                                  double *loss_out, int *tallies, void *work, void *stream);
+
+/*
+ * Padding of a fixed-capacity feed: rows [*rows, row_cap) of fd_y / fd_v [row_cap][n], fd_c / fd_sample [row_cap] become
+ * y = 0.5, v = 0, c = 0, sample = batch - 1; rows below *rows (icnn_be_implicit_feed wrote them) are left alone.  row_cap
+ * = batch x st->slots holds every feed of a state, since a sample keeps at most `slots` cuts active.
+ */
+ICNN_BE_API int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
+                                 int *fd_sample, void *stream);
+
+/*
+ * icnn_be_fc_surrogate_grad_bn / icnn_be_conv_surrogate_grad_bn over a feed of `rows` = row_cap rows of which only the
+ * first *rows_dev (a device int32, = row_offset[batch]) are real: the rest is padding as icnn_be_feed_pad writes it and
+ * contributes exactly nothing.  The work size is icnn_be_{fc,conv}_surrogate_grad_dev_work_floats(model, c, batch, rows) --
+ * larger than the compact entries' *_work_floats, which do not change: the forward products keep split-K partials for
+ * whatever plan the device count asks for.  Every launch and every other split-K plan come from row_cap; the
+ * multiplicity-weighted BatchNorm normalises by *rows_dev, so its statistics (and a fold into mv) and F_rows [0, *rows_dev)
+ * are the same bits as the compact call's; F_rows beyond are 0.  *rows_dev = 0: a zero gradient, mv unchanged.
+ * rows_dev = NULL is the compact entry.
+ */
+ICNN_BE_API size_t icnn_be_fc_surrogate_grad_dev_work_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, int batch,
+                                                            int rows);
+ICNN_BE_API size_t icnn_be_conv_surrogate_grad_dev_work_floats(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c,
+                                                              int batch, int rows);
+ICNN_BE_API int icnn_be_fc_surrogate_grad_dev(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, const float *x, int batch,
+                                              const int *row_offset, int rows, const double *y, const double *v,
+                                              const double *cvec, float *grad, float *F_rows, float *work,
+                                              const icnn_be_bn_moving *mv, int updates, const int *rows_dev, void *stream);
+ICNN_BE_API int icnn_be_conv_surrogate_grad_dev(const icnn_be_conv_model *model, const icnn_be_conv_ctx *c, const float *x,
+                                                int batch, const int *row_offset, int rows, const double *y, const double *v,
+                                                const double *cvec, float *grad, float *F_rows, float *work,
+                                                const icnn_be_bn_moving *mv, int updates, const int *rows_dev, void *stream);
+
+/*
+ * icnn_be_fc_context_bn / icnn_be_conv_context_bn in mode ICNN_BE_BN_BATCH whose fold count is read from the device:
+ * *updates_dev (int32, clamped to 0 .. ICNN_BE_MAX_ITERS) folds, the same bits as the host count.  work: the
+ * *_context_bn_work_floats.
+ */
+ICNN_BE_API int icnn_be_fc_context_bn_dev(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, const int *updates_dev,
+                                          const float *x, int batch, float *ctx, int ctx_width, float *work, void *stream);
+ICNN_BE_API int icnn_be_conv_context_bn_dev(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c,
+                                            const icnn_be_bn_moving *mv, const int *updates_dev, const float *x, int batch,
+                                            float *ctx, float *work, void *stream);
+
 /* ---- parameter update on the device (be_train_update.hip, additive to ABI 12) ------------------ */
 
 /*
