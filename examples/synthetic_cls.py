@@ -1,7 +1,8 @@
-"""Train the FICNN of the synthetic classification experiment (synthetic-cls/icnn.py) on the device: moons, circles or
-linearly separable points generated with NumPy, 30 steps of momentum GD as inference, full-batch TF-Adam with proj.
+"""Train the FICNN or the PICNN of the synthetic classification experiment (synthetic-cls/icnn.py) on the device: moons,
+circles or linearly separable points generated with NumPy, 30 steps of momentum GD as inference, full-batch TF-Adam with proj.
 
-    python examples/synthetic_cls.py [--dataset moons|circles|linear] [--epochs 100] [--head sum|linear] [--n 100]
+    python examples/synthetic_cls.py [--model ficnn|picnn] [--dataset moons|circles|linear] [--epochs 100]
+                                     [--head sum|linear] [--n 100]
 """
 import argparse
 import os
@@ -12,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from icnn_amd import ficnn  # noqa: E402
+from icnn_amd import ficnn, picnn, train  # noqa: E402
 
 
 def make_data(name, n, seed):
@@ -35,8 +36,21 @@ def make_data(name, n, seed):
     return X.astype(np.float32), Y.reshape(n, 1).astype(np.float32)
 
 
+def make_trainer(model, head, n, seed):
+    """the trainer of --model: makeCvx after initialisation (icnn.py:172), |W| for the FICNN here, |W| / 10 (:145) for the
+    PICNN; trainer.step(x, y) is one epoch"""
+    if model == "picnn":
+        spec = picnn.synthetic_spec()
+        params = picnn.make_convex(picnn.init_params(spec, seed), divisor=10)
+        return train.GDTrainer(picnn.FCModel(spec, params), n)
+    spec = ficnn.synthetic_spec(head)
+    params = ficnn.make_convex(ficnn.init_params(spec, seed))
+    return ficnn.GDTrainer(ficnn.FICNNModel(spec, params), n)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="ficnn", choices=["ficnn", "picnn"])
     ap.add_argument("--dataset", default="moons", choices=["moons", "circles", "linear"])
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--head", default="sum", choices=["sum", "linear"])
@@ -44,9 +58,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     X, Y = make_data(args.dataset, args.n, args.seed)
-    spec = ficnn.synthetic_spec(args.head)
-    params = ficnn.make_convex(ficnn.init_params(spec, args.seed))        # makeCvx after initialisation (icnn.py:172)
-    trainer = ficnn.GDTrainer(ficnn.FICNNModel(spec, params), args.n)
+    trainer = make_trainer(args.model, args.head, args.n, args.seed)
     x, y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
     for epoch in range(args.epochs):
         loss = trainer.step(x if epoch == 0 else None, y if epoch == 0 else None)

@@ -62,6 +62,7 @@ EXPORTS = [
     "icnn_be_feed_plan_work_bytes", "icnn_be_feed_plan", "icnn_be_feed_pad", "icnn_be_fc_surrogate_grad_dev",
     "icnn_be_conv_surrogate_grad_dev", "icnn_be_fc_context_bn_dev", "icnn_be_conv_context_bn_dev",
     "icnn_be_fc_surrogate_grad_dev_work_floats", "icnn_be_conv_surrogate_grad_dev_work_floats",
+    "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -98,7 +99,7 @@ class FcCtx(C.Structure):
     """struct icnn_be_fc_ctx"""
     _fields_ = [
         ("n_features", C.c_int), ("n", C.c_int), ("n_layers", C.c_int), ("width", C.c_int * MAX_LAYERS),
-        ("batchnorm", C.c_int), ("bn_eps", C.c_float),
+        ("batchnorm", C.c_int), ("bn_eps", C.c_float), ("u_last_relu", C.c_int),
         ("w_stage", C.c_void_p * MAX_LAYERS), ("b_stage", C.c_void_p * MAX_LAYERS),
         ("bn_gamma", C.c_void_p * MAX_LAYERS), ("bn_beta", C.c_void_p * MAX_LAYERS),
     ]
@@ -300,6 +301,10 @@ def load():
     lib.icnn_be_feed_plan.restype = C.c_int
     lib.icnn_be_feed_pad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.icnn_be_feed_pad.restype = C.c_int
+    lib.icnn_be_gd_feed_work_bytes.argtypes = [C.c_int]
+    lib.icnn_be_gd_feed_work_bytes.restype = C.c_size_t
+    lib.icnn_be_gd_feed.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 7)
+    lib.icnn_be_gd_feed.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
     lib.icnn_be_gd_workspace_bytes.argtypes = [C.c_int, C.c_int]

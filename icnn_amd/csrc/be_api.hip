@@ -1,6 +1,7 @@
 // C ABI of libicnn_be.so (see include/icnn_be.h for the contract and the reference lines
 // each entry point replaces).  Everything here only validates arguments and enqueues work.
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdint>
 #include <cmath>
 #include <cstdlib>
@@ -525,6 +526,7 @@ int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx,
     if (batch < 0 || max_iter < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     if (int rc = icnn_be::ctx_check(*cx)) return rc;
+    if (cx->u_last_relu) return ICNN_BE_EINVAL;        /* the in-kernel producer keeps the last u layer linear */
     /* the in-kernel context producer sizes its reads from the MODEL's layer widths while the stage matrices were laid out
        for cx's: both structs must describe the same network */
     if (cx->n != model->n || cx->n_layers != model->n_layers) return ICNN_BE_EINVAL;
@@ -569,6 +571,18 @@ int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_
     if (!rows || !fd_y || !fd_v || !fd_c || !fd_sample || batch < 1 || n < 1 || row_cap < 0) return ICNN_BE_EINVAL;
     if (row_cap == 0) return 0;
     hipError_t e = icnn_be::launch_feed_pad(rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+size_t icnn_be_gd_feed_work_bytes(int B) { return B < 0 ? 0 : icnn_be::gd_feed_work_bytes(B); }
+
+int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, double *v_rows,
+                    double *c_rows, int *row_offset, float *loss, int *f1_tallies, void *work, void *stream) {
+    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !coef || !v_rows || !c_rows || !row_offset || !loss || !work) return ICNN_BE_EINVAL;
+    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
+    icnn_be::GdFeedLaunch l{yK, t, coef, B, n, K, scale, v_rows, c_rows, row_offset, loss, f1_tallies, work};
+    hipError_t e = icnn_be::launch_gd_feed(l, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : fail(e);
 }
 

@@ -457,10 +457,10 @@ hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *
     a.W = c.w_stage[i]; a.ldw = ctx_stage_ld(c, i); a.N = ctx_stage_cols(c, i); a.bias = c.b_stage[i];
     a.a_vec = (prev_ld % 4 == 0) && (reinterpret_cast<uintptr_t>(prev) % 16 == 0);
     int col = 0, s = 0;
-    if (i < L) {            // u_i: input of the next stage; hidden layers are ReLU'd (:343), the last one is linear
-        int u_ld = 0;
+    if (i < L) {            // u_i: input of the next stage; hidden layers are ReLU'd (:343), the last one is linear unless
+        int u_ld = 0;       // u_last_relu (synthetic-cls/icnn.py:236-276)
         float *u_out = fc_ctx_u(c, batch, work, i, &u_ld);
-        a.seg[s++] = CtxSeg{col, col + c.width[i], u_ld, 0, i < L - 1 ? 1 : 0, 0, u_out};
+        a.seg[s++] = CtxSeg{col, col + c.width[i], u_ld, 0, i < L - 1 || c.u_last_relu ? 1 : 0, 0, u_out};
         col += c.width[i];
     }
     a.seg[s++] = CtxSeg{col, col + c.n, ctx_width, ctx_off, 0, 0, ctx};                       // yu_i

@@ -258,6 +258,22 @@ hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream);
 hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
                            int *fd_sample, hipStream_t stream);
 
+// ---- the back-optimisation training step's feed (be_train_gd.hip) -------------------
+struct GdFeedLaunch {
+    const double *yK;             // [B][n] y_K (float32 values)
+    const float *t;               // [B][n] targets
+    const double *coef;           // [K] step coefficients
+    int B, n, K;
+    float scale;                  // float32(1) / float32(B n)
+    double *v_rows, *c_rows;      // [B K][n], [B K]
+    int *row_offset;              // [B + 1]
+    float *loss;
+    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
+    void *work;                   // gd_feed_work_bytes(B)
+};
+size_t gd_feed_work_bytes(int batch);
+hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream);
+
 // ---- parameter update (be_train_update.hip) -----------------------------------------
 long long param_update_blocks(long long n);
 hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream);

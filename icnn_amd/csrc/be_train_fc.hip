@@ -202,8 +202,9 @@ __global__ __launch_bounds__(WBT) void tr_wbn_fwd_kernel(float *u, int ld, int B
     }
 }
 
-// du (gradient at u_i, [B][N]) -> the u columns of dpre_i (pitch ld_dpre).  mode 0: linear (last u layer); 1: ReLU only,
-// mask from u itself; 2: weighted BatchNorm backward then ReLU:
+// du (gradient at u_i, [B][N]) -> the u columns of dpre_i (pitch ld_dpre).  mode 0: linear (last u layer); 1: ReLU only
+// (hidden layers without BatchNorm, and the last u layer of a context with u_last_relu), mask from u itself;
+// 2: weighted BatchNorm backward then ReLU:
 //   S1 = sum_j du_j, S2 = sum_j du_j xhat_j,  dh_j = gamma inv (du_j - m_j / M (S1 + xhat_j S2)),  dgamma = S2, dbeta = S1
 __global__ __launch_bounds__(WBT) void tr_u_back_kernel(const float *du, int B, int N, int mode, const float *u, int ld_u,
                                                         const float *hsave, const float *xhat, const float *inv,
@@ -451,7 +452,7 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
         run.launch(tr_dpre_heads_kernel, grid_for((size_t)B * (ld - ucols)), 256, (const float *)dctx, (const float *)ctxb, B, C,
                    ucols, n, s.w[i], wp, s.yu_off[i], s.zu_off[i], s.gate_off[i], dpre[i], ld);
         if (i < L) {        // u_i columns from du = dprev_{i+1} (computed in the previous iteration)
-            const int mode = i == L - 1 ? 0 : (s.bn ? 2 : 1);
+            const int mode = i == L - 1 ? (cx.u_last_relu ? 1 : 0) : (s.bn ? 2 : 1);
             run.launch(tr_u_back_kernel, (s.w[i] + WBC - 1) / WBC, WBT, (const float *)du, B, s.w[i], mode, u[i], u_ld[i],
                        (const float *)hsave[i], (const float *)xhat[i], (const float *)inv[i], cx.bn_gamma[i],
                        (const float *)mult, (float)R, dpre[i], ld, mode == 2 ? grad + gl.gam[i] : nullptr,

@@ -1,0 +1,129 @@
+// The feed of the back-optimisation training step (synthetic-cls/icnn.py:117-139, multi-label-cls/icnn-back.py;
+// include/icnn_be.h icnn_be_gd_feed): everything between the unrolled GD solve and the surrogate gradient,
+// which a caller otherwise composes from six elementwise launches.
+//
+//   gd_feed_kernel   one workgroup per sample j: d = float32(y_K) - t and ybar = (d * 2) * scale in float32, the K rows
+//                    v[j K + k] = coef[k] * ybar of the sample (consecutive in memory: one coalesced sweep), c = 0 for
+//                    them, row_offset[j] = K j, the sample's sum of d^2 in double (every product exact) and, when asked,
+//                    its F1 tallies.  The last workgroup to take a ticket adds the per-sample sums, scales by 1 / (B n) in
+//                    double and rounds once to float32.  Every sum has one fixed order: the same bits on every call.
+#include <hip/hip_runtime.h>
+
+#include "be_kernels.h"
+
+namespace icnn_be {
+
+namespace {
+
+constexpr int GT = 256;
+
+struct GdFeedArgs {
+    GdFeedLaunch l;
+    double *partial;     // [B]
+    int *ticket;
+};
+
+// the same tree for every call; valid in every thread
+__device__ __forceinline__ double feed_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = GT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double out = red[0];
+    __syncthreads();
+    return out;
+}
+__device__ __forceinline__ int feed_count(int v, int *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = GT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const int out = red[0];
+    __syncthreads();
+    return out;
+}
+
+__global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double red[GT];
+    __shared__ int ired[GT];
+    __shared__ int s_last;
+    const GdFeedLaunch &l = a.l;
+    const int tid = threadIdx.x, j = blockIdx.x, n = l.n, K = l.K, B = l.B;
+    const double *y_row = l.yK + (size_t)j * n;
+    const float *t_row = l.t + (size_t)j * n;
+    // ---- this sample's squared error and tallies ----
+    double s = 0.0;
+    for (int i = tid; i < n; i += GT) {
+        const float d = (float)y_row[i] - t_row[i];
+        s = s + (double)d * (double)d;
+    }
+    s = feed_sum(s, red);
+    if (l.tallies) {
+        int tp = 0, fp = 0, fn = 0;
+        for (int i = tid; i < n; i += GT) {
+            const bool pred = y_row[i] >= 0.5, truth = (int)t_row[i] != 0;
+            tp += pred && truth;
+            fp += pred && !truth;
+            fn += !pred && truth;
+        }
+        tp = feed_count(tp, ired);
+        fp = feed_count(fp, ired);
+        fn = feed_count(fn, ired);
+        if (tid == 0) {
+            l.tallies[3 * j] = tp;
+            l.tallies[3 * j + 1] = fp;
+            l.tallies[3 * j + 2] = fn;
+        }
+    }
+    // ---- its K rows: element e = k n + i of the sample's [K][n] block ----
+    double *v_blk = l.v_rows + (size_t)j * K * n;
+    const size_t total = (size_t)K * n;
+    int k = tid / n, i = tid - k * n;           // advanced by GT per pass without a division
+    const int dk = GT / n, di = GT - dk * n;
+    for (size_t e = tid; e < total; e += GT) {
+        const float d = (float)y_row[i] - t_row[i];
+        const float ybar = (d * 2.0f) * l.scale;
+        v_blk[e] = l.coef[k] * (double)ybar;
+        k += dk;
+        i += di;
+        if (i >= n) { i -= n; ++k; }
+    }
+    for (int r = tid; r < K; r += GT) l.c_rows[(size_t)j * K + r] = 0.0;
+    if (tid == 0) {
+        l.row_offset[j] = K * j;
+        if (j == B - 1) l.row_offset[B] = K * B;
+        __hip_atomic_store(a.partial + j, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int ticket = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = ticket == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // ---- the last workgroup: the loss, per-sample parts in sample order within a thread, then the fixed tree ----
+    double tot = 0.0;
+    for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tot = feed_sum(tot, red);
+    if (tid == 0) {
+        *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
+        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
+    }
+}
+
+}  // namespace
+
+// the per-sample sums (8-byte aligned) and the ticket
+size_t gd_feed_work_bytes(int batch) { return sizeof(double) * (size_t)(batch > 0 ? batch : 1) + 16; }
+
+hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream) {
+    GdFeedArgs a{};
+    a.l = l;
+    a.partial = static_cast<double *>(l.work);
+    a.ticket = reinterpret_cast<int *>(a.partial + (l.B > 0 ? l.B : 1));
+    return launch_kernel(gd_feed_kernel, dim3(l.B), dim3(GT), 0, stream, a);
+}
+
+}  // namespace icnn_be

@@ -32,6 +32,7 @@ class FCSpec:
     alpha: float = 0.0        # 0 -> ReLU (multi-label); FLAGS.lrelu for negQ
     batchnorm: bool = True    # u-path BN in batch-statistics mode (icnn_ebundle.py:209,259)
     action_box: bool = False  # RL wrapper: network sees 2y-1, gradient doubled (icnn.py:148-158)
+    relu_last_u: bool = False  # synthetic-cls f_picnn ReLUs every u-layer (icnn.py:236-276); elsewhere the last one is linear
 
     @property
     def widths(self) -> List[int]:
@@ -80,6 +81,12 @@ def halfcheetah_spec():
     """RL defaults: dimO=17, dimA=6, l1size=l2size=200, lrelu=0.01, icnn_bn=False
     (RL/src/agent.py:9-10,23)."""
     return FCSpec(17, 6, (200, 200), alpha=0.01, batchnorm=False, action_box=True)
+
+
+def synthetic_spec():
+    """synthetic-cls `--model picnn` (icnn.py:236-276, f_picnn with szs [200, 200, 1]): two features, one label, no
+    BatchNorm, and the last u-layer ReLU'd like the hidden ones."""
+    return FCSpec(2, 1, (200, 200), batchnorm=False, relu_last_u=True)
 
 
 def _trunc_normal(rng, shape, std):
@@ -140,11 +147,14 @@ def init_params(spec: FCSpec, seed=0, regime="init", yu_bias=0.0, gate_bias=0.0)
     return p
 
 
-def make_convex(params):
-    """reference `makeCvx` (icnn_ebundle.py:143): |W| on every 'proj' weight."""
+def make_convex(params, divisor=1.0):
+    """reference `makeCvx` (icnn_ebundle.py:143): |W| on every 'proj' weight; |W| / divisor with a divisor other than 1
+    (synthetic-cls/icnn.py:145 divides by 10)."""
     for k in params:
         if "proj" in k and k.endswith("/W"):
             params[k] = np.abs(params[k])
+            if divisor != 1.0:
+                params[k] = params[k] / np.float32(divisor)
     return params
 
 
@@ -234,6 +244,8 @@ def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=
                 mean = u.mean(dim=0)
                 var = ((u - mean) ** 2).mean(dim=0)
                 u = (u - mean) / torch.sqrt(var + 1e-5) * t["u%d/bn/gamma" % i] + t["u%d/bn/beta" % i]
+        elif spec.relu_last_u:
+            u = torch.relu(u)
         us.append(u)
         prev = u
     parts = []
@@ -370,6 +382,7 @@ class FCModel(_BnMovingStats, _DeviceWeights):
             c.width[i] = w
         c.batchnorm = int(spec.batchnorm)
         c.bn_eps = 1e-5
+        c.u_last_relu = int(spec.relu_last_u)
         return c
 
     def _ctx_host(self, params):

@@ -21,6 +21,10 @@
                     back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
                     over the trajectory's rows with c = 0 and v = coefficient x dL/dy_K.
 
+    GDTrainer       one whole back-optimisation training step of an FC PICNN without a host wait (capturable): context,
+                    gd.solve with its trajectory, the fused feed of be_train_gd.hip (icnn_be_gd_feed: loss, dL/dy_K times
+                    the step coefficients, row offsets, F1 tallies), surrogate_grad, DeviceAdam.step.
+
 One training step of the multi-label experiment:
     solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
 or, for a caller that updates the weights itself,
@@ -637,6 +641,97 @@ class BundleTrainer:
         """the train F1 of the last step (util.macroF1; "xent" only; one wait)"""
         if self.f1_tallies is None:
             raise ValueError("F1 tallies exist for loss 'xent' only")
+        return macro_f1(self.f1_tallies)
+
+    @property
+    def t_steps(self) -> int:
+        return self.opt.t
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        return self.opt.params()
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return self.opt.host_params()
+
+
+# --------------------------------------------------------------------------------------------- #
+# The back-optimisation training step of the FC PICNNs as one device step
+# --------------------------------------------------------------------------------------------- #
+class GDTrainer:
+    """One training step of the back-optimisation scripts on a picnn.FCModel (synthetic-cls/icnn.py:117-139 with
+    picnn.synthetic_spec(); multi-label-cls/icnn-back.py with the loss mean((y_K - t)^2)) at one batch size, all of it enqueued
+    on the current stream without a host wait, so a step can be captured in a CUDA graph:
+
+        context (batch statistics) -> gd.solve(trajectory=True) from y0 -> icnn_be_gd_feed (be_train_gd.hip: the loss, the
+        rows v = coefficient x dL/dy_K, c = 0, row_offset, F1 tallies) -> surrogate_grad over the B K trajectory rows ->
+        DeviceAdam.step (TF-Adam and the reference's proj)
+
+    which is train.unrolled_grad with its torch elementwise launches folded into one kernel: the rows are the same bits, so
+    grad and the update are those of the hand-composed step.  Constructing one ATTACHES the model to its DeviceAdam and
+    allocates x, t, loss, the feed rows, the gradient and the gradient's workspace.  step() returns the loss (before the
+    update, as the reference's sess.run returns it) as a float32 device scalar.  After a step the device tensors loss, grad
+    (flat), y (y_K, float64 [B, n]) and, with f1=True, f1_tallies (int32 [B, 3], see macro_f1) hold its results; read them
+    after a synchronisation of your choosing.
+
+    bn_updates is passed to surrogate_grad: k > 0 folds the BatchNorm statistics of the step k times into model.bn_stats (the
+    caveat of unrolled_grad applies: the reference's graph calls f K times on its way to the loss, and whether TensorFlow
+    merges those identical x-only subgraphs is not pinned down, so the count is the caller's)."""
+
+    def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, bn_updates=0, f1=False):
+        if not isinstance(model, FCModel):
+            name = model.__name__ if isinstance(model, type) else type(model).__name__
+            raise TypeError("train.GDTrainer serves picnn.FCModel (ficnn.GDTrainer trains a FICNNModel), got %s" % name)
+        self.batch, self.n_iter, self.bn_updates = int(batch), int(n_iter), int(bn_updates)
+        if self.batch < 1 or self.n_iter < 1:
+            raise ValueError("batch and n_iter must be >= 1")
+        if self.bn_updates < 0:
+            raise ValueError("bn_updates must be >= 0, got %d" % self.bn_updates)
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.lr, self.momentum, self.y0 = float(lr), float(momentum), float(y0)
+        self.opt = DeviceAdam(model, lr=adam_lr)
+        B, K, n, dev = self.batch, self.n_iter, self.spec.n_labels, self.device
+        self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
+        self.scale = float(np.float32(1.0) / np.float32(B * n))
+        self.x = torch.zeros(B, self.spec.n_features, dtype=torch.float32, device=dev)
+        self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.y = None                                   # gd.solve's own y_K tensor, from the first step on
+        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
+        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
+        self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
+        self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
+        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev) if f1 else None
+        n_work = int(model._lib.icnn_be_gd_feed_work_bytes(B))
+        self._feed_work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)      # zeroed once: the ticket
+        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
+        self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
+
+    def step(self, x=None, t=None) -> torch.Tensor:
+        """One step on (x [B, n_features], t [B, n]); None keeps the batch of the previous call (graph replay)."""
+        from . import gd
+        if x is not None:
+            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
+        if t is not None:
+            self.t.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t.shape))
+        model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
+        model.context(self.x, out=self.ctx, work=self._ctx_work)
+        self.y, traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(model._lib.icnn_be_gd_feed(self.y.data_ptr(), self.t.data_ptr(), self._coef.data_ptr(), B, n, K, self.scale,
+                                              self.v_rows.data_ptr(), self.c_rows.data_ptr(), self.row_offset.data_ptr(),
+                                              self.loss.data_ptr(),
+                                              None if self.f1_tallies is None else self.f1_tallies.data_ptr(),
+                                              self._feed_work.data_ptr(), C.c_void_p(stream)), "icnn_be_gd_feed")
+        surrogate_grad(model, self.x, (traj.view(B * K, n), self.v_rows, self.c_rows), row_offset=self.row_offset,
+                       bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
+        self.opt.step(self.grad)
+        return self.loss
+
+    def macro_f1(self) -> float:
+        """the train F1 of the last step (util.macroF1; needs f1=True; one wait)"""
+        if self.f1_tallies is None:
+            raise ValueError("F1 tallies are kept with f1=True only")
         return macro_f1(self.f1_tallies)
 
     @property

@@ -306,13 +306,19 @@ ICNN_BE_API int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx
  *                (pad columns zero);  b_stage[i] the biases in the same column order.
  * multi-label-cls/icnn_ebundle.py:339-347 (u-path), :354-374 (heads); RL/src/icnn.py:339-385.  Hidden u layers
  * are ReLU'd, and batch-normalised with the statistics of the batch when `batchnorm` (bn_gamma/bn_beta[i], i <
- * n_layers-2, epsilon bn_eps = 1e-5); the last u layer is linear.  All pointers device memory.
+ * n_layers-2, epsilon bn_eps = 1e-5); the last u layer is linear, or ReLU'd (and never normalised) when u_last_relu != 0:
+ * the PICNN of synthetic-cls/icnn.py:236-276, which applies the ReLU to every u layer.  The flag is read by the context
+ * producers (icnn_be_fc_context*, _stage, _bn, _bn_dev) and by the x-only forward and backward of
+ * icnn_be_fc_surrogate_grad*; the y-path never sees it.  icnn_be_adam_fc_obs, whose in-kernel producer keeps the last u layer
+ * linear, returns ICNN_BE_EINVAL when it is set.  The field fills what used to be padding in front of the pointer arrays:
+ * sizeof is unchanged and a zero-initialised struct is the linear last layer as before.  All pointers device memory.
  */
 typedef struct icnn_be_fc_ctx {
     int n_features, n, n_layers;
     int width[ICNN_BE_MAX_LAYERS];      /* as icnn_be_fc_model.width */
     int batchnorm;
     float bn_eps;
+    int u_last_relu;                    /* != 0: u_{n_layers-2} = relu(.) instead of linear */
     const float *w_stage[ICNN_BE_MAX_LAYERS];
     const float *b_stage[ICNN_BE_MAX_LAYERS];
     const float *bn_gamma[ICNN_BE_MAX_LAYERS];
@@ -613,6 +619,33 @@ ICNN_BE_API int icnn_be_fc_context_bn_dev(const icnn_be_fc_ctx *c, const icnn_be
 ICNN_BE_API int icnn_be_conv_context_bn_dev(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c,
                                             const icnn_be_bn_moving *mv, const int *updates_dev, const float *x, int batch,
                                             float *ctx, float *work, void *stream);
+
+/* ---- the back-optimisation training step's feed (be_train_gd.hip, additive to ABI 12) ---------- */
+
+/*
+ * What lies between icnn_be_fc_gd (trajectory) and icnn_be_fc_surrogate_grad in a back-optimisation training step with the
+ * loss mean((y_K - t)^2) over B n (synthetic-cls/icnn.py:117-139, multi-label-cls/icnn-back.py), in ONE launch of B
+ * workgroups.  From yK [B][n] (float64 holding float32 values, icnn_be_fc_gd's y_out), the targets t [B][n] (float32) and the
+ * step coefficients coef [K] (float64, dy_K / dg_k), per element in float32 and without contraction
+ *   d = (float)yK - t;   ybar = (d * 2.0f) * scale        scale = float32(1) / float32(B n), formed by the caller
+ * and then
+ *   v_rows [B K][n]   v_rows[j K + k][i] = coef[k] * (double)ybar[j][i]          (one float64 product)
+ *   c_rows [B K]      0
+ *   row_offset [B+1]  row_offset[j] = K j
+ *   loss [1]          float32 of ( sum d^2 ) * (1.0 / (B n)): every d * d formed in float64 (exact), summed per sample by a
+ *                     fixed tree, the per-sample sums added by the last workgroup to take a ticket (each thread its samples
+ *                     in index order, then the same tree), rounded once -- the same bits on every call
+ *   f1_tallies [B][3] may be NULL: tp, fp, fn of example j over its labels with the prediction yK >= 0.5 and the truth
+ *                     (int)t != 0, the layout of icnn_be_feed_plan's tallies
+ * the (y, v, c) rows and row_offset of icnn_be_fc_surrogate_grad with y = the trajectory.  work:
+ * icnn_be_gd_feed_work_bytes(B) bytes, 8-byte aligned, ZEROED ONCE by the caller (the kernel re-arms it).  EINVAL for B, n
+ * or K < 1 or a NULL pointer other than f1_tallies, ELIMIT when B K exceeds INT_MAX, before anything is launched.  No
+ * accumulating atomics, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API size_t icnn_be_gd_feed_work_bytes(int B);
+ICNN_BE_API int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale,
+                                double *v_rows, double *c_rows, int *row_offset, float *loss, int *f1_tallies, void *work,
+                                void *stream);
 
 /* ---- parameter update on the device (be_train_update.hip, additive to ABI 12) ------------------ */
 
