@@ -62,7 +62,7 @@ EXPORTS = [
     "icnn_be_feed_plan_work_bytes", "icnn_be_feed_plan", "icnn_be_feed_pad", "icnn_be_fc_surrogate_grad_dev",
     "icnn_be_conv_surrogate_grad_dev", "icnn_be_fc_context_bn_dev", "icnn_be_conv_context_bn_dev",
     "icnn_be_fc_surrogate_grad_dev_work_floats", "icnn_be_conv_surrogate_grad_dev_work_floats",
-    "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed",
+    "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed", "icnn_be_gd_feed_px_work_bytes", "icnn_be_gd_feed_px",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -305,6 +305,10 @@ def load():
     lib.icnn_be_gd_feed_work_bytes.restype = C.c_size_t
     lib.icnn_be_gd_feed.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 7)
     lib.icnn_be_gd_feed.restype = C.c_int
+    lib.icnn_be_gd_feed_px_work_bytes.argtypes = [C.c_int] * 3
+    lib.icnn_be_gd_feed_px_work_bytes.restype = C.c_size_t
+    lib.icnn_be_gd_feed_px.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p] * 6)
+    lib.icnn_be_gd_feed_px.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
     lib.icnn_be_gd_workspace_bytes.argtypes = [C.c_int, C.c_int]

@@ -586,6 +586,24 @@ int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B,
     return e == hipSuccess ? 0 : fail(e);
 }
 
+size_t icnn_be_gd_feed_px_work_bytes(int B, int n, int K) {
+    return (B < 1 || n < 1 || K < 1) ? 0 : icnn_be::gd_feed_work_bytes(B);
+}
+
+int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, float px,
+                       double *v_rows, double *c_rows, int *row_offset, float *loss, void *work, void *stream) {
+    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
+    const int rows = (v_rows != nullptr) + (c_rows != nullptr) + (row_offset != nullptr);
+    if (rows != 0 && rows != 3) return ICNN_BE_EINVAL;
+    if (rows == 3 && !coef) return ICNN_BE_EINVAL;
+    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
+    if (rows == 3 && icnn_be::gd_feed_px_chunks(n, K) > icnn_be::GD_FEED_PX_MAX_CHUNKS) return ICNN_BE_ELIMIT;
+    icnn_be::GdFeedPxLaunch l{yK, t, coef, B, n, K, scale, px, v_rows, c_rows, row_offset, loss, work};
+    hipError_t e = icnn_be::launch_gd_feed_px(l, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
                           double *lam_rows, void *stream) {
     if (int rc = check_state(st)) return rc;

@@ -274,6 +274,27 @@ struct GdFeedLaunch {
 size_t gd_feed_work_bytes(int batch);
 hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream);
 
+// the same feed for the loss mean((px (y_K - t))^2), on a grid of B x S workgroups; v_rows, c_rows, row_offset (and coef)
+// NULL together: the loss alone
+struct GdFeedPxLaunch {
+    const double *yK;
+    const float *t;
+    const double *coef;
+    int B, n, K;
+    float scale, px;
+    double *v_rows, *c_rows;
+    int *row_offset;
+    float *loss;
+    void *work;                   // gd_feed_work_bytes(B)
+};
+#ifndef ICNN_BE_GD_FEED_PX_CHUNK
+#define ICNN_BE_GD_FEED_PX_CHUNK 8192         // an experiment builds another value (tools/conv_gd_step_time.py --alt-lib)
+#endif
+constexpr int GD_FEED_PX_CHUNK = ICNN_BE_GD_FEED_PX_CHUNK;   // elements of a sample's [K][n] block per workgroup, at most
+constexpr int GD_FEED_PX_MAX_CHUNKS = 65535; // gridDim.y
+long long gd_feed_px_chunks(int n, int K);
+hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream);
+
 // ---- parameter update (be_train_update.hip) -----------------------------------------
 long long param_update_blocks(long long n);
 hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream);

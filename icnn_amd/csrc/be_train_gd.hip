@@ -7,6 +7,11 @@
 //                    them, row_offset[j] = K j, the sample's sum of d^2 in double (every product exact) and, when asked,
 //                    its F1 tallies.  The last workgroup to take a ticket adds the per-sample sums, scales by 1 / (B n) in
 //                    double and rounds once to float32.  Every sum has one fixed order: the same bits on every call.
+//   gd_feed_px_kernel  the same feed for the loss mean((px (y_K - t))^2) of completion/icnn.back.py:149 (icnn_be_gd_feed_px;
+//                    DESIGN.md §17) on a two-dimensional grid: workgroup (j, c) writes chunk c of the S contiguous chunks of
+//                    sample j's [K][n] block, and workgroup (j, 0) alone forms the sample's sum, in gd_feed_kernel's order
+//                    and tree, and takes the ticket -- no output bit depends on S.  Without rows (the test phase) the grid
+//                    is B x 1 and only the loss is formed.
 #include <hip/hip_runtime.h>
 
 #include "be_kernels.h"
@@ -113,6 +118,71 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
     }
 }
 
+struct GdFeedPxArgs {
+    GdFeedPxLaunch l;
+    double *partial;     // [B]
+    int *ticket;
+    unsigned chunk;      // elements of a sample's [K][n] block per workgroup: ceil(K n / gridDim.y)
+};
+
+__global__ __launch_bounds__(GT) void gd_feed_px_kernel(GdFeedPxArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double red[GT];
+    __shared__ int s_last;
+    const GdFeedPxLaunch &l = a.l;
+    const int tid = threadIdx.x, j = blockIdx.x, n = l.n, K = l.K, B = l.B;
+    const double *y_row = l.yK + (size_t)j * n;
+    const float *t_row = l.t + (size_t)j * n;
+    if (l.v_rows) {
+        // ---- chunk blockIdx.y of the sample's K rows: elements e = k n + i in [lo, hi) ----
+        double *v_blk = l.v_rows + (size_t)j * K * n;
+        const size_t total = (size_t)K * n, lo = (size_t)blockIdx.y * a.chunk;
+        const size_t hi = lo + a.chunk < total ? lo + a.chunk : total;
+        const size_t e0 = lo + tid;
+        int k = (int)(e0 / (size_t)n), i = (int)(e0 - (size_t)k * n);    // one division, then advanced by GT per pass
+        const int dk = GT / n, di = GT - dk * n;
+        for (size_t e = e0; e < hi; e += GT) {
+            const float d = (float)y_row[i] - t_row[i];
+            const float u = l.px * d;
+            const float ybar = ((u * 2.0f) * l.scale) * l.px;
+            v_blk[e] = l.coef[k] * (double)ybar;
+            k += dk;
+            i += di;
+            if (i >= n) { i -= n; ++k; }
+        }
+    }
+    if (blockIdx.y != 0) return;
+    // ---- workgroup (j, 0): c, row_offset and this sample's squared error ----
+    if (l.v_rows) {
+        for (int r = tid; r < K; r += GT) l.c_rows[(size_t)j * K + r] = 0.0;
+        if (tid == 0) {
+            l.row_offset[j] = K * j;
+            if (j == B - 1) l.row_offset[B] = K * B;
+        }
+    }
+    double s = 0.0;
+    for (int i = tid; i < n; i += GT) {
+        const float u = l.px * ((float)y_row[i] - t_row[i]);
+        s = s + (double)u * (double)u;
+    }
+    s = feed_sum(s, red);
+    if (tid == 0) {
+        __hip_atomic_store(a.partial + j, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int ticket = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = ticket == B - 1;                   // one ticket per sample, whatever gridDim.y
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // ---- the last of them: the loss, as gd_feed_kernel forms it ----
+    double tot = 0.0;
+    for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tot = feed_sum(tot, red);
+    if (tid == 0) {
+        *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
+        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
+    }
+}
+
 }  // namespace
 
 // the per-sample sums (8-byte aligned) and the ticket
@@ -124,6 +194,22 @@ hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream) {
     a.partial = static_cast<double *>(l.work);
     a.ticket = reinterpret_cast<int *>(a.partial + (l.B > 0 ? l.B : 1));
     return launch_kernel(gd_feed_kernel, dim3(l.B), dim3(GT), 0, stream, a);
+}
+
+// S of the 2-D grid: ceil(K n / GD_FEED_PX_CHUNK) workgroups per sample (DESIGN.md §17 has the measurement behind the chunk)
+long long gd_feed_px_chunks(int n, int K) {
+    return ((long long)K * n + GD_FEED_PX_CHUNK - 1) / GD_FEED_PX_CHUNK;
+}
+
+hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream) {
+    GdFeedPxArgs a{};
+    a.l = l;
+    a.partial = static_cast<double *>(l.work);
+    a.ticket = reinterpret_cast<int *>(a.partial + (l.B > 0 ? l.B : 1));
+    const long long total = (long long)l.K * l.n;
+    const long long S = l.v_rows ? gd_feed_px_chunks(l.n, l.K) : 1;
+    a.chunk = (unsigned)((total + S - 1) / S);
+    return launch_kernel(gd_feed_px_kernel, dim3(l.B, (unsigned)S), dim3(GT), 0, stream, a);
 }
 
 }  // namespace icnn_be

@@ -25,6 +25,10 @@
                     gd.solve with its trajectory, the fused feed of be_train_gd.hip (icnn_be_gd_feed: loss, dL/dy_K times
                     the step coefficients, row offsets, F1 tallies), surrogate_grad, DeviceAdam.step.
 
+    ConvGDTrainer   the same step for the completion model (completion/icnn.back.py:131-165, 210-254) on a picnn.ConvModel,
+                    with the loss mean((255 (y_K - t))^2) and its feed on a two-dimensional grid (icnn_be_gd_feed_px), and
+                    the script's test phase as evaluate().
+
 One training step of the multi-label experiment:
     solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
 or, for a caller that updates the weights itself,
@@ -733,6 +737,151 @@ class GDTrainer:
         if self.f1_tallies is None:
             raise ValueError("F1 tallies are kept with f1=True only")
         return macro_f1(self.f1_tallies)
+
+    @property
+    def t_steps(self) -> int:
+        return self.opt.t
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        return self.opt.params()
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return self.opt.host_params()
+
+
+# --------------------------------------------------------------------------------------------- #
+# The back-optimisation training step and test phase of the completion model
+# --------------------------------------------------------------------------------------------- #
+class ConvGDTrainer:
+    """One training step of completion/icnn.back.py (:131-165 the graph, :210-239 the loop) on a picnn.ConvModel at one batch
+    size, with the loss mean((pixel_scale (y_K - t))^2) of :149, all of it enqueued on the current stream without a host wait,
+    so a step can be captured in a CUDA graph:
+
+        context (batch statistics) -> gd.solve(trajectory=True) from y0 -> icnn_be_gd_feed_px (be_train_gd.hip: the loss, the
+        rows v = coefficient x dL/dy_K, c = 0, row_offset) -> surrogate_grad over the B K trajectory rows -> DeviceAdam.step
+
+    which is train.unrolled_grad with its torch elementwise launches folded into one kernel: the rows are the same bits, so
+    grad and the update are those of the hand-composed step.  x is [B, H, W, 1]; its horizontal flip (icnn.back.py:220) is
+    the CALLER's, as for ConvModel.context.  y0: a scalar, an [n] row (the reference's meanY), an image [H, W, 1] or a [B, n]
+    array (images [B, H, W, 1] too); set_y0 replaces it, outside a capture.
+
+    Constructing one ATTACHES the model to its DeviceAdam and allocates x, t, y0, the context, loss, the feed rows, the
+    gradient and the workspaces.  step() returns the loss (before the update, as the reference's sess.run returns it) as a
+    float32 device scalar.  After a step the device tensors loss, grad (flat), y (y_K, float64 [B, n]) and traj (y_0 .. y_{K-1},
+    float64 [B, K, n]) hold its results; read them after a synchronisation of your choosing.  bn_updates is passed to surrogate_grad (unrolled_grad's caveat on
+    the count applies).
+
+    eval_batch = E also allocates the test phase (icnn.back.py:241-253): evaluate(x, t) runs the context with the MOVING
+    BatchNorm statistics, gd.solve from y0 without a trajectory and the loss-only form of the feed on exactly E samples; it
+    returns the float32 device scalar eval_loss, keeps y_eval, and changes no weight, optimiser state or statistic.  A
+    [B, n] y0 serves the test phase only when E = B."""
+
+    def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, pixel_scale=255.0, bn_updates=0,
+                 eval_batch=None):
+        if not isinstance(model, ConvModel):
+            name = model.__name__ if isinstance(model, type) else type(model).__name__
+            raise TypeError("train.ConvGDTrainer serves picnn.ConvModel (train.GDTrainer trains an FCModel), got %s" % name)
+        self.batch, self.n_iter, self.bn_updates = int(batch), int(n_iter), int(bn_updates)
+        self.eval_batch = None if eval_batch is None else int(eval_batch)
+        if self.batch < 1 or self.n_iter < 1:
+            raise ValueError("batch and n_iter must be >= 1")
+        if self.bn_updates < 0:
+            raise ValueError("bn_updates must be >= 0, got %d" % self.bn_updates)
+        if self.eval_batch is not None and self.eval_batch < 1:
+            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.lr, self.momentum, self.px = float(lr), float(momentum), float(np.float32(pixel_scale))
+        self.opt = DeviceAdam(model, lr=adam_lr)
+        B, K, E, n, dev = self.batch, self.n_iter, self.eval_batch, self.spec.n_labels, self.device
+        lib = model._lib
+        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
+        self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
+        self.scale = float(np.float32(1.0) / np.float32(B * n))
+        self.x = torch.zeros(B, self.spec.H, self.spec.W, 1, dtype=torch.float32, device=dev)
+        self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
+        self.y0 = torch.zeros(B, n, dtype=torch.float64, device=dev)
+        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.y = self.traj = None                       # gd.solve's own y_K and trajectory tensors, from the first step on
+        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
+        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
+        self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
+        self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
+        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        n_work = int(lib.icnn_be_gd_feed_px_work_bytes(B, n, K))
+        self._feed_work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)      # zeroed once: the ticket
+        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
+        self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
+        self.y_eval = self.eval_loss = None
+        if E is not None:
+            self.x_eval = torch.zeros(E, self.spec.H, self.spec.W, 1, dtype=torch.float32, device=dev)
+            self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
+            self.y0_eval = torch.zeros(E, n, dtype=torch.float64, device=dev)
+            self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            self.ctx_eval = torch.empty(E, self.spec.ctx_width, dtype=torch.float32, device=dev)
+            self._ctx_work_eval = torch.empty(model.context_work_floats(E), dtype=torch.float32, device=dev)
+            n_work = int(lib.icnn_be_gd_feed_px_work_bytes(E, n, K))
+            self._feed_work_eval = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)
+        self.set_y0(y0)
+
+    def set_y0(self, y0):
+        """The start point of step() and evaluate(): a scalar, an [n] row, an image [H, W, 1] or a [B, n] array ([B, H, W, 1]
+        too).  A copy from the host: call it outside a capture."""
+        n = self.spec.n_labels
+        y0 = torch.as_tensor(y0, dtype=torch.float64).to(self.device)
+        if y0.dim() >= 3:                               # an image, or one per sample
+            y0 = y0.reshape(-1, n)
+        if y0.dim() == 2 and y0.shape[0] == 1:
+            y0 = y0[0]
+        if y0.dim() > 2 or (y0.dim() >= 1 and y0.shape[-1] != n) or (y0.dim() == 2 and y0.shape[0] != self.batch):
+            raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
+                             % (n, self.batch, tuple(y0.shape)))
+        if self.eval_batch is not None:
+            if y0.dim() == 2 and self.eval_batch != self.batch:
+                raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
+            self.y0_eval.copy_(y0.expand(self.eval_batch, n))
+        self.y0.copy_(y0.expand(self.batch, n))
+
+    def _feed(self, y, t, B, loss, work, rows):
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        v, c, off, coef = ((self.v_rows.data_ptr(), self.c_rows.data_ptr(), self.row_offset.data_ptr(), self._coef.data_ptr())
+                           if rows else (None, None, None, None))
+        # scale is 1 / (B n) of the TRAINING batch: the loss-only form does not read it
+        _lib.check(self.model._lib.icnn_be_gd_feed_px(y.data_ptr(), t.data_ptr(), coef, B, self.spec.n_labels, self.n_iter,
+                                                      self.scale, self.px, v, c, off, loss.data_ptr(), work.data_ptr(),
+                                                      C.c_void_p(stream)), "icnn_be_gd_feed_px")
+
+    def step(self, x=None, t=None) -> torch.Tensor:
+        """One step on (x [B, H, W, 1] already h-flipped, t [B, n] or [B, H, W, 1]); None keeps the batch of the previous call
+        (graph replay)."""
+        from . import gd
+        if x is not None:
+            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
+        if t is not None:
+            self.t.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t.shape))
+        model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
+        model.context(self.x, out=self.ctx, work=self._ctx_work)
+        self.y, self.traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
+        self._feed(self.y, self.t, B, self.loss, self._feed_work, True)
+        surrogate_grad(model, self.x, (self.traj.view(B * K, n), self.v_rows, self.c_rows), row_offset=self.row_offset,
+                       bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
+        self.opt.step(self.grad)
+        return self.loss
+
+    def evaluate(self, x=None, t=None) -> torch.Tensor:
+        """The test phase on exactly eval_batch samples (x, t shaped as for step; None keeps the previous ones): the loss at
+        y_K from the moving BatchNorm statistics, a float32 device scalar (eval_loss); y_eval keeps y_K.  Nothing is
+        updated."""
+        from . import gd
+        if self.eval_batch is None:
+            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        if x is not None:
+            self.x_eval.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x_eval.shape))
+        if t is not None:
+            self.t_eval.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t_eval.shape))
+        self.model.context(self.x_eval, bn="moving", out=self.ctx_eval, work=self._ctx_work_eval)
+        self.y_eval = gd.solve(self.model, self.ctx_eval, self.y0_eval, self.n_iter, self.lr, self.momentum)[0]
+        self._feed(self.y_eval, self.t_eval, self.eval_batch, self.eval_loss, self._feed_work_eval, False)
+        return self.eval_loss
 
     @property
     def t_steps(self) -> int:

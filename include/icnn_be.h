@@ -647,6 +647,35 @@ ICNN_BE_API int icnn_be_gd_feed(const double *yK, const float *t, const double *
                                 double *v_rows, double *c_rows, int *row_offset, float *loss, int *f1_tallies, void *work,
                                 void *stream);
 
+/*
+ * icnn_be_gd_feed for the completion model's back-optimisation loss mean((px (y_K - t))^2) over B n, px = 255
+ * (completion/icnn.back.py:149), between icnn_be_conv_gd (trajectory) and icnn_be_conv_surrogate_grad; additive to ABI 12.
+ * Per element in float32, every operation rounded, without contraction
+ *   d = (float)yK - t;   u = px * d;   ybar = ((u * 2.0f) * scale) * px      scale = float32(1) / float32(B n)
+ * the order in which TensorFlow's gradient of reduce_mean(square(255. * (yn - trueY))) multiplies.  Like the rest of the
+ * PICNN arithmetic this order is NOT pinned at the TensorFlow boundary (its graph optimiser may reassociate the constants);
+ * px cannot be folded into scale without changing the float32 rounding of ybar.  Then
+ *   v_rows [B K][n]   v_rows[j K + k][i] = coef[k] * (double)ybar[j][i]          (one float64 product)
+ *   c_rows [B K]      0
+ *   row_offset [B+1]  row_offset[j] = K j
+ *   loss [1]          float32 of ( sum (double)u * (double)u ) * (1.0 / (B n)): every product exact, icnn_be_gd_feed's
+ *                     per-sample tree and its fixed order over the per-sample sums; only a ticket is atomic and it re-arms
+ *                     itself -- the same bits on every call
+ * With px = 1.0f every output is bit-equal to icnn_be_gd_feed's on the same inputs.  The grid is B x S workgroups: a sample's
+ * [K][n] block is written as S = ceil(K n / 8192) contiguous chunks of ceil(K n / S) elements (a boundary may fall inside a
+ * row), and the first workgroup of a sample alone forms its sum; no output bit depends on S.
+ *
+ * Loss only (the test phase, icnn.back.py:241-253): v_rows, c_rows and row_offset NULL, all three together; coef may then be
+ * NULL too and nothing but loss is written.  work: icnn_be_gd_feed_px_work_bytes(B, n, K) bytes (0 for an argument < 1),
+ * 8-byte aligned, ZEROED ONCE by the caller.  EINVAL for B, n or K < 1, for yK, t, loss or work NULL, for one or two of the
+ * three row pointers NULL, for coef NULL with rows; ELIMIT when B K exceeds INT_MAX or S exceeds 65535 -- all before anything
+ * is launched.  Vector stores only, no accumulating atomics, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API size_t icnn_be_gd_feed_px_work_bytes(int B, int n, int K);
+ICNN_BE_API int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale,
+                                   float px, double *v_rows, double *c_rows, int *row_offset, float *loss, void *work,
+                                   void *stream);
+
 /* ---- parameter update on the device (be_train_update.hip, additive to ABI 12) ------------------ */
 
 /*
