@@ -34,42 +34,53 @@ def _dact(v, alpha):
     return np.where(v > 0, F32(1), F32(alpha)).astype(F32)
 
 
-def u_path(params, x, n_hidden, batchnorm=True, eps=1e-5):
+def _caster(dtype):
+    """float32 (the default): arrays pass through untouched, as before; another dtype (float64: the restatement the
+    float32 context producers are measured against) promotes the float32 parameters and inputs"""
+    if dtype == F32:
+        return lambda a: a
+    return lambda a: np.asarray(a).astype(dtype)
+
+
+def u_path(params, x, n_hidden, batchnorm=True, eps=1e-5, dtype=F32):
     """x-only trunk: u_i = BN(relu(fc(u_{i-1}))) for i < L-1, u_{L-1} = fc(u_{L-2})
-    (icnn_ebundle.py:339-347; RL/src/icnn.py:345-354)."""
-    us, prev = [], x.astype(F32)
+    (icnn_ebundle.py:339-347; RL/src/icnn.py:345-354).  dtype: the arithmetic (float32 as the reference graph, or
+    float64 with the float32 parameters promoted)."""
+    D, c = dtype, _caster(dtype)
+    us, prev = [], x.astype(D)
     for i in range(n_hidden):
-        u = prev.dot(params["u%d/W" % i]) + params["u%d/b" % i]
+        u = prev.dot(c(params["u%d/W" % i])) + c(params["u%d/b" % i])
         if i < n_hidden - 1:
-            u = np.maximum(u, F32(0))
+            u = np.maximum(u, D(0))
             if batchnorm:
-                mean = u.mean(axis=0, dtype=F32)
-                var = ((u - mean) ** 2).mean(axis=0, dtype=F32)   # biased, as tf.nn.moments
-                u = (u - mean) / np.sqrt(var + F32(eps)) * params["u%d/bn/gamma" % i] \
-                    + params["u%d/bn/beta" % i]
-        us.append(u.astype(F32))
+                mean = u.mean(axis=0, dtype=D)
+                var = ((u - mean) ** 2).mean(axis=0, dtype=D)   # biased, as tf.nn.moments
+                u = (u - mean) / np.sqrt(var + D(eps)) * c(params["u%d/bn/gamma" % i]) \
+                    + c(params["u%d/bn/beta" % i])
+        us.append(u.astype(D))
         prev = us[-1]
     return us
 
 
-def context(params, x, szs, batchnorm=True):
+def context(params, x, szs, batchnorm=True, dtype=F32):
     """Everything in E(x, y) that does not depend on y, per layer i = 0..L:
          yu_i   = fc(prevU -> n)            multiplies y elementwise   (:363-365)
          zu_i   = fc(prevU -> s_i)          additive term              (:372-373)
          gate_i = relu(fc(prevU -> s_{i-1}))  multiplies z_{i-1}, i>0  (:354-356)
-    with prevU = x for i = 0 and u_{i-1} afterwards (:349, :384)."""
+    with prevU = x for i = 0 and u_{i-1} afterwards (:349, :384).  dtype as in u_path."""
+    D, c = dtype, _caster(dtype)
     L = len(szs)
-    us = u_path(params, x, L, batchnorm)
+    us = u_path(params, x, L, batchnorm, dtype=D)
     layers = []
     for i in range(L + 1):
-        prev = x.astype(F32) if i == 0 else us[i - 1]
-        yu = prev.dot(params["z%d_yu_u/W" % i]) + params["z%d_yu_u/b" % i]
-        zu = prev.dot(params["z%d_u/W" % i]) + params["z%d_u/b" % i]
+        prev = x.astype(D) if i == 0 else us[i - 1]
+        yu = prev.dot(c(params["z%d_yu_u/W" % i])) + c(params["z%d_yu_u/b" % i])
+        zu = prev.dot(c(params["z%d_u/W" % i])) + c(params["z%d_u/b" % i])
         gate = None
         if i > 0:
-            gate = np.maximum(prev.dot(params["z%d_zu_u/W" % i]) + params["z%d_zu_u/b" % i], F32(0))
-        layers.append(dict(yu=yu.astype(F32), zu=zu.astype(F32),
-                           gate=None if gate is None else gate.astype(F32)))
+            gate = np.maximum(prev.dot(c(params["z%d_zu_u/W" % i])) + c(params["z%d_zu_u/b" % i]), D(0))
+        layers.append(dict(yu=yu.astype(D), zu=zu.astype(D),
+                           gate=None if gate is None else gate.astype(D)))
     return layers
 
 
@@ -124,15 +135,15 @@ def make_fg(params, x, szs, alpha=0.0, batchnorm=True, box=None):
     return fg
 
 
-def flat_context(ctx):
-    """[B, C] float32 in the order the HIP kernels read it (include/icnn_be.h):
+def flat_context(ctx, dtype=F32):
+    """[B, C] float32 (or `dtype`) in the order the HIP kernels read it (include/icnn_be.h):
     for each layer i: yu_i (n) | zu_i (s_i) | gate_i (s_{i-1}, i > 0)."""
     parts = []
     for c in ctx:
         parts += [c["yu"], c["zu"]]
         if c["gate"] is not None:
             parts.append(c["gate"])
-    return np.ascontiguousarray(np.concatenate(parts, axis=1), dtype=F32)
+    return np.ascontiguousarray(np.concatenate(parts, axis=1), dtype=dtype)
 
 
 def unflatten_context(flat, n, widths):
