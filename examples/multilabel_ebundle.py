@@ -1,11 +1,13 @@
 """A short bundle-entropy training loop on seeded synthetic multi-label data, every iteration one replay of a captured
 train.BundleTrainer.step (the loop of multi-label-cls/icnn_ebundle.py:208-250 without a host wait inside the step).
 
-    python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10]
+    python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10] [--test-every 20]
 
 The labels are a noisy linear function of the features; the loss falls from the first steps on (685 to 639 over the
 default 60 steps on an MI355X).
 The host reads the loss and the F1 tallies only every `--every` steps, after a synchronisation of its own choosing.
+Every `--test-every` steps (0: never) the test phase of the script (:257-277) runs on a held-out split of the same
+distribution: one replay of a captured train.BundleTrainer.evaluate, then the test loss and macro-F1.
 """
 import argparse
 import os
@@ -23,16 +25,20 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--every", type=int, default=10)
+    ap.add_argument("--test-every", type=int, default=20)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     rng = np.random.RandomState(0)
-    n_features, n_labels, n_train = 40, 16, 1024
+    n_features, n_labels, n_train, n_test = 40, 16, 1024, 256
     spec = picnn.FCSpec(n_features, n_labels, (64, 32), alpha=0.0, batchnorm=True, action_box=False)
     X = rng.rand(n_train, n_features).astype(np.float32)
     W = rng.randn(n_features, n_labels)
     Y = ((X - 0.5) @ W + 0.3 * rng.randn(n_train, n_labels) > 0.8).astype(np.float64)
+    held_out = np.random.RandomState(1)                    # a generator of its own: the training data stay what they were
+    Xt = held_out.rand(n_test, n_features).astype(np.float32)
+    Yt = ((Xt - 0.5) @ W + 0.3 * held_out.randn(n_test, n_labels) > 0.8).astype(np.float64)
     model = picnn.FCModel(spec, picnn.init_params(spec, 0, "spread"), "cuda")
-    trainer = train.BundleTrainer(model, a.batch, n_iter=10, loss="xent", lr=1e-3)
+    trainer = train.BundleTrainer(model, a.batch, n_iter=10, loss="xent", lr=1e-3, eval_batch=n_test if a.test_every else None)
     Xd, Yd = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
 
     def batch():
@@ -50,6 +56,15 @@ def main():
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         trainer.step(None, None)
+    test_graph = None
+    if a.test_every:                                       # the whole held-out split is one evaluation batch
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            trainer.evaluate(torch.from_numpy(Xt).cuda(), torch.from_numpy(Yt).cuda())
+        torch.cuda.current_stream().wait_stream(s)
+        test_graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(test_graph):
+            trainer.evaluate(None, None)
     for i in range(1, a.steps + 1):
         batch()
         graph.replay()
@@ -59,6 +74,11 @@ def main():
             print("step %4d  loss %10.4f  macro F1 %.3f  feed rows %d of %d  fg evaluations %d"
                   % (i, float(trainer.loss.item()), trainer.macro_f1(), int(trainer.rows.item()), trainer.feed.row_cap,
                      int(trainer.fg_evals.item())))
+        if test_graph is not None and (i % a.test_every == 0 or i == a.steps):
+            test_graph.replay()
+            torch.cuda.synchronize()
+            print("           test loss %10.4f  test macro F1 %.3f  (%d held-out examples)"
+                  % (float(trainer.eval_loss.item()), trainer.eval_macro_f1(), n_test))
 
 
 if __name__ == "__main__":

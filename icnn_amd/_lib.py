@@ -25,6 +25,7 @@ MAX_ROUNDS = 128
 VARIANT = {"dual": 0, "rl": 1, "pdipm": 2}
 CUT_F32, CUT_F64 = 0, 1
 ST_SINGULAR, ST_NONFINITE, ST_OVERFLOW, ST_UNFINISHED = 1, 2, 4, 8
+ST_ERROR_MASK = ST_SINGULAR | ST_NONFINITE | ST_UNFINISHED | ST_OVERFLOW      # what stops a training step (icnn_be_step_gate)
 FLAG_NO_CYCLE_SHORTCUT = 1
 FLAG_TIME_SLICE = 2
 FLAG_LOCKSTEP = 4
@@ -63,6 +64,7 @@ EXPORTS = [
     "icnn_be_conv_surrogate_grad_dev", "icnn_be_fc_context_bn_dev", "icnn_be_conv_context_bn_dev",
     "icnn_be_fc_surrogate_grad_dev_work_floats", "icnn_be_conv_surrogate_grad_dev_work_floats",
     "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed", "icnn_be_gd_feed_px_work_bytes", "icnn_be_gd_feed_px",
+    "icnn_be_step_gate", "icnn_be_param_update_gated", "icnn_be_gated_copy",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -301,6 +303,8 @@ def load():
     lib.icnn_be_feed_plan.restype = C.c_int
     lib.icnn_be_feed_pad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.icnn_be_feed_pad.restype = C.c_int
+    lib.icnn_be_step_gate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_step_gate.restype = C.c_int
     lib.icnn_be_gd_feed_work_bytes.argtypes = [C.c_int]
     lib.icnn_be_gd_feed_work_bytes.restype = C.c_size_t
     lib.icnn_be_gd_feed.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 7)
@@ -311,6 +315,10 @@ def load():
     lib.icnn_be_gd_feed_px.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
+    lib.icnn_be_param_update_gated.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p, C.c_void_p]
+    lib.icnn_be_param_update_gated.restype = C.c_int
+    lib.icnn_be_gated_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]
+    lib.icnn_be_gated_copy.restype = C.c_int
     lib.icnn_be_gd_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_gd_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_fc_gd.argtypes = ([C.POINTER(FcModel), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]

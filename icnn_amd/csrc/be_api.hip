@@ -574,6 +574,12 @@ int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_
     return e == hipSuccess ? 0 : fail(e);
 }
 
+int icnn_be_step_gate(const int *counts, int mask, int *gate, void *stream) {
+    if (!counts || !gate) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_step_gate(counts, mask, gate, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 size_t icnn_be_gd_feed_work_bytes(int B) { return B < 0 ? 0 : icnn_be::gd_feed_work_bytes(B); }
 
 int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, double *v_rows,
@@ -839,7 +845,21 @@ int icnn_be_ficnn_surrogate_grad(const icnn_be_ficnn_model *model, const float *
 
 int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {
     if (int rc = check_param_update(a)) return rc;
-    hipError_t e = icnn_be::launch_param_update(*a, static_cast<hipStream_t>(stream));
+    hipError_t e = icnn_be::launch_param_update(*a, nullptr, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_param_update_gated(const icnn_be_param_update_args *a, const int *go, void *stream) {
+    if (!go) return ICNN_BE_EINVAL;
+    if (int rc = check_param_update(a)) return rc;
+    hipError_t e = icnn_be::launch_param_update(*a, go, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_gated_copy(float *dst, const float *src, long long n, const int *go, int want, void *stream) {
+    if (!dst || !src || !go || n < 0) return ICNN_BE_EINVAL;
+    if (n == 0) return 0;
+    hipError_t e = icnn_be::launch_gated_copy(dst, src, n, go, want, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : fail(e);
 }
 

@@ -257,6 +257,7 @@ size_t feed_plan_work_bytes(int batch);
 hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream);
 hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
                            int *fd_sample, hipStream_t stream);
+hipError_t launch_step_gate(const int *counts, int mask, int *gate, hipStream_t stream);
 
 // ---- the back-optimisation training step's feed (be_train_gd.hip) -------------------
 struct GdFeedLaunch {
@@ -297,7 +298,8 @@ hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream);
 
 // ---- parameter update (be_train_update.hip) -----------------------------------------
 long long param_update_blocks(long long n);
-hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream);
+hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream);   // go NULL: ungated
+hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream);
 
 // ---- the RL critic's step (be_rl_train.hip) -----------------------------------------
 struct RlTdLaunch {

@@ -9,6 +9,9 @@
 //                      n_iters / finished / status to the fg evaluation count (bundle_entropy.fg_evaluations) and the OR
 //                      of the status words.  Every sum has one fixed order: the same bits on every call.
 //   feed_pad_kernel    rows [rows, row_cap) of a fixed-capacity feed: y = 0.5, v = 0, c = 0, sample B - 1.
+//   step_gate_kernel   the skip on a solver error (completion/icnn_ebundle.py:225-237) as three words of device memory, from
+//                      the plan's counts: go, the BatchNorm fold count of a step that goes, the running total of steps that
+//                      did not.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -152,6 +155,15 @@ __global__ void feed_pad_kernel(const int *rows, int batch, int n, int row_cap, 
     }
 }
 
+// one workgroup, one lane: gate[2] is read and written by this lane alone, launches on a stream are ordered
+__global__ void step_gate_kernel(const int *counts, int mask, int *gate) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int go = (counts[2] & mask) == 0;
+    gate[0] = go;
+    gate[1] = go ? counts[1] : 0;
+    gate[2] = gate[2] + (go ? 0 : 1);
+}
+
 }  // namespace
 
 // the per-sample loss parts (8-byte aligned) and the ticket
@@ -172,6 +184,10 @@ hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, doubl
     const int blocks = (int)((most + 255) / 256 < 2048 ? (most + 255) / 256 : 2048);
     return launch_kernel(feed_pad_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, rows, batch, n, row_cap, fd_y,
                          fd_v, fd_c, fd_sample);
+}
+
+hipError_t launch_step_gate(const int *counts, int mask, int *gate, hipStream_t stream) {
+    return launch_kernel(step_gate_kernel, dim3(1), dim3(64), 0, stream, counts, mask, gate);
 }
 
 }  // namespace icnn_be

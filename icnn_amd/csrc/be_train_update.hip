@@ -11,6 +11,11 @@
 //   theta = theta - (lr_t * m) / (sqrt(v) + eps)
 //   theta = 0 if theta < 0 and the element is a proj weight (np.maximum(theta, 0): -0 and NaN stay)
 // lr_t = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t)) in double from the step count t, as train.TFAdam computes it.
+//
+// The gated form (icnn_be_param_update_gated) is the same kernel body behind one word of device memory: a
+// workgroup that reads *go == 0 leaves before it loads, stores or takes a ticket, so theta, m, v, the arena and both step
+// words stay as they were.  gated_copy_kernel is the gate's other consumer: dst = src when (*go != 0) == (want != 0), which
+// puts the BatchNorm moving statistics of a skipped step back from their shadow.
 #include "be_kernels.h"
 
 namespace icnn_be {
@@ -23,6 +28,7 @@ constexpr int UPD_PER_THREAD = 4;
 struct UpdArgs {
     icnn_be_param_update_args a;
     float b1, c1, b2, c2;
+    const int *go;       // the gated form's word; not read by the plain one
 };
 
 __device__ __forceinline__ bool in_proj(const icnn_be_param_update_args &a, long long j) {
@@ -31,11 +37,20 @@ __device__ __forceinline__ bool in_proj(const icnn_be_param_update_args &a, long
     return p;
 }
 
+template <bool GATED>
 __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
 #pragma clang fp contract(off)
     const icnn_be_param_update_args &a = u.a;
     __shared__ float s_lr_t;
     __shared__ int s_t;
+    if (GATED) {
+        // one read per workgroup; the word is not written while this launch runs, so every workgroup sees the same value
+        // and either all of them take a ticket or none does
+        __shared__ int s_go;
+        if (threadIdx.x == 0) s_go = *u.go;
+        __syncthreads();
+        if (s_go == 0) return;
+    }
     if (threadIdx.x == 0) {
         // updates done so far; the last workgroup of this launch writes t back only after every workgroup has taken its
         // ticket, and every workgroup reads the count before it takes one
@@ -103,6 +118,19 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
     }
 }
 
+constexpr int COPY_THREADS = 256;
+constexpr int COPY_MAX_BLOCKS = 1024;
+
+__global__ __launch_bounds__(COPY_THREADS) void gated_copy_kernel(float *dst, const float *src, long long n, const int *go,
+                                                                   int want) {
+    __shared__ int s_go;
+    if (threadIdx.x == 0) s_go = *go;
+    __syncthreads();
+    if ((s_go != 0) != (want != 0)) return;
+    const long long stride = (long long)gridDim.x * COPY_THREADS;
+    for (long long i = (long long)blockIdx.x * COPY_THREADS + threadIdx.x; i < n; i += stride) dst[i] = src[i];
+}
+
 }  // namespace
 
 long long param_update_blocks(long long n) {
@@ -110,14 +138,24 @@ long long param_update_blocks(long long n) {
     return (n + per_block - 1) / per_block;
 }
 
-hipError_t launch_param_update(const icnn_be_param_update_args &a, hipStream_t stream) {
+// go NULL: the plain update
+hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream) {
     UpdArgs u{};
     u.a = a;
     u.b1 = (float)a.beta1;
     u.c1 = (float)(1.0 - a.beta1);
     u.b2 = (float)a.beta2;
     u.c2 = (float)(1.0 - a.beta2);
-    return launch_kernel(param_update_kernel, dim3((unsigned)param_update_blocks(a.n)), dim3(UPD_THREADS), 0, stream, u);
+    u.go = go;
+    const dim3 grid((unsigned)param_update_blocks(a.n)), block(UPD_THREADS);
+    return go ? launch_kernel(param_update_kernel<true>, grid, block, 0, stream, u)
+              : launch_kernel(param_update_kernel<false>, grid, block, 0, stream, u);
+}
+
+hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream) {
+    const long long blocks = (n + COPY_THREADS - 1) / COPY_THREADS;
+    return launch_kernel(gated_copy_kernel, dim3((unsigned)(blocks < COPY_MAX_BLOCKS ? blocks : COPY_MAX_BLOCKS)),
+                         dim3(COPY_THREADS), 0, stream, dst, src, n, go, want);
 }
 
 }  // namespace icnn_be

@@ -283,6 +283,28 @@ class _BnMovingStats:
         """The moving statistics as host float32 arrays (waits for the work enqueued on the device)."""
         return {k: t.cpu().numpy().copy() for k, t in self.bn_stats.items()}
 
+    def flatten_bn_stats(self, align=64):
+        """Move the moving statistics into ONE float32 device buffer (every tensor of bn_stats becomes a view of it, in
+        bn_layers order, each starting on a multiple of `align` floats; values kept) and return that buffer, so that one copy
+        saves or restores all of them (train.BundleTrainer(skip_on_error=True)).  The tensors' addresses change: call it before
+        capturing anything that reads bn_stats.  Idempotent; a model without BatchNorm gets an empty buffer."""
+        flat = getattr(self, "_bn_flat", None)
+        if flat is not None:
+            return flat
+        keys = [k % i for i, _ in bn_layers(self.spec) for k in ("u%d/bn/moving_mean", "u%d/bn/moving_variance")]
+        assert set(keys) == set(self.bn_stats)
+        offs, at = [], 0
+        for k in keys:
+            offs.append(at)
+            at += -(-self.bn_stats[k].numel() // align) * align
+        flat = torch.zeros(at, dtype=torch.float32, device=self.device)
+        for k, off in zip(keys, offs):
+            view = flat[off:off + self.bn_stats[k].numel()]
+            view.copy_(self.bn_stats[k])
+            self.bn_stats[k] = view
+        self._bn_flat = flat
+        return flat
+
     def _c_bn(self):
         from . import _lib
         mv = _lib.BnMoving()

@@ -15,7 +15,9 @@
     BundleTrainer   one whole iteration of the bundle-entropy training loops without a host wait (capturable): context,
                     fused solve, FeedPlan (be_train_bundle.hip: row offsets, row count, fg evaluations, status OR, loss, F1
                     tallies), BatchNorm folds with a device count, PaddedFeed, surrogate_grad(rows_dev=), DeviceAdam.step
-                    (DESIGN.md §15).
+                    (DESIGN.md §15); the start point y0, the scripts' test phase as evaluate() and the device-side skip of
+                    the update on a solver error (icnn_be_step_gate, icnn_be_param_update_gated, icnn_be_gated_copy;
+                    DESIGN.md §18).
 
     unrolled_grad   the parameter gradient of a loss of y_K through the unrolled momentum-GD inference of gd.solve (the
                     back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
@@ -481,9 +483,13 @@ class DeviceAdam(_ArenaOwner):
         """updates done (reads the device counter: synchronises)"""
         return int(self.step_count[0].item())
 
-    def step(self, grad):
+    def step(self, grad, go=None):
         """One update with `grad`: the flat float32 [n] tensor surrogate_grad(..., flat=True) returns, or its dict form.
-        Enqueued on the current stream, no host synchronisation (capturable)."""
+        Enqueued on the current stream, no host synchronisation (capturable).  go: an int32 device tensor (one element,
+        icnn_be_step_gate's gate[0]); the update happens only where it is non-zero when the launch runs, and a launch that
+        finds 0 changes nothing, the step count included (icnn_be_param_update_gated)."""
+        if go is not None and (not torch.is_tensor(go) or go.dtype != torch.int32 or go.numel() != 1 or not go.is_cuda):
+            raise ValueError("go is one int32 on the device")
         if isinstance(grad, dict):
             grad = torch.cat([grad[name].reshape(-1) for name, _ in self.layout])
         grad = grad.to(self.device, torch.float32)
@@ -493,6 +499,10 @@ class DeviceAdam(_ArenaOwner):
             grad = grad.clone()
         self._args.grad = grad.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if go is not None:
+            _lib.check(self.model._lib.icnn_be_param_update_gated(C.byref(self._args), go.data_ptr(), C.c_void_p(stream)),
+                       "icnn_be_param_update_gated")
+            return
         _lib.check(self.model._lib.icnn_be_param_update(C.byref(self._args), C.c_void_p(stream)), "icnn_be_param_update")
 
     def load(self, params):
@@ -564,16 +574,38 @@ class BundleTrainer:
     picnn.FCModel; completion/icnn_ebundle.py with loss "mse" on a picnn.ConvModel) at one batch size, all of it enqueued
     on the current stream without a host wait, so a step can be captured in a CUDA graph:
 
-        context (batch statistics) -> FusedSolver.solve from y0 = 0.5 -> FeedPlan -> BatchNorm folds for the solve's fg
+        context (batch statistics) -> FusedSolver.solve from y0 -> FeedPlan -> BatchNorm folds for the solve's fg
         evaluations (models with BatchNorm) -> PaddedFeed -> surrogate_grad(bn_updates=1, rows_dev=) -> DeviceAdam.step
 
     Constructing one ATTACHES the model to its DeviceAdam and allocates every buffer; step allocates nothing.  After a step
     the device tensors loss (float64, what the reference prints as l_yN / the squared error), f1_tallies ("xent": int32 [B,
     3], see macro_f1), rows, fg_evals, status_or (int32 [1] each) and grad (the flat gradient) hold its results; read them
-    after a synchronisation of your choosing.  The update is NOT skipped on a solver error as the reference's completion loop
-    does on LinAlgError: call raise_on_error() and reload the weights if you need that."""
+    after a synchronisation of your choosing.
 
-    def __init__(self, model, batch, n_iter=10, loss="xent", variant="pdipm", lr=1e-3):
+    y0: the start point of every solve -- a scalar (0.5, the multi-label script), an [n] row (the completion script's
+    meanY, completion/icnn_ebundle.py:223-227), an image [H, W, 1] or a [B, n] array (images [B, H, W, 1] too); set_y0
+    replaces it, outside a capture.
+
+    skip_on_error=False: the update is NOT skipped on a solver error as the reference's completion loop does on LinAlgError;
+    call raise_on_error() and reload the weights if you need that.  skip_on_error=True: the skip happens on the device
+    (DESIGN.md §18).  Behind the plan icnn_be_step_gate turns status_or into the words went (int32 [1]: 1 when no sample has
+    ST_SINGULAR, ST_NONFINITE, ST_UNFINISHED or ST_OVERFLOW set) and skipped (int32 [1]: the running count of steps that did
+    not go, the reference's nErrors; giving up after some number of them stays the caller's policy, read it when you read the
+    loss).  The feed, the gradient and the loss of such a step are still computed and may be garbage; its update is
+    icnn_be_param_update_gated and its BatchNorm folds are undone from a shadow (icnn_be_gated_copy), so theta, m, v, the
+    arena, the step count and model.bn_stats are bit for bit what they were before the step.  The model's moving statistics
+    move into one buffer for that (model.flatten_bn_stats()).
+
+    eval_batch = E also allocates the scripts' test phase (multi-label-cls/icnn_ebundle.py:257-277,
+    completion/icnn_ebundle.py:264-300): evaluate(x, true_y) runs the context in eval_bn mode without a fold, a solve of its
+    own from y0 and a plan of its own on exactly E samples; it returns the float64 device scalar eval_loss, keeps y_eval and,
+    for "xent", eval_f1_tallies (eval_macro_f1() reads them), and changes no weight, optimiser state, statistic or result of
+    the training step.  eval_bn=None is what each script does at test time: "batch" for an FCModel (the multi-label script
+    keeps is_training(True), :259), "moving" for a ConvModel (the completion script sets is_training(False), :266).  A [B, n]
+    y0 serves the test phase only when E = B."""
+
+    def __init__(self, model, batch, n_iter=10, loss="xent", variant="pdipm", lr=1e-3, y0=0.5, eval_batch=None, eval_bn=None,
+                 skip_on_error=False):
         from .bundle_entropy import FusedSolver
         if loss not in _lib.LOSS:
             raise ValueError("loss must be 'xent' or 'mse', got %r" % (loss,))
@@ -587,12 +619,22 @@ class BundleTrainer:
         self.batch = int(batch)
         if self.batch < 1:
             raise ValueError("batch must be >= 1")
+        self.eval_batch = None if eval_batch is None else int(eval_batch)
+        if self.eval_batch is not None and self.eval_batch < 1:
+            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
+        self.conv = isinstance(model, ConvModel)
+        if eval_bn is None:
+            eval_bn = "moving" if self.conv else "batch"
+        if eval_bn not in _lib.BN_MODE:
+            raise ValueError("eval_bn must be 'batch' or 'moving', got %r" % (eval_bn,))
+        self.eval_bn, self.skip_on_error = eval_bn, bool(skip_on_error)
         self.model, self.spec, self.device = model, model.spec, model.device
         self.n_iter, self.loss_name, self.variant, self.lr = int(n_iter), loss, variant, float(lr)
-        self.conv = isinstance(model, ConvModel)
         self.has_bn = self.conv or bool(getattr(self.spec, "batchnorm", False))
         self.opt = DeviceAdam(model, lr=lr)
-        B, dev, n = self.batch, self.device, self.spec.n_labels
+        B, E, dev, n = self.batch, self.eval_batch, self.device, self.spec.n_labels
+        if E is not None and hasattr(model, "reserve"):
+            model.reserve(max(B, E))                    # grown here, never inside a capture
         self.solver = FusedSolver(model, B, self.n_iter, variant)
         st = self.solver.state
         self.plan = FeedPlan(st, loss)
@@ -608,25 +650,112 @@ class BundleTrainer:
         self.loss, self.f1_tallies = self.plan.loss, self.plan.f1_tallies
         self.rows, self.fg_evals, self.status_or = self.plan.rows, self.plan.fg_evals, self.plan.status_or
         self.row_offset = self.plan.row_offset
+        self.went = self.skipped = self._gate = self._bn_live = self._bn_shadow = None
+        if self.skip_on_error:
+            self._gate = torch.zeros(3, dtype=torch.int32, device=dev)              # go, folds, skipped
+            self.went, self.skipped = self._gate[0:1], self._gate[2:3]
+            if self.has_bn:
+                self._bn_live = model.flatten_bn_stats()
+                self._bn_shadow = torch.empty_like(self._bn_live)
+        self.y_eval = self.eval_loss = self.eval_f1_tallies = None
+        if E is not None:
+            self.eval_solver = FusedSolver(model, E, self.n_iter, variant)
+            self.eval_plan = FeedPlan(self.eval_solver.state, loss)
+            self.x_eval = torch.zeros((E,) + x_shape[1:], dtype=torch.float32, device=dev)
+            self.true_y_eval = torch.zeros(E, n, dtype=torch.float64, device=dev)
+            self.ctx_eval = torch.empty(E, self.spec.ctx_width, dtype=torch.float32, device=dev)
+            self._ctx_work_eval = torch.empty(model.context_work_floats(E), dtype=torch.float32, device=dev)
+            self.y_eval, self.eval_loss = self.eval_solver.y, self.eval_plan.loss
+            self.eval_f1_tallies = self.eval_plan.f1_tallies
+        self.y0 = self.y0_eval = None                   # float64 [B, n] / [E, n] once a start point is not a scalar
+        self._y0_scalar = 0.5
+        self.set_y0(y0)
 
-    def step(self, x=None, true_y=None) -> torch.Tensor:
-        """One iteration on (x, true_y [B, n]); None keeps the batch of the previous call (graph replay).  Returns the loss at
-        y* (before the update), a float64 device scalar."""
+    def set_y0(self, y0):
+        """The start point of step() and evaluate(): a scalar, an [n] row, an image [H, W, 1] or a [B, n] array ([B, H, W, 1]
+        too).  A copy from the host: call it outside a capture (a captured step keeps the KIND of start point it was captured
+        with: a scalar fills, anything else is copied from the tensors this call writes)."""
+        n = self.spec.n_labels
+        y0 = torch.as_tensor(y0, dtype=torch.float64)
+        if y0.dim() == 0:                               # the solver's fill_, as before there was a y0
+            self._y0_scalar = float(y0)
+            return
+        y0 = y0.to(self.device)
+        if y0.dim() >= 3 and y0.numel() % n == 0:       # an image, or one per sample
+            y0 = y0.reshape(-1, n)
+        if y0.dim() == 2 and y0.shape[0] == 1:
+            y0 = y0[0]
+        if y0.dim() > 2 or y0.shape[-1] != n or (y0.dim() == 2 and y0.shape[0] != self.batch):
+            raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
+                             % (n, self.batch, tuple(y0.shape)))
+        if self.eval_batch is not None:
+            if y0.dim() == 2 and self.eval_batch != self.batch:
+                raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
+            if self.y0_eval is None:
+                self.y0_eval = torch.empty(self.eval_batch, n, dtype=torch.float64, device=self.device)
+            self.y0_eval.copy_(y0.expand(self.eval_batch, n))
+        if self.y0 is None:
+            self.y0 = torch.empty(self.batch, n, dtype=torch.float64, device=self.device)
+        self.y0.copy_(y0.expand(self.batch, n))
+        self._y0_scalar = None
+
+    def _infer(self, x=None, true_y=None):
+        """the first half of step(): the copies, the context, the solve from y0 and the plan"""
         if x is not None:
             self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
         if true_y is not None:
             self.true_y.copy_(torch.as_tensor(true_y).to(self.device, torch.float64).reshape(self.true_y.shape))
-        model = self.model
-        model.context(self.x, out=self.ctx, work=self._ctx_work)
-        self.solver.solve(self.ctx, 0.5)
+        self.model.context(self.x, out=self.ctx, work=self._ctx_work)
+        self.solver.solve(self.ctx, self.y0 if self._y0_scalar is None else self._y0_scalar)
         self.plan.run(self.true_y)
+
+    def _learn(self):
+        """the second half of step(): the gate (skip_on_error), the BatchNorm folds, the feed, the gradient and the update,
+        all from what the plan left on the device"""
+        model, lib, gated = self.model, self.model._lib, self.skip_on_error
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if gated:
+            _lib.check(lib.icnn_be_step_gate(self.plan.counts.data_ptr(), _lib.ST_ERROR_MASK, self._gate.data_ptr(), stream),
+                       "icnn_be_step_gate")
+            if self.has_bn:
+                self._bn_shadow.copy_(self._bn_live)
         if self.has_bn:
             model.context(self.x, bn_updates=self.fg_evals, out=self._ctx_fold, work=self._ctx_work)
         self.feed.fill(self.plan, self.true_y)
         surrogate_grad(model, self.x, (self.feed.y, self.feed.v, self.feed.c), row_offset=self.row_offset, bn_updates=1,
                        flat=True, rows_dev=self.rows, out=self.grad, work=self._grad_work)
-        self.opt.step(self.grad)
+        self.opt.step(self.grad, go=self.went)
+        if gated and self.has_bn:                       # a step that did not go folds nothing
+            _lib.check(lib.icnn_be_gated_copy(self._bn_live.data_ptr(), self._bn_shadow.data_ptr(), self._bn_live.numel(),
+                                              self.went.data_ptr(), 0, stream), "icnn_be_gated_copy")
+
+    def step(self, x=None, true_y=None) -> torch.Tensor:
+        """One iteration on (x, true_y [B, n]); None keeps the batch of the previous call (graph replay).  Returns the loss at
+        y* (before the update), a float64 device scalar."""
+        self._infer(x, true_y)
+        self._learn()
         return self.loss
+
+    def evaluate(self, x=None, true_y=None) -> torch.Tensor:
+        """The test phase on exactly eval_batch samples (x, true_y shaped as for step; None keeps the previous ones): the loss
+        at y* of a solve from y0 with the context in eval_bn mode, a float64 device scalar (eval_loss); y_eval keeps y* and
+        eval_f1_tallies ("xent") the tallies.  Nothing is updated and no statistic is folded.  No host wait (capturable)."""
+        if self.eval_batch is None:
+            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        if x is not None:
+            self.x_eval.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x_eval.shape))
+        if true_y is not None:
+            self.true_y_eval.copy_(torch.as_tensor(true_y).to(self.device, torch.float64).reshape(self.true_y_eval.shape))
+        self.model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
+        self.eval_solver.solve(self.ctx_eval, self.y0_eval if self._y0_scalar is None else self._y0_scalar)
+        self.eval_plan.run(self.true_y_eval)
+        return self.eval_loss
+
+    def eval_macro_f1(self) -> float:
+        """the test F1 of the last evaluate() (util.macroF1; "xent" only; one wait)"""
+        if self.eval_f1_tallies is None:
+            raise ValueError("F1 tallies exist for loss 'xent' and a trainer constructed with eval_batch only")
+        return macro_f1(self.eval_f1_tallies)
 
     def raise_on_error(self):
         """BundleResult.raise_on_error from status_or (reads it: one wait).  The OR names no sample."""

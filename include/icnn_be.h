@@ -587,6 +587,18 @@ ICNN_BE_API int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap,
                                  int *fd_sample, void *stream);
 
 /*
+ * The skip of a training step on a solver error (completion/icnn_ebundle.py:225-237) as device words,
+ * one workgroup.  counts: the [3] int32 of icnn_be_feed_plan (rows, fg evaluations, OR of the status words); mask: the
+ * ICNN_BE_ST_* bits that stop a step; gate: [3] int32 in device memory, ZEROED ONCE by the caller:
+ *   gate[0]  "go"       1 if (counts[2] & mask) == 0, else 0
+ *   gate[1]  "folds"    counts[1] if go, else 0 (the BatchNorm fold count of a step that goes)
+ *   gate[2]  "skipped"  a running total: + 1 on every launch that does not go; the kernel never resets it
+ * gate[0] is the word icnn_be_param_update_gated and icnn_be_gated_copy take as `go`.  EINVAL for counts or gate NULL before
+ * anything is launched.  Vector stores only, no atomics, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_step_gate(const int *counts, int mask, int *gate, void *stream);
+
+/*
  * icnn_be_fc_surrogate_grad_bn / icnn_be_conv_surrogate_grad_bn over a feed of `rows` = row_cap rows of which only the
  * first *rows_dev (a device int32, = row_offset[batch]) are real: the rest is padding as icnn_be_feed_pad writes it and
  * contributes exactly nothing.  The work size is icnn_be_{fc,conv}_surrogate_grad_dev_work_floats(model, c, batch, rows) --
@@ -710,6 +722,23 @@ typedef struct icnn_be_param_update_args {
 } icnn_be_param_update_args;
 
 ICNN_BE_API int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream);
+
+/*
+ * icnn_be_param_update behind one int32 of device memory (icnn_be_step_gate's gate[0]), read once per workgroup.
+ * *go != 0: icnn_be_param_update, bit for bit -- theta, m, v, every arena copy, step[0].  *go == 0: nothing is written to
+ * theta, m, v or the arena, step[0] stays and the ticket step[1] stays zero, so a later launch is exactly the update it would
+ * have been without this one.  *go must not change while the launch runs.  EINVAL for go NULL and for everything
+ * icnn_be_param_update refuses, before anything is launched.  No host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_param_update_gated(const icnn_be_param_update_args *a, const int *go, void *stream);
+
+/*
+ * dst[0, n) = src[0, n) (float32) when (*go != 0) == (want != 0); otherwise dst is left alone.  With want = 0 it puts back
+ * what a skipped step must not have changed -- the BatchNorm moving statistics, from a shadow taken before the step's folds.
+ * *go is read once per workgroup.  EINVAL for dst, src or go NULL or n < 0; n = 0 launches nothing.  Vector stores only, no
+ * host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_gated_copy(float *dst, const float *src, long long n, const int *go, int want, void *stream);
 
 /* ---- the RL agent's critic step: TD target, loss, decay, Adam, proj, soft target update (be_rl_train.hip, additive to ABI 12) */
 
