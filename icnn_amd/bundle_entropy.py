@@ -470,8 +470,7 @@ class FusedSolver:
         dev = _pick_device(device if device is not None else model.device)
         n = model.spec.n_labels
         self.model, self.batch, self.n_iter = model, batch, n_iter
-        if hasattr(model, "reserve"):
-            model.reserve(batch)
+        model.reserve(batch)
         self.y = torch.empty(batch, n, dtype=torch.float64, device=dev)
         self.state = BundleState(self.y, n_iter, variant, torch.float32, flags, slots)
         self.f_work = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)

@@ -24,8 +24,8 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from . import _lib, gd, train
-from .picnn import _trunc_normal
+from . import _lib, gd, picnn, train
+from .picnn import _DeviceWeights, _host_ptr, _trunc_normal
 
 
 @dataclass(frozen=True)
@@ -65,6 +65,9 @@ class FICNNSpec:
     def ctx_width(self) -> int:
         return sum(self.widths[:self.evaluated])
 
+    def grad_layout(self) -> List[Tuple[str, tuple]]:
+        return grad_layout(self)
+
 
 def synthetic_spec(head="sum") -> FICNNSpec:
     """synthetic-cls defaults: 2-d points, one label, hidden layers [200, 200] (icnn.py:217)"""
@@ -92,27 +95,20 @@ def init_params(spec: FICNNSpec, seed=0) -> Dict[str, np.ndarray]:
 
 def make_convex(params):
     """reference `makeCvx` (icnn.py:145): |W| / 10 on every 'proj' weight"""
-    for k in params:
-        if "proj" in k and k.endswith("/W"):
-            params[k] = (np.abs(params[k]) / np.float32(10.0)).astype(np.float32)
-    return params
+    return picnn.make_convex(params, 10.0)
 
 
 def project(params):
     """reference `proj` (icnn.py:146): max(W, 0) on every 'proj' weight"""
-    for k in params:
-        if "proj" in k and k.endswith("/W"):
-            params[k] = np.maximum(params[k], 0)
-    return params
+    return picnn.project(params)
 
 
-class FICNNModel:
+class FICNNModel(_DeviceWeights):
     """Device-resident FICNN: every weight the kernels read packed into one buffer (context rows, MFMA fragments of the
     y- and z-weights in both orientations, head vectors) and the C descriptor.  Re-create, call `repack`, or attach a
     train.DeviceAdam after every weight update."""
-    solve_entry = "icnn_be_solve_ficnn"
-    gd_entry = "icnn_be_ficnn_gd"
-    _optimizer = None
+    solve_entry, gd_entry = "icnn_be_solve_ficnn", "icnn_be_ficnn_gd"
+    grad_entry, grad_floats_entry = "icnn_be_ficnn_surrogate_grad", "icnn_be_ficnn_grad_floats"
 
     def __init__(self, spec: FICNNSpec, params, device="cuda"):
         self.spec = spec
@@ -130,24 +126,18 @@ class FICNNModel:
         if n_floats == 0:
             raise ValueError("model shape rejected by libicnn_be (layer count / widths / LDS budget)")
         self.n_pack_floats = int(n_floats)
-        self.wpack = None
         self.repack(params)
 
-    # ---- weights -------------------------------------------------------------------------------------------
-    def _refuse_if_attached(self, what):
-        if self._optimizer is not None:
-            raise RuntimeError("%s: the weights of this model belong to a train.DeviceAdam; use its load(params)" % what)
+    def _descriptors(self):
+        return (C.byref(self.c_model),)
 
+    def check_x(self, x):
+        assert x.dim() == 2 and x.shape[1] == self.spec.n_features
+
+    # ---- weights -------------------------------------------------------------------------------------------
     def _pack_host(self, params) -> np.ndarray:
         """icnn_be_ficnn_pack of params: the host image of wpack (a copy of parameter elements, zeros elsewhere)"""
-        keep = []
-
-        def ptr(name):
-            a = np.ascontiguousarray(params[name], dtype=np.float32)
-            keep.append(a)
-            return a.ctypes.data
-
-        L1 = self.spec.n_layers
+        L1, ptr = self.spec.n_layers, _host_ptr(params)
         wx = (C.c_void_p * L1)(*[ptr("z_x%d/W" % i) for i in range(L1)])
         b = (C.c_void_p * L1)(*[ptr("z_x%d/b" % i) for i in range(L1)])
         wz = (C.c_void_p * L1)(*([None] + [ptr("z_z%d_proj/W" % i) for i in range(1, L1)]))
@@ -155,33 +145,16 @@ class FICNNModel:
         _lib.check(self._lib.icnn_be_ficnn_pack(C.byref(self.c_model), wx, b, wz, host.ctypes.data), "icnn_be_ficnn_pack")
         return host
 
-    def repack(self, params):
-        self._refuse_if_attached("repack")
-        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
-        self.c_model.wpack = self.wpack.data_ptr()
-        self.params = params
-
     def arena_parts(self, params):
         """the weight-arena hooks of train.DeviceAdam: one buffer, the pack"""
         return [("wpack", 0, self._pack_host(params))]
 
-    def _use_arena(self, optimizer, arena, parts, offsets):
-        (_, _, a), = parts
-        self.wpack = arena[offsets[0]:offsets[0] + a.size]
-        self.c_model.wpack = self.wpack.data_ptr()
-        self._arena_keep = arena
-        self._optimizer = optimizer
-        self.params = optimizer.params()
-
     # ---- evaluation ----------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def context(self, x: torch.Tensor) -> torch.Tensor:
         """x-only context rows [B, ctx_width] (c_i = x Wx_i + b_i) of x [B, n_features]; current stream."""
         x = x.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
-        assert x.dim() == 2 and x.shape[1] == self.spec.n_features
+        self.check_x(x)
         ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device)
         work = torch.empty(max(int(self._lib.icnn_be_ficnn_context_work_floats(C.byref(self.c_model), B)), 1),
                            dtype=torch.float32, device=self.device)
@@ -214,26 +187,11 @@ class FICNNModel:
 def surrogate_grad(model: FICNNModel, x: torch.Tensor, row_offset: torch.Tensor, y: torch.Tensor, v, c: torch.Tensor,
                    F_rows=None, flat=False):
     """train.surrogate_grad for a FICNNModel (icnn_be_ficnn_surrogate_grad); arguments already on the device."""
-    spec, dev = model.spec, model.device
-    B, R = x.shape[0], y.shape[0]
-    grad = torch.empty(int(model._lib.icnn_be_ficnn_grad_floats(C.byref(model.c_model))), dtype=torch.float32, device=dev)
-    if R == 0:
-        grad.zero_()
-    else:
-        n_work = int(model._lib.icnn_be_ficnn_surrogate_grad_work_floats(C.byref(model.c_model), B, R))
-        if n_work == 0:
-            raise ValueError("icnn_be_ficnn_surrogate_grad: shape rejected (batch %d, rows %d)" % (B, R))
-        work = torch.empty(n_work, dtype=torch.float32, device=dev)
-        if F_rows is not None:
-            assert F_rows.dtype == torch.float32 and F_rows.shape == (R,) and F_rows.is_contiguous()
-        _lib.check(model._lib.icnn_be_ficnn_surrogate_grad(
-            C.byref(model.c_model), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
-            None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(), None if F_rows is None else F_rows.data_ptr(),
-            work.data_ptr(), model._stream()), "icnn_be_ficnn_surrogate_grad")
-    return grad if flat else train.unpack_grad(spec, grad)
+    rows = (y, c) if v is None else (y, v, c)
+    return train.surrogate_grad(model, x, rows, row_offset=row_offset, F_rows=F_rows, flat=flat)
 
 
-class GDTrainer:
+class GDTrainer(train._Trainer):
     """The synthetic-cls training step (icnn.py:117-139, :189-194) at one batch size, all of it enqueued on the device:
     context, gd.solve(trajectory=True) from y0 = 0.5, the loss mean((y_K - t)^2) over B n and its adjoint
     ybar = float32(1/(B n)) (2 (y_K - t)) (TensorFlow's _MeanGrad / _SquareGrad), train.unrolled_grad, then DeviceAdam.step
@@ -243,9 +201,7 @@ class GDTrainer:
 
     def __init__(self, model: FICNNModel, batch: int, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5):
         self.model, self.spec, self.device = model, model.spec, model.device
-        self.batch = int(batch)
-        if self.batch < 1:
-            raise ValueError("batch must be >= 1")
+        self.batch = train._positive("batch", batch)
         self.n_iter, self.lr, self.momentum, self.y0 = int(n_iter), float(lr), float(momentum), float(y0)
         self.opt = train.DeviceAdam(model, lr=adam_lr)
         B, dev = self.batch, self.device
@@ -257,10 +213,8 @@ class GDTrainer:
 
     def step(self, x=None, t=None) -> torch.Tensor:
         """One step on (x [B, n_features], t [B, n]); None keeps the batch of the previous call (graph replay)."""
-        if x is not None:
-            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
-        if t is not None:
-            self.t.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t.shape))
+        self._put(self.x, x)
+        self._put(self.t, t)
         ctx = self.model.context(self.x)
         yK, traj, _ = gd.solve(self.model, ctx, self.y0, self.n_iter, self.lr, self.momentum, trajectory=True)
         d = yK.to(torch.float32) - self.t
@@ -269,13 +223,3 @@ class GDTrainer:
         grad = train.unrolled_grad(self.model, self.x, traj, ybar.to(torch.float64), self.lr, self.momentum, flat=True)
         self.opt.step(grad)
         return self.loss
-
-    @property
-    def t_steps(self) -> int:
-        return self.opt.t
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        return self.opt.params()
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.opt.host_params()

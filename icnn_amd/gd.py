@@ -17,7 +17,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .picnn import ConvModel
 
 
 def coefficients(n_iter: int, lr: float, momentum: float) -> np.ndarray:
@@ -40,7 +39,6 @@ def solve(model, ctx: torch.Tensor, y0, n_iter: int, lr: float, momentum: float,
     entry like a feed.  Returns (y, traj, energy): y float64 [B, n] = y_K (float32 values); traj float64 [B, n_iter, n] =
     y_0 .. y_{K-1} when `trajectory`, else None; energy float32 [B] = E(y_K) when `energy`, else None.  Enqueued on the
     current stream without any host synchronisation (capturable in a CUDA graph when y0 is a scalar or a device tensor)."""
-    conv = isinstance(model, ConvModel)
     spec, dev = model.spec, model.device
     n = spec.n_labels
     K = int(n_iter)
@@ -59,12 +57,10 @@ def solve(model, ctx: torch.Tensor, y0, n_iter: int, lr: float, momentum: float,
     traj = torch.empty(B, K, n, dtype=torch.float64, device=dev) if trajectory else None
     f = torch.empty(B, dtype=torch.float32, device=dev) if energy else None
     ws = torch.empty(max(int(model._lib.icnn_be_gd_workspace_bytes(B, n)), 1), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if conv:
-        model.reserve(B)
-    entry = "icnn_be_conv_gd" if conv else getattr(model, "gd_entry", "icnn_be_fc_gd")      # FICNNModel: icnn_be_ficnn_gd
+    model.reserve(B)
+    entry = model.gd_entry
     _lib.check(getattr(model._lib, entry)(
         C.byref(model.c_model), ctx.data_ptr(), y0.data_ptr(), B, K, float(lr), float(momentum), y.data_ptr(),
-        None if traj is None else traj.data_ptr(), None if f is None else f.data_ptr(), ws.data_ptr(), C.c_void_p(stream)),
+        None if traj is None else traj.data_ptr(), None if f is None else f.data_ptr(), ws.data_ptr(), model._stream()),
         entry)
     return y, traj, f

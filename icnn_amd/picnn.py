@@ -15,11 +15,14 @@ path) -- and (b) the *y-path weights* 'z{i}_yu/W' and
 Parameters are a dict of float32 arrays keyed by the reference's variable-scope
 names ('u0/W', 'z1_zu_proj/W', ...), W stored [in, out] as tflearn does.
 """
+import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
+
+from . import _lib
 
 
 @dataclass(frozen=True)
@@ -69,6 +72,25 @@ class FCSpec:
     def y_path_params(self) -> int:
         w, n = self.widths, self.n_labels
         return sum(n * w[i] + (w[i - 1] * w[i] if i > 0 else 0) for i in range(self.n_layers))
+
+    def grad_layout(self) -> List[Tuple[str, tuple]]:
+        """train.grad_layout of this spec: the order of init_params' keys"""
+        L, n, w = len(self.szs), self.n_labels, self.widths
+        out = []
+        prev = self.n_features
+        for i in range(L):
+            out += [("u%d/W" % i, (prev, self.szs[i])), ("u%d/b" % i, (self.szs[i],))]
+            if i < L - 1 and self.batchnorm:
+                out += [("u%d/bn/gamma" % i, (self.szs[i],)), ("u%d/bn/beta" % i, (self.szs[i],))]
+            prev = self.szs[i]
+        for i in range(L + 1):
+            in_u = self.n_features if i == 0 else self.szs[i - 1]
+            if i > 0:
+                out += [("z%d_zu_u/W" % i, (in_u, w[i - 1])), ("z%d_zu_u/b" % i, (w[i - 1],)),
+                        ("z%d_zu_proj/W" % i, (w[i - 1], w[i]))]
+            out += [("z%d_yu_u/W" % i, (in_u, n)), ("z%d_yu_u/b" % i, (n,)), ("z%d_yu/W" % i, (n, w[i])),
+                    ("z%d_u/W" % i, (in_u, w[i])), ("z%d_u/b" % i, (w[i],))]
+        return out
 
 
 def bibtex_spec():
@@ -260,11 +282,96 @@ def context(spec: FCSpec, params, x: torch.Tensor, all_reduce=None, batch_total=
     return ctx
 
 
-class _BnMovingStats:
-    """The BatchNorm moving statistics a device model owns (struct icnn_be_bn_moving): float32 device tensors keyed like
+def _host_ptr(params):
+    """ptr(name) -> the address of params[name] as a contiguous float32 array, for the C packers; the arrays stay
+    referenced for as long as ptr does"""
+    keep = []
+
+    def ptr(name):
+        a = np.ascontiguousarray(params[name], dtype=np.float32)
+        keep.append(a)
+        return a.ctypes.data
+    return ptr
+
+
+class _DeviceWeights:
+    """What the device models (FCModel, ConvModel, ficnn.FICNNModel) share: the upload of their weights and the weight arena
+    hooks of train.DeviceAdam.  A model class states the C entries it is served by -- solve_entry, gd_entry, grad_entry
+    (the stem of its surrogate-gradient entries), grad_floats_entry and grad_takes_stats --, _descriptors() (the leading
+    arguments they take), and check_x(x); it packs its weights in _pack_host(params) and lists the host arrays of its
+    context struct (_ctx_struct()) in _ctx_host(params): none for the FICNN, whose context reads the pack.
+
+    arena_parts(params) lists every buffer the kernels read -- ("wpack", 0, packed y-path), then ("w_stage" | "b_stage" |
+    "bn_gamma" | "bn_beta", index, array) in the order repack_context uploads them -- as host float32 arrays built by the
+    host packers.  Once a DeviceAdam owns the weights, c_model.wpack and every c_ctx pointer point into its arena for good,
+    `params` are live device views of its theta, and repack / repack_context / clamp raise instead of letting the packed
+    copies drift from theta."""
+    _optimizer = None
+    has_bn = False              # whether a u-layer is batch-normalised
+    grad_takes_stats = False    # whether its surrogate-gradient entries take moving statistics and a fold count (_c_bn())
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _descriptors(self):
+        return C.byref(self.c_model), C.byref(self.c_ctx)
+
+    def reserve(self, batch):
+        """Device scratch for evaluations of up to `batch` samples: none, but for the ConvModel."""
+
+    def _ctx_struct(self):
+        return None
+
+    def _ctx_host(self, params):
+        return []
+
+    def _refuse_if_attached(self, what):
+        if self._optimizer is not None:
+            raise RuntimeError("%s: the weights of this model belong to a train.DeviceAdam; use its load(params)" % what)
+
+    def repack_context(self, params):
+        """Upload the x-only weights (stage operands, BatchNorm gamma / beta) of the context producer."""
+        self._refuse_if_attached("repack_context")
+        c, keep = self._ctx_struct(), []
+        for field, i, a in self._ctx_host(params):
+            t = torch.from_numpy(a).to(self.device)
+            keep.append(t)
+            getattr(c, field)[i] = t.data_ptr()
+        self._ctx_keep, self.c_ctx = keep, c
+
+    def repack(self, params):
+        self._refuse_if_attached("repack")
+        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
+        self.c_model.wpack = self.wpack.data_ptr()
+        self.params = params
+        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
+        # the x-only stage weights follow the same parameter set
+        self.repack_context(params)
+
+    def arena_parts(self, params):
+        return [("wpack", 0, self._pack_host(params))] + self._ctx_host(params)
+
+    def _use_arena(self, optimizer, arena, parts, offsets):
+        c = self._ctx_struct()
+        for (field, i, a), off in zip(parts, offsets):
+            if field == "wpack":
+                self.wpack = arena[off:off + a.size]
+                self.c_model.wpack = self.wpack.data_ptr()
+            else:
+                getattr(c, field)[i] = arena.data_ptr() + 4 * off
+        self._ctx_keep, self.c_ctx = [arena], c
+        self._optimizer = optimizer
+        self.params = optimizer.params()
+
+
+class _PICNNDevice(_DeviceWeights):
+    """A PICNN on the device (FCModel, ConvModel): a _DeviceWeights model with a u-path, whose context has the BatchNorm
+    modes.  It owns the BatchNorm moving statistics (struct icnn_be_bn_moving): float32 device tensors keyed like
     init_bn_stats, updated in place (their addresses never change, so captured graphs keep finding them) and kept across
-    `repack`.  bn_decay: tflearn's `decay` (0.9)."""
+    `repack`.  bn_decay: tflearn's `decay` (0.9).  A class states context_entry, the stem of its context entries, and
+    _context_ends()."""
     bn_decay = 0.9
+    grad_takes_stats = True
 
     def _init_bn_stats(self):
         self.bn_stats = {k: torch.from_numpy(v).to(self.device) for k, v in init_bn_stats(self.spec).items()}
@@ -306,7 +413,6 @@ class _BnMovingStats:
         return flat
 
     def _c_bn(self):
-        from . import _lib
         mv = _lib.BnMoving()
         for i, _ in bn_layers(self.spec):
             mv.mean[i] = self.bn_stats["u%d/bn/moving_mean" % i].data_ptr()
@@ -325,55 +431,70 @@ class _BnMovingStats:
 
     @staticmethod
     def _bn_mode(bn, bn_updates):
-        from . import _lib
         if bn not in _lib.BN_MODE:
             raise ValueError("bn must be 'batch' or 'moving', got %r" % (bn,))
         if int(bn_updates) < 0 or (bn == "moving" and bn_updates):
             raise ValueError("bn_updates must be >= 0, and 0 in moving mode (got %r with bn=%r)" % (bn_updates, bn))
         return _lib.BN_MODE[bn]
 
+    def context_work_floats(self, batch) -> int:
+        """floats of the `work` buffer context(..., work=) takes at this batch size (any bn / bn_updates)"""
+        head, _ = self._context_ends()
+        return max(int(getattr(self._lib, self.context_entry + "_bn_work_floats")(head[0], batch)), 1)
 
-class _DeviceWeights:
-    """The weight arena hooks of a device model (train.DeviceAdam).  arena_parts(params) lists every buffer the kernels
-    read -- ("wpack", 0, packed y-path), then ("w_stage" | "b_stage" | "bn_gamma" | "bn_beta", index, array) in the order
-    repack_context uploads them -- as host float32 arrays built by the host packers.  Once a DeviceAdam owns the weights,
-    c_model.wpack and every c_ctx pointer point into its arena for good, `params` are live device views of its theta, and
-    repack / repack_context / clamp raise instead of letting the packed copies drift from theta."""
-    _optimizer = None
+    def context(self, x: torch.Tensor, bn="batch", bn_updates=0, out=None, work=None) -> torch.Tensor:
+        """x-only context rows [B, ctx_width] of the minibatch x (FCModel: [B, n_features]; ConvModel: [B, H, W, 1], already
+        h-flipped by the caller as completion/icnn_ebundle.py:215 does) by the HIP kernels of be_context.hip (one MFMA GEMM
+        per stage with routed epilogue, batch-statistics BatchNorm in place); current stream.  `context` / `conv_context`
+        above are the torch restatements the tests compare it with.
+        bn="moving": inference mode, BatchNorm with self.bn_stats (valid at batch 1; the completion test phase); bn="batch"
+        with bn_updates = k > 0: the same context, and the batch statistics folded k times into self.bn_stats (the *_context_bn
+        entry).  bn_updates may be an int32 device tensor (one element): the count is read on the device, no host wait
+        (*_context_bn_dev).  out / work: caller-owned buffers ([B, ctx_width] float32; context_work_floats(B) floats) for a
+        step that allocates nothing."""
+        k_dev = self._device_updates(bn, bn_updates) if torch.is_tensor(bn_updates) else None
+        mode = _lib.BN_MODE["batch"] if k_dev is not None else self._bn_mode(bn, bn_updates)
+        x = x.to(self.device, torch.float32).contiguous()
+        B = x.shape[0]
+        self.check_x(x)
+        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device) if out is None else out
+        assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32 and ctx.is_contiguous()
+        if work is not None:
+            assert work.dtype == torch.float32 and work.numel() >= self.context_work_floats(B)
+        entry, (head, tail) = self.context_entry, self._context_ends()
+        if k_dev is not None:
+            entry, bn_args = entry + "_bn_dev", (k_dev.data_ptr(),)
+        elif mode != _lib.BN_MODE["batch"] or bn_updates:
+            entry, bn_args = entry + "_bn", (mode, int(bn_updates))
+        else:
+            bn_args = ()
+        if bn_args:
+            mv = self._c_bn()
+            bn_args = (C.byref(mv),) + bn_args
+        if work is None:
+            if bn_args:
+                n_work = self.context_work_floats(B)
+            else:                                       # the plain entry has a work size of its own
+                n_work = max(int(getattr(self._lib, entry + "_work_floats")(head[0], B)), 1)
+            work = torch.empty(n_work, dtype=torch.float32, device=self.device)
+        _lib.check(getattr(self._lib, entry)(*head, *bn_args, x.data_ptr(), B, ctx.data_ptr(), *tail, work.data_ptr(),
+                                             self._stream()), entry)
+        return ctx
 
-    def _refuse_if_attached(self, what):
-        if self._optimizer is not None:
-            raise RuntimeError("%s: the weights of this model belong to a train.DeviceAdam; use its load(params)" % what)
 
-    def arena_parts(self, params):
-        return [("wpack", 0, self._pack_host(params))] + self._ctx_host(params)
-
-    def _use_arena(self, optimizer, arena, parts, offsets):
-        c = self._ctx_struct()
-        for (field, i, a), off in zip(parts, offsets):
-            if field == "wpack":
-                self.wpack = arena[off:off + a.size]
-                self.c_model.wpack = self.wpack.data_ptr()
-            else:
-                getattr(c, field)[i] = arena.data_ptr() + 4 * off
-        self._ctx_keep, self.c_ctx = [arena], c
-        self._optimizer = optimizer
-        self.params = optimizer.params()
-
-
-class FCModel(_BnMovingStats, _DeviceWeights):
-    solve_entry = "icnn_be_solve_fc"
+class FCModel(_PICNNDevice):
     """Device-resident y-path of one FC-PICNN: the packed 'z{i}_yu/W' / 'z{i}_zu_proj/W'
     weights (MFMA B-fragment order, both orientations) plus the C descriptor the
     kernels take.  Re-create (or call `repack`) after every weight update."""
+    solve_entry, gd_entry, context_entry = "icnn_be_solve_fc", "icnn_be_fc_gd", "icnn_be_fc_context"
+    grad_entry, grad_floats_entry = "icnn_be_fc_surrogate_grad", "icnn_be_fc_grad_floats"
 
     def __init__(self, spec: FCSpec, params, device="cuda"):
-        import ctypes as C
-
-        from . import _lib
         self.spec = spec
         self.params = params
         self.device = torch.device(device)
+        self.has_bn = bool(spec.batchnorm)
+        self.x_shape = (spec.n_features,)
         self._lib = _lib.load()
         m = _lib.FcModel()
         m.n = spec.n_labels
@@ -389,14 +510,16 @@ class FCModel(_BnMovingStats, _DeviceWeights):
         if n_floats == 0:
             raise ValueError("model shape rejected by libicnn_be (layer count / widths / LDS budget)")
         self.n_pack_floats = int(n_floats)
-        self.wpack = None
-        self._ctx_keep = None
-        self.c_ctx = None
         self._init_bn_stats()
         self.repack(params)                     # y-path pack + x-only stage weights
 
+    def check_x(self, x):
+        assert x.shape[1] == self.spec.n_features
+
+    def _context_ends(self):
+        return (C.byref(self.c_ctx),), (self.spec.ctx_width,)
+
     def _ctx_struct(self):
-        from . import _lib
         spec = self.spec
         c = _lib.FcCtx()
         c.n_features, c.n, c.n_layers = spec.n_features, spec.n_labels, spec.n_layers
@@ -416,94 +539,15 @@ class FCModel(_BnMovingStats, _DeviceWeights):
                         ("bn_beta", i, np.ascontiguousarray(params["u%d/bn/beta" % i], dtype=np.float32))]
         return out
 
-    def repack_context(self, params):
-        """Upload the x-only weights (stage concatenations, BN parameters) for icnn_be_fc_context."""
-        self._refuse_if_attached("repack_context")
-        c, keep = self._ctx_struct(), []
-        for field, i, a in self._ctx_host(params):
-            t = torch.from_numpy(a).to(self.device)
-            keep.append(t)
-            getattr(c, field)[i] = t.data_ptr()
-        self._ctx_keep, self.c_ctx = keep, c
-
-    def repack(self, params):
-        self._refuse_if_attached("repack")
-        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
-        self.c_model.wpack = self.wpack.data_ptr()
-        self.params = params
-        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
-        # the x-only stage weights follow the same parameter set
-        self.repack_context(params)
-
     def _pack_host(self, params):
         """icnn_be_fc_pack of params' y-path weights: the host image of wpack"""
-        import ctypes as C
-        L1 = self.spec.n_layers
-        keep = []
-
-        def ptr(name):
-            a = np.ascontiguousarray(params[name], dtype=np.float32)
-            keep.append(a)
-            return a.ctypes.data
-
+        L1, ptr = self.spec.n_layers, _host_ptr(params)
         yu = (C.c_void_p * L1)(*[ptr("z%d_yu/W" % i) for i in range(L1)])
         zu = (C.c_void_p * L1)(*([None] + [ptr("z%d_zu_proj/W" % i) for i in range(1, L1)]))
         host = np.empty(self.n_pack_floats, dtype=np.float32)
-        from . import _lib
         _lib.check(self._lib.icnn_be_fc_pack(C.byref(self.c_model), yu, zu, host.ctypes.data),
                    "icnn_be_fc_pack")
         return host
-
-    def context_work_floats(self, batch) -> int:
-        """floats of the `work` buffer context(..., work=) takes at this batch size (any bn / bn_updates)"""
-        import ctypes as C
-        return max(int(self._lib.icnn_be_fc_context_bn_work_floats(C.byref(self.c_ctx), batch)), 1)
-
-    def context(self, x: torch.Tensor, bn="batch", bn_updates=0, out=None, work=None) -> torch.Tensor:
-        """x-only context rows [B, ctx_width] of the minibatch x [B, n_features] by the HIP kernels of be_context.hip
-        (one MFMA GEMM per stage with routed epilogue, batch-statistics BatchNorm in place); current stream.
-        bn="moving": inference mode, BatchNorm with self.bn_stats (valid at batch 1); bn="batch" with bn_updates = k > 0:
-        the same context, and the batch statistics folded k times into self.bn_stats (icnn_be_fc_context_bn).  bn_updates
-        may be an int32 device tensor (one element): the count is read on the device, no host wait
-        (icnn_be_fc_context_bn_dev).  out / work: caller-owned buffers ([B, ctx_width] float32; context_work_floats(B)
-        floats) for a step that allocates nothing."""
-        import ctypes as C
-
-        from . import _lib
-        k_dev = self._device_updates(bn, bn_updates) if torch.is_tensor(bn_updates) else None
-        mode = _lib.BN_MODE["batch"] if k_dev is not None else self._bn_mode(bn, bn_updates)
-        x = x.to(self.device, torch.float32).contiguous()
-        B = x.shape[0]
-        assert x.shape[1] == self.spec.n_features
-        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device) if out is None else out
-        assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32 and ctx.is_contiguous()
-        if work is not None:
-            assert work.dtype == torch.float32 and work.numel() >= self.context_work_floats(B)
-        if k_dev is not None:
-            if work is None:
-                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            mv = self._c_bn()
-            _lib.check(self._lib.icnn_be_fc_context_bn_dev(C.byref(self.c_ctx), C.byref(mv), k_dev.data_ptr(), x.data_ptr(), B,
-                                                           ctx.data_ptr(), self.spec.ctx_width, work.data_ptr(),
-                                                           C.c_void_p(stream)), "icnn_be_fc_context_bn_dev")
-            return ctx
-        if mode != _lib.BN_MODE["batch"] or bn_updates:
-            if work is None:
-                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            mv = self._c_bn()
-            _lib.check(self._lib.icnn_be_fc_context_bn(C.byref(self.c_ctx), C.byref(mv), mode, int(bn_updates), x.data_ptr(), B,
-                                                       ctx.data_ptr(), self.spec.ctx_width, work.data_ptr(),
-                                                       C.c_void_p(stream)), "icnn_be_fc_context_bn")
-            return ctx
-        if work is None:
-            work = torch.empty(max(int(self._lib.icnn_be_fc_context_work_floats(C.byref(self.c_ctx), B)), 1),
-                               dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.icnn_be_fc_context(C.byref(self.c_ctx), x.data_ptr(), B, ctx.data_ptr(), self.spec.ctx_width,
-                                                work.data_ptr(), C.c_void_p(stream)), "icnn_be_fc_context")
-        return ctx
 
     def context_sharded(self, x_local: torch.Tensor, batch_total=None, all_reduce=None) -> torch.Tensor:
         """The same for ONE RANK'S SHARD of a data-parallel minibatch: context rows [B_local, ctx_width] of x_local with the
@@ -511,11 +555,8 @@ class FCModel(_BnMovingStats, _DeviceWeights):
         behind every normalised stage the ranks all-reduce 2 x width doubles (sum u, sum u^2; RCCL through
         torch.distributed by default), then icnn_be_fc_context_norm.  No rank touches rows it does not own
         (multi-label-cls/icnn_ebundle.py:339-347)."""
-        import ctypes as C
-
         import torch.distributed as dist
 
-        from . import _lib
         x = x_local.to(self.device, torch.float32).contiguous()
         B = x.shape[0]
         assert x.shape[1] == self.spec.n_features
@@ -552,9 +593,6 @@ class FCModel(_BnMovingStats, _DeviceWeights):
     def clamp(self, mode="proj"):
         """The reference's clamp ops on the device-resident packed 'zu_proj' weights: mode 'makeCvx' = |W|
         (icnn_ebundle.py:143,:204), 'proj' = max(W, 0) (:144,:244-245)."""
-        import ctypes as C
-
-        from . import _lib
         self._refuse_if_attached("clamp")
         code = {"makeCvx": _lib.CLAMP_ABS, "proj": _lib.CLAMP_RELU}[mode]
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -562,9 +600,6 @@ class FCModel(_BnMovingStats, _DeviceWeights):
 
     def fg(self, ctx: torch.Tensor, y: torch.Tensor, finished=None):
         """E[B] float32 and dE/dy[B, n] float32 at y (float64 [B, n]) on the current stream."""
-        import ctypes as C
-
-        from . import _lib
         B = y.shape[0]
         assert y.dtype == torch.float64 and y.is_contiguous() and ctx.is_contiguous()
         assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32
@@ -617,6 +652,29 @@ class ConvSpec:
         sizes += [m[1][0] * m[1][1] * m[1][2], m[1][0] * m[1][1], m[2][0] * m[2][1] * m[2][2]]   # gate2 yu2 zu2
         sizes += [self.flat_dim, CONV_FCS[0], CONV_FCS[0], 1]                      # gate3 zu3 gate4 zu4
         return sum(sizes)
+
+    def grad_layout(self) -> List[Tuple[str, tuple]]:
+        """train.grad_layout of this spec: the order of init_conv_params' keys"""
+        out, cin = [], 1
+        for l, (nf, k, s) in enumerate(CONV_LAYERS):
+            out += [("u%d/W" % l, (k, k, cin, nf)), ("u%d/b" % l, (nf,)), ("u%d/bn/gamma" % l, (nf,)),
+                    ("u%d/bn/beta" % l, (nf,))]
+            if l > 0:
+                out += [("z%d_zu_u/W" % l, (3, 3, cin, cin)), ("z%d_zu_u/b" % l, (cin,)),
+                        ("z%d_zu_proj/W" % l, (k, k, cin, nf))]
+            out += [("z%d_yu_u/W" % l, (3, 3, cin, 1)), ("z%d_yu_u/b" % l, (1,)), ("z%d_yu/W" % l, (k, k, 1, nf)),
+                    ("z%d_y_red/W" % l, (k, k, 1, 1)), ("z%d_y_red/b" % l, (1,)), ("z%d_u/W" % l, (k, k, cin, nf)),
+                    ("z%d_u/b" % l, (nf,))]
+            cin = nf
+        flat, fch = self.flat_dim, CONV_FCS[0]
+        out += [("u3/W", (flat, fch)), ("u3/b", (fch,)), ("u3/bn/gamma", (fch,)), ("u3/bn/beta", (fch,)), ("u4/W", (fch, 1)),
+                ("u4/b", (1,))]
+        prev = flat
+        for l, sz in zip((3, 4), CONV_FCS):
+            out += [("z%d_zu_u/W" % l, (prev, prev)), ("z%d_zu_u/b" % l, (prev,)), ("z%d_zu_proj/W" % l, (prev, sz)),
+                    ("z%d_u/W" % l, (prev, sz)), ("z%d_u/b" % l, (sz,))]
+            prev = sz
+        return out
 
 
 def _uniform_scaling(rng, shape, fan_in):
@@ -748,15 +806,15 @@ def stage_conv_weights(params):
             for ws, bs in CONV_CTX_STAGES]
 
 
-class ConvModel(_BnMovingStats, _DeviceWeights):
+class ConvModel(_PICNNDevice):
     """Device-resident y-path of the conv PICNN (struct icnn_be_conv_model + packed weights)."""
-    solve_entry = "icnn_be_solve_conv"
+    solve_entry, gd_entry, context_entry = "icnn_be_solve_conv", "icnn_be_conv_gd", "icnn_be_conv_context"
+    grad_entry, grad_floats_entry = "icnn_be_conv_surrogate_grad", "icnn_be_conv_grad_floats"
+    has_bn = True
 
     def __init__(self, spec: ConvSpec, params, device="cuda"):
-        import ctypes as C
-
-        from . import _lib
         self.spec, self.params, self.device = spec, params, torch.device(device)
+        self.x_shape = (spec.H, spec.W, 1)
         self._lib = _lib.load()
         m = _lib.ConvModel()
         m.H, m.W = spec.H, spec.W
@@ -774,12 +832,17 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
         self._init_bn_stats()
         self.repack(params)
 
+    def check_x(self, x):
+        assert tuple(x.shape[1:]) == self.x_shape
+
+    def _context_ends(self):
+        return self._descriptors(), ()
+
     def reserve(self, batch):
         """Device scratch for evaluations of up to `batch` samples (struct icnn_be_conv_model.work).  One ConvModel is used
         from ONE stream at a time (the scratch is written by every evaluation, include/icnn_be.h); growing it waits for the
         work already enqueued on the device, so an evaluation in flight on another stream never loses its buffer, and the
         old buffer stays referenced until then."""
-        import ctypes as C
         if self.c_model.work_batch >= batch:
             return
         n = int(self._lib.icnn_be_conv_work_floats(C.byref(self.c_model), batch))
@@ -788,27 +851,9 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
         self.work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
         self.c_model.work, self.c_model.work_batch = self.work.data_ptr(), batch
 
-    def repack(self, params):
-        self._refuse_if_attached("repack")
-        self.wpack = torch.from_numpy(self._pack_host(params)).to(self.device)
-        self.c_model.wpack = self.wpack.data_ptr()
-        self.params = params
-        # the per-update flow of INTEGRATION.md is model.repack(params) then model.context(x) / rl_adam.adam(model, obs):
-        # the x-only stage weights follow the same parameter set
-        self.repack_context(params)
-
     def _pack_host(self, params):
         """icnn_be_conv_pack of params' y-path weights: the host image of wpack"""
-        import ctypes as C
-
-        from . import _lib
-        keep = []
-
-        def ptr(name):
-            a = np.ascontiguousarray(params[name], dtype=np.float32)
-            keep.append(a)
-            return a.ctypes.data
-
+        ptr = _host_ptr(params)
         w_yu = (C.c_void_p * 3)(*[ptr("z%d_yu/W" % l) for l in range(3)])
         w_yr = (C.c_void_p * 3)(*([ptr("z%d_y_red/W" % l) for l in range(2)] + [None]))
         b_yr = (C.c_void_p * 3)(*([ptr("z%d_y_red/b" % l) for l in range(2)] + [None]))
@@ -819,7 +864,6 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
         return host
 
     def _ctx_struct(self):
-        from . import _lib
         c = _lib.ConvCtx()
         c.bn_eps = 1e-5
         return c
@@ -836,73 +880,9 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
                     ("bn_beta", i, np.ascontiguousarray(params["u%d/bn/beta" % i], np.float32))]
         return out
 
-    def repack_context(self, params):
-        """Upload the stage operands of the x-only context producer (struct icnn_be_conv_ctx, include/icnn_be.h)."""
-        self._refuse_if_attached("repack_context")
-        c, keep = self._ctx_struct(), []
-        for field, i, a in self._ctx_host(params):
-            t = torch.from_numpy(a).to(self.device)
-            keep.append(t)
-            getattr(c, field)[i] = t.data_ptr()
-        self._ctx_keep, self.c_ctx = keep, c
-
-    def context_work_floats(self, batch) -> int:
-        """floats of the `work` buffer context(..., work=) takes at this batch size (any bn / bn_updates)"""
-        import ctypes as C
-        return max(int(self._lib.icnn_be_conv_context_bn_work_floats(C.byref(self.c_model), batch)), 1)
-
-    def context(self, x: torch.Tensor, bn="batch", bn_updates=0, out=None, work=None) -> torch.Tensor:
-        """x-only context [B, ctx_width] of x [B, H, W, 1] (already h-flipped by the caller as
-        completion/icnn_ebundle.py:215 does), on the device: be_context.hip through `icnn_be_conv_context`
-        (`conv_context` above is the torch restatement the tests compare it with).  bn / bn_updates / out / work as
-        FCModel.context: bn="moving" is the inference mode of the completion test phase (icnn_be_conv_context_bn); an int32
-        device tensor as bn_updates is read on the device (icnn_be_conv_context_bn_dev)."""
-        import ctypes as C
-
-        from . import _lib
-        k_dev = self._device_updates(bn, bn_updates) if torch.is_tensor(bn_updates) else None
-        mode = _lib.BN_MODE["batch"] if k_dev is not None else self._bn_mode(bn, bn_updates)
-        x = x.to(self.device, torch.float32).contiguous()
-        B = x.shape[0]
-        assert tuple(x.shape[1:]) == (self.spec.H, self.spec.W, 1)
-        if getattr(self, "c_ctx", None) is None:
-            self.repack_context(self.params)
-        ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=self.device) if out is None else out
-        assert ctx.shape == (B, self.spec.ctx_width) and ctx.dtype == torch.float32 and ctx.is_contiguous()
-        if work is not None:
-            assert work.dtype == torch.float32 and work.numel() >= self.context_work_floats(B)
-        if k_dev is not None:
-            if work is None:
-                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            mv = self._c_bn()
-            _lib.check(self._lib.icnn_be_conv_context_bn_dev(C.byref(self.c_model), C.byref(self.c_ctx), C.byref(mv),
-                                                             k_dev.data_ptr(), x.data_ptr(), B, ctx.data_ptr(), work.data_ptr(),
-                                                             C.c_void_p(stream)), "icnn_be_conv_context_bn_dev")
-            return ctx
-        if mode != _lib.BN_MODE["batch"] or bn_updates:
-            if work is None:
-                work = torch.empty(self.context_work_floats(B), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            mv = self._c_bn()
-            _lib.check(self._lib.icnn_be_conv_context_bn(C.byref(self.c_model), C.byref(self.c_ctx), C.byref(mv), mode,
-                                                         int(bn_updates), x.data_ptr(), B, ctx.data_ptr(), work.data_ptr(),
-                                                         C.c_void_p(stream)), "icnn_be_conv_context_bn")
-            return ctx
-        if work is None:
-            n = int(self._lib.icnn_be_conv_context_work_floats(C.byref(self.c_model), B))
-            work = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.icnn_be_conv_context(C.byref(self.c_model), C.byref(self.c_ctx), x.data_ptr(), B,
-                                                  ctx.data_ptr(), work.data_ptr(), C.c_void_p(stream)), "icnn_be_conv_context")
-        return ctx
-
     def clamp(self, mode="proj"):
         """makeCvx ("makeCvx": |W|/2, completion/icnn_ebundle.py:145,:190) / proj (max(W, 0), :146,:248-249) on the
         packed convex weights, in place on the device."""
-        import ctypes as C
-
-        from . import _lib
         self._refuse_if_attached("clamp")
         code = {"makeCvx": _lib.CLAMP_ABS_HALF, "proj": _lib.CLAMP_RELU}[mode]
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -910,9 +890,6 @@ class ConvModel(_BnMovingStats, _DeviceWeights):
 
     def fg(self, ctx: torch.Tensor, y: torch.Tensor, finished=None):
         """E[B] and dE/dy[B, H*W] (float32) at y (float64, flat [B, H*W]) on the current stream."""
-        import ctypes as C
-
-        from . import _lib
         B = y.shape[0]
         assert y.dtype == torch.float64 and y.is_contiguous() and ctx.is_contiguous()
         assert y.shape[1] == self.spec.n_labels and ctx.shape == (B, self.spec.ctx_width)

@@ -49,9 +49,7 @@ class CriticTrainer:
         if not 0.0 <= tau <= 1.0:
             raise ValueError("tau must lie in [0, 1], got %r" % (tau,))
         self.critic, self.target, self.spec, self.device = critic, target, critic.spec, critic.device
-        self.batch = int(batch)
-        if self.batch < 1:
-            raise ValueError("batch must be >= 1")
+        self.batch = train._positive("batch", batch)
         self.lr, self.tau, self.discount, self.l2norm, self.wd = float(lr), float(tau), float(discount), float(l2norm), float(wd)
         self.lib = _lib.load()
         self.opt = train.DeviceAdam(critic, lr)

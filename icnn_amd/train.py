@@ -4,13 +4,19 @@
                     variable (multi-label-cls/icnn_ebundle.py:148-156; with v absent the RL critic's c-weighted energy,
                     RL/src/icnn.py:90-109): HIP kernels of be_train_fc.hip through icnn_be_fc_surrogate_grad.  For the
                     conv PICNN of the completion experiment (completion/icnn_ebundle.py:129-140) be_train_conv.hip
-                    through icnn_be_conv_surrogate_grad.
+                    through icnn_be_conv_surrogate_grad, for the FICNN be_train_ficnn.hip through
+                    icnn_be_ficnn_surrogate_grad.  The model classes state their entries, leading descriptors and input
+                    shape themselves (picnn._DeviceWeights); grad_layout is each spec's own (picnn.FCSpec / ConvSpec,
+                    ficnn.FICNNSpec).
     TFAdam          tf.train.AdamOptimizer's update rule on device tensors (torch plumbing, not a kernel).
     DeviceAdam      the same update, the reference's proj and the repack of every copy the kernels read, in one launch of
                     be_train_update.hip (icnn_be_param_update) over a flat theta; the model's packed weights live in one
                     device buffer (the arena) that the update writes in place.
     FollowerWeights the same theta and arena without optimiser state, for a model another launch writes (the RL agent's
                     target network, rl_train.CriticTrainer).
+
+    _Trainer        what the trainers below and ficnn.GDTrainer share round their step(): batch buffers, context buffers, the
+                    start point (_start_point), the views of the optimiser's theta.
 
     BundleTrainer   one whole iteration of the bundle-entropy training loops without a host wait (capturable): context,
                     fused solve, FeedPlan (be_train_bundle.hip: row offsets, row count, fg evaluations, status OR, loss, F1
@@ -46,55 +52,14 @@ import torch
 
 from . import _lib
 from .bundle_entropy import ImplicitFeed
-from .picnn import CONV_FCS, CONV_LAYERS, ConvModel, ConvSpec, FCModel, FCSpec
-
-
-def _conv_grad_layout(spec: ConvSpec) -> List[Tuple[str, tuple]]:
-    out, cin = [], 1
-    for l, (nf, k, s) in enumerate(CONV_LAYERS):
-        out += [("u%d/W" % l, (k, k, cin, nf)), ("u%d/b" % l, (nf,)), ("u%d/bn/gamma" % l, (nf,)), ("u%d/bn/beta" % l, (nf,))]
-        if l > 0:
-            out += [("z%d_zu_u/W" % l, (3, 3, cin, cin)), ("z%d_zu_u/b" % l, (cin,)), ("z%d_zu_proj/W" % l, (k, k, cin, nf))]
-        out += [("z%d_yu_u/W" % l, (3, 3, cin, 1)), ("z%d_yu_u/b" % l, (1,)), ("z%d_yu/W" % l, (k, k, 1, nf)),
-                ("z%d_y_red/W" % l, (k, k, 1, 1)), ("z%d_y_red/b" % l, (1,)), ("z%d_u/W" % l, (k, k, cin, nf)),
-                ("z%d_u/b" % l, (nf,))]
-        cin = nf
-    flat, fch = spec.flat_dim, CONV_FCS[0]
-    out += [("u3/W", (flat, fch)), ("u3/b", (fch,)), ("u3/bn/gamma", (fch,)), ("u3/bn/beta", (fch,)), ("u4/W", (fch, 1)),
-            ("u4/b", (1,))]
-    prev = flat
-    for l, sz in zip((3, 4), CONV_FCS):
-        out += [("z%d_zu_u/W" % l, (prev, prev)), ("z%d_zu_u/b" % l, (prev,)), ("z%d_zu_proj/W" % l, (prev, sz)),
-                ("z%d_u/W" % l, (prev, sz)), ("z%d_u/b" % l, (sz,))]
-        prev = sz
-    return out
+from .picnn import ConvModel, FCModel
 
 
 def grad_layout(spec) -> List[Tuple[str, tuple]]:
     """(name, shape) of every variable of the packed gradient, in the order include/icnn_be.h documents (the order of
-    picnn.init_params' keys for an FCSpec, of picnn.init_conv_params' for a ConvSpec)."""
-    if isinstance(spec, ConvSpec):
-        return _conv_grad_layout(spec)
-    from .ficnn import FICNNSpec
-    if isinstance(spec, FICNNSpec):
-        from .ficnn import grad_layout as ficnn_layout
-        return ficnn_layout(spec)
-    L, n, w = len(spec.szs), spec.n_labels, spec.widths
-    out = []
-    prev = spec.n_features
-    for i in range(L):
-        out += [("u%d/W" % i, (prev, spec.szs[i])), ("u%d/b" % i, (spec.szs[i],))]
-        if i < L - 1 and spec.batchnorm:
-            out += [("u%d/bn/gamma" % i, (spec.szs[i],)), ("u%d/bn/beta" % i, (spec.szs[i],))]
-        prev = spec.szs[i]
-    for i in range(L + 1):
-        in_u = spec.n_features if i == 0 else spec.szs[i - 1]
-        if i > 0:
-            out += [("z%d_zu_u/W" % i, (in_u, w[i - 1])), ("z%d_zu_u/b" % i, (w[i - 1],)),
-                    ("z%d_zu_proj/W" % i, (w[i - 1], w[i]))]
-        out += [("z%d_yu_u/W" % i, (in_u, n)), ("z%d_yu_u/b" % i, (n,)), ("z%d_yu/W" % i, (n, w[i])),
-                ("z%d_u/W" % i, (in_u, w[i])), ("z%d_u/b" % i, (w[i],))]
-    return out
+    picnn.init_params' keys for an FCSpec, of picnn.init_conv_params' for a ConvSpec, of ficnn.init_params' for a FICNNSpec);
+    each spec keeps its own."""
+    return spec.grad_layout()
 
 
 def unpack_grad(spec, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -110,12 +75,7 @@ def unpack_grad(spec, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
 
 
 def grad_floats(model) -> int:
-    from .ficnn import FICNNModel
-    if isinstance(model, FICNNModel):
-        return int(model._lib.icnn_be_ficnn_grad_floats(C.byref(model.c_model)))
-    if isinstance(model, ConvModel):
-        return int(model._lib.icnn_be_conv_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
-    return int(model._lib.icnn_be_fc_grad_floats(C.byref(model.c_model), C.byref(model.c_ctx)))
+    return int(getattr(model._lib, model.grad_floats_entry)(*model._descriptors()))
 
 
 def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows=None, bn_updates=0, flat=False,
@@ -138,15 +98,9 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     [0, count) are the compact call's bits, and a count of 0 gives a zero gradient and leaves bn_stats alone.  out / work:
     caller-owned float32 buffers (grad_floats(model); surrogate_work_floats(model, B, R)) for a step that allocates nothing."""
     spec, dev = model.spec, model.device
-    conv = isinstance(model, ConvModel)
     x = x.to(dev, torch.float32).contiguous()
     B = x.shape[0]
-    if conv:
-        assert tuple(x.shape[1:]) == (spec.H, spec.W, 1)
-        if getattr(model, "c_ctx", None) is None:
-            model.repack_context(model.params)
-    else:
-        assert x.shape[1] == spec.n_features
+    model.check_x(x)
     v = None
     if isinstance(feed_or_rows, ImplicitFeed):
         y, v, c = feed_or_rows.y, feed_or_rows.v, feed_or_rows.c
@@ -176,14 +130,12 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     bn_updates = int(bn_updates)
     if bn_updates < 0:
         raise ValueError("bn_updates must be >= 0, got %d" % bn_updates)
-    from . import ficnn
-    if isinstance(model, ficnn.FICNNModel):            # no BatchNorm: icnn_be_ficnn_surrogate_grad
+    entry = model.grad_entry
+    if not model.grad_takes_stats:                      # the FICNN's one entry: no moving statistics, no rows_dev form
         if bn_updates:
             raise ValueError("a FICNN has no BatchNorm statistics to fold (bn_updates=%d)" % bn_updates)
         if rows_dev is not None or out is not None or work is not None:
             raise ValueError("rows_dev / out / work are for the PICNN entries: icnn_be_ficnn_surrogate_grad has no such form")
-        return ficnn.surrogate_grad(model, x, row_offset, y, v, c, F_rows, flat)
-    entry = "icnn_be_conv_surrogate_grad" if conv else "icnn_be_fc_surrogate_grad"
     if rows_dev is not None and (not torch.is_tensor(rows_dev) or rows_dev.dtype != torch.int32 or rows_dev.numel() != 1
                                  or not rows_dev.is_cuda):
         raise ValueError("rows_dev is one int32 on the device")
@@ -197,25 +149,28 @@ def surrogate_grad(model, x: torch.Tensor, feed_or_rows, row_offset=None, F_rows
     assert work.dtype == torch.float32 and work.numel() >= n_work
     if F_rows is not None:
         assert F_rows.dtype == torch.float32 and F_rows.shape == (R,) and F_rows.is_contiguous()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    mv = model._c_bn()
-    args = [C.byref(model.c_model), C.byref(model.c_ctx), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
+    args = [*model._descriptors(), x.data_ptr(), B, row_offset.data_ptr(), R, y.data_ptr(),
             None if v is None else v.data_ptr(), c.data_ptr(), grad.data_ptr(),
-            None if F_rows is None else F_rows.data_ptr(), work.data_ptr(), C.byref(mv), bn_updates]
+            None if F_rows is None else F_rows.data_ptr(), work.data_ptr()]
+    stream = model._stream()
+    if not model.grad_takes_stats:
+        _lib.check(getattr(model._lib, entry)(*args, stream), entry)
+        return grad if flat else unpack_grad(spec, grad)
+    mv = model._c_bn()
     if rows_dev is None:
-        _lib.check(getattr(model._lib, entry + "_bn")(*args, C.c_void_p(stream)), entry)
+        _lib.check(getattr(model._lib, entry + "_bn")(*args, C.byref(mv), bn_updates, stream), entry)
     else:
-        _lib.check(getattr(model._lib, entry + "_dev")(*args, rows_dev.data_ptr(), C.c_void_p(stream)), entry + "_dev")
+        _lib.check(getattr(model._lib, entry + "_dev")(*args, C.byref(mv), bn_updates, rows_dev.data_ptr(), stream),
+                   entry + "_dev")
     return grad if flat else unpack_grad(spec, grad)
 
 
 def surrogate_work_floats(model, batch, rows, dev=False) -> int:
-    """floats of surrogate_grad's workspace for a PICNN at (batch, rows); dev: of the rows_dev form, which is larger (its
-    forward products keep split-K partials for any plan).  Raises on a shape the library rejects"""
-    entry = "icnn_be_conv_surrogate_grad" if isinstance(model, ConvModel) else "icnn_be_fc_surrogate_grad"
-    if dev:
-        entry += "_dev"
-    n_work = int(getattr(model._lib, entry + "_work_floats")(C.byref(model.c_model), C.byref(model.c_ctx), batch, rows))
+    """floats of surrogate_grad's workspace for `model` at (batch, rows); dev: of the rows_dev form (PICNNs only: a FICNN
+    has no such entry), which is larger (its forward products keep split-K partials for any plan).  Raises on a shape the
+    library rejects"""
+    entry = model.grad_entry + ("_dev" if dev else "")
+    n_work = int(getattr(model._lib, entry + "_work_floats")(*model._descriptors(), batch, rows))
     if n_work == 0:
         raise ValueError("%s: shape rejected (batch %d, rows %d)" % (entry, batch, rows))
     return n_work
@@ -397,7 +352,7 @@ class _ArenaOwner:
     and the arena that the model's descriptors point into once attached."""
 
     def _attach(self, model, max_proj=None):
-        if getattr(model, "_optimizer", None) is not None:
+        if model._optimizer is not None:
             raise RuntimeError("the model is already attached to a DeviceAdam")
         self.model, self.spec, self.device = model, model.spec, model.device
         self.layout = grad_layout(self.spec)
@@ -460,7 +415,7 @@ class DeviceAdam(_ArenaOwner):
     Constructing one ATTACHES the model: its packed weights move into one persistent device buffer (the arena) that
     c_model.wpack and every c_ctx pointer reference from then on, so solves, contexts and gradients captured in a graph keep
     reading the current weights.  An attached model's `params` are live device views of theta; its repack, repack_context
-    and clamp raise (use load)."""
+    and clamp raise (use load; m, v and the step count are kept)."""
 
     def __init__(self, model, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
         self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
@@ -505,10 +460,82 @@ class DeviceAdam(_ArenaOwner):
             return
         _lib.check(self.model._lib.icnn_be_param_update(C.byref(self._args), C.c_void_p(stream)), "icnn_be_param_update")
 
-    def load(self, params):
-        """Replace theta by `params` (host arrays or device tensors keyed like grad_layout) and rewrite the arena from
-        them through the host packers.  m, v and the step count are kept."""
-        _ArenaOwner.load(self, params)
+
+# --------------------------------------------------------------------------------------------- #
+# What the trainers share round their step(): argument checks, buffers, the start point, the optimiser's views
+# --------------------------------------------------------------------------------------------- #
+def _positive(name, value) -> int:
+    value = int(value)
+    if value < 1:
+        raise ValueError("%s must be >= 1" % name)
+    return value
+
+
+def _non_negative(name, value) -> int:
+    value = int(value)
+    if value < 0:
+        raise ValueError("%s must be >= 0, got %d" % (name, value))
+    return value
+
+
+def _ticket(n_bytes, device) -> torch.Tensor:
+    """the workspace of a feed kernel, zeroed once: it holds the ticket its blocks count themselves with"""
+    return torch.zeros((int(n_bytes) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def _start_point(y0, n, batch, eval_batch, device):
+    """A trainer's start point y0 -- a scalar, an [n] row, an image [H, W, 1] or a [B, n] array ([B, H, W, 1] too) -- as a
+    Python float (a scalar) or a float64 tensor on `device` that expands to [rows, n]: [n], or [B, n], which serves the
+    test phase only when eval_batch == batch."""
+    y0 = torch.as_tensor(y0, dtype=torch.float64)
+    if y0.dim() == 0:
+        return float(y0)
+    y0 = y0.to(device)
+    if y0.dim() >= 3 and y0.numel() % n == 0:           # an image, or one per sample
+        y0 = y0.reshape(-1, n)
+    if y0.dim() == 2 and y0.shape[0] == 1:
+        y0 = y0[0]
+    if y0.dim() > 2 or y0.shape[-1] != n or (y0.dim() == 2 and y0.shape[0] != batch):
+        raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
+                         % (n, batch, tuple(y0.shape)))
+    if eval_batch is not None and y0.dim() == 2 and eval_batch != batch:
+        raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
+    return y0
+
+
+class _Trainer:
+    """The scaffolding of a trainer that owns `model`, `device` and the DeviceAdam `opt`; its pipeline is its own step()."""
+
+    def _put(self, buf, value):
+        """copy a batch into its preallocated buffer; None keeps what the buffer holds (graph replay)"""
+        if value is not None:
+            buf.copy_(torch.as_tensor(value).to(self.device, buf.dtype).reshape(buf.shape))
+
+    def _context_buffers(self, batch):
+        """(ctx, work) of model.context(x, out=, work=) at this batch size"""
+        return (torch.empty(batch, self.spec.ctx_width, dtype=torch.float32, device=self.device),
+                torch.empty(self.model.context_work_floats(batch), dtype=torch.float32, device=self.device))
+
+    @property
+    def t_steps(self) -> int:
+        return self.opt.t
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        return self.opt.params()
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return self.opt.host_params()
+
+
+class _TrainF1:
+    """macro_f1() of the two trainers that keep the per-example tallies f1_tallies; where they were not asked for it is
+    None, and _no_tallies says when they exist."""
+
+    def macro_f1(self) -> float:
+        """the train F1 of the last step (util.macroF1; one wait)"""
+        if self.f1_tallies is None:
+            raise ValueError(self._no_tallies)
+        return macro_f1(self.f1_tallies)
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -529,8 +556,7 @@ class FeedPlan:
         self.rows, self.fg_evals, self.status_or = self.counts[0:1], self.counts[1:2], self.counts[2:3]
         self.loss = torch.zeros((), dtype=torch.float64, device=dev)
         self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev) if loss == "xent" else None
-        n_work = int(state.lib.icnn_be_feed_plan_work_bytes(B))
-        self._work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)       # zeroed once: the ticket
+        self._work = _ticket(state.lib.icnn_be_feed_plan_work_bytes(B), dev)
 
     def run(self, true_y):
         """enqueue the plan for the state's current contents and true_y (float64 [B, n] device tensor); no host wait"""
@@ -569,7 +595,7 @@ class PaddedFeed:
         return self
 
 
-class BundleTrainer:
+class BundleTrainer(_Trainer, _TrainF1):
     """One iteration of the bundle-entropy training loops (multi-label-cls/icnn_ebundle.py:208-250 with loss "xent" on a
     picnn.FCModel; completion/icnn_ebundle.py with loss "mse" on a picnn.ConvModel) at one batch size, all of it enqueued
     on the current stream without a host wait, so a step can be captured in a CUDA graph:
@@ -603,48 +629,46 @@ class BundleTrainer:
     the training step.  eval_bn=None is what each script does at test time: "batch" for an FCModel (the multi-label script
     keeps is_training(True), :259), "moving" for a ConvModel (the completion script sets is_training(False), :266).  A [B, n]
     y0 serves the test phase only when E = B."""
+    # what each script trains and tests with: (the model it serves, its loss, the BatchNorm mode of its test phase)
+    _SCRIPTS = ((FCModel, "xent", "batch"), (ConvModel, "mse", "moving"))
+    _no_tallies = "F1 tallies exist for loss 'xent' only"
 
     def __init__(self, model, batch, n_iter=10, loss="xent", variant="pdipm", lr=1e-3, y0=0.5, eval_batch=None, eval_bn=None,
                  skip_on_error=False):
         from .bundle_entropy import FusedSolver
         if loss not in _lib.LOSS:
             raise ValueError("loss must be 'xent' or 'mse', got %r" % (loss,))
-        if not isinstance(model, (FCModel, ConvModel)):
+        script = [s for s in self._SCRIPTS if isinstance(model, s[0])]
+        if not script:
             raise TypeError("BundleTrainer serves picnn.FCModel and picnn.ConvModel, got %s" % type(model).__name__)
-        want = "mse" if isinstance(model, ConvModel) else "xent"
+        _, want, script_bn = script[0]
         if loss != want:
             raise ValueError("a %s trains with loss %r, got %r" % (type(model).__name__, want, loss))
         if variant not in ("dual", "pdipm"):
             raise ValueError("variant must be 'dual' or 'pdipm' (the rl variant does not record n_iters), got %r" % (variant,))
-        self.batch = int(batch)
-        if self.batch < 1:
-            raise ValueError("batch must be >= 1")
+        self.batch = _positive("batch", batch)
         self.eval_batch = None if eval_batch is None else int(eval_batch)
         if self.eval_batch is not None and self.eval_batch < 1:
             raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
-        self.conv = isinstance(model, ConvModel)
         if eval_bn is None:
-            eval_bn = "moving" if self.conv else "batch"
+            eval_bn = script_bn
         if eval_bn not in _lib.BN_MODE:
             raise ValueError("eval_bn must be 'batch' or 'moving', got %r" % (eval_bn,))
         self.eval_bn, self.skip_on_error = eval_bn, bool(skip_on_error)
         self.model, self.spec, self.device = model, model.spec, model.device
         self.n_iter, self.loss_name, self.variant, self.lr = int(n_iter), loss, variant, float(lr)
-        self.has_bn = self.conv or bool(getattr(self.spec, "batchnorm", False))
+        self.has_bn = model.has_bn
         self.opt = DeviceAdam(model, lr=lr)
         B, E, dev, n = self.batch, self.eval_batch, self.device, self.spec.n_labels
-        if E is not None and hasattr(model, "reserve"):
-            model.reserve(max(B, E))                    # grown here, never inside a capture
+        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
         self.solver = FusedSolver(model, B, self.n_iter, variant)
         st = self.solver.state
         self.plan = FeedPlan(st, loss)
         self.feed = PaddedFeed(st)
-        x_shape = (B, self.spec.H, self.spec.W, 1) if self.conv else (B, self.spec.n_features)
-        self.x = torch.zeros(x_shape, dtype=torch.float32, device=dev)
+        self.x = torch.zeros((B,) + model.x_shape, dtype=torch.float32, device=dev)
         self.true_y = torch.zeros(B, n, dtype=torch.float64, device=dev)
-        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
+        self.ctx, self._ctx_work = self._context_buffers(B)
         self._ctx_fold = torch.empty_like(self.ctx) if self.has_bn else None
-        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
         self._grad_work = torch.empty(surrogate_work_floats(model, B, self.feed.row_cap, dev=True), dtype=torch.float32, device=dev)
         self.loss, self.f1_tallies = self.plan.loss, self.plan.f1_tallies
@@ -661,10 +685,9 @@ class BundleTrainer:
         if E is not None:
             self.eval_solver = FusedSolver(model, E, self.n_iter, variant)
             self.eval_plan = FeedPlan(self.eval_solver.state, loss)
-            self.x_eval = torch.zeros((E,) + x_shape[1:], dtype=torch.float32, device=dev)
+            self.x_eval = torch.zeros((E,) + model.x_shape, dtype=torch.float32, device=dev)
             self.true_y_eval = torch.zeros(E, n, dtype=torch.float64, device=dev)
-            self.ctx_eval = torch.empty(E, self.spec.ctx_width, dtype=torch.float32, device=dev)
-            self._ctx_work_eval = torch.empty(model.context_work_floats(E), dtype=torch.float32, device=dev)
+            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
             self.y_eval, self.eval_loss = self.eval_solver.y, self.eval_plan.loss
             self.eval_f1_tallies = self.eval_plan.f1_tallies
         self.y0 = self.y0_eval = None                   # float64 [B, n] / [E, n] once a start point is not a scalar
@@ -676,21 +699,11 @@ class BundleTrainer:
         too).  A copy from the host: call it outside a capture (a captured step keeps the KIND of start point it was captured
         with: a scalar fills, anything else is copied from the tensors this call writes)."""
         n = self.spec.n_labels
-        y0 = torch.as_tensor(y0, dtype=torch.float64)
-        if y0.dim() == 0:                               # the solver's fill_, as before there was a y0
-            self._y0_scalar = float(y0)
+        y0 = _start_point(y0, n, self.batch, self.eval_batch, self.device)
+        if isinstance(y0, float):                       # the solver's fill_, as before there was a y0
+            self._y0_scalar = y0
             return
-        y0 = y0.to(self.device)
-        if y0.dim() >= 3 and y0.numel() % n == 0:       # an image, or one per sample
-            y0 = y0.reshape(-1, n)
-        if y0.dim() == 2 and y0.shape[0] == 1:
-            y0 = y0[0]
-        if y0.dim() > 2 or y0.shape[-1] != n or (y0.dim() == 2 and y0.shape[0] != self.batch):
-            raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
-                             % (n, self.batch, tuple(y0.shape)))
         if self.eval_batch is not None:
-            if y0.dim() == 2 and self.eval_batch != self.batch:
-                raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
             if self.y0_eval is None:
                 self.y0_eval = torch.empty(self.eval_batch, n, dtype=torch.float64, device=self.device)
             self.y0_eval.copy_(y0.expand(self.eval_batch, n))
@@ -701,10 +714,8 @@ class BundleTrainer:
 
     def _infer(self, x=None, true_y=None):
         """the first half of step(): the copies, the context, the solve from y0 and the plan"""
-        if x is not None:
-            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
-        if true_y is not None:
-            self.true_y.copy_(torch.as_tensor(true_y).to(self.device, torch.float64).reshape(self.true_y.shape))
+        self._put(self.x, x)
+        self._put(self.true_y, true_y)
         self.model.context(self.x, out=self.ctx, work=self._ctx_work)
         self.solver.solve(self.ctx, self.y0 if self._y0_scalar is None else self._y0_scalar)
         self.plan.run(self.true_y)
@@ -742,10 +753,8 @@ class BundleTrainer:
         eval_f1_tallies ("xent") the tallies.  Nothing is updated and no statistic is folded.  No host wait (capturable)."""
         if self.eval_batch is None:
             raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        if x is not None:
-            self.x_eval.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x_eval.shape))
-        if true_y is not None:
-            self.true_y_eval.copy_(torch.as_tensor(true_y).to(self.device, torch.float64).reshape(self.true_y_eval.shape))
+        self._put(self.x_eval, x)
+        self._put(self.true_y_eval, true_y)
         self.model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
         self.eval_solver.solve(self.ctx_eval, self.y0_eval if self._y0_scalar is None else self._y0_scalar)
         self.eval_plan.run(self.true_y_eval)
@@ -770,27 +779,11 @@ class BundleTrainer:
         if bits & _lib.ST_OVERFLOW:
             raise MemoryError("the active bundle of a sample outgrew the cuts one workgroup can stage")
 
-    def macro_f1(self) -> float:
-        """the train F1 of the last step (util.macroF1; "xent" only; one wait)"""
-        if self.f1_tallies is None:
-            raise ValueError("F1 tallies exist for loss 'xent' only")
-        return macro_f1(self.f1_tallies)
-
-    @property
-    def t_steps(self) -> int:
-        return self.opt.t
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        return self.opt.params()
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.opt.host_params()
-
 
 # --------------------------------------------------------------------------------------------- #
 # The back-optimisation training step of the FC PICNNs as one device step
 # --------------------------------------------------------------------------------------------- #
-class GDTrainer:
+class GDTrainer(_Trainer, _TrainF1):
     """One training step of the back-optimisation scripts on a picnn.FCModel (synthetic-cls/icnn.py:117-139 with
     picnn.synthetic_spec(); multi-label-cls/icnn-back.py with the loss mean((y_K - t)^2)) at one batch size, all of it enqueued
     on the current stream without a host wait, so a step can be captured in a CUDA graph:
@@ -809,16 +802,16 @@ class GDTrainer:
     bn_updates is passed to surrogate_grad: k > 0 folds the BatchNorm statistics of the step k times into model.bn_stats (the
     caveat of unrolled_grad applies: the reference's graph calls f K times on its way to the loss, and whether TensorFlow
     merges those identical x-only subgraphs is not pinned down, so the count is the caller's)."""
+    _no_tallies = "F1 tallies are kept with f1=True only"
 
     def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, bn_updates=0, f1=False):
         if not isinstance(model, FCModel):
             name = model.__name__ if isinstance(model, type) else type(model).__name__
             raise TypeError("train.GDTrainer serves picnn.FCModel (ficnn.GDTrainer trains a FICNNModel), got %s" % name)
-        self.batch, self.n_iter, self.bn_updates = int(batch), int(n_iter), int(bn_updates)
+        self.batch, self.n_iter = int(batch), int(n_iter)
         if self.batch < 1 or self.n_iter < 1:
             raise ValueError("batch and n_iter must be >= 1")
-        if self.bn_updates < 0:
-            raise ValueError("bn_updates must be >= 0, got %d" % self.bn_updates)
+        self.bn_updates = _non_negative("bn_updates", bn_updates)
         self.model, self.spec, self.device = model, model.spec, model.device
         self.lr, self.momentum, self.y0 = float(lr), float(momentum), float(y0)
         self.opt = DeviceAdam(model, lr=adam_lr)
@@ -829,24 +822,20 @@ class GDTrainer:
         self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.y = None                                   # gd.solve's own y_K tensor, from the first step on
-        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
-        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
+        self.ctx, self._ctx_work = self._context_buffers(B)
         self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
         self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
         self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
         self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev) if f1 else None
-        n_work = int(model._lib.icnn_be_gd_feed_work_bytes(B))
-        self._feed_work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)      # zeroed once: the ticket
+        self._feed_work = _ticket(model._lib.icnn_be_gd_feed_work_bytes(B), dev)
         self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
         self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
 
     def step(self, x=None, t=None) -> torch.Tensor:
         """One step on (x [B, n_features], t [B, n]); None keeps the batch of the previous call (graph replay)."""
         from . import gd
-        if x is not None:
-            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
-        if t is not None:
-            self.t.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t.shape))
+        self._put(self.x, x)
+        self._put(self.t, t)
         model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
         model.context(self.x, out=self.ctx, work=self._ctx_work)
         self.y, traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
@@ -861,27 +850,11 @@ class GDTrainer:
         self.opt.step(self.grad)
         return self.loss
 
-    def macro_f1(self) -> float:
-        """the train F1 of the last step (util.macroF1; needs f1=True; one wait)"""
-        if self.f1_tallies is None:
-            raise ValueError("F1 tallies are kept with f1=True only")
-        return macro_f1(self.f1_tallies)
-
-    @property
-    def t_steps(self) -> int:
-        return self.opt.t
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        return self.opt.params()
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.opt.host_params()
-
 
 # --------------------------------------------------------------------------------------------- #
 # The back-optimisation training step and test phase of the completion model
 # --------------------------------------------------------------------------------------------- #
-class ConvGDTrainer:
+class ConvGDTrainer(_Trainer):
     """One training step of completion/icnn.back.py (:131-165 the graph, :210-239 the loop) on a picnn.ConvModel at one batch
     size, with the loss mean((pixel_scale (y_K - t))^2) of :149, all of it enqueued on the current stream without a host wait,
     so a step can be captured in a CUDA graph:
@@ -910,12 +883,11 @@ class ConvGDTrainer:
         if not isinstance(model, ConvModel):
             name = model.__name__ if isinstance(model, type) else type(model).__name__
             raise TypeError("train.ConvGDTrainer serves picnn.ConvModel (train.GDTrainer trains an FCModel), got %s" % name)
-        self.batch, self.n_iter, self.bn_updates = int(batch), int(n_iter), int(bn_updates)
+        self.batch, self.n_iter = int(batch), int(n_iter)
         self.eval_batch = None if eval_batch is None else int(eval_batch)
         if self.batch < 1 or self.n_iter < 1:
             raise ValueError("batch and n_iter must be >= 1")
-        if self.bn_updates < 0:
-            raise ValueError("bn_updates must be >= 0, got %d" % self.bn_updates)
+        self.bn_updates = _non_negative("bn_updates", bn_updates)
         if self.eval_batch is not None and self.eval_batch < 1:
             raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
         self.model, self.spec, self.device = model, model.spec, model.device
@@ -931,13 +903,11 @@ class ConvGDTrainer:
         self.y0 = torch.zeros(B, n, dtype=torch.float64, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.y = self.traj = None                       # gd.solve's own y_K and trajectory tensors, from the first step on
-        self.ctx = torch.empty(B, self.spec.ctx_width, dtype=torch.float32, device=dev)
-        self._ctx_work = torch.empty(model.context_work_floats(B), dtype=torch.float32, device=dev)
+        self.ctx, self._ctx_work = self._context_buffers(B)
         self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
         self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
         self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        n_work = int(lib.icnn_be_gd_feed_px_work_bytes(B, n, K))
-        self._feed_work = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)      # zeroed once: the ticket
+        self._feed_work = _ticket(lib.icnn_be_gd_feed_px_work_bytes(B, n, K), dev)
         self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
         self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
         self.y_eval = self.eval_loss = None
@@ -946,27 +916,17 @@ class ConvGDTrainer:
             self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
             self.y0_eval = torch.zeros(E, n, dtype=torch.float64, device=dev)
             self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
-            self.ctx_eval = torch.empty(E, self.spec.ctx_width, dtype=torch.float32, device=dev)
-            self._ctx_work_eval = torch.empty(model.context_work_floats(E), dtype=torch.float32, device=dev)
-            n_work = int(lib.icnn_be_gd_feed_px_work_bytes(E, n, K))
-            self._feed_work_eval = torch.zeros((n_work + 7) // 8, dtype=torch.float64, device=dev)
+            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
+            self._feed_work_eval = _ticket(lib.icnn_be_gd_feed_px_work_bytes(E, n, K), dev)
         self.set_y0(y0)
 
     def set_y0(self, y0):
         """The start point of step() and evaluate(): a scalar, an [n] row, an image [H, W, 1] or a [B, n] array ([B, H, W, 1]
         too).  A copy from the host: call it outside a capture."""
         n = self.spec.n_labels
-        y0 = torch.as_tensor(y0, dtype=torch.float64).to(self.device)
-        if y0.dim() >= 3:                               # an image, or one per sample
-            y0 = y0.reshape(-1, n)
-        if y0.dim() == 2 and y0.shape[0] == 1:
-            y0 = y0[0]
-        if y0.dim() > 2 or (y0.dim() >= 1 and y0.shape[-1] != n) or (y0.dim() == 2 and y0.shape[0] != self.batch):
-            raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
-                             % (n, self.batch, tuple(y0.shape)))
+        y0 = _start_point(y0, n, self.batch, self.eval_batch, self.device)
+        y0 = torch.as_tensor(y0, dtype=torch.float64, device=self.device)      # a scalar is expanded like a row
         if self.eval_batch is not None:
-            if y0.dim() == 2 and self.eval_batch != self.batch:
-                raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
             self.y0_eval.copy_(y0.expand(self.eval_batch, n))
         self.y0.copy_(y0.expand(self.batch, n))
 
@@ -983,10 +943,8 @@ class ConvGDTrainer:
         """One step on (x [B, H, W, 1] already h-flipped, t [B, n] or [B, H, W, 1]); None keeps the batch of the previous call
         (graph replay)."""
         from . import gd
-        if x is not None:
-            self.x.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x.shape))
-        if t is not None:
-            self.t.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t.shape))
+        self._put(self.x, x)
+        self._put(self.t, t)
         model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
         model.context(self.x, out=self.ctx, work=self._ctx_work)
         self.y, self.traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
@@ -1003,21 +961,9 @@ class ConvGDTrainer:
         from . import gd
         if self.eval_batch is None:
             raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        if x is not None:
-            self.x_eval.copy_(torch.as_tensor(x).to(self.device, torch.float32).reshape(self.x_eval.shape))
-        if t is not None:
-            self.t_eval.copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.t_eval.shape))
+        self._put(self.x_eval, x)
+        self._put(self.t_eval, t)
         self.model.context(self.x_eval, bn="moving", out=self.ctx_eval, work=self._ctx_work_eval)
         self.y_eval = gd.solve(self.model, self.ctx_eval, self.y0_eval, self.n_iter, self.lr, self.momentum)[0]
         self._feed(self.y_eval, self.t_eval, self.eval_batch, self.eval_loss, self._feed_work_eval, False)
         return self.eval_loss
-
-    @property
-    def t_steps(self) -> int:
-        return self.opt.t
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        return self.opt.params()
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.opt.host_params()

@@ -594,3 +594,56 @@ def test_ragged_lists_of_the_reference_tuple_are_lists_built_on_demand():
     assert _RaggedList(0, lambda: []) == [] and len(_RaggedList(0, lambda: [])) == 0
     lam = _RaggedList(2, lambda: [None, np.ones(2)])
     assert lam[0] is None and lam[1].shape == (2,)
+
+
+def test_models_state_entries_that_the_header_declares():
+    """Callers build every C entry name from what the model CLASS states (solve_entry, gd_entry, grad_floats_entry, the
+    stems grad_entry and context_entry plus the suffixes train.surrogate_grad / surrogate_work_floats and context append):
+    each is an export include/icnn_be.h declares.  No device, no instance."""
+    from icnn_amd import ficnn, picnn
+    header = open(os.path.join(REPO, "include", "icnn_be.h")).read()
+    declared = set(re.findall(r"ICNN_BE_API\s+[\w\s\*]+?\b(icnn_be_\w+)\s*\(", header))
+    picnn_grad = ("_bn", "_dev", "_work_floats", "_dev_work_floats")
+    picnn_ctx = ("", "_bn", "_bn_dev", "_work_floats", "_bn_work_floats")
+    for cls, grad, ctx in ((picnn.FCModel, picnn_grad, picnn_ctx), (picnn.ConvModel, picnn_grad, picnn_ctx),
+                           (ficnn.FICNNModel, ("", "_work_floats"), None)):
+        names = [cls.solve_entry, cls.gd_entry, cls.grad_floats_entry] + [cls.grad_entry + s for s in grad]
+        if ctx is not None:
+            names += [cls.context_entry + s for s in ctx]
+        for name in names:
+            assert name in declared, (cls.__name__, name)
+    assert len({picnn.FCModel.grad_entry, picnn.ConvModel.grad_entry, ficnn.FICNNModel.grad_entry}) == 3
+
+
+def test_grad_layout_of_each_spec_kind_follows_its_init_params():
+    """train.grad_layout stays a function of the spec, whichever module keeps the spec's layout: names in the key order of
+    the init function, shapes those of its arrays."""
+    from icnn_amd import ficnn, picnn, train
+    for spec, params in ((picnn.bibtex_spec(), picnn.init_params(picnn.bibtex_spec())),
+                         (picnn.ConvSpec(), picnn.init_conv_params(picnn.ConvSpec())),
+                         (ficnn.synthetic_spec(), ficnn.init_params(ficnn.synthetic_spec()))):
+        assert train.grad_layout(spec) == [(k, tuple(v.shape)) for k, v in params.items()], type(spec).__name__
+
+
+def test_trainers_start_point_forms():
+    """train._start_point, the one normaliser behind BundleTrainer.set_y0 and ConvGDTrainer.set_y0: a scalar comes back as
+    a Python float, every other accepted form as a float64 tensor that expands to the rows the trainers copy from it."""
+    from icnn_amd import train
+    H, W, B, E = 4, 2, 3, 5
+    n = H * W
+    rng = np.random.RandomState(0)
+    cpu = torch.device("cpu")
+    assert train._start_point(0.25, n, B, E, cpu) == 0.25 and isinstance(train._start_point(np.float32(0.5), n, B, None, cpu), float)
+    row, rows = rng.rand(n), rng.rand(B, n)
+    for given, want, eval_batch in ((row, row, E), (row.reshape(1, n), row, E), (row.reshape(H, W, 1), row, E),
+                                    (row.astype(np.float32), row.astype(np.float32).astype(np.float64), None),
+                                    (rows, rows, B), (rows, rows, None), (rows.reshape(B, H, W, 1), rows, B),
+                                    (torch.from_numpy(rows), rows, B)):
+        got = train._start_point(given, n, B, eval_batch, cpu)
+        assert torch.is_tensor(got) and got.dtype == torch.float64 and got.dim() == want.ndim
+        for count in (B, eval_batch or B):
+            assert np.array_equal(got.expand(count, n).numpy(), np.broadcast_to(want, (count, n)))
+    for bad, eval_batch in ((rng.rand(n + 1), None), (rng.rand(B + 1, n), None), (rng.rand(B + 1, H, W, 1), None),
+                            (rng.rand(2, B, n + 1), None), (rows, E), (rows.reshape(B, H, W, 1), E)):
+        with pytest.raises(ValueError):
+            train._start_point(bad, n, B, eval_batch, cpu)
