@@ -1,0 +1,115 @@
+"""The RL experiment's loop (RL/src/main.py:82-149) around icnn_amd.rl_agent.Agent on a small built-in environment: test
+episodes, then training episodes until the next multiple of --train, up to --total training steps, with --tmax and the
+returns logged.  The environment is NumPy: a damped point mass in dimA dimensions that the action pushes and the reward
+wants at the origin; the observation is (position, velocity), truncated or zero-padded to dimO.
+
+    python examples/rl_agent.py [--total 2000] [--train 200] [--test 2] [--tmax 50] [--warmup 100] [--bsize 64] [--iter 1]
+                                [--dimO 4] [--dimA 2] [--capture]
+"""
+import argparse
+import dataclasses
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+class PointMass:
+    """v <- (1 - damping) v + dt a,  p <- p + dt v,  reward -(|p|^2 + 0.1 |v|^2 + 0.01 |a|^2); an episode ends after
+    `horizon` steps or when the mass leaves the arena |p| <= 4."""
+
+    def __init__(self, dimO=4, dimA=2, horizon=40, dt=0.1, damping=0.1, seed=0):
+        self.dimO, self.dimA, self.horizon, self.dt, self.damping = dimO, dimA, horizon, dt, damping
+        self.rng = np.random.RandomState(seed)
+        self.reset()
+
+    def _obs(self):
+        full = np.concatenate([self.p, self.v])
+        out = np.zeros(self.dimO, np.float32)
+        k = min(self.dimO, full.size)
+        out[:k] = full[:k]
+        return out
+
+    def reset(self):
+        self.p = self.rng.uniform(-1, 1, self.dimA)
+        self.v = np.zeros(self.dimA)
+        self.steps = 0
+        return self._obs()
+
+    def step(self, action):
+        a = np.clip(np.asarray(action, np.float64).reshape(self.dimA), -1, 1)
+        self.v = (1 - self.damping) * self.v + self.dt * a
+        self.p = self.p + self.dt * self.v
+        self.steps += 1
+        reward = -(float(self.p @ self.p) + 0.1 * float(self.v @ self.v) + 0.01 * float(a @ a))
+        term = self.steps >= self.horizon or float(np.linalg.norm(self.p)) > 4.0
+        return self._obs(), reward, term
+
+
+def run_episode(env, agent, test, tmax):
+    """main.py:117-149"""
+    agent.reset(env.reset())
+    sum_reward, timestep, term = 0.0, 0, False
+    while not term:
+        action = agent.act(test=test)
+        observation, reward, term = env.step(action)
+        term = (not test and timestep + 1 >= tmax) or term
+        agent.observe(reward, term, observation, test=test)
+        sum_reward += reward
+        timestep += 1
+    return sum_reward, timestep
+
+
+def main():
+    import torch
+
+    from icnn_amd import picnn, rl_agent
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--total", type=int, default=2000)
+    ap.add_argument("--train", type=int, default=200)
+    ap.add_argument("--test", type=int, default=2)
+    ap.add_argument("--tmax", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--bsize", type=int, default=64)
+    ap.add_argument("--iter", type=int, default=1)
+    ap.add_argument("--rmsize", type=int, default=100000)
+    ap.add_argument("--dimO", type=int, default=4)
+    ap.add_argument("--dimA", type=int, default=2)
+    ap.add_argument("--l1size", type=int, default=64)
+    ap.add_argument("--l2size", type=int, default=64)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--capture", action="store_true")
+    args = ap.parse_args()
+    spec = dataclasses.replace(picnn.halfcheetah_spec(), n_features=args.dimO, n_labels=args.dimA,
+                               szs=(args.l1size, args.l2size), action_box=False)
+    params = picnn.init_params(spec, args.seed)
+    critic, target = picnn.FCModel(spec, params, "cuda"), picnn.FCModel(spec, params, "cuda")
+    agent = rl_agent.Agent(critic, target, bsize=args.bsize, warmup=args.warmup, iters=args.iter, rmsize=args.rmsize,
+                           seed=args.seed, capture=args.capture)
+    env = PointMass(args.dimO, args.dimA, seed=args.seed)
+    train_timestep = 0
+    while train_timestep < args.total:
+        rewards = [run_episode(env, agent, True, args.tmax)[0] for _ in range(args.test)]
+        print("Average test return {} after {} timestep of training.".format(np.mean(rewards), train_timestep))
+        rewards, checkpoint = [], train_timestep // args.train
+        while train_timestep // args.train == checkpoint:
+            reward, timestep = run_episode(env, agent, False, args.tmax)
+            rewards.append(reward)
+            train_timestep += timestep
+            if agent.t > agent.warmup:
+                loss = float(agent.loss.item())
+                if not np.isfinite(loss):
+                    raise RuntimeError("the critic's loss is not finite")
+                print("  + train {}\treturn {:.4f}\tloss {:.5e}".format(train_timestep, reward, loss))
+            else:
+                print("  + train {}\treturn {:.4f}\t(warm-up: no training yet)".format(train_timestep, reward))
+        print("Average train return {} after {} timestep of training.".format(np.mean(rewards), train_timestep))
+    agent.memory.raise_on_error()
+    torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main()

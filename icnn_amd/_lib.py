@@ -65,6 +65,7 @@ EXPORTS = [
     "icnn_be_fc_surrogate_grad_dev_work_floats", "icnn_be_conv_surrogate_grad_dev_work_floats",
     "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed", "icnn_be_gd_feed_px_work_bytes", "icnn_be_gd_feed_px",
     "icnn_be_step_gate", "icnn_be_param_update_gated", "icnn_be_gated_copy",
+    "icnn_be_replay_enqueue", "icnn_be_replay_sample",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -72,6 +73,14 @@ BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
 MAX_PROJ_RANGES = 8
 RL_TD_MAX_BLOCKS = 256
 RL_TD_WORK_BYTES = 8 * RL_TD_MAX_BLOCKS + 16
+REPLAY_CTRL_INTS = 8                       # ICNN_BE_REPLAY_CTRL_INTS: cursor, fill, draws, status, ticket
+REPLAY_MAX_ATTEMPTS = 256
+REPLAY_ST_EXHAUSTED, REPLAY_ST_STATE = 1, 2
+
+
+def replay_stage_bytes(dimO, dimA):
+    """ICNN_BE_REPLAY_STAGE_BYTES: action float64 [dimA], observation float32 [dimO], reward float32, terminal uint32"""
+    return 8 * dimA + 4 * dimO + 8
 
 
 class State(C.Structure):
@@ -152,6 +161,14 @@ class RlUpdateArgs(C.Structure):
     _fields_ = [
         ("adam", ParamUpdateArgs), ("target_theta", C.c_void_p), ("target_arena", C.c_void_p), ("decay", C.c_void_p),
         ("tau", C.c_float), ("l2norm", C.c_float), ("wd", C.c_float),
+    ]
+
+
+class Replay(C.Structure):
+    """struct icnn_be_replay"""
+    _fields_ = [
+        ("size", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("observations", C.c_void_p), ("actions", C.c_void_p),
+        ("rewards", C.c_void_p), ("terminals", C.c_void_p), ("ctrl", C.c_void_p),
     ]
 
 
@@ -331,6 +348,10 @@ def load():
     lib.icnn_be_rl_td.restype = C.c_int
     lib.icnn_be_rl_critic_update.argtypes = [C.POINTER(RlUpdateArgs), C.c_void_p]
     lib.icnn_be_rl_critic_update.restype = C.c_int
+    lib.icnn_be_replay_enqueue.argtypes = [C.POINTER(Replay), C.c_void_p, C.c_void_p]
+    lib.icnn_be_replay_enqueue.restype = C.c_int
+    lib.icnn_be_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 7
+    lib.icnn_be_replay_sample.restype = C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -362,6 +383,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_rl_update_args differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(8) != C.sizeof(FicnnModel):
         raise ImportError("ctypes struct layout of icnn_be_ficnn_model differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(9) != C.sizeof(Replay):
+        raise ImportError("ctypes struct layout of icnn_be_replay differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

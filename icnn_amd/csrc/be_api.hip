@@ -203,6 +203,16 @@ int check_param_update(const icnn_be_param_update_args *a) {
         if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
     return 0;
 }
+
+// what icnn_be_replay_enqueue and icnn_be_replay_sample refuse in the memory's descriptor
+int check_replay(const icnn_be_replay *m) {
+    if (!m || m->size < 3 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
+    if (!m->observations || !m->actions || !m->rewards || !m->terminals || !m->ctrl) return ICNN_BE_EINVAL;
+    const void *a4[] = {m->observations, m->actions, m->rewards, m->ctrl};
+    for (const void *p : a4)
+        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -216,7 +226,7 @@ size_t icnn_be_struct_size(int which) {
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
          : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving)
          : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args)
-         : which == 8 ? sizeof(icnn_be_ficnn_model) : 0;
+         : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -899,6 +909,27 @@ int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
         !std::isfinite(a->wd))
         return ICNN_BE_EINVAL;
     hipError_t e = icnn_be::launch_rl_critic_update(*a, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {
+    if (int rc = check_replay(m)) return rc;
+    if (!stage || reinterpret_cast<uintptr_t>(stage) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_replay_enqueue(*m, stage, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
+                          float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
+    if (int rc = check_replay(m)) return rc;
+    if (batch < 1 || fill < 2 || fill > m->size - 1) return ICNN_BE_EINVAL;
+    if (!obs || !act || !rew || !ob2 || !term || !idx) return ICNN_BE_EINVAL;
+    const void *a4[] = {obs, rew, ob2, idx};
+    for (const void *p : a4)
+        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    const icnn_be::ReplaySampleLaunch l{*m, batch, seed, obs, act, rew, ob2, term, idx};
+    hipError_t e = icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : fail(e);
 }
 

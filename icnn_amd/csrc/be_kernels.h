@@ -324,4 +324,20 @@ int rl_td_blocks(long long n_theta);
 hipError_t launch_rl_td(const RlTdLaunch &l, hipStream_t stream);
 hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream);
 
+// ---- the RL agent's replay memory (be_rl_replay.hip) -----------------------------------
+struct ReplaySampleLaunch {
+    icnn_be_replay m;
+    int batch;
+    unsigned long long seed;
+    float *obs;
+    double *act;
+    float *rew;
+    float *ob2;
+    unsigned char *term;
+    int *idx;
+};
+long long replay_sample_blocks(int batch);
+hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream);
+hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream);
+
 }  // namespace icnn_be

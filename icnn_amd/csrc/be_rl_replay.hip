@@ -1,0 +1,153 @@
+// The RL agent's replay memory on the device (RL/src/replay_memory.py; include/icnn_be.h, icnn_be_replay_enqueue and
+// icnn_be_replay_sample): the arrays, the cursor, the fill and the draw counter live in device memory, so
+// that a captured [sample, critic step] x iter reads the current values on every replay.
+//
+//   replay_enqueue_kernel   one transition from the staging row into slot i, then i <- (i + 1) % size and
+//                           n <- min(size - 1, n + 1) (replay_memory.py:27-34).  One wave: it runs once per environment step.
+//   replay_sample_kernel    a minibatch in one launch, one wave per sample.  The rejection loop of replay_memory.py:36-46 is
+//                           wave-uniform (every lane computes the same Philox4x32-10 word) and bounded at
+//                           ICNN_BE_REPLAY_MAX_ATTEMPTS; the lanes then copy the rows idx and idx + 1 (:48-52), dword by
+//                           dword -- a row starts at idx * dimO * 4 bytes, which is 16-byte aligned only when dimO % 4 == 0.
+//                           The last workgroup to take a ticket advances the draw counter and re-arms the ticket: every
+//                           workgroup has read the counter before it takes its ticket, which a plain store by workgroup 0
+//                           would not wait for.
+//
+// The candidate range is clamped to the arrays from the device's own n (2 <= n <= size - 1 gives cand <= size - 3 and
+// cand + 1 <= size - 2), so the gather stays inside the arrays whatever the control block holds.
+#include "be_kernels.h"
+
+namespace icnn_be {
+
+namespace {
+
+constexpr int ENQ_THREADS = 64;
+constexpr int SMP_WAVES = 4;
+constexpr int SMP_THREADS = 64 * SMP_WAVES;
+enum { CTRL_I = 0, CTRL_N = 1, CTRL_DRAWS = 2, CTRL_STATUS = 3, CTRL_TICKET = 4 };
+
+__device__ __forceinline__ int ctrl_load(const int *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// word 0 of Philox4x32-10 (Salmon et al., SC'11) at counter (c0, c1, c2, c3) and key (k0, k1)
+__device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                                        unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__global__ __launch_bounds__(ENQ_THREADS) void replay_enqueue_kernel(icnn_be_replay m, const unsigned char *stage) {
+    const int tid = threadIdx.x;
+    const int i = ctrl_load(m.ctrl + CTRL_I), n = ctrl_load(m.ctrl + CTRL_N);
+    if (i < 0 || i >= m.size) {                                    // never with a control block this library wrote
+        if (tid == 0) __hip_atomic_fetch_or(m.ctrl + CTRL_STATUS, ICNN_BE_REPLAY_ST_STATE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const double *s_act = reinterpret_cast<const double *>(stage);
+    const float *s_obs = reinterpret_cast<const float *>(stage + 8 * (size_t)m.dimA);
+    float *obs = m.observations + (long long)i * m.dimO;
+    float *act = m.actions + (long long)i * m.dimA;
+    for (int j = tid; j < m.dimO; j += ENQ_THREADS) obs[j] = s_obs[j];
+    for (int j = tid; j < m.dimA; j += ENQ_THREADS) act[j] = (float)s_act[j];    // the reference's actions array is float32
+    __syncthreads();
+    if (tid == 0) {
+        m.rewards[i] = s_obs[m.dimO];
+        m.terminals[i] = reinterpret_cast<const unsigned *>(s_obs + m.dimO + 1)[0] != 0u;
+        const int next = i + 1 == m.size ? 0 : i + 1;
+        __hip_atomic_store(m.ctrl + CTRL_I, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(m.ctrl + CTRL_N, n + 1 < m.size - 1 ? n + 1 : m.size - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+struct SampleArgs {
+    icnn_be_replay m;
+    int batch;
+    unsigned k0, k1;
+    float *obs;
+    double *act;
+    float *rew;
+    float *ob2;
+    unsigned char *term;
+    int *idx;
+};
+
+__global__ __launch_bounds__(SMP_THREADS) void replay_sample_kernel(SampleArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * SMP_WAVES + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int cur = __builtin_amdgcn_readfirstlane(ctrl_load(a.m.ctrl + CTRL_I));
+    const int n_dev = __builtin_amdgcn_readfirstlane(ctrl_load(a.m.ctrl + CTRL_N));
+    const unsigned draws = (unsigned)__builtin_amdgcn_readfirstlane(ctrl_load(a.m.ctrl + CTRL_DRAWS));
+    if (k < a.batch) {
+        const int n = n_dev < 2 ? 2 : n_dev > a.m.size - 1 ? a.m.size - 1 : n_dev;
+        const unsigned range = (unsigned)(n - 1);                  // randint(0, n - 1): uniform on [0, n - 2]
+        int cand = 0;
+        bool ok = false;
+        for (int attempt = 0; attempt < ICNN_BE_REPLAY_MAX_ATTEMPTS && !ok; ++attempt) {
+            const unsigned w = philox4x32_10_word0(draws, (unsigned)k, (unsigned)attempt, 0u, a.k0, a.k1);
+            cand = (int)__umulhi(w, range);
+            ok = cand != cur && a.m.terminals[cand] == 0;
+        }
+        if (lane == 0) {
+            const int st = (ok ? 0 : ICNN_BE_REPLAY_ST_EXHAUSTED) | (n == n_dev ? 0 : ICNN_BE_REPLAY_ST_STATE);
+            if (st) __hip_atomic_fetch_or(a.m.ctrl + CTRL_STATUS, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.rew[k] = a.m.rewards[cand];
+            a.term[k] = a.m.terminals[cand + 1];
+            a.idx[k] = cand;
+        }
+        const long long dimO = a.m.dimO, dimA = a.m.dimA;
+        const float *src = a.m.observations + (long long)cand * dimO;     // rows cand and cand + 1 are adjacent
+        float *o1 = a.obs + (long long)k * dimO, *o2 = a.ob2 + (long long)k * dimO;
+        for (long long j = lane; j < dimO; j += 64) {
+            o1[j] = src[j];
+            o2[j] = src[dimO + j];
+        }
+        const float *sa = a.m.actions + (long long)cand * dimA;
+        double *da = a.act + (long long)k * dimA;
+        for (long long j = lane; j < dimA; j += 64) da[j] = (double)sa[j];
+    }
+    // the draw counter: the last workgroup to arrive advances it and re-arms the ticket for the next launch
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int ticket = __hip_atomic_fetch_add(a.m.ctrl + CTRL_TICKET, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == (int)gridDim.x - 1) {
+            __hip_atomic_store(a.m.ctrl + CTRL_DRAWS, (int)(draws + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.m.ctrl + CTRL_TICKET, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+}  // namespace
+
+long long replay_sample_blocks(int batch) { return ((long long)batch + SMP_WAVES - 1) / SMP_WAVES; }
+
+hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream) {
+    return launch_kernel(replay_enqueue_kernel, dim3(1), dim3(ENQ_THREADS), 0, stream, m,
+                         static_cast<const unsigned char *>(stage));
+}
+
+hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream) {
+    SampleArgs a{};
+    a.m = l.m;
+    a.batch = l.batch;
+    a.k0 = (unsigned)(l.seed & 0xffffffffull);
+    a.k1 = (unsigned)(l.seed >> 32);
+    a.obs = l.obs;
+    a.act = l.act;
+    a.rew = l.rew;
+    a.ob2 = l.ob2;
+    a.term = l.term;
+    a.idx = l.idx;
+    return launch_kernel(replay_sample_kernel, dim3((unsigned)replay_sample_blocks(l.batch)), dim3(SMP_THREADS), 0, stream, a);
+}
+
+}  // namespace icnn_be

@@ -1,0 +1,196 @@
+"""The RL agent on the device: the replay memory of RL/src/replay_memory.py and the reset / act / observe /
+train cycle of RL/src/icnn.py:260-323 with FLAGS.icnn_opt == 'adam', around rl_train.CriticTrainer and rl_adam.AdamSolver.
+
+The memory's arrays, its cursor, its fill and the draw counter of the sampler live in device memory
+(icnn_amd/csrc/be_rl_replay.hip): a training iteration is [icnn_be_replay_sample into the trainer's buffers,
+CriticTrainer.step_buffers()] with no host data in it, so `iters` of them can be captured once and replayed on every
+environment step.  The one host wait per environment step is act()'s copy of the action to the environment.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, rl_adam, rl_train
+
+
+class ReplayMemory:
+    """RL/src/replay_memory.py on the device.  enqueue() stages one transition through a pageable host row and one blocking
+    copy, so the caller may reuse its arrays at once; sample() / sample_into() are one launch on the current stream without a
+    host wait.  n and i are host mirrors of the device's fill and cursor (deterministic, never read back).  The sampler
+    follows the reference's rule with its own random numbers: Philox4x32-10 keyed by `seed`, counter (draw, sample, attempt,
+    0), at most _lib.REPLAY_MAX_ATTEMPTS attempts per sample -- raise_on_error() reports a sample that spent them."""
+
+    def __init__(self, size, dimO, dimA, device="cuda", seed=0):
+        self.size, self.dimO, self.dimA, self.seed = int(size), int(dimO), int(dimA), int(seed)
+        if self.size < 3 or self.dimO < 1 or self.dimA < 1:
+            raise ValueError("a replay memory needs size >= 3, dimO >= 1 and dimA >= 1")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError("seed must fit 64 bits")
+        self.device = dev = torch.device(device)
+        self.lib = _lib.load()
+        self.observations = torch.zeros(self.size, self.dimO, dtype=torch.float32, device=dev)
+        self.actions = torch.zeros(self.size, self.dimA, dtype=torch.float32, device=dev)
+        self.rewards = torch.zeros(self.size, dtype=torch.float32, device=dev)
+        self.terminals = torch.zeros(self.size, dtype=torch.uint8, device=dev)
+        self.ctrl = torch.zeros(_lib.REPLAY_CTRL_INTS, dtype=torch.int32, device=dev)
+        self._stage = torch.zeros(_lib.replay_stage_bytes(self.dimO, self.dimA), dtype=torch.uint8, device=dev)
+        self._row = np.zeros(self._stage.numel(), np.uint8)          # pageable: the copy below returns once it is read
+        a = 8 * self.dimA
+        self._row_act, self._row_obs = self._row[:a].view(np.float64), self._row[a:a + 4 * self.dimO].view(np.float32)
+        self._row_rew = self._row[a + 4 * self.dimO:a + 4 * self.dimO + 4].view(np.float32)
+        self._row_term = self._row[a + 4 * self.dimO + 4:].view(np.uint32)
+        m = _lib.Replay()
+        m.size, m.dimO, m.dimA = self.size, self.dimO, self.dimA
+        m.observations, m.actions = self.observations.data_ptr(), self.actions.data_ptr()
+        m.rewards, m.terminals, m.ctrl = self.rewards.data_ptr(), self.terminals.data_ptr(), self.ctrl.data_ptr()
+        self._c = m
+        self._idx = {}                       # batch -> the int32 index buffer of sample_into (fixed: a captured graph writes it)
+        self.n = self.i = 0
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        """replay_memory.py:23-25, and the sampler back at draw 0 with a clear status word"""
+        self.ctrl.zero_()
+        self.n = self.i = 0
+
+    def enqueue(self, obs, term, act, rew):
+        """replay_memory.py:27-34 (argument order included).  Not capturable: a copy from the host."""
+        self._row_obs[:] = np.asarray(obs, np.float32).reshape(self.dimO)
+        self._row_act[:] = np.asarray(act, np.float64).reshape(self.dimA)
+        self._row_rew[0] = rew
+        self._row_term[0] = 1 if term else 0
+        self._stage.copy_(torch.from_numpy(self._row))
+        _lib.check(self.lib.icnn_be_replay_enqueue(C.byref(self._c), self._stage.data_ptr(), self._stream()),
+                   "icnn_be_replay_enqueue")
+        self.i = (self.i + 1) % self.size
+        self.n = min(self.size - 1, self.n + 1)
+
+    def _sample(self, batch, obs, act, rew, ob2, term, idx):
+        _lib.check(self.lib.icnn_be_replay_sample(C.byref(self._c), self.n, batch, self.seed, obs.data_ptr(), act.data_ptr(),
+                                                  rew.data_ptr(), ob2.data_ptr(), term.data_ptr(), idx.data_ptr(),
+                                                  self._stream()), "icnn_be_replay_sample")
+
+    def sample_into(self, trainer) -> torch.Tensor:
+        """replay_memory.py:36-55 straight into a CriticTrainer's obs / act / rew / ob2 / term buffers; returns the sampled
+        indices (int32 [B], a buffer of this memory that the next call at this batch size overwrites)."""
+        if trainer.obs.shape[1] != self.dimO or trainer.act.shape[1] != self.dimA or trainer.device != self.device:
+            raise ValueError("the trainer's shapes or device differ from the memory's")
+        B = trainer.batch
+        if B not in self._idx:
+            self._idx[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._sample(B, trainer.obs, trainer.act, trainer.rew, trainer.ob2, trainer.term, self._idx[B])
+        return self._idx[B]
+
+    def sample(self, batch):
+        """a minibatch as new tensors: (obs f32 [B, dimO], act f64 [B, dimA], rew f32 [B], ob2 f32 [B, dimO], term u8 [B],
+        idx i32 [B])"""
+        B, dev = int(batch), self.device
+        out = (torch.empty(B, self.dimO, dtype=torch.float32, device=dev), torch.empty(B, self.dimA, dtype=torch.float64, device=dev),
+               torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, self.dimO, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        self._sample(B, *out)
+        return out
+
+    @property
+    def status(self) -> int:
+        """the device's status word, an OR of _lib.REPLAY_ST_* (synchronises)"""
+        return int(self.ctrl[3].item())
+
+    def raise_on_error(self):
+        """Raise if a launch so far met an error on the device (synchronises): a sample that found no valid index within the
+        attempt bound, or a control block outside the arrays."""
+        st = self.status
+        if st & _lib.REPLAY_ST_EXHAUSTED:
+            raise RuntimeError("replay memory: a sample found no valid index in %d attempts (nearly every slot below n - 1 "
+                               "is terminal or the cursor's); its last candidate was used" % _lib.REPLAY_MAX_ATTEMPTS)
+        if st:
+            raise RuntimeError("replay memory: the device control block was outside the arrays (status %d)" % st)
+
+
+class Agent:
+    """`Agent` of RL/src/icnn.py with the adam inner optimiser: critic and target are picnn.FCModel of one spec with
+    action_box False.  The constructor builds the CriticTrainer at minibatch size `bsize` (lr, tau, discount, l2norm, wd and
+    max_iter go to it), initialises it as the reference does (:139-142: makeCvx, then target <- critic) and builds the
+    ReplayMemory of `rmsize` transitions.  seed: the exploration noise's np.random.RandomState and the memory's sampler.
+
+    capture=True: the first training observe() runs its `iters` iterations eagerly; the next one captures them once into a
+    graph (a linear chain of [sample, step] x iters) and every later observe() replays it."""
+
+    def __init__(self, critic, target, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1, seed=0,
+                 capture=False, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000):
+        if warmup < 2:
+            raise ValueError("warmup must be at least 2: the sampler needs two transitions, got %r" % (warmup,))
+        if iters < 0:
+            raise ValueError("iters must not be negative")
+        self.trainer = rl_train.CriticTrainer(critic, target, bsize, lr=lr, tau=tau, discount=discount, l2norm=l2norm, wd=wd,
+                                              max_iter=max_iter)
+        self.trainer.initialise()
+        self.critic, self.spec, self.device = critic, critic.spec, critic.device
+        self.dimO, self.dimA = self.spec.n_features, self.spec.n_labels
+        self.memory = ReplayMemory(rmsize, self.dimO, self.dimA, self.device, seed)
+        self.warmup, self.iters, self.outheta, self.ousigma = int(warmup), int(iters), float(outheta), float(ousigma)
+        self.rng = np.random.RandomState(seed)
+        self.capture = bool(capture)
+        self._solver = rl_adam.AdamSolver(critic, 1, max_iter)
+        self._graph, self._trained = None, False
+        self.noise = np.zeros(self.dimA)
+        self.observation = self.action = None
+        self.t = 0                           # observations seen in training (icnn.py:146)
+
+    def reset(self, obs):
+        """icnn.py:260-262"""
+        self.noise = np.zeros(self.dimA)
+        self.observation = obs
+
+    def act(self, test=False):
+        """icnn.py:264-288: the inner Adam on the critic at the current observation (inference-mode BatchNorm), plus the
+        Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns float64 [dimA]; the copy to the host is the one
+        synchronisation of an environment step."""
+        obs = torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO))
+        ctx = self.critic.context(obs, bn="moving") if self.spec.batchnorm else self.critic.context(obs)
+        action = self._solver.solve(ctx).act_best.cpu().numpy()
+        if not test:
+            self.noise -= self.outheta * self.noise - self.ousigma * self.rng.randn(self.dimA)
+            action += self.noise
+        action = np.clip(action, -1, 1)
+        self.action = np.atleast_1d(np.squeeze(action, axis=0))
+        return self.action
+
+    def observe(self, rew, term, obs2, test=False):
+        """icnn.py:290-302"""
+        obs1 = self.observation
+        self.observation = obs2
+        if not test:
+            self.t = self.t + 1
+            self.memory.enqueue(obs1, term, self.action, rew)
+            if self.t > self.warmup:
+                self._train_iters()
+
+    def _train_iters(self):
+        if self.iters == 0:
+            return
+        if not self.capture or not self._trained:
+            for _ in range(self.iters):
+                self.train()
+            self._trained = True
+            return
+        if self._graph is None:
+            self._graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph):
+                for _ in range(self.iters):
+                    self.train()
+        self._graph.replay()
+
+    def train(self) -> torch.Tensor:
+        """icnn.py:304-323: a minibatch from the memory into the trainer's buffers and one critic step.  Returns the
+        trainer's device loss scalar, without a host wait."""
+        self.memory.sample_into(self.trainer)
+        return self.trainer.step_buffers()
+
+    @property
+    def loss(self) -> torch.Tensor:
+        """the last training iteration's loss (the trainer's 0-d device tensor)"""
+        return self.trainer.loss

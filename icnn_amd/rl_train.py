@@ -118,6 +118,11 @@ class CriticTrainer:
         self.rew.copy_(torch.as_tensor(rew).reshape(self.rew.shape))
         self.ob2.copy_(torch.as_tensor(ob2).reshape(self.ob2.shape))
         self.term.copy_(torch.as_tensor(term).reshape(self.term.shape))
+        return self.step_buffers()
+
+    def step_buffers(self) -> torch.Tensor:
+        """step() on what the trainer's own obs / act / rew / ob2 / term buffers hold, without the five copies: the minibatch
+        was written there on the device (rl_agent.ReplayMemory.sample_into).  Same return value, no host synchronisation."""
         bn = self.spec.batchnorm
         # 1-3: the target
         ctx2 = self.target.context(self.ob2, bn="moving") if bn else self.target.context(self.ob2)

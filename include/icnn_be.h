@@ -218,7 +218,7 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
- * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8: lets a
+ * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9: lets a
  * foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
@@ -790,6 +790,53 @@ typedef struct icnn_be_rl_update_args {
 } icnn_be_rl_update_args;
 
 ICNN_BE_API int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream);
+
+/* ---- the RL agent's replay memory: enqueue and minibatch sampling (be_rl_replay.hip, additive to ABI 12) ---- */
+
+/*
+ * A replay memory of `size` transitions in device memory (RL/src/replay_memory.py).  ctrl: ICNN_BE_REPLAY_CTRL_INTS int32,
+ * zero for an empty memory: [0] the cursor i, [1] the fill n, [2] the draw counter, [3] the status word (an OR of
+ * ICNN_BE_REPLAY_ST_*), [4] a ticket the sampling kernel re-arms.  They live on the device so that a captured
+ * [sample, critic step] reads the current values on every replay; i and n are deterministic (i = enqueues % size,
+ * n = min(size - 1, enqueues)), so the host mirrors them without a synchronisation.
+ */
+#define ICNN_BE_REPLAY_CTRL_INTS 8
+#define ICNN_BE_REPLAY_MAX_ATTEMPTS 256
+#define ICNN_BE_REPLAY_ST_EXHAUSTED 1     /* a sample spent ICNN_BE_REPLAY_MAX_ATTEMPTS candidates and kept the last one */
+#define ICNN_BE_REPLAY_ST_STATE 2         /* the control block held a cursor or a fill outside the arrays */
+/* bytes of the staging row of icnn_be_replay_enqueue: action float64 [dimA], observation float32 [dimO], reward float32,
+ * terminal uint32 (nonzero: set), in this order */
+#define ICNN_BE_REPLAY_STAGE_BYTES(dimO, dimA) (8 * (size_t)(dimA) + 4 * (size_t)(dimO) + 8)
+typedef struct icnn_be_replay {
+    int size, dimO, dimA;
+    float *observations;              /* [size, dimO] */
+    float *actions;                   /* [size, dimA]: float32, as the reference stores them */
+    float *rewards;                   /* [size] */
+    unsigned char *terminals;         /* [size] */
+    int *ctrl;                        /* [ICNN_BE_REPLAY_CTRL_INTS] */
+} icnn_be_replay;
+
+/*
+ * replay_memory.py:27-34: the transition in the device staging row `stage` (layout above, 8-byte aligned) goes to slot i
+ * (the float64 action rounded to float32), then i <- (i + 1) % size and n <- min(size - 1, n + 1).  One launch, stream
+ * ordered after the copy that filled the row.  EINVAL for a NULL m or stage, size < 3, dimO < 1, dimA < 1, a NULL or
+ * misaligned array (4 bytes; stage 8), a misaligned stream, before anything is launched.  No host synchronisation.
+ */
+ICNN_BE_API int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream);
+
+/*
+ * replay_memory.py:36-55 as written: for each k < batch a candidate uniform on [0, n - 2] is drawn until it is neither
+ * the cursor i nor a terminal slot; then obs[k] = observations[idx], act[k] = (double)actions[idx], rew[k] = rewards[idx],
+ * ob2[k] = observations[idx + 1], term[k] = terminals[idx + 1] (no wrap handling), idx[k] = idx.  Candidate number
+ * `attempt` of sample k in draw d is the high 32 bits of word * (n - 1), word = word 0 of Philox4x32-10 at counter
+ * (d, k, attempt, 0) and key (seed low, seed high); d is the device's draw counter, which the launch advances by one.  At
+ * most ICNN_BE_REPLAY_MAX_ATTEMPTS candidates per sample: a sample that spends them keeps the last one (in range) and
+ * ICNN_BE_REPLAY_ST_EXHAUSTED is ORed into the status word.  fill: the host's mirror of n.  EINVAL for what
+ * icnn_be_replay_enqueue refuses in m, batch < 1, fill < 2 or > size - 1, a NULL or misaligned output (act 8 bytes, the
+ * others 4, term 1), a misaligned stream, before anything is launched.  No host synchronisation (capturable).
+ */
+ICNN_BE_API int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs,
+                                      double *act, float *rew, float *ob2, unsigned char *term, int *idx, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
