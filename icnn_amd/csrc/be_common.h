@@ -47,6 +47,27 @@ __device__ __forceinline__ float wave_sum_f(float v) {
     return v;
 }
 
+// One value per thread of a THREADS-wide workgroup reduced through red[THREADS] (LDS) by a fixed binary tree: thread t takes
+// op(red[t], red[t + s]) for s = THREADS / 2, ..., 1.  The order depends on nothing but THREADS, so the sums that are formed
+// this way (the losses of the training units) are the same bits on every call.  Valid in every thread; red is free again on
+// return.
+template <int THREADS, typename T, typename Op>
+__device__ __forceinline__ T block_tree_reduce(T v, T *red, Op op) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const T out = red[0];
+    __syncthreads();
+    return out;
+}
+template <int THREADS, typename T>
+__device__ __forceinline__ T block_tree_sum(T v, T *red) {
+    return block_tree_reduce<THREADS>(v, red, [](T a, T b) { return a + b; });
+}
+
 // Butterfly exchange inside groups of 8 lanes with DPP (no LDS traffic): steps 1 and 2 are
 // quad permutes, step 4 is row_half_mirror (lane i <- lane 7-i of its group of eight; after steps
 // 1 and 2 every lane of a quad holds the quad's sum, so this adds the other quad's sum).

@@ -160,6 +160,13 @@ hipError_t launch_tr_gemm(const float *A, long long sam, long long sak, const fl
 // [R][C] of each sample summed in row order
 hipError_t launch_tr_rows(const int *row_offset, int B, int R, int *samp, float *mult, hipStream_t stream);
 hipError_t launch_tr_segment_sum(const float *rows, const int *row_offset, int B, int R, int C, float *out, hipStream_t stream);
+// dst [(n + wprev)][w] = [ Wy ; Wz ] row-major out of the packed forward fragments at wpack + yf and wpack + zf (last: the
+// width-1 head's plain vectors); count floats of zero (a kernel: a captured step keeps its node types); out[col] = the sum
+// over the B rows of m[.][c0 + col] (pitch ld), rows in order
+hipError_t launch_tr_unpack(const float *wpack, long long yf, long long zf, int n, int wprev, int w, bool last, float *dst,
+                            hipStream_t stream);
+hipError_t launch_tr_zero(float *p, size_t count, hipStream_t stream);
+hipError_t launch_tr_colsum(const float *m, int ld, int B, int c0, int N, float *out, hipStream_t stream);
 
 // training gradient of the conv PICNN (be_train_conv.hip), as the FC one above
 size_t conv_grad_floats(const icnn_be_conv_model &m, const icnn_be_conv_ctx &c);
@@ -296,12 +303,13 @@ constexpr int GD_FEED_PX_MAX_CHUNKS = 65535; // gridDim.y
 long long gd_feed_px_chunks(int n, int K);
 hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream);
 
-// ---- parameter update (be_train_update.hip) -----------------------------------------
+// ---- parameter update (be_train_update.hip): plain, gated, and the RL critic's with its target net ------
 long long param_update_blocks(long long n);
 hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream);   // go NULL: ungated
+hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream);
 hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream);
 
-// ---- the RL critic's step (be_rl_train.hip) -----------------------------------------
+// ---- the RL critic's TD target and loss (be_rl_train.hip) ---------------------------
 struct RlTdLaunch {
     int batch, n;
     const float *e_critic;
@@ -322,7 +330,6 @@ struct RlTdLaunch {
 };
 int rl_td_blocks(long long n_theta);
 hipError_t launch_rl_td(const RlTdLaunch &l, hipStream_t stream);
-hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream);
 
 // ---- the RL agent's replay memory (be_rl_replay.hip) -----------------------------------
 struct ReplaySampleLaunch {

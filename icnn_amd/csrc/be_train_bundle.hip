@@ -31,34 +31,6 @@ struct PlanArgs {
     int *ticket;
 };
 
-// the same tree for every call; valid in every thread
-__device__ __forceinline__ double plan_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = PT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
-// op 0: sum, 1: max, 2: min, 3: or
-__device__ __forceinline__ int plan_reduce(int v, int *red, int op) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = PT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            const int a = red[threadIdx.x], b = red[threadIdx.x + s];
-            red[threadIdx.x] = op == 0 ? a + b : op == 1 ? max(a, b) : op == 2 ? min(a, b) : (a | b);
-        }
-        __syncthreads();
-    }
-    const int out = red[0];
-    __syncthreads();
-    return out;
-}
-
 __global__ __launch_bounds__(PT) void feed_plan_kernel(PlanArgs a) {
 #pragma clang fp contract(off)
     __shared__ double red[PT];
@@ -84,11 +56,11 @@ __global__ __launch_bounds__(PT) void feed_plan_kernel(PlanArgs a) {
             s = s + d * d;
         }
     }
-    s = plan_sum(s, red);
+    s = block_tree_sum<PT>(s, red);
     if (a.l.tallies && a.l.loss == ICNN_BE_LOSS_XENT) {
-        tp = plan_reduce(tp, ired, 0);
-        fp = plan_reduce(fp, ired, 0);
-        fn = plan_reduce(fn, ired, 0);
+        tp = block_tree_sum<PT>(tp, ired);
+        fp = block_tree_sum<PT>(fp, ired);
+        fn = block_tree_sum<PT>(fn, ired);
         if (tid == 0) {
             a.l.tallies[3 * u] = tp;
             a.l.tallies[3 * u + 1] = fp;
@@ -115,7 +87,7 @@ __global__ __launch_bounds__(PT) void feed_plan_kernel(PlanArgs a) {
         a.l.row_offset[b] = at;
         at += min(max(st.count[b], 0), st.slots);
     }
-    const int rows = plan_reduce(mine, ired, 0);
+    const int rows = block_tree_sum<PT>(mine, ired);
     // ---- fg evaluations (bundle_entropy.fg_evaluations), OR of the status words ----
     int all_done = 1, most = INT_MIN, bits = 0;
     for (int b = tid; b < B; b += PT) {
@@ -123,13 +95,13 @@ __global__ __launch_bounds__(PT) void feed_plan_kernel(PlanArgs a) {
         most = max(most, st.n_iters[b]);
         bits |= st.status[b];
     }
-    all_done = plan_reduce(all_done, ired, 2);
-    most = plan_reduce(most, ired, 1);
-    bits = plan_reduce(bits, ired, 3);
+    all_done = block_tree_reduce<PT>(all_done, ired, [](int a, int b) { return min(a, b); });
+    most = block_tree_reduce<PT>(most, ired, [](int a, int b) { return max(a, b); });
+    bits = block_tree_reduce<PT>(bits, ired, [](int a, int b) { return a | b; });
     // ---- the loss: per-sample parts in sample order within a thread, then the fixed tree ----
     double tot = 0.0;
     for (int b = tid; b < B; b += PT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot = plan_sum(tot, red);
+    tot = block_tree_sum<PT>(tot, red);
     if (tid == 0) {
         a.l.row_offset[B] = rows;
         a.l.counts[0] = rows;

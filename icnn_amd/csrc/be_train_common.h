@@ -1,6 +1,7 @@
-// Host runtime of the training units (be_train_common.hip, be_train_fc.hip, be_train_conv.hip): grid size, workspace walk
-// and the launch latch.  A gradient entry runs its whole step twice over the same code: a dry run (no workspace) that only
-// sizes the workspace, and the real run that carves it and launches.
+// Host runtime of the training units (be_train_common.hip, be_train_fc.hip, be_train_ficnn.hip, be_train_conv.hip): grid
+// size, workspace walk and the launch latch.  A gradient entry runs its whole step twice over the same code: a dry run (no
+// workspace) that only sizes the workspace, and the real run that carves it and launches.  And the one device accessor of
+// the packed forward operands that the units unpack their weights with.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,13 @@ namespace icnn_be {
 inline int grid_for(size_t total, int threads = 256) {
     const size_t b = (total + threads - 1) / threads;
     return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
+}
+
+// W[k][col] of a forward MFMA operand with N output columns, as pack_operand (be_picnn_fc_dev.h) and pack_frag
+// (be_picnn_conv.hip) lay it out: 16 x 16 fragments, k-block major, 64 lanes of four consecutive k each
+__device__ __forceinline__ float frag_at(const float *p, int N, int k, int col) {
+    const int NT = (N + 15) / 16, kb = k >> 4, kk = k & 15, lane = (kk >> 2) * 16 + (col & 15), nt = col >> 4;
+    return p[((size_t)(kb * NT + nt) * 64 + lane) * 4 + (kk & 3)];
 }
 
 // Workspace carving: the same walk sizes the buffer (dry run, base == nullptr) and launches (base != nullptr)
@@ -34,12 +42,15 @@ struct Runner {
     size_t part_need = 0;
     hipError_t err = hipSuccess;
     bool dry() const { return part == nullptr; }
+    // partials that a launcher called through call() asks for
+    void need(size_t floats) {
+        if (floats > part_need) part_need = floats;
+    }
     // C[M][N] (pitch ldc) = A B through launch_tr_gemm
     void gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, int M, int N, int K,
               float *C, long long ldc, const int *rows_dev = nullptr, int m_per_row = 0, bool dev_size = false) {
         // dev_size: size the partials for a device plan (the dry run of the device-count variant has no rows_dev yet)
-        const size_t need = tr_gemm_part_floats(M, N, K, dev_size || rows_dev != nullptr);
-        if (need > part_need) part_need = need;
+        need(tr_gemm_part_floats(M, N, K, dev_size || rows_dev != nullptr));
         if (err != hipSuccess || dry()) return;
         err = launch_tr_gemm(A, sam, sak, B, sbk, sbn, M, N, K, C, ldc, part, stream, rows_dev, m_per_row);
     }

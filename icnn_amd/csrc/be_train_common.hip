@@ -1,7 +1,8 @@
-// Kernels shared by the training gradients of both models (be_train_fc.hip, be_train_conv.hip): the ONE
-// f32-MFMA GEMM on strided operands that every product of a step runs through -- split-K with a fixed-order second pass, no
-// atomics, so a gradient is the same bits on every run and a whole entry can be captured in a graph -- and the per-row
-// bookkeeping of the feed.
+// Kernels shared by the training gradients of the models (be_train_fc.hip, be_train_ficnn.hip, be_train_conv.hip, DESIGN.md
+// §8-9): the ONE f32-MFMA GEMM on strided operands that every product of a step runs through -- split-K with a fixed-order
+// second pass, no atomics, so a gradient is the same bits on every run and a whole entry can be captured in a graph -- the
+// per-row bookkeeping of the feed, and the small helpers of a step: the stacked y-path weight out of its packed fragments,
+// zero fill and the bias column sums.
 #include <hip/hip_runtime.h>
 
 #include "be_train_common.h"
@@ -147,6 +148,38 @@ __global__ void tr_segment_sum_kernel(const float *rows, const int *row_offset, 
     }
 }
 
+// The y-path weights of a layer out of the packed fragments (both orientations are there; the forward one is read):
+// dst[(n + wprev)][w] = [ Wy ; Wz ] row-major; last: the width-1 head, whose two operands are plain vectors
+struct UnpackArgs {
+    const float *wpack;
+    long long yf, zf;
+    int n, wprev, w, last;
+    float *dst;
+};
+__global__ void tr_unpack_kernel(UnpackArgs a) {
+    const int rows = a.n + a.wprev, total = rows * a.w;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int k = i / a.w, col = i - k * a.w;
+        float v;
+        if (a.last) v = k < a.n ? a.wpack[a.yf + k] : a.wpack[a.zf + (k - a.n)];
+        else v = k < a.n ? frag_at(a.wpack + a.yf, a.w, k, col) : frag_at(a.wpack + a.zf, a.w, k - a.n, col);
+        a.dst[i] = v;
+    }
+}
+
+__global__ void tr_zero_kernel(float *p, size_t count) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
+}
+
+// out[col] = sum_j m[j][c0 + col], rows in order
+__global__ void tr_colsum_kernel(const float *m, int ld, int B, int c0, int N, float *out) {
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= N) return;
+    float s = 0.f;
+    for (int j = 0; j < B; ++j) s += m[(size_t)j * ld + c0 + col];
+    out[col] = s;
+}
+
 }  // namespace
 
 size_t tr_gemm_part_floats(int M, int N, int K, bool dev_plan) {
@@ -178,6 +211,20 @@ hipError_t launch_tr_rows(const int *row_offset, int B, int R, int *samp, float 
 hipError_t launch_tr_segment_sum(const float *rows, const int *row_offset, int B, int R, int C, float *out, hipStream_t stream) {
     return launch_kernel(tr_segment_sum_kernel, dim3(grid_for((size_t)B * C)), dim3(256), 0, stream, rows, row_offset, B, R, C,
                          out);
+}
+
+hipError_t launch_tr_unpack(const float *wpack, long long yf, long long zf, int n, int wprev, int w, bool last, float *dst,
+                            hipStream_t stream) {
+    UnpackArgs a{wpack, yf, zf, n, wprev, w, last ? 1 : 0, dst};
+    return launch_kernel(tr_unpack_kernel, dim3(grid_for((size_t)(n + wprev) * w)), dim3(256), 0, stream, a);
+}
+
+hipError_t launch_tr_zero(float *p, size_t count, hipStream_t stream) {
+    return launch_kernel(tr_zero_kernel, dim3(grid_for(count)), dim3(256), 0, stream, p, count);
+}
+
+hipError_t launch_tr_colsum(const float *m, int ld, int B, int c0, int N, float *out, hipStream_t stream) {
+    return launch_kernel(tr_colsum_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, m, ld, B, c0, N, out);
 }
 
 }  // namespace icnn_be

@@ -31,12 +31,6 @@ namespace {
 
 #define TC_LOOP(i, total) for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (total); i += (size_t)gridDim.x * blockDim.x)
 
-// W[kk][col] of a forward MFMA operand packed by pack_frag (be_picnn_conv.hip), N output columns
-__device__ __forceinline__ float frag_at(const float *p, int N, int kk, int col) {
-    const int NT = (N + 15) / 16, kb = kk >> 4, k4 = kk & 15, lane = (k4 >> 2) * 16 + (col & 15), nt = col >> 4;
-    return p[((size_t)(kb * NT + nt) * 64 + lane) * 4 + (k4 & 3)];
-}
-
 // stacked weight of conv z-layer l, [Kc][N] row-major, Kc = k*k*ch + 1, N = F + has_yr:
 //   (tap, c < cin, o < F) Wzu_l   (tap, cin, o < F) Wyu_l   (tap, cin + 1, F) Wyr_l   (bias row, F) byr_l   else 0
 struct WyArgs {
@@ -310,10 +304,6 @@ __global__ void tc_scatter_wy_kernel(ScatterArgs a) {
             a.byr[0] = d;
         }
     }
-}
-
-__global__ void tc_zero_kernel(float *p, size_t count) {
-    TC_LOOP(i, count) p[i] = 0.f;
 }
 
 // Weighted BatchNorm of a u-map [rows][N] (pitch ld; row = (sample, position), P positions per sample), BatchNorm over the R
@@ -710,8 +700,8 @@ hipError_t surrogate_run(const icnn_be_conv_model &m, const icnn_be_conv_ctx &cx
             run.launch(tc_route0_kernel, dim3(grid_for((size_t)R * n)), 256, ra, (const float *)dX, g.c_yu[0], drows);
         }
     }
-    run.launch(tc_zero_kernel, dim3(1), 64, grad + gl.yrW[2], (size_t)(g.K[2] * g.K[2] + 1));    // z2_y_red: never reaches E
-    run.launch(tc_zero_kernel, dim3(1), 256, grad + gl.u4W, (size_t)fch + 1);                     // u4: never read
+    run.call([&] { return launch_tr_zero(grad + gl.yrW[2], (size_t)(g.K[2] * g.K[2] + 1), stream); });   // z2_y_red: never reaches E
+    run.call([&] { return launch_tr_zero(grad + gl.u4W, (size_t)fch + 1, stream); });                    // u4: never read
 
     // 5. per-sample context gradient
     run.call([&] { return launch_tr_segment_sum(drows, row_offset, B, R, C, dctx, stream); });

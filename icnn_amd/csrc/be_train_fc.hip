@@ -21,35 +21,12 @@
 
 #include <climits>
 
-#include "be_picnn_fc_dev.h"   // the packed y-path layout (pack_offsets, kblocks, pad16)
+#include "be_picnn_fc_dev.h"   // the packed y-path layout (pack_offsets)
 #include "be_train_common.h"
 
 namespace icnn_be {
 
 namespace {
-
-// The y-path weights of every layer out of the packed fragments (both orientations are there; the forward one is read):
-// Wst_i[(n + w_{i-1})][w_i] = [ Wyu_i ; Wzu_i ] row-major
-struct UnpackArgs {
-    const float *wpack;
-    long long yu_f, zu_f;
-    int n, wprev, w, last;
-    float *dst;
-};
-__device__ __forceinline__ float packed_at(const float *p, int N, int k, int col) {
-    const int NT = pad16(N) / 16, kb = k >> 4, kk = k & 15, lane = (kk >> 2) * 16 + (col & 15), nt = col >> 4;
-    return p[((size_t)(kb * NT + nt) * 64 + lane) * 4 + (kk & 3)];
-}
-__global__ void tr_unpack_kernel(UnpackArgs a) {
-    const int rows = a.n + a.wprev, total = rows * a.w;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int k = i / a.w, col = i - k * a.w;
-        float v;
-        if (a.last) v = k < a.n ? a.wpack[a.yu_f + k] : a.wpack[a.zu_f + (k - a.n)];
-        else v = k < a.n ? packed_at(a.wpack + a.yu_f, a.w, k, col) : packed_at(a.wpack + a.zu_f, a.w, k - a.n, col);
-        a.dst[i] = v;
-    }
-}
 
 // network input of row r, column j: y rounded to float32 like a TensorFlow feed, 2y-1 for the RL wrapper; its tangent
 // direction v (times 2 for the wrapper, RL/src/icnn.py:148-158) -- as icnn_be_fc_fg reads y
@@ -267,15 +244,6 @@ __global__ void tr_dpre_heads_kernel(const float *dctx, const float *ctx, int B,
     }
 }
 
-// out[col] = sum_j dpre[j][c0 + col], rows in order
-__global__ void tr_colsum_kernel(const float *dpre, int ld, int B, int c0, int N, float *out) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= N) return;
-    float s = 0.f;
-    for (int j = 0; j < B; ++j) s += dpre[(size_t)j * ld + c0 + col];
-    out[col] = s;
-}
-
 struct TrainShape {
     int L, n, nf, C, B, R, R2, bn;
     int w[ICNN_BE_MAX_LAYERS];
@@ -411,10 +379,10 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
 
     // 1. rows and multiplicities, y-path weights
     run.call([&] { return launch_tr_rows(row_offset, B, R, samp, mult, stream); });
-    for (int i = 0; i <= L; ++i) {
-        UnpackArgs ua{m.wpack, po.yu_f[i], po.zu_f[i], n, i > 0 ? s.w[i - 1] : 0, s.w[i], i == L ? 1 : 0, wst[i]};
-        run.launch(tr_unpack_kernel, grid_for((size_t)s.pq_ld(i) * s.w[i]), 256, ua);
-    }
+    for (int i = 0; i <= L; ++i)        // Wst_i [(n + w_{i-1})][w_i] = [ Wyu_i ; Wzu_i ]
+        run.call([&] {
+            return launch_tr_unpack(m.wpack, po.yu_f[i], po.zu_f[i], n, i > 0 ? s.w[i - 1] : 0, s.w[i], i == L, wst[i], stream);
+        });
     // 2. x-only forward on the B samples (context producer's stage GEMMs), weighted BatchNorm
     for (int i = 0; i <= L; ++i) {
         run.call([&] { return launch_fc_context_stage(cx, i, x, B, ctxb, C, uwork, stream); });
@@ -470,8 +438,7 @@ hipError_t surrogate_run(const icnn_be_fc_model &m, const icnn_be_fc_ctx &cx, co
         if (i > 0) { segs[ns++] = Seg{c0, wp, gl.zuuW[i], gl.zuub[i]}; c0 += wp; }
         for (int q = 0; q < ns; ++q) {
             run.gemm(prev, 1, prev_ld, dpre[i] + segs[q].c0, ld, 1, K, segs[q].cols, B, grad + segs[q].wo, segs[q].cols);
-            run.launch(tr_colsum_kernel, (segs[q].cols + 255) / 256, 256, (const float *)dpre[i], ld, B, segs[q].c0, segs[q].cols,
-                       grad + segs[q].bo);
+            run.call([&] { return launch_tr_colsum(dpre[i], ld, B, segs[q].c0, segs[q].cols, grad + segs[q].bo, stream); });
         }
         if (i > 0)          // du_{i-1} = dpre_i W_stage_i^T  [B][w_{i-1}]
             run.gemm(dpre[i], ld, 1, cx.w_stage[i], 1, ld, B, K, ctx_stage_cols(cx, i), du, K);

@@ -1,7 +1,7 @@
 // Training gradient of the FICNN (synthetic-cls/icnn.py:133-139): the parameter gradient of
 //   F = sum_r c_r E(x_s(r), y_r) + <dE/dy(x_s(r), y_r), v_r>
 // over every variable, in the structure of be_train_fc.hip:
-//   1. the context c_i = x Wx_i + b_i on the B unique samples (one GEMM, bias row)
+//   1. the context c_i = x Wx_i + b_i on the B unique samples (launch_ficnn_context, be_ficnn.hip)
 //   2. rows forward, layer by layer: primal and tangent rows stacked into one operand P_i = [ y | z_{i-1} ; v | zdot_{i-1} ]
 //      ([2R][n + width_{i-1}]), one GEMM with [Wy_i ; Wz_i] gives both pre-activations; z = relu(a), zdot = relu'(a) pre_dot
 //   3. rows reverse: the two adjoint columns (abar seeded with c_r, adot with 1, through the head) run through the same
@@ -19,37 +19,6 @@
 namespace icnn_be {
 
 namespace {
-
-// [Wy_i ; Wz_i] row-major [(n + wprev)][w] out of the packed forward fragments (or the head's plain vectors)
-struct FUnpackArgs {
-    const float *wpack;
-    long long yf, zf;
-    int n, wprev, w, last;
-    float *dst;
-};
-__device__ __forceinline__ float f_packed_at(const float *p, int N, int k, int col) {
-    const int NT = pad16(N) / 16, kb = k >> 4, kk = k & 15, lane = (kk >> 2) * 16 + (col & 15), nt = col >> 4;
-    return p[((size_t)(kb * NT + nt) * 64 + lane) * 4 + (kk & 3)];
-}
-__global__ void fi_unpack_kernel(FUnpackArgs a) {
-    const int total = (a.n + a.wprev) * a.w;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int k = i / a.w, col = i - k * a.w;
-        float v;
-        if (a.last) v = k < a.n ? a.wpack[a.yf + k] : a.wpack[a.zf + (k - a.n)];
-        else v = k < a.n ? f_packed_at(a.wpack + a.yf, a.w, k, col) : f_packed_at(a.wpack + a.zf, a.w, k - a.n, col);
-        a.dst[i] = v;
-    }
-}
-
-__global__ void fi_zero_kernel(float *p, size_t count) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
-}
-
-__global__ void fi_bias_kernel(float *ctx, const float *b, int C, size_t total) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-        ctx[i] = ctx[i] + b[i % C];
-}
 
 struct FRowArgs {
     const double *y, *v, *c;
@@ -129,15 +98,6 @@ __global__ void fi_back_mask_kernel(const float *BD, const float *Dp, int R, int
         const int r = row < R ? row : row - R;
         adj_prev[i] = Dp[(size_t)r * wp + k] * BD[i];
     }
-}
-
-// out[col] = sum_j m[j][col], rows in order
-__global__ void fi_colsum_kernel(const float *m, int B, int N, float *out) {
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= N) return;
-    float s = 0.f;
-    for (int j = 0; j < B; ++j) s += m[(size_t)j * N + col];
-    out[col] = s;
 }
 
 struct FShape {
@@ -220,16 +180,16 @@ hipError_t f_surrogate_run(const icnn_be_ficnn_model &m, const FShape &s, const 
     FRowArgs ra{y, v, cvec, samp, ctxb, R, n, C};
 
     // 0. variables that do not reach E (head SUM)
-    if (!linear) run.launch(fi_zero_kernel, grid_for(gl.total - gl.xW[L]), 256, grad + gl.xW[L], gl.total - gl.xW[L]);
+    if (!linear) run.call([&] { return launch_tr_zero(grad + gl.xW[L], gl.total - gl.xW[L], stream); });
     // 1. rows, weights, context of the B samples
     run.call([&] { return launch_tr_rows(row_offset, B, R, samp, mult, stream); });
-    for (int i = 0; i < E; ++i) {
-        FUnpackArgs ua{m.wpack, i < L ? po.yf[i] : po.yL, i < L ? po.zf[i] : po.zL, n, i > 0 ? s.w[i - 1] : 0, s.w[i],
-                       i == L ? 1 : 0, wst[i]};
-        run.launch(fi_unpack_kernel, grid_for((size_t)s.pq_ld(i) * s.w[i]), 256, ua);
-    }
-    run.gemm(x, nf, 1, m.wpack + po.wx, C, 1, B, C, nf, ctxb, C);
-    run.launch(fi_bias_kernel, grid_for((size_t)B * C), 256, ctxb, (const float *)(m.wpack + po.bx), C, (size_t)B * C);
+    for (int i = 0; i < E; ++i)         // wst_i [(n + w_{i-1})][w_i] = [ Wy_i ; Wz_i ]
+        run.call([&] {
+            return launch_tr_unpack(m.wpack, i < L ? po.yf[i] : po.yL, i < L ? po.zf[i] : po.zL, n, i > 0 ? s.w[i - 1] : 0, s.w[i],
+                                    i == L, wst[i], stream);
+        });
+    run.need(ficnn_context_work_floats(m, B));
+    run.call([&] { return launch_ficnn_context(m, x, B, ctxb, run.part, stream); });
     // 2. rows forward
     for (int i = 0; i < E; ++i) {
         const int ld = s.pq_ld(i), w = s.w[i];
@@ -259,7 +219,7 @@ hipError_t f_surrogate_run(const icnn_be_ficnn_model &m, const FShape &s, const 
         }
         run.call([&] { return launch_tr_segment_sum(adj[i], row_offset, B, R, w, dctx, stream); });  // primal rows only
         run.gemm(x, 1, nf, dctx, w, 1, nf, w, B, grad + gl.xW[i], w);                                // x^T dctx
-        run.launch(fi_colsum_kernel, (w + 255) / 256, 256, (const float *)dctx, B, w, grad + gl.xb[i]);
+        run.call([&] { return launch_tr_colsum(dctx, w, B, 0, w, grad + gl.xb[i], stream); });
     }
     if (work_floats) *work_floats = fixed + run.part_need;
     return run.err;

@@ -28,30 +28,6 @@ struct GdFeedArgs {
     int *ticket;
 };
 
-// the same tree for every call; valid in every thread
-__device__ __forceinline__ double feed_sum(double v, double *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = GT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
-__device__ __forceinline__ int feed_count(int v, int *red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = GT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const int out = red[0];
-    __syncthreads();
-    return out;
-}
-
 __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
 #pragma clang fp contract(off)
     __shared__ double red[GT];
@@ -67,7 +43,7 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
         const float d = (float)y_row[i] - t_row[i];
         s = s + (double)d * (double)d;
     }
-    s = feed_sum(s, red);
+    s = block_tree_sum<GT>(s, red);
     if (l.tallies) {
         int tp = 0, fp = 0, fn = 0;
         for (int i = tid; i < n; i += GT) {
@@ -76,9 +52,9 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
             fp += pred && !truth;
             fn += !pred && truth;
         }
-        tp = feed_count(tp, ired);
-        fp = feed_count(fp, ired);
-        fn = feed_count(fn, ired);
+        tp = block_tree_sum<GT>(tp, ired);
+        fp = block_tree_sum<GT>(fp, ired);
+        fn = block_tree_sum<GT>(fn, ired);
         if (tid == 0) {
             l.tallies[3 * j] = tp;
             l.tallies[3 * j + 1] = fp;
@@ -111,7 +87,7 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
     // ---- the last workgroup: the loss, per-sample parts in sample order within a thread, then the fixed tree ----
     double tot = 0.0;
     for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot = feed_sum(tot, red);
+    tot = block_tree_sum<GT>(tot, red);
     if (tid == 0) {
         *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
         __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(GT) void gd_feed_px_kernel(GdFeedPxArgs a) {
         const float u = l.px * ((float)y_row[i] - t_row[i]);
         s = s + (double)u * (double)u;
     }
-    s = feed_sum(s, red);
+    s = block_tree_sum<GT>(s, red);
     if (tid == 0) {
         __hip_atomic_store(a.partial + j, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int ticket = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(GT) void gd_feed_px_kernel(GdFeedPxArgs a) {
     // ---- the last of them: the loss, as gd_feed_kernel forms it ----
     double tot = 0.0;
     for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot = feed_sum(tot, red);
+    tot = block_tree_sum<GT>(tot, red);
     if (tid == 0) {
         *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
         __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch

@@ -16,6 +16,12 @@
 // workgroup that reads *go == 0 leaves before it loads, stores or takes a ticket, so theta, m, v, the arena and both step
 // words stay as they were.  gated_copy_kernel is the gate's other consumer: dst = src when (*go != 0) == (want != 0), which
 // puts the BatchNorm moving statistics of a skipped step back from their shadow.
+//
+// The RL critic's form (icnn_be_rl_critic_update; DESIGN.md §13, RL/src/icnn.py:56-112) is a third instantiation of that
+// body.  Per element, ahead of the step above and from the pre-update theta (tests/test_rl_train.py restates it):
+//   target = target - tau * (target - theta)                 update_target
+//   g = g + k * theta on the decayed elements                k = l2norm * wd in float32 (TF's AddN of the two gradients)
+// and every new target value is scattered into the target's arena beside the critic's.
 #include "be_kernels.h"
 
 namespace icnn_be {
@@ -26,9 +32,9 @@ constexpr int UPD_THREADS = 256;
 constexpr int UPD_PER_THREAD = 4;
 
 struct UpdArgs {
-    icnn_be_param_update_args a;
-    float b1, c1, b2, c2;
-    const int *go;       // the gated form's word; not read by the plain one
+    icnn_be_rl_update_args r;   // r.adam: every form; the rest and k: the critic's alone
+    float b1, c1, b2, c2, k;
+    const int *go;              // the gated form's word; not read by the others
 };
 
 __device__ __forceinline__ bool in_proj(const icnn_be_param_update_args &a, long long j) {
@@ -37,10 +43,10 @@ __device__ __forceinline__ bool in_proj(const icnn_be_param_update_args &a, long
     return p;
 }
 
-template <bool GATED>
+template <bool GATED, bool CRITIC>
 __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
 #pragma clang fp contract(off)
-    const icnn_be_param_update_args &a = u.a;
+    const icnn_be_param_update_args &a = u.r.adam;
     __shared__ float s_lr_t;
     __shared__ int s_t;
     if (GATED) {
@@ -59,14 +65,20 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
         s_lr_t = (float)(a.lr * sqrt(1.0 - pow(a.beta2, (double)t)) / (1.0 - pow(a.beta1, (double)t)));
     }
     __syncthreads();
-    const float lr_t = s_lr_t, eps = a.eps;
+    const float lr_t = s_lr_t, eps = a.eps, tau = u.r.tau;
     const long long j0 = ((long long)blockIdx.x * UPD_THREADS + threadIdx.x) * UPD_PER_THREAD;
     if (j0 < a.n) {
         const int cnt = a.n - j0 < UPD_PER_THREAD ? (int)(a.n - j0) : UPD_PER_THREAD;
         float th[UPD_PER_THREAD] = {}, m[UPD_PER_THREAD] = {}, v[UPD_PER_THREAD] = {}, g[UPD_PER_THREAD] = {};
+        float tt[UPD_PER_THREAD] = {};      // the critic's target theta and decay mask; dead in the other forms
+        bool dk[UPD_PER_THREAD] = {};
         int off[UPD_PER_THREAD + 1] = {};
         if (cnt == UPD_PER_THREAD) {
             const float4 t4 = *reinterpret_cast<const float4 *>(a.theta + j0);
+            if (CRITIC) {
+                const float4 r4 = *reinterpret_cast<const float4 *>(u.r.target_theta + j0);
+                tt[0] = r4.x; tt[1] = r4.y; tt[2] = r4.z; tt[3] = r4.w;
+            }
             const float4 m4 = *reinterpret_cast<const float4 *>(a.m + j0);
             const float4 v4 = *reinterpret_cast<const float4 *>(a.v + j0);
             const float4 g4 = *reinterpret_cast<const float4 *>(a.grad + j0);
@@ -76,10 +88,17 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
             v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
             g[0] = g4.x; g[1] = g4.y; g[2] = g4.z; g[3] = g4.w;
             off[0] = o4.x; off[1] = o4.y; off[2] = o4.z; off[3] = o4.w;
+            if (CRITIC) {
+                const uchar4 d4 = *reinterpret_cast<const uchar4 *>(u.r.decay + j0);
+                dk[0] = d4.x; dk[1] = d4.y; dk[2] = d4.z; dk[3] = d4.w;
+            }
         } else {
             for (int k = 0; k < cnt; ++k) {
-                th[k] = a.theta[j0 + k]; m[k] = a.m[j0 + k]; v[k] = a.v[j0 + k]; g[k] = a.grad[j0 + k];
+                th[k] = a.theta[j0 + k];
+                if (CRITIC) tt[k] = u.r.target_theta[j0 + k];
+                m[k] = a.m[j0 + k]; v[k] = a.v[j0 + k]; g[k] = a.grad[j0 + k];
                 off[k] = a.dest_off[j0 + k];
+                if (CRITIC) dk[k] = u.r.decay[j0 + k];
             }
         }
         off[cnt] = a.dest_off[j0 + cnt];
@@ -88,23 +107,34 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
             // plain operators under the pragma above: the __f*_rn helpers are header functions outside its scope, and
             // the compiler fused their products into the sums.  sqrt: the float of the double root (correctly rounded
             // both times, and 53 >= 2 * 24 + 2 bits make the double rounding innocuous); v_sqrt_f32 alone is 1 ulp
-            m[k] = u.b1 * m[k] + u.c1 * g[k];
-            v[k] = u.b2 * v[k] + u.c2 * (g[k] * g[k]);
+            const float old = th[k];
+            if (CRITIC) tt[k] = tt[k] - tau * (tt[k] - old);                  // update_target, from the pre-update theta
+            const float gk = CRITIC && dk[k] ? g[k] + u.k * old : g[k];      // + d (l2norm wd |W|^2 / 2) / dW  (TF's AddN)
+            m[k] = u.b1 * m[k] + u.c1 * gk;
+            v[k] = u.b2 * v[k] + u.c2 * (gk * gk);
             const float root = (float)__builtin_sqrt((double)v[k]);
             th[k] = th[k] - (lr_t * m[k]) / (root + eps);
             if (th[k] < 0.f && in_proj(a, j0 + k)) th[k] = 0.f;
         }
         if (cnt == UPD_PER_THREAD) {
             *reinterpret_cast<float4 *>(a.theta + j0) = make_float4(th[0], th[1], th[2], th[3]);
+            if (CRITIC) *reinterpret_cast<float4 *>(u.r.target_theta + j0) = make_float4(tt[0], tt[1], tt[2], tt[3]);
             *reinterpret_cast<float4 *>(a.m + j0) = make_float4(m[0], m[1], m[2], m[3]);
             *reinterpret_cast<float4 *>(a.v + j0) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
-            for (int k = 0; k < cnt; ++k) { a.theta[j0 + k] = th[k]; a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k]; }
+            for (int k = 0; k < cnt; ++k) {
+                a.theta[j0 + k] = th[k];
+                if (CRITIC) u.r.target_theta[j0 + k] = tt[k];
+                a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k];
+            }
         }
         for (int k = 0; k < cnt; ++k)
             for (int d = off[k]; d < off[k + 1]; ++d) {
                 const int at = a.dest[d];
-                if (at >= 0 && at < a.arena_floats) a.arena[at] = th[k];
+                if (at >= 0 && at < a.arena_floats) {
+                    a.arena[at] = th[k];
+                    if (CRITIC) u.r.target_arena[at] = tt[k];
+                }
             }
     }
     // the step count: the last workgroup to arrive stores t and re-arms the ticket for the next launch
@@ -138,18 +168,34 @@ long long param_update_blocks(long long n) {
     return (n + per_block - 1) / per_block;
 }
 
-// go NULL: the plain update
-hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream) {
-    UpdArgs u{};
-    u.a = a;
+namespace {
+
+template <bool GATED, bool CRITIC>
+hipError_t launch_update(UpdArgs u, hipStream_t stream) {
+    const icnn_be_param_update_args &a = u.r.adam;
     u.b1 = (float)a.beta1;
     u.c1 = (float)(1.0 - a.beta1);
     u.b2 = (float)a.beta2;
     u.c2 = (float)(1.0 - a.beta2);
+    return launch_kernel(param_update_kernel<GATED, CRITIC>, dim3((unsigned)param_update_blocks(a.n)), dim3(UPD_THREADS), 0,
+                         stream, u);
+}
+
+}  // namespace
+
+// go NULL: the plain update
+hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream) {
+    UpdArgs u{};
+    u.r.adam = a;
     u.go = go;
-    const dim3 grid((unsigned)param_update_blocks(a.n)), block(UPD_THREADS);
-    return go ? launch_kernel(param_update_kernel<true>, grid, block, 0, stream, u)
-              : launch_kernel(param_update_kernel<false>, grid, block, 0, stream, u);
+    return go ? launch_update<true, false>(u, stream) : launch_update<false, false>(u, stream);
+}
+
+hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream) {
+    UpdArgs u{};
+    u.r = r;
+    u.k = r.l2norm * r.wd;                                          // float32 product of the two float32 constants
+    return launch_update<false, true>(u, stream);
 }
 
 hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream) {

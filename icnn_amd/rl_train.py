@@ -9,7 +9,7 @@ One step, enqueued on the current stream without a host synchronisation (a captu
     4. the critic's context of obs (batch statistics, folded once into the critic's moving statistics) and negQ at act
     5. icnn_be_rl_td: TD target, c_j, the loss (be_rl_train.hip)
     6. the critic's gradient of sum_j c_j negQ_j (train.surrogate_grad, one row per sample)
-    7. icnn_be_rl_critic_update: soft target update, L2 decay, TF-Adam, proj, both arenas (be_rl_train.hip)
+    7. icnn_be_rl_critic_update: soft target update, L2 decay, TF-Adam, proj, both arenas (be_train_update.hip)
 """
 import ctypes as C
 from typing import Dict

@@ -1,7 +1,7 @@
-"""The RL agent's critic training step on the device (rl_train.CriticTrainer, icnn_be_rl_td, icnn_be_rl_critic_update,
-be_rl_train.hip) against the host restatement of Agent.train() in tests/rl_train_ref.py: the ABI and its argument checks,
-the closed-form gradient of the loss (CPU), each kernel against NumPy, whole steps against the oracle, BatchNorm folds and
-graph capture (GPU)."""
+"""The RL agent's critic training step on the device (rl_train.CriticTrainer; icnn_be_rl_td, be_rl_train.hip;
+icnn_be_rl_critic_update, the critic instantiation of be_train_update.hip's kernel) against the host restatement of
+Agent.train() in tests/rl_train_ref.py: the ABI and its argument checks, the closed-form gradient of the loss (CPU), each
+kernel against NumPy, whole steps against the oracle, BatchNorm folds and graph capture (GPU)."""
 import ctypes as C
 import dataclasses
 import os
@@ -449,3 +449,75 @@ def test_captured_step_replays_equal_eager_steps():
     assert cap.t == 3
     for a, b in zip(cap_losses, losses):
         assert torch.equal(a, b)
+
+
+def _raw_update_case(n, t):
+    """theta, target, m, v, grad, a destination map in which parameter i has (i + 1) % 3 destinations scattered over an
+    arena with spare cells, and proj ranges that straddle the quad boundary at 4 and the workgroup boundary at 1024"""
+    rng = np.random.RandomState(1000 * n + t)
+    theta = (1e-2 * rng.randn(n)).astype(np.float32)
+    target = (theta + 1e-2 * rng.randn(n)).astype(np.float32)
+    m = (1e-3 * rng.randn(n)).astype(np.float32)
+    v = (1e-6 * rng.rand(n)).astype(np.float32)
+    g = (1e-2 * rng.randn(n)).astype(np.float32)
+    dest_off = np.concatenate([[0], np.cumsum((np.arange(n) + 1) % 3)]).astype(np.int32)
+    arena_floats = int(dest_off[-1]) + 5
+    dest = rng.permutation(arena_floats).astype(np.int32)           # the first dest_off[-1] are read
+    proj = [(2, min(n, 7))] if n > 2 else [(0, n)]
+    if n > 1024:
+        proj.append((1022, n))
+    return theta, target, m, v, g, dest_off, dest, arena_floats, proj
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("t", [1, 7])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1027])
+def test_critic_update_without_decay_is_the_plain_update(n, t):
+    """icnn_be_rl_critic_update with a decay mask of zeros (and a large l2norm wd that the mask must keep out) leaves
+    theta, m, v, the arena and the step word as icnn_be_param_update does from the same state, bit for bit, and the
+    target as tt - tau (tt - theta_old) in float32: one quad, a tail alone, a quad and a tail, and two workgroups."""
+    lib = _lib.load()
+    theta, target, m, v, g, dest_off, dest, arena_floats, proj = _raw_update_case(n, t)
+    assert -(-n // 1024) == (2 if n == 1027 else 1)                 # workgroups of 256 threads x 4 parameters
+    counts = np.diff(dest_off)
+    assert set(counts.tolist()) == ({0, 1, 2} if n >= 3 else {1})
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()       # noqa: E731
+    fill = np.full(arena_floats, -7.0, np.float32)
+    grad, d_off, d_dest = dev(g), dev(dest_off), dev(dest)
+    decay = torch.zeros(n + 3, dtype=torch.uint8, device="cuda")
+    runs = []
+    for critic in (False, True):
+        s = dict(theta=dev(theta), m=dev(m), v=dev(v), arena=dev(fill), tt=dev(target), ta=dev(fill),
+                 step=torch.tensor([t - 1, 0], dtype=torch.int32, device="cuda"))
+        r = _lib.RlUpdateArgs()
+        a = r.adam
+        a.n, a.theta, a.m, a.v, a.grad = n, s["theta"].data_ptr(), s["m"].data_ptr(), s["v"].data_ptr(), grad.data_ptr()
+        a.dest_off, a.dest, a.arena, a.arena_floats = d_off.data_ptr(), d_dest.data_ptr(), s["arena"].data_ptr(), arena_floats
+        a.step, a.lr, a.beta1, a.beta2, a.eps, a.n_proj = s["step"].data_ptr(), 1e-2, 0.9, 0.999, 1e-8, len(proj)
+        for i, (b, e) in enumerate(proj):
+            a.proj_begin[i], a.proj_end[i] = b, e
+        r.target_theta, r.target_arena, r.decay = s["tt"].data_ptr(), s["ta"].data_ptr(), decay.data_ptr()
+        r.tau, r.l2norm, r.wd = TAU, 1.0, 10.0
+        rc = lib.icnn_be_rl_critic_update(C.byref(r), None) if critic else lib.icnn_be_param_update(C.byref(a), None)
+        assert rc == 0
+        torch.cuda.synchronize()
+        runs.append({k: x.cpu().numpy() for k, x in s.items()})
+    plain, crit = runs
+    for k in ("theta", "m", "v", "arena"):
+        assert np.array_equal(_bits(crit[k]), _bits(plain[k])), k
+    assert crit["step"].tolist() == plain["step"].tolist() == [t, 0]
+    assert np.array_equal(_bits(plain["tt"]), _bits(target)) and np.array_equal(_bits(plain["ta"]), _bits(fill))
+    tt_new = target - np.float32(TAU) * (target - theta)
+    assert tt_new.dtype == np.float32 and np.array_equal(_bits(crit["tt"]), _bits(tt_new))
+    owner = np.repeat(np.arange(n), counts)
+    want_arena, want_ta = fill.copy(), fill.copy()
+    want_arena[dest[:owner.size]] = plain["theta"][owner]
+    want_ta[dest[:owner.size]] = tt_new[owner]
+    assert np.array_equal(_bits(plain["arena"]), _bits(want_arena)) and np.array_equal(_bits(crit["ta"]), _bits(want_ta))
+    # the update did something, and at the largest size the clamp acted inside a proj range and nowhere else
+    assert not np.array_equal(_bits(plain["theta"]), _bits(theta))
+    if n == 1027:
+        inside = np.zeros(n, bool)
+        for b, e in proj:
+            inside[b:e] = True
+        assert np.any(plain["theta"][inside] == 0) and np.all(plain["theta"][inside] >= 0) and np.any(plain["theta"][~inside] < 0)
