@@ -1,13 +1,16 @@
 """A short bundle-entropy training loop on seeded synthetic multi-label data, every iteration one replay of a captured
 train.BundleTrainer.step (the loop of multi-label-cls/icnn_ebundle.py:208-250 without a host wait inside the step).
 
-    python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10] [--test-every 20]
+    python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10] [--test-every 20] [--save DIR] [--resume FILE]
 
 The labels are a noisy linear function of the features; the loss falls from the first steps on (685 to 639 over the
 default 60 steps on an MI355X).
 The host reads the loss and the F1 tallies only every `--every` steps, after a synchronisation of its own choosing.
 Every `--test-every` steps (0: never) the test phase of the script (:257-277) runs on a held-out split of the same
 distribution: one replay of a captured train.BundleTrainer.evaluate, then the test loss and macro-F1.
+--save DIR keeps the model with the best test F1 (icnn_ebundle.py:274-277, `if testF1 > bestTestF1: save`) through a
+train.BestKeeper INSIDE the captured test graph -- the comparison and the snapshot happen on the device -- and writes
+DIR/best.npz and the checkpoint DIR/last.npz at the end; --resume FILE continues from such a checkpoint.
 """
 import argparse
 import os
@@ -17,7 +20,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from icnn_amd import picnn, train  # noqa: E402
+from icnn_amd import checkpoint, picnn, train  # noqa: E402
 
 
 def main():
@@ -26,7 +29,11 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--every", type=int, default=10)
     ap.add_argument("--test-every", type=int, default=20)
+    ap.add_argument("--save", default=None, metavar="DIR")
+    ap.add_argument("--resume", default=None, metavar="FILE")
     a = ap.parse_args()
+    if a.save and not a.test_every:
+        ap.error("--save keeps the best model by test F1: it needs --test-every > 0")
     torch.cuda.set_device(0)
     rng = np.random.RandomState(0)
     n_features, n_labels, n_train, n_test = 40, 16, 1024, 256
@@ -39,6 +46,8 @@ def main():
     Yt = ((Xt - 0.5) @ W + 0.3 * held_out.randn(n_test, n_labels) > 0.8).astype(np.float64)
     model = picnn.FCModel(spec, picnn.init_params(spec, 0, "spread"), "cuda")
     trainer = train.BundleTrainer(model, a.batch, n_iter=10, loss="xent", lr=1e-3, eval_batch=n_test if a.test_every else None)
+    # the keeper moves the BatchNorm statistics into one buffer: built before anything is captured
+    keeper = train.BestKeeper(trainer, mode="max", start=0.0) if a.save else None
     Xd, Yd = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
 
     def batch():
@@ -65,6 +74,11 @@ def main():
         test_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(test_graph):
             trainer.evaluate(None, None)
+            if keeper is not None:
+                keeper.offer_macro_f1(trainer.eval_f1_tallies)
+    if a.resume:                                           # into the existing tensors: the graphs above replay on the loaded state
+        checkpoint.load(a.resume, trainer, keeper=keeper)
+        print("resumed %s at step %d" % (a.resume, trainer.t_steps))
     for i in range(1, a.steps + 1):
         batch()
         graph.replay()
@@ -79,6 +93,12 @@ def main():
             torch.cuda.synchronize()
             print("           test loss %10.4f  test macro F1 %.3f  (%d held-out examples)"
                   % (float(trainer.eval_loss.item()), trainer.eval_macro_f1(), n_test))
+    if a.save:
+        os.makedirs(a.save, exist_ok=True)
+        checkpoint.save_best(os.path.join(a.save, "best.npz"), keeper)
+        checkpoint.save(os.path.join(a.save, "last.npz"), trainer, keeper=keeper)
+        print("kept %d of %d test phases, best test macro F1 %.3f: %s" % (keeper.kept, keeper.offers, keeper.best_value(),
+                                                                          os.path.join(a.save, "best.npz")))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,11 @@ returns logged.  The environment is NumPy: a damped point mass in dimA dimension
 wants at the origin; the observation is (position, velocity), truncated or zero-padded to dimO.
 
     python examples/rl_agent.py [--total 2000] [--train 200] [--test 2] [--tmax 50] [--warmup 100] [--bsize 64] [--iter 1]
-                                [--dimO 4] [--dimA 2] [--capture]
+                                [--dimO 4] [--dimA 2] [--capture] [--save FILE] [--resume FILE]
+
+--resume FILE restores the agent from a checkpoint before the loop (RL/src/icnn.py:134-137 restores the latest one at
+construction) and --save FILE writes one after it (RL/src/main.py:113-115): weights, optimiser state, noise, the random
+state and the replay memory, so that the agent continues as if it had not stopped.
 """
 import argparse
 import dataclasses
@@ -82,6 +86,8 @@ def main():
     ap.add_argument("--l2size", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--capture", action="store_true")
+    ap.add_argument("--save", default=None, metavar="FILE")
+    ap.add_argument("--resume", default=None, metavar="FILE")
     args = ap.parse_args()
     spec = dataclasses.replace(picnn.halfcheetah_spec(), n_features=args.dimO, n_labels=args.dimA,
                                szs=(args.l1size, args.l2size), action_box=False)
@@ -90,6 +96,10 @@ def main():
     agent = rl_agent.Agent(critic, target, bsize=args.bsize, warmup=args.warmup, iters=args.iter, rmsize=args.rmsize,
                            seed=args.seed, capture=args.capture)
     env = PointMass(args.dimO, args.dimA, seed=args.seed)
+    if args.resume:
+        from icnn_amd import checkpoint
+        checkpoint.load(args.resume, agent)
+        print("resumed {} at {} training observations".format(args.resume, agent.t))
     train_timestep = 0
     while train_timestep < args.total:
         rewards = [run_episode(env, agent, True, args.tmax)[0] for _ in range(args.test)]
@@ -109,6 +119,10 @@ def main():
         print("Average train return {} after {} timestep of training.".format(np.mean(rewards), train_timestep))
     agent.memory.raise_on_error()
     torch.cuda.synchronize()
+    if args.save:
+        from icnn_amd import checkpoint
+        checkpoint.save(args.save, agent)
+        print("saved {}".format(args.save))
 
 
 if __name__ == "__main__":

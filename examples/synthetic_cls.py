@@ -2,7 +2,10 @@
 circles or linearly separable points generated with NumPy, 30 steps of momentum GD as inference, full-batch TF-Adam with proj.
 
     python examples/synthetic_cls.py [--model ficnn|picnn] [--dataset moons|circles|linear] [--epochs 100]
-                                     [--head sum|linear] [--n 100]
+                                     [--head sum|linear] [--n 100] [--save DIR]
+
+--save DIR keeps the model with the best train loss (icnn.py:206-209) through a train.BestKeeper on the device and writes
+DIR/best.npz and the checkpoint DIR/last.npz at the end.  Unlike the script's `bestMSE is None or ...` a NaN loss is never kept.
 """
 import argparse
 import os
@@ -13,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from icnn_amd import ficnn, picnn, train  # noqa: E402
+from icnn_amd import checkpoint, ficnn, picnn, train  # noqa: E402
 
 
 def make_data(name, n, seed):
@@ -56,13 +59,23 @@ def main():
     ap.add_argument("--head", default="sum", choices=["sum", "linear"])
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--save", default=None, metavar="DIR")
     args = ap.parse_args()
     X, Y = make_data(args.dataset, args.n, args.seed)
     trainer = make_trainer(args.model, args.head, args.n, args.seed)
+    keeper = train.BestKeeper(trainer, mode="min") if args.save else None
     x, y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
     for epoch in range(args.epochs):
         loss = trainer.step(x if epoch == 0 else None, y if epoch == 0 else None)
+        if keeper is not None:
+            keeper.offer(loss)
         print("=== Epoch %d ===\n + loss: %.5e" % (epoch, float(loss.item())))
+    if args.save:
+        os.makedirs(args.save, exist_ok=True)
+        checkpoint.save_best(os.path.join(args.save, "best.npz"), keeper)
+        checkpoint.save(os.path.join(args.save, "last.npz"), trainer, keeper=keeper)
+        print("kept %d of %d epochs, best train loss %.5e: %s" % (keeper.kept, keeper.offers, keeper.best_value(),
+                                                                  os.path.join(args.save, "best.npz")))
 
 
 if __name__ == "__main__":

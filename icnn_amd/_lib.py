@@ -66,10 +66,12 @@ EXPORTS = [
     "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed", "icnn_be_gd_feed_px_work_bytes", "icnn_be_gd_feed_px",
     "icnn_be_step_gate", "icnn_be_param_update_gated", "icnn_be_gated_copy",
     "icnn_be_replay_enqueue", "icnn_be_replay_sample",
+    "icnn_be_gd_eval_work_bytes", "icnn_be_gd_eval", "icnn_be_macro_f1", "icnn_be_keep_best",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
 BN_MODE = {"batch": 0, "moving": 1}     # ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING
+KEEP_MODE = {"min": 0, "max": 1}        # ICNN_BE_KEEP_MIN / ICNN_BE_KEEP_MAX
 MAX_PROJ_RANGES = 8
 RL_TD_MAX_BLOCKS = 256
 RL_TD_WORK_BYTES = 8 * RL_TD_MAX_BLOCKS + 16
@@ -330,6 +332,14 @@ def load():
     lib.icnn_be_gd_feed_px_work_bytes.restype = C.c_size_t
     lib.icnn_be_gd_feed_px.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p] * 6)
     lib.icnn_be_gd_feed_px.restype = C.c_int
+    lib.icnn_be_gd_eval_work_bytes.argtypes = [C.c_int]
+    lib.icnn_be_gd_eval_work_bytes.restype = C.c_size_t
+    lib.icnn_be_gd_eval.argtypes = [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p] * 4
+    lib.icnn_be_gd_eval.restype = C.c_int
+    lib.icnn_be_macro_f1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_macro_f1.restype = C.c_int
+    lib.icnn_be_keep_best.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.icnn_be_keep_best.restype = C.c_int
     lib.icnn_be_param_update.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p]
     lib.icnn_be_param_update.restype = C.c_int
     lib.icnn_be_param_update_gated.argtypes = [C.POINTER(ParamUpdateArgs), C.c_void_p, C.c_void_p]

@@ -620,6 +620,29 @@ int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int
     return e == hipSuccess ? 0 : fail(e);
 }
 
+size_t icnn_be_gd_eval_work_bytes(int B) { return B < 1 ? 0 : icnn_be::gd_feed_work_bytes(B); }
+
+int icnn_be_gd_eval(const double *yK, const float *t, int B, int n, float *loss, int *f1_tallies, void *work, void *stream) {
+    if (B < 1 || n < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
+    icnn_be::GdEvalLaunch l{yK, t, B, n, loss, f1_tallies, work};
+    hipError_t e = icnn_be::launch_gd_eval(l, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_macro_f1(const int *tallies, int B, double *f1, void *stream) {
+    if (B < 1 || !tallies || !f1) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_macro_f1(tallies, B, f1, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
+int icnn_be_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, void *stream) {
+    if (!score || !best || !gate) return ICNN_BE_EINVAL;
+    if (mode != ICNN_BE_KEEP_MIN && mode != ICNN_BE_KEEP_MAX) return ICNN_BE_EINVAL;
+    hipError_t e = icnn_be::launch_keep_best(score, score_is_f64 != 0, mode, best, gate, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : fail(e);
+}
+
 int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
                           double *lam_rows, void *stream) {
     if (int rc = check_state(st)) return rc;

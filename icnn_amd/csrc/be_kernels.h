@@ -303,6 +303,20 @@ constexpr int GD_FEED_PX_MAX_CHUNKS = 65535; // gridDim.y
 long long gd_feed_px_chunks(int n, int K);
 hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream);
 
+// ---- the epoch level of the training scripts (be_train_epoch.hip) --------------------
+// the loss-only form of the feed above: loss [1] and, unless NULL, tallies [B][3]; nothing else is written
+struct GdEvalLaunch {
+    const double *yK;             // [B][n] y_K (float32 values)
+    const float *t;               // [B][n] targets
+    int B, n;
+    float *loss;
+    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
+    void *work;                   // gd_feed_work_bytes(B)
+};
+hipError_t launch_gd_eval(const GdEvalLaunch &l, hipStream_t stream);
+hipError_t launch_macro_f1(const int *tallies, int B, double *f1, hipStream_t stream);
+hipError_t launch_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, hipStream_t stream);
+
 // ---- parameter update (be_train_update.hip): plain, gated, and the RL critic's with its target net ------
 long long param_update_blocks(long long n);
 hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream);   // go NULL: ungated

@@ -15,12 +15,13 @@
 #include <hip/hip_runtime.h>
 
 #include "be_kernels.h"
+#include "be_train_gd_dev.h"
 
 namespace icnn_be {
 
 namespace {
 
-constexpr int GT = 256;
+constexpr int GT = GD_FEED_THREADS;
 
 struct GdFeedArgs {
     GdFeedLaunch l;
@@ -37,30 +38,9 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
     const int tid = threadIdx.x, j = blockIdx.x, n = l.n, K = l.K, B = l.B;
     const double *y_row = l.yK + (size_t)j * n;
     const float *t_row = l.t + (size_t)j * n;
-    // ---- this sample's squared error and tallies ----
-    double s = 0.0;
-    for (int i = tid; i < n; i += GT) {
-        const float d = (float)y_row[i] - t_row[i];
-        s = s + (double)d * (double)d;
-    }
-    s = block_tree_sum<GT>(s, red);
-    if (l.tallies) {
-        int tp = 0, fp = 0, fn = 0;
-        for (int i = tid; i < n; i += GT) {
-            const bool pred = y_row[i] >= 0.5, truth = (int)t_row[i] != 0;
-            tp += pred && truth;
-            fp += pred && !truth;
-            fn += !pred && truth;
-        }
-        tp = block_tree_sum<GT>(tp, ired);
-        fp = block_tree_sum<GT>(fp, ired);
-        fn = block_tree_sum<GT>(fn, ired);
-        if (tid == 0) {
-            l.tallies[3 * j] = tp;
-            l.tallies[3 * j + 1] = fp;
-            l.tallies[3 * j + 2] = fn;
-        }
-    }
+    // ---- this sample's squared error and tallies (be_train_gd_dev.h) ----
+    const double s = gd_sample_sqerr(y_row, t_row, n, red);
+    if (l.tallies) gd_sample_tallies(y_row, t_row, n, ired, l.tallies + 3 * (size_t)j);
     // ---- its K rows: element e = k n + i of the sample's [K][n] block ----
     double *v_blk = l.v_rows + (size_t)j * K * n;
     const size_t total = (size_t)K * n;
@@ -78,20 +58,9 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
     if (tid == 0) {
         l.row_offset[j] = K * j;
         if (j == B - 1) l.row_offset[B] = K * B;
-        __hip_atomic_store(a.partial + j, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int ticket = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == (int)gridDim.x - 1;
     }
-    __syncthreads();
-    if (!s_last) return;
-    // ---- the last workgroup: the loss, per-sample parts in sample order within a thread, then the fixed tree ----
-    double tot = 0.0;
-    for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot = block_tree_sum<GT>(tot, red);
-    if (tid == 0) {
-        *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
-    }
+    // ---- the loss, formed by the last workgroup to take a ticket ----
+    gd_loss_behind_ticket(a.partial, a.ticket, j, s, B, n, l.loss, red, &s_last);
 }
 
 struct GdFeedPxArgs {
@@ -142,21 +111,8 @@ __global__ __launch_bounds__(GT) void gd_feed_px_kernel(GdFeedPxArgs a) {
         s = s + (double)u * (double)u;
     }
     s = block_tree_sum<GT>(s, red);
-    if (tid == 0) {
-        __hip_atomic_store(a.partial + j, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int ticket = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = ticket == B - 1;                   // one ticket per sample, whatever gridDim.y
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // ---- the last of them: the loss, as gd_feed_kernel forms it ----
-    double tot = 0.0;
-    for (int b = tid; b < B; b += GT) tot = tot + __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    tot = block_tree_sum<GT>(tot, red);
-    if (tid == 0) {
-        *l.loss = (float)(tot * (1.0 / ((double)B * (double)n)));
-        __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch
-    }
+    // ---- one ticket per sample, whatever gridDim.y; the last of them forms the loss, as gd_feed_kernel does ----
+    gd_loss_behind_ticket(a.partial, a.ticket, j, s, B, n, l.loss, red, &s_last);
 }
 
 }  // namespace
@@ -167,8 +123,8 @@ size_t gd_feed_work_bytes(int batch) { return sizeof(double) * (size_t)(batch > 
 hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream) {
     GdFeedArgs a{};
     a.l = l;
-    a.partial = static_cast<double *>(l.work);
-    a.ticket = reinterpret_cast<int *>(a.partial + (l.B > 0 ? l.B : 1));
+    a.partial = gd_feed_partial(l.work);
+    a.ticket = gd_feed_ticket(l.work, l.B);
     return launch_kernel(gd_feed_kernel, dim3(l.B), dim3(GT), 0, stream, a);
 }
 
@@ -180,8 +136,8 @@ long long gd_feed_px_chunks(int n, int K) {
 hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream) {
     GdFeedPxArgs a{};
     a.l = l;
-    a.partial = static_cast<double *>(l.work);
-    a.ticket = reinterpret_cast<int *>(a.partial + (l.B > 0 ? l.B : 1));
+    a.partial = gd_feed_partial(l.work);
+    a.ticket = gd_feed_ticket(l.work, l.B);
     const long long total = (long long)l.K * l.n;
     const long long S = l.v_rows ? gd_feed_px_chunks(l.n, l.K) : 1;
     a.chunk = (unsigned)((total + S - 1) / S);

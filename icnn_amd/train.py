@@ -37,6 +37,11 @@
                     with the loss mean((255 (y_K - t))^2) and its feed on a two-dimensional grid (icnn_be_gd_feed_px), and
                     the script's test phase as evaluate().
 
+    BestKeeper      the scripts' "save when the score is better" on the device: icnn_be_keep_best (and icnn_be_macro_f1 for a
+                    score formed from F1 tallies) sets a gate, icnn_be_gated_copy snapshots theta, the arena and the BatchNorm
+                    statistics behind it (be_train_epoch.hip; DESIGN.md §20).  GDTrainer's test phase, evaluate(), is there too;
+                    icnn_amd.checkpoint saves and resumes the trainers.
+
 One training step of the multi-label experiment:
     solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
 or, for a caller that updates the weights itself,
@@ -801,10 +806,18 @@ class GDTrainer(_Trainer, _TrainF1):
 
     bn_updates is passed to surrogate_grad: k > 0 folds the BatchNorm statistics of the step k times into model.bn_stats (the
     caveat of unrolled_grad applies: the reference's graph calls f K times on its way to the loss, and whether TensorFlow
-    merges those identical x-only subgraphs is not pinned down, so the count is the caller's)."""
+    merges those identical x-only subgraphs is not pinned down, so the count is the caller's).
+
+    eval_batch = E also allocates the script's test phase (multi-label-cls/icnn-back.py:208-216): evaluate(x, t)
+    runs the context in eval_bn mode, gd.solve from y0 without a trajectory and the loss-only form of the feed
+    (icnn_be_gd_eval, be_train_epoch.hip) on exactly E samples; it returns the float32 device scalar eval_loss, keeps y_eval
+    and, with f1=True, eval_f1_tallies (eval_macro_f1() reads them), and changes no weight, optimiser state, statistic or
+    result tensor of the training step.  eval_bn=None is what the script does at test time: "moving" (it sets
+    is_training(False), :210); a model without BatchNorm ignores it."""
     _no_tallies = "F1 tallies are kept with f1=True only"
 
-    def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, bn_updates=0, f1=False):
+    def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, bn_updates=0, f1=False,
+                 eval_batch=None, eval_bn=None):
         if not isinstance(model, FCModel):
             name = model.__name__ if isinstance(model, type) else type(model).__name__
             raise TypeError("train.GDTrainer serves picnn.FCModel (ficnn.GDTrainer trains a FICNNModel), got %s" % name)
@@ -812,10 +825,19 @@ class GDTrainer(_Trainer, _TrainF1):
         if self.batch < 1 or self.n_iter < 1:
             raise ValueError("batch and n_iter must be >= 1")
         self.bn_updates = _non_negative("bn_updates", bn_updates)
+        self.eval_batch = None if eval_batch is None else int(eval_batch)
+        if self.eval_batch is not None and self.eval_batch < 1:
+            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
+        if eval_bn is None:
+            eval_bn = "moving"
+        if eval_bn not in _lib.BN_MODE:
+            raise ValueError("eval_bn must be 'batch' or 'moving', got %r" % (eval_bn,))
+        self.eval_bn = eval_bn if model.has_bn else "batch"         # without BatchNorm there is one context
         self.model, self.spec, self.device = model, model.spec, model.device
         self.lr, self.momentum, self.y0 = float(lr), float(momentum), float(y0)
         self.opt = DeviceAdam(model, lr=adam_lr)
-        B, K, n, dev = self.batch, self.n_iter, self.spec.n_labels, self.device
+        B, K, E, n, dev = self.batch, self.n_iter, self.eval_batch, self.spec.n_labels, self.device
+        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
         self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
         self.scale = float(np.float32(1.0) / np.float32(B * n))
         self.x = torch.zeros(B, self.spec.n_features, dtype=torch.float32, device=dev)
@@ -830,6 +852,14 @@ class GDTrainer(_Trainer, _TrainF1):
         self._feed_work = _ticket(model._lib.icnn_be_gd_feed_work_bytes(B), dev)
         self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
         self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
+        self.y_eval = self.eval_loss = self.eval_f1_tallies = None
+        if E is not None:
+            self.x_eval = torch.zeros(E, self.spec.n_features, dtype=torch.float32, device=dev)
+            self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
+            self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
+            self.eval_f1_tallies = torch.zeros(E, 3, dtype=torch.int32, device=dev) if f1 else None
+            self._eval_work = _ticket(model._lib.icnn_be_gd_eval_work_bytes(E), dev)
 
     def step(self, x=None, t=None) -> torch.Tensor:
         """One step on (x [B, n_features], t [B, n]); None keeps the batch of the previous call (graph replay)."""
@@ -849,6 +879,32 @@ class GDTrainer(_Trainer, _TrainF1):
                        bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
         self.opt.step(self.grad)
         return self.loss
+
+    def evaluate(self, x=None, t=None) -> torch.Tensor:
+        """The test phase on exactly eval_batch samples (x, t shaped as for step; None keeps the previous ones): the loss
+        mean((y_K - t)^2) at y_K of the unrolled GD from y0 with the context in eval_bn mode, a float32 device scalar
+        (eval_loss); y_eval keeps y_K and eval_f1_tallies (f1=True) the tallies.  Nothing is updated and no statistic is
+        folded.  No host wait (capturable)."""
+        from . import gd
+        if self.eval_batch is None:
+            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        self._put(self.x_eval, x)
+        self._put(self.t_eval, t)
+        model, E = self.model, self.eval_batch
+        model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
+        self.y_eval = gd.solve(model, self.ctx_eval, self.y0, self.n_iter, self.lr, self.momentum)[0]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(model._lib.icnn_be_gd_eval(self.y_eval.data_ptr(), self.t_eval.data_ptr(), E, self.spec.n_labels,
+                                              self.eval_loss.data_ptr(),
+                                              None if self.eval_f1_tallies is None else self.eval_f1_tallies.data_ptr(),
+                                              self._eval_work.data_ptr(), C.c_void_p(stream)), "icnn_be_gd_eval")
+        return self.eval_loss
+
+    def eval_macro_f1(self) -> float:
+        """the test F1 of the last evaluate() (util.macroF1; f1=True only; one wait)"""
+        if self.eval_f1_tallies is None:
+            raise ValueError("F1 tallies exist for a trainer constructed with f1=True and eval_batch only")
+        return macro_f1(self.eval_f1_tallies)
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -967,3 +1023,116 @@ class ConvGDTrainer(_Trainer):
         self.y_eval = gd.solve(self.model, self.ctx_eval, self.y0_eval, self.n_iter, self.lr, self.momentum)[0]
         self._feed(self.y_eval, self.t_eval, self.eval_batch, self.eval_loss, self._feed_work_eval, False)
         return self.eval_loss
+
+
+# --------------------------------------------------------------------------------------------- #
+# Keeping the best model on the device
+# --------------------------------------------------------------------------------------------- #
+class BestKeeper:
+    """The scripts' "save when the score is better" without a host round trip (multi-label-cls/icnn_ebundle.py:274-277: `if
+    testF1 > bestTestF1: save`, mode "max" with start=0.0; synthetic-cls/icnn.py:206-209: `bestMSE is None or trainMSE <
+    bestMSE`, mode "min"), for any trainer that owns a DeviceAdam as `.opt` (BundleTrainer, GDTrainer,
+    ConvGDTrainer, ficnn.GDTrainer, rl_train.CriticTrainer).
+
+    offer(score) enqueues icnn_be_keep_best on a one-element float32 or float64 device tensor and, behind its gate,
+    icnn_be_gated_copy of opt.theta, opt.arena and the model's BatchNorm moving statistics into snapshots: they change only
+    on an offer that is STRICTLY better than `best`.  offer_macro_f1(tallies) first forms util.macroF1 on the device
+    (icnn_be_macro_f1) into the keeper's own score word, so a captured [evaluate, offer_macro_f1(eval_f1_tallies)] keeps the
+    best test-F1 model with no host data.  No host wait in either.
+
+    start=None: -inf for "max", +inf for "min", so the first finite offer is kept.  One deviation from synthetic-cls:
+    `bestMSE is None or ...` would keep a NaN first loss; the keeper never keeps a NaN (no comparison with a NaN is true).
+
+    For a model with BatchNorm the constructor calls model.flatten_bn_stats(), which MOVES the statistics' addresses:
+    construct the keeper before capturing anything that reads them (a BundleTrainer(skip_on_error=True) has moved them
+    already).  The snapshots start as copies of the current state, so restore() before any kept offer puts that back.
+
+    best (float64 [1]) is the device scalar; offers, kept and best_value() read the device (one wait each)."""
+
+    def __init__(self, trainer, mode="max", start=None):
+        if mode not in _lib.KEEP_MODE:
+            raise ValueError("mode must be 'max' or 'min', got %r" % (mode,))
+        opt = getattr(trainer, "opt", None)
+        if not isinstance(opt, DeviceAdam):
+            raise TypeError("BestKeeper serves a trainer that owns a DeviceAdam as .opt, got %s" % type(trainer).__name__)
+        self.trainer, self.opt, self.model, self.mode = trainer, opt, opt.model, mode
+        self.device = dev = opt.device
+        self._lib = opt.model._lib
+        if start is None:
+            start = -math.inf if mode == "max" else math.inf
+        self.start = float(start)
+        self.best = torch.full((1,), self.start, dtype=torch.float64, device=dev)
+        self.gate = torch.zeros(3, dtype=torch.int32, device=dev)                # go, offers, kept
+        self.score = torch.zeros(1, dtype=torch.float64, device=dev)             # offer_macro_f1's score word
+        self.theta = opt.theta.clone()
+        self.arena = opt.arena.clone()
+        self._bn_live = self.bn = None
+        self._bn_views = {}
+        if getattr(self.model, "has_bn", False) and self.model.bn_stats:     # a one-layer u-path normalises nothing
+            self._bn_live = live = self.model.flatten_bn_stats()
+            self.bn = live.clone()
+            self._bn_views = {k: ((t.data_ptr() - live.data_ptr()) // 4, tuple(t.shape))
+                              for k, t in self.model.bn_stats.items()}
+
+    def _pairs(self):
+        """(snapshot, live) of everything the keeper keeps"""
+        pairs = [(self.theta, self.opt.theta), (self.arena, self.opt.arena)]
+        if self.bn is not None:
+            pairs.append((self.bn, self._bn_live))
+        return pairs
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def offer(self, score):
+        """Offer a one-element float32 or float64 device tensor; the snapshots follow when it is strictly better."""
+        if (not torch.is_tensor(score) or score.numel() != 1 or not score.is_cuda
+                or score.dtype not in (torch.float32, torch.float64)):
+            raise ValueError("score is one float32 or float64 on the device")
+        stream = self._stream()
+        _lib.check(self._lib.icnn_be_keep_best(score.data_ptr(), int(score.dtype == torch.float64), _lib.KEEP_MODE[self.mode],
+                                               self.best.data_ptr(), self.gate.data_ptr(), stream), "icnn_be_keep_best")
+        for snap, live in self._pairs():
+            _lib.check(self._lib.icnn_be_gated_copy(snap.data_ptr(), live.data_ptr(), live.numel(), self.gate.data_ptr(), 1,
+                                                    stream), "icnn_be_gated_copy")
+
+    def offer_macro_f1(self, tallies):
+        """Offer util.macroF1 of per-example tallies (int32 [B, 3] on the device: a trainer's f1_tallies / eval_f1_tallies)."""
+        if (not torch.is_tensor(tallies) or tallies.dtype != torch.int32 or not tallies.is_cuda or not tallies.is_contiguous()
+                or tallies.dim() != 2 or tallies.shape[1] != 3 or tallies.shape[0] < 1):
+            raise ValueError("tallies is a contiguous int32 [B, 3] device tensor, B >= 1")
+        _lib.check(self._lib.icnn_be_macro_f1(tallies.data_ptr(), tallies.shape[0], self.score.data_ptr(), self._stream()),
+                   "icnn_be_macro_f1")
+        self.offer(self.score)
+
+    @property
+    def offers(self) -> int:
+        """offers made (reads the device: one wait)"""
+        return int(self.gate[1].item())
+
+    @property
+    def kept(self) -> int:
+        """offers that were kept (reads the device: one wait)"""
+        return int(self.gate[2].item())
+
+    def best_value(self) -> float:
+        """the best score so far, `start` before any was kept (reads the device: one wait)"""
+        return float(self.best.item())
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        """the kept model's theta as a NumPy dict keyed like grad_layout (one copy; synchronises): what goes into best.npz"""
+        flat = self.theta.cpu().numpy()
+        return {name: t.numpy().copy() for name, t in unpack_grad(self.opt.spec, torch.from_numpy(flat)).items()}
+
+    def bn_stats(self) -> Dict[str, np.ndarray]:
+        """the kept model's BatchNorm moving statistics keyed like picnn.init_bn_stats ({} without BatchNorm; synchronises)"""
+        if self.bn is None:
+            return {}
+        flat = self.bn.cpu().numpy()
+        return {k: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for k, (off, shape) in self._bn_views.items()}
+
+    def restore(self):
+        """Copy the snapshots back: theta, the arena and the statistics become the kept model's, on the device.  Adam's m, v
+        and the step count are left alone."""
+        for snap, live in self._pairs():
+            live.copy_(snap)

@@ -688,6 +688,49 @@ ICNN_BE_API int icnn_be_gd_feed_px(const double *yK, const float *t, const doubl
                                    float px, double *v_rows, double *c_rows, int *row_offset, float *loss, void *work,
                                    void *stream);
 
+/* ---- the epoch level of the training scripts (be_train_epoch.hip, additive to ABI 12) ---- */
+
+/*
+ * The loss-only form of icnn_be_gd_feed: the test phase of the FC back-optimisation trainer
+ * (multi-label-cls/icnn-back.py:208-216), one launch of B workgroups behind icnn_be_fc_gd.  From yK [B][n] (float64 holding
+ * float32 values) and t [B][n] (float32) it writes
+ *   loss [1]          float32, the bits icnn_be_gd_feed writes for the same yK, t, B, n: the same float64 products, the same
+ *                     per-sample tree, the same fixed order over the per-sample sums (one copy of the device code serves both)
+ *   f1_tallies [B][3] may be NULL: the words icnn_be_gd_feed writes
+ * and nothing else.  work: icnn_be_gd_eval_work_bytes(B) bytes (0 for B < 1), 8-byte aligned, ZEROED ONCE by the caller (the
+ * kernel re-arms its ticket).  EINVAL for B or n < 1 or yK, t, loss or work NULL, before anything is launched.  Vector stores
+ * only, no accumulating atomics, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API size_t icnn_be_gd_eval_work_bytes(int B);
+ICNN_BE_API int icnn_be_gd_eval(const double *yK, const float *t, int B, int n, float *loss, int *f1_tallies, void *work,
+                                void *stream);
+
+/*
+ * util.macroF1 of the reference from per-example tallies [B][3] (tp, fp, fn; icnn_be_feed_plan's and icnn_be_gd_feed's
+ * layout): f1 [1] (float64, device memory) = the mean over the B examples of 2 tp / (2 tp + fp + fn), 0 where the
+ * denominator is 0.  One launch of one workgroup, which loops over B; every quotient is an IEEE float64 division, each
+ * thread adds its examples in index order and a fixed tree adds the threads, so every call on the same tallies gives the
+ * same bits.  EINVAL for B < 1 or a NULL pointer, before anything is launched.  Vector stores only, no atomics, no host
+ * synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_macro_f1(const int *tallies, int B, double *f1, void *stream);
+
+/*
+ * "Keep the model when the score is better" (multi-label-cls/icnn_ebundle.py:274-277, synthetic-cls/icnn.py:206-209) as
+ * device words, one workgroup.  score: one float32, or with score_is_f64 != 0 one float64, in device memory; mode:
+ * ICNN_BE_KEEP_MIN (smaller is better) or ICNN_BE_KEEP_MAX (larger is better); best: [1] float64 in device memory, which the
+ * CALLER initialises; gate: [3] int32 in device memory, ZEROED ONCE by the caller:
+ *   gate[0]  "go"      1 if the score is STRICTLY better than *best, else 0; a NaN score is never better
+ *   gate[1]  "offers"  a running total: + 1 on every launch
+ *   gate[2]  "kept"    a running total: + 1 on every launch that goes
+ * and *best = score when it goes.  gate[0] is the word icnn_be_gated_copy takes as `go`: the snapshot of the kept model is
+ * icnn_be_gated_copy(snapshot, live, n, gate, 1).  EINVAL for score, best or gate NULL or a mode outside {0, 1}, before
+ * anything is launched.  Vector stores only, no atomics, no host synchronisation (capturable in a HIP graph).
+ */
+#define ICNN_BE_KEEP_MIN 0
+#define ICNN_BE_KEEP_MAX 1
+ICNN_BE_API int icnn_be_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, void *stream);
+
 /* ---- parameter update on the device (be_train_update.hip, additive to ABI 12) ------------------ */
 
 /*
