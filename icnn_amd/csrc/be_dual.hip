@@ -115,7 +115,9 @@ __global__ __launch_bounds__(64, 3) void implicit_feed_kernel(FeedArgs a) {
     double s1 = 0.0, s2 = 0.0;
     for (int i = 0; i < k; ++i) { s1 += bcast(x1, i); s2 += bcast(x2, i); }
     const double ct = s1 / s2;
-    const double clam = x1 - ct * x2;                           // row layout, lane i < k
+    // one cut: the border row alone says c_lam = 0, whatever the 1 x 1 block is.  The elimination on the block gives it up to
+    // eps |x1| only, and 0/0 where every column of y is saturated (n = 1, y = 0 under the squared error: the block is zero)
+    const double clam = k == 1 ? 0.0 : x1 - ct * x2;            // row layout, lane i < k
     const double lam = lane < k ? st.lam[(size_t)u * T + lane] : 0.0;
     const int row0 = a.row_offset[u];
     if (lane < k) { a.fd_c[row0 + lane] = clam; a.fd_sample[row0 + lane] = u; }

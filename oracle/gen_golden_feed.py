@@ -25,6 +25,8 @@ import problems  # noqa: E402
 
 REF = "/root/reference"
 CASES = {"maxaffine_n159": 10, "lse_n33": 12, "zero_gradient": 6}
+# float64 cuts, B = 1 and n = 1: nIter as the solver goldens have it
+CASES.update({case: problems.GOLDEN_CASES[case][1] for case in ("c1_quadratic", "maxaffine_f64", "single_sample", "n_equals_1")})
 
 
 def lift(path, name):

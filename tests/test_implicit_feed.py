@@ -5,12 +5,15 @@ import os
 import numpy as np
 import pytest
 
+import feed_ref
 import problems
 from golden_util import GOLDEN_DIR
 from oracle import bundle_entropy_oracle as oracle
 from oracle import implicit_feed_oracle as feed_oracle
 
 CASES = {"maxaffine_n159": 10, "lse_n33": 12, "zero_gradient": 6}
+# float64 cuts (the double instances of the kernel), B = 1 and n = 1: nIter as the solver goldens have it
+CASES.update({case: problems.GOLDEN_CASES[case][1] for case in ("c1_quadratic", "maxaffine_f64", "single_sample", "n_equals_1")})
 
 
 def _load(case, loss):
@@ -46,8 +49,10 @@ def test_feed_kernel_matches_reference_golden(case, loss):
     # KKT solve amplifies that
     tol = 1e-3 if case == "lse_n33" else 1e-6
     scale_c = 1.0 + np.abs(gold["c"])
-    assert np.all(np.abs(feed.c.cpu().numpy() - gold["c"]) <= tol * scale_c)
     scale_v = 1.0 + np.abs(gold["v"])
+    print("%s %s: device vs golden c %.3e v %.3e" % (case, loss, np.max(np.abs(feed.c.cpu().numpy() - gold["c"]) / scale_c),
+                                                     np.max(np.abs(feed.v.cpu().numpy() - gold["v"]) / scale_v)))
+    assert np.all(np.abs(feed.c.cpu().numpy() - gold["c"]) <= tol * scale_c)
     assert np.all(np.abs(feed.v.cpu().numpy() - gold["v"]) <= tol * scale_v)
     # the y rows are the points the active cuts were taken at
     host_ys = res.ys.cpu().numpy()
@@ -83,5 +88,15 @@ def test_feed_kernel_wide_rows_with_more_slots_than_lds_rows():
     idx, rows_y, rows_v, rows_c = feed_oracle.feed_rows(y, labels, A, xs, lams, "mse")
     assert np.array_equal(feed.sample.cpu().numpy(), idx)
     assert np.array_equal(feed.y.cpu().numpy(), rows_y)
-    assert np.all(np.abs(feed.c.cpu().numpy() - rows_c) <= 1e-6 * (1.0 + np.abs(rows_c)))
-    assert np.all(np.abs(feed.v.cpu().numpy() - rows_v) <= 1e-6 * (1.0 + np.abs(rows_v)))
+    err_c = np.abs(feed.c.cpu().numpy() - rows_c) / (1.0 + np.abs(rows_c))
+    err_v = np.abs(feed.v.cpu().numpy() - rows_v) / (1.0 + np.abs(rows_v))
+    # the comparison is on the device's own state, so nothing but float64 summation and elimination order differs: tier A
+    #  -- provided the oracle itself is that good here, which the longdouble restatement says
+    _, _, v_ld, c_ld = feed_ref.feed_rows_ld(y, labels, A, xs, lams, "mse")
+    ora_c = np.abs(rows_c - c_ld) / (1.0 + np.abs(c_ld))
+    ora_v = np.abs(rows_v - v_ld) / (1.0 + np.abs(v_ld))
+    print("wide feed: count per sample %s (max %d), device vs oracle c %.3e v %.3e, oracle vs longdouble c %.3e v %.3e"
+          % (cnt.tolist(), cnt.max(), err_c.max(), err_v.max(), ora_c.max(), ora_v.max()))
+    assert np.all(err_c <= 1e-6) and np.all(err_v <= 1e-6)
+    assert ora_c.max() <= 1e-11 and ora_v.max() <= 1e-11
+    assert np.all(err_c <= 1e-9) and np.all(err_v <= 1e-9)
