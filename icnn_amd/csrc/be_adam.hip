@@ -331,7 +331,7 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
         RowsArgs r{};
         const int rows_lds = rows_layout(m, ROWS_MAX, r.lay) + (ROWS_MAX + 1) * 8;
         int resident = 1;
-        if (rows_lds <= 160 * 1024 && batch > ROWS_MAX) {      // more than one workgroup: they must all be resident
+        if (rows_lds <= LDS_BYTES && batch > ROWS_MAX) {      // more than one workgroup: they must all be resident
             if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
             int per_cu = 0;
             hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_rows_kernel),
@@ -340,7 +340,7 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
             resident = per_cu * device_cus();
         }
         const int per_wg = batch <= ROWS_MAX ? batch : (batch + resident - 1) / (resident > 0 ? resident : 1);
-        if (rows_lds <= 160 * 1024 && per_wg >= 1 && per_wg <= ROWS_MAX) {
+        if (rows_lds <= LDS_BYTES && per_wg >= 1 && per_wg <= ROWS_MAX) {
             r.a = a;
             r.per_wg = per_wg;
             if (obs) {
@@ -367,7 +367,7 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
     if (obs) return hipErrorNotSupported;
     a.red_off = (a.fa.lds_floats + 3) & ~3;
     lds = a.red_off * 4 + (NWAVE + 1) * 8;
-    if (lds > 160 * 1024) return hipErrorNotSupported;
+    if (lds > LDS_BYTES) return hipErrorNotSupported;
     if (a.tiles == 1) return launch_kernel(adam_fc_kernel, dim3(1), dim3(NTHREADS), lds, stream, a);
     if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_fc_kernel), lds); e != hipSuccess) return e;
     int per_cu = 0;

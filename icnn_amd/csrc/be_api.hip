@@ -21,6 +21,8 @@ int fail(hipError_t e) {
     return e == hipErrorInvalidValue ? ICNN_BE_EINVAL : ICNN_BE_ELAUNCH;
 }
 
+int done(hipError_t e) { return e == hipSuccess ? 0 : fail(e); }
+
 // everything about a state but its buffers
 int check_shape(const icnn_be_state *st) {
     if (!st) return ICNN_BE_EINVAL;
@@ -57,6 +59,15 @@ int check_bn_mode(const icnn_be_bn_moving *mv, int mode, int updates, const int 
     if (!mv || !(mv->decay >= 0.f && mv->decay <= 1.f)) return ICNN_BE_EINVAL;
     for (int l = 0; l < nl; ++l)
         if (n[l] > 0 && (!mv->mean[l] || !mv->var[l])) return ICNN_BE_EINVAL;
+    return 0;
+}
+
+// what icnn_be_fc_gd, icnn_be_conv_gd and icnn_be_ficnn_gd refuse alike
+template <typename Model>
+int check_gd_args(const Model *model, const float *ctx, const double *y0, const double *y_out, const void *workspace, int batch,
+                  int n_iter, double lr, double momentum) {
+    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
     return 0;
 }
 
@@ -130,6 +141,22 @@ hipError_t solve_rounds(const icnn_be_state &st, int budget, int total, float *f
         if (e != hipSuccess) return e;
     }
     return total > T ? icnn_be::launch_mark_unfinished(st, s) : hipSuccess;
+}
+
+/* The round solve of the models without a persistent kernel (icnn_be_solve_conv, icnn_be_solve_ficnn); returns the rounds or
+   an ICNN_BE_E* code.  Lockstep rounds at EVERY nIter (time slicing on request, ICNN_BE_FLAG_TIME_SLICE).  Slicing pays when a
+   round is held up by a Newton solve that runs its 100-update cap; since limit cycles at their rounding floor are recognised
+   (be_dual_dev.h, NOISE_TOL) those are one solve in a thousand, while every sliced solve pays nIter finishing rounds of
+   five launches for its few laggards.  Measured on the conv model at 256 samples (tools/conv_slice_experiment.py): nIter 30
+   lockstep 12.0 / 11.0 ms against 16.4 / 15.0 sliced on two instances, nIter 5 2.24 / 1.73 against 2.22 / 2.04.  No finishing
+   launch: the conv evaluation couples sixteen samples in the 2048 x 512 layer, so the stragglers get nIter whole rounds. */
+template <typename LaunchFg>
+int solve_generic(const icnn_be_state &st, float *f_work, float *g_work, hipStream_t s, LaunchFg launch_fg) {
+    const bool lockstep = (st.flags & ICNN_BE_FLAG_LOCKSTEP) || st.variant == ICNN_BE_VARIANT_PDIPM ||
+                          !(st.flags & ICNN_BE_FLAG_TIME_SLICE);
+    const int T = outer_iters(st), total = lockstep ? T : sliced_extra_rounds(T);
+    hipError_t e = solve_rounds(st, lockstep ? 0 : SLICE_BUDGET, total, f_work, g_work, s, launch_fg);
+    return e == hipSuccess ? total : fail(e);
 }
 
 struct SolvePlan {
@@ -237,8 +264,7 @@ void icnn_be_debug_profile_conv(long long *device_buf) { icnn_be::set_conv_profi
 int icnn_be_debug_fast_math(int which, const double *x, double *out, int count, void *stream) {
     if (which < 0 || which > 3 || !x || !out || count < 0) return ICNN_BE_EINVAL;
     if (count == 0) return 0;
-    hipError_t e = icnn_be::launch_fast_math(which, x, out, count, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fast_math(which, x, out, count, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_debug_profile_phases(void) { return icnn_be::DUAL_PROF_PHASES; }
@@ -262,8 +288,7 @@ int icnn_be_dual_lds_bytes(int n, int slots, int cut_dtype) {
 int icnn_be_state_init(const icnn_be_state *st, void *stream) {
     if (int rc = check_state(st)) return rc;
     if (st->batch == 0) return 0;
-    hipError_t e = icnn_be::launch_state_init(*st, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_state_init(*st, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_dual_step(const icnn_be_state *st, int t, const void *f, const void *g, void *stream) {
@@ -271,8 +296,7 @@ int icnn_be_dual_step(const icnn_be_state *st, int t, const void *f, const void 
     if (t < 0 || t >= (st->iters > 0 ? st->iters : st->slots) || !f || !g) return ICNN_BE_EINVAL;
     if (st->batch == 0) return 0;
     /* lockstep: every unfinished sample is at outer iteration t and completes it in this launch */
-    hipError_t e = icnn_be::launch_dual_step(*st, t, 0, f, g, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_dual_step(*st, t, 0, f, g, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_fc_pack_floats(const icnn_be_fc_model *shape) {
@@ -296,9 +320,7 @@ int icnn_be_fc_fg(const icnn_be_fc_model *model, const float *ctx, const double 
     if (!model || !ctx || !y || !f || !g || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_fc_fg(*model, ctx, y, batch, f, g, finished,
-                                         static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fc_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
@@ -368,9 +390,8 @@ int fc_context_bn(const icnn_be_fc_ctx *c, const icnn_be_bn_moving *mv, int mode
     /* a device count may be anything: the arguments a fold needs are checked as for one update */
     if (int rc = check_bn_mode(mv, mode, updates_dev ? 1 : updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream), mv, mode,
-                                              updates, updates_dev);
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fc_context(*c, x, batch, ctx, ctx_width, work, static_cast<hipStream_t>(stream), mv, mode,
+                                           updates, updates_dev));
 }
 }  // namespace
 
@@ -419,9 +440,8 @@ int icnn_be_fc_surrogate_grad_dev(const icnn_be_fc_model *model, const icnn_be_f
     icnn_be::fc_bn_widths(*c, n);
     if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, ICNN_BE_MAX_LAYERS)) return rc;
     if (int rc = icnn_be::fc_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
-    hipError_t e = icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                     static_cast<hipStream_t>(stream), mv, updates, rows_dev);
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fc_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                  static_cast<hipStream_t>(stream), mv, updates, rows_dev));
 }
 
 size_t icnn_be_fc_surrogate_grad_dev_work_floats(const icnn_be_fc_model *model, const icnn_be_fc_ctx *c, int batch, int rows) {
@@ -472,9 +492,8 @@ int icnn_be_conv_surrogate_grad_dev(const icnn_be_conv_model *model, const icnn_
     icnn_be::conv_bn_widths(g, n);
     if (int rc = check_bn_mode(mv, ICNN_BE_BN_BATCH, updates, n, 4)) return rc;
     if (int rc = icnn_be::conv_surrogate_shape(*model, *c, batch, rows, v != nullptr)) return rc;
-    hipError_t e = icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                       static_cast<hipStream_t>(stream), mv, updates, rows_dev);
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_conv_surrogate_grad(*model, *c, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                    static_cast<hipStream_t>(stream), mv, updates, rows_dev));
 }
 
 int icnn_be_fc_context_stage(const icnn_be_fc_ctx *c, int stage, const float *x, int batch, float *ctx, int ctx_width,
@@ -500,15 +519,13 @@ int icnn_be_fc_context_norm(const icnn_be_fc_ctx *c, int stage, int batch, doubl
     if (int rc = icnn_be::ctx_check(*c)) return rc;
     if (stage < 0 || stage >= c->n_layers - 2 || !c->batchnorm) return ICNN_BE_EINVAL;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_fc_context_norm(*c, stage, batch, batch_total, stats, work, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fc_context_norm(*c, stage, batch, batch_total, stats, work, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_fc_clamp(const icnn_be_fc_model *model, int mode, void *stream) {
     if (!model || !model->wpack || mode < ICNN_BE_CLAMP_ABS || mode > ICNN_BE_CLAMP_ABS_HALF) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
-    hipError_t e = icnn_be::launch_fc_clamp(*model, mode, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_fc_clamp(*model, mode, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_adam_workspace_bytes(int batch, int n) {
@@ -522,12 +539,11 @@ int icnn_be_adam_fc(const icnn_be_fc_model *model, const float *ctx, int batch, 
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (batch == 0) {
-        hipError_t e = hipMemsetAsync(iters, 0, sizeof(int), s);
-        return e == hipSuccess ? 0 : fail(e);
+        return done(hipMemsetAsync(iters, 0, sizeof(int), s));
     }
     hipError_t e = icnn_be::launch_adam_fc(*model, ctx, batch, max_iter, act_best, f_best, iters, workspace, s);
     if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
-    return e == hipSuccess ? 0 : fail(e);
+    return done(e);
 }
 
 int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, const float *obs, int batch, int max_iter,
@@ -544,12 +560,11 @@ int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx,
         if (cx->width[i] != model->width[i]) return ICNN_BE_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (batch == 0) {
-        hipError_t e = hipMemsetAsync(iters, 0, sizeof(int), s);
-        return e == hipSuccess ? 0 : fail(e);
+        return done(hipMemsetAsync(iters, 0, sizeof(int), s));
     }
     hipError_t e = icnn_be::launch_adam_fc(*model, nullptr, batch, max_iter, act_best, f_best, iters, workspace, s, cx, obs);
     if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
-    return e == hipSuccess ? 0 : fail(e);
+    return done(e);
 }
 
 int icnn_be_implicit_feed(const icnn_be_state *st, const double *y_true, int loss, const int *row_offset,
@@ -558,9 +573,8 @@ int icnn_be_implicit_feed(const icnn_be_state *st, const double *y_true, int los
     if (!y_true || !row_offset || !fd_y || !fd_v || !fd_c || !fd_sample) return ICNN_BE_EINVAL;
     if (loss != ICNN_BE_LOSS_XENT && loss != ICNN_BE_LOSS_MSE) return ICNN_BE_EINVAL;
     if (st->batch == 0) return 0;
-    hipError_t e = icnn_be::launch_implicit_feed(*st, y_true, loss, row_offset, fd_y, fd_v, fd_c, fd_sample,
-                                                 static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_implicit_feed(*st, y_true, loss, row_offset, fd_y, fd_v, fd_c, fd_sample,
+                                              static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_feed_plan_work_bytes(int batch) { return batch < 0 ? 0 : icnn_be::feed_plan_work_bytes(batch); }
@@ -572,22 +586,19 @@ int icnn_be_feed_plan(const icnn_be_state *st, const double *y_true, int loss, i
     if (loss != ICNN_BE_LOSS_XENT && loss != ICNN_BE_LOSS_MSE) return ICNN_BE_EINVAL;
     if (st->batch == 0) return 0;
     icnn_be::FeedPlanLaunch l{*st, y_true, loss, row_offset, counts, loss_out, tallies, work};
-    hipError_t e = icnn_be::launch_feed_plan(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_feed_plan(l, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c, int *fd_sample,
                      void *stream) {
     if (!rows || !fd_y || !fd_v || !fd_c || !fd_sample || batch < 1 || n < 1 || row_cap < 0) return ICNN_BE_EINVAL;
     if (row_cap == 0) return 0;
-    hipError_t e = icnn_be::launch_feed_pad(rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_feed_pad(rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_step_gate(const int *counts, int mask, int *gate, void *stream) {
     if (!counts || !gate) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_step_gate(counts, mask, gate, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_step_gate(counts, mask, gate, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_gd_feed_work_bytes(int B) { return B < 0 ? 0 : icnn_be::gd_feed_work_bytes(B); }
@@ -598,8 +609,7 @@ int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B,
     if (!yK || !t || !coef || !v_rows || !c_rows || !row_offset || !loss || !work) return ICNN_BE_EINVAL;
     if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
     icnn_be::GdFeedLaunch l{yK, t, coef, B, n, K, scale, v_rows, c_rows, row_offset, loss, f1_tallies, work};
-    hipError_t e = icnn_be::launch_gd_feed(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_gd_feed(l, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_gd_feed_px_work_bytes(int B, int n, int K) {
@@ -616,8 +626,7 @@ int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int
     if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
     if (rows == 3 && icnn_be::gd_feed_px_chunks(n, K) > icnn_be::GD_FEED_PX_MAX_CHUNKS) return ICNN_BE_ELIMIT;
     icnn_be::GdFeedPxLaunch l{yK, t, coef, B, n, K, scale, px, v_rows, c_rows, row_offset, loss, work};
-    hipError_t e = icnn_be::launch_gd_feed_px(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_gd_feed_px(l, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_gd_eval_work_bytes(int B) { return B < 1 ? 0 : icnn_be::gd_feed_work_bytes(B); }
@@ -626,21 +635,18 @@ int icnn_be_gd_eval(const double *yK, const float *t, int B, int n, float *loss,
     if (B < 1 || n < 1) return ICNN_BE_EINVAL;
     if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
     icnn_be::GdEvalLaunch l{yK, t, B, n, loss, f1_tallies, work};
-    hipError_t e = icnn_be::launch_gd_eval(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_gd_eval(l, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_macro_f1(const int *tallies, int B, double *f1, void *stream) {
     if (B < 1 || !tallies || !f1) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_macro_f1(tallies, B, f1, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_macro_f1(tallies, B, f1, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, void *stream) {
     if (!score || !best || !gate) return ICNN_BE_EINVAL;
     if (mode != ICNN_BE_KEEP_MIN && mode != ICNN_BE_KEEP_MAX) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_keep_best(score, score_is_f64 != 0, mode, best, gate, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_keep_best(score, score_is_f64 != 0, mode, best, gate, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
@@ -648,8 +654,7 @@ int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *
     if (int rc = check_state(st)) return rc;
     if (!row_offset || !G_rows || !ys_rows || !h_rows || !lam_rows) return ICNN_BE_EINVAL;
     if (st->batch == 0) return 0;
-    hipError_t e = icnn_be::launch_export_active(*st, row_offset, G_rows, ys_rows, h_rows, lam_rows, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_export_active(*st, row_offset, G_rows, ys_rows, h_rows, lam_rows, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_conv_pack_floats(const icnn_be_conv_model *shape) {
@@ -679,26 +684,24 @@ size_t icnn_be_gd_workspace_bytes(int batch, int n) {
 
 int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                   double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack || model->action_box) return ICNN_BE_EINVAL;
-    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
+    if (model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     if (batch == 0) return 0;
     hipError_t e = icnn_be::launch_fc_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
                                          static_cast<hipStream_t>(stream));
     if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
-    return e == hipSuccess ? 0 : fail(e);
+    return done(e);
 }
 
 int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                     double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
-    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (batch == 0) return 0;
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_conv_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
-                                           static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_conv_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
+                                        static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_conv_fg(const icnn_be_conv_model *model, const float *ctx, const double *y, int batch,
@@ -707,8 +710,7 @@ int icnn_be_conv_fg(const icnn_be_conv_model *model, const float *ctx, const dou
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (batch == 0) return 0;
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_conv_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_conv_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream)));
 }
 
 size_t icnn_be_conv_context_work_floats(const icnn_be_conv_model *shape, int batch) {
@@ -739,9 +741,8 @@ int conv_context_bn(const icnn_be_conv_model *shape, const icnn_be_conv_ctx *c, 
     icnn_be::conv_bn_widths(g, n);
     if (int rc = check_bn_mode(mv, mode, updates_dev ? 1 : updates, n, 4)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates,
-                                                updates_dev);
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_conv_context(g, *c, x, batch, ctx, work, static_cast<hipStream_t>(stream), mv, mode, updates,
+                                             updates_dev));
 }
 }  // namespace
 
@@ -759,8 +760,7 @@ int icnn_be_conv_context_bn_dev(const icnn_be_conv_model *shape, const icnn_be_c
 int icnn_be_conv_clamp(const icnn_be_conv_model *model, int mode, void *stream) {
     if (!model || !model->wpack || mode < ICNN_BE_CLAMP_ABS || mode > ICNN_BE_CLAMP_ABS_HALF) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
-    hipError_t e = icnn_be::launch_conv_clamp(*model, mode, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_conv_clamp(*model, mode, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const icnn_be_state *st,
@@ -772,20 +772,10 @@ int icnn_be_solve_conv(const icnn_be_conv_model *model, const float *ctx, const 
     if (st->batch > 0 && (!model->work || model->work_batch < st->batch)) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (st->batch == 0) return 0;
-    /* Lockstep rounds at EVERY nIter (round 3; time slicing on request, ICNN_BE_FLAG_TIME_SLICE).  Slicing pays when a round
-       is held up by a Newton solve that runs its 100-update cap; since limit cycles at their rounding floor are recognised
-       (be_dual_dev.h, NOISE_TOL) those are one solve in a thousand, while every sliced solve pays nIter finishing rounds of
-       five launches for its few laggards.  Measured at 256 samples (tools/conv_slice_experiment.py): nIter 30 lockstep
-       12.0 / 11.0 ms against 16.4 / 15.0 sliced on two instances, nIter 5 2.24 / 1.73 against 2.22 / 2.04.  No finishing
-       launch: its evaluation couples sixteen samples in the 2048 x 512 layer, so the stragglers get nIter whole rounds. */
-    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || st->variant == ICNN_BE_VARIANT_PDIPM ||
-                          !(st->flags & ICNN_BE_FLAG_TIME_SLICE);
-    const int T = outer_iters(*st), total = lockstep ? T : sliced_extra_rounds(T);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = solve_rounds(*st, lockstep ? 0 : SLICE_BUDGET, total, f_work, g_work, s, [&] {
+    return solve_generic(*st, f_work, g_work, s, [&] {
         return icnn_be::launch_conv_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
     });
-    return e == hipSuccess ? total : fail(e);
 }
 
 /* ---- FICNN (be_ficnn.hip, be_train_ficnn.hip) ---- */
@@ -813,8 +803,7 @@ int icnn_be_ficnn_context(const icnn_be_ficnn_model *model, const float *x, int 
     if (!model || !x || !ctx || !work || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_ficnn_context(*model, x, batch, ctx, work, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_ficnn_context(*model, x, batch, ctx, work, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_ficnn_fg(const icnn_be_ficnn_model *model, const float *ctx, const double *y, int batch, float *f, float *g,
@@ -822,19 +811,16 @@ int icnn_be_ficnn_fg(const icnn_be_ficnn_model *model, const float *ctx, const d
     if (!model || !ctx || !y || !f || !g || batch < 0 || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_ficnn_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_ficnn_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_ficnn_gd(const icnn_be_ficnn_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                      double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
-    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
     if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
     if (batch == 0) return 0;
-    hipError_t e = icnn_be::launch_ficnn_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
-                                            static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_ficnn_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
+                                         static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_solve_ficnn(const icnn_be_ficnn_model *model, const float *ctx, const icnn_be_state *st, float *f_work,
@@ -845,15 +831,10 @@ int icnn_be_solve_ficnn(const icnn_be_ficnn_model *model, const float *ctx, cons
     if (st->flags & ICNN_BE_FLAG_F64_ENERGY) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
     if (st->batch == 0) return 0;
-    /* the scheduling of icnn_be_solve_conv: lockstep rounds unless time slicing is asked for */
-    const bool lockstep = (st->flags & ICNN_BE_FLAG_LOCKSTEP) || st->variant == ICNN_BE_VARIANT_PDIPM ||
-                          !(st->flags & ICNN_BE_FLAG_TIME_SLICE);
-    const int T = outer_iters(*st), total = lockstep ? T : sliced_extra_rounds(T);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = solve_rounds(*st, lockstep ? 0 : SLICE_BUDGET, total, f_work, g_work, s, [&] {
+    return solve_generic(*st, f_work, g_work, s, [&] {
         return icnn_be::launch_ficnn_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s);
     });
-    return e == hipSuccess ? total : fail(e);
 }
 
 size_t icnn_be_ficnn_grad_floats(const icnn_be_ficnn_model *model) {
@@ -871,29 +852,25 @@ int icnn_be_ficnn_surrogate_grad(const icnn_be_ficnn_model *model, const float *
                                  void *stream) {
     if (!model || !x || !row_offset || !y || !cvec || !grad || !work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::ficnn_surrogate_shape(*model, batch, rows, v != nullptr)) return rc;
-    hipError_t e = icnn_be::launch_ficnn_surrogate_grad(*model, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
-                                                        static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_ficnn_surrogate_grad(*model, x, batch, row_offset, rows, y, v, cvec, grad, F_rows, work,
+                                                     static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {
     if (int rc = check_param_update(a)) return rc;
-    hipError_t e = icnn_be::launch_param_update(*a, nullptr, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_param_update(*a, nullptr, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_param_update_gated(const icnn_be_param_update_args *a, const int *go, void *stream) {
     if (!go) return ICNN_BE_EINVAL;
     if (int rc = check_param_update(a)) return rc;
-    hipError_t e = icnn_be::launch_param_update(*a, go, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_param_update(*a, go, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_gated_copy(float *dst, const float *src, long long n, const int *go, int want, void *stream) {
     if (!dst || !src || !go || n < 0) return ICNN_BE_EINVAL;
     if (n == 0) return 0;
-    hipError_t e = icnn_be::launch_gated_copy(dst, src, n, go, want, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_gated_copy(dst, src, n, go, want, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, const float *rew, const unsigned char *term,
@@ -917,8 +894,7 @@ int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, co
         return ICNN_BE_EINVAL;
     const icnn_be::RlTdLaunch l{batch, n, e_critic, act, rew, term, q2_src, act2, discount, theta, n_theta, decay,
                                 l2norm, wd, td, c, loss, work};
-    hipError_t e = icnn_be::launch_rl_td(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_rl_td(l, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
@@ -931,15 +907,13 @@ int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
     if (!(a->tau >= 0.f && a->tau <= 1.f) || !(a->l2norm >= 0.f) || !(a->wd >= 0.f) || !std::isfinite(a->l2norm) ||
         !std::isfinite(a->wd))
         return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_rl_critic_update(*a, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_rl_critic_update(*a, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {
     if (int rc = check_replay(m)) return rc;
     if (!stage || reinterpret_cast<uintptr_t>(stage) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    hipError_t e = icnn_be::launch_replay_enqueue(*m, stage, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_replay_enqueue(*m, stage, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
@@ -952,8 +926,7 @@ int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned
         if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
     if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
     const icnn_be::ReplaySampleLaunch l{*m, batch, seed, obs, act, rew, ob2, term, idx};
-    hipError_t e = icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : fail(e);
+    return done(icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int WAVE = 64;
+constexpr int LDS_BYTES = 160 * 1024;     // the LDS of one workgroup on gfx950
 
 // threadIdx.x through an opaque move.  Inside the round loop of a persistent kernel everything derived from the thread
 // index (lane, wave, MFMA fragment coordinates, LDS offsets) is loop invariant: the optimiser hoists it in front of

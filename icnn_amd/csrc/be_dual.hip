@@ -248,7 +248,7 @@ int dual_rows_fit(int n, int slots, int cut_dtype, int variant) {
     while (rows > 0) {
         const int b = dual_lds_bytes(n, slots, cut_dtype, variant, rows);
         if (b < 0) return 0;
-        if (b <= 160 * 1024) break;
+        if (b <= LDS_BYTES) break;
         --rows;
     }
     return rows;
@@ -291,13 +291,13 @@ bool choose_dual_step(const DualArgs &a, DualStepLaunch &c) {
             return carve(32, rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, waves, true, ipm, true).total;
         };
         c.lds = staged_lds(c.rows, c.waves);
-        if (c.lds > 160 * 1024 && c.waves > 1) {
+        if (c.lds > LDS_BYTES && c.waves > 1) {
             // the per-wave systems of an eight-wave sample do not fit next to the column buffers (interior point: five of
             // them; n_pad = 3072 from 23 rows on): the one-wave instance of the same body, whose carve-up has none
             c.waves = 1;
             c.lds = staged_lds(c.rows, 1);
         }
-        if (c.lds > 160 * 1024) return false;
+        if (c.lds > LDS_BYTES) return false;
         if (f64) {
             c.kern = ipm ? dual_step_kernel<double, 32, 1, false, true, true> : dual_step_kernel<double, 32, 1, false, false, true>;
         } else if (ipm) {
@@ -309,7 +309,7 @@ bool choose_dual_step(const DualArgs &a, DualStepLaunch &c) {
                 // of its WIDE_LR oldest rows, or for the plain device-memory body of a larger one
                 const int lds_b = ((staged_lds(c.rows < HV_KMAX ? c.rows : HV_KMAX, c.waves) + 15) & ~15) + WIDE_LR * a.ldA * 4;
                 const int lds_w = lds_b > c.lds ? lds_b : c.lds;
-                if (lds_w <= 160 * 1024) {
+                if (lds_w <= LDS_BYTES) {
                     c.kern = dual_step_wide_kernel;
                     c.lds = lds_w;
                 }
@@ -352,7 +352,7 @@ hipError_t launch_implicit_feed(const icnn_be_state &st, const double *y_true, i
     const int KT = big ? 32 : 16, cb = f64 ? 8 : 4;     // (one wave per sample here)
     int lds = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false).total;
     void (*kern)(FeedArgs);
-    if (lds > 160 * 1024) {              // wide rows with more slots than LDS rows: the staging area in device memory
+    if (lds > LDS_BYTES) {              // wide rows with more slots than LDS rows: the staging area in device memory
         if (!st.scratch || scratch_bytes(st) == 0) return hipErrorInvalidValue;
         lds = carve(KT, st.slots, a.ldA, a.n_pad, cb, a.plan.n_leaves, false, 1, true, false, true).total;
         kern = f64 ? (big ? implicit_feed_kernel<double, 32, true> : implicit_feed_kernel<double, 16, true>)

@@ -3,7 +3,8 @@
 //                       v_mfma_f32_16x16x4_f32 against pre-packed B fragments, ReLU masks recovered from the signs of the
 //                       stored activations (the design of fc_fg_tile, DESIGN.md §4, without gate or yu operands)
 //     ficnn_gd_kernel   unrolled momentum GD: a persistent workgroup per tile alternating phase A (the fg tile) and phase B
-//                       (the float32 update of be_gd.hip, one wave per sample), plus a final phase A for E(y_K)
+//                       (the float32 update, one wave per sample), plus a final phase A for E(y_K): the tile loop of
+//                       be_gd_dev.h that gd_fc_kernel (be_gd.hip) instantiates too, set up by the same gd_fill_args
 //     the context       c_i = x Wx_i + b_i of every evaluated layer: one f32-MFMA GEMM (launch_tr_gemm) and a bias row
 // Every float32 operation of the tile is written out (no contraction), so the same inputs give the same bits on every call
 // and the GD loop is bit-identical to a loop of ficnn fg launches plus the update.
@@ -13,6 +14,7 @@
 #include <cstring>
 
 #include "be_ficnn_dev.h"
+#include "be_gd_dev.h"
 #include "be_train_common.h"
 
 namespace icnn_be {
@@ -207,91 +209,19 @@ __global__ __launch_bounds__(NTHREADS) void ficnn_fg_kernel(FicnnArgs a) {
     ficnn_fg_tile(a, blockIdx.x, lds);
 }
 
-// ---- unrolled momentum GD (be_gd.hip's recurrence and recipe) ----
-struct FicnnGdArgs {
-    FicnnArgs fa;          // fa.y = y (the iterate), fa.g = per-iteration dE/dy, fa.f = f_out or scratch
-    const double *y0;
-    double *y;
-    float *v;
-    double *traj;
-    float *f_out;
-    int n_iter;
-    float lr, mu, c1;      // float32(lr), float32(mu), float32(1.0 + mu)
+// ---- unrolled momentum GD: the tile loop of be_gd_dev.h around ficnn_fg_tile ----
+struct FicnnTile {
+    template <typename A>
+    static __device__ __forceinline__ void run(const A &fa, int tile, float *lds) { ficnn_fg_tile(fa, tile, lds); }
 };
+typedef GdTileArgs<FicnnArgs> FicnnGdArgs;
 
-__device__ __forceinline__ void gd_step(float &y, float &v, float g, float lr, float mu, float c1) {
-#pragma clang fp contract(off)
-    const float mv = mu * v;
-    const float vn = mv - lr * g;
-    y = (y - mv) + c1 * vn;
-    v = vn;
-}
-
-// Phase A reads its arguments from the kernel-argument segment and is inlined into the iteration loop, with the thread
-// index read opaquely and -mllvm -disable-machine-licm for this unit (build.py): the recipe of be_gd.hip
-typedef const __attribute__((address_space(4))) FicnnGdArgs KArgs;
-__device__ __forceinline__ void phase_fg(KArgs *kp, int tile) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    asm volatile("" : "+s"(kp), "+s"(tile));
-    ficnn_fg_tile(kp->fa, tile, lds);
-}
-
-__device__ __forceinline__ void phase_update(KArgs *kp, int tile, int k) {
-#pragma clang fp contract(off)
-    asm volatile("" : "+s"(kp), "+s"(tile), "+s"(k));
-    const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-    const int n = kp->fa.n, u = tile * TM + wave;
-    if (u >= kp->fa.batch) return;
-    const size_t row = (size_t)u * n;
-    double *traj = kp->traj ? kp->traj + ((size_t)u * kp->n_iter + k) * n : nullptr;
-    const float lr = kp->lr, mu = kp->mu, c1 = kp->c1;
-    for (int j = lane; j < n; j += 64) {
-        float y = (float)kp->y[row + j], v = kp->v[row + j];
-        if (traj) traj[j] = (double)y;
-        gd_step(y, v, kp->fa.g[row + j], lr, mu, c1);
-        kp->y[row + j] = (double)y;
-        kp->v[row + j] = v;
-    }
-}
-
-__global__ __launch_bounds__(NTHREADS) void ficnn_gd_kernel(FicnnGdArgs a) {
-#pragma clang fp contract(off)
-    KArgs *kp = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-    const int tile = blockIdx.x;
-    {
-        const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-        const int n = a.fa.n, u = tile * TM + wave;
-        if (u < a.fa.batch)
-            for (int j = lane; j < n; j += 64) {         // y_0 rounded to float32 like a feed
-                const size_t i = (size_t)u * n + j;
-                a.y[i] = (double)(float)a.y0[i];
-                a.v[i] = 0.f;
-            }
-    }
-    __syncthreads();
-    const int K = a.n_iter;
-    for (int k = 0; k < K; ++k) {
-        phase_fg(kp, tile);
-        __syncthreads();                                 // g of the tile visible to its update waves
-        phase_update(kp, tile, k);
-        __syncthreads();                                 // y_{k+1} visible to the tile's next phase A
-    }
-    if (a.f_out) phase_fg(kp, tile);                     // E(y_K) -> fa.f = f_out
-}
+__global__ __launch_bounds__(NTHREADS) void ficnn_gd_kernel(FicnnGdArgs a) { gd_tile_loop<FicnnTile>(a); }
 
 // ---- context: ctx = x Wx + b ----
 __global__ void ficnn_bias_kernel(float *ctx, const float *b, int C, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
         ctx[i] = ctx[i] + b[i % C];
-}
-
-// the workspace layout of icnn_be_gd_workspace_bytes (be_gd.hip): v, g, f, each 256-byte aligned
-void gd_workspace_parts(int batch, int n, size_t &v, size_t &g, size_t &f) {
-    const size_t b = (size_t)(batch > 0 ? batch : 1), bn = b * (size_t)n;
-    auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-    v = 0;
-    g = up(bn * 4);
-    f = g + up(bn * 4);
 }
 
 }  // namespace
@@ -358,17 +288,8 @@ hipError_t launch_ficnn_gd(const icnn_be_ficnn_model &m, const float *ctx, const
     FicnnGdArgs a{};
     int lds = 0;
     if (ficnn_fill_args(m, a.fa, lds) != 0) return hipErrorInvalidValue;
-    size_t ov, og, of;
-    gd_workspace_parts(batch, m.n, ov, og, of);
-    unsigned char *base = static_cast<unsigned char *>(ws);
-    a.y0 = y0; a.y = y_out; a.traj = traj; a.f_out = f_out; a.n_iter = n_iter;
-    a.v = reinterpret_cast<float *>(base + ov);
-    a.lr = (float)lr;
-    a.mu = (float)momentum;
-    a.c1 = (float)(1.0 + momentum);
-    a.fa.ctx = ctx; a.fa.y = y_out; a.fa.batch = batch; a.fa.finished = nullptr;
-    a.fa.g = reinterpret_cast<float *>(base + og);
-    a.fa.f = f_out ? f_out : reinterpret_cast<float *>(base + of);
+    gd_fill_args(a, y0, y_out, traj, f_out, n_iter, lr, momentum, ws, batch);
+    a.fa.ctx = ctx;
     return launch_kernel(ficnn_gd_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
 }
 

@@ -88,7 +88,7 @@ inline int ficnn_check(const icnn_be_ficnn_model &m) {
     if (c != m.ctx_width) return ICNN_BE_EINVAL;
     for (int i = 0; i <= L; ++i)
         if (((long long)m.n_features + m.n) * m.width[i] > INT_MAX || (long long)m.n_features * c > INT_MAX) return ICNN_BE_ELIMIT;
-    if ((long long)ficnn_lds(m).floats * 4 > 160 * 1024) return ICNN_BE_ELIMIT;
+    if ((long long)ficnn_lds(m).floats * 4 > LDS_BYTES) return ICNN_BE_ELIMIT;
     return 0;
 }
 

@@ -282,7 +282,7 @@ bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int p
     out.sample_bytes = (carve(st.slots > 15 ? 32 : 16, st.slots, ldA, n_pad, 4, plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
     out.crow_off = out.dual_off + per_wg * out.sample_bytes;
     out.lds = out.crow_off + ((2 * ldA * 4 + 15) & ~15);
-    return out.lds <= 160 * 1024;
+    return out.lds <= LDS_BYTES;
 }
 
 bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget, FusedTileLayout &out) {
@@ -302,11 +302,11 @@ bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int t
     out.crow_off = ((fg_bytes > dual_bytes ? fg_bytes : dual_bytes) + 15) & ~15;
     out.lds = out.crow_off + crow_bytes;
     out.grouped = out.group_cap = out.need_off = 0;
-    if (out.lds > 160 * 1024 || big) {
+    if (out.lds > LDS_BYTES || big) {
         // the sixteen full-size bundles do not fit together: groups sized by what the samples hold (FusedArgs::grouped).
         // The staging region takes everything the workgroup can have; one sample's largest bundle must fit it.
         const int need_bytes = 2 * TM * 4;            // per sample: bytes needed this round, and its done flag
-        out.crow_off = (160 * 1024 - 1024 - crow_bytes - need_bytes) & ~15;      // (1 KB: the kernel's static LDS, 256 B today)
+        out.crow_off = (LDS_BYTES - 1024 - crow_bytes - need_bytes) & ~15;      // (1 KB: the kernel's static LDS, 256 B today)
         if (out.crow_off < fg_bytes || out.crow_off < out.sample_bytes) return false;
         out.grouped = 1; out.group_cap = out.crow_off; out.need_off = out.crow_off + crow_bytes;
         out.lds = out.need_off + need_bytes;

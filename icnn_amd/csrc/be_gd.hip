@@ -7,94 +7,31 @@
 // float32(1.0 + mu) with the sum formed in double.  (At k = 0 the reference's mu*v_0 is the Python 0.0 times mu, the same
 // value as mu * 0.f here, so the recurrence needs no special first step.)  No stopping rule and no coupling between samples:
 //     gd_fc_kernel    a persistent workgroup per 16-sample tile alternating phase A (fc_fg_tile) and phase B (one wave per
-//                     sample: the update above), y in the caller's y_out, v and g in the workspace
+//                     sample: the update above), y in the caller's y_out, v and g in the workspace: the tile loop of
+//                     be_gd_dev.h, which the FICNN's ficnn_gd_kernel (be_ficnn.hip) instantiates as well
 //     gd_rows_kernel  at most two samples per CU (the rule of launch_fc_fg): context rows, y and v in LDS for the whole loop
 //     gd_init_kernel / gd_update_kernel   the conv model's form: K rounds of the conv fg launches, each followed by the
 //                     elementwise update (same operations)
 // Both FC paths evaluate E and dE/dy with the operations of icnn_be_fc_fg, so the three forms agree bit for bit with a loop of
-// icnn_be_fc_fg plus this float32 update.
+// icnn_be_fc_fg plus this float32 update.  gd_step, the workspace layout and the float32 constants of every
+// form, the FICNN's included, are the ones of be_gd_dev.h; the layout and the constants are defined here.
 #include <cmath>
 
 #include "be_kernels.h"
-#include "be_picnn_fc_dev.h"
+#include "be_gd_dev.h"
 #include "be_picnn_fc_rows_dev.h"
 
 namespace icnn_be {
 
 namespace {
 
-struct GdArgs {
-    FcArgs fa;             // fa.y = y (the iterate), fa.g = per-iteration dE/dy, fa.f = f_out or scratch
-    const double *y0;      // [B][n] start (float32 values after rounding on entry)
-    double *y;             // [B][n] the iterate, y_K on exit (the caller's y_out)
-    float *v;              // [B][n] momentum (workspace)
-    double *traj;          // [B][K][n] y_0 .. y_{K-1}, or nullptr
-    float *f_out;          // [B] E(y_K), or nullptr: no final evaluation
-    int n_iter;
-    float lr, mu, c1;      // float32(lr), float32(mu), float32(1.0 + mu)
+struct FcTile {           // phase A of gd_tile_loop
+    template <typename A>
+    static __device__ __forceinline__ void run(const A &fa, int tile, float *lds) { fc_fg_tile(fa, tile, lds); }
 };
+typedef GdTileArgs<FcArgs> GdArgs;
 
-// One step of the recurrence for one element (shared by every path: the same float32 operations in the same order)
-__device__ __forceinline__ void gd_step(float &y, float &v, float g, float lr, float mu, float c1) {
-#pragma clang fp contract(off)
-    const float mv = mu * v;
-    const float vn = mv - lr * g;
-    y = (y - mv) + c1 * vn;
-    v = vn;
-}
-
-// Phase A reads its arguments from the kernel-argument segment and is inlined into the iteration loop, with the thread
-// index read opaquely (thread_id) and -mllvm -disable-machine-licm for this unit: the recipe of be_fused.hip / be_adam.hip
-typedef const __attribute__((address_space(4))) GdArgs KArgs;
-__device__ __forceinline__ void phase_fg(KArgs *kp, int tile) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    asm volatile("" : "+s"(kp), "+s"(tile));
-    fc_fg_tile(kp->fa, tile, lds);
-}
-
-// Phase B: wave w updates sample tile * TM + w (g from phase A through global memory, y and v in global memory)
-__device__ __forceinline__ void phase_update(KArgs *kp, int tile, int k) {
-#pragma clang fp contract(off)
-    asm volatile("" : "+s"(kp), "+s"(tile), "+s"(k));
-    const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-    const int n = kp->fa.n, u = tile * TM + wave;
-    if (u >= kp->fa.batch) return;
-    const size_t row = (size_t)u * n;
-    double *traj = kp->traj ? kp->traj + ((size_t)u * kp->n_iter + k) * n : nullptr;
-    const float lr = kp->lr, mu = kp->mu, c1 = kp->c1;
-    for (int j = lane; j < n; j += 64) {
-        float y = (float)kp->y[row + j], v = kp->v[row + j];
-        if (traj) traj[j] = (double)y;
-        gd_step(y, v, kp->fa.g[row + j], lr, mu, c1);
-        kp->y[row + j] = (double)y;
-        kp->v[row + j] = v;
-    }
-}
-
-__global__ __launch_bounds__(NTHREADS) void gd_fc_kernel(GdArgs a) {
-#pragma clang fp contract(off)
-    KArgs *kp = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-    const int tile = blockIdx.x;
-    {
-        const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-        const int n = a.fa.n, u = tile * TM + wave;
-        if (u < a.fa.batch)
-            for (int j = lane; j < n; j += 64) {         // y_0 rounded to float32 like a feed
-                const size_t i = (size_t)u * n + j;
-                a.y[i] = (double)(float)a.y0[i];
-                a.v[i] = 0.f;
-            }
-    }
-    __syncthreads();
-    const int K = a.n_iter;
-    for (int k = 0; k < K; ++k) {
-        phase_fg(kp, tile);
-        __syncthreads();                                 // g of the tile visible to its update waves
-        phase_update(kp, tile, k);
-        __syncthreads();                                 // y_{k+1} visible to the tile's next phase A
-    }
-    if (a.f_out) phase_fg(kp, tile);                     // E(y_K) -> fa.f = f_out
-}
+__global__ __launch_bounds__(NTHREADS) void gd_fc_kernel(GdArgs a) { gd_tile_loop<FcTile>(a); }
 
 struct GdRowsArgs {
     GdArgs a;
@@ -173,11 +110,10 @@ __global__ void gd_update_kernel(double *y, float *v, const float *g, double *tr
     v[i] = vk;
 }
 
-struct Workspace {
-    size_t v, g, f, total;
-};
-Workspace workspace(int batch, int n) {
-    Workspace w;
+}  // namespace
+
+GdWorkspace gd_workspace(int batch, int n) {
+    GdWorkspace w;
     const size_t b = (size_t)(batch > 0 ? batch : 1), bn = b * (size_t)n;
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
@@ -186,20 +122,13 @@ Workspace workspace(int batch, int n) {
     return w;
 }
 
-void constants(double lr, double momentum, GdArgs &a) {
-    a.lr = (float)lr;
-    a.mu = (float)momentum;
-    a.c1 = (float)(1.0 + momentum);
-}
+GdConstants gd_constants(double lr, double momentum) { return {(float)lr, (float)momentum, (float)(1.0 + momentum)}; }
 
-}  // namespace
-
-size_t gd_workspace_bytes(int batch, int n) { return workspace(batch, n).total; }
+size_t gd_workspace_bytes(int batch, int n) { return gd_workspace(batch, n).total; }
 
 bool gd_constants_ok(double lr, double momentum) {
-    GdArgs a{};
-    constants(lr, momentum, a);
-    return std::isfinite(lr) && std::isfinite(momentum) && std::isfinite(a.lr) && std::isfinite(a.mu) && std::isfinite(a.c1);
+    const GdConstants c = gd_constants(lr, momentum);
+    return std::isfinite(lr) && std::isfinite(momentum) && std::isfinite(c.lr) && std::isfinite(c.mu) && std::isfinite(c.c1);
 }
 
 hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
@@ -207,14 +136,8 @@ hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const doubl
     GdArgs a{};
     int lds = 0;
     if (fill_args(m, a.fa, lds) != 0) return hipErrorInvalidValue;
-    const Workspace w = workspace(batch, m.n);
-    unsigned char *base = static_cast<unsigned char *>(ws);
-    a.y0 = y0; a.y = y_out; a.traj = traj; a.f_out = f_out; a.n_iter = n_iter;
-    a.v = reinterpret_cast<float *>(base + w.v);
-    constants(lr, momentum, a);
-    a.fa.ctx = ctx; a.fa.y = y_out; a.fa.batch = batch; a.fa.finished = nullptr; a.fa.prof = fc_profile_buffer();
-    a.fa.g = reinterpret_cast<float *>(base + w.g);
-    a.fa.f = f_out ? f_out : reinterpret_cast<float *>(base + w.f);
+    gd_fill_args(a, y0, y_out, traj, f_out, n_iter, lr, momentum, ws, batch);
+    a.fa.ctx = ctx; a.fa.prof = fc_profile_buffer();
     // at most two samples per CU: a workgroup per one or two samples on the VALU path (launch_fc_fg's rule)
     const int cus = device_cus();
     const int per_wg = (batch + cus - 1) / cus;
@@ -222,7 +145,7 @@ hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const doubl
         GdRowsArgs r{};
         const int rows_bytes = rows_layout(m, per_wg, r.lay);
         const int yv_bytes = per_wg * 2 * pad16(m.n) * 4;
-        if (rows_bytes + yv_bytes <= 160 * 1024) {
+        if (rows_bytes + yv_bytes <= LDS_BYTES) {
             r.a = a;
             r.per_wg = per_wg;
             r.yv_off = rows_bytes / 4;
@@ -230,16 +153,15 @@ hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const doubl
                                  stream, r);
         }
     }
-    if (lds > 160 * 1024) return hipErrorNotSupported;
+    if (lds > LDS_BYTES) return hipErrorNotSupported;
     return launch_kernel(gd_fc_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
 }
 
 hipError_t launch_conv_gd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                           double momentum, double *y_out, double *traj, float *f_out, void *ws, hipStream_t stream) {
-    GdArgs c{};
-    constants(lr, momentum, c);
+    const GdConstants c = gd_constants(lr, momentum);
     const int n = m.H * m.W;
-    const Workspace w = workspace(batch, n);
+    const GdWorkspace w = gd_workspace(batch, n);
     unsigned char *base = static_cast<unsigned char *>(ws);
     float *v = reinterpret_cast<float *>(base + w.v), *g = reinterpret_cast<float *>(base + w.g);
     float *f = f_out ? f_out : reinterpret_cast<float *>(base + w.f);

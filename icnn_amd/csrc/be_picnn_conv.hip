@@ -633,7 +633,7 @@ int conv_layout(const icnn_be_conv_model &m, ConvLayout &L) {
     L.lds_fwd = 4 * (2 * simg + 2 * r4(sm1) + 2 * r4(sm2) + r4(map_floats(sm1, a.F[0])) + r4(map_floats(sm2, a.F[1])));
     L.lds_bwd = 4 * (r4(map_floats(sm3, a.F[2])) + r4(map_floats(sm2, a.F[1])) + r4(map_floats(sm1, a.F[0])) + r4(sm2) + r4(sm1));
     L.lds_fcb = 4 * 16 * (a.fch + 8);
-    if (L.lds_fwd > 160 * 1024 || L.lds_bwd > 160 * 1024 || L.lds_fcb > 160 * 1024) return ICNN_BE_ELIMIT;
+    if (L.lds_fwd > LDS_BYTES || L.lds_bwd > LDS_BYTES || L.lds_fcb > LDS_BYTES) return ICNN_BE_ELIMIT;
     a.wpack = m.wpack;
     return 0;
 }

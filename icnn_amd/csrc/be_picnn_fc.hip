@@ -90,7 +90,7 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
         FgRowsArgs r{};
         const int per_wg = (batch + cus - 1) / cus;
         const int rows_lds = rows_layout(m, per_wg <= 2 ? per_wg : 1, r.lay);
-        if (per_wg <= 2 && rows_lds <= 160 * 1024) {        // at most two samples per CU
+        if (per_wg <= 2 && rows_lds <= LDS_BYTES) {        // at most two samples per CU
             r.fa = a;
             r.per_wg = per_wg;
             return launch_kernel(fc_fg_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_lds, stream, r);

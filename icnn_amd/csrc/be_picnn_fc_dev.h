@@ -528,7 +528,7 @@ inline int fill_args(const icnn_be_fc_model &m, FcArgs &a, int &lds_bytes) {
     a.dl_off = lo; lo += TM * a.zb_ld[L - 1];
     a.lds_floats = lo;
     lds_bytes = lo * 4;
-    if (lds_bytes > 160 * 1024) return ICNN_BE_ELIMIT;
+    if (lds_bytes > LDS_BYTES) return ICNN_BE_ELIMIT;
     a.wpack = m.wpack;
     return 0;
 }
