@@ -38,6 +38,8 @@ FLAG_MFMA_CONTRACTION = 256
 LOSS = {"xent": 0, "mse": 1}
 # ICNN_BE_PATH_*: how icnn_be_solve_fc runs a solve (icnn_be_debug_solve_plan)
 PATHS = ["ROWS", "TILE", "TILE_BUDGETED_THEN_ROWS", "ROUNDS_LOCKSTEP", "ROUNDS_SLICED_THEN_ROWS", "ROUNDS_SLICED_EXTRA"]
+# ICNN_BE_ADAM_*: which kernel icnn_be_adam_fc launches (icnn_be_debug_adam_plan)
+ADAM_KERNELS = ["NONE", "ROWS", "TILE"]
 ERRORS = {-1: "ICNN_BE_EINVAL (bad argument)", -2: "ICNN_BE_ELIMIT (size beyond a compiled-in limit)",
           -3: "ICNN_BE_ELAUNCH (HIP launch failed)"}
 
@@ -50,7 +52,7 @@ EXPORTS = [
     "icnn_be_fc_context_work_floats", "icnn_be_fc_context", "icnn_be_fc_context_stage", "icnn_be_fc_context_norm", "icnn_be_fc_clamp",
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
-    "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan",
+    "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
@@ -244,6 +246,8 @@ def load():
     lib.icnn_be_debug_solve_plan.argtypes = [C.POINTER(FcModel), C.POINTER(State), C.c_int, C.POINTER(C.c_int * 3)]
     lib.icnn_be_debug_solve_plan.restype = C.c_int
     lib.icnn_be_debug_profile_phases.restype = C.c_int
+    lib.icnn_be_debug_adam_plan.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx), C.c_int, C.POINTER(C.c_int * 4)]
+    lib.icnn_be_debug_adam_plan.restype = C.c_int
     lib.icnn_be_adam_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_adam_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
@@ -419,3 +423,14 @@ def solve_plan(model, state, cus=0):
     if rc < 0:
         check(rc, "icnn_be_debug_solve_plan")
     return (PATHS[rc],) + tuple(out)
+
+
+def adam_plan(model, batch, ctx=None):
+    """(kernel name, states per workgroup, workgroups, cooperative, obs form accepted) of icnn_be_adam_fc for an FcModel and
+    a batch on the current device (icnn_be_debug_adam_plan); `ctx`: the FcCtx icnn_be_adam_fc_obs would get, for the last
+    entry (False without one).  Enqueues nothing; asks the runtime for the kernels' occupancy, so it needs a device."""
+    out = (C.c_int * 4)()
+    rc = load().icnn_be_debug_adam_plan(C.byref(model), C.byref(ctx) if ctx is not None else None, int(batch), C.byref(out))
+    if rc < 0:
+        check(rc, "icnn_be_debug_adam_plan")
+    return (ADAM_KERNELS[rc], out[0], out[1], bool(out[2]), bool(out[3]))

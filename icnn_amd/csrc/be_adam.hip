@@ -305,6 +305,78 @@ Workspace workspace(int batch, int n) {
 
 size_t adam_workspace_bytes(int batch, int n) { return workspace(batch, n).total; }
 
+namespace {
+
+// What launch_adam_fc does with a model and a batch, decided in ONE place (icnn_be_debug_adam_plan reports it; results are
+// bit-identical whichever kernel runs).  dim(action) <= 64 with at most ROWS_MAX states per resident workgroup: the latency
+// path (adam_rows_kernel, everything in LDS and registers), as few states per workgroup as keep all workgroups resident;
+// otherwise 16-state MFMA tiles (adam_fc_kernel).  One workgroup is an ordinary launch, several a cooperative one: the
+// stopping rule needs them all resident, and ICNN_BE_ADAM_NONE says they would not be.  With `cx` the plan also says
+// whether the observations can take the place of the context rows: latency path only, a model without BatchNorm, the
+// producer's scratch inside the row's operand region.  Enqueues nothing; with more than ROWS_MAX states it asks the
+// runtime how many workgroups fit a CU (and raises the kernel's dynamic-LDS limit first, as the launch would).
+struct AdamLaunch {
+    AdamPlan plan;
+    int lds;              // dynamic LDS bytes of the launch
+    RowsLayout lay;       // the latency path's
+};
+
+hipError_t plan_adam(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, FcArgs &fa, AdamLaunch &p) {
+    p = AdamLaunch{};
+    int lds = 0;
+    if (fill_args(m, fa, lds) != 0) return hipErrorInvalidValue;
+    if (m.n <= 64) {   // latency path: 1-4 states per workgroup, as many workgroups as fit
+        const int rows_lds = rows_layout(m, ROWS_MAX, p.lay) + (ROWS_MAX + 1) * 8;
+        int resident = 1;
+        if (rows_lds <= LDS_BYTES && batch > ROWS_MAX) {      // more than one workgroup: they must all be resident
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
+            int per_cu = 0;
+            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_rows_kernel),
+                                                                        RTHREADS, rows_lds);
+            if (e != hipSuccess) return e;
+            resident = per_cu * device_cus();
+        }
+        const int per_wg = batch <= ROWS_MAX ? batch : (batch + resident - 1) / (resident > 0 ? resident : 1);
+        if (rows_lds <= LDS_BYTES && per_wg >= 1 && per_wg <= ROWS_MAX) {
+            const int wgs = (batch + per_wg - 1) / per_wg;
+            p.plan = {ICNN_BE_ADAM_ROWS, per_wg, wgs, wgs > 1, 0};
+            p.lds = rows_lds;
+            if (cx && !cx->batchnorm && cx->n == m.n && cx->n_layers == m.n_layers) {
+                for (int i = 0; i < m.n_layers; ++i)           // (icnn_be_adam_fc_obs has refused these already: the stage matrices
+                    if (cx->width[i] != m.width[i]) return hipErrorInvalidValue;   //  are laid out for cx's widths, read with m's)
+                int wmax = cx->n_features;
+                for (int i = 0; i + 1 < m.n_layers; ++i) wmax = m.width[i] > wmax ? m.width[i] : wmax;
+                p.plan.obs_ok = 2 * wmax <= p.lay.ctx_off;                      // scratch = the row's operand region
+            }
+            return hipSuccess;
+        }
+    }
+    const int tiles = (batch + TM - 1) / TM;
+    lds = ((fa.lds_floats + 3) & ~3) * 4 + (NWAVE + 1) * 8;     // the reduction scratch behind fc_fg_tile's LDS
+    if (lds > LDS_BYTES) return hipSuccess;                     // ICNN_BE_ADAM_NONE
+    p.lds = lds;
+    if (tiles > 1) {
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_fc_kernel), lds); e != hipSuccess) return e;
+        int per_cu = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_fc_kernel),
+                                                                    NTHREADS, lds);
+        if (e != hipSuccess) return e;
+        if (tiles > per_cu * device_cus()) return hipSuccess;   // ICNN_BE_ADAM_NONE
+    }
+    p.plan = {ICNN_BE_ADAM_TILE, TM, tiles, tiles > 1, 0};
+    return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan) {
+    FcArgs fa{};
+    AdamLaunch p;
+    const hipError_t e = plan_adam(m, cx, batch, fa, p);
+    plan = p.plan;
+    return e;
+}
+
 // hipErrorNotSupported: more tiles than a cooperative launch can keep resident (the stopping rule needs them all)
 // `cx` + `obs` instead of `ctx`: observation -> action in ONE launch (latency path only: at most ROWS_MAX states per
 // workgroup, a model without BatchNorm); hipErrorNotSupported otherwise -- the caller produces the context first.
@@ -312,8 +384,9 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
                           float *f_best, int *iters, void *ws, hipStream_t stream, const icnn_be_fc_ctx *cx,
                           const float *obs) {
     AdamArgs a{};
-    int lds = 0;
-    if (fill_args(m, a.fa, lds) != 0) return hipErrorInvalidValue;
+    AdamLaunch p;
+    if (hipError_t e = plan_adam(m, obs ? cx : nullptr, batch, a.fa, p); e != hipSuccess) return e;
+    if (p.plan.kernel == ICNN_BE_ADAM_NONE || (obs && !p.plan.obs_ok)) return hipErrorNotSupported;
     const Workspace w = workspace(batch, m.n);
     unsigned char *base = static_cast<unsigned char *>(ws);
     a.act = reinterpret_cast<double *>(base + w.act);
@@ -326,60 +399,29 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
     a.fa.f = reinterpret_cast<float *>(base + w.f);
     a.act_best = act_best; a.f_best = f_best; a.iters = iters;
     a.max_iter = max_iter;
-    a.tiles = (batch + TM - 1) / TM;
-    if (m.n <= 64) {   // latency path (everything in LDS and registers): 1-4 states per workgroup, as many workgroups as fit
+    a.tiles = p.plan.workgroups;
+    if (p.plan.cooperative)
+        if (hipError_t e = hipMemsetAsync(a.arrive, 0, sizeof(unsigned) * a.tiles, stream); e != hipSuccess) return e;
+    if (p.plan.kernel == ICNN_BE_ADAM_ROWS) {
         RowsArgs r{};
-        const int rows_lds = rows_layout(m, ROWS_MAX, r.lay) + (ROWS_MAX + 1) * 8;
-        int resident = 1;
-        if (rows_lds <= LDS_BYTES && batch > ROWS_MAX) {      // more than one workgroup: they must all be resident
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
-            int per_cu = 0;
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_rows_kernel),
-                                                                        RTHREADS, rows_lds);
-            if (e != hipSuccess) return e;
-            resident = per_cu * device_cus();
+        r.a = a;
+        r.lay = p.lay;
+        r.per_wg = p.plan.per_wg;
+        if (obs) {
+            r.cr.obs = obs;
+            r.cr.n_features = cx->n_features;
+            for (int i = 0; i < m.n_layers; ++i) { r.cr.w_stage[i] = cx->w_stage[i]; r.cr.b_stage[i] = cx->b_stage[i]; }
         }
-        const int per_wg = batch <= ROWS_MAX ? batch : (batch + resident - 1) / (resident > 0 ? resident : 1);
-        if (rows_lds <= LDS_BYTES && per_wg >= 1 && per_wg <= ROWS_MAX) {
-            r.a = a;
-            r.per_wg = per_wg;
-            if (obs) {
-                if (!cx || cx->batchnorm || cx->n != m.n || cx->n_layers != m.n_layers) return hipErrorNotSupported;
-                for (int i = 0; i < m.n_layers; ++i)           // (icnn_be_adam_fc_obs has refused these already: the stage matrices
-                    if (cx->width[i] != m.width[i]) return hipErrorInvalidValue;   //  are laid out for cx's widths, read with m's)
-                int wmax = cx->n_features;
-                for (int i = 0; i + 1 < m.n_layers; ++i) wmax = m.width[i] > wmax ? m.width[i] : wmax;
-                if (2 * wmax > r.lay.ctx_off) return hipErrorNotSupported;      // scratch = the row's operand region
-                r.cr.obs = obs;
-                r.cr.n_features = cx->n_features;
-                for (int i = 0; i < m.n_layers; ++i) { r.cr.w_stage[i] = cx->w_stage[i]; r.cr.b_stage[i] = cx->b_stage[i]; }
-            }
-            r.a.tiles = (batch + per_wg - 1) / per_wg;
-            if (r.a.tiles == 1) return launch_kernel(adam_rows_kernel, dim3(1), dim3(RTHREADS), rows_lds, stream, r);
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
-            hipError_t e = hipMemsetAsync(r.a.arrive, 0, sizeof(unsigned) * r.a.tiles, stream);
-            if (e != hipSuccess) return e;
-            void *params[] = {&r};
-            return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_rows_kernel), dim3(r.a.tiles),
-                                              dim3(RTHREADS), params, (unsigned)rows_lds, stream);
-        }
+        if (!p.plan.cooperative) return launch_kernel(adam_rows_kernel, dim3(1), dim3(RTHREADS), p.lds, stream, r);
+        void *params[] = {&r};
+        return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_rows_kernel), dim3(a.tiles), dim3(RTHREADS),
+                                          params, (unsigned)p.lds, stream);
     }
-    if (obs) return hipErrorNotSupported;
     a.red_off = (a.fa.lds_floats + 3) & ~3;
-    lds = a.red_off * 4 + (NWAVE + 1) * 8;
-    if (lds > LDS_BYTES) return hipErrorNotSupported;
-    if (a.tiles == 1) return launch_kernel(adam_fc_kernel, dim3(1), dim3(NTHREADS), lds, stream, a);
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_fc_kernel), lds); e != hipSuccess) return e;
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_fc_kernel),
-                                                                NTHREADS, lds);
-    if (e != hipSuccess) return e;
-    if (a.tiles > per_cu * device_cus()) return hipErrorNotSupported;
-    e = hipMemsetAsync(a.arrive, 0, sizeof(unsigned) * a.tiles, stream);
-    if (e != hipSuccess) return e;
+    if (!p.plan.cooperative) return launch_kernel(adam_fc_kernel, dim3(1), dim3(NTHREADS), p.lds, stream, a);
     void *params[] = {&a};
-    return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_fc_kernel), dim3(a.tiles), dim3(NTHREADS),
-                                      params, (unsigned)lds, stream);
+    return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_fc_kernel), dim3(a.tiles), dim3(NTHREADS), params,
+                                      (unsigned)p.lds, stream);
 }
 
 }  // namespace icnn_be

@@ -546,6 +546,21 @@ int icnn_be_adam_fc(const icnn_be_fc_model *model, const float *ctx, int batch, 
     return done(e);
 }
 
+int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]) {
+    if (!model || !out || batch < 1 || model->action_box) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (cx) {                                          /* what icnn_be_adam_fc_obs refuses */
+        if (int rc = icnn_be::ctx_check(*cx)) return rc;
+        if (cx->u_last_relu || cx->n != model->n || cx->n_layers != model->n_layers) return ICNN_BE_EINVAL;
+        for (int i = 0; i < model->n_layers; ++i)
+            if (cx->width[i] != model->width[i]) return ICNN_BE_EINVAL;
+    }
+    icnn_be::AdamPlan p{};
+    if (hipError_t e = icnn_be::adam_fc_plan(*model, cx, batch, p); e != hipSuccess) return fail(e);
+    out[0] = p.per_wg; out[1] = p.workgroups; out[2] = p.cooperative; out[3] = p.obs_ok;
+    return p.kernel;
+}
+
 int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, const float *obs, int batch, int max_iter,
                         double *act_best, float *f_best, int *iters, void *workspace, void *stream) {
     if (!model || !cx || !obs || !act_best || !f_best || !iters || !workspace || !model->wpack) return ICNN_BE_EINVAL;

@@ -209,6 +209,16 @@ size_t adam_workspace_bytes(int batch, int n);
 hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch, int max_iter, double *act_best,
                           float *f_best, int *iters, void *workspace, hipStream_t stream,
                           const icnn_be_fc_ctx *cx = nullptr, const float *obs = nullptr);
+// The launch of launch_adam_fc for a model and a batch (icnn_be_debug_adam_plan); launch_adam_fc launches from exactly this.
+// With `cx`, obs_ok: the observation form is accepted (else hipErrorNotSupported).  Enqueues nothing.
+struct AdamPlan {
+    int kernel;        // ICNN_BE_ADAM_ROWS, ICNN_BE_ADAM_TILE, or ICNN_BE_ADAM_NONE: hipErrorNotSupported
+    int per_wg;        // states per workgroup
+    int workgroups;
+    int cooperative;   // several workgroups: all resident, the stopping rule's sum goes through a grid exchange
+    int obs_ok;
+};
+hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan);
 
 // Unrolled momentum gradient descent on y (be_gd.hip): the FC form is one launch (persistent tiles or the per-sample rows
 // path), the conv form 1 + K (+1) rounds of launches.  hipErrorNotSupported: the model's tile does not fit the LDS.

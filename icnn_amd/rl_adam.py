@@ -50,10 +50,12 @@ class AdamSolver:
 
     def solve_obs(self, obs: torch.Tensor):
         """Observation -> action in ONE launch (`icnn_be_adam_fc_obs`): the x-only context rows are computed inside the
-        Adam kernel.  Latency path only (at most four states per workgroup, no BatchNorm); returns None when the shape is
-        outside it -- the caller then uses `solve(model.context(obs))`."""
+        Adam kernel.  Latency path only (at most four states per workgroup, no BatchNorm, the last u-layer linear); returns
+        None when the model or the shape is outside it -- the caller then uses `solve(model.context(obs))`."""
         obs = obs.to(self.model.device, torch.float32).contiguous()
         assert obs.shape == (self.batch, self.model.spec.n_features)
+        if self.model.spec.relu_last_u:                    # the in-kernel producer keeps the last u-layer linear: the library
+            return None                                    # refuses such a context description as a bad argument
         stream = torch.cuda.current_stream(obs.device).cuda_stream
         rc = self.lib.icnn_be_adam_fc_obs(C.byref(self.model.c_model), C.byref(self.model.c_ctx), obs.data_ptr(), self.batch,
                                           self.max_iter, self.act_best.data_ptr(), self.f_best.data_ptr(),

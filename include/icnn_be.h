@@ -82,6 +82,11 @@ extern "C" {
 #define ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS 4  /* nIter time-sliced rounds + one finishing per-sample launch */
 #define ICNN_BE_PATH_ROUNDS_SLICED_EXTRA 5      /* nIter time-sliced rounds + nIter unbudgeted rounds for the stragglers */
 
+/* which kernel icnn_be_adam_fc launches (icnn_be_debug_adam_plan) */
+#define ICNN_BE_ADAM_NONE 0                     /* none: more workgroups than stay resident, or no layout fits (ICNN_BE_ELIMIT) */
+#define ICNN_BE_ADAM_ROWS 1                     /* the latency path: 1-4 states per workgroup, state in LDS and registers */
+#define ICNN_BE_ADAM_TILE 2                     /* 16-state MFMA tiles */
+
 /* return codes */
 #define ICNN_BE_EINVAL (-1)    /* bad argument */
 #define ICNN_BE_ELIMIT (-2)    /* size beyond a compiled-in limit */
@@ -1128,6 +1133,16 @@ ICNN_BE_API void icnn_be_debug_profile_conv(long long *device_buf);
  * ICNN_BE_EINVAL, nothing is planned).  Host arithmetic only: needs neither a GPU nor any buffer of the model or the state.
  */
 ICNN_BE_API int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state *st, int cus, int out[3]);
+/*
+ * The launch icnn_be_adam_fc makes for this model and batch on the current device: returns an ICNN_BE_ADAM_* code and fills
+ * out = { states per workgroup, workgroups, 1 if the launch is cooperative (several workgroups, all resident), 1 if
+ * icnn_be_adam_fc_obs accepts this model with the context description cx (0 with cx == NULL, and wherever that entry answers
+ * ICNN_BE_ELIMIT) }; ICNN_BE_ADAM_NONE (out all zero) where icnn_be_adam_fc answers ICNN_BE_ELIMIT.  A negative error code for
+ * what both entries refuse as a bad argument (batch 0: ICNN_BE_EINVAL, nothing is planned).  Enqueues nothing and reads no
+ * buffer of the model or of cx; with more than four states it asks the runtime how many workgroups a CU holds, so it needs
+ * a device.
+ */
+ICNN_BE_API int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]);
 
 #ifdef __cplusplus
 }

@@ -26,8 +26,12 @@ B1, B2, SMOOTH, EPS, ALPHA = 0.9, 0.999, 0.5, 1e-8, 0.01
 BOX = 1. - 1e-8
 
 
-def adam(func, obs, n_act, max_iter=1000):
-    """-> (act_best[B,n] float64, iterations run (== max_iter if the rule never fired), f_best[B])."""
+def adam(func, obs, n_act, max_iter=1000, drift_trace=None, moved_mask=None):
+    """-> (act_best[B,n] float64, iterations run (== max_iter if the rule never fired), f_best[B]).
+    Diagnostics for the tests of the stopping rule, both off by default: `drift_trace`, a list that receives the smoothed
+    displacement the rule compares with 1e-3, one float per iteration from 1 on (drift_trace[it - 1]); `moved_mask`
+    [B] bool, False = that sample's displacement is left out of the batch sum (the mean still divides by B): what a
+    batch-wide sum that lost those samples would decide.  The iterates do not depend on either."""
     B = obs.shape[0]
     x = np.zeros((B, n_act))
     mom1 = np.zeros_like(x)
@@ -45,8 +49,12 @@ def adam(func, obs, n_act, max_iter=1000):
             moved[better] = np.linalg.norm(x[better] - best_x[better], axis=1)
             best_x[better] = x[better]
             best_f[better] = f[better]
+            if moved_mask is not None:
+                moved = np.where(moved_mask, moved, 0.)
             step_mean = np.mean(moved)                                   # :184
             drift = step_mean if drift is None else SMOOTH * drift + (1. - SMOOTH) * step_mean   # :185-186
+            if drift_trace is not None:
+                drift_trace.append(float(drift))
             if drift < 1e-3 and it > 5:                                  # :188
                 return best_x, it, best_f
         mom1 = B1 * mom1 + (1. - B1) * g                                 # :194  (float32 product, float64 sum)

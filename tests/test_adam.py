@@ -60,22 +60,33 @@ def _oracle_adam(spec, params, ctx_host, max_iter):
 def test_adam_kernel_matches_oracle(B, seed, max_iter):
     """One launch for the whole loop: 1-4 states per workgroup on the VALU path while the workgroups fit the GPU (one
     workgroup for the agent's act() shape, a cooperative launch with a grid barrier per iteration beyond), 16-state
-    MFMA tiles for larger batches (1100 here).  Both sides evaluate negQ in the same float32 order and
-    the entropy term / moments with the same operations, so the iteration count must be equal and the best
-    iterates agree to float64 rounding (the bar of BASELINE.json is 1e-5)."""
+    MFMA tiles for larger batches.  icnn_be_debug_adam_plan on the 256-CU device: 256 states are 256 workgroups of one,
+    700 are 234 workgroups of three (the last holds one), 1100 are 69 tiles (the last holds twelve).  Both sides
+    evaluate negQ in the same float32 order and the entropy term / moments with the same operations, so the iteration
+    count must be equal and the best iterates agree to float64 rounding (the bar of BASELINE.json is 1e-5).
+    On this network the stopping rule fires at about iteration 82 on batches of 16 and more (earlier on the small ones,
+    where a state that never improves on act = 0 does not move at all): batches 7, 700 and 1100 -- the two largest
+    launches among them -- run into their max_iter of 9, 60 and 40, every other case stops on the rule, and both is asserted.
+    The cases in which the rule FIRES on the large launches, and on every other launch shape, are in
+    tests/test_adam_architectures.py."""
     import torch
 
-    from icnn_amd import picnn, rl_adam
+    from icnn_amd import _lib, picnn, rl_adam
     spec, params, obs = _negq_problem(B, seed)
     model = picnn.FCModel(spec, params)
+    plan = _lib.adam_plan(model.c_model, B)
+    large = {256: ("ROWS", 1, 256, True, False), 700: ("ROWS", 3, 234, True, False), 1100: ("TILE", 16, 69, True, False)}
+    if B in large and torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count == 256:
+        assert plan == large[B], plan
     ctx = model.context(torch.from_numpy(obs))[:B].contiguous()
     res = rl_adam.AdamSolver(model, B, max_iter).solve(ctx)
     torch.cuda.synchronize()
     best, iters, f_best = _oracle_adam(spec, params, ctx.cpu().numpy(), max_iter)
     got = res.act_best.cpu().numpy()
-    print("adam B=%d: %d iterations (oracle %d), max |d act_best| %.3e" % (B, int(res.iters.item()), iters,
-                                                                            np.max(np.abs(got - best))))
+    print("adam B=%d: plan %s, %d iterations (oracle %d), max |d act_best| %.3e" % (B, plan, int(res.iters.item()), iters,
+                                                                                   np.max(np.abs(got - best))))
     assert int(res.iters.item()) == iters
+    assert iters > 5 and (iters == max_iter) == (B in (7, 700, 1100))
     assert np.max(np.abs(got - best)) <= 1e-9
     assert np.max(np.abs(res.f_best.cpu().numpy() - f_best)) <= 1e-6
     assert np.all(np.abs(got) <= 1.0 - 1e-8)

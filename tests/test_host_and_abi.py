@@ -98,6 +98,53 @@ def test_adam_obs_entry_refuses_mismatched_model_and_context_descriptions():
     assert lib.icnn_be_adam_fc_obs(*args) == -1
 
 
+def test_adam_obs_entry_refuses_a_relu_last_u_context_without_batchnorm():
+    """The in-kernel context producer keeps the last u-layer linear, so a context description with u_last_relu set is a bad
+    argument to icnn_be_adam_fc_obs (ICNN_BE_EINVAL, not the ICNN_BE_ELIMIT that sends a caller to context + Adam) also for a
+    model without BatchNorm, at any batch, and icnn_be_debug_adam_plan refuses it alike.  rl_adam.AdamSolver.solve_obs
+    therefore answers None for such a model before it calls the library.  Nothing is enqueued: no GPU needed."""
+    from icnn_amd import _lib
+    lib = _lib.load()
+    m = _lib.FcModel()
+    m.n, m.n_layers = 6, 3
+    m.width[0], m.width[1], m.width[2] = 24, 16, 1
+    m.alpha, m.action_box = 0.01, 0
+    m.ctx_width = 3 * 6 + 24 + 16 + 1 + 24 + 16
+    dummy = (C.c_float * 4)()
+    m.wpack = C.cast(dummy, C.c_void_p)
+    assert lib.icnn_be_fc_pack_floats(C.byref(m)) > 0
+    cx = _lib.FcCtx()
+    cx.n_features, cx.n, cx.n_layers = 7, 6, 3
+    cx.width[0], cx.width[1], cx.width[2] = 24, 16, 1
+    cx.batchnorm, cx.bn_eps, cx.u_last_relu = 0, 1e-5, 1
+    for i in range(3):
+        cx.w_stage[i] = C.cast(dummy, C.c_void_p)
+        cx.b_stage[i] = C.cast(dummy, C.c_void_p)
+    out = (C.c_int * 4)()
+    for batch in (0, 1, 3, 700):
+        assert lib.icnn_be_adam_fc_obs(C.byref(m), C.byref(cx), dummy, batch, 10, dummy, dummy, dummy, dummy, None) == -1
+    assert lib.icnn_be_debug_adam_plan(C.byref(m), C.byref(cx), 3, C.byref(out)) == -1
+    # up to four states the plan is host arithmetic (one workgroup, no occupancy query): without the flag it is the latency
+    # path with the observation form accepted, and 7 features against ctx_off = 464 are far inside the scratch guard
+    cx.u_last_relu = 0
+    assert _lib.adam_plan(m, 3, cx) == ("ROWS", 3, 1, False, True)
+    assert _lib.adam_plan(m, 3) == ("ROWS", 3, 1, False, False)
+    cx.n_features = 233                                              # 2 * 233 > 464: outside the guard
+    assert _lib.adam_plan(m, 3, cx) == ("ROWS", 3, 1, False, False)
+    cx.n_features = 232
+    assert _lib.adam_plan(m, 3, cx) == ("ROWS", 3, 1, False, True)
+    cx.batchnorm = 1
+    cx.bn_gamma[0] = cx.bn_beta[0] = C.cast(dummy, C.c_void_p)
+    assert _lib.adam_plan(m, 3, cx) == ("ROWS", 3, 1, False, False)
+    m.n = 65                                                         # one tile: still no device needed
+    m.ctx_width = 3 * 65 + 24 + 16 + 1 + 24 + 16
+    assert _lib.adam_plan(m, 16) == ("TILE", 16, 1, False, False)
+    assert lib.icnn_be_debug_adam_plan(C.byref(m), None, 0, C.byref(out)) == -1       # nothing to plan
+    assert lib.icnn_be_debug_adam_plan(C.byref(m), None, 16, None) == -1
+    m.action_box = 1
+    assert lib.icnn_be_debug_adam_plan(C.byref(m), None, 16, C.byref(out)) == -1      # as icnn_be_adam_fc refuses it
+
+
 def test_context_stage_accepts_an_empty_shard_with_null_buffers():
     """a data-parallel rank whose shard is empty (batch < world size) hands over zero-element tensors, whose data
     pointers are NULL; icnn_be_fc_context_stage must return its "sums pending" code (1) for the normalised stages -- so that
