@@ -1,11 +1,14 @@
-"""A short bundle-entropy training loop on seeded synthetic multi-label data, every iteration one replay of a captured
-train.BundleTrainer.step (the loop of multi-label-cls/icnn_ebundle.py:208-250 without a host wait inside the step).
+"""A short bundle-entropy training loop on seeded synthetic multi-label data (the loop of multi-label-cls/icnn_ebundle.py:208-250)
+with no host data in it: the training set lives on the device (train.DeviceDataset), and `--every` iterations of [minibatch
+draw, train.BundleTrainer.step, log row] are one graph that a train.EpochRunner captures once and replays.
 
     python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10] [--test-every 20] [--save DIR] [--resume FILE]
 
-The labels are a noisy linear function of the features; the loss falls from the first steps on (685 to 639 over the
-default 60 steps on an MI355X).
-The host reads the loss and the F1 tallies only every `--every` steps, after a synchronisation of its own choosing.
+The labels are a noisy linear function of the features; the loss falls from the first steps on (685.7 at step 10 to 642.3 at
+step 60 with the defaults on an MI355X).
+The host reads the per-step losses from the device log (train.StepLog) and the F1 tallies only every `--every` steps.
+The minibatches are drawn with the library's Philox stream (include/icnn_be.h, icnn_be_dataset_draw), not NumPy's
+Mersenne Twister: the batch sequence, and with it the printed numbers, differ from those of versions that drew on the host.
 Every `--test-every` steps (0: never) the test phase of the script (:257-277) runs on a held-out split of the same
 distribution: one replay of a captured train.BundleTrainer.evaluate, then the test loss and macro-F1.
 --save DIR keeps the model with the best test F1 (icnn_ebundle.py:274-277, `if testF1 > bestTestF1: save`) through a
@@ -48,23 +51,13 @@ def main():
     trainer = train.BundleTrainer(model, a.batch, n_iter=10, loss="xent", lr=1e-3, eval_batch=n_test if a.test_every else None)
     # the keeper moves the BatchNorm statistics into one buffer: built before anything is captured
     keeper = train.BestKeeper(trainer, mode="max", start=0.0) if a.save else None
-    Xd, Yd = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
-
-    def batch():
-        idx = torch.from_numpy(rng.randint(n_train, size=a.batch)).cuda()
-        trainer.x.copy_(Xd[idx])
-        trainer.true_y.copy_(Yd[idx])
-
-    # warm up on a side stream, then capture one step; the batch lives in trainer.x / trainer.true_y
-    batch()
+    data = train.DeviceDataset((X, Y), seed=0)
+    every = max(1, a.every)
+    log = train.StepLog([("loss", trainer.loss)], every)
+    # [draw, step, log] x every: the first run is eager, the second captures the chain, later ones replay it
+    runner = train.EpochRunner(trainer, data, every, log=log)
+    tail = train.EpochRunner(trainer, data, 1, log=log)    # the steps behind the last whole chain
     s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        trainer.step(None, None)
-    torch.cuda.current_stream().wait_stream(s)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        trainer.step(None, None)
     test_graph = None
     if a.test_every:                                       # the whole held-out split is one evaluation batch
         s.wait_stream(torch.cuda.current_stream())
@@ -77,17 +70,25 @@ def main():
             if keeper is not None:
                 keeper.offer_macro_f1(trainer.eval_f1_tallies)
     if a.resume:                                           # into the existing tensors: the graphs above replay on the loaded state
-        checkpoint.load(a.resume, trainer, keeper=keeper)
-        print("resumed %s at step %d" % (a.resume, trainer.t_steps))
-    for i in range(1, a.steps + 1):
-        batch()
-        graph.replay()
-        if i % a.every == 0 or i == a.steps:
-            torch.cuda.synchronize()
+        checkpoint.load(a.resume, trainer, keeper=keeper, dataset=data)
+        print("resumed %s at step %d, draw %d" % (a.resume, trainer.t_steps, data.draws))
+    i = 0
+    while i < a.steps:
+        stop = min(a.steps, (i // every + 1) * every)
+        if a.test_every:                                   # a test phase falls where it fell before: on its own multiples
+            stop = min(stop, (i // a.test_every + 1) * a.test_every)
+        if stop - i == every:
+            runner.run()
+        else:
+            for _ in range(stop - i):
+                tail.run()
+        i = stop
+        if i % every == 0 or i == a.steps:
+            losses = log.read()["loss"]                    # synchronises
             trainer.raise_on_error()
-            print("step %4d  loss %10.4f  macro F1 %.3f  feed rows %d of %d  fg evaluations %d"
-                  % (i, float(trainer.loss.item()), trainer.macro_f1(), int(trainer.rows.item()), trainer.feed.row_cap,
-                     int(trainer.fg_evals.item())))
+            print("step %4d  loss %10.4f  (mean of the last %d: %.4f)  macro F1 %.3f  feed rows %d of %d  fg evaluations %d"
+                  % (i, losses[-1], len(losses), losses.mean(), trainer.macro_f1(), int(trainer.rows.item()),
+                     trainer.feed.row_cap, int(trainer.fg_evals.item())))
         if test_graph is not None and (i % a.test_every == 0 or i == a.steps):
             test_graph.replay()
             torch.cuda.synchronize()
@@ -96,7 +97,7 @@ def main():
     if a.save:
         os.makedirs(a.save, exist_ok=True)
         checkpoint.save_best(os.path.join(a.save, "best.npz"), keeper)
-        checkpoint.save(os.path.join(a.save, "last.npz"), trainer, keeper=keeper)
+        checkpoint.save(os.path.join(a.save, "last.npz"), trainer, keeper=keeper, dataset=data)
         print("kept %d of %d test phases, best test macro F1 %.3f: %s" % (keeper.kept, keeper.offers, keeper.best_value(),
                                                                           os.path.join(a.save, "best.npz")))
 

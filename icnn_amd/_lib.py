@@ -69,6 +69,7 @@ EXPORTS = [
     "icnn_be_step_gate", "icnn_be_param_update_gated", "icnn_be_gated_copy",
     "icnn_be_replay_enqueue", "icnn_be_replay_sample",
     "icnn_be_gd_eval_work_bytes", "icnn_be_gd_eval", "icnn_be_macro_f1", "icnn_be_keep_best",
+    "icnn_be_dataset_draw", "icnn_be_log_row",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -80,6 +81,12 @@ RL_TD_WORK_BYTES = 8 * RL_TD_MAX_BLOCKS + 16
 REPLAY_CTRL_INTS = 8                       # ICNN_BE_REPLAY_CTRL_INTS: cursor, fill, draws, status, ticket
 REPLAY_MAX_ATTEMPTS = 256
 REPLAY_ST_EXHAUSTED, REPLAY_ST_STATE = 1, 2
+DATASET_MAX_ARRAYS = 4                     # ICNN_BE_DATASET_MAX_ARRAYS
+DATASET_CTRL_INTS = 8                      # ICNN_BE_DATASET_CTRL_INTS: draws, status, ticket
+DATASET_ST_STATE = 1
+LOG_MAX_COLUMNS = 8                        # ICNN_BE_LOG_MAX_COLUMNS
+LOG_CTRL_INTS = 4                          # ICNN_BE_LOG_CTRL_INTS: the cursor
+LOG_KIND = {"float32": 0, "float64": 1, "int32": 2}     # ICNN_BE_LOG_F32 / _F64 / _I32
 
 
 def replay_stage_bytes(dimO, dimA):
@@ -173,6 +180,22 @@ class Replay(C.Structure):
     _fields_ = [
         ("size", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("observations", C.c_void_p), ("actions", C.c_void_p),
         ("rewards", C.c_void_p), ("terminals", C.c_void_p), ("ctrl", C.c_void_p),
+    ]
+
+
+class Dataset(C.Structure):
+    """struct icnn_be_dataset"""
+    _fields_ = [
+        ("n_rows", C.c_int), ("n_arrays", C.c_int), ("src", C.c_void_p * DATASET_MAX_ARRAYS),
+        ("row_words", C.c_int * DATASET_MAX_ARRAYS), ("ctrl", C.c_void_p),
+    ]
+
+
+class StepLog(C.Structure):
+    """struct icnn_be_step_log"""
+    _fields_ = [
+        ("rows", C.c_void_p), ("ctrl", C.c_void_p), ("cap", C.c_int), ("width", C.c_int),
+        ("col", C.c_void_p * LOG_MAX_COLUMNS), ("kind", C.c_int * LOG_MAX_COLUMNS),
     ]
 
 
@@ -366,6 +389,11 @@ def load():
     lib.icnn_be_replay_enqueue.restype = C.c_int
     lib.icnn_be_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 7
     lib.icnn_be_replay_sample.restype = C.c_int
+    lib.icnn_be_dataset_draw.argtypes = [C.POINTER(Dataset), C.c_int, C.c_ulonglong, C.POINTER(C.c_void_p), C.c_void_p,
+                                         C.c_void_p]
+    lib.icnn_be_dataset_draw.restype = C.c_int
+    lib.icnn_be_log_row.argtypes = [C.POINTER(StepLog), C.c_void_p]
+    lib.icnn_be_log_row.restype = C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -399,6 +427,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_ficnn_model differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(9) != C.sizeof(Replay):
         raise ImportError("ctypes struct layout of icnn_be_replay differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(10) != C.sizeof(Dataset) or lib.icnn_be_struct_size(11) != C.sizeof(StepLog):
+        raise ImportError("ctypes struct layout of icnn_be_dataset / icnn_be_step_log differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

@@ -13,6 +13,8 @@ result depends on:
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
                          then resets it
     train.BestKeeper     best, the gate counters, the snapshots of theta and of the statistics
+    train.DeviceDataset  seed, n_rows, the draw counter and the control block -- not the data: a resumed run rebuilds the
+                         set from its arrays and continues the uninterrupted run's batch sequence
 
 The arenas (the packed copies of theta the kernels read) are not stored: load() rewrites them from theta.
 
@@ -172,9 +174,16 @@ def _torch_dtype_name(t) -> str:
 # --------------------------------------------------------------------------------------------- #
 # save / load
 # --------------------------------------------------------------------------------------------- #
-def save(path, obj, keeper=None, memory=True):
-    """Write a checkpoint of `obj` (and of `keeper`, a train.BestKeeper on it) to `path`.  Reads the device: one wait.
-    memory (the Agent only): include the replay memory."""
+def _dataset_host(dataset) -> dict:
+    """the control block of a train.DeviceDataset and what identifies its stream, as arrays (reads the device)"""
+    ctrl = dataset.ctrl.cpu().numpy()
+    return {"data/seed": np.asarray(dataset.seed, np.uint64), "data/n_rows": np.asarray(dataset.n_rows, np.int64),
+            "data/draws": np.asarray(int(ctrl[0]), np.int64), "data/ctrl": ctrl}
+
+
+def save(path, obj, keeper=None, memory=True, dataset=None):
+    """Write a checkpoint of `obj` (and of `keeper`, a train.BestKeeper on it, and of `dataset`, the train.DeviceDataset that
+    feeds it) to `path`.  Reads the device: one wait.  memory (the Agent only): include the replay memory."""
     kind = _kind(obj)
     trainer = obj.trainer if kind == "Agent" else obj
     if keeper is not None and keeper.opt is not trainer.opt:
@@ -189,6 +198,8 @@ def save(path, obj, keeper=None, memory=True):
         arrays[name] = t.detach().cpu().numpy()
     if kind == "Agent":
         arrays.update(_agent_host(obj, bool(memory)))
+    if dataset is not None:
+        arrays.update(_dataset_host(dataset))
     write_arrays(path, arrays)
 
 
@@ -224,9 +235,11 @@ def _check_array(arrays, name, shape, dtype):
     return a
 
 
-def load(path, obj, keeper=None):
-    """Copy the checkpoint at `path` into `obj` (and `keeper`): into the existing tensors, so captured graphs stay valid.
-    Everything is checked first; a ValueError names the field that does not fit and nothing has been written then."""
+def load(path, obj, keeper=None, dataset=None):
+    """Copy the checkpoint at `path` into `obj` (and `keeper`, and `dataset`): into the existing tensors, so captured graphs
+    stay valid.  Everything is checked first; a ValueError names the field that does not fit and nothing has been written
+    then.  A dataset's seed and row count must be the file's (a captured draw carries them), and the file holds a dataset's
+    state exactly when the call gives one."""
     import torch
     kind = _kind(obj)
     trainer = obj.trainer if kind == "Agent" else obj
@@ -256,6 +269,17 @@ def load(path, obj, keeper=None):
     for name in arrays:                                         # state in the file that this object has no place for
         if (name in ("gate",) or name.startswith(state_prefixes)) and name not in tensors and name != "keeper/mode":
             raise ValueError("%s: in the file, but this object keeps no such state" % name)
+    has_data = any(name.startswith("data/") for name in arrays)
+    if has_data != (dataset is not None):
+        raise ValueError("dataset: the file %s a dataset's state, the call %s a dataset"
+                         % ("holds" if has_data else "does not hold", "gives" if dataset is not None else "gives no"))
+    if dataset is not None:
+        for name, mine in (("data/n_rows", dataset.n_rows), ("data/seed", dataset.seed)):
+            if _scalar(arrays, name) != mine:
+                raise ValueError("%s: %d in the file, %d here" % (name, _scalar(arrays, name), mine))
+        data_ctrl = _check_array(arrays, "data/ctrl", dataset.ctrl.shape, np.int32)
+        if _scalar(arrays, "data/draws") != int(data_ctrl[0]):
+            raise ValueError("data/draws: %d in the file, its control block says %d" % (_scalar(arrays, "data/draws"), data_ctrl[0]))
     host = None
     if kind == "Agent":
         mem = obj.memory
@@ -291,6 +315,9 @@ def load(path, obj, keeper=None):
             t.copy_(torch.from_numpy(arrays[name]))
         for theta, arena, pmap in _arena_owners(kind, obj, keeper):
             arena.copy_(torch.from_numpy(pmap.scatter(theta.cpu().numpy())))
+        if dataset is not None:
+            dataset.ctrl.copy_(torch.from_numpy(arrays["data/ctrl"]))
+            dataset.draws = int(arrays["data/ctrl"][0])
         if kind == "Agent":
             mem = obj.memory
             obj.t, obj._trained = int(host["t"]), bool(host["trained"])

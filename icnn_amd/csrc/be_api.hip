@@ -253,7 +253,8 @@ size_t icnn_be_struct_size(int which) {
          : which == 2 ? sizeof(icnn_be_fc_ctx) : which == 3 ? sizeof(icnn_be_conv_model)
          : which == 4 ? sizeof(icnn_be_conv_ctx) : which == 5 ? sizeof(icnn_be_bn_moving)
          : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args)
-         : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay) : 0;
+         : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay)
+         : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -942,6 +943,33 @@ int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned
     if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
     const icnn_be::ReplaySampleLaunch l{*m, batch, seed, obs, act, rew, ob2, term, idx};
     return done(icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_dataset_draw(const icnn_be_dataset *d, int batch, unsigned long long seed, void *const dst[], int *idx,
+                         void *stream) {
+    if (!d || !d->ctrl || !idx || !dst) return ICNN_BE_EINVAL;
+    if (d->n_rows < 1 || batch < 1 || d->n_arrays < 1 || d->n_arrays > ICNN_BE_DATASET_MAX_ARRAYS) return ICNN_BE_EINVAL;
+    for (int a = 0; a < d->n_arrays; ++a) {
+        if (!d->src[a] || !dst[a] || d->row_words[a] < 1) return ICNN_BE_EINVAL;
+        if (reinterpret_cast<uintptr_t>(d->src[a]) % 16 || reinterpret_cast<uintptr_t>(dst[a]) % 16) return ICNN_BE_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(idx) % 16 || reinterpret_cast<uintptr_t>(d->ctrl) % 4 ||
+        reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    const icnn_be::DatasetDrawLaunch l{*d, batch, seed, dst, idx};
+    return done(icnn_be::launch_dataset_draw(l, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_log_row(const icnn_be_step_log *L, void *stream) {
+    if (!L || !L->rows || !L->ctrl || L->cap < 1 || L->width < 1 || L->width > ICNN_BE_LOG_MAX_COLUMNS) return ICNN_BE_EINVAL;
+    for (int j = 0; j < L->width; ++j) {
+        if (!L->col[j] || L->kind[j] < ICNN_BE_LOG_F32 || L->kind[j] > ICNN_BE_LOG_I32) return ICNN_BE_EINVAL;
+        if (reinterpret_cast<uintptr_t>(L->col[j]) % (L->kind[j] == ICNN_BE_LOG_F64 ? 8 : 4)) return ICNN_BE_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(L->rows) % 8 || reinterpret_cast<uintptr_t>(L->ctrl) % 4 ||
+        reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_log_row(*L, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

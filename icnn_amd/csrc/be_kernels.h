@@ -371,4 +371,15 @@ long long replay_sample_blocks(int batch);
 hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream);
 hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream);
 
+// ---- the training set on the device and the step log (be_train_data.hip) ----------------------
+struct DatasetDrawLaunch {
+    icnn_be_dataset d;
+    int batch;
+    unsigned long long seed;
+    void *const *dst;             // [d.n_arrays]
+    int *idx;
+};
+hipError_t launch_dataset_draw(const DatasetDrawLaunch &l, hipStream_t stream);
+hipError_t launch_log_row(const icnn_be_step_log &L, hipStream_t stream);
+
 }  // namespace icnn_be

@@ -223,8 +223,8 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
- * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9: lets a
- * foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
+ * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -885,6 +885,71 @@ ICNN_BE_API int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stag
  */
 ICNN_BE_API int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs,
                                       double *act, float *rew, float *ob2, unsigned char *term, int *idx, void *stream);
+
+/* ---- the training set on the device: minibatch draw and step log (be_train_data.hip, additive to ABI 12) ---- */
+
+/*
+ * A training set of n_rows examples in device memory, as up to ICNN_BE_DATASET_MAX_ARRAYS arrays that share their first
+ * dimension (trainX, trainY of multi-label-cls/icnn_ebundle.py:214, icnn-back.py:190, completion/icnn_ebundle.py:210,
+ * icnn.back.py:216).  Array a has n_rows rows of row_words[a] 4-byte words: the draw copies words and knows no element type
+ * (a float64 row of n values is 2 n words).  ctrl: ICNN_BE_DATASET_CTRL_INTS int32, zero for a fresh set: [0] the draw
+ * counter, [1] the status word (an OR of ICNN_BE_DATASET_ST_*), [2] a ticket the draw re-arms, the rest reserved (zero).
+ * They live on the device so that a captured draw reads the current counter on every replay.
+ */
+#define ICNN_BE_DATASET_MAX_ARRAYS 4
+#define ICNN_BE_DATASET_CTRL_INTS 8
+#define ICNN_BE_DATASET_ST_STATE 1        /* a launch found the ticket outside its grid: two draws of one set ran at once */
+typedef struct icnn_be_dataset {
+    int n_rows;                                        /* N >= 1 */
+    int n_arrays;                                      /* 1 .. ICNN_BE_DATASET_MAX_ARRAYS */
+    const void *src[ICNN_BE_DATASET_MAX_ARRAYS];       /* [n_rows][row_words[a]] words, 16-byte aligned */
+    int row_words[ICNN_BE_DATASET_MAX_ARRAYS];         /* >= 1 */
+    int *ctrl;                                         /* [ICNN_BE_DATASET_CTRL_INTS] */
+} icnn_be_dataset;
+
+/*
+ * `I = npr.randint(nTrain, size=batch); trainX[I], trainY[I]` in one launch: for k < batch
+ *   idx[k] = (word * N) >> 32,  word = word 0 of Philox4x32-10 at counter (draws, k, 0, 1) and key (seed low, seed high)
+ * -- the map of icnn_be_replay_sample with the domain tag 1 in counter word 3, so that a training set and a replay memory
+ * at one seed do not share a stream -- and row idx[k] of array a is copied bit for bit to row k of dst[a], for every array.
+ * Rows are drawn independently, with replacement.  Every index has probability floor(2^32 / N) or ceil(2^32 / N) over
+ * 2^32: a relative spread of at most N / 2^32.  draws is the device's draw counter, which the launch advances by one (the
+ * last workgroup to take the ticket does, and re-arms the ticket): a captured launch replayed r times is r different
+ * minibatches.  dst[a]: [batch][row_words[a]] words; idx: int32 [batch], never NULL.  One workgroup per sample; rows of
+ * row_words % 4 == 0 move as 16-byte words, others word by word.  EINVAL for a NULL d, ctrl, idx, dst or any src / dst[a],
+ * n_rows < 1, batch < 1, n_arrays outside [1, ICNN_BE_DATASET_MAX_ARRAYS], row_words < 1, a src, dst[a] or idx that is not
+ * 16-byte aligned, a ctrl that is not 4-byte aligned, a misaligned stream, before anything is launched.  Vector stores
+ * only, no accumulating atomics beyond the ticket, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_dataset_draw(const icnn_be_dataset *d, int batch, unsigned long long seed, void *const dst[], int *idx,
+                                     void *stream);
+
+/*
+ * A ring of per-step scalars in device memory (what the scripts write to train.csv every iteration): rows float64
+ * [cap][width]; ctrl int32 [ICNN_BE_LOG_CTRL_INTS], zero for an empty log, [0] the cursor = rows appended so far.  Column j is
+ * one scalar in device memory, col[j], of kind[j] (ICNN_BE_LOG_F32 / _F64 / _I32).
+ */
+#define ICNN_BE_LOG_MAX_COLUMNS 8
+#define ICNN_BE_LOG_CTRL_INTS 4
+#define ICNN_BE_LOG_F32 0
+#define ICNN_BE_LOG_F64 1
+#define ICNN_BE_LOG_I32 2
+typedef struct icnn_be_step_log {
+    double *rows;                                      /* [cap][width], 8-byte aligned */
+    int *ctrl;                                         /* [ICNN_BE_LOG_CTRL_INTS] */
+    int cap;                                           /* >= 1 */
+    int width;                                         /* 1 .. ICNN_BE_LOG_MAX_COLUMNS */
+    const void *col[ICNN_BE_LOG_MAX_COLUMNS];
+    int kind[ICNN_BE_LOG_MAX_COLUMNS];
+} icnn_be_step_log;
+
+/*
+ * rows[cursor % cap][j] = (double)*col[j] for j < width (exact for all three kinds), then cursor <- cursor + 1.  One wave.
+ * EINVAL for a NULL L, rows, ctrl or col[j], cap < 1, width outside [1, ICNN_BE_LOG_MAX_COLUMNS], an unknown kind, rows
+ * not 8-byte aligned (ctrl and the columns: the alignment of their type), a misaligned stream, before anything is launched.
+ * Vector stores only, no atomics, no host synchronisation (capturable in a HIP graph).
+ */
+ICNN_BE_API int icnn_be_log_row(const icnn_be_step_log *L, void *stream);
 
 /* ---- the reference's return value (SURVEY.md 8(b) "Return / ownership") ------------------------ */
 
