@@ -47,7 +47,7 @@ EXPORTS = [
     "icnn_be_abi_version", "icnn_be_last_hip_error", "icnn_be_struct_size", "icnn_be_dual_lds_bytes", "icnn_be_bundle_capacity", "icnn_be_scratch_bytes",
     "icnn_be_state_init",
     "icnn_be_dual_step", "icnn_be_fc_pack_floats", "icnn_be_fc_pack", "icnn_be_fc_fg",
-    "icnn_be_solve_fc", "icnn_be_conv_pack_floats", "icnn_be_conv_work_floats", "icnn_be_conv_pack", "icnn_be_conv_fg", "icnn_be_solve_conv",
+    "icnn_be_solve_fc", "icnn_be_solve_fc_reset", "icnn_be_conv_pack_floats", "icnn_be_conv_work_floats", "icnn_be_conv_pack", "icnn_be_conv_fg", "icnn_be_solve_conv",
     "icnn_be_implicit_feed", "icnn_be_export_active", "icnn_be_adam_workspace_bytes", "icnn_be_adam_fc", "icnn_be_adam_fc_obs",
     "icnn_be_fc_context_work_floats", "icnn_be_fc_context", "icnn_be_fc_context_stage", "icnn_be_fc_context_norm", "icnn_be_fc_clamp",
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
@@ -248,6 +248,8 @@ def load():
     lib.icnn_be_solve_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.POINTER(State), C.c_void_p,
                                      C.c_void_p, C.c_void_p]
     lib.icnn_be_solve_fc.restype = C.c_int
+    lib.icnn_be_solve_fc_reset.argtypes = (lib.icnn_be_solve_fc.argtypes[:-1] + [C.c_void_p, C.c_double, C.c_void_p])
+    lib.icnn_be_solve_fc_reset.restype = C.c_int
     lib.icnn_be_conv_pack_floats.argtypes = [C.POINTER(ConvModel)]
     lib.icnn_be_conv_pack_floats.restype = C.c_size_t
     lib.icnn_be_conv_work_floats.argtypes = [C.POINTER(ConvModel), C.c_int]

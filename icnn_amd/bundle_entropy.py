@@ -479,11 +479,27 @@ class FusedSolver:
     def solve(self, ctx: torch.Tensor, y0=0.5):
         assert ctx.is_contiguous() and ctx.dtype == torch.float32
         assert ctx.shape == (self.batch, self.model.spec.ctx_width)
+        st = self.state
+        if self.model.solve_entry == "icnn_be_solve_fc":
+            # the reset rides in the solve's first launch (icnn_be_solve_fc_reset): the workgroup that owns a sample writes its
+            # y row and control words itself
+            y0_ptr, fill = None, 0.0
+            if torch.is_tensor(y0):
+                y0 = y0.to(self.y.device, torch.float64).expand(self.y.shape).contiguous()
+                y0_ptr = y0.data_ptr()
+            else:
+                fill = float(y0)
+            self._y0 = y0                                  # alive until the next call: the launch reads it asynchronously
+            rounds = st.lib.icnn_be_solve_fc_reset(C.byref(self.model.c_model), ctx.data_ptr(), C.byref(st.c_state),
+                                                   self.f_work.data_ptr(), self.g_work.data_ptr(), y0_ptr, fill, st.stream())
+            if rounds < 0:
+                _lib.check(rounds, "icnn_be_solve_fc_reset")
+            st.rounds = rounds
+            return BundleResult(st)
         if torch.is_tensor(y0):
             self.y.copy_(y0)
         else:
             self.y.fill_(float(y0))
-        st = self.state
         st.init()
         rounds = getattr(st.lib, self.model.solve_entry)(C.byref(self.model.c_model), ctx.data_ptr(),
                                                          C.byref(st.c_state), self.f_work.data_ptr(),

@@ -324,8 +324,13 @@ int icnn_be_fc_fg(const icnn_be_fc_model *model, const float *ctx, const double 
     return done(icnn_be::launch_fc_fg(*model, ctx, y, batch, f, g, finished, static_cast<hipStream_t>(stream)));
 }
 
-int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
-                     float *f_work, float *g_work, void *stream) {
+namespace {
+/* icnn_be_solve_fc and icnn_be_solve_fc_reset.  reset.on: the solve starts from y0 / the constant and from a fresh state.  A plan
+   that begins with a persistent kernel resets inside that launch (every sample has one owner there); the others -- launch
+   pairs, and budgeted tiles, whose finishing launch must find the state the tiles left -- get the reset as launches of its
+   own in front. */
+int solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st, float *f_work, float *g_work,
+             const icnn_be::SolveReset &reset, void *stream) {
     if (int rc = check_state(st)) return rc;
     if (!model || !ctx || !f_work || !g_work || !model->wpack) return ICNN_BE_EINVAL;
     if (int rc = check_fc_solve(model, st)) return rc;
@@ -337,14 +342,22 @@ int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn
     auto finish = [&] { return icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, 1, prof, s, true); };
     auto fg = [&] { return icnn_be::launch_fc_fg(*model, ctx, st->y, st->batch, f_work, g_work, st->skip_fg, s); };
     hipError_t e = hipSuccess;
+    const bool in_kernel = p.path == ICNN_BE_PATH_ROWS || p.path == ICNN_BE_PATH_TILE;
+    if (reset.on && !in_kernel) {
+        e = icnn_be::launch_y_reset(*st, reset, s);
+        if (e == hipSuccess) e = icnn_be::launch_state_init(*st, s);
+        if (e != hipSuccess) return fail(e);
+    }
     switch (p.path) {
     case ICNN_BE_PATH_ROWS:
-        e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, p.per_wg, prof, s, false);
+        e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, p.per_wg, prof, s, false, reset);
         break;
     case ICNN_BE_PATH_TILE:
+        e = icnn_be::launch_fused_fc_solve(*model, ctx, *st, f_work, g_work, prof, s, p.per_wg, p.budget, reset);
+        break;
     case ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS:
         e = icnn_be::launch_fused_fc_solve(*model, ctx, *st, f_work, g_work, prof, s, p.per_wg, p.budget);
-        if (e == hipSuccess && p.path == ICNN_BE_PATH_TILE_BUDGETED_THEN_ROWS) e = finish();
+        if (e == hipSuccess) e = finish();
         break;
     case ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS:
         e = solve_rounds(*st, p.budget, outer_iters(*st), f_work, g_work, s, fg);
@@ -354,6 +367,17 @@ int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn
         e = solve_rounds(*st, p.budget, p.rounds, f_work, g_work, s, fg);
     }
     return e == hipSuccess ? p.rounds : fail(e);
+}
+}  // namespace
+
+int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
+                     float *f_work, float *g_work, void *stream) {
+    return solve_fc(model, ctx, st, f_work, g_work, icnn_be::SolveReset{}, stream);
+}
+
+int icnn_be_solve_fc_reset(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
+                           float *f_work, float *g_work, const double *y0, double y0_fill, void *stream) {
+    return solve_fc(model, ctx, st, f_work, g_work, icnn_be::SolveReset{1, y0, y0_fill}, stream);
 }
 
 int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state *st, int cus, int out[3]) {

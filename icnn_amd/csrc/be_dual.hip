@@ -187,6 +187,11 @@ __global__ void state_init_kernel(icnn_be_state st) {
     st.skip_fg[u] = 0;
 }
 
+// y <- y0 (or a constant) in front of a solve whose first launch is not a persistent kernel (launch_y_reset)
+__global__ __launch_bounds__(256) void y_reset_kernel(double *y, const double *y0, double fill, size_t count) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) y[i] = y0 ? y0[i] : fill;
+}
+
 // closing launch of a solve whose stragglers were given a fixed number of rounds: who is still behind says so
 __global__ void mark_unfinished_kernel(icnn_be_state st) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
@@ -257,6 +262,12 @@ int dual_rows_fit(int n, int slots, int cut_dtype, int variant) {
 hipError_t launch_state_init(const icnn_be_state &st, hipStream_t stream) {
     const int threads = st.batch > ICNN_BE_MAX_ROUNDS ? st.batch : ICNN_BE_MAX_ROUNDS;
     return launch_kernel(state_init_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, st);
+}
+
+hipError_t launch_y_reset(const icnn_be_state &st, const SolveReset &rs, hipStream_t stream) {
+    const size_t count = (size_t)st.batch * st.n, blocks = (count + 255) / 256;
+    return launch_kernel(y_reset_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, st.y, rs.y0, rs.fill,
+                         count);
 }
 
 namespace {

@@ -44,8 +44,34 @@ struct FusedArgs {
                        // [TM] int array behind the constant rows)
     int group_cap, need_off;
     long long *trace;  // diagnostic (profiling build, icnn_be_debug_trace): [B][ICNN_BE_MAX_ITERS][DUAL_TRACE_WORDS] or null
+    SolveReset reset;  // on: the state is reset in front of round 0 (reset_sample)
 };
 typedef const __attribute__((address_space(4))) FusedArgs KArgs;
+
+// The reset of a solve inside its first launch: what the caller's y <- y0 and state_init_kernel (be_dual.hip) write for sample
+// u, written by the wave that owns the sample for the whole solve.  st.pending is left alone: only the launch rounds of the
+// other plans write it.  The caller's barrier (with its workgroup-scope release) makes the words visible to the other waves of
+// the workgroup; no other workgroup ever reads them.
+__device__ __forceinline__ void reset_sample(const icnn_be_state &st, const SolveReset &rs, int u, int lane) {
+    const int n = st.n;
+    double *yr = st.y + (size_t)u * n;
+    if (rs.y0) {
+        const double *src = rs.y0 + (size_t)u * n;
+        for (int j = lane; j < n; j += 64) yr[j] = src[j];
+    } else {
+        for (int j = lane; j < n; j += 64) yr[j] = rs.fill;
+    }
+    if (lane == 0) {
+        st.count[u] = 0;
+        st.finished[u] = 0;
+        st.status[u] = 0;
+        st.n_iters[u] = st.iters > 0 ? st.iters : st.slots;
+        st.newton_iters[u] = 0;
+        st.t_next[u] = 0;
+        st.phase[u] = 0;
+        st.skip_fg[u] = 0;
+    }
+}
 
 // RL: the variant of RL/src/bundle_entropy.py (clipped y, Armijo search, early stop); IPM: the interior-point variant of
 // lib/bundle_entropy.py (round 4: the module the reference's scripts import runs through the persistent kernels as well)
@@ -58,6 +84,11 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
         float *crow = reinterpret_cast<float *>(smem + args.crow_off);  // behind phase A's buffers: written once
         for (int j = thread_id(); j < 2 * args.da.ldA; j += NTHREADS) crow[j] = j < args.da.ldA ? 0.f : 1.f;
         if (args.grouped && thread_id() < TM) reinterpret_cast<int *>(smem + args.need_off)[TM + thread_id()] = 0;   // done flags
+    }
+    if (args.reset.on) {                                            // wave w owns sample w of the tile
+        const int wave = uni(thread_id() >> 6), u = blockIdx.x * args.fa.tile_rows + wave;
+        if (wave < args.fa.tile_rows && u < args.da.st.batch) reset_sample(args.da.st, args.reset, u, thread_id() & 63);
+        __syncthreads();                                            // phase A reads the skip flags of the tile on wave 0
     }
     const int rounds = args.rounds;
     for (int r = 0; r < rounds; ++r) {
@@ -176,6 +207,7 @@ struct FusedRowsArgs {
     int resume;                        // finishing pass after time-sliced rounds: only samples that still have rounds to
                                        // run (parked in a Newton loop or behind by the rounds they were parked in) do
                                        // anything, each from its own outer-iteration counter, with no update budget
+    SolveReset reset;                  // on (never with resume): the state is reset in front of round 0 (reset_sample)
 };
 typedef const __attribute__((address_space(4))) FusedRowsArgs KRArgs;
 
@@ -230,6 +262,10 @@ __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArg
             todo = args.da.st.finished[u] == 0 && args.da.st.t_next[u] < args.iters;
         }
         if (!__syncthreads_or(todo)) return;
+    }
+    if (args.reset.on) {                                            // wave w owns sample w of the workgroup; the barriers of
+        const int wave = uni(thread_id() >> 6);                     // rows_setup below publish the words to the other waves
+        if (wave < batch0) reset_sample(args.da.st, args.reset, s_base0 + wave, thread_id() & 63);
     }
     {
         float *crow = reinterpret_cast<float *>(smem + args.crow_off);
@@ -315,7 +351,9 @@ bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int t
 }
 
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume) {
+                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume,
+                                   const SolveReset &reset) {
+    if (resume && reset.on) return hipErrorInvalidValue;
     FusedRowsLayout lay;
     if (!fused_rows_layout(m, st, per_wg, resume, lay)) return hipErrorInvalidValue;
     FusedRowsArgs args{};
@@ -331,6 +369,7 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
     args.crow_off = lay.crow_off;
     args.rounds = args.iters = st.iters > 0 ? st.iters : st.slots;
     args.resume = resume ? 1 : 0;
+    args.reset = reset;
     const bool big = st.slots > 15;
     const int which = (st.variant == ICNN_BE_VARIANT_RL ? 1 : 0) + (big ? 2 : 0);
     auto kern = which == 0 ? fused_rows_solve_kernel<false, 16> : which == 1 ? fused_rows_solve_kernel<true, 16>
@@ -344,7 +383,9 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
 }
 
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget) {
+                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget,
+                                 const SolveReset &reset) {
+    if (budget > 0 && reset.on) return hipErrorInvalidValue;
     FusedTileLayout lay;
     if (!fused_tile_layout(m, st, tile_rows, budget, lay)) return hipErrorInvalidValue;
     FusedArgs args{};
@@ -357,6 +398,7 @@ hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, co
     args.crow_off = lay.crow_off; args.samples_off = 0; args.sample_bytes = lay.sample_bytes;
     args.grouped = lay.grouped; args.group_cap = lay.group_cap; args.need_off = lay.need_off;
     args.trace = dual_trace_buffer();
+    args.reset = reset;
     const bool rl = st.variant == ICNN_BE_VARIANT_RL, big = st.slots > 15;
     auto kern = big ? (rl ? fused_fc_solve_kernel<true, 32> : fused_fc_solve_kernel<false, 32>)
                     : (rl ? fused_fc_solve_kernel<true, 16> : fused_fc_solve_kernel<false, 16>);

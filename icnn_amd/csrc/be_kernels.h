@@ -68,6 +68,15 @@ int dual_lds_bytes(int n, int slots, int cut_dtype, int variant, int rows = 0);
 int dual_rows_fit(int n, int slots, int cut_dtype, int variant);
 size_t scratch_bytes(const icnn_be_state &st);
 hipError_t launch_state_init(const icnn_be_state &st, hipStream_t stream);
+// The reset of a solve (icnn_be_solve_fc_reset): row u of st.y <- y0[u] ([B][n] float64), or the constant `fill` where y0 is
+// NULL, and what launch_state_init writes.  on = 0: the state is reset already (icnn_be_solve_fc; every later launch of a solve).
+struct SolveReset {
+    int on;
+    const double *y0;
+    double fill;
+};
+// st.y <- y0 / fill as its own launch, for the plans whose first launch is not a persistent kernel
+hipError_t launch_y_reset(const icnn_be_state &st, const SolveReset &rs, hipStream_t stream);
 hipError_t launch_mark_unfinished(const icnn_be_state &st, hipStream_t stream);
 hipError_t launch_dual_step(const icnn_be_state &st, int round, int budget, const void *f, const void *g,
                             hipStream_t stream);
@@ -192,10 +201,14 @@ struct FusedRowsLayout {
 // per-sample solve, per_wg (1..4) samples per workgroup; resume: the finishing launch after budgeted rounds
 bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int per_wg, bool resume, FusedRowsLayout &out);
 // hipErrorInvalidValue: a shape the layout functions refuse (the plan never sends one)
+// reset.on: every sample's owner (wave w of a tile; the waves below the workgroup's sample count) writes its y row and control
+// words in front of round 0 -- the first launch of a solve only, never a `resume` or a budgeted launch
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget);
+                                 float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget,
+                                 const SolveReset &reset = SolveReset{});
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
-                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume);
+                                   float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume,
+                                   const SolveReset &reset = SolveReset{});
 int dual_waves(int n, int cut_dtype, int variant);
 long long *dual_profile_buffer();
 void set_dual_trace_buffer(long long *buf);

@@ -144,9 +144,21 @@ __device__ __forceinline__ float act_fn(float p, float alpha) { return p > 0.f ?
 // otherwise the wait-count pass, merging that order with the loop's at the loop header, drains the ring with vmcnt(0) in every
 // turn --, and a slot's refill behind the MFMAs that read it.
 // Per output element the accumulation is the k-ordered fma chain oracle/picnn_chain.c reproduces.
-template <bool TWO, int RD>              // RD: depth of the fragment ring = unroll factor; KB a multiple of it
+//
+// `pre` (the first GEMM of a unit): the requests of the unit's epilogue operands -- eight or nine context loads per lane that
+// miss the L2 --, issued BEHIND the ring's first RD requests.  The vector-memory counter retires in order: requested in front
+// of the ring, every one of them had to land before the first MFMA of the unit could start.  The first turn of the loop is then
+// taken outside it: a wait at the loop header is one instruction for every turn and has to assume the back edge's state (only
+// the refills outstanding), so inside the loop the first turn would wait for `pre`'s loads all the same; peeled, its waits
+// count them as younger than the fragments and leave them in flight, and the first refill's wait at the loop header is the
+// first that covers them.
+struct NoPre {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <bool TWO, int RD, typename Pre>   // RD: depth of the fragment ring = unroll factor; KB a multiple of it
 __device__ __forceinline__ void gemm_loop(const float *ap, const f4 *bp0, const f4 *bp1, size_t kstride, int KB,
-                                          f4 &acc0, f4 &acc1) {
+                                          f4 &acc0, f4 &acc1, Pre pre) {
+    constexpr bool PEEL = !__is_same(Pre, NoPre);
     f4 b0[RD], b1[RD];
 #pragma unroll
     for (int d = 0; d < RD; ++d) {       // issued in the order of use, pinned: the wait-count pass merges this order with the
@@ -157,8 +169,10 @@ __device__ __forceinline__ void gemm_loop(const float *ap, const f4 *bp0, const 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    pre();
+    __builtin_amdgcn_sched_barrier(0);
     f4 an = *reinterpret_cast<const f4 *>(ap);
-    for (int kb0 = 0; kb0 < KB; kb0 += RD) {
+    auto turn = [&](int kb0) {
 #pragma unroll
         for (int d = 0; d < RD; ++d) {
             const int kb = kb0 + d;
@@ -191,10 +205,13 @@ __device__ __forceinline__ void gemm_loop(const float *ap, const f4 *bp0, const 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-    }
+    };
+    if (PEEL && KB > 0) turn(0);
+    for (int kb0 = PEEL ? RD : 0; kb0 < KB; kb0 += RD) turn(kb0);
 }
+template <typename Pre = NoPre>
 __device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *Wp, int KB, int NT, int nt0, int nt1,
-                                           f4 &acc0, f4 &acc1) {
+                                           f4 &acc0, f4 &acc1, Pre pre = Pre{}) {
     const int lane = thread_id() & 63, r16 = lane & 15, q = lane >> 4;
     nt0 = __builtin_amdgcn_readfirstlane(nt0);
     nt1 = __builtin_amdgcn_readfirstlane(nt1);
@@ -204,8 +221,8 @@ __device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *
     const size_t kstride = (size_t)NT * 64;              // f4 elements between consecutive k-blocks of a tile
     static_assert(TILE_RD == 2, "the odd k-block below");
     const int KBe = KB & ~1;
-    if (nt1 >= 0) gemm_loop<true, TILE_RD>(ap, bp0, bp1, kstride, KBe, acc0, acc1);
-    else gemm_loop<false, TILE_RD>(ap, bp0, bp1, kstride, KBe, acc0, acc1);
+    if (TILE_PAIR && nt1 >= 0) gemm_loop<true, TILE_RD>(ap, bp0, bp1, kstride, KBe, acc0, acc1, pre);
+    else gemm_loop<false, TILE_RD>(ap, bp0, bp1, kstride, KBe, acc0, acc1, pre);
     // (see kblocks_tile: rare widths; one k-block without a ring behind the loop.  A second loop instance with a ring of PF for
     //  them -- never executed on the benchmark's network -- cost it 3 %: 1.069 against 1.038 ms on one box)
     if (KB & 1) {
@@ -325,24 +342,29 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
         for (int nt = wave; nt < NT; nt += TILE_STEP) {
             const int nt1 = TILE_PAIR && nt + NWAVE < NT ? nt + NWAVE : -1;
             f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            // epilogue operands (x-only context) are requested before the MFMA loops so that their
-            // HBM/L2 latency is hidden behind them
+            // epilogue operands (x-only context): requested in front of the MFMA loops so that their HBM/L2 latency is hidden
+            // behind them, but behind the first weight fragments of the unit (gemm_loop, `pre`).  Every lane loads, rows and
+            // columns outside the tile from row 0 / column 0 of it: a load under a branch cannot be counted by the wait in
+            // front of the first MFMA, which then assumes none was issued and waits for all of them.  The epilogues read the
+            // operands of real rows and columns only.
             float czu[2][4], cgt[2][4], wz[2];
+            auto operands = [&] {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int tile = h == 0 ? nt : nt1;
-                const int col = tile * 16 + r16;
-                wz[h] = last && tile >= 0 && col < wi ? wzL[col] : 0.f;
+                for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
+                    const int tile = h == 0 ? nt : nt1;
+                    const int col = tile * 16 + r16;
+                    const int cc = tile >= 0 && col < wi ? col : 0;
+                    wz[h] = wzL[last ? cc : 0];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 4 * q + r;
-                    const bool ok = tile >= 0 && row < rows && col < wi;
-                    const float *c = ctx + (size_t)(ok ? row : 0) * C;
-                    czu[h][r] = ok ? c[a.zu_off[i] + col] : 0.f;
-                    cgt[h][r] = ok ? c[a.gate_off[i + 1] + col] : 0.f;
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 4 * q + r;
+                        const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
+                        czu[h][r] = c[a.zu_off[i] + cc];
+                        cgt[h][r] = c[a.gate_off[i + 1] + cc];
+                    }
                 }
-            }
-            gemm_tiles(lds + a.aop_off[i], ldY, Wy, KBy, NT, nt, nt1, acc[0], acc[1]);
+            };
+            gemm_tiles(lds + a.aop_off[i], ldY, Wy, KBy, NT, nt, nt1, acc[0], acc[1], operands);
             if (i > 0)
                 gemm_tiles(lds + a.zb_off[i - 1], a.zb_ld[i - 1], a.wpack + a.w_zu_f[i],
                            kblocks_tile(a.width[i - 1]), NT, nt, nt1, acc[0], acc[1]);
@@ -389,20 +411,25 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                 const int nt1 = TILE_PAIR && nt + NWAVE < NTy ? nt + NWAVE : -1;
                 f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                 float cyu[2][4], cyL[2][4], wy[2];
+                // (not the first backward phase: cyL is not used; its loads repeat cyu's addresses)
+                const int offL = first ? a.yu_off[L] : a.yu_off[i];
+                auto operands = [&] {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int tile = h == 0 ? nt : nt1;
-                    const int col = tile * 16 + r16;
-                    wy[h] = first && tile >= 0 && col < n ? wyL[col] : 0.f;
+                    for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
+                        const int tile = h == 0 ? nt : nt1;
+                        const int col = tile * 16 + r16;
+                        const int cc = tile >= 0 && col < n ? col : 0;
+                        wy[h] = wyL[first ? cc : 0];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 4 * q + r;
-                        const bool ok = tile >= 0 && row < rows && col < n;
-                        cyu[h][r] = ok ? ctx[(size_t)row * C + a.yu_off[i] + col] : 0.f;
-                        cyL[h][r] = ok && first ? ctx[(size_t)row * C + a.yu_off[L] + col] : 0.f;
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = 4 * q + r;
+                            const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
+                            cyu[h][r] = c[a.yu_off[i] + cc];
+                            cyL[h][r] = c[offL + cc];
+                        }
                     }
-                }
-                gemm_tiles(delta, ldd, Wt, KB, NTy, nt, nt1, acc[0], acc[1]);
+                };
+                gemm_tiles(delta, ldd, Wt, KB, NTy, nt, nt1, acc[0], acc[1], operands);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int tile = h == 0 ? nt : nt1;
@@ -430,18 +457,20 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                 const int nt1 = TILE_PAIR && nt + NWAVE < NTp ? nt + NWAVE : -1;
                 f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                 float cga[2][4];
+                auto operands = [&] {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int tile = h == 0 ? nt : nt1;
-                    const int col = tile * 16 + r16;
+                    for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
+                        const int tile = h == 0 ? nt : nt1;
+                        const int col = tile * 16 + r16;
+                        const int cc = tile >= 0 && col < wp ? col : 0;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 4 * q + r;
-                        const bool ok = tile >= 0 && row < rows && col < wp;
-                        cga[h][r] = ok ? ctx[(size_t)row * C + a.gate_off[i] + col] : 0.f;
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = 4 * q + r;
+                            cga[h][r] = ctx[(size_t)(row < rows ? row : 0) * C + a.gate_off[i] + cc];
+                        }
                     }
-                }
-                gemm_tiles(delta, ldd, Wt, KB, NTp, nt, nt1, acc[0], acc[1]);
+                };
+                gemm_tiles(delta, ldd, Wt, KB, NTp, nt, nt1, acc[0], acc[1], operands);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int tile = h == 0 ? nt : nt1;

@@ -301,6 +301,19 @@ ICNN_BE_API int icnn_be_fc_fg(const icnn_be_fc_model *model, const float *ctx, c
 ICNN_BE_API int icnn_be_solve_fc(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
                      float *f_work, float *g_work, void *stream);
 
+/*
+ * icnn_be_solve_fc with the reset of the solve inside it: bit for bit
+ *     st->y <- y0 ; icnn_be_state_init(st) ; icnn_be_solve_fc(model, ctx, st, f_work, g_work)
+ * where row u of st->y starts from y0[u] (device, [B][n] float64; y0 may be st->y itself: the rows stay) or, with
+ * y0 == NULL, from the constant y0_fill.  Where the solve begins with a persistent kernel (ICNN_BE_PATH_ROWS,
+ * ICNN_BE_PATH_TILE) the workgroup that owns a sample for the whole solve writes its y row and control words in front of
+ * round 0: one launch per solve instead of three and no separate pass over y.  On the other plans the entry enqueues the
+ * reset itself in front of the first round.  st->pending is only reset there (nothing else writes it).  Same return
+ * values and error codes as icnn_be_solve_fc; no host synchronisation, capturable in a HIP graph.  (Added within ABI 12.)
+ */
+ICNN_BE_API int icnn_be_solve_fc_reset(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
+                     float *f_work, float *g_work, const double *y0, double y0_fill, void *stream);
+
 /* ---- x-only context producer and weight clamps ------------------------ */
 
 /*
