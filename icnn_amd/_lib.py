@@ -70,6 +70,8 @@ EXPORTS = [
     "icnn_be_replay_enqueue", "icnn_be_replay_sample",
     "icnn_be_gd_eval_work_bytes", "icnn_be_gd_eval", "icnn_be_macro_f1", "icnn_be_keep_best",
     "icnn_be_dataset_draw", "icnn_be_log_row",
+    "icnn_be_ddpg_param_floats", "icnn_be_ddpg_work_bytes", "icnn_be_ddpg_work_offsets", "icnn_be_ddpg_chain", "icnn_be_ddpg_grads",
+    "icnn_be_ddpg_update", "icnn_be_ddpg_step", "icnn_be_ddpg_act", "icnn_be_ddpg_q",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -87,6 +89,11 @@ DATASET_ST_STATE = 1
 LOG_MAX_COLUMNS = 8                        # ICNN_BE_LOG_MAX_COLUMNS
 LOG_CTRL_INTS = 4                          # ICNN_BE_LOG_CTRL_INTS: the cursor
 LOG_KIND = {"float32": 0, "float64": 1, "int32": 2}     # ICNN_BE_LOG_F32 / _F64 / _I32
+DDPG_MAX_OBS, DDPG_MAX_ACT, DDPG_MAX_HIDDEN = 600, 32, 600     # ICNN_BE_DDPG_MAX_*
+DDPG_STEP_INTS = 4                         # ICNN_BE_DDPG_STEP_INTS: updates of the critic, of the policy, the ticket
+# ICNN_BE_DDPG_W_*: the pieces of the DDPG workspace, in order
+DDPG_WORK = ["a2", "y", "q", "td", "a", "qpi", "xa", "h2q", "d3q", "d2q", "d1q", "h1p", "h2p", "h2c", "d3p", "d2p", "d1p", "sq",
+             "upd"]
 
 
 def replay_stage_bytes(dimO, dimA):
@@ -196,6 +203,19 @@ class StepLog(C.Structure):
     _fields_ = [
         ("rows", C.c_void_p), ("ctrl", C.c_void_p), ("cap", C.c_int), ("width", C.c_int),
         ("col", C.c_void_p * LOG_MAX_COLUMNS), ("kind", C.c_int * LOG_MAX_COLUMNS),
+    ]
+
+
+class DdpgArgs(C.Structure):
+    """struct icnn_be_ddpg_args"""
+    _fields_ = [
+        ("batch", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("l1", C.c_int), ("l2", C.c_int),
+        ("obs", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p), ("ob2", C.c_void_p), ("term", C.c_void_p),
+        ("theta_q", C.c_void_p), ("theta_p", C.c_void_p), ("target_q", C.c_void_p), ("target_p", C.c_void_p),
+        ("m_q", C.c_void_p), ("v_q", C.c_void_p), ("m_p", C.c_void_p), ("v_p", C.c_void_p),
+        ("grad_q", C.c_void_p), ("grad_p", C.c_void_p), ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
+        ("rate", C.c_double), ("prate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float), ("pl2norm", C.c_float),
     ]
 
 
@@ -396,6 +416,20 @@ def load():
     lib.icnn_be_dataset_draw.restype = C.c_int
     lib.icnn_be_log_row.argtypes = [C.POINTER(StepLog), C.c_void_p]
     lib.icnn_be_log_row.restype = C.c_int
+    DA = C.POINTER(DdpgArgs)
+    lib.icnn_be_ddpg_param_floats.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong)] * 2
+    lib.icnn_be_ddpg_param_floats.restype = C.c_int
+    lib.icnn_be_ddpg_work_bytes.argtypes = [C.c_int] * 5
+    lib.icnn_be_ddpg_work_bytes.restype = C.c_size_t
+    lib.icnn_be_ddpg_work_offsets.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_longlong * len(DDPG_WORK))]
+    lib.icnn_be_ddpg_work_offsets.restype = C.c_int
+    for name in ("chain", "grads", "update", "step"):
+        fn = getattr(lib, "icnn_be_ddpg_" + name)
+        fn.argtypes, fn.restype = [DA, C.c_void_p], C.c_int
+    lib.icnn_be_ddpg_act.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_ddpg_act.restype = C.c_int
+    lib.icnn_be_ddpg_q.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_ddpg_q.restype = C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -431,6 +465,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_replay differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(10) != C.sizeof(Dataset) or lib.icnn_be_struct_size(11) != C.sizeof(StepLog):
         raise ImportError("ctypes struct layout of icnn_be_dataset / icnn_be_step_log differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(13) != C.sizeof(DdpgArgs):
+        raise ImportError("ctypes struct layout of icnn_be_ddpg_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

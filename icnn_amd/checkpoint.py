@@ -8,7 +8,8 @@ result depends on:
     every trainer        theta, Adam's m and v, the device step count; the BatchNorm moving statistics of a model that has them
     BundleTrainer        with skip_on_error, the gate words (the skipped count among them)
     CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step)
-    Agent                its CriticTrainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
+    ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
+    Agent, DDPGAgent     its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
                          with memory=True, the filled part of the four replay arrays and the control block (cursor, fill, draw
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
                          then resets it
@@ -81,14 +82,18 @@ def spec_json(spec) -> str:
 # What each object's state is made of
 # --------------------------------------------------------------------------------------------- #
 def _kind(obj) -> str:
-    from . import ficnn, rl_agent, rl_train, train
+    from . import ddpg, ficnn, rl_agent, rl_train, train
     for cls, kind in ((train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
                       (train.ConvGDTrainer, "ConvGDTrainer"), (ficnn.GDTrainer, "ficnn.GDTrainer"),
-                      (rl_train.CriticTrainer, "CriticTrainer"), (rl_agent.Agent, "Agent")):
+                      (rl_train.CriticTrainer, "CriticTrainer"), (rl_agent.Agent, "Agent"),
+                      (ddpg.DDPGTrainer, "DDPGTrainer"), (rl_agent.DDPGAgent, "DDPGAgent")):
         if isinstance(obj, cls):
             return kind
-    raise TypeError("checkpoint serves BundleTrainer, GDTrainer, ConvGDTrainer, ficnn.GDTrainer, CriticTrainer and Agent, got %s"
-                    % type(obj).__name__)
+    raise TypeError("checkpoint serves BundleTrainer, GDTrainer, ConvGDTrainer, ficnn.GDTrainer, CriticTrainer, Agent, "
+                    "DDPGTrainer and DDPGAgent, got %s" % type(obj).__name__)
+
+
+AGENTS = {"Agent": "CriticTrainer", "DDPGAgent": "DDPGTrainer"}     # an agent's kind -> its trainer's
 
 
 def _model_stats(prefix, model, out):
@@ -99,6 +104,12 @@ def _model_stats(prefix, model, out):
 
 def _trainer_tensors(kind, obj) -> dict:
     """name -> the live device tensor, for everything of a trainer that is a device tensor"""
+    if kind == "DDPGTrainer":
+        out = {"theta/" + w: t for w, t in obj.theta.items()}
+        for w in "pq":
+            out["m/" + w], out["v/" + w] = obj.m[w], obj.v[w]
+        out["step"] = obj.step_count
+        return out
     out = {"theta": obj.opt.theta, "m": obj.opt.m, "v": obj.opt.v, "step": obj.opt.step_count}
     if kind == "CriticTrainer":
         _model_stats("", obj.critic, out)
@@ -120,6 +131,8 @@ def _keeper_tensors(keeper) -> dict:
 
 def _arena_owners(kind, obj, keeper):
     """(theta, arena, ParamMap) of every arena that load() rewrites from its theta"""
+    if AGENTS.get(kind, kind) == "DDPGTrainer":              # the DDPG kernels read the flat vectors themselves
+        return []
     trainer = obj.trainer if kind == "Agent" else obj
     owners = [(trainer.opt.theta, trainer.opt.arena, trainer.opt.map)]
     if kind in ("CriticTrainer", "Agent"):
@@ -185,18 +198,18 @@ def save(path, obj, keeper=None, memory=True, dataset=None):
     """Write a checkpoint of `obj` (and of `keeper`, a train.BestKeeper on it, and of `dataset`, the train.DeviceDataset that
     feeds it) to `path`.  Reads the device: one wait.  memory (the Agent only): include the replay memory."""
     kind = _kind(obj)
-    trainer = obj.trainer if kind == "Agent" else obj
+    trainer = obj.trainer if kind in AGENTS else obj
     if keeper is not None and keeper.opt is not trainer.opt:
         raise ValueError("keeper: it keeps another trainer's model")
     arrays = {"kind": np.asarray(kind), "spec": np.asarray(spec_json(trainer.spec)),
               "has_keeper": np.asarray(int(keeper is not None), np.int64)}
-    tensors = _trainer_tensors("CriticTrainer" if kind == "Agent" else kind, trainer)
+    tensors = _trainer_tensors(AGENTS.get(kind, kind), trainer)
     if keeper is not None:
         arrays["keeper/mode"] = np.asarray(keeper.mode)
         tensors.update(_keeper_tensors(keeper))
     for name, t in tensors.items():
         arrays[name] = t.detach().cpu().numpy()
-    if kind == "Agent":
+    if kind in AGENTS:
         arrays.update(_agent_host(obj, bool(memory)))
     if dataset is not None:
         arrays.update(_dataset_host(dataset))
@@ -242,7 +255,7 @@ def load(path, obj, keeper=None, dataset=None):
     state exactly when the call gives one."""
     import torch
     kind = _kind(obj)
-    trainer = obj.trainer if kind == "Agent" else obj
+    trainer = obj.trainer if kind in AGENTS else obj
     if keeper is not None and keeper.opt is not trainer.opt:
         raise ValueError("keeper: it keeps another trainer's model")
     arrays = read_arrays(path)
@@ -258,7 +271,7 @@ def load(path, obj, keeper=None, dataset=None):
     if has_keeper != (keeper is not None):
         raise ValueError("keeper: the file %s a keeper's state, the call %s a keeper"
                          % ("holds" if has_keeper else "does not hold", "gives" if keeper is not None else "gives no"))
-    tensors = _trainer_tensors("CriticTrainer" if kind == "Agent" else kind, trainer)
+    tensors = _trainer_tensors(AGENTS.get(kind, kind), trainer)
     if keeper is not None:
         if "keeper/mode" not in arrays or str(arrays["keeper/mode"]) != keeper.mode:
             raise ValueError("keeper/mode: the file's keeper is %s, this one %r" % (arrays.get("keeper/mode"), keeper.mode))
@@ -281,7 +294,7 @@ def load(path, obj, keeper=None, dataset=None):
         if _scalar(arrays, "data/draws") != int(data_ctrl[0]):
             raise ValueError("data/draws: %d in the file, its control block says %d" % (_scalar(arrays, "data/draws"), data_ctrl[0]))
     host = None
-    if kind == "Agent":
+    if kind in AGENTS:
         mem = obj.memory
         for name, mine in (("memory/rmsize", mem.size), ("memory/dimO", mem.dimO), ("memory/dimA", mem.dimA)):
             if _scalar(arrays, name) != mine:
@@ -318,7 +331,7 @@ def load(path, obj, keeper=None, dataset=None):
         if dataset is not None:
             dataset.ctrl.copy_(torch.from_numpy(arrays["data/ctrl"]))
             dataset.draws = int(arrays["data/ctrl"][0])
-        if kind == "Agent":
+        if kind in AGENTS:
             mem = obj.memory
             obj.t, obj._trained = int(host["t"]), bool(host["trained"])
             obj.noise = arrays["agent/noise"].copy()

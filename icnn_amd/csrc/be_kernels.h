@@ -395,4 +395,16 @@ struct DatasetDrawLaunch {
 hipError_t launch_dataset_draw(const DatasetDrawLaunch &l, hipStream_t stream);
 hipError_t launch_log_row(const icnn_be_step_log &L, hipStream_t stream);
 
+// ---- the DDPG step (be_ddpg.hip) ----------------------------------------------------
+long long ddpg_policy_floats(int dimO, int dimA, int l1, int l2);
+long long ddpg_critic_floats(int dimO, int dimA, int l1, int l2);
+bool ddpg_fits(int dimO, int dimA, int l1, int l2);      // the chain kernel's LDS
+// floats of the workspace; off (or NULL): the float offset of each ICNN_BE_DDPG_W_* piece
+size_t ddpg_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
+hipError_t launch_ddpg_chain(const icnn_be_ddpg_args &d, hipStream_t stream);
+hipError_t launch_ddpg_grads(const icnn_be_ddpg_args &d, hipStream_t stream);
+hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStream_t stream);
+hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, const float *theta, const float *obs,
+                               const double *act, int B, float *out, hipStream_t stream);
+
 }  // namespace icnn_be

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, rl_adam, rl_train
+from . import _lib, ddpg, rl_adam, rl_train
 
 
 class ReplayMemory:
@@ -110,48 +110,36 @@ class ReplayMemory:
             raise RuntimeError("replay memory: the device control block was outside the arrays (status %d)" % st)
 
 
-class Agent:
-    """`Agent` of RL/src/icnn.py with the adam inner optimiser: critic and target are picnn.FCModel of one spec with
-    action_box False.  The constructor builds the CriticTrainer at minibatch size `bsize` (lr, tau, discount, l2norm, wd and
-    max_iter go to it), initialises it as the reference does (:139-142: makeCvx, then target <- critic) and builds the
-    ReplayMemory of `rmsize` transitions.  seed: the exploration noise's np.random.RandomState and the memory's sampler.
+class _AgentCycle:
+    """What the agents share: the replay memory, the Ornstein-Uhlenbeck noise, observe() and the `iters` training iterations
+    per observation, eager or captured.  A subclass builds self.trainer (obs / act / rew / ob2 / term buffers, step_buffers(),
+    loss) and calls _setup()."""
 
-    capture=True: the first training observe() runs its `iters` iterations eagerly; the next one captures them once into a
-    graph (a linear chain of [sample, step] x iters) and every later observe() replays it."""
-
-    def __init__(self, critic, target, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1, seed=0,
-                 capture=False, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000):
-        if warmup < 2:
-            raise ValueError("warmup must be at least 2: the sampler needs two transitions, got %r" % (warmup,))
-        if iters < 0:
-            raise ValueError("iters must not be negative")
-        self.trainer = rl_train.CriticTrainer(critic, target, bsize, lr=lr, tau=tau, discount=discount, l2norm=l2norm, wd=wd,
-                                              max_iter=max_iter)
-        self.trainer.initialise()
-        self.critic, self.spec, self.device = critic, critic.spec, critic.device
-        self.dimO, self.dimA = self.spec.n_features, self.spec.n_labels
+    def _setup(self, dimO, dimA, device, warmup, iters, rmsize, outheta, ousigma, seed, capture):
+        self.dimO, self.dimA, self.device = int(dimO), int(dimA), device
         self.memory = ReplayMemory(rmsize, self.dimO, self.dimA, self.device, seed)
         self.warmup, self.iters, self.outheta, self.ousigma = int(warmup), int(iters), float(outheta), float(ousigma)
         self.rng = np.random.RandomState(seed)
         self.capture = bool(capture)
-        self._solver = rl_adam.AdamSolver(critic, 1, max_iter)
         self._graph, self._trained = None, False
         self.noise = np.zeros(self.dimA)
         self.observation = self.action = None
         self.t = 0                           # observations seen in training (icnn.py:146)
+
+    @staticmethod
+    def _check_cycle(warmup, iters):
+        if warmup < 2:
+            raise ValueError("warmup must be at least 2: the sampler needs two transitions, got %r" % (warmup,))
+        if iters < 0:
+            raise ValueError("iters must not be negative")
 
     def reset(self, obs):
         """icnn.py:260-262"""
         self.noise = np.zeros(self.dimA)
         self.observation = obs
 
-    def act(self, test=False):
-        """icnn.py:264-288: the inner Adam on the critic at the current observation (inference-mode BatchNorm), plus the
-        Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns float64 [dimA]; the copy to the host is the one
-        synchronisation of an environment step."""
-        obs = torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO))
-        ctx = self.critic.context(obs, bn="moving") if self.spec.batchnorm else self.critic.context(obs)
-        action = self._solver.solve(ctx).act_best.cpu().numpy()
+    def _explore(self, action, test):
+        """the raw action [1, dimA] (float64, host) plus the Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1]"""
         if not test:
             self.noise -= self.outheta * self.noise - self.ousigma * self.rng.randn(self.dimA)
             action += self.noise
@@ -185,7 +173,7 @@ class Agent:
         self._graph.replay()
 
     def train(self) -> torch.Tensor:
-        """icnn.py:304-323: a minibatch from the memory into the trainer's buffers and one critic step.  Returns the
+        """icnn.py:304-323: a minibatch from the memory into the trainer's buffers and one training step.  Returns the
         trainer's device loss scalar, without a host wait."""
         self.memory.sample_into(self.trainer)
         return self.trainer.step_buffers()
@@ -194,3 +182,57 @@ class Agent:
     def loss(self) -> torch.Tensor:
         """the last training iteration's loss (the trainer's 0-d device tensor)"""
         return self.trainer.loss
+
+
+class Agent(_AgentCycle):
+    """`Agent` of RL/src/icnn.py with the adam inner optimiser: critic and target are picnn.FCModel of one spec with
+    action_box False.  The constructor builds the CriticTrainer at minibatch size `bsize` (lr, tau, discount, l2norm, wd and
+    max_iter go to it), initialises it as the reference does (:139-142: makeCvx, then target <- critic) and builds the
+    ReplayMemory of `rmsize` transitions.  seed: the exploration noise's np.random.RandomState and the memory's sampler.
+
+    capture=True: the first training observe() runs its `iters` iterations eagerly; the next one captures them once into a
+    graph (a linear chain of [sample, step] x iters) and every later observe() replays it."""
+
+    def __init__(self, critic, target, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1, seed=0,
+                 capture=False, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000):
+        self._check_cycle(warmup, iters)
+        self.trainer = rl_train.CriticTrainer(critic, target, bsize, lr=lr, tau=tau, discount=discount, l2norm=l2norm, wd=wd,
+                                              max_iter=max_iter)
+        self.trainer.initialise()
+        self.critic, self.spec = critic, critic.spec
+        self._setup(self.spec.n_features, self.spec.n_labels, critic.device, warmup, iters, rmsize, outheta, ousigma, seed,
+                    capture)
+        self._solver = rl_adam.AdamSolver(critic, 1, max_iter)
+
+    def act(self, test=False):
+        """icnn.py:264-288: the inner Adam on the critic at the current observation (inference-mode BatchNorm), plus the
+        Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns float64 [dimA]; the copy to the host is the one
+        synchronisation of an environment step."""
+        obs = torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO))
+        ctx = self.critic.context(obs, bn="moving") if self.spec.batchnorm else self.critic.context(obs)
+        action = self._solver.solve(ctx).act_best.cpu().numpy()
+        return self._explore(action, test)
+
+
+class DDPGAgent(_AgentCycle):
+    """`Agent` of RL/src/ddpg.py around ddpg.DDPGTrainer: the same reset / act / observe / train cycle, memory,
+    noise and capture as Agent; act() is one launch of the policy at the current observation (icnn_be_ddpg_act).  l1, l2,
+    rate, prate, tau, discount, l2norm and pl2norm go to the trainer; seed also draws its initial weights."""
+
+    def __init__(self, dimO, dimA, l1=200, l2=200, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1,
+                 seed=0, capture=False, rate=1e-3, prate=1e-4, tau=0.01, discount=0.99, l2norm=1e-4, pl2norm=0.0,
+                 device="cuda"):
+        self._check_cycle(warmup, iters)
+        self.trainer = ddpg.DDPGTrainer(dimO, dimA, l1, l2, batch=bsize, rate=rate, prate=prate, tau=tau, discount=discount,
+                                        l2norm=l2norm, pl2norm=pl2norm, seed=seed, device=device)
+        self.spec = self.trainer.spec
+        self._setup(dimO, dimA, self.trainer.device, warmup, iters, rmsize, outheta, ousigma, seed, capture)
+        self._obs1 = torch.zeros(1, self.dimO, dtype=torch.float32, device=self.device)
+        self._act1 = torch.zeros(1, self.dimA, dtype=torch.float32, device=self.device)
+
+    def act(self, test=False):
+        """ddpg.py:129-134: pi(observation), plus the Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns
+        float64 [dimA]; the copy to the host is the one synchronisation of an environment step."""
+        self._obs1.copy_(torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO)))
+        action = self.trainer.policy(self._obs1, out=self._act1).cpu().numpy().astype(np.float64)
+        return self._explore(action, test)

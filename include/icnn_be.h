@@ -224,7 +224,7 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
  * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
- * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -1221,6 +1221,94 @@ ICNN_BE_API int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const ic
  * a device.
  */
 ICNN_BE_API int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]);
+
+/* ---- the DDPG agent: fused actor-critic step, EMA targets, act (be_ddpg.hip, additive to ABI 12) ---- */
+
+/*
+ * DDPG of RL/src/ddpg.py with the networks of ddpg_nets_dm.py, all float32.  A net is one flat vector in the order W1, b1,
+ * W2, b2, W3, b3, every W row-major [in][out]:
+ *   policy  a = tanh(relu(relu(o W1 + b1) W2 + b2) W3 + b3)          W1 [dimO][l1], W2 [l1][l2], W3 [l2][dimA]
+ *   critic  q = relu([relu(o W1 + b1), a] W2 + b2) W3 + b3           W1 [dimO][l1], W2 [l1 + dimA][l2], W3 [l2][1]
+ * One step on the minibatch (obs, act, rew, ob2, term), everything read from the parameters as they are when it begins:
+ *   a2 = pi(ob2; target_p), q2 = Q(ob2, a2; target_q), y = term ? rew : rew + discount q2
+ *   td = Q(obs, act; theta_q) - y, loss_q = mean td^2 + l2norm sum theta_q^2 / 2 (all six variables), g_q = d loss_q / d theta_q
+ *   loss_p = -mean Q(obs, pi(obs; theta_p); theta_q) + pl2norm sum theta_p^2 / 2, g_p = d loss_p / d theta_p
+ *   TF-Adam on both nets (icnn_be_param_update's element arithmetic with eps as given and no proj; lr = rate for theta_q,
+ *   prate for theta_p; each net its own m, v and step count), then target <- target - tau (target - theta_new).
+ * icnn_be_ddpg_chain does the per-sample part (one launch) and leaves the layer inputs and pre-activation deltas in the
+ * workspace; icnn_be_ddpg_grads forms grad_q and grad_p from them (one launch, one fma chain over the batch per element, no atomics);
+ * icnn_be_ddpg_update updates both nets and both targets in one launch and writes loss_q; icnn_be_ddpg_step is the three in
+ * that order.  act: float64, rounded to float32 once on load.
+ *
+ * The workspace: icnn_be_ddpg_work_bytes bytes, 16-byte aligned; icnn_be_ddpg_work_offsets gives the offset in floats of
+ * each piece ICNN_BE_DDPG_W_* ([batch][width] float32 unless said otherwise); the chain writes nothing outside the rows
+ * < batch of its pieces.  step: ICNN_BE_DDPG_STEP_INTS int32, zero for fresh nets: [0] updates of the critic, [1] of the
+ * policy, [2] a ticket (zero between launches); a captured step replayed k times is k steps.
+ *
+ * Sizes: 1 <= dimO <= ICNN_BE_DDPG_MAX_OBS, 1 <= dimA <= ICNN_BE_DDPG_MAX_ACT, 1 <= l1, l2 <= ICNN_BE_DDPG_MAX_HIDDEN,
+ * batch >= 1.  EINVAL for anything else, a NULL or misaligned pointer (the nets, m, v, the gradients and work 16 bytes, act 8,
+ * the rest 4), tau outside [0, 1], a non-finite discount, a negative or non-finite l2norm / pl2norm, beta outside [0, 1),
+ * eps <= 0, a non-finite rate, before anything is launched.  No entry synchronises; all are capturable.
+ */
+#define ICNN_BE_DDPG_MAX_OBS 600
+#define ICNN_BE_DDPG_MAX_ACT 32
+#define ICNN_BE_DDPG_MAX_HIDDEN 600
+#define ICNN_BE_DDPG_STEP_INTS 4
+#define ICNN_BE_DDPG_W_A2 0    /* pi(ob2; target_p) [dimA] */
+#define ICNN_BE_DDPG_W_Y 1     /* y [1] */
+#define ICNN_BE_DDPG_W_Q 2     /* Q(obs, act) [1] */
+#define ICNN_BE_DDPG_W_TD 3    /* td [1] */
+#define ICNN_BE_DDPG_W_A 4     /* pi(obs) [dimA] */
+#define ICNN_BE_DDPG_W_QPI 5   /* Q(obs, pi(obs)) [1] */
+#define ICNN_BE_DDPG_W_XA 6    /* the critic's [h1, act] [l1 + dimA] */
+#define ICNN_BE_DDPG_W_H2Q 7   /* the critic's h2 at (obs, act) [l2] */
+#define ICNN_BE_DDPG_W_D3Q 8   /* the critic's deltas: 2 td / batch [1], [l2], [l1] */
+#define ICNN_BE_DDPG_W_D2Q 9
+#define ICNN_BE_DDPG_W_D1Q 10
+#define ICNN_BE_DDPG_W_H1P 11  /* the policy's h1 [l1], h2 [l2] at obs */
+#define ICNN_BE_DDPG_W_H2P 12
+#define ICNN_BE_DDPG_W_H2C 13  /* the critic's h2 at (obs, pi(obs)) [l2] */
+#define ICNN_BE_DDPG_W_D3P 14  /* the policy's deltas [dimA], [l2], [l1] */
+#define ICNN_BE_DDPG_W_D2P 15
+#define ICNN_BE_DDPG_W_D1P 16
+#define ICNN_BE_DDPG_W_SQ 17   /* float64 [tiles of 16 samples]: each tile's sum of td^2 */
+#define ICNN_BE_DDPG_W_UPD 18  /* float64: the update's partial sums of theta_q^2 */
+#define ICNN_BE_DDPG_WORK_PIECES 19
+typedef struct icnn_be_ddpg_args {
+    int batch, dimO, dimA, l1, l2;
+    const float *obs;                 /* [batch][dimO] */
+    const double *act;                /* [batch][dimA] */
+    const float *rew;                 /* [batch] */
+    const float *ob2;                 /* [batch][dimO] */
+    const unsigned char *term;        /* [batch] */
+    float *theta_q, *theta_p, *target_q, *target_p;
+    float *m_q, *v_q, *m_p, *v_p;     /* Adam's moments */
+    float *grad_q, *grad_p;           /* the step's gradients, before the decay term */
+    int *step;                        /* [ICNN_BE_DDPG_STEP_INTS] */
+    float *loss;                      /* loss_q of the step */
+    void *work;
+    double rate, prate, beta1, beta2;
+    float eps, tau, discount, l2norm, pl2norm;
+} icnn_be_ddpg_args;                  /* icnn_be_struct_size(13) */
+
+/* floats of theta_p (*np) and theta_q (*nq); EINVAL for sizes out of range */
+ICNN_BE_API int icnn_be_ddpg_param_floats(int dimO, int dimA, int l1, int l2, long long *np, long long *nq);
+/* 0 for sizes out of range */
+ICNN_BE_API size_t icnn_be_ddpg_work_bytes(int batch, int dimO, int dimA, int l1, int l2);
+ICNN_BE_API int icnn_be_ddpg_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_DDPG_WORK_PIECES]);
+ICNN_BE_API int icnn_be_ddpg_chain(const icnn_be_ddpg_args *a, void *stream);
+ICNN_BE_API int icnn_be_ddpg_grads(const icnn_be_ddpg_args *a, void *stream);
+ICNN_BE_API int icnn_be_ddpg_update(const icnn_be_ddpg_args *a, void *stream);
+ICNN_BE_API int icnn_be_ddpg_step(const icnn_be_ddpg_args *a, void *stream);
+/*
+ * out[batch][dimA] = pi(obs; theta_p): what act() pays per environment step, one workgroup per 16 observations (batch 1:
+ * one workgroup), the bits of the chain's ICNN_BE_DDPG_W_A.  icnn_be_ddpg_q: out[batch] = Q(obs, act; theta_q), the bits of
+ * ICNN_BE_DDPG_W_Q.  EINVAL as above (theta 16 bytes, act 8, obs and out 4).
+ */
+ICNN_BE_API int icnn_be_ddpg_act(int dimO, int dimA, int l1, int l2, const float *theta_p, const float *obs, int batch, float *out,
+                                 void *stream);
+ICNN_BE_API int icnn_be_ddpg_q(int dimO, int dimA, int l1, int l2, const float *theta_q, const float *obs, const double *act,
+                               int batch, float *out, void *stream);
 
 #ifdef __cplusplus
 }
