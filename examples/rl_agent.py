@@ -1,11 +1,11 @@
 """The RL experiment's loop (RL/src/main.py:82-149) around icnn_amd.rl_agent.Agent (--model ICNN, the default) or
-icnn_amd.rl_agent.DDPGAgent (--model DDPG; RL/src/main.py:49-57) on a small built-in environment: test
+icnn_amd.rl_agent.DDPGAgent / NAFAgent (--model DDPG / NAF; RL/src/main.py:49-57) on a small built-in environment: test
 episodes, then training episodes until the next multiple of --train, up to --total training steps, with --tmax and the
 returns logged.  The environment is NumPy: a damped point mass in dimA dimensions that the action pushes and the reward
 wants at the origin; the observation is (position, velocity), truncated or zero-padded to dimO.
 
     python examples/rl_agent.py [--total 2000] [--train 200] [--test 2] [--tmax 50] [--warmup 100] [--bsize 64] [--iter 1]
-                                [--dimO 4] [--dimA 2] [--capture] [--save FILE] [--resume FILE] [--model {ICNN,DDPG}]
+                                [--dimO 4] [--dimA 2] [--capture] [--save FILE] [--resume FILE] [--model {ICNN,DDPG,NAF}]
 
 --resume FILE restores the agent from a checkpoint before the loop (RL/src/icnn.py:134-137 restores the latest one at
 construction) and --save FILE writes one after it (RL/src/main.py:113-115): weights, optimiser state, noise, the random
@@ -89,11 +89,14 @@ def main():
     ap.add_argument("--capture", action="store_true")
     ap.add_argument("--save", default=None, metavar="FILE")
     ap.add_argument("--resume", default=None, metavar="FILE")
-    ap.add_argument("--model", choices=("ICNN", "DDPG"), default="ICNN")
+    ap.add_argument("--model", choices=("ICNN", "DDPG", "NAF"), default="ICNN")
     args = ap.parse_args()
     if args.model == "DDPG":
         agent = rl_agent.DDPGAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
                                    iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture)
+    elif args.model == "NAF":
+        agent = rl_agent.NAFAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
+                                  iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture)
     else:
         spec = dataclasses.replace(picnn.halfcheetah_spec(), n_features=args.dimO, n_labels=args.dimA,
                                    szs=(args.l1size, args.l2size), action_box=False)

@@ -72,6 +72,8 @@ EXPORTS = [
     "icnn_be_dataset_draw", "icnn_be_log_row",
     "icnn_be_ddpg_param_floats", "icnn_be_ddpg_work_bytes", "icnn_be_ddpg_work_offsets", "icnn_be_ddpg_chain", "icnn_be_ddpg_grads",
     "icnn_be_ddpg_update", "icnn_be_ddpg_step", "icnn_be_ddpg_act", "icnn_be_ddpg_q",
+    "icnn_be_naf_param_floats", "icnn_be_naf_work_bytes", "icnn_be_naf_work_offsets", "icnn_be_naf_chain", "icnn_be_naf_grads",
+    "icnn_be_naf_update", "icnn_be_naf_step", "icnn_be_naf_act", "icnn_be_naf_q",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -94,6 +96,11 @@ DDPG_STEP_INTS = 4                         # ICNN_BE_DDPG_STEP_INTS: updates of 
 # ICNN_BE_DDPG_W_*: the pieces of the DDPG workspace, in order
 DDPG_WORK = ["a2", "y", "q", "td", "a", "qpi", "xa", "h2q", "d3q", "d2q", "d1q", "h1p", "h2p", "h2c", "d3p", "d2p", "d1p", "sq",
              "upd"]
+NAF_MAX_OBS, NAF_MAX_ACT, NAF_MAX_HIDDEN = 600, 32, 600        # ICNN_BE_NAF_MAX_*
+NAF_STEP_INTS = 4                          # ICNN_BE_NAF_STEP_INTS: the updates, the ticket
+# ICNN_BE_NAF_W_*: the pieces of the NAF workspace, in order
+NAF_WORK = ["y", "u", "l", "ld", "h", "adv", "q", "td", "h1l", "h2l", "h1u", "h2u", "h1v", "h2v", "d3l", "d2l", "d1l", "d3u", "d2u",
+            "d1u", "d3v", "d2v", "d1v", "sq", "upd"]
 
 
 def replay_stage_bytes(dimO, dimA):
@@ -216,6 +223,20 @@ class DdpgArgs(C.Structure):
         ("grad_q", C.c_void_p), ("grad_p", C.c_void_p), ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
         ("rate", C.c_double), ("prate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
         ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float), ("pl2norm", C.c_float),
+    ]
+
+
+class NafArgs(C.Structure):
+    """struct icnn_be_naf_args"""
+    _fields_ = [
+        ("batch", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("l1", C.c_int), ("l2", C.c_int),
+        ("obs", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p), ("ob2", C.c_void_p), ("term", C.c_void_p),
+        ("theta_l", C.c_void_p), ("theta_u", C.c_void_p), ("theta_v", C.c_void_p), ("target_v", C.c_void_p),
+        ("m_l", C.c_void_p), ("v_l", C.c_void_p), ("m_u", C.c_void_p), ("v_u", C.c_void_p), ("m_v", C.c_void_p), ("v_v", C.c_void_p),
+        ("grad_l", C.c_void_p), ("grad_u", C.c_void_p), ("grad_v", C.c_void_p),
+        ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
+        ("rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float),
     ]
 
 
@@ -430,6 +451,20 @@ def load():
     lib.icnn_be_ddpg_act.restype = C.c_int
     lib.icnn_be_ddpg_q.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.icnn_be_ddpg_q.restype = C.c_int
+    NA = C.POINTER(NafArgs)
+    lib.icnn_be_naf_param_floats.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong)] * 3
+    lib.icnn_be_naf_param_floats.restype = C.c_int
+    lib.icnn_be_naf_work_bytes.argtypes = [C.c_int] * 5
+    lib.icnn_be_naf_work_bytes.restype = C.c_size_t
+    lib.icnn_be_naf_work_offsets.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_longlong * len(NAF_WORK))]
+    lib.icnn_be_naf_work_offsets.restype = C.c_int
+    for name in ("chain", "grads", "update", "step"):
+        fn = getattr(lib, "icnn_be_naf_" + name)
+        fn.argtypes, fn.restype = [NA, C.c_void_p], C.c_int
+    lib.icnn_be_naf_act.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_naf_act.restype = C.c_int
+    lib.icnn_be_naf_q.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_naf_q.restype = C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -467,6 +502,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_dataset / icnn_be_step_log differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(13) != C.sizeof(DdpgArgs):
         raise ImportError("ctypes struct layout of icnn_be_ddpg_args differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(14) != C.sizeof(NafArgs):
+        raise ImportError("ctypes struct layout of icnn_be_naf_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

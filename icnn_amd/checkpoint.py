@@ -9,7 +9,8 @@ result depends on:
     BundleTrainer        with skip_on_error, the gate words (the skipped count among them)
     CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step)
     ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
-    Agent, DDPGAgent     its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
+    naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count
+    Agent, DDPGAgent, NAFAgent   its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
                          with memory=True, the filled part of the four replay arrays and the control block (cursor, fill, draw
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
                          then resets it
@@ -82,18 +83,20 @@ def spec_json(spec) -> str:
 # What each object's state is made of
 # --------------------------------------------------------------------------------------------- #
 def _kind(obj) -> str:
-    from . import ddpg, ficnn, rl_agent, rl_train, train
+    from . import ddpg, ficnn, naf, rl_agent, rl_train, train
     for cls, kind in ((train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
                       (train.ConvGDTrainer, "ConvGDTrainer"), (ficnn.GDTrainer, "ficnn.GDTrainer"),
                       (rl_train.CriticTrainer, "CriticTrainer"), (rl_agent.Agent, "Agent"),
-                      (ddpg.DDPGTrainer, "DDPGTrainer"), (rl_agent.DDPGAgent, "DDPGAgent")):
+                      (ddpg.DDPGTrainer, "DDPGTrainer"), (rl_agent.DDPGAgent, "DDPGAgent"),
+                      (naf.NAFTrainer, "NAFTrainer"), (rl_agent.NAFAgent, "NAFAgent")):
         if isinstance(obj, cls):
             return kind
     raise TypeError("checkpoint serves BundleTrainer, GDTrainer, ConvGDTrainer, ficnn.GDTrainer, CriticTrainer, Agent, "
-                    "DDPGTrainer and DDPGAgent, got %s" % type(obj).__name__)
+                    "DDPGTrainer, DDPGAgent, NAFTrainer and NAFAgent, got %s" % type(obj).__name__)
 
 
-AGENTS = {"Agent": "CriticTrainer", "DDPGAgent": "DDPGTrainer"}     # an agent's kind -> its trainer's
+FLAT_TRAINERS = ("DDPGTrainer", "NAFTrainer")               # trainers whose state is flat vectors in dicts theta, m, v
+AGENTS = {"Agent": "CriticTrainer", "DDPGAgent": "DDPGTrainer", "NAFAgent": "NAFTrainer"}     # an agent's kind -> its trainer's
 
 
 def _model_stats(prefix, model, out):
@@ -104,9 +107,9 @@ def _model_stats(prefix, model, out):
 
 def _trainer_tensors(kind, obj) -> dict:
     """name -> the live device tensor, for everything of a trainer that is a device tensor"""
-    if kind == "DDPGTrainer":
+    if kind in FLAT_TRAINERS:
         out = {"theta/" + w: t for w, t in obj.theta.items()}
-        for w in "pq":
+        for w in obj.m:
             out["m/" + w], out["v/" + w] = obj.m[w], obj.v[w]
         out["step"] = obj.step_count
         return out
@@ -131,7 +134,7 @@ def _keeper_tensors(keeper) -> dict:
 
 def _arena_owners(kind, obj, keeper):
     """(theta, arena, ParamMap) of every arena that load() rewrites from its theta"""
-    if AGENTS.get(kind, kind) == "DDPGTrainer":              # the DDPG kernels read the flat vectors themselves
+    if AGENTS.get(kind, kind) in FLAT_TRAINERS:              # their kernels read the flat vectors themselves
         return []
     trainer = obj.trainer if kind == "Agent" else obj
     owners = [(trainer.opt.theta, trainer.opt.arena, trainer.opt.map)]

@@ -255,7 +255,7 @@ size_t icnn_be_struct_size(int which) {
          : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args)
          : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay)
          : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log)
-         : which == 13 ? sizeof(icnn_be_ddpg_args) : 0;
+         : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -1037,6 +1037,95 @@ int icnn_be_ddpg_q(int dimO, int dimA, int l1, int l2, const float *theta_q, con
         return ICNN_BE_EINVAL;
     return done(icnn_be::launch_ddpg_forward(true, dimO, dimA, l1, l2, theta_q, obs, act, batch, out,
                                              static_cast<hipStream_t>(stream)));
+}
+
+namespace {
+bool naf_sizes_ok(int dimO, int dimA, int l1, int l2) {
+    return dimO >= 1 && dimO <= ICNN_BE_NAF_MAX_OBS && dimA >= 1 && dimA <= ICNN_BE_NAF_MAX_ACT && l1 >= 1 &&
+           l1 <= ICNN_BE_NAF_MAX_HIDDEN && l2 >= 1 && l2 <= ICNN_BE_NAF_MAX_HIDDEN && icnn_be::naf_fits(dimO, dimA, l1, l2);
+}
+
+// what every icnn_be_naf_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
+int check_naf(const icnn_be_naf_args *a, void *stream, bool need_loss) {
+    if (!a || a->batch < 1 || !naf_sizes_ok(a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
+    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
+                         a->grad_l, a->grad_u, a->grad_v, a->work};
+    for (const void *p : a16)
+        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
+    const void *a4[] = {a->obs, a->rew, a->ob2, a->step};
+    for (const void *p : a4)
+        if (misaligned(p, 4)) return ICNN_BE_EINVAL;
+    if (misaligned(a->act, 8) || !a->term || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    if (need_loss ? misaligned(a->loss, 4) : reinterpret_cast<uintptr_t>(a->loss) % 4 != 0) return ICNN_BE_EINVAL;
+    if (!(a->tau >= 0.f && a->tau <= 1.f) || !std::isfinite(a->discount)) return ICNN_BE_EINVAL;
+    if (!(a->l2norm >= 0.f) || !std::isfinite(a->l2norm)) return ICNN_BE_EINVAL;
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f)) return ICNN_BE_EINVAL;
+    if (!std::isfinite(a->rate)) return ICNN_BE_EINVAL;
+    return 0;
+}
+}  // namespace
+
+int icnn_be_naf_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv) {
+    if (!naf_sizes_ok(dimO, dimA, l1, l2) || !nl || !nu || !nv) return ICNN_BE_EINVAL;
+    *nl = icnn_be::naf_net_floats(dimO, l1, l2, dimA * dimA);
+    *nu = icnn_be::naf_net_floats(dimO, l1, l2, dimA);
+    *nv = icnn_be::naf_net_floats(dimO, l1, l2, 1);
+    return 0;
+}
+
+size_t icnn_be_naf_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return 0;
+    return icnn_be::naf_work_floats(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
+}
+
+int icnn_be_naf_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_WORK_PIECES]) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
+    icnn_be::naf_work_floats(batch, dimO, dimA, l1, l2, off);
+    return 0;
+}
+
+int icnn_be_naf_chain(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_chain(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_grads(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_update(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_step(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, true)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = icnn_be::launch_naf_chain(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_naf_grads(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_naf_update(*a, true, s);
+    return done(e);
+}
+
+int icnn_be_naf_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *obs, int batch, float *out,
+                    void *stream) {
+    // the U net is DDPG's policy; its launch needs DDPG's LDS plan, which holds wherever NAF's does
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_u, 16) || misaligned(obs, 4) || misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_ddpg_forward(false, dimO, dimA, l1, l2, theta_u, obs, nullptr, batch, out,
+                                             static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                  const float *obs, const double *act, int batch, float *out, void *stream) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(obs, 4) || misaligned(act, 8) ||
+        misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_naf_q(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, obs, act, batch, out,
+                                      static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {

@@ -7,14 +7,14 @@
 //                        policy and the critic at (obs, pi(obs)), and both backward chains down to the pre-activation deltas.
 //                        Layer inputs and deltas go to the workspace; rows past the batch and columns past a width are
 //                        predicated off.  No grid barrier: nothing in it crosses samples.
-//   ddpg_grads_kernel    dW = X^T Delta over the batch and the column sums of Delta for the six layers, one launch over a
-//                        table: a layer's W and b are one [(in + 1)][out] block of the flat gradient, the product of
+//   ddpg_grads_kernel    dW = X^T Delta over the batch and the column sums of Delta for the six layers (nine for be_naf.hip),
+//                        one launch over a table: a layer's W and b are one [(in + 1)][out] block of the flat gradient, the product of
 //                        [X, 1]^T and Delta; a wave owns a 16 x 32 block and runs one fma chain over the batch per element.
 //                        No atomics, no split of the sum: the same bits on every run.
-//   ddpg_update_kernel   both nets in one launch: g + k theta (k = 0 leaves g as it is), TF-Adam with the arithmetic of
+//   ddpg_update_kernel   a table of parameter sets (here both nets; be_naf.hip brings three) in one launch: g + k theta (k = 0 leaves g as it is), TF-Adam with the arithmetic of
 //                        param_update_kernel (be_train_update.hip), then target <- target - tau (target - theta_new), from
-//                        the NEW theta (ddpg.py orders the moving average behind the assignment).  The critic's workgroups
-//                        also reduce sum theta_old^2, and the last workgroup by ticket forms loss_q from the tile partials
+//                        the NEW theta (ddpg.py orders the moving average behind the assignment) for a set that has a
+//                        target.  The workgroups of the leading sets (here the critic's) also reduce sum theta_old^2, and the last workgroup by ticket forms loss_q from the tile partials
 //                        and those, each in index order (the scheme of rl_td_kernel).
 //   ddpg_act_kernel      pi(obs) for B observations, ddpg_q_kernel Q(obs, act): the layer routines of the chain kernel, so
 //                        the bits of its policy output.
@@ -22,29 +22,13 @@
 // Products: mfma_f32_16x16x4f32, a wave owning two 16-column tiles of the output at a time (two independent accumulators);
 // per 16 values of k a lane takes four consecutive k (the k order inside the block is permuted alike in both operands).
 #include "be_kernels.h"
+#include "be_tile.h"
 #include "be_train_common.h"
 
 namespace icnn_be {
 
 namespace {
 
-constexpr int DT = 512;                  // 8 waves; tile_dot splits them into 16 groups of 32 lanes, one per sample
-constexpr int TS = 16;                   // samples per tile
-static_assert(DT == 32 * TS, "tile_dot: one group of 32 lanes per sample");
-
-struct Net {
-    const float *W1, *b1, *W2, *b2, *W3, *b3;
-};
-__device__ __forceinline__ Net policy_net(const float *t, int dimO, int dimA, int l1, int l2) {
-    Net n;
-    n.W1 = t;
-    n.b1 = n.W1 + (size_t)dimO * l1;
-    n.W2 = n.b1 + l1;
-    n.b2 = n.W2 + (size_t)l1 * l2;
-    n.W3 = n.b2 + l2;
-    n.b3 = n.W3 + (size_t)l2 * dimA;
-    return n;
-}
 __device__ __forceinline__ Net critic_net(const float *t, int dimO, int dimA, int l1, int l2) {
     Net n;
     n.W1 = t;
@@ -54,88 +38,6 @@ __device__ __forceinline__ Net critic_net(const float *t, int dimO, int dimA, in
     n.W3 = n.b2 + l2;
     n.b3 = n.W3 + l2;
     return n;
-}
-
-// epi(s, j, sum_{k < K} in[s][k] Bm(k, j)) for the 16 rows s of the tile and j < N;  Bm(k, j) = W[k sk + j sj].
-// in: LDS, row pitch pin >= K rounded up to 16.  Every wave calls it; no barrier inside.
-template <typename Epi>
-__device__ __forceinline__ void tile_gemm(const float *in, int pin, int K, const float *W, long long sk, long long sj, int N, Epi epi) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, q = lane >> 4;
-    const int NT = (N + 15) >> 4;
-    for (int nt = 2 * wave; nt < NT; nt += 2 * (DT / 64)) {
-        const int c0 = nt * 16 + r16, c1 = c0 + 16;
-        const bool v0 = c0 < N, v1 = c1 < N;
-        const float *w0 = W + (long long)c0 * sj, *w1 = W + (long long)c1 * sj;
-        f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < K; k0 += 16) {
-            const int kb = k0 + 4 * q;
-            const f4 av = *reinterpret_cast<const f4 *>(in + r16 * pin + kb);
-            float af[4], b0[4], b1[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int kk = kb + j;
-                const bool ok = kk < K;
-                af[j] = ok ? av[j] : 0.f;
-                b0[j] = ok && v0 ? w0[(long long)kk * sk] : 0.f;
-                b1[j] = ok && v1 ? w1[(long long)kk * sk] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b0[j], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b1[j], acc1, 0, 0, 0);
-            }
-        }
-        // acc[r] = C[row 4 q + r][column r16 of the tile]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (v0) epi(4 * q + r, c0, acc0[r]);
-            if (v1) epi(4 * q + r, c1, acc1[r]);
-        }
-    }
-}
-
-// sum_k in[s][k] w[k] for s = tid / 32, in every lane of that group; a fixed order
-__device__ __forceinline__ float tile_dot(const float *in, int pin, int K, const float *w) {
-    const int s = threadIdx.x >> 5, l = threadIdx.x & 31;
-    float acc = 0.f;
-    for (int k = l; k < K; k += 32) acc = fmaf(in[s * pin + k], w[k], acc);
-    for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    return acc;
-}
-
-// the rows of this tile: s0 the first sample, rows how many of the 16 exist
-struct Tile {
-    int s0, rows;
-};
-
-// dst[s][c0 + c] = src[s0 + s][c], zero in the rows past the batch
-template <typename T>
-__device__ __forceinline__ void load_rows(float *dst, int pitch, int c0, const T *src, int width, Tile t) {
-    for (int i = threadIdx.x; i < TS * width; i += DT) {
-        const int s = i / width, c = i - s * width;
-        dst[s * pitch + c0 + c] = s < t.rows ? (float)src[(size_t)(t.s0 + s) * width + c] : 0.f;
-    }
-}
-
-// out[s][oc0 + j] = relu(in[s] . W[:, j] + b[j]) into LDS, and into g[s0 + s][gc0 + j] (pitch gw) where g is not NULL
-__device__ __forceinline__ void layer_relu(const float *in, int pin, int K, const float *W, const float *b, int N, float *out, int pout,
-                                           float *g, int gw, Tile t) {
-    tile_gemm(in, pin, K, W, N, 1, N, [&](int s, int j, float acc) {
-        float v = acc + b[j];
-        v = v > 0.f ? v : 0.f;
-        out[s * pout + j] = v;
-        if (g && s < t.rows) g[(size_t)(t.s0 + s) * gw + j] = v;
-    });
-}
-
-// out[s][j] = tanh(in[s] . W[:, j] + b[j]), likewise
-__device__ __forceinline__ void layer_tanh(const float *in, int pin, int K, const float *W, const float *b, int N, float *out, int pout,
-                                           float *g, Tile t) {
-    tile_gemm(in, pin, K, W, N, 1, N, [&](int s, int j, float acc) {
-        const float v = tanhf(acc + b[j]);
-        if (out) out[s * pout + j] = v;
-        if (s < t.rows) g[(size_t)(t.s0 + s) * N + j] = v;
-    });
 }
 
 struct ChainArgs {
@@ -317,16 +219,6 @@ __global__ __launch_bounds__(DT) void ddpg_q_kernel(FwdArgs a) {
 
 constexpr int GW = 4;                    // waves per workgroup; a wave owns a 16 x 32 block of one layer's [(in + 1)][out]
 
-struct GradProd {
-    const float *X, *D;                  // the layer's input [B][in] and pre-activation delta [B][out]
-    float *G;                            // dW [in][out], then db [out]: one [(in + 1)][out] block of the flat gradient
-    int in, out, wave0;                  // wave0: the first wave of this layer
-};
-struct GradArgs {
-    GradProd p[6];
-    int B, waves;
-};
-
 // G[m][j] = sum_b X1[b][m] D[b][j] with X1 = [X, 1]: the row of ones makes the bias gradient row `in` of the same product.
 // One fma chain over the batch in index order per element (no split of the sum, no atomics): the same bits on every run.
 __global__ __launch_bounds__(64 * GW) void ddpg_grads_kernel(GradArgs a) {
@@ -335,8 +227,8 @@ __global__ __launch_bounds__(64 * GW) void ddpg_grads_kernel(GradArgs a) {
     if (w >= a.waves) return;
     GradProd p = a.p[0];
 #pragma unroll
-    for (int i = 1; i < 6; ++i)
-        if (w >= a.p[i].wave0) p = a.p[i];
+    for (int i = 1; i < GRAD_PRODUCTS; ++i)
+        if (i < a.count && w >= a.p[i].wave0) p = a.p[i];
     const int local = w - p.wave0, pairs = (p.out + 31) >> 5;
     const int tm = local / pairs, tn = local - tm * pairs;
     const int m = tm * 16 + r16, c0 = tn * 32 + r16, c1 = c0 + 16;
@@ -367,43 +259,24 @@ __global__ __launch_bounds__(64 * GW) void ddpg_grads_kernel(GradArgs a) {
     }
 }
 
-// ---- the update of both nets and loss_q ----
+// ---- the update of a table of parameter sets and loss_q ----
 
 constexpr int UT = 256;
 constexpr int UPT = 4;
-
-struct NetUpd {
-    float *theta, *m, *v, *target;
-    const float *grad;
-    long long n;
-    int blocks;
-    float k;                // the decay coefficient: l2norm for the critic, pl2norm for the policy
-    double lr;
-};
-struct UpdArgs {
-    NetUpd net[2];          // 0: the critic, 1: the policy
-    int *step;              // [0] updates of the critic, [1] of the policy, [2] the ticket
-    double beta1, beta2;
-    float b1, c1, b2, c2, eps, tau;
-    float *loss;            // NULL: no loss
-    const double *sq;       // [tiles] the chain kernel's sums of td^2
-    int tiles, batch;
-    double l2norm;
-    double *partial;        // [net[0].blocks]
-};
 
 __global__ __launch_bounds__(UT) void ddpg_update_kernel(UpdArgs u) {
 #pragma clang fp contract(off)
     __shared__ float s_lr_t;
     __shared__ double red[UT];
     __shared__ int s_last;
-    const int which = (int)blockIdx.x < u.net[0].blocks ? 0 : 1;
-    const NetUpd &a = u.net[which];
-    const int block = which ? (int)blockIdx.x - u.net[0].blocks : (int)blockIdx.x;
+    int which = 0, block = (int)blockIdx.x;
+    while (which + 1 < u.sets && block >= u.set[which].blocks) block -= u.set[which++].blocks;
+    const ParamSet &a = u.set[which];
+    const bool has_target = a.target != nullptr;
     if (threadIdx.x == 0) {
         // updates done so far: the last workgroup writes the counts back only after every workgroup has taken its ticket, and
         // every workgroup reads its count before it takes one
-        const int t = __hip_atomic_load(u.step + which, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+        const int t = __hip_atomic_load(u.step + a.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
         s_lr_t = (float)(a.lr * sqrt(1.0 - pow(u.beta2, (double)t)) / (1.0 - pow(u.beta1, (double)t)));
     }
     __syncthreads();
@@ -415,7 +288,7 @@ __global__ __launch_bounds__(UT) void ddpg_update_kernel(UpdArgs u) {
         float th[UPT] = {}, m[UPT] = {}, v[UPT] = {}, g[UPT] = {}, tt[UPT] = {};
         if (cnt == UPT) {
             const float4 t4 = *reinterpret_cast<const float4 *>(a.theta + j0);
-            const float4 r4 = *reinterpret_cast<const float4 *>(a.target + j0);
+            const float4 r4 = has_target ? *reinterpret_cast<const float4 *>(a.target + j0) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float4 m4 = *reinterpret_cast<const float4 *>(a.m + j0);
             const float4 v4 = *reinterpret_cast<const float4 *>(a.v + j0);
             const float4 g4 = *reinterpret_cast<const float4 *>(a.grad + j0);
@@ -426,7 +299,7 @@ __global__ __launch_bounds__(UT) void ddpg_update_kernel(UpdArgs u) {
             g[0] = g4.x; g[1] = g4.y; g[2] = g4.z; g[3] = g4.w;
         } else {
             for (int k = 0; k < cnt; ++k) {
-                th[k] = a.theta[j0 + k]; tt[k] = a.target[j0 + k];
+                th[k] = a.theta[j0 + k]; tt[k] = has_target ? a.target[j0 + k] : 0.f;
                 m[k] = a.m[j0 + k]; v[k] = a.v[j0 + k]; g[k] = a.grad[j0 + k];
             }
         }
@@ -445,45 +318,42 @@ __global__ __launch_bounds__(UT) void ddpg_update_kernel(UpdArgs u) {
         }
         if (cnt == UPT) {
             *reinterpret_cast<float4 *>(a.theta + j0) = make_float4(th[0], th[1], th[2], th[3]);
-            *reinterpret_cast<float4 *>(a.target + j0) = make_float4(tt[0], tt[1], tt[2], tt[3]);
+            if (has_target) *reinterpret_cast<float4 *>(a.target + j0) = make_float4(tt[0], tt[1], tt[2], tt[3]);
             *reinterpret_cast<float4 *>(a.m + j0) = make_float4(m[0], m[1], m[2], m[3]);
             *reinterpret_cast<float4 *>(a.v + j0) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
             for (int k = 0; k < cnt; ++k) {
-                a.theta[j0 + k] = th[k]; a.target[j0 + k] = tt[k];
-                a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k];
+                a.theta[j0 + k] = th[k]; a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k];
+                if (has_target) a.target[j0 + k] = tt[k];
             }
         }
     }
-    // loss_q's decay sum: one partial per workgroup of the critic
-    if (u.loss && which == 0) {
+    // loss_q's decay sum: one partial per workgroup of the sets that enter it
+    if (u.loss && (int)blockIdx.x < u.reg_blocks) {
         ssq = block_tree_sum<UT>(ssq, red);
-        if (threadIdx.x == 0) __hip_atomic_store(u.partial + block, ssq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) __hip_atomic_store(u.partial + blockIdx.x, ssq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int ticket = __hip_atomic_fetch_add(u.step + 2, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int ticket = __hip_atomic_fetch_add(u.step + u.slots, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         s_last = ticket == (int)gridDim.x - 1;
         if (s_last) {
             // the last workgroup: the step counts, the loss, and the ticket re-armed for the next launch
-            for (int w = 0; w < 2; ++w) {
+            for (int w = 0; w < u.slots; ++w) {
                 const int t = __hip_atomic_load(u.step + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(u.step + w, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (u.loss) {
                 double sq = 0.0, reg = 0.0;
                 for (int i = 0; i < u.tiles; ++i) sq = sq + u.sq[i];
-                for (int b = 0; b < u.net[0].blocks; ++b)
+                for (int b = 0; b < u.reg_blocks; ++b)
                     reg = reg + __hip_atomic_load(u.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 *u.loss = (float)(sq / (double)u.batch + u.l2norm * (0.5 * reg));
             }
-            __hip_atomic_store(u.step + 2, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(u.step + u.slots, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
-
-inline int pitch_of(int w) { return ((w + 15) & ~15) + 4; }
-inline int max2(int x, int y) { return x > y ? x : y; }
 
 struct Pitches {
     int PA, PB, PC, PD, PS;
@@ -554,22 +424,35 @@ hipError_t launch_ddpg_grads(const icnn_be_ddpg_args &d, hipStream_t stream) {
     const int dimO = d.dimO, dimA = d.dimA, l1 = d.l1, l2 = d.l2;
     GradArgs a{};
     a.B = d.batch;
-    int n = 0;
-    // the layers in the order of the flat gradients: W and b of a layer are one [(in + 1)][out] block
-    auto layer = [&](const float *X, int in, const float *D, int out, float *&g) {
-        a.p[n++] = GradProd{X, D, g, in, out, a.waves};
-        a.waves += ((in + 1 + 15) / 16) * ((out + 31) / 32);
-        g += (size_t)(in + 1) * out;
-    };
+    // the layers in the order of the flat gradients
     float *g = d.grad_q;
-    layer(d.obs, dimO, w + off[ICNN_BE_DDPG_W_D1Q], l1, g);
-    layer(w + off[ICNN_BE_DDPG_W_XA], l1 + dimA, w + off[ICNN_BE_DDPG_W_D2Q], l2, g);
-    layer(w + off[ICNN_BE_DDPG_W_H2Q], l2, w + off[ICNN_BE_DDPG_W_D3Q], 1, g);
+    a.layer(d.obs, dimO, w + off[ICNN_BE_DDPG_W_D1Q], l1, g);
+    a.layer(w + off[ICNN_BE_DDPG_W_XA], l1 + dimA, w + off[ICNN_BE_DDPG_W_D2Q], l2, g);
+    a.layer(w + off[ICNN_BE_DDPG_W_H2Q], l2, w + off[ICNN_BE_DDPG_W_D3Q], 1, g);
     g = d.grad_p;
-    layer(d.obs, dimO, w + off[ICNN_BE_DDPG_W_D1P], l1, g);
-    layer(w + off[ICNN_BE_DDPG_W_H1P], l1, w + off[ICNN_BE_DDPG_W_D2P], l2, g);
-    layer(w + off[ICNN_BE_DDPG_W_H2P], l2, w + off[ICNN_BE_DDPG_W_D3P], dimA, g);
+    a.layer(d.obs, dimO, w + off[ICNN_BE_DDPG_W_D1P], l1, g);
+    a.layer(w + off[ICNN_BE_DDPG_W_H1P], l1, w + off[ICNN_BE_DDPG_W_D2P], l2, g);
+    a.layer(w + off[ICNN_BE_DDPG_W_H2P], l2, w + off[ICNN_BE_DDPG_W_D3P], dimA, g);
+    return launch_grad_table(a, stream);
+}
+
+hipError_t launch_grad_table(const GradArgs &a, hipStream_t stream) {
     return launch_kernel(ddpg_grads_kernel, dim3((a.waves + GW - 1) / GW), dim3(64 * GW), 0, stream, a);
+}
+
+void update_coefficients(UpdArgs &u, double beta1, double beta2) {
+    u.beta1 = beta1;
+    u.beta2 = beta2;
+    u.b1 = (float)beta1;
+    u.c1 = (float)(1.0 - beta1);
+    u.b2 = (float)beta2;
+    u.c2 = (float)(1.0 - beta2);
+}
+
+hipError_t launch_param_sets_update(const UpdArgs &u, hipStream_t stream) {
+    int blocks = 0;
+    for (int i = 0; i < u.sets; ++i) blocks += u.set[i].blocks;
+    return launch_kernel(ddpg_update_kernel, dim3((unsigned)blocks), dim3(UT), 0, stream, u);
 }
 
 hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStream_t stream) {
@@ -578,15 +461,14 @@ hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStr
     float *w = static_cast<float *>(d.work);
     UpdArgs u{};
     const long long nq = ddpg_critic_floats(d.dimO, d.dimA, d.l1, d.l2), np = ddpg_policy_floats(d.dimO, d.dimA, d.l1, d.l2);
-    u.net[0] = NetUpd{d.theta_q, d.m_q, d.v_q, d.target_q, d.grad_q, nq, (int)param_update_blocks(nq), d.l2norm, d.rate};
-    u.net[1] = NetUpd{d.theta_p, d.m_p, d.v_p, d.target_p, d.grad_p, np, (int)param_update_blocks(np), d.pl2norm, d.prate};
+    // 0: the critic (step count 0), 1: the policy (step count 1); only the critic's decay sum enters loss_q
+    u.set[0] = ParamSet{d.theta_q, d.m_q, d.v_q, d.target_q, d.grad_q, nq, (int)param_update_blocks(nq), 0, d.l2norm, d.rate};
+    u.set[1] = ParamSet{d.theta_p, d.m_p, d.v_p, d.target_p, d.grad_p, np, (int)param_update_blocks(np), 1, d.pl2norm, d.prate};
+    u.sets = 2;
     u.step = d.step;
-    u.beta1 = d.beta1;
-    u.beta2 = d.beta2;
-    u.b1 = (float)d.beta1;
-    u.c1 = (float)(1.0 - d.beta1);
-    u.b2 = (float)d.beta2;
-    u.c2 = (float)(1.0 - d.beta2);
+    u.slots = 2;
+    u.reg_blocks = u.set[0].blocks;
+    update_coefficients(u, d.beta1, d.beta2);
     u.eps = d.eps;
     u.tau = d.tau;
     u.loss = with_loss ? d.loss : nullptr;
@@ -595,7 +477,7 @@ hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStr
     u.batch = d.batch;
     u.l2norm = (double)d.l2norm;
     u.partial = reinterpret_cast<double *>(w + off[ICNN_BE_DDPG_W_UPD]);
-    return launch_kernel(ddpg_update_kernel, dim3((unsigned)(u.net[0].blocks + u.net[1].blocks)), dim3(UT), 0, stream, u);
+    return launch_param_sets_update(u, stream);
 }
 
 hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, const float *theta, const float *obs,

@@ -407,4 +407,14 @@ hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStr
 hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, const float *theta, const float *obs,
                                const double *act, int B, float *out, hipStream_t stream);
 
+// ---- the NAF step (be_naf.hip) ------------------------------------------------------
+long long naf_net_floats(int dimO, int l1, int l2, int out);      // out: dimA^2 (L), dimA (U), 1 (V)
+bool naf_fits(int dimO, int dimA, int l1, int l2);       // the chain kernel's LDS
+size_t naf_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
+hipError_t launch_naf_chain(const icnn_be_naf_args &d, hipStream_t stream);
+hipError_t launch_naf_grads(const icnn_be_naf_args &d, hipStream_t stream);
+hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStream_t stream);
+hipError_t launch_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                        const float *obs, const double *act, int B, float *out, hipStream_t stream);
+
 }  // namespace icnn_be

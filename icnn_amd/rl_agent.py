@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ddpg, rl_adam, rl_train
+from . import _lib, ddpg, naf, rl_adam, rl_train
 
 
 class ReplayMemory:
@@ -232,6 +232,29 @@ class DDPGAgent(_AgentCycle):
 
     def act(self, test=False):
         """ddpg.py:129-134: pi(observation), plus the Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns
+        float64 [dimA]; the copy to the host is the one synchronisation of an environment step."""
+        self._obs1.copy_(torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO)))
+        action = self.trainer.policy(self._obs1, out=self._act1).cpu().numpy().astype(np.float64)
+        return self._explore(action, test)
+
+
+class NAFAgent(_AgentCycle):
+    """`Agent` of RL/src/naf.py around naf.NAFTrainer: the same reset / act / observe / train cycle, memory,
+    noise and capture as Agent; act() is one launch of the U net at the current observation (icnn_be_naf_act).  l1, l2, rate,
+    tau, discount, l2norm and initstd go to the trainer; seed also draws its initial weights."""
+
+    def __init__(self, dimO, dimA, l1=200, l2=200, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1,
+                 seed=0, capture=False, rate=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, initstd=0.01, device="cuda"):
+        self._check_cycle(warmup, iters)
+        self.trainer = naf.NAFTrainer(dimO, dimA, l1, l2, batch=bsize, rate=rate, tau=tau, discount=discount, l2norm=l2norm,
+                                      seed=seed, device=device, initstd=initstd)
+        self.spec = self.trainer.spec
+        self._setup(dimO, dimA, self.trainer.device, warmup, iters, rmsize, outheta, ousigma, seed, capture)
+        self._obs1 = torch.zeros(1, self.dimO, dtype=torch.float32, device=self.device)
+        self._act1 = torch.zeros(1, self.dimA, dtype=torch.float32, device=self.device)
+
+    def act(self, test=False):
+        """naf.py:116-121: u(observation), plus the Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns
         float64 [dimA]; the copy to the host is the one synchronisation of an environment step."""
         self._obs1.copy_(torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO)))
         action = self.trainer.policy(self._obs1, out=self._act1).cpu().numpy().astype(np.float64)

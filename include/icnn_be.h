@@ -224,7 +224,8 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
 /* sizeof(icnn_be_state) for which = 0, sizeof(icnn_be_fc_model) for 1, sizeof(icnn_be_fc_ctx) for 2,
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
  * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
- * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13,
+ * sizeof(icnn_be_naf_args) for 14: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -1309,6 +1310,104 @@ ICNN_BE_API int icnn_be_ddpg_act(int dimO, int dimA, int l1, int l2, const float
                                  void *stream);
 ICNN_BE_API int icnn_be_ddpg_q(int dimO, int dimA, int l1, int l2, const float *theta_q, const float *obs, const double *act,
                                int batch, float *out, void *stream);
+
+/* ---- the NAF agent: fused Q step with the L-matrix head, act (be_naf.hip, additive to ABI 12) ---- */
+
+/*
+ * NAF of RL/src/naf.py with the networks of naf_nets_dm.py and naf_bn False, all float32.  Three nets theta_l, theta_u,
+ * theta_v, each one flat vector in the order W1, b1, W2, b2, W3, b3, every W row-major [in][out] (the layout of DDPG's
+ * policy) with W1 [dimO][l1], W2 [l1][l2] and W3 [l2][dimA^2] (L), [l2][dimA] (U), [l2][1] (V);
+ * mlp(o; theta) = relu(relu(o W1 + b1) W2 + b2) W3 + b3.  Per sample:
+ *   l = mlp(obs; theta_l) read as a row-major [dimA][dimA] matrix; Lm[i][j] = l[i][j] below the diagonal, exp(l[i][i]) on
+ *   it, 0 above;  u = tanh(mlp(obs; theta_u));  delta = act - u;  h[j] = sum_{i >= j} delta[i] Lm[i][j] (an fma chain in
+ *   ascending i);  A = -1/2 sum_j h[j]^2 (ascending j);  q = mlp(obs; theta_v) + A.
+ * One step on the minibatch (obs, act, rew, ob2, term), everything read from the parameters as they are when it begins:
+ *   y = term ? rew : rew + discount mlp(ob2; target_v)     (the target's advantage is the constant 0)
+ *   td = q - y, loss_q = mean td^2 + l2norm sum theta^2 / 2 over all 18 variables, g = d loss_q / d (theta_l, theta_u, theta_v)
+ *   ONE TF-Adam over the three vectors (icnn_be_param_update's element arithmetic with eps as given and no proj, one step
+ *   count), then target_v <- target_v - tau (target_v - theta_v_new).
+ * icnn_be_naf_chain does the per-sample part (one launch) and leaves the layer inputs and pre-activation deltas in the
+ * workspace; icnn_be_naf_grads forms grad_l, grad_u and grad_v from them (one launch, one fma chain over the batch per
+ * element, no atomics); icnn_be_naf_update updates the three nets and the target in one launch and writes loss_q;
+ * icnn_be_naf_step is the three in that order.  act: float64, rounded to float32 once on load.
+ *
+ * The workspace: icnn_be_naf_work_bytes bytes, 16-byte aligned; icnn_be_naf_work_offsets gives the offset in floats of each
+ * piece ICNN_BE_NAF_W_* ([batch][width] float32 unless said otherwise); the chain writes nothing outside the rows < batch of
+ * its pieces.  step: ICNN_BE_NAF_STEP_INTS int32, zero for fresh nets: [0] the updates, [1] a ticket (zero between
+ * launches); a captured step replayed k times is k steps.
+ *
+ * Sizes: 1 <= dimO <= ICNN_BE_NAF_MAX_OBS, 1 <= dimA <= ICNN_BE_NAF_MAX_ACT, 1 <= l1, l2 <= ICNN_BE_NAF_MAX_HIDDEN,
+ * batch >= 1; at these maxima the chain kernel takes 148864 bytes of LDS (the obs rows and the dimA^2 = 1024 wide l rows
+ * share one buffer).  EINVAL for anything else, a NULL or misaligned pointer (the nets, m, v, the gradients and work 16
+ * bytes, act 8, the rest 4), tau outside [0, 1], a non-finite discount, a negative or non-finite l2norm, beta outside [0, 1),
+ * eps <= 0, a non-finite rate, before anything is launched.  No entry synchronises; all are capturable.
+ */
+#define ICNN_BE_NAF_MAX_OBS 600
+#define ICNN_BE_NAF_MAX_ACT 32
+#define ICNN_BE_NAF_MAX_HIDDEN 600
+#define ICNN_BE_NAF_STEP_INTS 4
+#define ICNN_BE_NAF_W_Y 0      /* y [1] */
+#define ICNN_BE_NAF_W_U 1      /* u [dimA] */
+#define ICNN_BE_NAF_W_L 2      /* l [dimA^2] */
+#define ICNN_BE_NAF_W_LD 3     /* the diagonal of Lm, exp(l[i][i]) [dimA] */
+#define ICNN_BE_NAF_W_H 4      /* h [dimA] */
+#define ICNN_BE_NAF_W_ADV 5    /* A [1] */
+#define ICNN_BE_NAF_W_Q 6      /* q [1] */
+#define ICNN_BE_NAF_W_TD 7     /* td [1] */
+#define ICNN_BE_NAF_W_H1L 8    /* the hidden layers of the L net [l1], [l2] */
+#define ICNN_BE_NAF_W_H2L 9
+#define ICNN_BE_NAF_W_H1U 10   /* of the U net */
+#define ICNN_BE_NAF_W_H2U 11
+#define ICNN_BE_NAF_W_H1V 12   /* of the V net */
+#define ICNN_BE_NAF_W_H2V 13
+#define ICNN_BE_NAF_W_D3L 14   /* the deltas of the L net: d loss / d l [dimA^2], [l2], [l1] */
+#define ICNN_BE_NAF_W_D2L 15
+#define ICNN_BE_NAF_W_D1L 16
+#define ICNN_BE_NAF_W_D3U 17   /* of the U net: before the tanh [dimA], [l2], [l1] */
+#define ICNN_BE_NAF_W_D2U 18
+#define ICNN_BE_NAF_W_D1U 19
+#define ICNN_BE_NAF_W_D3V 20   /* of the V net: 2 td / batch [1], [l2], [l1] */
+#define ICNN_BE_NAF_W_D2V 21
+#define ICNN_BE_NAF_W_D1V 22
+#define ICNN_BE_NAF_W_SQ 23    /* float64 [tiles of 16 samples]: each tile's sum of td^2 */
+#define ICNN_BE_NAF_W_UPD 24   /* float64: the update's partial sums of theta^2 */
+#define ICNN_BE_NAF_WORK_PIECES 25
+typedef struct icnn_be_naf_args {
+    int batch, dimO, dimA, l1, l2;
+    const float *obs;                 /* [batch][dimO] */
+    const double *act;                /* [batch][dimA] */
+    const float *rew;                 /* [batch] */
+    const float *ob2;                 /* [batch][dimO] */
+    const unsigned char *term;        /* [batch] */
+    float *theta_l, *theta_u, *theta_v, *target_v;      /* separately allocated */
+    float *m_l, *v_l, *m_u, *v_u, *m_v, *v_v;           /* Adam's moments */
+    float *grad_l, *grad_u, *grad_v;  /* the step's gradients, before the decay term */
+    int *step;                        /* [ICNN_BE_NAF_STEP_INTS] */
+    float *loss;                      /* loss_q of the step */
+    void *work;
+    double rate, beta1, beta2;
+    float eps, tau, discount, l2norm;
+} icnn_be_naf_args;                   /* icnn_be_struct_size(14) */
+
+/* floats of theta_l (*nl), theta_u (*nu) and theta_v (*nv); EINVAL for sizes out of range */
+ICNN_BE_API int icnn_be_naf_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv);
+/* 0 for sizes out of range */
+ICNN_BE_API size_t icnn_be_naf_work_bytes(int batch, int dimO, int dimA, int l1, int l2);
+ICNN_BE_API int icnn_be_naf_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_WORK_PIECES]);
+ICNN_BE_API int icnn_be_naf_chain(const icnn_be_naf_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_grads(const icnn_be_naf_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_update(const icnn_be_naf_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_step(const icnn_be_naf_args *a, void *stream);
+/*
+ * icnn_be_naf_act: out[batch][dimA] = u(obs; theta_u), what act() pays per environment step: the U net has the layout and
+ * the function of DDPG's policy, so this is icnn_be_ddpg_act's launch on theta_u, and the bits of the chain's
+ * ICNN_BE_NAF_W_U.  icnn_be_naf_q: out[batch] = q(obs, act; theta_l, theta_u, theta_v), the bits of ICNN_BE_NAF_W_Q.
+ * EINVAL as above (theta 16 bytes, act 8, obs and out 4).
+ */
+ICNN_BE_API int icnn_be_naf_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *obs, int batch, float *out,
+                                void *stream);
+ICNN_BE_API int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                              const float *obs, const double *act, int batch, float *out, void *stream);
 
 #ifdef __cplusplus
 }
