@@ -74,6 +74,8 @@ EXPORTS = [
     "icnn_be_ddpg_update", "icnn_be_ddpg_step", "icnn_be_ddpg_act", "icnn_be_ddpg_q",
     "icnn_be_naf_param_floats", "icnn_be_naf_work_bytes", "icnn_be_naf_work_offsets", "icnn_be_naf_chain", "icnn_be_naf_grads",
     "icnn_be_naf_update", "icnn_be_naf_step", "icnn_be_naf_act", "icnn_be_naf_q",
+    "icnn_be_ff_param_floats", "icnn_be_ff_work_bytes", "icnn_be_ff_work_offsets", "icnn_be_ff_forward", "icnn_be_ff_backward",
+    "icnn_be_ff_grads", "icnn_be_ff_update", "icnn_be_ff_step", "icnn_be_ff_eval",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -101,6 +103,11 @@ NAF_STEP_INTS = 4                          # ICNN_BE_NAF_STEP_INTS: the updates,
 # ICNN_BE_NAF_W_*: the pieces of the NAF workspace, in order
 NAF_WORK = ["y", "u", "l", "ld", "h", "adv", "q", "td", "h1l", "h2l", "h1u", "h2u", "h1v", "h2v", "d3l", "d2l", "d1l", "d3u", "d2u",
             "d1u", "d3v", "d2v", "d1v", "sq", "upd"]
+FF_MAX_LAYERS, FF_MAX_FEATURES, FF_MAX_WIDTH, FF_MAX_BATCH = 4, 4096, 1024, 512     # ICNN_BE_FF_MAX_*
+FF_STEP_INTS = 4                           # ICNN_BE_FF_STEP_INTS: the updates, the ticket
+# ICNN_BE_FF_W_*: the pieces of the feed-forward workspace, in order; a / h / stat / dz of hidden layer i + 1 at "a%d" % i, ...
+FF_WORK = (["a%d" % i for i in range(4)] + ["h%d" % i for i in range(4)] + ["stat%d" % i for i in range(4)]
+           + ["dz%d" % i for i in range(4)] + ["dlogit", "part", "ctl"])
 
 
 def replay_stage_bytes(dimO, dimA):
@@ -237,6 +244,20 @@ class NafArgs(C.Structure):
         ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
         ("rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
         ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float),
+    ]
+
+
+class FfArgs(C.Structure):
+    """struct icnn_be_ff_args"""
+    _fields_ = [
+        ("batch", C.c_int), ("n_features", C.c_int), ("n_labels", C.c_int), ("n_layers", C.c_int),
+        ("width", C.c_int * FF_MAX_LAYERS),
+        ("x", C.c_void_p), ("true_y", C.c_void_p),
+        ("theta", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p),
+        ("mv", BnMoving),
+        ("step", C.c_void_p), ("loss", C.c_void_p), ("yhat", C.c_void_p), ("f1_tallies", C.c_void_p), ("work", C.c_void_p),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("eps", C.c_float), ("bn_eps", C.c_float),
     ]
 
 
@@ -465,6 +486,18 @@ def load():
     lib.icnn_be_naf_act.restype = C.c_int
     lib.icnn_be_naf_q.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.icnn_be_naf_q.restype = C.c_int
+    FA = C.POINTER(FfArgs)
+    ff_dims = [C.c_int] * 3 + [C.POINTER(C.c_int)]
+    lib.icnn_be_ff_param_floats.argtypes = ff_dims + [C.POINTER(C.c_longlong)]
+    lib.icnn_be_ff_param_floats.restype = C.c_int
+    lib.icnn_be_ff_work_bytes.argtypes = [C.c_int] + ff_dims
+    lib.icnn_be_ff_work_bytes.restype = C.c_size_t
+    lib.icnn_be_ff_work_offsets.argtypes = [C.c_int] + ff_dims + [C.POINTER(C.c_longlong * len(FF_WORK))]
+    lib.icnn_be_ff_work_offsets.restype = C.c_int
+    lib.icnn_be_ff_forward.argtypes, lib.icnn_be_ff_forward.restype = [FA, C.c_int, C.c_void_p], C.c_int
+    for name in ("backward", "grads", "update", "step", "eval"):
+        fn = getattr(lib, "icnn_be_ff_" + name)
+        fn.argtypes, fn.restype = [FA, C.c_void_p], C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -504,6 +537,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_ddpg_args differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(14) != C.sizeof(NafArgs):
         raise ImportError("ctypes struct layout of icnn_be_naf_args differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(16) != C.sizeof(FfArgs):
+        raise ImportError("ctypes struct layout of icnn_be_ff_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

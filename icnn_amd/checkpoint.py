@@ -10,6 +10,7 @@ result depends on:
     CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step)
     ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
     naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count
+    ff.FFTrainer         the flat theta/ff, m/ff, v/ff, the step count and the moving statistics bn/mean<i>, bn/var<i>
     Agent, DDPGAgent, NAFAgent   its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
                          with memory=True, the filled part of the four replay arrays and the control block (cursor, fill, draw
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
@@ -83,8 +84,8 @@ def spec_json(spec) -> str:
 # What each object's state is made of
 # --------------------------------------------------------------------------------------------- #
 def _kind(obj) -> str:
-    from . import ddpg, ficnn, naf, rl_agent, rl_train, train
-    for cls, kind in ((train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
+    from . import ddpg, ff, ficnn, naf, rl_agent, rl_train, train
+    for cls, kind in ((ff.FFTrainer, "FFTrainer"), (train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
                       (train.ConvGDTrainer, "ConvGDTrainer"), (ficnn.GDTrainer, "ficnn.GDTrainer"),
                       (rl_train.CriticTrainer, "CriticTrainer"), (rl_agent.Agent, "Agent"),
                       (ddpg.DDPGTrainer, "DDPGTrainer"), (rl_agent.DDPGAgent, "DDPGAgent"),
@@ -92,10 +93,10 @@ def _kind(obj) -> str:
         if isinstance(obj, cls):
             return kind
     raise TypeError("checkpoint serves BundleTrainer, GDTrainer, ConvGDTrainer, ficnn.GDTrainer, CriticTrainer, Agent, "
-                    "DDPGTrainer, DDPGAgent, NAFTrainer and NAFAgent, got %s" % type(obj).__name__)
+                    "DDPGTrainer, DDPGAgent, NAFTrainer, NAFAgent and ff.FFTrainer, got %s" % type(obj).__name__)
 
 
-FLAT_TRAINERS = ("DDPGTrainer", "NAFTrainer")               # trainers whose state is flat vectors in dicts theta, m, v
+FLAT_TRAINERS = ("DDPGTrainer", "NAFTrainer", "FFTrainer")  # trainers whose state is flat vectors in dicts theta, m, v
 AGENTS = {"Agent": "CriticTrainer", "DDPGAgent": "DDPGTrainer", "NAFAgent": "NAFTrainer"}     # an agent's kind -> its trainer's
 
 
@@ -112,6 +113,8 @@ def _trainer_tensors(kind, obj) -> dict:
         for w in obj.m:
             out["m/" + w], out["v/" + w] = obj.m[w], obj.v[w]
         out["step"] = obj.step_count
+        if kind == "FFTrainer":
+            _model_stats("", obj.model, out)
         return out
     out = {"theta": obj.opt.theta, "m": obj.opt.m, "v": obj.opt.v, "step": obj.opt.step_count}
     if kind == "CriticTrainer":

@@ -255,7 +255,8 @@ size_t icnn_be_struct_size(int which) {
          : which == 6 ? sizeof(icnn_be_param_update_args) : which == 7 ? sizeof(icnn_be_rl_update_args)
          : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay)
          : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log)
-         : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args) : 0;
+         : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args)
+         : which == 16 ? sizeof(icnn_be_ff_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -1126,6 +1127,103 @@ int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, cons
         return ICNN_BE_EINVAL;
     return done(icnn_be::launch_naf_q(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, obs, act, batch, out,
                                       static_cast<hipStream_t>(stream)));
+}
+
+namespace {
+bool ff_sizes_ok(int n_features, int n_labels, int n_layers, const int *width) {
+    if (n_features < 1 || n_features > ICNN_BE_FF_MAX_FEATURES || n_labels < 1 || n_labels > ICNN_BE_FF_MAX_WIDTH) return false;
+    if (n_layers < 1 || n_layers > ICNN_BE_FF_MAX_LAYERS || !width) return false;
+    for (int i = 0; i < n_layers; ++i)
+        if (width[i] < 1 || width[i] > ICNN_BE_FF_MAX_WIDTH) return false;
+    return true;
+}
+
+// what an icnn_be_ff_* entry needs beyond the sizes
+enum : unsigned {
+    FF_TRAIN_BATCH = 1, FF_X = 2, FF_Y = 4, FF_OUT = 8, FF_MOVING = 16, FF_GRAD = 32, FF_ADAM = 64, FF_WORK = 128, FF_LOSS = 256
+};
+int check_ff(const icnn_be_ff_args *a, void *stream, unsigned need) {
+    if (!a || !ff_sizes_ok(a->n_features, a->n_labels, a->n_layers, a->width)) return ICNN_BE_EINVAL;
+    if (a->batch < 1 || ((need & FF_TRAIN_BATCH) && (a->batch < 2 || a->batch > ICNN_BE_FF_MAX_BATCH))) return ICNN_BE_EINVAL;
+    if (misaligned(a->theta, 16) || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    if ((need & FF_WORK) && misaligned(a->work, 16)) return ICNN_BE_EINVAL;
+    if ((need & FF_X) && misaligned(a->x, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_Y) && misaligned(a->true_y, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_OUT) && misaligned(a->yhat, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_LOSS) && (misaligned(a->loss, 4) || reinterpret_cast<uintptr_t>(a->f1_tallies) % 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_GRAD) && misaligned(a->grad, 16)) return ICNN_BE_EINVAL;
+    if (need & FF_ADAM) {
+        if (misaligned(a->m, 16) || misaligned(a->v, 16) || misaligned(a->step, 4)) return ICNN_BE_EINVAL;
+        if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f) || !std::isfinite(a->lr))
+            return ICNN_BE_EINVAL;
+    }
+    if (need & FF_MOVING) {
+        for (int i = 0; i < a->n_layers; ++i)
+            if (misaligned(a->mv.mean[i], 4) || misaligned(a->mv.var[i], 4)) return ICNN_BE_EINVAL;
+        if (!(a->mv.decay >= 0.f && a->mv.decay <= 1.f)) return ICNN_BE_EINVAL;
+    }
+    if (!(a->bn_eps > 0.f)) return ICNN_BE_EINVAL;
+    return 0;
+}
+}  // namespace
+
+int icnn_be_ff_param_floats(int n_features, int n_labels, int n_layers, const int *width, long long *n) {
+    if (!ff_sizes_ok(n_features, n_labels, n_layers, width) || !n) return ICNN_BE_EINVAL;
+    *n = icnn_be::ff_param_floats(n_features, n_labels, n_layers, width);
+    return 0;
+}
+
+size_t icnn_be_ff_work_bytes(int batch, int n_features, int n_labels, int n_layers, const int *width) {
+    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width)) return 0;
+    return icnn_be::ff_work_floats(batch, n_features, n_labels, n_layers, width, nullptr) * sizeof(float);
+}
+
+int icnn_be_ff_work_offsets(int batch, int n_features, int n_labels, int n_layers, const int *width,
+                            long long off[ICNN_BE_FF_WORK_PIECES]) {
+    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width) || !off) return ICNN_BE_EINVAL;
+    icnn_be::ff_work_floats(batch, n_features, n_labels, n_layers, width, off);
+    return 0;
+}
+
+int icnn_be_ff_forward(const icnn_be_ff_args *a, int mode, void *stream) {
+    if (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING) return ICNN_BE_EINVAL;
+    const bool with_y = a && a->true_y;
+    unsigned need = FF_X | FF_OUT | FF_WORK | (with_y ? FF_Y | FF_LOSS : 0u);
+    need |= mode == ICNN_BE_BN_MOVING ? FF_MOVING : FF_TRAIN_BATCH;
+    if (int rc = check_ff(a, stream, need)) return rc;
+    return done(icnn_be::launch_ff_forward(*a, mode, with_y, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_backward(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_WORK | FF_GRAD)) return rc;
+    return done(icnn_be::launch_ff_backward(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_grads(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_WORK | FF_GRAD)) return rc;
+    return done(icnn_be::launch_ff_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_update(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_GRAD | FF_ADAM)) return rc;
+    return done(icnn_be::launch_ff_update(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_step(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_GRAD | FF_ADAM | FF_WORK))
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = icnn_be::launch_ff_forward(*a, ICNN_BE_BN_BATCH, true, s);
+    if (e == hipSuccess) e = icnn_be::launch_ff_backward(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_ff_grads(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_ff_update(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_ff_fold(*a, s);
+    return done(e);
+}
+
+int icnn_be_ff_eval(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_WORK)) return rc;
+    return done(icnn_be::launch_ff_forward(*a, ICNN_BE_BN_MOVING, true, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {

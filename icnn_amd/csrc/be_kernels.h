@@ -417,4 +417,14 @@ hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStrea
 hipError_t launch_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
                         const float *obs, const double *act, int B, float *out, hipStream_t stream);
 
+// ---- the feed-forward baseline (be_ff.hip) ---------------------------------------------
+long long ff_param_floats(int n_features, int n_labels, int n_layers, const int *width);
+size_t ff_work_floats(int B, int n_features, int n_labels, int n_layers, const int *width, long long *off);
+// the L layer launches and the head; with_y: loss, tallies and (batch mode) d loss / d logits too
+hipError_t launch_ff_forward(const icnn_be_ff_args &d, int mode, bool with_y, hipStream_t stream);
+hipError_t launch_ff_backward(const icnn_be_ff_args &d, hipStream_t stream);
+hipError_t launch_ff_grads(const icnn_be_ff_args &d, hipStream_t stream);
+hipError_t launch_ff_update(const icnn_be_ff_args &d, hipStream_t stream);
+hipError_t launch_ff_fold(const icnn_be_ff_args &d, hipStream_t stream);
+
 }  // namespace icnn_be

@@ -1,0 +1,308 @@
+"""The feed-forward baseline of the multi-label experiment on the device: the model and the training loop of
+multi-label-cls/ff.py around icnn_be_ff_* (icnn_amd/csrc/be_ff.hip), all float32.
+
+L = len(layer_sizes) hidden layers; w_0 = n_features:
+    a_i = relu(h_{i-1} W_i + b_i),  h_i = (a_i - mu_i) gamma_i / sqrt(sigma2_i + 1e-5) + beta_i,  h_0 = x
+    yhat = sigmoid(h_L W_o + b_o),  loss = -sum y log(yhat + 1e-10) - sum (1 - y) log(1 - yhat + 1e-10)   (a SUM)
+One flat float32 vector theta: for i = 1..L  W_i [w_{i-1}, w_i], b_i, gamma_i, beta_i;  then W_o [w_L, n_labels], b_o.
+In training mode (mu, sigma2) are the batch mean and the biased batch variance, and a step folds them once into the moving
+pair of every layer (decay 0.9); in inference mode the moving pair normalises and nothing is written.  One step, enqueued on
+the current stream without a host synchronisation (a captured step replayed k times is k steps), 2 L + 4 launches:
+    L layer forwards, the head (yhat, loss, tallies, d loss / d logits), L layer backwards, the weight gradients, one TF-Adam
+    (lr 1e-3, betas 0.9 / 0.999, eps 1e-8) over theta, the fold
+"""
+import ctypes as C
+import dataclasses
+from typing import Dict, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .train import _Trainer, _TrainF1
+
+BN_EPS = 1e-5
+
+
+@dataclasses.dataclass(frozen=True)
+class FFSpec:
+    n_features: int
+    n_labels: int
+    layer_sizes: Tuple[int, ...] = (600,)
+
+    def __post_init__(self):
+        object.__setattr__(self, "layer_sizes", tuple(int(w) for w in self.layer_sizes))
+
+
+def bibtex_ff_spec() -> FFSpec:
+    """ff.py's defaults on Bibtex: 1836 features, 159 labels, one hidden layer of 600"""
+    return FFSpec(1836, 159, (600,))
+
+
+def layout(spec):
+    """[(name, shape)] of the variables in the order of the flat vector"""
+    out, w_in = [], spec.n_features
+    for i, w in enumerate(spec.layer_sizes, 1):
+        out += [("W%d" % i, (w_in, w)), ("b%d" % i, (w,)), ("gamma%d" % i, (w,)), ("beta%d" % i, (w,))]
+        w_in = w
+    return out + [("Wo", (w_in, spec.n_labels)), ("bo", (spec.n_labels,))]
+
+
+def n_floats(spec) -> int:
+    return sum(int(np.prod(shape)) for _, shape in layout(spec))
+
+
+def flatten(spec, params) -> np.ndarray:
+    parts = []
+    for name, shape in layout(spec):
+        a = np.asarray(params[name], np.float32)
+        if a.shape != shape:
+            raise ValueError("%s: shape %s, expected %s" % (name, a.shape, shape))
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+def unflatten(spec, flat) -> Dict[str, np.ndarray]:
+    out, at = {}, 0
+    for name, shape in layout(spec):
+        n = int(np.prod(shape))
+        out[name] = np.asarray(flat[at:at + n]).reshape(shape).copy()
+        at += n
+    return out
+
+
+def init_params(spec, seed) -> Dict[str, np.ndarray]:
+    """ff.py:114-126 with NumPy's stream, drawn in the order of the flat vector: W and b of a layer uniform in
+    +-1/sqrt(the layer's OUTPUT width) (the logits layer: n_labels), gamma ~ N(1, 0.002), beta = 0; float32."""
+    rng = np.random.RandomState(seed)
+    out = {}
+    for name, shape in layout(spec):
+        if name[0] in "Wb" and not name.startswith("beta"):
+            r = 1.0 / np.sqrt(shape[-1])
+            out[name] = rng.uniform(-r, r, shape).astype(np.float32)
+        elif name.startswith("gamma"):
+            out[name] = (1.0 + 0.002 * rng.standard_normal(shape)).astype(np.float32)
+        else:
+            out[name] = np.zeros(shape, np.float32)
+    return out
+
+
+def _widths(spec):
+    return (C.c_int * _lib.FF_MAX_LAYERS)(*spec.layer_sizes)
+
+
+def _dims(spec):
+    return (spec.n_features, spec.n_labels, len(spec.layer_sizes), _widths(spec))
+
+
+class FFModel:
+    """The flat theta on the device, the moving statistics bn_stats {"mean<i>", "var<i>"} of hidden layer i + 1 (mean 0,
+    variance 1 at the start) and bn_decay.  params: a dict of named arrays or a flat vector; None: init_params(spec, seed)."""
+    has_bn = True
+
+    def __init__(self, spec, params=None, seed=0, device="cuda", bn_decay=0.9):
+        if not 1 <= len(spec.layer_sizes) <= _lib.FF_MAX_LAYERS:
+            raise ValueError("1 to %d hidden layers, got %d" % (_lib.FF_MAX_LAYERS, len(spec.layer_sizes)))
+        if not 0.0 <= bn_decay <= 1.0:
+            raise ValueError("bn_decay must lie in [0, 1], got %r" % (bn_decay,))
+        self.spec, self.device, self.bn_decay = spec, torch.device(device), float(bn_decay)
+        self._lib = _lib.load()
+        n = C.c_longlong()
+        if self._lib.icnn_be_ff_param_floats(*_dims(spec), C.byref(n)) != 0:
+            raise ValueError("sizes beyond what the feed-forward kernels support: %r" % (spec,))
+        self.n = int(n.value)
+        assert self.n == n_floats(spec)
+        self.theta = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.bn_stats = {}
+        for i, w in enumerate(spec.layer_sizes):
+            self.bn_stats["mean%d" % i] = torch.zeros(w, dtype=torch.float32, device=self.device)
+            self.bn_stats["var%d" % i] = torch.ones(w, dtype=torch.float32, device=self.device)
+        self.load(init_params(spec, seed) if params is None else params)
+
+    def load(self, params):
+        """copy a dict of named arrays (or a flat vector) into the existing theta"""
+        flat = flatten(self.spec, params) if isinstance(params, dict) else np.asarray(params, np.float32)
+        if flat.shape != (self.n,):
+            raise ValueError("theta: %s values, expected %d" % (flat.shape, self.n))
+        self.theta.copy_(torch.from_numpy(np.ascontiguousarray(flat)))
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return unflatten(self.spec, self.theta.cpu().numpy())
+
+    def work(self, batch) -> torch.Tensor:
+        """a zeroed workspace for `batch` rows"""
+        nbytes = self._lib.icnn_be_ff_work_bytes(int(batch), *_dims(self.spec))
+        if nbytes == 0:
+            raise ValueError("batch must be >= 1, got %r" % (batch,))
+        return torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+
+    def args(self, batch, work) -> "_lib.FfArgs":
+        """the descriptor of this model at one batch size, without data and optimiser pointers"""
+        a = _lib.FfArgs()
+        a.batch, a.n_features, a.n_labels, a.n_layers = int(batch), self.spec.n_features, self.spec.n_labels, len(self.spec.layer_sizes)
+        a.width = _widths(self.spec)
+        a.theta, a.work = self.theta.data_ptr(), work.data_ptr()
+        for i in range(a.n_layers):
+            a.mv.mean[i] = self.bn_stats["mean%d" % i].data_ptr()
+            a.mv.var[i] = self.bn_stats["var%d" % i].data_ptr()
+        a.mv.decay = self.bn_decay
+        a.lr, a.beta1, a.beta2, a.eps, a.bn_eps = 1e-3, 0.9, 0.999, 1e-8, BN_EPS
+        return a
+
+    def predict(self, x, bn="moving") -> torch.Tensor:
+        """yhat [B, n_labels] for x [B, n_features] float32 on the device; bn "moving" (inference mode, any B) or "batch" (the
+        statistics of this batch, 2 <= B <= 512).  Nothing of the model is written.  No host synchronisation."""
+        if bn not in _lib.BN_MODE:
+            raise ValueError("bn must be 'batch' or 'moving', got %r" % (bn,))
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2 and x.shape[1] == self.spec.n_features and x.is_cuda
+        work = self.work(x.shape[0])
+        out = torch.empty(x.shape[0], self.spec.n_labels, dtype=torch.float32, device=self.device)
+        a = self.args(x.shape[0], work)
+        a.x, a.yhat = x.data_ptr(), out.data_ptr()
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self._lib.icnn_be_ff_forward(C.byref(a), _lib.BN_MODE[bn], stream), "icnn_be_ff_forward")
+        return out
+
+
+class FFTrainer(_Trainer, _TrainF1):
+    """model, Adam's state and the whole training step at one batch size.  step() returns the loss at the weights the step
+    began with: the trainer's 0-d float32 device tensor `loss`; yhat [B, n_labels] and f1_tallies [B, 3] (tp, fp, fn per
+    example; macro_f1() reads them) are those of the same forward.  eval_batch = E also allocates the script's test phase
+    (ff.py:187-196): evaluate(x, true_y) runs inference mode on exactly E samples into eval_loss, eval_yhat, eval_f1_tallies and
+    changes nothing else.  grad holds the last step's flat gradient, work_view(name) the pieces of the workspace
+    (_lib.FF_WORK)."""
+    _no_tallies = "the feed-forward trainer always keeps its tallies"
+
+    def __init__(self, model, batch, lr=1e-3, eval_batch=None):
+        if not isinstance(model, FFModel):
+            raise TypeError("ff.FFTrainer serves ff.FFModel, got %s" % type(model).__name__)
+        self.batch = int(batch)
+        if not 2 <= self.batch <= _lib.FF_MAX_BATCH:
+            raise ValueError("batch must lie in [2, %d], got %r" % (_lib.FF_MAX_BATCH, batch))
+        self.eval_batch = None if eval_batch is None else int(eval_batch)
+        if self.eval_batch is not None and self.eval_batch < 1:
+            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
+        self.model, self.spec, self.device, self.lib = model, model.spec, model.device, model._lib
+        self.lr = float(lr)
+        B, n, dev, f32 = self.batch, model.n, self.device, torch.float32
+        self.x = torch.zeros(B, self.spec.n_features, dtype=f32, device=dev)
+        self.true_y = torch.zeros(B, self.spec.n_labels, dtype=f32, device=dev)
+        self.yhat = torch.zeros(B, self.spec.n_labels, dtype=f32, device=dev)
+        self.loss = torch.zeros((), dtype=f32, device=dev)
+        self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev)
+        # dicts of flat vectors, as the other flat trainers keep them (checkpoint.py)
+        self.theta = {"ff": model.theta}
+        self.m = {"ff": torch.zeros(n, dtype=f32, device=dev)}
+        self.v = {"ff": torch.zeros(n, dtype=f32, device=dev)}
+        self.grad = torch.zeros(n, dtype=f32, device=dev)
+        self.step_count = torch.zeros(_lib.FF_STEP_INTS, dtype=torch.int32, device=dev)
+        self.work = model.work(B)
+        self.work_offsets = self._offsets(B)
+        self._args = self._describe(B, self.work, self.x, self.true_y, self.yhat, self.loss, self.f1_tallies)
+        self.eval_loss = self.eval_yhat = self.eval_f1_tallies = None
+        if self.eval_batch is not None:
+            E = self.eval_batch
+            self.x_eval = torch.zeros(E, self.spec.n_features, dtype=f32, device=dev)
+            self.true_y_eval = torch.zeros(E, self.spec.n_labels, dtype=f32, device=dev)
+            self.eval_yhat = torch.zeros(E, self.spec.n_labels, dtype=f32, device=dev)
+            self.eval_loss = torch.zeros((), dtype=f32, device=dev)
+            self.eval_f1_tallies = torch.zeros(E, 3, dtype=torch.int32, device=dev)
+            self.eval_work = model.work(E)
+            self._eval_args = self._describe(E, self.eval_work, self.x_eval, self.true_y_eval, self.eval_yhat, self.eval_loss,
+                                             self.eval_f1_tallies)
+
+    def _offsets(self, batch):
+        off = (C.c_longlong * len(_lib.FF_WORK))()
+        _lib.check(self.lib.icnn_be_ff_work_offsets(batch, *_dims(self.spec), C.byref(off)), "icnn_be_ff_work_offsets")
+        return dict(zip(_lib.FF_WORK, (int(x) for x in off)))
+
+    def _describe(self, batch, work, x, true_y, yhat, loss, tallies):
+        a = self.model.args(batch, work)
+        a.x, a.true_y, a.yhat, a.loss, a.f1_tallies = (t.data_ptr() for t in (x, true_y, yhat, loss, tallies))
+        a.m, a.v, a.grad, a.step = self.m["ff"].data_ptr(), self.v["ff"].data_ptr(), self.grad.data_ptr(), self.step_count.data_ptr()
+        a.lr = self.lr
+        return a
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, name, args=None):
+        _lib.check(getattr(self.lib, name)(C.byref(self._args if args is None else args), self._stream()), name)
+
+    # ---- the step and its parts ----
+    def forward(self, bn="batch"):
+        """icnn_be_ff_forward alone on the trainer's buffers: the workspace, yhat, loss, f1_tallies"""
+        _lib.check(self.lib.icnn_be_ff_forward(C.byref(self._args), _lib.BN_MODE[bn], self._stream()), "icnn_be_ff_forward")
+
+    def backward(self):
+        self._call("icnn_be_ff_backward")
+
+    def grads(self):
+        self._call("icnn_be_ff_grads")
+
+    def update(self):
+        self._call("icnn_be_ff_update")
+
+    def step(self, x=None, true_y=None) -> torch.Tensor:
+        """One step on (x [B, n_features], true_y [B, n_labels]); None keeps what the buffers hold (graph replay)."""
+        self._put(self.x, x)
+        self._put(self.true_y, true_y)
+        self._call("icnn_be_ff_step")
+        return self.loss
+
+    def evaluate(self, x=None, true_y=None) -> torch.Tensor:
+        """The test phase on exactly eval_batch samples in inference mode: eval_loss (returned), eval_yhat, eval_f1_tallies.
+        Nothing of the model, the optimiser or the training step's results is written.  No host wait (capturable)."""
+        if self.eval_batch is None:
+            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        self._put(self.x_eval, x)
+        self._put(self.true_y_eval, true_y)
+        self._call("icnn_be_ff_eval", self._eval_args)
+        return self.eval_loss
+
+    def eval_macro_f1(self) -> float:
+        """the test F1 of the last evaluate() (util.macroF1; one wait)"""
+        from .train import macro_f1
+        if self.eval_f1_tallies is None:
+            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        return macro_f1(self.eval_f1_tallies)
+
+    def work_view(self, name, eval=False) -> torch.Tensor:
+        """a live view of one piece of the workspace (of evaluate()'s with eval=True): "a<i>", "h<i>", "dz<i>" [B, width],
+        "stat<i>" [2, width] (mu, sigma2), "dlogit" [B, n_labels]"""
+        B = self.eval_batch if eval else self.batch
+        work = self.eval_work if eval else self.work
+        at = (self._offsets(B) if eval else self.work_offsets)[name]
+        if name == "dlogit":
+            rows, width = B, self.spec.n_labels
+        else:
+            width = self.spec.layer_sizes[int(name[-1])]
+            rows = 2 if name.startswith("stat") else B
+        return work[at:at + rows * width].view(rows, width)
+
+    # ---- parameters ----
+    @property
+    def t_steps(self) -> int:
+        """updates done (synchronises)"""
+        return int(self.step_count[0].item())
+
+    def params(self) -> Dict[str, torch.Tensor]:
+        """live views of the variables inside theta"""
+        out, at = {}, 0
+        for name, shape in layout(self.spec):
+            n = int(np.prod(shape))
+            out[name] = self.model.theta[at:at + n].view(shape)
+            at += n
+        return out
+
+    def host_params(self) -> Dict[str, np.ndarray]:
+        return self.model.host_params()
+
+    def load(self, params, reset=True):
+        """Copy a dict of named arrays (or a flat vector) into the existing theta.  reset: Adam's moments and the step count
+        back to zero.  The moving statistics stay.  Synchronises."""
+        self.model.load(params)
+        if reset:
+            self.m["ff"].zero_()
+            self.v["ff"].zero_()
+            self.step_count.zero_()

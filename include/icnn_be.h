@@ -225,7 +225,7 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
  * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
  * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13,
- * sizeof(icnn_be_naf_args) for 14: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_naf_args) for 14, 0 for 15, sizeof(icnn_be_ff_args) for 16: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -1408,6 +1408,82 @@ ICNN_BE_API int icnn_be_naf_act(int dimO, int dimA, int l1, int l2, const float 
                                 void *stream);
 ICNN_BE_API int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
                               const float *obs, const double *act, int batch, float *out, void *stream);
+
+/* ---- the feed-forward baseline of the multi-label experiment (be_ff.hip, additive to ABI 12) ---- */
+
+/*
+ * multi-label-cls/ff.py, all float32.  n_layers = L hidden layers of widths width[0 .. L-1]; w_0 = n_features:
+ *   a_i = relu(h_{i-1} W_i + b_i),  h_i = (a_i - mu_i) gamma_i / sqrt(sigma2_i + bn_eps) + beta_i,  h_0 = x
+ *   yhat = sigmoid(h_L W_o + b_o),  loss = - sum y log(yhat + 1e-10) - sum (1 - y) log(1 - yhat + 1e-10)  over batch and labels
+ * theta is one flat vector: for i = 1..L  W_i [w_{i-1}][w_i], b_i, gamma_i, beta_i;  then W_o [w_L][n_labels], b_o.  m, v and
+ * grad have its layout.  mv.mean[i] / mv.var[i] are the moving pair of hidden layer i + 1 (width[i] floats).
+ *
+ * In ICNN_BE_BN_BATCH mode mu is the batch mean and sigma2 the biased two-pass variance; in ICNN_BE_BN_MOVING mode they are
+ * the moving pair, every row is independent of the others and nothing is written to mv.
+ *   icnn_be_ff_forward   the L layers and the head in `mode`: yhat, and with true_y != NULL the loss, the F1 tallies (unless
+ *                        NULL) and, in batch mode, d loss / d logits.  L + 1 launches.
+ *   icnn_be_ff_backward  after a batch-mode forward with true_y: the pre-activation deltas of every hidden layer, and
+ *                        d gamma, d beta into grad.  L launches.
+ *   icnn_be_ff_grads     the weight and bias gradients into grad: one launch, one fma chain over the batch per element.
+ *   icnn_be_ff_update    one TF-Adam over theta with the step count step[0]: one launch.
+ *   icnn_be_ff_step      forward (batch mode), backward, grads, update, and ONE fold of every layer's (mu, sigma2) into mv:
+ *                        2 L + 4 launches.  loss and yhat are those at the weights the step began with.
+ *   icnn_be_ff_eval      forward in moving mode with true_y: yhat, loss, tallies.
+ * loss is the float64 sum of the head's per-workgroup float64 partials in index order, rounded to float32 once.  f1_tallies
+ * [batch][3] = (tp, fp, fn) of yhat >= 0.5 against (int)y per example, icnn_be_macro_f1's layout.  No float atomics: every
+ * run gives the same bits.  No host synchronisation (capturable in a HIP graph).
+ *
+ * The workspace: icnn_be_ff_work_bytes bytes, 16-byte aligned, ZEROED ONCE by the caller (it holds the ticket the head's
+ * workgroups count themselves with; the kernel re-arms it); icnn_be_ff_work_offsets gives the offset in floats of each piece
+ * ICNN_BE_FF_W_*.  Nothing outside the rows < batch of a piece is written.  step: ICNN_BE_FF_STEP_INTS int32, zero for a fresh
+ * model: [0] the updates, [1] a ticket.
+ *
+ * Sizes: 1 <= n_layers <= ICNN_BE_FF_MAX_LAYERS, 1 <= n_features <= ICNN_BE_FF_MAX_FEATURES, 1 <= width[i], n_labels <=
+ * ICNN_BE_FF_MAX_WIDTH; batch-mode entries 2 <= batch <= ICNN_BE_FF_MAX_BATCH, moving mode any batch >= 1.  Anything else, a
+ * NULL pointer an entry needs, theta / m / v / grad / work not 16-byte aligned, another pointer not 4-byte aligned, or a decay
+ * outside [0, 1] is ICNN_BE_EINVAL before any launch (0 from icnn_be_ff_work_bytes).
+ */
+#define ICNN_BE_FF_MAX_LAYERS 4
+#define ICNN_BE_FF_MAX_FEATURES 4096
+#define ICNN_BE_FF_MAX_WIDTH 1024
+#define ICNN_BE_FF_MAX_BATCH 512
+#define ICNN_BE_FF_STEP_INTS 4
+#define ICNN_BE_FF_W_A 0       /* + i: a_{i+1} [batch][width[i]], i < ICNN_BE_FF_MAX_LAYERS (empty beyond n_layers) */
+#define ICNN_BE_FF_W_H 4       /* + i: h_{i+1} */
+#define ICNN_BE_FF_W_STAT 8    /* + i: mu [width[i]] then sigma2 [width[i]], what a batch-mode forward normalised with */
+#define ICNN_BE_FF_W_DZ 12     /* + i: d loss / d (h_i W_{i+1} + b_{i+1}) */
+#define ICNN_BE_FF_W_DLOGIT 16 /* d loss / d logits [batch][n_labels] */
+#define ICNN_BE_FF_W_PART 17   /* float64: the head's partial sums of the loss */
+#define ICNN_BE_FF_W_CTL 18    /* int32: the head's ticket */
+#define ICNN_BE_FF_WORK_PIECES 19
+typedef struct icnn_be_ff_args {
+    int batch, n_features, n_labels, n_layers;
+    int width[ICNN_BE_FF_MAX_LAYERS];
+    const float *x;                   /* [batch][n_features] */
+    const float *true_y;              /* [batch][n_labels] */
+    float *theta, *m, *v, *grad;
+    icnn_be_bn_moving mv;
+    int *step;                        /* [ICNN_BE_FF_STEP_INTS] */
+    float *loss;                      /* [1] */
+    float *yhat;                      /* [batch][n_labels] */
+    int *f1_tallies;                  /* [batch][3], may be NULL */
+    void *work;
+    double lr, beta1, beta2;
+    float eps, bn_eps;
+} icnn_be_ff_args;                    /* icnn_be_struct_size(16) */
+
+/* floats of theta; EINVAL for sizes out of range */
+ICNN_BE_API int icnn_be_ff_param_floats(int n_features, int n_labels, int n_layers, const int *width, long long *n);
+/* 0 for sizes out of range */
+ICNN_BE_API size_t icnn_be_ff_work_bytes(int batch, int n_features, int n_labels, int n_layers, const int *width);
+ICNN_BE_API int icnn_be_ff_work_offsets(int batch, int n_features, int n_labels, int n_layers, const int *width,
+                                        long long off[ICNN_BE_FF_WORK_PIECES]);
+ICNN_BE_API int icnn_be_ff_forward(const icnn_be_ff_args *a, int mode, void *stream);
+ICNN_BE_API int icnn_be_ff_backward(const icnn_be_ff_args *a, void *stream);
+ICNN_BE_API int icnn_be_ff_grads(const icnn_be_ff_args *a, void *stream);
+ICNN_BE_API int icnn_be_ff_update(const icnn_be_ff_args *a, void *stream);
+ICNN_BE_API int icnn_be_ff_step(const icnn_be_ff_args *a, void *stream);
+ICNN_BE_API int icnn_be_ff_eval(const icnn_be_ff_args *a, void *stream);
 
 #ifdef __cplusplus
 }
