@@ -2,8 +2,8 @@
 y0, the skip of a step on a solver error (skip_on_error) and the test phase (evaluate).  The shapes are those of
 tests/test_bundle_trainer.py ("small": FCSpec(20, 12, (24, 12), batchnorm) at B = 9 / nIter 6; "conv": the default ConvSpec
 at B = 6 / nIter 3).  Every comparison is between two orders of the same launches, or between a launch and its ungated form:
-torch.equal, no tolerance.  A solver error is produced by writing a status word by hand between the two halves of a step,
-never by feeding the solve kernels bad inputs."""
+torch.equal, no tolerance.  A solver error is produced by writing a status word by hand between the two halves of a step;
+one test (test_a_nan_in_the_input_skips_the_step_end_to_end) feeds the step a NaN instead and lets the solve set the bit."""
 import inspect
 
 import numpy as np
@@ -241,6 +241,36 @@ def test_a_skipped_step_changes_nothing_and_the_next_is_the_twins(kind, variant,
     with pytest.raises(ERRORS[bit]):
         tr.raise_on_error()
     tr.step(None, None)                                      # the next clean step: as if the bad one had never been
+    twin.step(None, None)
+    torch.cuda.synchronize()
+    _same_state(tr, _state(twin), twin)
+    assert tr.t_steps == 2 and int(tr.skipped.item()) == 1 and int(tr.went.item()) == 1
+    tr.raise_on_error()
+
+
+@pytest.mark.gpu
+def test_a_nan_in_the_input_skips_the_step_end_to_end():
+    """No hand-written status word: one NaN in one sample's features.  The solve itself sets ICNN_BE_ST_NONFINITE (BatchNorm may
+    spread the NaN over the whole minibatch: only what the gate promises is asserted), the step does not go, and the next
+    clean step is the twin's."""
+    tr, x, t = _trainer("small", "dual", skip_on_error=True)
+    twin, _, _ = _trainer("small", "dual")
+    tr.step(x, t)
+    twin.step(x, t)
+    before = _state(tr)
+    _same_state(twin, before)
+    bad = x.clone()
+    bad[3, 7] = float("nan")
+    tr.step(bad, t)
+    torch.cuda.synchronize()
+    _same_state(tr, before)                                  # theta, m, v, arena, both step words, every statistic
+    assert tr.t_steps == 1
+    assert int(tr.skipped.item()) == 1 and int(tr.went.item()) == 0
+    assert int(tr.status_or.item()) & _lib.ST_NONFINITE
+    assert int(tr.solver.state.status[3].item()) & _lib.ST_NONFINITE
+    with pytest.raises(FloatingPointError):
+        tr.raise_on_error()
+    tr.step(x, t)                                            # the clean batch again
     twin.step(None, None)
     torch.cuda.synchronize()
     _same_state(tr, _state(twin), twin)

@@ -1,7 +1,8 @@
 """CPU-only: the dispatch table of icnn_be_solve_fc (icnn_be_debug_solve_plan), pinned at 256 CUs (MI355X).  The plan is
 host arithmetic over the model and state descriptors, so neither a GPU nor any buffer is needed (wpack and every state
 pointer stay null).  The rows cover every BASELINE configuration, the shapes and flag sets of the GPU tests that compare
-two dispatch paths (tests/test_gpu_parity.py), and the corners of the rule."""
+two dispatch paths (tests/test_gpu_parity.py), the full batches and shards of tests/test_sample_independence.py, and the
+corners of the rule."""
 import ctypes as C
 import os
 import subprocess
@@ -9,7 +10,7 @@ import sys
 
 import pytest
 
-from icnn_amd import _lib, picnn
+from icnn_amd import _lib, dist, picnn
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUS = 256
@@ -77,6 +78,33 @@ TABLE = [
     ((BIB, 16384, 30, "dual", 0, None), ("TILE", 16, 0, 30)),                        # nIter > 15: no upper bound
     ((BIB, 1008, 30, "dual", SLICE | PERS, None), ("TILE_BUDGETED_THEN_ROWS", 4, 8, 31)),
     ((BIB, 1008, 30, "dual", LOCK, None), ("ROUNDS_LOCKSTEP", 0, 0, 30)),
+    # tests/test_sample_independence.py: the smallest batches at which the default dispatch puts the full batch and its
+    # contiguous shards (dist.shard_bounds, world 2, 4, 8) on different kernels; every path is the one the rule was expected to
+    # give, no batch size had to move.  1043 = 130 tiles of 8 and one of 3, 260 quads and one of 3
+    ((BIB, 1043, 10, "dual", 0, None), ("TILE", 8, 0, 10)),
+    ((BIB, 522, 10, "dual", 0, None), ("ROWS", 3, 0, 10)),
+    ((BIB, 521, 10, "dual", 0, None), ("ROWS", 3, 0, 10)),
+    ((BIB, 261, 10, "dual", 0, None), ("ROWS", 2, 0, 10)),
+    ((BIB, 260, 10, "dual", 0, None), ("ROWS", 2, 0, 10)),
+    ((BIB, 131, 10, "dual", 0, None), ("ROWS", 1, 0, 10)),
+    ((BIB, 130, 10, "dual", 0, None), ("ROWS", 1, 0, 10)),
+    ((BIB, 1, 10, "dual", 0, None), ("ROWS", 1, 0, 10)),                             # one sample alone
+    ((BIB, 1043, 20, "dual", 0, None), ("TILE", 8, 0, 20)),                          # nIter > 15: the 32-slot tile instance
+    ((BIB, 522, 20, "dual", 0, None), ("ROWS", 3, 0, 20)),
+    ((BIB, 261, 20, "dual", 0, None), ("ROWS", 2, 0, 20)),
+    ((BIB, 131, 20, "dual", 0, None), ("ROWS", 1, 0, 20)),
+    ((BIB, 2051, 10, "dual", 0, None), ("TILE", 16, 0, 10)),
+    ((BIB, 1026, 10, "dual", 0, None), ("TILE", 8, 0, 10)),                          # 16-row against 8-row tiles
+    ((BIB, 513, 10, "dual", 0, None), ("ROWS", 3, 0, 10)),
+    ((BIB, 257, 10, "dual", 0, None), ("ROWS", 2, 0, 10)),
+    ((BIB, 256, 10, "dual", 0, None), ("ROWS", 1, 0, 10)),
+    ((BIB, 1043, 10, "pdipm", 0, None), ("TILE", 8, 0, 10)),
+    ((BIB, 522, 10, "pdipm", 0, None), ("ROWS", 3, 0, 10)),
+    ((BIB, 131, 10, "pdipm", 0, None), ("ROWS", 1, 0, 10)),
+    ((HC, 1043, 5, "rl", 0, None), ("ROUNDS_LOCKSTEP", 0, 0, 5)),                    # the four-samples-per-wave dual step
+    ((HC, 522, 5, "rl", 0, None), ("ROWS", 3, 0, 5)),
+    ((HC, 261, 5, "rl", 0, None), ("ROWS", 2, 0, 5)),
+    ((HC, 131, 5, "rl", 0, None), ("ROWS", 1, 0, 5)),
 ]
 
 # the shapes and flag sets of the GPU tests that compare two dispatch paths: (test, spec, B, nIter, variant, slots, flags A,
@@ -98,6 +126,13 @@ PAIRS = [("pdipm_persistent", BIB, B, T, "pdipm", None, 0, TWO)
         [("overflow", BIB, B, T, "dual", S, 0, TWO) for B, S, T in [(1100, 16, 40), (1100, 20, 36), (40, 16, 40)]] + \
         [("time_sliced", BIB, 1100, 30, "dual", None, SLICE, LOCK)]
 
+# tests/test_sample_independence.py solves a full batch in one launch and again as the contiguous shards of `world` ranks:
+# (spec, B, nIter, variant) x world; the full batch and at least one shard must differ in (path, samples per workgroup)
+FULL_BATCHES = [(BIB, 1043, 10, "dual"), (BIB, 1043, 20, "dual"), (BIB, 2051, 10, "dual"), (BIB, 1043, 10, "pdipm"),
+                (HC, 1043, 5, "rl")]
+WORLDS = (2, 4, 8)
+SHARDS = [full + (world,) for full in FULL_BATCHES for world in WORLDS]
+
 
 @pytest.mark.parametrize("args,expected", TABLE, ids=["%d_%d_%s_%d" % (a[1], a[2], a[3], a[4]) for a, _ in TABLE])
 def test_solve_plan_table(args, expected):
@@ -109,6 +144,15 @@ def test_dispatch_pairs_of_the_gpu_tests_take_different_paths(pair):
     _, spec, B, n_iter, variant, slots, fa, fb = pair
     a, b = plan(spec, B, n_iter, variant, fa, slots), plan(spec, B, n_iter, variant, fb, slots)
     assert a[0] != b[0], (a, b)
+
+
+@pytest.mark.parametrize("case", SHARDS, ids=["%d_%d_%s_world%d" % c[1:] for c in SHARDS])
+def test_shards_of_the_sample_independence_tests_leave_the_full_batchs_kernel(case):
+    spec, B, n_iter, variant, world = case
+    full = plan(spec, B, n_iter, variant)
+    sizes = sorted({hi - lo for lo, hi in (dist.shard_bounds(B, world, r) for r in range(world))})
+    shards = [plan(spec, size, n_iter, variant) for size in sizes]
+    assert any(s[:2] != full[:2] for s in shards), (full, shards)
 
 
 def test_profile_buffer_changes_no_path():
