@@ -1,4 +1,5 @@
 _FF = ("FFSpec", "FFModel", "FFTrainer", "bibtex_ff_spec")
+_FCN = ("FCNSpec", "FCNModel", "FCNTrainer", "olivetti_fcn_spec")
 
 
 def __getattr__(name):
@@ -6,4 +7,7 @@ def __getattr__(name):
     if name in _FF:
         from . import ff
         return getattr(ff, name)
+    if name in _FCN:
+        from . import fcn
+        return getattr(fcn, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -76,6 +76,8 @@ EXPORTS = [
     "icnn_be_naf_update", "icnn_be_naf_step", "icnn_be_naf_act", "icnn_be_naf_q",
     "icnn_be_ff_param_floats", "icnn_be_ff_work_bytes", "icnn_be_ff_work_offsets", "icnn_be_ff_forward", "icnn_be_ff_backward",
     "icnn_be_ff_grads", "icnn_be_ff_update", "icnn_be_ff_step", "icnn_be_ff_eval",
+    "icnn_be_fcn_param_floats", "icnn_be_fcn_work_bytes", "icnn_be_fcn_work_offsets", "icnn_be_fcn_forward", "icnn_be_fcn_backward",
+    "icnn_be_fcn_grads", "icnn_be_fcn_update", "icnn_be_fcn_step", "icnn_be_fcn_eval",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -108,6 +110,10 @@ FF_STEP_INTS = 4                           # ICNN_BE_FF_STEP_INTS: the updates, 
 # ICNN_BE_FF_W_*: the pieces of the feed-forward workspace, in order; a / h / stat / dz of hidden layer i + 1 at "a%d" % i, ...
 FF_WORK = (["a%d" % i for i in range(4)] + ["h%d" % i for i in range(4)] + ["stat%d" % i for i in range(4)]
            + ["dz%d" % i for i in range(4)] + ["dlogit", "part", "ctl"])
+FCN_MAX_K, FCN_MAX_HW, FCN_MAX_BATCH, FCN_MAX_EVAL_BATCH = 64, 128, 128, 65536     # ICNN_BE_FCN_MAX_*
+FCN_STEP_INTS = 4                          # ICNN_BE_FCN_STEP_INTS: the updates, the ticket
+# ICNN_BE_FCN_W_*: the pieces of the FCN workspace, in order; h<i> / dz<i>: output and delta of conv1..3, up1..3
+FCN_WORK = ["h%d" % i for i in range(6)] + ["dy"] + ["dz%d" % i for i in range(6)] + ["wpart", "lpart", "ctl"]
 
 
 def replay_stage_bytes(dimO, dimA):
@@ -258,6 +264,18 @@ class FfArgs(C.Structure):
         ("step", C.c_void_p), ("loss", C.c_void_p), ("yhat", C.c_void_p), ("f1_tallies", C.c_void_p), ("work", C.c_void_p),
         ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
         ("eps", C.c_float), ("bn_eps", C.c_float),
+    ]
+
+
+class FcnArgs(C.Structure):
+    """struct icnn_be_fcn_args"""
+    _fields_ = [
+        ("batch", C.c_int), ("H", C.c_int), ("W", C.c_int), ("k", C.c_int),
+        ("x", C.c_void_p), ("t", C.c_void_p),
+        ("theta", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p),
+        ("step", C.c_void_p), ("loss", C.c_void_p), ("yhat", C.c_void_p), ("work", C.c_void_p),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+        ("eps", C.c_float), ("pixel_scale", C.c_float),
     ]
 
 
@@ -498,6 +516,14 @@ def load():
     for name in ("backward", "grads", "update", "step", "eval"):
         fn = getattr(lib, "icnn_be_ff_" + name)
         fn.argtypes, fn.restype = [FA, C.c_void_p], C.c_int
+    CA = C.POINTER(FcnArgs)
+    lib.icnn_be_fcn_param_floats.argtypes, lib.icnn_be_fcn_param_floats.restype = [C.c_int] * 3 + [C.POINTER(C.c_longlong)], C.c_int
+    lib.icnn_be_fcn_work_bytes.argtypes, lib.icnn_be_fcn_work_bytes.restype = [C.c_int] * 4, C.c_size_t
+    lib.icnn_be_fcn_work_offsets.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong * len(FCN_WORK))]
+    lib.icnn_be_fcn_work_offsets.restype = C.c_int
+    for name in ("forward", "backward", "grads", "update", "step", "eval"):
+        fn = getattr(lib, "icnn_be_fcn_" + name)
+        fn.argtypes, fn.restype = [CA, C.c_void_p], C.c_int
     FM = C.POINTER(FicnnModel)
     lib.icnn_be_ficnn_pack_floats.argtypes = [FM]
     lib.icnn_be_ficnn_pack_floats.restype = C.c_size_t
@@ -539,6 +565,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_naf_args differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(16) != C.sizeof(FfArgs):
         raise ImportError("ctypes struct layout of icnn_be_ff_args differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(18) != C.sizeof(FcnArgs):
+        raise ImportError("ctypes struct layout of icnn_be_fcn_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

@@ -11,6 +11,7 @@ result depends on:
     ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
     naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count
     ff.FFTrainer         the flat theta/ff, m/ff, v/ff, the step count and the moving statistics bn/mean<i>, bn/var<i>
+    fcn.FCNTrainer       the flat theta/fcn, m/fcn, v/fcn and the step count
     Agent, DDPGAgent, NAFAgent   its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
                          with memory=True, the filled part of the four replay arrays and the control block (cursor, fill, draw
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
@@ -84,8 +85,8 @@ def spec_json(spec) -> str:
 # What each object's state is made of
 # --------------------------------------------------------------------------------------------- #
 def _kind(obj) -> str:
-    from . import ddpg, ff, ficnn, naf, rl_agent, rl_train, train
-    for cls, kind in ((ff.FFTrainer, "FFTrainer"), (train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
+    from . import ddpg, fcn, ff, ficnn, naf, rl_agent, rl_train, train
+    for cls, kind in ((ff.FFTrainer, "FFTrainer"), (fcn.FCNTrainer, "FCNTrainer"), (train.BundleTrainer, "BundleTrainer"), (train.GDTrainer, "GDTrainer"),
                       (train.ConvGDTrainer, "ConvGDTrainer"), (ficnn.GDTrainer, "ficnn.GDTrainer"),
                       (rl_train.CriticTrainer, "CriticTrainer"), (rl_agent.Agent, "Agent"),
                       (ddpg.DDPGTrainer, "DDPGTrainer"), (rl_agent.DDPGAgent, "DDPGAgent"),
@@ -93,10 +94,10 @@ def _kind(obj) -> str:
         if isinstance(obj, cls):
             return kind
     raise TypeError("checkpoint serves BundleTrainer, GDTrainer, ConvGDTrainer, ficnn.GDTrainer, CriticTrainer, Agent, "
-                    "DDPGTrainer, DDPGAgent, NAFTrainer, NAFAgent and ff.FFTrainer, got %s" % type(obj).__name__)
+                    "DDPGTrainer, DDPGAgent, NAFTrainer, NAFAgent, ff.FFTrainer and fcn.FCNTrainer, got %s" % type(obj).__name__)
 
 
-FLAT_TRAINERS = ("DDPGTrainer", "NAFTrainer", "FFTrainer")  # trainers whose state is flat vectors in dicts theta, m, v
+FLAT_TRAINERS = ("DDPGTrainer", "NAFTrainer", "FFTrainer", "FCNTrainer")  # trainers whose state is flat vectors in dicts theta, m, v
 AGENTS = {"Agent": "CriticTrainer", "DDPGAgent": "DDPGTrainer", "NAFAgent": "NAFTrainer"}     # an agent's kind -> its trainer's
 
 

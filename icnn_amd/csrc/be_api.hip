@@ -22,6 +22,12 @@ int fail(hipError_t e) {
 }
 
 int done(hipError_t e) { return e == hipSuccess ? 0 : fail(e); }
+}  // namespace
+
+// for the entries defined beside their kernels (be_fcn.hip)
+int icnn_be::api_done(hipError_t e) { return done(e); }
+
+namespace {
 
 // everything about a state but its buffers
 int check_shape(const icnn_be_state *st) {
@@ -256,7 +262,7 @@ size_t icnn_be_struct_size(int which) {
          : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay)
          : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log)
          : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args)
-         : which == 16 ? sizeof(icnn_be_ff_args) : 0;
+         : which == 16 ? sizeof(icnn_be_ff_args) : which == 18 ? sizeof(icnn_be_fcn_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */

@@ -427,4 +427,8 @@ hipError_t launch_ff_grads(const icnn_be_ff_args &d, hipStream_t stream);
 hipError_t launch_ff_update(const icnn_be_ff_args &d, hipStream_t stream);
 hipError_t launch_ff_fold(const icnn_be_ff_args &d, hipStream_t stream);
 
+// ---- the FCN baseline (be_fcn.hip defines its icnn_be_fcn_* entries itself) ---------------
+// 0, or the C ABI's error code with the HIP error kept for icnn_be_last_hip_error (be_api.hip)
+int api_done(hipError_t e);
+
 }  // namespace icnn_be

@@ -1299,16 +1299,17 @@ class EpochRunner:
     """`steps` iterations of [dataset.draw_into(*buffers), trainer.step(), log.append()] per run(), with no host wait inside:
     the first run() is eager, the second captures the chain once on a side stream and replays it, later runs replay
     (DESIGN.md §21).  After r runs the trainer's state is that of r x steps eager iterations bit for bit, whichever runs
-    were eager, capturing or replays.  trainer: a BundleTrainer (FC or conv), GDTrainer, ConvGDTrainer or ff.FFTrainer; step() reads its
+    were eager, capturing or replays.  trainer: a BundleTrainer (FC or conv), GDTrainer, ConvGDTrainer, ff.FFTrainer or fcn.FCNTrainer; step() reads its
     buffers as step(None, None) does.  buffers: where the dataset's arrays go, by default (trainer.x, trainer.true_y) for a
     trainer that has true_y, else (trainer.x, trainer.t).  log: a StepLog, appended to after every step.
 
     With BundleTrainer(skip_on_error=True) a skipped step still consumes its draw, as the reference draws before its try."""
 
     def __init__(self, trainer, dataset, steps, log=None, buffers=None):
+        from .fcn import FCNTrainer
         from .ff import FFTrainer
-        if not isinstance(trainer, (BundleTrainer, GDTrainer, ConvGDTrainer, FFTrainer)):
-            raise TypeError("EpochRunner serves BundleTrainer, GDTrainer, ConvGDTrainer and ff.FFTrainer, got %s"
+        if not isinstance(trainer, (BundleTrainer, GDTrainer, ConvGDTrainer, FFTrainer, FCNTrainer)):
+            raise TypeError("EpochRunner serves BundleTrainer, GDTrainer, ConvGDTrainer, ff.FFTrainer and fcn.FCNTrainer, got %s"
                             % type(trainer).__name__)
         if not isinstance(dataset, DeviceDataset):
             raise TypeError("dataset is a train.DeviceDataset, got %s" % type(dataset).__name__)

@@ -225,7 +225,8 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
  * sizeof(icnn_be_conv_model) for 3, sizeof(icnn_be_conv_ctx) for 4, sizeof(icnn_be_bn_moving) for 5,
  * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
  * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13,
- * sizeof(icnn_be_naf_args) for 14, 0 for 15, sizeof(icnn_be_ff_args) for 16: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_naf_args) for 14, 0 for 15, sizeof(icnn_be_ff_args) for 16, 0 for 17,
+ * sizeof(icnn_be_fcn_args) for 18: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -1484,6 +1485,70 @@ ICNN_BE_API int icnn_be_ff_grads(const icnn_be_ff_args *a, void *stream);
 ICNN_BE_API int icnn_be_ff_update(const icnn_be_ff_args *a, void *stream);
 ICNN_BE_API int icnn_be_ff_step(const icnn_be_ff_args *a, void *stream);
 ICNN_BE_API int icnn_be_ff_eval(const icnn_be_ff_args *a, void *stream);
+
+/* ---- the FCN baseline of the completion experiment (be_fcn.hip, additive to ABI 12) ----
+ *
+ * completion/baseline.py's fully convolutional net on single-channel images [batch][H][W], all float32:
+ *   conv1..3   3x3, stride 2, dilation 2, padding 2 (1 -> k, k -> k, k -> k): output i reads inputs 2i-2, 2i, 2i+2
+ *   up1..3     transposed 3x3, stride 2, padding 1, output_padding 1 (k -> k): out[o] += in[i] w[t], o = 2i - 1 + t
+ *   up4        transposed 1x1 (k -> 1);  ReLU behind every layer but up4;  yhat = up4's output
+ *   loss = mean((pixel_scale (yhat - t))^2) over batch H W;  torch's Adam (eps outside the bias correction).
+ * theta: one flat vector in the order and layouts of torch's model.parameters(): conv_i.weight [k][Cin][3][3], conv_i.bias,
+ * up_i.weight [Cin][Cout][3][3], up_i.bias, up4.weight [k][1][1][1], up4.bias: 45 k^2 + 16 k + 1 floats.
+ *
+ *   icnn_be_fcn_forward   the seven layers: the six ReLU outputs into the workspace (channels last: [batch][h][w][k]) and yhat;
+ *                         with t != NULL also loss, d loss / d yhat and up3's delta (batch <= ICNN_BE_FCN_MAX_BATCH).
+ *   icnn_be_fcn_backward  after a forward with t: the pre-activation deltas of up2 ... conv1.
+ *   icnn_be_fcn_grads     the flat gradient into grad: partial sums over fixed chunks of positions, added in index order.
+ *   icnn_be_fcn_update    one torch-Adam over theta with the step count step[0], which advances by one: one launch.
+ *   icnn_be_fcn_step      forward, backward, grads, update.
+ *   icnn_be_fcn_eval      forward and loss alone: yhat, loss and the activations; no delta, nothing of the model.
+ * No entry synchronises; every entry is capturable; results have the same bits on every run.
+ *
+ * The workspace: icnn_be_fcn_work_bytes bytes, 16-byte aligned, ZEROED ONCE by the caller (it holds the ticket of the loss;
+ * the kernel re-arms it); icnn_be_fcn_work_offsets gives the offset in floats of each piece ICNN_BE_FCN_W_*.  step:
+ * ICNN_BE_FCN_STEP_INTS int32, zero for a fresh optimiser (the updates done, the update's ticket).
+ *
+ * Sizes: k a multiple of 16 in [16, ICNN_BE_FCN_MAX_K]; H and W multiples of 8 in [8, ICNN_BE_FCN_MAX_HW]; 1 <= batch <=
+ * ICNN_BE_FCN_MAX_BATCH for every entry that trains (forward with t, backward, grads, step), 1 <= batch <=
+ * ICNN_BE_FCN_MAX_EVAL_BATCH otherwise.  Anything else, a NULL or misaligned pointer (16 bytes: theta, m, v, grad, work; 4
+ * bytes: the rest), betas outside [0, 1) or eps <= 0 is ICNN_BE_EINVAL before any launch (0 from icnn_be_fcn_work_bytes). */
+#define ICNN_BE_FCN_MAX_K 64
+#define ICNN_BE_FCN_MAX_HW 128
+#define ICNN_BE_FCN_MAX_BATCH 128
+#define ICNN_BE_FCN_MAX_EVAL_BATCH 65536
+#define ICNN_BE_FCN_STEP_INTS 4
+#define ICNN_BE_FCN_W_H 0       /* + i, i < 6: the ReLU output of conv1, conv2, conv3, up1, up2, up3 [batch][h_i][w_i][k] */
+#define ICNN_BE_FCN_W_DY 6      /* d loss / d yhat [batch][H][W] */
+#define ICNN_BE_FCN_W_DZ 7      /* + i, i < 6: d loss / d (pre-activation of layer i), zero where the ReLU is off */
+#define ICNN_BE_FCN_W_WPART 13  /* the chunk partials of the gradient */
+#define ICNN_BE_FCN_W_LPART 14  /* float64: the partial sums of the loss and of d yhat, two per workgroup */
+#define ICNN_BE_FCN_W_CTL 15    /* [0] int32: the loss's ticket; [1] float: sum of d yhat (up4.bias's gradient) */
+#define ICNN_BE_FCN_WORK_PIECES 16
+typedef struct icnn_be_fcn_args {
+    int batch, H, W, k;
+    const float *x;                   /* [batch][H][W] */
+    const float *t;                   /* [batch][H][W]; NULL in icnn_be_fcn_forward: yhat alone */
+    float *theta, *m, *v, *grad;
+    int *step;                        /* [ICNN_BE_FCN_STEP_INTS] */
+    float *loss;                      /* [1] */
+    float *yhat;                      /* [batch][H][W] */
+    void *work;
+    double lr, beta1, beta2;
+    float eps, pixel_scale;
+} icnn_be_fcn_args;                   /* icnn_be_struct_size(18) */
+
+/* floats of theta; EINVAL for sizes out of range */
+ICNN_BE_API int icnn_be_fcn_param_floats(int H, int W, int k, long long *n);
+/* 0 for sizes out of range */
+ICNN_BE_API size_t icnn_be_fcn_work_bytes(int batch, int H, int W, int k);
+ICNN_BE_API int icnn_be_fcn_work_offsets(int batch, int H, int W, int k, long long off[ICNN_BE_FCN_WORK_PIECES]);
+ICNN_BE_API int icnn_be_fcn_forward(const icnn_be_fcn_args *a, void *stream);
+ICNN_BE_API int icnn_be_fcn_backward(const icnn_be_fcn_args *a, void *stream);
+ICNN_BE_API int icnn_be_fcn_grads(const icnn_be_fcn_args *a, void *stream);
+ICNN_BE_API int icnn_be_fcn_update(const icnn_be_fcn_args *a, void *stream);
+ICNN_BE_API int icnn_be_fcn_step(const icnn_be_fcn_args *a, void *stream);
+ICNN_BE_API int icnn_be_fcn_eval(const icnn_be_fcn_args *a, void *stream);
 
 #ifdef __cplusplus
 }
