@@ -112,25 +112,17 @@ PartAt part_at(const Shape &s) {
 int head_blocks(const Shape &s) { return (int)((s.pos[5] + HEAD_POS - 1) / HEAD_POS); }
 
 size_t work_walk(const Shape &s, long long *off) {
-    Carver c{nullptr};
     size_t floats[ICNN_BE_FCN_WORK_PIECES] = {};
     for (int i = 0; i < 6; ++i) floats[ICNN_BE_FCN_W_H + i] = floats[ICNN_BE_FCN_W_DZ + i] = (size_t)s.pos[i] * s.k;
     floats[ICNN_BE_FCN_W_DY] = (size_t)s.pos[5];
     floats[ICNN_BE_FCN_W_WPART] = (size_t)part_at(s).end;
     floats[ICNN_BE_FCN_W_LPART] = 4 * (size_t)head_blocks(s);
     floats[ICNN_BE_FCN_W_CTL] = 4;
-    for (int i = 0; i < ICNN_BE_FCN_WORK_PIECES; ++i) {
-        if (off) off[i] = (long long)c.at;
-        c.take(floats[i]);
-    }
-    return c.at;
+    return WorkPieces<ICNN_BE_FCN_WORK_PIECES>::walk(floats, off);
 }
 
-struct Work {
-    long long off[ICNN_BE_FCN_WORK_PIECES];
-    float *w;
-    Work(const icnn_be_fcn_args &d, const Shape &s) : w(static_cast<float *>(d.work)) { work_walk(s, off); }
-    float *at(int piece) const { return w + off[piece]; }
+struct Work : WorkPieces<ICNN_BE_FCN_WORK_PIECES> {
+    Work(const icnn_be_fcn_args &d, const Shape &s) : WorkPieces(d.work) { work_walk(s, off); }
 };
 
 // ---- conv1 --------------------------------------------------------------------------------------------------------------

@@ -14,8 +14,8 @@
 //                         (a ticket, nobody waits) adds the partials in index order and writes the loss.
 //   ff_layer_bwd_kernel   du = delta_{i+1} W_{i+1}^T for the workgroup's columns, S1 and S2 over the batch in LDS, da, the
 //                         ReLU mask from the stored a_i, dz_i; d gamma_i and d beta_i go straight into the flat gradient.
-//   the weight gradients  ddpg_grads_kernel (be_ddpg.hip) over a table of the L + 1 products.
-//   the update            ddpg_update_kernel over one parameter set without a target.
+//   the weight gradients  grad_table_kernel (be_train_table.hip) over a table of the L + 1 products.
+//   the update            param_sets_update_kernel (be_train_table.hip) over one parameter set without a target.
 //   the fold              bn_fold_kernel (be_context.hip).
 //
 // The product (col_gemm): the wave w owns the 16-row tiles w, w + 8, ... of the workgroup's rows; K is streamed in chunks of
@@ -25,8 +25,8 @@
 // accumulator layout; two accumulators per tile take the k steps alternately and are added at the end, so a sum's order
 // depends on K alone: a row's result has the same bits wherever the row lies in whichever batch, whatever the chunk.
 #include "be_kernels.h"
-#include "be_tile.h"
 #include "be_train_common.h"
+#include "be_train_table.h"
 
 namespace icnn_be {
 
@@ -341,7 +341,6 @@ int row_groups(int B, int mode) { return mode == ICNN_BE_BN_MOVING ? (B + FROWS_
 
 // the workspace, piece by piece (ICNN_BE_FF_W_*): float offsets
 size_t work_walk(int B, int nl, const int *width, int n_labels, long long *off) {
-    Carver c{nullptr};
     const size_t b = (size_t)B;
     size_t floats[ICNN_BE_FF_WORK_PIECES] = {};
     for (int i = 0; i < nl; ++i) {
@@ -351,11 +350,7 @@ size_t work_walk(int B, int nl, const int *width, int n_labels, long long *off) 
     floats[ICNN_BE_FF_W_DLOGIT] = b * n_labels;
     floats[ICNN_BE_FF_W_PART] = 2 * (size_t)col_blocks(n_labels) * row_groups(B, ICNN_BE_BN_MOVING);
     floats[ICNN_BE_FF_W_CTL] = 4;
-    for (int i = 0; i < ICNN_BE_FF_WORK_PIECES; ++i) {
-        if (off) off[i] = (long long)c.at;
-        c.take(floats[i]);
-    }
-    return c.at;
+    return WorkPieces<ICNN_BE_FF_WORK_PIECES>::walk(floats, off);
 }
 
 // where the variables of the flat vector begin: W_i, then b_i, gamma_i, beta_i behind it; i == n_layers: W_o, b_o
@@ -378,11 +373,8 @@ ThetaAt theta_at(const icnn_be_ff_args &d, int i) {
     return t;
 }
 
-struct Work {
-    long long off[ICNN_BE_FF_WORK_PIECES];
-    float *w;
-    Work(const icnn_be_ff_args &d) : w(static_cast<float *>(d.work)) { work_walk(d.batch, d.n_layers, d.width, d.n_labels, off); }
-    float *at(int piece) const { return w + off[piece]; }
+struct Work : WorkPieces<ICNN_BE_FF_WORK_PIECES> {
+    Work(const icnn_be_ff_args &d) : WorkPieces(d.work) { work_walk(d.batch, d.n_layers, d.width, d.n_labels, off); }
 };
 
 }  // namespace
@@ -459,6 +451,8 @@ hipError_t launch_ff_backward(const icnn_be_ff_args &d, hipStream_t stream) {
     return hipSuccess;
 }
 
+static_assert(ICNN_BE_FF_MAX_LAYERS + 1 <= GRAD_PRODUCTS, "launch_ff_grads: GradArgs::layer does not check its index");
+
 hipError_t launch_ff_grads(const icnn_be_ff_args &d, hipStream_t stream) {
     const Work w(d);
     GradArgs a{};
@@ -478,7 +472,7 @@ hipError_t launch_ff_grads(const icnn_be_ff_args &d, hipStream_t stream) {
 }
 
 hipError_t launch_ff_update(const icnn_be_ff_args &d, hipStream_t stream) {
-    UpdArgs u{};
+    ParamSetsArgs u{};
     const long long n = ff_param_floats(d.n_features, d.n_labels, d.n_layers, d.width);
     u.set[0] = ParamSet{d.theta, d.m, d.v, nullptr, d.grad, n, (int)param_update_blocks(n), 0, 0.f, d.lr};
     u.sets = 1;

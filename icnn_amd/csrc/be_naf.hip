@@ -8,9 +8,9 @@
 //                        pre-activation deltas.  Products are tile_gemm of be_tile.h; the head is per-sample VALU work, a
 //                        group of 32 lanes per sample with lane j owning column j of the L matrix and every sum one fma
 //                        chain in index order.  full = 0 stops after q: that is icnn_be_naf_q, with the chain's bits.
-//   the weight gradients  ddpg_grads_kernel (be_ddpg.hip) over a table of the nine layers.
-//   the update            ddpg_update_kernel over three parameter sets with one step count; only V has a target; sum
-//                        theta_old^2 of all three enters loss_q.
+//   the weight gradients  grad_table_kernel (be_train_table.hip) over a table of the nine layers.
+//   the update            param_sets_update_kernel (be_train_table.hip) over three parameter sets with one step count; only V
+//                        has a target; sum theta_old^2 of all three enters loss_q.
 //   u for B rows          the U net is DDPG's policy: be_api.hip launches ddpg_act_kernel on theta_u.
 //
 // LDS: bA holds the obs rows and later, when no first layer needs them any more, the dimA^2 wide l rows (then d loss / d l in
@@ -19,6 +19,7 @@
 #include "be_kernels.h"
 #include "be_tile.h"
 #include "be_train_common.h"
+#include "be_train_table.h"
 
 namespace icnn_be {
 
@@ -222,7 +223,6 @@ long long update_blocks(int dimO, int dimA, int l1, int l2) {
 
 // the workspace, piece by piece (ICNN_BE_NAF_W_*): float offsets
 size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
-    Carver c{nullptr};
     const size_t b = (size_t)B, nL = (size_t)dimA * dimA;
     const int tiles = (B + TS - 1) / TS;
     const size_t width[ICNN_BE_NAF_WORK_PIECES] = {
@@ -231,12 +231,12 @@ size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
         b * nL, b * l2, b * l1, b * dimA, b * l2, b * l1, b, b * l2, b * l1,   // the deltas of L, U, V
         2 * (size_t)tiles,                                                  // sums of td^2, float64
         2 * (size_t)update_blocks(dimO, dimA, l1, l2)};                     // the update's partials, float64
-    for (int i = 0; i < ICNN_BE_NAF_WORK_PIECES; ++i) {
-        if (off) off[i] = (long long)c.at;
-        c.take(width[i]);
-    }
-    return c.at;
+    return WorkPieces<ICNN_BE_NAF_WORK_PIECES>::walk(width, off);
 }
+
+struct Work : WorkPieces<ICNN_BE_NAF_WORK_PIECES> {
+    Work(const icnn_be_naf_args &d) : WorkPieces(d.work) { work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off); }
+};
 
 }  // namespace
 
@@ -249,9 +249,7 @@ bool naf_fits(int dimO, int dimA, int l1, int l2) { return pitches(dimO, dimA, l
 size_t naf_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off) { return work_walk(B, dimO, dimA, l1, l2, off); }
 
 hipError_t launch_naf_chain(const icnn_be_naf_args &d, hipStream_t stream) {
-    long long off[ICNN_BE_NAF_WORK_PIECES];
-    work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off);
-    float *w = static_cast<float *>(d.work);
+    const Work w(d);
     const Pitches p = pitches(d.dimO, d.dimA, d.l1, d.l2);
     NafChainArgs a{};
     a.B = d.batch; a.dimO = d.dimO; a.dimA = d.dimA; a.l1 = d.l1; a.l2 = d.l2; a.full = 1;
@@ -259,15 +257,15 @@ hipError_t launch_naf_chain(const icnn_be_naf_args &d, hipStream_t stream) {
     a.tl = d.theta_l; a.tu = d.theta_u; a.tv = d.theta_v; a.ttv = d.target_v;
     a.discount = d.discount;
     a.inv_b = 1.f / (float)d.batch;
-    a.y = w + off[ICNN_BE_NAF_W_Y]; a.u = w + off[ICNN_BE_NAF_W_U]; a.l = w + off[ICNN_BE_NAF_W_L];
-    a.ld = w + off[ICNN_BE_NAF_W_LD]; a.h = w + off[ICNN_BE_NAF_W_H]; a.adv = w + off[ICNN_BE_NAF_W_ADV];
-    a.q = w + off[ICNN_BE_NAF_W_Q]; a.td = w + off[ICNN_BE_NAF_W_TD];
-    a.h1l = w + off[ICNN_BE_NAF_W_H1L]; a.h2l = w + off[ICNN_BE_NAF_W_H2L]; a.h1u = w + off[ICNN_BE_NAF_W_H1U];
-    a.h2u = w + off[ICNN_BE_NAF_W_H2U]; a.h1v = w + off[ICNN_BE_NAF_W_H1V]; a.h2v = w + off[ICNN_BE_NAF_W_H2V];
-    a.d3l = w + off[ICNN_BE_NAF_W_D3L]; a.d2l = w + off[ICNN_BE_NAF_W_D2L]; a.d1l = w + off[ICNN_BE_NAF_W_D1L];
-    a.d3u = w + off[ICNN_BE_NAF_W_D3U]; a.d2u = w + off[ICNN_BE_NAF_W_D2U]; a.d1u = w + off[ICNN_BE_NAF_W_D1U];
-    a.d3v = w + off[ICNN_BE_NAF_W_D3V]; a.d2v = w + off[ICNN_BE_NAF_W_D2V]; a.d1v = w + off[ICNN_BE_NAF_W_D1V];
-    a.sq = reinterpret_cast<double *>(w + off[ICNN_BE_NAF_W_SQ]);
+    a.y = w.at(ICNN_BE_NAF_W_Y); a.u = w.at(ICNN_BE_NAF_W_U); a.l = w.at(ICNN_BE_NAF_W_L);
+    a.ld = w.at(ICNN_BE_NAF_W_LD); a.h = w.at(ICNN_BE_NAF_W_H); a.adv = w.at(ICNN_BE_NAF_W_ADV);
+    a.q = w.at(ICNN_BE_NAF_W_Q); a.td = w.at(ICNN_BE_NAF_W_TD);
+    a.h1l = w.at(ICNN_BE_NAF_W_H1L); a.h2l = w.at(ICNN_BE_NAF_W_H2L); a.h1u = w.at(ICNN_BE_NAF_W_H1U);
+    a.h2u = w.at(ICNN_BE_NAF_W_H2U); a.h1v = w.at(ICNN_BE_NAF_W_H1V); a.h2v = w.at(ICNN_BE_NAF_W_H2V);
+    a.d3l = w.at(ICNN_BE_NAF_W_D3L); a.d2l = w.at(ICNN_BE_NAF_W_D2L); a.d1l = w.at(ICNN_BE_NAF_W_D1L);
+    a.d3u = w.at(ICNN_BE_NAF_W_D3U); a.d2u = w.at(ICNN_BE_NAF_W_D2U); a.d1u = w.at(ICNN_BE_NAF_W_D1U);
+    a.d3v = w.at(ICNN_BE_NAF_W_D3V); a.d2v = w.at(ICNN_BE_NAF_W_D2V); a.d1v = w.at(ICNN_BE_NAF_W_D1V);
+    a.sq = reinterpret_cast<double *>(w.at(ICNN_BE_NAF_W_SQ));
     a.PA = p.PA; a.PB = p.PB; a.PC = p.PC; a.PS = p.PS;
     return launch_kernel(naf_chain_kernel, dim3((d.batch + TS - 1) / TS), dim3(DT), p.bytes(), stream, a);
 }
@@ -285,33 +283,29 @@ hipError_t launch_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l
 }
 
 hipError_t launch_naf_grads(const icnn_be_naf_args &d, hipStream_t stream) {
-    long long off[ICNN_BE_NAF_WORK_PIECES];
-    work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off);
-    float *w = static_cast<float *>(d.work);
+    const Work w(d);
     const int dimO = d.dimO, dimA = d.dimA, l1 = d.l1, l2 = d.l2;
     GradArgs a{};
     a.B = d.batch;
     // the nine layers in the order of the three flat gradients
     float *g = d.grad_l;
-    a.layer(d.obs, dimO, w + off[ICNN_BE_NAF_W_D1L], l1, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H1L], l1, w + off[ICNN_BE_NAF_W_D2L], l2, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H2L], l2, w + off[ICNN_BE_NAF_W_D3L], dimA * dimA, g);
+    a.layer(d.obs, dimO, w.at(ICNN_BE_NAF_W_D1L), l1, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H1L), l1, w.at(ICNN_BE_NAF_W_D2L), l2, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H2L), l2, w.at(ICNN_BE_NAF_W_D3L), dimA * dimA, g);
     g = d.grad_u;
-    a.layer(d.obs, dimO, w + off[ICNN_BE_NAF_W_D1U], l1, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H1U], l1, w + off[ICNN_BE_NAF_W_D2U], l2, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H2U], l2, w + off[ICNN_BE_NAF_W_D3U], dimA, g);
+    a.layer(d.obs, dimO, w.at(ICNN_BE_NAF_W_D1U), l1, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H1U), l1, w.at(ICNN_BE_NAF_W_D2U), l2, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H2U), l2, w.at(ICNN_BE_NAF_W_D3U), dimA, g);
     g = d.grad_v;
-    a.layer(d.obs, dimO, w + off[ICNN_BE_NAF_W_D1V], l1, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H1V], l1, w + off[ICNN_BE_NAF_W_D2V], l2, g);
-    a.layer(w + off[ICNN_BE_NAF_W_H2V], l2, w + off[ICNN_BE_NAF_W_D3V], 1, g);
+    a.layer(d.obs, dimO, w.at(ICNN_BE_NAF_W_D1V), l1, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H1V), l1, w.at(ICNN_BE_NAF_W_D2V), l2, g);
+    a.layer(w.at(ICNN_BE_NAF_W_H2V), l2, w.at(ICNN_BE_NAF_W_D3V), 1, g);
     return launch_grad_table(a, stream);
 }
 
 hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStream_t stream) {
-    long long off[ICNN_BE_NAF_WORK_PIECES];
-    work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off);
-    float *w = static_cast<float *>(d.work);
-    UpdArgs u{};
+    const Work w(d);
+    ParamSetsArgs u{};
     const long long nl = naf_net_floats(d.dimO, d.l1, d.l2, d.dimA * d.dimA), nu = naf_net_floats(d.dimO, d.l1, d.l2, d.dimA),
                     nv = naf_net_floats(d.dimO, d.l1, d.l2, 1);
     // one optimizer: the three sets read the one step count; only V has a target; all three enter loss_q's decay sum
@@ -326,11 +320,11 @@ hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStrea
     u.eps = d.eps;
     u.tau = d.tau;
     u.loss = with_loss ? d.loss : nullptr;
-    u.sq = reinterpret_cast<const double *>(w + off[ICNN_BE_NAF_W_SQ]);
+    u.sq = reinterpret_cast<const double *>(w.at(ICNN_BE_NAF_W_SQ));
     u.tiles = (d.batch + TS - 1) / TS;
     u.batch = d.batch;
     u.l2norm = (double)d.l2norm;
-    u.partial = reinterpret_cast<double *>(w + off[ICNN_BE_NAF_W_UPD]);
+    u.partial = reinterpret_cast<double *>(w.at(ICNN_BE_NAF_W_UPD));
     return launch_param_sets_update(u, stream);
 }
 

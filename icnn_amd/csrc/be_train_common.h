@@ -1,7 +1,8 @@
 // Host runtime of the training units (be_train_common.hip, be_train_fc.hip, be_train_ficnn.hip, be_train_conv.hip): grid
 // size, workspace walk and the launch latch.  A gradient entry runs its whole step twice over the same code: a dry run (no
-// workspace) that only sizes the workspace, and the real run that carves it and launches.  And the one device accessor of
-// the packed forward operands that the units unpack their weights with.
+// workspace) that only sizes the workspace, and the real run that carves it and launches.  The flat-vector trainers
+// (be_ddpg.hip, be_naf.hip, be_ff.hip, be_fcn.hip) lay their workspace out in named pieces instead: WorkPieces.  And the one
+// device accessor of the packed forward operands that the units unpack their weights with.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,25 @@ struct Carver {
         float *p = base ? base + at : nullptr;
         at += (floats + 63) & ~size_t(63);       // 256-byte alignment of every piece
         return p;
+    }
+};
+
+// A workspace that the host can query piece by piece (the ICNN_BE_*_W_* tables of include/icnn_be.h): a unit's own walk gives
+// walk() the floats of every piece, and its launchers reach a piece through at()
+template <int PIECES>
+struct WorkPieces {
+    long long off[PIECES];
+    float *w;
+    explicit WorkPieces(void *work) : w(static_cast<float *>(work)) {}
+    float *at(int piece) const { return w + off[piece]; }
+    // off[i] (off not NULL): the float offset of piece i; returns the floats of the whole workspace
+    static size_t walk(const size_t (&floats)[PIECES], long long *off) {
+        Carver c{nullptr};
+        for (int i = 0; i < PIECES; ++i) {
+            if (off) off[i] = (long long)c.at;
+            c.take(floats[i]);
+        }
+        return c.at;
     }
 };
 

@@ -3,14 +3,9 @@
 // (include/icnn_be.h, icnn_be_param_update).
 //
 // One thread per four consecutive parameters: 16-byte loads and stores on the theta / m / v / grad streams, four CSR
-// offsets of the map with one more 16-byte load, then the scattered stores of the copies.  The arithmetic of one element,
-// float32, correctly rounded at every operation, no contraction (the NumPy restatement of tests/test_device_update.py
-// reproduces it bit for bit; sqrt as the float of the double root, which is the correctly rounded float root):
-//   m = b1 * m + c1 * g                 b1 = (float)beta1, c1 = (float)(1 - beta1)
-//   v = b2 * v + c2 * (g * g)           b2 = (float)beta2, c2 = (float)(1 - beta2)
-//   theta = theta - (lr_t * m) / (sqrt(v) + eps)
+// offsets of the map with one more 16-byte load, then the scattered stores of the copies.  The arithmetic of one element is
+// tf_adam_element with tf_adam_lr_t's step size (be_tf_adam.h), and behind it
 //   theta = 0 if theta < 0 and the element is a proj weight (np.maximum(theta, 0): -0 and NaN stay)
-// lr_t = (float)(lr * sqrt(1 - beta2^t) / (1 - beta1^t)) in double from the step count t, as train.TFAdam computes it.
 //
 // The gated form (icnn_be_param_update_gated) is the same kernel body behind one word of device memory: a
 // workgroup that reads *go == 0 leaves before it loads, stores or takes a ticket, so theta, m, v, the arena and both step
@@ -23,13 +18,14 @@
 //   g = g + k * theta on the decayed elements                k = l2norm * wd in float32 (TF's AddN of the two gradients)
 // and every new target value is scattered into the target's arena beside the critic's.
 #include "be_kernels.h"
+#include "be_tf_adam.h"
 
 namespace icnn_be {
 
 namespace {
 
-constexpr int UPD_THREADS = 256;
-constexpr int UPD_PER_THREAD = 4;
+constexpr int UPD_THREADS = ADAM_THREADS;
+constexpr int UPD_PER_THREAD = ADAM_PER_THREAD;
 
 struct UpdArgs {
     icnn_be_rl_update_args r;   // r.adam: every form; the rest and k: the critic's alone
@@ -62,7 +58,7 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
         // ticket, and every workgroup reads the count before it takes one
         const int t = __hip_atomic_load(a.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
         s_t = t;
-        s_lr_t = (float)(a.lr * sqrt(1.0 - pow(a.beta2, (double)t)) / (1.0 - pow(a.beta1, (double)t)));
+        s_lr_t = tf_adam_lr_t(a.lr, a.beta1, a.beta2, t);
     }
     __syncthreads();
     const float lr_t = s_lr_t, eps = a.eps, tau = u.r.tau;
@@ -74,19 +70,12 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
         bool dk[UPD_PER_THREAD] = {};
         int off[UPD_PER_THREAD + 1] = {};
         if (cnt == UPD_PER_THREAD) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(a.theta + j0);
-            if (CRITIC) {
-                const float4 r4 = *reinterpret_cast<const float4 *>(u.r.target_theta + j0);
-                tt[0] = r4.x; tt[1] = r4.y; tt[2] = r4.z; tt[3] = r4.w;
-            }
-            const float4 m4 = *reinterpret_cast<const float4 *>(a.m + j0);
-            const float4 v4 = *reinterpret_cast<const float4 *>(a.v + j0);
-            const float4 g4 = *reinterpret_cast<const float4 *>(a.grad + j0);
+            load_quad(th, a.theta + j0);
+            if (CRITIC) load_quad(tt, u.r.target_theta + j0);
+            load_quad(m, a.m + j0);
+            load_quad(v, a.v + j0);
+            load_quad(g, a.grad + j0);
             const int4 o4 = *reinterpret_cast<const int4 *>(a.dest_off + j0);
-            th[0] = t4.x; th[1] = t4.y; th[2] = t4.z; th[3] = t4.w;
-            m[0] = m4.x; m[1] = m4.y; m[2] = m4.z; m[3] = m4.w;
-            v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
-            g[0] = g4.x; g[1] = g4.y; g[2] = g4.z; g[3] = g4.w;
             off[0] = o4.x; off[1] = o4.y; off[2] = o4.z; off[3] = o4.w;
             if (CRITIC) {
                 const uchar4 d4 = *reinterpret_cast<const uchar4 *>(u.r.decay + j0);
@@ -104,23 +93,17 @@ __global__ __launch_bounds__(UPD_THREADS) void param_update_kernel(UpdArgs u) {
         off[cnt] = a.dest_off[j0 + cnt];
 #pragma unroll
         for (int k = 0; k < UPD_PER_THREAD; ++k) {
-            // plain operators under the pragma above: the __f*_rn helpers are header functions outside its scope, and
-            // the compiler fused their products into the sums.  sqrt: the float of the double root (correctly rounded
-            // both times, and 53 >= 2 * 24 + 2 bits make the double rounding innocuous); v_sqrt_f32 alone is 1 ulp
             const float old = th[k];
             if (CRITIC) tt[k] = tt[k] - tau * (tt[k] - old);                  // update_target, from the pre-update theta
             const float gk = CRITIC && dk[k] ? g[k] + u.k * old : g[k];      // + d (l2norm wd |W|^2 / 2) / dW  (TF's AddN)
-            m[k] = u.b1 * m[k] + u.c1 * gk;
-            v[k] = u.b2 * v[k] + u.c2 * (gk * gk);
-            const float root = (float)__builtin_sqrt((double)v[k]);
-            th[k] = th[k] - (lr_t * m[k]) / (root + eps);
+            th[k] = tf_adam_element(old, m[k], v[k], gk, u.b1, u.c1, u.b2, u.c2, lr_t, eps);
             if (th[k] < 0.f && in_proj(a, j0 + k)) th[k] = 0.f;
         }
         if (cnt == UPD_PER_THREAD) {
-            *reinterpret_cast<float4 *>(a.theta + j0) = make_float4(th[0], th[1], th[2], th[3]);
-            if (CRITIC) *reinterpret_cast<float4 *>(u.r.target_theta + j0) = make_float4(tt[0], tt[1], tt[2], tt[3]);
-            *reinterpret_cast<float4 *>(a.m + j0) = make_float4(m[0], m[1], m[2], m[3]);
-            *reinterpret_cast<float4 *>(a.v + j0) = make_float4(v[0], v[1], v[2], v[3]);
+            store_quad(a.theta + j0, th);
+            if (CRITIC) store_quad(u.r.target_theta + j0, tt);
+            store_quad(a.m + j0, m);
+            store_quad(a.v + j0, v);
         } else {
             for (int k = 0; k < cnt; ++k) {
                 a.theta[j0 + k] = th[k];

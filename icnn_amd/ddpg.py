@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import flat as _flat
 
 NETS = ("q", "p", "target_q", "target_p")
 
@@ -40,27 +41,16 @@ def layout(spec, which):
 
 
 def n_floats(spec, which) -> int:
-    return sum(int(np.prod(shape)) for _, shape in layout(spec, which))
+    return _flat.n_floats(layout(spec, which))
 
 
 def flatten(spec, which, params) -> np.ndarray:
     """the flat float32 vector of a dict of named arrays"""
-    parts = []
-    for name, shape in layout(spec, which):
-        a = np.asarray(params[name], np.float32)
-        if a.shape != shape:
-            raise ValueError("%s/%s: shape %s, expected %s" % (which, name, a.shape, shape))
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
+    return _flat.flatten(layout(spec, which), params, which + "/")
 
 
 def unflatten(spec, which, flat) -> Dict[str, np.ndarray]:
-    out, at = {}, 0
-    for name, shape in layout(spec, which):
-        n = int(np.prod(shape))
-        out[name] = np.asarray(flat[at:at + n]).reshape(shape).copy()
-        at += n
-    return out
+    return _flat.unflatten(layout(spec, which), flat)
 
 
 def init_params(dimO, dimA, l1, l2, seed, final_p=3e-3, final_q=3e-4):
@@ -82,11 +72,13 @@ def init_params(dimO, dimA, l1, l2, seed, final_p=3e-3, final_q=3e-4):
     return out
 
 
-class DDPGTrainer:
+class DDPGTrainer(_flat.ReplayTrainer):
     """Both nets, both targets, Adam's state and the whole training step at one minibatch size.  obs / act (float64) / rew /
     ob2 / term are named and typed as rl_train.CriticTrainer's, so rl_agent.ReplayMemory.sample_into fills them.  The nets
     start from init_params(seed) with the targets as copies.  grad_q / grad_p hold the last step's gradients (before the decay
-    term), work_view(name) the pieces of the chain's workspace (_lib.DDPG_WORK)."""
+    term), work_view(name) the pieces of the chain's workspace (_lib.DDPG_WORK).  chain() is icnn_be_ddpg_chain, grads() leaves
+    grad_q and grad_p, update() moves both nets and both targets."""
+    _entry = "icnn_be_ddpg_"
 
     def __init__(self, dimO, dimA, l1=200, l2=200, batch=256, rate=1e-3, prate=1e-4, tau=0.01, discount=0.99, l2norm=1e-4,
                  pl2norm=0.0, seed=0, device="cuda", eps=1e-4, beta1=0.9, beta2=0.999):
@@ -105,11 +97,7 @@ class DDPGTrainer:
         self.l2norm, self.pl2norm = float(l2norm), float(pl2norm)
         self.device = dev = torch.device(device)
         B, f32 = self.batch, torch.float32
-        self.obs = torch.zeros(B, self.spec.dimO, dtype=f32, device=dev)
-        self.ob2 = torch.zeros_like(self.obs)
-        self.act = torch.zeros(B, self.spec.dimA, dtype=torch.float64, device=dev)
-        self.rew = torch.zeros(B, dtype=f32, device=dev)
-        self.term = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self._minibatch_buffers()
         self.theta = {w: torch.zeros(self.n[w[-1]], dtype=f32, device=dev) for w in NETS}
         self.m = {w: torch.zeros(self.n[w], dtype=f32, device=dev) for w in "pq"}
         self.v = {w: torch.zeros(self.n[w], dtype=f32, device=dev) for w in "pq"}
@@ -121,9 +109,7 @@ class DDPGTrainer:
         if work_bytes == 0:
             raise ValueError("sizes beyond what the DDPG kernels support: %r" % (self.spec,))
         self.work = torch.zeros(work_bytes // 4, dtype=f32, device=dev)
-        off = (C.c_longlong * len(_lib.DDPG_WORK))()
-        _lib.check(self.lib.icnn_be_ddpg_work_offsets(B, *self._dims(), C.byref(off)), "icnn_be_ddpg_work_offsets")
-        self.work_offsets = dict(zip(_lib.DDPG_WORK, (int(x) for x in off)))
+        self.work_offsets = self._work_offsets("icnn_be_ddpg_work_offsets", _lib.DDPG_WORK, B, *self._dims())
         a = _lib.DdpgArgs()
         a.batch, a.dimO, a.dimA, a.l1, a.l2 = (B,) + self._dims()
         a.obs, a.act, a.rew, a.ob2, a.term = (t.data_ptr() for t in (self.obs, self.act, self.rew, self.ob2, self.term))
@@ -137,44 +123,6 @@ class DDPGTrainer:
         self._args = a
         params = init_params(*self._dims(), seed=seed)
         self.load(p=params["p"], q=params["q"])
-
-    def _dims(self):
-        s = self.spec
-        return (s.dimO, s.dimA, s.l1, s.l2)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _call(self, name):
-        _lib.check(getattr(self.lib, name)(C.byref(self._args), self._stream()), name)
-
-    # ---- the step and its parts ----
-    def chain(self):
-        """icnn_be_ddpg_chain alone on the trainer's buffers"""
-        self._call("icnn_be_ddpg_chain")
-
-    def grads(self):
-        """icnn_be_ddpg_grads alone: grad_q and grad_p from the workspace the chain left"""
-        self._call("icnn_be_ddpg_grads")
-
-    def update(self):
-        """icnn_be_ddpg_update alone: both nets and targets from grad_q / grad_p, and loss_q"""
-        self._call("icnn_be_ddpg_update")
-
-    def step_buffers(self) -> torch.Tensor:
-        """One step on what the trainer's obs / act / rew / ob2 / term hold.  Returns loss_q at the pre-update weights: the
-        trainer's 0-d float32 device tensor, which the next step overwrites.  No host synchronisation."""
-        self._call("icnn_be_ddpg_step")
-        return self.loss
-
-    def step(self, obs, act, rew, ob2, term) -> torch.Tensor:
-        """step_buffers() on the minibatch (obs [B, dimO], act [B, dimA], rew [B], ob2 [B, dimO], term [B] bool)"""
-        self.obs.copy_(torch.as_tensor(obs).reshape(self.obs.shape))
-        self.act.copy_(torch.as_tensor(act).reshape(self.act.shape))
-        self.rew.copy_(torch.as_tensor(rew).reshape(self.rew.shape))
-        self.ob2.copy_(torch.as_tensor(ob2).reshape(self.ob2.shape))
-        self.term.copy_(torch.as_tensor(term).reshape(self.term.shape))
-        return self.step_buffers()
 
     def work_view(self, name) -> torch.Tensor:
         """a live view of one piece of the workspace: [B, width] float32; "sq" float64 [tiles]"""
@@ -190,12 +138,7 @@ class DDPGTrainer:
     # ---- forward passes ----
     def policy(self, obs, out=None, which="p") -> torch.Tensor:
         """pi(obs) for obs [B', dimO] float32 on the device: float32 [B', dimA] (icnn_be_ddpg_act; no host synchronisation)"""
-        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[1] == self.spec.dimO and obs.is_cuda
-        if out is None:
-            out = torch.empty(obs.shape[0], self.spec.dimA, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.icnn_be_ddpg_act(*self._dims(), self.theta[which].data_ptr(), obs.data_ptr(), obs.shape[0],
-                                             out.data_ptr(), self._stream()), "icnn_be_ddpg_act")
-        return out
+        return self._act(which, obs, out)
 
     def q(self, obs, act, which="q") -> torch.Tensor:
         """Q(obs, act) for obs [B', dimO] float32 and act [B', dimA] float64 on the device: float32 [B']"""
@@ -223,14 +166,7 @@ class DDPGTrainer:
         given = {"p": p, "q": q, "target_p": target_p if target_p is not None else p,
                  "target_q": target_q if target_q is not None else q}
         for which, params in given.items():
-            if params is None:
-                continue
-            flat = flatten(self.spec, which[-1], params) if isinstance(params, dict) else np.asarray(params, np.float32)
-            if flat.shape != (self.n[which[-1]],):
-                raise ValueError("%s: %s values, expected %d" % (which, flat.shape, self.n[which[-1]]))
-            self.theta[which].copy_(torch.from_numpy(np.ascontiguousarray(flat)))
+            if params is not None:
+                _flat.copy_into(self.theta[which], layout(self.spec, which[-1]), params, which, which[-1] + "/")
         if reset:
-            for w in "pq":
-                self.m[w].zero_()
-                self.v[w].zero_()
-            self.step_count.zero_()
+            self._reset_adam()

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import flat as _flat
 from .train import _Trainer
 
 LAYERS = ("conv1", "conv2", "conv3", "up1", "up2", "up3", "up4")
@@ -54,26 +55,15 @@ def layout(spec):
 
 
 def n_floats(spec) -> int:
-    return sum(int(np.prod(shape)) for _, shape in layout(spec))
+    return _flat.n_floats(layout(spec))
 
 
 def flatten(spec, params) -> np.ndarray:
-    parts = []
-    for name, shape in layout(spec):
-        a = np.asarray(params[name], np.float32)
-        if a.shape != shape:
-            raise ValueError("%s: shape %s, expected %s" % (name, a.shape, shape))
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
+    return _flat.flatten(layout(spec), params)
 
 
 def unflatten(spec, flat) -> Dict[str, np.ndarray]:
-    out, at = {}, 0
-    for name, shape in layout(spec):
-        n = int(np.prod(shape))
-        out[name] = np.asarray(flat[at:at + n]).reshape(shape).copy()
-        at += n
-    return out
+    return _flat.unflatten(layout(spec), flat)
 
 
 def fan_in(name, shape) -> int:
@@ -117,12 +107,7 @@ class FCNModel:
         """copy a dict of torch-named arrays (or a flat vector) into the existing theta"""
         if isinstance(params, dict):
             params = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in params.items()}
-            flat = flatten(self.spec, params)
-        else:
-            flat = np.asarray(params, np.float32)
-        if flat.shape != (self.n,):
-            raise ValueError("theta: %s values, expected %d" % (flat.shape, self.n))
-        self.theta.copy_(torch.from_numpy(np.ascontiguousarray(flat)))
+        _flat.copy_into(self.theta, layout(self.spec), params, "theta")
 
     load_state_dict = load
 
@@ -159,7 +144,7 @@ class FCNModel:
         return out
 
 
-class FCNTrainer(_Trainer):
+class FCNTrainer(_flat.FlatTrainer, _Trainer):
     """model, Adam's state and the whole training step at one batch size.  step() returns the loss at the weights the step
     began with: the trainer's 0-d float32 device tensor `loss`; yhat [B, H * W] is that of the same forward.  eval_batch = E
     also allocates the script's test phase (baseline.py:102-108): evaluate(x, t) runs forward and loss on exactly E images
@@ -205,9 +190,7 @@ class FCNTrainer(_Trainer):
             self._eval_args = self._describe(E, self.eval_work, self.x_eval, self.t_eval, self.y_eval, self.eval_loss)
 
     def _offsets(self, batch):
-        off = (C.c_longlong * len(_lib.FCN_WORK))()
-        _lib.check(self.lib.icnn_be_fcn_work_offsets(batch, *_dims(self.spec), C.byref(off)), "icnn_be_fcn_work_offsets")
-        return dict(zip(_lib.FCN_WORK, (int(x) for x in off)))
+        return self._work_offsets("icnn_be_fcn_work_offsets", _lib.FCN_WORK, batch, *_dims(self.spec))
 
     def _describe(self, batch, work, x, t, yhat, loss):
         a = self.model.args(batch, work)
@@ -215,12 +198,6 @@ class FCNTrainer(_Trainer):
         a.m, a.v, a.grad, a.step = self.m["fcn"].data_ptr(), self.v["fcn"].data_ptr(), self.grad.data_ptr(), self.step_count.data_ptr()
         a.lr, a.pixel_scale = self.lr, self.pixel_scale
         return a
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _call(self, name, args=None):
-        _lib.check(getattr(self.lib, name)(C.byref(self._args if args is None else args), self._stream()), name)
 
     # ---- the step and its parts ----
     def forward(self):
@@ -282,12 +259,7 @@ class FCNTrainer(_Trainer):
 
     def params(self) -> Dict[str, torch.Tensor]:
         """live views of the variables inside theta"""
-        out, at = {}, 0
-        for name, shape in layout(self.spec):
-            n = int(np.prod(shape))
-            out[name] = self.model.theta[at:at + n].view(shape)
-            at += n
-        return out
+        return _flat.views(layout(self.spec), self.model.theta)
 
     def host_params(self) -> Dict[str, np.ndarray]:
         return self.model.host_params()
@@ -297,6 +269,4 @@ class FCNTrainer(_Trainer):
         count back to zero.  Synchronises."""
         self.model.load(params)
         if reset:
-            self.m["fcn"].zero_()
-            self.v["fcn"].zero_()
-            self.step_count.zero_()
+            self._reset_adam()

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import flat as _flat
 from .train import _Trainer, _TrainF1
 
 BN_EPS = 1e-5
@@ -49,26 +50,15 @@ def layout(spec):
 
 
 def n_floats(spec) -> int:
-    return sum(int(np.prod(shape)) for _, shape in layout(spec))
+    return _flat.n_floats(layout(spec))
 
 
 def flatten(spec, params) -> np.ndarray:
-    parts = []
-    for name, shape in layout(spec):
-        a = np.asarray(params[name], np.float32)
-        if a.shape != shape:
-            raise ValueError("%s: shape %s, expected %s" % (name, a.shape, shape))
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
+    return _flat.flatten(layout(spec), params)
 
 
 def unflatten(spec, flat) -> Dict[str, np.ndarray]:
-    out, at = {}, 0
-    for name, shape in layout(spec):
-        n = int(np.prod(shape))
-        out[name] = np.asarray(flat[at:at + n]).reshape(shape).copy()
-        at += n
-    return out
+    return _flat.unflatten(layout(spec), flat)
 
 
 def init_params(spec, seed) -> Dict[str, np.ndarray]:
@@ -121,10 +111,7 @@ class FFModel:
 
     def load(self, params):
         """copy a dict of named arrays (or a flat vector) into the existing theta"""
-        flat = flatten(self.spec, params) if isinstance(params, dict) else np.asarray(params, np.float32)
-        if flat.shape != (self.n,):
-            raise ValueError("theta: %s values, expected %d" % (flat.shape, self.n))
-        self.theta.copy_(torch.from_numpy(np.ascontiguousarray(flat)))
+        _flat.copy_into(self.theta, layout(self.spec), params, "theta")
 
     def host_params(self) -> Dict[str, np.ndarray]:
         return unflatten(self.spec, self.theta.cpu().numpy())
@@ -164,7 +151,7 @@ class FFModel:
         return out
 
 
-class FFTrainer(_Trainer, _TrainF1):
+class FFTrainer(_flat.FlatTrainer, _Trainer, _TrainF1):
     """model, Adam's state and the whole training step at one batch size.  step() returns the loss at the weights the step
     began with: the trainer's 0-d float32 device tensor `loss`; yhat [B, n_labels] and f1_tallies [B, 3] (tp, fp, fn per
     example; macro_f1() reads them) are those of the same forward.  eval_batch = E also allocates the script's test phase
@@ -212,9 +199,7 @@ class FFTrainer(_Trainer, _TrainF1):
                                              self.eval_f1_tallies)
 
     def _offsets(self, batch):
-        off = (C.c_longlong * len(_lib.FF_WORK))()
-        _lib.check(self.lib.icnn_be_ff_work_offsets(batch, *_dims(self.spec), C.byref(off)), "icnn_be_ff_work_offsets")
-        return dict(zip(_lib.FF_WORK, (int(x) for x in off)))
+        return self._work_offsets("icnn_be_ff_work_offsets", _lib.FF_WORK, batch, *_dims(self.spec))
 
     def _describe(self, batch, work, x, true_y, yhat, loss, tallies):
         a = self.model.args(batch, work)
@@ -222,12 +207,6 @@ class FFTrainer(_Trainer, _TrainF1):
         a.m, a.v, a.grad, a.step = self.m["ff"].data_ptr(), self.v["ff"].data_ptr(), self.grad.data_ptr(), self.step_count.data_ptr()
         a.lr = self.lr
         return a
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _call(self, name, args=None):
-        _lib.check(getattr(self.lib, name)(C.byref(self._args if args is None else args), self._stream()), name)
 
     # ---- the step and its parts ----
     def forward(self, bn="batch"):
@@ -288,12 +267,7 @@ class FFTrainer(_Trainer, _TrainF1):
 
     def params(self) -> Dict[str, torch.Tensor]:
         """live views of the variables inside theta"""
-        out, at = {}, 0
-        for name, shape in layout(self.spec):
-            n = int(np.prod(shape))
-            out[name] = self.model.theta[at:at + n].view(shape)
-            at += n
-        return out
+        return _flat.views(layout(self.spec), self.model.theta)
 
     def host_params(self) -> Dict[str, np.ndarray]:
         return self.model.host_params()
@@ -303,6 +277,4 @@ class FFTrainer(_Trainer, _TrainF1):
         back to zero.  The moving statistics stay.  Synchronises."""
         self.model.load(params)
         if reset:
-            self.m["ff"].zero_()
-            self.v["ff"].zero_()
-            self.step_count.zero_()
+            self._reset_adam()
