@@ -40,6 +40,8 @@ LOSS = {"xent": 0, "mse": 1}
 PATHS = ["ROWS", "TILE", "TILE_BUDGETED_THEN_ROWS", "ROUNDS_LOCKSTEP", "ROUNDS_SLICED_THEN_ROWS", "ROUNDS_SLICED_EXTRA"]
 # ICNN_BE_ADAM_*: which kernel icnn_be_adam_fc launches (icnn_be_debug_adam_plan)
 ADAM_KERNELS = ["NONE", "ROWS", "TILE"]
+# ICNN_BE_DUAL_PLAN_*: which kernel icnn_be_dual_step launches (icnn_be_debug_dual_plan)
+DUAL_KERNELS = ["small", "body", "wide"]
 ERRORS = {-1: "ICNN_BE_EINVAL (bad argument)", -2: "ICNN_BE_ELIMIT (size beyond a compiled-in limit)",
           -3: "ICNN_BE_ELAUNCH (HIP launch failed)"}
 
@@ -52,7 +54,7 @@ EXPORTS = [
     "icnn_be_fc_context_work_floats", "icnn_be_fc_context", "icnn_be_fc_context_stage", "icnn_be_fc_context_norm", "icnn_be_fc_clamp",
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
-    "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan",
+    "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan", "icnn_be_debug_dual_plan",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
@@ -353,6 +355,8 @@ def load():
     lib.icnn_be_debug_profile_phases.restype = C.c_int
     lib.icnn_be_debug_adam_plan.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx), C.c_int, C.POINTER(C.c_int * 4)]
     lib.icnn_be_debug_adam_plan.restype = C.c_int
+    lib.icnn_be_debug_dual_plan.argtypes = [C.POINTER(State), C.c_int, C.POINTER(C.c_int * 8)]
+    lib.icnn_be_debug_dual_plan.restype = C.c_int
     lib.icnn_be_adam_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_adam_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
@@ -602,3 +606,15 @@ def adam_plan(model, batch, ctx=None):
     if rc < 0:
         check(rc, "icnn_be_debug_adam_plan")
     return (ADAM_KERNELS[rc], out[0], out[1], bool(out[2]), bool(out[3]))
+
+
+def dual_plan(state, t):
+    """(cut type 'float' | 'double', KT or KS, waves per workgroup, variant name, bundle staged in scratch, 'small' | 'body' |
+    'wide', LDS bytes, staged rows) of the launch icnn_be_dual_step(state, t, ...) makes (icnn_be_debug_dual_plan).  Host
+    arithmetic on the State's shape fields, flags and on whether `scratch` is set: no GPU, no buffers needed."""
+    out = (C.c_int * 8)()
+    rc = load().icnn_be_debug_dual_plan(C.byref(state), int(t), C.byref(out))
+    if rc < 0:
+        check(rc, "icnn_be_debug_dual_plan")
+    variant = [name for name, code in VARIANT.items() if code == out[3]][0]
+    return ("double" if out[0] == CUT_F64 else "float", out[1], out[2], variant, bool(out[4]), DUAL_KERNELS[out[5]], out[6], out[7])

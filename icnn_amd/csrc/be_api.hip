@@ -308,6 +308,17 @@ int icnn_be_dual_step(const icnn_be_state *st, int t, const void *f, const void 
     return done(icnn_be::launch_dual_step(*st, t, 0, f, g, static_cast<hipStream_t>(stream)));
 }
 
+int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[8]) {
+    if (!out) return ICNN_BE_EINVAL;
+    if (int rc = check_shape(st)) return rc;
+    if (t < 0 || t >= (st->iters > 0 ? st->iters : st->slots) || st->batch == 0) return ICNN_BE_EINVAL;
+    icnn_be::DualStepPlan p;
+    if (!icnn_be::plan_dual_step(*st, t, p)) return ICNN_BE_EINVAL;
+    out[0] = p.cut; out[1] = p.kt; out[2] = p.waves; out[3] = p.variant;
+    out[4] = p.staged; out[5] = p.kernel; out[6] = p.lds; out[7] = p.rows;
+    return 0;
+}
+
 size_t icnn_be_fc_pack_floats(const icnn_be_fc_model *shape) {
     if (!shape || icnn_be::fc_check_model(*shape) != 0) return 0;
     return icnn_be::fc_pack_floats(*shape);

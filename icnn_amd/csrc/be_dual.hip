@@ -272,17 +272,28 @@ hipError_t launch_y_reset(const icnn_be_state &st, const SolveReset &rs, hipStre
 
 namespace {
 typedef void (*DualKernel)(DualArgs);
-struct DualStepLaunch {
+struct DualStepLaunch : DualStepPlan {     // (waves: per sample = per workgroup; lds: dynamic bytes; rows: staged rows)
     DualKernel kern;
-    int waves, lds, rows;
 };
+
+// One instance of dual_step_kernel: the launch's fields come from the instance's own template arguments
+template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false>
+void pick(DualStepLaunch &c) {
+    c.kern = dual_step_kernel<CutT, KT, NW, RL, IPM, GLB>;
+    c.cut = sizeof(CutT) == 8 ? ICNN_BE_CUT_F64 : ICNN_BE_CUT_F32;
+    c.kt = KT;
+    c.waves = NW;
+    c.variant = RL ? ICNN_BE_VARIANT_RL : IPM ? ICNN_BE_VARIANT_PDIPM : ICNN_BE_VARIANT_DUAL;
+    c.staged = GLB;
+    c.kernel = ICNN_BE_DUAL_PLAN_BODY;
+}
 
 // the bundle in LDS: CutT, KT, NW fixed by the caller, the variant picks the body
 template <typename CutT, int KT, int NW>
-DualKernel dual_kernel_for(int variant) {
-    if (variant == ICNN_BE_VARIANT_RL) return dual_step_kernel<CutT, KT, 1, true>;     // dual_waves() never widens variant RL
-    if (variant == ICNN_BE_VARIANT_PDIPM) return dual_step_kernel<CutT, KT, NW, false, true>;
-    return dual_step_kernel<CutT, KT, NW, false>;
+void pick_for(DualStepLaunch &c, int variant) {
+    if (variant == ICNN_BE_VARIANT_RL) pick<CutT, KT, 1, true>(c);     // dual_waves() never widens variant RL
+    else if (variant == ICNN_BE_VARIANT_PDIPM) pick<CutT, KT, NW, false, true>(c);
+    else pick<CutT, KT, NW, false>(c);
 }
 
 // Which dual_step_kernel instance the launch `a` runs, on how many waves, with how much LDS and how many staged rows.
@@ -293,35 +304,36 @@ bool choose_dual_step(const DualArgs &a, DualStepLaunch &c) {
     const bool global = st.flags & ICNN_BE_FLAG_GLOBAL_BUNDLE;
     const int fit = dual_rows_fit(st.n, st.slots, st.cut_dtype, st.variant);
     c.rows = a.rows;
-    c.waves = dual_waves(st.n, st.cut_dtype, st.variant);
+    int waves = dual_waves(st.n, st.cut_dtype, st.variant);
     if ((c.rows > fit || global) && st.scratch && scratch_bytes(st) > 0) {
         // wide rows: the LDS holds fewer cuts than there are iterations.  From the round on in which a bundle could outgrow
         // it, the bundle is staged in st.scratch instead (same kernel, the sweeps at L2 latency); without a scratch area the
         // capacity stays and a sample that exceeds it stops with ICNN_BE_ST_OVERFLOW
-        auto staged_lds = [&](int rows, int waves) {
-            return carve(32, rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, waves, true, ipm, true).total;
+        auto staged_lds = [&](int rows, int nw) {
+            return carve(32, rows, a.ldA, a.n_pad, f64 ? 8 : 4, a.plan.n_leaves, false, nw, true, ipm, true).total;
         };
-        c.lds = staged_lds(c.rows, c.waves);
-        if (c.lds > LDS_BYTES && c.waves > 1) {
+        c.lds = staged_lds(c.rows, waves);
+        if (c.lds > LDS_BYTES && waves > 1) {
             // the per-wave systems of an eight-wave sample do not fit next to the column buffers (interior point: five of
             // them; n_pad = 3072 from 23 rows on): the one-wave instance of the same body, whose carve-up has none
-            c.waves = 1;
+            waves = 1;
             c.lds = staged_lds(c.rows, 1);
         }
         if (c.lds > LDS_BYTES) return false;
         if (f64) {
-            c.kern = ipm ? dual_step_kernel<double, 32, 1, false, true, true> : dual_step_kernel<double, 32, 1, false, false, true>;
+            ipm ? pick<double, 32, 1, false, true, true>(c) : pick<double, 32, 1, false, false, true>(c);
         } else if (ipm) {
-            c.kern = c.waves > 1 ? dual_step_kernel<float, 32, 8, false, true, true> : dual_step_kernel<float, 32, 1, false, true, true>;
+            waves > 1 ? pick<float, 32, 8, false, true, true>(c) : pick<float, 32, 1, false, true, true>(c);
         } else {
-            c.kern = c.waves > 1 ? dual_step_kernel<float, 32, 8, false, false, true> : dual_step_kernel<float, 32, 1, false, false, true>;
-            if (c.waves > 1 && !global) {
+            waves > 1 ? pick<float, 32, 8, false, false, true>(c) : pick<float, 32, 1, false, false, true>(c);
+            if (waves > 1 && !global) {
                 // split staging (dual_step_wide_kernel): LDS for the carve-up of a bundle of up to HV_KMAX cuts + the mirror
                 // of its WIDE_LR oldest rows, or for the plain device-memory body of a larger one
-                const int lds_b = ((staged_lds(c.rows < HV_KMAX ? c.rows : HV_KMAX, c.waves) + 15) & ~15) + WIDE_LR * a.ldA * 4;
+                const int lds_b = ((staged_lds(c.rows < HV_KMAX ? c.rows : HV_KMAX, waves) + 15) & ~15) + WIDE_LR * a.ldA * 4;
                 const int lds_w = lds_b > c.lds ? lds_b : c.lds;
                 if (lds_w <= LDS_BYTES) {
-                    c.kern = dual_step_wide_kernel;
+                    c.kern = dual_step_wide_kernel;     // <float, 32, 8, dual, staged>, as picked above
+                    c.kernel = ICNN_BE_DUAL_PLAN_WIDE;
                     c.lds = lds_w;
                 }
             }
@@ -330,22 +342,39 @@ bool choose_dual_step(const DualArgs &a, DualStepLaunch &c) {
     }
     if (c.rows > fit) c.rows = fit;
     c.lds = dual_lds_bytes(st.n, st.slots, st.cut_dtype, st.variant, c.rows);
-    if (st.variant == ICNN_BE_VARIANT_RL) c.waves = 1;
-    c.kern = f64 ? (big ? dual_kernel_for<double, 32, 1>(st.variant) : dual_kernel_for<double, 16, 1>(st.variant))
-           : c.waves > 1 ? (big ? dual_kernel_for<float, 32, 8>(st.variant) : dual_kernel_for<float, 16, 8>(st.variant))
-                         : (big ? dual_kernel_for<float, 32, 1>(st.variant) : dual_kernel_for<float, 16, 1>(st.variant));
+    if (f64) big ? pick_for<double, 32, 1>(c, st.variant) : pick_for<double, 16, 1>(c, st.variant);
+    else if (waves > 1) big ? pick_for<float, 32, 8>(c, st.variant) : pick_for<float, 16, 8>(c, st.variant);
+    else big ? pick_for<float, 32, 1>(c, st.variant) : pick_for<float, 16, 1>(c, st.variant);
+    return true;
+}
+
+// arguments and instance of launch_dual_step's launch in `round` (not the small kernel's)
+bool prepare_dual_step(DualArgs &a, DualStepLaunch &c, const icnn_be_state &st, int round, int budget, const void *f, const void *g) {
+    if (!make_dual_args(a, st, f, g, round, budget, round + 1 < st.slots ? round + 1 : st.slots, g_prof) || !choose_dual_step(a, c))
+        return false;
+    a.rows = c.rows;
     return true;
 }
 }  // namespace
+
+bool plan_dual_step(const icnn_be_state &st, int round, DualStepPlan &p) {
+    if (dual_step_small_fits(st, 0)) {
+        plan_dual_step_small(st, p);
+        return true;
+    }
+    DualArgs a;
+    DualStepLaunch c;
+    if (!prepare_dual_step(a, c, st, round, 0, nullptr, nullptr)) return false;
+    p = c;
+    return true;
+}
 
 hipError_t launch_dual_step(const icnn_be_state &st, int round, int budget, const void *f, const void *g,
                             hipStream_t stream) {
     if (dual_step_small_fits(st, budget)) return launch_dual_step_small(st, round, f, g, stream);
     DualArgs a;
     DualStepLaunch c;
-    if (!make_dual_args(a, st, f, g, round, budget, round + 1 < st.slots ? round + 1 : st.slots, g_prof) || !choose_dual_step(a, c))
-        return hipErrorInvalidValue;
-    a.rows = c.rows;
+    if (!prepare_dual_step(a, c, st, round, budget, f, g)) return hipErrorInvalidValue;
     return launch_kernel(c.kern, dim3(st.batch), dim3(64 * c.waves), c.lds, stream, a);
 }
 

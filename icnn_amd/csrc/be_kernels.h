@@ -83,6 +83,14 @@ hipError_t launch_dual_step(const icnn_be_state &st, int round, int budget, cons
 // narrow rows (n <= 16), variant RL: four samples per wave, one per 16-lane DPP row (be_dual_small.hip)
 bool dual_step_small_fits(const icnn_be_state &st, int budget);
 hipError_t launch_dual_step_small(const icnn_be_state &st, int round, const void *f, const void *g, hipStream_t stream);
+// Which kernel instance a dual-step launch runs (icnn_be_debug_dual_plan, ICNN_BE_DUAL_PLAN_*): written where the instance is
+// picked, from the instance's own template arguments, and the launchers launch from it
+struct DualStepPlan {
+    int cut, kt, waves, variant, staged, kernel, lds, rows;
+};
+// the plan of launch_dual_step(st, round, 0, ...), no launch; false: no instance fits
+bool plan_dual_step(const icnn_be_state &st, int round, DualStepPlan &p);
+void plan_dual_step_small(const icnn_be_state &st, DualStepPlan &p);
 
 hipError_t launch_fast_math(int which, const double *x, double *out, int count, hipStream_t stream);
 hipError_t launch_export_active(const icnn_be_state &st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,

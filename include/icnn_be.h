@@ -87,6 +87,11 @@ extern "C" {
 #define ICNN_BE_ADAM_ROWS 1                     /* the latency path: 1-4 states per workgroup, state in LDS and registers */
 #define ICNN_BE_ADAM_TILE 2                     /* 16-state MFMA tiles */
 
+/* which kernel icnn_be_dual_step launches (icnn_be_debug_dual_plan, out[5]) */
+#define ICNN_BE_DUAL_PLAN_SMALL 0               /* dual_step_small_kernel: n <= 16, variant rl, four samples per wave */
+#define ICNN_BE_DUAL_PLAN_BODY 1                /* dual_step_kernel: one workgroup of 1 or 8 waves per sample */
+#define ICNN_BE_DUAL_PLAN_WIDE 2                /* dual_step_wide_kernel: eight waves, bundle staged in scratch, oldest rows mirrored in LDS */
+
 /* return codes */
 #define ICNN_BE_EINVAL (-1)    /* bad argument */
 #define ICNN_BE_ELIMIT (-2)    /* size beyond a compiled-in limit */
@@ -1223,6 +1228,16 @@ ICNN_BE_API int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const ic
  * a device.
  */
 ICNN_BE_API int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]);
+/*
+ * The kernel instance icnn_be_dual_step(st, t, ...) launches (additive to ABI 12): returns 0 and fills out = { cut type of the
+ * instance (ICNN_BE_CUT_*), its bundle tile KT (16 or 32; small kernel: its KS, 5, 8 or 16), waves per workgroup, its variant
+ * (ICNN_BE_VARIANT_*), 1 if the bundle is staged in st->scratch instead of LDS, the kernel (ICNN_BE_DUAL_PLAN_*), bytes of
+ * dynamic LDS, bundle rows the staging area holds }, or a negative error code where icnn_be_dual_step refuses the shape or t
+ * (ICNN_BE_EINVAL also for batch 0, where nothing is launched, and where no instance fits).  It is the launcher's own choice,
+ * taken by the launcher's own code, without the launch: host arithmetic on the shape fields, the flags and on whether
+ * st->scratch is set.  Needs no GPU; the buffer pointers of the state are neither read nor checked.
+ */
+ICNN_BE_API int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[8]);
 
 /* ---- the DDPG agent: fused actor-critic step, EMA targets, act (be_ddpg.hip, additive to ABI 12) ---- */
 
