@@ -6,7 +6,9 @@ wants at the origin; the observation is (position, velocity), truncated or zero-
 
     python examples/rl_agent.py [--total 2000] [--train 200] [--test 2] [--tmax 50] [--warmup 100] [--bsize 64] [--iter 1]
                                 [--dimO 4] [--dimA 2] [--capture] [--save FILE] [--resume FILE] [--model {ICNN,DDPG,NAF}]
+                                [--naf-bn]
 
+--naf-bn (with --model NAF): the NAF networks with BatchNorm, agent.py:22's naf_bn.
 --resume FILE restores the agent from a checkpoint before the loop (RL/src/icnn.py:134-137 restores the latest one at
 construction) and --save FILE writes one after it (RL/src/main.py:113-115): weights, optimiser state, noise, the random
 state and the replay memory, so that the agent continues as if it had not stopped.
@@ -90,13 +92,16 @@ def main():
     ap.add_argument("--save", default=None, metavar="FILE")
     ap.add_argument("--resume", default=None, metavar="FILE")
     ap.add_argument("--model", choices=("ICNN", "DDPG", "NAF"), default="ICNN")
+    ap.add_argument("--naf-bn", action="store_true")
     args = ap.parse_args()
+    if args.naf_bn and args.model != "NAF":
+        ap.error("--naf-bn needs --model NAF")
     if args.model == "DDPG":
         agent = rl_agent.DDPGAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
                                    iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture)
     elif args.model == "NAF":
         agent = rl_agent.NAFAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
-                                  iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture)
+                                  iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture, naf_bn=args.naf_bn)
     else:
         spec = dataclasses.replace(picnn.halfcheetah_spec(), n_features=args.dimO, n_labels=args.dimA,
                                    szs=(args.l1size, args.l2size), action_box=False)

@@ -80,6 +80,9 @@ EXPORTS = [
     "icnn_be_ff_grads", "icnn_be_ff_update", "icnn_be_ff_step", "icnn_be_ff_eval",
     "icnn_be_fcn_param_floats", "icnn_be_fcn_work_bytes", "icnn_be_fcn_work_offsets", "icnn_be_fcn_forward", "icnn_be_fcn_backward",
     "icnn_be_fcn_grads", "icnn_be_fcn_update", "icnn_be_fcn_step", "icnn_be_fcn_eval",
+    "icnn_be_naf_bn_param_floats", "icnn_be_naf_bn_layout", "icnn_be_naf_bn_work_bytes", "icnn_be_naf_bn_work_offsets",
+    "icnn_be_naf_bn_chain", "icnn_be_naf_bn_grads", "icnn_be_naf_bn_update", "icnn_be_naf_bn_step", "icnn_be_naf_bn_act",
+    "icnn_be_naf_bn_q",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -107,6 +110,13 @@ NAF_STEP_INTS = 4                          # ICNN_BE_NAF_STEP_INTS: the updates,
 # ICNN_BE_NAF_W_*: the pieces of the NAF workspace, in order
 NAF_WORK = ["y", "u", "l", "ld", "h", "adv", "q", "td", "h1l", "h2l", "h1u", "h2u", "h1v", "h2v", "d3l", "d2l", "d1l", "d3u", "d2u",
             "d1u", "d3v", "d2v", "d1v", "sq", "upd"]
+NAF_BN_MAX_BATCH = 512                     # ICNN_BE_NAF_BN_MAX_BATCH
+NAF_BN_PASSES = ("l", "u", "v", "t")       # ICNN_BE_NAF_BN_PASSES: the three nets at obs, the target at ob2
+NAF_BN_VARS = ["W1", "b1", "W2", "b2", "W3", "b3", "beta0", "beta1", "beta2"]     # ICNN_BE_NAF_BN_VARS
+# ICNN_BE_NAF_BN_W_*: the pieces of the NAF-BN workspace, in order; a piece per pass carries the pass's letter
+NAF_BN_WORK = (["y", "u", "l", "ld", "h", "adv", "q", "td"] + ["d3" + p for p in "luv"]
+               + [k + p for k in ("h0", "h1", "h2", "xh1", "xh2") for p in "luvt"]
+               + [k + p for k in ("d1", "d2") for p in "luv"] + ["stat" + p for p in "luvt"] + ["sq", "upd"])
 FF_MAX_LAYERS, FF_MAX_FEATURES, FF_MAX_WIDTH, FF_MAX_BATCH = 4, 4096, 1024, 512     # ICNN_BE_FF_MAX_*
 FF_STEP_INTS = 4                           # ICNN_BE_FF_STEP_INTS: the updates, the ticket
 # ICNN_BE_FF_W_*: the pieces of the feed-forward workspace, in order; a / h / stat / dz of hidden layer i + 1 at "a%d" % i, ...
@@ -252,6 +262,21 @@ class NafArgs(C.Structure):
         ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
         ("rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
         ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float),
+    ]
+
+
+class NafBnArgs(C.Structure):
+    """struct icnn_be_naf_bn_args"""
+    _fields_ = [
+        ("batch", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("l1", C.c_int), ("l2", C.c_int),
+        ("obs", C.c_void_p), ("act", C.c_void_p), ("rew", C.c_void_p), ("ob2", C.c_void_p), ("term", C.c_void_p),
+        ("theta_l", C.c_void_p), ("theta_u", C.c_void_p), ("theta_v", C.c_void_p), ("target_v", C.c_void_p),
+        ("m_l", C.c_void_p), ("v_l", C.c_void_p), ("m_u", C.c_void_p), ("v_u", C.c_void_p), ("m_v", C.c_void_p), ("v_v", C.c_void_p),
+        ("grad_l", C.c_void_p), ("grad_u", C.c_void_p), ("grad_v", C.c_void_p),
+        ("mv_l", C.c_void_p), ("mv_u", C.c_void_p), ("mv_v", C.c_void_p),
+        ("step", C.c_void_p), ("loss", C.c_void_p), ("work", C.c_void_p),
+        ("rate", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("bn_decay", C.c_double),
+        ("eps", C.c_float), ("tau", C.c_float), ("discount", C.c_float), ("l2norm", C.c_float), ("bn_eps", C.c_float),
     ]
 
 
@@ -508,6 +533,23 @@ def load():
     lib.icnn_be_naf_act.restype = C.c_int
     lib.icnn_be_naf_q.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p]
     lib.icnn_be_naf_q.restype = C.c_int
+    NB = C.POINTER(NafBnArgs)
+    lib.icnn_be_naf_bn_param_floats.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong)] * 5
+    lib.icnn_be_naf_bn_param_floats.restype = C.c_int
+    lib.icnn_be_naf_bn_layout.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_longlong * len(NAF_BN_VARS))]
+    lib.icnn_be_naf_bn_layout.restype = C.c_int
+    lib.icnn_be_naf_bn_work_bytes.argtypes = [C.c_int] * 5
+    lib.icnn_be_naf_bn_work_bytes.restype = C.c_size_t
+    lib.icnn_be_naf_bn_work_offsets.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_longlong * len(NAF_BN_WORK))]
+    lib.icnn_be_naf_bn_work_offsets.restype = C.c_int
+    for name in ("chain", "grads", "update", "step"):
+        fn = getattr(lib, "icnn_be_naf_bn_" + name)
+        fn.argtypes, fn.restype = [NB, C.c_void_p], C.c_int
+    lib.icnn_be_naf_bn_act.argtypes = [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.icnn_be_naf_bn_act.restype = C.c_int
+    lib.icnn_be_naf_bn_q.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+                                     + [C.c_void_p] * 3)
+    lib.icnn_be_naf_bn_q.restype = C.c_int
     FA = C.POINTER(FfArgs)
     ff_dims = [C.c_int] * 3 + [C.POINTER(C.c_int)]
     lib.icnn_be_ff_param_floats.argtypes = ff_dims + [C.POINTER(C.c_longlong)]
@@ -571,6 +613,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_ff_args differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(18) != C.sizeof(FcnArgs):
         raise ImportError("ctypes struct layout of icnn_be_fcn_args differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(20) != C.sizeof(NafBnArgs):
+        raise ImportError("ctypes struct layout of icnn_be_naf_bn_args differs from libicnn_be.so's")
     if lib.icnn_be_abi_version() != ABI_VERSION:
         raise ImportError("libicnn_be.so ABI %d != binding ABI %d; rebuild with python -m icnn_amd.build"
                           % (lib.icnn_be_abi_version(), ABI_VERSION))

@@ -9,7 +9,8 @@ result depends on:
     BundleTrainer        with skip_on_error, the gate words (the skipped count among them)
     CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step)
     ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
-    naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count
+    naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count;
+                         with bn=True the betas and their moments lie inside those, and bn/l, bn/u, bn/v are the moving pairs
     ff.FFTrainer         the flat theta/ff, m/ff, v/ff, the step count and the moving statistics bn/mean<i>, bn/var<i>
     fcn.FCNTrainer       the flat theta/fcn, m/fcn, v/fcn and the step count
     Agent, DDPGAgent, NAFAgent   its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
@@ -116,6 +117,9 @@ def _trainer_tensors(kind, obj) -> dict:
         out["step"] = obj.step_count
         if kind == "FFTrainer":
             _model_stats("", obj.model, out)
+        if getattr(obj, "bn", False):                           # naf.NAFTrainer(bn=True): a net's moving pairs, one vector
+            for w, t in obj.mv.items():
+                out["bn/" + w] = t
         return out
     out = {"theta": obj.opt.theta, "m": obj.opt.m, "v": obj.opt.v, "step": obj.opt.step_count}
     if kind == "CriticTrainer":

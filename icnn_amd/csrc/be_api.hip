@@ -262,7 +262,8 @@ size_t icnn_be_struct_size(int which) {
          : which == 8 ? sizeof(icnn_be_ficnn_model) : which == 9 ? sizeof(icnn_be_replay)
          : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log)
          : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args)
-         : which == 16 ? sizeof(icnn_be_ff_args) : which == 18 ? sizeof(icnn_be_fcn_args) : 0;
+         : which == 16 ? sizeof(icnn_be_ff_args) : which == 18 ? sizeof(icnn_be_fcn_args)
+         : which == 20 ? sizeof(icnn_be_naf_bn_args) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -1144,6 +1145,107 @@ int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, cons
         return ICNN_BE_EINVAL;
     return done(icnn_be::launch_naf_q(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, obs, act, batch, out,
                                       static_cast<hipStream_t>(stream)));
+}
+
+namespace {
+bool naf_bn_sizes_ok(int batch, int dimO, int dimA, int l1, int l2) {
+    return batch >= 1 && batch <= ICNN_BE_NAF_BN_MAX_BATCH && naf_sizes_ok(dimO, dimA, l1, l2) && icnn_be::naf_bn_fits(dimA, l2);
+}
+
+// what every icnn_be_naf_bn_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
+int check_naf_bn(const icnn_be_naf_bn_args *a, void *stream, bool need_loss) {
+    if (!a || !naf_bn_sizes_ok(a->batch, a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
+    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
+                         a->grad_l, a->grad_u, a->grad_v, a->work};
+    for (const void *p : a16)
+        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
+    const void *a4[] = {a->obs, a->rew, a->ob2, a->step, a->mv_l, a->mv_u, a->mv_v};
+    for (const void *p : a4)
+        if (misaligned(p, 4)) return ICNN_BE_EINVAL;
+    if (misaligned(a->act, 8) || !a->term || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    if (need_loss ? misaligned(a->loss, 4) : reinterpret_cast<uintptr_t>(a->loss) % 4 != 0) return ICNN_BE_EINVAL;
+    if (!(a->tau >= 0.f && a->tau <= 1.f) || !std::isfinite(a->discount)) return ICNN_BE_EINVAL;
+    if (!(a->l2norm >= 0.f) || !std::isfinite(a->l2norm)) return ICNN_BE_EINVAL;
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f)) return ICNN_BE_EINVAL;
+    if (!std::isfinite(a->rate) || !(a->bn_eps > 0.f) || !(a->bn_decay >= 0.0 && a->bn_decay <= 1.0)) return ICNN_BE_EINVAL;
+    return 0;
+}
+}  // namespace
+
+int icnn_be_naf_bn_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv, long long *nt,
+                                long long *ns) {
+    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || !nl || !nu || !nv || !nt || !ns) return ICNN_BE_EINVAL;
+    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 0, nullptr, nl, nullptr);
+    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 1, nullptr, nu, nullptr);
+    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 2, nullptr, nv, nt);
+    *ns = 2LL * (dimO + l1 + l2);
+    return 0;
+}
+
+int icnn_be_naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long off[ICNN_BE_NAF_BN_VARS]) {
+    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || which < 0 || which > 2 || !off) return ICNN_BE_EINVAL;
+    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, which, off, nullptr, nullptr);
+    return 0;
+}
+
+size_t icnn_be_naf_bn_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2)) return 0;
+    return icnn_be::naf_bn_work_floats(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
+}
+
+int icnn_be_naf_bn_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_BN_WORK_PIECES]) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
+    icnn_be::naf_bn_work_floats(batch, dimO, dimA, l1, l2, off);
+    return 0;
+}
+
+int icnn_be_naf_bn_chain(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_bn_chain(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_grads(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_bn_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_update(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return done(icnn_be::launch_naf_bn_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_step(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, true)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = icnn_be::launch_naf_bn_chain(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_naf_bn_grads(*a, s);
+    if (e == hipSuccess) e = icnn_be::launch_naf_bn_update(*a, true, s);
+    if (e == hipSuccess) e = icnn_be::launch_naf_bn_fold(*a, s);
+    return done(e);
+}
+
+int icnn_be_naf_bn_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *mv_u, float bn_eps, int mode,
+                       const float *obs, int batch, float *out, void *work, void *stream) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_u, 16) || misaligned(work, 16) || misaligned(mv_u, 4) || misaligned(obs, 4) || misaligned(out, 4) ||
+        reinterpret_cast<uintptr_t>(stream) % 8 || !(bn_eps > 0.f))
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_naf_bn_forward(dimO, dimA, l1, l2, nullptr, theta_u, nullptr, nullptr, mv_u, nullptr, bn_eps,
+                                               mode == ICNN_BE_BN_MOVING, obs, nullptr, batch, out, work,
+                                               static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                     const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps, int mode, const float *obs,
+                     const double *act, int batch, float *out, void *work, void *stream) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(work, 16) ||
+        misaligned(mv_l, 4) || misaligned(mv_u, 4) || misaligned(mv_v, 4) || misaligned(obs, 4) || misaligned(act, 8) ||
+        misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8 || !(bn_eps > 0.f))
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_naf_bn_forward(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, mv_l, mv_u, mv_v, bn_eps,
+                                               mode == ICNN_BE_BN_MOVING, obs, act, batch, out, work,
+                                               static_cast<hipStream_t>(stream)));
 }
 
 namespace {

@@ -425,6 +425,21 @@ hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStrea
 hipError_t launch_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
                         const float *obs, const double *act, int B, float *out, hipStream_t stream);
 
+// ---- NAF with BatchNorm (be_naf_bn.hip) ------------------------------------------------
+bool naf_bn_fits(int dimA, int l2);                      // the per-sample kernel's LDS
+// off[ICNN_BE_NAF_BN_VARS], the floats of the vector and of its W and b alone; each may be NULL.  which: 0 L, 1 U, 2 V
+void naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long *off, long long *n, long long *plain);
+size_t naf_bn_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
+hipError_t launch_naf_bn_chain(const icnn_be_naf_bn_args &d, hipStream_t stream);
+hipError_t launch_naf_bn_grads(const icnn_be_naf_bn_args &d, hipStream_t stream);
+hipError_t launch_naf_bn_update(const icnn_be_naf_bn_args &d, bool with_loss, hipStream_t stream);
+hipError_t launch_naf_bn_fold(const icnn_be_naf_bn_args &d, hipStream_t stream);
+// theta_l NULL: u(obs) into out [B][dimA]; else q(obs, act) into out [B]
+hipError_t launch_naf_bn_forward(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u,
+                                 const float *theta_v, const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps,
+                                 int moving, const float *obs, const double *act, int B, float *out, void *work,
+                                 hipStream_t stream);
+
 // ---- the feed-forward baseline (be_ff.hip) ---------------------------------------------
 long long ff_param_floats(int n_features, int n_labels, int n_layers, const int *width);
 size_t ff_work_floats(int B, int n_features, int n_labels, int n_layers, const int *width, long long *off);

@@ -7,7 +7,8 @@
 //                        td and the tile's sum of td^2, the head's backward and the three backward chains down to the
 //                        pre-activation deltas.  Products are tile_gemm of be_tile.h; the head is per-sample VALU work, a
 //                        group of 32 lanes per sample with lane j owning column j of the L matrix and every sum one fma
-//                        chain in index order.  full = 0 stops after q: that is icnn_be_naf_q, with the chain's bits.
+//                        chain in index order (be_naf_head.h, shared with be_naf_bn.hip).  full = 0 stops after q: that is
+//                        icnn_be_naf_q, with the chain's bits.
 //   the weight gradients  grad_table_kernel (be_train_table.hip) over a table of the nine layers.
 //   the update            param_sets_update_kernel (be_train_table.hip) over three parameter sets with one step count; only V
 //                        has a target; sum theta_old^2 of all three enters loss_q.
@@ -17,6 +18,7 @@
 // place); bB and bC the two hidden layers of the net at hand.  The hidden layers of U and V are not kept: their backward
 // chains re-read the masks from the workspace, which this workgroup wrote.
 #include "be_kernels.h"
+#include "be_naf_head.h"
 #include "be_tile.h"
 #include "be_train_common.h"
 #include "be_train_table.h"
@@ -101,20 +103,8 @@ __global__ __launch_bounds__(DT) void naf_chain_kernel(NafChainArgs a) {
     __syncthreads();
     // ---- the head: Lm, delta, h, A, q.  The loops are uniform; a lane's own part is predicated behind the shuffle ----
     float *lr = bA + s32 * PA;                                   // l of this sample, row-major [dimA][dimA]
-    const float uj = col ? sU[s32 * PS + j] : 0.f;
-    const float dl = col ? sD[s32 * PS + j] - uj : 0.f;          // delta[j]
-    const float e = col ? expf(lr[j * dimA + j]) : 0.f;          // Lm[j][j]
-    float hj = 0.f;
-    for (int i = 0; i < dimA; ++i) {
-        const float di = __shfl(dl, i, 32);
-        if (col && i >= j) hj = fmaf(di, i == j ? e : lr[i * dimA + j], hj);
-    }
-    float ss = 0.f;
-    for (int c = 0; c < dimA; ++c) {
-        const float hc = __shfl(hj, c, 32);
-        ss = fmaf(hc, hc, ss);
-    }
-    const float adv = -0.5f * ss, q = v + adv;
+    const NafHead H = naf_head_forward(lr, sU + s32 * PS, sD + s32 * PS, dimA, j);
+    const float e = H.e, hj = H.hj, adv = H.adv, q = v + adv;
     if (row && j == 0) a.q[gs] = q;
     if (!a.full) return;
     const float td = q - y, d3 = a.inv_b * (2.f * td);
@@ -134,13 +124,8 @@ __global__ __launch_bounds__(DT) void naf_chain_kernel(NafChainArgs a) {
         vd[s32] = row ? d3 : 0.f;
     }
     // ---- the head's backward: gh[j] = -d3 h[j]; lane j reads ROW j of l for u's delta before the columns are overwritten ----
-    const float gh = -d3 * hj;
-    float acc_u = 0.f;
-    for (int c = 0; c < dimA; ++c) {
-        const float g = __shfl(gh, c, 32);
-        if (col && c <= j) acc_u = fmaf(g, c == j ? e : lr[j * dimA + c], acc_u);
-    }
-    const float du = -acc_u * (1.f - uj * uj);
+    float gh;
+    const float du = naf_head_du(H, lr, dimA, j, d3, gh);
     __syncthreads();
     if (tid == 0) {
         double s = 0.0;
@@ -151,14 +136,7 @@ __global__ __launch_bounds__(DT) void naf_chain_kernel(NafChainArgs a) {
         sD[s32 * PS + j] = du;
         if (row) a.d3u[gs * dimA + j] = du;
     }
-    for (int i = 0; i < dimA; ++i) {                             // d loss / d l, column j, in place
-        const float di = __shfl(dl, i, 32);
-        if (col) {
-            const float g = i < j ? 0.f : i == j ? (di * gh) * e : di * gh;
-            lr[i * dimA + j] = g;
-            if (row) a.d3l[gs * nL + i * dimA + j] = g;
-        }
-    }
+    naf_head_dl(H, lr, dimA, j, gh, row ? a.d3l + gs * nL : nullptr);       // d loss / d l, column j, in place
     __syncthreads();
     // ---- L's backward chain: its hidden layers are still in bB and bC ----
     tile_gemm(bA, PA, nL, L.W3, 1, nL, l2, [&](int s, int c, float acc) {

@@ -1,4 +1,4 @@
-// The tile routines that the per-sample chain kernels share (be_ddpg.hip, be_naf.hip): one workgroup of DT threads works on
+// The tile routines that the per-sample chain kernels share (be_ddpg.hip, be_naf.hip, be_naf_bn.hip): one workgroup of DT threads works on
 // a tile of TS samples whose activations lie in LDS.  Device code only; each translation unit gets its own copy.
 #pragma once
 #include "be_kernels.h"

@@ -1,4 +1,4 @@
-// The two table kernels of the flat-vector trainers (be_train_table.hip; be_ddpg.hip, be_naf.hip and be_ff.hip fill the
+// The two table kernels of the flat-vector trainers (be_train_table.hip; be_ddpg.hip, be_naf.hip, be_naf_bn.hip, be_ff.hip fill the
 // tables): the weight and bias gradients of a table of layers in one launch, and the update of a table of parameter sets in one.
 #pragma once
 #include "be_kernels.h"
@@ -33,6 +33,8 @@ struct ParamSet {
     int blocks, slot;                    // blocks: param_update_blocks(n); slot: which step count this set reads
     float k;                             // the decay coefficient
     double lr;
+    long long tail;                      // the last `tail` elements (NAF-BN's betas) get no decay, stay out of sum theta^2 and
+                                         // have no target: the target holds n - tail floats
 };
 struct ParamSetsArgs {
     ParamSet set[UPDATE_SETS];

@@ -11,6 +11,7 @@
 //                             orders the moving average behind the assignment) for a set that has a target.  The workgroups of
 //                             the leading sets also reduce sum theta_old^2, and the last workgroup by ticket forms loss_q from
 //                             the chain kernel's tile partials and those, each in index order (the scheme of rl_td_kernel).
+//                             The last `tail` elements of a set are exempt from the decay, the sum and the target.
 #include "be_train_table.h"
 
 #include "be_common.h"
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(UT) void param_sets_update_kernel(ParamSetsArgs u) 
     while (which + 1 < u.sets && block >= u.set[which].blocks) block -= u.set[which++].blocks;
     const ParamSet &a = u.set[which];
     const bool has_target = a.target != nullptr;
+    const long long plain = a.n - a.tail;    // the elements behind it: no decay, not in sum theta^2, not in the target
     if (threadIdx.x == 0) {
         // updates done so far: the last workgroup writes the counts back only after every workgroup has taken its ticket, and
         // every workgroup reads its count before it takes one
@@ -86,38 +88,47 @@ __global__ __launch_bounds__(UT) void param_sets_update_kernel(ParamSetsArgs u) 
     double ssq = 0.0;
     if (j0 < a.n) {
         const int cnt = a.n - j0 < UPT ? (int)(a.n - j0) : UPT;
+        const int tcnt = !has_target || plain <= j0 ? 0 : plain - j0 < UPT ? (int)(plain - j0) : UPT;       // of the target
         float th[UPT] = {}, m[UPT] = {}, v[UPT] = {}, g[UPT] = {}, tt[UPT] = {};
         if (cnt == UPT) {
             load_quad(th, a.theta + j0);
-            if (has_target) load_quad(tt, a.target + j0);
             load_quad(m, a.m + j0);
             load_quad(v, a.v + j0);
             load_quad(g, a.grad + j0);
         } else {
             for (int k = 0; k < cnt; ++k) {
-                th[k] = a.theta[j0 + k]; tt[k] = has_target ? a.target[j0 + k] : 0.f;
+                th[k] = a.theta[j0 + k];
                 m[k] = a.m[j0 + k]; v[k] = a.v[j0 + k]; g[k] = a.grad[j0 + k];
             }
+        }
+        if (tcnt == UPT) {
+            load_quad(tt, a.target + j0);
+        } else {
+            for (int k = 0; k < tcnt; ++k) tt[k] = a.target[j0 + k];
         }
 #pragma unroll
         for (int k = 0; k < UPT; ++k) {
             // the decay term in front of the step and the target rule behind it, from the new theta
             const float old = th[k];
-            ssq = ssq + (double)old * (double)old;                  // the padding elements are zero
-            const float gk = a.k != 0.f ? g[k] + a.k * old : g[k];
+            const bool pl = j0 + k < plain;
+            if (pl) ssq = ssq + (double)old * (double)old;
+            const float gk = a.k != 0.f && pl ? g[k] + a.k * old : g[k];
             th[k] = tf_adam_element(old, m[k], v[k], gk, u.b1, u.c1, u.b2, u.c2, lr_t, eps);
             tt[k] = tt[k] - tau * (tt[k] - th[k]);
         }
         if (cnt == UPT) {
             store_quad(a.theta + j0, th);
-            if (has_target) store_quad(a.target + j0, tt);
             store_quad(a.m + j0, m);
             store_quad(a.v + j0, v);
         } else {
             for (int k = 0; k < cnt; ++k) {
                 a.theta[j0 + k] = th[k]; a.m[j0 + k] = m[k]; a.v[j0 + k] = v[k];
-                if (has_target) a.target[j0 + k] = tt[k];
             }
+        }
+        if (tcnt == UPT) {
+            store_quad(a.target + j0, tt);
+        } else {
+            for (int k = 0; k < tcnt; ++k) a.target[j0 + k] = tt[k];
         }
     }
     // loss_q's decay sum: one partial per workgroup of the sets that enter it

@@ -241,13 +241,15 @@ class DDPGAgent(_AgentCycle):
 class NAFAgent(_AgentCycle):
     """`Agent` of RL/src/naf.py around naf.NAFTrainer: the same reset / act / observe / train cycle, memory,
     noise and capture as Agent; act() is one launch of the U net at the current observation (icnn_be_naf_act).  l1, l2, rate,
-    tau, discount, l2norm and initstd go to the trainer; seed also draws its initial weights."""
+    tau, discount, l2norm and initstd go to the trainer; seed also draws its initial weights.  naf_bn: the networks with
+    BatchNorm (agent.py:22); act() then normalises with U's moving pairs (naf.py:118)."""
 
     def __init__(self, dimO, dimA, l1=200, l2=200, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1,
-                 seed=0, capture=False, rate=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, initstd=0.01, device="cuda"):
+                 seed=0, capture=False, rate=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, initstd=0.01, device="cuda",
+                 naf_bn=False):
         self._check_cycle(warmup, iters)
         self.trainer = naf.NAFTrainer(dimO, dimA, l1, l2, batch=bsize, rate=rate, tau=tau, discount=discount, l2norm=l2norm,
-                                      seed=seed, device=device, initstd=initstd)
+                                      seed=seed, device=device, initstd=initstd, bn=naf_bn)
         self.spec = self.trainer.spec
         self._setup(dimO, dimA, self.trainer.device, warmup, iters, rmsize, outheta, ousigma, seed, capture)
         self._obs1 = torch.zeros(1, self.dimO, dtype=torch.float32, device=self.device)

@@ -1565,6 +1565,101 @@ ICNN_BE_API int icnn_be_fcn_update(const icnn_be_fcn_args *a, void *stream);
 ICNN_BE_API int icnn_be_fcn_step(const icnn_be_fcn_args *a, void *stream);
 ICNN_BE_API int icnn_be_fcn_eval(const icnn_be_fcn_args *a, void *stream);
 
+/* ---- NAF with BatchNorm, naf_bn True (be_naf_bn.hip, additive to ABI 12) ----
+ *
+ * RL/src/naf_nets_dm.py:18-34 with naf_bn True: a BatchNorm (decay 0.999, epsilon 1e-3, a trainable beta, no gamma) in front of
+ * the first layer and between each hidden product and its ReLU, in all three nets.  One site, S = dimO + l1 + l2 columns in all:
+ *   batch mode   mu, var = the mean and the biased two-pass variance of a column over the batch; out = (x - mu) / sqrt(var +
+ *                bn_eps) + beta
+ *   moving mode  the same with the net's moving pair
+ *   h0 = BN0(obs);  h1 = relu(BN1(h0 W1 + b1));  h2 = relu(BN2(h1 W2 + b2));  out = h2 W3 + b3;  the head is icnn_be_naf_*'s.
+ * theta_l, theta_u, theta_v: the flat vector of icnn_be_naf_* (W1, b1, W2, b2, W3, b3) with beta0 [dimO], beta1 [l1], beta2
+ * [l2] behind it; m, v and grad have that layout.  target_v: W and b alone, the flat vector of icnn_be_naf_*.  mv_l, mv_u,
+ * mv_v: the moving pairs of a net, 2 S floats: mean0, var0 [dimO each], mean1, var1 [l1], mean2, var2 [l2] (fresh: means 0,
+ * variances 1).  The target pass mlp(ob2) reads target_v's W and b with theta_v's betas (naf.py:42-71, the reuse arguments).
+ *
+ * One step: the four passes (L, U, V at obs, the target at ob2) in batch mode, each on the statistics of its own input; y, the
+ * head, td, loss_q = mean td^2 + l2norm sum theta^2 / 2 over the 18 W and b (the betas stay out), its gradient with respect to
+ * the W, b and the nine betas (the target under stop_gradient); ONE TF-Adam over the three vectors, the decay term for W and b
+ * alone; target_v from the new W and b of V; then the fold  m <- m - (m - batch) (1 - bn_decay)  in float32 of L's and U's pairs
+ * once and of V's twice, first with the statistics at obs, then with those at ob2.
+ *   icnn_be_naf_bn_chain    forward and backward down to every pre-activation delta and the nine d beta (in grad): 7 launches
+ *   icnn_be_naf_bn_grads    the eighteen weight and bias gradients: one launch
+ *   icnn_be_naf_bn_update   the update and loss_q: one launch;  no fold
+ *   icnn_be_naf_bn_step     chain, grads, update, fold: 10 launches
+ *   icnn_be_naf_bn_act      out[batch][dimA] = u(obs) in `mode` (ICNN_BE_BN_BATCH / ICNN_BE_BN_MOVING)
+ *   icnn_be_naf_bn_q        out[batch] = q(obs, act) in `mode`
+ * act and q go through a workspace of icnn_be_naf_bn_work_bytes(batch, ...) bytes of their own batch; they write nothing
+ * of the model.  No entry synchronises; all are capturable; no float atomics: every run gives the same bits.
+ *
+ * The workspace: 16-byte aligned; icnn_be_naf_bn_work_offsets gives the offset in floats of each piece ICNN_BE_NAF_BN_W_*
+ * ([batch][width] float32 unless said otherwise); nothing outside the rows < batch of a piece is written.  A piece "+ p" exists
+ * per pass p = 0 (L), 1 (U), 2 (V), 3 (the target at ob2).  step: as icnn_be_naf_*.
+ *
+ * Sizes: those of icnn_be_naf_* and 1 <= batch <= ICNN_BE_NAF_BN_MAX_BATCH in every entry (a workgroup holds a column of the
+ * whole batch); batch 1 is legal: var = 0 and a site's output is beta.  EINVAL as icnn_be_naf_*, also for a mode that is neither,
+ * bn_eps <= 0 or bn_decay outside [0, 1], before anything is launched (0 from icnn_be_naf_bn_work_bytes).
+ */
+#define ICNN_BE_NAF_BN_MAX_BATCH 512
+#define ICNN_BE_NAF_BN_PASSES 4
+#define ICNN_BE_NAF_BN_VARS 9     /* W1, b1, W2, b2, W3, b3, beta0, beta1, beta2 */
+#define ICNN_BE_NAF_BN_W_Y 0      /* the per-sample pieces of icnn_be_naf_*: y, u, l, diag Lm, h, A, q, td */
+#define ICNN_BE_NAF_BN_W_U 1
+#define ICNN_BE_NAF_BN_W_L 2
+#define ICNN_BE_NAF_BN_W_LD 3
+#define ICNN_BE_NAF_BN_W_H 4
+#define ICNN_BE_NAF_BN_W_ADV 5
+#define ICNN_BE_NAF_BN_W_Q 6
+#define ICNN_BE_NAF_BN_W_TD 7
+#define ICNN_BE_NAF_BN_W_D3 8     /* + p, p < 3: layer 3's delta [dimA^2], [dimA], [1] */
+#define ICNN_BE_NAF_BN_W_H0 11    /* + p: BN0's output [dimO] */
+#define ICNN_BE_NAF_BN_W_H1 15    /* + p: relu(BN1(.)) [l1] */
+#define ICNN_BE_NAF_BN_W_H2 19    /* + p: relu(BN2(.)) [l2] */
+#define ICNN_BE_NAF_BN_W_XH1 23   /* + p: the normalised pre-activation of BN1, before beta [l1] */
+#define ICNN_BE_NAF_BN_W_XH2 27   /* + p: of BN2 [l2] */
+#define ICNN_BE_NAF_BN_W_D1 31    /* + p, p < 3: d loss / d (h0 W1 + b1) [l1] */
+#define ICNN_BE_NAF_BN_W_D2 34    /* + p, p < 3: d loss / d (h1 W2 + b2) [l2] */
+#define ICNN_BE_NAF_BN_W_STAT 37  /* + p: [2 S] the batch statistics in the layout of mv_* */
+#define ICNN_BE_NAF_BN_W_SQ 41    /* float64 [tiles of 16 samples]: each tile's sum of td^2 */
+#define ICNN_BE_NAF_BN_W_UPD 42   /* float64: the update's partial sums of theta^2 */
+#define ICNN_BE_NAF_BN_WORK_PIECES 43
+typedef struct icnn_be_naf_bn_args {
+    int batch, dimO, dimA, l1, l2;
+    const float *obs;                 /* [batch][dimO] */
+    const double *act;                /* [batch][dimA] */
+    const float *rew;                 /* [batch] */
+    const float *ob2;                 /* [batch][dimO] */
+    const unsigned char *term;        /* [batch] */
+    float *theta_l, *theta_u, *theta_v, *target_v;      /* separately allocated */
+    float *m_l, *v_l, *m_u, *v_u, *m_v, *v_v;           /* Adam's moments */
+    float *grad_l, *grad_u, *grad_v;  /* the step's gradients, before the decay term */
+    float *mv_l, *mv_u, *mv_v;        /* the moving pairs, [2 S] each */
+    int *step;                        /* [ICNN_BE_NAF_STEP_INTS] */
+    float *loss;                      /* loss_q of the step */
+    void *work;
+    double rate, beta1, beta2, bn_decay;
+    float eps, tau, discount, l2norm, bn_eps;
+} icnn_be_naf_bn_args;                /* icnn_be_struct_size(20) */
+
+/* floats of theta_l (*nl), theta_u (*nu), theta_v (*nv), target_v (*nt) and of one net's moving pairs (*ns = 2 S) */
+ICNN_BE_API int icnn_be_naf_bn_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv,
+                                            long long *nt, long long *ns);
+/* off[i]: where variable i (ICNN_BE_NAF_BN_VARS, in the order W1 .. b3, beta0 .. beta2) of net `which` (0 L, 1 U, 2 V) begins */
+ICNN_BE_API int icnn_be_naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long off[ICNN_BE_NAF_BN_VARS]);
+/* 0 for sizes out of range */
+ICNN_BE_API size_t icnn_be_naf_bn_work_bytes(int batch, int dimO, int dimA, int l1, int l2);
+ICNN_BE_API int icnn_be_naf_bn_work_offsets(int batch, int dimO, int dimA, int l1, int l2,
+                                            long long off[ICNN_BE_NAF_BN_WORK_PIECES]);
+ICNN_BE_API int icnn_be_naf_bn_chain(const icnn_be_naf_bn_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_bn_grads(const icnn_be_naf_bn_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_bn_update(const icnn_be_naf_bn_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_bn_step(const icnn_be_naf_bn_args *a, void *stream);
+ICNN_BE_API int icnn_be_naf_bn_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *mv_u, float bn_eps,
+                                   int mode, const float *obs, int batch, float *out, void *work, void *stream);
+ICNN_BE_API int icnn_be_naf_bn_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u,
+                                 const float *theta_v, const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps,
+                                 int mode, const float *obs, const double *act, int batch, float *out, void *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,841 @@
+"""NAF with BatchNorm on the device (naf.NAFTrainer(bn=True), rl_agent.NAFAgent(naf_bn=True), icnn_be_naf_bn_*,
+be_naf_bn.hip) against tests/naf_bn_ref.py: the reference's gradients against torch.autograd, the ABI and its
+argument checks, the layout and the initial state (CPU); the forward and backward kernels, the weight gradients, the update
+and the fold, whole steps eager and captured, policy / q in both modes, the agent's cycle and checkpoints (GPU).  Every
+tolerance is the reference's running bound of that quantity (naf_bn_ref's docstring).
+
+How sharp the bounds are.  A bound that runs from the minibatch through three BatchNorm sites and back is a worst case, and it
+grows by a factor of the order 6 sqrt(fan-in) per site (ff_ref's docstring).  At the shipped shape and at B = 512 it EXCEEDS
+the quantity itself for q, td, every delta, every d beta and the gradients of W1 and W2, so there
+test_chain_against_the_reference can only catch an error of the quantity's own size or more, not a wrong term; on the small
+shapes the same holds for the first layer (dz1, d beta1, the gradient of W1).  What checks the kernels' arithmetic at every
+shape is test_layers_from_the_devices_own_operands: every launch against the reference applied to the operands that launch
+read, under the rounding bound of that one stage, which it asserts to be below 5 % of the quantity (median) wherever the
+batch has 8 rows or more.  The two WIDE shapes keep the end-to-end bounds below the quantities too (q, td, dz2, d beta2, the
+gradients of W2 and W3) with a K of 160 that col_gemm streams in two chunks, forward and backward."""
+import ctypes as C
+import functools
+import importlib.util
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import naf_bn_ref as ref
+import naf_ref
+from icnn_amd import _lib, checkpoint, naf, rl_agent
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAXB = _lib.NAF_BN_MAX_BATCH
+# (B, dimO, dimA, l1, l2): the smallest batch with a variance, every tile partial, a 1 x 1 L; one row over a tile with exact
+# column tiles; K and N tails; dimA^2 = 25; the degenerate batch (var = 0, a site's output is beta); the longest column and the
+# shortest staged chunk; the shipped shape.  WIDE: K = 160 in two chunks of 128 at a batch whose end-to-end bounds stay small:
+# l1 = 160 is layer 2's forward and BN1's backward (dout = dz2 W2^T has K = 24, BN0's has K = 160), l2 = 160 the other way round
+WIDE = [(8, 3, 1, 160, 24), (8, 3, 1, 24, 160)]
+SMALL = [(2, 3, 1, 5, 7), (17, 5, 2, 16, 16), (33, 3, 3, 20, 12), (20, 11, 5, 33, 18), (1, 3, 1, 5, 7)] + WIDE
+LONGEST = (MAXB, 3, 1, 16, 16)
+SHIPPED = (256, 17, 6, 200, 200)
+SHAPES = SMALL + [LONGEST, SHIPPED]
+# The draw each shape is tested at.  The masks of a small shape must match exactly, so its draw must have no BatchNorm output
+# below its own bound: MARGIN is the smallest |o| / bound of these draws on the CPU, which
+# test_small_shapes_have_no_ambiguous_unit asserts (within 1 %: the figure is recorded, not chosen).  The seeds are the best of
+# 0 .. 11 on the CPU: BatchNorm's bounds are wide (naf_bn_ref, ff_ref), so the margins are smaller than test_naf's.  At the
+# shipped shape and at the longest column (49152 masked units) every seed has ambiguous units, so flips there are legitimate;
+# test_chain_against_the_reference prints how many units are ambiguous and how many flipped.
+SEED = {SMALL[0]: 3, SMALL[1]: 9, SMALL[2]: 3, SMALL[3]: 5, SMALL[4]: 10, WIDE[0]: 4, WIDE[1]: 4, LONGEST: 0, SHIPPED: 0}
+MARGIN = {SMALL[0]: 326.1, SMALL[1]: 5.291, SMALL[2]: 3.599, SMALL[3]: 3.076, SMALL[4]: 12.78, WIDE[0]: 2.6, WIDE[1]: 3.113}
+DISCOUNT = float(np.float32(0.99))
+NEW_EXPORTS = ["icnn_be_naf_bn_param_floats", "icnn_be_naf_bn_layout", "icnn_be_naf_bn_work_bytes", "icnn_be_naf_bn_work_offsets",
+               "icnn_be_naf_bn_chain", "icnn_be_naf_bn_grads", "icnn_be_naf_bn_update", "icnn_be_naf_bn_step",
+               "icnn_be_naf_bn_act", "icnn_be_naf_bn_q"]
+W = ("l", "u", "v")
+
+
+def _nets(shape, seed):
+    """the three nets with betas and V's target (W and b of a draw of its own)"""
+    _, dimO, dimA, l1, l2 = shape
+    a, b = ref.uniform_params(dimO, dimA, l1, l2, seed), naf_ref.uniform_params(dimO, dimA, l1, l2, seed + 100)
+    return a, b["V"]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(shape):
+    seed = SEED[shape]
+    nets, target = _nets(shape, seed)
+    mb = naf_ref.batch(shape[0], shape[1], shape[2], seed)
+    return (nets, target, mb) + ref.reference_step(nets, target, mb, DISCOUNT)
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+
+
+@pytest.mark.parametrize("shape", [(5, 3, 2, 6, 4), (7, 4, 3, 5, 9)])
+def test_reference_gradients_match_autograd(shape):
+    """the analytic gradient of naf_bn_ref against torch.autograd in float64: betas included, the target detached, V's betas
+    shared with the target pass (which gives them no gradient)"""
+    B, dimO, dimA, l1, l2 = shape
+    nets, target = _nets(shape, 3)
+    mb = naf_ref.batch(B, dimO, dimA, 3)
+    l2norm = 1e-2
+    p, fw, _, d, _, _, _ = ref.reference_step(nets, target, mb, DISCOUNT)
+
+    def t(net, grad):
+        return {k: torch.tensor(np.asarray(v, np.float64), requires_grad=grad) for k, v in net.items()}
+
+    def bn(x, beta):
+        mu = x.mean(0)
+        var = ((x - mu) ** 2).mean(0)
+        return (x - mu) / torch.sqrt(var + ref.BN_EPS) + beta
+
+    def mlp(N, betas, o):
+        h = bn(o, betas["beta0"])
+        h = torch.relu(bn(h @ N["W1"] + N["b1"], betas["beta1"]))
+        h = torch.relu(bn(h @ N["W2"] + N["b2"], betas["beta2"]))
+        return h @ N["W3"] + N["b3"]
+
+    obs, act, rew, ob2 = (torch.tensor(np.asarray(x, np.float64)) for x in mb[:4])
+    term = torch.tensor(mb[4] != 0)
+    T = {w: t(nets[w], True) for w in ref.NETS}
+    tT = t(target, False)
+    y = torch.where(term, rew, rew + DISCOUNT * mlp(tT, T["V"], ob2)[:, 0]).detach()
+    lm = mlp(T["L"], T["L"], obs).reshape(B, dimA, dimA)
+    Lm = torch.tril(lm, -1) + torch.diag_embed(torch.exp(torch.diagonal(lm, dim1=1, dim2=2)))
+    delta = act - torch.tanh(mlp(T["U"], T["U"], obs))
+    h = torch.bmm(delta[:, None, :], Lm)[:, 0]
+    q = mlp(T["V"], T["V"], obs)[:, 0] - 0.5 * (h * h).sum(1)
+    sq = sum((T[w][k] ** 2).sum() for w in ref.NETS for k in ref.PLAIN)
+    loss = ((q - y) ** 2).mean() + l2norm * 0.5 * sq
+    np.testing.assert_allclose(fw["q"], q.detach().numpy(), rtol=1e-12)
+    for w in ref.NETS:
+        auto = torch.autograd.grad(loss, [T[w][k] for k in ref.NAMES], retain_graph=True)
+        want = np.concatenate([x.numpy().reshape(-1) for x in auto])
+        decay = np.concatenate([l2norm * ref.flat(ref.f64(nets[w]), ref.PLAIN), np.zeros(dimO + l1 + l2)])
+        assert np.abs(want).max() > 1e-3
+        np.testing.assert_allclose(d["g" + w] + decay, want, rtol=1e-9, atol=1e-13)
+        # a bias in front of a BatchNorm cancels: its gradient is zero but for the sum's rounding
+        assert np.abs(d["b1" + w]).max() < 1e-14 and np.abs(d["b2" + w]).max() < 1e-14
+        # so does beta0, which meets BN1 through a linear layer: the column sums of dz1 are zero
+        assert np.abs(d["beta0" + w]).max() < 1e-14
+        assert np.abs(d["beta1" + w]).max() > 1e-6 and np.abs(d["beta2" + w]).max() > 1e-6
+    assert abs(ref.loss_q(nets, fw, l2norm) - loss.item()) < 1e-13
+
+
+def test_new_exports_declared_and_abi():
+    lib = _lib.load()
+    header = open(os.path.join(REPO, "include", "icnn_be.h")).read()
+    for name in NEW_EXPORTS:
+        assert re.search(r"ICNN_BE_API\s+(int|size_t)\s+%s\s*\(" % name, header), name
+        assert name in _lib.EXPORTS and hasattr(lib, name)
+    assert lib.icnn_be_abi_version() == 12 and "#define ICNN_BE_ABI_VERSION 12" in header
+    assert lib.icnn_be_struct_size(20) == C.sizeof(_lib.NafBnArgs) > C.sizeof(_lib.NafArgs)
+    assert all(lib.icnn_be_struct_size(i) == 0 for i in (12, 15, 17, 19, 21))
+    for name, value in (("MAX_BATCH", MAXB), ("PASSES", len(_lib.NAF_BN_PASSES)), ("VARS", len(_lib.NAF_BN_VARS)),
+                        ("WORK_PIECES", len(_lib.NAF_BN_WORK))):
+        assert "#define ICNN_BE_NAF_BN_%s %d" % (name, value) in header
+    assert MAXB >= 256
+    at = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define ICNN_BE_NAF_BN_W_(\w+) (\d+)\b", header)}
+    for i, piece in enumerate(_lib.NAF_BN_WORK):
+        base = piece.upper() if piece.upper() in at else piece[:-1].upper()
+        assert at[base] + ("luvt".index(piece[-1]) if base != piece.upper() else 0) == i, piece
+
+
+def test_layout_and_flatten_round_trip():
+    lib = _lib.load()
+    for dims in ((376, 17, 600, 600), (1, 1, 1, 1), (17, 6, 200, 200), (3, 2, 5, 7)):
+        spec = naf.NAFSpec(*dims)
+        n = [C.c_longlong() for _ in range(5)]
+        assert lib.icnn_be_naf_bn_param_floats(*dims, *[C.byref(x) for x in n]) == 0
+        S = dims[0] + dims[2] + dims[3]
+        assert [x.value for x in n] == [naf.n_floats(spec, w, bn=True) for w in W] + [naf.n_floats(spec, "v"), 2 * S]
+        assert naf.n_floats(spec, "u", bn=True) == naf.n_floats(spec, "u") + S
+        for i, w in enumerate(W):
+            off = (C.c_longlong * len(_lib.NAF_BN_VARS))()
+            assert lib.icnn_be_naf_bn_layout(*dims, i, C.byref(off)) == 0
+            lay = naf.layout(spec, w, bn=True)
+            assert [name for name, _ in lay] == _lib.NAF_BN_VARS
+            assert list(off) == list(np.cumsum([0] + [int(np.prod(s)) for _, s in lay])[:-1])
+        off = (C.c_longlong * len(_lib.NAF_BN_WORK))()
+        assert lib.icnn_be_naf_bn_work_offsets(MAXB, *dims, C.byref(off)) == 0
+        off = list(off)
+        assert off[0] == 0 and all(b >= a for a, b in zip(off, off[1:])) and all(o % 4 == 0 for o in off)
+        assert lib.icnn_be_naf_bn_work_bytes(MAXB, *dims) >= 4 * off[-1] + 8
+    spec = naf.NAFSpec(3, 2, 5, 7)
+    rng = np.random.RandomState(0)
+    for w in W:
+        net = {name: rng.randn(*shape).astype(np.float32) for name, shape in naf.layout(spec, w, bn=True)}
+        vec = naf.flatten(spec, w, net, bn=True)
+        assert vec.shape == (naf.n_floats(spec, w, bn=True),)
+        assert np.array_equal(vec[:naf.n_floats(spec, w)], naf.flatten(spec, w, net))       # the betas lie behind NAF's vector
+        back = naf.unflatten(spec, w, vec, bn=True)
+        assert list(back) == _lib.NAF_BN_VARS and all(np.array_equal(back[k], net[k]) for k in net)
+    assert [name for name, _ in naf.moving_layout(spec)] == ["mean0", "var0", "mean1", "var1", "mean2", "var2"]
+
+
+def _fake_args(**kw):
+    """a descriptor of pointers that are never followed: every entry must refuse it before a launch"""
+    a = _lib.NafBnArgs()
+    a.batch, a.dimO, a.dimA, a.l1, a.l2 = 4, 3, 1, 5, 7
+    for i, (name, _) in enumerate(f for f in _lib.NafBnArgs._fields_ if f[1] is C.c_void_p):
+        setattr(a, name, 4096 * (i + 1))
+    a.rate, a.beta1, a.beta2, a.bn_decay = 1e-3, 0.9, 0.999, 0.999
+    a.eps, a.tau, a.discount, a.l2norm, a.bn_eps = 1e-4, 0.01, 0.99, 1e-4, 1e-3
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_invalid_arguments_are_refused_before_a_launch():
+    lib = _lib.load()
+    entries = [lib.icnn_be_naf_bn_chain, lib.icnn_be_naf_bn_grads, lib.icnn_be_naf_bn_update, lib.icnn_be_naf_bn_step]
+    bad = [dict(batch=0), dict(batch=-3), dict(batch=MAXB + 1), dict(dimO=0), dict(dimO=_lib.NAF_MAX_OBS + 1), dict(dimA=0),
+           dict(dimA=_lib.NAF_MAX_ACT + 1), dict(l1=0), dict(l1=_lib.NAF_MAX_HIDDEN + 1), dict(l2=-1),
+           dict(l2=_lib.NAF_MAX_HIDDEN + 1), dict(tau=1.5), dict(discount=float("nan")), dict(l2norm=-1.0), dict(beta1=1.0),
+           dict(eps=0.0), dict(rate=float("inf")), dict(bn_eps=0.0), dict(bn_eps=float("nan")), dict(bn_decay=1.5),
+           dict(bn_decay=-0.1)]
+    pointers = [name for name, kind in _lib.NafBnArgs._fields_ if kind is C.c_void_p]
+    bad += [{name: None} for name in pointers if name != "loss"]
+    bad += [{name: 4096 + 4} for name in ("theta_l", "theta_u", "theta_v", "target_v", "m_v", "grad_u", "work")]
+    bad += [{name: 4096 + 2} for name in ("obs", "rew", "ob2", "step", "loss", "mv_l", "mv_u", "mv_v")]
+    for kw in bad:
+        for fn in entries:
+            assert fn(C.byref(_fake_args(**kw)), None) == -1, kw
+    for fn in entries:
+        assert fn(None, None) == -1
+        assert fn(C.byref(_fake_args()), C.c_void_p(4)) == -1           # a misaligned stream
+    assert lib.icnn_be_naf_bn_step(C.byref(_fake_args(loss=None)), None) == -1
+    assert lib.icnn_be_naf_bn_work_bytes(0, 3, 1, 5, 7) == 0 and lib.icnn_be_naf_bn_work_bytes(MAXB + 1, 3, 1, 5, 7) == 0
+    assert lib.icnn_be_naf_bn_work_bytes(MAXB, 3, 1, 5, 7) > 0 and lib.icnn_be_naf_bn_work_bytes(1, 3, 1, 5, 601) == 0
+    eps = C.c_float(1e-3)
+
+    def act(dims=(3, 1, 5, 7), ptr=(4096, 8192), bn_eps=eps, mode=1, obs=12288, batch=4, out=16384, work=20480, stream=None):
+        return lib.icnn_be_naf_bn_act(*dims, *ptr, bn_eps, mode, obs, batch, out, work, stream)
+
+    def q(dims=(3, 1, 5, 7), ptr=tuple(4096 * (i + 1) for i in range(6)), bn_eps=eps, mode=0, obs=4096 * 7, a=4096 * 8, batch=4,
+          out=4096 * 9, work=4096 * 10, stream=None):
+        return lib.icnn_be_naf_bn_q(*dims, *ptr, bn_eps, mode, obs, a, batch, out, work, stream)
+
+    for fn, n_ptr in ((act, 2), (q, 6)):
+        for kw in (dict(batch=0), dict(batch=MAXB + 1), dict(dims=(3, 1, 5, 601)), dict(dims=(0, 1, 5, 7)), dict(dims=(3, 33, 5, 7)),
+                   dict(mode=2), dict(mode=-1), dict(obs=None), dict(out=None), dict(work=None), dict(work=4096 + 4),
+                   dict(bn_eps=C.c_float(0.0)), dict(stream=C.c_void_p(4))):
+            assert fn(**kw) == -1, kw
+        for i in range(n_ptr):
+            good = [4096 * (k + 1) for k in range(n_ptr)]
+            assert fn(ptr=tuple(None if k == i else p for k, p in enumerate(good))) == -1
+            assert fn(ptr=tuple(p + 2 if k == i else p for k, p in enumerate(good))) == -1
+    assert q(a=None) == -1 and q(a=4096 * 8 + 4) == -1
+
+
+def test_initial_state_and_load_on_the_host():
+    """a fresh trainer: betas 0, moving means 0, moving variances 1, the W of NAFTrainer() at the same seed (no launch: CPU)"""
+    tr = naf.NAFTrainer(3, 2, 5, 7, batch=4, seed=5, device="cpu", bn=True)
+    plain = naf.init_params(3, 2, 5, 7, seed=5)
+    for w in W:
+        net = tr.host_params(w)
+        assert list(net) == _lib.NAF_BN_VARS
+        assert all(np.array_equal(net[k], plain[w][k]) for k in plain[w])
+        assert all(not net["beta%d" % i].any() for i in range(3))
+        mv = tr.host_moving(w)
+        assert all(not mv["mean%d" % i].any() and np.all(mv["var%d" % i] == 1.0) for i in range(3))
+        assert mv["mean0"].shape == (3,) and mv["var1"].shape == (5,) and mv["var2"].shape == (7,)
+    target = tr.host_params("target_v")
+    assert list(target) == list(plain["v"]) and all(np.array_equal(target[k], plain["v"][k]) for k in target)
+    assert tr.theta["target_v"].numel() == naf.n_floats(tr.spec, "v") == tr.n["v"] - 15
+    # a flat v carries its betas; the target that follows it takes W and b alone
+    vec = np.arange(tr.n["v"], dtype=np.float32)
+    tr.load(v=vec)
+    assert np.array_equal(tr.theta["target_v"].numpy(), vec[:tr.n["v"] - 15])
+    assert np.array_equal(tr.host_params("v")["beta2"], vec[-7:])
+    with pytest.raises(ValueError):
+        naf.NAFTrainer(3, 2, 5, 7, batch=MAXB + 1, device="cpu", bn=True)
+    assert not naf.NAFTrainer(3, 2, 5, 7, batch=4, device="cpu").bn
+
+
+@pytest.mark.parametrize("shape", SMALL)
+def test_small_shapes_have_no_ambiguous_unit(shape):
+    """the precondition of the exact mask comparison: no BatchNorm output of the small shapes lies below its own bound"""
+    r = _reference(shape)
+    p, ambiguous = r[3], r[9]
+    assert not any(a.any() for a in ambiguous.values())
+    margin = ref.margin(p)
+    print("smallest |o| / bound %.4g" % margin)
+    assert margin > 2 and abs(margin / MARGIN[shape] - 1) < 0.01
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+
+
+def _trainer(shape, seed=None, **kw):
+    """a NAFTrainer(bn=True) at `shape` holding the test's nets, non-trivial moving pairs and the minibatch"""
+    B, dimO, dimA, l1, l2 = shape
+    seed = SEED.get(shape, 0) if seed is None else seed
+    nets, target = _nets(shape, seed)
+    tr = naf.NAFTrainer(dimO, dimA, l1, l2, batch=B, discount=DISCOUNT, bn=True, **kw)
+    tr.load(l=nets["L"], u=nets["U"], v=nets["V"], target_v=target)
+    tr.load_moving(**{w.lower(): m for w, m in ref.moving_stats(dimO, l1, l2, seed).items()})
+    obs, act, rew, ob2, term = naf_ref.batch(B, dimO, dimA, seed)
+    for dst, src in ((tr.obs, obs), (tr.act, act), (tr.rew, rew), (tr.ob2, ob2), (tr.term, term)):
+        dst.copy_(torch.from_numpy(src))
+    return tr
+
+
+def _host(t):
+    return t.cpu().numpy().astype(np.float64)
+
+
+def _within(name, got, want, bound):
+    bound = np.broadcast_to(bound, want.shape)
+    err = np.abs(got - want)
+    assert got.shape == want.shape and err.size
+    worst = np.unravel_index(np.argmax(err / np.maximum(bound, 1e-300)), err.shape)
+    print("%s: largest error / bound %.3g (error %.3e, bound %.3e)" % (name, err[worst] / max(bound[worst], 1e-300), err[worst],
+                                                                      bound[worst]))
+    assert np.all(np.isfinite(got)) and np.all(err <= bound), "%s: error %.3e beyond its bound %.3e at %s" % (
+        name, err[worst], bound[worst], worst)
+
+
+def _stats(tr, p):
+    """{site: (mu, var)} of pass p from the device's workspace"""
+    s = tr.spec
+    return naf._flat.unflatten(naf.moving_layout(s), tr.work_view("stat" + p).cpu().numpy())
+
+
+def _betas_grad(tr, w):
+    s = tr.spec
+    return tr.grad[w].cpu().numpy()[naf.n_floats(s, w):]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_chain_against_the_reference(shape):
+    B, dimO, dimA, l1, l2 = shape
+    nets, target, mb, p, fw, bound_fw, _, _, own, ambiguous = _reference(shape)
+    tr = _trainer(shape)
+    tr.work.view(torch.int32).fill_(0x7fc0beef)                 # a NaN
+    for w in W:
+        tr.grad[w].fill_(float("nan"))
+    tr.chain()
+    torch.cuda.synchronize()
+    work = tr.work.cpu().numpy().view(np.uint32)
+    # nothing outside the B rows of each piece is written
+    written = np.zeros(work.size, bool)
+    for name in _lib.NAF_BN_WORK[:_lib.NAF_BN_WORK.index("upd")]:
+        if name in ("xh1t", "xh2t"):
+            continue                                            # empty: the target pass has no backward
+        v = tr.work_view(name)
+        at = tr.work_offsets[name]
+        written[at:at + v.numel() * (2 if name == "sq" else 1)] = True
+    assert np.all(work[~written] == 0x7fc0beef) and (~written).sum() > 0
+    assert not np.any(work[written] == 0x7fc0beef)
+    # ---- forward: (mu, var) of the twelve sites, the activations, the head ----
+    for pw in "LUVT":
+        v, e = p[pw]
+        st = _stats(tr, pw.lower())
+        for i in range(3):
+            _within("mu%d%s" % (i, pw), st["mean%d" % i].astype(np.float64), v["mu%d" % i], e["mu%d" % i])
+            _within("var%d%s" % (i, pw), st["var%d" % i].astype(np.float64), v["var%d" % i], e["var%d" % i])
+            _within("h%d%s" % (i, pw), _host(tr.work_view("h%d%s" % (i, pw.lower()))), v["h%d" % i], e["h%d" % i])
+            if i and pw != "T":
+                _within("xh%d%s" % (i, pw), _host(tr.work_view("xh%d%s" % (i, pw.lower()))), v["xh%d" % i], e["xh%d" % i])
+        if B == 1:                                              # the degenerate batch: var = 0 and a site's output is beta
+            assert all(not st["var%d" % i].any() for i in range(3))
+            betas = nets["V" if pw == "T" else pw]
+            assert np.array_equal(tr.work_view("h0" + pw.lower()).cpu().numpy()[0], betas["beta0"])
+            assert np.array_equal(tr.work_view("h2" + pw.lower()).cpu().numpy()[0], np.maximum(betas["beta2"], 0))
+    for name in ("y", "u", "l", "ld", "h", "adv", "q", "td"):
+        got = _host(tr.work_view(name))
+        _within(name, got if fw[name].ndim == 2 else got[:, 0], fw[name], bound_fw[name])
+    sq = tr.work_view("sq").cpu().numpy()
+    td32 = tr.work_view("td").cpu().numpy()[:, 0].astype(np.float64)
+    np.testing.assert_allclose(sq, [np.sum(td32[i:i + 16] ** 2) for i in range(0, B, 16)], rtol=17 * 2.0 ** -53, atol=0)
+    # ---- the masks: the reference's everywhere except at ambiguous units (the small shapes have none) ----
+    dev_masks = {k + w: (_host(tr.work_view(k + w.lower())) > 0).astype(np.float64) for k in ("h1", "h2") for w in ref.NETS}
+    n_ambiguous = sum(int(a.sum()) for a in ambiguous.values())
+    flips = sum(int((dev_masks[k] != own[k]).sum()) for k in own)
+    print("ambiguous units: %d of %d; mask flips: %d" % (n_ambiguous, sum(a.size for a in ambiguous.values()), flips))
+    if shape in SMALL:
+        assert n_ambiguous == 0 and flips == 0
+    for k in dev_masks:
+        assert np.array_equal(dev_masks[k][~ambiguous[k]], own[k][~ambiguous[k]]), k
+    # ---- backward at the device's masks: the three deltas per net and the nine d beta ----
+    _, _, _, d, bound_d, _, _ = ref.reference_step(nets, target, mb, DISCOUNT, masks=dev_masks)
+    for w in ref.NETS:
+        lw = w.lower()
+        _within("d3" + w, _host(tr.work_view("d3" + lw)), d["d3" + w], bound_d["d3" + w])
+        _within("dz2" + w, _host(tr.work_view("d2" + lw)), d["dz2" + w], bound_d["dz2" + w])
+        _within("dz1" + w, _host(tr.work_view("d1" + lw)), d["dz1" + w], bound_d["dz1" + w])
+        got = _betas_grad(tr, lw).astype(np.float64)
+        want = np.concatenate([d["beta%d" % i + w] for i in range(3)])
+        assert np.abs(want).max() > 1e-7
+        _within("dbeta" + w, got, want, np.concatenate([bound_d["beta%d" % i + w] for i in range(3)]))
+        assert np.all(np.isnan(tr.grad[lw].cpu().numpy()[:naf.n_floats(tr.spec, lw)]))      # the chain leaves W and b to grads()
+    g3 = tr.work_view("d3l").cpu().numpy().reshape(B, dimA, dimA)
+    assert not g3[:, np.triu(np.ones((dimA, dimA), bool), 1)].any()      # the upper triangle: exactly zero
+    if shape in WIDE:                                           # here the end-to-end bounds are below the quantities
+        for name, want, bound in [("q", fw["q"], bound_fw["q"]), ("td", fw["td"], bound_fw["td"])] + [
+                (k + w, d[k + w], bound_d[k + w]) for w in ref.NETS for k in ("dz2", "beta2", "W2", "W3")]:
+            ratio = float(np.median(bound / np.maximum(np.abs(want), 1e-300)))
+            print("%s: median bound / |value| %.3g" % (name, ratio))
+            assert ratio < 0.5, name
+    # ---- the eighteen weight and bias gradients against the reference (b1 and b2: the absolute bound of a sum that cancels) ----
+    tr.grads()
+    torch.cuda.synchronize()
+    for w in ref.NETS:
+        n = naf.n_floats(tr.spec, w.lower())
+        _within("g" + w, tr.grad[w.lower()].cpu().numpy().astype(np.float64)[:n], d["g" + w][:n], bound_d["g" + w][:n])
+
+
+def _sharp(name, want, bound, B):
+    """a stage's own rounding bound must say something: below 5 % of the quantity at the median, where a batch can have one"""
+    ratio = float(np.median(np.broadcast_to(bound, want.shape) / np.maximum(np.abs(want), 1e-300)))
+    print("%s: median bound / |value| %.3g" % (name, ratio))
+    assert B < 8 or ratio < 0.05, name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_layers_from_the_devices_own_operands(shape):
+    """Every launch of the chain against the reference applied to what that launch read from the workspace, so that each
+    bound is one stage's rounding and stays sharp at every shape: the two hidden layers of the four passes, layer 3 with y and
+    the head, the head's backward, BN2's and BN1's backward and d beta0."""
+    B, dimO, dimA, l1, l2 = shape
+    tr = _trainer(shape)
+    for w in W:
+        tr.grad[w].fill_(float("nan"))
+    tr.chain()
+    torch.cuda.synchronize()
+    nets = {w.upper(): tr.host_params(w) for w in W}
+    target = tr.host_params("target_v")
+    mb = naf_ref.batch(B, dimO, dimA, SEED[shape])
+    view = {n: _host(tr.work_view(n)) for n in _lib.NAF_BN_WORK if n not in ("sq", "upd", "xh1t", "xh2t")}
+    # ---- forward: a layer from the device's own input ----
+    out, eout = {}, {}
+    for pw in "LUVT":
+        p, N, betas = pw.lower(), (target if pw == "T" else nets[pw]), nets["V" if pw == "T" else pw]
+        st = _stats(tr, p)
+        for i in (1, 2):
+            v, e = ref.stage_forward(view["h%d%s" % (i - 1, p)], N["W%d" % i], N["b%d" % i], betas["beta%d" % i])
+            tag = "%d%s" % (i, pw)
+            _within("mu" + tag, st["mean%d" % i].astype(np.float64), v["mu"], e["mu"])
+            _within("var" + tag, st["var%d" % i].astype(np.float64), v["var"], e["var"])
+            if pw != "T":
+                _within("xh" + tag, view["xh%d%s" % (i, p)], v["xh"], e["xh"])
+                if B > 1:
+                    _sharp("xh" + tag, v["xh"], e["xh"], B)
+            _within("h" + tag, view["h%d%s" % (i, p)], v["h"], e["h"])
+        out[pw], eout[pw] = ref.stage_output(view["h2" + p], N["W3"], N["b3"])
+    # ---- layer 3, y, the head and its backward from the device's own h2 ----
+    fw, e = ref.head_from_outputs(out, eout, mb, DISCOUNT)
+    for name in ("y", "u", "l", "ld", "h", "adv", "q", "td"):
+        _within(name, view[name] if fw[name].ndim == 2 else view[name][:, 0], fw[name], e[name])
+    _sharp("q", fw["q"], e["q"], B)
+    _sharp("td", fw["td"], e["td"], B)
+    d3, ed3 = ref.head_backward(nets, fw, e)
+    for pw in "LUV":
+        _within("d3" + pw, view["d3" + pw.lower()], d3["d3" + pw], ed3["d3" + pw])
+    _sharp("d3V", d3["d3V"], ed3["d3V"], B)
+    # ---- backward: a site from the delta above it, the stored activation's sign, the stored xhat and variance ----
+    for pw in "LUV":
+        p, N = pw.lower(), nets[pw]
+        st = _stats(tr, p)
+        got_beta = _betas_grad(tr, p).astype(np.float64)
+        for i in (2, 1):
+            v, e = ref.stage_backward(view["d%d%s" % (i + 1, p)], N["W%d" % (i + 1)], view["h%d%s" % (i, p)] > 0,
+                                      view["xh%d%s" % (i, p)], st["var%d" % i])
+            tag = "%d%s" % (i, pw)
+            _within("dz" + tag, view["d%d%s" % (i, p)], v["dz"], e["dz"])
+            at = dimO if i == 1 else dimO + l1
+            _within("dbeta" + tag, got_beta[at:at + v["dbeta"].size], v["dbeta"], e["dbeta"])
+            if B > 2:                                           # (a batch of two has dz = 0 but for eps)
+                _sharp("dz" + tag, v["dz"], e["dz"], B)
+                _sharp("dbeta" + tag, v["dbeta"], e["dbeta"], B)
+                assert np.abs(v["dz"]).max() > 1e-6
+        D1, W1 = view["d1" + p], np.asarray(N["W1"], np.float64)
+        dh0 = D1 @ W1.T                                         # its column sums cancel: an absolute bound
+        edh0 = ref.e_matmul(D1, np.zeros_like(D1), W1.T, None)
+        _within("dbeta0" + pw, got_beta[:dimO], dh0.sum(0), ref.e_rowsum(dh0, edh0))
+
+
+@pytest.mark.gpu
+def test_constant_column_has_zero_variance_and_xhat():
+    shape = (33, 3, 3, 20, 12)
+    tr = _trainer(shape)
+    tr.obs[:, 1] = 0.3                                          # not a dyadic number: its sum over 33 rows rounds
+    tr.ob2[:, 2] = -0.7
+    tr.chain()
+    tr.grads()
+    torch.cuda.synchronize()
+    for pw, col, value in (("l", 1, 0.3), ("u", 1, 0.3), ("v", 1, 0.3), ("t", 2, -0.7)):
+        st = _stats(tr, pw)
+        assert st["var0"][col] == 0.0 and st["mean0"][col] == np.float32(value)
+        beta0 = tr.host_params("v" if pw == "t" else pw)["beta0"]
+        assert np.all(tr.work_view("h0" + pw).cpu().numpy()[:, col] == beta0[col])      # xhat exactly 0
+    names = [n for n in _lib.NAF_BN_WORK if n not in ("xh1t", "xh2t", "upd", "sq")]
+    assert all(torch.isfinite(tr.work_view(n)).all() for n in names)
+    assert all(torch.isfinite(tr.grad[w]).all() for w in W)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", SHAPES)
+def test_weight_gradients_from_the_devices_own_operands(shape):
+    B = shape[0]
+    tr = _trainer(shape)
+    tr.chain()
+    tr.grads()
+    torch.cuda.synchronize()
+    got = {w: tr.grad[w].cpu().numpy() for w in W}
+    for w in W:
+        X = [_host(tr.work_view(k + w)) for k in ("h0", "h1", "h2")]
+        D = [_host(tr.work_view(k + w)) for k in ("d1", "d2", "d3")]
+        want = np.concatenate([np.concatenate([(x.T @ dd).reshape(-1), dd.sum(0)]) for x, dd in zip(X, D)])
+        mag = np.concatenate([np.concatenate([(np.abs(x).T @ np.abs(dd)).reshape(-1), np.abs(dd).sum(0)]) for x, dd in zip(X, D)])
+        assert np.abs(want).max() > 1e-6
+        _within("g_" + w, got[w][:want.size].astype(np.float64), want, B * ref.U * mag)       # one chain of B fma per element
+    # a second run gives the same bits
+    for w in W:
+        tr.grad[w].fill_(7.0)
+    tr.chain()
+    tr.grads()
+    torch.cuda.synchronize()
+    for w in W:
+        assert np.array_equal(tr.grad[w].cpu().numpy().view(np.uint32), got[w].view(np.uint32)), w
+
+
+def _state(tr):
+    out = {w: tr.theta[w] for w in naf.NETS}
+    for w in W:
+        out["m_" + w], out["v_" + w], out["mv_" + w] = tr.m[w], tr.v[w], tr.mv[w]
+    return out
+
+
+def _snapshot(tr):
+    return {k: t.cpu().numpy().copy() for k, t in _state(tr).items()}
+
+
+def _expected_update(tr, before, g, t):
+    """update32 of the three nets from the state `before`, the device's gradients and the ONE step count after the update: W and
+    b with the decay term, the betas without; only V has a target, of its W and b"""
+    out = {}
+    for w in W:
+        n = naf.n_floats(tr.spec, w)
+        parts = []
+        for sl, k in ((slice(0, n), tr.l2norm), (slice(n, None), 0.0)):
+            target = before["target_v"] if w == "v" and sl.start == 0 else np.zeros_like(before[w][sl])     # else: dropped
+            parts.append(naf_ref.update32(before[w][sl], before["m_" + w][sl], before["v_" + w][sl], target, g[w][sl], t, tr.rate, k,
+                                          tr.tau))
+        out.update({w: np.concatenate([parts[0][0], parts[1][0]]), "m_" + w: np.concatenate([parts[0][1], parts[1][1]]),
+                    "v_" + w: np.concatenate([parts[0][2], parts[1][2]])})
+        if w == "v":
+            out["target_v"] = parts[0][3]
+    return out
+
+
+def _expected_fold(tr, before):
+    """the float32 fold of the device's own (mu, var): L and U once, V twice in the order obs, ob2"""
+    stat = {p: tr.work_view("stat" + p).cpu().numpy() for p in "luvt"}
+    return {"mv_l": ref.fold32(before["mv_l"], stat["l"], tr.bn_decay), "mv_u": ref.fold32(before["mv_u"], stat["u"], tr.bn_decay),
+            "mv_v": ref.fold32(ref.fold32(before["mv_v"], stat["v"], tr.bn_decay), stat["t"], tr.bn_decay)}
+
+
+def _same_bits(got, want):
+    for k in want:
+        assert np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(33, 3, 3, 20, 12), (2, 3, 1, 5, 7), WIDE[0], SHIPPED])
+def test_three_whole_steps_eager_and_captured(shape):
+    B, dimO, dimA, l1, l2 = shape
+    kw = dict(l2norm=1e-2, rate=1e-3, tau=0.05)
+    tr = _trainer(shape, **kw)
+    mb = naf_ref.batch(B, dimO, dimA, SEED[shape])
+    eager = []
+    for t in (1, 2, 3):
+        before = _snapshot(tr)
+        nets = {w.upper(): tr.host_params(w) for w in W}
+        target = tr.host_params("target_v")
+        loss = tr.step_buffers()
+        torch.cuda.synchronize()
+        g = {w: tr.grad[w].cpu().numpy() for w in W}
+        after = _snapshot(tr)
+        want = _expected_update(tr, before, g, t)
+        want.update(_expected_fold(tr, before))
+        _same_bits(after, want)
+        assert tr.t == t
+        _, fw, bound_fw, _, _, _, _ = ref.reference_step(nets, target, mb, DISCOUNT)
+        want_loss = ref.loss_q(nets, fw, kw["l2norm"])
+        bound = bound_fw["loss_td"] + 2 * ref.U * want_loss     # td's own error, then float64 sums rounded to float32 once
+        print("loss_q %.9g, reference %.9g, bound %.3e" % (loss.item(), want_loss, bound))
+        assert abs(loss.item() - want_loss) <= bound
+        eager.append((after, loss.item()))
+    assert all(not np.array_equal(eager[0][0][k], eager[2][0][k]) for k in eager[0][0])
+    # a captured step replayed three times: a warm-up step outside the graph, undone, then the capture
+    cap, fresh = _trainer(shape, **kw), _trainer(shape, **kw)
+    cap.step_buffers()
+    torch.cuda.synchronize()
+    for dst, src in zip(_state(cap).values(), _state(fresh).values()):
+        dst.copy_(src)
+    cap.step_count.zero_()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = cap.step_buffers().clone()
+    for after, loss in eager:
+        g.replay()
+        torch.cuda.synchronize()
+        _same_bits(_snapshot(cap), after)
+        assert np.float32(out.item()).view(np.uint32) == np.float32(loss).view(np.uint32)
+    assert cap.t == 3
+
+
+@pytest.mark.gpu
+def test_update_leaves_the_betas_out_of_decay_loss_and_target():
+    shape = (20, 11, 5, 33, 18)
+    losses = []
+    for scale in (1.0, 3.0):
+        tr = _trainer(shape, l2norm=0.5, rate=1e-3, tau=0.3)
+        n = {w: naf.n_floats(tr.spec, w) for w in W}
+        for w in W:
+            tr.theta[w][n[w]:] *= scale
+        tr.chain()
+        tr.grads()
+        for w in W:                                             # a zero gradient: only a decay term could move a parameter
+            tr.grad[w].zero_()
+        before = _snapshot(tr)
+        tr.update()
+        torch.cuda.synchronize()
+        after = _snapshot(tr)
+        for w in W:
+            assert np.array_equal(after[w][n[w]:], before[w][n[w]:]), w         # the betas: no decay
+            assert np.all(after[w][:n[w]] != before[w][:n[w]])                     # W and b: decay
+        _same_bits(after, _expected_update(tr, before, {w: np.zeros_like(before[w]) for w in W}, 1))
+        assert after["target_v"].size == n["v"]                 # the EMA of the new V's W and b, nothing of the betas
+        td = tr.work_view("td").cpu().numpy()[:, 0].astype(np.float64)
+        losses.append(tr.loss.item() - np.mean(td ** 2))
+        reg = 0.5 * 0.5 * sum(np.sum(before[w][:n[w]].astype(np.float64) ** 2) for w in W)
+        assert abs(losses[-1] - reg) <= 4 * ref.U * tr.loss.item()
+    assert abs(losses[0] - losses[1]) <= 8 * ref.U * (abs(losses[0]) + 1.0)      # the betas, scaled, are not in the sum of squares
+
+
+@pytest.mark.gpu
+def test_every_entry_is_capturable():
+    tr = _trainer((17, 5, 2, 16, 16))
+    tr.step_buffers()
+    u, q = tr.policy(tr.obs), tr.q(tr.obs, tr.act)              # warm-up: the workspaces of policy and q exist
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        tr.chain()
+        tr.grads()
+        tr.update()
+        tr.step_buffers()
+        for mode in ("moving", "batch"):
+            tr.policy(tr.obs, out=u, bn=mode)
+            tr.q(tr.obs, tr.act, bn=mode)
+    t = tr.t
+    g.replay()
+    torch.cuda.synchronize()
+    assert tr.t == t + 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(17, 5, 2, 16, 16), (20, 11, 5, 33, 18), (1, 3, 1, 5, 7)] + WIDE + [SHIPPED])
+def test_policy_and_q_in_both_modes(shape):
+    B, dimO, dimA, l1, l2 = shape
+    nets, target, mb = _reference(shape)[:3]
+    tr = _trainer(shape)
+    stats = ref.moving_stats(dimO, l1, l2, SEED[shape])
+    _, fw, e = ref.step_forward(nets, target, mb, DISCOUNT, stats=stats)
+    u, q = tr.policy(tr.obs), tr.q(tr.obs, tr.act)
+    torch.cuda.synchronize()
+    _within("u moving", _host(u), fw["u"], e["u"])
+    _within("q moving", _host(q), fw["q"], e["q"])
+    # rows are independent in moving mode: the first rows alone give the same bits
+    k = max(1, B // 2)
+    u2, q2 = tr.policy(tr.obs[:k].contiguous()), tr.q(tr.obs[:k].contiguous(), tr.act[:k].contiguous())
+    assert torch.equal(u2, u[:k]) and torch.equal(q2, q[:k])
+    # batch mode is the chain's forward
+    tr.chain()
+    ub, qb = tr.policy(tr.obs, bn="batch"), tr.q(tr.obs, tr.act, bn="batch")
+    assert torch.equal(ub, tr.work_view("u")) and torch.equal(qb, tr.work_view("q")[:, 0])
+    # with the moving pairs set to this batch's own statistics, moving mode agrees with batch mode within both bounds
+    own = {w: _stats(tr, w) for w in W}
+    tr.load_moving(**own)
+    um, qm = tr.policy(tr.obs), tr.q(tr.obs, tr.act)
+    torch.cuda.synchronize()
+    _, fw_b, e_b = ref.step_forward(nets, target, mb, DISCOUNT)
+    _, fw_m, e_m = ref.step_forward(nets, target, mb, DISCOUNT, stats={w.upper(): own[w] for w in W})
+    gap_u = np.abs(fw_b["u"] - fw_m["u"]) + e_b["u"] + e_m["u"]          # the references differ by the statistics' rounding
+    gap_q = np.abs(fw_b["q"] - fw_m["q"]) + e_b["q"] + e_m["q"]
+    _within("u moving = batch", _host(um), _host(ub), gap_u)
+    _within("q moving = batch", _host(qm), _host(qb), gap_q)
+
+
+@pytest.mark.gpu
+def test_defaults_keep_their_bits_next_to_a_bn_trainer():
+    def plain():
+        tr = naf.NAFTrainer(5, 2, 16, 12, batch=17, seed=2, initstd=0.3)
+        obs, act, rew, ob2, term = naf_ref.batch(17, 5, 2, 1)
+        for _ in range(2):
+            tr.step(obs, act, rew, ob2, term)
+        torch.cuda.synchronize()
+        assert not tr.bn and not hasattr(tr, "mv")
+        with pytest.raises(ValueError):                         # a plain trainer has no mode to choose
+            tr.policy(tr.obs, bn="batch")
+        with pytest.raises(ValueError):
+            tr.q(tr.obs, tr.act, bn="moving")
+        return {k: t.cpu().numpy().copy() for k, t in list(tr.theta.items()) + [("loss", tr.loss.reshape(1))]}
+
+    first = plain()
+    bn = _trainer((17, 5, 2, 16, 16))
+    for _ in range(2):
+        bn.step_buffers()
+    bn.policy(bn.obs)
+    torch.cuda.synchronize()
+    _same_bits(plain(), first)
+
+
+# ---- the agent ----
+
+EPISODE_STEPS, EPISODE_ENDS, WARMUP = 40, (13, 27), 8
+
+
+def _script(dimO):
+    """the scripted environment: observation t + 1 and the reward depend on the step and on the action taken"""
+    rng = np.random.RandomState(11)
+    base = rng.uniform(-1, 1, (EPISODE_STEPS + 1, dimO)).astype(np.float32)
+
+    def next_obs(t, action):
+        return (0.8 * base[t + 1] + 0.2 * np.float32(np.tanh(action.sum()))).astype(np.float32)
+
+    return base, next_obs
+
+
+def _agent(capture, seed=3):
+    return rl_agent.NAFAgent(5, 3, l1=16, l2=12, bsize=16, warmup=WARMUP, iters=2, rmsize=64, seed=seed, capture=capture, tau=0.05,
+                             l2norm=1e-3, initstd=0.3, naf_bn=True)
+
+
+def _run(agent, first, last):
+    """steps first .. last - 1 of the scripted episode; an episode ends after the steps of EPISODE_ENDS"""
+    base, next_obs = _script(agent.dimO)
+    actions = []
+    if first == 0:
+        agent.reset(base[0])
+    for t in range(first, last):
+        action = agent.act()
+        actions.append(action.copy())
+        term = t in EPISODE_ENDS
+        agent.observe(float(np.cos(t) - np.abs(action).sum()), term, next_obs(t, action))
+        if term:
+            agent.reset(base[t + 1])
+    return np.array(actions)
+
+
+def _agent_state(agent):
+    torch.cuda.synchronize()
+    out = _snapshot(agent.trainer)
+    out["step"] = agent.trainer.step_count.cpu().numpy()
+    out["loss"] = np.atleast_1d(agent.trainer.loss.cpu().numpy())
+    return out
+
+
+@pytest.mark.gpu
+def test_agent_capture_on_and_off_agree():
+    runs = []
+    for capture in (False, True):
+        agent = _agent(capture)
+        actions = _run(agent, 0, EPISODE_STEPS)
+        agent.memory.raise_on_error()
+        assert agent.trainer.bn and agent.t == EPISODE_STEPS and agent.trainer.t == 2 * (EPISODE_STEPS - WARMUP)
+        assert (agent._graph is not None) == capture
+        assert np.abs(actions).max() <= 1.0 and actions.dtype == np.float64 and actions.shape == (EPISODE_STEPS, 3)
+        runs.append((actions, _agent_state(agent)))
+    assert np.array_equal(runs[0][0], runs[1][0])
+    for k in runs[0][1]:
+        assert np.array_equal(runs[0][1][k].view(np.uint8), runs[1][1][k].view(np.uint8)), k
+    fresh = _agent_state(_agent(False))
+    assert all(not np.array_equal(runs[0][1]["mv_" + w], fresh["mv_" + w]) for w in W)       # training moved the moving pairs
+    # act(test=True) is u in moving mode, without noise
+    obs0 = torch.from_numpy(_script(5)[0][:1]).cuda()
+    agent.reset(_script(5)[0][0])
+    want = agent.trainer.policy(obs0, bn="moving").cpu().numpy()[0]
+    other = agent.trainer.policy(obs0, bn="batch").cpu().numpy()[0]
+    assert np.array_equal(agent.act(test=True), np.clip(want.astype(np.float64), -1, 1)) and not agent.noise.any()
+    assert np.abs(want).max() > 0 and not np.array_equal(want, other)
+
+
+@pytest.mark.gpu
+def test_agent_on_the_point_mass_through_warmup_into_training():
+    """examples/rl_agent.py's environment and episode loop: silent until the warm-up is over, then one step per observation;
+    eager and captured agree bit for bit"""
+    spec = importlib.util.spec_from_file_location("example_rl_agent", os.path.join(REPO, "examples", "rl_agent.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    runs = []
+    for capture in (False, True):
+        agent = rl_agent.NAFAgent(4, 2, l1=16, l2=12, bsize=16, warmup=20, iters=1, rmsize=256, seed=1, capture=capture,
+                                  initstd=0.3, naf_bn=True)
+        env = mod.PointMass(4, 2, horizon=15, seed=2)
+        start = _agent_state(agent)
+        returns = [mod.run_episode(env, agent, False, 12)]
+        quiet = _agent_state(agent)
+        assert agent.t == 12 and agent.trainer.t == 0
+        assert all(np.array_equal(quiet[k].view(np.uint8), start[k].view(np.uint8)) for k in start)
+        returns += [mod.run_episode(env, agent, False, 12) for _ in range(3)]
+        returns.append(mod.run_episode(env, agent, True, 12))   # a test episode: act() without noise, nothing is learnt
+        agent.memory.raise_on_error()
+        assert agent.t == 48 and agent.trainer.t == 28 and all(steps == 12 for _, steps in returns[:4])
+        assert np.isfinite(agent.trainer.loss.item()) and all(np.isfinite(r) for r, _ in returns)
+        runs.append((returns, _agent_state(agent)))
+    assert runs[0][0] == runs[1][0]
+    for k in runs[0][1]:
+        assert np.array_equal(runs[0][1][k].view(np.uint8), runs[1][1][k].view(np.uint8)), k
+        assert k in ("step", "loss") or not np.array_equal(runs[0][1][k], start[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("capture", [False, True])
+def test_agent_checkpoint_resumes_bit_for_bit(capture, tmp_path):
+    whole = _agent(capture)
+    want_actions = _run(whole, 0, EPISODE_STEPS)
+    want = _agent_state(whole)
+    cut = 25
+    first = _agent(capture)
+    got_head = _run(first, 0, cut)
+    path = tmp_path / "naf_bn.npz"
+    checkpoint.save(path, first)
+    if capture:                                                 # a graph captured before the load replays on the loaded state
+        second = _agent(capture)
+        _run(second, 0, 12)
+        graph = second._graph
+        assert graph is not None
+    else:
+        second = _agent(capture, seed=9)                        # other weights, another noise stream, another sampler seed
+    pointers = {k: t.data_ptr() for k, t in _state(second.trainer).items()}
+    checkpoint.load(path, second)
+    assert pointers == {k: t.data_ptr() for k, t in _state(second.trainer).items()}     # into the existing tensors
+    if capture:
+        assert second._graph is graph
+    got_tail = _run(second, cut, EPISODE_STEPS)
+    second.memory.raise_on_error()
+    assert np.array_equal(np.concatenate([got_head, got_tail]), want_actions)
+    got = _agent_state(second)
+    for k in want:
+        assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
+    # the trainer alone; a file of one kind does not load into a trainer of the other
+    tr = naf.NAFTrainer(5, 3, 16, 12, batch=16, seed=1, bn=True)
+    checkpoint.save(tmp_path / "trainer.npz", second.trainer)
+    checkpoint.load(tmp_path / "trainer.npz", tr)
+    _same_bits(_snapshot(tr), _snapshot(second.trainer))
+    plain = naf.NAFTrainer(5, 3, 16, 12, batch=16, seed=1)
+    with pytest.raises(ValueError):
+        checkpoint.load(tmp_path / "trainer.npz", plain)
+    checkpoint.save(tmp_path / "plain.npz", plain)
+    with pytest.raises(ValueError):
+        checkpoint.load(tmp_path / "plain.npz", tr)
+    again = naf.NAFTrainer(5, 3, 16, 12, batch=16, seed=7)
+    checkpoint.load(tmp_path / "plain.npz", again)              # bn=False into bn=False: bit for bit, as before
+    assert all(torch.equal(again.theta[w], plain.theta[w]) for w in naf.NETS)
