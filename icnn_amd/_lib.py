@@ -83,6 +83,8 @@ EXPORTS = [
     "icnn_be_naf_bn_param_floats", "icnn_be_naf_bn_layout", "icnn_be_naf_bn_work_bytes", "icnn_be_naf_bn_work_offsets",
     "icnn_be_naf_bn_chain", "icnn_be_naf_bn_grads", "icnn_be_naf_bn_update", "icnn_be_naf_bn_step", "icnn_be_naf_bn_act",
     "icnn_be_naf_bn_q",
+    "icnn_be_pgd_workspace_bytes", "icnn_be_fc_pgd", "icnn_be_conv_pgd", "icnn_be_entropy_objective", "icnn_be_bundle_trace",
+    "icnn_be_dual_bound",
 ]
 FICNN_HEAD = {"sum": 0, "linear": 1}     # ICNN_BE_FICNN_HEAD_*
 CLAMP_ABS, CLAMP_RELU, CLAMP_ABS_HALF = 0, 1, 2
@@ -491,6 +493,19 @@ def load():
     lib.icnn_be_fc_gd.restype = C.c_int
     lib.icnn_be_conv_gd.argtypes = [C.POINTER(ConvModel)] + lib.icnn_be_fc_gd.argtypes[1:]
     lib.icnn_be_conv_gd.restype = C.c_int
+    lib.icnn_be_pgd_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.icnn_be_pgd_workspace_bytes.restype = C.c_size_t
+    lib.icnn_be_fc_pgd.argtypes = ([C.POINTER(FcModel), C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_double] * 3
+                                   + [C.c_void_p] * 5)
+    lib.icnn_be_fc_pgd.restype = C.c_int
+    lib.icnn_be_conv_pgd.argtypes = [C.POINTER(ConvModel)] + lib.icnn_be_fc_pgd.argtypes[1:]
+    lib.icnn_be_conv_pgd.restype = C.c_int
+    lib.icnn_be_entropy_objective.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_entropy_objective.restype = C.c_int
+    lib.icnn_be_bundle_trace.argtypes = [C.POINTER(State), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.icnn_be_bundle_trace.restype = C.c_int
+    lib.icnn_be_dual_bound.argtypes = [C.POINTER(State), C.c_void_p, C.c_void_p]
+    lib.icnn_be_dual_bound.restype = C.c_int
     lib.icnn_be_rl_td.argtypes = ([C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_void_p, C.c_longlong, C.c_void_p,
                                                                          C.c_float, C.c_float] + [C.c_void_p] * 5)
     lib.icnn_be_rl_td.restype = C.c_int

@@ -20,15 +20,17 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 SOURCES = ["be_api.hip", "be_dual.hip", "be_dual_small.hip", "be_picnn_fc.hip", "be_picnn_conv.hip", "be_fused.hip", "be_adam.hip",
            "be_context.hip", "be_train_common.hip", "be_train_fc.hip", "be_train_conv.hip", "be_train_update.hip", "be_gd.hip", "be_rl_train.hip",
            "be_ficnn.hip", "be_train_ficnn.hip", "be_train_bundle.hip", "be_train_gd.hip", "be_rl_replay.hip",
-           "be_train_epoch.hip", "be_train_data.hip", "be_train_table.hip", "be_ddpg.hip", "be_naf.hip", "be_naf_bn.hip", "be_ff.hip", "be_fcn.hip"]
+           "be_train_epoch.hip", "be_train_data.hip", "be_train_table.hip", "be_ddpg.hip", "be_naf.hip", "be_naf_bn.hip", "be_ff.hip", "be_fcn.hip",
+           "be_pgd.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, "icnn_be.h")]
 LIB = os.path.join(CSRC, "libicnn_be.so")
 PROF_DIR = os.path.join(CSRC, "prof")
 PROF_LIB = os.path.join(PROF_DIR, "libicnn_be.so")
-# Per-file compiler options.  be_fused.hip, be_adam.hip, be_gd.hip, be_ficnn.hip: MachineLICM hoists the literals of both inlined phases in front of the
+# Per-file compiler options.  be_fused.hip, be_adam.hip, be_gd.hip, be_ficnn.hip, be_pgd.hip: MachineLICM hoists the literals of both inlined phases in front of the
 # round loop of the persistent kernels, where they are spilled to scratch memory (be_fused.hip, FusedArgs comment).
 EXTRA_FLAGS = {"be_fused.hip": ["-mllvm", "-disable-machine-licm"], "be_adam.hip": ["-mllvm", "-disable-machine-licm"],
-               "be_gd.hip": ["-mllvm", "-disable-machine-licm"], "be_ficnn.hip": ["-mllvm", "-disable-machine-licm"]}
+               "be_gd.hip": ["-mllvm", "-disable-machine-licm"], "be_ficnn.hip": ["-mllvm", "-disable-machine-licm"],
+               "be_pgd.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def _stale(lib=LIB):

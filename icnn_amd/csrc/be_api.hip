@@ -77,6 +77,15 @@ int check_gd_args(const Model *model, const float *ctx, const double *y0, const 
     return 0;
 }
 
+// what icnn_be_fc_pgd and icnn_be_conv_pgd refuse alike
+template <typename Model>
+int check_pgd_args(const Model *model, const float *ctx, const double *y0, const double *y_out, const void *workspace, int batch,
+                   int n_iter, double lr, double lo, double hi) {
+    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !icnn_be::pgd_constants_ok(lr, lo, hi)) return ICNN_BE_EINVAL;
+    return 0;
+}
+
 // what icnn_be_solve_fc requires of a model and a state beyond their buffers
 int check_fc_solve(const icnn_be_fc_model *model, const icnn_be_state *st) {
     if (int rc = check_shape(st)) return rc;
@@ -762,6 +771,54 @@ int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const dou
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
     return done(icnn_be::launch_conv_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,
                                         static_cast<hipStream_t>(stream)));
+}
+
+size_t icnn_be_pgd_workspace_bytes(int batch, int n) {
+    return batch < 0 || n < 1 ? 0 : icnn_be::pgd_workspace_bytes(batch, n);
+}
+
+int icnn_be_fc_pgd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                   double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace, void *stream) {
+    if (int rc = check_pgd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, lo, hi)) return rc;
+    if (model->action_box) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    hipError_t e = icnn_be::launch_fc_pgd(*model, ctx, y0, batch, n_iter, lr, lo, hi, y_out, obj, obj_final, workspace,
+                                          static_cast<hipStream_t>(stream));
+    if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
+    return done(e);
+}
+
+int icnn_be_conv_pgd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                     double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace, void *stream) {
+    if (int rc = check_pgd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, lo, hi)) return rc;
+    if (int rc = icnn_be::conv_check_model(*model)) return rc;
+    if (batch == 0) return 0;
+    if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_conv_pgd(*model, ctx, y0, batch, n_iter, lr, lo, hi, y_out, obj, obj_final, workspace,
+                                         static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_entropy_objective(const float *E, const double *y, int batch, int n, double *out, void *stream) {
+    if (!E || !y || !out || batch < 0 || n < 1) return ICNN_BE_EINVAL;
+    if (batch == 0) return 0;
+    return done(icnn_be::launch_entropy_objective(E, y, batch, n, out, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_bundle_trace(const icnn_be_state *st, double *obj, int *calls, void *stream) {
+    if (int rc = check_state(st)) return rc;
+    if (!obj || !calls || !st->fvals) return ICNN_BE_EINVAL;
+    if (st->variant == ICNN_BE_VARIANT_RL) return ICNN_BE_EINVAL;      /* its callback has no x */
+    if (st->iters != 0) return ICNN_BE_ELIMIT;                         /* recycled slots hold no per-iteration history */
+    if (st->batch == 0) return 0;
+    return done(icnn_be::launch_bundle_trace(*st, obj, calls, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_dual_bound(const icnn_be_state *st, double *out, void *stream) {
+    if (int rc = check_state(st)) return rc;
+    if (!out) return ICNN_BE_EINVAL;
+    if (st->batch == 0) return 0;
+    return done(icnn_be::launch_dual_bound(*st, out, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_conv_fg(const icnn_be_conv_model *model, const float *ctx, const double *y, int batch,

@@ -249,6 +249,19 @@ hipError_t launch_fc_gd(const icnn_be_fc_model &m, const float *ctx, const doubl
                         double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
 hipError_t launch_conv_gd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                           double momentum, double *y_out, double *traj, float *f_out, void *workspace, hipStream_t stream);
+// Projected gradient descent on E - H(y), the objective's traces and the bundle's lower bound (be_pgd.hip): the forms and the
+// dispatch rule of the GD launchers above.  obj [K][B] and obj_final [B] may be NULL.
+size_t pgd_workspace_bytes(int batch, int n);
+bool pgd_constants_ok(double lr, double lo, double hi);   // lr finite, 0 < float32(lo), float32(hi) < 1, lo < hi
+hipError_t launch_fc_pgd(const icnn_be_fc_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                         double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace,
+                         hipStream_t stream);
+hipError_t launch_conv_pgd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
+                           double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace,
+                           hipStream_t stream);
+hipError_t launch_entropy_objective(const float *E, const double *y, int batch, int n, double *out, hipStream_t stream);
+hipError_t launch_bundle_trace(const icnn_be_state &st, double *obj, int *calls, hipStream_t stream);
+hipError_t launch_dual_bound(const icnn_be_state &st, double *out, hipStream_t stream);
 // ---- FICNN (be_ficnn.hip: context, energy / gradient, GD; be_train_ficnn.hip: training gradient) ----
 int ficnn_check_model(const icnn_be_ficnn_model &m);
 size_t ficnn_pack_floats(const icnn_be_ficnn_model &m);

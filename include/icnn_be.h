@@ -1044,6 +1044,61 @@ ICNN_BE_API int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ct
                                 double lr, double momentum, double *y_out, double *traj, float *f_out, void *workspace,
                                 void *stream);
 
+/* ---- projected gradient descent on E - H(y), objective traces, the bundle's lower bound (be_pgd.hip, additive to ABI 12) ---- */
+
+/* bytes of device scratch icnn_be_fc_pgd / icnn_be_conv_pgd need for `batch` samples of dim(y) = n (0: bad arguments) */
+ICNN_BE_API size_t icnn_be_pgd_workspace_bytes(int batch, int n);
+
+/*
+ * n_iter iterations of projected gradient descent on the entropy-scaled objective E(x, y) - H(y), H(y) = -sum_j [y_j log y_j
+ * + (1 - y_j) log(1 - y_j)]: what multi-label-cls/ebundle-vs-gd.py:110-132 and completion/ebundle-iter.py:115-139 run through
+ * bamos_opt.pgd.solve_batch with minIter == maxIter.  That module is not part of the reference tree: the iteration is
+ * defined HERE (parity unpinned), and its stopping rule, which those scripts switch off, is not built.  From
+ * y_0 = clip(y0, lo, hi) (the scripts start inside the box; it keeps the logarithms finite), for k = 0 .. n_iter-1
+ *     yf      = float64(float32(y_k))                          what the float32 energy is fed
+ *     E, g    = the float32 energy and dE/dy at yf, by the operations of icnn_be_fc_fg / icnn_be_conv_fg
+ *     e_k     = float64(E) + sum_j [yf log yf + (1 - yf) log(1 - yf)]      float64; a NaN term counts 0 (the scripts' entr())
+ *     G_k     = (float64(g) + log yf) - log(1 - yf)
+ *     y_{k+1} = min(max(y_k - lr G_k, lo), hi)                 float64, every operation rounded, no contraction
+ * The scripts' box is lo = 1e-6, hi = 1 - 1e-6.  y0 [B][n] float64 (may alias y_out).  Out (device): y_out [B][n] = y_K;
+ * obj (may be NULL) [n_iter][B] = e_k, what the scripts' callback sees before the update; obj_final (may be NULL) [B] = e_K
+ * from one more evaluation.  Samples are independent and a sample's e_k does not depend on its batch.  FC: one launch;
+ * conv: 1 + 5 n_iter (+5) launches (the model's `work` must hold `batch`, SINGLE-STREAM as for icnn_be_conv_fg).  Enqueued
+ * on `stream`, no host synchronisation (capturable).  ICNN_BE_EINVAL before any launch for n_iter < 1, batch < 0, a
+ * non-finite lr, a box that violates 0 < float32(lo), float32(hi) < 1, lo < hi, a NULL model, ctx, y0, y_out or workspace,
+ * an action_box model, or a shape the fg entries reject; ICNN_BE_ELIMIT for a model whose evaluation does not fit the LDS.
+ */
+ICNN_BE_API int icnn_be_fc_pgd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter,
+                               double lr, double lo, double hi, double *y_out, double *obj, double *obj_final,
+                               void *workspace, void *stream);
+ICNN_BE_API int icnn_be_conv_pgd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter,
+                                 double lr, double lo, double hi, double *y_out, double *obj, double *obj_final,
+                                 void *workspace, void *stream);
+
+/* out[u] = float64(E[u]) - H(y[u]) for E [B] float32 and y [B][n] float64 (not rounded), the entropy summed in float64 with
+ * the scripts' convention: an element whose term is NaN (0 log 0 at y = 0 and y = 1, any y outside [0, 1]) counts 0. */
+ICNN_BE_API int icnn_be_entropy_objective(const float *E, const double *y, int batch, int n, double *out, void *stream);
+
+/*
+ * The entropy-scaled objective per outer iteration of a finished fused solve, variants DUAL and PDIPM: what a
+ * callback(t, f, x) that records f - entr(x) would have seen (lib/bundle_entropy_dual.py:144-145), from st->fvals, st->ys,
+ * st->t_next, st->finished and st->y alone.  obj [st->slots][B] (device): obj[t][u] = f_t(u) - H(x_t(u)), where a sample that
+ * has left the loop keeps its iterate and its last energy and a sample that stopped on its own cut (rank test) is read from
+ * slot t_next.  calls (device int32): the number of callback invocations -- st->slots, or 1 + the iteration in which the
+ * last sample finished --; rows t >= *calls are NaN.  ICNN_BE_EINVAL for variant RL (its callback has no x, and its stall
+ * rule needs one more evaluation) or a state without fvals; ICNN_BE_ELIMIT when st->iters != 0 (recycled slots hold no
+ * per-iteration history).
+ */
+ICNN_BE_API int icnn_be_bundle_trace(const icnn_be_state *st, double *obj, int *calls, void *stream);
+
+/*
+ * The bundle's lower bound of min_y E(y) - H(y): with lam the multipliers of sample u's active cuts (g_i, h_i) and
+ * a = sum_i lam_i g_i,  out[u] = sum_i lam_i h_i - sum_j log(1 + exp(-a_j))  in float64 -- every cut under-estimates the convex
+ * E, so for lam on the simplex  min_y E - H >= min_y <a, y> + lam . h - H(y), whose minimum is that value.  float32 and
+ * float64 cuts; a sample without a cut gives -inf.
+ */
+ICNN_BE_API int icnn_be_dual_bound(const icnn_be_state *st, double *out, void *stream);
+
 /* ---- fully input-convex network, FICNN (synthetic-cls/icnn.py; be_ficnn.hip, be_train_ficnn.hip, additive to ABI 12) --- */
 
 #define ICNN_BE_FICNN_HEAD_SUM 0     /* the reference's f_ficnn: E = sum_k z_{L-1,k} (its last layer never reassigns z) */
