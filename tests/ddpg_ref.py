@@ -198,6 +198,80 @@ def reference_step(P, Q, PT, QT, mb, discount, masks=None):
     return fw, bound_fw, d, bound_d, own, ambiguous
 
 
+def stage_linear(x, W, b=None):
+    """x W + b from operands taken as exact (what one launch read) and its one-layer bound (K + 1) u (|x| |W| + |b|)"""
+    x, W = np.asarray(x, np.float64), np.asarray(W, np.float64)
+    z, m = x @ W, np.abs(x) @ np.abs(W)
+    if b is not None:
+        z, m = z + np.asarray(b, np.float64), m + np.abs(np.asarray(b, np.float64))
+    return z, (x.shape[1] + 1) * U * m
+
+
+class Stages:
+    """What a stage-wise check collects: want / bound of every stored quantity recomputed from the stored quantities it was
+    formed from, and pre[name] = (z, bound) of every ReLU layer, whose sign the stored mask must have wherever |z| > bound."""
+
+    def __init__(self):
+        self.want, self.bound, self.pre = {}, {}, {}
+
+    def put(self, name, want, bound):
+        self.want[name], self.bound[name] = want, bound
+
+    def relu(self, name, x, W, b):
+        z, e = stage_linear(x, W, b)
+        self.pre[name] = (z, e)
+        self.put(name, np.maximum(z, 0.0), np.where(z < -e, 0.0, e))         # a unit that is off beyond its bound is exactly 0
+
+    def back(self, name, delta, W, h):
+        """(delta W^T) [h > 0]: a delta through a layer's weights and the stored activation's sign"""
+        z, e = stage_linear(delta, np.asarray(W, np.float64).T)
+        mask = np.asarray(h) > 0
+        self.put(name, z * mask, e * mask)
+
+    def ambiguous(self):
+        return {k: np.abs(z) < e for k, (z, e) in self.pre.items()}
+
+
+def stage_step(P, Q, obs, dev, B):
+    """Every stored layer output and delta of the chain at obs from the stored quantities `dev` it was formed from (xa, h2q, q,
+    y, td, d3q, d2q, h1p, h2p, a, h2c, d3p, d2p: float64 arrays as the workspace holds them), each under one layer's rounding:
+    a product (K + 1) u (|x| |W| + |b|), tanh TANH_ROUNDINGS more on its value, an elementwise operation u.  The target path
+    keeps none of its layers, so a2 and y have no stage of their own."""
+    P, Q, obs = f64(P), f64(Q), np.asarray(obs, np.float64)
+    l1 = P["W1"].shape[1]
+    s = Stages()
+    qh1 = dev["xa"][:, :l1]
+    s.relu("qh1", obs, Q["W1"], Q["b1"])
+    s.relu("h2q", dev["xa"], Q["W2"], Q["b2"])
+    z, e = stage_linear(dev["h2q"], Q["W3"], Q["b3"])
+    s.put("q", z[:, 0], e[:, 0])
+    td = dev["q"] - dev["y"]
+    s.put("td", td, U * np.abs(td))
+    d3 = 2.0 * dev["td"] / B
+    s.put("d3q", d3[:, None], 2 * U * np.abs(d3)[:, None])                   # 1 / B rounded, then one product
+    d2 = dev["d3q"] * Q["W3"][:, 0][None, :] * (dev["h2q"] > 0)
+    s.put("d2q", d2, U * np.abs(d2))
+    s.back("d1q", dev["d2q"], Q["W2"][:l1], qh1)
+    s.relu("h1p", obs, P["W1"], P["b1"])
+    s.relu("h2p", dev["h1p"], P["W2"], P["b2"])
+    z, e = stage_linear(dev["h2p"], P["W3"], P["b3"])
+    s.put("a", np.tanh(z), e + TANH_ROUNDINGS * U * np.abs(np.tanh(z)))      # tanh's slope is at most 1
+    s.relu("h2c", np.concatenate([qh1, dev["a"]], axis=1), Q["W2"], Q["b2"])
+    z, e = stage_linear(dev["h2c"], Q["W3"], Q["b3"])
+    s.put("qpi", z[:, 0], e[:, 0])
+    # d3p = (d2c W2[action rows]^T) (1 - a^2); d2c = -(1 / B) W3 [h2c > 0] is not stored: two roundings, then the product's
+    c = -(1.0 / B) * Q["W3"][:, 0][None, :] * (dev["h2c"] > 0)
+    ec = 2 * U * np.abs(c)
+    Wa = np.abs(Q["W2"][l1:]).T
+    da, eda = c @ Q["W2"][l1:].T, ec @ Wa + (c.shape[1] + 1) * U * ((np.abs(c) + ec) @ Wa)
+    w = 1.0 - dev["a"] ** 2
+    ew = 2 * U * (1.0 + dev["a"] ** 2)
+    s.put("d3p", da * w, eda * (np.abs(w) + ew) + np.abs(da) * ew + U * (np.abs(da) + eda) * (np.abs(w) + ew))
+    s.back("d2p", dev["d3p"], P["W3"], dev["h2p"])
+    s.back("d1p", dev["d2p"], P["W2"], dev["h1p"])
+    return s
+
+
 def adam_lr_t(lr, beta1, beta2, t):
     return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
 

@@ -24,6 +24,7 @@ states a bound for expf.
 import numpy as np
 
 from ddpg_ref import NAMES, TANH_ROUNDINGS, U, Exact, Mag, absnet, adam_lr_t, f64, flat, update32  # noqa: F401
+from ddpg_ref import Stages, stage_linear
 
 EXP_ROUNDINGS = TANH_ROUNDINGS
 NETS = ("L", "U", "V")
@@ -186,6 +187,50 @@ def weight_grads(obs, h, d):
 
 def loss_q(nets, fw, l2norm):
     return np.mean(fw["td"] ** 2) + l2norm * 0.5 * sum(np.sum(flat(N) ** 2) for N in nets)
+
+
+def stage_step(L, Un, V, obs, act, dev, B):
+    """Every stored layer output and delta of the chain at obs from the stored quantities `dev` it was formed from (h1, h2,
+    d3, d2 of the three nets, l, y: float64 arrays as the workspace holds them), each under its own stage's rounding
+    (ddpg_ref.Stages): a layer's product (K + 1) u (|x| |W| + |b|); the head -- u, diag Lm, h, A, q, td and the three d3 -- by
+    forward_errors and step_backward entered with the stored l and y as exact and with layer 3's bound for tanh's argument
+    and for V's output, which are not stored.  The target pass keeps none of its layers, so y has no stage of its own."""
+    nets = {"l": f64(L), "u": f64(Un), "v": f64(V)}
+    obs, act = np.asarray(obs, np.float64), np.asarray(act, np.float64)
+    dimA = act.shape[1]
+    s = Stages()
+    for w, N in nets.items():
+        s.relu("h1" + w, obs, N["W1"], N["b1"])
+        s.relu("h2" + w, dev["h1" + w], N["W2"], N["b2"])
+    s.put("l", *stage_linear(dev["h2l"], nets["l"]["W3"], nets["l"]["b3"]))
+    pre_u, e_pre_u = stage_linear(dev["h2u"], nets["u"]["W3"], nets["u"]["b3"])
+    v, e_v = (t[:, 0] for t in stage_linear(dev["h2v"], nets["v"]["W3"], nets["v"]["b3"]))
+    u = np.tanh(pre_u)
+    Lm = lm_of(dev["l"].reshape(B, dimA, dimA))
+    delta = act - u
+    h = np.einsum("bi,bij->bj", delta, Lm)
+    adv = -0.5 * np.sum(h * h, axis=1)
+    q = v + adv
+    d = np.arange(dimA)
+    fw = {"y": dev["y"], "l": dev["l"], "pre_u": pre_u, "v": v, "u": u, "Lm": Lm, "ld": Lm[:, d, d], "delta": delta, "h": h,
+          "adv": adv, "q": q, "td": q - dev["y"]}
+    # forward_errors forms n u M of its inputs; with n = 1 and M = e / u it starts from the bounds given here
+    mg = {"l": np.zeros_like(dev["l"]), "pre_u": e_pre_u / U, "v": e_v / U, "y": np.zeros_like(dev["y"])}
+    n = {"out": 1, "y": 1}
+    for k in ("z1", "h1", "z2", "h2"):
+        n[k] = 0
+        for w in "luv":
+            mg[k + w] = 0.0
+    e = forward_errors(fw, mg, n, dimA)
+    for k in ("u", "ld", "h", "adv", "q", "td"):
+        s.put(k, fw[k], e[k])
+    zero = {k + w: np.zeros((B, nets["l"]["W%s" % k[1]].shape[1])) for k in ("h1", "h2") for w in "luv"}
+    d3, ed3 = step_backward(nets["l"], nets["u"], nets["v"], fw, e, zero)
+    for w, N in nets.items():
+        s.put("d3" + w, d3["d3" + w], ed3["d3" + w])
+        s.back("d2" + w, dev["d3" + w], N["W3"], dev["h2" + w])
+        s.back("d1" + w, dev["d2" + w], N["W2"], dev["h1" + w])
+    return s
 
 
 MASKS = {"h1l": "z1l", "h2l": "z2l", "h1u": "z1u", "h2u": "z2u", "h1v": "z1v", "h2v": "z2v"}

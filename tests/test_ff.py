@@ -6,7 +6,11 @@ derives for that quantity; none was measured on the device.
 
 The end-to-end bounds are worst-case and grow by about 6 sqrt(fan-in) per BatchNorm layer (ff_ref's docstring), so every
 launch is also checked from the device's own inputs, where the bound holds one layer's roundings.  Every test prints its
-largest error as a fraction of the bound (pytest -s); DESIGN.md §24 records them."""
+largest error as a fraction of the bound (pytest -s); DESIGN.md §24 records them.
+
+The LARGE shapes are training batches of 129 to 512 rows: col_gemm (be_col_gemm.h) at every length of its staged chunk, with
+several row tiles per wave, the prefetch of the next chunk, both load paths and a trailing partial chunk at each; and one test
+holds the header's promise that a row's bits depend neither on its batch nor on the chunk."""
 import ctypes as C
 import functools
 import os
@@ -25,18 +29,30 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the shipped shape
 SMALL = [(2, 3, (5,), 1), (17, 5, (16,), 2), (33, 7, (20, 12), 3), (48, 21, (33, 18, 9), 17)]
 SHIPPED = (128, 1836, (600,), 159)
-SHAPES = SMALL + [SHIPPED]
+# Batches past 128 rows, where col_gemm stages shorter chunks and a wave owns several row tiles (be_col_gemm.h): chunks of 64
+# from 129 rows on (9 row tiles: wave 0 alone owns two), the last row count with them (K = 64 + 4: whole float4 loads, two
+# chunks); chunks of 32 from the first padded count whose 64-chunk no longer fits (272; K = 32 + 4), at 17 row tiles with
+# scalar loads, two chunks and a tail (backward K = 3 and 12), at three chunks with a tail (backward K = 17), and at the
+# largest batch: four tiles per wave, five chunks, the largest LDS footprint
+EXACT_LARGE = (129, 5, (16,), 2)
+CAPPED_LARGE = [(256, 68, (48,), 16), (272, 36, (48,), 16), (257, 37, (20, 12), 3), (300, 70, (33,), 17), (512, 133, (40, 24), 5)]
+LARGE = [EXACT_LARGE] + CAPPED_LARGE
+EXACT = SMALL + [EXACT_LARGE]
+SHAPES = SMALL + [SHIPPED] + LARGE
 # The draw each shape is tested at.  A small shape's masks and decisions must match exactly, so its draw has no ReLU
 # pre-activation and no logit below its own bound: MARGIN is the smallest |z| / bound over both kinds at these draws on the CPU,
 # which test_small_shapes_have_no_ambiguous_unit asserts within 1 % (the figure is recorded, not chosen).  The shipped shape
-# may have at most 1 % of either.
-SEED = {SMALL[0]: 0, SMALL[1]: 0, SMALL[2]: 2, SMALL[3]: 1, SHIPPED: 0}
-MARGIN = {SMALL[0]: 1.019e4, SMALL[1]: 575.7, SMALL[2]: 33.33, SMALL[3]: 11.85}
+# may have at most 1 % of either, and so may the large batches but the first: of the seeds 0 .. 11 on the CPU only 129 rows
+# have one whose margin exceeds 8, the others take the seed with the fewest ambiguous units (none at 272 and 257 rows, 0.02 %
+# at 256, 0.04 % at 300, 0.08 % at 512, where seed 1 leaves ff_ref.head no bound).
+SEED = {SMALL[0]: 0, SMALL[1]: 0, SMALL[2]: 2, SMALL[3]: 1, SHIPPED: 0, EXACT_LARGE: 10, CAPPED_LARGE[0]: 7, CAPPED_LARGE[1]: 7,
+        CAPPED_LARGE[2]: 11, CAPPED_LARGE[3]: 9, CAPPED_LARGE[4]: 0}
+MARGIN = {SMALL[0]: 1.019e4, SMALL[1]: 575.7, SMALL[2]: 33.33, SMALL[3]: 11.85, EXACT_LARGE: 165.0}
 # What a shape's draw differs in from ff_ref's defaults.  Behind three BatchNorm layers the worst-case bound of a logit is some
 # 1e-2 (ff_ref's docstring), so among 816 logits of order 1 some would always lie below it; that shape's output biases are 2 to
 # 3 in magnitude, either sign, which keeps every logit away from 0 while its hidden units stay mixed (the seed is chosen for
 # those).  The shipped shape takes Bibtex's kind of input, 0 / 1 rows with 4 % ones.
-DRAW = {SMALL[3]: dict(logit_offset=2.0), SHIPPED: dict(density=0.04)}
+DRAW = {SMALL[3]: dict(logit_offset=2.0), SHIPPED: dict(density=0.04), CAPPED_LARGE[4]: dict(logit_offset=2.0)}
 NEW_EXPORTS = ["icnn_be_ff_param_floats", "icnn_be_ff_work_bytes", "icnn_be_ff_work_offsets", "icnn_be_ff_forward",
                "icnn_be_ff_backward", "icnn_be_ff_grads", "icnn_be_ff_update", "icnn_be_ff_step", "icnn_be_ff_eval"]
 SENTINEL = 0x7fc0beef
@@ -263,7 +279,7 @@ def _margin(v, e, L):
     return min([(np.abs(v["z%d" % i]) / e["z%d" % i]).min() for i in range(1, L + 1)] + [(np.abs(v["logit"]) / e["logit"]).min()])
 
 
-@pytest.mark.parametrize("shape", SMALL)
+@pytest.mark.parametrize("shape", EXACT)
 def test_small_shapes_have_no_ambiguous_unit(shape):
     """the precondition of the exact mask and decision comparison, from the reference alone"""
     _, _, _, v, e, ambiguous = _reference(shape)
@@ -276,6 +292,16 @@ def test_small_shapes_have_no_ambiguous_unit(shape):
 
 def test_shipped_shape_has_few_ambiguous_units():
     _, _, _, v, e, ambiguous = _reference(SHIPPED)
+    for k, a in ambiguous.items():
+        print("ambiguous %s: %d of %d" % (k, a.sum(), a.size))
+        assert a.mean() <= 0.01
+    assert np.abs(v["logit"]).max() < 8
+
+
+@pytest.mark.parametrize("shape", CAPPED_LARGE)
+def test_large_batches_have_few_ambiguous_units(shape):
+    """the same cap for the batches past 128 rows that have no seed without an ambiguous unit"""
+    _, _, _, v, e, ambiguous = _reference(shape)
     for k, a in ambiguous.items():
         print("ambiguous %s: %d of %d" % (k, a.sum(), a.size))
         assert a.mean() <= 0.01
@@ -384,7 +410,7 @@ def test_forward_and_backward_against_the_reference(shape):
     # masks and decisions: the reference's everywhere except at ambiguous units (the small shapes have none)
     n_ambiguous = sum(int(a.sum()) for a in ambiguous.values())
     print("ambiguous units and decisions: %d" % n_ambiguous)
-    if shape in SMALL:
+    if shape in EXACT:
         assert n_ambiguous == 0
     masks = {i: (dev_a[i] > 0).astype(np.float64) for i in dev_a}
     for i in masks:
@@ -459,6 +485,45 @@ def test_weight_gradients_from_the_devices_own_operands(shape):
     tr.grads()
     torch.cuda.synchronize()
     assert np.array_equal(tr.grad.cpu().numpy().view(np.uint32), got.view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_features", [70, 72])
+def test_a_rows_first_layer_has_the_same_bits_at_every_chunk_length(n_features):
+    """be_col_gemm.h: "a row's result has the same bits wherever the row lies in whichever batch, whatever the chunk".  a_1 =
+    relu(x W + b) is stored and does not depend on BatchNorm, so the same rows under the same weights give the same bits in
+    batches of 128, 200 and 300 rows (chunks of 128, 64 and 32) and in evaluate()'s groups of 128 rows; 70 features take the
+    scalar loads and a tail in every chunk length, 72 the float4 loads"""
+    shape = (300, n_features, (33,), 17)
+    P = ref.uniform_params(shape, 5)
+    x, y = ref.batch(shape, 5)
+    a = {}
+    for rows in (128, 200, 300):
+        tr = ff.FFTrainer(ff.FFModel(_spec(shape), P), rows, eval_batch=300 if rows == 300 else None)
+        tr.x.copy_(torch.from_numpy(x[:rows]))
+        tr.true_y.copy_(torch.from_numpy(y[:rows]))
+        tr.work.view(torch.int32).fill_(SENTINEL)
+        ctl = tr.work_offsets["ctl"]
+        tr.work[ctl:ctl + 4].zero_()
+        tr.forward("batch")
+        torch.cuda.synchronize()
+        a[rows] = tr.work_view("a0").cpu().numpy().view(np.uint32).copy()
+    tr.eval_work.view(torch.int32).fill_(SENTINEL)
+    tr.eval_work[ctl:ctl + 4].zero_()                              # 300 rows as the last trainer's batch: the same layout
+    tr.evaluate(torch.from_numpy(x), torch.from_numpy(y))
+    torch.cuda.synchronize()
+    a["moving"] = tr.work_view("a0", eval=True).cpu().numpy().view(np.uint32).copy()
+    x64, W, b = x.astype(np.float64), P["W1"].astype(np.float64), P["b1"].astype(np.float64)
+    want, bound = np.maximum(x64 @ W + b, 0.0), ref.e_matmul(x64, np.zeros_like(x64), W, b)
+    for key, got in a.items():                                     # the rows are this product's, not stale or shifted ones
+        assert not np.any(got == SENTINEL), key
+        _within("a1 of %s rows" % key, got.view(np.float32), want[:got.shape[0]], bound[:got.shape[0]])
+    assert (a[300] != 0).mean() > 0.5
+    for key in (200, 300, "moving"):
+        assert np.array_equal(a[key][:128], a[128]), key
+    for key in (300, "moving"):
+        assert np.array_equal(a[key][128:200], a[200][128:]), key
+    assert np.array_equal(a["moving"], a[300])
 
 
 def _state(tr):
@@ -559,7 +624,7 @@ def _fold_expected(before, v, L):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [SMALL[2], SHIPPED])
+@pytest.mark.parametrize("shape", [SMALL[2], SHIPPED, CAPPED_LARGE[2]])
 def test_three_whole_steps_eager_and_captured(shape):
     L = _L(shape)
     x, y = _batch(shape, SEED[shape])

@@ -1,7 +1,8 @@
 """NAF on the device (icnn_amd/naf.py, rl_agent.NAFAgent, icnn_be_naf_*, be_naf.hip) against
 tests/naf_ref.py: the reference's analytic gradients against torch.autograd, the ABI and its argument checks, init_params
 (CPU); the chain kernel, the weight gradients, the update, whole steps eager and captured, policy / q and the agent's cycle
-with checkpoints (GPU).  Every tolerance is the reference's running bound n u M of that quantity (naf_ref's docstring)."""
+with checkpoints (GPU).  Every tolerance is the reference's running bound n u M of that quantity (naf_ref's docstring); the
+stage-wise test of the wide nets takes one stage's bound from the device's own operands (naf_ref.stage_step)."""
 import ctypes as C
 import functools
 import os
@@ -20,12 +21,20 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the widest head among the reference's environments, on narrow hidden layers; the shipped shape
 SMALL = [(1, 3, 1, 5, 7), (17, 5, 2, 16, 16), (33, 3, 3, 20, 12), (20, 11, 5, 33, 18), (16, 4, 17, 8, 8)]
 SHIPPED = (256, 17, 6, 200, 200)
-SHAPES = SMALL + [SHIPPED]
+# WIDE: hidden layers past 256 columns, where a wave of tile_gemm (be_tile.h) walks its column tiles more than once: 17 column
+# tiles, so the second pass runs one tile with its pair predicated off, and a partial last tile; one column into tile 17 with K
+# tails of 300 and 257; the largest sizes the ABI accepts, whose L head has dimA^2 = 1024 columns: four passes of every wave
+WIDE = [(17, 5, 2, 272, 260), (33, 40, 3, 300, 257)]
+WIDEST = (20, 600, 32, 600, 600)
+SHAPES = SMALL + [SHIPPED] + WIDE + [WIDEST]
 # The draw each shape is tested at.  The masks of a small shape must match exactly, so its draw must have no pre-activation
 # below its own bound: MARGIN is the smallest |z| / bound of these draws on the CPU, which
 # test_small_shapes_have_no_ambiguous_unit asserts (within 1 %: the figure is recorded, not chosen).  The shipped shape has
 # ambiguous units at every seed (test_chain_kernel_against_the_reference prints how many), so flips there are legitimate.
-SEED = {SMALL[0]: 0, SMALL[1]: 0, SMALL[2]: 0, SMALL[3]: 0, SMALL[4]: 0, SHIPPED: 0}
+# The WIDE shapes have some at every seed of 0 .. 11 too, at most 0.02 % and 0.14 % of any mask at these
+# (test_wide_shapes_have_few_ambiguous_units caps them at 1 %); at WIDEST 3 % of the second layers' units are ambiguous end to
+# end, and what tests that shape, and every WIDE one, layer by layer is test_stages_from_the_devices_own_operands.
+SEED = {SMALL[0]: 0, SMALL[1]: 0, SMALL[2]: 0, SMALL[3]: 0, SMALL[4]: 0, SHIPPED: 0, WIDE[0]: 1, WIDE[1]: 0, WIDEST: 0}
 MARGIN = {SMALL[0]: 82.09, SMALL[1]: 32.58, SMALL[2]: 16.04, SMALL[3]: 122.4, SMALL[4]: 597.6}
 DISCOUNT = float(np.float32(0.99))
 NEW_EXPORTS = ["icnn_be_naf_param_floats", "icnn_be_naf_work_bytes", "icnn_be_naf_work_offsets", "icnn_be_naf_chain",
@@ -220,6 +229,48 @@ def test_small_shapes_have_no_ambiguous_unit(shape):
     assert margin > 8 and abs(margin / MARGIN[shape] - 1) < 0.01
 
 
+@pytest.mark.parametrize("shape", WIDE)
+def test_wide_shapes_have_few_ambiguous_units(shape):
+    """at most 1 % of the units of any mask lie below their own end-to-end bound"""
+    ambiguous = _reference(shape)[10]
+    for k, a in ambiguous.items():
+        print("ambiguous %s: %d of %d" % (k, a.sum(), a.size))
+        assert a.mean() <= 0.01, k
+
+
+STAGE_INPUTS = ("l", "y") + tuple(k + w for k in ("h1", "h2", "d3", "d2") for w in W)
+
+
+@pytest.mark.parametrize("shape", WIDE + [WIDEST])
+def test_stage_bounds_leave_few_units_ambiguous(shape):
+    """the precondition of the stage-wise mask comparison, from the reference's own activations: under one layer's rounding
+    at most 1 % of a layer's units lie below their bound"""
+    L, Un, V, _, mb, fw, _, d = _reference(shape)[:8]
+    dev = {k: fw[k] if k in fw else d[k] for k in STAGE_INPUTS}
+    s = ref.stage_step(L, Un, V, mb[0], mb[1], dev, shape[0])
+    assert set(s.pre) == set(ref.MASKS)
+    for k, a in s.ambiguous().items():
+        print("ambiguous %s: %d of %d" % (k, a.sum(), a.size))
+        assert a.mean() <= 0.01, k
+    # the stages, chained through the reference's own values, restate the reference's step
+    for k, want in s.want.items():
+        np.testing.assert_allclose(want, d[k] if k in d else fw[k], rtol=1e-12, atol=1e-14, err_msg=k)
+
+
+def test_the_widest_nets_are_accepted_and_one_more_unit_is_refused():
+    """WIDEST is the largest every dimension goes, its LDS fits (naf_fits), and one more hidden unit or action dimension is
+    refused by the size entries, before any launch"""
+    lib = _lib.load()
+    B, dimO, dimA, l1, l2 = WIDEST
+    assert (dimO, dimA, l1, l2) == (_lib.NAF_MAX_OBS, _lib.NAF_MAX_ACT, _lib.NAF_MAX_HIDDEN, _lib.NAF_MAX_HIDDEN)
+    for shape in WIDE + [WIDEST]:
+        assert lib.icnn_be_naf_work_bytes(*shape) > 0
+    for bad in ((dimO, dimA, l1 + 1, l2), (dimO, dimA, l1, l2 + 1), (dimO, dimA + 1, l1, l2), (dimO + 1, dimA, l1, l2)):
+        assert lib.icnn_be_naf_work_bytes(B, *bad) == 0, bad
+        assert lib.icnn_be_naf_work_offsets(B, *bad, C.byref((C.c_longlong * len(_lib.NAF_WORK))())) == -1, bad
+        assert lib.icnn_be_naf_param_floats(*bad, *[C.byref(C.c_longlong()) for _ in W]) == -1, bad
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 
 
@@ -291,6 +342,33 @@ def test_chain_kernel_against_the_reference(shape):
         _within(name, _host(tr.work_view(name)), d[name], bound_d[name])
     g3 = tr.work_view("d3l").cpu().numpy().reshape(B, dimA, dimA)
     assert not g3[:, np.triu(np.ones((dimA, dimA), bool), 1)].any()      # the upper triangle: exactly zero
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", WIDE + [WIDEST])
+def test_stages_from_the_devices_own_operands(shape):
+    """Every stored layer output and delta of the chain once more, from the stored quantities it was formed from and the
+    device's own parameters (naf_ref.stage_step): each bound holds one stage's roundings and stays sharp at the widest nets,
+    where the end-to-end bounds say little.  A mask has the sign of its pre-activation wherever that exceeds its bound."""
+    B, dimO, dimA, l1, l2 = shape
+    tr = _trainer(shape)
+    tr.chain()
+    torch.cuda.synchronize()
+    names = STAGE_INPUTS + ("u", "ld", "h", "adv", "q", "td") + tuple("d1" + w for w in W)
+    dev = {k: _host(tr.work_view(k)) for k in names}
+    for k in ("y", "adv", "q", "td"):
+        dev[k] = dev[k][:, 0]
+    s = ref.stage_step(*[tr.host_params(w) for w in W], _host(tr.obs), _host(tr.act), dev, B)
+    for name, (z, e) in s.pre.items():
+        sure = np.abs(z) > e
+        print("%s: %d of %d units below their bound" % (name, (~sure).sum(), sure.size))
+        assert (~sure).mean() <= 0.01, name
+        assert np.array_equal((dev[name] > 0)[sure], (z > 0)[sure]), name
+    for name in s.want:
+        assert np.abs(s.want[name]).max() > 1e-7, name
+        _within("stage " + name, dev[name], s.want[name], s.bound[name])
+        ratio = float(np.median(s.bound[name][s.want[name] != 0] / np.abs(s.want[name][s.want[name] != 0])))
+        print("stage %s: median bound / |value| %.3g" % (name, ratio))
 
 
 @pytest.mark.gpu
@@ -438,11 +516,13 @@ def test_three_whole_steps_eager_and_captured(shape):
 @pytest.mark.parametrize("B", [1, 17])
 def test_policy_and_q_equal_the_chain_bit_for_bit(B):
     """at the trainer's batch, and at B' != batch: the first rows of a larger batch through a forward launch of their own"""
-    for dims in ((5, 2, 16, 16), (11, 5, 33, 18), (4, 17, 8, 8), (17, 6, 200, 200)):
+    for dims in [(5, 2, 16, 16), (11, 5, 33, 18), (4, 17, 8, 8), (17, 6, 200, 200)] + [s[1:] for s in WIDE + [WIDEST]]:
         tr = _trainer((B,) + dims)
         tr.chain()
         u, q = tr.policy(tr.obs), tr.q(tr.obs, tr.act)
         big = _trainer((B + 20,) + dims)
+        for w in naf.NETS:                                          # the same nets, whatever seed either shape is drawn at
+            big.theta[w].copy_(tr.theta[w])
         big.obs[:B].copy_(tr.obs)
         big.act[:B].copy_(tr.act)
         u2, q2 = big.policy(big.obs[:B].contiguous()), big.q(big.obs[:B].contiguous(), big.act[:B].contiguous())
