@@ -6,8 +6,9 @@ wants at the origin; the observation is (position, velocity), truncated or zero-
 
     python examples/rl_agent.py [--total 2000] [--train 200] [--test 2] [--tmax 50] [--warmup 100] [--bsize 64] [--iter 1]
                                 [--dimO 4] [--dimA 2] [--capture] [--save FILE] [--resume FILE] [--model {ICNN,DDPG,NAF}]
-                                [--naf-bn]
+                                [--naf-bn] [--icnn-opt {adam,bundle_entropy}]
 
+--icnn-opt (with --model ICNN): the agent's inner optimiser, FLAGS.icnn_opt of RL/src/icnn.py:39-44.
 --naf-bn (with --model NAF): the NAF networks with BatchNorm, agent.py:22's naf_bn.
 --resume FILE restores the agent from a checkpoint before the loop (RL/src/icnn.py:134-137 restores the latest one at
 construction) and --save FILE writes one after it (RL/src/main.py:113-115): weights, optimiser state, noise, the random
@@ -93,6 +94,7 @@ def main():
     ap.add_argument("--resume", default=None, metavar="FILE")
     ap.add_argument("--model", choices=("ICNN", "DDPG", "NAF"), default="ICNN")
     ap.add_argument("--naf-bn", action="store_true")
+    ap.add_argument("--icnn-opt", choices=("adam", "bundle_entropy"), default="adam")
     args = ap.parse_args()
     if args.naf_bn and args.model != "NAF":
         ap.error("--naf-bn needs --model NAF")
@@ -108,7 +110,7 @@ def main():
         params = picnn.init_params(spec, args.seed)
         critic, target = picnn.FCModel(spec, params, "cuda"), picnn.FCModel(spec, params, "cuda")
         agent = rl_agent.Agent(critic, target, bsize=args.bsize, warmup=args.warmup, iters=args.iter, rmsize=args.rmsize,
-                               seed=args.seed, capture=args.capture)
+                               seed=args.seed, capture=args.capture, opt=args.icnn_opt)
     env = PointMass(args.dimO, args.dimA, seed=args.seed)
     if args.resume:
         from icnn_amd import checkpoint

@@ -60,7 +60,7 @@ EXPORTS = [
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
     "icnn_be_fc_surrogate_grad_bn", "icnn_be_conv_surrogate_grad_bn", "icnn_be_param_update",
     "icnn_be_gd_workspace_bytes", "icnn_be_fc_gd", "icnn_be_conv_gd",
-    "icnn_be_rl_td", "icnn_be_rl_critic_update",
+    "icnn_be_rl_td", "icnn_be_rl_critic_update", "icnn_be_rl_bundle_solve",
     "icnn_be_ficnn_pack_floats", "icnn_be_ficnn_pack", "icnn_be_ficnn_context_work_floats", "icnn_be_ficnn_context",
     "icnn_be_ficnn_fg", "icnn_be_ficnn_gd", "icnn_be_solve_ficnn", "icnn_be_ficnn_grad_floats",
     "icnn_be_ficnn_surrogate_grad_work_floats", "icnn_be_ficnn_surrogate_grad",
@@ -359,6 +359,8 @@ def load():
     lib.icnn_be_solve_fc.restype = C.c_int
     lib.icnn_be_solve_fc_reset.argtypes = (lib.icnn_be_solve_fc.argtypes[:-1] + [C.c_void_p, C.c_double, C.c_void_p])
     lib.icnn_be_solve_fc_reset.restype = C.c_int
+    lib.icnn_be_rl_bundle_solve.argtypes = (lib.icnn_be_solve_fc.argtypes[:-1] + [C.c_double, C.c_void_p, C.c_void_p, C.c_void_p])
+    lib.icnn_be_rl_bundle_solve.restype = C.c_int
     lib.icnn_be_conv_pack_floats.argtypes = [C.POINTER(ConvModel)]
     lib.icnn_be_conv_pack_floats.restype = C.c_size_t
     lib.icnn_be_conv_work_floats.argtypes = [C.POINTER(ConvModel), C.c_int]

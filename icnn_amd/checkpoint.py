@@ -7,7 +7,9 @@ result depends on:
 
     every trainer        theta, Adam's m and v, the device step count; the BatchNorm moving statistics of a model that has them
     BundleTrainer        with skip_on_error, the gate words (the skipped count among them)
-    CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step)
+    CriticTrainer        also the target's theta and moving statistics (the critic update keeps no state beyond m, v, step),
+                         and `opt`, `n_iter`: its inner optimiser; load() refuses a file of the other one (a file without
+                         `opt` was written by the adam branch)
     ddpg.DDPGTrainer     the four flat nets (theta/q, theta/p, theta/target_q, theta/target_p), m and v of both nets, the step counts
     naf.NAFTrainer       the four flat nets (theta/l, theta/u, theta/v, theta/target_v), m and v of the three nets, the step count;
                          with bn=True the betas and their moments lie inside those, and bn/l, bn/u, bn/v are the moving pairs
@@ -214,6 +216,8 @@ def save(path, obj, keeper=None, memory=True, dataset=None):
         raise ValueError("keeper: it keeps another trainer's model")
     arrays = {"kind": np.asarray(kind), "spec": np.asarray(spec_json(trainer.spec)),
               "has_keeper": np.asarray(int(keeper is not None), np.int64)}
+    if AGENTS.get(kind, kind) == "CriticTrainer":             # the inner optimiser the step was run with (FLAGS.icnn_opt)
+        arrays["opt"], arrays["n_iter"] = np.asarray(trainer.opt_name), np.asarray(trainer.n_iter, np.int64)
     tensors = _trainer_tensors(AGENTS.get(kind, kind), trainer)
     if keeper is not None:
         arrays["keeper/mode"] = np.asarray(keeper.mode)
@@ -278,6 +282,14 @@ def load(path, obj, keeper=None, dataset=None):
         raise ValueError("kind: the file holds a %s, the object is a %s" % (arrays["kind"], kind))
     if str(arrays["spec"]) != spec_json(trainer.spec):
         raise ValueError("spec: the file's model is %s, the object's %s" % (arrays["spec"], spec_json(trainer.spec)))
+    if AGENTS.get(kind, kind) == "CriticTrainer":             # a file from before the bundle-entropy branch is an adam one
+        if "opt" in arrays and (arrays["opt"].shape != () or arrays["opt"].dtype.kind != "U"):
+            raise ValueError("opt: not a string")
+        opt = str(arrays["opt"]) if "opt" in arrays else "adam"
+        if opt != trainer.opt_name:
+            raise ValueError("opt: the file was written with the %s inner optimiser, this object runs %s" % (opt, trainer.opt_name))
+        if opt == "bundle_entropy" and _scalar(arrays, "n_iter") != trainer.n_iter:
+            raise ValueError("n_iter: %d in the file, %d here" % (_scalar(arrays, "n_iter"), trainer.n_iter))
     has_keeper = bool(_scalar(arrays, "has_keeper"))
     if has_keeper != (keeper is not None):
         raise ValueError("keeper: the file %s a keeper's state, the call %s a keeper"

@@ -409,6 +409,25 @@ int icnn_be_solve_fc_reset(const icnn_be_fc_model *model, const float *ctx, cons
     return solve_fc(model, ctx, st, f_work, g_work, icnn_be::SolveReset{1, y0, y0_fill}, stream);
 }
 
+int icnn_be_rl_bundle_solve(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st, float *f_work,
+                            float *g_work, double y0_fill, double *act_out, float *q_out, void *stream) {
+    if (!model || !ctx || !st || !f_work || !g_work || !act_out) return ICNN_BE_EINVAL;
+    if (int rc = check_state(st)) return rc;
+    if (!model->wpack || model->action_box == 0 || st->variant != ICNN_BE_VARIANT_RL || st->cut_dtype != ICNN_BE_CUT_F32)
+        return ICNN_BE_EINVAL;
+    if (!std::isfinite(y0_fill)) return ICNN_BE_EINVAL;
+    if (int rc = check_fc_solve(model, st)) return rc;
+    if (st->batch == 0) return 0;
+    const SolvePlan p = plan_fc_solve(*model, *st, icnn_be::device_cus(), env_tile_budget());
+    if (p.path < 0) return p.path;
+    if (p.path != ICNN_BE_PATH_ROWS) return ICNN_BE_ELIMIT;      /* the epilogue lives in the per-sample kernel only */
+    const icnn_be::RowsValue value{act_out, q_out};
+    hipError_t e = icnn_be::launch_fused_rows_solve(*model, ctx, *st, f_work, g_work, p.per_wg, icnn_be::dual_profile_buffer(),
+                                                    static_cast<hipStream_t>(stream), false,
+                                                    icnn_be::SolveReset{1, nullptr, y0_fill}, &value);
+    return e == hipSuccess ? p.rounds : fail(e);
+}
+
 int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state *st, int cus, int out[3]) {
     if (!out) return ICNN_BE_EINVAL;
     if (int rc = check_fc_solve(model, st)) return rc;

@@ -208,10 +208,14 @@ struct FusedRowsArgs {
                                        // run (parked in a Newton loop or behind by the rounds they were parked in) do
                                        // anything, each from its own outer-iteration counter, with no update budget
     SolveReset reset;                  // on (never with resume): the state is reset in front of round 0 (reset_sample)
+    RowsValue value;                   // VALUE kernels only (icnn_be_rl_bundle_solve): where the epilogue writes 2y - 1 and E(y)
 };
 typedef const __attribute__((address_space(4))) FusedRowsArgs KRArgs;
 
 // phase A of the per-sample kernel: the VALU evaluation of be_picnn_fc_rows_dev.h on all waves
+// VALUE: the same evaluation as the epilogue of icnn_be_rl_bundle_solve -- the energy goes to value.q and the action 2y - 1
+// (float64, from the y the input was rounded from) to value.act; the work arrays keep what the last round left in them
+template <bool VALUE = false>
 __device__ __forceinline__ void rows_phase_fg(KRArgs *kp, int s_base, int batch, int tid) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -237,6 +241,16 @@ __device__ __forceinline__ void rows_phase_fg(KRArgs *kp, int s_base, int batch,
     __syncthreads();
     lap(13);
     rows_eval(k.fa, k.lay, lds, batch, tid, lap);
+    if constexpr (VALUE) {
+        if (wave < batch) {
+            if (lane == 0 && k.value.q) k.value.q[s_base + wave] = lds[k.lay.f_off + wave];
+            for (int j = lane; j < n; j += 64) {
+                const size_t at = (size_t)(s_base + wave) * n + j;
+                k.value.act[at] = 2.0 * k.da.st.y[at] - 1.0;
+            }
+        }
+        return;
+    }
     if (wave < batch) {                  // hand-over to the dual step of the sample (same wave) through its work arrays
         const float gscale = k.fa.action_box ? 2.f : 1.f;
         if (lane == 0) k.fa.f[s_base + wave] = lds[k.lay.f_off + wave];
@@ -248,7 +262,9 @@ __device__ __forceinline__ void rows_phase_fg(KRArgs *kp, int s_base, int batch,
 // KS > 0: narrow rows (n <= 16, variant RL): the dual steps of ALL samples of the workgroup (at most four) run on wave 0, one
 // sample per 16-lane DPP row with the bundle in registers (be_dual_small_dev.h, KS = its row count) -- the RL agent's act()
 // and its replay batches up to four samples per CU.  Bit-identical to the wave-per-sample phase.
-template <bool RL, int KT, int KS = 0, bool IPM = false>
+// VALUE (variant RL, never a resume launch): one more evaluation of every sample of the workgroup behind the last round
+// (rows_phase_fg<true>), whichever way the workgroup left the round loop.
+template <bool RL, int KT, int KS = 0, bool IPM = false, bool VALUE = false>
 __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArgs args) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int per_wg = args.per_wg;
@@ -302,6 +318,15 @@ __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArg
         }
         if (!__syncthreads_or(live)) break;                         // every sample of the workgroup has left the loop
     }
+    if constexpr (VALUE) {
+        // Both ways out of the loop pass the barrier above behind the last dual step, but with narrow rows wave 0 wrote the y
+        // rows that waves 1.. now read: a full barrier, whose workgroup-scope release / acquire covers global memory.
+        __syncthreads();
+        KRArgs *kp = kp0;
+        int s_base = s_base0, batch = batch0;
+        asm volatile("" : "+s"(kp), "+s"(s_base), "+s"(batch));
+        rows_phase_fg<true>(kp, s_base, batch, thread_id());
+    }
 }
 
 }  // namespace
@@ -352,8 +377,9 @@ bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int t
 
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                    float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume,
-                                   const SolveReset &reset) {
+                                   const SolveReset &reset, const RowsValue *value) {
     if (resume && reset.on) return hipErrorInvalidValue;
+    if (value && (resume || st.variant != ICNN_BE_VARIANT_RL || !value->act)) return hipErrorInvalidValue;
     FusedRowsLayout lay;
     if (!fused_rows_layout(m, st, per_wg, resume, lay)) return hipErrorInvalidValue;
     FusedRowsArgs args{};
@@ -370,6 +396,7 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
     args.rounds = args.iters = st.iters > 0 ? st.iters : st.slots;
     args.resume = resume ? 1 : 0;
     args.reset = reset;
+    if (value) args.value = *value;
     const bool big = st.slots > 15;
     const int which = (st.variant == ICNN_BE_VARIANT_RL ? 1 : 0) + (big ? 2 : 0);
     auto kern = which == 0 ? fused_rows_solve_kernel<false, 16> : which == 1 ? fused_rows_solve_kernel<true, 16>
@@ -379,6 +406,12 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
     if (!resume && dual_step_small_fits(st, 0))         // narrow rows, variant RL: all dual steps of the workgroup on wave 0
         kern = st.slots <= 5 ? fused_rows_solve_kernel<true, 16, 5> : st.slots <= 7 ? fused_rows_solve_kernel<true, 16, 8>
                                                                                   : fused_rows_solve_kernel<true, 16, 16>;
+    if (value) {                                        // the same choice among the RL forms, with the value epilogue
+        kern = big ? fused_rows_solve_kernel<true, 32, 0, false, true> : fused_rows_solve_kernel<true, 16, 0, false, true>;
+        if (dual_step_small_fits(st, 0))
+            kern = st.slots <= 5 ? fused_rows_solve_kernel<true, 16, 5, false, true>
+                 : st.slots <= 7 ? fused_rows_solve_kernel<true, 16, 8, false, true> : fused_rows_solve_kernel<true, 16, 16, false, true>;
+    }
     return launch_kernel(kern, dim3((st.batch + per_wg - 1) / per_wg), dim3(RTHREADS), lay.lds, stream, args);
 }
 

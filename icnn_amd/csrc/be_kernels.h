@@ -214,9 +214,15 @@ bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int p
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                  float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget,
                                  const SolveReset &reset = SolveReset{});
+// value (icnn_be_rl_bundle_solve; variant RL, never with resume): behind the last round every sample of the workgroup is
+// evaluated once more at its st.y: act[u][j] = 2 y[u][j] - 1 (float64 [B][n]) and q[u] = its energy (float32 [B], may be null)
+struct RowsValue {
+    double *act;
+    float *q;
+};
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                    float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume,
-                                   const SolveReset &reset = SolveReset{});
+                                   const SolveReset &reset = SolveReset{}, const RowsValue *value = nullptr);
 int dual_waves(int n, int cut_dtype, int variant);
 long long *dual_profile_buffer();
 void set_dual_trace_buffer(long long *buf);

@@ -16,7 +16,7 @@ Parameters are a dict of float32 arrays keyed by the reference's variable-scope
 names ('u0/W', 'z1_zu_proj/W', ...), W stored [in, out] as tflearn does.
 """
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -611,6 +611,46 @@ class FCModel(_PICNNDevice):
                                            None if finished is None else finished.data_ptr(),
                                            C.c_void_p(stream)), "icnn_be_fc_fg")
         return f, g
+
+    def boxed(self):
+        """A view of this model with action_box on (the RL wrapper of RL/src/icnn.py:148-158: the network sees 2y - 1, the
+        gradient is doubled), for the bundle-entropy solve on a model that everything else reads as is.  The view shares the
+        packed weights, the stage weights and the BatchNorm tensors and follows the model when a train.DeviceAdam or a
+        train.FollowerWeights attaches it: its descriptor is read from the model's at every use."""
+        if self.spec.action_box:
+            return self
+        return _BoxedFCModel(self)
+
+
+def _follow(name):
+    return property(lambda self: getattr(self._base, name))
+
+
+class _BoxedFCModel(FCModel):
+    """FCModel.boxed(): the methods of FCModel on the base model's buffers, with action_box = 1 in spec and c_model.  It owns
+    nothing: whatever would change the weights or move the statistics is the base model's to do."""
+    _optimizer, has_bn, bn_decay = _follow("_optimizer"), _follow("has_bn"), _follow("bn_decay")
+
+    def __init__(self, base):
+        self._base = base
+        self.spec = replace(base.spec, action_box=True)
+        self._c_model = _lib.FcModel()
+
+    def __getattr__(self, name):                 # what the view does not hold itself: device, wpack, c_ctx, bn_stats, params, ...
+        if name == "_base":
+            raise AttributeError(name)
+        return getattr(self._base, name)
+
+    @property
+    def c_model(self):
+        C.memmove(C.byref(self._c_model), C.byref(self._base.c_model), C.sizeof(_lib.FcModel))
+        self._c_model.action_box = 1
+        return self._c_model
+
+    def _owned_by_base(self, *args, **kwargs):
+        raise RuntimeError("a boxed() view owns no weights or statistics: call this on the model it views")
+
+    repack = repack_context = clamp = flatten_bn_stats = _use_arena = _owned_by_base
 
 
 # --------------------------------------------------------------------------------------------- #

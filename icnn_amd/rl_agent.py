@@ -1,5 +1,6 @@
 """The RL agent on the device: the replay memory of RL/src/replay_memory.py and the reset / act / observe /
-train cycle of RL/src/icnn.py:260-323 with FLAGS.icnn_opt == 'adam', around rl_train.CriticTrainer and rl_adam.AdamSolver.
+train cycle of RL/src/icnn.py:260-323 with either FLAGS.icnn_opt, around rl_train.CriticTrainer and rl_adam.AdamSolver /
+rl_bundle.BundleActionSolver.
 
 The memory's arrays, its cursor, its fill and the draw counter of the sampler live in device memory
 (icnn_amd/csrc/be_rl_replay.hip): a training iteration is [icnn_be_replay_sample into the trainer's buffers,
@@ -11,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ddpg, naf, rl_adam, rl_train
+from . import _lib, ddpg, naf, rl_adam, rl_bundle, rl_train
 
 
 class ReplayMemory:
@@ -185,8 +186,9 @@ class _AgentCycle:
 
 
 class Agent(_AgentCycle):
-    """`Agent` of RL/src/icnn.py with the adam inner optimiser: critic and target are picnn.FCModel of one spec with
-    action_box False.  The constructor builds the CriticTrainer at minibatch size `bsize` (lr, tau, discount, l2norm, wd and
+    """`Agent` of RL/src/icnn.py with either inner optimiser (opt = FLAGS.icnn_opt: "adam", or "bundle_entropy" at n_iter
+    rounds; anything else raises the reference's RuntimeError): critic and target are picnn.FCModel of one spec
+    with action_box False.  The constructor builds the CriticTrainer at minibatch size `bsize` (lr, tau, discount, l2norm, wd and
     max_iter go to it), initialises it as the reference does (:139-142: makeCvx, then target <- critic) and builds the
     ReplayMemory of `rmsize` transitions.  seed: the exploration noise's np.random.RandomState and the memory's sampler.
 
@@ -194,23 +196,29 @@ class Agent(_AgentCycle):
     graph (a linear chain of [sample, step] x iters) and every later observe() replays it."""
 
     def __init__(self, critic, target, bsize=256, warmup=1000, iters=1, rmsize=500000, outheta=0.15, ousigma=0.1, seed=0,
-                 capture=False, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000):
+                 capture=False, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000, opt="adam", n_iter=5):
+        if opt not in rl_train.OPTS:
+            raise RuntimeError("Unrecognized ICNN optimizer: " + str(opt))      # RL/src/icnn.py:44
         self._check_cycle(warmup, iters)
         self.trainer = rl_train.CriticTrainer(critic, target, bsize, lr=lr, tau=tau, discount=discount, l2norm=l2norm, wd=wd,
-                                              max_iter=max_iter)
+                                              max_iter=max_iter, opt=opt, n_iter=n_iter)
         self.trainer.initialise()
-        self.critic, self.spec = critic, critic.spec
+        self.critic, self.spec, self.opt = critic, critic.spec, opt
         self._setup(self.spec.n_features, self.spec.n_labels, critic.device, warmup, iters, rmsize, outheta, ousigma, seed,
                     capture)
-        self._solver = rl_adam.AdamSolver(critic, 1, max_iter)
+        if opt == "adam":
+            self._solver = rl_adam.AdamSolver(critic, 1, max_iter)
+        else:
+            self._solver = rl_bundle.BundleActionSolver(critic, 1, n_iter)
 
     def act(self, test=False):
-        """icnn.py:264-288: the inner Adam on the critic at the current observation (inference-mode BatchNorm), plus the
-        Ornstein-Uhlenbeck noise unless `test`, clipped to [-1, 1].  Returns float64 [dimA]; the copy to the host is the one
-        synchronisation of an environment step."""
+        """icnn.py:264-288: the inner optimiser (Adam on negQ_entr, or the bundle-entropy solve on negQ: 2y* - 1) on the critic
+        at the current observation (inference-mode BatchNorm), plus the Ornstein-Uhlenbeck noise unless `test`, clipped to
+        [-1, 1].  Returns float64 [dimA]; the copy to the host is the one synchronisation of an environment step."""
         obs = torch.from_numpy(np.asarray(self.observation, np.float32).reshape(1, self.dimO))
         ctx = self.critic.context(obs, bn="moving") if self.spec.batchnorm else self.critic.context(obs)
-        action = self._solver.solve(ctx).act_best.cpu().numpy()
+        res = self._solver.solve(ctx)
+        action = (res.act_best if self.opt == "adam" else res.act).cpu().numpy()
         return self._explore(action, test)
 
 

@@ -1,5 +1,5 @@
 """The RL agent's critic training step on the device: `Agent.train()` of RL/src/icnn.py:304-323 (graph :56-112) with
-FLAGS.icnn_opt == 'adam' (DESIGN.md §13).
+FLAGS.icnn_opt == 'adam'  or 'bundle_entropy' (DESIGN.md §28).
 
 One step, enqueued on the current stream without a host synchronisation (a captured step replayed k times is k steps):
     1. target context of ob2 with the moving BatchNorm statistics (tflearn.is_training(False), :316)
@@ -10,6 +10,10 @@ One step, enqueued on the current stream without a host synchronisation (a captu
     5. icnn_be_rl_td: TD target, c_j, the loss (be_rl_train.hip)
     6. the critic's gradient of sum_j c_j negQ_j (train.surrogate_grad, one row per sample)
     7. icnn_be_rl_critic_update: soft target update, L2 decay, TF-Adam, proj, both arenas (be_train_update.hip)
+
+opt="bundle_entropy" replaces 2-3: act2 = 2y* - 1 of the bundle-entropy solve on the target's boxed() view and negQ_target(ob2,
+act2) out of the same launch (rl_bundle.BundleActionSolver); icnn_be_rl_td then adds the entropy of act2 (:455-458).  With
+BatchNorm the value is evaluated afresh with the batch statistics of ob2, as in 3.
 """
 import ctypes as C
 from typing import Dict
@@ -17,7 +21,9 @@ from typing import Dict
 import numpy as np
 import torch
 
-from . import _lib, picnn, rl_adam, train
+from . import _lib, picnn, rl_adam, rl_bundle, train
+
+OPTS = ("adam", "bundle_entropy")        # FLAGS.icnn_opt (RL/src/icnn.py:39-44)
 
 
 def decay_mask(spec) -> np.ndarray:
@@ -36,16 +42,24 @@ class CriticTrainer:
     """The critic's whole training step at one minibatch size.  Constructing one ATTACHES both models: the critic to a
     train.DeviceAdam (its Adam state and arena), the target to a train.FollowerWeights (an arena of its own), so that the
     descriptors of both stay fixed and a captured step keeps reading the current weights of each.  `critic` and `target`
-    are picnn.FCModel of one spec with action_box False (the adam branch optimises the action itself).
+    are picnn.FCModel of one spec with action_box False (the adam branch optimises the action itself; the bundle-entropy
+    branch solves on target.boxed() and leaves the stored actions and the gradient on the plain view).
+    opt: the inner optimiser of step 2, "adam" (max_iter) or "bundle_entropy" (n_iter, the reference's nIter = 5).
 
     wd: the weight decay of tflearn's fully_connected (its default 0.001, taken from tflearn's source); the loss carries
     l2norm * sum_W wd |W|^2 / 2 (RL/src/icnn.py:90-93)."""
 
-    def __init__(self, critic, target, batch, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000):
+    def __init__(self, critic, target, batch, lr=1e-3, tau=0.01, discount=0.99, l2norm=1e-4, wd=1e-3, max_iter=1000,
+                 opt="adam", n_iter=5):
+        if opt not in OPTS:
+            raise RuntimeError("Unrecognized ICNN optimizer: " + str(opt))      # RL/src/icnn.py:44
+        if opt == "bundle_entropy" and not 1 <= int(n_iter) <= _lib.MAX_ITERS:
+            raise ValueError("n_iter must be in 1..%d, got %r" % (_lib.MAX_ITERS, n_iter))
         if critic.spec != target.spec:
             raise ValueError("the critic and the target must share one spec")
         if critic.spec.action_box:
-            raise ValueError("the adam branch takes the action as is: build the models with action_box=False")
+            raise ValueError("build the models with action_box=False: the adam branch takes the action as is, the "
+                             "bundle_entropy branch boxes the target itself")
         if not 0.0 <= tau <= 1.0:
             raise ValueError("tau must lie in [0, 1], got %r" % (tau,))
         self.critic, self.target, self.spec, self.device = critic, target, critic.spec, critic.device
@@ -56,7 +70,11 @@ class CriticTrainer:
         self.follower = train.FollowerWeights(target)
         if not _same_map(self.opt.map, self.follower.map):
             raise AssertionError("the critic's and the target's parameter maps differ")
-        self.solver = rl_adam.AdamSolver(target, self.batch, max_iter)
+        self.opt_name, self.n_iter = opt, int(n_iter)
+        if opt == "adam":
+            self.solver = rl_adam.AdamSolver(target, self.batch, max_iter)
+        else:
+            self.solver = rl_bundle.BundleActionSolver(target, self.batch, self.n_iter)
         dev, B, spec = self.device, self.batch, self.spec
         self.obs = torch.zeros(B, spec.n_features, dtype=torch.float32, device=dev)
         self.ob2 = torch.zeros_like(self.obs)
@@ -127,10 +145,13 @@ class CriticTrainer:
         # 1-3: the target
         ctx2 = self.target.context(self.ob2, bn="moving") if bn else self.target.context(self.ob2)
         res = self.solver.solve(ctx2)
-        self.act2 = res.act_best
+        bundle = self.opt_name == "bundle_entropy"
+        self.act2 = res.act if bundle else res.act_best
         if bn:
             e2, _ = self.target.fg(self.target.context(self.ob2, bn="batch", bn_updates=1), self.act2)
             self.q2_src, act2 = e2, self.act2
+        elif bundle:                         # negQ_target(ob2, act2) from the solve's launch; the entropy is icnn_be_rl_td's
+            self.q2_src, act2 = res.q, self.act2
         else:
             self.q2_src, act2 = res.f_best, None
         # 4: the critic's value at (obs, act)

@@ -859,6 +859,25 @@ typedef struct icnn_be_rl_update_args {
 
 ICNN_BE_API int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream);
 
+/*
+ * The inner optimiser of the RL agent with FLAGS.icnn_opt == 'bundle_entropy' (RL/src/icnn.py:148-158): the bundle-entropy
+ * solve of variant RL on an action_box model, with the action and its value out of the same launch.  Bit for bit
+ *     icnn_be_solve_fc_reset(model, ctx, st, f_work, g_work, NULL, y0_fill)
+ *     act_out[u][j] = 2.0 * st->y[u][j] - 1.0                                   (float64, no contraction)
+ *     q_out[u]      = the f[u] of icnn_be_fc_fg(model, ctx, st->y, ...)         (negQ at act_out; q_out may be NULL)
+ * in ONE launch of the persistent per-sample kernel: behind the last round every sample of the workgroup -- one that the
+ * stall rule finished early included -- is evaluated once more at its float64 st->y.  f_work and g_work are left as the
+ * solve leaves them.  A singular system leaves a nonzero status word and the sample keeps its iterate, as everywhere.
+ * EINVAL before any launch: a NULL model, ctx, st, f_work, g_work or act_out, model->action_box == 0, st->variant not RL,
+ * st->cut_dtype not F32, a non-finite y0_fill, and whatever icnn_be_solve_fc refuses.  ELIMIT: the plan of this model and
+ * state is not ICNN_BE_PATH_ROWS (more than four samples per CU, icnn_be_debug_solve_plan); the caller then composes the
+ * three steps above.  Returns the rounds like icnn_be_solve_fc (0 for an empty batch).  No host synchronisation,
+ * capturable in a HIP graph.  (Added within ABI 12.)
+ */
+ICNN_BE_API int icnn_be_rl_bundle_solve(const icnn_be_fc_model *model, const float *ctx, const icnn_be_state *st,
+                                        float *f_work, float *g_work, double y0_fill, double *act_out, float *q_out,
+                                        void *stream);
+
 /* ---- the RL agent's replay memory: enqueue and minibatch sampling (be_rl_replay.hip, additive to ABI 12) ---- */
 
 /*

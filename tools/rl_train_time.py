@@ -7,7 +7,12 @@
                with TD, decay and the Polyak update in torch ops and a host repack of the target FCModel
     oracle     tests/rl_train_ref.py's NumPy step (CPU; one step)
 
-    python tools/rl_train_time.py [--steps 20] [--warmup 3] [--no-oracle]
+    python tools/rl_train_time.py [--steps 20] [--warmup 3] [--no-oracle] [--opt {adam,bundle_entropy}]
+
+--opt bundle_entropy: the step with the bundle-entropy inner optimiser -- captured, eager, per launch --, the
+target solve as the one-launch entry against the three-step composition (--repeats timings of --steps calls each: min, median,
+max) and act() at B = 1 (context + inner optimiser, wall clock, median of 50 as tools/act_latency.py) for both optimisers.
+The host-composed path and the oracle are the adam branch's.
 Prints one JSON line."""
 import argparse
 import dataclasses
@@ -23,7 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
-from icnn_amd import picnn, rl_adam, rl_train, train  # noqa: E402
+from icnn_amd import picnn, rl_adam, rl_bundle, rl_train, train  # noqa: E402
 
 
 def _ms(fn, steps, warmup):
@@ -39,13 +44,31 @@ def _ms(fn, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+def _act_us(model, solver, obs):
+    """context + inner optimiser at one observation: wall clock, median of 50 (tools/act_latency.py)"""
+    for _ in range(5):
+        solver.solve(model.context(obs))
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(50):
+        t0 = time.perf_counter()
+        solver.solve(model.context(obs))
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return 1e6 * float(np.median(ts))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--no-oracle", action="store_true")
+    ap.add_argument("--opt", choices=rl_train.OPTS, default="adam")
+    ap.add_argument("--n-iter", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=7)
     args = ap.parse_args()
+    bundle = args.opt == "bundle_entropy"
     B = args.batch
     spec = dataclasses.replace(picnn.halfcheetah_spec(), action_box=False)
     params = picnn.init_params(spec, 0, "spread", yu_bias=1.0, gate_bias=1.0)
@@ -55,9 +78,9 @@ def main():
     rew = torch.from_numpy((2 * rng.randn(B)).astype(np.float32)).cuda()
     ob2 = obs + 0.1 * torch.randn_like(obs)
     term = torch.from_numpy(rng.rand(B) < 0.2).cuda()
-    out = {"batch": B, "params": None}
+    out = {"batch": B, "params": None, "opt": args.opt}
 
-    tr = rl_train.CriticTrainer(picnn.FCModel(spec, params), picnn.FCModel(spec, params), B)
+    tr = rl_train.CriticTrainer(picnn.FCModel(spec, params), picnn.FCModel(spec, params), B, opt=args.opt, n_iter=args.n_iter)
     tr.initialise()
     out["params"] = tr.opt.n
     out["eager_ms"] = _ms(lambda: tr.step(obs, act, rew, ob2, term), args.steps, args.warmup)
@@ -74,14 +97,32 @@ def main():
     grad = train.surrogate_grad(tr.critic, tr.obs, (tr.act, tr.c), flat=True)
     stages = {
         "target_context": lambda: tr.target.context(tr.ob2),
-        "target_adam": lambda: tr.solver.solve(ctx2),
+        ("target_bundle" if bundle else "target_adam"): lambda: tr.solver.solve(ctx2),
         "critic_context": lambda: tr.critic.context(tr.obs),
         "critic_fg": lambda: tr.critic.fg(ctx, tr.act),
-        "rl_td": lambda: tr.td_loss(e, res.f_best, None),
+        "rl_td": (lambda: tr.td_loss(e, res.q, res.act)) if bundle else (lambda: tr.td_loss(e, res.f_best, None)),
         "surrogate_grad": lambda: train.surrogate_grad(tr.critic, tr.obs, (tr.act, tr.c), flat=True),
         "rl_critic_update": lambda: tr.update(grad),
     }
     out["launch_ms"] = {k: _ms(f, args.steps, args.warmup) for k, f in stages.items()}
+    if bundle:
+        # the target solve alone: the one-launch entry against [solve_fc_reset, 2y - 1, fc_fg] on the same build, interleaved
+        solvers = {"entry": rl_bundle.BundleActionSolver(tr.target, B, args.n_iter, entry=True),
+                   "composed": rl_bundle.BundleActionSolver(tr.target, B, args.n_iter, entry=False)}
+        times = {k: [] for k in solvers}
+        for _ in range(args.repeats):
+            for k, sv in solvers.items():
+                times[k].append(_ms(lambda: sv.solve(ctx2), args.steps, args.warmup))
+        assert solvers["entry"].used_entry and not solvers["composed"].used_entry
+        out["solve_ms"] = {k: {"min": min(t), "median": float(np.median(t)), "max": max(t)} for k, t in times.items()}
+        # act() at B = 1, both optimisers on one critic (tools/act_latency.py's model)
+        model1 = picnn.FCModel(spec, picnn.init_params(spec, 11, "spread", yu_bias=1.0, gate_bias=1.0))
+        obs1 = torch.from_numpy(np.random.RandomState(12).randn(1, spec.n_features).astype(np.float32)).cuda()
+        out["act_us"] = {"adam": _act_us(model1, rl_adam.AdamSolver(model1, 1, 1000), obs1),
+                         "bundle_entropy": _act_us(model1, rl_bundle.BundleActionSolver(model1, 1, args.n_iter), obs1),
+                         "bundle_entropy_composed": _act_us(model1, rl_bundle.BundleActionSolver(model1, 1, args.n_iter, entry=False), obs1)}
+        print(json.dumps(out))
+        return
 
     # the host-composed path: the existing pieces, torch ops for TD / decay / Polyak, a host repack of the target
     critic, target = picnn.FCModel(spec, params), picnn.FCModel(spec, params)
