@@ -68,21 +68,12 @@ int check_bn_mode(const icnn_be_bn_moving *mv, int mode, int updates, const int 
     return 0;
 }
 
-// what icnn_be_fc_gd, icnn_be_conv_gd and icnn_be_ficnn_gd refuse alike
+// what the GD and PGD entries of every model refuse alike; constants_ok: gd_constants_ok / pgd_constants_ok of the call's own
 template <typename Model>
 int check_gd_args(const Model *model, const float *ctx, const double *y0, const double *y_out, const void *workspace, int batch,
-                  int n_iter, double lr, double momentum) {
+                  int n_iter, bool constants_ok) {
     if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
-    if (batch < 0 || n_iter < 1 || !icnn_be::gd_constants_ok(lr, momentum)) return ICNN_BE_EINVAL;
-    return 0;
-}
-
-// what icnn_be_fc_pgd and icnn_be_conv_pgd refuse alike
-template <typename Model>
-int check_pgd_args(const Model *model, const float *ctx, const double *y0, const double *y_out, const void *workspace, int batch,
-                   int n_iter, double lr, double lo, double hi) {
-    if (!model || !ctx || !y0 || !y_out || !workspace || !model->wpack) return ICNN_BE_EINVAL;
-    if (batch < 0 || n_iter < 1 || !icnn_be::pgd_constants_ok(lr, lo, hi)) return ICNN_BE_EINVAL;
+    if (batch < 0 || n_iter < 1 || !constants_ok) return ICNN_BE_EINVAL;
     return 0;
 }
 
@@ -772,7 +763,8 @@ size_t icnn_be_gd_workspace_bytes(int batch, int n) {
 
 int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                   double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
+    const bool constants_ok = icnn_be::gd_constants_ok(lr, momentum);
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, constants_ok)) return rc;
     if (model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     if (batch == 0) return 0;
@@ -784,7 +776,8 @@ int icnn_be_fc_gd(const icnn_be_fc_model *model, const float *ctx, const double 
 
 int icnn_be_conv_gd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                     double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
+    const bool constants_ok = icnn_be::gd_constants_ok(lr, momentum);
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, constants_ok)) return rc;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (batch == 0) return 0;
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
@@ -798,7 +791,8 @@ size_t icnn_be_pgd_workspace_bytes(int batch, int n) {
 
 int icnn_be_fc_pgd(const icnn_be_fc_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                    double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace, void *stream) {
-    if (int rc = check_pgd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, lo, hi)) return rc;
+    const bool constants_ok = icnn_be::pgd_constants_ok(lr, lo, hi);
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, constants_ok)) return rc;
     if (model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
     if (batch == 0) return 0;
@@ -810,7 +804,8 @@ int icnn_be_fc_pgd(const icnn_be_fc_model *model, const float *ctx, const double
 
 int icnn_be_conv_pgd(const icnn_be_conv_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                      double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace, void *stream) {
-    if (int rc = check_pgd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, lo, hi)) return rc;
+    const bool constants_ok = icnn_be::pgd_constants_ok(lr, lo, hi);
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, constants_ok)) return rc;
     if (int rc = icnn_be::conv_check_model(*model)) return rc;
     if (batch == 0) return 0;
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
@@ -952,7 +947,8 @@ int icnn_be_ficnn_fg(const icnn_be_ficnn_model *model, const float *ctx, const d
 
 int icnn_be_ficnn_gd(const icnn_be_ficnn_model *model, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                      double momentum, double *y_out, double *traj, float *f_out, void *workspace, void *stream) {
-    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, lr, momentum)) return rc;
+    const bool constants_ok = icnn_be::gd_constants_ok(lr, momentum);
+    if (int rc = check_gd_args(model, ctx, y0, y_out, workspace, batch, n_iter, constants_ok)) return rc;
     if (int rc = icnn_be::ficnn_check_model(*model)) return rc;
     if (batch == 0) return 0;
     return done(icnn_be::launch_ficnn_gd(*model, ctx, y0, batch, n_iter, lr, momentum, y_out, traj, f_out, workspace,

@@ -3,8 +3,8 @@
 //                       v_mfma_f32_16x16x4_f32 against pre-packed B fragments, ReLU masks recovered from the signs of the
 //                       stored activations (the design of fc_fg_tile, DESIGN.md §4, without gate or yu operands)
 //     ficnn_gd_kernel   unrolled momentum GD: a persistent workgroup per tile alternating phase A (the fg tile) and phase B
-//                       (the float32 update, one wave per sample), plus a final phase A for E(y_K): the tile loop of
-//                       be_gd_dev.h that gd_fc_kernel (be_gd.hip) instantiates too, set up by the same gd_fill_args
+//                       (the float32 update, one wave per sample), plus a final phase A for E(y_K): be_gd_dev.h's gd_tile_loop
+//                       with MomentumRule around this unit's tile, set up by gd_fill_args like gd_fc_kernel (be_gd.hip)
 //     the context       c_i = x Wx_i + b_i of every evaluated layer: one f32-MFMA GEMM (launch_tr_gemm) and a bias row
 // Every float32 operation of the tile is written out (no contraction), so the same inputs give the same bits on every call
 // and the GD loop is bit-identical to a loop of ficnn fg launches plus the update.
@@ -209,14 +209,14 @@ __global__ __launch_bounds__(NTHREADS) void ficnn_fg_kernel(FicnnArgs a) {
     ficnn_fg_tile(a, blockIdx.x, lds);
 }
 
-// ---- unrolled momentum GD: the tile loop of be_gd_dev.h around ficnn_fg_tile ----
+// ---- unrolled momentum GD: the tile loop of be_gd_dev.h around ficnn_fg_tile, under the momentum rule ----
 struct FicnnTile {
     template <typename A>
     static __device__ __forceinline__ void run(const A &fa, int tile, float *lds) { ficnn_fg_tile(fa, tile, lds); }
 };
 typedef GdTileArgs<FicnnArgs> FicnnGdArgs;
 
-__global__ __launch_bounds__(NTHREADS) void ficnn_gd_kernel(FicnnGdArgs a) { gd_tile_loop<FicnnTile>(a); }
+__global__ __launch_bounds__(NTHREADS) void ficnn_gd_kernel(FicnnGdArgs a) { gd_tile_loop<FicnnTile, MomentumRule>(a); }
 
 // ---- context: ctx = x Wx + b ----
 __global__ void ficnn_bias_kernel(float *ctx, const float *b, int C, size_t total) {

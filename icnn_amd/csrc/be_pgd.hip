@@ -8,12 +8,11 @@
 //     e_k     = float64(E) + sum_j [ yf log yf + (1 - yf) log(1 - yf) ]  float64; a NaN term counts 0 (the scripts' entr())
 //     G_k     = (float64(g) + log yf) - log(1 - yf)
 //     y_{k+1} = min(max(y_k - lr G_k, lo), hi)                          float64, no contraction
-// K iterations always (no stopping rule), no coupling between samples.  The three forms mirror be_gd.hip's and take
-// launch_fc_gd's dispatch rule:
-//     pgd_fc_kernel     a persistent workgroup per 16-sample tile alternating phase A (fc_fg_tile) and phase B (one wave per
-//                       sample: the update above), y in the caller's y_out, g and E in the workspace
-//     pgd_rows_kernel   at most two samples per CU: context rows and the float64 iterate in LDS for the whole loop
-//     pgd_init_kernel / pgd_conv_update_kernel   the conv model's form: K rounds of the conv fg launches, each followed by a
+// K iterations always (no stopping rule), no coupling between samples.  This unit is the iterate loop of be_gd_dev.h with
+// PgdRule, in the three forms and under the dispatch rule that be_gd.hip gives the momentum rule:
+//     pgd_fc_kernel     gd_tile_loop around fc_fg_tile: y in the caller's y_out, g and E in the workspace
+//     pgd_rows_kernel   gd_rows_loop (be_gd_rows_dev.h): at most two samples per CU, context rows and the float64 iterate in LDS
+//     pgd_init_kernel / pgd_conv_update_kernel / pgd_conv_final_kernel   the conv model's launches inside conv_gd_rounds: a
 //                       workgroup per sample doing the update and e_k
 // A sample's entropy sum is formed in an order that depends on n alone (lane-strided partials in index order, then a fixed
 // butterfly; the conv form: thread-strided partials and a fixed tree), so e_k has the same bits whatever the batch.
@@ -23,8 +22,7 @@
 #include <cmath>
 
 #include "be_kernels.h"
-#include "be_picnn_fc_dev.h"
-#include "be_picnn_fc_rows_dev.h"
+#include "be_gd_rows_dev.h"
 
 namespace icnn_be {
 
@@ -58,8 +56,11 @@ __device__ __forceinline__ double entr_at(double y, bool round32) {
 
 __device__ __forceinline__ double clip(double y, double lo, double hi) { return fmin(fmax(y, lo), hi); }
 
-struct PgdArgs {
-    FcArgs fa;             // fa.y = y (the iterate), fa.g = per-iteration dE/dy, fa.f = per-iteration E
+// ---- the PGD rule: a float64 y from clip(y0); e_k = float64(E) + the wave's sum of the entropy terms per iteration, e_K
+// from the final evaluation ----
+template <typename FA>
+struct PgdTileArgs {
+    FA fa;                 // fa.y = y (the iterate), fa.g = per-iteration dE/dy, fa.f = per-iteration E
     const double *y0;      // [B][n] start
     double *y;             // [B][n] the iterate, y_K on exit (the caller's y_out)
     double *obj;           // [K][B] e_k, or nullptr
@@ -67,126 +68,35 @@ struct PgdArgs {
     int n_iter;
     double lr, lo, hi;
 };
+typedef PgdTileArgs<FcArgs> PgdArgs;
 
-// ---- tile form: the loop of be_gd_dev.h's gd_tile_loop with this unit's phase B (same recipe: arguments read from the
-// kernel-argument segment, thread index read opaquely, -mllvm -disable-machine-licm for the unit) ----
-typedef const __attribute__((address_space(4))) PgdArgs KPgd;
-
-__device__ __forceinline__ void pgd_phase_fg(KPgd *kp, int tile) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    asm volatile("" : "+s"(kp), "+s"(tile));
-    fc_fg_tile(kp->fa, tile, lds);
-}
-
-// Phase B: wave w updates sample tile * TM + w; final: the entropy of y_K alone (e_K = E(y_K) + ...), no update
-__device__ __forceinline__ void pgd_phase_update(KPgd *kp, int tile, int k, bool final) {
-#pragma clang fp contract(off)
-    asm volatile("" : "+s"(kp), "+s"(tile), "+s"(k));
-    const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-    const int n = kp->fa.n, u = tile * TM + wave;
-    if (u >= kp->fa.batch) return;
-    const size_t row = (size_t)u * n;
-    const double lr = kp->lr, lo = kp->lo, hi = kp->hi;
-    double part = 0.0;
-    for (int j = lane; j < n; j += 64) {
-        double y = kp->y[row + j];
-        if (final) {
-            part += entr_at(y, true);
-        } else {
-            part += pgd_step(y, kp->fa.g[row + j], lr, lo, hi);
-            kp->y[row + j] = y;
-        }
+struct PgdRule {
+    template <typename FA> using Args = PgdTileArgs<FA>;
+    static constexpr bool sums = true;
+    static constexpr size_t ws_state_bytes = 0;
+    typedef double Elem;
+    struct Iter { double lr, lo, hi; };
+    template <typename A> ICNN_BE_RULE_FN Elem start(const A &a, double y0) { return clip(y0, a.lo, a.hi); }
+    ICNN_BE_RULE_FN float fed(Elem y) { return (float)y; }
+    ICNN_BE_RULE_FN double result(Elem y) { return y; }
+    template <typename A> ICNN_BE_RULE_FN Iter iter(const A &a, int, int) { return {a.lr, a.lo, a.hi}; }
+    ICNN_BE_RULE_FN double step(const Iter &it, Elem &y, const float *g, int) { return pgd_step(y, *g, it.lr, it.lo, it.hi); }
+    ICNN_BE_RULE_FN double term(Elem y) { return entr_at(y, true); }
+    template <typename A> ICNN_BE_RULE_FN bool wants_final(const A &a) { return a.obj_final != nullptr; }
+    template <typename A> ICNN_BE_RULE_FN double *out(const A &a, int k, bool final) {
+        return final ? a.obj_final : (a.obj ? a.obj + (size_t)k * a.fa.batch : nullptr);
     }
-    const double ent = wave_sum(part);
-    double *out = final ? kp->obj_final : (kp->obj ? kp->obj + (size_t)k * kp->fa.batch : nullptr);
-    if (out && lane == 0) out[u] = (double)kp->fa.f[u] + ent;
-}
-
-__global__ __launch_bounds__(NTHREADS) void pgd_fc_kernel(PgdArgs a) {
-    KPgd *kp = (KPgd *)__builtin_amdgcn_kernarg_segment_ptr();
-    const int tile = blockIdx.x;
-    {
-        const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-        const int n = a.fa.n, u = tile * TM + wave;
-        if (u < a.fa.batch)
-            for (int j = lane; j < n; j += 64) {
-                const size_t i = (size_t)u * n + j;
-                a.y[i] = clip(a.y0[i], a.lo, a.hi);
-            }
-    }
-    __syncthreads();
-    const int K = a.n_iter;
-    for (int k = 0; k < K; ++k) {
-        pgd_phase_fg(kp, tile);
-        __syncthreads();                                 // g and E of the tile visible to its update waves
-        pgd_phase_update(kp, tile, k, false);
-        __syncthreads();                                 // y_{k+1} visible to the tile's next phase A
-    }
-    if (a.obj_final) {
-        pgd_phase_fg(kp, tile);
-        __syncthreads();
-        pgd_phase_update(kp, tile, K, true);
-    }
-}
-
-// ---- rows form ----
-struct PgdRowsArgs {
-    PgdArgs a;
-    RowsLayout lay;
-    int per_wg;
-    int y_off;             // LDS floats (an even number): per sample the float64 iterate y[npad], behind the rows layout
+    // global memory: the caller's y_out.  LDS: per sample y[npad] in float64 (the rows layout ends 16-byte aligned)
+    template <typename A> ICNN_BE_RULE_FN Elem load(const A &a, size_t i) { return a.y[i]; }
+    template <typename A> ICNN_BE_RULE_FN void store(const A &a, size_t i, Elem y) { a.y[i] = y; }
+    static constexpr int lds_floats(int npad) { return 2 * npad; }
+    ICNN_BE_RULE_FN Elem lds_load(const float *s, int, int j) { return reinterpret_cast<const double *>(s)[j]; }
+    ICNN_BE_RULE_FN void lds_store(float *s, int, int j, Elem y) { reinterpret_cast<double *>(s)[j] = y; }
 };
 
-__global__ __launch_bounds__(RTHREADS) void pgd_rows_kernel(PgdRowsArgs r) {
-#pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const PgdArgs &a = r.a;
-    const FcArgs &fa = a.fa;
-    const RowsLayout &lay = r.lay;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int n = fa.n, npad = pad16(n), RF = lay.row_floats;
-    const int s_base = blockIdx.x * r.per_wg;
-    const int batch = fa.batch - s_base < r.per_wg ? fa.batch - s_base : r.per_wg;
-    double *ys = reinterpret_cast<double *>(lds + r.y_off) + wave * npad;     // only touched by waves < batch
-    rows_setup(fa, lay, lds, s_base, batch, tid);
-    if (wave < batch) {
-        float *row = lds + wave * RF;
-        for (int j = lane; j < n; j += 64) {
-            const double y = clip(a.y0[(size_t)(s_base + wave) * n + j], a.lo, a.hi);
-            ys[j] = y;
-            rows_set_input(fa, lay, row, j, (float)y);
-        }
-    }
-    __syncthreads();
-    const double lr = a.lr, lo = a.lo, hi = a.hi;
-    for (int k = 0; k < a.n_iter; ++k) {
-        rows_eval(fa, lay, lds, batch, tid, [](int) {});     // ends with a workgroup barrier
-        if (wave < batch) {
-            float *row = lds + wave * RF;
-            double part = 0.0;
-            for (int j = lane; j < n; j += 64) {
-                double y = ys[j];
-                part += pgd_step(y, row[lay.g_off + j], lr, lo, hi);
-                ys[j] = y;
-                rows_set_input(fa, lay, row, j, (float)y);
-            }
-            const double ent = wave_sum(part);
-            if (a.obj && lane == 0) a.obj[(size_t)k * fa.batch + s_base + wave] = (double)lds[lay.f_off + wave] + ent;
-        }
-        __syncthreads();
-    }
-    if (wave < batch)
-        for (int j = lane; j < n; j += 64) a.y[(size_t)(s_base + wave) * n + j] = ys[j];
-    if (a.obj_final) {
-        rows_eval(fa, lay, lds, batch, tid, [](int) {});
-        if (wave < batch) {
-            double part = 0.0;
-            for (int j = lane; j < n; j += 64) part += entr_at(ys[j], true);
-            const double ent = wave_sum(part);
-            if (lane == 0) a.obj_final[s_base + wave] = (double)lds[lay.f_off + wave] + ent;
-        }
-    }
-}
+__global__ __launch_bounds__(NTHREADS) void pgd_fc_kernel(PgdArgs a) { gd_tile_loop<FcTile, PgdRule>(a); }
+
+__global__ __launch_bounds__(RTHREADS) void pgd_rows_kernel(GdRowsArgs<PgdRule> r) { gd_rows_loop(r); }
 
 // ---- conv model: elementwise start, and a workgroup per sample for the update around the conv fg launches ----
 constexpr int CTHREADS = 256;
@@ -342,22 +252,9 @@ __global__ __launch_bounds__(OTHREADS) void dual_bound_kernel(icnn_be_state st, 
     if (lane == 0) out[u] = lh - sp;
 }
 
-struct PgdWorkspace {
-    size_t g, f, total;
-};
-PgdWorkspace pgd_workspace(int batch, int n) {
-    PgdWorkspace w;
-    const size_t b = (size_t)(batch > 0 ? batch : 1), bn = b * (size_t)n;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    w.g = take(bn * 4); w.f = take(b * 4);
-    w.total = o;
-    return w;
-}
-
 }  // namespace
 
-size_t pgd_workspace_bytes(int batch, int n) { return pgd_workspace(batch, n).total; }
+size_t pgd_workspace_bytes(int batch, int n) { return gd_workspace(batch, n, PgdRule::ws_state_bytes).total; }
 
 bool pgd_constants_ok(double lr, double lo, double hi) {
     return std::isfinite(lr) && 0.f < (float)lo && (float)hi < 1.f && lo < hi;
@@ -368,54 +265,33 @@ hipError_t launch_fc_pgd(const icnn_be_fc_model &m, const float *ctx, const doub
     PgdArgs a{};
     int lds = 0;
     if (fill_args(m, a.fa, lds) != 0) return hipErrorInvalidValue;
-    const PgdWorkspace w = pgd_workspace(batch, m.n);
-    unsigned char *base = static_cast<unsigned char *>(ws);
-    a.y0 = y0; a.y = y_out; a.obj = obj; a.obj_final = obj_final; a.n_iter = n_iter;
+    gd_fill_loop(a, y0, y_out, n_iter, ws, batch, PgdRule::ws_state_bytes);
+    a.obj = obj; a.obj_final = obj_final;
     a.lr = lr; a.lo = lo; a.hi = hi;
-    a.fa.y = y_out; a.fa.batch = batch; a.fa.finished = nullptr;
-    a.fa.g = reinterpret_cast<float *>(base + w.g);
-    a.fa.f = reinterpret_cast<float *>(base + w.f);
     a.fa.ctx = ctx; a.fa.prof = fc_profile_buffer();
-    // at most two samples per CU: a workgroup per one or two samples on the VALU path (launch_fc_gd's rule)
-    const int cus = device_cus();
-    const int per_wg = (batch + cus - 1) / cus;
-    if (per_wg <= 2) {
-        PgdRowsArgs r{};
-        const int rows_bytes = (rows_layout(m, per_wg, r.lay) + 7) & ~7;      // the float64 iterate behind it, 8-byte aligned
-        const int y_bytes = per_wg * 2 * pad16(m.n) * 4;
-        if (rows_bytes + y_bytes <= LDS_BYTES) {
-            r.a = a;
-            r.per_wg = per_wg;
-            r.y_off = rows_bytes / 4;
-            return launch_kernel(pgd_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_bytes + y_bytes,
-                                 stream, r);
-        }
-    }
-    if (lds > LDS_BYTES) return hipErrorNotSupported;
-    return launch_kernel(pgd_fc_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
+    return launch_fc_gd_rule<PgdRule>(m, a, batch, lds, pgd_fc_kernel, pgd_rows_kernel, stream);
 }
 
 hipError_t launch_conv_pgd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                            double lo, double hi, double *y_out, double *obj, double *obj_final, void *ws,
                            hipStream_t stream) {
     const int n = m.H * m.W;
-    const PgdWorkspace w = pgd_workspace(batch, n);
+    const GdWorkspace w = gd_workspace(batch, n, PgdRule::ws_state_bytes);
     unsigned char *base = static_cast<unsigned char *>(ws);
     float *g = reinterpret_cast<float *>(base + w.g), *f = reinterpret_cast<float *>(base + w.f);
     const size_t count = (size_t)batch * n;
     const dim3 grid((unsigned)((count + CTHREADS - 1) / CTHREADS));
-    if (hipError_t e = launch_kernel(pgd_init_kernel, grid, dim3(CTHREADS), 0, stream, y0, y_out, count, lo, hi); e != hipSuccess)
-        return e;
-    for (int k = 0; k < n_iter; ++k) {
-        if (hipError_t e = launch_conv_fg(m, ctx, y_out, batch, f, g, nullptr, stream); e != hipSuccess) return e;
-        hipError_t e = launch_kernel(pgd_conv_update_kernel, dim3(batch), dim3(CTHREADS), 0, stream, y_out, (const float *)g,
-                                     (const float *)f, obj ? obj + (size_t)k * batch : nullptr, n, lr, lo, hi);
-        if (e != hipSuccess) return e;
-    }
-    if (!obj_final) return hipSuccess;
-    if (hipError_t e = launch_conv_fg(m, ctx, y_out, batch, f, g, nullptr, stream); e != hipSuccess) return e;
-    return launch_kernel(pgd_conv_final_kernel, dim3(batch), dim3(CTHREADS), 0, stream, (const double *)y_out, (const float *)f,
-                         obj_final, n);
+    return conv_gd_rounds(
+        m, ctx, y_out, batch, n_iter, f, g, obj_final != nullptr, stream,
+        [&] { return launch_kernel(pgd_init_kernel, grid, dim3(CTHREADS), 0, stream, y0, y_out, count, lo, hi); },
+        [&](int k) {
+            return launch_kernel(pgd_conv_update_kernel, dim3(batch), dim3(CTHREADS), 0, stream, y_out, (const float *)g,
+                                 (const float *)f, obj ? obj + (size_t)k * batch : nullptr, n, lr, lo, hi);
+        },
+        [&] {
+            return launch_kernel(pgd_conv_final_kernel, dim3(batch), dim3(CTHREADS), 0, stream, (const double *)y_out,
+                                 (const float *)f, obj_final, n);
+        });
 }
 
 hipError_t launch_entropy_objective(const float *E, const double *y, int batch, int n, double *out, hipStream_t stream) {

@@ -86,11 +86,9 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
     a.ctx = ctx; a.y = y; a.f = f; a.g = g; a.finished = finished; a.batch = batch;
     a.prof = g_fc_prof;
     if (!g_fc_prof) {       // (the phase profiler instruments the tile kernel)
-        const int cus = device_cus();
         FgRowsArgs r{};
-        const int per_wg = (batch + cus - 1) / cus;
-        const int rows_lds = rows_layout(m, per_wg <= 2 ? per_wg : 1, r.lay);
-        if (per_wg <= 2 && rows_lds <= LDS_BYTES) {        // at most two samples per CU
+        int rows_lds = 0;
+        if (const int per_wg = rows_per_wg(m, batch, 0, r.lay, rows_lds)) {        // at most two samples per CU
             r.fa = a;
             r.per_wg = per_wg;
             return launch_kernel(fc_fg_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_lds, stream, r);

@@ -47,6 +47,19 @@ inline int rows_layout(const icnn_be_fc_model &m, int rows, RowsLayout &r) {
     return o * 4;
 }
 
+// The dispatch rule of the FC launchers (launch_fc_fg, the GD and PGD loops): with at most two samples per CU a workgroup
+// per one or two samples takes this path, when the layout and `extra` more LDS bytes per sample behind it fit.  Returns the
+// samples per workgroup, with r and the layout's bytes filled in (a multiple of 16: every part above is a multiple of four
+// floats), or 0: use the tiles.
+inline int rows_per_wg(const icnn_be_fc_model &m, int batch, int extra, RowsLayout &r, int &rows_bytes) {
+    const int cus = device_cus(), per_wg = (batch + cus - 1) / cus;
+    if (per_wg <= 2) {
+        rows_bytes = rows_layout(m, per_wg, r);
+        if (rows_bytes + per_wg * extra <= LDS_BYTES) return per_wg;
+    }
+    return 0;
+}
+
 // acc[s] += A[s][0 .. 16 KB) . W[., col] in MFMA order for S samples that share every weight fragment; A[s] in LDS,
 // Wp a packed operand.  KB = kblocks(K), a multiple of PF: the pack carries zero fragments and the LDS operands zero
 // columns up to there, so the loop body is straight-line code -- a PF-slot fragment ring filled GV_AHEAD k-blocks

@@ -27,11 +27,10 @@ import torch
 from . import _lib
 
 LO, HI = 1e-6, 1.0 - 1e-6                   # the scripts' proj (ebundle-vs-gd.py:116-117)
-_PGD_ENTRY = {"icnn_be_fc_gd": "icnn_be_fc_pgd", "icnn_be_conv_gd": "icnn_be_conv_pgd"}
 
 
 def _entry(model):
-    entry = _PGD_ENTRY.get(getattr(model, "gd_entry", None))
+    entry = getattr(model, "pgd_entry", None)          # stated by the model class, next to gd_entry (picnn.py)
     if entry is None:
         raise TypeError("pgd serves FCModel and ConvModel, not %s" % type(model).__name__)
     return entry

@@ -487,6 +487,7 @@ class FCModel(_PICNNDevice):
     weights (MFMA B-fragment order, both orientations) plus the C descriptor the
     kernels take.  Re-create (or call `repack`) after every weight update."""
     solve_entry, gd_entry, context_entry = "icnn_be_solve_fc", "icnn_be_fc_gd", "icnn_be_fc_context"
+    pgd_entry = "icnn_be_fc_pgd"
     grad_entry, grad_floats_entry = "icnn_be_fc_surrogate_grad", "icnn_be_fc_grad_floats"
 
     def __init__(self, spec: FCSpec, params, device="cuda"):
@@ -849,6 +850,7 @@ def stage_conv_weights(params):
 class ConvModel(_PICNNDevice):
     """Device-resident y-path of the conv PICNN (struct icnn_be_conv_model + packed weights)."""
     solve_entry, gd_entry, context_entry = "icnn_be_solve_conv", "icnn_be_conv_gd", "icnn_be_conv_context"
+    pgd_entry = "icnn_be_conv_pgd"
     grad_entry, grad_floats_entry = "icnn_be_conv_surrogate_grad", "icnn_be_conv_grad_floats"
     has_bn = True
 

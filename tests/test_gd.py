@@ -228,6 +228,28 @@ def test_fc_equals_loop_of_fg(B):
     assert torch.equal(y, yy.double()) and torch.equal(E, E_ref)
 
 
+@pytest.mark.gpu
+def test_optional_outputs_do_not_change_y():
+    """The loop decides by null pointers what it records: all four combinations of trajectory and energy, on the rows path
+    (B = 17) and on the tiles with a partial last tile (530), leave y_K and every output that is present unchanged."""
+    from icnn_amd import gd
+    spec = _small_spec()
+    for B in (17, 530):
+        params, x, y0 = _fc_problem(spec, B, 0)
+        model = picnn.FCModel(spec, params, "cuda")
+        ctx = model.context(torch.from_numpy(x))
+        y0 = torch.from_numpy(y0).cuda()
+        yf, trajf, Ef = gd.solve(model, ctx, y0, 3, LR, MU, trajectory=True, energy=True)
+        for trajectory in (True, False):
+            for energy in (True, False):
+                y, traj, E = gd.solve(model, ctx, y0, 3, LR, MU, trajectory=trajectory, energy=energy)
+                torch.cuda.synchronize()
+                assert (traj is not None) == trajectory and (E is not None) == energy
+                assert torch.equal(y, yf), (B, trajectory, energy)
+                assert traj is None or torch.equal(traj, trajf), (B, trajectory, energy)
+                assert E is None or torch.equal(E, Ef), (B, trajectory, energy)
+
+
 def _small_gd_problem(K, lr, mu):
     """Small spec, screened so that no float64 pre-activation along the whole trajectory (and no u-path / gate
     pre-activation) is within 1e-4 of zero: the float32 masks of the device then agree with the float64 ones."""

@@ -202,7 +202,10 @@ def test_python_solve_refuses_bad_arguments():
     spec = _small_spec()
 
     class _M:                                          # solve checks its arguments before touching the library
-        gd_entry = "icnn_be_fc_gd"
+        gd_entry, pgd_entry = "icnn_be_fc_gd", "icnn_be_fc_pgd"
+
+    class _F:                                          # a model class that states no pgd_entry, like ficnn.FICNNModel
+        gd_entry = "icnn_be_ficnn_gd"
     m = _M()
     m.spec, m.device = spec, torch.device("cpu")
     ctx = torch.zeros(3, spec.ctx_width)
@@ -216,9 +219,13 @@ def test_python_solve_refuses_bad_arguments():
     m.spec = picnn.halfcheetah_spec()
     with pytest.raises(ValueError):
         pgd.solve(m, ctx, 0.5, 3, 0.1)
-    m.spec, m.gd_entry = spec, "icnn_be_ficnn_gd"
-    with pytest.raises(TypeError):
+    m = _F()
+    m.spec, m.device = spec, torch.device("cpu")
+    with pytest.raises(TypeError, match="pgd serves FCModel and ConvModel, not _F"):
         pgd.solve(m, ctx, 0.5, 3, 0.1)
+    from icnn_amd import ficnn
+    assert not hasattr(ficnn.FICNNModel, "pgd_entry")
+    assert (picnn.FCModel.pgd_entry, picnn.ConvModel.pgd_entry) == ("icnn_be_fc_pgd", "icnn_be_conv_pgd")
     with pytest.raises(TypeError):
         pgd.bundle_trace(object())
 
@@ -375,6 +382,17 @@ def test_optional_outputs_do_not_change_y():
         torch.cuda.synchronize()
         assert obj2 is None and fin2 is None and fin3 is None
         assert torch.equal(y, y2) and torch.equal(y, y3) and torch.equal(obj, obj3)
+        # the loop decides by null pointers what it records: all four combinations, on the rows path (17) and on the tiles
+        # with a partial last tile (530), leave y and every output that is present unchanged
+        yf, objf, finf = pgd.solve(model, ctx, 0.5, 3, 0.1, trace=True, final=True)
+        for trace in (True, False):
+            for final in (True, False):
+                yc, objc, finc = pgd.solve(model, ctx, 0.5, 3, 0.1, trace=trace, final=final)
+                torch.cuda.synchronize()
+                assert (objc is not None) == trace and (finc is not None) == final
+                assert torch.equal(yc, yf), (B, trace, final)
+                assert objc is None or torch.equal(objc, objf), (B, trace, final)
+                assert finc is None or torch.equal(finc, finf), (B, trace, final)
 
 
 @pytest.mark.gpu
