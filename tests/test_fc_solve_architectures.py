@@ -483,7 +483,7 @@ def test_moving_mode_context_matches_float64(name, B):
 @pytest.mark.gpu
 @pytest.mark.parametrize("lr,mu", [(0.01, 0.3), (0.05, 0.9)])
 @pytest.mark.parametrize("B", [37, 530])
-@pytest.mark.parametrize("name", ["L1_n9", "n20_deep4", "n270", "deep8"])
+@pytest.mark.parametrize("name", ["L1_n9", "n20_deep4", "n270", "deep8", "L1_n1", "n33", "n70"])
 def test_gd_solve_bit_exact(name, B, lr, mu):
     """gd.solve with K = 4 and K = 9 against the float32 recurrence around the kernel-order oracle: trajectory, y_K and
     E(y_K) bit for bit.  Batch 37 takes gd_rows_kernel (at most two samples per CU), 530 gd_fc_kernel with a last tile of two

@@ -31,7 +31,7 @@ def _setup(spec, B, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("B", [1, 3, 17])
 def test_conv_solve_against_restatement(B):
     from icnn_amd import pgd
     K, lr = 3, 0.1
