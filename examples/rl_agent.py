@@ -56,6 +56,55 @@ class PointMass:
         return self._obs(), reward, term
 
 
+class VecPointMass:
+    """E independent PointMass environments stepped as arrays: step() returns obs [E, dimO], reward [E], term [E] and restarts
+    the environments that ended (their returned observation is the new episode's first)."""
+
+    def __init__(self, n_envs, dimO=4, dimA=2, horizon=40, dt=0.1, damping=0.1, seed=0):
+        self.E, self.dimO, self.dimA, self.horizon, self.dt, self.damping = n_envs, dimO, dimA, horizon, dt, damping
+        self.rng = np.random.RandomState(seed)
+        self.p, self.v = np.zeros((n_envs, dimA)), np.zeros((n_envs, dimA))
+        self.steps = np.zeros(n_envs, np.int64)
+
+    def _obs(self):
+        full = np.concatenate([self.p, self.v], axis=1)
+        out = np.zeros((self.E, self.dimO), np.float32)
+        k = min(self.dimO, full.shape[1])
+        out[:, :k] = full[:, :k]
+        return out
+
+    def reset(self, mask=None):
+        mask = np.ones(self.E, bool) if mask is None else mask
+        self.p[mask] = self.rng.uniform(-1, 1, (int(mask.sum()), self.dimA))
+        self.v[mask] = 0.0
+        self.steps[mask] = 0
+        return self._obs()
+
+    def step(self, action):
+        a = np.clip(np.asarray(action, np.float64).reshape(self.E, self.dimA), -1, 1)
+        self.v = (1 - self.damping) * self.v + self.dt * a
+        self.p = self.p + self.dt * self.v
+        self.steps += 1
+        reward = -((self.p * self.p).sum(1) + 0.1 * (self.v * self.v).sum(1) + 0.01 * (a * a).sum(1))
+        term = (self.steps >= self.horizon) | (np.linalg.norm(self.p, axis=1) > 4.0)
+        return self._obs(), reward, term
+
+
+def run_vector(env, agent, total):
+    """`total` training observations, E a step: an environment that ends is restarted and its noise row zeroed"""
+    agent.reset(env.reset())
+    returns, running = [], np.zeros(env.E)
+    while agent.t < total:
+        observation, reward, term = env.step(agent.act())
+        agent.observe(reward, term, observation)
+        running += reward
+        if term.any():
+            returns += running[term].tolist()
+            running[term] = 0.0
+            agent.reset(env.reset(term), mask=term)
+    return returns
+
+
 def run_episode(env, agent, test, tmax):
     """main.py:117-149"""
     agent.reset(env.reset())
@@ -95,27 +144,35 @@ def main():
     ap.add_argument("--model", choices=("ICNN", "DDPG", "NAF"), default="ICNN")
     ap.add_argument("--naf-bn", action="store_true")
     ap.add_argument("--icnn-opt", choices=("adam", "bundle_entropy"), default="adam")
+    ap.add_argument("--envs", type=int, default=None, metavar="E", help="E environments a step (a vectorised PointMass)")
     args = ap.parse_args()
+    vec = dict(n_envs=args.envs) if args.envs is not None else {}
     if args.naf_bn and args.model != "NAF":
         ap.error("--naf-bn needs --model NAF")
     if args.model == "DDPG":
         agent = rl_agent.DDPGAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
-                                   iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture)
+                                   iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture, **vec)
     elif args.model == "NAF":
         agent = rl_agent.NAFAgent(args.dimO, args.dimA, l1=args.l1size, l2=args.l2size, bsize=args.bsize, warmup=args.warmup,
-                                  iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture, naf_bn=args.naf_bn)
+                                  iters=args.iter, rmsize=args.rmsize, seed=args.seed, capture=args.capture, naf_bn=args.naf_bn, **vec)
     else:
         spec = dataclasses.replace(picnn.halfcheetah_spec(), n_features=args.dimO, n_labels=args.dimA,
                                    szs=(args.l1size, args.l2size), action_box=False)
         params = picnn.init_params(spec, args.seed)
         critic, target = picnn.FCModel(spec, params, "cuda"), picnn.FCModel(spec, params, "cuda")
         agent = rl_agent.Agent(critic, target, bsize=args.bsize, warmup=args.warmup, iters=args.iter, rmsize=args.rmsize,
-                               seed=args.seed, capture=args.capture, opt=args.icnn_opt)
+                               seed=args.seed, capture=args.capture, opt=args.icnn_opt, **vec)
     env = PointMass(args.dimO, args.dimA, seed=args.seed)
     if args.resume:
         from icnn_amd import checkpoint
         checkpoint.load(args.resume, agent)
         print("resumed {} at {} training observations".format(args.resume, agent.t))
+    if args.envs is not None:
+        returns = run_vector(VecPointMass(args.envs, args.dimO, args.dimA, seed=args.seed), agent, args.total)
+        loss = float(agent.loss.item()) if agent.t > agent.warmup and agent.iters else float("nan")
+        print("{} environments, {} training observations, {} episodes, mean return {:.4f}, loss {:.5e}".format(
+            args.envs, agent.t, len(returns), np.mean(returns) if returns else float("nan"), loss))
+        args.total = 0
     train_timestep = 0
     while train_timestep < args.total:
         rewards = [run_episode(env, agent, True, args.tmax)[0] for _ in range(args.test)]

@@ -51,6 +51,7 @@ EXPORTS = [
     "icnn_be_dual_step", "icnn_be_fc_pack_floats", "icnn_be_fc_pack", "icnn_be_fc_fg",
     "icnn_be_solve_fc", "icnn_be_solve_fc_reset", "icnn_be_conv_pack_floats", "icnn_be_conv_work_floats", "icnn_be_conv_pack", "icnn_be_conv_fg", "icnn_be_solve_conv",
     "icnn_be_implicit_feed", "icnn_be_export_active", "icnn_be_adam_workspace_bytes", "icnn_be_adam_fc", "icnn_be_adam_fc_obs",
+    "icnn_be_adam_fc_each", "icnn_be_debug_adam_each_plan",
     "icnn_be_fc_context_work_floats", "icnn_be_fc_context", "icnn_be_fc_context_stage", "icnn_be_fc_context_norm", "icnn_be_fc_clamp",
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
@@ -70,6 +71,7 @@ EXPORTS = [
     "icnn_be_gd_feed_work_bytes", "icnn_be_gd_feed", "icnn_be_gd_feed_px_work_bytes", "icnn_be_gd_feed_px",
     "icnn_be_step_gate", "icnn_be_param_update_gated", "icnn_be_gated_copy",
     "icnn_be_replay_enqueue", "icnn_be_replay_sample",
+    "icnn_be_vec_replay_enqueue", "icnn_be_vec_replay_sample", "icnn_be_explore",
     "icnn_be_gd_eval_work_bytes", "icnn_be_gd_eval", "icnn_be_macro_f1", "icnn_be_keep_best",
     "icnn_be_dataset_draw", "icnn_be_log_row",
     "icnn_be_ddpg_param_floats", "icnn_be_ddpg_work_bytes", "icnn_be_ddpg_work_offsets", "icnn_be_ddpg_chain", "icnn_be_ddpg_grads",
@@ -221,6 +223,14 @@ class Replay(C.Structure):
     _fields_ = [
         ("size", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("observations", C.c_void_p), ("actions", C.c_void_p),
         ("rewards", C.c_void_p), ("terminals", C.c_void_p), ("ctrl", C.c_void_p),
+    ]
+
+
+class VecReplay(C.Structure):
+    """struct icnn_be_vec_replay"""
+    _fields_ = [
+        ("steps", C.c_int), ("n_envs", C.c_int), ("dimO", C.c_int), ("dimA", C.c_int), ("observations", C.c_void_p),
+        ("actions", C.c_void_p), ("rewards", C.c_void_p), ("terminals", C.c_void_p), ("ctrl", C.c_void_p),
     ]
 
 
@@ -390,6 +400,10 @@ def load():
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_adam_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.icnn_be_adam_fc.restype = C.c_int
+    lib.icnn_be_adam_fc_each.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.icnn_be_adam_fc_each.restype = C.c_int
+    lib.icnn_be_debug_adam_each_plan.argtypes = [C.POINTER(FcModel), C.c_int, C.POINTER(C.c_int * 2)]
+    lib.icnn_be_debug_adam_each_plan.restype = C.c_int
     lib.icnn_be_adam_fc_obs.argtypes = [C.POINTER(FcModel), C.POINTER(FcCtx), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
     lib.icnn_be_adam_fc_obs.restype = C.c_int
     lib.icnn_be_fc_context_work_floats.argtypes = [C.POINTER(FcCtx), C.c_int]
@@ -517,6 +531,13 @@ def load():
     lib.icnn_be_replay_enqueue.restype = C.c_int
     lib.icnn_be_replay_sample.argtypes = [C.POINTER(Replay), C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 7
     lib.icnn_be_replay_sample.restype = C.c_int
+    lib.icnn_be_vec_replay_enqueue.argtypes = [C.POINTER(VecReplay)] + [C.c_void_p] * 5
+    lib.icnn_be_vec_replay_enqueue.restype = C.c_int
+    lib.icnn_be_vec_replay_sample.argtypes = [C.POINTER(VecReplay), C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 7
+    lib.icnn_be_vec_replay_sample.restype = C.c_int
+    lib.icnn_be_explore.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                    C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p]
+    lib.icnn_be_explore.restype = C.c_int
     lib.icnn_be_dataset_draw.argtypes = [C.POINTER(Dataset), C.c_int, C.c_ulonglong, C.POINTER(C.c_void_p), C.c_void_p,
                                          C.c_void_p]
     lib.icnn_be_dataset_draw.restype = C.c_int
@@ -620,6 +641,8 @@ def load():
         raise ImportError("ctypes struct layout of icnn_be_ficnn_model differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(9) != C.sizeof(Replay):
         raise ImportError("ctypes struct layout of icnn_be_replay differs from libicnn_be.so's")
+    if lib.icnn_be_struct_size(22) != C.sizeof(VecReplay):
+        raise ImportError("ctypes struct layout of icnn_be_vec_replay differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(10) != C.sizeof(Dataset) or lib.icnn_be_struct_size(11) != C.sizeof(StepLog):
         raise ImportError("ctypes struct layout of icnn_be_dataset / icnn_be_step_log differs from libicnn_be.so's")
     if lib.icnn_be_struct_size(13) != C.sizeof(DdpgArgs):
@@ -667,6 +690,16 @@ def adam_plan(model, batch, ctx=None):
     if rc < 0:
         check(rc, "icnn_be_debug_adam_plan")
     return (ADAM_KERNELS[rc], out[0], out[1], bool(out[2]), bool(out[3]))
+
+
+def adam_each_plan(model, batch):
+    """(kernel name, states per workgroup, workgroups) of icnn_be_adam_fc_each for an FcModel and a batch on the current
+    device (icnn_be_debug_adam_each_plan): the per-state stopping rule, one ordinary launch, no residency limit."""
+    out = (C.c_int * 2)()
+    rc = load().icnn_be_debug_adam_each_plan(C.byref(model), int(batch), C.byref(out))
+    if rc < 0:
+        check(rc, "icnn_be_debug_adam_each_plan")
+    return (ADAM_KERNELS[rc], out[0], out[1])
 
 
 def dual_plan(state, t):

@@ -18,7 +18,9 @@ result depends on:
     Agent, DDPGAgent, NAFAgent   its trainer, t, noise, observation, action, the RandomState (as arrays), the sampler's seed and,
                          with memory=True, the filled part of the four replay arrays and the control block (cursor, fill, draw
                          counter, status); memory=False leaves the memory out, as the reference's checkpoint does, and load()
-                         then resets it
+                         then resets it.  An agent of n_envs environments also records n_envs, the device noise [E, dimA], the
+                         exploration's step counter and seed, and its memory's arrays by time rows; load() refuses a file of
+                         another n_envs, and a single-environment file for a vector agent or the other way round
     train.BestKeeper     best, the gate counters, the snapshots of theta and of the statistics
     train.DeviceDataset  seed, n_rows, the draw counter and the control block -- not the data: a resumed run rebuilds the
                          set from its arrays and continues the uninterrupted run's batch sequence
@@ -172,7 +174,7 @@ def _agent_host(agent, with_memory) -> dict:
 
     out = {
         "agent/t": np.asarray(agent.t, np.int64), "agent/trained": np.asarray(int(agent._trained), np.int64),
-        "agent/noise": np.array(agent.noise, np.float64),
+        "agent/noise": np.array(agent.noise, np.float64) if agent.n_envs is None else agent.explorer.noise.cpu().numpy(),
         "agent/has_observation": np.asarray(int(agent.observation is not None), np.int64),
         "agent/observation": optional(agent.observation),
         "agent/has_action": np.asarray(int(agent.action is not None), np.int64),
@@ -183,6 +185,10 @@ def _agent_host(agent, with_memory) -> dict:
         "memory/dimA": np.asarray(mem.dimA, np.int64), "memory/seed": np.asarray(mem.seed, np.uint64),
         "memory/saved": np.asarray(int(with_memory), np.int64),
     }
+    if agent.n_envs is not None:       # E environments a step: the file says so, and carries the device noise's step counter
+        out["agent/n_envs"] = np.asarray(agent.n_envs, np.int64)
+        out["explore/counter"] = agent.explorer.counter.cpu().numpy()
+        out["explore/seed"] = np.asarray(agent.explorer.seed, np.uint64)
     if with_memory:
         rows = _filled(mem)
         out["memory/ctrl"] = mem.ctrl.cpu().numpy()
@@ -319,19 +325,27 @@ def load(path, obj, keeper=None, dataset=None):
     host = None
     if kind in AGENTS:
         mem = obj.memory
+        E = obj.n_envs
+        file_envs = _scalar(arrays, "agent/n_envs") if "agent/n_envs" in arrays else None
+        if file_envs != E:
+            raise ValueError("n_envs: the file is of %s, the object of %s" % tuple(
+                "a single-environment agent" if e is None else "an agent of %d environments" % e for e in (file_envs, E)))
         for name, mine in (("memory/rmsize", mem.size), ("memory/dimO", mem.dimO), ("memory/dimA", mem.dimA)):
             if _scalar(arrays, name) != mine:
                 raise ValueError("%s: %d in the file, %d here" % (name.split("/")[1], _scalar(arrays, name), mine))
         host = {k: _scalar(arrays, "agent/" + k) for k in ("t", "trained", "has_observation", "has_action")}
         host["seed"] = _scalar(arrays, "memory/seed")
         host["saved"] = bool(_scalar(arrays, "memory/saved"))
-        _check_array(arrays, "agent/noise", (obj.dimA,), np.float64)
+        _check_array(arrays, "agent/noise", (obj.dimA,) if E is None else (E, obj.dimA), np.float64)
+        if E is not None:
+            _check_array(arrays, "explore/counter", (1,), np.int32)
+            host["explore_seed"] = _scalar(arrays, "explore/seed")
         for name in ("agent/observation", "agent/action"):
             if name not in arrays:
                 raise ValueError("%s: missing from the file" % name)
-        if host["has_observation"] and arrays["agent/observation"].size != obj.dimO:
+        if host["has_observation"] and arrays["agent/observation"].size != (E or 1) * obj.dimO:
             raise ValueError("agent/observation: %d values in the file, dimO is %d" % (arrays["agent/observation"].size, obj.dimO))
-        if host["has_action"] and arrays["agent/action"].size != obj.dimA:
+        if host["has_action"] and arrays["agent/action"].size != (E or 1) * obj.dimA:
             raise ValueError("agent/action: %d values in the file, dimA is %d" % (arrays["agent/action"].size, obj.dimA))
         _check_array(arrays, "rng/keys", (624,), np.uint32)
         _check_array(arrays, "rng/cached_gaussian", (), np.float64)
@@ -357,9 +371,20 @@ def load(path, obj, keeper=None, dataset=None):
         if kind in AGENTS:
             mem = obj.memory
             obj.t, obj._trained = int(host["t"]), bool(host["trained"])
-            obj.noise = arrays["agent/noise"].copy()
             obj.observation = arrays["agent/observation"].copy() if host["has_observation"] else None
             obj.action = arrays["agent/action"].copy() if host["has_action"] else None
+            if obj.n_envs is None:
+                obj.noise = arrays["agent/noise"].copy()
+            else:                                               # the device side of the vector cycle
+                ex = obj.explorer
+                ex.noise.copy_(torch.from_numpy(arrays["agent/noise"]))
+                ex.counter.copy_(torch.from_numpy(arrays["explore/counter"]))
+                ex.seed = int(host["explore_seed"])
+                if obj.observation is not None:
+                    obj.observation = obj.observation.astype(np.float32).reshape(obj.n_envs, obj.dimO)
+                    obj._obs_dev.copy_(torch.from_numpy(obj.observation))
+                if obj.action is not None:
+                    ex.action.copy_(torch.from_numpy(obj.action.reshape(obj.n_envs, obj.dimA)))
             obj.rng.set_state(("MT19937", arrays["rng/keys"], int(host["pos"]), int(host["has_gauss"]),
                                float(arrays["rng/cached_gaussian"])))
             if int(host["seed"]) != mem.seed:                   # a captured sampler launch carries the seed it was captured with

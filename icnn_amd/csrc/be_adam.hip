@@ -77,6 +77,10 @@ __device__ __forceinline__ void phase_fg(KArgs *kp, int tile) {
     fc_fg_tile(kp->fa, tile, lds);
 }
 
+// EACH: the stopping rule of every state on its own (icnn_be_adam_fc_each): drift from the state's own displacement, a state
+// whose rule has fired is frozen (phase A still evaluates its row, phase B leaves it alone), the workgroup leaves when none of
+// its states is live.  No exchange between workgroups, a.iters is [B].
+template <bool EACH>
 __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -95,6 +99,8 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
     double pow1 = 1.0, pow2 = 1.0, drift = -1.0;                    // drift < 0: not yet defined (:186)
     float best_f = 0.f;                                             // wave-uniform, written out when it improves
     int it = 0;
+    bool live = mine;                                               // EACH: this wave's state has not fired yet
+    int fired = a.max_iter;
     long long tick = ICNN_BE_PROF_ON(a.fa.prof) ? (long long)__builtin_readcyclecounter() : 0;
     auto lap = [&](int phase) {          // diagnostic only (tools/fc_phase_profile.py adam): slots 14/15 of phase A's table
         if (ICNN_BE_PROF_ON(a.fa.prof)) {
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
         if (ICNN_BE_PROF_ON(a.fa.prof)) tick = (long long)__builtin_readcyclecounter();
         // ---- f = negQ + sum_j pen_j, g += d pen / d act; best iterate (:176-183) ----
         double moved = 0.0;
-        if (mine) {
+        if (EACH ? live : mine) {
             float tot = 0.f;
             for (int j0 = 0; j0 < n; j0 += 64) {
                 const int j = j0 + lane;
@@ -141,8 +147,20 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
                 moved = sqrt(wave_sum(d2));
             }
         }
-        // ---- stopping rule over the whole batch (:184-192) ----
-        if (it > 0) {
+        // ---- stopping rule over the whole batch (:184-192), or over this state as a batch of one ----
+        if constexpr (EACH) {
+            if (it > 0 && live) {
+                drift = drift < 0.0 ? moved : 0.5 * drift + 0.5 * moved;
+                if (drift < 1e-3 && it > 5) { live = false; fired = it; }
+            }
+            if (it > 5) {                                           // the exit is the workgroup's: OR of `live` over the waves
+                if (lane == 0) red[wave] = live ? 1.0 : 0.0;
+                __syncthreads();
+                double any = 0.0;
+                for (int w = 0; w < NWAVE; ++w) any += red[w];
+                if (any == 0.0) break;
+            }
+        } else if (it > 0) {
             if (lane == 0) red[wave] = moved;
             __syncthreads();
             if (wave == 0) {
@@ -160,7 +178,7 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
         // ---- moments and the clipped step (:194-203) ----
         pow1 *= b1;
         pow2 *= b2;
-        if (mine)
+        if (EACH ? live : mine)
             for (int j = lane; j < n; j += 64) {
                 const float ge = a.fa.g[row + j];
                 const double mj = b1 * a.m[row + j] + (double)(c1 * ge);
@@ -175,7 +193,11 @@ __global__ __launch_bounds__(NTHREADS) void adam_fc_kernel(AdamArgs a) {
         __syncthreads();                                            // act visible to the tile's next phase A
         lap(15);
     }
-    if (tile == 0 && tid == 0) *a.iters = it;
+    if constexpr (EACH) {
+        if (mine && lane == 0) a.iters[u] = fired;
+    } else if (tile == 0 && tid == 0) {
+        *a.iters = it;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -195,6 +217,7 @@ struct RowsArgs {
     CtxRowsArgs cr;                    // cr.obs != nullptr: the context rows are computed here from the observations
 };
 
+template <bool EACH>
 __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -215,6 +238,8 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
     double x = 0.0, m1 = 0.0, m2 = 0.0, best_x = 0.0, pow1 = 1.0, pow2 = 1.0, drift = -1.0;
     float best_f = 0.f;
     int it = 0;
+    bool live = wave < batch;                                         // EACH: as in adam_fc_kernel
+    int fired = r.a.max_iter;
     long long tick = ICNN_BE_PROF_ON(fa.prof) ? (long long)__builtin_readcyclecounter() : 0;
     auto lap = [&](int phase) {          // diagnostic only (tools/fc_phase_profile.py adam): [wave][phase] cycle sums
         if (ICNN_BE_PROF_ON(fa.prof)) {
@@ -231,7 +256,7 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
         // ================= phase B: the same operations as adam_fc_kernel, state in registers =================
         double moved = 0.0;
         float ge = 0.f;
-        if (wave < batch) {
+        if (EACH ? live : wave < batch) {
             const float *row = lds + wave * RF;
             float pen = 0.f;
             if (lane < n) {
@@ -249,7 +274,19 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
                 moved = sqrt(wave_sum(d * d));
             }
         }
-        if (it > 0) {
+        if constexpr (EACH) {
+            if (it > 0 && live) {
+                drift = drift < 0.0 ? moved : 0.5 * drift + 0.5 * moved;
+                if (drift < 1e-3 && it > 5) { live = false; fired = it; }
+            }
+            if (it > 5) {
+                if (lane == 0 && wave < ROWS_MAX) red[wave] = live ? 1.0 : 0.0;
+                __syncthreads();
+                double any = 0.0;
+                for (int w = 0; w < batch; ++w) any += red[w];
+                if (any == 0.0) break;
+            }
+        } else if (it > 0) {
             if (lane == 0 && wave < ROWS_MAX) red[wave] = wave < batch ? moved : 0.0;
             __syncthreads();
             double ssum = 0.0;
@@ -269,7 +306,7 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
         lap(14);
         pow1 *= b1;
         pow2 *= b2;
-        if (mine) {
+        if (EACH ? mine && live : mine) {
             m1 = b1 * m1 + (double)(c1 * ge);
             m2 = b2 * m2 + (double)(c2 * (ge * ge));
             const double mhat = m1 / (1. - pow1);
@@ -283,7 +320,11 @@ __global__ __launch_bounds__(RTHREADS) void adam_rows_kernel(RowsArgs r) {
     }
     if (mine) r.a.act_best[(size_t)(s_base + wave) * n + lane] = best_x;
     if (wave < batch && lane == 0) r.a.f_best[s_base + wave] = best_f;
-    if (blockIdx.x == 0 && tid == 0) *r.a.iters = it;
+    if constexpr (EACH) {
+        if (wave < batch && lane == 0) r.a.iters[s_base + wave] = fired;
+    } else if (blockIdx.x == 0 && tid == 0) {
+        *r.a.iters = it;
+    }
 }
 
 struct Workspace {
@@ -321,7 +362,13 @@ struct AdamLaunch {
     RowsLayout lay;       // the latency path's
 };
 
-hipError_t plan_adam(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, FcArgs &fa, AdamLaunch &p) {
+// `each` (icnn_be_adam_fc_each): the same rule for the rows path -- 1-4 states per workgroup over as many workgroups as would be
+// resident --, but nothing couples the workgroups: an ordinary launch, and any number of 16-state tiles beyond it.
+hipError_t plan_adam(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, FcArgs &fa, AdamLaunch &p,
+                     bool each = false) {
+    const void *rows_kernel = each ? reinterpret_cast<const void *>(adam_rows_kernel<true>)
+                                   : reinterpret_cast<const void *>(adam_rows_kernel<false>);
+    const void *tile_kernel = reinterpret_cast<const void *>(adam_fc_kernel<false>);
     p = AdamLaunch{};
     int lds = 0;
     if (fill_args(m, fa, lds) != 0) return hipErrorInvalidValue;
@@ -329,17 +376,16 @@ hipError_t plan_adam(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int ba
         const int rows_lds = rows_layout(m, ROWS_MAX, p.lay) + (ROWS_MAX + 1) * 8;
         int resident = 1;
         if (rows_lds <= LDS_BYTES && batch > ROWS_MAX) {      // more than one workgroup: they must all be resident
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_rows_kernel), rows_lds); e != hipSuccess) return e;
+            if (hipError_t e = ensure_dynamic_lds(rows_kernel, rows_lds); e != hipSuccess) return e;
             int per_cu = 0;
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_rows_kernel),
-                                                                        RTHREADS, rows_lds);
+            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rows_kernel, RTHREADS, rows_lds);
             if (e != hipSuccess) return e;
             resident = per_cu * device_cus();
         }
         const int per_wg = batch <= ROWS_MAX ? batch : (batch + resident - 1) / (resident > 0 ? resident : 1);
         if (rows_lds <= LDS_BYTES && per_wg >= 1 && per_wg <= ROWS_MAX) {
             const int wgs = (batch + per_wg - 1) / per_wg;
-            p.plan = {ICNN_BE_ADAM_ROWS, per_wg, wgs, wgs > 1, 0};
+            p.plan = {ICNN_BE_ADAM_ROWS, per_wg, wgs, wgs > 1 && !each, 0};
             p.lds = rows_lds;
             if (cx && !cx->batchnorm && cx->n == m.n && cx->n_layers == m.n_layers) {
                 for (int i = 0; i < m.n_layers; ++i)           // (icnn_be_adam_fc_obs has refused these already: the stage matrices
@@ -355,24 +401,23 @@ hipError_t plan_adam(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int ba
     lds = ((fa.lds_floats + 3) & ~3) * 4 + (NWAVE + 1) * 8;     // the reduction scratch behind fc_fg_tile's LDS
     if (lds > LDS_BYTES) return hipSuccess;                     // ICNN_BE_ADAM_NONE
     p.lds = lds;
-    if (tiles > 1) {
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void *>(adam_fc_kernel), lds); e != hipSuccess) return e;
+    if (tiles > 1 && !each) {
+        if (hipError_t e = ensure_dynamic_lds(tile_kernel, lds); e != hipSuccess) return e;
         int per_cu = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(adam_fc_kernel),
-                                                                    NTHREADS, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tile_kernel, NTHREADS, lds);
         if (e != hipSuccess) return e;
         if (tiles > per_cu * device_cus()) return hipSuccess;   // ICNN_BE_ADAM_NONE
     }
-    p.plan = {ICNN_BE_ADAM_TILE, TM, tiles, tiles > 1, 0};
+    p.plan = {ICNN_BE_ADAM_TILE, TM, tiles, tiles > 1 && !each, 0};
     return hipSuccess;
 }
 
 }  // namespace
 
-hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan) {
+hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan, bool each) {
     FcArgs fa{};
     AdamLaunch p;
-    const hipError_t e = plan_adam(m, cx, batch, fa, p);
+    const hipError_t e = plan_adam(m, each ? nullptr : cx, batch, fa, p, each);
     plan = p.plan;
     return e;
 }
@@ -382,10 +427,11 @@ hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int
 // workgroup, a model without BatchNorm); hipErrorNotSupported otherwise -- the caller produces the context first.
 hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch, int max_iter, double *act_best,
                           float *f_best, int *iters, void *ws, hipStream_t stream, const icnn_be_fc_ctx *cx,
-                          const float *obs) {
+                          const float *obs, bool each) {
     AdamArgs a{};
     AdamLaunch p;
-    if (hipError_t e = plan_adam(m, obs ? cx : nullptr, batch, a.fa, p); e != hipSuccess) return e;
+    if (each && obs) return hipErrorInvalidValue;
+    if (hipError_t e = plan_adam(m, obs ? cx : nullptr, batch, a.fa, p, each); e != hipSuccess) return e;
     if (p.plan.kernel == ICNN_BE_ADAM_NONE || (obs && !p.plan.obs_ok)) return hipErrorNotSupported;
     const Workspace w = workspace(batch, m.n);
     unsigned char *base = static_cast<unsigned char *>(ws);
@@ -412,15 +458,17 @@ hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch
             r.cr.n_features = cx->n_features;
             for (int i = 0; i < m.n_layers; ++i) { r.cr.w_stage[i] = cx->w_stage[i]; r.cr.b_stage[i] = cx->b_stage[i]; }
         }
-        if (!p.plan.cooperative) return launch_kernel(adam_rows_kernel, dim3(1), dim3(RTHREADS), p.lds, stream, r);
+        if (each) return launch_kernel(adam_rows_kernel<true>, dim3(a.tiles), dim3(RTHREADS), p.lds, stream, r);
+        if (!p.plan.cooperative) return launch_kernel(adam_rows_kernel<false>, dim3(1), dim3(RTHREADS), p.lds, stream, r);
         void *params[] = {&r};
-        return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_rows_kernel), dim3(a.tiles), dim3(RTHREADS),
+        return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_rows_kernel<false>), dim3(a.tiles), dim3(RTHREADS),
                                           params, (unsigned)p.lds, stream);
     }
     a.red_off = (a.fa.lds_floats + 3) & ~3;
-    if (!p.plan.cooperative) return launch_kernel(adam_fc_kernel, dim3(1), dim3(NTHREADS), p.lds, stream, a);
+    if (each) return launch_kernel(adam_fc_kernel<true>, dim3(a.tiles), dim3(NTHREADS), p.lds, stream, a);
+    if (!p.plan.cooperative) return launch_kernel(adam_fc_kernel<false>, dim3(1), dim3(NTHREADS), p.lds, stream, a);
     void *params[] = {&a};
-    return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_fc_kernel), dim3(a.tiles), dim3(NTHREADS), params,
+    return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(adam_fc_kernel<false>), dim3(a.tiles), dim3(NTHREADS), params,
                                       (unsigned)p.lds, stream);
 }
 

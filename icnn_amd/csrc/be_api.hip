@@ -246,6 +246,17 @@ int check_replay(const icnn_be_replay *m) {
         if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
     return 0;
 }
+
+// the same for the memory of E lockstep environments; idx = c * E + e is an int
+int check_vec_replay(const icnn_be_vec_replay *m) {
+    if (!m || m->steps < 3 || m->n_envs < 1 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
+    if ((long long)m->steps * m->n_envs > 0x7fffffffLL) return ICNN_BE_ELIMIT;
+    if (!m->observations || !m->actions || !m->rewards || !m->terminals || !m->ctrl) return ICNN_BE_EINVAL;
+    const void *a4[] = {m->observations, m->actions, m->rewards, m->ctrl};
+    for (const void *p : a4)
+        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -263,7 +274,7 @@ size_t icnn_be_struct_size(int which) {
          : which == 10 ? sizeof(icnn_be_dataset) : which == 11 ? sizeof(icnn_be_step_log)
          : which == 13 ? sizeof(icnn_be_ddpg_args) : which == 14 ? sizeof(icnn_be_naf_args)
          : which == 16 ? sizeof(icnn_be_ff_args) : which == 18 ? sizeof(icnn_be_fcn_args)
-         : which == 20 ? sizeof(icnn_be_naf_bn_args) : 0;
+         : which == 20 ? sizeof(icnn_be_naf_bn_args) : which == 22 ? sizeof(icnn_be_vec_replay) : 0;
 }
 
 /* diagnostic hooks (include/icnn_be.h): per-phase cycle counters */
@@ -608,6 +619,27 @@ int icnn_be_adam_fc(const icnn_be_fc_model *model, const float *ctx, int batch, 
     hipError_t e = icnn_be::launch_adam_fc(*model, ctx, batch, max_iter, act_best, f_best, iters, workspace, s);
     if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
     return done(e);
+}
+
+int icnn_be_adam_fc_each(const icnn_be_fc_model *model, const float *ctx, int batch, int max_iter, double *act_best,
+                         float *f_best, int *iters, void *workspace, void *stream) {
+    if (!model || !ctx || !act_best || !f_best || !iters || !workspace || !model->wpack) return ICNN_BE_EINVAL;
+    if (batch < 0 || max_iter < 1 || model->action_box) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (batch == 0) return 0;                          /* iters is [0]: nothing to write */
+    hipError_t e = icnn_be::launch_adam_fc(*model, ctx, batch, max_iter, act_best, f_best, iters, workspace,
+                                           static_cast<hipStream_t>(stream), nullptr, nullptr, true);
+    if (e == hipErrorNotSupported) return ICNN_BE_ELIMIT;
+    return done(e);
+}
+
+int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int batch, int out[2]) {
+    if (!model || !out || batch < 1 || model->action_box) return ICNN_BE_EINVAL;
+    if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    icnn_be::AdamPlan p{};
+    if (hipError_t e = icnn_be::adam_fc_plan(*model, nullptr, batch, p, true); e != hipSuccess) return fail(e);
+    out[0] = p.per_wg; out[1] = p.workgroups;
+    return p.kernel;
 }
 
 int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]) {
@@ -1434,6 +1466,42 @@ int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned
     if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
     const icnn_be::ReplaySampleLaunch l{*m, batch, seed, obs, act, rew, ob2, term, idx};
     return done(icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_vec_replay_enqueue(const icnn_be_vec_replay *m, const float *obs, const double *act, const float *rew,
+                               const unsigned char *term, void *stream) {
+    if (int rc = check_vec_replay(m)) return rc;
+    if (!obs || !act || !rew || !term) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(obs) % 4 || reinterpret_cast<uintptr_t>(rew) % 4 || reinterpret_cast<uintptr_t>(act) % 8 ||
+        reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_vec_replay_enqueue(*m, obs, act, rew, term, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_vec_replay_sample(const icnn_be_vec_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
+                              float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
+    if (int rc = check_vec_replay(m)) return rc;
+    if (batch < 1 || fill < 2 || fill > m->steps - 1) return ICNN_BE_EINVAL;
+    if (!obs || !act || !rew || !ob2 || !term || !idx) return ICNN_BE_EINVAL;
+    const void *a4[] = {obs, rew, ob2, idx};
+    for (const void *p : a4)
+        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    const icnn_be::ReplaySampleLaunch l{icnn_be_replay{}, batch, seed, obs, act, rew, ob2, term, idx};
+    return done(icnn_be::launch_vec_replay_sample(*m, l, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_explore(int n_envs, int dimA, const void *raw, int raw_f32, double *noise, int *counter, double theta, double sigma,
+                    unsigned long long seed, int test, double *action, void *stream) {
+    if (n_envs < 1 || dimA < 1 || !raw || !noise || !counter || !action) return ICNN_BE_EINVAL;
+    if ((long long)n_envs * dimA > 0x7fffffffLL) return ICNN_BE_ELIMIT;
+    if (!(theta == theta) || !(sigma == sigma)) return ICNN_BE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(raw) % (raw_f32 ? 4 : 8) || reinterpret_cast<uintptr_t>(noise) % 8 ||
+        reinterpret_cast<uintptr_t>(action) % 8 || reinterpret_cast<uintptr_t>(counter) % 4 ||
+        reinterpret_cast<uintptr_t>(stream) % 8)
+        return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_explore(n_envs, dimA, raw, raw_f32 != 0, noise, counter, theta, sigma, seed, test != 0, action,
+                                        static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_dataset_draw(const icnn_be_dataset *d, int batch, unsigned long long seed, void *const dst[], int *idx,

@@ -235,7 +235,7 @@ long long *fc_profile_buffer();
 size_t adam_workspace_bytes(int batch, int n);
 hipError_t launch_adam_fc(const icnn_be_fc_model &m, const float *ctx, int batch, int max_iter, double *act_best,
                           float *f_best, int *iters, void *workspace, hipStream_t stream,
-                          const icnn_be_fc_ctx *cx = nullptr, const float *obs = nullptr);
+                          const icnn_be_fc_ctx *cx = nullptr, const float *obs = nullptr, bool each = false);
 // The launch of launch_adam_fc for a model and a batch (icnn_be_debug_adam_plan); launch_adam_fc launches from exactly this.
 // With `cx`, obs_ok: the observation form is accepted (else hipErrorNotSupported).  Enqueues nothing.
 struct AdamPlan {
@@ -245,7 +245,8 @@ struct AdamPlan {
     int cooperative;   // several workgroups: all resident, the stopping rule's sum goes through a grid exchange
     int obs_ok;
 };
-hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan);
+// `each`: the stopping rule per state (icnn_be_adam_fc_each): iters is [batch], no workgroup waits for another, never cooperative.
+hipError_t adam_fc_plan(const icnn_be_fc_model &m, const icnn_be_fc_ctx *cx, int batch, AdamPlan &plan, bool each = false);
 
 // Unrolled momentum gradient descent on y (be_gd.hip): the FC form is one launch (persistent tiles or the per-sample rows
 // path), the conv form 1 + K (+1) rounds of launches.  hipErrorNotSupported: the model's tile does not fit the LDS.
@@ -410,6 +411,12 @@ struct ReplaySampleLaunch {
 long long replay_sample_blocks(int batch);
 hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream);
 hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream);
+// E lockstep environments (icnn_be_vec_replay; l.m is not read) and the exploration noise (icnn_be_explore)
+hipError_t launch_vec_replay_enqueue(const icnn_be_vec_replay &m, const float *obs, const double *act, const float *rew,
+                                     const unsigned char *term, hipStream_t stream);
+hipError_t launch_vec_replay_sample(const icnn_be_vec_replay &m, const ReplaySampleLaunch &l, hipStream_t stream);
+hipError_t launch_explore(int n_envs, int dimA, const void *raw, bool raw_f32, double *noise, int *counter, double theta,
+                          double sigma, unsigned long long seed, bool test, double *action, hipStream_t stream);
 
 // ---- the training set on the device and the step log (be_train_data.hip) ----------------------
 struct DatasetDrawLaunch {

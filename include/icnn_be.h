@@ -231,7 +231,7 @@ ICNN_BE_API const char *icnn_be_last_hip_error(void);
  * sizeof(icnn_be_param_update_args) for 6, sizeof(icnn_be_rl_update_args) for 7, sizeof(icnn_be_ficnn_model) for 8, sizeof(icnn_be_replay) for 9,
  * sizeof(icnn_be_dataset) for 10, sizeof(icnn_be_step_log) for 11, 0 for 12, sizeof(icnn_be_ddpg_args) for 13,
  * sizeof(icnn_be_naf_args) for 14, 0 for 15, sizeof(icnn_be_ff_args) for 16, 0 for 17,
- * sizeof(icnn_be_fcn_args) for 18: lets a foreign-language binding verify its struct layout at load time. */
+ * sizeof(icnn_be_fcn_args) for 18, 0 for 19, sizeof(icnn_be_naf_bn_args) for 20, 0 for 21, sizeof(icnn_be_vec_replay) for 22: lets a foreign-language binding verify its struct layout at load time. */
 ICNN_BE_API size_t icnn_be_struct_size(int which);
 
 /* bytes of dynamic LDS one workgroup of the dual-step kernel needs (diagnostic) */
@@ -925,6 +925,58 @@ ICNN_BE_API int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stag
 ICNN_BE_API int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs,
                                       double *act, float *rew, float *ob2, unsigned char *term, int *idx, void *stream);
 
+/* ---- E environments a step: the vector replay memory and the exploration noise (be_rl_replay.hip, additive to ABI 12) ---- */
+
+/*
+ * The replay memory of n_envs environments that step in lockstep: `steps` time rows of n_envs transitions each, so every one
+ * of the n_envs columns is the memory of RL/src/replay_memory.py.  ctrl as in icnn_be_replay; the cursor and the fill count
+ * time rows.  steps * n_envs must fit an int (ICNN_BE_ELIMIT).
+ */
+typedef struct icnn_be_vec_replay {
+    int steps, n_envs, dimO, dimA;
+    float *observations;              /* [steps][n_envs][dimO] */
+    float *actions;                   /* [steps][n_envs][dimA]: float32 */
+    float *rewards;                   /* [steps][n_envs] */
+    unsigned char *terminals;         /* [steps][n_envs] */
+    int *ctrl;                        /* [ICNN_BE_REPLAY_CTRL_INTS] */
+} icnn_be_vec_replay;
+
+/*
+ * One launch writes time row i for every environment from DEVICE buffers -- obs float32 [n_envs][dimO], act float64
+ * [n_envs][dimA] (rounded to float32), rew float32 [n_envs], term uint8 [n_envs] (nonzero: set) -- then i <- (i + 1) % steps and
+ * n <- min(steps - 1, n + 1), as replay_memory.py:33-34.  EINVAL for a NULL m, steps < 3, n_envs, dimO or dimA < 1, a NULL or
+ * misaligned pointer (act 8 bytes, obs and rew 4), a misaligned stream.  No host data, no synchronisation: capturable.
+ */
+ICNN_BE_API int icnn_be_vec_replay_enqueue(const icnn_be_vec_replay *m, const float *obs, const double *act, const float *rew,
+                                           const unsigned char *term, void *stream);
+
+/*
+ * icnn_be_replay_sample's rule per column.  For sample k, attempt a, draw d: the time index c = hi32(w0 * (n - 1)), w0 = word
+ * 0 of Philox4x32-10 at counter (d, k, a, 0), and the environment e = hi32(w2 * n_envs), w2 = word 0 at counter (d, k, a, 2),
+ * key (seed low, seed high).  The draw is valid when c is not the cursor and terminals[c][e] == 0.  Outputs from (c, e) and its
+ * successor (c + 1, e) -- two rows n_envs * dimO floats apart; idx[k] = c * n_envs + e.  Attempt bound, status words, ticket
+ * and draw counter as icnn_be_replay_sample; with n_envs = 1 every output and the control block equal that entry's on the same
+ * transitions.  Refusals as there (fill: the host's mirror of n, 2 <= fill <= steps - 1).  Capturable.
+ */
+ICNN_BE_API int icnn_be_vec_replay_sample(const icnn_be_vec_replay *m, int fill, int batch, unsigned long long seed, float *obs,
+                                          double *act, float *rew, float *ob2, unsigned char *term, int *idx, void *stream);
+
+/*
+ * The Ornstein-Uhlenbeck exploration of n_envs actions in one launch (RL/src/icnn.py:276-283 per environment).  raw: the
+ * optimiser's or the policy's output [n_envs][dimA], float64, or float32 with raw_f32 != 0.  test == 0:
+ *     noise <- noise - (theta * noise - sigma * z)     float64, no contraction
+ *     action = min(max(raw + noise, -1), 1)
+ * and the step counter *counter (device int32) advances by one, so a captured launch draws fresh numbers on every replay.
+ * test != 0: action = min(max(raw, -1), 1); noise and counter are left alone.  z is the project's own stream (not
+ * np.random.randn's): with (w0, w1, w2, w3) = Philox4x32-10 at counter (step, e, j, 3) and key (seed low, seed high),
+ *     u1 = (((w1 << 32 | w0) >> 11) + 1) * 2^-53  in (0, 1],   u2 = ((w3 << 32 | w2) >> 11) * 2^-53  in [0, 1),
+ *     z  = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2)      all float64.
+ * noise float64 [n_envs][dimA], action float64 [n_envs][dimA] (may be raw).  EINVAL for n_envs or dimA < 1, a NULL or
+ * misaligned pointer, a NaN theta or sigma; ICNN_BE_ELIMIT where n_envs * dimA does not fit an int.  No host synchronisation.
+ */
+ICNN_BE_API int icnn_be_explore(int n_envs, int dimA, const void *raw, int raw_f32, double *noise, int *counter, double theta,
+                                double sigma, unsigned long long seed, int test, double *action, void *stream);
+
 /* ---- the training set on the device: minibatch draw and step log (be_train_data.hip, additive to ABI 12) ---- */
 
 /*
@@ -1023,6 +1075,19 @@ ICNN_BE_API size_t icnn_be_adam_workspace_bytes(int batch, int n);
  */
 ICNN_BE_API int icnn_be_adam_fc(const icnn_be_fc_model *model, const float *ctx, int batch, int max_iter,
                                 double *act_best, float *f_best, int *iters, void *workspace, void *stream);
+
+/*
+ * icnn_be_adam_fc with the stopping rule applied to every state on its own (additive to ABI 12): row u of act_best, f_best and
+ * iters[B] is, bit for bit, what icnn_be_adam_fc returns for the batch that consists of row u alone -- the smoothed
+ * displacement is the state's own, a state whose rule has fired keeps its best iterate and takes no further step, and
+ * iters[u] is the iteration at which its rule fired (max_iter if it never did).  What a vector of environments needs: an
+ * action that does not depend on the other environments' observations.  Same arguments and the same refusals otherwise;
+ * `workspace` as icnn_be_adam_workspace_bytes says.  One ordinary launch: no workgroup waits for another, so any batch runs
+ * and there is no residency limit (ICNN_BE_ELIMIT only where no layout fits the LDS).  dim(action) <= 64 and at most four
+ * states per resident workgroup: the latency path; 16-state MFMA tiles otherwise (icnn_be_debug_adam_each_plan).
+ */
+ICNN_BE_API int icnn_be_adam_fc_each(const icnn_be_fc_model *model, const float *ctx, int batch, int max_iter,
+                                     double *act_best, float *f_best, int *iters, void *workspace, void *stream);
 
 /*
  * The same from the observations themselves: obs[B][n_features] -> the x-only context rows (cx: the stage weights of
@@ -1302,6 +1367,12 @@ ICNN_BE_API int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const ic
  * a device.
  */
 ICNN_BE_API int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]);
+/*
+ * The launch icnn_be_adam_fc_each makes (additive to ABI 12): returns ICNN_BE_ADAM_ROWS or ICNN_BE_ADAM_TILE and fills
+ * out = { states per workgroup, workgroups }; ICNN_BE_ADAM_NONE (out all zero) where no layout fits the LDS.  Never cooperative.
+ * Errors and device use as icnn_be_debug_adam_plan.
+ */
+ICNN_BE_API int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int batch, int out[2]);
 /*
  * The kernel instance icnn_be_dual_step(st, t, ...) launches (additive to ABI 12): returns 0 and fills out = { cut type of the
  * instance (ICNN_BE_CUT_*), its bundle tile KT (16 or 32; small kernel: its KS, 5, 8 or 16), waves per workgroup, its variant
