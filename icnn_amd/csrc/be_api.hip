@@ -1,8 +1,10 @@
-// C ABI of libicnn_be.so (see include/icnn_be.h for the contract and the reference lines
-// each entry point replaces).  Everything here only validates arguments and enqueues work.
+// C ABI of libicnn_be.so (see include/icnn_be.h for the contract and the reference lines each entry point replaces): the
+// error state, the per-device launch configuration, the solve plan, and every entry that takes an icnn_be_state, a model
+// (icnn_be_fc_model, icnn_be_conv_model, icnn_be_ficnn_model) or a context descriptor (icnn_be_fc_ctx, icnn_be_conv_ctx).
+// Those entries share checks across units and own the dispatch.  An entry that takes none of them concerns one unit only
+// and is defined in that unit, behind its kernels (be_api_check.h has what such entries share).  Everything here only
+// validates arguments and enqueues work.
 #include <hip/hip_runtime.h>
-#include <climits>
-#include <cstdint>
 #include <cmath>
 #include <cstdlib>
 
@@ -10,6 +12,7 @@
 #include <mutex>
 #include <utility>
 
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "icnn_be.h"
 
@@ -24,7 +27,7 @@ int fail(hipError_t e) {
 int done(hipError_t e) { return e == hipSuccess ? 0 : fail(e); }
 }  // namespace
 
-// for the entries defined beside their kernels (be_fcn.hip)
+// for the entries defined beside their kernels
 int icnn_be::api_done(hipError_t e) { return done(e); }
 
 namespace {
@@ -216,46 +219,6 @@ SolvePlan plan_fc_solve(const icnn_be_fc_model &m, const icnn_be_state &st, int 
     if (!two && icnn_be::fused_rows_layout(m, st, 1, true, rows))
         return {ICNN_BE_PATH_ROUNDS_SLICED_THEN_ROWS, 0, SLICE_BUDGET, T + 1};
     return {ICNN_BE_PATH_ROUNDS_SLICED_EXTRA, 0, SLICE_BUDGET, sliced_extra_rounds(T)};
-}
-}  // namespace
-
-namespace {
-// what icnn_be_param_update and icnn_be_rl_critic_update refuse before any launch
-int check_param_update(const icnn_be_param_update_args *a) {
-    if (!a || a->n < 1 || !a->theta || !a->m || !a->v || !a->grad || !a->dest_off || !a->dest || !a->arena || !a->step)
-        return ICNN_BE_EINVAL;
-    if (a->arena_floats < 0 || a->arena_floats > 0x7fffffffLL || icnn_be::param_update_blocks(a->n) > 0x7fffffffLL)
-        return ICNN_BE_EINVAL;
-    const void *aligned[] = {a->theta, a->m, a->v, a->grad, a->dest_off};
-    for (const void *p : aligned)
-        if (reinterpret_cast<uintptr_t>(p) % 16) return ICNN_BE_EINVAL;
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f && a->lr == a->lr))
-        return ICNN_BE_EINVAL;
-    if (a->n_proj < 0 || a->n_proj > ICNN_BE_MAX_PROJ_RANGES) return ICNN_BE_EINVAL;
-    for (int r = 0; r < a->n_proj; ++r)
-        if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
-    return 0;
-}
-
-// what icnn_be_replay_enqueue and icnn_be_replay_sample refuse in the memory's descriptor
-int check_replay(const icnn_be_replay *m) {
-    if (!m || m->size < 3 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
-    if (!m->observations || !m->actions || !m->rewards || !m->terminals || !m->ctrl) return ICNN_BE_EINVAL;
-    const void *a4[] = {m->observations, m->actions, m->rewards, m->ctrl};
-    for (const void *p : a4)
-        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
-    return 0;
-}
-
-// the same for the memory of E lockstep environments; idx = c * E + e is an int
-int check_vec_replay(const icnn_be_vec_replay *m) {
-    if (!m || m->steps < 3 || m->n_envs < 1 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
-    if ((long long)m->steps * m->n_envs > 0x7fffffffLL) return ICNN_BE_ELIMIT;
-    if (!m->observations || !m->actions || !m->rewards || !m->terminals || !m->ctrl) return ICNN_BE_EINVAL;
-    const void *a4[] = {m->observations, m->actions, m->rewards, m->ctrl};
-    for (const void *p : a4)
-        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
-    return 0;
 }
 }  // namespace
 
@@ -688,8 +651,6 @@ int icnn_be_implicit_feed(const icnn_be_state *st, const double *y_true, int los
                                               static_cast<hipStream_t>(stream)));
 }
 
-size_t icnn_be_feed_plan_work_bytes(int batch) { return batch < 0 ? 0 : icnn_be::feed_plan_work_bytes(batch); }
-
 int icnn_be_feed_plan(const icnn_be_state *st, const double *y_true, int loss, int *row_offset, int *counts,
                       double *loss_out, int *tallies, void *work, void *stream) {
     if (int rc = check_state(st)) return rc;
@@ -698,66 +659,6 @@ int icnn_be_feed_plan(const icnn_be_state *st, const double *y_true, int loss, i
     if (st->batch == 0) return 0;
     icnn_be::FeedPlanLaunch l{*st, y_true, loss, row_offset, counts, loss_out, tallies, work};
     return done(icnn_be::launch_feed_plan(l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c, int *fd_sample,
-                     void *stream) {
-    if (!rows || !fd_y || !fd_v || !fd_c || !fd_sample || batch < 1 || n < 1 || row_cap < 0) return ICNN_BE_EINVAL;
-    if (row_cap == 0) return 0;
-    return done(icnn_be::launch_feed_pad(rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_step_gate(const int *counts, int mask, int *gate, void *stream) {
-    if (!counts || !gate) return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_step_gate(counts, mask, gate, static_cast<hipStream_t>(stream)));
-}
-
-size_t icnn_be_gd_feed_work_bytes(int B) { return B < 0 ? 0 : icnn_be::gd_feed_work_bytes(B); }
-
-int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, double *v_rows,
-                    double *c_rows, int *row_offset, float *loss, int *f1_tallies, void *work, void *stream) {
-    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
-    if (!yK || !t || !coef || !v_rows || !c_rows || !row_offset || !loss || !work) return ICNN_BE_EINVAL;
-    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
-    icnn_be::GdFeedLaunch l{yK, t, coef, B, n, K, scale, v_rows, c_rows, row_offset, loss, f1_tallies, work};
-    return done(icnn_be::launch_gd_feed(l, static_cast<hipStream_t>(stream)));
-}
-
-size_t icnn_be_gd_feed_px_work_bytes(int B, int n, int K) {
-    return (B < 1 || n < 1 || K < 1) ? 0 : icnn_be::gd_feed_work_bytes(B);
-}
-
-int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, float px,
-                       double *v_rows, double *c_rows, int *row_offset, float *loss, void *work, void *stream) {
-    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
-    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
-    const int rows = (v_rows != nullptr) + (c_rows != nullptr) + (row_offset != nullptr);
-    if (rows != 0 && rows != 3) return ICNN_BE_EINVAL;
-    if (rows == 3 && !coef) return ICNN_BE_EINVAL;
-    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
-    if (rows == 3 && icnn_be::gd_feed_px_chunks(n, K) > icnn_be::GD_FEED_PX_MAX_CHUNKS) return ICNN_BE_ELIMIT;
-    icnn_be::GdFeedPxLaunch l{yK, t, coef, B, n, K, scale, px, v_rows, c_rows, row_offset, loss, work};
-    return done(icnn_be::launch_gd_feed_px(l, static_cast<hipStream_t>(stream)));
-}
-
-size_t icnn_be_gd_eval_work_bytes(int B) { return B < 1 ? 0 : icnn_be::gd_feed_work_bytes(B); }
-
-int icnn_be_gd_eval(const double *yK, const float *t, int B, int n, float *loss, int *f1_tallies, void *work, void *stream) {
-    if (B < 1 || n < 1) return ICNN_BE_EINVAL;
-    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
-    icnn_be::GdEvalLaunch l{yK, t, B, n, loss, f1_tallies, work};
-    return done(icnn_be::launch_gd_eval(l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_macro_f1(const int *tallies, int B, double *f1, void *stream) {
-    if (B < 1 || !tallies || !f1) return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_macro_f1(tallies, B, f1, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, void *stream) {
-    if (!score || !best || !gate) return ICNN_BE_EINVAL;
-    if (mode != ICNN_BE_KEEP_MIN && mode != ICNN_BE_KEEP_MAX) return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_keep_best(score, score_is_f64 != 0, mode, best, gate, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_export_active(const icnn_be_state *st, const int *row_offset, void *G_rows, double *ys_rows, double *h_rows,
@@ -843,12 +744,6 @@ int icnn_be_conv_pgd(const icnn_be_conv_model *model, const float *ctx, const do
     if (!model->work || model->work_batch < batch) return ICNN_BE_EINVAL;
     return done(icnn_be::launch_conv_pgd(*model, ctx, y0, batch, n_iter, lr, lo, hi, y_out, obj, obj_final, workspace,
                                          static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_entropy_objective(const float *E, const double *y, int batch, int n, double *out, void *stream) {
-    if (!E || !y || !out || batch < 0 || n < 1) return ICNN_BE_EINVAL;
-    if (batch == 0) return 0;
-    return done(icnn_be::launch_entropy_objective(E, y, batch, n, out, static_cast<hipStream_t>(stream)));
 }
 
 int icnn_be_bundle_trace(const icnn_be_state *st, double *obj, int *calls, void *stream) {
@@ -1020,516 +915,4 @@ int icnn_be_ficnn_surrogate_grad(const icnn_be_ficnn_model *model, const float *
                                                      static_cast<hipStream_t>(stream)));
 }
 
-int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) {
-    if (int rc = check_param_update(a)) return rc;
-    return done(icnn_be::launch_param_update(*a, nullptr, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_param_update_gated(const icnn_be_param_update_args *a, const int *go, void *stream) {
-    if (!go) return ICNN_BE_EINVAL;
-    if (int rc = check_param_update(a)) return rc;
-    return done(icnn_be::launch_param_update(*a, go, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_gated_copy(float *dst, const float *src, long long n, const int *go, int want, void *stream) {
-    if (!dst || !src || !go || n < 0) return ICNN_BE_EINVAL;
-    if (n == 0) return 0;
-    return done(icnn_be::launch_gated_copy(dst, src, n, go, want, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, const float *rew, const unsigned char *term,
-                  const float *q2_src, const double *act2, float discount, const float *theta, long long n_theta,
-                  const unsigned char *decay, float l2norm, float wd, float *td, double *c, float *loss, void *work,
-                  void *stream) {
-    if (batch < 1 || n < 1 || n_theta < 1 || n_theta > 0x7fffffffLL) return ICNN_BE_EINVAL;
-    if (!e_critic || !act || !rew || !term || !q2_src || !theta || !decay || !td || !c || !loss || !work)
-        return ICNN_BE_EINVAL;
-    const uintptr_t a8[] = {reinterpret_cast<uintptr_t>(act), reinterpret_cast<uintptr_t>(act2),
-                            reinterpret_cast<uintptr_t>(c)};
-    for (uintptr_t p : a8)
-        if (p % 8) return ICNN_BE_EINVAL;
-    const uintptr_t a4[] = {reinterpret_cast<uintptr_t>(e_critic), reinterpret_cast<uintptr_t>(rew),
-                            reinterpret_cast<uintptr_t>(q2_src), reinterpret_cast<uintptr_t>(theta),
-                            reinterpret_cast<uintptr_t>(td), reinterpret_cast<uintptr_t>(loss)};
-    for (uintptr_t p : a4)
-        if (p % 4) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(work) % 16 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    if (!std::isfinite(discount) || !(l2norm >= 0.f) || !(wd >= 0.f) || !std::isfinite(l2norm) || !std::isfinite(wd))
-        return ICNN_BE_EINVAL;
-    const icnn_be::RlTdLaunch l{batch, n, e_critic, act, rew, term, q2_src, act2, discount, theta, n_theta, decay,
-                                l2norm, wd, td, c, loss, work};
-    return done(icnn_be::launch_rl_td(l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
-    if (!a) return ICNN_BE_EINVAL;
-    if (int rc = check_param_update(&a->adam)) return rc;
-    if (!a->target_theta || !a->target_arena || !a->decay) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->target_theta) % 16 || reinterpret_cast<uintptr_t>(a->decay) % 4 ||
-        reinterpret_cast<uintptr_t>(a->target_arena) % 4 || reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    if (!(a->tau >= 0.f && a->tau <= 1.f) || !(a->l2norm >= 0.f) || !(a->wd >= 0.f) || !std::isfinite(a->l2norm) ||
-        !std::isfinite(a->wd))
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_rl_critic_update(*a, static_cast<hipStream_t>(stream)));
-}
-
-namespace {
-bool ddpg_sizes_ok(int dimO, int dimA, int l1, int l2) {
-    return dimO >= 1 && dimO <= ICNN_BE_DDPG_MAX_OBS && dimA >= 1 && dimA <= ICNN_BE_DDPG_MAX_ACT && l1 >= 1 &&
-           l1 <= ICNN_BE_DDPG_MAX_HIDDEN && l2 >= 1 && l2 <= ICNN_BE_DDPG_MAX_HIDDEN && icnn_be::ddpg_fits(dimO, dimA, l1, l2);
-}
-bool misaligned(const void *p, uintptr_t to) { return !p || reinterpret_cast<uintptr_t>(p) % to; }
-
-// what every icnn_be_ddpg_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
-int check_ddpg(const icnn_be_ddpg_args *a, void *stream, bool need_loss) {
-    if (!a || a->batch < 1 || !ddpg_sizes_ok(a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
-    const void *a16[] = {a->theta_q, a->theta_p, a->target_q, a->target_p, a->m_q, a->v_q, a->m_p, a->v_p, a->grad_q, a->grad_p,
-                         a->work};
-    for (const void *p : a16)
-        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
-    const void *a4[] = {a->obs, a->rew, a->ob2, a->step};
-    for (const void *p : a4)
-        if (misaligned(p, 4)) return ICNN_BE_EINVAL;
-    if (misaligned(a->act, 8) || !a->term || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    if (need_loss ? misaligned(a->loss, 4) : reinterpret_cast<uintptr_t>(a->loss) % 4 != 0) return ICNN_BE_EINVAL;
-    if (!(a->tau >= 0.f && a->tau <= 1.f) || !std::isfinite(a->discount)) return ICNN_BE_EINVAL;
-    if (!(a->l2norm >= 0.f) || !(a->pl2norm >= 0.f) || !std::isfinite(a->l2norm) || !std::isfinite(a->pl2norm)) return ICNN_BE_EINVAL;
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f)) return ICNN_BE_EINVAL;
-    if (!std::isfinite(a->rate) || !std::isfinite(a->prate)) return ICNN_BE_EINVAL;
-    return 0;
-}
-}  // namespace
-
-int icnn_be_ddpg_param_floats(int dimO, int dimA, int l1, int l2, long long *np, long long *nq) {
-    if (!ddpg_sizes_ok(dimO, dimA, l1, l2) || !np || !nq) return ICNN_BE_EINVAL;
-    *np = icnn_be::ddpg_policy_floats(dimO, dimA, l1, l2);
-    *nq = icnn_be::ddpg_critic_floats(dimO, dimA, l1, l2);
-    return 0;
-}
-
-size_t icnn_be_ddpg_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
-    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return 0;
-    return icnn_be::ddpg_work_floats(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
-}
-
-int icnn_be_ddpg_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_DDPG_WORK_PIECES]) {
-    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
-    icnn_be::ddpg_work_floats(batch, dimO, dimA, l1, l2, off);
-    return 0;
-}
-
-int icnn_be_ddpg_chain(const icnn_be_ddpg_args *a, void *stream) {
-    if (int rc = check_ddpg(a, stream, false)) return rc;
-    return done(icnn_be::launch_ddpg_chain(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ddpg_grads(const icnn_be_ddpg_args *a, void *stream) {
-    if (int rc = check_ddpg(a, stream, false)) return rc;
-    return done(icnn_be::launch_ddpg_grads(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ddpg_update(const icnn_be_ddpg_args *a, void *stream) {
-    if (int rc = check_ddpg(a, stream, false)) return rc;
-    return done(icnn_be::launch_ddpg_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ddpg_step(const icnn_be_ddpg_args *a, void *stream) {
-    if (int rc = check_ddpg(a, stream, true)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = icnn_be::launch_ddpg_chain(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_ddpg_grads(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_ddpg_update(*a, true, s);
-    return done(e);
-}
-
-int icnn_be_ddpg_act(int dimO, int dimA, int l1, int l2, const float *theta_p, const float *obs, int batch, float *out,
-                     void *stream) {
-    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_p, 16) || misaligned(obs, 4) || misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_ddpg_forward(false, dimO, dimA, l1, l2, theta_p, obs, nullptr, batch, out,
-                                             static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ddpg_q(int dimO, int dimA, int l1, int l2, const float *theta_q, const float *obs, const double *act, int batch,
-                   float *out, void *stream) {
-    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_q, 16) || misaligned(obs, 4) || misaligned(act, 8) || misaligned(out, 4) ||
-        reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_ddpg_forward(true, dimO, dimA, l1, l2, theta_q, obs, act, batch, out,
-                                             static_cast<hipStream_t>(stream)));
-}
-
-namespace {
-bool naf_sizes_ok(int dimO, int dimA, int l1, int l2) {
-    return dimO >= 1 && dimO <= ICNN_BE_NAF_MAX_OBS && dimA >= 1 && dimA <= ICNN_BE_NAF_MAX_ACT && l1 >= 1 &&
-           l1 <= ICNN_BE_NAF_MAX_HIDDEN && l2 >= 1 && l2 <= ICNN_BE_NAF_MAX_HIDDEN && icnn_be::naf_fits(dimO, dimA, l1, l2);
-}
-
-// what every icnn_be_naf_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
-int check_naf(const icnn_be_naf_args *a, void *stream, bool need_loss) {
-    if (!a || a->batch < 1 || !naf_sizes_ok(a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
-    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
-                         a->grad_l, a->grad_u, a->grad_v, a->work};
-    for (const void *p : a16)
-        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
-    const void *a4[] = {a->obs, a->rew, a->ob2, a->step};
-    for (const void *p : a4)
-        if (misaligned(p, 4)) return ICNN_BE_EINVAL;
-    if (misaligned(a->act, 8) || !a->term || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    if (need_loss ? misaligned(a->loss, 4) : reinterpret_cast<uintptr_t>(a->loss) % 4 != 0) return ICNN_BE_EINVAL;
-    if (!(a->tau >= 0.f && a->tau <= 1.f) || !std::isfinite(a->discount)) return ICNN_BE_EINVAL;
-    if (!(a->l2norm >= 0.f) || !std::isfinite(a->l2norm)) return ICNN_BE_EINVAL;
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f)) return ICNN_BE_EINVAL;
-    if (!std::isfinite(a->rate)) return ICNN_BE_EINVAL;
-    return 0;
-}
-}  // namespace
-
-int icnn_be_naf_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv) {
-    if (!naf_sizes_ok(dimO, dimA, l1, l2) || !nl || !nu || !nv) return ICNN_BE_EINVAL;
-    *nl = icnn_be::naf_net_floats(dimO, l1, l2, dimA * dimA);
-    *nu = icnn_be::naf_net_floats(dimO, l1, l2, dimA);
-    *nv = icnn_be::naf_net_floats(dimO, l1, l2, 1);
-    return 0;
-}
-
-size_t icnn_be_naf_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
-    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return 0;
-    return icnn_be::naf_work_floats(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
-}
-
-int icnn_be_naf_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_WORK_PIECES]) {
-    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
-    icnn_be::naf_work_floats(batch, dimO, dimA, l1, l2, off);
-    return 0;
-}
-
-int icnn_be_naf_chain(const icnn_be_naf_args *a, void *stream) {
-    if (int rc = check_naf(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_chain(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_grads(const icnn_be_naf_args *a, void *stream) {
-    if (int rc = check_naf(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_grads(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_update(const icnn_be_naf_args *a, void *stream) {
-    if (int rc = check_naf(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_step(const icnn_be_naf_args *a, void *stream) {
-    if (int rc = check_naf(a, stream, true)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = icnn_be::launch_naf_chain(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_naf_grads(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_naf_update(*a, true, s);
-    return done(e);
-}
-
-int icnn_be_naf_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *obs, int batch, float *out,
-                    void *stream) {
-    // the U net is DDPG's policy; its launch needs DDPG's LDS plan, which holds wherever NAF's does
-    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_u, 16) || misaligned(obs, 4) || misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_ddpg_forward(false, dimO, dimA, l1, l2, theta_u, obs, nullptr, batch, out,
-                                             static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
-                  const float *obs, const double *act, int batch, float *out, void *stream) {
-    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(obs, 4) || misaligned(act, 8) ||
-        misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_naf_q(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, obs, act, batch, out,
-                                      static_cast<hipStream_t>(stream)));
-}
-
-namespace {
-bool naf_bn_sizes_ok(int batch, int dimO, int dimA, int l1, int l2) {
-    return batch >= 1 && batch <= ICNN_BE_NAF_BN_MAX_BATCH && naf_sizes_ok(dimO, dimA, l1, l2) && icnn_be::naf_bn_fits(dimA, l2);
-}
-
-// what every icnn_be_naf_bn_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
-int check_naf_bn(const icnn_be_naf_bn_args *a, void *stream, bool need_loss) {
-    if (!a || !naf_bn_sizes_ok(a->batch, a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
-    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
-                         a->grad_l, a->grad_u, a->grad_v, a->work};
-    for (const void *p : a16)
-        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
-    const void *a4[] = {a->obs, a->rew, a->ob2, a->step, a->mv_l, a->mv_u, a->mv_v};
-    for (const void *p : a4)
-        if (misaligned(p, 4)) return ICNN_BE_EINVAL;
-    if (misaligned(a->act, 8) || !a->term || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    if (need_loss ? misaligned(a->loss, 4) : reinterpret_cast<uintptr_t>(a->loss) % 4 != 0) return ICNN_BE_EINVAL;
-    if (!(a->tau >= 0.f && a->tau <= 1.f) || !std::isfinite(a->discount)) return ICNN_BE_EINVAL;
-    if (!(a->l2norm >= 0.f) || !std::isfinite(a->l2norm)) return ICNN_BE_EINVAL;
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f)) return ICNN_BE_EINVAL;
-    if (!std::isfinite(a->rate) || !(a->bn_eps > 0.f) || !(a->bn_decay >= 0.0 && a->bn_decay <= 1.0)) return ICNN_BE_EINVAL;
-    return 0;
-}
-}  // namespace
-
-int icnn_be_naf_bn_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv, long long *nt,
-                                long long *ns) {
-    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || !nl || !nu || !nv || !nt || !ns) return ICNN_BE_EINVAL;
-    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 0, nullptr, nl, nullptr);
-    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 1, nullptr, nu, nullptr);
-    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, 2, nullptr, nv, nt);
-    *ns = 2LL * (dimO + l1 + l2);
-    return 0;
-}
-
-int icnn_be_naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long off[ICNN_BE_NAF_BN_VARS]) {
-    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || which < 0 || which > 2 || !off) return ICNN_BE_EINVAL;
-    icnn_be::naf_bn_layout(dimO, dimA, l1, l2, which, off, nullptr, nullptr);
-    return 0;
-}
-
-size_t icnn_be_naf_bn_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
-    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2)) return 0;
-    return icnn_be::naf_bn_work_floats(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
-}
-
-int icnn_be_naf_bn_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_BN_WORK_PIECES]) {
-    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
-    icnn_be::naf_bn_work_floats(batch, dimO, dimA, l1, l2, off);
-    return 0;
-}
-
-int icnn_be_naf_bn_chain(const icnn_be_naf_bn_args *a, void *stream) {
-    if (int rc = check_naf_bn(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_bn_chain(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_bn_grads(const icnn_be_naf_bn_args *a, void *stream) {
-    if (int rc = check_naf_bn(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_bn_grads(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_bn_update(const icnn_be_naf_bn_args *a, void *stream) {
-    if (int rc = check_naf_bn(a, stream, false)) return rc;
-    return done(icnn_be::launch_naf_bn_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_bn_step(const icnn_be_naf_bn_args *a, void *stream) {
-    if (int rc = check_naf_bn(a, stream, true)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = icnn_be::launch_naf_bn_chain(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_naf_bn_grads(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_naf_bn_update(*a, true, s);
-    if (e == hipSuccess) e = icnn_be::launch_naf_bn_fold(*a, s);
-    return done(e);
-}
-
-int icnn_be_naf_bn_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *mv_u, float bn_eps, int mode,
-                       const float *obs, int batch, float *out, void *work, void *stream) {
-    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_u, 16) || misaligned(work, 16) || misaligned(mv_u, 4) || misaligned(obs, 4) || misaligned(out, 4) ||
-        reinterpret_cast<uintptr_t>(stream) % 8 || !(bn_eps > 0.f))
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_naf_bn_forward(dimO, dimA, l1, l2, nullptr, theta_u, nullptr, nullptr, mv_u, nullptr, bn_eps,
-                                               mode == ICNN_BE_BN_MOVING, obs, nullptr, batch, out, work,
-                                               static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_naf_bn_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
-                     const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps, int mode, const float *obs,
-                     const double *act, int batch, float *out, void *work, void *stream) {
-    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING)) return ICNN_BE_EINVAL;
-    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(work, 16) ||
-        misaligned(mv_l, 4) || misaligned(mv_u, 4) || misaligned(mv_v, 4) || misaligned(obs, 4) || misaligned(act, 8) ||
-        misaligned(out, 4) || reinterpret_cast<uintptr_t>(stream) % 8 || !(bn_eps > 0.f))
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_naf_bn_forward(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, mv_l, mv_u, mv_v, bn_eps,
-                                               mode == ICNN_BE_BN_MOVING, obs, act, batch, out, work,
-                                               static_cast<hipStream_t>(stream)));
-}
-
-namespace {
-bool ff_sizes_ok(int n_features, int n_labels, int n_layers, const int *width) {
-    if (n_features < 1 || n_features > ICNN_BE_FF_MAX_FEATURES || n_labels < 1 || n_labels > ICNN_BE_FF_MAX_WIDTH) return false;
-    if (n_layers < 1 || n_layers > ICNN_BE_FF_MAX_LAYERS || !width) return false;
-    for (int i = 0; i < n_layers; ++i)
-        if (width[i] < 1 || width[i] > ICNN_BE_FF_MAX_WIDTH) return false;
-    return true;
-}
-
-// what an icnn_be_ff_* entry needs beyond the sizes
-enum : unsigned {
-    FF_TRAIN_BATCH = 1, FF_X = 2, FF_Y = 4, FF_OUT = 8, FF_MOVING = 16, FF_GRAD = 32, FF_ADAM = 64, FF_WORK = 128, FF_LOSS = 256
-};
-int check_ff(const icnn_be_ff_args *a, void *stream, unsigned need) {
-    if (!a || !ff_sizes_ok(a->n_features, a->n_labels, a->n_layers, a->width)) return ICNN_BE_EINVAL;
-    if (a->batch < 1 || ((need & FF_TRAIN_BATCH) && (a->batch < 2 || a->batch > ICNN_BE_FF_MAX_BATCH))) return ICNN_BE_EINVAL;
-    if (misaligned(a->theta, 16) || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    if ((need & FF_WORK) && misaligned(a->work, 16)) return ICNN_BE_EINVAL;
-    if ((need & FF_X) && misaligned(a->x, 4)) return ICNN_BE_EINVAL;
-    if ((need & FF_Y) && misaligned(a->true_y, 4)) return ICNN_BE_EINVAL;
-    if ((need & FF_OUT) && misaligned(a->yhat, 4)) return ICNN_BE_EINVAL;
-    if ((need & FF_LOSS) && (misaligned(a->loss, 4) || reinterpret_cast<uintptr_t>(a->f1_tallies) % 4)) return ICNN_BE_EINVAL;
-    if ((need & FF_GRAD) && misaligned(a->grad, 16)) return ICNN_BE_EINVAL;
-    if (need & FF_ADAM) {
-        if (misaligned(a->m, 16) || misaligned(a->v, 16) || misaligned(a->step, 4)) return ICNN_BE_EINVAL;
-        if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f) || !std::isfinite(a->lr))
-            return ICNN_BE_EINVAL;
-    }
-    if (need & FF_MOVING) {
-        for (int i = 0; i < a->n_layers; ++i)
-            if (misaligned(a->mv.mean[i], 4) || misaligned(a->mv.var[i], 4)) return ICNN_BE_EINVAL;
-        if (!(a->mv.decay >= 0.f && a->mv.decay <= 1.f)) return ICNN_BE_EINVAL;
-    }
-    if (!(a->bn_eps > 0.f)) return ICNN_BE_EINVAL;
-    return 0;
-}
-}  // namespace
-
-int icnn_be_ff_param_floats(int n_features, int n_labels, int n_layers, const int *width, long long *n) {
-    if (!ff_sizes_ok(n_features, n_labels, n_layers, width) || !n) return ICNN_BE_EINVAL;
-    *n = icnn_be::ff_param_floats(n_features, n_labels, n_layers, width);
-    return 0;
-}
-
-size_t icnn_be_ff_work_bytes(int batch, int n_features, int n_labels, int n_layers, const int *width) {
-    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width)) return 0;
-    return icnn_be::ff_work_floats(batch, n_features, n_labels, n_layers, width, nullptr) * sizeof(float);
-}
-
-int icnn_be_ff_work_offsets(int batch, int n_features, int n_labels, int n_layers, const int *width,
-                            long long off[ICNN_BE_FF_WORK_PIECES]) {
-    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width) || !off) return ICNN_BE_EINVAL;
-    icnn_be::ff_work_floats(batch, n_features, n_labels, n_layers, width, off);
-    return 0;
-}
-
-int icnn_be_ff_forward(const icnn_be_ff_args *a, int mode, void *stream) {
-    if (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING) return ICNN_BE_EINVAL;
-    const bool with_y = a && a->true_y;
-    unsigned need = FF_X | FF_OUT | FF_WORK | (with_y ? FF_Y | FF_LOSS : 0u);
-    need |= mode == ICNN_BE_BN_MOVING ? FF_MOVING : FF_TRAIN_BATCH;
-    if (int rc = check_ff(a, stream, need)) return rc;
-    return done(icnn_be::launch_ff_forward(*a, mode, with_y, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ff_backward(const icnn_be_ff_args *a, void *stream) {
-    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_WORK | FF_GRAD)) return rc;
-    return done(icnn_be::launch_ff_backward(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ff_grads(const icnn_be_ff_args *a, void *stream) {
-    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_WORK | FF_GRAD)) return rc;
-    return done(icnn_be::launch_ff_grads(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ff_update(const icnn_be_ff_args *a, void *stream) {
-    if (int rc = check_ff(a, stream, FF_GRAD | FF_ADAM)) return rc;
-    return done(icnn_be::launch_ff_update(*a, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_ff_step(const icnn_be_ff_args *a, void *stream) {
-    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_GRAD | FF_ADAM | FF_WORK))
-        return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = icnn_be::launch_ff_forward(*a, ICNN_BE_BN_BATCH, true, s);
-    if (e == hipSuccess) e = icnn_be::launch_ff_backward(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_ff_grads(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_ff_update(*a, s);
-    if (e == hipSuccess) e = icnn_be::launch_ff_fold(*a, s);
-    return done(e);
-}
-
-int icnn_be_ff_eval(const icnn_be_ff_args *a, void *stream) {
-    if (int rc = check_ff(a, stream, FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_WORK)) return rc;
-    return done(icnn_be::launch_ff_forward(*a, ICNN_BE_BN_MOVING, true, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {
-    if (int rc = check_replay(m)) return rc;
-    if (!stage || reinterpret_cast<uintptr_t>(stage) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_replay_enqueue(*m, stage, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
-                          float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
-    if (int rc = check_replay(m)) return rc;
-    if (batch < 1 || fill < 2 || fill > m->size - 1) return ICNN_BE_EINVAL;
-    if (!obs || !act || !rew || !ob2 || !term || !idx) return ICNN_BE_EINVAL;
-    const void *a4[] = {obs, rew, ob2, idx};
-    for (const void *p : a4)
-        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    const icnn_be::ReplaySampleLaunch l{*m, batch, seed, obs, act, rew, ob2, term, idx};
-    return done(icnn_be::launch_replay_sample(l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_vec_replay_enqueue(const icnn_be_vec_replay *m, const float *obs, const double *act, const float *rew,
-                               const unsigned char *term, void *stream) {
-    if (int rc = check_vec_replay(m)) return rc;
-    if (!obs || !act || !rew || !term) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(obs) % 4 || reinterpret_cast<uintptr_t>(rew) % 4 || reinterpret_cast<uintptr_t>(act) % 8 ||
-        reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_vec_replay_enqueue(*m, obs, act, rew, term, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_vec_replay_sample(const icnn_be_vec_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
-                              float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
-    if (int rc = check_vec_replay(m)) return rc;
-    if (batch < 1 || fill < 2 || fill > m->steps - 1) return ICNN_BE_EINVAL;
-    if (!obs || !act || !rew || !ob2 || !term || !idx) return ICNN_BE_EINVAL;
-    const void *a4[] = {obs, rew, ob2, idx};
-    for (const void *p : a4)
-        if (reinterpret_cast<uintptr_t>(p) % 4) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(act) % 8 || reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
-    const icnn_be::ReplaySampleLaunch l{icnn_be_replay{}, batch, seed, obs, act, rew, ob2, term, idx};
-    return done(icnn_be::launch_vec_replay_sample(*m, l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_explore(int n_envs, int dimA, const void *raw, int raw_f32, double *noise, int *counter, double theta, double sigma,
-                    unsigned long long seed, int test, double *action, void *stream) {
-    if (n_envs < 1 || dimA < 1 || !raw || !noise || !counter || !action) return ICNN_BE_EINVAL;
-    if ((long long)n_envs * dimA > 0x7fffffffLL) return ICNN_BE_ELIMIT;
-    if (!(theta == theta) || !(sigma == sigma)) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(raw) % (raw_f32 ? 4 : 8) || reinterpret_cast<uintptr_t>(noise) % 8 ||
-        reinterpret_cast<uintptr_t>(action) % 8 || reinterpret_cast<uintptr_t>(counter) % 4 ||
-        reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_explore(n_envs, dimA, raw, raw_f32 != 0, noise, counter, theta, sigma, seed, test != 0, action,
-                                        static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_dataset_draw(const icnn_be_dataset *d, int batch, unsigned long long seed, void *const dst[], int *idx,
-                         void *stream) {
-    if (!d || !d->ctrl || !idx || !dst) return ICNN_BE_EINVAL;
-    if (d->n_rows < 1 || batch < 1 || d->n_arrays < 1 || d->n_arrays > ICNN_BE_DATASET_MAX_ARRAYS) return ICNN_BE_EINVAL;
-    for (int a = 0; a < d->n_arrays; ++a) {
-        if (!d->src[a] || !dst[a] || d->row_words[a] < 1) return ICNN_BE_EINVAL;
-        if (reinterpret_cast<uintptr_t>(d->src[a]) % 16 || reinterpret_cast<uintptr_t>(dst[a]) % 16) return ICNN_BE_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(idx) % 16 || reinterpret_cast<uintptr_t>(d->ctrl) % 4 ||
-        reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    const icnn_be::DatasetDrawLaunch l{*d, batch, seed, dst, idx};
-    return done(icnn_be::launch_dataset_draw(l, static_cast<hipStream_t>(stream)));
-}
-
-int icnn_be_log_row(const icnn_be_step_log *L, void *stream) {
-    if (!L || !L->rows || !L->ctrl || L->cap < 1 || L->width < 1 || L->width > ICNN_BE_LOG_MAX_COLUMNS) return ICNN_BE_EINVAL;
-    for (int j = 0; j < L->width; ++j) {
-        if (!L->col[j] || L->kind[j] < ICNN_BE_LOG_F32 || L->kind[j] > ICNN_BE_LOG_I32) return ICNN_BE_EINVAL;
-        if (reinterpret_cast<uintptr_t>(L->col[j]) % (L->kind[j] == ICNN_BE_LOG_F64 ? 8 : 4)) return ICNN_BE_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(L->rows) % 8 || reinterpret_cast<uintptr_t>(L->ctrl) % 4 ||
-        reinterpret_cast<uintptr_t>(stream) % 8)
-        return ICNN_BE_EINVAL;
-    return done(icnn_be::launch_log_row(*L, static_cast<hipStream_t>(stream)));
-}
-
 }  // extern "C"
-

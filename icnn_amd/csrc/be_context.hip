@@ -421,8 +421,9 @@ hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const
     return launch_kernel(bn_fold_kernel, dim3((most + 255) / 256, nl), dim3(256), 0, stream, a);
 }
 
-hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
-                            const float *beta, float eps, hipStream_t stream) {
+// inference-mode BatchNorm in place on u[rows][ld], columns [0, cols)
+static hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
+                                   const float *beta, float eps, hipStream_t stream) {
     const size_t total = (size_t)rows * cols;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     return launch_kernel(ctx_bn_affine_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, u, ld, rows, cols, mean, var,

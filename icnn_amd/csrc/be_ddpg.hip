@@ -16,6 +16,7 @@
 //
 // Products: mfma_f32_16x16x4f32, a wave owning two 16-column tiles of the output at a time (two independent accumulators);
 // per 16 values of k a lane takes four consecutive k (the k order inside the block is permuted alike in both operands).
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_tile.h"
 #include "be_train_common.h"
@@ -220,7 +221,14 @@ Pitches pitches(int dimO, int dimA, int l1, int l2) {
     return {pitch_of(max2(dimO, l2)), pitch_of(max2(l1 + dimA, l2)), pitch_of(max2(l1, l2)), pitch_of(l2), pitch_of(dimA)};
 }
 
-// the workspace, piece by piece (ICNN_BE_DDPG_W_*): float offsets
+long long ddpg_policy_floats(int dimO, int dimA, int l1, int l2) {
+    return (long long)dimO * l1 + l1 + (long long)l1 * l2 + l2 + (long long)l2 * dimA + dimA;
+}
+long long ddpg_critic_floats(int dimO, int dimA, int l1, int l2) {
+    return (long long)dimO * l1 + l1 + (long long)(l1 + dimA) * l2 + l2 + l2 + 1;
+}
+
+// the workspace, piece by piece (ICNN_BE_DDPG_W_*): float offsets; off may be NULL
 size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
     const size_t b = (size_t)B;
     const int tiles = (B + TS - 1) / TS;
@@ -236,19 +244,6 @@ size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
 struct Work : WorkPieces<ICNN_BE_DDPG_WORK_PIECES> {
     Work(const icnn_be_ddpg_args &d) : WorkPieces(d.work) { work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off); }
 };
-
-}  // namespace
-
-long long ddpg_policy_floats(int dimO, int dimA, int l1, int l2) {
-    return (long long)dimO * l1 + l1 + (long long)l1 * l2 + l2 + (long long)l2 * dimA + dimA;
-}
-long long ddpg_critic_floats(int dimO, int dimA, int l1, int l2) {
-    return (long long)dimO * l1 + l1 + (long long)(l1 + dimA) * l2 + l2 + l2 + 1;
-}
-
-bool ddpg_fits(int dimO, int dimA, int l1, int l2) { return pitches(dimO, dimA, l1, l2).chain_bytes() <= LDS_BYTES; }
-
-size_t ddpg_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off) { return work_walk(B, dimO, dimA, l1, l2, off); }
 
 hipError_t launch_ddpg_chain(const icnn_be_ddpg_args &d, hipStream_t stream) {
     const Work w(d);
@@ -310,6 +305,15 @@ hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStr
     return launch_param_sets_update(u, stream);
 }
 
+}  // namespace
+
+// the sizes every icnn_be_ddpg_* entry accepts: the limits of include/icnn_be.h and the chain kernel's LDS
+bool ddpg_sizes_ok(int dimO, int dimA, int l1, int l2) {
+    return dimO >= 1 && dimO <= ICNN_BE_DDPG_MAX_OBS && dimA >= 1 && dimA <= ICNN_BE_DDPG_MAX_ACT && l1 >= 1 &&
+           l1 <= ICNN_BE_DDPG_MAX_HIDDEN && l2 >= 1 && l2 <= ICNN_BE_DDPG_MAX_HIDDEN &&
+           pitches(dimO, dimA, l1, l2).chain_bytes() <= LDS_BYTES;
+}
+
 hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, const float *theta, const float *obs,
                                const double *act, int B, float *out, hipStream_t stream) {
     const Pitches p = pitches(dimO, dimA, l1, l2);
@@ -317,4 +321,82 @@ hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, 
     return launch_kernel(critic ? ddpg_q_kernel : ddpg_act_kernel, dim3((B + TS - 1) / TS), dim3(DT), p.fwd_bytes(), stream, a);
 }
 
+namespace {
+// what every icnn_be_ddpg_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
+int check_ddpg(const icnn_be_ddpg_args *a, void *stream, bool need_loss) {
+    if (!a || !ddpg_sizes_ok(a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
+    if (int rc = check_replay_step(*a, stream, need_loss)) return rc;
+    const void *a16[] = {a->theta_q, a->theta_p, a->target_q, a->target_p, a->m_q, a->v_q, a->m_p, a->v_p, a->grad_q, a->grad_p};
+    for (const void *p : a16)
+        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
+    if (!(a->pl2norm >= 0.f) || !std::isfinite(a->pl2norm) || !std::isfinite(a->prate)) return ICNN_BE_EINVAL;
+    return 0;
+}
+}  // namespace
+
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_ddpg_param_floats(int dimO, int dimA, int l1, int l2, long long *np, long long *nq) {
+    if (!ddpg_sizes_ok(dimO, dimA, l1, l2) || !np || !nq) return ICNN_BE_EINVAL;
+    *np = ddpg_policy_floats(dimO, dimA, l1, l2);
+    *nq = ddpg_critic_floats(dimO, dimA, l1, l2);
+    return 0;
+}
+
+size_t icnn_be_ddpg_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
+    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return 0;
+    return work_walk(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
+}
+
+int icnn_be_ddpg_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_DDPG_WORK_PIECES]) {
+    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
+    work_walk(batch, dimO, dimA, l1, l2, off);
+    return 0;
+}
+
+int icnn_be_ddpg_chain(const icnn_be_ddpg_args *a, void *stream) {
+    if (int rc = check_ddpg(a, stream, false)) return rc;
+    return api_done(launch_ddpg_chain(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ddpg_grads(const icnn_be_ddpg_args *a, void *stream) {
+    if (int rc = check_ddpg(a, stream, false)) return rc;
+    return api_done(launch_ddpg_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ddpg_update(const icnn_be_ddpg_args *a, void *stream) {
+    if (int rc = check_ddpg(a, stream, false)) return rc;
+    return api_done(launch_ddpg_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ddpg_step(const icnn_be_ddpg_args *a, void *stream) {
+    if (int rc = check_ddpg(a, stream, true)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch_ddpg_chain(*a, s);
+    if (e == hipSuccess) e = launch_ddpg_grads(*a, s);
+    if (e == hipSuccess) e = launch_ddpg_update(*a, true, s);
+    return api_done(e);
+}
+
+int icnn_be_ddpg_act(int dimO, int dimA, int l1, int l2, const float *theta_p, const float *obs, int batch, float *out,
+                     void *stream) {
+    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_p, 16) || misaligned(obs, 4) || misaligned(out, 4) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    return api_done(launch_ddpg_forward(false, dimO, dimA, l1, l2, theta_p, obs, nullptr, batch, out,
+                                        static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ddpg_q(int dimO, int dimA, int l1, int l2, const float *theta_q, const float *obs, const double *act, int batch,
+                   float *out, void *stream) {
+    if (batch < 1 || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_q, 16) || misaligned(obs, 4) || misaligned(act, 8) || misaligned(out, 4) || !stream_ok(stream))
+        return ICNN_BE_EINVAL;
+    return api_done(launch_ddpg_forward(true, dimO, dimA, l1, l2, theta_q, obs, act, batch, out,
+                                        static_cast<hipStream_t>(stream)));
+}
+
+}  // extern "C"

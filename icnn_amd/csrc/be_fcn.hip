@@ -26,6 +26,7 @@
 //   fcn_adam_kernel    torch.optim.Adam's element arithmetic with the step count on the device
 #include <cmath>
 
+#include "be_api_check.h"
 #include "be_common.h"
 #include "be_kernels.h"
 #include "be_train_common.h"
@@ -647,12 +648,10 @@ hipError_t launch_update(const icnn_be_fcn_args &d, hipStream_t stream) {
 // what an entry needs beyond the sizes
 enum : unsigned { N_TRAIN = 1, N_X = 2, N_T = 4, N_YHAT = 8, N_LOSS = 16, N_GRAD = 32, N_ADAM = 64, N_WORK = 128, N_THETA = 256 };
 
-bool misaligned(const void *p, uintptr_t to) { return !p || reinterpret_cast<uintptr_t>(p) % to; }
-
 int check(const icnn_be_fcn_args *a, void *stream, unsigned need) {
     if (!a || !sizes_ok(a->H, a->W, a->k)) return ICNN_BE_EINVAL;
     if (a->batch < 1 || a->batch > ((need & N_TRAIN) ? ICNN_BE_FCN_MAX_BATCH : ICNN_BE_FCN_MAX_EVAL_BATCH)) return ICNN_BE_EINVAL;
-    if (reinterpret_cast<uintptr_t>(stream) % 8) return ICNN_BE_EINVAL;
+    if (!stream_ok(stream)) return ICNN_BE_EINVAL;
     if ((need & N_THETA) && misaligned(a->theta, 16)) return ICNN_BE_EINVAL;
     if ((need & N_WORK) && misaligned(a->work, 16)) return ICNN_BE_EINVAL;
     if ((need & N_X) && misaligned(a->x, 4)) return ICNN_BE_EINVAL;
@@ -662,8 +661,7 @@ int check(const icnn_be_fcn_args *a, void *stream, unsigned need) {
     if ((need & N_GRAD) && misaligned(a->grad, 16)) return ICNN_BE_EINVAL;
     if (need & N_ADAM) {
         if (misaligned(a->m, 16) || misaligned(a->v, 16) || misaligned(a->step, 4)) return ICNN_BE_EINVAL;
-        if (!(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps > 0.f) || !std::isfinite(a->lr))
-            return ICNN_BE_EINVAL;
+        if (!adam_constants_ok(a->beta1, a->beta2, a->eps) || !std::isfinite(a->lr)) return ICNN_BE_EINVAL;
     }
     return 0;
 }

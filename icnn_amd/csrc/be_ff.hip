@@ -19,6 +19,7 @@
 //   the fold              bn_fold_kernel (be_context.hip).
 //
 // The product (col_gemm), the column sums and the accumulator walk are be_col_gemm.h.
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_train_common.h"
 #include "be_col_gemm.h"
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(FT) void ff_layer_bwd_kernel(FfBwdArgs p) {
 
 int row_groups(int B, int mode) { return mode == ICNN_BE_BN_MOVING ? (B + FROWS_MOVING - 1) / FROWS_MOVING : 1; }
 
-// the workspace, piece by piece (ICNN_BE_FF_W_*): float offsets
+// the workspace, piece by piece (ICNN_BE_FF_W_*): float offsets; off may be NULL
 size_t work_walk(int B, int nl, const int *width, int n_labels, long long *off) {
     const size_t b = (size_t)B;
     size_t floats[ICNN_BE_FF_WORK_PIECES] = {};
@@ -244,8 +245,6 @@ struct Work : WorkPieces<ICNN_BE_FF_WORK_PIECES> {
     Work(const icnn_be_ff_args &d) : WorkPieces(d.work) { work_walk(d.batch, d.n_layers, d.width, d.n_labels, off); }
 };
 
-}  // namespace
-
 long long ff_param_floats(int n_features, int n_labels, int n_layers, const int *width) {
     long long n = 0;
     int in = n_features;
@@ -256,11 +255,7 @@ long long ff_param_floats(int n_features, int n_labels, int n_layers, const int 
     return n + (long long)(in + 1) * n_labels;
 }
 
-size_t ff_work_floats(int B, int n_features, int n_labels, int n_layers, const int *width, long long *off) {
-    (void)n_features;
-    return work_walk(B, n_layers, width, n_labels, off);
-}
-
+// the L layer launches and the head; with_y: loss, tallies and (batch mode) d loss / d logits too
 hipError_t launch_ff_forward(const icnn_be_ff_args &d, int mode, bool with_y, hipStream_t stream) {
     const Work w(d);
     const int moving = mode == ICNN_BE_BN_MOVING, B = d.batch, groups = row_groups(B, mode);
@@ -357,4 +352,105 @@ hipError_t launch_ff_fold(const icnn_be_ff_args &d, hipStream_t stream) {
     return launch_bn_fold(d.mv, stat, d.width, d.n_layers, 1, stream);
 }
 
+bool ff_sizes_ok(int n_features, int n_labels, int n_layers, const int *width) {
+    if (n_features < 1 || n_features > ICNN_BE_FF_MAX_FEATURES || n_labels < 1 || n_labels > ICNN_BE_FF_MAX_WIDTH) return false;
+    if (n_layers < 1 || n_layers > ICNN_BE_FF_MAX_LAYERS || !width) return false;
+    for (int i = 0; i < n_layers; ++i)
+        if (width[i] < 1 || width[i] > ICNN_BE_FF_MAX_WIDTH) return false;
+    return true;
+}
+
+// what an icnn_be_ff_* entry needs beyond the sizes
+enum : unsigned {
+    FF_TRAIN_BATCH = 1, FF_X = 2, FF_Y = 4, FF_OUT = 8, FF_MOVING = 16, FF_GRAD = 32, FF_ADAM = 64, FF_WORK = 128, FF_LOSS = 256
+};
+int check_ff(const icnn_be_ff_args *a, void *stream, unsigned need) {
+    if (!a || !ff_sizes_ok(a->n_features, a->n_labels, a->n_layers, a->width)) return ICNN_BE_EINVAL;
+    if (a->batch < 1 || ((need & FF_TRAIN_BATCH) && (a->batch < 2 || a->batch > ICNN_BE_FF_MAX_BATCH))) return ICNN_BE_EINVAL;
+    if (misaligned(a->theta, 16) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    if ((need & FF_WORK) && misaligned(a->work, 16)) return ICNN_BE_EINVAL;
+    if ((need & FF_X) && misaligned(a->x, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_Y) && misaligned(a->true_y, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_OUT) && misaligned(a->yhat, 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_LOSS) && (misaligned(a->loss, 4) || reinterpret_cast<uintptr_t>(a->f1_tallies) % 4)) return ICNN_BE_EINVAL;
+    if ((need & FF_GRAD) && misaligned(a->grad, 16)) return ICNN_BE_EINVAL;
+    if (need & FF_ADAM) {
+        if (misaligned(a->m, 16) || misaligned(a->v, 16) || misaligned(a->step, 4)) return ICNN_BE_EINVAL;
+        if (!adam_constants_ok(a->beta1, a->beta2, a->eps) || !std::isfinite(a->lr)) return ICNN_BE_EINVAL;
+    }
+    if (need & FF_MOVING) {
+        for (int i = 0; i < a->n_layers; ++i)
+            if (misaligned(a->mv.mean[i], 4) || misaligned(a->mv.var[i], 4)) return ICNN_BE_EINVAL;
+        if (!(a->mv.decay >= 0.f && a->mv.decay <= 1.f)) return ICNN_BE_EINVAL;
+    }
+    if (!(a->bn_eps > 0.f)) return ICNN_BE_EINVAL;
+    return 0;
+}
+
+}  // namespace
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_ff_param_floats(int n_features, int n_labels, int n_layers, const int *width, long long *n) {
+    if (!ff_sizes_ok(n_features, n_labels, n_layers, width) || !n) return ICNN_BE_EINVAL;
+    *n = ff_param_floats(n_features, n_labels, n_layers, width);
+    return 0;
+}
+
+size_t icnn_be_ff_work_bytes(int batch, int n_features, int n_labels, int n_layers, const int *width) {
+    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width)) return 0;
+    return work_walk(batch, n_layers, width, n_labels, nullptr) * sizeof(float);
+}
+
+int icnn_be_ff_work_offsets(int batch, int n_features, int n_labels, int n_layers, const int *width,
+                            long long off[ICNN_BE_FF_WORK_PIECES]) {
+    if (batch < 1 || !ff_sizes_ok(n_features, n_labels, n_layers, width) || !off) return ICNN_BE_EINVAL;
+    work_walk(batch, n_layers, width, n_labels, off);
+    return 0;
+}
+
+int icnn_be_ff_forward(const icnn_be_ff_args *a, int mode, void *stream) {
+    if (mode != ICNN_BE_BN_BATCH && mode != ICNN_BE_BN_MOVING) return ICNN_BE_EINVAL;
+    const bool with_y = a && a->true_y;
+    unsigned need = FF_X | FF_OUT | FF_WORK | (with_y ? FF_Y | FF_LOSS : 0u);
+    need |= mode == ICNN_BE_BN_MOVING ? FF_MOVING : FF_TRAIN_BATCH;
+    if (int rc = check_ff(a, stream, need)) return rc;
+    return api_done(launch_ff_forward(*a, mode, with_y, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_backward(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_WORK | FF_GRAD)) return rc;
+    return api_done(launch_ff_backward(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_grads(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_WORK | FF_GRAD)) return rc;
+    return api_done(launch_ff_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_update(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_GRAD | FF_ADAM)) return rc;
+    return api_done(launch_ff_update(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_ff_step(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_TRAIN_BATCH | FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_GRAD | FF_ADAM | FF_WORK))
+        return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch_ff_forward(*a, ICNN_BE_BN_BATCH, true, s);
+    if (e == hipSuccess) e = launch_ff_backward(*a, s);
+    if (e == hipSuccess) e = launch_ff_grads(*a, s);
+    if (e == hipSuccess) e = launch_ff_update(*a, s);
+    if (e == hipSuccess) e = launch_ff_fold(*a, s);
+    return api_done(e);
+}
+
+int icnn_be_ff_eval(const icnn_be_ff_args *a, void *stream) {
+    if (int rc = check_ff(a, stream, FF_X | FF_Y | FF_OUT | FF_LOSS | FF_MOVING | FF_WORK)) return rc;
+    return api_done(launch_ff_forward(*a, ICNN_BE_BN_MOVING, true, static_cast<hipStream_t>(stream)));
+}
+
+}  // extern "C"

@@ -1,4 +1,6 @@
-// Internal launch interfaces between the C ABI (be_api.hip) and the kernels.
+// Internal launch interfaces between the C ABI (be_api.hip) and the kernels, and between the units.  Only what a second
+// translation unit calls is declared here: an entry that takes no icnn_be_state, model or context descriptor is defined in
+// its own unit (be_api.hip has the rule), and that unit's launchers are file-local.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,12 +124,10 @@ hipError_t launch_fc_context(const icnn_be_fc_ctx &c, const float *x, int batch,
                              int updates = 0, const int *updates_dev = nullptr);
 size_t ctx_bn_work_floats(const icnn_be_fc_ctx &c, int batch);
 // `updates` folds of stat[l] (mean [n[l]] then biased variance [n[l]], device) into mv's layers 0 .. nl-1 (n[l] = 0: none),
-// one launch; and inference-mode BatchNorm in place on u[rows][ld], columns [0, cols).  updates_dev (device int32, may be
-// NULL) replaces `updates` by a count read on the device; gate_dev (may be NULL): no fold when *gate_dev <= 0
+// one launch.  updates_dev (device int32, may be NULL) replaces `updates` by a count read on the device; gate_dev (may be
+// NULL): no fold when *gate_dev <= 0
 hipError_t launch_bn_fold(const icnn_be_bn_moving &mv, float *const *stat, const int *n, int nl, int updates,
                           hipStream_t stream, const int *updates_dev = nullptr, const int *gate_dev = nullptr);
-hipError_t launch_bn_affine(float *u, int ld, int rows, int cols, const float *mean, const float *var, const float *gamma,
-                            const float *beta, float eps, hipStream_t stream);
 hipError_t launch_fc_context_stage(const icnn_be_fc_ctx &c, int i, const float *x, int batch, float *ctx, int ctx_width,
                                    float *work, hipStream_t stream);
 int launch_fc_context_sums(const icnn_be_fc_ctx &c, int i, int batch, float *work, double *stats, hipStream_t stream,
@@ -266,7 +266,6 @@ hipError_t launch_fc_pgd(const icnn_be_fc_model &m, const float *ctx, const doub
 hipError_t launch_conv_pgd(const icnn_be_conv_model &m, const float *ctx, const double *y0, int batch, int n_iter, double lr,
                            double lo, double hi, double *y_out, double *obj, double *obj_final, void *workspace,
                            hipStream_t stream);
-hipError_t launch_entropy_objective(const float *E, const double *y, int batch, int n, double *out, hipStream_t stream);
 hipError_t launch_bundle_trace(const icnn_be_state &st, double *obj, int *calls, hipStream_t stream);
 hipError_t launch_dual_bound(const icnn_be_state &st, double *out, hipStream_t stream);
 // ---- FICNN (be_ficnn.hip: context, energy / gradient, GD; be_train_ficnn.hip: training gradient) ----
@@ -309,175 +308,20 @@ struct FeedPlanLaunch {
     int *row_offset, *counts;     // [B + 1]; counts[3] = rows, fg evaluations, OR of the status words
     double *loss_out;
     int *tallies;                 // [B][3] tp / fp / fn (cross entropy; may be NULL)
-    void *work;                   // feed_plan_work_bytes(B)
+    void *work;                   // icnn_be_feed_plan_work_bytes(B)
 };
-size_t feed_plan_work_bytes(int batch);
 hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream);
-hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
-                           int *fd_sample, hipStream_t stream);
-hipError_t launch_step_gate(const int *counts, int mask, int *gate, hipStream_t stream);
 
-// ---- the back-optimisation training step's feed (be_train_gd.hip) -------------------
-struct GdFeedLaunch {
-    const double *yK;             // [B][n] y_K (float32 values)
-    const float *t;               // [B][n] targets
-    const double *coef;           // [K] step coefficients
-    int B, n, K;
-    float scale;                  // float32(1) / float32(B n)
-    double *v_rows, *c_rows;      // [B K][n], [B K]
-    int *row_offset;              // [B + 1]
-    float *loss;
-    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
-    void *work;                   // gd_feed_work_bytes(B)
-};
-size_t gd_feed_work_bytes(int batch);
-hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream);
-
-// the same feed for the loss mean((px (y_K - t))^2), on a grid of B x S workgroups; v_rows, c_rows, row_offset (and coef)
-// NULL together: the loss alone
-struct GdFeedPxLaunch {
-    const double *yK;
-    const float *t;
-    const double *coef;
-    int B, n, K;
-    float scale, px;
-    double *v_rows, *c_rows;
-    int *row_offset;
-    float *loss;
-    void *work;                   // gd_feed_work_bytes(B)
-};
-#ifndef ICNN_BE_GD_FEED_PX_CHUNK
-#define ICNN_BE_GD_FEED_PX_CHUNK 8192         // an experiment builds another value (tools/conv_gd_step_time.py --alt-lib)
-#endif
-constexpr int GD_FEED_PX_CHUNK = ICNN_BE_GD_FEED_PX_CHUNK;   // elements of a sample's [K][n] block per workgroup, at most
-constexpr int GD_FEED_PX_MAX_CHUNKS = 65535; // gridDim.y
-long long gd_feed_px_chunks(int n, int K);
-hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream);
-
-// ---- the epoch level of the training scripts (be_train_epoch.hip) --------------------
-// the loss-only form of the feed above: loss [1] and, unless NULL, tallies [B][3]; nothing else is written
-struct GdEvalLaunch {
-    const double *yK;             // [B][n] y_K (float32 values)
-    const float *t;               // [B][n] targets
-    int B, n;
-    float *loss;
-    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
-    void *work;                   // gd_feed_work_bytes(B)
-};
-hipError_t launch_gd_eval(const GdEvalLaunch &l, hipStream_t stream);
-hipError_t launch_macro_f1(const int *tallies, int B, double *f1, hipStream_t stream);
-hipError_t launch_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, hipStream_t stream);
-
-// ---- parameter update (be_train_update.hip): plain, gated, and the RL critic's with its target net ------
+// ---- parameter update (be_train_update.hip): the workgroups of an n-element update, which the table update of
+// be_train_table.hip and its callers size their partial sums by
 long long param_update_blocks(long long n);
-hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream);   // go NULL: ungated
-hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream);
-hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream);
 
-// ---- the RL critic's TD target and loss (be_rl_train.hip) ---------------------------
-struct RlTdLaunch {
-    int batch, n;
-    const float *e_critic;
-    const double *act;
-    const float *rew;
-    const unsigned char *term;
-    const float *q2_src;
-    const double *act2;
-    float discount;
-    const float *theta;
-    long long n_theta;
-    const unsigned char *decay;
-    float l2norm, wd;
-    float *td;
-    double *c;
-    float *loss;
-    void *work;
-};
-int rl_td_blocks(long long n_theta);
-hipError_t launch_rl_td(const RlTdLaunch &l, hipStream_t stream);
-
-// ---- the RL agent's replay memory (be_rl_replay.hip) -----------------------------------
-struct ReplaySampleLaunch {
-    icnn_be_replay m;
-    int batch;
-    unsigned long long seed;
-    float *obs;
-    double *act;
-    float *rew;
-    float *ob2;
-    unsigned char *term;
-    int *idx;
-};
-long long replay_sample_blocks(int batch);
-hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream);
-hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream);
-// E lockstep environments (icnn_be_vec_replay; l.m is not read) and the exploration noise (icnn_be_explore)
-hipError_t launch_vec_replay_enqueue(const icnn_be_vec_replay &m, const float *obs, const double *act, const float *rew,
-                                     const unsigned char *term, hipStream_t stream);
-hipError_t launch_vec_replay_sample(const icnn_be_vec_replay &m, const ReplaySampleLaunch &l, hipStream_t stream);
-hipError_t launch_explore(int n_envs, int dimA, const void *raw, bool raw_f32, double *noise, int *counter, double theta,
-                          double sigma, unsigned long long seed, bool test, double *action, hipStream_t stream);
-
-// ---- the training set on the device and the step log (be_train_data.hip) ----------------------
-struct DatasetDrawLaunch {
-    icnn_be_dataset d;
-    int batch;
-    unsigned long long seed;
-    void *const *dst;             // [d.n_arrays]
-    int *idx;
-};
-hipError_t launch_dataset_draw(const DatasetDrawLaunch &l, hipStream_t stream);
-hipError_t launch_log_row(const icnn_be_step_log &L, hipStream_t stream);
-
-// ---- the DDPG step (be_ddpg.hip) ----------------------------------------------------
-long long ddpg_policy_floats(int dimO, int dimA, int l1, int l2);
-long long ddpg_critic_floats(int dimO, int dimA, int l1, int l2);
-bool ddpg_fits(int dimO, int dimA, int l1, int l2);      // the chain kernel's LDS
-// floats of the workspace; off (or NULL): the float offset of each ICNN_BE_DDPG_W_* piece
-size_t ddpg_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
-hipError_t launch_ddpg_chain(const icnn_be_ddpg_args &d, hipStream_t stream);
-hipError_t launch_ddpg_grads(const icnn_be_ddpg_args &d, hipStream_t stream);
-hipError_t launch_ddpg_update(const icnn_be_ddpg_args &d, bool with_loss, hipStream_t stream);
+// ---- what the RL units call of one another ------------------------------------------------
+// the sizes every icnn_be_ddpg_* / icnn_be_naf_* entry accepts: the limits of include/icnn_be.h and the chain kernel's LDS
+bool ddpg_sizes_ok(int dimO, int dimA, int l1, int l2);
+bool naf_sizes_ok(int dimO, int dimA, int l1, int l2);
+// pi(obs) (critic false, act NULL) or Q(obs, act) of DDPG's nets for B rows; icnn_be_naf_act runs NAF's U net through it
 hipError_t launch_ddpg_forward(bool critic, int dimO, int dimA, int l1, int l2, const float *theta, const float *obs,
                                const double *act, int B, float *out, hipStream_t stream);
-
-// ---- the NAF step (be_naf.hip) ------------------------------------------------------
-long long naf_net_floats(int dimO, int l1, int l2, int out);      // out: dimA^2 (L), dimA (U), 1 (V)
-bool naf_fits(int dimO, int dimA, int l1, int l2);       // the chain kernel's LDS
-size_t naf_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
-hipError_t launch_naf_chain(const icnn_be_naf_args &d, hipStream_t stream);
-hipError_t launch_naf_grads(const icnn_be_naf_args &d, hipStream_t stream);
-hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStream_t stream);
-hipError_t launch_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
-                        const float *obs, const double *act, int B, float *out, hipStream_t stream);
-
-// ---- NAF with BatchNorm (be_naf_bn.hip) ------------------------------------------------
-bool naf_bn_fits(int dimA, int l2);                      // the per-sample kernel's LDS
-// off[ICNN_BE_NAF_BN_VARS], the floats of the vector and of its W and b alone; each may be NULL.  which: 0 L, 1 U, 2 V
-void naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long *off, long long *n, long long *plain);
-size_t naf_bn_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off);
-hipError_t launch_naf_bn_chain(const icnn_be_naf_bn_args &d, hipStream_t stream);
-hipError_t launch_naf_bn_grads(const icnn_be_naf_bn_args &d, hipStream_t stream);
-hipError_t launch_naf_bn_update(const icnn_be_naf_bn_args &d, bool with_loss, hipStream_t stream);
-hipError_t launch_naf_bn_fold(const icnn_be_naf_bn_args &d, hipStream_t stream);
-// theta_l NULL: u(obs) into out [B][dimA]; else q(obs, act) into out [B]
-hipError_t launch_naf_bn_forward(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u,
-                                 const float *theta_v, const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps,
-                                 int moving, const float *obs, const double *act, int B, float *out, void *work,
-                                 hipStream_t stream);
-
-// ---- the feed-forward baseline (be_ff.hip) ---------------------------------------------
-long long ff_param_floats(int n_features, int n_labels, int n_layers, const int *width);
-size_t ff_work_floats(int B, int n_features, int n_labels, int n_layers, const int *width, long long *off);
-// the L layer launches and the head; with_y: loss, tallies and (batch mode) d loss / d logits too
-hipError_t launch_ff_forward(const icnn_be_ff_args &d, int mode, bool with_y, hipStream_t stream);
-hipError_t launch_ff_backward(const icnn_be_ff_args &d, hipStream_t stream);
-hipError_t launch_ff_grads(const icnn_be_ff_args &d, hipStream_t stream);
-hipError_t launch_ff_update(const icnn_be_ff_args &d, hipStream_t stream);
-hipError_t launch_ff_fold(const icnn_be_ff_args &d, hipStream_t stream);
-
-// ---- the FCN baseline (be_fcn.hip defines its icnn_be_fcn_* entries itself) ---------------
-// 0, or the C ABI's error code with the HIP error kept for icnn_be_last_hip_error (be_api.hip)
-int api_done(hipError_t e);
 
 }  // namespace icnn_be

@@ -12,11 +12,12 @@
 //   the weight gradients  grad_table_kernel (be_train_table.hip) over a table of the nine layers.
 //   the update            param_sets_update_kernel (be_train_table.hip) over three parameter sets with one step count; only V
 //                        has a target; sum theta_old^2 of all three enters loss_q.
-//   u for B rows          the U net is DDPG's policy: be_api.hip launches ddpg_act_kernel on theta_u.
+//   u for B rows          the U net is DDPG's policy: icnn_be_naf_act launches ddpg_act_kernel on theta_u.
 //
 // LDS: bA holds the obs rows and later, when no first layer needs them any more, the dimA^2 wide l rows (then d loss / d l in
 // place); bB and bC the two hidden layers of the net at hand.  The hidden layers of U and V are not kept: their backward
 // chains re-read the masks from the workspace, which this workgroup wrote.
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_naf_head.h"
 #include "be_tile.h"
@@ -194,12 +195,16 @@ Pitches pitches(int dimO, int dimA, int l1, int l2) {
     return {pitch_of(max2(dimO, dimA * dimA)), pitch_of(l1), pitch_of(l2), pitch_of(dimA)};
 }
 
+long long naf_net_floats(int dimO, int l1, int l2, int out) {      // out: dimA^2 (L), dimA (U), 1 (V)
+    return (long long)dimO * l1 + l1 + (long long)l1 * l2 + l2 + (long long)l2 * out + out;
+}
+
 long long update_blocks(int dimO, int dimA, int l1, int l2) {
     return param_update_blocks(naf_net_floats(dimO, l1, l2, dimA * dimA)) + param_update_blocks(naf_net_floats(dimO, l1, l2, dimA)) +
            param_update_blocks(naf_net_floats(dimO, l1, l2, 1));
 }
 
-// the workspace, piece by piece (ICNN_BE_NAF_W_*): float offsets
+// the workspace, piece by piece (ICNN_BE_NAF_W_*): float offsets; off may be NULL
 size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
     const size_t b = (size_t)B, nL = (size_t)dimA * dimA;
     const int tiles = (B + TS - 1) / TS;
@@ -215,16 +220,6 @@ size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
 struct Work : WorkPieces<ICNN_BE_NAF_WORK_PIECES> {
     Work(const icnn_be_naf_args &d) : WorkPieces(d.work) { work_walk(d.batch, d.dimO, d.dimA, d.l1, d.l2, off); }
 };
-
-}  // namespace
-
-long long naf_net_floats(int dimO, int l1, int l2, int out) {
-    return (long long)dimO * l1 + l1 + (long long)l1 * l2 + l2 + (long long)l2 * out + out;
-}
-
-bool naf_fits(int dimO, int dimA, int l1, int l2) { return pitches(dimO, dimA, l1, l2).bytes() <= LDS_BYTES; }
-
-size_t naf_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off) { return work_walk(B, dimO, dimA, l1, l2, off); }
 
 hipError_t launch_naf_chain(const icnn_be_naf_args &d, hipStream_t stream) {
     const Work w(d);
@@ -306,4 +301,93 @@ hipError_t launch_naf_update(const icnn_be_naf_args &d, bool with_loss, hipStrea
     return launch_param_sets_update(u, stream);
 }
 
+// what every icnn_be_naf_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
+int check_naf(const icnn_be_naf_args *a, void *stream, bool need_loss) {
+    if (!a || !naf_sizes_ok(a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
+    if (int rc = check_replay_step(*a, stream, need_loss)) return rc;
+    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
+                         a->grad_l, a->grad_u, a->grad_v};
+    for (const void *p : a16)
+        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
+    return 0;
+}
+
+}  // namespace
+
+// the sizes every icnn_be_naf_* entry accepts (and, with its own on top, every icnn_be_naf_bn_* entry): the limits of
+// include/icnn_be.h and the chain kernel's LDS
+bool naf_sizes_ok(int dimO, int dimA, int l1, int l2) {
+    return dimO >= 1 && dimO <= ICNN_BE_NAF_MAX_OBS && dimA >= 1 && dimA <= ICNN_BE_NAF_MAX_ACT && l1 >= 1 &&
+           l1 <= ICNN_BE_NAF_MAX_HIDDEN && l2 >= 1 && l2 <= ICNN_BE_NAF_MAX_HIDDEN &&
+           pitches(dimO, dimA, l1, l2).bytes() <= LDS_BYTES;
+}
+
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_naf_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv) {
+    if (!naf_sizes_ok(dimO, dimA, l1, l2) || !nl || !nu || !nv) return ICNN_BE_EINVAL;
+    *nl = naf_net_floats(dimO, l1, l2, dimA * dimA);
+    *nu = naf_net_floats(dimO, l1, l2, dimA);
+    *nv = naf_net_floats(dimO, l1, l2, 1);
+    return 0;
+}
+
+size_t icnn_be_naf_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return 0;
+    return work_walk(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
+}
+
+int icnn_be_naf_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_WORK_PIECES]) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
+    work_walk(batch, dimO, dimA, l1, l2, off);
+    return 0;
+}
+
+int icnn_be_naf_chain(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return api_done(launch_naf_chain(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_grads(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return api_done(launch_naf_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_update(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, false)) return rc;
+    return api_done(launch_naf_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_step(const icnn_be_naf_args *a, void *stream) {
+    if (int rc = check_naf(a, stream, true)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch_naf_chain(*a, s);
+    if (e == hipSuccess) e = launch_naf_grads(*a, s);
+    if (e == hipSuccess) e = launch_naf_update(*a, true, s);
+    return api_done(e);
+}
+
+int icnn_be_naf_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *obs, int batch, float *out,
+                    void *stream) {
+    // the U net is DDPG's policy; its launch needs DDPG's LDS plan, which holds wherever NAF's does
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2) || !ddpg_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_u, 16) || misaligned(obs, 4) || misaligned(out, 4) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    return api_done(launch_ddpg_forward(false, dimO, dimA, l1, l2, theta_u, obs, nullptr, batch, out,
+                                        static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                  const float *obs, const double *act, int batch, float *out, void *stream) {
+    if (batch < 1 || !naf_sizes_ok(dimO, dimA, l1, l2)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(obs, 4) || misaligned(act, 8) ||
+        misaligned(out, 4) || !stream_ok(stream))
+        return ICNN_BE_EINVAL;
+    return api_done(launch_naf_q(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, obs, act, batch, out,
+                                 static_cast<hipStream_t>(stream)));
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 //   naf_bn_input_bwd_kernel   d beta0 = the column sums of dz1 W1^T
 //   naf_bn_fold_kernel    the moving pairs: L and U once, V twice (obs, then ob2)
 //   the weight gradients  grad_table_kernel, the update param_sets_update_kernel with the betas as the exempt tail
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_col_gemm.h"
 #include "be_naf_head.h"
@@ -330,7 +331,7 @@ NetAt net_at(int dimO, int l1, int l2, int out) {
 }
 int out_of(int which, int dimA) { return which == 0 ? dimA * dimA : which == 1 ? dimA : 1; }
 
-// the workspace, piece by piece (ICNN_BE_NAF_BN_W_*): float offsets
+// the workspace, piece by piece (ICNN_BE_NAF_BN_W_*): float offsets; off may be NULL
 size_t work_walk(int B, int dimO, int dimA, int l1, int l2, long long *off) {
     const size_t b = (size_t)B, S = (size_t)dimO + l1 + l2;
     const int tiles = (B + TS - 1) / TS;
@@ -416,10 +417,7 @@ hipError_t launch_sample(const BnSampleArgs &a, hipStream_t stream) {
     return launch_kernel(naf_bn_sample_kernel, dim3((a.B + TS - 1) / TS), dim3(DT), pitches(a.dimA, a.l2).bytes(), stream, a);
 }
 
-}  // namespace
-
-bool naf_bn_fits(int dimA, int l2) { return pitches(dimA, l2).bytes() <= LDS_BYTES; }
-
+// off[ICNN_BE_NAF_BN_VARS], the floats of the vector and of its W and b alone; each may be NULL.  which: 0 L, 1 U, 2 V
 void naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long *off, long long *n, long long *plain) {
     const NetAt at = net_at(dimO, l1, l2, out_of(which, dimA));
     if (off)
@@ -431,8 +429,6 @@ void naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long *off
     if (n) *n = at.n;
     if (plain) *plain = at.plain;
 }
-
-size_t naf_bn_work_floats(int B, int dimO, int dimA, int l1, int l2, long long *off) { return work_walk(B, dimO, dimA, l1, l2, off); }
 
 hipError_t launch_naf_bn_chain(const icnn_be_naf_bn_args &d, hipStream_t stream) {
     const Work w(d);
@@ -540,6 +536,7 @@ hipError_t launch_naf_bn_fold(const icnn_be_naf_bn_args &d, hipStream_t stream) 
     return launch_kernel(naf_bn_fold_kernel, dim3((a.n + 255) / 256, PASSES - 1), dim3(256), 0, stream, a);
 }
 
+// theta_l NULL: u(obs) into out [B][dimA]; else q(obs, act) into out [B]
 hipError_t launch_naf_bn_forward(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u,
                                  const float *theta_v, const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps,
                                  int moving, const float *obs, const double *act, int B, float *out, void *work,
@@ -565,4 +562,108 @@ hipError_t launch_naf_bn_forward(int dimO, int dimA, int l1, int l2, const float
     return launch_sample(s, stream);
 }
 
+// NAF's sizes, the batch the column kernels hold and the per-sample kernel's LDS
+bool naf_bn_sizes_ok(int batch, int dimO, int dimA, int l1, int l2) {
+    return batch >= 1 && batch <= ICNN_BE_NAF_BN_MAX_BATCH && naf_sizes_ok(dimO, dimA, l1, l2) &&
+           pitches(dimA, l2).bytes() <= LDS_BYTES;
+}
+
+bool bn_mode_ok(int mode) { return mode == ICNN_BE_BN_BATCH || mode == ICNN_BE_BN_MOVING; }
+
+// what every icnn_be_naf_bn_* entry that takes the descriptor refuses before any launch; need_loss: loss may not be NULL
+int check_naf_bn(const icnn_be_naf_bn_args *a, void *stream, bool need_loss) {
+    if (!a || !naf_bn_sizes_ok(a->batch, a->dimO, a->dimA, a->l1, a->l2)) return ICNN_BE_EINVAL;
+    if (int rc = check_replay_step(*a, stream, need_loss)) return rc;
+    const void *a16[] = {a->theta_l, a->theta_u, a->theta_v, a->target_v, a->m_l, a->v_l, a->m_u, a->v_u, a->m_v, a->v_v,
+                         a->grad_l, a->grad_u, a->grad_v};
+    for (const void *p : a16)
+        if (misaligned(p, 16)) return ICNN_BE_EINVAL;
+    if (misaligned(a->mv_l, 4) || misaligned(a->mv_u, 4) || misaligned(a->mv_v, 4)) return ICNN_BE_EINVAL;
+    if (!(a->bn_eps > 0.f) || !(a->bn_decay >= 0.0 && a->bn_decay <= 1.0)) return ICNN_BE_EINVAL;
+    return 0;
+}
+
+}  // namespace
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_naf_bn_param_floats(int dimO, int dimA, int l1, int l2, long long *nl, long long *nu, long long *nv, long long *nt,
+                                long long *ns) {
+    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || !nl || !nu || !nv || !nt || !ns) return ICNN_BE_EINVAL;
+    naf_bn_layout(dimO, dimA, l1, l2, 0, nullptr, nl, nullptr);
+    naf_bn_layout(dimO, dimA, l1, l2, 1, nullptr, nu, nullptr);
+    naf_bn_layout(dimO, dimA, l1, l2, 2, nullptr, nv, nt);
+    *ns = 2LL * (dimO + l1 + l2);
+    return 0;
+}
+
+int icnn_be_naf_bn_layout(int dimO, int dimA, int l1, int l2, int which, long long off[ICNN_BE_NAF_BN_VARS]) {
+    if (!naf_bn_sizes_ok(1, dimO, dimA, l1, l2) || which < 0 || which > 2 || !off) return ICNN_BE_EINVAL;
+    naf_bn_layout(dimO, dimA, l1, l2, which, off, nullptr, nullptr);
+    return 0;
+}
+
+size_t icnn_be_naf_bn_work_bytes(int batch, int dimO, int dimA, int l1, int l2) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2)) return 0;
+    return work_walk(batch, dimO, dimA, l1, l2, nullptr) * sizeof(float);
+}
+
+int icnn_be_naf_bn_work_offsets(int batch, int dimO, int dimA, int l1, int l2, long long off[ICNN_BE_NAF_BN_WORK_PIECES]) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || !off) return ICNN_BE_EINVAL;
+    work_walk(batch, dimO, dimA, l1, l2, off);
+    return 0;
+}
+
+int icnn_be_naf_bn_chain(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return api_done(launch_naf_bn_chain(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_grads(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return api_done(launch_naf_bn_grads(*a, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_update(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, false)) return rc;
+    return api_done(launch_naf_bn_update(*a, a->loss != nullptr, static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_step(const icnn_be_naf_bn_args *a, void *stream) {
+    if (int rc = check_naf_bn(a, stream, true)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = launch_naf_bn_chain(*a, s);
+    if (e == hipSuccess) e = launch_naf_bn_grads(*a, s);
+    if (e == hipSuccess) e = launch_naf_bn_update(*a, true, s);
+    if (e == hipSuccess) e = launch_naf_bn_fold(*a, s);
+    return api_done(e);
+}
+
+int icnn_be_naf_bn_act(int dimO, int dimA, int l1, int l2, const float *theta_u, const float *mv_u, float bn_eps, int mode,
+                       const float *obs, int batch, float *out, void *work, void *stream) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || !bn_mode_ok(mode)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_u, 16) || misaligned(work, 16) || misaligned(mv_u, 4) || misaligned(obs, 4) || misaligned(out, 4) ||
+        !stream_ok(stream) || !(bn_eps > 0.f))
+        return ICNN_BE_EINVAL;
+    return api_done(launch_naf_bn_forward(dimO, dimA, l1, l2, nullptr, theta_u, nullptr, nullptr, mv_u, nullptr, bn_eps,
+                                          mode == ICNN_BE_BN_MOVING, obs, nullptr, batch, out, work,
+                                          static_cast<hipStream_t>(stream)));
+}
+
+int icnn_be_naf_bn_q(int dimO, int dimA, int l1, int l2, const float *theta_l, const float *theta_u, const float *theta_v,
+                     const float *mv_l, const float *mv_u, const float *mv_v, float bn_eps, int mode, const float *obs,
+                     const double *act, int batch, float *out, void *work, void *stream) {
+    if (!naf_bn_sizes_ok(batch, dimO, dimA, l1, l2) || !bn_mode_ok(mode)) return ICNN_BE_EINVAL;
+    if (misaligned(theta_l, 16) || misaligned(theta_u, 16) || misaligned(theta_v, 16) || misaligned(work, 16) ||
+        misaligned(mv_l, 4) || misaligned(mv_u, 4) || misaligned(mv_v, 4) || misaligned(obs, 4) || misaligned(act, 8) ||
+        misaligned(out, 4) || !stream_ok(stream) || !(bn_eps > 0.f))
+        return ICNN_BE_EINVAL;
+    return api_done(launch_naf_bn_forward(dimO, dimA, l1, l2, theta_l, theta_u, theta_v, mv_l, mv_u, mv_v, bn_eps,
+                                          mode == ICNN_BE_BN_MOVING, obs, act, batch, out, work,
+                                          static_cast<hipStream_t>(stream)));
+}
+
+}  // extern "C"

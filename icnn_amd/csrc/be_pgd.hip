@@ -21,6 +21,7 @@
 // bound of min_y E - H).
 #include <cmath>
 
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_gd_rows_dev.h"
 
@@ -294,11 +295,6 @@ hipError_t launch_conv_pgd(const icnn_be_conv_model &m, const float *ctx, const 
         });
 }
 
-hipError_t launch_entropy_objective(const float *E, const double *y, int batch, int n, double *out, hipStream_t stream) {
-    return launch_kernel(entropy_objective_kernel, dim3((batch + OWAVES - 1) / OWAVES), dim3(OTHREADS), 0, stream, E, y, batch, n,
-                         out);
-}
-
 hipError_t launch_bundle_trace(const icnn_be_state &st, double *obj, int *calls, hipStream_t stream) {
     const dim3 grid((st.batch + OWAVES - 1) / OWAVES);
     if (hipError_t e = launch_kernel(trace_zero_kernel, dim3(1), dim3(1), 0, stream, calls); e != hipSuccess) return e;
@@ -314,3 +310,16 @@ hipError_t launch_dual_bound(const icnn_be_state &st, double *out, hipStream_t s
 }
 
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_entropy_objective(const float *E, const double *y, int batch, int n, double *out, void *stream) {
+    if (!E || !y || !out || batch < 0 || n < 1) return ICNN_BE_EINVAL;
+    if (batch == 0) return 0;
+    return api_done(launch_kernel(entropy_objective_kernel, dim3((batch + OWAVES - 1) / OWAVES), dim3(OTHREADS), 0,
+                                  static_cast<hipStream_t>(stream), E, y, batch, n, out));
+}
+
+}  // extern "C"

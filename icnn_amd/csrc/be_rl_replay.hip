@@ -21,6 +21,7 @@
 //
 // The candidate range is clamped to the arrays from the device's own n (2 <= n <= size - 1 gives cand <= size - 3 and
 // cand + 1 <= size - 2), so the gather stays inside the arrays whatever the control block holds.
+#include "be_api_check.h"
 #include "be_kernels.h"
 
 namespace icnn_be {
@@ -277,60 +278,106 @@ __global__ __launch_bounds__(EXP_THREADS) void explore_kernel(ExploreArgs a) {
     if (threadIdx.x == 0 && !a.test) __hip_atomic_store(a.counter, (int)(step + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+unsigned sample_blocks(int batch) { return (unsigned)(((long long)batch + SMP_WAVES - 1) / SMP_WAVES); }
+
+// what icnn_be_replay_enqueue and icnn_be_replay_sample refuse in the memory's descriptor
+int check_replay(const icnn_be_replay *m) {
+    if (!m || m->size < 3 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
+    if (misaligned(m->observations, 4) || misaligned(m->actions, 4) || misaligned(m->rewards, 4) || !m->terminals ||
+        misaligned(m->ctrl, 4))
+        return ICNN_BE_EINVAL;
+    return 0;
+}
+
+// the same for the memory of E lockstep environments; idx = c * E + e is an int
+int check_vec_replay(const icnn_be_vec_replay *m) {
+    if (!m || m->steps < 3 || m->n_envs < 1 || m->dimO < 1 || m->dimA < 1) return ICNN_BE_EINVAL;
+    if ((long long)m->steps * m->n_envs > 0x7fffffffLL) return ICNN_BE_ELIMIT;
+    if (misaligned(m->observations, 4) || misaligned(m->actions, 4) || misaligned(m->rewards, 4) || !m->terminals ||
+        misaligned(m->ctrl, 4))
+        return ICNN_BE_EINVAL;
+    return 0;
+}
+
+// a minibatch drawn from `slots` transitions of which `fill` are written: what both sample entries refuse, then the
+// arguments their kernels share
+template <typename Args>
+int sample_args(Args &a, int slots, int fill, int batch, unsigned long long seed, float *obs, double *act, float *rew,
+                float *ob2, unsigned char *term, int *idx, void *stream) {
+    if (batch < 1 || fill < 2 || fill > slots - 1) return ICNN_BE_EINVAL;
+    if (misaligned(obs, 4) || misaligned(act, 8) || misaligned(rew, 4) || misaligned(ob2, 4) || !term || misaligned(idx, 4) ||
+        !stream_ok(stream))
+        return ICNN_BE_EINVAL;
+    a.batch = batch;
+    a.k0 = (unsigned)(seed & 0xffffffffull);
+    a.k1 = (unsigned)(seed >> 32);
+    a.obs = obs;
+    a.act = act;
+    a.rew = rew;
+    a.ob2 = ob2;
+    a.term = term;
+    a.idx = idx;
+    return 0;
+}
+
 }  // namespace
+}  // namespace icnn_be
 
-long long replay_sample_blocks(int batch) { return ((long long)batch + SMP_WAVES - 1) / SMP_WAVES; }
+using namespace icnn_be;
 
-hipError_t launch_replay_enqueue(const icnn_be_replay &m, const void *stage, hipStream_t stream) {
-    return launch_kernel(replay_enqueue_kernel, dim3(1), dim3(ENQ_THREADS), 0, stream, m,
-                         static_cast<const unsigned char *>(stage));
+extern "C" {
+
+int icnn_be_replay_enqueue(const icnn_be_replay *m, const void *stage, void *stream) {
+    if (int rc = check_replay(m)) return rc;
+    if (misaligned(stage, 8) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(replay_enqueue_kernel, dim3(1), dim3(ENQ_THREADS), 0, static_cast<hipStream_t>(stream), *m,
+                                  static_cast<const unsigned char *>(stage)));
 }
 
-hipError_t launch_replay_sample(const ReplaySampleLaunch &l, hipStream_t stream) {
+int icnn_be_replay_sample(const icnn_be_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
+                          float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
+    if (int rc = check_replay(m)) return rc;
     SampleArgs a{};
-    a.m = l.m;
-    a.batch = l.batch;
-    a.k0 = (unsigned)(l.seed & 0xffffffffull);
-    a.k1 = (unsigned)(l.seed >> 32);
-    a.obs = l.obs;
-    a.act = l.act;
-    a.rew = l.rew;
-    a.ob2 = l.ob2;
-    a.term = l.term;
-    a.idx = l.idx;
-    return launch_kernel(replay_sample_kernel, dim3((unsigned)replay_sample_blocks(l.batch)), dim3(SMP_THREADS), 0, stream, a);
+    if (int rc = sample_args(a, m->size, fill, batch, seed, obs, act, rew, ob2, term, idx, stream)) return rc;
+    a.m = *m;
+    return api_done(launch_kernel(replay_sample_kernel, dim3(sample_blocks(batch)), dim3(SMP_THREADS), 0,
+                                  static_cast<hipStream_t>(stream), a));
 }
 
-hipError_t launch_vec_replay_enqueue(const icnn_be_vec_replay &m, const float *obs, const double *act, const float *rew,
-                                     const unsigned char *term, hipStream_t stream) {
-    return launch_kernel(vec_replay_enqueue_kernel, dim3(1), dim3(VENQ_THREADS), 0, stream, m, obs, act, rew, term);
+int icnn_be_vec_replay_enqueue(const icnn_be_vec_replay *m, const float *obs, const double *act, const float *rew,
+                               const unsigned char *term, void *stream) {
+    if (int rc = check_vec_replay(m)) return rc;
+    if (misaligned(obs, 4) || misaligned(act, 8) || misaligned(rew, 4) || !term || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(vec_replay_enqueue_kernel, dim3(1), dim3(VENQ_THREADS), 0, static_cast<hipStream_t>(stream), *m,
+                                  obs, act, rew, term));
 }
 
-hipError_t launch_vec_replay_sample(const icnn_be_vec_replay &m, const ReplaySampleLaunch &l, hipStream_t stream) {
+int icnn_be_vec_replay_sample(const icnn_be_vec_replay *m, int fill, int batch, unsigned long long seed, float *obs, double *act,
+                              float *rew, float *ob2, unsigned char *term, int *idx, void *stream) {
+    if (int rc = check_vec_replay(m)) return rc;
     VecSampleArgs a{};
-    a.m = m;
-    a.batch = l.batch;
-    a.k0 = (unsigned)(l.seed & 0xffffffffull);
-    a.k1 = (unsigned)(l.seed >> 32);
-    a.obs = l.obs;
-    a.act = l.act;
-    a.rew = l.rew;
-    a.ob2 = l.ob2;
-    a.term = l.term;
-    a.idx = l.idx;
-    return launch_kernel(vec_replay_sample_kernel, dim3((unsigned)replay_sample_blocks(l.batch)), dim3(SMP_THREADS), 0, stream, a);
+    if (int rc = sample_args(a, m->steps, fill, batch, seed, obs, act, rew, ob2, term, idx, stream)) return rc;
+    a.m = *m;
+    return api_done(launch_kernel(vec_replay_sample_kernel, dim3(sample_blocks(batch)), dim3(SMP_THREADS), 0,
+                                  static_cast<hipStream_t>(stream), a));
 }
 
-hipError_t launch_explore(int n_envs, int dimA, const void *raw, bool raw_f32, double *noise, int *counter, double theta,
-                          double sigma, unsigned long long seed, bool test, double *action, hipStream_t stream) {
+int icnn_be_explore(int n_envs, int dimA, const void *raw, int raw_f32, double *noise, int *counter, double theta, double sigma,
+                    unsigned long long seed, int test, double *action, void *stream) {
+    if (n_envs < 1 || dimA < 1 || !raw || !noise || !counter || !action) return ICNN_BE_EINVAL;
+    if ((long long)n_envs * dimA > 0x7fffffffLL) return ICNN_BE_ELIMIT;
+    if (!(theta == theta) || !(sigma == sigma)) return ICNN_BE_EINVAL;
+    if (misaligned(raw, raw_f32 ? 4 : 8) || misaligned(noise, 8) || misaligned(action, 8) || misaligned(counter, 4) ||
+        !stream_ok(stream))
+        return ICNN_BE_EINVAL;
     ExploreArgs a{};
     a.count = n_envs * dimA;
-    a.dimA = dimA; a.raw_f32 = raw_f32; a.test = test;
+    a.dimA = dimA; a.raw_f32 = raw_f32 != 0; a.test = test != 0;
     a.raw = raw; a.noise = noise; a.action = action; a.counter = counter;
     a.theta = theta; a.sigma = sigma;
     a.k0 = (unsigned)(seed & 0xffffffffull);
     a.k1 = (unsigned)(seed >> 32);
-    return launch_kernel(explore_kernel, dim3(1), dim3(EXP_THREADS), 0, stream, a);
+    return api_done(launch_kernel(explore_kernel, dim3(1), dim3(EXP_THREADS), 0, static_cast<hipStream_t>(stream), a));
 }
 
-}  // namespace icnn_be
+}  // extern "C"

@@ -9,6 +9,7 @@
 //                            and the last workgroup to take a ticket does the per-sample part (a few hundred samples) and
 //                            adds the partials in workgroup order -- a fixed order for a given shape, so the loss is
 //                            bitwise repeatable.  tests/test_rl_train.py restates it in NumPy.
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_rl_dev.h"
 
@@ -89,37 +90,54 @@ __global__ __launch_bounds__(TD_THREADS) void rl_td_kernel(TdArgs a) {
     }
 }
 
-}  // namespace
-
 int rl_td_blocks(long long n_theta) {
     const long long per_block = (long long)TD_THREADS * 4;
     const long long b = (n_theta + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : b > ICNN_BE_RL_TD_MAX_BLOCKS ? ICNN_BE_RL_TD_MAX_BLOCKS : b);
 }
 
-hipError_t launch_rl_td(const RlTdLaunch &l, hipStream_t stream) {
+}  // namespace
+}  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_rl_td(int batch, int n, const float *e_critic, const double *act, const float *rew, const unsigned char *term,
+                  const float *q2_src, const double *act2, float discount, const float *theta, long long n_theta,
+                  const unsigned char *decay, float l2norm, float wd, float *td, double *c, float *loss, void *work,
+                  void *stream) {
+    if (batch < 1 || n < 1 || n_theta < 1 || n_theta > 0x7fffffffLL) return ICNN_BE_EINVAL;
+    if (misaligned(e_critic, 4) || misaligned(rew, 4) || misaligned(q2_src, 4) || misaligned(theta, 4) || misaligned(td, 4) ||
+        misaligned(loss, 4) || !term || !decay)
+        return ICNN_BE_EINVAL;
+    if (misaligned(act, 8) || reinterpret_cast<uintptr_t>(act2) % 8 || misaligned(c, 8) || misaligned(work, 16) || !stream_ok(stream))
+        return ICNN_BE_EINVAL;
+    if (!std::isfinite(discount) || !(l2norm >= 0.f) || !(wd >= 0.f) || !std::isfinite(l2norm) || !std::isfinite(wd))
+        return ICNN_BE_EINVAL;
     TdArgs a{};
-    a.batch = l.batch;
-    a.n = l.n;
-    a.e = l.e_critic;
-    a.act = l.act;
-    a.rew = l.rew;
-    a.term = l.term;
-    a.q2 = l.q2_src;
-    a.act2 = l.act2;
-    a.discount = l.discount;
-    a.inv_b = 1.f / (float)l.batch;                                // float32 1 / B, as TF's _MeanGrad divides
-    a.theta = l.theta;
-    a.n_theta = l.n_theta;
-    a.decay = l.decay;
-    a.l2norm = (double)l.l2norm;
-    a.wd = (double)l.wd;
-    a.td = l.td;
-    a.c = l.c;
-    a.loss = l.loss;
-    a.partial = reinterpret_cast<double *>(static_cast<char *>(l.work) + 16);
-    a.ticket = static_cast<int *>(l.work);
-    return launch_kernel(rl_td_kernel, dim3((unsigned)rl_td_blocks(l.n_theta)), dim3(TD_THREADS), 0, stream, a);
+    a.batch = batch;
+    a.n = n;
+    a.e = e_critic;
+    a.act = act;
+    a.rew = rew;
+    a.term = term;
+    a.q2 = q2_src;
+    a.act2 = act2;                                                 // NULL: q2_src already holds negQ_entr
+    a.discount = discount;
+    a.inv_b = 1.f / (float)batch;                                  // float32 1 / B, as TF's _MeanGrad divides
+    a.theta = theta;
+    a.n_theta = n_theta;
+    a.decay = decay;
+    a.l2norm = (double)l2norm;
+    a.wd = (double)wd;
+    a.td = td;
+    a.c = c;
+    a.loss = loss;
+    a.partial = reinterpret_cast<double *>(static_cast<char *>(work) + 16);
+    a.ticket = static_cast<int *>(work);
+    return api_done(launch_kernel(rl_td_kernel, dim3((unsigned)rl_td_blocks(n_theta)), dim3(TD_THREADS), 0,
+                                  static_cast<hipStream_t>(stream), a));
 }
 
-}  // namespace icnn_be
+}  // extern "C"

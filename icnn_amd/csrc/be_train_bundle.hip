@@ -16,6 +16,7 @@
 
 #include <climits>
 
+#include "be_api_check.h"
 #include "be_kernels.h"
 
 namespace icnn_be {
@@ -138,9 +139,6 @@ __global__ void step_gate_kernel(const int *counts, int mask, int *gate) {
 
 }  // namespace
 
-// the per-sample loss parts (8-byte aligned) and the ticket
-size_t feed_plan_work_bytes(int batch) { return sizeof(double) * (size_t)(batch > 0 ? batch : 1) + 16; }
-
 hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream) {
     PlanArgs a{};
     a.l = l;
@@ -150,16 +148,28 @@ hipError_t launch_feed_plan(const FeedPlanLaunch &l, hipStream_t stream) {
     return launch_kernel(feed_plan_kernel, dim3(l.st.batch), dim3(PT), 0, stream, a);
 }
 
-hipError_t launch_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c,
-                           int *fd_sample, hipStream_t stream) {
+}  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+// the per-sample loss parts (8-byte aligned) and the ticket
+size_t icnn_be_feed_plan_work_bytes(int batch) { return batch < 0 ? 0 : sizeof(double) * (size_t)(batch > 0 ? batch : 1) + 16; }
+
+int icnn_be_feed_pad(const int *rows, int batch, int n, int row_cap, double *fd_y, double *fd_v, double *fd_c, int *fd_sample,
+                     void *stream) {
+    if (!rows || !fd_y || !fd_v || !fd_c || !fd_sample || batch < 1 || n < 1 || row_cap < 0) return ICNN_BE_EINVAL;
+    if (row_cap == 0) return 0;
     const size_t most = (size_t)row_cap * n;
     const int blocks = (int)((most + 255) / 256 < 2048 ? (most + 255) / 256 : 2048);
-    return launch_kernel(feed_pad_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, rows, batch, n, row_cap, fd_y,
-                         fd_v, fd_c, fd_sample);
+    return api_done(launch_kernel(feed_pad_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                  rows, batch, n, row_cap, fd_y, fd_v, fd_c, fd_sample));
 }
 
-hipError_t launch_step_gate(const int *counts, int mask, int *gate, hipStream_t stream) {
-    return launch_kernel(step_gate_kernel, dim3(1), dim3(64), 0, stream, counts, mask, gate);
+int icnn_be_step_gate(const int *counts, int mask, int *gate, void *stream) {
+    if (!counts || !gate) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(step_gate_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), counts, mask, gate));
 }
 
-}  // namespace icnn_be
+}  // extern "C"

@@ -14,6 +14,7 @@
 //
 // The index is umulhi(word, N) < N for every 32-bit word and a workgroup exists only for k < batch, so the gather stays inside
 // the arrays whatever the control block holds.
+#include "be_api_check.h"
 #include "be_kernels.h"
 
 namespace icnn_be {
@@ -102,19 +103,37 @@ __global__ __launch_bounds__(LOG_THREADS) void log_row_kernel(icnn_be_step_log L
 }
 
 }  // namespace
-
-hipError_t launch_dataset_draw(const DatasetDrawLaunch &l, hipStream_t stream) {
-    DrawArgs a{};
-    a.d = l.d;
-    a.k0 = (unsigned)(l.seed & 0xffffffffull);
-    a.k1 = (unsigned)(l.seed >> 32);
-    for (int i = 0; i < l.d.n_arrays; ++i) a.dst[i] = l.dst[i];
-    a.idx = l.idx;
-    return launch_kernel(dataset_draw_kernel, dim3((unsigned)l.batch), dim3(DRAW_THREADS), 0, stream, a);
-}
-
-hipError_t launch_log_row(const icnn_be_step_log &L, hipStream_t stream) {
-    return launch_kernel(log_row_kernel, dim3(1), dim3(LOG_THREADS), 0, stream, L);
-}
-
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_dataset_draw(const icnn_be_dataset *d, int batch, unsigned long long seed, void *const dst[], int *idx,
+                         void *stream) {
+    if (!d || !d->ctrl || !idx || !dst) return ICNN_BE_EINVAL;
+    if (d->n_rows < 1 || batch < 1 || d->n_arrays < 1 || d->n_arrays > ICNN_BE_DATASET_MAX_ARRAYS) return ICNN_BE_EINVAL;
+    for (int a = 0; a < d->n_arrays; ++a)
+        if (misaligned(d->src[a], 16) || misaligned(dst[a], 16) || d->row_words[a] < 1) return ICNN_BE_EINVAL;
+    if (misaligned(idx, 16) || misaligned(d->ctrl, 4) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    DrawArgs a{};
+    a.d = *d;
+    a.k0 = (unsigned)(seed & 0xffffffffull);
+    a.k1 = (unsigned)(seed >> 32);
+    for (int i = 0; i < d->n_arrays; ++i) a.dst[i] = dst[i];
+    a.idx = idx;
+    return api_done(launch_kernel(dataset_draw_kernel, dim3((unsigned)batch), dim3(DRAW_THREADS), 0,
+                                  static_cast<hipStream_t>(stream), a));
+}
+
+int icnn_be_log_row(const icnn_be_step_log *L, void *stream) {
+    if (!L || !L->rows || !L->ctrl || L->cap < 1 || L->width < 1 || L->width > ICNN_BE_LOG_MAX_COLUMNS) return ICNN_BE_EINVAL;
+    for (int j = 0; j < L->width; ++j) {
+        if (L->kind[j] < ICNN_BE_LOG_F32 || L->kind[j] > ICNN_BE_LOG_I32) return ICNN_BE_EINVAL;
+        if (misaligned(L->col[j], L->kind[j] == ICNN_BE_LOG_F64 ? 8 : 4)) return ICNN_BE_EINVAL;
+    }
+    if (misaligned(L->rows, 8) || misaligned(L->ctrl, 4) || !stream_ok(stream)) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(log_row_kernel, dim3(1), dim3(LOG_THREADS), 0, static_cast<hipStream_t>(stream), *L));
+}
+
+}  // extern "C"

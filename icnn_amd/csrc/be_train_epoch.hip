@@ -12,6 +12,7 @@
 //                     *best = score when it goes.  go is the word icnn_be_gated_copy takes, which makes the snapshot.
 #include <hip/hip_runtime.h>
 
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_train_gd_dev.h"
 
@@ -20,6 +21,16 @@ namespace icnn_be {
 namespace {
 
 constexpr int GT = GD_FEED_THREADS;
+
+// the loss-only form of the feed of be_train_gd.hip: loss [1] and, unless NULL, tallies [B][3]; nothing else is written
+struct GdEvalLaunch {
+    const double *yK;             // [B][n] y_K (float32 values)
+    const float *t;               // [B][n] targets
+    int B, n;
+    float *loss;
+    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
+    void *work;                   // gd_feed_work_bytes(B)
+};
 
 struct GdEvalArgs {
     GdEvalLaunch l;
@@ -68,21 +79,34 @@ __global__ void keep_best_kernel(const void *score, int score_is_f64, int mode, 
 }
 
 }  // namespace
-
-hipError_t launch_gd_eval(const GdEvalLaunch &l, hipStream_t stream) {
-    GdEvalArgs a{};
-    a.l = l;
-    a.partial = gd_feed_partial(l.work);
-    a.ticket = gd_feed_ticket(l.work, l.B);
-    return launch_kernel(gd_eval_kernel, dim3(l.B), dim3(GT), 0, stream, a);
-}
-
-hipError_t launch_macro_f1(const int *tallies, int B, double *f1, hipStream_t stream) {
-    return launch_kernel(macro_f1_kernel, dim3(1), dim3(F1T), 0, stream, tallies, B, f1);
-}
-
-hipError_t launch_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, hipStream_t stream) {
-    return launch_kernel(keep_best_kernel, dim3(1), dim3(64), 0, stream, score, score_is_f64, mode, best, gate);
-}
-
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+size_t icnn_be_gd_eval_work_bytes(int B) { return B < 1 ? 0 : gd_feed_work_bytes(B); }
+
+int icnn_be_gd_eval(const double *yK, const float *t, int B, int n, float *loss, int *f1_tallies, void *work, void *stream) {
+    if (B < 1 || n < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
+    GdEvalArgs a{};
+    a.l = GdEvalLaunch{yK, t, B, n, loss, f1_tallies, work};
+    a.partial = gd_feed_partial(work);
+    a.ticket = gd_feed_ticket(work, B);
+    return api_done(launch_kernel(gd_eval_kernel, dim3(B), dim3(GT), 0, static_cast<hipStream_t>(stream), a));
+}
+
+int icnn_be_macro_f1(const int *tallies, int B, double *f1, void *stream) {
+    if (B < 1 || !tallies || !f1) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(macro_f1_kernel, dim3(1), dim3(F1T), 0, static_cast<hipStream_t>(stream), tallies, B, f1));
+}
+
+int icnn_be_keep_best(const void *score, int score_is_f64, int mode, double *best, int *gate, void *stream) {
+    if (!score || !best || !gate) return ICNN_BE_EINVAL;
+    if (mode != ICNN_BE_KEEP_MIN && mode != ICNN_BE_KEEP_MAX) return ICNN_BE_EINVAL;
+    return api_done(launch_kernel(keep_best_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), score,
+                                  (int)(score_is_f64 != 0), mode, best, gate));
+}
+
+}  // extern "C"

@@ -14,6 +14,9 @@
 //                    is B x 1 and only the loss is formed.
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_train_gd_dev.h"
 
@@ -22,6 +25,20 @@ namespace icnn_be {
 namespace {
 
 constexpr int GT = GD_FEED_THREADS;
+
+// the arguments of icnn_be_gd_feed
+struct GdFeedLaunch {
+    const double *yK;             // [B][n] y_K (float32 values)
+    const float *t;               // [B][n] targets
+    const double *coef;           // [K] step coefficients
+    int B, n, K;
+    float scale;                  // float32(1) / float32(B n)
+    double *v_rows, *c_rows;      // [B K][n], [B K]
+    int *row_offset;              // [B + 1]
+    float *loss;
+    int *tallies;                 // [B][3] tp / fp / fn (may be NULL)
+    void *work;                   // gd_feed_work_bytes(B)
+};
 
 struct GdFeedArgs {
     GdFeedLaunch l;
@@ -62,6 +79,25 @@ __global__ __launch_bounds__(GT) void gd_feed_kernel(GdFeedArgs a) {
     // ---- the loss, formed by the last workgroup to take a ticket ----
     gd_loss_behind_ticket(a.partial, a.ticket, j, s, B, n, l.loss, red, &s_last);
 }
+
+// the same feed for the loss mean((px (y_K - t))^2), on a grid of B x S workgroups; v_rows, c_rows, row_offset (and coef)
+// NULL together: the loss alone
+struct GdFeedPxLaunch {
+    const double *yK;
+    const float *t;
+    const double *coef;
+    int B, n, K;
+    float scale, px;
+    double *v_rows, *c_rows;
+    int *row_offset;
+    float *loss;
+    void *work;                   // gd_feed_work_bytes(B)
+};
+#ifndef ICNN_BE_GD_FEED_PX_CHUNK
+#define ICNN_BE_GD_FEED_PX_CHUNK 8192         // an experiment builds another value (tools/conv_gd_step_time.py --alt-lib)
+#endif
+constexpr int GD_FEED_PX_CHUNK = ICNN_BE_GD_FEED_PX_CHUNK;   // elements of a sample's [K][n] block per workgroup, at most
+constexpr int GD_FEED_PX_MAX_CHUNKS = 65535; // gridDim.y
 
 struct GdFeedPxArgs {
     GdFeedPxLaunch l;
@@ -115,33 +151,50 @@ __global__ __launch_bounds__(GT) void gd_feed_px_kernel(GdFeedPxArgs a) {
     gd_loss_behind_ticket(a.partial, a.ticket, j, s, B, n, l.loss, red, &s_last);
 }
 
-}  // namespace
-
-// the per-sample sums (8-byte aligned) and the ticket
-size_t gd_feed_work_bytes(int batch) { return sizeof(double) * (size_t)(batch > 0 ? batch : 1) + 16; }
-
-hipError_t launch_gd_feed(const GdFeedLaunch &l, hipStream_t stream) {
-    GdFeedArgs a{};
-    a.l = l;
-    a.partial = gd_feed_partial(l.work);
-    a.ticket = gd_feed_ticket(l.work, l.B);
-    return launch_kernel(gd_feed_kernel, dim3(l.B), dim3(GT), 0, stream, a);
-}
-
 // S of the 2-D grid: ceil(K n / GD_FEED_PX_CHUNK) workgroups per sample (DESIGN.md §17 has the measurement behind the chunk)
 long long gd_feed_px_chunks(int n, int K) {
     return ((long long)K * n + GD_FEED_PX_CHUNK - 1) / GD_FEED_PX_CHUNK;
 }
 
-hipError_t launch_gd_feed_px(const GdFeedPxLaunch &l, hipStream_t stream) {
-    GdFeedPxArgs a{};
-    a.l = l;
-    a.partial = gd_feed_partial(l.work);
-    a.ticket = gd_feed_ticket(l.work, l.B);
-    const long long total = (long long)l.K * l.n;
-    const long long S = l.v_rows ? gd_feed_px_chunks(l.n, l.K) : 1;
-    a.chunk = (unsigned)((total + S - 1) / S);
-    return launch_kernel(gd_feed_px_kernel, dim3(l.B, (unsigned)S), dim3(GT), 0, stream, a);
+}  // namespace
+}  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+size_t icnn_be_gd_feed_work_bytes(int B) { return B < 0 ? 0 : gd_feed_work_bytes(B); }
+
+int icnn_be_gd_feed(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, double *v_rows,
+                    double *c_rows, int *row_offset, float *loss, int *f1_tallies, void *work, void *stream) {
+    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !coef || !v_rows || !c_rows || !row_offset || !loss || !work) return ICNN_BE_EINVAL;
+    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
+    GdFeedArgs a{};
+    a.l = GdFeedLaunch{yK, t, coef, B, n, K, scale, v_rows, c_rows, row_offset, loss, f1_tallies, work};
+    a.partial = gd_feed_partial(work);
+    a.ticket = gd_feed_ticket(work, B);
+    return api_done(launch_kernel(gd_feed_kernel, dim3(B), dim3(GT), 0, static_cast<hipStream_t>(stream), a));
 }
 
-}  // namespace icnn_be
+size_t icnn_be_gd_feed_px_work_bytes(int B, int n, int K) { return (B < 1 || n < 1 || K < 1) ? 0 : gd_feed_work_bytes(B); }
+
+int icnn_be_gd_feed_px(const double *yK, const float *t, const double *coef, int B, int n, int K, float scale, float px,
+                       double *v_rows, double *c_rows, int *row_offset, float *loss, void *work, void *stream) {
+    if (B < 1 || n < 1 || K < 1) return ICNN_BE_EINVAL;
+    if (!yK || !t || !loss || !work) return ICNN_BE_EINVAL;
+    const int rows = (v_rows != nullptr) + (c_rows != nullptr) + (row_offset != nullptr);
+    if (rows != 0 && rows != 3) return ICNN_BE_EINVAL;
+    if (rows == 3 && !coef) return ICNN_BE_EINVAL;
+    if ((long long)B * K > INT_MAX) return ICNN_BE_ELIMIT;
+    const long long total = (long long)K * n, S = rows == 3 ? gd_feed_px_chunks(n, K) : 1;
+    if (S > GD_FEED_PX_MAX_CHUNKS) return ICNN_BE_ELIMIT;
+    GdFeedPxArgs a{};
+    a.l = GdFeedPxLaunch{yK, t, coef, B, n, K, scale, px, v_rows, c_rows, row_offset, loss, work};
+    a.partial = gd_feed_partial(work);
+    a.ticket = gd_feed_ticket(work, B);
+    a.chunk = (unsigned)((total + S - 1) / S);
+    return api_done(launch_kernel(gd_feed_px_kernel, dim3(B, (unsigned)S), dim3(GT), 0, static_cast<hipStream_t>(stream), a));
+}
+
+}  // extern "C"

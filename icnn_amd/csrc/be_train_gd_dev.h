@@ -11,7 +11,8 @@ namespace icnn_be {
 
 constexpr int GD_FEED_THREADS = 256;
 
-// where a feed's work area (gd_feed_work_bytes(B), zeroed once) keeps the per-sample sums and the ticket
+// a feed's work area (zeroed once): the per-sample sums (8-byte aligned) and the ticket, and where it keeps them
+inline size_t gd_feed_work_bytes(int B) { return sizeof(double) * (size_t)(B > 0 ? B : 1) + 16; }
 __host__ __device__ inline double *gd_feed_partial(void *work) { return static_cast<double *>(work); }
 __host__ __device__ inline int *gd_feed_ticket(void *work, int B) {
     return reinterpret_cast<int *>(static_cast<double *>(work) + (B > 0 ? B : 1));

@@ -17,6 +17,7 @@
 //   target = target - tau * (target - theta)                 update_target
 //   g = g + k * theta on the decayed elements                k = l2norm * wd in float32 (TF's AddN of the two gradients)
 // and every new target value is scattered into the target's arena beside the critic's.
+#include "be_api_check.h"
 #include "be_kernels.h"
 #include "be_tf_adam.h"
 
@@ -164,27 +165,64 @@ hipError_t launch_update(UpdArgs u, hipStream_t stream) {
                          stream, u);
 }
 
-}  // namespace
+// what icnn_be_param_update, its gated form and icnn_be_rl_critic_update refuse before any launch
+int check_param_update(const icnn_be_param_update_args *a) {
+    if (!a || a->n < 1 || !a->dest || !a->arena || !a->step) return ICNN_BE_EINVAL;
+    if (misaligned(a->theta, 16) || misaligned(a->m, 16) || misaligned(a->v, 16) || misaligned(a->grad, 16) ||
+        misaligned(a->dest_off, 16))
+        return ICNN_BE_EINVAL;
+    if (a->arena_floats < 0 || a->arena_floats > 0x7fffffffLL || param_update_blocks(a->n) > 0x7fffffffLL) return ICNN_BE_EINVAL;
+    if (!adam_constants_ok(a->beta1, a->beta2, a->eps) || !(a->lr == a->lr)) return ICNN_BE_EINVAL;
+    if (a->n_proj < 0 || a->n_proj > ICNN_BE_MAX_PROJ_RANGES) return ICNN_BE_EINVAL;
+    for (int r = 0; r < a->n_proj; ++r)
+        if (a->proj_begin[r] < 0 || a->proj_begin[r] > a->proj_end[r] || a->proj_end[r] > a->n) return ICNN_BE_EINVAL;
+    return 0;
+}
 
 // go NULL: the plain update
-hipError_t launch_param_update(const icnn_be_param_update_args &a, const int *go, hipStream_t stream) {
+int param_update(const icnn_be_param_update_args *a, const int *go, void *stream) {
+    if (int rc = check_param_update(a)) return rc;
     UpdArgs u{};
-    u.r.adam = a;
+    u.r.adam = *a;
     u.go = go;
-    return go ? launch_update<true, false>(u, stream) : launch_update<false, false>(u, stream);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    return api_done(go ? launch_update<true, false>(u, s) : launch_update<false, false>(u, s));
 }
 
-hipError_t launch_rl_critic_update(const icnn_be_rl_update_args &r, hipStream_t stream) {
-    UpdArgs u{};
-    u.r = r;
-    u.k = r.l2norm * r.wd;                                          // float32 product of the two float32 constants
-    return launch_update<false, true>(u, stream);
-}
-
-hipError_t launch_gated_copy(float *dst, const float *src, long long n, const int *go, int want, hipStream_t stream) {
-    const long long blocks = (n + COPY_THREADS - 1) / COPY_THREADS;
-    return launch_kernel(gated_copy_kernel, dim3((unsigned)(blocks < COPY_MAX_BLOCKS ? blocks : COPY_MAX_BLOCKS)),
-                         dim3(COPY_THREADS), 0, stream, dst, src, n, go, want);
-}
-
+}  // namespace
 }  // namespace icnn_be
+
+using namespace icnn_be;
+
+extern "C" {
+
+int icnn_be_param_update(const icnn_be_param_update_args *a, void *stream) { return param_update(a, nullptr, stream); }
+
+int icnn_be_param_update_gated(const icnn_be_param_update_args *a, const int *go, void *stream) {
+    if (!go) return ICNN_BE_EINVAL;
+    return param_update(a, go, stream);
+}
+
+int icnn_be_gated_copy(float *dst, const float *src, long long n, const int *go, int want, void *stream) {
+    if (!dst || !src || !go || n < 0) return ICNN_BE_EINVAL;
+    if (n == 0) return 0;
+    const long long blocks = (n + COPY_THREADS - 1) / COPY_THREADS;
+    return api_done(launch_kernel(gated_copy_kernel, dim3((unsigned)(blocks < COPY_MAX_BLOCKS ? blocks : COPY_MAX_BLOCKS)),
+                                  dim3(COPY_THREADS), 0, static_cast<hipStream_t>(stream), dst, src, n, go, want));
+}
+
+int icnn_be_rl_critic_update(const icnn_be_rl_update_args *a, void *stream) {
+    if (!a) return ICNN_BE_EINVAL;
+    if (int rc = check_param_update(&a->adam)) return rc;
+    if (misaligned(a->target_theta, 16) || misaligned(a->decay, 4) || misaligned(a->target_arena, 4) || !stream_ok(stream))
+        return ICNN_BE_EINVAL;
+    if (!(a->tau >= 0.f && a->tau <= 1.f) || !(a->l2norm >= 0.f) || !(a->wd >= 0.f) || !std::isfinite(a->l2norm) ||
+        !std::isfinite(a->wd))
+        return ICNN_BE_EINVAL;
+    UpdArgs u{};
+    u.r = *a;
+    u.k = a->l2norm * a->wd;                                        // float32 product of the two float32 constants
+    return api_done(launch_update<false, true>(u, static_cast<hipStream_t>(stream)));
+}
+
+}  // extern "C"
