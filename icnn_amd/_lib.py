@@ -35,6 +35,9 @@ FLAG_F64_ENERGY = 32
 FLAG_GLOBAL_BUNDLE = 64
 FLAG_WAVE_PER_SAMPLE = 128
 FLAG_MFMA_CONTRACTION = 256
+FLAG_GENERIC_SHAPE = 512
+# ICNN_BE_SHAPE_*: which instance of the persistent tile kernel a solve launches (icnn_be_debug_shape_instance)
+SHAPE_INSTANCES = ["generic", "bibtex_kt16", "bibtex_kt32_grouped"]
 LOSS = {"xent": 0, "mse": 1}
 # ICNN_BE_PATH_*: how icnn_be_solve_fc runs a solve (icnn_be_debug_solve_plan)
 PATHS = ["ROWS", "TILE", "TILE_BUDGETED_THEN_ROWS", "ROUNDS_LOCKSTEP", "ROUNDS_SLICED_THEN_ROWS", "ROUNDS_SLICED_EXTRA"]
@@ -56,6 +59,7 @@ EXPORTS = [
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan", "icnn_be_debug_dual_plan",
+    "icnn_be_debug_shape_instance",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
@@ -396,6 +400,8 @@ def load():
     lib.icnn_be_debug_adam_plan.restype = C.c_int
     lib.icnn_be_debug_dual_plan.argtypes = [C.POINTER(State), C.c_int, C.POINTER(C.c_int * 8)]
     lib.icnn_be_debug_dual_plan.restype = C.c_int
+    lib.icnn_be_debug_shape_instance.argtypes = [C.POINTER(FcModel), C.POINTER(State)]
+    lib.icnn_be_debug_shape_instance.restype = C.c_int
     lib.icnn_be_adam_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_adam_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
@@ -679,6 +685,15 @@ def solve_plan(model, state, cus=0):
     if rc < 0:
         check(rc, "icnn_be_debug_solve_plan")
     return (PATHS[rc],) + tuple(out)
+
+
+def shape_instance(model, state):
+    """Name (SHAPE_INSTANCES) of the persistent tile kernel's instance icnn_be_solve_fc launches for an FcModel and a State:
+    'generic', or the instance compiled for that network's shape (icnn_be_debug_shape_instance).  Host arithmetic."""
+    rc = load().icnn_be_debug_shape_instance(C.byref(model), C.byref(state))
+    if rc < 0:
+        check(rc, "icnn_be_debug_shape_instance")
+    return SHAPE_INSTANCES[rc]
 
 
 def adam_plan(model, batch, ctx=None):

@@ -403,6 +403,19 @@ int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state 
     return p.path;
 }
 
+int icnn_be_debug_shape_instance(const icnn_be_fc_model *model, const icnn_be_state *st) {
+    /* float64 cuts: icnn_be_solve_fc launches nothing for them, so no instance either; everything else it refuses is refused here */
+    if (model && st && st->cut_dtype == ICNN_BE_CUT_F64 && check_shape(st) == 0 && st->n == model->n && st->batch > 0 &&
+        icnn_be::fc_check_model(*model) == 0)
+        return ICNN_BE_SHAPE_GENERIC;
+    if (int rc = check_fc_solve(model, st)) return rc;
+    if (st->batch == 0) return ICNN_BE_EINVAL;
+    const SolvePlan p = plan_fc_solve(*model, *st, icnn_be::device_cus(), env_tile_budget());
+    if (p.path < 0) return p.path;
+    if (p.path != ICNN_BE_PATH_TILE) return ICNN_BE_SHAPE_GENERIC;
+    return icnn_be::fused_shape_instance(*model, *st, p.per_wg, p.budget);
+}
+
 size_t icnn_be_fc_context_work_floats(const icnn_be_fc_ctx *c, int batch) {
     if (!c || batch < 0 || icnn_be::ctx_check(*c) != 0) return 0;
     return icnn_be::ctx_work_floats(*c, batch);

@@ -104,7 +104,7 @@ struct PairwisePlan {
     signed char prog[PW_MAX_PROG];   // postfix: >= 0 push leaf, -1 add the two on top
 };
 
-inline void pw_build_rec(PairwisePlan &p, int start, int n, int level) {
+constexpr void pw_build_rec(PairwisePlan &p, int start, int n, int level) {
     if (n <= 128) {
         p.leaf_start[p.n_leaves] = (short)start;
         p.leaf_len[p.n_leaves] = (short)n;
@@ -120,7 +120,7 @@ inline void pw_build_rec(PairwisePlan &p, int start, int n, int level) {
     pw_build_rec(p, start + n2, n - n2, level + 1);
     p.prog[p.n_prog++] = -1;
 }
-inline bool pw_build(PairwisePlan &p, int n) {
+constexpr bool pw_build(PairwisePlan &p, int n) {
     p.n_leaves = 0;
     p.n_prog = 0;
     p.depth = -1;

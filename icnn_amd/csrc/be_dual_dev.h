@@ -1071,7 +1071,10 @@ __device__ __forceinline__ void for_columns(const CutT *As, int ldA, int k, int 
 // SLICED = false: the caller never parks a sample (no update budget, state fresh from icnn_be_state_init: the persistent
 // tile kernel in its default form) -- the park / resume paths and their live values are compiled out (headline solve 1.024 ->
 // 1.016 ms on one box; cf. ICNN_BE_PROF, be_common.h).
-template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false, int LR = 0, bool SLICED = true, typename ArgsT>
+// Shape (be_kernels.h): n, n_pad, ldA and the pairwise plan from the arguments (DynShape), or as constants (FixedDual: the
+// fixed instances of the persistent tile kernel).
+template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false, int LR = 0, bool SLICED = true,
+          typename Shape = DynShape, typename ArgsT>
 __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, unsigned char *smem, int round,
                                                int rows_cap, const CutT *crow_shared) {
     constexpr int NT = 64 * NW;
@@ -1106,13 +1109,14 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     if (t >= TI) return;
     const bool resume = SLICED && __builtin_amdgcn_readfirstlane(phase_u) != 0;
 
-    const int n = st.n, n_pad = a.n_pad, ldA = a.ldA;
+    const int n = Shape::n(a), n_pad = Shape::n_pad(a), ldA = Shape::ldA(a);
+    const auto &plan = Shape::plan(a);
     const int HP = (rows_cap + 1) | 1;     // odd pitch of the (k x k+1) matrix H | A z in LDS
     // RL (variant of RL/src/bundle_entropy.py) is a template parameter: its Armijo line search, softplus
     // sums and pivot regularisation are compiled out of the dual-variant kernels.
     // a bundle cannot hold more cuts than outer iterations have been started: rows <= round + 1
     static_assert(!IPM || !RL, "interior point is a variant of its own");
-    const Carve cv = carve(KT, rows_cap, ldA, n_pad, (int)sizeof(CutT), a.plan.n_leaves, RL, NW, crow_shared == nullptr, IPM, GLB);
+    const Carve cv = carve(KT, rows_cap, ldA, n_pad, (int)sizeof(CutT), plan.n_leaves, RL, NW, crow_shared == nullptr, IPM, GLB);
     // this wave's share of the columns (multiple of 16)
     const int cchunk = NW == 1 ? n_pad : (((n_pad / 16 + NW - 1) / NW) * 16);
     const int cbeg = wave * cchunk < n_pad ? wave * cchunk : n_pad;
@@ -1129,7 +1133,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     double *Hp = reinterpret_cast<double *>(smem + cv.Hp) + (NW == 1 ? 0 : wave * rows_cap * HP);   // my partial
     double *Hp0 = reinterpret_cast<double *>(smem + cv.Hp);
     double *leaf = Hm;                                        // pairwise-sum scratch aliases Hm
-    double *psum = Hm + KT * a.plan.n_leaves;                 // [2*KT] results of pairwise sums
+    double *psum = Hm + KT * plan.n_leaves;                 // [2*KT] results of pairwise sums
     int *slots = reinterpret_cast<int *>(smem + cv.ints);
 
     const CutT *g_row = static_cast<const CutT *>(a.g) + (size_t)u * n;
@@ -1296,7 +1300,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
         }
         sample_sync<NW>();
         lap(13);
-        np_pairwise_rows<NW, double>(a.plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
+        np_pairwise_rows<NW, double>(plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
         h_new = f_u - psum[0];                        // fi - np.sum(gi * x)
         if (tid == 0) {
             h_u[slot_new] = h_new;
@@ -1468,7 +1472,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     } else {
         // c = np.sum(A, axis=1) + b with the row sum in the cut dtype (dual :18)
         CutT *rowsum = reinterpret_cast<CutT *>(psum);
-        np_pairwise_rows<NW, CutT>(a.plan, k, [&](int r, int j) { return As[r * ldA + j]; },
+        np_pairwise_rows<NW, CutT>(plan, k, [&](int r, int j) { return As[r * ldA + j]; },
                                    reinterpret_cast<CutT *>(leaf), rowsum, tid);
         const double c_i = lane < k ? (double)rowsum[lane] + h_i : 0.0;
         sample_sync<NW>();
@@ -1567,7 +1571,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
                 for (int i = 0; i < k; ++i) dmax = fmax(dmax, fabs(bcast(step, i)));
                 tt = fmin(1.0 / dmax, 1.0);                                      // rl :64
                 sample_sync<NW>();
-                np_pairwise_rows<NW, double>(a.plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
+                np_pairwise_rows<NW, double>(plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
                 double cl = 0.0;
                 for (int i = 0; i < k; ++i) { cl += bcast(c_i * lam, i); slope += bcast(step * g0, i); }
                 fval = -cl + psum[0];                                            // :34
@@ -1590,7 +1594,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
                             sp[j] = j < n ? softplus_fast(aj) : 0.0;
                         }
                         sample_sync<NW>();
-                        np_pairwise_rows<NW, double>(a.plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
+                        np_pairwise_rows<NW, double>(plan, 1, [&](int, int j) { return sp[j]; }, leaf, psum, tid);
                         double cl = 0.0;
                         for (int i = 0; i < k; ++i) cl += bcast(c_i * lam_new, i);
                         const double f_new = -cl + psum[0];

@@ -76,14 +76,20 @@ __device__ __forceinline__ void reset_sample(const icnn_be_state &st, const Solv
 // RL: the variant of RL/src/bundle_entropy.py (clipped y, Armijo search, early stop); IPM: the interior-point variant of
 // lib/bundle_entropy.py (round 4: the module the reference's scripts import runs through the persistent kernels as well)
 // SLICED: the budgeted form (ICNN_BE_FLAG_PERSISTENT | ICNN_BE_FLAG_TIME_SLICE, variant dual): samples may be parked
-template <bool RL, int KT, bool IPM = false, bool SLICED = false>
+// Shape (be_kernels.h): DynShape, or a FixedShape instance the launcher takes when -- and only when -- model and state match it
+// (pick_shape_instance below): n, the widths and everything that follows from them are constants of the instance.
+// GROUPED: -1 = args.grouped decides at run time; 0 / 1 = the launcher's layout decision is the instance's, and the dual body of
+// the other form is not compiled in.
+template <bool RL, int KT, bool IPM = false, bool SLICED = false, typename Shape = DynShape, int GROUPED = -1>
 __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     KArgs *kp0 = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     {
+        const int ldA = Shape::ldA(args.da);
         float *crow = reinterpret_cast<float *>(smem + args.crow_off);  // behind phase A's buffers: written once
-        for (int j = thread_id(); j < 2 * args.da.ldA; j += NTHREADS) crow[j] = j < args.da.ldA ? 0.f : 1.f;
-        if (args.grouped && thread_id() < TM) reinterpret_cast<int *>(smem + args.need_off)[TM + thread_id()] = 0;   // done flags
+        for (int j = thread_id(); j < 2 * ldA; j += NTHREADS) crow[j] = j < ldA ? 0.f : 1.f;
+        if ((GROUPED < 0 ? args.grouped != 0 : GROUPED != 0) && thread_id() < TM)
+            reinterpret_cast<int *>(smem + args.need_off)[TM + thread_id()] = 0;   // done flags
     }
     if (args.reset.on) {                                            // wave w owns sample w of the tile
         const int wave = uni(thread_id() >> 6), u = blockIdx.x * args.fa.tile_rows + wave;
@@ -95,17 +101,17 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
         KArgs *kp = kp0;
         int tile = blockIdx.x;
         asm volatile("" : "+s"(kp), "+s"(tile));                    // nothing derived from the arguments is carried
-        fc_fg_tile(kp->fa, tile, reinterpret_cast<float *>(smem));  // phase A: f, g of the tile -> global work arrays
+        fc_fg_tile<Shape>(kp->fa, tile, reinterpret_cast<float *>(smem));  // phase A: f, g of the tile -> global work arrays
         __syncthreads();                                            // ... visible to the tile's dual waves
         int wave = uni(thread_id() >> 6), round = r;
         asm volatile("" : "+s"(kp), "+s"(tile), "+s"(wave), "+s"(round));
         KArgs &k = *kp;
         const int u = tile * k.fa.tile_rows + wave;
         const bool mine = wave < k.fa.tile_rows && u < k.da.st.batch;
-        if (!k.grouped) {
+        if (GROUPED < 0 ? !k.grouped : GROUPED == 0) {
             if (mine) {                                             // phase B: wave w = sample w of the tile
                 const int rows_cap = round + 1 < k.da.st.slots ? round + 1 : k.da.st.slots;
-                dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED>(k.da, u, thread_id() & 63,
+                dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63,
                                                                         smem + k.samples_off + wave * k.sample_bytes, round, rows_cap,
                                                                         reinterpret_cast<const float *>(smem + k.crow_off));
             }
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
         // as the launch pairs and the per-sample kernel do, instead of writing a 32nd row behind the sample's arrays
         if (kk > k.da.st.slots) kk = k.da.st.slots;
         if ((thread_id() & 63) == 0)
-            need[wave] = kk > 0 ? (carve(KT, kk, k.da.ldA, k.da.n_pad, 4, k.da.plan.n_leaves, RL, 1, false, IPM).total + 15) & ~15 : 0;
+            need[wave] = kk > 0 ? (carve(KT, kk, Shape::ldA(k.da), Shape::n_pad(k.da), 4, Shape::plan(k.da).n_leaves, RL, 1, false, IPM).total + 15) & ~15 : 0;
         __syncthreads();
         // (Round 6, tried and withdrawn: dealing the regions longest-first by the Newton updates of the sample's previous dual
         //  step.  The sample that ends a round is not predictable from its last round -- rank 10 of 16 on average,
@@ -175,7 +181,7 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
             }
             wait_lap(14);
             if (ICNN_BE_PROF_ON(k.trace) && tr) tr[1] = (long long)__builtin_readcyclecounter();
-            dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED>(k.da, u, thread_id() & 63, smem + k.samples_off + my_off, round, kk,
+            dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63, smem + k.samples_off + my_off, round, kk,
                                                                     reinterpret_cast<const float *>(smem + k.crow_off));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // its LDS traffic is complete before the flag is seen
             if ((thread_id() & 63) == 0) __atomic_store_n(&done[wave], round + 1, __ATOMIC_RELAXED);
@@ -415,6 +421,47 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
     return launch_kernel(kern, dim3((st.batch + per_wg - 1) / per_wg), dim3(RTHREADS), lay.lds, stream, args);
 }
 
+namespace {
+// The Bibsonomy network of the multi-label experiment (picnn.bibtex_spec(): 159 labels, hidden widths 600 and 159): the
+// benchmark's model, whose shape does not change between the calls of a training or test run.
+typedef FixedShape<159, 600, 159, 1> BibtexShape;
+
+// Everything a fixed instance holds as a constant against what the launcher's own functions (fill_args with pack_offsets,
+// make_dual_args with pw_build) produced for THIS model and state: the instance is taken only where all of it agrees.
+template <typename Shape>
+bool shape_matches(const FcArgs &fa, const DualArgs &da) {
+    const PairwisePlan &p = da.plan, &q = Shape::PLAN;
+    bool ok = fc_geom_same(fa, Shape::GEOM) && da.st.n == Shape::N_ROW && da.n_pad == Shape::N_PAD && da.ldA == Shape::LDA &&
+              p.n_leaves == q.n_leaves && p.n_prog == q.n_prog && p.depth == q.depth;
+    for (int i = 0; ok && i < q.n_leaves; ++i) ok = p.leaf_start[i] == q.leaf_start[i] && p.leaf_len[i] == q.leaf_len[i];
+    for (int i = 0; ok && i < q.n_prog; ++i) ok = p.prog[i] == q.prog[i];
+    return ok;
+}
+
+// ICNN_BE_SHAPE_*: the instance a launch with these arguments and this layout takes
+int pick_shape_instance(const FusedArgs &args, const FusedTileLayout &lay) {
+    const icnn_be_state &st = args.da.st;
+    if ((st.flags & ICNN_BE_FLAG_GENERIC_SHAPE) || st.variant != ICNN_BE_VARIANT_DUAL || st.cut_dtype != ICNN_BE_CUT_F32 ||
+        args.da.budget > 0 || !shape_matches<BibtexShape>(args.fa, args.da))
+        return ICNN_BE_SHAPE_GENERIC;
+    const bool big = st.slots > 15;
+    if (!big && !lay.grouped) return ICNN_BE_SHAPE_BIBTEX_KT16;
+    if (big && lay.grouped) return ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED;
+    return ICNN_BE_SHAPE_GENERIC;
+}
+
+}  // namespace
+
+int fused_shape_instance(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget) {
+    FusedArgs args{};       // what launch_fused_fc_solve fills, but for the buffers
+    FusedTileLayout lay;
+    int fg_bytes = 0;
+    if (!fused_tile_layout(m, st, tile_rows, budget, lay) || fill_args(m, args.fa, fg_bytes) != 0 ||
+        !make_dual_args(args.da, st, nullptr, nullptr, 0, budget, st.slots, nullptr))
+        return ICNN_BE_SHAPE_GENERIC;
+    return pick_shape_instance(args, lay);
+}
+
 hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                  float *g_work, long long *dual_prof, hipStream_t stream, int tile_rows, int budget,
                                  const SolveReset &reset) {
@@ -437,6 +484,11 @@ hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, co
                     : (rl ? fused_fc_solve_kernel<true, 16> : fused_fc_solve_kernel<false, 16>);
     if (st.variant == ICNN_BE_VARIANT_PDIPM) kern = big ? fused_fc_solve_kernel<false, 32, true> : fused_fc_solve_kernel<false, 16, true>;
     if (budget > 0) kern = big ? fused_fc_solve_kernel<false, 32, false, true> : fused_fc_solve_kernel<false, 16, false, true>;
+    switch (pick_shape_instance(args, lay)) {           // (never with a budget, never another variant)
+    case ICNN_BE_SHAPE_BIBTEX_KT16: kern = fused_fc_solve_kernel<false, 16, false, false, BibtexShape, 0>; break;
+    case ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED: kern = fused_fc_solve_kernel<false, 32, false, false, BibtexShape, 1>; break;
+    default: break;
+    }
     return launch_kernel(kern, dim3((st.batch + tile_rows - 1) / tile_rows), dim3(NTHREADS), lay.lds, stream, args);
 }
 

@@ -28,11 +28,42 @@ void set_conv_profile_buffer(long long *buf);
 
 // Row pitch with pitch % 32 == 2: the MFMA operand gather (16 rows x 2 adjacent
 // columns per 32-lane group) then touches 32 distinct LDS banks.
-inline int dual_row_pitch(int n_pad) {
+constexpr int dual_row_pitch(int n_pad) {
     int p = n_pad;
     while (p % 32 != 2) ++p;
     return p;
 }
+
+// Shape policies of the persistent tile kernel (be_fused.hip) and of the device functions it inlines: where the hot paths
+// take their geometry from.  Two policies, one interface.  DynShape reads what the launcher put into the arguments (DualArgs,
+// FcArgs): every kernel but the fixed instances.  FixedShape<n, widths...> (be_picnn_fc_dev.h, on top of FixedDual<n> here)
+// yields the same quantities as constant expressions, derived by the very functions the launchers fill the arguments with
+// (dual_row_pitch, pw_build, fc_geom): the compiler folds them into immediates instead of keeping them live in SGPRs.
+struct DynShape {
+    static constexpr bool FIXED = false;
+    static constexpr int LAYER_UNROLL = 1;                      // the layer loops of fc_fg_tile stay loops
+    template <typename A> static __device__ __forceinline__ int n(const A &a) { return a.st.n; }
+    template <typename A> static __device__ __forceinline__ int n_pad(const A &a) { return a.n_pad; }
+    template <typename A> static __device__ __forceinline__ int ldA(const A &a) { return a.ldA; }
+    template <typename A> static __device__ __forceinline__ const auto &plan(const A &a) { return a.plan; }
+    template <typename A> static __device__ __forceinline__ const A &fc(const A &a) { return a; }
+};
+constexpr PairwisePlan pw_plan(int n) {
+    PairwisePlan p{};
+    pw_build(p, n);
+    return p;
+}
+template <int N>
+struct FixedDual {
+    static constexpr bool FIXED = true;
+    static constexpr int N_ROW = N, N_PAD = (N + 15) & ~15, LDA = dual_row_pitch(N_PAD);
+    static constexpr PairwisePlan PLAN = pw_plan(N);
+    static_assert(N >= 1 && N <= 128 * PW_MAX_LEAVES / 2, "n beyond the pairwise-sum plan");
+    template <typename A> static __device__ __forceinline__ int n(const A &) { return N_ROW; }
+    template <typename A> static __device__ __forceinline__ int n_pad(const A &) { return N_PAD; }
+    template <typename A> static __device__ __forceinline__ int ldA(const A &) { return LDA; }
+    template <typename A> static __device__ __forceinline__ const PairwisePlan &plan(const A &) { return PLAN; }
+};
 
 // Per-device launch configuration (a process may drive several GPUs: the caches are keyed by device ordinal and
 // guarded by a mutex).  ensure_dynamic_lds raises a kernel's dynamic-LDS limit on the CURRENT device when needed;
@@ -223,6 +254,8 @@ struct RowsValue {
 hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, const icnn_be_state &st, float *f_work,
                                    float *g_work, int per_wg, long long *dual_prof, hipStream_t stream, bool resume,
                                    const SolveReset &reset = SolveReset{}, const RowsValue *value = nullptr);
+// ICNN_BE_SHAPE_*: the instance of the persistent tile kernel launch_fused_fc_solve takes for these arguments (host arithmetic)
+int fused_shape_instance(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget);
 int dual_waves(int n, int cut_dtype, int variant);
 long long *dual_profile_buffer();
 void set_dual_trace_buffer(long long *buf);

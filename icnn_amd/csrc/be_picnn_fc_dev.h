@@ -27,7 +27,7 @@ constexpr int TM = 16;     // samples per workgroup
 constexpr int NWAVE = 16;  // waves per workgroup
 constexpr int NTHREADS = NWAVE * 64;
 
-__host__ __device__ inline int pad16(int v) { return (v + 15) & ~15; }
+__host__ __device__ constexpr int pad16(int v) { return (v + 15) & ~15; }
 
 struct FcArgs {
     int n, L;                              // L = number of hidden z-layers (n_layers - 1)
@@ -63,12 +63,12 @@ constexpr int TILE_RD = 2;
 // were never the bound -- with eight accumulator and ring registers fewer in the 128-register kernels.
 constexpr bool TILE_PAIR = false;
 constexpr int TILE_STEP = (TILE_PAIR ? 2 : 1) * NWAVE;
-__host__ __device__ inline int kblocks(int K) { return (pad16(K) / 16 + PF - 1) / PF * PF; }
+__host__ __device__ constexpr int kblocks(int K) { return (pad16(K) / 16 + PF - 1) / PF * PF; }
 // k-blocks the MFMA tile loops of fc_fg_tile walk: the real ones, up to a multiple of their ring depth (the pack's further
 // zero fragments would add nothing: acc + 0 * a == acc bit for bit, acc is never -0)
 // (an odd number of real k-blocks that IS the pack's -- 5, 15, 25: widths 65-80, 225-240, ... -- has no zero fragment to round
 // up into; gemm_tiles runs their last k-block behind the loop)
-__host__ __device__ inline int kblocks_tile(int K) {
+__host__ __device__ constexpr int kblocks_tile(int K) {
     const int up = (pad16(K) / 16 + TILE_RD - 1) / TILE_RD * TILE_RD;
     return up <= kblocks(K) ? up : kblocks(K);
 }
@@ -76,14 +76,14 @@ __host__ __device__ inline int kblocks_tile(int K) {
 // LDS row pitch (floats): multiple of 4 and == 8 (mod 64) so that the ds_read_b128 A-fragment gather
 // (16 rows x 4 k-quads) is bank-conflict free, and wide enough for every k-block the GEMM
 // loops read (the padded ones included).
-__host__ __device__ inline int lds_pitch(int width) {
+__host__ __device__ constexpr int lds_pitch(int width) {
     int p = kblocks(width) * 16;
     while ((p & 63) != 8) p += 4;
     return p;
 }
 
 // floats of one packed GEMM operand W[K][N]
-inline size_t packed_floats(int K, int N) { return (size_t)kblocks(K) * (pad16(N) / 16) * 256; }
+constexpr size_t packed_floats(int K, int N) { return (size_t)kblocks(K) * (pad16(N) / 16) * 256; }
 
 // pack[(kb*NT + nt)*256 + lane*4 + s] = W[kb*16 + 4*(lane>>4) + s][nt*16 + (lane&15)]
 // `transpose`: the logical operand is src^T (src stored [N][K] row-major).
@@ -110,27 +110,115 @@ struct PackOffsets {
         zu_b[ICNN_BE_MAX_LAYERS];
     size_t total;
 };
-PackOffsets pack_offsets(const icnn_be_fc_model &m) {
+constexpr PackOffsets pack_offsets(int n, int n_layers, const int *width) {
     PackOffsets o{};
     size_t at = 0;
-    const int L = m.n_layers - 1;
+    const int L = n_layers - 1;
     for (int i = 0; i <= L; ++i) {
-        const int wi = m.width[i];
+        const int wi = width[i];
         if (i < L) {
-            o.yu_f[i] = (long long)at; at += packed_floats(m.n, wi);
-            o.yu_b[i] = (long long)at; at += packed_floats(wi, m.n);
+            o.yu_f[i] = (long long)at; at += packed_floats(n, wi);
+            o.yu_b[i] = (long long)at; at += packed_floats(wi, n);
             if (i > 0) {
-                o.zu_f[i] = (long long)at; at += packed_floats(m.width[i - 1], wi);
-                o.zu_b[i] = (long long)at; at += packed_floats(wi, m.width[i - 1]);
+                o.zu_f[i] = (long long)at; at += packed_floats(width[i - 1], wi);
+                o.zu_b[i] = (long long)at; at += packed_floats(wi, width[i - 1]);
             }
         } else {   // final scalar layer: plain vectors, 16-float aligned
-            o.yu_f[i] = o.yu_b[i] = (long long)at; at += (size_t)pad16(m.n);
-            o.zu_f[i] = o.zu_b[i] = (long long)at; at += (size_t)pad16(m.width[i - 1]);
+            o.yu_f[i] = o.yu_b[i] = (long long)at; at += (size_t)pad16(n);
+            o.zu_f[i] = o.zu_b[i] = (long long)at; at += (size_t)pad16(width[i - 1]);
         }
     }
     o.total = at;
     return o;
 }
+inline PackOffsets pack_offsets(const icnn_be_fc_model &m) { return pack_offsets(m.n, m.n_layers, m.width); }
+
+// The geometry of a model: everything fc_fg_tile needs that follows from n and the widths alone.  ONE walk (fc_geom) yields it
+// for both shape policies (be_kernels.h): fill_args copies it into the FcArgs of a launch, FixedShape keeps it as a constant.
+// The field names are FcArgs' own, so that the device code reads either through the same expressions.
+struct FcGeom {
+    int n, L;
+    int width[ICNN_BE_MAX_LAYERS];
+    int ctx_width;
+    int yu_off[ICNN_BE_MAX_LAYERS], zu_off[ICNN_BE_MAX_LAYERS], gate_off[ICNN_BE_MAX_LAYERS];
+    long long w_yu_f[ICNN_BE_MAX_LAYERS], w_yu_b[ICNN_BE_MAX_LAYERS];
+    long long w_zu_f[ICNN_BE_MAX_LAYERS], w_zu_b[ICNN_BE_MAX_LAYERS];
+    int zb_off[ICNN_BE_MAX_LAYERS], zb_ld[ICNN_BE_MAX_LAYERS];
+    int ldY, ybuf_off, aop_off[ICNN_BE_MAX_LAYERS], gbuf_off, dl_off, lds_floats;
+};
+// 0, or ICNN_BE_EINVAL: not a network (no hidden layer, too many, a width below 1, a final width other than 1)
+constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a) {
+    const int L = n_layers - 1;
+    if (L < 1 || n_layers > ICNN_BE_MAX_LAYERS || width[L] != 1 || n < 1) return ICNN_BE_EINVAL;
+    a.n = n;
+    a.L = L;
+    int o = 0, lo = 0;
+    for (int i = 0; i <= L; ++i) {
+        if (width[i] < 1) return ICNN_BE_EINVAL;
+        a.width[i] = width[i];
+        a.yu_off[i] = o; o += n;
+        a.zu_off[i] = o; o += width[i];
+        a.gate_off[i] = -1;
+        if (i > 0) { a.gate_off[i] = o; o += width[i - 1]; }
+    }
+    a.ctx_width = o;
+    const PackOffsets po = pack_offsets(n, n_layers, width);
+    for (int i = 0; i <= L; ++i) {
+        a.w_yu_f[i] = po.yu_f[i]; a.w_yu_b[i] = po.yu_b[i];
+        a.w_zu_f[i] = po.zu_f[i]; a.w_zu_b[i] = po.zu_b[i];
+    }
+    a.ldY = lds_pitch(n);
+    a.ybuf_off = lo; lo += TM * a.ldY;
+    for (int i = 0; i < L; ++i) { a.aop_off[i] = lo; lo += TM * a.ldY; }
+    a.gbuf_off = lo; lo += TM * a.ldY;
+    for (int i = 0; i < L; ++i) {
+        a.zb_ld[i] = lds_pitch(width[i]);
+        a.zb_off[i] = lo; lo += TM * a.zb_ld[i];
+    }
+    a.dl_off = lo; lo += TM * a.zb_ld[L - 1];
+    a.lds_floats = lo;
+    return 0;
+}
+// dst (FcArgs or FcGeom) <- the geometry; same(): every geometry field of `a` is g's
+template <typename Dst>
+constexpr void fc_geom_copy(Dst &d, const FcGeom &g) {
+    d.n = g.n; d.L = g.L; d.ctx_width = g.ctx_width;
+    d.ldY = g.ldY; d.ybuf_off = g.ybuf_off; d.gbuf_off = g.gbuf_off; d.dl_off = g.dl_off; d.lds_floats = g.lds_floats;
+    for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i) {
+        d.width[i] = g.width[i];
+        d.yu_off[i] = g.yu_off[i]; d.zu_off[i] = g.zu_off[i]; d.gate_off[i] = g.gate_off[i];
+        d.w_yu_f[i] = g.w_yu_f[i]; d.w_yu_b[i] = g.w_yu_b[i]; d.w_zu_f[i] = g.w_zu_f[i]; d.w_zu_b[i] = g.w_zu_b[i];
+        d.zb_off[i] = g.zb_off[i]; d.zb_ld[i] = g.zb_ld[i]; d.aop_off[i] = g.aop_off[i];
+    }
+}
+template <typename A>
+constexpr bool fc_geom_same(const A &a, const FcGeom &g) {
+    bool ok = a.n == g.n && a.L == g.L && a.ctx_width == g.ctx_width && a.ldY == g.ldY && a.ybuf_off == g.ybuf_off &&
+              a.gbuf_off == g.gbuf_off && a.dl_off == g.dl_off && a.lds_floats == g.lds_floats;
+    for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i)
+        ok = ok && a.width[i] == g.width[i] && a.yu_off[i] == g.yu_off[i] && a.zu_off[i] == g.zu_off[i] &&
+             a.gate_off[i] == g.gate_off[i] && a.w_yu_f[i] == g.w_yu_f[i] && a.w_yu_b[i] == g.w_yu_b[i] &&
+             a.w_zu_f[i] == g.w_zu_f[i] && a.w_zu_b[i] == g.w_zu_b[i] && a.zb_off[i] == g.zb_off[i] &&
+             a.zb_ld[i] == g.zb_ld[i] && a.aop_off[i] == g.aop_off[i];
+    return ok;
+}
+
+// The fixed shape policy (be_kernels.h): y of N entries, layer widths W... (the last one is the scalar head's 1).
+template <int N, int... W>
+struct FixedShape : FixedDual<N> {
+    static constexpr int N_LAYERS = (int)sizeof...(W);
+    static constexpr int LAYER_UNROLL = ICNN_BE_MAX_LAYERS;     // the layer loops of fc_fg_tile unroll completely
+    static constexpr FcGeom make() {
+        const int w[ICNN_BE_MAX_LAYERS] = {W...};
+        FcGeom g{};
+        fc_geom(N, N_LAYERS, w, g);
+        return g;
+    }
+    static constexpr FcGeom GEOM = make();
+    static_assert(N_LAYERS >= 2 && N_LAYERS <= ICNN_BE_MAX_LAYERS && GEOM.L == N_LAYERS - 1, "not a network");
+    static_assert(GEOM.lds_floats * 4 <= LDS_BYTES, "the tile's activation buffers do not fit the LDS");
+    template <typename A> static __device__ __forceinline__ const FcGeom &fc(const A &) { return GEOM; }
+};
 
 __device__ __forceinline__ float act_fn(float p, float alpha) { return p > 0.f ? p : alpha * p; }
 
@@ -244,19 +332,22 @@ __device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *
 
 // One tile of TM samples (workgroup-wide: NTHREADS threads, `lds` = the dynamic shared memory of the workgroup).
 // Stand-alone kernel: one workgroup per tile.  be_fused.hip calls it once per round from its persistent workgroup.
-template <typename ArgsT>          // FcArgs by value, or a reference into the kernel-argument segment (be_fused.hip)
+// Shape (be_kernels.h): where the geometry comes from -- the arguments (DynShape), or constants (FixedShape: `ge` below is a
+// constant object, the layer loops unroll, and every gemm_tiles call sees constant KB, NT, strides and LDS pitches)
+template <typename Shape = DynShape, typename ArgsT>   // ArgsT: FcArgs by value, or a reference into the kernel-argument segment (be_fused.hip)
 __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds) {
     // Every float32 operation below is written out (explicit fmaf, no compiler contraction) so that
     // oracle/picnn_chain.c can reproduce the kernel's result bit for bit.
 #pragma clang fp contract(off)
     const int tid = thread_id(), lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, q = lane >> 4;
+    const auto &ge = Shape::fc(a);
     const int TR = a.tile_rows;
     const int s0 = tile * TR;
     const int rows = min(TR, a.batch - s0);
-    const int n = a.n, L = a.L, C = a.ctx_width, ldY = a.ldY;
+    const int n = ge.n, L = ge.L, C = ge.ctx_width, ldY = ge.ldY;
     const int npad = pad16(n);
-    float *ybuf = lds + a.ybuf_off;      // y (network input)
+    float *ybuf = lds + ge.ybuf_off;      // y (network input)
     long long tick = ICNN_BE_PROF_ON(a.prof) ? (long long)__builtin_readcyclecounter() : 0;
     auto lap = [&](int phase) {          // diagnostic only (tools/fc_phase_profile.py)
         if (ICNN_BE_PROF_ON(a.prof)) {
@@ -277,8 +368,8 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
         if (tid < rows) live = a.finished[s0 + tid] == 0;
     }
     const float *ctx = a.ctx + (size_t)s0 * C;
-    float *gbuf = lds + a.gbuf_off;      // dE/dy accumulator of the backward pass
-    float *dl = lds + a.dl_off;          // delta_{L-1} (the activations z_{L-1} stay intact for the energy)
+    float *gbuf = lds + ge.gbuf_off;      // dE/dy accumulator of the backward pass
+    float *dl = lds + ge.dl_off;          // delta_{L-1} (the activations z_{L-1} stay intact for the energy)
 
     // Wave w prepares row w of the tile (TM == NWAVE): no index arithmetic beyond lane strides.
     // The GEMMs read k-blocks up to a multiple of PF, i.e. pad columns [pad16(width), pitch) that no phase writes:
@@ -290,9 +381,9 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
             const int w16 = pad16(width);
             for (int j = w16 + lane; j < ld; j += 64) buf[wave * ld + j] = 0.f;
         };
-        for (int i = 0; i < L; ++i) zero_pad(lds + a.aop_off[i], ldY, n);
-        for (int i = 0; i < L; ++i) zero_pad(lds + a.zb_off[i], a.zb_ld[i], a.width[i]);
-        zero_pad(dl, a.zb_ld[L - 1], a.width[L - 1]);
+        for (int i = 0; i < L; ++i) zero_pad(lds + ge.aop_off[i], ldY, n);
+        for (int i = 0; i < L; ++i) zero_pad(lds + ge.zb_off[i], ge.zb_ld[i], ge.width[i]);
+        zero_pad(dl, ge.zb_ld[L - 1], ge.width[L - 1]);
     }
     // network input: y rounded to float32 like a TensorFlow feed (RL wrapper feeds 2y-1), and with it the y-operand
     // y * yu_i of EVERY layer; all loads of a lane's elements are issued before the first use
@@ -309,7 +400,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                 yd[k] = ok ? a.y[(size_t)(s0 + r) * n + j] : 0.0;
 #pragma unroll
                 for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i)
-                    cu[k][i] = ok && i < L ? ctx[(size_t)r * C + a.yu_off[i] + j] : 0.f;
+                    cu[k][i] = ok && i < L ? ctx[(size_t)r * C + ge.yu_off[i] + j] : 0.f;
             }
             if (j0 == 0 && a.finished && !__syncthreads_or(live)) return;     // (uniform: every thread takes j0 = 0)
 #pragma unroll
@@ -321,7 +412,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                     ybuf[r * ldY + j] = ok ? v : 0.f;
 #pragma unroll
                     for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i)
-                        if (i < L) lds[a.aop_off[i] + r * ldY + j] = ok ? v * cu[k][i] : 0.f;
+                        if (i < L) lds[ge.aop_off[i] + r * ldY + j] = ok ? v * cu[k][i] : 0.f;
                 }
             }
         }
@@ -330,15 +421,16 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     lap(0);
 
     // ---------------- forward ------------------------------------------------------------
-    const float *wyL = a.wpack + a.w_yu_f[L];       // final scalar layer: plain vectors
-    const float *wzL = a.wpack + a.w_zu_f[L];
+    const float *wyL = a.wpack + ge.w_yu_f[L];       // final scalar layer: plain vectors
+    const float *wzL = a.wpack + ge.w_zu_f[L];
+#pragma unroll(Shape::LAYER_UNROLL)
     for (int i = 0; i < L; ++i) {
-        const int wi = a.width[i], wpad = pad16(wi);
+        const int wi = ge.width[i], wpad = pad16(wi);
         const bool last = i == L - 1;
-        float *zout = lds + a.zb_off[i];
-        const int ldo = a.zb_ld[i];
+        float *zout = lds + ge.zb_off[i];
+        const int ldo = ge.zb_ld[i];
         const int NT = wpad / 16, KBy = kblocks_tile(n);
-        const float *Wy = a.wpack + a.w_yu_f[i];
+        const float *Wy = a.wpack + ge.w_yu_f[i];
         for (int nt = wave; nt < NT; nt += TILE_STEP) {
             const int nt1 = TILE_PAIR && nt + NWAVE < NT ? nt + NWAVE : -1;
             f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -359,15 +451,15 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                     for (int r = 0; r < 4; ++r) {
                         const int row = 4 * q + r;
                         const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
-                        czu[h][r] = c[a.zu_off[i] + cc];
-                        cgt[h][r] = c[a.gate_off[i + 1] + cc];
+                        czu[h][r] = c[ge.zu_off[i] + cc];
+                        cgt[h][r] = c[ge.gate_off[i + 1] + cc];
                     }
                 }
             };
-            gemm_tiles(lds + a.aop_off[i], ldY, Wy, KBy, NT, nt, nt1, acc[0], acc[1], operands);
+            gemm_tiles(lds + ge.aop_off[i], ldY, Wy, KBy, NT, nt, nt1, acc[0], acc[1], operands);
             if (i > 0)
-                gemm_tiles(lds + a.zb_off[i - 1], a.zb_ld[i - 1], a.wpack + a.w_zu_f[i],
-                           kblocks_tile(a.width[i - 1]), NT, nt, nt1, acc[0], acc[1]);
+                gemm_tiles(lds + ge.zb_off[i - 1], ge.zb_ld[i - 1], a.wpack + ge.w_zu_f[i],
+                           kblocks_tile(ge.width[i - 1]), NT, nt, nt1, acc[0], acc[1]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int tile = h == 0 ? nt : nt1;
@@ -395,14 +487,15 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     }
 
     // ---------------- backward (the energy of the final scalar layer rides along in its last phase) ---------
+#pragma unroll(Shape::LAYER_UNROLL)
     for (int i = L - 1; i >= 0; --i) {
-        const int wi = a.width[i];
+        const int wi = ge.width[i];
         const bool first = i == L - 1;
-        const float *delta = first ? dl : lds + a.zb_off[i];
-        const int ldd = a.zb_ld[i], KB = kblocks_tile(wi);
+        const float *delta = first ? dl : lds + ge.zb_off[i];
+        const int ldd = ge.zb_ld[i], KB = kblocks_tile(wi);
         const int NTy = npad / 16;
         {   // dE/dy (+)= yu_i * (delta_i Wyu_i^T), starting from yu_L * wyu_L
-            const float *Wt = a.wpack + a.w_yu_b[i];
+            const float *Wt = a.wpack + ge.w_yu_b[i];
             // (with a delta product behind it in the same phase, i > 0, the few dE/dy tiles go to the waves counted from the
             //  top: those have the fewest delta tiles -- Bibsonomy step 1: ten dE/dy tiles + 38 delta tiles = three per wave
             //  instead of four on waves 0..5 and two on waves 10..15)
@@ -412,7 +505,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                 f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                 float cyu[2][4], cyL[2][4], wy[2];
                 // (not the first backward phase: cyL is not used; its loads repeat cyu's addresses)
-                const int offL = first ? a.yu_off[L] : a.yu_off[i];
+                const int offL = first ? ge.yu_off[L] : ge.yu_off[i];
                 auto operands = [&] {
 #pragma unroll
                     for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
@@ -424,7 +517,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                         for (int r = 0; r < 4; ++r) {
                             const int row = 4 * q + r;
                             const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
-                            cyu[h][r] = c[a.yu_off[i] + cc];
+                            cyu[h][r] = c[ge.yu_off[i] + cc];
                             cyL[h][r] = c[offL + cc];
                         }
                     }
@@ -448,10 +541,10 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
         }
         lap(i == 0 ? 11 : 8);
         if (i > 0) {   // delta_{i-1} = gate_i * (delta_i Wzu_i^T) * act'(pre_{i-1})
-            const int wp = a.width[i - 1];
-            float *zprev = lds + a.zb_off[i - 1];
-            const int ldp = a.zb_ld[i - 1];
-            const float *Wt = a.wpack + a.w_zu_b[i];
+            const int wp = ge.width[i - 1];
+            float *zprev = lds + ge.zb_off[i - 1];
+            const int ldp = ge.zb_ld[i - 1];
+            const float *Wt = a.wpack + ge.w_zu_b[i];
             const int NTp = pad16(wp) / 16;
             for (int nt = wave; nt < NTp; nt += TILE_STEP) {
                 const int nt1 = TILE_PAIR && nt + NWAVE < NTp ? nt + NWAVE : -1;
@@ -466,7 +559,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int row = 4 * q + r;
-                            cga[h][r] = ctx[(size_t)(row < rows ? row : 0) * C + a.gate_off[i] + cc];
+                            cga[h][r] = ctx[(size_t)(row < rows ? row : 0) * C + ge.gate_off[i] + cc];
                         }
                     }
                 };
@@ -493,8 +586,8 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
         } else {
             // E = z_{L-1} . wzu_L + (y * yu_L) . wyu_L + zu_L, one wave per row: on the waves that have no dE/dy tile
             // in this phase where there are any (n < 256), after the tile otherwise
-            const float *zl = lds + a.zb_off[L - 1];
-            const int ldz = a.zb_ld[L - 1], wl = a.width[L - 1];
+            const float *zl = lds + ge.zb_off[L - 1];
+            const int ldz = ge.zb_ld[L - 1], wl = ge.width[L - 1];
             const int busy = NTy < NWAVE ? NTy : NWAVE, idle = NWAVE - busy;
             const int r0 = idle > 0 ? wave - busy : wave, rstep = idle > 0 ? idle : NWAVE;
             if (r0 >= 0)
@@ -503,10 +596,10 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                     float part = 0.f;
                     for (int j = lane; j < wl; j += 64) part = __builtin_fmaf(zl[r * ldz + j], wzL[j], part);
                     for (int j = lane; j < n; j += 64) {
-                        const float yy = ybuf[r * ldY + j] * c[a.yu_off[L] + j];
+                        const float yy = ybuf[r * ldY + j] * c[ge.yu_off[L] + j];
                         part = __builtin_fmaf(yy, wyL[j], part);
                     }
-                    const float e = wave_sum_f(part) + c[a.zu_off[L]];
+                    const float e = wave_sum_f(part) + c[ge.zu_off[L]];
                     if (lane == 0) a.f[s0 + r] = e;
                 }
             lap(7);
@@ -523,40 +616,14 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
 
 
 inline int fill_args(const icnn_be_fc_model &m, FcArgs &a, int &lds_bytes) {
-    const int L = m.n_layers - 1;
-    if (L < 1 || m.n_layers > ICNN_BE_MAX_LAYERS || m.width[L] != 1 || m.n < 1) return ICNN_BE_EINVAL;
-    a.n = m.n;
-    a.L = L;
+    FcGeom g{};
+    if (int rc = fc_geom(m.n, m.n_layers, m.width, g)) return rc;
+    if (g.ctx_width != m.ctx_width) return ICNN_BE_EINVAL;
+    fc_geom_copy(a, g);
     a.alpha = m.alpha;
     a.action_box = m.action_box;
     a.tile_rows = TM;
-    int o = 0, lo = 0;
-    for (int i = 0; i <= L; ++i) {
-        if (m.width[i] < 1) return ICNN_BE_EINVAL;
-        a.width[i] = m.width[i];
-        a.yu_off[i] = o; o += m.n;
-        a.zu_off[i] = o; o += m.width[i];
-        a.gate_off[i] = -1;
-        if (i > 0) { a.gate_off[i] = o; o += m.width[i - 1]; }
-    }
-    if (o != m.ctx_width) return ICNN_BE_EINVAL;
-    a.ctx_width = o;
-    const PackOffsets po = pack_offsets(m);
-    for (int i = 0; i <= L; ++i) {
-        a.w_yu_f[i] = po.yu_f[i]; a.w_yu_b[i] = po.yu_b[i];
-        a.w_zu_f[i] = po.zu_f[i]; a.w_zu_b[i] = po.zu_b[i];
-    }
-    a.ldY = lds_pitch(m.n);
-    a.ybuf_off = lo; lo += TM * a.ldY;
-    for (int i = 0; i < L; ++i) { a.aop_off[i] = lo; lo += TM * a.ldY; }
-    a.gbuf_off = lo; lo += TM * a.ldY;
-    for (int i = 0; i < L; ++i) {
-        a.zb_ld[i] = lds_pitch(m.width[i]);
-        a.zb_off[i] = lo; lo += TM * a.zb_ld[i];
-    }
-    a.dl_off = lo; lo += TM * a.zb_ld[L - 1];
-    a.lds_floats = lo;
-    lds_bytes = lo * 4;
+    lds_bytes = g.lds_floats * 4;
     if (lds_bytes > LDS_BYTES) return ICNN_BE_ELIMIT;
     a.wpack = m.wpack;
     return 0;

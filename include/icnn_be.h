@@ -134,6 +134,10 @@ extern "C" {
                                           * (another summation order: results agree to ~1e-13, not bit for bit;
                                           * tests/test_gpu_parity.py).  Wider float32 rows take the same column-chunked
                                           * passes from either place (same order, same bits). */
+#define ICNN_BE_FLAG_GENERIC_SHAPE 512     /* icnn_be_solve_fc: the persistent tile kernel never takes an instance compiled for one
+                                          * network's shape (ICNN_BE_SHAPE_*), always the generic one that reads the shape from
+                                          * its arguments.  Same operations in the same order: bit-identical results (the
+                                          * identity tests and same-library A/B timings use it) */
 #define ICNN_BE_FLAG_F64_ENERGY 32        /* icnn_be_dual_step: f is float64 [B] whatever the cut dtype (an `fg` that
                                           * returns float64 energies with float32 gradients: the reference's
                                           * bi = fi - sum(gi * x) keeps fi's precision, dual :143) */
@@ -1383,6 +1387,21 @@ ICNN_BE_API int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int 
  * st->scratch is set.  Needs no GPU; the buffer pointers of the state are neither read nor checked.
  */
 ICNN_BE_API int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[8]);
+/*
+ * The instance of the persistent tile kernel icnn_be_solve_fc launches for this model and state on the current device
+ * (additive to ABI 12): ICNN_BE_SHAPE_GENERIC -- the kernel that reads the network's shape from its arguments; also where the
+ * plan (icnn_be_debug_solve_plan) is not ICNN_BE_PATH_TILE -- or the id of an instance compiled for one shape.  Such an instance
+ * is taken only where n, the number of layers, every width and the context width of the model equal its constants, the variant
+ * is dual, the cuts are float32, the launch has no update budget, and the layout decision (the dual phase in groups or not) is
+ * the instance's; ICNN_BE_FLAG_GENERIC_SHAPE switches them off.  It is the launcher's own choice, taken by the launcher's own
+ * code: host arithmetic, no GPU needed (without one the plan is that of a 256-CU device).  A negative error code for what
+ * icnn_be_solve_fc refuses (batch 0: ICNN_BE_EINVAL), but for a float64 cut dtype: ICNN_BE_SHAPE_GENERIC, as for every other
+ * state no instance was compiled for.
+ */
+#define ICNN_BE_SHAPE_GENERIC 0
+#define ICNN_BE_SHAPE_BIBTEX_KT16 1           /* n = 159, widths 600 / 159 / 1 (the Bibsonomy net), up to 15 slots, not grouped */
+#define ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED 2   /* the same net, 16..32 slots, the dual phase in groups */
+ICNN_BE_API int icnn_be_debug_shape_instance(const icnn_be_fc_model *model, const icnn_be_state *st);
 
 /* ---- the DDPG agent: fused actor-critic step, EMA targets, act (be_ddpg.hip, additive to ABI 12) ---- */
 
