@@ -59,7 +59,7 @@ EXPORTS = [
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan", "icnn_be_debug_dual_plan",
-    "icnn_be_debug_shape_instance",
+    "icnn_be_debug_shape_instance", "icnn_be_debug_fc_deal",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
     "icnn_be_fc_context_bn_work_floats", "icnn_be_fc_context_bn", "icnn_be_conv_context_bn_work_floats", "icnn_be_conv_context_bn",
@@ -402,6 +402,8 @@ def load():
     lib.icnn_be_debug_dual_plan.restype = C.c_int
     lib.icnn_be_debug_shape_instance.argtypes = [C.POINTER(FcModel), C.POINTER(State)]
     lib.icnn_be_debug_shape_instance.restype = C.c_int
+    lib.icnn_be_debug_fc_deal.argtypes = [C.POINTER(FcModel), C.POINTER(C.c_int), C.c_int]
+    lib.icnn_be_debug_fc_deal.restype = C.c_int
     lib.icnn_be_adam_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.icnn_be_adam_workspace_bytes.restype = C.c_size_t
     lib.icnn_be_adam_fc.argtypes = [C.POINTER(FcModel), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
@@ -694,6 +696,21 @@ def shape_instance(model, state):
     if rc < 0:
         check(rc, "icnn_be_debug_shape_instance")
     return SHAPE_INSTANCES[rc]
+
+
+UNIT_KINDS = ["fwd_y", "fwd_z", "delta", "dedy", "e"]        # ICNN_BE_UNIT_*
+
+
+def fc_deal(model):
+    """The deal of one tile evaluation of an FcModel (icnn_be_debug_fc_deal): a list of (kind, layer, tile, interval, wave,
+    interval of the result), kind one of UNIT_KINDS.  Host arithmetic."""
+    lib = load()
+    count = lib.icnn_be_debug_fc_deal(C.byref(model), None, 0)
+    if count < 0:
+        check(count, "icnn_be_debug_fc_deal")
+    out = (C.c_int * (6 * count))()
+    lib.icnn_be_debug_fc_deal(C.byref(model), out, count)
+    return [(UNIT_KINDS[out[6 * k]],) + tuple(out[6 * k + 1:6 * k + 6]) for k in range(count)]
 
 
 def adam_plan(model, batch, ctx=None):

@@ -403,6 +403,11 @@ int icnn_be_debug_solve_plan(const icnn_be_fc_model *model, const icnn_be_state 
     return p.path;
 }
 
+int icnn_be_debug_fc_deal(const icnn_be_fc_model *model, int *out, int cap) {
+    if (!model || cap < 0 || (cap > 0 && !out)) return ICNN_BE_EINVAL;
+    return icnn_be::fc_deal_units(*model, out, cap);
+}
+
 int icnn_be_debug_shape_instance(const icnn_be_fc_model *model, const icnn_be_state *st) {
     /* float64 cuts: icnn_be_solve_fc launches nothing for them, so no instance either; everything else it refuses is refused here */
     if (model && st && st->cut_dtype == ICNN_BE_CUT_F64 && check_shape(st) == 0 && st->n == model->n && st->batch > 0 &&

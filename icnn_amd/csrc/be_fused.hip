@@ -472,7 +472,7 @@ hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, co
     int fg_bytes = 0;
     if (fill_args(m, args.fa, fg_bytes) != 0) return hipErrorInvalidValue;
     args.fa.ctx = ctx; args.fa.y = st.y; args.fa.f = f_work; args.fa.g = g_work; args.fa.finished = st.skip_fg;
-    args.fa.batch = st.batch; args.fa.prof = nullptr; args.fa.tile_rows = tile_rows;
+    args.fa.batch = st.batch; args.fa.prof = fc_profile_buffer(); args.fa.tile_rows = tile_rows;   // (laps: profiling build only)
     if (!make_dual_args(args.da, st, f_work, g_work, 0, budget, st.slots, dual_prof)) return hipErrorInvalidValue;
     args.rounds = st.iters > 0 ? st.iters : st.slots;
     args.crow_off = lay.crow_off; args.samples_off = 0; args.sample_bytes = lay.sample_bytes;

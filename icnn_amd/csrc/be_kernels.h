@@ -133,6 +133,7 @@ hipError_t launch_implicit_feed(const icnn_be_state &st, const double *y_true, i
 
 // ---- FC-PICNN energy / gradient --------------------------------------------------
 int fc_check_model(const icnn_be_fc_model &m);
+int fc_deal_units(const icnn_be_fc_model &m, int *out, int cap);   // icnn_be_debug_fc_deal
 size_t fc_pack_floats(const icnn_be_fc_model &m);
 int fc_pack(const icnn_be_fc_model &m, const float *const *w_yu, const float *const *w_zu, float *out);
 hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const double *y, int batch,

@@ -121,4 +121,49 @@ int fc_check_model(const icnn_be_fc_model &m) {
     return fill_args(m, a, lds);
 }
 
+
+// The deal as records { kind, layer, tile, interval, wave, interval of the result } (icnn_be_debug_fc_deal): read off the
+// table and the home-wave rules fc_fg_tile itself follows.
+int fc_deal_units(const icnn_be_fc_model &m, int *out, int cap) {
+    FcGeom g{};
+    if (int rc = fc_geom(m.n, m.n_layers, m.width, g)) return rc;
+    static_assert(FC_UNIT_FWD_Y == ICNN_BE_UNIT_FWD_Y && FC_UNIT_FWD_Z == ICNN_BE_UNIT_FWD_Z && FC_UNIT_DELTA == ICNN_BE_UNIT_DELTA &&
+                  FC_UNIT_DEDY == ICNN_BE_UNIT_DEDY && FC_UNIT_E == ICNN_BE_UNIT_E, "include/icnn_be.h");
+    const FcDeal &d = g.deal;
+    const int L = g.L, NTy = pad16(g.n) / 16;
+    int count = 0;
+    auto put = [&](int kind, int layer, int tile, int interval, int wave, int result) {
+        if (count < cap) {
+            const int rec[6] = {kind, layer, tile, interval, wave, result};
+            for (int k = 0; k < 6; ++k) out[6 * count + k] = rec[k];
+        }
+        ++count;
+    };
+    auto bwd = [&](int layer) { return 2 * L - 1 - layer; };      // the backward interval of a layer
+    for (int i = 0; i < L; ++i) {
+        const int NT = pad16(g.width[i]) / 16;
+        for (int t = 0; t < NT; ++t) {
+            const int wave = fc_home_wave(t);
+            put(FC_UNIT_FWD_Y, i, t, i, wave, i);
+            if (i > 0) put(FC_UNIT_FWD_Z, i, t, i, wave, i);
+        }
+    }
+    for (int i = L - 1; i >= 0; --i) {
+        if (i > 0)
+            for (int t = 0; t < pad16(g.width[i - 1]) / 16; ++t) put(FC_UNIT_DELTA, i, t, bwd(i), fc_home_wave(t), bwd(i));
+        for (int t = 0; t < NTy; ++t) {
+            if (!d.bwd_moved) {
+                put(FC_UNIT_DEDY, i, t, bwd(i), fc_home_wave_dedy(i, t), bwd(i));
+                continue;
+            }
+            for (int w = 0; w < NWAVE; ++w)
+                if (d.dy_mask[i][w] >> t & 1) put(FC_UNIT_DEDY, i, t, bwd(i > 0 ? i - 1 : 0), w, i > 0 ? bwd(i - 1) : 2 * L);
+        }
+    }
+    for (int r = 0; r < TM; ++r)
+        for (int w = 0; w < NWAVE; ++w)
+            if (d.e_mask[w] >> r & 1) put(FC_UNIT_E, L, r, bwd(0), w, bwd(0));
+    return count;
+}
+
 }  // namespace icnn_be

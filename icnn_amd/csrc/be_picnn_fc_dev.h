@@ -29,6 +29,13 @@ constexpr int NTHREADS = NWAVE * 64;
 
 __host__ __device__ constexpr int pad16(int v) { return (v + 15) & ~15; }
 
+// The deal of one evaluation (fc_deal below): which wave runs which moved unit in which barrier interval.  Part of the geometry.
+struct FcDeal {
+    int bwd_moved;                                     // dE/dy_i runs in the interval of layer i - 1, dE/dy_0 ends behind the last barrier
+    unsigned short dy_mask[ICNN_BE_MAX_LAYERS][NWAVE]; // [i][w]: the tiles of dE/dy_i on wave w (bwd_moved)
+    unsigned short e_mask[NWAVE];                      // [w]: the energy rows of wave w
+};
+
 struct FcArgs {
     int n, L;                              // L = number of hidden z-layers (n_layers - 1)
     int width[ICNN_BE_MAX_LAYERS];
@@ -40,6 +47,7 @@ struct FcArgs {
     long long w_zu_f[ICNN_BE_MAX_LAYERS], w_zu_b[ICNN_BE_MAX_LAYERS];
     int zb_off[ICNN_BE_MAX_LAYERS], zb_ld[ICNN_BE_MAX_LAYERS];          // LDS float offsets / pitches
     int ldY, ybuf_off, aop_off[ICNN_BE_MAX_LAYERS], gbuf_off, dl_off, lds_floats;   // aop_i = y * yu_i
+    FcDeal deal;
     const float *wpack, *ctx;
     const double *y;
     float *f, *g;
@@ -145,7 +153,69 @@ struct FcGeom {
     long long w_zu_f[ICNN_BE_MAX_LAYERS], w_zu_b[ICNN_BE_MAX_LAYERS];
     int zb_off[ICNN_BE_MAX_LAYERS], zb_ld[ICNN_BE_MAX_LAYERS];
     int ldY, ybuf_off, aop_off[ICNN_BE_MAX_LAYERS], gbuf_off, dl_off, lds_floats;
+    FcDeal deal;
 };
+
+// ---- the deal -------------------------------------------------------------------------------------------------------------
+// An evaluation is 2 L barrier intervals: forward layers 0 .. L-1 (intervals 0 .. L-1), backward layers L-1 .. 0 (intervals
+// L .. 2L-1), and what runs behind the last barrier (interval 2L).  Its units, each one 16-column output tile of one GEMM:
+//   FC_UNIT_FWD_Y  (y * yu_i) Wyu_i             FC_UNIT_FWD_Z  (z_{i-1} gate_i) Wzu_i, continuing FWD_Y's accumulator, + epilogue
+//   FC_UNIT_DELTA  delta_i Wzu_i^T (-> delta_{i-1})   FC_UNIT_DEDY  delta_i Wyu_i^T (-> gbuf)   FC_UNIT_E  one energy row
+// Tile t of a GEMM belongs to wave t % NWAVE in the interval of its layer (fc_home_wave), and the narrow GEMMs leave waves idle
+// there.  fc_deal moves the DEDY units, which need less than their interval's barrier provides: DEDY of layer i+1 reads
+// delta_{i+1}, which interval i+1 already had, and runs in the backward interval of layer i on the waves with the shortest
+// chains there (counted in k-blocks, ties to the highest wave) -- if dE/dy has at most one tile per wave.  DEDY of layer 0
+// stays, keeps its accumulator across the last barrier and forms g = gscale * fma(cyu_0, acc, gbuf) from there, so gbuf sees
+// the same fma chain L-1 .. 0 per element and the separate pass that stored g is gone.  With more than NWAVE tiles of dE/dy
+// every unit stays at home (same bits).  The energy rows ride in the last interval, row by row onto the shortest chains.
+// (Measured and left out, DESIGN.md section 6: FWD_Y of a narrow layer an interval early with the accumulator carried across the
+//  barrier, and the energy rows in the first backward interval.)
+enum { FC_UNIT_FWD_Y = 0, FC_UNIT_FWD_Z = 1, FC_UNIT_DELTA = 2, FC_UNIT_DEDY = 3, FC_UNIT_E = 4 };
+constexpr int FC_E_ROW_COST = 2;      // an energy row, in k-blocks of a GEMM chain (one memory round trip and a few fmas)
+// the wave with the shortest chain (ties: the highest)
+constexpr int fc_deal_pick(const int *load) {
+    int best = NWAVE - 1;
+    for (int w = NWAVE - 2; w >= 0; --w)
+        if (load[w] < load[best]) best = w;
+    return best;
+}
+constexpr FcDeal fc_deal(int n, int L, const int *width) {
+    FcDeal d{};
+    const int NTy = pad16(n) / 16;
+    d.bwd_moved = NTy <= NWAVE;
+    for (int i = L - 1; i >= 0; --i) {                   // backward interval of layer i
+        int load[NWAVE] = {};
+        if (i > 0)
+            for (int t = 0; t < pad16(width[i - 1]) / 16; ++t) load[t % NWAVE] += kblocks_tile(width[i]);
+        if (d.bwd_moved) {
+            if (i == 0)
+                for (int t = 0; t < NTy; ++t) {
+                    d.dy_mask[0][t] = (unsigned short)(1u << t);
+                    load[t] += kblocks_tile(width[0]);
+                }
+            if (i + 1 < L)
+                for (int t = 0; t < NTy; ++t) {
+                    const int w = fc_deal_pick(load);
+                    d.dy_mask[i + 1][w] |= (unsigned short)(1u << t);
+                    load[w] += kblocks_tile(width[i + 1]);
+                }
+        } else {
+            for (int t = 0; t < NTy; ++t) load[i > 0 ? NWAVE - 1 - t % NWAVE : t % NWAVE] += kblocks_tile(width[i]);
+        }
+        if (i == 0)
+            for (int r = 0; r < TM; ++r) {
+                const int w = fc_deal_pick(load);
+                d.e_mask[w] |= (unsigned short)(1u << r);
+                load[w] += FC_E_ROW_COST;
+            }
+    }
+    return d;
+}
+// the wave of tile t of a GEMM the deal leaves in the interval of its layer (DEDY: with a DELTA product behind it in the same
+// interval, i > 0, the few dE/dy tiles are counted from the top -- those waves have the fewest delta tiles)
+__host__ __device__ constexpr int fc_home_wave(int t) { return t % NWAVE; }
+__host__ __device__ constexpr int fc_home_wave_dedy(int layer, int t) { return layer > 0 ? NWAVE - 1 - t % NWAVE : t % NWAVE; }
+
 // 0, or ICNN_BE_EINVAL: not a network (no hidden layer, too many, a width below 1, a final width other than 1)
 constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a) {
     const int L = n_layers - 1;
@@ -177,6 +247,7 @@ constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a) {
     }
     a.dl_off = lo; lo += TM * a.zb_ld[L - 1];
     a.lds_floats = lo;
+    a.deal = fc_deal(n, L, width);
     return 0;
 }
 // dst (FcArgs or FcGeom) <- the geometry; same(): every geometry field of `a` is g's
@@ -184,6 +255,7 @@ template <typename Dst>
 constexpr void fc_geom_copy(Dst &d, const FcGeom &g) {
     d.n = g.n; d.L = g.L; d.ctx_width = g.ctx_width;
     d.ldY = g.ldY; d.ybuf_off = g.ybuf_off; d.gbuf_off = g.gbuf_off; d.dl_off = g.dl_off; d.lds_floats = g.lds_floats;
+    d.deal = g.deal;
     for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i) {
         d.width[i] = g.width[i];
         d.yu_off[i] = g.yu_off[i]; d.zu_off[i] = g.zu_off[i]; d.gate_off[i] = g.gate_off[i];
@@ -349,8 +421,8 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     const int npad = pad16(n);
     float *ybuf = lds + ge.ybuf_off;      // y (network input)
     long long tick = ICNN_BE_PROF_ON(a.prof) ? (long long)__builtin_readcyclecounter() : 0;
-    auto lap = [&](int phase) {          // diagnostic only (tools/fc_phase_profile.py)
-        if (ICNN_BE_PROF_ON(a.prof)) {
+    auto lap = [&](int phase) {          // diagnostic only (tools/fc_phase_profile.py; it knows the slots of up to two layers)
+        if (ICNN_BE_PROF_ON(a.prof) && phase < FC_PROF_PHASES) {
             const long long now = (long long)__builtin_readcyclecounter();
             if (lane == 0)
                 atomicAdd(reinterpret_cast<unsigned long long *>(a.prof) +
@@ -421,18 +493,22 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     lap(0);
 
     // ---------------- forward ------------------------------------------------------------
+    static_assert(!TILE_PAIR, "the dE/dy_0 unit carries ONE accumulator across the last barrier");
+    const auto &deal = ge.deal;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
     const float *wyL = a.wpack + ge.w_yu_f[L];       // final scalar layer: plain vectors
     const float *wzL = a.wpack + ge.w_zu_f[L];
+    const int KBy = kblocks_tile(n);
 #pragma unroll(Shape::LAYER_UNROLL)
     for (int i = 0; i < L; ++i) {
         const int wi = ge.width[i], wpad = pad16(wi);
         const bool last = i == L - 1;
         float *zout = lds + ge.zb_off[i];
         const int ldo = ge.zb_ld[i];
-        const int NT = wpad / 16, KBy = kblocks_tile(n);
+        const int NT = wpad / 16;
         const float *Wy = a.wpack + ge.w_yu_f[i];
-        for (int nt = wave; nt < NT; nt += TILE_STEP) {
-            const int nt1 = TILE_PAIR && nt + NWAVE < NT ? nt + NWAVE : -1;
+        for (int nt = fc_home_wave(wave); nt < NT; nt += TILE_STEP) {
+            const int nt1 = -1;
             f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             // epilogue operands (x-only context): requested in front of the MFMA loops so that their HBM/L2 latency is hidden
             // behind them, but behind the first weight fragments of the unit (gemm_loop, `pre`).  Every lane loads, rows and
@@ -486,131 +562,174 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
         lap(3 + 3 * i);
     }
 
-    // ---------------- backward (the energy of the final scalar layer rides along in its last phase) ---------
+    // ---------------- backward (the energy of the final scalar layer rides along in its last interval) ---------
+    const int NTy = npad / 16;
+    const bool bmoved = deal.bwd_moved;
+    f4 gacc = {0.f, 0.f, 0.f, 0.f};                  // dE/dy_0 of this wave's tile and its operand, kept across the last barrier
+    float gcyu[4] = {0.f, 0.f, 0.f, 0.f};
+    int gtile = -1;
+    // one tile of dE/dy (+)= yu_j * (delta_j Wyu_j^T), starting from yu_L * wyu_L; `defer`: the fma into gbuf is left to the caller
+    auto dy_unit = [&](int j, int nt, bool defer) {
+        const bool first = j == L - 1;
+        const float *delta = first ? dl : lds + ge.zb_off[j];
+        f4 acc = {0.f, 0.f, 0.f, 0.f}, none = {0.f, 0.f, 0.f, 0.f};
+        float cyu[4], cyL[4], wy;
+        // (not the first backward layer: cyL is not used; its loads repeat cyu's addresses)
+        const int offL = first ? ge.yu_off[L] : ge.yu_off[j];
+        const int col = nt * 16 + r16;
+        auto operands = [&] {
+            const int cc = col < n ? col : 0;
+            wy = wyL[first ? cc : 0];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 4 * q + r;
+                const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
+                cyu[r] = c[ge.yu_off[j] + cc];
+                cyL[r] = c[offL + cc];
+            }
+        };
+        gemm_tiles(delta, ge.zb_ld[j], a.wpack + ge.w_yu_b[j], kblocks_tile(ge.width[j]), NTy, nt, -1, acc, none, operands);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * q + r;
+            if (row < rows && col < n) {
+                const float g_in = first ? cyL[r] * wy : gbuf[row * ldY + col];
+                if (!defer) gbuf[row * ldY + col] = __builtin_fmaf(cyu[r], acc[r], g_in);
+                else if (first) gbuf[row * ldY + col] = g_in;
+            }
+            gcyu[r] = defer ? cyu[r] : gcyu[r];
+        }
+        if (defer) {
+            gacc = acc;
+            gtile = nt;
+        }
+    };
 #pragma unroll(Shape::LAYER_UNROLL)
     for (int i = L - 1; i >= 0; --i) {
         const int wi = ge.width[i];
         const bool first = i == L - 1;
         const float *delta = first ? dl : lds + ge.zb_off[i];
         const int ldd = ge.zb_ld[i], KB = kblocks_tile(wi);
-        const int NTy = npad / 16;
-        {   // dE/dy (+)= yu_i * (delta_i Wyu_i^T), starting from yu_L * wyu_L
-            const float *Wt = a.wpack + ge.w_yu_b[i];
-            // (with a delta product behind it in the same phase, i > 0, the few dE/dy tiles go to the waves counted from the
-            //  top: those have the fewest delta tiles -- Bibsonomy step 1: ten dE/dy tiles + 38 delta tiles = three per wave
-            //  instead of four on waves 0..5 and two on waves 10..15)
-            const int wy = i > 0 ? NWAVE - 1 - wave : wave;
-            for (int nt = wy; nt < NTy; nt += TILE_STEP) {
-                const int nt1 = TILE_PAIR && nt + NWAVE < NTy ? nt + NWAVE : -1;
-                f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                float cyu[2][4], cyL[2][4], wy[2];
-                // (not the first backward phase: cyL is not used; its loads repeat cyu's addresses)
-                const int offL = first ? ge.yu_off[L] : ge.yu_off[i];
-                auto operands = [&] {
-#pragma unroll
-                    for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
-                        const int tile = h == 0 ? nt : nt1;
-                        const int col = tile * 16 + r16;
-                        const int cc = tile >= 0 && col < n ? col : 0;
-                        wy[h] = wyL[first ? cc : 0];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 4 * q + r;
-                            const float *c = ctx + (size_t)(row < rows ? row : 0) * C;
-                            cyu[h][r] = c[ge.yu_off[i] + cc];
-                            cyL[h][r] = c[offL + cc];
-                        }
-                    }
-                };
-                gemm_tiles(delta, ldd, Wt, KB, NTy, nt, nt1, acc[0], acc[1], operands);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int tile = h == 0 ? nt : nt1;
-                    if (tile < 0) continue;
-                    const int col = tile * 16 + r16;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = 4 * q + r;
-                        if (row < rows && col < n) {
-                            const float g_in = first ? cyL[h][r] * wy[h] : gbuf[row * ldY + col];
-                            gbuf[row * ldY + col] = __builtin_fmaf(cyu[h][r], acc[h][r], g_in);
-                        }
-                    }
-                }
-            }
-        }
-        lap(i == 0 ? 11 : 8);
+        if (!bmoved)
+            for (int nt = fc_home_wave_dedy(i, wave); nt < NTy; nt += TILE_STEP) dy_unit(i, nt, false);
         if (i > 0) {   // delta_{i-1} = gate_i * (delta_i Wzu_i^T) * act'(pre_{i-1})
             const int wp = ge.width[i - 1];
             float *zprev = lds + ge.zb_off[i - 1];
             const int ldp = ge.zb_ld[i - 1];
             const float *Wt = a.wpack + ge.w_zu_b[i];
             const int NTp = pad16(wp) / 16;
-            for (int nt = wave; nt < NTp; nt += TILE_STEP) {
-                const int nt1 = TILE_PAIR && nt + NWAVE < NTp ? nt + NWAVE : -1;
-                f4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                float cga[2][4];
+            for (int nt = fc_home_wave(wave); nt < NTp; nt += TILE_STEP) {
+                f4 acc = {0.f, 0.f, 0.f, 0.f}, none = {0.f, 0.f, 0.f, 0.f};
+                float cga[4];
+                const int col = nt * 16 + r16;
                 auto operands = [&] {
-#pragma unroll
-                    for (int h = 0; h < (TILE_PAIR ? 2 : 1); ++h) {
-                        const int tile = h == 0 ? nt : nt1;
-                        const int col = tile * 16 + r16;
-                        const int cc = tile >= 0 && col < wp ? col : 0;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 4 * q + r;
-                            cga[h][r] = ctx[(size_t)(row < rows ? row : 0) * C + ge.gate_off[i] + cc];
-                        }
-                    }
-                };
-                gemm_tiles(delta, ldd, Wt, KB, NTp, nt, nt1, acc[0], acc[1], operands);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int tile = h == 0 ? nt : nt1;
-                    if (tile < 0) continue;
-                    const int col = tile * 16 + r16;
+                    const int cc = col < wp ? col : 0;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int row = 4 * q + r;
-                        float d = 0.f;
-                        if (row < rows && col < wp) {
-                            const float gate = cga[h][r];
-                            const float ga = gate * acc[h][r];
-                            d = ga * (zprev[row * ldp + col] > 0.f ? 1.f : a.alpha);
-                        }
-                        zprev[row * ldp + col] = d;
+                        cga[r] = ctx[(size_t)(row < rows ? row : 0) * C + ge.gate_off[i] + cc];
                     }
+                };
+                gemm_tiles(delta, ldd, Wt, KB, NTp, nt, -1, acc, none, operands);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 4 * q + r;
+                    float d = 0.f;
+                    if (row < rows && col < wp) {
+                        const float gate = cga[r];
+                        const float ga = gate * acc[r];
+                        d = ga * (zprev[row * ldp + col] > 0.f ? 1.f : a.alpha);
+                    }
+                    zprev[row * ldp + col] = d;
                 }
             }
-            lap(9);
-        } else {
-            // E = z_{L-1} . wzu_L + (y * yu_L) . wyu_L + zu_L, one wave per row: on the waves that have no dE/dy tile
-            // in this phase where there are any (n < 256), after the tile otherwise
+        }
+        if (bmoved && i == 0 && deal.dy_mask[0][wv]) dy_unit(0, __builtin_ctz(deal.dy_mask[0][wv]), true);
+        lap(i == 0 ? 10 : 8);
+        if (bmoved && i + 1 < L)     // dE/dy of the layer behind: its delta is a whole interval old
+            for (unsigned m = deal.dy_mask[i + 1][wv]; m; m &= m - 1) dy_unit(i + 1, __builtin_ctz(m), false);
+        if (i == 0) lap(11);
+        if (i == 0) {
+            // E = z_{L-1} . wzu_L + (y * yu_L) . wyu_L + zu_L, a row per wave at a time (two, where the deal gives a wave more
+            // than one): every operand of the pair's first 256 columns is requested before the first fma
             const float *zl = lds + ge.zb_off[L - 1];
             const int ldz = ge.zb_ld[L - 1], wl = ge.width[L - 1];
-            const int busy = NTy < NWAVE ? NTy : NWAVE, idle = NWAVE - busy;
-            const int r0 = idle > 0 ? wave - busy : wave, rstep = idle > 0 ? idle : NWAVE;
-            if (r0 >= 0)
-                for (int r = r0; r < rows; r += rstep) {
-                    const float *c = ctx + (size_t)r * C;
-                    float part = 0.f;
-                    for (int j = lane; j < wl; j += 64) part = __builtin_fmaf(zl[r * ldz + j], wzL[j], part);
-                    for (int j = lane; j < n; j += 64) {
-                        const float yy = ybuf[r * ldY + j] * c[ge.yu_off[L] + j];
-                        part = __builtin_fmaf(yy, wyL[j], part);
-                    }
-                    const float e = wave_sum_f(part) + c[ge.zu_off[L]];
-                    if (lane == 0) a.f[s0 + r] = e;
+            unsigned m = rows > 0 ? deal.e_mask[wv] & ((1u << rows) - 1u) : 0u;
+            while (m) {
+                int rr[2];
+                rr[0] = rr[1] = __builtin_ctz(m);
+                m &= m - 1;
+                const bool two = m != 0;
+                if (two) {
+                    rr[1] = __builtin_ctz(m);
+                    m &= m - 1;
                 }
+                const float *c[2] = {ctx + (size_t)rr[0] * C, ctx + (size_t)rr[1] * C};
+                float part[2] = {0.f, 0.f}, cy[2][4], wyv[4], czL[2];
+                auto y_loads = [&](int j0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = j0 + 64 * k + lane, jc = j < n ? j : 0;
+                        wyv[k] = wyL[jc];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) cy[h][k] = c[h][ge.yu_off[L] + jc];
+                    }
+                };
+                y_loads(0);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) czL[h] = c[h][ge.zu_off[L]];
+                for (int j0 = 0; j0 < wl; j0 += 256) {
+                    float wzv[4], zv[2][4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = j0 + 64 * k + lane, jc = j < wl ? j : 0;
+                        wzv[k] = wzL[jc];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) zv[h][k] = zl[rr[h] * ldz + jc];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h)
+                            part[h] = j0 + 64 * k + lane < wl ? __builtin_fmaf(zv[h][k], wzv[k], part[h]) : part[h];
+                }
+                for (int j0 = 0; j0 < n; j0 += 256) {
+                    if (j0 > 0) y_loads(j0);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int j = j0 + 64 * k + lane, jc = j < n ? j : 0;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const float yy = ybuf[rr[h] * ldY + jc] * cy[h][k];
+                            part[h] = j < n ? __builtin_fmaf(yy, wyv[k], part[h]) : part[h];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float e = wave_sum_f(part[h]) + czL[h];
+                    if (lane == 0 && (h == 0 || two)) a.f[s0 + rr[h]] = e;
+                }
+            }
             lap(7);
         }
         __syncthreads();
-        lap(i == 0 ? 12 : 10);
+        lap(i == 0 ? 12 : 9);
     }
 
     const float gscale = a.action_box ? 2.f : 1.f;    // RL/src/icnn.py:152  grad *= 2
-    if (wave < rows)
-        for (int j = lane; j < n; j += 64) a.g[(size_t)(s0 + wave) * n + j] = gscale * gbuf[wave * ldY + j];
+    if (!bmoved) {
+        if (wave < rows)
+            for (int j = lane; j < n; j += 64) a.g[(size_t)(s0 + wave) * n + j] = gscale * gbuf[wave * ldY + j];
+    } else if (gtile >= 0) {   // g = gscale * (dE/dy_0's fma into gbuf): the chain of this wave's tile ends here, behind the barrier
+        const int col = gtile * 16 + r16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * q + r;
+            if (row < rows && col < n)
+                a.g[(size_t)(s0 + row) * n + col] = gscale * __builtin_fmaf(gcyu[r], gacc[r], gbuf[row * ldY + col]);
+        }
+    }
     lap(13);
 }
 

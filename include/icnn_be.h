@@ -1402,6 +1402,24 @@ ICNN_BE_API int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[
 #define ICNN_BE_SHAPE_BIBTEX_KT16 1           /* n = 159, widths 600 / 159 / 1 (the Bibsonomy net), up to 15 slots, not grouped */
 #define ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED 2   /* the same net, 16..32 slots, the dual phase in groups */
 ICNN_BE_API int icnn_be_debug_shape_instance(const icnn_be_fc_model *model, const icnn_be_state *st);
+/*
+ * The deal of one tile evaluation of this model (additive to ABI 12): which of the workgroup's 16 waves runs which unit in which
+ * barrier interval, as the tile kernels read it (fc_deal, be_picnn_fc_dev.h; the same for every kernel around fc_fg_tile and for
+ * the shape instances).  With L = n_layers - 1 hidden layers an evaluation has the intervals 0 .. L-1 (forward layers 0 .. L-1),
+ * L .. 2L-1 (backward layers L-1 .. 0) and 2L (behind the last barrier).  One record of six ints per unit:
+ *   { kind, layer, tile, interval, wave, interval in which the unit's result is written }
+ * kind ICNN_BE_UNIT_FWD_Y: tile `tile` of (y * yu_layer) Wyu_layer; FWD_Z: the same accumulator continued with
+ * (z_{layer-1} gate_layer) Wzu_layer (layer >= 1); DELTA: delta_layer Wzu_layer^T (layer >= 1); DEDY: delta_layer Wyu_layer^T,
+ * added into the gradient (the last field is 2L where the accumulator crosses the last barrier and g is stored from it);
+ * E: energy row `tile` of the 16.  Returns the number of records, writing the first `cap` of them (out may be null with cap 0),
+ * or a negative error code for a model icnn_be_fc_check refuses.  Host arithmetic, no GPU needed.
+ */
+#define ICNN_BE_UNIT_FWD_Y 0
+#define ICNN_BE_UNIT_FWD_Z 1
+#define ICNN_BE_UNIT_DELTA 2
+#define ICNN_BE_UNIT_DEDY 3
+#define ICNN_BE_UNIT_E 4
+ICNN_BE_API int icnn_be_debug_fc_deal(const icnn_be_fc_model *model, int *out, int cap);
 
 /* ---- the DDPG agent: fused actor-critic step, EMA targets, act (be_ddpg.hip, additive to ABI 12) ---- */
 
