@@ -23,7 +23,6 @@ import torch
 
 from . import _lib
 from . import flat as _flat
-from .train import _Trainer
 
 LAYERS = ("conv1", "conv2", "conv3", "up1", "up2", "up3", "up4")
 
@@ -144,91 +143,33 @@ class FCNModel:
         return out
 
 
-class FCNTrainer(_flat.FlatTrainer, _Trainer):
+class FCNTrainer(_flat.SupervisedTrainer):
     """model, Adam's state and the whole training step at one batch size.  step() returns the loss at the weights the step
     began with: the trainer's 0-d float32 device tensor `loss`; yhat [B, H * W] is that of the same forward.  eval_batch = E
     also allocates the script's test phase (baseline.py:102-108): evaluate(x, t) runs forward and loss on exactly E images
     into eval_loss and y_eval and changes nothing else.  grad holds the last step's flat gradient, work_view(name) the pieces of
     the workspace (_lib.FCN_WORK).  x is [B, H, W, 1] and t [B, H * W], the buffers of ConvGDTrainer."""
+    _entry, _key, _work_names, _step_ints = "icnn_be_fcn_", "fcn", _lib.FCN_WORK, _lib.FCN_STEP_INTS
+    _fields = ("x", "t", "yhat", "loss")
+    _eval_fields = ("x_eval", "t_eval", "y_eval", "eval_loss")
+    _extra = ("lr", "pixel_scale")
+    _layout, _dims = staticmethod(layout), staticmethod(_dims)
 
     def __init__(self, model, batch, lr=1e-4, pixel_scale=255.0, eval_batch=None):
         if not isinstance(model, FCNModel):
             raise TypeError("fcn.FCNTrainer serves fcn.FCNModel, got %s" % type(model).__name__)
-        self.batch = int(batch)
-        if not 1 <= self.batch <= _lib.FCN_MAX_BATCH:
+        if not 1 <= int(batch) <= _lib.FCN_MAX_BATCH:
             raise ValueError("batch must lie in [1, %d], got %r" % (_lib.FCN_MAX_BATCH, batch))
-        self.eval_batch = None if eval_batch is None else int(eval_batch)
-        if self.eval_batch is not None and not 1 <= self.eval_batch <= _lib.FCN_MAX_EVAL_BATCH:
-            raise ValueError("eval_batch must lie in [1, %d], got %d" % (_lib.FCN_MAX_EVAL_BATCH, self.eval_batch))
+        eval_batch = _flat._eval_batch(eval_batch, most=_lib.FCN_MAX_EVAL_BATCH)
         if not pixel_scale > 0:
             raise ValueError("pixel_scale must be positive, got %r" % (pixel_scale,))
-        self.model, self.spec, self.device, self.lib = model, model.spec, model.device, model._lib
         self.lr, self.pixel_scale = float(lr), float(pixel_scale)
-        B, n, dev, f32 = self.batch, model.n, self.device, torch.float32
-        H, W = self.spec.H, self.spec.W
-        self.x = torch.zeros(B, H, W, 1, dtype=f32, device=dev)
-        self.t = torch.zeros(B, H * W, dtype=f32, device=dev)
-        self.yhat = torch.zeros(B, H * W, dtype=f32, device=dev)
-        self.loss = torch.zeros((), dtype=f32, device=dev)
-        # dicts of flat vectors, as the other flat trainers keep them (checkpoint.py)
-        self.theta = {"fcn": model.theta}
-        self.m = {"fcn": torch.zeros(n, dtype=f32, device=dev)}
-        self.v = {"fcn": torch.zeros(n, dtype=f32, device=dev)}
-        self.grad = torch.zeros(n, dtype=f32, device=dev)
-        self.step_count = torch.zeros(_lib.FCN_STEP_INTS, dtype=torch.int32, device=dev)
-        self.work = model.work(B)
-        self.work_offsets = self._offsets(B)
-        self._args = self._describe(B, self.work, self.x, self.t, self.yhat, self.loss)
-        self.eval_loss = self.y_eval = None
-        if self.eval_batch is not None:
-            E = self.eval_batch
-            self.x_eval = torch.zeros(E, H, W, 1, dtype=f32, device=dev)
-            self.t_eval = torch.zeros(E, H * W, dtype=f32, device=dev)
-            self.y_eval = torch.zeros(E, H * W, dtype=f32, device=dev)
-            self.eval_loss = torch.zeros((), dtype=f32, device=dev)
-            self.eval_work = model.work(E)
-            self._eval_args = self._describe(E, self.eval_work, self.x_eval, self.t_eval, self.y_eval, self.eval_loss)
+        super().__init__(model, int(batch), eval_batch)
 
-    def _offsets(self, batch):
-        return self._work_offsets("icnn_be_fcn_work_offsets", _lib.FCN_WORK, batch, *_dims(self.spec))
-
-    def _describe(self, batch, work, x, t, yhat, loss):
-        a = self.model.args(batch, work)
-        a.x, a.t, a.yhat, a.loss = (b.data_ptr() for b in (x, t, yhat, loss))
-        a.m, a.v, a.grad, a.step = self.m["fcn"].data_ptr(), self.v["fcn"].data_ptr(), self.grad.data_ptr(), self.step_count.data_ptr()
-        a.lr, a.pixel_scale = self.lr, self.pixel_scale
-        return a
-
-    # ---- the step and its parts ----
-    def forward(self):
-        """icnn_be_fcn_forward alone on the trainer's buffers: the activations, yhat, loss, d yhat and up3's delta"""
-        self._call("icnn_be_fcn_forward")
-
-    def backward(self):
-        self._call("icnn_be_fcn_backward")
-
-    def grads(self):
-        self._call("icnn_be_fcn_grads")
-
-    def update(self):
-        self._call("icnn_be_fcn_update")
-
-    def step(self, x=None, t=None) -> torch.Tensor:
-        """One step on (x [B, H, W], t [B, H * W]); None keeps what the buffers hold (graph replay)."""
-        self._put(self.x, x)
-        self._put(self.t, t)
-        self._call("icnn_be_fcn_step")
-        return self.loss
-
-    def evaluate(self, x=None, t=None) -> torch.Tensor:
-        """The test phase on exactly eval_batch images: eval_loss (returned) and y_eval.  Nothing of the model, the optimiser
-        or the training step's results is written.  No host wait (capturable)."""
-        if self.eval_batch is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        self._put(self.x_eval, x)
-        self._put(self.t_eval, t)
-        self._call("icnn_be_fcn_eval", self._eval_args)
-        return self.eval_loss
+    def _buffers(self, rows):
+        f32, dev, H, W = torch.float32, self.device, self.spec.H, self.spec.W
+        return (torch.zeros(rows, H, W, 1, dtype=f32, device=dev), torch.zeros(rows, H * W, dtype=f32, device=dev),
+                torch.zeros(rows, H * W, dtype=f32, device=dev), torch.zeros((), dtype=f32, device=dev))
 
     def piece_shape(self, name, batch):
         """the shape of a piece of the workspace that holds images: "h<i>", "dz<i>" [B, h, w, k], "dy" [B, H, W]"""
@@ -250,23 +191,3 @@ class FCNTrainer(_flat.FlatTrainer, _Trainer):
             return work[at:min(later) if later else work.numel()]
         shape = self.piece_shape(name, B)
         return work[at:at + int(np.prod(shape))].view(shape)
-
-    # ---- parameters ----
-    @property
-    def t_steps(self) -> int:
-        """updates done (synchronises)"""
-        return int(self.step_count[0].item())
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        """live views of the variables inside theta"""
-        return _flat.views(layout(self.spec), self.model.theta)
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.model.host_params()
-
-    def load(self, params, reset=True):
-        """Copy a dict of torch-named arrays (or a flat vector) into the existing theta.  reset: Adam's moments and the step
-        count back to zero.  Synchronises."""
-        self.model.load(params)
-        if reset:
-            self._reset_adam()

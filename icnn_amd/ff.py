@@ -20,7 +20,6 @@ import torch
 
 from . import _lib
 from . import flat as _flat
-from .train import _Trainer, _TrainF1
 
 BN_EPS = 1e-5
 
@@ -151,100 +150,37 @@ class FFModel:
         return out
 
 
-class FFTrainer(_flat.FlatTrainer, _Trainer, _TrainF1):
+class FFTrainer(_flat.SupervisedTrainer, _flat._TrainF1):
     """model, Adam's state and the whole training step at one batch size.  step() returns the loss at the weights the step
     began with: the trainer's 0-d float32 device tensor `loss`; yhat [B, n_labels] and f1_tallies [B, 3] (tp, fp, fn per
     example; macro_f1() reads them) are those of the same forward.  eval_batch = E also allocates the script's test phase
     (ff.py:187-196): evaluate(x, true_y) runs inference mode on exactly E samples into eval_loss, eval_yhat, eval_f1_tallies and
     changes nothing else.  grad holds the last step's flat gradient, work_view(name) the pieces of the workspace
-    (_lib.FF_WORK)."""
+    (_lib.FF_WORK).  x is [B, n_features] and true_y [B, n_labels]."""
     _no_tallies = "the feed-forward trainer always keeps its tallies"
+    _entry, _key, _work_names, _step_ints = "icnn_be_ff_", "ff", _lib.FF_WORK, _lib.FF_STEP_INTS
+    _fields = ("x", "true_y", "yhat", "loss", "f1_tallies")
+    _eval_fields = ("x_eval", "true_y_eval", "eval_yhat", "eval_loss", "eval_f1_tallies")
+    _extra = ("lr",)
+    _layout, _dims = staticmethod(layout), staticmethod(_dims)
 
     def __init__(self, model, batch, lr=1e-3, eval_batch=None):
         if not isinstance(model, FFModel):
             raise TypeError("ff.FFTrainer serves ff.FFModel, got %s" % type(model).__name__)
-        self.batch = int(batch)
-        if not 2 <= self.batch <= _lib.FF_MAX_BATCH:
+        if not 2 <= int(batch) <= _lib.FF_MAX_BATCH:
             raise ValueError("batch must lie in [2, %d], got %r" % (_lib.FF_MAX_BATCH, batch))
-        self.eval_batch = None if eval_batch is None else int(eval_batch)
-        if self.eval_batch is not None and self.eval_batch < 1:
-            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
-        self.model, self.spec, self.device, self.lib = model, model.spec, model.device, model._lib
         self.lr = float(lr)
-        B, n, dev, f32 = self.batch, model.n, self.device, torch.float32
-        self.x = torch.zeros(B, self.spec.n_features, dtype=f32, device=dev)
-        self.true_y = torch.zeros(B, self.spec.n_labels, dtype=f32, device=dev)
-        self.yhat = torch.zeros(B, self.spec.n_labels, dtype=f32, device=dev)
-        self.loss = torch.zeros((), dtype=f32, device=dev)
-        self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev)
-        # dicts of flat vectors, as the other flat trainers keep them (checkpoint.py)
-        self.theta = {"ff": model.theta}
-        self.m = {"ff": torch.zeros(n, dtype=f32, device=dev)}
-        self.v = {"ff": torch.zeros(n, dtype=f32, device=dev)}
-        self.grad = torch.zeros(n, dtype=f32, device=dev)
-        self.step_count = torch.zeros(_lib.FF_STEP_INTS, dtype=torch.int32, device=dev)
-        self.work = model.work(B)
-        self.work_offsets = self._offsets(B)
-        self._args = self._describe(B, self.work, self.x, self.true_y, self.yhat, self.loss, self.f1_tallies)
-        self.eval_loss = self.eval_yhat = self.eval_f1_tallies = None
-        if self.eval_batch is not None:
-            E = self.eval_batch
-            self.x_eval = torch.zeros(E, self.spec.n_features, dtype=f32, device=dev)
-            self.true_y_eval = torch.zeros(E, self.spec.n_labels, dtype=f32, device=dev)
-            self.eval_yhat = torch.zeros(E, self.spec.n_labels, dtype=f32, device=dev)
-            self.eval_loss = torch.zeros((), dtype=f32, device=dev)
-            self.eval_f1_tallies = torch.zeros(E, 3, dtype=torch.int32, device=dev)
-            self.eval_work = model.work(E)
-            self._eval_args = self._describe(E, self.eval_work, self.x_eval, self.true_y_eval, self.eval_yhat, self.eval_loss,
-                                             self.eval_f1_tallies)
+        super().__init__(model, int(batch), _flat._eval_batch(eval_batch))
 
-    def _offsets(self, batch):
-        return self._work_offsets("icnn_be_ff_work_offsets", _lib.FF_WORK, batch, *_dims(self.spec))
+    def _buffers(self, rows):
+        f32, dev, spec = torch.float32, self.device, self.spec
+        return (torch.zeros(rows, spec.n_features, dtype=f32, device=dev), torch.zeros(rows, spec.n_labels, dtype=f32, device=dev),
+                torch.zeros(rows, spec.n_labels, dtype=f32, device=dev), torch.zeros((), dtype=f32, device=dev),
+                torch.zeros(rows, 3, dtype=torch.int32, device=dev))
 
-    def _describe(self, batch, work, x, true_y, yhat, loss, tallies):
-        a = self.model.args(batch, work)
-        a.x, a.true_y, a.yhat, a.loss, a.f1_tallies = (t.data_ptr() for t in (x, true_y, yhat, loss, tallies))
-        a.m, a.v, a.grad, a.step = self.m["ff"].data_ptr(), self.v["ff"].data_ptr(), self.grad.data_ptr(), self.step_count.data_ptr()
-        a.lr = self.lr
-        return a
-
-    # ---- the step and its parts ----
     def forward(self, bn="batch"):
         """icnn_be_ff_forward alone on the trainer's buffers: the workspace, yhat, loss, f1_tallies"""
         _lib.check(self.lib.icnn_be_ff_forward(C.byref(self._args), _lib.BN_MODE[bn], self._stream()), "icnn_be_ff_forward")
-
-    def backward(self):
-        self._call("icnn_be_ff_backward")
-
-    def grads(self):
-        self._call("icnn_be_ff_grads")
-
-    def update(self):
-        self._call("icnn_be_ff_update")
-
-    def step(self, x=None, true_y=None) -> torch.Tensor:
-        """One step on (x [B, n_features], true_y [B, n_labels]); None keeps what the buffers hold (graph replay)."""
-        self._put(self.x, x)
-        self._put(self.true_y, true_y)
-        self._call("icnn_be_ff_step")
-        return self.loss
-
-    def evaluate(self, x=None, true_y=None) -> torch.Tensor:
-        """The test phase on exactly eval_batch samples in inference mode: eval_loss (returned), eval_yhat, eval_f1_tallies.
-        Nothing of the model, the optimiser or the training step's results is written.  No host wait (capturable)."""
-        if self.eval_batch is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        self._put(self.x_eval, x)
-        self._put(self.true_y_eval, true_y)
-        self._call("icnn_be_ff_eval", self._eval_args)
-        return self.eval_loss
-
-    def eval_macro_f1(self) -> float:
-        """the test F1 of the last evaluate() (util.macroF1; one wait)"""
-        from .train import macro_f1
-        if self.eval_f1_tallies is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        return macro_f1(self.eval_f1_tallies)
 
     def work_view(self, name, eval=False) -> torch.Tensor:
         """a live view of one piece of the workspace (of evaluate()'s with eval=True): "a<i>", "h<i>", "dz<i>" [B, width],
@@ -258,23 +194,3 @@ class FFTrainer(_flat.FlatTrainer, _Trainer, _TrainF1):
             width = self.spec.layer_sizes[int(name[-1])]
             rows = 2 if name.startswith("stat") else B
         return work[at:at + rows * width].view(rows, width)
-
-    # ---- parameters ----
-    @property
-    def t_steps(self) -> int:
-        """updates done (synchronises)"""
-        return int(self.step_count[0].item())
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        """live views of the variables inside theta"""
-        return _flat.views(layout(self.spec), self.model.theta)
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.model.host_params()
-
-    def load(self, params, reset=True):
-        """Copy a dict of named arrays (or a flat vector) into the existing theta.  reset: Adam's moments and the step count
-        back to zero.  The moving statistics stay.  Synchronises."""
-        self.model.load(params)
-        if reset:
-            self._reset_adam()

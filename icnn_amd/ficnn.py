@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, gd, picnn, train
+from .flat import _positive, _Trainer
 from .picnn import _DeviceWeights, _host_ptr, _trunc_normal
 
 
@@ -191,7 +192,7 @@ def surrogate_grad(model: FICNNModel, x: torch.Tensor, row_offset: torch.Tensor,
     return train.surrogate_grad(model, x, rows, row_offset=row_offset, F_rows=F_rows, flat=flat)
 
 
-class GDTrainer(train._Trainer):
+class GDTrainer(_Trainer):
     """The synthetic-cls training step (icnn.py:117-139, :189-194) at one batch size, all of it enqueued on the device:
     context, gd.solve(trajectory=True) from y0 = 0.5, the loss mean((y_K - t)^2) over B n and its adjoint
     ybar = float32(1/(B n)) (2 (y_K - t)) (TensorFlow's _MeanGrad / _SquareGrad), train.unrolled_grad, then DeviceAdam.step
@@ -201,7 +202,7 @@ class GDTrainer(train._Trainer):
 
     def __init__(self, model: FICNNModel, batch: int, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5):
         self.model, self.spec, self.device = model, model.spec, model.device
-        self.batch = train._positive("batch", batch)
+        self.batch = _positive("batch", batch)
         self.n_iter, self.lr, self.momentum, self.y0 = int(n_iter), float(lr), float(momentum), float(y0)
         self.opt = train.DeviceAdam(model, lr=adam_lr)
         B, dev = self.batch, self.device

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, picnn, rl_adam, rl_bundle, train
+from .flat import _positive
 
 OPTS = ("adam", "bundle_entropy")        # FLAGS.icnn_opt (RL/src/icnn.py:39-44)
 
@@ -63,7 +64,7 @@ class CriticTrainer:
         if not 0.0 <= tau <= 1.0:
             raise ValueError("tau must lie in [0, 1], got %r" % (tau,))
         self.critic, self.target, self.spec, self.device = critic, target, critic.spec, critic.device
-        self.batch = train._positive("batch", batch)
+        self.batch = _positive("batch", batch)
         self.lr, self.tau, self.discount, self.l2norm, self.wd = float(lr), float(tau), float(discount), float(l2norm), float(wd)
         self.lib = _lib.load()
         self.opt = train.DeviceAdam(critic, lr)

@@ -16,7 +16,8 @@
                     target network, rl_train.CriticTrainer).
 
     _Trainer        what the trainers below and ficnn.GDTrainer share round their step(): batch buffers, context buffers, the
-                    start point (_start_point), the views of the optimiser's theta.
+                    start point (_start_point), the test phase's checks, the views of the optimiser's theta.  It lives in
+                    icnn_amd.flat with the argument checks and macro_f1; the names stay importable from here.
 
     BundleTrainer   one whole iteration of the bundle-entropy training loops without a host wait (capturable): context,
                     fused solve, FeedPlan (be_train_bundle.hip: row offsets, row count, fg evaluations, status OR, loss, F1
@@ -29,23 +30,14 @@
                     back-optimisation scripts, multi-label-cls/icnn-back.py, completion/icnn.back.py): one surrogate_grad
                     over the trajectory's rows with c = 0 and v = coefficient x dL/dy_K.
 
-    GDTrainer       one whole back-optimisation training step of an FC PICNN without a host wait (capturable): context,
-                    gd.solve with its trajectory, the fused feed of be_train_gd.hip (icnn_be_gd_feed: loss, dL/dy_K times
-                    the step coefficients, row offsets, F1 tallies), surrogate_grad, DeviceAdam.step.
+    UnrolledGDTrainer  one whole back-optimisation training step without a host wait (capturable): context, gd.solve with its
+                    trajectory, a fused feed of be_train_gd.hip (loss, dL/dy_K times the step coefficients, row offsets),
+                    surrogate_grad, DeviceAdam.step; and the scripts' test phase as evaluate().  GDTrainer is that step on an
+                    FC PICNN (icnn_be_gd_feed with its F1 tallies, icnn_be_gd_eval), ConvGDTrainer on the
+                    completion model (completion/icnn.back.py:131-165, 210-254) with the loss mean((255 (y_K - t))^2) and
+                    its feed on a two-dimensional grid (icnn_be_gd_feed_px).
 
-    ConvGDTrainer   the same step for the completion model (completion/icnn.back.py:131-165, 210-254) on a picnn.ConvModel,
-                    with the loss mean((255 (y_K - t))^2) and its feed on a two-dimensional grid (icnn_be_gd_feed_px), and
-                    the script's test phase as evaluate().
-
-    BestKeeper      the scripts' "save when the score is better" on the device: icnn_be_keep_best (and icnn_be_macro_f1 for a
-                    score formed from F1 tallies) sets a gate, icnn_be_gated_copy snapshots theta, the arena and the BatchNorm
-                    statistics behind it (be_train_epoch.hip; DESIGN.md §20).  GDTrainer's test phase, evaluate(), is there too;
-                    icnn_amd.checkpoint saves and resumes the trainers.
-
-    DeviceDataset   the training arrays on the device and the scripts' `I = npr.randint(nTrain, size=batch); trainX[I],
-                    trainY[I]` as one launch (icnn_be_dataset_draw, be_train_data.hip); StepLog, the per-iteration scalars of
-                    train.csv in a device ring (icnn_be_log_row); EpochRunner, [draw, step, log] x k captured once and replayed
-                    (DESIGN.md §21).
+    BestKeeper, DeviceDataset, StepLog, EpochRunner  the epoch level (icnn_amd.epoch), re-exported here.
 
 One training step of the multi-label experiment:
     solve -> bundle_entropy.implicit_feed -> surrogate_grad(flat=True) -> DeviceAdam.step
@@ -60,8 +52,9 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from .bundle_entropy import ImplicitFeed
+from . import _lib, gd
+from .bundle_entropy import FusedSolver, ImplicitFeed
+from .flat import _eval_batch, _non_negative, _positive, _start_point, _ticket, _Trainer, _TrainF1, macro_f1  # noqa: F401
 from .picnn import ConvModel, FCModel
 
 
@@ -186,20 +179,6 @@ def surrogate_work_floats(model, batch, rows, dev=False) -> int:
     return n_work
 
 
-def macro_f1(tallies) -> float:
-    """util.macroF1 of the reference from per-example tallies [B, 3] (tp, fp, fn over the labels of each example, prediction
-    y >= 0.5): that function transposes both arrays before sklearn's f1_score(average='macro'), so sklearn's classes are the
-    EXAMPLES and the macro average runs over them -- mean over examples of 2 tp / (2 tp + fp + fn), 0 where the denominator
-    is 0 (an example without a positive label or prediction).  Host arithmetic; a device tensor is copied (one wait)."""
-    t = tallies.detach().cpu().numpy() if torch.is_tensor(tallies) else np.asarray(tallies)
-    t = t.reshape(-1, 3).astype(np.float64)
-    if t.shape[0] == 0:
-        return 0.0
-    den = 2.0 * t[:, 0] + t[:, 1] + t[:, 2]
-    f1 = np.where(den > 0, 2.0 * t[:, 0] / np.where(den > 0, den, 1.0), 0.0)
-    return float(f1.mean())
-
-
 _COEF_CACHE: Dict[tuple, torch.Tensor] = {}
 
 
@@ -210,8 +189,7 @@ def unrolled_coefficients(n_iter, lr, momentum, device) -> torch.Tensor:
     key = (K, float(lr), float(momentum), str(device))
     coef = _COEF_CACHE.get(key)
     if coef is None:
-        from .gd import coefficients
-        coef = torch.from_numpy(coefficients(K, lr, momentum)).to(device).view(1, K, 1)
+        coef = torch.from_numpy(gd.coefficients(K, lr, momentum)).to(device).view(1, K, 1)
         _COEF_CACHE[key] = coef
     return coef
 
@@ -472,83 +450,6 @@ class DeviceAdam(_ArenaOwner):
 
 
 # --------------------------------------------------------------------------------------------- #
-# What the trainers share round their step(): argument checks, buffers, the start point, the optimiser's views
-# --------------------------------------------------------------------------------------------- #
-def _positive(name, value) -> int:
-    value = int(value)
-    if value < 1:
-        raise ValueError("%s must be >= 1" % name)
-    return value
-
-
-def _non_negative(name, value) -> int:
-    value = int(value)
-    if value < 0:
-        raise ValueError("%s must be >= 0, got %d" % (name, value))
-    return value
-
-
-def _ticket(n_bytes, device) -> torch.Tensor:
-    """the workspace of a feed kernel, zeroed once: it holds the ticket its blocks count themselves with"""
-    return torch.zeros((int(n_bytes) + 7) // 8, dtype=torch.float64, device=device)
-
-
-def _start_point(y0, n, batch, eval_batch, device):
-    """A trainer's start point y0 -- a scalar, an [n] row, an image [H, W, 1] or a [B, n] array ([B, H, W, 1] too) -- as a
-    Python float (a scalar) or a float64 tensor on `device` that expands to [rows, n]: [n], or [B, n], which serves the
-    test phase only when eval_batch == batch."""
-    y0 = torch.as_tensor(y0, dtype=torch.float64)
-    if y0.dim() == 0:
-        return float(y0)
-    y0 = y0.to(device)
-    if y0.dim() >= 3 and y0.numel() % n == 0:           # an image, or one per sample
-        y0 = y0.reshape(-1, n)
-    if y0.dim() == 2 and y0.shape[0] == 1:
-        y0 = y0[0]
-    if y0.dim() > 2 or y0.shape[-1] != n or (y0.dim() == 2 and y0.shape[0] != batch):
-        raise ValueError("y0 is a scalar, an [n] row, an [H, W, 1] image or a [B, n] array (n = %d, B = %d), got %s"
-                         % (n, batch, tuple(y0.shape)))
-    if eval_batch is not None and y0.dim() == 2 and eval_batch != batch:
-        raise ValueError("a per-sample y0 [B, n] serves evaluate() only when eval_batch == batch")
-    return y0
-
-
-class _Trainer:
-    """The scaffolding of a trainer that owns `model`, `device` and the DeviceAdam `opt`; its pipeline is its own step()."""
-
-    def _put(self, buf, value):
-        """copy a batch into its preallocated buffer; None keeps what the buffer holds (graph replay)"""
-        if value is not None:
-            buf.copy_(torch.as_tensor(value).to(self.device, buf.dtype).reshape(buf.shape))
-
-    def _context_buffers(self, batch):
-        """(ctx, work) of model.context(x, out=, work=) at this batch size"""
-        return (torch.empty(batch, self.spec.ctx_width, dtype=torch.float32, device=self.device),
-                torch.empty(self.model.context_work_floats(batch), dtype=torch.float32, device=self.device))
-
-    @property
-    def t_steps(self) -> int:
-        return self.opt.t
-
-    def params(self) -> Dict[str, torch.Tensor]:
-        return self.opt.params()
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        return self.opt.host_params()
-
-
-class _TrainF1:
-    """macro_f1() of the two trainers that keep the per-example tallies f1_tallies; where they were not asked for it is
-    None, and _no_tallies says when they exist."""
-
-    def macro_f1(self) -> float:
-        """the train F1 of the last step (util.macroF1; one wait)"""
-        if self.f1_tallies is None:
-            raise ValueError(self._no_tallies)
-        return macro_f1(self.f1_tallies)
-
-
-# --------------------------------------------------------------------------------------------- #
 # The bundle-entropy training step as one device step
 # --------------------------------------------------------------------------------------------- #
 class FeedPlan:
@@ -642,10 +543,10 @@ class BundleTrainer(_Trainer, _TrainF1):
     # what each script trains and tests with: (the model it serves, its loss, the BatchNorm mode of its test phase)
     _SCRIPTS = ((FCModel, "xent", "batch"), (ConvModel, "mse", "moving"))
     _no_tallies = "F1 tallies exist for loss 'xent' only"
+    _no_eval_tallies = "F1 tallies exist for loss 'xent' and a trainer constructed with eval_batch only"
 
     def __init__(self, model, batch, n_iter=10, loss="xent", variant="pdipm", lr=1e-3, y0=0.5, eval_batch=None, eval_bn=None,
                  skip_on_error=False):
-        from .bundle_entropy import FusedSolver
         if loss not in _lib.LOSS:
             raise ValueError("loss must be 'xent' or 'mse', got %r" % (loss,))
         script = [s for s in self._SCRIPTS if isinstance(model, s[0])]
@@ -657,9 +558,7 @@ class BundleTrainer(_Trainer, _TrainF1):
         if variant not in ("dual", "pdipm"):
             raise ValueError("variant must be 'dual' or 'pdipm' (the rl variant does not record n_iters), got %r" % (variant,))
         self.batch = _positive("batch", batch)
-        self.eval_batch = None if eval_batch is None else int(eval_batch)
-        if self.eval_batch is not None and self.eval_batch < 1:
-            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
+        self.eval_batch = _eval_batch(eval_batch)
         if eval_bn is None:
             eval_bn = script_bn
         if eval_bn not in _lib.BN_MODE:
@@ -761,20 +660,13 @@ class BundleTrainer(_Trainer, _TrainF1):
         """The test phase on exactly eval_batch samples (x, true_y shaped as for step; None keeps the previous ones): the loss
         at y* of a solve from y0 with the context in eval_bn mode, a float64 device scalar (eval_loss); y_eval keeps y* and
         eval_f1_tallies ("xent") the tallies.  Nothing is updated and no statistic is folded.  No host wait (capturable)."""
-        if self.eval_batch is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
+        self._require_eval()
         self._put(self.x_eval, x)
         self._put(self.true_y_eval, true_y)
         self.model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
         self.eval_solver.solve(self.ctx_eval, self.y0_eval if self._y0_scalar is None else self._y0_scalar)
         self.eval_plan.run(self.true_y_eval)
         return self.eval_loss
-
-    def eval_macro_f1(self) -> float:
-        """the test F1 of the last evaluate() (util.macroF1; "xent" only; one wait)"""
-        if self.eval_f1_tallies is None:
-            raise ValueError("F1 tallies exist for loss 'xent' and a trainer constructed with eval_batch only")
-        return macro_f1(self.eval_f1_tallies)
 
     def raise_on_error(self):
         """BundleResult.raise_on_error from status_or (reads it: one wait).  The OR names no sample."""
@@ -791,9 +683,83 @@ class BundleTrainer(_Trainer, _TrainF1):
 
 
 # --------------------------------------------------------------------------------------------- #
-# The back-optimisation training step of the FC PICNNs as one device step
+# The back-optimisation training step and test phase as one device step each
 # --------------------------------------------------------------------------------------------- #
-class GDTrainer(_Trainer, _TrainF1):
+class UnrolledGDTrainer(_Trainer):
+    """What GDTrainer and ConvGDTrainer share: the buffers of a back-optimisation step at one batch size, and
+
+        step()      context (batch statistics) -> gd.solve(trajectory=True) from the start point -> self._feed(traj): the
+                    loss, the rows v = coefficient x dL/dy_K, c = 0, row_offset -> surrogate_grad over the B K trajectory
+                    rows -> DeviceAdam.step
+        evaluate()  context in self.eval_bn mode -> gd.solve without a trajectory -> self._eval_feed(): eval_loss
+
+    all enqueued on the current stream without a host wait.  Constructing one ATTACHES the model to its DeviceAdam and
+    allocates every buffer (x is model.x_shape per sample, t [B, n] float32).  A subclass supplies the two feed entries, the
+    bytes of their workspaces (_feed_work_bytes), the start point of either phase (_start) and eval_bn."""
+
+    def __init__(self, model, batch, n_iter, lr, momentum, adam_lr, bn_updates, eval_batch):
+        self.batch, self.n_iter = int(batch), int(n_iter)
+        if self.batch < 1 or self.n_iter < 1:
+            raise ValueError("batch and n_iter must be >= 1")
+        self.bn_updates = _non_negative("bn_updates", bn_updates)
+        self.eval_batch = _eval_batch(eval_batch)
+        self.model, self.spec, self.device = model, model.spec, model.device
+        self.lr, self.momentum = float(lr), float(momentum)
+        self.opt = DeviceAdam(model, lr=adam_lr)
+        B, K, E, n, dev = self.batch, self.n_iter, self.eval_batch, self.spec.n_labels, self.device
+        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
+        self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
+        self.scale = float(np.float32(1.0) / np.float32(B * n))
+        self.x = torch.zeros((B,) + model.x_shape, dtype=torch.float32, device=dev)
+        self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.y = None                                   # gd.solve's own y_K tensor, from the first step on
+        self.ctx, self._ctx_work = self._context_buffers(B)
+        self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
+        self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
+        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        self._feed_work = _ticket(self._feed_work_bytes(B, False), dev)
+        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
+        self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
+        self.y_eval = self.eval_loss = None
+        if E is not None:
+            self.x_eval = torch.zeros((E,) + model.x_shape, dtype=torch.float32, device=dev)
+            self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
+            self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
+            self._feed_work_eval = _ticket(self._feed_work_bytes(E, True), dev)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def step(self, x=None, t=None) -> torch.Tensor:
+        """One step on (x [B, *model.x_shape] -- a ConvModel's already h-flipped --, t [B, n] or images); None keeps the batch
+        of the previous call (graph replay).  Returns the loss before the update, a float32 device scalar."""
+        self._put(self.x, x)
+        self._put(self.t, t)
+        model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
+        model.context(self.x, out=self.ctx, work=self._ctx_work)
+        self.y, traj, _ = gd.solve(model, self.ctx, self._start(False), K, self.lr, self.momentum, trajectory=True)
+        self._feed(traj)
+        surrogate_grad(model, self.x, (traj.view(B * K, n), self.v_rows, self.c_rows), row_offset=self.row_offset,
+                       bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
+        self.opt.step(self.grad)
+        return self.loss
+
+    def evaluate(self, x=None, t=None) -> torch.Tensor:
+        """The test phase on exactly eval_batch samples (x, t shaped as for step; None keeps the previous ones): the loss at
+        y_K of the unrolled GD from the start point with the context in eval_bn mode, a float32 device scalar (eval_loss);
+        y_eval keeps y_K.  Nothing is updated and no statistic is folded.  No host wait (capturable)."""
+        self._require_eval()
+        self._put(self.x_eval, x)
+        self._put(self.t_eval, t)
+        self.model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
+        self.y_eval = gd.solve(self.model, self.ctx_eval, self._start(True), self.n_iter, self.lr, self.momentum)[0]
+        self._eval_feed()
+        return self.eval_loss
+
+
+class GDTrainer(UnrolledGDTrainer, _TrainF1):
     """One training step of the back-optimisation scripts on a picnn.FCModel (synthetic-cls/icnn.py:117-139 with
     picnn.synthetic_spec(); multi-label-cls/icnn-back.py with the loss mean((y_K - t)^2)) at one batch size, all of it enqueued
     on the current stream without a host wait, so a step can be captured in a CUDA graph:
@@ -820,102 +786,46 @@ class GDTrainer(_Trainer, _TrainF1):
     result tensor of the training step.  eval_bn=None is what the script does at test time: "moving" (it sets
     is_training(False), :210); a model without BatchNorm ignores it."""
     _no_tallies = "F1 tallies are kept with f1=True only"
+    _no_eval_tallies = "F1 tallies exist for a trainer constructed with f1=True and eval_batch only"
 
     def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, bn_updates=0, f1=False,
                  eval_batch=None, eval_bn=None):
         if not isinstance(model, FCModel):
             name = model.__name__ if isinstance(model, type) else type(model).__name__
             raise TypeError("train.GDTrainer serves picnn.FCModel (ficnn.GDTrainer trains a FICNNModel), got %s" % name)
-        self.batch, self.n_iter = int(batch), int(n_iter)
-        if self.batch < 1 or self.n_iter < 1:
-            raise ValueError("batch and n_iter must be >= 1")
-        self.bn_updates = _non_negative("bn_updates", bn_updates)
-        self.eval_batch = None if eval_batch is None else int(eval_batch)
-        if self.eval_batch is not None and self.eval_batch < 1:
-            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
         if eval_bn is None:
             eval_bn = "moving"
         if eval_bn not in _lib.BN_MODE:
             raise ValueError("eval_bn must be 'batch' or 'moving', got %r" % (eval_bn,))
+        super().__init__(model, batch, n_iter, lr, momentum, adam_lr, bn_updates, eval_batch)
         self.eval_bn = eval_bn if model.has_bn else "batch"         # without BatchNorm there is one context
-        self.model, self.spec, self.device = model, model.spec, model.device
-        self.lr, self.momentum, self.y0 = float(lr), float(momentum), float(y0)
-        self.opt = DeviceAdam(model, lr=adam_lr)
-        B, K, E, n, dev = self.batch, self.n_iter, self.eval_batch, self.spec.n_labels, self.device
-        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
-        self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
-        self.scale = float(np.float32(1.0) / np.float32(B * n))
-        self.x = torch.zeros(B, self.spec.n_features, dtype=torch.float32, device=dev)
-        self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.y = None                                   # gd.solve's own y_K tensor, from the first step on
-        self.ctx, self._ctx_work = self._context_buffers(B)
-        self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
-        self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
-        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        self.y0 = float(y0)
+        B, E, dev = self.batch, self.eval_batch, self.device
         self.f1_tallies = torch.zeros(B, 3, dtype=torch.int32, device=dev) if f1 else None
-        self._feed_work = _ticket(model._lib.icnn_be_gd_feed_work_bytes(B), dev)
-        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
-        self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
-        self.y_eval = self.eval_loss = self.eval_f1_tallies = None
-        if E is not None:
-            self.x_eval = torch.zeros(E, self.spec.n_features, dtype=torch.float32, device=dev)
-            self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
-            self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
-            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
-            self.eval_f1_tallies = torch.zeros(E, 3, dtype=torch.int32, device=dev) if f1 else None
-            self._eval_work = _ticket(model._lib.icnn_be_gd_eval_work_bytes(E), dev)
+        self.eval_f1_tallies = torch.zeros(E, 3, dtype=torch.int32, device=dev) if f1 and E is not None else None
 
-    def step(self, x=None, t=None) -> torch.Tensor:
-        """One step on (x [B, n_features], t [B, n]); None keeps the batch of the previous call (graph replay)."""
-        from . import gd
-        self._put(self.x, x)
-        self._put(self.t, t)
-        model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
-        model.context(self.x, out=self.ctx, work=self._ctx_work)
-        self.y, traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(model._lib.icnn_be_gd_feed(self.y.data_ptr(), self.t.data_ptr(), self._coef.data_ptr(), B, n, K, self.scale,
-                                              self.v_rows.data_ptr(), self.c_rows.data_ptr(), self.row_offset.data_ptr(),
-                                              self.loss.data_ptr(),
-                                              None if self.f1_tallies is None else self.f1_tallies.data_ptr(),
-                                              self._feed_work.data_ptr(), C.c_void_p(stream)), "icnn_be_gd_feed")
-        surrogate_grad(model, self.x, (traj.view(B * K, n), self.v_rows, self.c_rows), row_offset=self.row_offset,
-                       bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
-        self.opt.step(self.grad)
-        return self.loss
+    def _feed_work_bytes(self, rows, eval):
+        lib = self.model._lib
+        return lib.icnn_be_gd_eval_work_bytes(rows) if eval else lib.icnn_be_gd_feed_work_bytes(rows)
 
-    def evaluate(self, x=None, t=None) -> torch.Tensor:
-        """The test phase on exactly eval_batch samples (x, t shaped as for step; None keeps the previous ones): the loss
-        mean((y_K - t)^2) at y_K of the unrolled GD from y0 with the context in eval_bn mode, a float32 device scalar
-        (eval_loss); y_eval keeps y_K and eval_f1_tallies (f1=True) the tallies.  Nothing is updated and no statistic is
-        folded.  No host wait (capturable)."""
-        from . import gd
-        if self.eval_batch is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        self._put(self.x_eval, x)
-        self._put(self.t_eval, t)
-        model, E = self.model, self.eval_batch
-        model.context(self.x_eval, bn=self.eval_bn, out=self.ctx_eval, work=self._ctx_work_eval)
-        self.y_eval = gd.solve(model, self.ctx_eval, self.y0, self.n_iter, self.lr, self.momentum)[0]
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(model._lib.icnn_be_gd_eval(self.y_eval.data_ptr(), self.t_eval.data_ptr(), E, self.spec.n_labels,
-                                              self.eval_loss.data_ptr(),
-                                              None if self.eval_f1_tallies is None else self.eval_f1_tallies.data_ptr(),
-                                              self._eval_work.data_ptr(), C.c_void_p(stream)), "icnn_be_gd_eval")
-        return self.eval_loss
+    def _start(self, eval):
+        return self.y0
 
-    def eval_macro_f1(self) -> float:
-        """the test F1 of the last evaluate() (util.macroF1; f1=True only; one wait)"""
-        if self.eval_f1_tallies is None:
-            raise ValueError("F1 tallies exist for a trainer constructed with f1=True and eval_batch only")
-        return macro_f1(self.eval_f1_tallies)
+    def _feed(self, traj):
+        _lib.check(self.model._lib.icnn_be_gd_feed(self.y.data_ptr(), self.t.data_ptr(), self._coef.data_ptr(), self.batch,
+                                                   self.spec.n_labels, self.n_iter, self.scale, self.v_rows.data_ptr(),
+                                                   self.c_rows.data_ptr(), self.row_offset.data_ptr(), self.loss.data_ptr(),
+                                                   None if self.f1_tallies is None else self.f1_tallies.data_ptr(),
+                                                   self._feed_work.data_ptr(), self._stream()), "icnn_be_gd_feed")
+
+    def _eval_feed(self):
+        _lib.check(self.model._lib.icnn_be_gd_eval(self.y_eval.data_ptr(), self.t_eval.data_ptr(), self.eval_batch,
+                                                   self.spec.n_labels, self.eval_loss.data_ptr(),
+                                                   None if self.eval_f1_tallies is None else self.eval_f1_tallies.data_ptr(),
+                                                   self._feed_work_eval.data_ptr(), self._stream()), "icnn_be_gd_eval")
 
 
-# --------------------------------------------------------------------------------------------- #
-# The back-optimisation training step and test phase of the completion model
-# --------------------------------------------------------------------------------------------- #
-class ConvGDTrainer(_Trainer):
+class ConvGDTrainer(UnrolledGDTrainer):
     """One training step of completion/icnn.back.py (:131-165 the graph, :210-239 the loop) on a picnn.ConvModel at one batch
     size, with the loss mean((pixel_scale (y_K - t))^2) of :149, all of it enqueued on the current stream without a host wait,
     so a step can be captured in a CUDA graph:
@@ -938,47 +848,20 @@ class ConvGDTrainer(_Trainer):
     BatchNorm statistics, gd.solve from y0 without a trajectory and the loss-only form of the feed on exactly E samples; it
     returns the float32 device scalar eval_loss, keeps y_eval, and changes no weight, optimiser state or statistic.  A
     [B, n] y0 serves the test phase only when E = B."""
+    eval_bn = "moving"                                  # the script's test phase sets is_training(False)
 
     def __init__(self, model, batch, n_iter=30, lr=0.01, momentum=0.9, adam_lr=1e-3, y0=0.5, pixel_scale=255.0, bn_updates=0,
                  eval_batch=None):
         if not isinstance(model, ConvModel):
             name = model.__name__ if isinstance(model, type) else type(model).__name__
             raise TypeError("train.ConvGDTrainer serves picnn.ConvModel (train.GDTrainer trains an FCModel), got %s" % name)
-        self.batch, self.n_iter = int(batch), int(n_iter)
-        self.eval_batch = None if eval_batch is None else int(eval_batch)
-        if self.batch < 1 or self.n_iter < 1:
-            raise ValueError("batch and n_iter must be >= 1")
-        self.bn_updates = _non_negative("bn_updates", bn_updates)
-        if self.eval_batch is not None and self.eval_batch < 1:
-            raise ValueError("eval_batch must be >= 1, got %d" % self.eval_batch)
-        self.model, self.spec, self.device = model, model.spec, model.device
-        self.lr, self.momentum, self.px = float(lr), float(momentum), float(np.float32(pixel_scale))
-        self.opt = DeviceAdam(model, lr=adam_lr)
-        B, K, E, n, dev = self.batch, self.n_iter, self.eval_batch, self.spec.n_labels, self.device
-        lib = model._lib
-        model.reserve(max(B, E or 0))                   # grown here, never inside a capture
-        self._coef = unrolled_coefficients(K, self.lr, self.momentum, dev)         # uploaded now, not inside a capture
-        self.scale = float(np.float32(1.0) / np.float32(B * n))
-        self.x = torch.zeros(B, self.spec.H, self.spec.W, 1, dtype=torch.float32, device=dev)
-        self.t = torch.zeros(B, n, dtype=torch.float32, device=dev)
+        super().__init__(model, batch, n_iter, lr, momentum, adam_lr, bn_updates, eval_batch)
+        self.px = float(np.float32(pixel_scale))
+        self.traj = None                                # gd.solve's own trajectory tensor, from the first step on
+        B, E, n, dev = self.batch, self.eval_batch, self.spec.n_labels, self.device
         self.y0 = torch.zeros(B, n, dtype=torch.float64, device=dev)
-        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.y = self.traj = None                       # gd.solve's own y_K and trajectory tensors, from the first step on
-        self.ctx, self._ctx_work = self._context_buffers(B)
-        self.v_rows = torch.zeros(B * K, n, dtype=torch.float64, device=dev)
-        self.c_rows = torch.zeros(B * K, dtype=torch.float64, device=dev)
-        self.row_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        self._feed_work = _ticket(lib.icnn_be_gd_feed_px_work_bytes(B, n, K), dev)
-        self.grad = torch.zeros(self.opt.n, dtype=torch.float32, device=dev)
-        self._grad_work = torch.empty(surrogate_work_floats(model, B, B * K), dtype=torch.float32, device=dev)
-        self.y_eval = self.eval_loss = None
         if E is not None:
-            self.x_eval = torch.zeros(E, self.spec.H, self.spec.W, 1, dtype=torch.float32, device=dev)
-            self.t_eval = torch.zeros(E, n, dtype=torch.float32, device=dev)
             self.y0_eval = torch.zeros(E, n, dtype=torch.float64, device=dev)
-            self.eval_loss = torch.zeros((), dtype=torch.float32, device=dev)
-            self.ctx_eval, self._ctx_work_eval = self._context_buffers(E)
-            self._feed_work_eval = _ticket(lib.icnn_be_gd_feed_px_work_bytes(E, n, K), dev)
         self.set_y0(y0)
 
     def set_y0(self, y0):
@@ -991,362 +874,27 @@ class ConvGDTrainer(_Trainer):
             self.y0_eval.copy_(y0.expand(self.eval_batch, n))
         self.y0.copy_(y0.expand(self.batch, n))
 
-    def _feed(self, y, t, B, loss, work, rows):
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+    def _feed_work_bytes(self, rows, eval):
+        return self.model._lib.icnn_be_gd_feed_px_work_bytes(rows, self.spec.n_labels, self.n_iter)
+
+    def _start(self, eval):
+        return self.y0_eval if eval else self.y0
+
+    def _feed_px(self, y, t, B, loss, work, rows):
         v, c, off, coef = ((self.v_rows.data_ptr(), self.c_rows.data_ptr(), self.row_offset.data_ptr(), self._coef.data_ptr())
                            if rows else (None, None, None, None))
         # scale is 1 / (B n) of the TRAINING batch: the loss-only form does not read it
         _lib.check(self.model._lib.icnn_be_gd_feed_px(y.data_ptr(), t.data_ptr(), coef, B, self.spec.n_labels, self.n_iter,
                                                       self.scale, self.px, v, c, off, loss.data_ptr(), work.data_ptr(),
-                                                      C.c_void_p(stream)), "icnn_be_gd_feed_px")
+                                                      self._stream()), "icnn_be_gd_feed_px")
 
-    def step(self, x=None, t=None) -> torch.Tensor:
-        """One step on (x [B, H, W, 1] already h-flipped, t [B, n] or [B, H, W, 1]); None keeps the batch of the previous call
-        (graph replay)."""
-        from . import gd
-        self._put(self.x, x)
-        self._put(self.t, t)
-        model, B, K, n = self.model, self.batch, self.n_iter, self.spec.n_labels
-        model.context(self.x, out=self.ctx, work=self._ctx_work)
-        self.y, self.traj, _ = gd.solve(model, self.ctx, self.y0, K, self.lr, self.momentum, trajectory=True)
-        self._feed(self.y, self.t, B, self.loss, self._feed_work, True)
-        surrogate_grad(model, self.x, (self.traj.view(B * K, n), self.v_rows, self.c_rows), row_offset=self.row_offset,
-                       bn_updates=self.bn_updates, flat=True, out=self.grad, work=self._grad_work)
-        self.opt.step(self.grad)
-        return self.loss
+    def _feed(self, traj):
+        self.traj = traj                                # kept: y_0 .. y_{K-1} of the last step
+        self._feed_px(self.y, self.t, self.batch, self.loss, self._feed_work, True)
 
-    def evaluate(self, x=None, t=None) -> torch.Tensor:
-        """The test phase on exactly eval_batch samples (x, t shaped as for step; None keeps the previous ones): the loss at
-        y_K from the moving BatchNorm statistics, a float32 device scalar (eval_loss); y_eval keeps y_K.  Nothing is
-        updated."""
-        from . import gd
-        if self.eval_batch is None:
-            raise ValueError("evaluate() needs a trainer constructed with eval_batch")
-        self._put(self.x_eval, x)
-        self._put(self.t_eval, t)
-        self.model.context(self.x_eval, bn="moving", out=self.ctx_eval, work=self._ctx_work_eval)
-        self.y_eval = gd.solve(self.model, self.ctx_eval, self.y0_eval, self.n_iter, self.lr, self.momentum)[0]
-        self._feed(self.y_eval, self.t_eval, self.eval_batch, self.eval_loss, self._feed_work_eval, False)
-        return self.eval_loss
+    def _eval_feed(self):
+        self._feed_px(self.y_eval, self.t_eval, self.eval_batch, self.eval_loss, self._feed_work_eval, False)
 
 
-# --------------------------------------------------------------------------------------------- #
-# Keeping the best model on the device
-# --------------------------------------------------------------------------------------------- #
-class BestKeeper:
-    """The scripts' "save when the score is better" without a host round trip (multi-label-cls/icnn_ebundle.py:274-277: `if
-    testF1 > bestTestF1: save`, mode "max" with start=0.0; synthetic-cls/icnn.py:206-209: `bestMSE is None or trainMSE <
-    bestMSE`, mode "min"), for any trainer that owns a DeviceAdam as `.opt` (BundleTrainer, GDTrainer,
-    ConvGDTrainer, ficnn.GDTrainer, rl_train.CriticTrainer).
-
-    offer(score) enqueues icnn_be_keep_best on a one-element float32 or float64 device tensor and, behind its gate,
-    icnn_be_gated_copy of opt.theta, opt.arena and the model's BatchNorm moving statistics into snapshots: they change only
-    on an offer that is STRICTLY better than `best`.  offer_macro_f1(tallies) first forms util.macroF1 on the device
-    (icnn_be_macro_f1) into the keeper's own score word, so a captured [evaluate, offer_macro_f1(eval_f1_tallies)] keeps the
-    best test-F1 model with no host data.  No host wait in either.
-
-    start=None: -inf for "max", +inf for "min", so the first finite offer is kept.  One deviation from synthetic-cls:
-    `bestMSE is None or ...` would keep a NaN first loss; the keeper never keeps a NaN (no comparison with a NaN is true).
-
-    For a model with BatchNorm the constructor calls model.flatten_bn_stats(), which MOVES the statistics' addresses:
-    construct the keeper before capturing anything that reads them (a BundleTrainer(skip_on_error=True) has moved them
-    already).  The snapshots start as copies of the current state, so restore() before any kept offer puts that back.
-
-    best (float64 [1]) is the device scalar; offers, kept and best_value() read the device (one wait each)."""
-
-    def __init__(self, trainer, mode="max", start=None):
-        if mode not in _lib.KEEP_MODE:
-            raise ValueError("mode must be 'max' or 'min', got %r" % (mode,))
-        opt = getattr(trainer, "opt", None)
-        if not isinstance(opt, DeviceAdam):
-            raise TypeError("BestKeeper serves a trainer that owns a DeviceAdam as .opt, got %s" % type(trainer).__name__)
-        self.trainer, self.opt, self.model, self.mode = trainer, opt, opt.model, mode
-        self.device = dev = opt.device
-        self._lib = opt.model._lib
-        if start is None:
-            start = -math.inf if mode == "max" else math.inf
-        self.start = float(start)
-        self.best = torch.full((1,), self.start, dtype=torch.float64, device=dev)
-        self.gate = torch.zeros(3, dtype=torch.int32, device=dev)                # go, offers, kept
-        self.score = torch.zeros(1, dtype=torch.float64, device=dev)             # offer_macro_f1's score word
-        self.theta = opt.theta.clone()
-        self.arena = opt.arena.clone()
-        self._bn_live = self.bn = None
-        self._bn_views = {}
-        if getattr(self.model, "has_bn", False) and self.model.bn_stats:     # a one-layer u-path normalises nothing
-            self._bn_live = live = self.model.flatten_bn_stats()
-            self.bn = live.clone()
-            self._bn_views = {k: ((t.data_ptr() - live.data_ptr()) // 4, tuple(t.shape))
-                              for k, t in self.model.bn_stats.items()}
-
-    def _pairs(self):
-        """(snapshot, live) of everything the keeper keeps"""
-        pairs = [(self.theta, self.opt.theta), (self.arena, self.opt.arena)]
-        if self.bn is not None:
-            pairs.append((self.bn, self._bn_live))
-        return pairs
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def offer(self, score):
-        """Offer a one-element float32 or float64 device tensor; the snapshots follow when it is strictly better."""
-        if (not torch.is_tensor(score) or score.numel() != 1 or not score.is_cuda
-                or score.dtype not in (torch.float32, torch.float64)):
-            raise ValueError("score is one float32 or float64 on the device")
-        stream = self._stream()
-        _lib.check(self._lib.icnn_be_keep_best(score.data_ptr(), int(score.dtype == torch.float64), _lib.KEEP_MODE[self.mode],
-                                               self.best.data_ptr(), self.gate.data_ptr(), stream), "icnn_be_keep_best")
-        for snap, live in self._pairs():
-            _lib.check(self._lib.icnn_be_gated_copy(snap.data_ptr(), live.data_ptr(), live.numel(), self.gate.data_ptr(), 1,
-                                                    stream), "icnn_be_gated_copy")
-
-    def offer_macro_f1(self, tallies):
-        """Offer util.macroF1 of per-example tallies (int32 [B, 3] on the device: a trainer's f1_tallies / eval_f1_tallies)."""
-        if (not torch.is_tensor(tallies) or tallies.dtype != torch.int32 or not tallies.is_cuda or not tallies.is_contiguous()
-                or tallies.dim() != 2 or tallies.shape[1] != 3 or tallies.shape[0] < 1):
-            raise ValueError("tallies is a contiguous int32 [B, 3] device tensor, B >= 1")
-        _lib.check(self._lib.icnn_be_macro_f1(tallies.data_ptr(), tallies.shape[0], self.score.data_ptr(), self._stream()),
-                   "icnn_be_macro_f1")
-        self.offer(self.score)
-
-    @property
-    def offers(self) -> int:
-        """offers made (reads the device: one wait)"""
-        return int(self.gate[1].item())
-
-    @property
-    def kept(self) -> int:
-        """offers that were kept (reads the device: one wait)"""
-        return int(self.gate[2].item())
-
-    def best_value(self) -> float:
-        """the best score so far, `start` before any was kept (reads the device: one wait)"""
-        return float(self.best.item())
-
-    def host_params(self) -> Dict[str, np.ndarray]:
-        """the kept model's theta as a NumPy dict keyed like grad_layout (one copy; synchronises): what goes into best.npz"""
-        flat = self.theta.cpu().numpy()
-        return {name: t.numpy().copy() for name, t in unpack_grad(self.opt.spec, torch.from_numpy(flat)).items()}
-
-    def bn_stats(self) -> Dict[str, np.ndarray]:
-        """the kept model's BatchNorm moving statistics keyed like picnn.init_bn_stats ({} without BatchNorm; synchronises)"""
-        if self.bn is None:
-            return {}
-        flat = self.bn.cpu().numpy()
-        return {k: flat[off:off + int(np.prod(shape))].reshape(shape).copy() for k, (off, shape) in self._bn_views.items()}
-
-    def restore(self):
-        """Copy the snapshots back: theta, the arena and the statistics become the kept model's, on the device.  Adam's m, v
-        and the step count are left alone."""
-        for snap, live in self._pairs():
-            live.copy_(snap)
-
-
-# --------------------------------------------------------------------------------------------- #
-# The training set on the device: minibatch draw, step log, epochs as a graph
-# --------------------------------------------------------------------------------------------- #
-class DeviceDataset:
-    """The training arrays of the supervised scripts on the device, and their `I = npr.randint(nTrain, size=batch);
-    trainX[I], trainY[I]` (multi-label-cls/icnn_ebundle.py:214, icnn-back.py:190, completion/icnn_ebundle.py:210,
-    icnn.back.py:216) as one launch without a host wait (icnn_be_dataset_draw, be_train_data.hip).
-
-    arrays: 1 to 4 tensors or ndarrays that share their first dimension N, typically (X float32 [N, *x_shape], Y [N, n]) with
-    Y in the dtype of the trainer buffer it feeds (float64 for BundleTrainer.true_y, float32 for the GD trainers' t); they
-    are copied into contiguous device tensors this object owns.  The draw copies rows bit for bit and knows no transform: the
-    completion scripts' h-flip of x (completion/icnn_ebundle.py:215) is the same flip on every batch, so flip once when
-    building the set.
-
-    The indices follow npr.randint's rule -- independent, with replacement -- with this library's own random numbers:
-    idx[k] = (word * N) >> 32 with word = word 0 of Philox4x32-10 at counter (draw, k, 0, 1) and key `seed`.  The draw
-    counter lives on the device and every launch advances it, so a captured draw_into replayed r times is r different
-    minibatches.  `draws` is its host mirror, deterministic and never read back: every draw_into call adds one, a capture's
-    calls included; whoever replays a captured draw adds what the replay made (EpochRunner does)."""
-
-    def __init__(self, arrays, device="cuda", seed=0):
-        if torch.is_tensor(arrays) or isinstance(arrays, np.ndarray):
-            arrays = (arrays,)
-        arrays = tuple(arrays)
-        if not 1 <= len(arrays) <= _lib.DATASET_MAX_ARRAYS:
-            raise ValueError("a dataset holds 1 to %d arrays, got %d" % (_lib.DATASET_MAX_ARRAYS, len(arrays)))
-        self.seed = int(seed)
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError("seed must fit 64 bits")
-        self.device = dev = torch.device(device)
-        self.lib = _lib.load()
-        self.arrays, self.row_words = [], []
-        for i, a in enumerate(arrays):
-            a = torch.as_tensor(a)
-            if a.dim() < 1 or a.shape[0] != torch.as_tensor(arrays[0]).shape[0]:
-                raise ValueError("array %d: the arrays share their first dimension" % i)
-            row_bytes = (a.numel() // max(a.shape[0], 1)) * a.element_size()
-            if a.shape[0] < 1 or row_bytes < 4 or row_bytes % 4:
-                raise ValueError("array %d: a dataset needs N >= 1 rows of whole 4-byte words, got shape %s of %s"
-                                 % (i, tuple(a.shape), a.dtype))
-            own = torch.empty(a.shape, dtype=a.dtype, device=dev)
-            own.copy_(a)
-            self.arrays.append(own)
-            self.row_words.append(row_bytes // 4)
-        self.n_rows = int(self.arrays[0].shape[0])
-        if self.n_rows >= 1 << 31:
-            raise ValueError("a dataset holds fewer than 2^31 rows")
-        self.ctrl = torch.zeros(_lib.DATASET_CTRL_INTS, dtype=torch.int32, device=dev)
-        d = _lib.Dataset()
-        d.n_rows, d.n_arrays, d.ctrl = self.n_rows, len(self.arrays), self.ctrl.data_ptr()
-        for i, (a, w) in enumerate(zip(self.arrays, self.row_words)):
-            d.src[i], d.row_words[i] = a.data_ptr(), w
-        self._c = d
-        self._idx = {}                       # batch -> the int32 index buffer (fixed: a captured graph writes it)
-        self.draws = 0
-
-    def reset(self):
-        """back to draw 0 with a clear status word"""
-        self.ctrl.zero_()
-        self.draws = 0
-
-    def draw_into(self, *buffers) -> torch.Tensor:
-        """One minibatch into `buffers`, one per array: contiguous tensors on the dataset's device, in the array's dtype,
-        with the array's row size and a common first dimension B (a view of the first B rows of a larger buffer will do).
-        Returns the drawn indices (int32 [B], a buffer of this dataset that the next draw at this batch size overwrites).
-        One launch on the current stream, no host wait (capturable)."""
-        if len(buffers) != len(self.arrays):
-            raise ValueError("the dataset holds %d arrays, got %d buffers" % (len(self.arrays), len(buffers)))
-        B = None
-        for i, (buf, a, w) in enumerate(zip(buffers, self.arrays, self.row_words)):
-            if not torch.is_tensor(buf) or buf.device != a.device:
-                raise ValueError("buffer %d: not a tensor on %s" % (i, a.device))
-            if buf.dtype != a.dtype or not buf.is_contiguous():
-                raise ValueError("buffer %d: a contiguous %s tensor is needed, got %s" % (i, a.dtype, buf.dtype))
-            if buf.dim() < 1 or buf.shape[0] < 1 or buf.numel() != buf.shape[0] * (a.numel() // self.n_rows):
-                raise ValueError("buffer %d: rows of %d elements are needed, got shape %s"
-                                 % (i, a.numel() // self.n_rows, tuple(buf.shape)))
-            if B is not None and buf.shape[0] != B:
-                raise ValueError("buffer %d: %d rows, the first buffer has %d" % (i, buf.shape[0], B))
-            if buf.data_ptr() % 16:
-                raise ValueError("buffer %d: not 16-byte aligned" % i)
-            B = int(buf.shape[0])
-        if B not in self._idx:
-            self._idx[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
-        dst = (C.c_void_p * len(buffers))(*[b.data_ptr() for b in buffers])
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.icnn_be_dataset_draw(C.byref(self._c), B, self.seed, dst, self._idx[B].data_ptr(), stream),
-                   "icnn_be_dataset_draw")
-        self.draws += 1
-        return self._idx[B]
-
-    @property
-    def status(self) -> int:
-        """the device's status word, an OR of _lib.DATASET_ST_* (synchronises)"""
-        return int(self.ctrl[1].item())
-
-    def raise_on_error(self):
-        """Raise if a launch so far met an error on the device (synchronises)."""
-        st = self.status
-        if st:
-            raise RuntimeError("dataset: a draw found its ticket outside its grid -- two draws of one dataset ran at the "
-                               "same time (status %d)" % st)
-
-
-class StepLog:
-    """The per-iteration scalars the scripts write to train.csv, kept on the device so that reading them needs no
-    synchronisation per step (icnn_be_log_row, be_train_data.hip).  columns: up to 8 (name, tensor) with the
-    tensor one float32, float64 or int32 on the device (a trainer's loss, rows, went ...); capacity: rows of the ring.
-    append() is one launch, no host wait (capturable): it widens every scalar to float64 (exactly) into row cursor %
-    capacity and advances the device cursor."""
-
-    def __init__(self, columns, capacity):
-        columns = list(columns)
-        if not 1 <= len(columns) <= _lib.LOG_MAX_COLUMNS:
-            raise ValueError("a step log has 1 to %d columns, got %d" % (_lib.LOG_MAX_COLUMNS, len(columns)))
-        self.capacity = _positive("capacity", capacity)
-        self.names = [str(name) for name, _ in columns]
-        if len(set(self.names)) != len(self.names):
-            raise ValueError("column names repeat: %s" % self.names)
-        self.columns = [t for _, t in columns]
-        L = _lib.StepLog()
-        for j, t in enumerate(self.columns):
-            kind = _lib.LOG_KIND.get(str(t.dtype).replace("torch.", "")) if torch.is_tensor(t) else None
-            if kind is None or t.numel() != 1 or not t.is_cuda or t.device != self.columns[0].device:
-                raise ValueError("column %r: one float32, float64 or int32 on the device is needed" % self.names[j])
-            L.col[j], L.kind[j] = t.data_ptr(), kind
-        self.device = dev = self.columns[0].device
-        self.lib = _lib.load()
-        self.rows = torch.zeros(self.capacity, len(columns), dtype=torch.float64, device=dev)
-        self.ctrl = torch.zeros(_lib.LOG_CTRL_INTS, dtype=torch.int32, device=dev)
-        L.rows, L.ctrl, L.cap, L.width = self.rows.data_ptr(), self.ctrl.data_ptr(), self.capacity, len(columns)
-        self._c = L
-        self._read = 0                       # rows handed out so far: the cursor at the last read()
-
-    def append(self):
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.icnn_be_log_row(C.byref(self._c), stream), "icnn_be_log_row")
-
-    def read(self) -> Dict[str, np.ndarray]:
-        """The rows appended since the last read(), in order, as name -> float64 array.  Synchronises the device.
-        RuntimeError if more than `capacity` rows were appended since the last read(): the oldest were overwritten (the
-        next read() starts behind them)."""
-        torch.cuda.synchronize(self.device)
-        cursor = int(self.ctrl[0].item())
-        first, self._read = self._read, cursor
-        if cursor - first > self.capacity:
-            raise RuntimeError("step log: %d rows appended since the last read(), the ring keeps %d"
-                               % (cursor - first, self.capacity))
-        rows = self.rows.cpu().numpy()[np.arange(first, cursor, dtype=np.int64) % self.capacity]
-        return {name: rows[:, j].copy() for j, name in enumerate(self.names)}
-
-
-class EpochRunner:
-    """`steps` iterations of [dataset.draw_into(*buffers), trainer.step(), log.append()] per run(), with no host wait inside:
-    the first run() is eager, the second captures the chain once on a side stream and replays it, later runs replay
-    (DESIGN.md §21).  After r runs the trainer's state is that of r x steps eager iterations bit for bit, whichever runs
-    were eager, capturing or replays.  trainer: a BundleTrainer (FC or conv), GDTrainer, ConvGDTrainer, ff.FFTrainer or fcn.FCNTrainer; step() reads its
-    buffers as step(None, None) does.  buffers: where the dataset's arrays go, by default (trainer.x, trainer.true_y) for a
-    trainer that has true_y, else (trainer.x, trainer.t).  log: a StepLog, appended to after every step.
-
-    With BundleTrainer(skip_on_error=True) a skipped step still consumes its draw, as the reference draws before its try."""
-
-    def __init__(self, trainer, dataset, steps, log=None, buffers=None):
-        from .fcn import FCNTrainer
-        from .ff import FFTrainer
-        if not isinstance(trainer, (BundleTrainer, GDTrainer, ConvGDTrainer, FFTrainer, FCNTrainer)):
-            raise TypeError("EpochRunner serves BundleTrainer, GDTrainer, ConvGDTrainer, ff.FFTrainer and fcn.FCNTrainer, got %s"
-                            % type(trainer).__name__)
-        if not isinstance(dataset, DeviceDataset):
-            raise TypeError("dataset is a train.DeviceDataset, got %s" % type(dataset).__name__)
-        if log is not None and not isinstance(log, StepLog):
-            raise TypeError("log is a train.StepLog, got %s" % type(log).__name__)
-        self.trainer, self.dataset, self.log = trainer, dataset, log
-        self.steps = _positive("steps", steps)
-        if buffers is None:
-            buffers = (trainer.x, trainer.true_y if hasattr(trainer, "true_y") else trainer.t)
-        self.buffers = tuple(buffers)
-        self.runs = 0
-        self._graph = None
-
-    def _chain(self):
-        for _ in range(self.steps):
-            self.dataset.draw_into(*self.buffers)
-            self.trainer.step()
-            if self.log is not None:
-                self.log.append()
-
-    def run(self):
-        """`steps` iterations, enqueued on the current stream"""
-        if self.runs == 0:
-            self._chain()
-            self.runs = 1
-            return
-        if self._graph is None:
-            draws = self.dataset.draws
-            s = torch.cuda.Stream(self.dataset.device)
-            s.wait_stream(torch.cuda.current_stream(self.dataset.device))
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(graph, stream=s):
-                    self._chain()
-            torch.cuda.current_stream(self.dataset.device).wait_stream(s)
-            self.dataset.draws = draws                  # the capture launched nothing
-            self._graph = graph
-        self._graph.replay()
-        self.dataset.draws += self.steps
-        self.runs += 1
+# the epoch level names the trainers above, so its module is imported behind them; its classes are re-exported here
+from .epoch import BestKeeper, DeviceDataset, EpochRunner, StepLog  # noqa: E402, F401
