@@ -36,6 +36,7 @@ FLAG_GLOBAL_BUNDLE = 64
 FLAG_WAVE_PER_SAMPLE = 128
 FLAG_MFMA_CONTRACTION = 256
 FLAG_GENERIC_SHAPE = 512
+FLAG_NO_ROUND_CLASSES = 1024
 # ICNN_BE_SHAPE_*: which instance of the persistent tile kernel a solve launches (icnn_be_debug_shape_instance)
 SHAPE_INSTANCES = ["generic", "bibtex_kt16", "bibtex_kt32_grouped"]
 LOSS = {"xent": 0, "mse": 1}

@@ -646,99 +646,16 @@ __device__ __forceinline__ double row_bcast(double v) {
     return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + P, 0xf, 0xf, true);   // bound_ctrl: no "old" value to set up
 }
 
-template <int KS>
-__device__ __noinline__ int inertia_not_above_dpp(const double *Hm_, int HP, int k, double mu) {
-    static_assert(KS <= 16, "row broadcasts stay inside one 16-lane row");
-    const int lane = lane_id();
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); mu = uni(mu);
-    double M[KS];
-#pragma unroll
-    for (int j = 0; j < KS; ++j) M[j] = Hm[(lane < k ? lane : 0) * HP + (j < k ? j : 0)];
-#pragma unroll
-    for (int j = 0; j < KS; ++j) pin(M[j]);                       // unconditional loads, all in flight
-#pragma unroll
-    for (int j = 0; j < KS; ++j)
-        M[j] = (lane < k && j < k) ? M[j] - (j == lane ? mu : 0.0) : (j == lane ? 1.0 : 0.0);
-    double dp = 1.0;                                              // lane p keeps pivot p
-    static_for<0, KS>([&](auto P) {
-        constexpr int p = decltype(P)::value;
-        const double d = row_bcast<p>(M[p]);
-        dp = lane == p ? d : dp;
-        const double nf = lane > p ? -(M[p] * rcp_nr(d)) : 0.0;
-        static_for<p + 1, KS>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            M[j] = __builtin_fma(nf, row_bcast<p>(M[j]), M[j]);
-        });
-    });
-    // pivots up to the first exact zero count individually; behind it everything counts as suspect
-    const unsigned long long nonpos = __ballot(lane < k && !(dp > 0.0));
-    const unsigned long long zero = __ballot(lane < k && dp == 0.0);
-    if (zero) {
-        const int p0 = __builtin_ctzll(zero);
-        return __popcll(nonpos & ((2ull << p0) - 1ull)) + (k - p0 - 1);
-    }
-    return __popcll(nonpos);
-}
-
-// TRI: the system is read from the packed upper triangle the fused VALU pass leaves for a one-wave sample -- entry (r, c),
-// r <= c, at c (c + 1) / 2 + r (be_dual_valu_dev.h) -- instead of from a k x (k + 1) matrix: no gather of the sums into a matrix
-// in front of every Newton update, three index operations per entry here.  Same values, same elimination.
-template <int KS, bool TRI = false>
-__device__ __noinline__ StepResult newton_step_dpp(const double *Hm_, int HP, int k, int piv,
-                                                   unsigned long long fmask, bool is_free, double g0) {
-    static_assert(KS <= 16, "row broadcasts stay inside one 16-lane row");
-    const int lane = lane_id();
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); piv = uni(piv); fmask = uni(fmask);
-    double M[KS + 1];
-    const int rl = lane < k ? lane : 0;
-    auto at = [&](int i, int j) -> int {                 // where H[i][j] lives
-        if (!TRI) return i * HP + j;
-        const int c = i > j ? i : j, r = i > j ? j : i;
-        return c * (c + 1) / 2 + r;
-    };
-    double h_ip = Hm[at(rl, piv)], h_pp = Hm[at(piv, piv)];
-#pragma unroll
-    for (int j = 0; j < KS; ++j) M[j] = Hm[at(rl, j < k ? j : 0)];
-    pin(h_ip);
-    pin(h_pp);
-#pragma unroll
-    for (int j = 0; j < KS; ++j) pin(M[j]);                       // all loads in flight, none sunk into a branch
-    // H0[i][j] = ((H[i][j] - keep_i H[j][piv]) - H[i][piv] keep_j) + H[piv][piv] keep_i keep_j, where H[j][piv]
-    // is what lane j holds as its own H[.][piv]: one row broadcast instead of a second LDS read (and no second
-    // register array -- this function's register need is what the caller has to spill around the call)
-    static_for<0, KS>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        double hv = ((M[j] - row_bcast<j>(h_ip)) - h_ip) + h_pp;
-        pin(hv);                                                  // plain select below, no exec-mask branch
-        const bool use = j < k && is_free && ((fmask >> j) & 1ull);
-        M[j] = use ? hv : (j == lane ? 1.0 : 0.0);
-    });
-    M[KS] = is_free ? -g0 : 0.0;
-    double rinv = 1.0;                                            // lane p keeps 1 / pivot p
-    bool bad = false;
-    static_for<0, KS>([&](auto P) {
-        constexpr int p = decltype(P)::value;
-        const double d = row_bcast<p>(M[p]);
-        bad |= !(d != 0.0);                                       // exact zero (or NaN): singular for LAPACK
-        const double inv = rcp_nr(d);
-        rinv = lane == p ? inv : rinv;
-        const double nf = lane > p ? -(M[p] * inv) : 0.0;
-        static_for<p + 1, KS + 1>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            M[j] = __builtin_fma(nf, row_bcast<p>(M[j]), M[j]);
-        });
-        __builtin_amdgcn_sched_barrier(0);     // keep the broadcasts of later pivots from being hoisted (registers)
-    });
-    if (__ballot(bad) & 0xffffull) return StepResult{0.0, 0};
-    static_for<0, KS>([&](auto Q) {
-        constexpr int p = KS - 1 - decltype(Q)::value;
-        const double x = row_bcast<p>(M[KS] * rinv);
-        M[KS] = lane == p ? x : (lane < p ? __builtin_fma(-M[p], x, M[KS]) : M[KS]);
-    });
-    return StepResult{is_free ? M[KS] : 0.0, 1};
-}
+#define DPP_ROWS_ATTR __noinline__
+#define DPP_ROWS_NAME(f) f
+#include "be_dual_dpp_rows.h"
+#undef DPP_ROWS_ATTR
+#undef DPP_ROWS_NAME
+#define DPP_ROWS_ATTR __forceinline__
+#define DPP_ROWS_NAME(f) f##_inl
+#include "be_dual_dpp_rows.h"
+#undef DPP_ROWS_ATTR
+#undef DPP_ROWS_NAME
 
 // ---- KS > 16 (round 6): the same eliminations spread over the WHOLE wave ---------------------------------------------------
 // Bundles of 17 .. 32 cuts used to fall back to one row per lane with `v_readlane` broadcasts (newton_step_ks: 12.4 k cycles
@@ -930,8 +847,15 @@ __device__ __noinline__ int inertia_not_above_2d(const double *Hm_, int HP, int 
 
 // The statically unrolled routines above cost O(KS^2) predicated steps whatever k is, so they are
 // instantiated for several sizes and the smallest one that holds the bundle is used.
-template <int KT>
+// KCAP > 0 (dual_step_body): k <= KCAP <= 8, and the instance today's dispatch picks for k is inlined instead of called.
+template <int KT, int KCAP = 0>
 __device__ __forceinline__ int inertia_not_above(const double *Hm, int HP, int k, double mu) {
+    if constexpr (KCAP > 0) {
+        static_assert(KCAP <= 8, "capped bodies hold bundles of up to eight cuts");
+        if (KCAP <= 4 || k <= 4) return inertia_not_above_dpp_inl<4>(Hm, HP, k, mu);
+        if (KCAP <= 6 || k <= 6) return inertia_not_above_dpp_inl<6>(Hm, HP, k, mu);
+        return inertia_not_above_dpp_inl<8>(Hm, HP, k, mu);
+    }
     if (k <= 4) return inertia_not_above_dpp<4>(Hm, HP, k, mu);
     if (k <= 6) return inertia_not_above_dpp<6>(Hm, HP, k, mu);
     if (k <= 8) return inertia_not_above_dpp<8>(Hm, HP, k, mu);
@@ -946,8 +870,14 @@ __device__ __forceinline__ int inertia_not_above(const double *Hm, int HP, int k
     return 0;
 }
 // (one-wave samples on the fused VALU pass: bundles of up to HV_K1MAX = 8 cuts, system in the pass's packed triangle)
+template <int KCAP = 0>
 __device__ __forceinline__ StepResult newton_step_tri(const double *P, int k, int piv, unsigned long long fmask, bool is_free,
                                                       double g0) {
+    if constexpr (KCAP > 0) {                            // the same choice by k, inlined
+        if (KCAP <= 4 || k <= 4) return newton_step_dpp_inl<4, true>(P, 0, k, piv, fmask, is_free, g0);
+        if (KCAP <= 6 || k <= 6) return newton_step_dpp_inl<6, true>(P, 0, k, piv, fmask, is_free, g0);
+        return newton_step_dpp_inl<8, true>(P, 0, k, piv, fmask, is_free, g0);
+    }
     if (k <= 4) return newton_step_dpp<4, true>(P, 0, k, piv, fmask, is_free, g0);
     if (k <= 6) return newton_step_dpp<6, true>(P, 0, k, piv, fmask, is_free, g0);
     return newton_step_dpp<8, true>(P, 0, k, piv, fmask, is_free, g0);
@@ -1073,8 +1003,13 @@ __device__ __forceinline__ void for_columns(const CutT *As, int ldA, int k, int 
 // 1.016 ms on one box; cf. ICNN_BE_PROF, be_common.h).
 // Shape (be_kernels.h): n, n_pad, ldA and the pairwise plan from the arguments (DynShape), or as constants (FixedDual: the
 // fixed instances of the persistent tile kernel).
+// KCAP > 0: the caller guarantees rows_cap <= KCAP <= HV_K1MAX and that the fused VALU pass is what every bundle of two and
+// more cuts takes (one-wave float32 rows of up to 192 columns, no ICNN_BE_FLAG_MFMA_CONTRACTION: the round classes of the
+// persistent tile kernel, be_fused.hip).  The pass, the reduced Newton solve and the inertia count are then inlined in the
+// instance today's dispatch picks for k, the MFMA sweep is not compiled in, and no function is called in the Newton loop.
+// Same instances, same arithmetic, same bits.  KCAP = 0: the body as it always was.
 template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false, int LR = 0, bool SLICED = true,
-          typename Shape = DynShape, typename ArgsT>
+          typename Shape = DynShape, int KCAP = 0, typename ArgsT>
 __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, unsigned char *smem, int round,
                                                int rows_cap, const CutT *crow_shared) {
     constexpr int NT = 64 * NW;
@@ -1116,6 +1051,11 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     // sums and pivot regularisation are compiled out of the dual-variant kernels.
     // a bundle cannot hold more cuts than outer iterations have been started: rows <= round + 1
     static_assert(!IPM || !RL, "interior point is a variant of its own");
+    if constexpr (KCAP > 0) {
+        static_assert(NW == 1 && KT == 16 && !RL && !IPM && !GLB && LR == 0 && sizeof(CutT) == 4, "capped bodies: one-wave dual variant");
+        static_assert(KCAP <= HV_K1MAX && Shape::FIXED && Shape::N_PAD <= 192 && hv_pitch(KCAP) <= Shape::N_PAD,
+                      "every bundle of a capped body takes the fused VALU pass");
+    }
     const Carve cv = carve(KT, rows_cap, ldA, n_pad, (int)sizeof(CutT), plan.n_leaves, RL, NW, crow_shared == nullptr, IPM, GLB);
     // this wave's share of the columns (multiple of 16)
     const int cchunk = NW == 1 ? n_pad : (((n_pad / 16 + NW - 1) / NW) * 16);
@@ -1336,7 +1276,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     // Up to HV_K1MAX = 8 cuts: the pass costs k (k + 3) / 2 sums per column and their reduction, the sweep a fixed number of
     // MFMAs -- measured crossover on the long solves (4096 x 30: sweep only 6.65 ms, pass up to 8 cuts 6.50, up to 16 7.24;
     // 4096 x 15: 1.97 / 1.76 / 1.78).
-    const bool valu = hv_on && (NW > 1 || (n_pad <= 192 && sizeof(CutT) == 4 && k <= HV_K1MAX)) && !RL && !IPM && k >= 2 &&
+    const bool valu = KCAP > 0 ? k >= 2 : hv_on && (NW > 1 || (n_pad <= 192 && sizeof(CutT) == 4 && k <= HV_K1MAX)) && !RL && !IPM && k >= 2 &&
                       k <= HV_KMAX && (LR == 0 || mirror) && n_pad <= 256 * NW && NW * hv_p <= n_pad;
     double *hv_part = zs;
     const HvEntry hv_first = hv_entry<true>(lane, k, HP);  // this lane's first entry of the per-update gather
@@ -1393,8 +1333,8 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
             }
             sample_sync<NW>();
         } else {
-            if (valu) {                                    // (be_dual_valu_dev.h)
-                hv_column_pass_k<CutT, NW, false, LR, GLB, (NW == 1 && KT > 16)>(As, AsL, ldA, k, rows_cap, n, n_pad, tid, 0.0, hv_part + wave * hv_p);
+            if (KCAP > 0 || valu) {                        // (be_dual_valu_dev.h)
+                hv_column_pass_k<CutT, NW, false, LR, GLB, (NW == 1 && KT > 16), KCAP>(As, AsL, ldA, k, rows_cap, n, n_pad, tid, 0.0, hv_part + wave * hv_p);
                 sample_sync<NW>();
                 hv_gather<NW, false>(hv_part, hv_p, Hm, HP, k, tid, NT, hv_entry<false>(tid, k, HP));   // the whole sample: the shared copy
             } else {
@@ -1419,9 +1359,9 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
             const double lo = fmax(dmax, total / (double)k);     // Rayleigh quotients <= lambda_max
             const double hi = fmin(trace, rmax);                 // trace, Gershgorin  >= lambda_max
             const double c2 = cfac * cfac;
-            if (inertia_not_above<KT>(Hm, HP, k, c2 * hi) == 0) {
+            if (inertia_not_above<KT, KCAP>(Hm, HP, k, c2 * hi) == 0) {
                 deficient = false;
-            } else if (inertia_not_above<KT>(Hm, HP, k, c2 * lo) > 0) {
+            } else if (inertia_not_above<KT, KCAP>(Hm, HP, k, c2 * lo) > 0) {
                 deficient = true;
             } else {
                 jacobi_lane0<KT, NW>(Hm, HP, k, tid);
@@ -1502,9 +1442,9 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
         while (updates < cap) {
             if (SLICED && budget-- <= 0) { parked = true; break; }
             // a = A^T lam, z = sigmoid(a), w = z (1 - z)                     dual :32-33
-            if (valu) {
+            if (KCAP > 0 || valu) {
                 double *part = hv_part + (updates & 1) * (NW * hv_p);
-                hv_column_pass_k<CutT, NW, true, LR, GLB, (NW == 1 && KT > 16)>(As, AsL, ldA, k, rows_cap, n, n_pad, tid, lam, part + wave * hv_p);
+                hv_column_pass_k<CutT, NW, true, LR, GLB, (NW == 1 && KT > 16), KCAP>(As, AsL, ldA, k, rows_cap, n, n_pad, tid, lam, part + wave * hv_p);
                 sample_sync<NW>();
                 lap(4);
                 if (NW > 1) hv_gather<NW, true>(part, hv_p, Hp, HP, k, lane, 64, hv_first);  // this wave's own copy of H | A z
@@ -1531,7 +1471,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
             // one wave per sample on the pass: there is no other wave's share to add, the sums are read where the pass left
             // them -- the packed upper triangle (k <= 8: the instance's size is the bundle's), A z behind it
             static_assert(HV_K1MAX <= 8 && hv_padded(HV_K1MAX) == HV_K1MAX, "the packed triangle of a k-cut bundle is the k-cut instance's");
-            const bool tri = NW == 1 && valu;
+            const bool tri = KCAP > 0 || (NW == 1 && valu);
             const int hvT = k * (k + 1) / 2;
 
             const double grad = lane < k ? -c_i + (tri ? hv_part[(updates & 1) * (NW * hv_p) + hvT + lane] : Hq[lane * HP + k]) : 0.0;     // dual :35
@@ -1554,7 +1494,7 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
             if (sqrt(nrm2) < GRAD_TOL) break;                                    // :50 -> return lam
 
             lap(8);
-            const StepResult sr = tri ? newton_step_tri(hv_part + (updates & 1) * (NW * hv_p), k, piv, fmask, is_free, g0)
+            const StepResult sr = tri ? newton_step_tri<KCAP>(hv_part + (updates & 1) * (NW * hv_p), k, piv, fmask, is_free, g0)
                                       : newton_step<KT>(Hq, HP, k, piv, fmask, is_free, g0);
             const double step = sr.step;
             if (!__builtin_amdgcn_readfirstlane(sr.ok)) {

@@ -229,9 +229,26 @@ __device__ __noinline__ void hv_column_pass_fn(const CutT *As_, const CutT *AsL_
 // ALLFN: every instance as a function (the 32-slot one-wave kernels: bundles of up to 8 cuts are the first rounds of a long
 // solve there, and the inlined instances made the Newton loop of ALL its updates spill -- configs[3] moved 5.4 GB per launch
 // against 3.0 GB; the 16-slot kernels, whose bundles mostly ARE that small, are faster with the instances inlined)
-template <typename CutT, int NW, bool HESS, int LR, bool GSRC, bool ALLFN = false>
+// KCAP > 0 (dual_step_body): k <= KCAP <= HV_K1MAX, only the instances up to KCAP are compiled in, every one of them inlined
+// (the 8-cut instance too: a body that never holds a larger bundle has the registers for it)
+template <typename CutT, int K, int KCAP, int NW, bool HESS, int LR>
+__device__ __forceinline__ void hv_column_pass_upto(const CutT *As, const CutT *AsL, int ldA, int k, int zrow, int n, int n_pad,
+                                                    int tid, double lam, double *Pw) {
+    if constexpr (K >= KCAP) {
+        hv_column_pass<CutT, K, NW, HESS, LR>(As, AsL, ldA, k, zrow, n, n_pad, tid, lam, Pw);
+    } else {
+        if (hv_padded(k) <= K) hv_column_pass<CutT, K, NW, HESS, LR>(As, AsL, ldA, k, zrow, n, n_pad, tid, lam, Pw);   // wave-uniform
+        else hv_column_pass_upto<CutT, K + 1, KCAP, NW, HESS, LR>(As, AsL, ldA, k, zrow, n, n_pad, tid, lam, Pw);
+    }
+}
+template <typename CutT, int NW, bool HESS, int LR, bool GSRC, bool ALLFN = false, int KCAP = 0>
 __device__ __forceinline__ void hv_column_pass_k(const CutT *As, const CutT *AsL, int ldA, int k, int zrow, int n, int n_pad,
                                                  int tid, double lam, double *Pw) {
+    if constexpr (KCAP > 0) {
+        static_assert(KCAP <= HV_K1MAX && hv_padded(KCAP) == KCAP && !ALLFN, "capped bodies: bundles of up to eight cuts");
+        hv_column_pass_upto<CutT, 2, KCAP, NW, HESS, LR>(As, AsL, ldA, k, zrow, n, n_pad, tid, lam, Pw);
+        return;
+    }
     if constexpr (ALLFN) {
         switch (hv_padded(k)) {
         case 2: hv_column_pass_fn<CutT, 2, NW, HESS, LR, GSRC>(As, AsL, ldA, k, zrow, n, n_pad, tid, lam, Pw); break;

@@ -21,6 +21,11 @@ namespace {
 
 static_assert(NWAVE == TM, "one wave per sample in the dual phase");
 
+// Round class of the Bibsonomy headline instance (fused_fc_solve_kernel, CLASSES): rounds 0 .. 7, whose bundles hold at most
+// eight cuts, run the dual body compiled for that cap.  One class: bodies for up to 4 and up to 6 cuts on top of it measured
+// within the noise of this one (profiles/round_classes_ab.md) and are not in the tree.
+constexpr int ROUND_CLASS_CAP = HV_K1MAX;
+
 // One kernel parameter, read through the kernel-argument segment (s_load) by both phases.
 //
 // Both phases are INLINED into the round loop.  As non-inlined functions (round 1) each of them saved and restored
@@ -80,8 +85,12 @@ __device__ __forceinline__ void reset_sample(const icnn_be_state &st, const Solv
 // (pick_shape_instance below): n, the widths and everything that follows from them are constants of the instance.
 // GROUPED: -1 = args.grouped decides at run time; 0 / 1 = the launcher's layout decision is the instance's, and the dual body of
 // the other form is not compiled in.
-template <bool RL, int KT, bool IPM = false, bool SLICED = false, typename Shape = DynShape, int GROUPED = -1>
+// CLASSES (with GROUPED = 0, KT = 16, variant dual on the fused VALU pass): rows_cap = round + 1 is wave-uniform and known from
+// the round alone, so the rounds whose bundles hold at most ROUND_CLASS_CAP cuts run a dual body compiled for that cap
+// (dual_step_body, KCAP): no function call in its Newton loop, no MFMA sweep compiled in.  Later rounds run the body as it is.
+template <bool RL, int KT, bool IPM = false, bool SLICED = false, typename Shape = DynShape, int GROUPED = -1, bool CLASSES = false>
 __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args) {
+    static_assert(!CLASSES || (GROUPED == 0 && KT == 16 && !RL && !IPM && !SLICED), "round classes: the ungrouped 16-slot dual instance");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     KArgs *kp0 = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     {
@@ -111,9 +120,13 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
         if (GROUPED < 0 ? !k.grouped : GROUPED == 0) {
             if (mine) {                                             // phase B: wave w = sample w of the tile
                 const int rows_cap = round + 1 < k.da.st.slots ? round + 1 : k.da.st.slots;
-                dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63,
-                                                                        smem + k.samples_off + wave * k.sample_bytes, round, rows_cap,
-                                                                        reinterpret_cast<const float *>(smem + k.crow_off));
+                unsigned char *region = smem + k.samples_off + wave * k.sample_bytes;
+                const float *crow = reinterpret_cast<const float *>(smem + k.crow_off);
+                if (CLASSES && round < ROUND_CLASS_CAP)             // rows_cap <= round + 1 <= the cap of the class
+                    dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape, CLASSES ? ROUND_CLASS_CAP : 0>(
+                        k.da, u, thread_id() & 63, region, round, rows_cap, crow);
+                else
+                    dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63, region, round, rows_cap, crow);
             }
             __syncthreads();                                        // y, skip flags visible to the next phase A
             continue;
@@ -485,7 +498,13 @@ hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, co
     if (st.variant == ICNN_BE_VARIANT_PDIPM) kern = big ? fused_fc_solve_kernel<false, 32, true> : fused_fc_solve_kernel<false, 16, true>;
     if (budget > 0) kern = big ? fused_fc_solve_kernel<false, 32, false, true> : fused_fc_solve_kernel<false, 16, false, true>;
     switch (pick_shape_instance(args, lay)) {           // (never with a budget, never another variant)
-    case ICNN_BE_SHAPE_BIBTEX_KT16: kern = fused_fc_solve_kernel<false, 16, false, false, BibtexShape, 0>; break;
+    case ICNN_BE_SHAPE_BIBTEX_KT16:
+        // the round classes are compiled for the fused VALU pass: a launch that keeps the MFMA sweep, or asks for the one body,
+        // runs the instance without them
+        kern = (st.flags & (ICNN_BE_FLAG_NO_ROUND_CLASSES | ICNN_BE_FLAG_MFMA_CONTRACTION))
+                   ? fused_fc_solve_kernel<false, 16, false, false, BibtexShape, 0>
+                   : fused_fc_solve_kernel<false, 16, false, false, BibtexShape, 0, true>;
+        break;
     case ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED: kern = fused_fc_solve_kernel<false, 32, false, false, BibtexShape, 1>; break;
     default: break;
     }

@@ -138,6 +138,10 @@ extern "C" {
                                           * network's shape (ICNN_BE_SHAPE_*), always the generic one that reads the shape from
                                           * its arguments.  Same operations in the same order: bit-identical results (the
                                           * identity tests and same-library A/B timings use it) */
+#define ICNN_BE_FLAG_NO_ROUND_CLASSES 1024 /* icnn_be_solve_fc (additive to ABI 12): the Bibsonomy instance of the persistent tile
+                                          * kernel runs one dual body in every round instead of the body compiled for the
+                                          * rounds whose bundles hold at most 8 cuts in rounds 0 .. 7 (be_fused.hip).  Same operations
+                                          * in the same order: bit-identical results (identity tests, same-library A/B) */
 #define ICNN_BE_FLAG_F64_ENERGY 32        /* icnn_be_dual_step: f is float64 [B] whatever the cut dtype (an `fg` that
                                           * returns float64 energies with float32 gradients: the reference's
                                           * bi = fi - sum(gi * x) keeps fi's precision, dual :143) */
