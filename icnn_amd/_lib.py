@@ -60,6 +60,7 @@ EXPORTS = [
     "icnn_be_conv_context_work_floats", "icnn_be_conv_context", "icnn_be_conv_clamp",
     "icnn_be_debug_profile", "icnn_be_debug_profile_fc", "icnn_be_debug_profile_conv", "icnn_be_debug_profile_phases",
     "icnn_be_debug_fast_math", "icnn_be_debug_trace", "icnn_be_debug_solve_plan", "icnn_be_debug_adam_plan", "icnn_be_debug_dual_plan",
+    "icnn_be_debug_dual_step_body",
     "icnn_be_debug_shape_instance", "icnn_be_debug_fc_deal",
     "icnn_be_fc_grad_floats", "icnn_be_fc_surrogate_grad_work_floats", "icnn_be_fc_surrogate_grad",
     "icnn_be_conv_grad_floats", "icnn_be_conv_surrogate_grad_work_floats", "icnn_be_conv_surrogate_grad",
@@ -401,6 +402,8 @@ def load():
     lib.icnn_be_debug_adam_plan.restype = C.c_int
     lib.icnn_be_debug_dual_plan.argtypes = [C.POINTER(State), C.c_int, C.POINTER(C.c_int * 8)]
     lib.icnn_be_debug_dual_plan.restype = C.c_int
+    lib.icnn_be_debug_dual_step_body.argtypes = [C.POINTER(State), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.icnn_be_debug_dual_step_body.restype = C.c_int
     lib.icnn_be_debug_shape_instance.argtypes = [C.POINTER(FcModel), C.POINTER(State)]
     lib.icnn_be_debug_shape_instance.restype = C.c_int
     lib.icnn_be_debug_fc_deal.argtypes = [C.POINTER(FcModel), C.POINTER(C.c_int), C.c_int]

@@ -91,6 +91,14 @@ class BundleState:
         _lib.check(self.lib.icnn_be_dual_step(C.byref(self.c_state), t, f.data_ptr(), g.data_ptr(),
                                               self.stream()), "icnn_be_dual_step")
 
+    def step_body(self, t, f: torch.Tensor, g: torch.Tensor, which: int, rows_mode: int = 0):
+        """step() through one of the dual bodies only the persistent tile kernel contains (icnn_be_debug_dual_step_body;
+        diagnostic, float32 cuts at n = 159 only)."""
+        assert f.is_contiguous() and g.is_contiguous() and g.dtype == self.G.dtype == f.dtype == torch.float32
+        assert f.shape == (self.B,) and g.shape == (self.B, self.n)
+        _lib.check(self.lib.icnn_be_debug_dual_step_body(C.byref(self.c_state), t, f.data_ptr(), g.data_ptr(), which, rows_mode,
+                                                         self.stream()), "icnn_be_debug_dual_step_body")
+
 
 def fg_evaluations(n_iters, nIter, finished=None):
     """How many times the reference's solveBatch evaluated `fg` on the minibatch -- the number of BatchNorm folds of

@@ -294,6 +294,13 @@ int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[8]) {
     return 0;
 }
 
+int icnn_be_debug_dual_step_body(const icnn_be_state *st, int t, const void *f, const void *g, int which, int rows_mode,
+                                 void *stream) {
+    if (int rc = check_state(st)) return rc;
+    if (t < 0 || t >= (st->iters > 0 ? st->iters : st->slots) || !f || !g) return ICNN_BE_EINVAL;
+    return done(icnn_be::launch_dual_body_probe(*st, t, f, g, which, rows_mode, static_cast<hipStream_t>(stream)));
+}
+
 size_t icnn_be_fc_pack_floats(const icnn_be_fc_model *shape) {
     if (!shape || icnn_be::fc_check_model(*shape) != 0) return 0;
     return icnn_be::fc_pack_floats(*shape);

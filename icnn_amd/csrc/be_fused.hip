@@ -350,8 +350,15 @@ __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArg
 
 }  // namespace
 
-bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int per_wg, bool resume, FusedRowsLayout &out) {
+// LDS of one sample's dual step in the persistent kernels: the carve-up of a bundle that fills every slot, without constant
+// rows of its own (the workgroup shares one pair)
+static int sample_region_bytes(const icnn_be_state &st, int ldA, int n_pad, int n_leaves) {
     const bool rl = st.variant == ICNN_BE_VARIANT_RL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
+    return (carve(st.slots > 15 ? 32 : 16, st.slots, ldA, n_pad, 4, n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+}
+
+bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int per_wg, bool resume, FusedRowsLayout &out) {
+    const bool ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
     if (st.cut_dtype != ICNN_BE_CUT_F32 || per_wg < 1 || per_wg > ROWS_MAX) return false;
     if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || (ipm && resume)) return false;
     PairwisePlan plan;
@@ -359,7 +366,7 @@ bool fused_rows_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int p
     const int n_pad = (st.n + 15) & ~15, ldA = dual_row_pitch(n_pad);
     RowsLayout lay;
     out.dual_off = (rows_layout(m, per_wg, lay) + 15) & ~15;
-    out.sample_bytes = (carve(st.slots > 15 ? 32 : 16, st.slots, ldA, n_pad, 4, plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+    out.sample_bytes = sample_region_bytes(st, ldA, n_pad, plan.n_leaves);
     out.crow_off = out.dual_off + per_wg * out.sample_bytes;
     out.lds = out.crow_off + ((2 * ldA * 4 + 15) & ~15);
     return out.lds <= LDS_BYTES;
@@ -375,7 +382,7 @@ bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int t
     if (fill_args(m, fa, fg_bytes) != 0 || !pw_build(plan, st.n)) return false;
     const bool big = st.slots > 15;
     const int n_pad = (st.n + 15) & ~15, ldA = dual_row_pitch(n_pad);
-    out.sample_bytes = (carve(big ? 32 : 16, st.slots, ldA, n_pad, 4, plan.n_leaves, rl, 1, false, ipm).total + 15) & ~15;
+    out.sample_bytes = sample_region_bytes(st, ldA, n_pad, plan.n_leaves);
     // phase B: sixteen bundles from offset 0 (they overlay phase A's buffers); the shared constant rows live behind
     // whichever region is larger, where neither phase overwrites them
     const int crow_bytes = (2 * ldA * 4 + 15) & ~15, dual_bytes = TM * out.sample_bytes;
@@ -442,13 +449,54 @@ typedef FixedShape<159, 600, 159, 1> BibtexShape;
 // Everything a fixed instance holds as a constant against what the launcher's own functions (fill_args with pack_offsets,
 // make_dual_args with pw_build) produced for THIS model and state: the instance is taken only where all of it agrees.
 template <typename Shape>
-bool shape_matches(const FcArgs &fa, const DualArgs &da) {
+bool dual_shape_matches(const DualArgs &da) {       // the half a dual body holds: n, the row pitch, the pairwise-sum plan
     const PairwisePlan &p = da.plan, &q = Shape::PLAN;
-    bool ok = fc_geom_same(fa, Shape::GEOM) && da.st.n == Shape::N_ROW && da.n_pad == Shape::N_PAD && da.ldA == Shape::LDA &&
+    bool ok = da.st.n == Shape::N_ROW && da.n_pad == Shape::N_PAD && da.ldA == Shape::LDA &&
               p.n_leaves == q.n_leaves && p.n_prog == q.n_prog && p.depth == q.depth;
     for (int i = 0; ok && i < q.n_leaves; ++i) ok = p.leaf_start[i] == q.leaf_start[i] && p.leaf_len[i] == q.leaf_len[i];
     for (int i = 0; ok && i < q.n_prog; ++i) ok = p.prog[i] == q.prog[i];
     return ok;
+}
+template <typename Shape>
+bool shape_matches(const FcArgs &fa, const DualArgs &da) {
+    return fc_geom_same(fa, Shape::GEOM) && dual_shape_matches<Shape>(da);
+}
+
+// One round of a dual body that only the fixed instances above contain (icnn_be_debug_dual_step_body), on its own: one
+// single-wave workgroup per sample, called the way fused_fc_solve_kernel calls it -- DualArgs first in the argument struct and
+// handed on as a reference into the kernel-argument segment, the constant rows written once to LDS and shared, rows_cap formed
+// as the ungrouped (rows_mode 0) or the grouped round loop (rows_mode 1: kk) forms it, the register budget of the 16-wave
+// workgroup (the launch bound, not the launch, sets it).
+struct BodyProbeArgs {
+    DualArgs da;       // first: dual_step_body re-reads it at offset 0 of the kernel-argument segment
+    int round, rounds, rows_mode, crow_off;
+};
+typedef const __attribute__((address_space(4))) BodyProbeArgs KPArgs;
+
+template <int KT, int KCAP>
+__global__ __launch_bounds__(NTHREADS) void dual_body_probe_kernel(BodyProbeArgs args) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    {
+        float *crow = reinterpret_cast<float *>(smem + args.crow_off);  // behind the sample's region
+        for (int j = thread_id(); j < 2 * BibtexShape::LDA; j += 64) crow[j] = j < BibtexShape::LDA ? 0.f : 1.f;
+    }
+    __syncthreads();
+    KPArgs *kp = (KPArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    int u = blockIdx.x;
+    asm volatile("" : "+s"(kp), "+s"(u));
+    KPArgs &k = *kp;
+    const int round = k.round;
+    int rows_cap = round + 1 < k.da.st.slots ? round + 1 : k.da.st.slots;
+    if (k.rows_mode) {                                              // the grouped loop: sized by the cuts the sample holds
+        int kk = 0;
+        if (k.da.st.finished[u] == 0 && k.da.st.t_next[u] < k.rounds) kk = k.da.st.count[u] + 1;
+        kk = uni(kk);
+        if (kk > k.da.st.slots) kk = k.da.st.slots;
+        if (kk <= 0) return;
+        rows_cap = kk;
+    }
+    dual_step_body<float, KT, 1, false, false, false, 0, false, BibtexShape, KCAP>(
+        k.da, u, thread_id() & 63, smem, round, rows_cap, reinterpret_cast<const float *>(smem + k.crow_off));
 }
 
 // ICNN_BE_SHAPE_*: the instance a launch with these arguments and this layout takes
@@ -509,6 +557,29 @@ hipError_t launch_fused_fc_solve(const icnn_be_fc_model &m, const float *ctx, co
     default: break;
     }
     return launch_kernel(kern, dim3((st.batch + tile_rows - 1) / tile_rows), dim3(NTHREADS), lay.lds, stream, args);
+}
+
+hipError_t launch_dual_body_probe(const icnn_be_state &st, int round, const void *f, const void *g, int which, int rows_mode,
+                                  hipStream_t stream) {
+    BodyProbeArgs args{};
+    if (st.variant != ICNN_BE_VARIANT_DUAL || st.cut_dtype != ICNN_BE_CUT_F32 ||
+        (st.flags & (ICNN_BE_FLAG_GLOBAL_BUNDLE | ICNN_BE_FLAG_TIME_SLICE)) ||
+        !make_dual_args(args.da, st, f, g, round, 0, st.slots, nullptr) || !dual_shape_matches<BibtexShape>(args.da))
+        return hipErrorInvalidValue;
+    const bool big = st.slots > 15;
+    if (which < 1 || which > 3 || big != (which == 3) || rows_mode < 0 || rows_mode > 1 || (rows_mode == 1 && which == 2))
+        return hipErrorInvalidValue;
+    // the capped body is compiled for rows_cap <= round + 1 <= its cap and for the fused VALU pass
+    if (which == 2 && (round >= ROUND_CLASS_CAP || (st.flags & ICNN_BE_FLAG_MFMA_CONTRACTION))) return hipErrorInvalidValue;
+    if (st.batch == 0) return hipSuccess;
+    args.round = round;
+    args.rounds = st.iters > 0 ? st.iters : st.slots;
+    args.rows_mode = rows_mode;
+    args.crow_off = sample_region_bytes(st, args.da.ldA, args.da.n_pad, args.da.plan.n_leaves);
+    const int lds = args.crow_off + ((2 * args.da.ldA * 4 + 15) & ~15);
+    auto kern = which == 1 ? dual_body_probe_kernel<16, 0> : which == 2 ? dual_body_probe_kernel<16, ROUND_CLASS_CAP>
+                                                                        : dual_body_probe_kernel<32, 0>;
+    return launch_kernel(kern, dim3(st.batch), dim3(64), lds, stream, args);
 }
 
 }  // namespace icnn_be

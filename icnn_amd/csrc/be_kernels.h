@@ -257,6 +257,11 @@ hipError_t launch_fused_rows_solve(const icnn_be_fc_model &m, const float *ctx, 
                                    const SolveReset &reset = SolveReset{}, const RowsValue *value = nullptr);
 // ICNN_BE_SHAPE_*: the instance of the persistent tile kernel launch_fused_fc_solve takes for these arguments (host arithmetic)
 int fused_shape_instance(const icnn_be_fc_model &m, const icnn_be_state &st, int tile_rows, int budget);
+// icnn_be_debug_dual_step_body: round `round` of a dual body that only the tile kernel's Bibsonomy instances contain, on its own
+// (which: 1 the 16-slot body, 2 the same capped at the round class, 3 the 32-slot body; rows_mode: 0 rows_cap from the round, 1
+// from the cuts each sample holds).  hipErrorInvalidValue, nothing launched: what the entry's contract in icnn_be.h refuses
+hipError_t launch_dual_body_probe(const icnn_be_state &st, int round, const void *f, const void *g, int which, int rows_mode,
+                                  hipStream_t stream);
 int dual_waves(int n, int cut_dtype, int variant);
 long long *dual_profile_buffer();
 void set_dual_trace_buffer(long long *buf);

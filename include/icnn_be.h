@@ -1392,6 +1392,25 @@ ICNN_BE_API int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int 
  */
 ICNN_BE_API int icnn_be_debug_dual_plan(const icnn_be_state *st, int t, int out[8]);
 /*
+ * One round of a dual body that only the persistent tile kernel's Bibsonomy instances contain, without the tile kernel around it
+ * (additive to ABI 12; tests/test_dual_body_probe.py).  Semantics of icnn_be_dual_step(st, t, f, g): one launch, one wave per
+ * sample, no update budget, the same operations in the same order -- so the same bits, newton_iters and status included, wherever
+ * both form their sums by the same routine.  The body is called the way the tile kernel calls it: its arguments first in the
+ * kernel-argument struct, the two constant rows shared in LDS, the sample's LDS region sized by the tile layout.
+ *   which 1      the body of ICNN_BE_SHAPE_BIBTEX_KT16 from round 8 on (and of every round under ICNN_BE_FLAG_NO_ROUND_CLASSES)
+ *   which 2      the body of its rounds 0..7: compiled for at most eight cuts, no MFMA sweep in it
+ *   which 3      the body of ICNN_BE_SHAPE_BIBTEX_KT32_GROUPED
+ *   rows_mode 0  the staging holds min(t + 1, slots) rows, as in the ungrouped round loop
+ *   rows_mode 1  per sample count + 1 rows (at most slots), as the grouped loop sizes it; a finished sample, or one whose own
+ *                iteration counter is past the last iteration, is left alone.  With which 1 and 3.
+ * ICNN_BE_EINVAL, before any launch, unless: the variant is dual with float32 cuts; n is the instances' 159; slots <= 15 for
+ * which 1 and 2, slots > 15 for which 3; for which 2 t < 8 and ICNN_BE_FLAG_MFMA_CONTRACTION is not set; neither
+ * ICNN_BE_FLAG_GLOBAL_BUNDLE nor ICNN_BE_FLAG_TIME_SLICE is set; and whatever icnn_be_dual_step refuses.  Batch 0: 0, nothing
+ * is launched.  Not for production use.
+ */
+ICNN_BE_API int icnn_be_debug_dual_step_body(const icnn_be_state *st, int t, const void *f, const void *g, int which,
+                                             int rows_mode, void *stream);
+/*
  * The instance of the persistent tile kernel icnn_be_solve_fc launches for this model and state on the current device
  * (additive to ABI 12): ICNN_BE_SHAPE_GENERIC -- the kernel that reads the network's shape from its arguments; also where the
  * plan (icnn_be_debug_solve_plan) is not ICNN_BE_PATH_TILE -- or the id of an instance compiled for one shape.  Such an instance

@@ -65,12 +65,28 @@ def _sample_rng(seed, u, bump):
     return np.random.RandomState([seed, u, bump])
 
 
-def synth_round(seed, n, slots, cut_dtype, variant, t, ks, iters=0, f64_energy=False, reseed=()):
+def full_bundle(rng, n, cnt, cut_dtype, c, sigma):
+    """cnt + 1 cuts that survive the round: tangents of phi(y) = c/2 |y - ybar|^2, ybar uniform in [0.2, 0.8]^n, at points
+    y* + sigma randn clipped to [0.01, 0.99], y* the minimiser of phi - H (Newton on c (y - ybar) + logit(y) = 0).  Cuts of one
+    strongly convex function taken around the round's own solution all carry weight there, where random cuts prune each other.
+    Returns (points [cnt + 1, n], g = c (p - ybar) in the cut dtype, h = phi(p) - <g, p>, phi(p)); the last is the round's."""
+    ybar = 0.2 + 0.6 * rng.rand(n)
+    ystar = np.full(n, 0.5)
+    for _ in range(60):
+        ystar = np.clip(ystar - (c * (ystar - ybar) + np.log(ystar / (1 - ystar))) / (c + 1 / (ystar * (1 - ystar))), 1e-9, 1 - 1e-9)
+    pts = np.clip(ystar + sigma * rng.randn(cnt + 1, n), 0.01, 0.99)
+    g = (c * (pts - ybar)).astype(cut_dtype)
+    phi = 0.5 * c * np.sum((pts - ybar) ** 2, axis=1)
+    return pts, g, phi - np.sum(g.astype(F64) * pts, axis=1), phi
+
+
+def synth_round(seed, n, slots, cut_dtype, variant, t, ks, iters=0, f64_energy=False, reseed=(), full=None):
     """The state in front of round t.  ks[u] is the bundle size k the round works on (count = k - 1 older cuts + the new one), or
     (kind, k) for a special sample.  The older cuts sit in a random subset of the slots 0..t-1 in random order -- with iters >
     slots in a random subset of ALL slots, so that the new cut must take the lowest free one.  G = scale randn in the cut dtype,
     ys uniform, h = 0.3 randn at those slots; NaN in every other slot of G, ys, h, fvals and in all of lam; active[u, count:]
-    repeats an inactive slot.  Every sample has its own RandomState([seed, u, bump]), bump = dict(reseed).get(u, 0)."""
+    repeats an inactive slot.  Every sample has its own RandomState([seed, u, bump]), bump = dict(reseed).get(u, 0).
+    full = (c, sigma): the live samples' cuts, points and energies are full_bundle's instead -- bundles that stay full."""
     cut_dtype = np.dtype(cut_dtype).type
     f_dtype = F64 if (f64_energy or cut_dtype == F64) else F32
     B = len(ks)
@@ -107,6 +123,10 @@ def synth_round(seed, n, slots, cut_dtype, variant, t, ks, iters=0, f64_energy=F
         y[u] = 0.05 + 0.9 * rng.rand(n)
         g[u] = (scale * rng.randn(n)).astype(cut_dtype)
         f[u] = f_dtype(rng.randn())
+        if full is not None and kind == "live":
+            pts, g_all, h_all, phi = full_bundle(rng, n, cnt, cut_dtype, *full)
+            G[u, own], ys[u, own], h[u, own], fvals[u, own] = g_all[:cnt], pts[:cnt], h_all[:cnt], phi[:cnt]
+            y[u], g[u], f[u] = pts[cnt], g_all[cnt], f_dtype(phi[cnt])
         if kind == "dup":
             assert cnt >= 1
             g[u] = G[u, own[rng.randint(cnt)]]
@@ -382,6 +402,7 @@ K15 = (1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15)
 K31 = (1, 8, 9, 12, 13, 16, 17, 20, 21, 24, 25, 31)
 K10 = (1, 2, 5, 8, 9, 10)
 GLB, WPS, MFMA, E64 = FLAG_GLOBAL_BUNDLE, FLAG_WAVE_PER_SAMPLE, FLAG_MFMA_CONTRACTION, FLAG_F64_ENERGY
+FULL = (4.0, 0.05)                 # full_bundle's (c, sigma)
 
 CASES = [
     # one wave, float32, LDS, dual
@@ -452,6 +473,23 @@ CASES = [
     # single rows
     ("f32_16_dual_recycled", _plan("float", 16, 1, "dual"), F32, 10, 48, "dual", 0, 17, K10 + (DUP,), {"iters": 24}),
     ("f32_16_dual_f64energy", _plan("float", 16, 1, "dual"), F32, 10, 48, "dual", E64, 9, K10, {"f64_energy": True}),
+] + [
+    # n = 159 (n_pad 160): the width of the persistent tile kernel's fixed-shape instances, whose dual bodies
+    # tests/test_dual_body_probe.py runs on these same rows.  t <= 7: the rounds of the body capped at eight cuts.
+    ("f32_16_dual_n159_%s" % tag, _plan("float", 16, 1, "dual"), F32, slots, 159, "dual", 0, t, ks)
+    for tag, slots, t, ks in (("t7", 10, 7, (1, 2, 3, 4, 5, 6, 7, 8, FIN, DUP, ZERO)), ("t5", 10, 5, (1, 2, 3, 4, 5, 6, ("dup", 3))),
+                              ("t3", 10, 3, (1, 2, 3, 4, ("dup", 2))), ("t0", 10, 0, (1, ZERO)), ("t9", 10, 9, (1, 2, 4, 5, 8, 9, 10, DUP)),
+                              ("s5_t4", 5, 4, (1, 2, 3, 4, 5)))       # s5: rows_cap is held by the slots, not by t + 1
+] + [
+    ("f32_32_dual_n159", _plan("float", 32, 1, "dual"), F32, 31, 159, "dual", 0, 30, K31 + (FIN, DUP, ZERO)),
+] + [
+    # the same width on bundles that stay full (full_bundle): random cuts prune hard -- the k = 8 sample of the t7 row above ends
+    # its round with 3 cuts
+    ("f32_16_dual_n159_full_%s" % tag, _plan("float", 16, 1, "dual"), F32, slots, 159, "dual", 0, t, ks, {"full": FULL})
+    for tag, slots, t, ks in (("t7", 10, 7, (2, 3, 4, 5, 6, 7, 8, 8)), ("t5", 10, 5, (2, 3, 4, 5, 6, 6)), ("t3", 10, 3, (2, 3, 4, 4)),
+                              ("t1", 10, 1, (2, 2)), ("t9", 10, 9, (8, 9, 10, 10)), ("s8_t7", 8, 7, (7, 8, 8)))
+] + [
+    ("f32_32_dual_n159_full_t20", _plan("float", 32, 1, "dual"), F32, 31, 159, "dual", 0, 20, (8, 9, 12, 13, 16, 17, 20, 21), {"full": FULL}),
 ]
 CASE_IDS = [c[0] for c in CASES]
 
@@ -537,6 +575,10 @@ RESEED = {
     ('f32_32_pdipm8_glb_n2048', 4): 1,
     ('f32_32_pdipm8_glb_n2048', 5): 2,
     ('f32_32_pdipm8_glb_n2048', 6): 1,
+    # the full rows' own condition (test_full_rows_stay_full): a draw whose oracle round keeps 16 and more cuts
+    ('f32_32_dual_n159_full_t20', 4): 11,
+    ('f32_32_dual_n159_full_t20', 6): 13,
+    ('f32_32_dual_n159_full_t20', 7): 5,
 }
 
 
@@ -557,7 +599,8 @@ def case_state(name):
         return base
     _, _, cut, slots, n, variant, flags, t, ks = case[:9]
     reseed = tuple((u, b) for (row, u), b in sorted(RESEED.items()) if row == name)
-    return synth_round(zlib.crc32(name.encode()), n, slots, cut, variant, t, ks, opt.get("iters", 0), opt.get("f64_energy", False), reseed)
+    return synth_round(zlib.crc32(name.encode()), n, slots, cut, variant, t, ks, opt.get("iters", 0), opt.get("f64_energy", False), reseed,
+                       opt.get("full"))
 
 
 PERTURB_DRAWS = 3

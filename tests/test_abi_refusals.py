@@ -355,6 +355,36 @@ def test_refusals(name):
     assert not wrong, "%s:\n  %s" % (name, "\n  ".join(wrong))
 
 
+def test_debug_dual_step_body_refusals():
+    """icnn_be_debug_dual_step_body (be_api.hip; it takes a state, so it is not one of ENTRIES): what it refuses before any
+    launch, next to the nearest call it accepts.  Every state here has batch 0, where an accepted call returns 0 and launches
+    nothing either."""
+    fn = _lib.load().icnn_be_debug_dual_step_body
+    MFMA, GLB, SLICE = _lib.FLAG_MFMA_CONTRACTION, _lib.FLAG_GLOBAL_BUNDLE, _lib.FLAG_TIME_SLICE
+
+    def call(t=3, which=1, rows_mode=0, f=P(40), g=P(41), st="state", **kw):
+        s = fill(_lib.State, **dict(dict(batch=0, n=159, slots=10, cut_dtype=_lib.CUT_F32, variant=_lib.VARIANT["dual"], flags=0, iters=0), **kw))
+        return fn(C.byref(s) if st == "state" else st, t, f, g, which, rows_mode, None)
+
+    accepted = [dict(), dict(which=2), dict(rows_mode=1), dict(t=0), dict(t=9), dict(which=2, t=7), dict(which=1, flags=MFMA),
+                dict(slots=15), dict(which=2, slots=15), dict(which=3, slots=16), dict(which=3, slots=31, t=30, rows_mode=1),
+                dict(which=3, slots=16, flags=MFMA), dict(slots=10, iters=24, t=20), dict(which=2, slots=5, t=4),
+                dict(flags=_lib.FLAG_F64_ENERGY)]
+    refused = [dict(st=None), dict(f=None), dict(g=None), dict(t=-1), dict(t=10), dict(slots=10, iters=24, t=24),
+               dict(variant=_lib.VARIANT["rl"]), dict(variant=_lib.VARIANT["pdipm"]), dict(cut_dtype=_lib.CUT_F64),
+               dict(n=158), dict(n=160), dict(n=48),
+               dict(which=0), dict(which=4), dict(which=-1), dict(rows_mode=-1), dict(rows_mode=2), dict(which=2, rows_mode=1),
+               dict(which=3), dict(which=3, slots=15), dict(which=1, slots=16), dict(which=2, slots=16),
+               dict(which=2, t=8), dict(which=2, t=9), dict(which=2, slots=10, iters=24, t=8), dict(which=2, flags=MFMA),
+               dict(flags=GLB), dict(which=3, slots=31, flags=GLB), dict(flags=SLICE), dict(which=2, flags=SLICE)]
+    refused += [{name: None} for name in pointers(_lib.State, skip=("scratch", "fvals"))]
+    wrong = ["accepted case %r: %d" % (kw, call(**kw)) for kw in accepted if call(**kw) != 0]
+    wrong += ["refused case %r: %d" % (kw, call(**kw)) for kw in refused if call(**kw) != EINVAL]
+    if call(slots=_lib.MAX_SLOTS + 1, which=3) != ELIMIT:
+        wrong.append("more slots than ICNN_BE_MAX_SLOTS")
+    assert not wrong, "\n  ".join(wrong)
+
+
 def test_every_moved_entry_is_covered():
     assert set(ENTRIES) <= set(_lib.EXPORTS)
     assert len(ENTRIES) == 61

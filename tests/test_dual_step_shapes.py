@@ -24,6 +24,11 @@ dual_step_wide_kernel row; the interior point's one-wave fallback at n = 2560 be
 the eight-wave VALU pass and ipm_solve_waves reach 20 cuts only where 8 hv_pitch(20) = 1856 and 8 x 252 = 2016 fit the row, so
 their 20 | 21 rows are at n = 2048; the interior point's unrolled passes reach 12 cuts for 103 <= n_pad <= 192 (n = 177) and
 ipm_solve_wide_one_fn 20 cuts from n_pad = 252 (n = 255).
+
+The rows at n = 159 are the width of the persistent tile kernel's fixed-shape instances; tests/test_dual_body_probe.py runs the
+dual bodies that only that kernel contains on the same states.  Random cuts prune each other, so the `full` rows there hold cuts
+of one strongly convex function around the round's solution (dual_step_ref.full_bundle): their bundles leave the round as full
+as they entered it (test_full_rows_stay_full).
 """
 import ctypes as C
 import os
@@ -262,6 +267,29 @@ def test_preconditions_of_the_comparison(name):
     assert not bad, bad
 
 
+FULL_ROWS = [c[0] for c in R.CASES if "full" in R.case_options(c)]
+
+
+@pytest.mark.parametrize("name", FULL_ROWS)
+def test_full_rows_stay_full(name):
+    """What the `full` rows are for, as a condition on the inputs: up to the cap of eight (HV_K1MAX, the round class of the tile
+    kernel) every bundle size the row lists is the size of some sample's bundle AFTER the oracle's round -- that many multipliers
+    stay positive --, and the 31-slot row keeps 16 and more cuts somewhere.  Reached through RESEED, never by exempting a
+    sample."""
+    case = _case(name)
+    s = R.case_state(name)
+    ref, _ = R.case_reference(name)
+    assert set(s.kind) == {"live"} and len(FULL_ROWS) == 7
+    after = set(ref["count"].tolist())
+    for k in sorted({_k_of(k) for k in case[8]}):
+        if k <= R.HV_K1MAX:
+            assert k in after, (name, k, ref["count"].tolist())
+    for u in range(s.B):                    # no rank-test exit, no pruned-to-one sample: every round here is a Newton solve
+        assert ref["lam_full"][u] is not None and ref["newton"][u] >= 2 and ref["count"][u] >= 2
+    if case[3] > 15:
+        assert max(after) >= 16
+
+
 def _oracle_optimality(name):
     s = R.case_state(name)
     ref, _ = R.case_reference(name)
@@ -299,15 +327,19 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
-def _launch(s, flags, plan=None):
-    """(state before, state after) of one icnn_be_dual_step launch on the row's state"""
+def _launch(s, flags, plan=None, step=None):
+    """(state before, state after) of one icnn_be_dual_step launch on the row's state; step(st, t, f, g): another entry's launch
+    in its place (tests/test_dual_body_probe.py)"""
     import torch
     st, f, g = s.to_device(flags)
     if plan is not None:                 # the state that is launched gets the instance the row names
         from icnn_amd import _lib
         assert _lib.dual_plan(st.c_state, s.t)[:6] == plan
     before = _snapshot(st)
-    st.step(s.t, f, g)
+    if step is not None:
+        step(st, s.t, f, g)
+    else:
+        st.step(s.t, f, g)
     torch.cuda.synchronize()
     return before, _snapshot(st)
 
