@@ -1,5 +1,6 @@
-// Device code of the dual step (included by be_dual.hip and be_fused.hip): helpers, the f64 MFMA contractions,
-// the register-resident small algebra and dual_step_body.  Everything is in an anonymous namespace.
+// Device code of the dual step (included by be_dual.hip and be_fused.hip): the body's config (DualCfg), dual_step_body and the
+// two kernels that are nothing but the body.  The helpers live in headers by subject, included below.  Everything is in an
+// anonymous namespace.
 #pragma once
 // Dual step of the bundle-entropy method: one wave64 = one sample.
 //
@@ -23,6 +24,12 @@
 #include "be_common.h"
 #include "be_kernels.h"
 #include "icnn_be.h"
+
+#include "be_dual_cut.h"     // cut types, the LDS carve-up, wave-uniform and opaque values
+#include "be_dual_mfma.h"    // the float64 MFMA contractions
+#include "be_dual_math.h"    // rcp_nr, fast_exp, fast_log, softplus_fast, sigmoid_fast
+#include "be_dual_solve.h"   // reduced Newton solves and inertia counts (with be_dual_dpp_rows.h)
+#include "be_dual_cols.h"    // row reductions and the column loop
 
 namespace icnn_be {
 
@@ -48,970 +55,77 @@ constexpr double ACCEL_NEG_RESID = 1e-10;  // oscillating subsequences (negative
 constexpr double ACCEL_D2MAX = 1e-3;   // only once lam_t - lam_{t-2} is this small
 constexpr double ACCEL_RMAX = 0.98;    // and the contraction ratio is below this
 
-template <typename T> struct Cut;
-// NumPy's float32 exp is not correctly rounded (39 % of results are 1-2 ulp off); the
-// reference computes the k = 1 update y = 1/(1+exp(g)) with it in float32 (dual :168), and
-// that y is the point of the next cut.  To start from bit-identical iterates the device
-// evaluates the same operation sequence as numpy/_core/src/umath/
-// loops_exponent_log.dispatch.c.src (simd_exp_FLOAT, AVX512F/AVX2 paths): Cody-Waite
-// reduction by round(x log2e) with fused multiply-adds, a (5,2) rational minimax, scalef.
-// Every operation is a single IEEE float32 rounding, so the result is bit-identical
-// (checked against np.exp on the GPU box by tests/test_gpu_parity.py).
-__device__ __noinline__ float numpy_expf(float x) {
-#pragma clang fp contract(off)
-    if (x != x) return x;
-    if (x >= 88.72283935546875f) return __builtin_inff();
-    if (x <= -103.97208404541015625f) return 0.0f;
-    float q = x * 1.44269504088896341f;
-    q = q + 12582912.0f;                       // 0x1.8p23: round to nearest integer
-    q = q - 12582912.0f;
-    float r = __builtin_fmaf(q, -6.93145752e-1f, x);
-    r = __builtin_fmaf(q, -1.42860677e-6f, r);
-    float num = __builtin_fmaf(5.082762527590693718096e-04f, r, 6.757896990527504603057e-03f);
-    num = __builtin_fmaf(num, r, 5.114512081637298353406e-02f);
-    num = __builtin_fmaf(num, r, 2.473615434895520810817e-01f);
-    num = __builtin_fmaf(num, r, 7.257664613233124478488e-01f);
-    num = __builtin_fmaf(num, r, 9.999999999980870924916e-01f);
-    float den = __builtin_fmaf(2.159509375685829852307e-02f, r, -2.742335390411667452936e-01f);
-    den = __builtin_fmaf(den, r, 1.0f);
-    const float poly = num / den;
-    return ldexpf(poly, (int)q);
-}
-
-template <> struct Cut<float> {
-    static constexpr double eps = 1.1920928955078125e-07;
-    static __device__ __forceinline__ float sigmoid_neg(float g) {
-#pragma clang fp contract(off)
-        const float e = numpy_expf(g);
-        const float d = 1.0f + e;
-        return 1.0f / d;
-    }
-};
-template <> struct Cut<double> {
-    static constexpr double eps = 2.220446049250313e-16;
-    static __device__ __forceinline__ double sigmoid_neg(double g) { return 1.0 / (1.0 + exp(g)); }
-};
-
-__device__ __forceinline__ double softplus_stable(double v) {   // dual :6-12
-    return v > 1.0 ? log1p(exp(-v)) + v : log1p(exp(v));
-}
-
-// LDS carve-up shared by host (size query) and device.  The pairwise-sum scratch aliases the
-// Hm region (they are never live together).
-struct Carve {
-    int As, zs, ws, sp, yv, dv, Hm, Hp, ints, total;
-};
-constexpr int IPM_KMAX_WAVES = 20; // most cuts ipm_solve_waves (be_ipm_dev.h, 256-register kernels) takes
-// rl: variant RL keeps the softplus terms in a column buffer of its own; ipm: the interior-point variant needs that
-// buffer (residual ry) and two more (y, dy)
-__host__ __device__ inline Carve carve(int KT, int rows, int ldA, int n_pad, int cut_bytes, int n_leaves,
-                                       bool rl, int nw = 1, bool own_const_rows = true, bool ipm = false,
-                                       bool glb = false) {
-    Carve c;
-    int o = 0;
-    auto take = [&](int bytes) { int at = o; o += (bytes + 15) & ~15; return at; };
-    // + a row of zeros and a row of ones (contract_mfma) unless shared; glb: the rows live in device memory (st.scratch)
-    c.As = take(glb ? 0 : (rows + (own_const_rows ? 2 : 0)) * ldA * cut_bytes);
-    c.zs = take(n_pad * 8);
-    c.ws = take(n_pad * 8);
-    c.sp = (rl || ipm) ? take(n_pad * 8) : c.ws;
-    c.yv = ipm ? take(n_pad * 8) : c.zs;
-    c.dv = ipm ? take(n_pad * 8) : c.zs;
-    const int hp = (rows + 1) | 1;
-    int hm = rows * hp * 8;
-    const int scratch = (KT * n_leaves + 2 * KT) * 8;
-    if (scratch > hm) hm = scratch;
-    c.Hm = take(hm);
-    // per-wave partial contractions (the rank test's Gram matrix of ALL rows in both variants, the Newton system of variant
-    // dual) / each wave's own copy of the k x (k + 1) system (interior point on several waves).  Where this does not fit next to
-    // the column buffers the launcher takes the one-wave instance (launch_dual_step: interior point at n_pad = 3072 from 23 rows)
-    c.Hp = nw > 1 ? take(nw * rows * hp * 8) : c.Hm;
-    c.ints = take(KT * 4);
-    c.total = o;
-    return c;
-}
-
-// wave-uniform source lane -> value of that lane in every lane (v_readlane_b32 x2, no LDS)
-__device__ __forceinline__ double bcast(double x, int src_lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), src_lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src_lane);
-    return __hiloint2double(hi, lo);
-}
-
-// Arguments of a non-inlined device function arrive in VGPRs and pointers as generic addresses: the
-// compiler then treats every branch on them as divergent (exec-mask juggling) and every LDS access
-// as a FLAT access.  These helpers restore what the caller knows: wave-uniform scalars, LDS pointers.
-typedef const __attribute__((address_space(3))) double lds_cdouble;
-// Opaque use of a value: the compiler must materialise it here (stops it from sinking loads into branches).
-__device__ __forceinline__ void pin(double &v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin(float &v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ unsigned long long uni(unsigned long long v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ double uni(double v) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
-                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
-// D = A B^T style contractions over the columns of the LDS bundle with f64 MFMA.
-//   HESS = false:  Hm[i][j] = sum_c A[i][c] A[j][c]                     (Gram, rank test)
-//   HESS = true :  Hm[i][j] = sum_c A[i][c] w[c] A[j][c]   (j < k)       dual :36
-//                  Hm[i][k] = sum_c A[i][c] z[c]                         dual :35
-// A operand: lane (r16, q) holds A[ti*16+r16][c0+q]; B operand: lane holds B[c0+q][tj*16+r16].
-// Result: lane holds D[ti*16 + q + 4r][tj*16 + r16], r = 0..3 (f64 C/D map).
-// Small bundles (at most 8 rows/columns of output): v_mfma_f64_4x4x4_4b_f64, whose four 4x4 blocks
-// are used as the 2x2 tiling of an 8x8 result.  Measured lane layout on gfx950
-// (tools/probes/mfma_f64_4x4_probe.hip): with kq = lane>>4, block = (lane>>2)&3, r = lane&3
-//   A operand lane holds A_block[r][kq], B operand lane holds B_block[kq][r],
-//   result lane holds D_block[lane>>4][lane&3].
-// Same 4 columns per instruction as the 16x16x4 form, but 4 passes instead of 16.
-// Operand masking without arithmetic: the bundle in LDS is followed by a row of zeros (row `zrow`) and
-// a row of ones (row `zrow + 1`).  A lane whose output row/column is outside the bundle reads the zero
-// row; the lane that produces column k (A z) reads the ones row and z instead of a bundle row and w.
-// So per k-step a lane converts two cut values and does one multiply -- same bits as masking with 0/1
-// factors (x * 1 = x, fma(x, w, +-0) = x * w).
-struct NoLap { __device__ void operator()(int) const {} };
-template <typename CutT, bool HESS, typename LapF = NoLap>
-__device__ void contract_mfma_8x8(const CutT *As, int ldA, int k, const CutT *crow, int cbeg, int cend,
-                                  const double *ws, const double *zs, double *Hm, int HP, LapF lapf = LapF()) {
-    const int lane = thread_id() & 63, kq = lane >> 4, blk = (lane >> 2) & 3, r = lane & 3;
-    const int ra = 4 * (blk >> 1) + r, cb = 4 * (blk & 1) + r;
-    const bool zcol = HESS && cb == k;
-    // crow: the constant rows -- zeros at crow[0 .. ldA), ones at crow[ldA .. 2 ldA)
-    const CutT *pa = (ra < k ? As + ra * ldA : crow) + kq;
-    const CutT *pb = (cb < k ? As + cb * ldA : (zcol ? crow + ldA : crow)) + kq;
-    const double *pwz = (zcol ? zs : ws) + kq;
-    double acc0 = 0.0, acc1 = 0.0;                       // two chains hide the MFMA latency
-    cbeg = uni(cbeg); cend = uni(cend);                  // scalar loop control
-    // Software pipeline, distance one: the LDS reads of the next 16 columns are issued before the four
-    // MFMAs of the current 16, so the LDS round trip overlaps the arithmetic instead of preceding it.
-    // Two register sets alternate (no copies); scheduling barriers and an opaque use after the MFMAs
-    // keep the compiler from folding the prefetch back into "load, wait, use".
-    CutT xa[4], xb[4], ya[4], yb[4];
-    double xw[4], yw[4];
-    auto gather = [&](int c0, CutT (&ga)[4], CutT (&gb)[4], double (&gw)[4]) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            ga[s] = pa[c0 + 4 * s];
-            gb[s] = pb[c0 + 4 * s];
-            if (HESS) gw[s] = pwz[c0 + 4 * s];
-        }
-    };
-    auto stage = [&](int cnext, CutT (&ca)[4], CutT (&cb_)[4], double (&cw)[4], CutT (&na)[4], CutT (&nb)[4],
-                     double (&nw)[4]) {
-        gather(cnext, na, nb, nw);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const double av = (double)ca[s];
-            const double bv = HESS ? (double)cb_[s] * cw[s] : (double)cb_[s];
-            if (s & 1) acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(av, bv, acc1, 0, 0, 0);
-            else acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(av, bv, acc0, 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) { pin(na[s]); pin(nb[s]); if (HESS) pin(nw[s]); }
-    };
-    if (cbeg < cend) gather(cbeg, xa, xb, xw);
-    // Nothing may be outstanding when the loop is entered: otherwise the wait-count pass, merging the
-    // preheader state into the loop header, puts an lgkmcnt(0) right behind the prefetch of every stage.
-    __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0), visible to the wait-count pass
-    lapf(10);
-    const int clast = cend - 16;
-    for (int c0 = cbeg; c0 < cend; c0 += 32) {           // column range is a multiple of 16
-        stage(c0 + 16 < cend ? c0 + 16 : clast, xa, xb, xw, ya, yb, yw);
-        if (c0 + 16 < cend) stage(c0 + 32 < cend ? c0 + 32 : clast, ya, yb, yw, xa, xb, xw);
-    }
-    lapf(11);
-    const int row = 4 * (blk >> 1) + kq, col = 4 * (blk & 1) + r;
-    const int ncolsB = HESS ? k + 1 : k;
-    if (row < k && col < ncolsB) Hm[row * HP + col] = acc0 + acc1;
-}
-
-// 17 .. 20 cuts (round 6): TWO 16 x 16 tiles instead of the three of the (ti, tj) tiling below, whose tiles (0, 1) and (1, 1)
-// hold 1 .. 5 useful columns each.  A tile's A-operand rows and B-operand columns need not be contiguous -- every lane picks its
-// row pointer --, so the pairs that involve the extra rows e = 16 .. k - 1 fit ONE tile:
-//   tile 1   rows 0 .. 15  x  columns 0 .. 14 and A z (HESS) / 0 .. 15 (Gram);  H[i][15] = H[15][i] by symmetry (HESS)
-//   tile 2   rows 4 .. 19  x  columns { 16 .. 19,  A z,  0 .. 3,  15 }: (i, e) for i = 4 .. 19, (A z)_e, (e, i) for i = 0 .. 3
-//            mirrored into (i, e), and the diagonal entry (15, 15) that tile 1 gave up for A z.
-// A float64 16x16x4 MFMA occupies the wave for ~125 cycles with its operand set-up (tools/probes/dual_update_probe.hip: 5.0 k
-// cycles per tile sweep of 160 columns), so a Newton update at 17 .. 20 cuts drops from 15 k to 10 k cycles here, the rank
-// test's Gram matrix from 13.6 k to 9.4 k.  Same k-ordered fma chains per entry; the entries (i, 15), i < 15, and (i, e), i < 4,
-// are now formed with the OTHER factor carrying the weight w (H is symmetric: they differ from the three-tile result in the
-// last bit).  Every kernel takes this path for such bundles, so the dispatch paths stay bit-identical among themselves.
-template <typename CutT, bool HESS>
-__device__ void contract_mfma_cover2(const CutT *As, int ldA, int k, const CutT *crow, int cbeg, int cend, const double *ws,
-                                     const double *zs, double *Hm, int HP) {
-    const int lane = thread_id() & 63, r16 = lane & 15, q = lane >> 4;
-    cbeg = uni(cbeg); cend = uni(cend);
-    constexpr int ZC = 64, NONE = 65;                          // B-operand column codes besides a bundle row
-#pragma unroll 1
-    for (int t = 0; t < 2; ++t) {
-        const int ra = t == 0 ? r16 : 4 + r16;                 // A-operand row of this lane
-        int cb;                                                // B-operand column of this lane
-        if (t == 0) cb = HESS ? (r16 < 15 ? r16 : ZC) : r16;
-        else if (r16 < 4) cb = 16 + r16;
-        else if (HESS) cb = r16 == 4 ? ZC : (r16 < 9 ? r16 - 5 : (r16 == 9 ? 15 : NONE));
-        else cb = r16 < 8 ? r16 - 4 : NONE;
-        const bool zcol = cb == ZC;
-        const CutT *pa = (ra < k ? As + ra * ldA : crow) + q;
-        const CutT *pb = (cb < k ? As + cb * ldA : (zcol ? crow + ldA : crow)) + q;
-        const double *pwz = (zcol ? zs : ws) + q;
-        d4 acc = {0.0, 0.0, 0.0, 0.0}, acc_odd = {0.0, 0.0, 0.0, 0.0};
-        CutT xa[4], xb[4], ya[4], yb[4];                       // software pipeline as in contract_mfma_8x8
-        double xw[4], yw[4];
-        auto gather = [&](int c0, CutT (&ga)[4], CutT (&gb)[4], double (&gw)[4]) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                ga[s] = pa[c0 + 4 * s];
-                gb[s] = pb[c0 + 4 * s];
-                if (HESS) gw[s] = pwz[c0 + 4 * s];
-            }
-        };
-        auto stage = [&](int cnext, CutT (&ca)[4], CutT (&cb_)[4], double (&cw)[4], CutT (&na)[4], CutT (&nb)[4], double (&nw)[4]) {
-            gather(cnext, na, nb, nw);
-            __builtin_amdgcn_sched_barrier(0);
-            // all four operand chains (cvt, cvt, mul) FIRST, then the four MFMAs back to back: float64 VALU work issued while
-            // the wave's own float64 MFMA is in flight stalls on the shared DP pipe -- interleaved, an MFMA with its chain costs
-            // a lone wave 204 cycles, batched 115 (the MFMA alone: 70; tools/probes/mfma_overlap_probe.hip).  Same arithmetic.
-            double av[4], bv[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                av[s] = (double)ca[s];
-                bv[s] = HESS ? (double)cb_[s] * cw[s] : (double)cb_[s];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if (s & 1) acc_odd = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc_odd, 0, 0, 0);
-                else acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { pin(na[s]); pin(nb[s]); if (HESS) pin(nw[s]); }
-        };
-        if (cbeg < cend) gather(cbeg, xa, xb, xw);
-        __builtin_amdgcn_s_waitcnt(0xc07f);                    // lgkmcnt(0), see contract_mfma_8x8
-        const int clast = cend - 16;
-        for (int c0 = cbeg; c0 < cend; c0 += 32) {             // column range is a multiple of 16
-            stage(c0 + 16 < cend ? c0 + 16 : clast, xa, xb, xw, ya, yb, yw);
-            if (c0 + 16 < cend) stage(c0 + 32 < cend ? c0 + 32 : clast, ya, yb, yw, xa, xb, xw);
-        }
-        acc += acc_odd;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = (t == 0 ? 0 : 4) + q + 4 * r;      // bundle row of this result
-            if (row >= k) continue;
-            if (zcol) {
-                if (t == 0 || row >= 16) Hm[row * HP + k] = acc[r];
-            } else if (t == 0) {
-                Hm[row * HP + cb] = acc[r];                                        // (rows 0 .. 15) x (columns 0 .. 14 | 15)
-                if (HESS && row == 15) Hm[cb * HP + 15] = acc[r];                  // H[i][15] = H[15][i]
-            } else if (cb < k) {
-                if (cb >= 16) {                                                    // (i, e), i = 4 .. 19
-                    Hm[row * HP + cb] = acc[r];
-                    if (row < 16) Hm[cb * HP + row] = acc[r];
-                } else if (cb < 4) {                                               // (e, i), i = 0 .. 3, and its mirror
-                    if (row >= 16) { Hm[row * HP + cb] = acc[r]; Hm[cb * HP + row] = acc[r]; }
-                } else if (row == 15) {                                            // cb == 15: the diagonal entry
-                    Hm[15 * HP + 15] = acc[r];
-                }
-            }
-        }
-    }
-}
-
-template <typename CutT, int KT, bool HESS, typename LapF = NoLap>
-__device__ void contract_mfma(const CutT *As, int ldA, int k, const CutT *crow, int cbeg, int cend, const double *ws,
-                              const double *zs, double *Hm, int HP, LapF lapf = LapF()) {
-    const int lane = thread_id() & 63, r16 = lane & 15, q = lane >> 4;
-    const int ncolsB = HESS ? k + 1 : k;
-    if (ncolsB <= 8) {
-        contract_mfma_8x8<CutT, HESS>(As, ldA, k, crow, cbeg, cend, ws, zs, Hm, HP, lapf);
-        return;
-    }
-    if (KT > 16 && k >= 17 && k <= 20) {
-        contract_mfma_cover2<CutT, HESS>(As, ldA, k, crow, cbeg, cend, ws, zs, Hm, HP);
-        return;
-    }
-    cbeg = uni(cbeg); cend = uni(cend);
-    for (int ti = 0; ti * 16 < k; ++ti) {
-        for (int tj = ti; tj * 16 < ncolsB; ++tj) {
-            d4 acc = {0.0, 0.0, 0.0, 0.0}, acc_odd = {0.0, 0.0, 0.0, 0.0};   // two chains: a dependent
-            const int ra = ti * 16 + r16, cb = tj * 16 + r16;              // 16x16x4 f64 MFMA costs 65 cycles
-            const bool zcol = HESS && cb == k;
-            const CutT *pa = (ra < k ? As + ra * ldA : crow) + q;
-            const CutT *pb = (cb < k ? As + cb * ldA : (zcol ? crow + ldA : crow)) + q;
-            const double *pwz = (zcol ? zs : ws) + q;
-            CutT xa[4], xb[4], ya[4], yb[4];                    // software pipeline as in contract_mfma_8x8
-            double xw[4], yw[4];
-            auto gather = [&](int c0, CutT (&ga)[4], CutT (&gb)[4], double (&gw)[4]) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    ga[s] = pa[c0 + 4 * s];
-                    gb[s] = pb[c0 + 4 * s];
-                    if (HESS) gw[s] = pwz[c0 + 4 * s];
-                }
-            };
-            auto stage = [&](int cnext, CutT (&ca)[4], CutT (&cb_)[4], double (&cw)[4], CutT (&na)[4],
-                             CutT (&nb)[4], double (&nw)[4]) {
-                gather(cnext, na, nb, nw);
-                __builtin_amdgcn_sched_barrier(0);
-                // (round 6: the four operand chains first, then the MFMAs back to back -- see contract_mfma_cover2)
-                double av[4], bv[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    av[s] = (double)ca[s];
-                    bv[s] = HESS ? (double)cb_[s] * cw[s] : (double)cb_[s];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    // (only in the 32-slot kernels, whose bundles actually live here: the 16-slot kernel is held
-                    //  to 128 VGPRs and the second accumulator would spill in its Newton loop)
-                    if (KT > 16 && (s & 1)) acc_odd = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc_odd, 0, 0, 0);
-                    else acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) { pin(na[s]); pin(nb[s]); if (HESS) pin(nw[s]); }
-            };
-            if (cbeg < cend) gather(cbeg, xa, xb, xw);
-            __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0), see contract_mfma_8x8
-            const int clast = cend - 16;
-            for (int c0 = cbeg; c0 < cend; c0 += 32) {          // column range is a multiple of 16
-                stage(c0 + 16 < cend ? c0 + 16 : clast, xa, xb, xw, ya, yb, yw);
-                if (c0 + 16 < cend) stage(c0 + 32 < cend ? c0 + 32 : clast, ya, yb, yw, xa, xb, xw);
-            }
-            if (KT > 16) acc += acc_odd;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = ti * 16 + q + 4 * r, col = tj * 16 + r16;
-                if (row < k && col < ncolsB) {
-                    Hm[row * HP + col] = acc[r];
-                    if (tj != ti && col < k) Hm[col * HP + row] = acc[r];
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Small dense algebra, register resident: lane i holds row i of the (<= KT x KT) system in
-// statically indexed registers, pivot rows are broadcast with v_readlane -- no LDS, no barriers.
-// ---------------------------------------------------------------------------------------------
-
-// 1/d to within an ulp or two: v_rcp_f64 plus two Newton-Raphson steps (what the IEEE division
-// expansion does internally, minus its scaling and fix-up instructions).  Pivots are never denormal
-// or infinite here (entries of A w A^T with |A| finite, w <= 1/4), so the shortcuts are safe.
-__device__ __forceinline__ double rcp_nr(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    double e = __builtin_fma(-d, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-d, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-
-// exp and log for the inner loops (round 5).  The library routines (ocml) cost ~55 (exp) and ~130 (log) instructions per call
-// for a correctly rounded-ish result with full special-case handling; a Newton update evaluates three sigmoids per lane, an
-// interior-point iteration three logarithms, and at sixteen samples per CU the dual phase is bound by instruction issue
-// (DESIGN.md section 6).  These are plain argument reductions + Horner polynomials, ~21 and ~33 instructions, relative error
-// below 3e-16 on their domains -- the iterations they feed are self-correcting (a fixed point of the Newton / KKT iteration
-// is a fixed point with either routine, to that accuracy).  NOT used where a value is final: y = 1 / (1 + exp(A^T lam))
-// (dual :165) keeps the library exp and IEEE division.
-//   fast_exp(x): x clamped to [-750, 750] (0 / +inf beyond, as exp itself), k = rint(x log2 e), r = x - k ln2 (two-term ln2,
-//   |r| <= 0.3466), exp(r) by its Taylor polynomial of degree 13 (next term 0.3466^14 / 14! = 4e-18), scaled by 2^k.
-__device__ __forceinline__ double fast_exp(double x) {
-    x = fmin(fmax(x, -750.0), 750.0);
-    const double kf = __builtin_rint(x * 1.4426950408889634);
-    double r = __builtin_fma(kf, -6.93147180369123816490e-01, x);        // ln2 hi (trailing zeros: k * hi is exact)
-    r = __builtin_fma(kf, -1.90821492927058770002e-10, r);               // ln2 lo
-    double p = 1.6059043836821613e-10;                                   // 1/13!
-    p = __builtin_fma(p, r, 2.08767569878681e-09);                       // 1/12!
-    p = __builtin_fma(p, r, 2.505210838544172e-08);                      // 1/11!
-    p = __builtin_fma(p, r, 2.755731922398589e-07);                      // 1/10!
-    p = __builtin_fma(p, r, 2.7557319223985893e-06);                     // 1/9!
-    p = __builtin_fma(p, r, 2.48015873015873e-05);                       // 1/8!
-    p = __builtin_fma(p, r, 1.984126984126984e-04);                      // 1/7!
-    p = __builtin_fma(p, r, 1.388888888888889e-03);                      // 1/6!
-    p = __builtin_fma(p, r, 8.333333333333333e-03);                      // 1/5!
-    p = __builtin_fma(p, r, 4.1666666666666664e-02);                     // 1/4!
-    p = __builtin_fma(p, r, 1.6666666666666666e-01);                     // 1/3!
-    p = __builtin_fma(p, r, 0.5);
-    p = __builtin_fma(p, r, 1.0);
-    p = __builtin_fma(p, r, 1.0);
-    return __builtin_amdgcn_ldexp(p, (int)kf);
-}
-//   fast_log(x), x > 0 finite: x = m 2^e with m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1) (|s| <= 0.1716),
-//   log m = 2 atanh(s) = 2 s + s^3 (2/3 + 2/5 s^2 + ... + 2/21 s^18) (next term 1.5e-18 relative), + e ln2 in two terms.
-__device__ __forceinline__ double fast_log(double x) {
-    double m = __builtin_amdgcn_frexp_mant(x);                           // [0.5, 1)
-    int e = __builtin_amdgcn_frexp_exp(x);
-    const bool low = m < 0.70710678118654752;
-    m = low ? m + m : m;
-    e = low ? e - 1 : e;
-    const double s = (m - 1.0) * rcp_nr(m + 1.0);
-    const double s2 = s * s;
-    double p = 2.0 / 21.0;
-    p = __builtin_fma(p, s2, 2.0 / 19.0);
-    p = __builtin_fma(p, s2, 2.0 / 17.0);
-    p = __builtin_fma(p, s2, 2.0 / 15.0);
-    p = __builtin_fma(p, s2, 2.0 / 13.0);
-    p = __builtin_fma(p, s2, 2.0 / 11.0);
-    p = __builtin_fma(p, s2, 2.0 / 9.0);
-    p = __builtin_fma(p, s2, 2.0 / 7.0);
-    p = __builtin_fma(p, s2, 2.0 / 5.0);
-    p = __builtin_fma(p, s2, 2.0 / 3.0);
-    const double lm = __builtin_fma(s * s2, p, s + s);
-    const double ed = (double)e;
-    return __builtin_fma(ed, 6.93147180369123816490e-01, __builtin_fma(ed, 1.90821492927058770002e-10, lm));
-}
-
-// softplus for the RL variant's objective values (rl :34, :72: one per column and Armijo trial), same branches as
-// softplus_stable (dual :6-12): log1p(u) = log(w) + (u - (w - 1)) / w with w = 1 + u rounded -- the second term restores what
-// the rounding of 1 + u lost (u itself when u < 1e-16), so the result keeps full relative accuracy for tiny u
-__device__ __forceinline__ double softplus_fast(double v) {
-    const bool big = v > 1.0;
-    const double u = fast_exp(big ? -v : v);
-    const double w = 1.0 + u;
-    const double l = __builtin_fma(u - (w - 1.0), __builtin_amdgcn_rcp(w), fast_log(w));
-    return big ? l + v : l;
-}
-
-// sigmoid(a) = 1 / (1 + exp(-a)) for the Newton update's column weights (dual :33): exp(-a) capped at e^700 so that the
-// reciprocal's Newton steps stay finite (z = 1e-304 where the exact quotient underflows to 0: w = z (1 - z) is as negligible)
-__device__ __forceinline__ double sigmoid_fast(double a) { return rcp_nr(1.0 + fast_exp(fmin(-a, 700.0))); }
-
-// Unpivoted LDL^T inertia: number of eigenvalues of S (k x k, in Hm) that are not above mu.
-// Rows and columns >= k are identity, so the elimination needs no per-column bound checks.
-template <int KT>
-__device__ __noinline__ int inertia_not_above_ks(const double *Hm_, int HP, int k, double mu) {
-    const int lane = lane_id();
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); mu = uni(mu);
-    double M[KT];
-#pragma unroll
-    for (int j = 0; j < KT; ++j) M[j] = Hm[(lane < k ? lane : 0) * HP + (j < k ? j : 0)];
-#pragma unroll
-    for (int j = 0; j < KT; ++j) pin(M[j]);                       // unconditional loads, all in flight
-#pragma unroll
-    for (int j = 0; j < KT; ++j)
-        M[j] = (lane < k && j < k) ? M[j] - (j == lane ? mu : 0.0) : (j == lane ? 1.0 : 0.0);
-    int neg = 0;
-#pragma unroll
-    for (int p = 0; p < KT; ++p) {
-        if (p < k) {
-            const double d = bcast(M[p], p);
-            if (!(d > 0.0)) {
-                ++neg;
-                if (d == 0.0) return neg + (k - p - 1);
-            }
-            const double f = lane > p ? M[p] * rcp_nr(d) : 0.0;
-#pragma unroll
-            for (int j = p + 1; j < KT; ++j) M[j] -= f * bcast(M[j], p);
-        }
-    }
-    return neg;
-}
-
-// Cyclic Jacobi eigenvalues of the symmetric k x k matrix in Hm (destroyed), lane 0 only.
-// Rare path of the rank test.  Eigenvalues end up on the diagonal.
-template <int KT, int NW>
-__device__ void jacobi_lane0(double *Ms, int HP, int k, int tid) {
-    if (tid == 0) {
-        for (int sweep = 0; sweep < 30; ++sweep) {
-            double off = 0.0, tr = 0.0;
-            for (int p = 0; p < k; ++p) tr += Ms[p * HP + p];
-            for (int p = 0; p < k - 1; ++p)
-                for (int q = p + 1; q < k; ++q) {
-                    const double apq = Ms[p * HP + q];
-                    off += apq * apq;
-                    if (apq == 0.0) continue;
-                    const double theta = (Ms[q * HP + q] - Ms[p * HP + p]) / (2.0 * apq);
-                    const double t = theta != 0.0
-                        ? copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0)) : 1.0;
-                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                    for (int j = 0; j < k; ++j) {
-                        const double rp = Ms[p * HP + j], rq = Ms[q * HP + j];
-                        Ms[p * HP + j] = c * rp - s * rq;
-                        Ms[q * HP + j] = s * rp + c * rq;
-                    }
-                    for (int i = 0; i < k; ++i) {
-                        const double cp = Ms[i * HP + p], cq = Ms[i * HP + q];
-                        Ms[i * HP + p] = c * cp - s * cq;
-                        Ms[i * HP + q] = s * cp + c * cq;
-                    }
-                }
-            const double lim = 1e-22 * tr;
-            if (off <= 1e-60 || off <= lim * lim) break;
-        }
-    }
-    sample_sync<NW>();
-}
-
-// Solve the reduced Newton system H0[free,free] d = -g0[free] (dual :45,:53-55).  Lane i builds row
-// i of the masked full-size system (identity on bound rows, so the free block is untouched),
-// Gaussian elimination in natural order: the reduced Hessian is symmetric positive semi-definite,
-// no pivoting is needed and the result equals LAPACK's up to rounding.  Returns false on an exactly
-// zero pivot -- what LAPACK reports as singular: variant DUAL raises there (dual :56-63), variant RL
-// keeps lam and leaves the Newton loop (rl :55-62).  With duplicate cuts (the RL variant has no rank
-// test) the MFMA-built Hessian has bit-identical rows, so the exact zero is the normal outcome there;
-// see DESIGN.md "RL variant and degenerate bundles" for what the reference's own LAPACK does on them.
-// Result in registers: an output reference of a non-inlined function would live in scratch memory
-// (a round trip through the vector memory path on every Newton update).
-struct StepResult {
-    double step;
-    int ok;
-};
-template <int KT>
-__device__ __noinline__ StepResult newton_step_ks(const double *Hm_, int HP, int k, int piv, unsigned long long fmask,
-                                                  bool is_free, double g0) {
-    const int lane = lane_id();
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); piv = uni(piv); fmask = uni(fmask);
-    double M[KT + 1];
-    // unconditional (clamped) LDS reads + selects: no exec-mask branches around the loads.  Eight columns at a time:
-    // two KT-sized operand arrays next to M made the 32-slot kernels need 241 VGPRs (two waves per SIMD); the
-    // arithmetic per entry is unchanged
-    const int rl = lane < k ? lane : 0;
-    double h_ip = Hm[rl * HP + piv], h_pp = Hm[piv * HP + piv];
-    pin(h_ip);
-    pin(h_pp);
-    static_assert(KT % 4 == 0, "columns are loaded four at a time");
-#pragma unroll
-    for (int j0 = 0; j0 < KT; j0 += 4) {
-        double h_ij[4], h_jp[4];
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = j0 + jj, jc = j < k ? j : 0;
-            h_ij[jj] = Hm[rl * HP + jc];
-            h_jp[jj] = Hm[jc * HP + piv];
-        }
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) { pin(h_ij[jj]); pin(h_jp[jj]); }   // the four pairs in flight, none sunk into a branch
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = j0 + jj;
-            // H0[i][j] = ((H[i][j] - keep_i H[j][piv]) - H[i][piv] keep_j) + H[piv][piv] keep_i keep_j
-            const double hv = ((h_ij[jj] - h_jp[jj]) - h_ip) + h_pp;
-            const bool use = j < k && is_free && ((fmask >> j) & 1ull);
-            M[j] = use ? hv : (j == lane ? 1.0 : 0.0);
-        }
-    }
-    M[KT] = is_free ? -g0 : 0.0;
-    // Rows/columns that are bound or >= k are identity: pivots there are skipped (scalar branch), and
-    // columns need no bound checks.  Lane p keeps 1/pivot_p for the back substitution.
-    double rinv = 1.0;
-#pragma unroll
-    for (int p = 0; p < KT; ++p) {
-        if (p < k && ((fmask >> p) & 1ull)) {
-            const double d = bcast(M[p], p);
-            if (!(d != 0.0)) return StepResult{0.0, 0};           // exact zero (or NaN): singular for LAPACK
-            const double inv = rcp_nr(d);
-            rinv = lane == p ? inv : rinv;
-            const double f = lane > p ? M[p] * inv : 0.0;
-#pragma unroll
-            for (int j = p + 1; j < KT; ++j) M[j] -= f * bcast(M[j], p);
-            M[KT] -= f * bcast(M[KT], p);
-        }
-    }
-#pragma unroll
-    for (int p = KT - 1; p >= 0; --p) {
-        if (p < k && ((fmask >> p) & 1ull)) {
-            const double x = bcast(M[KT] * rinv, p);
-            M[KT] = lane == p ? x : (lane < p ? M[KT] - M[p] * x : M[KT]);
-        }
-    }
-    return StepResult{is_free ? M[KT] : 0.0, 1};
-}
-
-// ---- KS <= 16: the same eliminations with DPP64 row broadcasts ---------------------------------
-// gfx90a+ can broadcast one lane of every 16-lane row to the whole row in a single 64-bit DPP move
-// (v_mov_b64_dpp row_newbcast:P).  With the system in lanes 0..15 this replaces the two v_readlane +
-// hazard nop of the SGPR route, keeps everything in VGPRs and lets the elimination be straight-line
-// code: identity rows (bound, or >= k) have pivot 1 and multiplier -0, so they are processed like any
-// other row instead of being branched around.  Lanes 16..63 compute on garbage and are ignored.
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-template <int P>
-__device__ __forceinline__ double row_bcast(double v) {
-    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + P, 0xf, 0xf, true);   // bound_ctrl: no "old" value to set up
-}
-
-#define DPP_ROWS_ATTR __noinline__
-#define DPP_ROWS_NAME(f) f
-#include "be_dual_dpp_rows.h"
-#undef DPP_ROWS_ATTR
-#undef DPP_ROWS_NAME
-#define DPP_ROWS_ATTR __forceinline__
-#define DPP_ROWS_NAME(f) f##_inl
-#include "be_dual_dpp_rows.h"
-#undef DPP_ROWS_ATTR
-#undef DPP_ROWS_NAME
-
-// ---- KS > 16 (round 6): the same eliminations spread over the WHOLE wave ---------------------------------------------------
-// Bundles of 17 .. 32 cuts used to fall back to one row per lane with `v_readlane` broadcasts (newton_step_ks: 12.4 k cycles
-// at 17 cuts against 6.7 k for the DPP form at 16; inertia 10 k against 3.8 k -- tools/probes/dual_update_probe.hip), with 20 to 32
-// of the 64 lanes holding a row of 20 .. 32 entries each.  Here the system is dealt over the four 16-lane DPP rows ("quarters"):
-//   lane 16 q + r holds, of matrix rows r and 16 + r, the columns j = 4 s + q (slot s): KS / 4 entries per row instead of KS,
-// so a pivot step is one row broadcast + one or two fused multiply-adds per SLOT (not per column), all four quarters working.
-// What crosses the quarters is the multiplier column -(M[i][p] / d) -- formed by the quarter that owns column p, handed to the
-// others by v_permlane16_swap + v_permlane32_swap (gfx950) -- and, in the back substitution, the four columns of a slot at a time.
-// The right-hand side is kept in every quarter.  Every entry sees exactly the operations of newton_step_dpp / newton_step_ks in the
-// same order (fma(-(M[i][p] inv), M[p][j], M[i][j]) per pivot, identity rows with multiplier -0), so the result is bit-identical.
-__device__ __forceinline__ void swap16(double &x, double &y) {      // x = [x0 y0 x2 y2], y = [x1 y1 x3 y3] (quarters of the wave)
-    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-    x = __hiloint2double((int)hi[0], (int)lo[0]);
-    y = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ void swap32(double &x, double &y) {      // x = [x0 x1 y0 y1], y = [x2 x3 y2 y3]
-    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-    x = __hiloint2double((int)hi[0], (int)lo[0]);
-    y = __hiloint2double((int)hi[1], (int)lo[1]);
-}
-// every lane gets what lane 16 Q + (lane & 15) holds
-template <int Q>
-__device__ __forceinline__ double quarter_bcast(double v) {
-    double a = v, b = v;
-    swap16(a, b);                                    // a = [v0 v0 v2 v2], b = [v1 v1 v3 v3]
-    double c = (Q & 1) ? b : a, d = c;
-    swap32(c, d);                                    // c = lower half twice, d = upper half twice
-    return Q < 2 ? c : d;
-}
-// the four quarters' values of v, in every lane: out[q] = what lane 16 q + (lane & 15) holds
-__device__ __forceinline__ void quarter_gather(double v, double (&out)[4]) {
-    double a = v, b = v;
-    swap16(a, b);
-    double a2 = a, b2 = b;
-    swap32(a, a2);                                   // a = [v0 v0 v0 v0], a2 = [v2 ...]
-    swap32(b, b2);                                   // b = [v1 ...],      b2 = [v3 ...]
-    out[0] = a; out[1] = b; out[2] = a2; out[3] = b2;
-}
-
-template <int KS>
-__device__ __noinline__ StepResult newton_step_2d(const double *Hm_, int HP, int k, int piv, unsigned long long fmask,
-                                                  bool is_free, double g0) {
-    static_assert(KS > 16 && KS <= 32 && KS % 4 == 0, "two matrix rows per lane, four columns per slot");
-    constexpr int NS = KS / 4;
-    const int lane = lane_id(), q = lane >> 4, r = lane & 15;
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); piv = uni(piv); fmask = uni(fmask);
-    const int i0 = r, i1 = 16 + r;                       // the two matrix rows of this lane
-    const int rl0 = i0 < k ? i0 : 0, rl1 = i1 < k ? i1 : 0;
-    // -g0 of the lane's two rows: row layout (lane i = row i) -> quarters 0 and 1 hold them
-    const double gm = is_free ? -g0 : 0.0;
-    double b0 = quarter_bcast<0>(gm), b1 = quarter_bcast<1>(gm);
-    const bool free0 = (fmask >> i0) & 1ull, free1 = (fmask >> i1) & 1ull;
-    double h_ip0 = Hm[rl0 * HP + piv], h_ip1 = Hm[rl1 * HP + piv], h_pp = Hm[piv * HP + piv];
-    double M0[NS], M1[NS], hc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int j = 4 * s + q, jc = j < k ? j : 0;
-        M0[s] = Hm[rl0 * HP + jc];
-        M1[s] = Hm[rl1 * HP + jc];
-        hc[s] = Hm[jc * HP + piv];
-    }
-    pin(h_ip0); pin(h_ip1); pin(h_pp);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { pin(M0[s]); pin(M1[s]); pin(hc[s]); }      // all loads in flight, none sunk into a branch
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        // H0[i][j] = ((H[i][j] - keep_i H[j][piv]) - H[i][piv] keep_j) + H[piv][piv] keep_i keep_j
-        const int j = 4 * s + q;
-        const bool fj = j < k && ((fmask >> j) & 1ull);
-        double hv0 = ((M0[s] - hc[s]) - h_ip0) + h_pp, hv1 = ((M1[s] - hc[s]) - h_ip1) + h_pp;
-        pin(hv0); pin(hv1);
-        M0[s] = (fj && free0) ? hv0 : (j == i0 ? 1.0 : 0.0);
-        M1[s] = (fj && free1) ? hv1 : (j == i1 ? 1.0 : 0.0);
-    }
-    double rinv0 = 1.0, rinv1 = 1.0;                     // lane (p & 3, p & 15) keeps 1 / pivot p
-    bool bad = false;
-    static_for<0, KS>([&](auto P) {
-        constexpr int p = decltype(P)::value, qp = p & 3, sp = p >> 2, rp = p & 15;
-        constexpr bool upper = p >= 16;                  // the pivot row is one of the rows 16 + r
-        const double d = row_bcast<rp>(upper ? M1[sp] : M0[sp]);          // (meaningful in quarter qp)
-        bad |= q == qp && !(d != 0.0);                   // exact zero (or NaN): singular for LAPACK
-        const double inv = rcp_nr(d);
-        double nf0 = 0.0, nf1;
-        if constexpr (!upper) {
-            rinv0 = i0 == p ? inv : rinv0;
-            nf0 = quarter_bcast<qp>(i0 > p ? -(M0[sp] * inv) : 0.0);
-            nf1 = quarter_bcast<qp>(-(M1[sp] * inv));
-        } else {
-            rinv1 = i1 == p ? inv : rinv1;
-            nf1 = quarter_bcast<qp>(i1 > p ? -(M1[sp] * inv) : 0.0);
-        }
-        static_for<sp, NS>([&](auto S) {                 // (columns <= p of slot sp take part: they are never read again)
-            constexpr int s = decltype(S)::value;
-            const double pr = row_bcast<rp>(upper ? M1[s] : M0[s]);
-            if constexpr (!upper) M0[s] = __builtin_fma(nf0, pr, M0[s]);
-            M1[s] = __builtin_fma(nf1, pr, M1[s]);
-        });
-        const double pb = row_bcast<rp>(upper ? b1 : b0);
-        if constexpr (!upper) b0 = __builtin_fma(nf0, pb, b0);
-        b1 = __builtin_fma(nf1, pb, b1);
-        __builtin_amdgcn_sched_barrier(0);     // keep the broadcasts of later pivots from being hoisted (registers)
-    });
-    if (__ballot(bad)) return StepResult{0.0, 0};
-    // back substitution, a slot (four columns, one per quarter) at a time: every quarter gets the slot's columns of its rows
-    static_for<0, NS>([&](auto S) {
-        constexpr int s = NS - 1 - decltype(S)::value;
-        double u0[4], u1[4];
-        quarter_gather(M0[s], u0);
-        if constexpr (4 * s + 3 > 16) quarter_gather(M1[s], u1);
-        static_for<0, 4>([&](auto C) {
-            constexpr int qp = 3 - decltype(C)::value, p = 4 * s + qp, rp = p & 15;
-            constexpr bool upper = p >= 16;
-            const double x = bcast((upper ? b1 : b0) * (upper ? rinv1 : rinv0), 16 * qp + rp);
-            b0 = i0 == p ? x : (i0 < p ? __builtin_fma(-u0[qp], x, b0) : b0);
-            if constexpr (p >= 16) b1 = i1 == p ? x : (i1 < p ? __builtin_fma(-u1[qp], x, b1) : b1);
-        });
-    });
-    // back to the row layout: lane i < 16 has its step in b0 (quarter 0), lane 16 + r in b1 -- which quarter 1 holds as well
-    const double step = q == 0 ? b0 : (q == 1 ? b1 : 0.0);
-    return StepResult{is_free ? step : 0.0, 1};
-}
-
-// Unpivoted LDL^T inertia in the same layout (cf. inertia_not_above_dpp): no right-hand side, no back substitution
-template <int KS>
-__device__ __noinline__ int inertia_not_above_2d(const double *Hm_, int HP, int k, double mu) {
-    static_assert(KS > 16 && KS <= 32 && KS % 4 == 0, "two matrix rows per lane, four columns per slot");
-    constexpr int NS = KS / 4;
-    const int lane = lane_id(), q = lane >> 4, r = lane & 15;
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    HP = uni(HP); k = uni(k); mu = uni(mu);
-    const int i0 = r, i1 = 16 + r;
-    double M0[NS], M1[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int j = 4 * s + q, jc = j < k ? j : 0;
-        M0[s] = Hm[(i0 < k ? i0 : 0) * HP + jc];
-        M1[s] = Hm[(i1 < k ? i1 : 0) * HP + jc];
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { pin(M0[s]); pin(M1[s]); }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int j = 4 * s + q;
-        M0[s] = (i0 < k && j < k) ? M0[s] - (j == i0 ? mu : 0.0) : (j == i0 ? 1.0 : 0.0);
-        M1[s] = (i1 < k && j < k) ? M1[s] - (j == i1 ? mu : 0.0) : (j == i1 ? 1.0 : 0.0);
-    }
-    double dp0 = 1.0, dp1 = 1.0;                         // lane (p & 3, p & 15) keeps pivot p
-    static_for<0, KS>([&](auto P) {
-        constexpr int p = decltype(P)::value, qp = p & 3, sp = p >> 2, rp = p & 15;
-        constexpr bool upper = p >= 16;
-        const double d = row_bcast<rp>(upper ? M1[sp] : M0[sp]);
-        const double inv = rcp_nr(d);
-        double nf0 = 0.0, nf1;
-        if constexpr (!upper) {
-            dp0 = (q == qp && i0 == p) ? d : dp0;
-            nf0 = quarter_bcast<qp>(i0 > p ? -(M0[sp] * inv) : 0.0);
-            nf1 = quarter_bcast<qp>(-(M1[sp] * inv));
-        } else {
-            dp1 = (q == qp && i1 == p) ? d : dp1;
-            nf1 = quarter_bcast<qp>(i1 > p ? -(M1[sp] * inv) : 0.0);
-        }
-        static_for<sp, NS>([&](auto S) {
-            constexpr int s = decltype(S)::value;
-            const double pr = row_bcast<rp>(upper ? M1[s] : M0[s]);
-            if constexpr (!upper) M0[s] = __builtin_fma(nf0, pr, M0[s]);
-            M1[s] = __builtin_fma(nf1, pr, M1[s]);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    // pivot p sits in lane 16 (p & 3) + (p & 15) as dp0 (p < 16) or dp1: ballots per pivot class, in pivot order
-    // of every group of lanes r, 16 + r, 32 + r, 48 + r exactly one -- quarter r & 3 -- owns pivots r and 16 + r
-    const bool own = (r & 3) == q;
-    auto fold = [](unsigned long long m) -> unsigned { return (unsigned)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xffffull); };
-    unsigned nonpos = fold(__ballot(own && !(dp0 > 0.0))) | (fold(__ballot(own && !(dp1 > 0.0))) << 16);
-    unsigned zero = fold(__ballot(own && dp0 == 0.0)) | (fold(__ballot(own && dp1 == 0.0)) << 16);
-    const unsigned live = k >= 32 ? 0xffffffffu : ((1u << k) - 1u);
-    nonpos &= live; zero &= live;
-    // pivots up to the first exact zero count individually; behind it everything counts as suspect
-    if (zero) {
-        const int p0 = __builtin_ctz(zero);
-        return __popc(nonpos & ((2u << p0) - 1u)) + (k - p0 - 1);
-    }
-    return __popc(nonpos);
-}
-
-// The statically unrolled routines above cost O(KS^2) predicated steps whatever k is, so they are
-// instantiated for several sizes and the smallest one that holds the bundle is used.
-// KCAP > 0 (dual_step_body): k <= KCAP <= 8, and the instance today's dispatch picks for k is inlined instead of called.
-template <int KT, int KCAP = 0>
-__device__ __forceinline__ int inertia_not_above(const double *Hm, int HP, int k, double mu) {
-    if constexpr (KCAP > 0) {
-        static_assert(KCAP <= 8, "capped bodies hold bundles of up to eight cuts");
-        if (KCAP <= 4 || k <= 4) return inertia_not_above_dpp_inl<4>(Hm, HP, k, mu);
-        if (KCAP <= 6 || k <= 6) return inertia_not_above_dpp_inl<6>(Hm, HP, k, mu);
-        return inertia_not_above_dpp_inl<8>(Hm, HP, k, mu);
-    }
-    if (k <= 4) return inertia_not_above_dpp<4>(Hm, HP, k, mu);
-    if (k <= 6) return inertia_not_above_dpp<6>(Hm, HP, k, mu);
-    if (k <= 8) return inertia_not_above_dpp<8>(Hm, HP, k, mu);
-    if (k <= 10) return inertia_not_above_dpp<10>(Hm, HP, k, mu);
-    if (k <= 12) return inertia_not_above_dpp<12>(Hm, HP, k, mu);
-    if (KT == 16 || k <= 16) return inertia_not_above_dpp<16>(Hm, HP, k, mu);
-    if constexpr (KT > 16) {                             // (round 6: the system dealt over the whole wave, above)
-        if (k <= 20) return inertia_not_above_2d<20>(Hm, HP, k, mu);
-        if (k <= 24) return inertia_not_above_2d<24>(Hm, HP, k, mu);
-        return inertia_not_above_2d<32>(Hm, HP, k, mu);
-    }
-    return 0;
-}
-// (one-wave samples on the fused VALU pass: bundles of up to HV_K1MAX = 8 cuts, system in the pass's packed triangle)
-template <int KCAP = 0>
-__device__ __forceinline__ StepResult newton_step_tri(const double *P, int k, int piv, unsigned long long fmask, bool is_free,
-                                                      double g0) {
-    if constexpr (KCAP > 0) {                            // the same choice by k, inlined
-        if (KCAP <= 4 || k <= 4) return newton_step_dpp_inl<4, true>(P, 0, k, piv, fmask, is_free, g0);
-        if (KCAP <= 6 || k <= 6) return newton_step_dpp_inl<6, true>(P, 0, k, piv, fmask, is_free, g0);
-        return newton_step_dpp_inl<8, true>(P, 0, k, piv, fmask, is_free, g0);
-    }
-    if (k <= 4) return newton_step_dpp<4, true>(P, 0, k, piv, fmask, is_free, g0);
-    if (k <= 6) return newton_step_dpp<6, true>(P, 0, k, piv, fmask, is_free, g0);
-    return newton_step_dpp<8, true>(P, 0, k, piv, fmask, is_free, g0);
-}
-template <int KT>
-__device__ __forceinline__ StepResult newton_step(const double *Hm, int HP, int k, int piv, unsigned long long fmask,
-                                                  bool is_free, double g0) {
-    if (k <= 4) return newton_step_dpp<4>(Hm, HP, k, piv, fmask, is_free, g0);
-    if (k <= 6) return newton_step_dpp<6>(Hm, HP, k, piv, fmask, is_free, g0);
-    if (k <= 8) return newton_step_dpp<8>(Hm, HP, k, piv, fmask, is_free, g0);
-    if (k <= 10) return newton_step_dpp<10>(Hm, HP, k, piv, fmask, is_free, g0);
-    if (k <= 12) return newton_step_dpp<12>(Hm, HP, k, piv, fmask, is_free, g0);
-    if (KT == 16 || k <= 16) return newton_step_dpp<16>(Hm, HP, k, piv, fmask, is_free, g0);
-    if constexpr (KT > 16) {                             // (round 6: the system dealt over the whole wave, above)
-        if (k <= 20) return newton_step_2d<20>(Hm, HP, k, piv, fmask, is_free, g0);
-        if (k <= 24) return newton_step_2d<24>(Hm, HP, k, piv, fmask, is_free, g0);
-        return newton_step_2d<32>(Hm, HP, k, piv, fmask, is_free, g0);
-    }
-    return StepResult{0.0, 0};
-}
-
-// Butterfly reduction over the first 16 lanes (the row that holds a bundle of up to 16 multipliers):
-// quad permutes, row_half_mirror, row_mirror -- 4 DPP steps, every lane of the row ends up with the
-// result (lane 0 is read back as the wave-uniform value).  Replaces k-step v_readlane scans.
-template <typename Op>
-__device__ __forceinline__ double row16_reduce(double v, Op op) {
-    v = op(v, dpp_move<0xB1>(v));
-    v = op(v, dpp_move<0x4E>(v));
-    v = op(v, dpp_move<0x141>(v));
-    v = op(v, dpp_move<0x140>(v));
-    return uni(v);
-}
-
-// The same for bundles of up to 32 cuts (the 32-slot kernels): the rows of lanes 0..15 and 16..31 are reduced
-// side by side, then combined.  `v` must be the operation's neutral element outside the bundle; k <= 16 (wave-uniform)
-// takes the single-row result, so the 32-slot kernels run the 16-slot kernels' instruction sequence on small bundles.
-template <int KT, typename Op>
-__device__ __forceinline__ double rows_reduce(double v, int k, Op op) {
-    v = op(v, dpp_move<0xB1>(v));
-    v = op(v, dpp_move<0x4E>(v));
-    v = op(v, dpp_move<0x141>(v));
-    v = op(v, dpp_move<0x140>(v));
-    if (KT == 16 || k <= 16) return uni(v);
-    return op(bcast(v, 0), bcast(v, 16));
-}
-
-// a_j = sum_i lam_i A[i][j] for the columns j = tid + c * nt owned by this thread, NC of them in
-// statically indexed registers: the LDS reads of several rows and all NC columns are in flight together
-// and the NC transcendental chains that follow (exp, divide) interleave instead of running one after the
-// other.  `fin(j, valid, a_j)` must do its arithmetic unconditionally and only guard its stores.
-// Accumulation order over i is the plain sequential one (same bits as the scalar loop).
-template <typename CutT, int NC, typename F>
-__device__ __forceinline__ void columns_nc(const CutT *As, int ldA, int k, int zrow, int n_pad, int nt, int tid,
-                                           double lam, F &&fin) {
-    double acc[NC];
-    int jc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int j = tid + c * nt;
-        jc[c] = j < n_pad ? j : n_pad - 1;
-        acc[c] = 0.0;
-    }
-    // rows in groups of four (4 * NC LDS reads in flight), then the remainder one by one -- the order of
-    // the accumulation is the plain i = 0..k-1 one
-    int i0 = 0;
-    for (; i0 + 4 <= k; i0 += 4) {
-        CutT av[4][NC];
-        double li[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            li[d] = bcast(lam, i0 + d);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) av[d][c] = As[(i0 + d) * ldA + jc[c]];
-        }
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] += li[d] * (double)av[d][c];
-    }
-    for (; i0 < k; ++i0) {
-        const double li = bcast(lam, i0);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] += li * (double)As[i0 * ldA + jc[c]];
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) fin(tid + c * nt, tid + c * nt < n_pad, acc[c]);
-}
-template <typename CutT, typename F>
-__device__ __forceinline__ void for_columns(const CutT *As, int ldA, int k, int zrow, int n_pad, int nt, int tid,
-                                            double lam, F &&fin) {
-    const int per_thread = (n_pad + nt - 1) / nt;
-    if (per_thread == 3) columns_nc<CutT, 3>(As, ldA, k, zrow, n_pad, nt, tid, lam, fin);
-    else if (per_thread <= 2) columns_nc<CutT, 2>(As, ldA, k, zrow, n_pad, nt, tid, lam, fin);
-    else if (per_thread == 4) columns_nc<CutT, 4>(As, ldA, k, zrow, n_pad, nt, tid, lam, fin);
-    else
-        for (int j0 = 0; j0 < n_pad; j0 += 4 * nt)       // wide rows: four columns per thread at a time
-            columns_nc<CutT, 4>(As + j0, ldA, k, zrow, n_pad - j0, nt, tid, lam,
-                                [&](int j, bool valid, double aj) { fin(j0 + j, valid, aj); });
-}
-
 #include "be_dual_valu_dev.h"
 #include "be_ipm_dev.h"
 
-// NW = waves per sample.  NW = 1: one wave64 owns the sample (n up to a few hundred).  NW > 1 (large n,
-// e.g. the 2048-pixel completion model): the columns are split over NW waves -- column phase, MFMA sweep
-// (per-wave partial results summed through LDS) and y update scale with NW -- while every wave runs the
-// small row-layout algebra redundantly on identical data, so no multiplier ever has to be exchanged.
-// The body works on sample `u` with the 64 NW threads whose index is `tid`, in the LDS region `smem`; `round`
-// and `rows` (the most bundle rows any sample can hold in this round) come from the caller; `crow` points at
-// shared constant rows (zeros, ones) or is null, in which case the sample keeps its own behind its bundle.
-// Stand-alone kernel below: one workgroup per sample.  be_fused.hip: one single-wave sample per wave of a
-// 16-wave workgroup (NW = 1, so nothing in here synchronises beyond the wave).
-// ArgsT: DualArgs as the kernel's by-value parameter, or a reference into the kernel-argument segment
-// (address space 4) when the caller is a non-inlined phase function of be_fused.hip.
-// IPM: the interior-point variant (lib/bundle_entropy.py): same cut bookkeeping and rank test, then y AND the
-// multipliers come from pdipm_pc (be_ipm_dev.h) and multipliers <= 1e-8 are pruned (:234-237).
-// GLB: the staged bundle (rows + the two constant rows) lives in the sample's slice of st.scratch instead of LDS -- the
-// rounds of a wide-row solve whose bundle no longer fits the workgroup's 160 KB.  Same code, same arithmetic.
-// LR > 0 (with GLB; dual_step_wide_kernel): split staging -- the LR oldest rows of the bundle are ALSO copied into LDS behind the
-// carve-up, for the fused VALU pass of be_dual_valu_dev.h (everything else reads the device-memory copy as in any GLB round).
-// SLICED = false: the caller never parks a sample (no update budget, state fresh from icnn_be_state_init: the persistent
-// tile kernel in its default form) -- the park / resume paths and their live values are compiled out (headline solve 1.024 ->
-// 1.016 ms on one box; cf. ICNN_BE_PROF, be_common.h).
-// Shape (be_kernels.h): n, n_pad, ldA and the pairwise plan from the arguments (DynShape), or as constants (FixedDual: the
-// fixed instances of the persistent tile kernel).
-// KCAP > 0: the caller guarantees rows_cap <= KCAP <= HV_K1MAX and that the fused VALU pass is what every bundle of two and
-// more cuts takes (one-wave float32 rows of up to 192 columns, no ICNN_BE_FLAG_MFMA_CONTRACTION: the round classes of the
-// persistent tile kernel, be_fused.hip).  The pass, the reduced Newton solve and the inertia count are then inlined in the
-// instance today's dispatch picks for k, the MFMA sweep is not compiled in, and no function is called in the Newton loop.
-// Same instances, same arithmetic, same bits.  KCAP = 0: the body as it always was.
-template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false, int LR = 0, bool SLICED = true,
-          typename Shape = DynShape, int KCAP = 0, typename ArgsT>
+// What dual_step_body is compiled for.  The body works on sample `u` with the 64 NW threads whose index is `tid`, in the LDS
+// region `smem`; `round` and `rows` (the most bundle rows any sample can hold in this round) come from the caller; `crow` points
+// at shared constant rows (zeros, ones) or is null, in which case the sample keeps its own behind its bundle.  Stand-alone
+// kernel below: one workgroup per sample.  be_fused.hip: one single-wave sample per wave of a 16-wave workgroup (NW = 1, so
+// nothing in there synchronises beyond the wave).  ArgsT, the body's other template parameter: DualArgs as the kernel's by-value
+// parameter, or a reference into the kernel-argument segment (address space 4) when the caller is a non-inlined phase function
+// of be_fused.hip.
+template <typename Shape, int KCAP>
+constexpr bool dual_cap_on_valu_pass() {               // (DualCfg::KCAP; a shape policy without constants has no capped body)
+    if constexpr (KCAP > 0) return KCAP <= HV_K1MAX && Shape::FIXED && Shape::N_PAD <= 192 && hv_pitch(KCAP) <= Shape::N_PAD;
+    else return true;
+}
+template <typename CutT_, int KT_, int NW_, bool RL_, bool IPM_ = false, bool GLB_ = false, int LR_ = 0, bool SLICED_ = true,
+          typename Shape_ = DynShape, int KCAP_ = 0>
+struct DualCfg {
+    using CutT = CutT_;                // dtype of the cuts: float or double
+    static constexpr int KT = KT_;     // bundle slots the register-resident algebra is sized for: 16 or 32
+    // Waves per sample.  NW = 1: one wave64 owns the sample (n up to a few hundred).  NW > 1 (large n, e.g. the 2048-pixel
+    // completion model): the columns are split over NW waves -- column phase, MFMA sweep (per-wave partial results summed through
+    // LDS) and y update scale with NW -- while every wave runs the small row-layout algebra redundantly on identical data, so
+    // no multiplier ever has to be exchanged.
+    static constexpr int NW = NW_;
+    // The variant of RL/src/bundle_entropy.py: its Armijo line search, softplus sums and pivot regularisation are compiled out
+    // of the dual-variant kernels.
+    static constexpr bool RL = RL_;
+    // The interior-point variant (lib/bundle_entropy.py): same cut bookkeeping and rank test, then y AND the multipliers come
+    // from pdipm_pc (be_ipm_dev.h) and multipliers <= 1e-8 are pruned (:234-237).
+    static constexpr bool IPM = IPM_;
+    // The staged bundle (rows + the two constant rows) lives in the sample's slice of st.scratch instead of LDS -- the rounds of
+    // a wide-row solve whose bundle no longer fits the workgroup's 160 KB.  Same code, same arithmetic.
+    static constexpr bool GLB = GLB_;
+    // LR > 0 (with GLB; dual_step_wide_kernel): split staging -- the LR oldest rows of the bundle are ALSO copied into LDS behind
+    // the carve-up, for the fused VALU pass of be_dual_valu_dev.h (everything else reads the device-memory copy as in any GLB round).
+    static constexpr int LR = LR_;
+    // SLICED = false: the caller never parks a sample (no update budget, state fresh from icnn_be_state_init: the persistent
+    // tile kernel in its default form) -- the park / resume paths and their live values are compiled out (headline solve 1.024 ->
+    // 1.016 ms on one box; cf. ICNN_BE_PROF, be_common.h).
+    static constexpr bool SLICED = SLICED_;
+    // (be_kernels.h): n, n_pad, ldA and the pairwise plan from the arguments (DynShape), or as constants (FixedDual: the fixed
+    // instances of the persistent tile kernel).
+    using Shape = Shape_;
+    // KCAP > 0: the caller guarantees rows_cap <= KCAP <= HV_K1MAX and that the fused VALU pass is what every bundle of two and
+    // more cuts takes (one-wave float32 rows of up to 192 columns, no ICNN_BE_FLAG_MFMA_CONTRACTION: the round classes of the
+    // persistent tile kernel, be_fused.hip).  The pass, the reduced Newton solve and the inertia count are then inlined in the
+    // instance today's dispatch picks for k, the MFMA sweep is not compiled in, and no function is called in the Newton loop.
+    // Same instances, same arithmetic, same bits.  KCAP = 0: the body as it always was.
+    static constexpr int KCAP = KCAP_;
+
+    static_assert(!IPM || !RL, "interior point is a variant of its own");
+    static_assert(LR == 0 || GLB, "split staging belongs to the device-memory rounds");
+    static_assert(KCAP == 0 || (NW == 1 && KT == 16 && !RL && !IPM && !GLB && LR == 0 && sizeof(CutT) == 4),
+                  "capped bodies: one-wave dual variant");
+    static_assert(dual_cap_on_valu_pass<Shape, KCAP>(), "every bundle of a capped body takes the fused VALU pass");
+};
+// The config of a one-wave body inside a persistent tile kernel: C with the three things such a caller decides, so that the
+// call site names only what differs from the defaults above.
+template <typename C, bool SLICED, typename Shape, int KCAP = 0>
+using DualCfgTile = DualCfg<typename C::CutT, C::KT, C::NW, C::RL, C::IPM, C::GLB, C::LR, SLICED, Shape, KCAP>;
+
+// One round of one sample.  Cfg: a DualCfg; the arguments are described there.  (Why this is still one function with the
+// Newton history kept by hand: profiles/dual_body_split_ab.md.)
+template <typename Cfg, typename ArgsT>
 __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, unsigned char *smem, int round,
-                                               int rows_cap, const CutT *crow_shared) {
+                                               int rows_cap, const typename Cfg::CutT *crow_shared) {
+    using CutT = typename Cfg::CutT;
+    using Shape = typename Cfg::Shape;
+    constexpr int KT = Cfg::KT, NW = Cfg::NW, LR = Cfg::LR, KCAP = Cfg::KCAP;
+    constexpr bool RL = Cfg::RL, IPM = Cfg::IPM, GLB = Cfg::GLB, SLICED = Cfg::SLICED;
     constexpr int NT = 64 * NW;
     const auto &st = a.st;
     const int lane = tid & 63, wave = tid >> 6;
@@ -1050,19 +164,12 @@ __device__ __forceinline__ void dual_step_body(const ArgsT &a, int u, int tid, u
     // RL (variant of RL/src/bundle_entropy.py) is a template parameter: its Armijo line search, softplus
     // sums and pivot regularisation are compiled out of the dual-variant kernels.
     // a bundle cannot hold more cuts than outer iterations have been started: rows <= round + 1
-    static_assert(!IPM || !RL, "interior point is a variant of its own");
-    if constexpr (KCAP > 0) {
-        static_assert(NW == 1 && KT == 16 && !RL && !IPM && !GLB && LR == 0 && sizeof(CutT) == 4, "capped bodies: one-wave dual variant");
-        static_assert(KCAP <= HV_K1MAX && Shape::FIXED && Shape::N_PAD <= 192 && hv_pitch(KCAP) <= Shape::N_PAD,
-                      "every bundle of a capped body takes the fused VALU pass");
-    }
     const Carve cv = carve(KT, rows_cap, ldA, n_pad, (int)sizeof(CutT), plan.n_leaves, RL, NW, crow_shared == nullptr, IPM, GLB);
     // this wave's share of the columns (multiple of 16)
     const int cchunk = NW == 1 ? n_pad : (((n_pad / 16 + NW - 1) / NW) * 16);
     const int cbeg = wave * cchunk < n_pad ? wave * cchunk : n_pad;
     const int cend = cbeg + cchunk < n_pad ? cbeg + cchunk : n_pad;
     CutT *As = GLB ? static_cast<CutT *>(st.scratch) + (size_t)u * (st.slots + 2) * ldA : reinterpret_cast<CutT *>(smem + cv.As);
-    static_assert(LR == 0 || GLB, "split staging belongs to the device-memory rounds");
     CutT *AsL = reinterpret_cast<CutT *>(smem + ((cv.total + 15) & ~15));          // LR > 0: [LR][ldA], the oldest rows
     const bool mirror = LR > 0 && rows_cap <= HV_KMAX;     // split staging: the LR oldest rows also in LDS (there is room up to
                                                            // the carve-up of a HV_KMAX-cut bundle, dual_step_wide_kernel)
@@ -1749,13 +856,13 @@ __global__ __launch_bounds__(512, 1) void dual_step_wide_kernel(DualArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int k = __builtin_amdgcn_readfirstlane(a.st.count[blockIdx.x]) + 1;
     const int mid = a.rows < HV_KMAX ? a.rows : HV_KMAX;
-    dual_step_body<float, 32, 8, false, false, true, WIDE_LR>(a, blockIdx.x, threadIdx.x, smem, a.round, k <= mid ? mid : a.rows, nullptr);
+    dual_step_body<DualCfg<float, 32, 8, false, false, /* GLB */ true, /* LR */ WIDE_LR>>(a, blockIdx.x, threadIdx.x, smem, a.round, k <= mid ? mid : a.rows, nullptr);
 }
 
 template <typename CutT, int KT, int NW, bool RL, bool IPM = false, bool GLB = false>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? (RL && KT > 16 ? 2 : 4) : 1) void dual_step_kernel(DualArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    dual_step_body<CutT, KT, NW, RL, IPM, GLB>(a, blockIdx.x, threadIdx.x, smem, a.round, a.rows, nullptr);
+    dual_step_body<DualCfg<CutT, KT, NW, RL, IPM, GLB>>(a, blockIdx.x, threadIdx.x, smem, a.round, a.rows, nullptr);
 }
 
 

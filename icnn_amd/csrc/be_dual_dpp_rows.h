@@ -1,7 +1,7 @@
 // The DPP row algebra of the dual step -- unpivoted LDL^T inertia and the reduced Newton solve for systems of up to 16 rows --
-// as text that be_dual_dev.h includes twice (inside its namespaces; no include guard):
+// as text that be_dual_solve.h includes twice (inside its namespaces; no include guard):
 //   DPP_ROWS_ATTR = __noinline__,    DPP_ROWS_NAME(f) = f         the functions every dual body calls
-//   DPP_ROWS_ATTR = __forceinline__, DPP_ROWS_NAME(f) = f##_inl   the same code inlined: the capped bodies (dual_step_body, KCAP > 0)
+//   DPP_ROWS_ATTR = __forceinline__, DPP_ROWS_NAME(f) = f##_inl   the same code inlined: the capped bodies (DualCfg::KCAP > 0)
 // Two definitions from one text, so that the called functions keep the tokens (and the machine code) they always had.
 template <int KS>
 __device__ DPP_ROWS_ATTR int DPP_ROWS_NAME(inertia_not_above_dpp)(const double *Hm_, int HP, int k, double mu) {

@@ -64,6 +64,32 @@ template <typename T> __device__ __forceinline__ T np_sum_row(T e, int n) {
     return np_sum16(v, n);
 }
 
+// The last iterates of a row's projected Newton loop (this lane's multiplier) and how many of them are valid.  The exact-cycle
+// rule below must stay in step with the one dual_step_body writes out by hand (periods 1 .. 3 of its 1 .. 4; a cap of 20
+// updates leaves its other stopping rules nothing to do here).
+struct LamHistory {
+    double prev1 = 0.0, prev2 = 0.0, prev3 = 0.0;      // lam_{t-1} .. lam_{t-3}
+    int hist = 0;                                      // valid previous iterates (counted up to 4 as in dual_step_body)
+    __device__ __forceinline__ void push(double lam_new) {
+        prev3 = prev2;
+        prev2 = prev1;
+        prev1 = lam_new;
+        hist = hist < 4 ? hist + 1 : 4;
+    }
+    // lam_new repeats the iterate PERIOD updates back, `left` updates short of the cap: the iterate the cap would end on,
+    // lam_cap = lam_{t + r} with r = left mod PERIOD and lam_{t+1} = lam_{t+1-PERIOD}
+    template <int PERIOD>
+    __device__ __forceinline__ double cycle_point(int left, double lam_new) const {
+        static_assert(PERIOD == 2 || PERIOD == 3, "periods the rule tests beyond 1");
+        if constexpr (PERIOD == 2) {
+            return (left & 1) ? prev1 : lam_new;
+        } else {
+            const int r = left % 3;
+            return r == 0 ? lam_new : (r == 1 ? prev2 : prev1);
+        }
+    }
+};
+
 struct SmallArgs {
     icnn_be_state st;
     const void *f;
@@ -144,10 +170,9 @@ __device__ __forceinline__ void dual_step_quad_rl(const ArgsT &a, int u0, int ns
         const double c_i = r < k ? (double)np_sum16(Arow, n) + h_i : 0.0;
         const int cap = 20, backoff_cap = 10;                    // rl :29, :65
         const bool shortcut = !(st.flags & ICNN_BE_FLAG_NO_CYCLE_SHORTCUT);
-        double prev1 = 0.0, prev2 = 0.0, prev3 = 0.0;
-        int hist = 0;
+        LamHistory h;                                            // per row: hist is a per-lane value, equal within a row
         bool run = live && k > 1;                                // this row's sample is still in its Newton loop
-        const bool path8 = KS <= 8 || k + 1 <= 8;                // the 8x8 MFMA form: two accumulator chains (be_dual_dev.h)
+        const bool path8 = KS <= 8 || k + 1 <= 8;                // the 8x8 MFMA form: two accumulator chains (be_dual_mfma.h)
         while (__any(run)) {
             // a = A^T lam, z = sigmoid(a), w = z (1 - z), softplus terms                     rl :31-34
             // (rows i >= k contribute lam_i A[i][j] = 0 * 0: the chain of the wave-per-sample kernel, which stops at k, and
@@ -157,7 +182,7 @@ __device__ __forceinline__ void dual_step_quad_rl(const ArgsT &a, int u0, int ns
                 constexpr int i = decltype(I)::value;
                 aj = aj + rbc<i>(lam) * (double)Acol[i];
             });
-            double z = sigmoid_fast(aj);                         // (be_dual_dev.h; the same routine as the wave-per-sample kernel)
+            double z = sigmoid_fast(aj);                         // (be_dual_math.h; the same routine as the wave-per-sample kernel)
             double w = z * (1.0 - z);
             if (!col) { z = 0.0; w = 0.0; }
             const double sp = col ? softplus_fast(aj) : 0.0;
@@ -304,24 +329,18 @@ __device__ __forceinline__ void dual_step_quad_rl(const ArgsT &a, int u0, int ns
                 ++updates;
                 double lam_next = lam_new;
                 bool stop = returned;
-                if (!stop && shortcut && hist >= 1) {
-                    if (row_ballot(fabs(lam_new - prev1) > CYCLE_TOL) == 0) {
+                if (!stop && shortcut && h.hist >= 1) {              // exact repeats of period 1 .. 3, as in dual_step_body
+                    if (row_ballot(fabs(lam_new - h.prev1) > CYCLE_TOL) == 0) {
                         stop = true;
-                    } else if (hist >= 2 && row_ballot(fabs(lam_new - prev2) > CYCLE_TOL) == 0) {
-                        lam_next = ((cap - updates) & 1) ? prev1 : lam_new;
+                    } else if (h.hist >= 2 && row_ballot(fabs(lam_new - h.prev2) > CYCLE_TOL) == 0) {
+                        lam_next = h.cycle_point<2>(cap - updates, lam_new);
                         stop = true;
-                    } else if (hist >= 3 && row_ballot(fabs(lam_new - prev3) > CYCLE_TOL) == 0) {
-                        const int rem = (cap - updates) % 3;
-                        lam_next = rem == 0 ? lam_new : (rem == 1 ? prev2 : prev1);
+                    } else if (h.hist >= 3 && row_ballot(fabs(lam_new - h.prev3) > CYCLE_TOL) == 0) {
+                        lam_next = h.cycle_point<3>(cap - updates, lam_new);
                         stop = true;
                     }
                 }
-                if (!stop) {
-                    prev3 = prev2;
-                    prev2 = prev1;
-                    prev1 = lam_new;
-                    hist = hist < 4 ? hist + 1 : 4;
-                }
+                if (!stop) h.push(lam_new);
                 lam = lam_next;
                 leave = stop || updates >= cap;
             }

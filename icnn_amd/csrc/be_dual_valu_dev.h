@@ -197,7 +197,7 @@ __device__ __forceinline__ void hv_column_pass(AP As, LP AsL, int ldA, int k, in
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            z[c] = sigmoid_fast(acc[c]);                      // dual :33 (be_dual_dev.h: fast_exp + reciprocal)
+            z[c] = sigmoid_fast(acc[c]);                      // dual :33 (be_dual_math.h: fast_exp + reciprocal)
             w[c] = z[c] * (1.0 - z[c]);
         }
     }
@@ -229,7 +229,7 @@ __device__ __noinline__ void hv_column_pass_fn(const CutT *As_, const CutT *AsL_
 // ALLFN: every instance as a function (the 32-slot one-wave kernels: bundles of up to 8 cuts are the first rounds of a long
 // solve there, and the inlined instances made the Newton loop of ALL its updates spill -- configs[3] moved 5.4 GB per launch
 // against 3.0 GB; the 16-slot kernels, whose bundles mostly ARE that small, are faster with the instances inlined)
-// KCAP > 0 (dual_step_body): k <= KCAP <= HV_K1MAX, only the instances up to KCAP are compiled in, every one of them inlined
+// KCAP > 0 (DualCfg::KCAP, be_dual_dev.h): k <= KCAP <= HV_K1MAX, only the instances up to KCAP are compiled in, every one of them inlined
 // (the 8-cut instance too: a body that never holds a larger bundle has the registers for it)
 template <typename CutT, int K, int KCAP, int NW, bool HESS, int LR>
 __device__ __forceinline__ void hv_column_pass_upto(const CutT *As, const CutT *AsL, int ldA, int k, int zrow, int n, int n_pad,

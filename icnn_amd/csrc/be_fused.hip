@@ -91,6 +91,7 @@ __device__ __forceinline__ void reset_sample(const icnn_be_state &st, const Solv
 template <bool RL, int KT, bool IPM = false, bool SLICED = false, typename Shape = DynShape, int GROUPED = -1, bool CLASSES = false>
 __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args) {
     static_assert(!CLASSES || (GROUPED == 0 && KT == 16 && !RL && !IPM && !SLICED), "round classes: the ungrouped 16-slot dual instance");
+    using Wave = DualCfg<float, KT, 1, RL, IPM>;                    // phase B: one wave per sample
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     KArgs *kp0 = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     {
@@ -123,10 +124,9 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
                 unsigned char *region = smem + k.samples_off + wave * k.sample_bytes;
                 const float *crow = reinterpret_cast<const float *>(smem + k.crow_off);
                 if (CLASSES && round < ROUND_CLASS_CAP)             // rows_cap <= round + 1 <= the cap of the class
-                    dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape, CLASSES ? ROUND_CLASS_CAP : 0>(
-                        k.da, u, thread_id() & 63, region, round, rows_cap, crow);
+                    dual_step_body<DualCfgTile<Wave, SLICED, Shape, CLASSES ? ROUND_CLASS_CAP : 0>>(k.da, u, thread_id() & 63, region, round, rows_cap, crow);
                 else
-                    dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63, region, round, rows_cap, crow);
+                    dual_step_body<DualCfgTile<Wave, SLICED, Shape>>(k.da, u, thread_id() & 63, region, round, rows_cap, crow);
             }
             __syncthreads();                                        // y, skip flags visible to the next phase A
             continue;
@@ -194,8 +194,8 @@ __global__ __launch_bounds__(NTHREADS) void fused_fc_solve_kernel(FusedArgs args
             }
             wait_lap(14);
             if (ICNN_BE_PROF_ON(k.trace) && tr) tr[1] = (long long)__builtin_readcyclecounter();
-            dual_step_body<float, KT, 1, RL, IPM, false, 0, SLICED, Shape>(k.da, u, thread_id() & 63, smem + k.samples_off + my_off, round, kk,
-                                                                    reinterpret_cast<const float *>(smem + k.crow_off));
+            dual_step_body<DualCfgTile<Wave, SLICED, Shape>>(k.da, u, thread_id() & 63, smem + k.samples_off + my_off, round, kk,
+                                                             reinterpret_cast<const float *>(smem + k.crow_off));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // its LDS traffic is complete before the flag is seen
             if ((thread_id() & 63) == 0) __atomic_store_n(&done[wave], round + 1, __ATOMIC_RELAXED);
             if (ICNN_BE_PROF_ON(k.da.prof)) tq = (long long)__builtin_readcyclecounter();
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(RTHREADS) void fused_rows_solve_kernel(FusedRowsArg
         } else {
             if (wave < batch) {
                 const int rows_cap = !k.resume && round + 1 < k.da.st.slots ? round + 1 : k.da.st.slots;
-                dual_step_body<float, KT, 1, RL, IPM>(k.da, s_base + wave, thread_id() & 63, smem + k.dual_off + wave * k.sample_bytes,
-                                                      round, rows_cap, reinterpret_cast<const float *>(smem + k.crow_off));
+                dual_step_body<DualCfg<float, KT, 1, RL, IPM>>(k.da, s_base + wave, thread_id() & 63, smem + k.dual_off + wave * k.sample_bytes,
+                                                               round, rows_cap, reinterpret_cast<const float *>(smem + k.crow_off));
             }
             if (wave < batch && (thread_id() & 63) == 0) {
                 const int u = s_base + wave;
@@ -495,8 +495,8 @@ __global__ __launch_bounds__(NTHREADS) void dual_body_probe_kernel(BodyProbeArgs
         if (kk <= 0) return;
         rows_cap = kk;
     }
-    dual_step_body<float, KT, 1, false, false, false, 0, false, BibtexShape, KCAP>(
-        k.da, u, thread_id() & 63, smem, round, rows_cap, reinterpret_cast<const float *>(smem + k.crow_off));
+    using Body = DualCfgTile<DualCfg<float, KT, 1, false>, false, BibtexShape, KCAP>;     // as the tile kernel's instances
+    dual_step_body<Body>(k.da, u, thread_id() & 63, smem, round, rows_cap, reinterpret_cast<const float *>(smem + k.crow_off));
 }
 
 // ICNN_BE_SHAPE_*: the instance a launch with these arguments and this layout takes

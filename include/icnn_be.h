@@ -1345,7 +1345,7 @@ ICNN_BE_API void icnn_be_debug_trace(long long *device_buf);
 /* counters per sample of icnn_be_debug_profile's buffer (16): size the buffer from this, not from a literal */
 ICNN_BE_API int icnn_be_debug_profile_phases(void);
 /*
- * The exp / log / softplus / sigmoid the INNER iterations use in place of the math library's (be_dual_dev.h: fast_exp,
+ * The exp / log / softplus / sigmoid the INNER iterations use in place of the math library's (be_dual_math.h: fast_exp,
  * fast_log, softplus_fast, sigmoid_fast -- lean argument reductions + Horner polynomials; values that are final, y =
  * 1 / (1 + exp(A^T lam)) of lib/bundle_entropy_dual.py:165, keep the library routines), evaluated on caller-supplied
  * arguments: out[i] = f(x[i]), which = 0 exp, 1 log, 2 softplus (logexp1p, dual :6-12), 3 sigmoid.  Lets a test bound

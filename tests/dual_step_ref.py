@@ -366,7 +366,7 @@ def ipm_nv(K):
 
 def sums_path(plan, n, k, flags, rows):
     """(routine, instance size) that sample of k cuts runs on the launch `plan` with `rows` staged rows: be_dual_dev.h `valu`
-    (:1335), be_ipm_dev.h ipm_solve (:636-640, :721), be_dual_dev.h `waves_ok` (:1446).  'mfma' is the general sweep."""
+    (dual_step_body), be_ipm_dev.h ipm_solve (:636-640, :721), be_dual_dev.h `waves_ok` (dual_step_body).  'mfma' is the general sweep."""
     cut, kt, nw, variant, staged, kernel = plan
     n_pad = (n + 15) & ~15
     f32 = cut == "float"

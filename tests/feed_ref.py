@@ -142,7 +142,7 @@ def synth_state(seed, n, slots, cut_dtype, variant, ks, loss):
                       active=active, count=np.array(ks, dtype=np.int32), labels=labels, sat=sat)
 
 
-# ---- which instance the launcher picks (be_dual.hip launch_implicit_feed, be_dual_dev.h carve, be_common.h pw_build) ----------
+# ---- which instance the launcher picks (be_dual.hip launch_implicit_feed, be_dual_cut.h carve, be_common.h pw_build) ----------
 LDS_LIMIT = 160 * 1024
 
 

@@ -79,7 +79,7 @@ def _row_pitch(n_pad):
 
 
 def _carve(KT, rows, n, rl, ipm, own_const_rows=False):
-    """bytes of one sample's staging region: float32 cuts on one wave (carve, be_dual_dev.h)"""
+    """bytes of one sample's staging region: float32 cuts on one wave (carve, be_dual_cut.h)"""
     n_pad = _a16(n)
     o = _a16((rows + (2 if own_const_rows else 0)) * _row_pitch(n_pad) * 4) + 2 * _a16(n_pad * 8)
     o += _a16(n_pad * 8) * ((1 if rl or ipm else 0) + (2 if ipm else 0))

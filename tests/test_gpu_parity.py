@@ -1505,7 +1505,7 @@ def test_bibsonomy_pdipm_full_batch_matches_order_matched_oracle(n_iter):
 
 
 def test_fast_math_routines_of_the_inner_loops_are_accurate():
-    """fast_exp / fast_log / softplus_fast / sigmoid_fast (be_dual_dev.h) replaced the math library inside every Newton update
+    """fast_exp / fast_log / softplus_fast / sigmoid_fast (be_dual_math.h) replaced the math library inside every Newton update
     and interior-point iteration in round 5; their error bound lived in a probe nobody ran.
     Through the diagnostic export icnn_be_debug_fast_math, against x87 extended precision (64-bit significand): relative error
     <= 5e-16 on the ranges the iterations feed them, correct limits at the clamp (+-750), at +-inf, at subnormal log arguments,

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(512) void probe(double *out, double *sink, int k, i
 }
 
 // ---- Record of a withdrawn attempt (round 6): the Hessian sweep on SEVERAL waves, bit for bit. --------------
-// The maps below restate the two tiles of contract_mfma_cover2 (be_dual_dev.h); the probe asserts that the blocked sweep on
+// The maps below restate the two tiles of contract_mfma_cover2 (be_dual_mfma.h); the probe asserts that the blocked sweep on
 // eight waves reproduces the one-wave sweep in every entry for 9 .. 31 cuts.  It did (profiles/r06_blocked_sweep_probe.txt), and
 // the cooperative continuation of parked Newton solves built on it was bit-identical on every shape -- and slower
 // (profiles/r06_coop_continuation_withdrawn.txt), so neither is in the library.

@@ -1,6 +1,6 @@
-// Accuracy of fast_exp / fast_log (be_dual_dev.h) against the library routines, on the GPU: max relative error over dense
+// Accuracy of fast_exp / fast_log (be_dual_math.h) against the library routines, on the GPU: max relative error over dense
 // samples of the ranges the dual step feeds them.
-#include "be_dual_dev.h"
+#include "be_dual_math.h"
 #include <cstdio>
 #include <cmath>
 using namespace icnn_be;
