@@ -15,6 +15,7 @@ import zlib
 
 import numpy as np
 
+from icnn_amd._lib import FLAG_F64_ENERGY, FLAG_GLOBAL_BUNDLE, FLAG_MFMA_CONTRACTION, FLAG_WAVE_PER_SAMPLE
 from oracle import bundle_entropy_oracle as oracle
 
 LD = np.longdouble
@@ -22,8 +23,6 @@ F32, F64 = np.float32, np.float64
 SCALES = (1.0, 0.3, 0.05)          # mixed inside a batch: pruning happens without being constructed
 CONTROL = ("count", "n_iters", "finished", "status", "newton_iters", "t_next", "phase", "skip_fg")
 NEWTON_CAP = {"dual": 100, "rl": 20, "pdipm": 20}     # oracle.VARIANTS[*].newton_cap; interior_point's range(20)
-
-FLAG_F64_ENERGY, FLAG_GLOBAL_BUNDLE, FLAG_WAVE_PER_SAMPLE, FLAG_MFMA_CONTRACTION = 32, 64, 128, 256     # include/icnn_be.h
 
 
 class RoundState:

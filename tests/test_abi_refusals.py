@@ -114,7 +114,7 @@ D4 = [3, 2, 8, 8]                        # dimO, dimA, l1, l2
 
 
 def ll(n=1):
-    return [C.c_longlong() for _ in range(n)]
+    return [C.byref(C.c_longlong()) for _ in range(n)]          # a host out-parameter is declared void *: no implicit byref
 
 
 step_entries("icnn_be_ddpg_", _lib.DdpgArgs, lambda: fill(_lib.DdpgArgs, prate=1e-4, pl2norm=0.0, **SIZES, **STEP), DDPG_LIMITS,

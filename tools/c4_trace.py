@@ -24,7 +24,6 @@ x = torch.from_numpy((np.random.RandomState(1000).rand(B, spec.n_features) < 0.0
 model = picnn.FCModel(spec, params)
 ctx = model.context(x)
 lib = _lib.load()
-lib.icnn_be_debug_trace.argtypes = [C.c_void_p]
 solver = bundle_entropy.FusedSolver(model, B, n_iter, "dual")
 solver.solve(ctx)
 torch.cuda.synchronize()

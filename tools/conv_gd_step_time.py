@@ -131,9 +131,7 @@ def feed_alone(reps, warmup, inner, alt_lib, res):
     calls = [("feed_px", px_call(lib, new)), ("feed", old_call)]
     outs = [new, old]
     if alt_lib:
-        alt = C.CDLL(os.path.abspath(alt_lib))
-        alt.icnn_be_gd_feed_px.argtypes = lib.icnn_be_gd_feed_px.argtypes
-        alt.icnn_be_gd_feed_px.restype = C.c_int
+        alt = _lib.declare(C.CDLL(os.path.abspath(alt_lib)), ["icnn_be_gd_feed_px"])
         outs.append(buffers())
         calls.append(("feed_alt", px_call(alt, outs[-1])))
     for _ in range(2):                                   # alternate the candidates: two rounds each, the later one kept
