@@ -3,8 +3,12 @@ bundle-entropy solve's entropy-scaled objective mean(E - H(y)) per iteration aga
 objective at lr 0.1, 0.01 and 0.001 -- the data of the paper's convergence figure --, and the solve's own duality gap.
 
     python examples/ebundle_vs_gd.py [--model fc|conv] [--seed 0] [--variant pdipm|dual]
+                                     [--dataset bibtex|bookmarks|delicious] [--layerSizes 600 [600]]
 
---model fc    the multi-label script's settings: 10 samples, bundle nIter 10, PGD 10 iterations from y0 = 0.5
+--model fc    the multi-label script's settings: 10 samples, bundle nIter 10, PGD 10 iterations from y0 = 0.5, on a network
+              of the dataset's shape (bibtex 1836 features / 159 labels, bookmarks 2150 / 208, delicious 500 / 983) with the
+              hidden widths --layerSizes (the script's own default is 600 600; the label count is appended).  Shapes whose
+              16-sample evaluation tile outgrows the LDS run on tiles of 8 or 4 rows (model.tile_rows is printed)
 --model conv  the completion script's: 1 sample, bundle nIter 30, PGD 50 iterations from the mean image
 
 The scripts load a trained checkpoint; here the model is a seeded random draw in the "spread" regime (pre-activations of the
@@ -23,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from icnn_amd import bundle_entropy, pgd, picnn  # noqa: E402
 
 LRS = (0.1, 0.01, 0.001)                      # ebundle-vs-gd.py:119
+DATASETS = {"bibtex": picnn.bibtex_spec, "bookmarks": picnn.bookmarks_spec, "delicious": picnn.delicious_spec}
 
 
 def row(values):
@@ -34,11 +39,13 @@ def main():
     ap.add_argument("--model", choices=("fc", "conv"), default="fc")
     ap.add_argument("--variant", choices=("pdipm", "dual"), default="pdipm")     # the scripts import lib/bundle_entropy.py
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dataset", choices=sorted(DATASETS), default="bibtex")
+    ap.add_argument("--layerSizes", type=int, nargs="+", default=[600])
     a = ap.parse_args()
     torch.cuda.set_device(0)
     rng = np.random.RandomState(a.seed)
     if a.model == "fc":
-        spec = picnn.bibtex_spec()
+        spec = DATASETS[a.dataset](tuple(a.layerSizes))
         B, n_iter, K = 10, 10, 10                                                # ebundle-vs-gd.py:85,107,132
         model = picnn.FCModel(spec, picnn.init_params(spec, a.seed, "spread"), "cuda")
         x = torch.from_numpy((rng.rand(B, spec.n_features) < 0.04).astype(np.float32))
@@ -55,6 +62,9 @@ def main():
     gap = pgd.gap(model, ctx, res)
     runs = {lr: pgd.solve(model, ctx, torch.from_numpy(y0).cuda(), K, lr, final=True) for lr in LRS}
     calls = int(calls.item())
+    if a.model == "fc":
+        print("%s %s: %d features, %d labels, evaluation tiles of %d rows"
+              % (a.dataset, " ".join(map(str, a.layerSizes)), spec.n_features, spec.n_labels, model.tile_rows))
     print("%s, %d sample(s): mean entropy-scaled objective per iteration" % (a.model, B))
     print("bundle entropy (%s, %d of %d iterations)" % (a.variant, calls, n_iter))
     print("   ", row(obj[:calls].mean(dim=1).tolist()))

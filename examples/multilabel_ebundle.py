@@ -3,6 +3,12 @@ with no host data in it: the training set lives on the device (train.DeviceDatas
 draw, train.BundleTrainer.step, log row] are one graph that a train.EpochRunner captures once and replays.
 
     python examples/multilabel_ebundle.py [--steps 60] [--batch 64] [--every 10] [--test-every 20] [--save DIR] [--resume FILE]
+                                          [--dataset bibtex|bookmarks|delicious] [--layerSizes 600 [600]]
+
+Without --dataset the network is a small one (40 features, 16 labels, hidden widths 64); with it, the network has the
+dataset's shape (bibtex 1836 features / 159 labels, bookmarks 2150 / 208, delicious 500 / 983) and the hidden widths
+--layerSizes of the script, on synthetic data of that shape.  Shapes whose 16-sample evaluation tile outgrows the LDS run
+on tiles of 8 or 4 rows (FCModel.tile_rows).
 
 The labels are a noisy linear function of the features; the loss falls from the first steps on (685.7 at step 10 to 642.3 at
 step 60 with the defaults on an MI355X).
@@ -26,6 +32,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from icnn_amd import checkpoint, picnn, train  # noqa: E402
 
 
+DATASETS = {"bibtex": picnn.bibtex_spec, "bookmarks": picnn.bookmarks_spec, "delicious": picnn.delicious_spec}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
@@ -34,6 +43,8 @@ def main():
     ap.add_argument("--test-every", type=int, default=20)
     ap.add_argument("--save", default=None, metavar="DIR")
     ap.add_argument("--resume", default=None, metavar="FILE")
+    ap.add_argument("--dataset", choices=sorted(DATASETS), default=None)
+    ap.add_argument("--layerSizes", type=int, nargs="+", default=[600])
     a = ap.parse_args()
     if a.save and not a.test_every:
         ap.error("--save keeps the best model by test F1: it needs --test-every > 0")
@@ -41,13 +52,28 @@ def main():
     rng = np.random.RandomState(0)
     n_features, n_labels, n_train, n_test = 40, 16, 1024, 256
     spec = picnn.FCSpec(n_features, n_labels, (64, 32), alpha=0.0, batchnorm=True, action_box=False)
-    X = rng.rand(n_train, n_features).astype(np.float32)
-    W = rng.randn(n_features, n_labels)
-    Y = ((X - 0.5) @ W + 0.3 * rng.randn(n_train, n_labels) > 0.8).astype(np.float64)
+    if a.dataset:
+        spec = DATASETS[a.dataset](tuple(a.layerSizes))
+        n_features, n_labels = spec.n_features, spec.n_labels
     held_out = np.random.RandomState(1)                    # a generator of its own: the training data stay what they were
-    Xt = held_out.rand(n_test, n_features).astype(np.float32)
-    Yt = ((Xt - 0.5) @ W + 0.3 * held_out.randn(n_test, n_labels) > 0.8).astype(np.float64)
+    if a.dataset:                                          # bag-of-words features: 4 % of them set, as in the other examples
+        W = rng.randn(n_features, n_labels) / np.sqrt(0.04 * n_features)
+
+        def draw(g, rows):
+            x = (g.rand(rows, n_features) < 0.04).astype(np.float32)
+            return x, ((x - 0.04) @ W + 0.3 * g.randn(rows, n_labels) > 0.8).astype(np.float64)
+        X, Y = draw(rng, n_train)
+        Xt, Yt = draw(held_out, n_test)
+    else:
+        X = rng.rand(n_train, n_features).astype(np.float32)
+        W = rng.randn(n_features, n_labels)
+        Y = ((X - 0.5) @ W + 0.3 * rng.randn(n_train, n_labels) > 0.8).astype(np.float64)
+        Xt = held_out.rand(n_test, n_features).astype(np.float32)
+        Yt = ((Xt - 0.5) @ W + 0.3 * held_out.randn(n_test, n_labels) > 0.8).astype(np.float64)
     model = picnn.FCModel(spec, picnn.init_params(spec, 0, "spread"), "cuda")
+    if a.dataset:
+        print("%s %s: %d features, %d labels, evaluation tiles of %d rows"
+              % (a.dataset, " ".join(map(str, a.layerSizes)), n_features, n_labels, model.tile_rows))
     trainer = train.BundleTrainer(model, a.batch, n_iter=10, loss="xent", lr=1e-3, eval_batch=n_test if a.test_every else None)
     # the keeper moves the BatchNorm statistics into one buffer: built before anything is captured
     keeper = train.BestKeeper(trainer, mode="max", start=0.0) if a.save else None

@@ -83,7 +83,10 @@ def read_arrays(path) -> Dict[str, np.ndarray]:
 
 def spec_json(spec) -> str:
     """a model spec (a frozen dataclass of numbers, strings and tuples) as a JSON string"""
-    return json.dumps(dataclasses.asdict(spec), sort_keys=True)
+    d = dataclasses.asdict(spec)
+    if d.get("tile_rows", 0) is None:       # FCSpec's default (the library picks the tile): files from before the field still match
+        del d["tile_rows"]
+    return json.dumps(d, sort_keys=True)
 
 
 # --------------------------------------------------------------------------------------------- #

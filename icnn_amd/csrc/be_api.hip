@@ -306,6 +306,11 @@ size_t icnn_be_fc_pack_floats(const icnn_be_fc_model *shape) {
     return icnn_be::fc_pack_floats(*shape);
 }
 
+int icnn_be_fc_tile_rows(const icnn_be_fc_model *shape) {
+    if (!shape) return ICNN_BE_EINVAL;
+    return icnn_be::fc_tile_rows(*shape);
+}
+
 int icnn_be_fc_pack(const icnn_be_fc_model *shape, const float *const *w_yu_host,
                     const float *const *w_zu_host, float *out_host) {
     if (!shape || !w_yu_host || !w_zu_host || !out_host) return ICNN_BE_EINVAL;
@@ -389,6 +394,7 @@ int icnn_be_rl_bundle_solve(const icnn_be_fc_model *model, const float *ctx, con
         return ICNN_BE_EINVAL;
     if (!std::isfinite(y0_fill)) return ICNN_BE_EINVAL;
     if (int rc = check_fc_solve(model, st)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;  /* the agents' networks are small: 16-row models only */
     if (st->batch == 0) return 0;
     const SolvePlan p = plan_fc_solve(*model, *st, icnn_be::device_cus(), env_tile_budget());
     if (p.path < 0) return p.path;
@@ -600,6 +606,7 @@ int icnn_be_adam_fc(const icnn_be_fc_model *model, const float *ctx, int batch, 
     if (!model || !ctx || !act_best || !f_best || !iters || !workspace || !model->wpack) return ICNN_BE_EINVAL;
     if (batch < 0 || max_iter < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;      /* the Adam kernels own 16-row tiles */
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (batch == 0) {
         return done(hipMemsetAsync(iters, 0, sizeof(int), s));
@@ -614,6 +621,7 @@ int icnn_be_adam_fc_each(const icnn_be_fc_model *model, const float *ctx, int ba
     if (!model || !ctx || !act_best || !f_best || !iters || !workspace || !model->wpack) return ICNN_BE_EINVAL;
     if (batch < 0 || max_iter < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;      /* the Adam kernels own 16-row tiles */
     if (batch == 0) return 0;                          /* iters is [0]: nothing to write */
     hipError_t e = icnn_be::launch_adam_fc(*model, ctx, batch, max_iter, act_best, f_best, iters, workspace,
                                            static_cast<hipStream_t>(stream), nullptr, nullptr, true);
@@ -624,6 +632,7 @@ int icnn_be_adam_fc_each(const icnn_be_fc_model *model, const float *ctx, int ba
 int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int batch, int out[2]) {
     if (!model || !out || batch < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;
     icnn_be::AdamPlan p{};
     if (hipError_t e = icnn_be::adam_fc_plan(*model, nullptr, batch, p, true); e != hipSuccess) return fail(e);
     out[0] = p.per_wg; out[1] = p.workgroups;
@@ -633,6 +642,7 @@ int icnn_be_debug_adam_each_plan(const icnn_be_fc_model *model, int batch, int o
 int icnn_be_debug_adam_plan(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx, int batch, int out[4]) {
     if (!model || !out || batch < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;
     if (cx) {                                          /* what icnn_be_adam_fc_obs refuses */
         if (int rc = icnn_be::ctx_check(*cx)) return rc;
         if (cx->u_last_relu || cx->n != model->n || cx->n_layers != model->n_layers) return ICNN_BE_EINVAL;
@@ -650,6 +660,7 @@ int icnn_be_adam_fc_obs(const icnn_be_fc_model *model, const icnn_be_fc_ctx *cx,
     if (!model || !cx || !obs || !act_best || !f_best || !iters || !workspace || !model->wpack) return ICNN_BE_EINVAL;
     if (batch < 0 || max_iter < 1 || model->action_box) return ICNN_BE_EINVAL;
     if (int rc = icnn_be::fc_check_model(*model)) return rc;
+    if (icnn_be::fc_narrow_model(*model)) return ICNN_BE_ELIMIT;      /* the Adam kernels own 16-row tiles */
     if (int rc = icnn_be::ctx_check(*cx)) return rc;
     if (cx->u_last_relu) return ICNN_BE_EINVAL;        /* the in-kernel producer keeps the last u layer linear */
     /* the in-kernel context producer sizes its reads from the MODEL's layer widths while the stage matrices were laid out

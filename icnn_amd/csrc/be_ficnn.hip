@@ -213,6 +213,8 @@ __global__ __launch_bounds__(NTHREADS) void ficnn_fg_kernel(FicnnArgs a) {
 struct FicnnTile {
     template <typename A>
     static __device__ __forceinline__ void run(const A &fa, int tile, float *lds) { ficnn_fg_tile(fa, tile, lds); }
+    template <typename A>
+    static __device__ __forceinline__ int rows(const A &) { return TM; }
 };
 typedef GdTileArgs<FicnnArgs> FicnnGdArgs;
 

@@ -376,6 +376,9 @@ bool fused_tile_layout(const icnn_be_fc_model &m, const icnn_be_state &st, int t
     const bool rl = st.variant == ICNN_BE_VARIANT_RL, ipm = st.variant == ICNN_BE_VARIANT_PDIPM;
     if (st.cut_dtype != ICNN_BE_CUT_F32 || (tile_rows != 4 && tile_rows != 8 && tile_rows != TM)) return false;
     if (dual_waves(st.n, st.cut_dtype, st.variant) != 1 || ((ipm || rl) && budget > 0)) return false;
+    // a narrow model (icnn_be_fc_model.tile_rows 8 or 4) has no persistent tile kernel: the plan falls through to the launch
+    // pairs, whose fc_fg_kernel runs the narrow tile.  (The tile kernel's own 4 / 8 sample tiles are 16-row LDS layouts.)
+    if (fc_model_narrow(m)) return false;
     FcArgs fa{};
     int fg_bytes = 0;
     PairwisePlan plan;

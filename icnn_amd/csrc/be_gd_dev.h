@@ -108,7 +108,8 @@ struct MomentumRule {
 // ---- the tile form ----
 // Phase A reads its arguments from the kernel-argument segment and is inlined into the iteration loop, with the thread
 // index read opaquely (thread_id) and -mllvm -disable-machine-licm for the unit: the recipe of be_fused.hip / be_adam.hip.
-// Tile::run(fa, tile, lds) is the model's energy/gradient tile.
+// Tile::run(fa, tile, lds) is the model's energy/gradient tile, Tile::rows(fa) the samples it holds (TM; the FC-PICNN's narrow
+// tiles 8 or 4): tile t owns samples t * rows .. , wave w < rows the w-th of them.
 template <typename Tile, typename KArgs>
 __device__ __forceinline__ void gd_phase_fg(KArgs *kp, int tile) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -116,15 +117,16 @@ __device__ __forceinline__ void gd_phase_fg(KArgs *kp, int tile) {
     Tile::run(kp->fa, tile, lds);
 }
 
-// Phase B: wave w updates sample tile * TM + w (g and E from phase A through global memory); final: no update, the summing
+// Phase B: wave w updates sample tile * rows + w (g and E from phase A through global memory); final: no update, the summing
 // rule's record of the final evaluation alone
-template <typename Rule, typename KArgs>
+template <typename Tile, typename Rule, typename KArgs>
 __device__ __forceinline__ void gd_phase_update(KArgs *kp, int tile, int k, bool final) {
 #pragma clang fp contract(off)
     asm volatile("" : "+s"(kp), "+s"(tile), "+s"(k));
     const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-    const int n = kp->fa.n, u = tile * TM + wave;
-    if (u >= kp->fa.batch) return;
+    const int TR = Tile::rows(kp->fa);
+    const int n = kp->fa.n, u = tile * TR + wave;
+    if (wave >= TR || u >= kp->fa.batch) return;
     const size_t row = (size_t)u * n;
     const typename Rule::Iter it = Rule::iter(*kp, u, k);
     [[maybe_unused]] double part = 0.0;
@@ -157,8 +159,9 @@ __device__ __forceinline__ void gd_tile_loop(const Args &a) {
     const int tile = blockIdx.x;
     {
         const int tid = thread_id(), wave = tid >> 6, lane = tid & 63;
-        const int n = a.fa.n, u = tile * TM + wave;
-        if (u < a.fa.batch)
+        const int TR = Tile::rows(a.fa);
+        const int n = a.fa.n, u = tile * TR + wave;
+        if (wave < TR && u < a.fa.batch)
             for (int j = lane; j < n; j += 64) {
                 const size_t i = (size_t)u * n + j;
                 Rule::store(a, i, Rule::start(a, a.y0[i]));
@@ -169,14 +172,14 @@ __device__ __forceinline__ void gd_tile_loop(const Args &a) {
     for (int k = 0; k < K; ++k) {
         gd_phase_fg<Tile>(kp, tile);
         __syncthreads();                                 // g and E of the tile visible to its update waves
-        gd_phase_update<Rule>(kp, tile, k, false);
+        gd_phase_update<Tile, Rule>(kp, tile, k, false);
         __syncthreads();                                 // y_{k+1} visible to the tile's next phase A
     }
     if (Rule::wants_final(a)) {
         gd_phase_fg<Tile>(kp, tile);                     // E(y_K) -> fa.f
         if constexpr (Rule::sums) {
             __syncthreads();
-            gd_phase_update<Rule>(kp, tile, K, true);
+            gd_phase_update<Tile, Rule>(kp, tile, K, true);
         }
     }
 }

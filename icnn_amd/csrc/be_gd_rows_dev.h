@@ -12,6 +12,8 @@ namespace {
 struct FcTile {           // phase A of gd_tile_loop
     template <typename A>
     static __device__ __forceinline__ void run(const A &fa, int tile, float *lds) { fc_fg_tile(fa, tile, lds); }
+    template <typename A>
+    static __device__ __forceinline__ int rows(const A &fa) { return fa.tile_rows; }
 };
 
 template <typename Rule>
@@ -98,7 +100,7 @@ hipError_t launch_fc_gd_rule(const icnn_be_fc_model &m, const A &a, int batch, i
                              stream, r);
     }
     if (tile_lds > LDS_BYTES) return hipErrorNotSupported;
-    return launch_kernel(tile_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), tile_lds, stream, a);
+    return launch_kernel(tile_kernel, dim3((batch + a.fa.tile_rows - 1) / a.fa.tile_rows), dim3(NTHREADS), tile_lds, stream, a);
 }
 
 }  // namespace

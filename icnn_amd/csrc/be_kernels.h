@@ -133,6 +133,10 @@ hipError_t launch_implicit_feed(const icnn_be_state &st, const double *y_true, i
 
 // ---- FC-PICNN energy / gradient --------------------------------------------------
 int fc_check_model(const icnn_be_fc_model &m);
+// the rows of a model's evaluation tile (icnn_be_fc_model.tile_rows): fc_narrow_model -- 8 or 4, LDS sized for that many;
+// fc_tile_rows -- the largest of 16, 8, 4 that fits the LDS (icnn_be_fc_tile_rows), or ICNN_BE_ELIMIT / ICNN_BE_EINVAL
+bool fc_narrow_model(const icnn_be_fc_model &m);
+int fc_tile_rows(const icnn_be_fc_model &m);
 int fc_deal_units(const icnn_be_fc_model &m, int *out, int cap);   // icnn_be_debug_fc_deal
 size_t fc_pack_floats(const icnn_be_fc_model &m);
 int fc_pack(const icnn_be_fc_model &m, const float *const *w_yu, const float *const *w_zu, float *out);

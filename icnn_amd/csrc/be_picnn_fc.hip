@@ -94,7 +94,7 @@ hipError_t launch_fc_fg(const icnn_be_fc_model &m, const float *ctx, const doubl
             return launch_kernel(fc_fg_rows_kernel, dim3((batch + per_wg - 1) / per_wg), dim3(RTHREADS), rows_lds, stream, r);
         }
     }
-    return launch_kernel(fc_fg_kernel, dim3((batch + TM - 1) / TM), dim3(NTHREADS), lds, stream, a);
+    return launch_kernel(fc_fg_kernel, dim3((batch + a.tile_rows - 1) / a.tile_rows), dim3(NTHREADS), lds, stream, a);
 }
 
 hipError_t launch_fc_clamp(const icnn_be_fc_model &m, int mode, hipStream_t stream) {
@@ -119,6 +119,19 @@ int fc_check_model(const icnn_be_fc_model &m) {
     FcArgs a{};
     int lds = 0;
     return fill_args(m, a, lds);
+}
+
+bool fc_narrow_model(const icnn_be_fc_model &m) { return fc_model_narrow(m); }
+
+// icnn_be_fc_tile_rows: the largest tile of 16, 8, 4 rows whose LDS buffers fit, whatever m.tile_rows says
+int fc_tile_rows(const icnn_be_fc_model &m) {
+    for (int R = TM; R >= 4; R /= 2) {
+        FcGeom g{};
+        if (int rc = fc_geom(m.n, m.n_layers, m.width, g, R)) return rc;
+        if (g.ctx_width != m.ctx_width) return ICNN_BE_EINVAL;
+        if (g.lds_floats * 4 <= LDS_BYTES) return R;
+    }
+    return ICNN_BE_ELIMIT;
 }
 
 

@@ -7,7 +7,8 @@
 //   dE/dy = sum_i yu_i * (delta_i Wyu_i^T),  delta_{i-1} = gate_i * (delta_i Wzu_i^T) * act'(.)
 //   (what tf.gradients(E_, y_) evaluates, icnn_ebundle.py:146).
 //
-// One workgroup owns a tile of TM = 16 samples (one MFMA M-tile) for the whole chain: the
+// One workgroup owns a tile of TM = 16 samples (one MFMA M-tile; 8 or 4 for a model whose 16-row tile outgrows the LDS:
+// icnn_be_fc_model.tile_rows, FcGeom.lds_rows) for the whole chain: the
 // activations never leave LDS, the x-only context (yu, zu, gate) is read once per layer with
 // coalesced loads, and the non-negative W^(z) / unconstrained W^(y) weights are streamed from
 // L2/HBM exactly once per workgroup per pass as pre-packed v_mfma_f32_16x16x4_f32 B-fragments
@@ -47,13 +48,14 @@ struct FcArgs {
     long long w_zu_f[ICNN_BE_MAX_LAYERS], w_zu_b[ICNN_BE_MAX_LAYERS];
     int zb_off[ICNN_BE_MAX_LAYERS], zb_ld[ICNN_BE_MAX_LAYERS];          // LDS float offsets / pitches
     int ldY, ybuf_off, aop_off[ICNN_BE_MAX_LAYERS], gbuf_off, dl_off, lds_floats;   // aop_i = y * yu_i
+    int lds_rows;                          // rows every LDS buffer holds: TM, or the model's narrow tile (8, 4); >= tile_rows
     FcDeal deal;
     const float *wpack, *ctx;
     const double *y;
     float *f, *g;
     const int *finished;
     int batch;
-    int tile_rows;      // samples a workgroup's 16-row MFMA tile actually holds (16; 4 or 8 when the batch has fewer
+    int tile_rows;      // samples a workgroup's 16-row MFMA tile actually holds (lds_rows; 4 or 8 when the batch has fewer
                         // than a full tile per CU: be_fused.hip) -- the other rows are zero
     long long *prof;    // diagnostic: [workgroup][wave][FC_PROF_PHASES] cycle counters, else nullptr
 };
@@ -153,6 +155,7 @@ struct FcGeom {
     long long w_zu_f[ICNN_BE_MAX_LAYERS], w_zu_b[ICNN_BE_MAX_LAYERS];
     int zb_off[ICNN_BE_MAX_LAYERS], zb_ld[ICNN_BE_MAX_LAYERS];
     int ldY, ybuf_off, aop_off[ICNN_BE_MAX_LAYERS], gbuf_off, dl_off, lds_floats;
+    int lds_rows;
     FcDeal deal;
 };
 
@@ -217,9 +220,12 @@ __host__ __device__ constexpr int fc_home_wave(int t) { return t % NWAVE; }
 __host__ __device__ constexpr int fc_home_wave_dedy(int layer, int t) { return layer > 0 ? NWAVE - 1 - t % NWAVE : t % NWAVE; }
 
 // 0, or ICNN_BE_EINVAL: not a network (no hidden layer, too many, a width below 1, a final width other than 1)
-constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a) {
+// R: the rows of the evaluation tile (TM, 8 or 4) -- the LDS buffers hold R rows each, nothing else depends on it
+constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a, int R = TM) {
     const int L = n_layers - 1;
     if (L < 1 || n_layers > ICNN_BE_MAX_LAYERS || width[L] != 1 || n < 1) return ICNN_BE_EINVAL;
+    if (R != TM && R != 8 && R != 4) return ICNN_BE_EINVAL;
+    a.lds_rows = R;
     a.n = n;
     a.L = L;
     int o = 0, lo = 0;
@@ -238,14 +244,14 @@ constexpr int fc_geom(int n, int n_layers, const int *width, FcGeom &a) {
         a.w_zu_f[i] = po.zu_f[i]; a.w_zu_b[i] = po.zu_b[i];
     }
     a.ldY = lds_pitch(n);
-    a.ybuf_off = lo; lo += TM * a.ldY;
-    for (int i = 0; i < L; ++i) { a.aop_off[i] = lo; lo += TM * a.ldY; }
-    a.gbuf_off = lo; lo += TM * a.ldY;
+    a.ybuf_off = lo; lo += R * a.ldY;
+    for (int i = 0; i < L; ++i) { a.aop_off[i] = lo; lo += R * a.ldY; }
+    a.gbuf_off = lo; lo += R * a.ldY;
     for (int i = 0; i < L; ++i) {
         a.zb_ld[i] = lds_pitch(width[i]);
-        a.zb_off[i] = lo; lo += TM * a.zb_ld[i];
+        a.zb_off[i] = lo; lo += R * a.zb_ld[i];
     }
-    a.dl_off = lo; lo += TM * a.zb_ld[L - 1];
+    a.dl_off = lo; lo += R * a.zb_ld[L - 1];
     a.lds_floats = lo;
     a.deal = fc_deal(n, L, width);
     return 0;
@@ -255,6 +261,7 @@ template <typename Dst>
 constexpr void fc_geom_copy(Dst &d, const FcGeom &g) {
     d.n = g.n; d.L = g.L; d.ctx_width = g.ctx_width;
     d.ldY = g.ldY; d.ybuf_off = g.ybuf_off; d.gbuf_off = g.gbuf_off; d.dl_off = g.dl_off; d.lds_floats = g.lds_floats;
+    d.lds_rows = g.lds_rows;
     d.deal = g.deal;
     for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i) {
         d.width[i] = g.width[i];
@@ -266,7 +273,7 @@ constexpr void fc_geom_copy(Dst &d, const FcGeom &g) {
 template <typename A>
 constexpr bool fc_geom_same(const A &a, const FcGeom &g) {
     bool ok = a.n == g.n && a.L == g.L && a.ctx_width == g.ctx_width && a.ldY == g.ldY && a.ybuf_off == g.ybuf_off &&
-              a.gbuf_off == g.gbuf_off && a.dl_off == g.dl_off && a.lds_floats == g.lds_floats;
+              a.gbuf_off == g.gbuf_off && a.dl_off == g.dl_off && a.lds_floats == g.lds_floats && a.lds_rows == g.lds_rows;
     for (int i = 0; i < ICNN_BE_MAX_LAYERS; ++i)
         ok = ok && a.width[i] == g.width[i] && a.yu_off[i] == g.yu_off[i] && a.zu_off[i] == g.zu_off[i] &&
              a.gate_off[i] == g.gate_off[i] && a.w_yu_f[i] == g.w_yu_f[i] && a.w_yu_b[i] == g.w_yu_b[i] &&
@@ -289,6 +296,7 @@ struct FixedShape : FixedDual<N> {
     static constexpr FcGeom GEOM = make();
     static_assert(N_LAYERS >= 2 && N_LAYERS <= ICNN_BE_MAX_LAYERS && GEOM.L == N_LAYERS - 1, "not a network");
     static_assert(GEOM.lds_floats * 4 <= LDS_BYTES, "the tile's activation buffers do not fit the LDS");
+    static_assert(GEOM.lds_rows == TM, "the fixed instances are 16-row tiles");
     template <typename A> static __device__ __forceinline__ const FcGeom &fc(const A &) { return GEOM; }
 };
 
@@ -304,6 +312,8 @@ __device__ __forceinline__ float act_fn(float p, float alpha) { return p > 0.f ?
 // otherwise the wait-count pass, merging that order with the loop's at the loop header, drains the ring with vmcnt(0) in every
 // turn --, and a slot's refill behind the MFMAs that read it.
 // Per output element the accumulation is the k-ordered fma chain oracle/picnn_chain.c reproduces.
+// A narrow tile (A holds R = 8 or 4 rows, gemm_tiles' rmask = R - 1): an MFMA output row depends on its own A row alone, so the
+// lanes of rows >= R gather row r16 & rmask -- a valid one -- and the callers drop their outputs.  One AND in front of the loop.
 //
 // `pre` (the first GEMM of a unit): the requests of the unit's epilogue operands -- eight or nine context loads per lane that
 // miss the L2 --, issued BEHIND the ring's first RD requests.  The vector-memory counter retires in order: requested in front
@@ -370,12 +380,12 @@ __device__ __forceinline__ void gemm_loop(const float *ap, const f4 *bp0, const 
     for (int kb0 = PEEL ? RD : 0; kb0 < KB; kb0 += RD) turn(kb0);
 }
 template <typename Pre = NoPre>
-__device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *Wp, int KB, int NT, int nt0, int nt1,
+__device__ __forceinline__ void gemm_tiles(const float *A, int ld, int rmask, const float *Wp, int KB, int NT, int nt0, int nt1,
                                            f4 &acc0, f4 &acc1, Pre pre = Pre{}) {
     const int lane = thread_id() & 63, r16 = lane & 15, q = lane >> 4;
     nt0 = __builtin_amdgcn_readfirstlane(nt0);
     nt1 = __builtin_amdgcn_readfirstlane(nt1);
-    const float *ap = A + r16 * ld + 4 * q;
+    const float *ap = A + (r16 & rmask) * ld + 4 * q;
     const f4 *bp0 = reinterpret_cast<const f4 *>(Wp) + (size_t)nt0 * 64 + lane;
     const f4 *bp1 = reinterpret_cast<const f4 *>(Wp) + (size_t)(nt1 >= 0 ? nt1 : nt0) * 64 + lane;
     const size_t kstride = (size_t)NT * 64;              // f4 elements between consecutive k-blocks of a tile
@@ -402,6 +412,13 @@ __device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *
     }
 }
 
+// (A of TM rows: be_ficnn.hip)
+template <typename Pre = NoPre>
+__device__ __forceinline__ void gemm_tiles(const float *A, int ld, const float *Wp, int KB, int NT, int nt0, int nt1,
+                                           f4 &acc0, f4 &acc1, Pre pre = Pre{}) {
+    gemm_tiles(A, ld, TM - 1, Wp, KB, NT, nt0, nt1, acc0, acc1, pre);
+}
+
 // One tile of TM samples (workgroup-wide: NTHREADS threads, `lds` = the dynamic shared memory of the workgroup).
 // Stand-alone kernel: one workgroup per tile.  be_fused.hip calls it once per round from its persistent workgroup.
 // Shape (be_kernels.h): where the geometry comes from -- the arguments (DynShape), or constants (FixedShape: `ge` below is a
@@ -417,6 +434,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     const int TR = a.tile_rows;
     const int s0 = tile * TR;
     const int rows = min(TR, a.batch - s0);
+    const int LR = ge.lds_rows, rmask = LR - 1;      // rows of the LDS buffers (a constant TM for a fixed shape); rows <= LR
     const int n = ge.n, L = ge.L, C = ge.ctx_width, ldY = ge.ldY;
     const int npad = pad16(n);
     float *ybuf = lds + ge.ybuf_off;      // y (network input)
@@ -443,7 +461,8 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     float *gbuf = lds + ge.gbuf_off;      // dE/dy accumulator of the backward pass
     float *dl = lds + ge.dl_off;          // delta_{L-1} (the activations z_{L-1} stay intact for the energy)
 
-    // Wave w prepares row w of the tile (TM == NWAVE): no index arithmetic beyond lane strides.
+    // Wave w prepares row w of the tile (TM == NWAVE): no index arithmetic beyond lane strides.  A narrow tile has rows for
+    // the first LR waves only: the others load nothing (their row is none of the batch's) and store nothing.
     // The GEMMs read k-blocks up to a multiple of PF, i.e. pad columns [pad16(width), pitch) that no phase writes:
     // zero them (their packed weights are zero, but 0 * stale-NaN would not be).  Everything below pad16(width) is
     // written for all TM rows by the phase that produces the buffer.
@@ -451,7 +470,8 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
     {
         auto zero_pad = [&](float *buf, int ld, int width) {
             const int w16 = pad16(width);
-            for (int j = w16 + lane; j < ld; j += 64) buf[wave * ld + j] = 0.f;
+            if (wave < LR)
+                for (int j = w16 + lane; j < ld; j += 64) buf[wave * ld + j] = 0.f;
         };
         for (int i = 0; i < L; ++i) zero_pad(lds + ge.aop_off[i], ldY, n);
         for (int i = 0; i < L; ++i) zero_pad(lds + ge.zb_off[i], ge.zb_ld[i], ge.width[i]);
@@ -478,7 +498,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int j = j0 + 64 * k + lane;
-                if (j < npad) {
+                if (j < npad && r < LR) {
                     const float v = a.action_box ? (float)(2.0 * yd[k] - 1.0) : (float)yd[k];
                     const bool ok = row_ok && j < n;
                     ybuf[r * ldY + j] = ok ? v : 0.f;
@@ -532,9 +552,9 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                     }
                 }
             };
-            gemm_tiles(lds + ge.aop_off[i], ldY, Wy, KBy, NT, nt, nt1, acc[0], acc[1], operands);
+            gemm_tiles(lds + ge.aop_off[i], ldY, rmask, Wy, KBy, NT, nt, nt1, acc[0], acc[1], operands);
             if (i > 0)
-                gemm_tiles(lds + ge.zb_off[i - 1], ge.zb_ld[i - 1], a.wpack + ge.w_zu_f[i],
+                gemm_tiles(lds + ge.zb_off[i - 1], ge.zb_ld[i - 1], rmask, a.wpack + ge.w_zu_f[i],
                            kblocks_tile(ge.width[i - 1]), NT, nt, nt1, acc[0], acc[1]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -552,8 +572,10 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                         const float gw = cgt[h][r] * wz[h];
                         d = gw * (v > 0.f ? 1.f : a.alpha);
                     }
-                    zout[row * ldo + col] = v;
-                    if (last) dl[row * ldo + col] = d;
+                    if (row < LR) {                           // (a narrow tile has no such row: its output is dropped)
+                        zout[row * ldo + col] = v;
+                        if (last) dl[row * ldo + col] = d;
+                    }
                 }
             }
         }
@@ -588,7 +610,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                 cyL[r] = c[offL + cc];
             }
         };
-        gemm_tiles(delta, ge.zb_ld[j], a.wpack + ge.w_yu_b[j], kblocks_tile(ge.width[j]), NTy, nt, -1, acc, none, operands);
+        gemm_tiles(delta, ge.zb_ld[j], rmask, a.wpack + ge.w_yu_b[j], kblocks_tile(ge.width[j]), NTy, nt, -1, acc, none, operands);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = 4 * q + r;
@@ -630,7 +652,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                         cga[r] = ctx[(size_t)(row < rows ? row : 0) * C + ge.gate_off[i] + cc];
                     }
                 };
-                gemm_tiles(delta, ldd, Wt, KB, NTp, nt, -1, acc, none, operands);
+                gemm_tiles(delta, ldd, rmask, Wt, KB, NTp, nt, -1, acc, none, operands);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 4 * q + r;
@@ -640,7 +662,7 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
                         const float ga = gate * acc[r];
                         d = ga * (zprev[row * ldp + col] > 0.f ? 1.f : a.alpha);
                     }
-                    zprev[row * ldp + col] = d;
+                    if (row < LR) zprev[row * ldp + col] = d;
                 }
             }
         }
@@ -734,14 +756,22 @@ __device__ __forceinline__ void fc_fg_tile(const ArgsT &a, int tile, float *lds)
 }
 
 
+// rows of the model's evaluation tile: TM (tile_rows 0 or 16), a narrow tile (8, 4), or 0: not a tile
+inline int fc_model_rows(const icnn_be_fc_model &m) {
+    return m.tile_rows == 0 || m.tile_rows == TM ? TM : m.tile_rows == 8 || m.tile_rows == 4 ? m.tile_rows : 0;
+}
+inline bool fc_model_narrow(const icnn_be_fc_model &m) { return fc_model_rows(m) != TM; }
+
 inline int fill_args(const icnn_be_fc_model &m, FcArgs &a, int &lds_bytes) {
     FcGeom g{};
-    if (int rc = fc_geom(m.n, m.n_layers, m.width, g)) return rc;
+    const int R = fc_model_rows(m);
+    if (R == 0) return ICNN_BE_EINVAL;
+    if (int rc = fc_geom(m.n, m.n_layers, m.width, g, R)) return rc;
     if (g.ctx_width != m.ctx_width) return ICNN_BE_EINVAL;
     fc_geom_copy(a, g);
     a.alpha = m.alpha;
     a.action_box = m.action_box;
-    a.tile_rows = TM;
+    a.tile_rows = R;
     lds_bytes = g.lds_floats * 4;
     if (lds_bytes > LDS_BYTES) return ICNN_BE_ELIMIT;
     a.wpack = m.wpack;

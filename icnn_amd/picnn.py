@@ -17,7 +17,7 @@ names ('u0/W', 'z1_zu_proj/W', ...), W stored [in, out] as tflearn does.
 """
 import ctypes as C
 from dataclasses import dataclass, replace
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -36,6 +36,7 @@ class FCSpec:
     batchnorm: bool = True    # u-path BN in batch-statistics mode (icnn_ebundle.py:209,259)
     action_box: bool = False  # RL wrapper: network sees 2y-1, gradient doubled (icnn.py:148-158)
     relu_last_u: bool = False  # synthetic-cls f_picnn ReLUs every u-layer (icnn.py:236-276); elsewhere the last one is linear
+    tile_rows: Optional[int] = None   # samples per evaluation tile (16, 8, 4); None: the largest whose LDS buffers fit
 
     @property
     def widths(self) -> List[int]:
@@ -93,10 +94,20 @@ class FCSpec:
         return out
 
 
-def bibtex_spec():
+def bibtex_spec(szs=(600,)):
     """multi-label-cls defaults: 1836 features, 159 labels, --layerSizes 600
-    (icnn_ebundle.py:40; bibsonomy.py:19)."""
-    return FCSpec(1836, 159, (600, 159))
+    (icnn_ebundle.py:40; bibsonomy.py:19).  `szs`: --layerSizes; the label count is appended (icnn_ebundle.py:321-323)."""
+    return FCSpec(1836, 159, tuple(szs) + (159,))
+
+
+def bookmarks_spec(szs=(600,)):
+    """multi-label-cls --dataset bookmarks: 2150 features, 208 labels."""
+    return FCSpec(2150, 208, tuple(szs) + (208,))
+
+
+def delicious_spec(szs=(600,)):
+    """multi-label-cls --dataset delicious: 500 features, 983 labels (an evaluation tile of 4 rows: FCModel.tile_rows)."""
+    return FCSpec(500, 983, tuple(szs) + (983,))
 
 
 def halfcheetah_spec():
@@ -507,9 +518,15 @@ class FCModel(_PICNNDevice):
         m.ctx_width = spec.ctx_width
         m.wpack = None
         self.c_model = m
+        # rows of the evaluation tile: the spec's, or the largest of 16, 8, 4 whose activation buffers fit the LDS
+        rows = self._lib.icnn_be_fc_tile_rows(C.byref(m)) if spec.tile_rows is None else int(spec.tile_rows)
+        if rows == _lib.ELIMIT:
+            raise ValueError("model shape rejected by libicnn_be (layer count / widths / LDS budget)")
+        m.tile_rows = max(rows, 0)          # (another error: the pack refuses the shape below)
         n_floats = self._lib.icnn_be_fc_pack_floats(C.byref(m))
         if n_floats == 0:
             raise ValueError("model shape rejected by libicnn_be (layer count / widths / LDS budget)")
+        self.tile_rows = int(m.tile_rows)
         self.n_pack_floats = int(n_floats)
         self._init_bn_stats()
         self.repack(params)                     # y-path pack + x-only stage weights

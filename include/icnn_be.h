@@ -205,6 +205,13 @@ typedef struct icnn_be_fc_model {
     int action_box;                     /* 1: RL wrapper, network sees 2y-1 and dE/dy is doubled
                                            (RL/src/icnn.py:148-158) */
     int ctx_width;                      /* floats per context row (checked against the shape) */
+    int tile_rows;                      /* samples per evaluation tile: 0 or 16 = the 16-row MFMA tile, whose activation
+                                           buffers must fit 160 KB of LDS (else ICNN_BE_ELIMIT from every entry); 8 or 4 = a
+                                           narrow tile, the LDS sized for that many rows (icnn_be_fc_tile_rows() picks one).
+                                           Results do not depend on it bit for bit, the pack neither.  Anything else is
+                                           ICNN_BE_EINVAL.  Narrow tiles: fg, solve (per-sample kernel or launch pairs), gd,
+                                           pgd, context and the training entries; icnn_be_adam_fc* and
+                                           icnn_be_rl_bundle_solve return ICNN_BE_ELIMIT for 8 and 4 */
     const float *wpack;                 /* packed y-path weights, icnn_be_fc_pack_floats() floats */
 } icnn_be_fc_model;
 
@@ -270,8 +277,15 @@ ICNN_BE_API int icnn_be_state_init(const icnn_be_state *st, void *stream);
  */
 ICNN_BE_API int icnn_be_dual_step(const icnn_be_state *st, int t, const void *f, const void *g, void *stream);
 
-/* Number of floats of the packed weight buffer for a model shape (wpack may be NULL). */
+/* Number of floats of the packed weight buffer for a model shape (wpack may be NULL); 0 for a shape the entries refuse.
+ * The pack does not depend on shape->tile_rows: same count and contents for 16, 8 and 4. */
 ICNN_BE_API size_t icnn_be_fc_pack_floats(const icnn_be_fc_model *shape);
+
+/* The largest evaluation tile of 16, 8 or 4 rows whose activation buffers fit 160 KB of LDS for this shape (n, n_layers,
+ * width, ctx_width are read; shape->tile_rows is ignored): the value to store in tile_rows.  ICNN_BE_ELIMIT: not even four
+ * rows fit; ICNN_BE_EINVAL: not a network.  Host arithmetic.  The tile needs
+ * 4 R (pitch(n) (L + 2) + sum_i pitch(width[i]) + pitch(width[L-1])) bytes, pitch() the LDS row pitch of a width. */
+ICNN_BE_API int icnn_be_fc_tile_rows(const icnn_be_fc_model *shape);
 
 /*
  * Pack the y-path weights for the kernels (host -> host; upload the result and
