@@ -16,6 +16,11 @@ struct Pair {
     double a, b;
     int ok;
 };
+// LDS (and, GSRC, device-memory) pointers of the column passes and the factor: ds / global instead of flat accesses
+typedef __attribute__((address_space(3))) double *LdsDbl;
+typedef const __attribute__((address_space(3))) double *LdsCDbl;
+template <typename CutT, bool GSRC = false>
+using IpmCutPtr = std::conditional_t<GSRC, const __attribute__((address_space(1))) CutT *, const __attribute__((address_space(3))) CutT *>;
 
 // Full-wave reductions without the LDS crossbar: __shfl_xor is two ds_bpermute per double and step, six dependent steps --
 // about 1.2 k cycles per reduction, and an interior-point iteration does two dozen (round 4: 28 k of its ~45 k cycles).  Here:
@@ -99,8 +104,12 @@ __device__ __noinline__ Pair spd_solve2(const double *Hm_, int HP, int k, double
 // 1 and multiplier -0 and are processed like any other, so the elimination is straight-line code; 1 / pivot by v_rcp_f64 +
 // two Newton-Raphson steps.  Same elimination order as spd_solve2 (natural order, no pivoting).  Round 4: 4384 -> 3466 us
 // per 4096 x 10 solve, 1745 -> 1365 us at 128 x 10.
-template <int KS>
-__device__ __noinline__ Pair spd_solve2_dpp(const double *Hm_, int HP, int k, double diag, double ra, double rb) {
+// The corrector's system has the SAME matrix as the predictor's (:41-43 factor once, :48 and :63 solve twice): FACTOR = true
+// leaves the elimination's multipliers (below the diagonal), 1 / pivot (diagonal) and upper triangle in F[KS][KS] (LDS, row =
+// lane), and spd_resolve_dpp replays them on another right-hand side: KS forward and KS backward steps instead of the
+// O(KS^2) elimination.  FACTOR = false keeps 1 / pivot in a register of its own and touches no F.
+template <int KS, bool FACTOR>
+__device__ __noinline__ Pair spd_eliminate2_dpp(const double *Hm_, int HP, int k, double diag, double ra, double rb, double *F_) {
     static_assert(KS <= 16, "row broadcasts stay inside one 16-lane row");
     const int lane = lane_id();
     lds_cdouble *Hm = (lds_cdouble *)Hm_;
@@ -122,7 +131,7 @@ __device__ __noinline__ Pair spd_solve2_dpp(const double *Hm_, int HP, int k, do
         const double d = row_bcast<p>(M[p]);
         bad |= !(d > 0.0);
         const double inv = rcp_nr(d);
-        rinv = lane == p ? inv : rinv;
+        if constexpr (!FACTOR) rinv = lane == p ? inv : rinv;
         const double nf = lane > p ? -(M[p] * inv) : 0.0;
         static_for<p + 1, KS>([&](auto J) {
             constexpr int j = decltype(J)::value;
@@ -130,61 +139,20 @@ __device__ __noinline__ Pair spd_solve2_dpp(const double *Hm_, int HP, int k, do
         });
         ra = __builtin_fma(nf, row_bcast<p>(ra), ra);
         rb = __builtin_fma(nf, row_bcast<p>(rb), rb);
+        if constexpr (FACTOR) M[p] = lane > p ? nf : (lane == p ? inv : M[p]);    // the factor: multiplier | 1 / pivot | upper triangle
         __builtin_amdgcn_sched_barrier(0);     // keep the broadcasts of later pivots from being hoisted (registers)
     });
-    static_for<0, KS>([&](auto Q) {
-        constexpr int p = KS - 1 - decltype(Q)::value;
-        const double xa = row_bcast<p>(ra * rinv), xb = row_bcast<p>(rb * rinv);
-        ra = lane == p ? xa : (lane < p ? __builtin_fma(-M[p], xa, ra) : ra);
-        rb = lane == p ? xb : (lane < p ? __builtin_fma(-M[p], xb, rb) : rb);
-    });
-    return Pair{ra, rb, (__ballot(bad && lane < KS) & 0xffffull) ? 0 : 1};
-}
-// The corrector's system has the SAME matrix as the predictor's (:41-43 factor once, :48 and :63 solve twice): FACTOR = true
-// leaves the elimination's multipliers (below the diagonal), 1 / pivot (diagonal) and upper triangle in F[KS][KS] (LDS, row =
-// lane), and spd_resolve_dpp replays them on another right-hand side: KS forward and KS backward steps instead of the
-// O(KS^2) elimination.
-template <int KS>
-__device__ __noinline__ Pair spd_factor2_dpp(const double *Hm_, int HP, int k, double diag, double ra, double rb, double *F_) {
-    static_assert(KS <= 16, "row broadcasts stay inside one 16-lane row");
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    const int lane = lane_id();
-    lds_cdouble *Hm = (lds_cdouble *)Hm_;
-    LdsDbl F = (LdsDbl)F_;
-    HP = uni(HP); k = uni(k);
-    double M[KS];
-    const int rl = lane < k ? lane : 0;
+    if constexpr (FACTOR) {
+        if (lane < KS) {
 #pragma unroll
-    for (int j = 0; j < KS; ++j) M[j] = Hm[rl * HP + (j < k ? j : 0)];
-#pragma unroll
-    for (int j = 0; j < KS; ++j) pin(M[j]);
-#pragma unroll
-    for (int j = 0; j < KS; ++j)
-        M[j] = (lane < k && j < k) ? M[j] + (j == lane ? diag : 0.0) : (j == lane ? 1.0 : 0.0);
-    if (!(lane < k)) { ra = 0.0; rb = 0.0; }
-    bool bad = false;
-    static_for<0, KS>([&](auto P) {
-        constexpr int p = decltype(P)::value;
-        const double d = row_bcast<p>(M[p]);
-        bad |= !(d > 0.0);
-        const double inv = rcp_nr(d);
-        const double nf = lane > p ? -(M[p] * inv) : 0.0;
-        static_for<p + 1, KS>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            M[j] = __builtin_fma(nf, row_bcast<p>(M[j]), M[j]);
-        });
-        ra = __builtin_fma(nf, row_bcast<p>(ra), ra);
-        rb = __builtin_fma(nf, row_bcast<p>(rb), rb);
-        M[p] = lane > p ? nf : (lane == p ? inv : M[p]);       // the factor: multiplier | 1 / pivot | upper triangle
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    if (lane < KS) {
-#pragma unroll
-        for (int j = 0; j < KS; ++j) F[lane * KS + j] = M[j];
+            for (int j = 0; j < KS; ++j) ((LdsDbl)F_)[lane * KS + j] = M[j];
+        }
     }
     static_for<0, KS>([&](auto Q) {
         constexpr int p = KS - 1 - decltype(Q)::value;
-        const double xa = row_bcast<p>(lane == p ? ra * M[p] : 0.0), xb = row_bcast<p>(lane == p ? rb * M[p] : 0.0);
+        // (lane p's quotient: ra * M[p] once M[p] holds 1 / pivot, the same number as ra * rinv)
+        const double xa = row_bcast<p>(FACTOR ? (lane == p ? ra * M[p] : 0.0) : ra * rinv);
+        const double xb = row_bcast<p>(FACTOR ? (lane == p ? rb * M[p] : 0.0) : rb * rinv);
         ra = lane == p ? xa : (lane < p ? __builtin_fma(-M[p], xa, ra) : ra);
         rb = lane == p ? xb : (lane < p ? __builtin_fma(-M[p], xb, rb) : rb);
     });
@@ -192,7 +160,6 @@ __device__ __noinline__ Pair spd_factor2_dpp(const double *Hm_, int HP, int k, d
 }
 template <int KS>
 __device__ __noinline__ double spd_resolve_dpp(const double *F_, int k, double r) {
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
     const int lane = lane_id();
     LdsCDbl F = (LdsCDbl)F_;
     k = uni(k);
@@ -221,12 +188,12 @@ __device__ __forceinline__ int spd_factor_size(int k, int cap) {
 }
 __device__ __forceinline__ Pair spd_factor2_k(int ks, const double *Hm, int HP, int k, double diag, double ra, double rb, double *F) {
     switch (ks) {
-    case 4: return spd_factor2_dpp<4>(Hm, HP, k, diag, ra, rb, F);
-    case 6: return spd_factor2_dpp<6>(Hm, HP, k, diag, ra, rb, F);
-    case 8: return spd_factor2_dpp<8>(Hm, HP, k, diag, ra, rb, F);
-    case 10: return spd_factor2_dpp<10>(Hm, HP, k, diag, ra, rb, F);
-    case 12: return spd_factor2_dpp<12>(Hm, HP, k, diag, ra, rb, F);
-    default: return spd_factor2_dpp<16>(Hm, HP, k, diag, ra, rb, F);
+    case 4: return spd_eliminate2_dpp<4, true>(Hm, HP, k, diag, ra, rb, F);
+    case 6: return spd_eliminate2_dpp<6, true>(Hm, HP, k, diag, ra, rb, F);
+    case 8: return spd_eliminate2_dpp<8, true>(Hm, HP, k, diag, ra, rb, F);
+    case 10: return spd_eliminate2_dpp<10, true>(Hm, HP, k, diag, ra, rb, F);
+    case 12: return spd_eliminate2_dpp<12, true>(Hm, HP, k, diag, ra, rb, F);
+    default: return spd_eliminate2_dpp<16, true>(Hm, HP, k, diag, ra, rb, F);
     }
 }
 __device__ __forceinline__ double spd_resolve_k(int ks, const double *F, int k, double r) {
@@ -242,12 +209,12 @@ __device__ __forceinline__ double spd_resolve_k(int ks, const double *F, int k, 
 
 template <int KT>
 __device__ __forceinline__ Pair spd_solve2_k(const double *Hm, int HP, int k, double diag, double ra, double rb) {
-    if (k <= 4) return spd_solve2_dpp<4>(Hm, HP, k, diag, ra, rb);
-    if (k <= 6) return spd_solve2_dpp<6>(Hm, HP, k, diag, ra, rb);
-    if (k <= 8) return spd_solve2_dpp<8>(Hm, HP, k, diag, ra, rb);
-    if (k <= 10) return spd_solve2_dpp<10>(Hm, HP, k, diag, ra, rb);
-    if (k <= 12) return spd_solve2_dpp<12>(Hm, HP, k, diag, ra, rb);
-    if (KT == 16 || k <= 16) return spd_solve2_dpp<16>(Hm, HP, k, diag, ra, rb);
+    // (no instance of 4: reached only where spd_factor_size(k, n_pad) == 0, and 4 * 4 <= n_pad, a multiple of 16, always fits)
+    if (k <= 6) return spd_eliminate2_dpp<6, false>(Hm, HP, k, diag, ra, rb, nullptr);
+    if (k <= 8) return spd_eliminate2_dpp<8, false>(Hm, HP, k, diag, ra, rb, nullptr);
+    if (k <= 10) return spd_eliminate2_dpp<10, false>(Hm, HP, k, diag, ra, rb, nullptr);
+    if (k <= 12) return spd_eliminate2_dpp<12, false>(Hm, HP, k, diag, ra, rb, nullptr);
+    if (KT == 16 || k <= 16) return spd_eliminate2_dpp<16, false>(Hm, HP, k, diag, ra, rb, nullptr);
     return spd_solve2<KT>(Hm, HP, k, diag, ra, rb);
 }
 
@@ -283,38 +250,16 @@ constexpr int IPM_KMAX = 12;       // one wave per sample (the persistent kernel
 __host__ __device__ constexpr int ipm_nv(int K) { return K * (K + 1) / 2 + 2 * K + 1; }
 __host__ __device__ constexpr int ipm_chunk(int K) { return hv_chunk_len(ipm_nv(K), 24); }
 
-template <typename CutT, int K, int E0, int EN, int NV, typename PP>
-__device__ __forceinline__ void ipm_chunks(const CutT (&av)[K][3], const double (&w)[3], const double (&zz)[3], const double (&yy)[3],
-                                           const double (&ry)[3], int lane, PP Pw) {
-    if constexpr (E0 < NV) {
-        constexpr int N = E0 + EN <= NV ? EN : NV - E0, T = K * (K + 1) / 2;
-        double v[N];
-#pragma unroll
-        for (int e = 0; e < N; ++e) v[e] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double ad[K];
-#pragma unroll
-            for (int i = 0; i < K; ++i) ad[i] = (double)av[i][c];
-#pragma unroll
-            for (int e = 0; e < N; ++e) {
-                const int ge = E0 + e;                                // (compile-time after unrolling)
-                if (ge < T) v[e] = __builtin_fma(ad[hv_wrow(ge)], ad[hv_wcol(ge)] * w[c], v[e]);      // as hv_chunks
-                else if (ge < T + K) v[e] = __builtin_fma(ad[ge - T < K ? ge - T : 0], zz[c], v[e]);
-                else if (ge < T + 2 * K) v[e] = __builtin_fma(ad[ge - T - K >= 0 && ge - T - K < K ? ge - T - K : 0], yy[c], v[e]);
-                else v[e] = __builtin_fma(ry[c], ry[c], v[e]);
-            }
-        }
-        hv_transpose_reduce<N>(v, lane);
-        const int idx = hv_index(N, lane);
-        if (idx >= 0) Pw[E0 + idx] = v[0];
-        ipm_chunks<CutT, K, E0 + EN, EN, NV>(av, w, zz, yy, ry, lane, Pw);
-    }
-}
-
-// the lane's three columns of the staged bundle (rows >= k of a padded instance: zero by a select on an in-bounds read)
+// ---- one chunk = the lane's three columns c0 + lane + 64 c: the bodies that the narrow passes (c0 = 0, one chunk) and the
+// wide passes (below: a loop over the chunks) share ---------------------------------------------------------------------------
+// the chunk's bundle columns (rows >= k of a padded instance: zero by a select on an in-bounds read), its y and, where bv is
+// given, its entries of a second column vector; jc: the column indices clamped into the row (what a clamped column computes
+// is not stored and does not count)
 template <typename CutT, int K, typename AP>
-__device__ __forceinline__ void ipm_load_columns(AP As, int ldA, int k, const int (&jc)[3], CutT (&av)[K][3]) {
+__device__ __forceinline__ void ipm_load_chunk(AP As, int ldA, int k, int n_pad, int c0, int lane, LdsCDbl yv, int (&jc)[3],
+                                               CutT (&av)[K][3], double (&y)[3], LdsCDbl bv, double (&b0)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) jc[c] = c0 + lane + 64 * c < n_pad ? c0 + lane + 64 * c : n_pad - 1;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -322,46 +267,127 @@ __device__ __forceinline__ void ipm_load_columns(AP As, int ldA, int k, const in
             const CutT v = As[(i < k ? i : 0) * ldA + jc[c]];
             av[i][c] = i < k ? v : (CutT)0;
         }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { y[c] = yv[jc[c]]; b0[c] = bv[jc[c]]; }
+}
+template <typename CutT, int K, typename AP>
+__device__ __forceinline__ void ipm_load_chunk(AP As, int ldA, int k, int n_pad, int c0, int lane, LdsCDbl yv, int (&jc)[3],
+                                               CutT (&av)[K][3], double (&y)[3]) {
+    double none[3];
+    ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, c0, lane, yv, jc, av, y, yv, none);          // (the second read of y: dropped)
 }
 
-template <typename CutT, int K>
-__device__ __noinline__ void ipm_pass1_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_, double *rys_,
-                                          double *Pw_, double z) {
-    typedef const __attribute__((address_space(3))) CutT *LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    LdsCut As = (LdsCut)As_;
-    LdsCDbl yv = (LdsCDbl)yv_;
-    LdsDbl rys = (LdsDbl)rys_, Pw = (LdsDbl)Pw_;
-    ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad);
-    const int lane = lane_id();
-    int jc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) jc[c] = lane + 64 * c < n_pad ? lane + 64 * c : n_pad - 1;
-    CutT av[K][3];
-    ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
-    double y[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) y[c] = yv[jc[c]];
-    double zi[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) zi[i] = bcast(z, i);                  // (z is 0 in the lanes beyond the bundle)
-    double w[3], zz[3], yy[3], ry[3];
+// pass 1, residual: ry = grad + G^T z (:17, :26) -> rys and ry[]; Hinv, Hinv ry and y, zero beyond n, -> w[], zz[], yy[] and,
+// STORE_WZ, Hinv and Hinv ry -> ws, zs.  zi: the multipliers, broadcast (0 beyond the bundle)
+template <bool STORE_WZ, typename CutT, int K>
+__device__ __forceinline__ void ipm_residual_chunk(const CutT (&av)[K][3], const double (&y)[3], const double (&zi)[K], int n, int n_pad,
+                                                   int c0, int lane, LdsDbl rys, LdsDbl ws, LdsDbl zs, double (&w)[3], double (&zz)[3],
+                                                   double (&yy)[3], double (&ry)[3]) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const int j = lane + 64 * c;
+        const int j = c0 + lane + 64 * c;
         const double grad = fast_log(y[c] * rcp_nr(1.0 - y[c]));           // :17  log y - log(1 - y)
         const double hinv = y[c] * (1.0 - y[c]);                      // :19  1 / (1/y + 1/(1-y))
         double gz = 0.0;
 #pragma unroll
         for (int i = 0; i < K; ++i) gz += zi[i] * (double)av[i][c];   // (G^T z)_j, cuts in order (absent rows: + 0 * 0)
         const double r = j < n ? grad + gz : 0.0;
-        if (j < n_pad) rys[j] = r;
         ry[c] = r;
         w[c] = j < n ? hinv : 0.0;
         zz[c] = j < n ? hinv * r : 0.0;
         yy[c] = j < n ? y[c] : 0.0;
+        if (j < n_pad) {
+            rys[j] = r;
+            if constexpr (STORE_WZ) { ws[j] = w[c]; zs[j] = zz[c]; }
+        }
     }
+}
+
+// pass 1, sums: the chunk's terms of the N values from entry E0 on -- M = G Hinv G^T (triangle, as hv_chunks), G Hinv ry,
+// G y, |ry|^2 -- added to v[] in column order
+template <int E0, typename CutT, int K, int N>
+__device__ __forceinline__ void ipm_sum_chunk(const CutT (&av)[K][3], const double (&w)[3], const double (&zz)[3], const double (&yy)[3],
+                                              const double (&ry)[3], double (&v)[N]) {
+    constexpr int T = K * (K + 1) / 2;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double ad[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) ad[i] = (double)av[i][c];
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            const int ge = E0 + e;                                // (compile-time after unrolling)
+            if (ge < T) v[e] = __builtin_fma(ad[hv_wrow(ge)], ad[hv_wcol(ge)] * w[c], v[e]);      // as hv_chunks
+            else if (ge < T + K) v[e] = __builtin_fma(ad[ge - T < K ? ge - T : 0], zz[c], v[e]);
+            else if (ge < T + 2 * K) v[e] = __builtin_fma(ad[ge - T - K >= 0 && ge - T - K < K ? ge - T - K : 0], yy[c], v[e]);
+            else v[e] = __builtin_fma(ry[c], ry[c], v[e]);
+        }
+    }
+}
+
+// passes 2 and 3: FIRST, the affine dy = -Hinv (b0 + G^T dz) with b0 = ry (:50); else dy = b0 - Hinv G^T dz_c with b0 = the
+// affine dy (:66).  dy -> dyv; `st` goes on with the lane's smallest step ratio over y and 1 - y (NO_STEP: none) and whether
+// it saw a negative (1) / a positive (2) direction.  di: the multipliers' direction, broadcast
+struct IpmStep { double m; int neg; };
+template <bool FIRST, typename CutT, int K>
+__device__ __forceinline__ IpmStep ipm_dy_chunk(const CutT (&av)[K][3], const double (&y)[3], const double (&b0)[3], const double (&di)[K],
+                                                int n, int n_pad, int c0, int lane, LdsDbl dyv, IpmStep st) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int j = c0 + lane + 64 * c;
+        const double hinv = j < n ? y[c] * (1.0 - y[c]) : 0.0;
+        double gd = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) gd += di[i] * (double)av[i][c];
+        const double dy = FIRST ? -hinv * (b0[c] + gd) : b0[c] - hinv * gd;
+        if (j < n_pad) dyv[j] = dy;
+        if (j < n) {
+            st.m = fmin(st.m, ratio_step_box(y[c], dy));
+            st.neg |= (dy < 0.0 ? 1 : 0) | (dy > 0.0 ? 2 : 0);
+        }
+    }
+    return st;
+}
+
+// the N sums of a run: ONE transposing butterfly, lane hv_index(N, lane) stores
+template <int N>
+__device__ __forceinline__ void ipm_reduce_store(double (&v)[N], int lane, LdsDbl Pw) {
+    hv_transpose_reduce<N>(v, lane);
+    const int idx = hv_index(N, lane);
+    if (idx >= 0) Pw[idx] = v[0];
+}
+
+template <typename CutT, int K, int E0, int EN, int NV>
+__device__ __forceinline__ void ipm_chunks(const CutT (&av)[K][3], const double (&w)[3], const double (&zz)[3], const double (&yy)[3],
+                                           const double (&ry)[3], int lane, LdsDbl Pw) {
+    if constexpr (E0 < NV) {
+        constexpr int N = E0 + EN <= NV ? EN : NV - E0;
+        double v[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) v[e] = 0.0;
+        ipm_sum_chunk<E0>(av, w, zz, yy, ry, v);
+        ipm_reduce_store<N>(v, lane, Pw + E0);
+        ipm_chunks<CutT, K, E0 + EN, EN, NV>(av, w, zz, yy, ry, lane, Pw);
+    }
+}
+
+template <typename CutT, int K>
+__device__ __noinline__ void ipm_pass1_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_, double *rys_,
+                                          double *Pw_, double z) {
+    IpmCutPtr<CutT> As = (IpmCutPtr<CutT>)As_;
+    LdsCDbl yv = (LdsCDbl)yv_;
+    LdsDbl rys = (LdsDbl)rys_, Pw = (LdsDbl)Pw_;
+    ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad);
+    const int lane = lane_id();
+    int jc[3];
+    CutT av[K][3];
+    double y[3];
+    ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, 0, lane, yv, jc, av, y);
+    double zi[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) zi[i] = bcast(z, i);                  // (z is 0 in the lanes beyond the bundle)
+    double w[3], zz[3], yy[3], ry[3];
+    ipm_residual_chunk<false>(av, y, zi, n, n_pad, 0, lane, rys, LdsDbl(), LdsDbl(), w, zz, yy, ry);
     ipm_chunks<CutT, K, 0, ipm_chunk(K), ipm_nv(K)>(av, w, zz, yy, ry, lane, Pw);
 }
 
@@ -369,81 +395,38 @@ __device__ __noinline__ void ipm_pass1_fn(const CutT *As_, int ldA, int k, int n
 template <typename CutT, int K>
 __device__ __noinline__ double ipm_pass2_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_,
                                             const double *rys_, double *dyv_, double dz) {
-    typedef const __attribute__((address_space(3))) CutT *LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    LdsCut As = (LdsCut)As_;
+    IpmCutPtr<CutT> As = (IpmCutPtr<CutT>)As_;
     LdsCDbl yv = (LdsCDbl)yv_, rys = (LdsCDbl)rys_;
     LdsDbl dyv = (LdsDbl)dyv_;
     ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad);
     const int lane = lane_id();
     int jc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) jc[c] = lane + 64 * c < n_pad ? lane + 64 * c : n_pad - 1;
     CutT av[K][3];
-    ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
     double y[3], ry[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { y[c] = yv[jc[c]]; ry[c] = rys[jc[c]]; }
+    ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, 0, lane, yv, jc, av, y, rys, ry);
     double di[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) di[i] = bcast(dz, i);
-    double m = NO_STEP;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int j = lane + 64 * c;
-        const double hinv = j < n ? y[c] * (1.0 - y[c]) : 0.0;
-        double gd = 0.0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) gd += di[i] * (double)av[i][c];
-        const double dy = -hinv * (ry[c] + gd);
-        if (j < n_pad) dyv[j] = dy;
-        if (j < n) m = fmin(m, ratio_step_box(y[c], dy));
-    }
-    return m;
+    return ipm_dy_chunk<true>(av, y, ry, di, n, n_pad, 0, lane, dyv, IpmStep{NO_STEP, 0}).m;     // (the flags: dropped)
 }
 
 // dy -= Hinv G^T dz_c (:66) -> dyv; the lane's smallest ratio and whether it saw a negative / a positive direction
-struct IpmStep { double m; int neg; };
 template <typename CutT, int K>
 __device__ __noinline__ IpmStep ipm_pass3_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_, double *dyv_,
                                              double dz) {
-    typedef const __attribute__((address_space(3))) CutT *LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    LdsCut As = (LdsCut)As_;
+    IpmCutPtr<CutT> As = (IpmCutPtr<CutT>)As_;
     LdsCDbl yv = (LdsCDbl)yv_;
     LdsDbl dyv = (LdsDbl)dyv_;
     ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad);
     const int lane = lane_id();
     int jc[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) jc[c] = lane + 64 * c < n_pad ? lane + 64 * c : n_pad - 1;
     CutT av[K][3];
-    ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
     double y[3], d0[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { y[c] = yv[jc[c]]; d0[c] = dyv[jc[c]]; }
+    ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, 0, lane, yv, jc, av, y, (LdsCDbl)dyv, d0);
     double di[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) di[i] = bcast(dz, i);
-    double m = NO_STEP;
-    int neg = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int j = lane + 64 * c;
-        const double hinv = j < n ? y[c] * (1.0 - y[c]) : 0.0;
-        double gd = 0.0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) gd += di[i] * (double)av[i][c];
-        const double dy = d0[c] - hinv * gd;
-        if (j < n_pad) dyv[j] = dy;
-        if (j < n) {
-            m = fmin(m, ratio_step_box(y[c], dy));
-            neg |= (dy < 0.0 ? 1 : 0) | (dy > 0.0 ? 2 : 0);
-        }
-    }
-    return IpmStep{m, neg};
+    return ipm_dy_chunk<false>(av, y, d0, di, n, n_pad, 0, lane, dyv, IpmStep{NO_STEP, 0});
 }
 
 // ---- the same passes for WIDE rows (n_pad > 192: the completion model's 2048 pixels on one wave): column chunks of 192 ------
@@ -455,10 +438,7 @@ __device__ __noinline__ IpmStep ipm_pass3_fn(const CutT *As_, int ldA, int k, in
 template <typename CutT, int K, bool GSRC = false>
 __device__ __noinline__ void ipm_wide1a_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_, double *rys_,
                                            double *ws_, double *zs_, double z, int c_first, int c_step) {
-    typedef std::conditional_t<GSRC, const __attribute__((address_space(1))) CutT *, const __attribute__((address_space(3))) CutT *> LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    LdsCut As = (LdsCut)As_;
+    IpmCutPtr<CutT, GSRC> As = (IpmCutPtr<CutT, GSRC>)As_;
     LdsCDbl yv = (LdsCDbl)yv_;
     LdsDbl rys = (LdsDbl)rys_, ws = (LdsDbl)ws_, zs = (LdsDbl)zs_;
     ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad); c_first = uni(c_first); c_step = uni(c_step);
@@ -468,83 +448,44 @@ __device__ __noinline__ void ipm_wide1a_fn(const CutT *As_, int ldA, int k, int 
     for (int i = 0; i < K; ++i) zi[i] = bcast(z, i);
     for (int c0 = c_first; c0 < n_pad; c0 += c_step) {
         int jc[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) jc[c] = c0 + lane + 64 * c < n_pad ? c0 + lane + 64 * c : n_pad - 1;
         CutT av[K][3];
-        ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
-        double y[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) y[c] = yv[jc[c]];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int j = c0 + lane + 64 * c;
-            const double grad = fast_log(y[c] * rcp_nr(1.0 - y[c]));
-            const double hinv = y[c] * (1.0 - y[c]);
-            double gz = 0.0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) gz += zi[i] * (double)av[i][c];
-            const double r = j < n ? grad + gz : 0.0;
-            if (j < n_pad) {
-                rys[j] = r;
-                ws[j] = j < n ? hinv : 0.0;
-                zs[j] = j < n ? hinv * r : 0.0;
-            }
-        }
+        double y[3], w[3], zz[3], yy[3], ry[3];
+        ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, c0, lane, yv, jc, av, y);
+        ipm_residual_chunk<true>(av, y, zi, n, n_pad, c0, lane, rys, ws, zs, w, zz, yy, ry);
     }
 }
 
-template <typename CutT, int K, int E0, int EN, int NV, typename AP, typename CP, typename PP>
-__device__ __forceinline__ void ipm_wide_sums(AP As, int ldA, int k, int n, int n_pad, CP ws, CP zs, CP yv, CP rys, int lane, PP Pw,
-                                              int c_first, int c_step) {
+template <typename CutT, int K, int E0, int EN, int NV, typename AP>
+__device__ __forceinline__ void ipm_wide_sums(AP As, int ldA, int k, int n, int n_pad, LdsCDbl ws, LdsCDbl zs, LdsCDbl yv, LdsCDbl rys,
+                                              int lane, LdsDbl Pw, int c_first, int c_step) {
     if constexpr (E0 < NV) {
-        constexpr int N = E0 + EN <= NV ? EN : NV - E0, T = K * (K + 1) / 2;
+        constexpr int N = E0 + EN <= NV ? EN : NV - E0;
         double v[N];
 #pragma unroll
         for (int e = 0; e < N; ++e) v[e] = 0.0;
         for (int c0 = c_first; c0 < n_pad; c0 += c_step) {
             int jc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) jc[c] = c0 + lane + 64 * c < n_pad ? c0 + lane + 64 * c : n_pad - 1;
             CutT av[K][3];
-            ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
-            double w[3], zz[3], yy[3], ry[3];
+            double yr[3], w[3], zz[3], yy[3], ry[3];
+            ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, c0, lane, yv, jc, av, yr);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const bool in = c0 + lane + 64 * c < n;          // (beyond n: the stored values are zeros, y is not)
                 w[c] = ws[jc[c]]; zz[c] = zs[jc[c]]; ry[c] = rys[jc[c]];
-                const double yr = yv[jc[c]];
                 if (!(c0 + lane + 64 * c < n_pad)) { w[c] = 0.0; zz[c] = 0.0; ry[c] = 0.0; }     // clamped re-reads
-                yy[c] = in ? yr : 0.0;
+                yy[c] = in ? yr[c] : 0.0;
             }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double ad[K];
-#pragma unroll
-                for (int i = 0; i < K; ++i) ad[i] = (double)av[i][c];
-#pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    const int ge = E0 + e;
-                    if (ge < T) v[e] = __builtin_fma(ad[hv_wrow(ge)], ad[hv_wcol(ge)] * w[c], v[e]);
-                    else if (ge < T + K) v[e] = __builtin_fma(ad[ge - T < K ? ge - T : 0], zz[c], v[e]);
-                    else if (ge < T + 2 * K) v[e] = __builtin_fma(ad[ge - T - K >= 0 && ge - T - K < K ? ge - T - K : 0], yy[c], v[e]);
-                    else v[e] = __builtin_fma(ry[c], ry[c], v[e]);
-                }
-            }
+            ipm_sum_chunk<E0>(av, w, zz, yy, ry, v);
         }
-        hv_transpose_reduce<N>(v, lane);
-        const int idx = hv_index(N, lane);
-        if (idx >= 0) Pw[E0 + idx] = v[0];
+        ipm_reduce_store<N>(v, lane, Pw + E0);
         ipm_wide_sums<CutT, K, E0 + EN, EN, NV>(As, ldA, k, n, n_pad, ws, zs, yv, rys, lane, Pw, c_first, c_step);
     }
 }
 template <typename CutT, int K, bool GSRC = false>
 __device__ __noinline__ void ipm_wide1b_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *ws_, const double *zs_,
                                            const double *yv_, const double *rys_, double *Pw_, int c_first, int c_step) {
-    typedef std::conditional_t<GSRC, const __attribute__((address_space(1))) CutT *, const __attribute__((address_space(3))) CutT *> LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
     ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad); c_first = uni(c_first); c_step = uni(c_step);
-    ipm_wide_sums<CutT, K, 0, ipm_chunk(K), ipm_nv(K)>((LdsCut)As_, ldA, k, n, n_pad, (LdsCDbl)ws_, (LdsCDbl)zs_, (LdsCDbl)yv_,
+    ipm_wide_sums<CutT, K, 0, ipm_chunk(K), ipm_nv(K)>((IpmCutPtr<CutT, GSRC>)As_, ldA, k, n, n_pad, (LdsCDbl)ws_, (LdsCDbl)zs_, (LdsCDbl)yv_,
                                                        (LdsCDbl)rys_, lane_id(), (LdsDbl)Pw_, c_first, c_step);
 }
 
@@ -552,10 +493,7 @@ __device__ __noinline__ void ipm_wide1b_fn(const CutT *As_, int ldA, int k, int 
 template <typename CutT, int K, bool FIRST, bool GSRC = false>
 __device__ __noinline__ IpmStep ipm_wide23_fn(const CutT *As_, int ldA, int k, int n, int n_pad, const double *yv_,
                                               const double *rys_, double *dyv_, double dz, int c_first, int c_step) {
-    typedef std::conditional_t<GSRC, const __attribute__((address_space(1))) CutT *, const __attribute__((address_space(3))) CutT *> LdsCut;
-    typedef const __attribute__((address_space(3))) double *LdsCDbl;
-    typedef __attribute__((address_space(3))) double *LdsDbl;
-    LdsCut As = (LdsCut)As_;
+    IpmCutPtr<CutT, GSRC> As = (IpmCutPtr<CutT, GSRC>)As_;
     LdsCDbl yv = (LdsCDbl)yv_, rys = (LdsCDbl)rys_;
     LdsDbl dyv = (LdsDbl)dyv_;
     ldA = uni(ldA); k = uni(k); n = uni(n); n_pad = uni(n_pad);
@@ -563,34 +501,16 @@ __device__ __noinline__ IpmStep ipm_wide23_fn(const CutT *As_, int ldA, int k, i
     double di[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) di[i] = bcast(dz, i);
-    double m = NO_STEP;
-    int neg = 0;
+    IpmStep st{NO_STEP, 0};
     c_first = uni(c_first); c_step = uni(c_step);
     for (int c0 = c_first; c0 < n_pad; c0 += c_step) {
         int jc[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) jc[c] = c0 + lane + 64 * c < n_pad ? c0 + lane + 64 * c : n_pad - 1;
         CutT av[K][3];
-        ipm_load_columns<CutT, K>(As, ldA, k, jc, av);
         double y[3], b0[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { y[c] = yv[jc[c]]; b0[c] = FIRST ? rys[jc[c]] : dyv[jc[c]]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int j = c0 + lane + 64 * c;
-            const double hinv = j < n ? y[c] * (1.0 - y[c]) : 0.0;
-            double gd = 0.0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) gd += di[i] * (double)av[i][c];
-            const double dy = FIRST ? -hinv * (b0[c] + gd) : b0[c] - hinv * gd;
-            if (j < n_pad) dyv[j] = dy;
-            if (j < n) {
-                m = fmin(m, ratio_step_box(y[c], dy));
-                neg |= (dy < 0.0 ? 1 : 0) | (dy > 0.0 ? 2 : 0);
-            }
-        }
+        ipm_load_chunk<CutT, K>(As, ldA, k, n_pad, c0, lane, yv, jc, av, y, FIRST ? rys : (LdsCDbl)dyv, b0);
+        st = ipm_dy_chunk<FIRST>(av, y, b0, di, n, n_pad, c0, lane, dyv, st);
     }
-    return IpmStep{m, neg};
+    return st;
 }
 
 #define IPM_K_SWITCH(kk, CALL)                                                                                     \

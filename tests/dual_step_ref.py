@@ -365,7 +365,8 @@ def ipm_nv(K):
 
 def sums_path(plan, n, k, flags, rows):
     """(routine, instance size) that sample of k cuts runs on the launch `plan` with `rows` staged rows: be_dual_dev.h `valu`
-    (dual_step_body), be_ipm_dev.h ipm_solve (:636-640, :721), be_dual_dev.h `waves_ok` (dual_step_body).  'mfma' is the general sweep."""
+    (dual_step_body), be_ipm_dev.h ipm_solve (its conditions `hv_ok`, `fast`, the wide-one dispatch in front of the loop and the
+    weighted-pass branch of the sums), be_dual_dev.h `waves_ok` (dual_step_body).  'mfma' is the general sweep."""
     cut, kt, nw, variant, staged, kernel = plan
     n_pad = (n + 15) & ~15
     f32 = cut == "float"
@@ -432,6 +433,9 @@ CASES = [
     # need ipm_nv(12) = 103 <= n_pad <= 192, ipm_solve_wide_one_fn at 20 cuts ipm_nv(20) = 251 <= n_pad
     ("f32_32_pdipm_n177", _plan("float", 32, 1, "pdipm"), F32, 31, 177, "pdipm", 0, 30, (1, 2, 8, 9, 12, 13, 15)),
     ("f32_32_pdipm_n255", _plan("float", 32, 1, "pdipm"), F32, 31, 255, "pdipm", 0, 30, (2, 18, 19, 20, 21, 31)),
+    # n_pad = 32: no room for the factor of spd_factor_size's 6, 10 and 16 (36, 100, 256 > 32), so these bundles solve twice with
+    # the non-factor form of the elimination at KS = 6, 10, 16 (the rows above reach it at 8, 12, 16 only)
+    ("f32_16_pdipm_n17", _plan("float", 16, 1, "pdipm"), F32, 15, 17, "pdipm", 0, 14, (5, 6, 9, 10, 13)),
     # float64 cuts
     ("f64_16_dual_n40", _plan("double", 16, 1, "dual"), F64, 15, 40, "dual", 0, 14, K15 + (FIN, DUP, ZERO)),
     ("f64_32_dual_n40", _plan("double", 32, 1, "dual"), F64, 31, 40, "dual", 0, 30, K31 + (FIN, DUP, ZERO)),
@@ -570,6 +574,10 @@ RESEED = {
     ('f32_32_pdipm_n255', 2): 7,
     ('f32_32_pdipm_n255', 4): 2,
     ('f32_32_pdipm_n255', 5): 1,
+    ('f32_16_pdipm_n17', 0): 9,
+    ('f32_16_pdipm_n17', 1): 9,
+    ('f32_16_pdipm_n17', 2): 10,
+    ('f32_16_pdipm_n17', 4): 1,
     ('f32_32_pdipm8_glb_n2048', 2): 1,
     ('f32_32_pdipm8_glb_n2048', 4): 1,
     ('f32_32_pdipm8_glb_n2048', 5): 2,

@@ -152,8 +152,8 @@ FAMILIES = {
 ROUTINE_INSTANCES = {
     ("valu", 1): {2, 4, 5, 6, 7, 8},                                  # hv_column_pass_k, one wave: up to HV_K1MAX = 8
     ("valu", 8): {2, 4, 5, 6, 7, 8, 10, 12, 14, 16, 18, 20},          # eight waves: up to HV_KMAX = 20, needs 8 hv_pitch(k) <= n_pad
-    ("ipm_unrolled", 1): {2, 7, 10, 12},                              # IPM_K_SWITCH: up to IPM_KMAX = 12, needs ipm_nv(K) <= n_pad <= 192
-    ("ipm_weighted", 1): {8},                                         # hv_weighted_pass where the unrolled pass does not fit the row
+    ("ipm_unrolled", 1): {2, 5, 7, 10, 12},                           # IPM_K_SWITCH: up to IPM_KMAX = 12, needs ipm_nv(K) <= n_pad <= 192
+    ("ipm_weighted", 1): {6, 8},                                      # hv_weighted_pass where the unrolled pass does not fit the row
     ("ipm_wide_one", 1): {2, 12, 14, 18, 20},                         # IPM_K_SWITCH_WAVES on one wave, n_pad > 192
     ("ipm_waves", 8): {2, 12, 14, 20},                                # ... on eight: needs 8 (ipm_nv(K) + 3 & ~3) <= n_pad
 }
